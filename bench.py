@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X KKT path: KKT factor+solve per second (fp64).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c2]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c2] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one KKT system whose data are already
 resident in HBM: Hqp_IpMatrix::factor followed by Hqp_IpMatrix::solve (one solve +
@@ -18,6 +18,11 @@ the full-system engine (round 1's headline; its rate is also carried as an extra
 line).  N>1: one process per GPU, every rank factors+solves its own system (different seed):
 independent KKT systems shard with no data-path collective ("weak"); --one-system: ONE system
 over the ranks ("strong").
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds, after the timed
+steps, what else the line carries: the rate with host vectors, per-kernel-class times and the roofline,
+the replicas pass (N>1), the interior-point runs, the CPU baseline of the reference and the other
+sizes and configurations.  --dump-outputs DIR writes what the last timed step returned as .npy files.
 
 Prints ONE JSON line on rank 0.
 """
@@ -75,6 +80,25 @@ def kernel_source_sha16():
         with open(os.path.join(ROOT, "hqp_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, d, res):
+    """--dump-outputs: what a caller of the timed path receives from its last step - the four blocks of the
+    solution (dx, dy, dz, dw) and the residual - as float64 .npy files.  Above DUMP_LIMIT_BYTES in all, every
+    block is cut to the same fraction of its entries, chosen by a fixed seed (sorted indices)."""
+    os.makedirs(directory, exist_ok=True)
+    arrs = [(v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float64, copy=False) for v in d]
+    budget = DUMP_LIMIT_BYTES // 8 - 1024  # entries, with room for the .npy headers
+    total = sum(a.size for a in arrs)
+    for name, a in zip(("dx", "dy", "dz", "dw"), arrs):
+        if total > budget:
+            k = a.size * budget // total
+            a = a[np.sort(np.random.default_rng(1234).choice(a.size, size=k, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+    np.save(os.path.join(directory, "residual.npy"), np.array([res], dtype=np.float64))
 
 
 def class_work(struct, rank=None):
@@ -580,7 +604,8 @@ def bench_c4(args):
     t0 = time.perf_counter()
     mat.init_dense(dq)
     t_init = time.perf_counter() - t0
-    dq.norm_A = max(float(blk.abs().sum(1).max()) + 1.0 for blk in dq.F)  # for the interior-point run below
+    if args.full:
+        dq.norm_A = max(float(blk.abs().sum(1).max()) + 1.0 for blk in dq.F)  # for the interior-point run below
     dq.F = None  # the engine holds its own copy of the blocks
     torch.cuda.empty_cache()
     g = torch.Generator(device="cuda").manual_seed(100 + (0 if one else rank))
@@ -604,12 +629,49 @@ def bench_c4(args):
     kdist.fence()
     elapsed = kdist.max_over_ranks(time.perf_counter() - t0)
     dog.disarm()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d, res)
     st = mat.stats()
     all_devices = None
     if one:  # which GPU every rank computed on (the bench line shows that N ranks meant N GPUs)
         import torch.distributed as tdist
         all_devices = [None] * world
         tdist.all_gather_object(all_devices, f"{os.uname().nodename}:cuda:{torch.cuda.current_device()}")
+    out = {
+        "metric": "KKT factor+solve/sec (fp64)",
+        "value": args.steps * (1 if one else world) / elapsed,
+        "unit": "KKT factor+solve/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if one else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "vectors": "resident in HBM",
+        "shard": {"ranks": world, "transport": transport, "comm_ranks": comm_ranks,
+                  "devices": sorted(set(all_devices)) if all_devices else None,
+                  "bytes_allgather_per_factor": st["bytes_exchange_factor"], "bytes_panels_this_rank": st["bytes_panels"],
+                  "flops_rank0": st["flops_local"], "allgathers_per_factor": st["n_exchange_blocks"],
+                  "per_rank": None} if one else None,
+        "config": {"workload": f"C4 = BASELINE configs[3], the metric's 10^6-variable DOCP: multistage LQ optimal control QP, K={K} stages, "
+                               f"nx={nx} states, nu={nu} controls -> n={n} me={me} m={m}, dense fx/fu handed over as blocks, x_0 fixed, "
+                               f"box bounds on u; plugin LQDOCP (STAGED engine), "
+                               + (f"ONE system over {world} GPUs (memory sharded: every rank holds its column strip of every F_k and its row strip of every V_k; "
+                                  f"per stage the gather of the F blocks, requested a stage ahead, and ONE gather of the blocks of G_xx)"
+                                  if one else "one system per GPU"),
+                   "stages": K, "nx": nx, "nu": nu, "n": n, "me": me, "m": m, "plugin": "LQDOCP",
+                   "kkt_dim_full": n + me + m, "hbm_gb": (st["bytes_panels"] + st["bytes_updates"]) / 1e9},
+        "residual": res,
+        "refine_rounds": st["refine_rounds"],
+        "init_s": t_init,
+        "ms_factor": st["ms_factor"], "ms_solve": st["ms_solve"],
+    }
+    if not args.full:
+        return out if rank == 0 else None
+    # --full: everything below is extra information, measured in passes of its own after the timed steps
     # the same step as a host with its vectors in (pinned) host memory sees it - SURVEY.md 8(d): z, w, r1..r4 go
     # to the device and dx..dw come back per call; extra information, never `value`
     host_rate = None
@@ -746,40 +808,12 @@ def bench_c4(args):
         "residual": {"ms_per_step": per_step.get("residual"), "launches_per_step": launches.get("residual")},
     }
     fac_ms = sum(per_step.get(k, 0.0) for k in ("staged_gemm", "staged_gemm_upd", "staged_small", "assemble"))
-    out = {
-        "metric": "KKT factor+solve/sec (fp64)",
-        "value": args.steps * (1 if one else world) / elapsed,
-        "unit": "KKT factor+solve/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong" if one else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "vectors": "resident in HBM",
+    if one:
+        out["shard"]["per_rank"] = per_rank
+    out.update({
         "value_with_host_vectors": host_rate,  # PCIe per call (33 MB each way in all): what the shim's host sees
-        "shard": {"ranks": world, "transport": transport, "comm_ranks": comm_ranks,
-                  "devices": sorted(set(all_devices)) if all_devices else None,
-                  "bytes_allgather_per_factor": st["bytes_exchange_factor"], "bytes_panels_this_rank": st["bytes_panels"],
-                  "flops_rank0": st["flops_local"], "allgathers_per_factor": st["n_exchange_blocks"],
-                  "per_rank": per_rank} if one else None,
         "replicas_value": replicas["value"] if replicas else None,
         "replicas": replicas,
-        "config": {"workload": f"C4 = BASELINE configs[3], the metric's 10^6-variable DOCP: multistage LQ optimal control QP, K={K} stages, "
-                               f"nx={nx} states, nu={nu} controls -> n={n} me={me} m={m}, dense fx/fu handed over as blocks, x_0 fixed, "
-                               f"box bounds on u; plugin LQDOCP (STAGED engine), "
-                               + (f"ONE system over {world} GPUs (memory sharded: every rank holds its column strip of every F_k and its row strip of every V_k; "
-                                  f"per stage the gather of the F blocks, requested a stage ahead, and ONE gather of the blocks of G_xx)"
-                                  if one else "one system per GPU"),
-                   "stages": K, "nx": nx, "nu": nu, "n": n, "me": me, "m": m, "plugin": "LQDOCP",
-                   "kkt_dim_full": n + me + m, "hbm_gb": (st["bytes_panels"] + st["bytes_updates"]) / 1e9},
-        "residual": res,
-        "refine_rounds": st["refine_rounds"],
-        "init_s": t_init,
-        "ms_factor": st["ms_factor"], "ms_solve": st["ms_solve"],
         "kernel_ms_per_step": per_step,
         "kernel_launches_per_step": launches,
         "kernels": kernels,
@@ -788,7 +822,7 @@ def bench_c4(args):
                          "frac_fp64_peak_whole_factor": st["flops_factor"] / (st["ms_factor"] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS
                          if st["ms_factor"] else None},
         "roofline": roofline,
-    }
+    })
     if world == 1 and not args.no_ip:
         # second half of BASELINE.json's metric: interior-point iterations per second on the SAME 10^6-variable DOCP,
         # the whole Mehrotra loop device-resident (hqpkkt_mehrotra: per iteration 1 factorisation, 2 solves, the
@@ -827,7 +861,7 @@ def bench_c4(args):
         a2 = argparse.Namespace(**vars(args))
         # (the GPU has idled through the CPU baseline above - about a minute of host work: enough warm-up steps for its
         # clocks to be back before the 10 timed ones, a step takes 3 ms)
-        a2.steps, a2.warmup = min(args.steps, 10), 50
+        a2.steps, a2.warmup, a2.dump_outputs = min(args.steps, 10), 50, None
         c2 = bench_c2(a2, extras=False)
         out["c2_banded_kkt"] = {k: c2[k] for k in ("value", "unit", "ms_per_step", "residual", "roofline", "init_s")} if c2 else None
         out["ip_iterations"] = ip_iterations(2000)
@@ -875,7 +909,15 @@ def parse_args():
     ap.add_argument("--no-retry", action="store_true", help="N>1: do not start the ranks a second time with --transport torch")
     ap.add_argument("--leaf-size", type=int, default=0)
     ap.add_argument("--max-pivots", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also the secondary measurements: host-vector rate, per-kernel-class times "
+                         "and roofline, replicas pass, interior-point runs, CPU baseline of the reference, other sizes and "
+                         "configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (dx, dy, dz, dw, residual) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but this process was started as one of WORLD_SIZE={os.environ.get('WORLD_SIZE')} ranks")
     return args
@@ -981,9 +1023,43 @@ def bench_c2(args, extras=True):
     fence()
     elapsed = time.perf_counter() - t0
     elapsed = kdist.max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d, res)
     st = mat.stats()
+    if rank == 0:
+        out = {
+            "metric": "KKT factor+solve/sec (fp64)",
+            "value": args.steps * (1 if one else world) / elapsed,
+            "unit": "KKT factor+solve/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong" if one else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "vectors": "host pointers (PCIe per call)" if args.host_vectors else "resident in HBM",
+            "config": {"workload": f"C2 synthetic banded KKT: n={prog.n} me={prog.me} m={prog.m} band={args.band} "
+                                   f"-> KKT dim {st['dim']}, mat_sbw {st['sbw']}, plugin {args.mode} "
+                                   + (f"(ONE system sharded over {world} GPUs)" if one else "(one system per GPU)"),
+                       "kkt_dim": st["dim"], "mat_sbw": st["sbw"], "plugin": args.mode,
+                       "supernodes": st["n_supernodes"], "tree_levels": st["n_levels"], "max_front": st["max_front"],
+                       "nnz_kkt": st["nnz_kkt"], "nnz_factor": st["nnz_factor"]},
+            "residual": res,
+            "refine_rounds": st["refine_rounds"],
+            "n_2x2": st["n_2x2"], "n_perturbed": st["n_perturbed"],
+            "init_s": t_init,
+            "shard": {"ranks": st["shard_count"], "replicated_top_supernodes": st["n_top"],
+                      "exchange_blocks": st["n_exchange_blocks"], "flops_rank0": st["flops_local"],
+                      "flops_top": st["flops_top"], "bytes_exchange_factor": st["bytes_exchange_factor"],
+                      "bytes_exchange_step": st["bytes_exchange_step"]} if one else None,
+        }
+    if not args.full:
+        return out if rank == 0 else None
 
-    # per-kernel-class device time (HIP events on the library's stream around every
+    # --full: per-kernel-class device time (HIP events on the library's stream around every
     # launch), taken in a separate untimed pass over the same workload
     mat.set_profile(True)
     nprof = max(3, min(args.steps, 10))
@@ -1034,40 +1110,13 @@ def bench_c2(args, extras=True):
         model = {"flops_band_model": float(N) * beta * beta, "factor_ms": fac_ms,
                  "tflops_band_model": float(N) * beta * beta / (fac_ms * 1e-3) / 1e12 if fac_ms > 0 else None,
                  "tflops_as_implemented": st["flops_factor"] / (fac_ms * 1e-3) / 1e12 if fac_ms > 0 else None}
-        out = {
-            "metric": "KKT factor+solve/sec (fp64)",
-            "value": args.steps * (1 if one else world) / elapsed,
-            "unit": "KKT factor+solve/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if one else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "vectors": "host pointers (PCIe per call)" if args.host_vectors else "resident in HBM",
-            "config": {"workload": f"C2 synthetic banded KKT: n={prog.n} me={prog.me} m={prog.m} band={args.band} "
-                                   f"-> KKT dim {st['dim']}, mat_sbw {st['sbw']}, plugin {args.mode} "
-                                   + (f"(ONE system sharded over {world} GPUs)" if one else "(one system per GPU)"),
-                       "kkt_dim": st["dim"], "mat_sbw": st["sbw"], "plugin": args.mode,
-                       "supernodes": st["n_supernodes"], "tree_levels": st["n_levels"], "max_front": st["max_front"],
-                       "nnz_kkt": st["nnz_kkt"], "nnz_factor": st["nnz_factor"]},
-            "residual": res,
-            "refine_rounds": st["refine_rounds"],
-            "n_2x2": st["n_2x2"], "n_perturbed": st["n_perturbed"],
-            "init_s": t_init,
-            "shard": {"ranks": st["shard_count"], "replicated_top_supernodes": st["n_top"],
-                      "exchange_blocks": st["n_exchange_blocks"], "flops_rank0": st["flops_local"],
-                      "flops_top": st["flops_top"], "bytes_exchange_factor": st["bytes_exchange_factor"],
-                      "bytes_exchange_step": st["bytes_exchange_step"]} if one else None,
+        out.update({
             "kernel_ms_per_step": per_step,
             "kernel_launches_per_step": launches,
             "kernels": kernels,
             "factor_model": model,
             "roofline": roofline,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and extras:
             out["cpu_baseline"] = cpu_baseline(prog, state)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]

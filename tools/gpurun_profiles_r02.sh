@@ -15,12 +15,12 @@ cp $O/pmc_traffic.json profiles/r02_pmc_traffic_c4.json
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- $B > /dev/null 2>&1
 python tools/pmc_busy.py $O/pmc_mfma > $O/r02_pmc_mfma_busy.txt 2>&1
 # the bench line (driver's command) and its kernel statistics
-python bench.py --steps 20 --warmup 3 2>$O/r02_bench.err | grep '^{' | tail -1 > $O/r02_bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r02_bench_under_rocprof.json
+python bench.py --full --steps 20 --warmup 3 2>$O/r02_bench.err | grep '^{' | tail -1 > $O/r02_bench.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r02_bench_under_rocprof.json
 cp $(ls $O/kt/*/*kernel_stats.csv | tail -1) $O/r02_kernel_stats.csv
 # other sizes of the same structure (K = 200) and round 1's headline workload
 for nx in 1000 2000 3000; do python tools/c4_bench.py 200 $nx 50 3 --profile 2>/dev/null | grep '^{' | tail -1 >> $O/r02_c4_sizes.jsonl; done
-python bench.py --workload c2 --steps 20 --warmup 3 2>/dev/null | grep '^{' | tail -1 > $O/r02_bench_c2.json
+python bench.py --full --workload c2 --steps 20 --warmup 3 2>/dev/null | grep '^{' | tail -1 > $O/r02_bench_c2.json
 python tools/staged_probe.py gemm 2>/dev/null > $O/r02_dgemm_sizes.txt
 python tools/update_time.py 2>/dev/null | grep '^{' | tail -1 > $O/r02_update_time.json
 # configs[4] stand-in: the sparse NLP through the reference's SQP host (reference's RedSpBKP up to 150 x 150 cells)

@@ -13,12 +13,12 @@ cp $O/pmc_traffic.json $O/r06_pmc_traffic_c4.json; cp $O/r06_pmc_traffic_c4.json
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- $B > /dev/null 2>&1
 python tools/pmc_busy.py $O/pmc_mfma > $O/r06_pmc_mfma_busy.txt 2>&1
 # the bench line (driver's command) and its kernel statistics
-timeout 900 python bench.py --steps 20 --warmup 3 2>$O/r06_bench.err | grep '^{' | tail -1 > $O/r06_bench.json
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_under_rocprof.json
+timeout 900 python bench.py --full --steps 20 --warmup 3 2>$O/r06_bench.err | grep '^{' | tail -1 > $O/r06_bench.json
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_under_rocprof.json
 cp $(ls $O/kt/*/*kernel_stats.csv | tail -1) $O/r06_kernel_stats.csv
 # C2 (tree engine): bench line, kernel statistics, launch by launch, counters, stamps inside the pivot-block and the panel kernels
-timeout 300 python bench.py --workload c2 --steps 30 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_c2.json
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --workload c2 --steps 20 --warmup 3 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_c2_under_rocprof.json
+timeout 300 python bench.py --full --workload c2 --steps 30 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_c2.json
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --full --workload c2 --steps 20 --warmup 3 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_c2_under_rocprof.json
 cp $(ls $O/kt2/*/*kernel_stats.csv | tail -1) $O/r06_kernel_stats_c2.csv
 timeout 300 bash tools/c2_trace.sh 160 > $O/r06_c2_timeline.txt 2>&1
 timeout 600 bash tools/pmc_tree.sh > $O/r06_pmc_tree.txt 2>&1
@@ -57,7 +57,7 @@ done
 # the cut form of the fp64 product: equal shares against the work table, and the table's stamps
 { for t in 0 1 0 1; do echo "== HQPKKT_SK_TABLE=$t"; HQPKKT_SK_TABLE=$t python3 tools/dgemm_stamps.py 5000x5050x5000x0 5050x5050x5000x1 3000x3050x3000x0 2>&1 | grep -v amdgpu; done; } > $O/r06_sk_table.txt
 HQPKKT_DGEMM_STAMPS=1 python3 tools/dgemm_stamps.py 5000x5050x5000x0 5050x5050x5000x1 2>&1 | grep -v amdgpu > $O/r06_sk_stamps.txt
-HQPKKT_SK_TABLE=0 timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_equal_shares.json
+HQPKKT_SK_TABLE=0 timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_equal_shares.json
 # configs[4] stand-ins (mesh 300 x 300, 1000 x 1000, band of 21 with 1000 far couplings at 10^5 variables, the mesh with 1 % far couplings)
 timeout 600 python tools/mesh_bench.py 2>/dev/null | grep '^{' | tail -1 > $O/r06_mesh_bench.json
 # SURVEY C5's row density (10 ... 100 entries per row) at 1e5 variables
@@ -67,7 +67,7 @@ timeout 900 python tools/c5_irregular.py 2>/dev/null | grep '^{' > $O/r06_c5_irr
 # mid-size stages
 for nx in 1000 2000 3000; do timeout 300 python tools/c4_bench.py 200 $nx 50 3 2>/dev/null | grep '^{' | tail -1 >> $O/r06_c4_sizes.jsonl; done
 # N > 1 path: bench.py starting its own two ranks on the one GPU (exchange staged through gloo: functional, not a measurement)
-timeout 600 python bench.py --gpus 2 --backend gloo --share-gpu --stages 20 --steps 3 --warmup 1 --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_2rank_shared.json
+timeout 600 python bench.py --full --gpus 2 --backend gloo --share-gpu --stages 20 --steps 3 --warmup 1 --no-ip 2>/dev/null | grep '^{' | tail -1 > $O/r06_bench_2rank_shared.json
 # one rank of P on the one GPU with a transport that moves nothing: the pieces of the sharded stage (tools/shard_model.py)
 timeout 600 bash tools/slice_products.sh > $O/r06_slice_products.txt 2>&1
 echo "## the model (tools/shard_model.py)" >> $O/r06_slice_products.txt

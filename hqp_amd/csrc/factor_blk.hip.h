@@ -1,5 +1,5 @@
 // Pivot block of a general front (33 .. 256 pivots): dense Bunch-Kaufman LDL' and the
-// explicit inverse M = L11^-1, on the matrix pipe.  Included by hqpkkt.hip after
+// explicit inverse M = L11^-1, on the matrix pipe.  Included by tree.hip after
 // kernels.hip.h (round 4; k_factor_diag of rounds 1-3 stays selectable for same-box
 // comparisons).
 //
@@ -35,6 +35,14 @@
 // blocks (vectors through LDS), then the panels go on behind it (a panel may start in the
 // middle of a block).
 #pragma once
+
+// the instances tree.hip launches
+#ifndef FB_NS160
+#define FB_NS160 5  // blocks per block-holding wavefront of k_factor_blk for fronts of 129 .. 160 pivots (7 with FB_OWNSIMD: nine such wavefronts)
+#endif
+#ifndef FB_OWNSIMD
+#define FB_OWNSIMD false  // true: the elimination wavefront of k_factor_blk shares its SIMD with no block-holding wavefront (measured slower)
+#endif
 
 namespace kktdev {
 

@@ -1,0 +1,496 @@
+// Internal header of the C-ABI library (include/hqpkkt.h): the handle and what the units share - device buffers,
+// per-class timing, graph capture, and the functions one unit calls in another.  The units:
+//   tree.hip           device residency and kernel sequencing of the tree engine (kernels.hip.h, factor_blk.hip.h,
+//                      solve_top.hip.h), the vector staging of a call, the residual and the posted read-backs
+//   staged_engine.hip  the STAGED engine (staged.hip.h, staged_host.hip.h)
+//   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
+//   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
+#pragma once
+#include "../../include/hqpkkt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <chrono>
+#include <cstring>
+#include <atomic>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "analysis.hpp"
+#include "staged_plan.hpp"
+#include "device_common.hip.h"
+
+// The kernels that more than one unit launches: defined once (kernels.hip.h, compiled into tree.hip)
+namespace kktdev {
+__global__ void k_weights(int mode, int m, int nme, const double *z, const double *w, double *wt, double *sc, int *status);
+__global__ void k_red_t(int m, const double *w, const double *zw, const double *r3, const double *r4, double *t);
+__global__ void k_red_dzdw(int m, const int *Cp, const int *Cc, const int *Cs, const double *vals, const double *dx,
+                           const double *zw, const double *t, const double *r3, double *dz, double *dw);
+__global__ void k_gather_values(int nnz, const int *src, const double *vals, double *out);
+__global__ void k_zd_weak(int n, CsrDev Q, CsrDev AT, int *flag);
+__global__ void k_clear(double *p, long long n, int *words);
+__global__ void k_copy_vectors(CopyList L, int nvec);
+__global__ void k_axpy4(int n, int me, int m, double alpha, const double *e1, const double *e2, const double *e3,
+                        const double *e4, double *d1, double *d2, double *d3, double *d4);
+}  // namespace kktdev
+using namespace kktdev;  // (the units are written against kktdev's names)
+
+// (everything below is internal to the library: not exported)
+#pragma GCC visibility push(hidden)
+
+extern char g_last_hip_error[512];  // the text of the last HIP error (hqpkkt_strerror)
+
+#define HIPCHK(call)                                                              \
+  do {                                                                            \
+    hipError_t e_ = (call);                                                       \
+    if (e_ != hipSuccess) {                                                       \
+      std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "%s:%d %s: %s", __FILE__, \
+                    __LINE__, #call, hipGetErrorString(e_));                      \
+      return HQPKKT_E_DEVICE;                                                     \
+    }                                                                             \
+  } while (0)
+
+template <class T>
+struct DBuf {
+  T *p = nullptr;
+  size_t count = 0;
+  int alloc(size_t k) {
+    release();
+    count = k;
+    if (hipMalloc((void **)&p, sizeof(T) * (k ? k : 1)) != hipSuccess) {
+      p = nullptr;
+      return HQPKKT_E_MEM;
+    }
+    return 0;
+  }
+  int upload(const std::vector<T> &v) {
+    int e = alloc(v.size());
+    if (e) return e;
+    if (!v.empty() &&
+        hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess)
+      return HQPKKT_E_DEVICE;
+    return 0;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    count = 0;
+  }
+};
+
+struct CsrBuf {
+  DBuf<int> ptr, col, src;
+  DBuf<double> val;  // values in CSR order, refreshed by hqpkkt_set_values
+  int upload(const Analysis::Csr &c) {
+    int e;
+    if ((e = ptr.upload(c.ptr)) || (e = col.upload(c.col)) || (e = src.upload(c.src)) || (e = val.alloc(c.src.size())))
+      return e;
+    return 0;
+  }
+  CsrDev dev() const { return CsrDev{ptr.p, col.p, src.p, val.p}; }
+  void release() { ptr.release(), col.release(), src.release(), val.release(); }
+};
+
+// per-kernel-class device timing (hqpkkt_set_profile): HIP events on the
+// handle's stream around every launch, summed per class after the call
+enum { KC_ASSEMBLE = 0, KC_FACTOR_DIAG, KC_PANEL_SOLVE, KC_SCHUR_UPDATE,
+       KC_SOLVE_FWD, KC_SOLVE_BWD, KC_VECTOR, KC_RESIDUAL, KC_ST_GEMM, KC_ST_SMALL, KC_ST_VEC, KC_ST_GEMM_UPD, KC_XCHG, KC_SOLVE_TOP, KC_COUNT };
+static const char *const kc_names[KC_COUNT] = {"assemble", "factor_diag", "panel_solve",
+                                               "schur_update", "solve_fwd", "solve_bwd", "vector",
+                                               "residual", "staged_gemm", "staged_small", "staged_gemv", "staged_gemm_upd",
+                                               "exchange", "solve_top"};
+struct Prof {
+  bool on = false;
+  std::vector<hipEvent_t> pool;
+  std::vector<int> cls;
+  size_t used = 0;
+  double ms[KC_COUNT] = {0};
+  long long launches[KC_COUNT] = {0};
+  hipEvent_t get() {
+    if (used == pool.size()) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return nullptr;
+      pool.push_back(e);
+    }
+    return pool[used++];
+  }
+  void begin(int c, hipStream_t s) {
+    if (!on) return;
+    hipEvent_t e = get();
+    cls.push_back(c);
+    if (e) (void)hipEventRecord(e, s);
+  }
+  void end(hipStream_t s) {
+    if (!on) return;
+    hipEvent_t e = get();
+    if (e) (void)hipEventRecord(e, s);
+  }
+  // call after the stream has been synchronised
+  void collect() {
+    for (size_t k = 0; k + 1 < used && k / 2 < cls.size(); k += 2) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, pool[k], pool[k + 1]) == hipSuccess) {
+        ms[cls[k / 2]] += t;
+        launches[cls[k / 2]]++;
+      }
+    }
+    used = 0;
+    cls.clear();
+  }
+  void reset() {
+    for (int c = 0; c < KC_COUNT; c++) ms[c] = 0, launches[c] = 0;
+  }
+  void destroy() {
+    for (auto e : pool) (void)hipEventDestroy(e);
+    pool.clear();
+  }
+};
+#define KLAUNCH(h, c, ...)        \
+  do {                            \
+    (h)->prof.begin(c, (h)->stream); \
+    __VA_ARGS__;                  \
+    (h)->prof.end((h)->stream);   \
+  } while (0)
+
+struct StagedDev;  // (staged_host.hip.h)
+void staged_release(StagedDev *sd, bool destroy);
+
+struct hqpkkt {
+  hqpkkt_opts opts;
+  Prof prof;
+  Analysis an;
+  StagedDev *sd = nullptr;  // HQPKKT_MODE_STAGED: the stage blocks (staged_host.hip.h)
+  double ge_tol = 1.0e-6;   // rank decision of the stage constraints (_ge_tol, hqp/Hqp_IpLQDOCP.C:113)
+  bool analyzed = false, uploaded = false, have_values = false, factored = false;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, evs0 = nullptr, evs1 = nullptr;
+  hipEvent_t evt0 = nullptr, evt1 = nullptr;  // total time of an interior-point run (hqpkkt_mehrotra / _franke)
+  hqpkkt_stats st;
+
+  // symbolic structure on the device
+  DBuf<int> piv_start, npiv, nbor, parent, bidx, rel, child_ptr, child_idx, ent_a, ent_b,
+      term_ptr, diag_ent, q2e, pinv;
+  struct DevSched {  // device copy of an Analysis::Sched
+    DBuf<int> level_nodes, upd_tiles, slabs, gslabs, cblks;
+    void release() {
+      level_nodes.release(), upd_tiles.release(), slabs.release();
+      gslabs.release(), cblks.release();
+    }
+  } ds[2];
+  DBuf<long long> zero_panel;  // (offset, length) pairs, sharded mode
+  DBuf<int> simple_src, simple_wi;  // FULL: compact single-term records of the entries (k_assemble_simple)
+  DBuf<signed char> keep_e;
+  // one system over several ranks: collectives are delegated to the caller
+  int shard_rank = 0, shard_count = 1;
+  hqpkkt_exchange_fn xchg_fn = nullptr;
+  hqpkkt_exchange_stream_fn xchg_sfn = nullptr;  // stream-ordered form (RCCL): nothing is drained
+  void *xchg_ctx = nullptr;
+  DBuf<long long> bptr, panel_off, upd_off, x_off, cb_off, ent_dst, linv_off, pinv_off;
+  DBuf<TermDev> terms;
+  DBuf<signed char> esign;
+  CsrBuf Qf, A, AT, C, CT;
+  // numeric state
+  DBuf<double> vals, wt, sc, ent_val, panel, upd, xar, dinv, rhs, xsol, cb, ytmp, vtmp, linv;
+  DBuf<int> ptype, lperm, flags;  // flags: [0] status, [1] n_2x2, [2] n_perturbed
+  // [0] kmax, [1] residual max: inside the flags buffer (ints 120..123) so that status and
+  // maxima come back in ONE copy; hpin: pinned host memory those copies land in
+  struct {
+    unsigned long long *p = nullptr;
+  } bits;
+  double *hpin = nullptr;  // 128 doubles: 0..63 status words (as ints), 64.. the IP loop's scalars
+  // Read-backs without a copy and without hipStreamSynchronize (round 6): hpin is mapped, coherent host memory; a
+  // one-wavefront kernel at the point of the stream where the words are final stores them there and a sequence number
+  // behind them (k_post_words, kernels.hip.h), the host spins on that number (post_wait).  Measured (tools/post_probe.hip):
+  // 6 us per read-back behind a queue of small kernels against 16 for hipMemcpyAsync + hipStreamSynchronize - the
+  // device-resident interior-point loops read back three times per iteration.
+  double *hpin_dev = nullptr;  // the device's address of hpin
+  unsigned post_seq = 0;       // the number the last posting kernel in the stream will store (hpin word HPIN_SEQ)
+  // host vectors of a small system: packed into / out of pinned memory by the CPU, ONE
+  // transfer each way instead of six + four staged copies from pageable memory
+  double *hvals = nullptr;   // pinned host staging of Qx | Ax | Cx (hqpkkt_values_staging), nq + na + nc doubles
+  size_t hvals_elems = 0;    // ... as allocated: a new analysis with another pattern allocates again
+  double *hstage = nullptr;
+  size_t hstage_in = 0, hstage_out = 0;  // doubles; 0 = system too large, copy vector by vector
+  const double *out_pending = nullptr;   // results wait in hstage + hstage_in for unstage()
+  bool out_by_kernel = false;            // ... written there by a kernel in front of the posting kernel (no stream synchronisation needed)
+  bool host_graph_call = false;          // inside a solve whose first part ran as hqpkkt::ghost_step (no timing events in the stream)
+  double *hstage_dev = nullptr;          // the device's address of hstage (pinned, coherent: kernels copy in and out of it)
+  // vectors: staging for host pointers + refinement work vectors
+  DBuf<double> vin;   // z w r1 r2 r3 r4
+  DBuf<double> vout;  // dx dy dz dw
+  DBuf<double> vres;  // residual vectors _r1.._r4
+  DBuf<double> vcor;  // corrections _dx.._dw
+  DBuf<double> tz;    // REDUCED temporary (m)
+  DBuf<double> ipv;   // interior-point driver: x y z w | r1..r4 | dxa..dwa | dx..dw | c b d | partials | scalars
+  size_t lds_panel = 0, lds_bwdb = 0;
+  // per schedule and tree level the largest pivot count (and border) among the general fronts of the level (k_factor_blk)
+  std::vector<int> level_maxp[2], level_maxb[2];
+  // the device-resident interior-point loops: cancelled multiplier pivots are replaced (kernels.hip.h, TINY_REPLACE_WORD)
+  // only in the SECOND attempt of a run whose first attempt - without the replacement, i.e. with the factors the
+  // reference's own loop gets from this plugin through the shim - ended "degenerate" or singular
+  bool tiny_replace_in_loop = false;
+  // the top levels of the tree solved in one launch (solve_top.hip.h): fronts of the levels >= top_lt, root first
+  int top_n = 0, top_lt = 1 << 30, top_ns = 3;  // top_ns: 3 = k_solve_top<3, 11>, 4 = <4, 10>
+  size_t top_lds = 0;
+  DBuf<int> top_nodes, top_idx, top_bpos, top_up;  // top_up: the fronts leaves first (top_split)
+  bool top_split = false;  // more fronts than one launch may hold at once: the two sweeps as launches of their own
+  unsigned long long *top_stamps = nullptr;  // (hqpkkt_debug_solve_top_stamps)
+  // trees of small fronts only (the double-integrator structure): each sweep of the solve is ONE launch over all levels
+  // (k_solve_fwd_small<true> / k_solve_bwd_small<true>); tree_x: the exchange arrays (2 x cb_elems, then 2 x dim)
+  bool small_tree = false, tree_factor = false;  // tree_factor: ... and the factorisation too (k_factor_diag_small<true, true>)
+  DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
+  DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
+  DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
+  // captured kernel sequences (factor; step on the caller's vectors; step on the
+  // refinement's residual vectors): replayed with hipGraphLaunch
+  struct GraphSlot {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ge = nullptr;
+    unsigned n_posts = 0;  // posted read-backs inside (k_post_words counts on the device; the host counts along at every replay)
+    void drop() {
+      if (ge) (void)hipGraphExecDestroy(ge);
+      if (g) (void)hipGraphDestroy(g);
+      ge = nullptr, g = nullptr, n_posts = 0;
+    }
+  } gfactor[2], gstep[2][3];  // [phase], [caller's / refinement's vectors][phase]
+  // A caller with HOST vectors (the reference's solvers through the shim): the packed vectors are read out of the pinned
+  // staging buffer by a kernel, the results written into it by a kernel, and the status words posted - a whole call is
+  // one graph on the compute queue (no copy engine between the launches: 9 - 13 us at each change of engine,
+  // profiles/r06_shim_timeline.txt) and ends with the posted words, not a stream synchronisation
+  GraphSlot ghost_factor, ghost_step;
+  // The device-resident interior-point loops hand over the same device vectors in every iteration: their sequences are
+  // captured ON those vectors (no copies into and out of the handle's staging buffers), one graph per set of pointers.
+  struct DirectGraph {
+    const void *key[10];
+    GraphSlot g;
+  };
+  std::vector<DirectGraph> gdirect_step, gdirect_factor;
+  // ... and whole SEGMENTS of an iteration of the device-resident loops - everything between two read-backs: the
+  // factorisation, a solve, its residual and the posting kernel - as one graph (ip_segment)
+  std::vector<DirectGraph> gdirect_seg;
+  // ... and a caller's own factor / solve call on its device vectors with its residual and the posted words
+  std::vector<DirectGraph> gdirect_call;
+  GraphSlot &direct_slot(std::vector<DirectGraph> &cache, const void *const (&key)[10]) {
+    for (auto &d : cache)
+      if (std::memcmp(d.key, key, sizeof(key)) == 0) return d.g;
+    if (cache.size() >= 6) {  // (Mehrotra's loop has two sets + the refinement's, Franke's one + the refinement's)
+      cache.front().g.drop();
+      cache.erase(cache.begin());
+    }
+    cache.emplace_back();
+    std::memcpy(cache.back().key, key, sizeof(key));
+    return cache.back().g;
+  }
+  bool use_graphs = true, capturing = false;
+  unsigned cap_posts = 0;  // posted read-backs of the capture in progress
+  DBuf<unsigned> post_seq_dev;  // the sequence number of the posted read-backs, counted by k_post_words
+  // inside hqpkkt_mehrotra: factor() returns without waiting for its status (read with the
+  // residual of the solve that follows), solve() leaves its result in the stream
+  bool lazy = false, factor_unchecked = false;
+  // hqpkkt_factor / hqpkkt_solve of a caller with DEVICE vectors: the second call in a row with the same pointers works
+  // on the caller's vectors themselves (no staging copies; the sequences are captured on them, DirectGraph) - set for
+  // the duration of that call.  last_f / last_s: the pointers of the previous call of either kind
+  bool direct_now = false;
+  const void *last_f[2] = {nullptr, nullptr}, *last_s[10] = {};
+  // hqpkkt_franke: the first residual of a solve is not waited for - it comes back with the scalars of the iteration
+  // (one read-back per iteration); residual_pending: such a residual is in the stream, collect_residual() reads it
+  bool defer_residual = false, residual_pending = false;
+  int res_read = 122;  // the word of the flags buffer the residual kernels leave their maximum in (cleared by k_post_words)
+  bool no_polled = false;      // a polled launch gave up once: per-level launches for the rest of the handle's life (poll_fallback)
+  bool soft_singular = false;  // the factorisation perturbed an exactly zero pivot (counters[3])
+  bool soft_tiny = false;      // ... or met a pivot below 1e-13 max|K| on a multiplier-type row (counters[4])
+  double refine_target = 0.0;  // > 0: the refinement of hqpkkt_solve aims below mat_eps (set by hqpkkt_franke)
+  // hqpkkt_mehrotra left x, y and the hot-start candidates of z, w in ipv (same dimensions)
+  bool ip_hot_valid = false;
+  bool fr_hot_valid = false;  // hqpkkt_franke left x, y, z, w in ipv (same dimensions)
+  double fr_rhomin = 0.0;     // ... and its qp_rhomin, which hot_start keeps (hqp/Hqp_IpsFranke.C:222-266)
+  // the caller's pattern (hqpkkt_analyze), kept for the one repetition of the symbolic phase
+  // that zd_policy -1 may ask for when the first values arrive; zd_used: policy of h->an
+  std::vector<int> pQp, pQi, pAp, pAi, pCp, pCi;
+  int zd_used = 2;
+  bool zd_decided = true;
+  // zd_policy -1 on a QP with weak Hessian diagonals: the values on the host, so that a solve
+  // whose refinement fails can switch the handle to policy 0 (symbolic phase, upload, values,
+  // factorisation again) and repeat itself
+  bool zd_weak = false;
+  std::vector<double> hQ, hA, hC;
+  bool short_rows = false;  // CSR rows of a handful of entries: 4 lanes per row in the SpMV kernels
+  void drop_graphs() {
+    for (auto &g : gfactor) g.drop();
+    ghost_factor.drop(), ghost_step.drop();
+    for (auto &gs : gstep)
+      for (auto &g : gs) g.drop();
+    for (auto &d : gdirect_step) d.g.drop();
+    for (auto &d : gdirect_factor) d.g.drop();
+    for (auto &d : gdirect_seg) d.g.drop();
+    for (auto &d : gdirect_call) d.g.drop();
+    gdirect_step.clear(), gdirect_factor.clear(), gdirect_seg.clear(), gdirect_call.clear();
+  }
+
+  DevTree tree() const {
+    return DevTree{piv_start.p, npiv.p,     nbor.p,  parent.p, bptr.p,      bidx.p,     rel.p,
+                   panel_off.p, upd_off.p, x_off.p, cb_off.p, child_ptr.p, child_idx.p, pinv.p, pinv_off.p};
+  }
+  void release_device(bool keep_ip = false) {  // keep_ip: hqpkkt_mehrotra's vectors and the pinned words stay
+    DBuf<int> *ib[] = {&piv_start, &npiv, &nbor, &parent, &bidx, &rel, &child_ptr, &child_idx,
+                       &ent_a, &ent_b, &term_ptr, &diag_ent, &q2e, &pinv, &ptype, &lperm, &flags,
+                       &top_nodes, &top_idx, &top_bpos, &top_up, &tree_words, &tree_down};
+    for (auto b : ib) b->release();
+    ds[0].release(), ds[1].release(), keep_e.release(), simple_src.release(), simple_wi.release();
+    DBuf<long long> *lb[] = {&bptr, &panel_off, &upd_off, &x_off, &cb_off, &ent_dst, &linv_off, &pinv_off,
+                             &zero_panel};
+    for (auto b : lb) b->release();
+    DBuf<double> *db[] = {&vals, &wt, &sc, &ent_val, &panel, &upd, &xar, &dinv, &rhs, &xsol,
+                          &cb, &vin, &vout, &vres, &vcor, &tz, &ytmp, &vtmp, &linv, &top_x, &tree_x, &tree_u};
+    for (auto b : db) b->release();
+    if (!keep_ip) ipv.release();
+    terms.release(), esign.release(), bits.p = nullptr;
+    if (hpin && !keep_ip) (void)hipHostFree(hpin), hpin = nullptr, hpin_dev = nullptr, post_seq_dev.release(), post_seq = 0;
+    if (hstage) (void)hipHostFree(hstage), hstage = nullptr, hstage_dev = nullptr;
+    // (keep_ip = the re-analysis inside hqpkkt_solve, switch_to_policy0: the pattern and with it the sizes of the
+    // pinned value staging stay, and a host may hold the pointers of hqpkkt_values_staging)
+    if (hvals && !keep_ip) (void)hipHostFree(hvals), hvals = nullptr, hvals_elems = 0;
+    hstage_in = hstage_out = 0;
+    Qf.release(), A.release(), AT.release(), C.release(), CT.release();
+    if (sd) staged_release(sd, false);
+    drop_graphs();
+    uploaded = have_values = factored = false;
+  }
+};
+
+static inline int nblk(long long work, int bs = 256) { return (int)((work + bs - 1) / bs); }
+// grid of k_copy_vectors: enough workgroups for the longest vector, at most 1024
+static inline int copy_blocks(const CopyList &L) {
+  int mx = 1;
+  for (int v = 0; v < 6; v++) mx = std::max(mx, L.len[v]);
+  return std::min(1024, std::max(1, nblk(mx)));
+}
+
+// pointers of the six input vectors / four outputs for the current call
+struct Vecs {
+  const double *z, *w, *r1, *r2, *r3, *r4;
+  double *dx, *dy, *dz, *dw;
+};
+
+struct OutPtrs {
+  double *dx, *dy, *dz, *dw;
+};
+
+// replay (or first capture) of a kernel sequence as a hipGraph; falls back to
+// eager launches while per-kernel profiling is on
+template <class F>
+static int graphed(hqpkkt_t *h, hqpkkt::GraphSlot &slot, F body) {
+  if (!h->use_graphs || h->prof.on || h->capturing) return body();  // (capturing: a sequence inside a segment's capture)
+  if (!slot.ge) {
+    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    h->capturing = true, h->cap_posts = 0;
+    int e = body();
+    h->capturing = false;
+    hipGraph_t g = nullptr;
+    hipError_t ce = hipStreamEndCapture(h->stream, &g);
+    if (e) {
+      if (g) (void)hipGraphDestroy(g);
+      h->post_seq -= h->cap_posts;  // (nothing was posted)
+      return e;
+    }
+    if (ce != hipSuccess || !g) {  // capture not possible: run eagerly from now on
+      h->use_graphs = false;
+      (void)hipGetLastError();
+      h->post_seq -= h->cap_posts;
+      return body();
+    }
+    slot.g = g;
+    if (hipGraphInstantiate(&slot.ge, g, nullptr, nullptr, 0) != hipSuccess) {
+      slot.drop();
+      h->use_graphs = false;
+      (void)hipGetLastError();
+      h->post_seq -= h->cap_posts;
+      return body();
+    }
+    slot.n_posts = h->cap_posts;  // (the host has counted them during the capture)
+  } else
+    h->post_seq += slot.n_posts;
+  HIPCHK(hipGraphLaunch(slot.ge, h->stream));
+  return 0;
+}
+
+// The exchange steps of a sharded system: the handle's stream is
+// drained, the caller's collective runs, and the next phase starts afterwards.
+// (Defined here and static: staged_host.hip.h, which the STAGED unit includes as it is, declares it static.)
+static int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on = nullptr) {
+  // (profiled as the class "exchange": in the stream-ordered form the time between the collective's place in
+  // the stream and its completion - the wait for the slowest rank and the transfer)
+  if (h->xchg_sfn) {  // the collective is put into the handle's stream (or `on`) behind the kernels that fill `buf`
+    hipStream_t st = on ? on : h->stream;
+    h->prof.begin(KC_XCHG, st);
+    const int rc = h->xchg_sfn(h->xchg_ctx, op, buf, slot, nslots, (void *)st);
+    h->prof.end(st);
+    return rc ? HQPKKT_E_DEVICE : 0;
+  }
+  if (!h->xchg_fn) return HQPKKT_E_INTERN;
+  h->prof.begin(KC_XCHG, h->stream);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int rc = h->xchg_fn(h->xchg_ctx, op, buf, slot, nslots);
+  h->prof.end(h->stream);
+  return rc ? HQPKKT_E_DEVICE : 0;
+}
+
+// The C ABI promises that nothing is thrown across it (the shim's callers longjmp through Meschach
+// frames): every entry point that allocates with the standard library runs inside this guard.
+template <class F>
+static int guarded(F body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    return HQPKKT_E_MEM;
+  } catch (...) {
+    return HQPKKT_E_INTERN;
+  }
+}
+
+static const int HQPKKT_E_POLL = -7001;  // internal: a polled launch gave up (poll_fallback); never leaves the library
+
+static inline float elapsed(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = -1.f;
+  return ms;
+}
+
+// ---- what one unit calls in another
+// tree.hip
+int ensure_device(hqpkkt_t *h);
+int alloc_hpin(hqpkkt_t *h);
+int upload(hqpkkt_t *h);
+bool poll_fallback(hqpkkt_t *h, const int *hs);
+bool host_graphs_ok(const hqpkkt_t *h);
+size_t stage_pack(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3, const double *r4);
+int stage_in(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3, const double *r4,
+             Vecs &v);
+void stage_out_ptrs(hqpkkt_t *h, Vecs &v);
+int stage_out(hqpkkt_t *h, const Vecs &v, double *dx, double *dy, double *dz, double *dw);
+void unstage(hqpkkt_t *h, double *dx, double *dy, double *dz, double *dw);
+int do_factor(hqpkkt_t *h, const Vecs &v);
+int do_step(hqpkkt_t *h, const Vecs &v, int which);
+int post_words(hqpkkt_t *h, const double *out, int n_out, bool residual = false);
+int post_wait(hqpkkt_t *h);
+int residual_launch(hqpkkt_t *h, const Vecs &v);
+int run_residual(hqpkkt_t *h, const Vecs &v, double *res, const OutPtrs *out = nullptr);
+int collect_residual(hqpkkt_t *h, double *res);
+// staged_engine.hip
+int staged_analyze_csr(hqpkkt_t *h, int n, int me, int m);
+int staged_set_values_csr(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx);
+int staged_factor(hqpkkt_t *h, const Vecs &v);
+int staged_step(hqpkkt_t *h, const Vecs &v, int which);
+int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn);
+int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out);
+// hqpkkt.hip
+int solve_vecs(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3,
+               const double *r4, double *dx, double *dy, double *dz, double *dw, Vecs &v);
+int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const double *r1, const double *r2, const double *r3,
+               const double *r4, double *dx, double *dy, double *dz, double *dw, double res, double *res_out);
+
+#pragma GCC visibility pop

@@ -1,4 +1,5 @@
-// gfx950 kernels of the KKT path.  Included once by hqpkkt.hip.
+// gfx950 kernels of the KKT path (the tree engine).  Included once, by tree.hip; the
+// types and wave-level helpers the other units share are in device_common.hip.h.
 //
 // Data layout in HBM (all fp64 values, int32 indices, int64 arena offsets):
 //   vals   [nq+na+nc+1]   Qx | Ax | Cx | 1.0            (hqpkkt_set_values)
@@ -16,22 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+
+#include "device_common.hip.h"
 namespace kktdev {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double4_t mfma_f64(double a, double b, double4_t c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-struct DevTree {
-  const int *piv_start, *npiv, *nbor, *parent;
-  const long long *bptr;
-  const int *bidx, *rel;
-  const long long *panel_off, *upd_off, *x_off, *cb_off;
-  const int *child_ptr, *child_idx;
-  const int *pinv;            // per child: parent front index -> child border index (-1: none)
-  const long long *pinv_off;
-};
 
 // Sum of the children's update blocks at front position (fi, fj), fi >= fj, of `node`:
 // what an extend-add pass would have added to that entry (children in slot order).
@@ -45,96 +33,6 @@ __device__ __forceinline__ double gather_children(const DevTree &T, const double
     if (ci >= 0 && cj >= 0) s += upd[T.upd_off[c] + (long long)cj * T.nbor[c] + ci];
   }
   return s;
-}
-
-// order-preserving max for non-negative doubles through their bit pattern
-// (the read-modify-writes of a launch's workgroups on ONE word are served one after the other, ~6 ns each: launches that
-// end in this keep their grids at a thousand or two workgroups; a look at the word first - an agent-scope load - cost
-// k_assemble_simple more than it saved k_residual)
-__device__ __forceinline__ void atomic_max_pos(unsigned long long *addr, double v) {
-  atomicMax(addr, (unsigned long long)__double_as_longlong(v));
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-// max over the 64 lanes of a non-negative value with DPP row operations (no LDS
-// crossbar traffic); the result is broadcast to every lane
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double v) {
-  const long long b = __double_as_longlong(v);
-  int lo = (int)(b & 0xffffffffLL), hi = (int)(b >> 32);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wave_max_dpp(double v) {
-  v = fmax(v, dpp_move<0xb1, 0xf>(v));   // quad_perm [1,0,3,2]
-  v = fmax(v, dpp_move<0x4e, 0xf>(v));   // quad_perm [2,3,0,1]
-  v = fmax(v, dpp_move<0x124, 0xf>(v));  // row_ror 4
-  v = fmax(v, dpp_move<0x128, 0xf>(v));  // row_ror 8
-  v = fmax(v, dpp_move<0x142, 0xa>(v));  // row_bcast 15
-  v = fmax(v, dpp_move<0x143, 0xc>(v));  // row_bcast 31 -> lane 63 holds the max
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), 63);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// sum over the 64 lanes the same way (lanes a DPP step does not reach contribute zero); broadcast to every lane
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move0(double v) {
-  const long long b = __double_as_longlong(v);
-  int lo = (int)(b & 0xffffffffLL), hi = (int)(b >> 32);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-  v += dpp_move0<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_move0<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_move0<0x124, 0xf>(v);  // row_ror 4
-  v += dpp_move0<0x128, 0xf>(v);  // row_ror 8: every lane of a row has the row's sum
-  v += dpp_move0<0x142, 0xa>(v);  // row_bcast 15: rows 1 and 3 add the sum of the row before
-  v += dpp_move0<0x143, 0xc>(v);  // row_bcast 31: rows 2 and 3 add lane 31 -> lane 63 holds the total
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), 63);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// same for a float (the arg-max search of the pivot column runs in fp32: an fp64
-// max costs ~40 cycles of latency per step on gfx950, an fp32 one a few)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL,
-                                                    ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_max_dpp_f(float v) {
-  v = fmaxf(v, dpp_move_f<0xb1, 0xf>(v));
-  v = fmaxf(v, dpp_move_f<0x4e, 0xf>(v));
-  v = fmaxf(v, dpp_move_f<0x124, 0xf>(v));
-  v = fmaxf(v, dpp_move_f<0x128, 0xf>(v));
-  v = fmaxf(v, dpp_move_f<0x142, 0xa>(v));
-  v = fmaxf(v, dpp_move_f<0x143, 0xc>(v));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-// 1/d by the hardware estimate and two Newton steps (error ~1 ulp; the pivot is
-// bounded away from zero and from overflow by the perturbation test)
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = fma(fma(-d, x, 1.0), x, x);
-  x = fma(fma(-d, x, 1.0), x, x);
-  return x;
-}
-
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // ---------------------------------------------------------------- assembly
@@ -161,11 +59,6 @@ __global__ void k_weights(int mode, int m, int nme, const double *__restrict__ z
     wt[j] = zj / wj;
   }
 }
-
-struct TermDev {
-  int s1, s2, wi;
-  double sgn;
-};
 
 // An exactly zero pivot is E_SING for the reference (hqp/spBKP.C:699-700), whose pivot search
 // sees the whole remaining column.  Here the search ends at the supernode's pivot block: in a
@@ -207,9 +100,6 @@ __device__ double soft_pivot_pert = 1e-6;
 // the reference's E_SING; a zero that turns up at the END of a run whose first factorisations were clean is cancellation
 // (w / z of 1e-21 beside 1e+9 at a gap of 4e-8: campaign case 187 of round 6) and is replaced like any other cancelled
 // pivot.  Without the replacement a zero stays the reference's E_SING (zero_pivot_slot above).
-static const int TINY_REPLACE_WORD = 112;
-// (the word: 0 off; TINY_REPLACE_ON: cancelled pivots that are not exactly zero; TINY_REPLACE_ZEROS: exactly zero ones as well)
-static const int TINY_REPLACE_ON = 0x01010101, TINY_REPLACE_ZEROS = 0x02020202;  // (set by hipMemsetAsync: a byte value)
 __device__ __forceinline__ bool tiny_replace(const int *counters, double d) {
   const int t = counters[TINY_REPLACE_WORD - 1];
   return t != 0 && (d != 0.0 || t == TINY_REPLACE_ZEROS) && soft_pivot_pert > 0.0;
@@ -1121,8 +1011,6 @@ int dn;
 // no arithmetic produces) until then; the consumer's lanes poll exactly the words they need.  No flags, no cache
 // maintenance: one memory round trip per tree level.  The arrays exist twice: solve e uses copy e & 1 and every front
 // puts the sentinel back into ITS words of the other copy, which nobody reads during this solve.
-static const unsigned long long XW_SENTINEL = 0x7ff8dead0badc0deULL;
-static const int XW_GAVE_UP = 110;  // index into the handle's flags buffer: a poll gave up (~2^20 tries)
 // tries before a poll gives up.  A device global so that a test can shorten it (HQPKKT_POLL_LIMIT, read when a handle
 // uploads its tree): with 0 every poll that has to wait gives up, which forces the fall-back to the per-level launches.
 __device__ int xw_poll_limit = 1 << 20;
@@ -2368,15 +2256,6 @@ k_schur_update_big(DevTree T, const int *__restrict__ tiles, const double *__res
   }
 }
 
-// MFMA layout self-test: C(16x16) = A(16x16) * B(16x16), all row-major
-__global__ void k_mfma_selftest(const double *A, const double *B, double *C) {
-  const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
-  double4_t acc = {0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < 16; k0 += 4)
-    acc = mfma_f64(A[lr * 16 + k0 + lk], B[(k0 + lk) * 16 + lr], acc);
-  for (int rg = 0; rg < 4; rg++) C[(lk + 4 * rg) * 16 + lr] = acc[rg];
-}
-
 // ------------------------------------------------------------------ solves
 // The sweeps over the assembly tree run level by level:
 //   forward    per (supernode, 64-row slab): t = rhs(pivots) + children contributions,
@@ -2879,10 +2758,6 @@ k_unpack_dzdw(int n, int me, int m, int nb_first, const int *__restrict__ q2e, c
 //   rho3 = r3 - (C dx - dw),           rho4 = r4 - (z.*dw + w.*dz)
 // Sixteen lanes (one DPP row) share a matrix row: they stride its non-zeros with
 // coalesced index / value loads and add up with DPP row rotations.
-struct CsrDev {
-  const int *ptr, *col, *src;
-  const double *val;  // the values in CSR order (gathered through src once per update())
-};
 __global__ void k_gather_values(int nnz, const int *__restrict__ src, const double *__restrict__ vals,
                                 double *__restrict__ out) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2899,33 +2774,6 @@ __global__ void k_zd_weak(int n, CsrDev Q, CsrDev AT, int *__restrict__ flag) {
     if (Q.col[k] == i) qd = fabs(Q.val[k]);
   for (int k = AT.ptr[i]; k < AT.ptr[i + 1]; k++) am = fmax(am, fabs(AT.val[k]));
   if (am > 0.0 && qd < 0.01 * am) atomicOr(flag, 1);
-}
-// sum over the LPR (16 or 4) consecutive lanes that share a CSR row
-template <int LPR>
-__device__ __forceinline__ double row_sum(double v) {
-  v += dpp_move<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_move<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]
-  if (LPR == 16) {
-    v += dpp_move<0x124, 0xf>(v);  // row_ror 4
-    v += dpp_move<0x128, 0xf>(v);  // row_ror 8 -> every lane of the row holds the sum
-  }
-  return v;
-}
-template <int LPR>
-__device__ __forceinline__ double row_dot(const CsrDev M, const double *__restrict__ vals,
-                                          const double *__restrict__ x, int row, int sub) {
-  // (two entries per lane in flight: the loop is a chain of index -> value round trips, 80 - 160 entries per row on
-  // the banded systems)
-  double s = 0.0, t = 0.0;
-  const int e = M.ptr[row + 1];
-  int k = M.ptr[row] + sub;
-  for (; k + LPR < e; k += 2 * LPR) {
-    const int c0 = M.col[k], c1 = M.col[k + LPR];
-    const double v0 = M.val[k], v1 = M.val[k + LPR];
-    s += v0 * x[c0], t += v1 * x[c1];
-  }
-  if (k < e) s += M.val[k] * x[M.col[k]];
-  return row_sum<LPR>(s + t);
 }
 // LPR lanes per CSR row: 16 for the banded systems, 4 when the rows hold a handful of
 // entries (DOCP / Prg_DID matrices: 1-3 per row)
@@ -3012,9 +2860,6 @@ __global__ void __launch_bounds__(256) k_clear(double *__restrict__ p, long long
 // posts along.  residual != 0 (the post behind a residual kernel): the residual maximum (word 61 of `flags`, k_residual)
 // goes along and is cleared once it is on its way - the next residual kernel starts from zero whatever ran in between;
 // any other post leaves the host's copy of that word as the last such post has written it.
-#define HPIN_DOUBLES 256
-#define HPIN_SEQ 200  // the double of hpin whose first four bytes hold the sequence number
-#define HPIN_ZM 208   // two doubles the HOST writes for a kernel to read: zeta and mu of a step of the Franke loop (k_fr_rhs)
 __global__ void __launch_bounds__(64) k_post_words(int *__restrict__ flags, const double *__restrict__ out, int n_out,
                                                    double *__restrict__ host, unsigned *__restrict__ dev_seq, int residual) {
   const int lane = threadIdx.x;
@@ -3073,11 +2918,6 @@ __global__ void k_mask_vector(int n, const signed char *__restrict__ keep, doubl
   if (i < n && !keep[i]) x[i] = 0.0;
 }
 
-struct CopyList {
-  const double *src[6];
-  double *dst[6];
-  int len[6];
-};
 __global__ void k_copy_vectors(CopyList L, int nvec) {
   for (int v = 0; v < nvec; v++) {
     const double *__restrict__ s = L.src[v];

@@ -1,0 +1,500 @@
+// The STAGED engine (HQPKKT_MODE_STAGED, staged.hip.h / staged_host.hip.h): its entry points of the C ABI, what the
+// other units call (factor, step, the dense dynamics' share of the residual products), and its debug entry points.
+#include "hqpkkt_handle.hpp"
+
+#include <algorithm>
+
+#include "staged.hip.h"
+#include "staged_host.hip.h"
+
+int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  if (!P.dense_dyn) return 0;
+  int nzmax = 1, npmax = 1;
+  for (int k = 0; k < P.K; k++) nzmax = std::max(nzmax, P.nk[k] + P.mk[k]), npmax = std::max(npmax, P.nk[k + 1]);
+  nzmax = std::max(nzmax, P.nk[P.K]);
+  if (P.sharded) {
+    // the rank's share of both products from its local blocks (staged.hip.h, DynLoc), summed over the ranks
+    const long long tot = d.dyn_sum_x2 + P.ndyn;
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_zero<<<nblk(tot), 256, 0, h->stream>>>(tot, d.dyn_sum.p));
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dynloc_ax<<<dim3(std::min((npmax + 3) / 4, 2048), P.K), 256, 0, h->stream>>>(d.dyn_loc.p, d.F.p, v.dx,
+                                                                                                           d.dyn_sum.p + d.dyn_sum_x2));
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dynloc_aty<<<dim3((nzmax + 255) / 256, P.K + 1), 256, 0, h->stream>>>(d.dyn_loc.p, d.F.p, v.dy, d.dyn_sum.p));
+    int e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, d.dyn_sum.p, tot, 1);
+    if (e) return e;
+    *x1 = d.dyn_sum.p, *x2 = d.dyn_sum.p + d.dyn_sum_x2, *ndyn = P.ndyn;
+    return 0;
+  }
+  const bool two_passes = false;  // (one pass over F for both products; the two-pass kernels stay for blocks the fused one does not take)
+  const int nbc = (nzmax + 255) / 256;
+  if (!two_passes && d.dyn_part.p && d.dyn_part_cols == nbc) {
+    // one pass over F for both products (k_st_dyn_both), then the row sums' column blocks
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_both<<<dim3(nbc, P.K + 1), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dx, v.dy, d.dyn_x1.p,
+                                                                                        d.dyn_part.p, nbc));
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_ax_finish<<<dim3((npmax + 255) / 256, P.K), 256, 0, h->stream>>>(d.dyn_desc.p, d.dyn_part.p, nbc,
+                                                                                                     v.dx, d.dyn_x2.p));
+  } else {
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_ax<<<dim3(std::min((npmax + 3) / 4, 2048), P.K), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dx,
+                                                                                                          d.dyn_x2.p));
+    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_aty<<<dim3((nzmax + 255) / 256, P.K + 1), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dy,
+                                                                                                   d.dyn_x1.p));
+  }
+  *x1 = d.dyn_x1.p, *x2 = d.dyn_x2.p, *ndyn = P.ndyn;
+  return 0;
+}
+static bool staged_is_sharded(hqpkkt_t *h) { return h->sd && h->sd->plan.sharded; }
+int staged_factor(hqpkkt_t *h, const Vecs &v) {
+  if (staged_is_sharded(h)) return staged_run_factor(h, v.z, v.w);  // an exchange per stage: not captured
+  return graphed(h, h->gfactor[0], [&]() { return staged_run_factor(h, v.z, v.w); });
+}
+int staged_step(hqpkkt_t *h, const Vecs &v, int which) {
+  if (staged_is_sharded(h)) return staged_run_step(h, v);  // exchanges inside the sweeps: not captured
+  return graphed(h, h->gstep[which][0], [&]() { return staged_run_step(h, v); });
+}
+// hqpkkt_analyze / hqpkkt_set_values of a handle in HQPKKT_MODE_STAGED: the CSR hand-over of the dynamics
+int staged_analyze_csr(hqpkkt_t *h, int n, int me, int m) { return staged_analyze(h, n, me, m); }
+int staged_set_values_csr(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx) { return staged_set_values(h, Qx, Ax, Cx); }
+void staged_release(StagedDev *sd, bool destroy) {
+  if (!sd) return;
+  sd->release();
+  if (destroy) delete sd;
+}
+
+// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 34); the handle is in HQPKKT_MODE_STAGED and analysed
+int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
+  if (!h->sd) return HQPKKT_E_INTERN;
+  const kktdev::StagedPlan &P = h->sd->plan;
+  switch (what) {
+    case 20: out = P.nk; break;  // the plan
+    case 21: out = P.mk; break;
+    case 22: out = P.nmk; break;
+    case 23: out = P.eq_ptr; break;
+    case 24: out = P.eq_rows; break;
+    case 25: out = P.fix_rows; break;
+    case 26: out = P.cap; break;
+    case 27: out = P.xcut; break;  // over several ranks: column cuts, (K+1) x (ranks+1)
+    case 33:  // over several ranks: the blocks of G_xx, 10 ints each: stage, block row, block column, r0, r1, c0,
+              // c1, owner, computed in the owner's own rows (1) or transposed (0), offset inside the owner's slot
+      for (int k = 0; k < P.K && !P.xrect_ptr.empty(); k++)
+        for (int q = P.xrect_ptr[k]; q < P.xrect_ptr[k + 1]; q++) {
+          const kktdev::StagedPlan::XRect &x = P.xrects[q];
+          for (int val : {k, x.a, x.b, x.r0, x.r1, x.c0, x.c1, x.owner, x.mine_rows ? 1 : 0, (int)x.off}) out.push_back(val);
+        }
+      break;
+    case 34:  // ... and this rank's tiles of its blocks' products: per stage a count, then the tiles (tile row in the strip << 16 | tile column)
+      for (int k = 0; k < P.K && !P.gtile_ptr.empty(); k++) {
+        out.push_back(P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
+        for (int q = P.gtile_ptr[k]; q < P.gtile_ptr[k + 1]; q++) out.push_back(P.gtile[q]);
+      }
+      break;
+    case 28:  // [0] stages whose blocked elimination ran, [1] those of them that fell back to the one-workgroup form
+      out.assign(2, 0);
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out.data(), h->flags.p + 6, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return HQPKKT_E_DEVICE;
+      break;
+    case 32:  // free initial state of many components: [0] blocked inverse ran, [1] fell back to the LU factors
+      // ... [2] the pivot block that gave up (1-based, 0: none), [3], [4] |K_jj|, |K_jj^-1| of that block, [5] max |K0 K0^-1 - I|
+      // (floats as their bit patterns; the words of the blocked sweep's scratch area as the LAST factorisation left them)
+      out.assign(6, 0);
+      if (hipDeviceSynchronize() != hipSuccess ||
+          hipMemcpy(out.data(), h->flags.p + stg::X0_BLOCKED, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return HQPKKT_E_DEVICE;
+      if (P.big0 &&
+          hipMemcpy(out.data() + 2, stg::big_scratch(h->sd->misc.p + P.oScr, P.q0max).flags + 1, sizeof(int) * 4,
+                    hipMemcpyDeviceToHost) != hipSuccess)
+        return HQPKKT_E_DEVICE;
+      break;
+    default: return HQPKKT_E_RANGE;
+  }
+  return 0;
+}
+
+extern "C" {
+
+int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (!h->sd) h->sd = new (std::nothrow) StagedDev;
+    if (!h->sd) return HQPKKT_E_MEM;
+    kktdev::StagedPlan &P = h->sd->plan;
+    P.given_nx.clear(), P.given_nu.clear();
+    if (K <= 0) return 0;  // back to detection from the staircase of A
+    if (!nx || !nu) return HQPKKT_E_NULL;
+    for (int k = 0; k <= K; k++)
+      if (nx[k] < 1) return HQPKKT_E_RANGE;
+    for (int k = 0; k < K; k++)
+      if (nu[k] < 0) return HQPKKT_E_RANGE;
+    P.given_nx.assign(nx, nx + K + 1), P.given_nu.assign(nu, nu + K);
+    return 0;
+  });
+}
+
+int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int n_total, int me_rest, int m, const int *Qp,
+                          const int *Qi, const int *Ep, const int *Ei, const int *Cp, const int *Ci) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    int e = hqpkkt_set_stages(h, K, nx, nu);
+    if (e) return e;
+    if (K < 1) return HQPKKT_E_RANGE;
+    long long n = nx[K], ndyn = 0;
+    for (int k = 0; k < K; k++) n += (long long)nx[k] + nu[k], ndyn += nx[k + 1];
+    if (n > 0x7fffffffLL || ndyn + me_rest > 0x7fffffffLL || me_rest < 0 || m < 0) return HQPKKT_E_RANGE;
+    if (n != n_total) return HQPKKT_E_SIZES;  // Q, E, C were built for another number of variables
+    if ((n > 0 && (!Qp || (Qp[n] > 0 && !Qi))) || (me_rest > 0 && (!Ep || (Ep[me_rest] > 0 && !Ei))) ||
+        (m > 0 && (!Cp || (Cp[m] > 0 && !Ci))))
+      return HQPKKT_E_NULL;
+    if (h->uploaded) {
+      (void)hipSetDevice(h->opts.device);
+      (void)hipStreamSynchronize(h->stream);
+      h->release_device();
+    }
+    h->analyzed = false;
+    h->ip_hot_valid = h->fr_hot_valid = false;
+    const int me = (int)ndyn + me_rest;
+    h->pQp.assign(Qp, Qp + n + 1), h->pQi.assign(Qi, Qi + Qp[n]);
+    h->pAp.assign((size_t)me + 1, 0);  // the dynamics rows are empty: they come as dense blocks
+    for (int i = 0; i <= me_rest; i++) h->pAp[ndyn + i] = me_rest ? Ep[i] : 0;
+    h->pAi.clear();
+    if (me_rest && Ep[me_rest]) h->pAi.assign(Ei, Ei + Ep[me_rest]);
+    h->pCp.clear(), h->pCi.clear();
+    if (m) h->pCp.assign(Cp, Cp + m + 1), h->pCi.assign(Ci, Ci + Cp[m]);
+    h->zd_decided = true, h->zd_weak = false;
+    return staged_analyze(h, (int)n, me, m, true);
+  });
+}
+
+int hqpkkt_set_values_staged(hqpkkt_t *h, const double *Qx, const double *const *F, const long long *ldF,
+                             const double *Ex, const double *Cx) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd) return HQPKKT_E_INTERN;
+    Analysis &an = h->an;
+    if ((an.nq && !Qx) || (an.na && !Ex) || (an.nc && !Cx) || (F && !ldF)) return HQPKKT_E_NULL;
+    if (!h->sd->plan.dense_dyn) return HQPKKT_E_INTERN;  // analysed for the CSR hand-over
+    if (!F) {  // the blocks came one by one (hqpkkt_set_stage_block): every one of them, since the analysis
+      const std::vector<char> &bs = h->sd->blocks_set;
+      if ((int)bs.size() != h->sd->plan.K || std::find(bs.begin(), bs.end(), 0) != bs.end()) return HQPKKT_E_INTERN;
+    }
+    return staged_set_values(h, Qx, Ex, Cx, F, ldF, true);
+  });
+}
+
+int hqpkkt_detect_stages(int n, int rows, const int *row_len, const int *last_col, const int *prev_col, int cap, int *K,
+                         int *nx, int *nu, int *dyn_rows) {
+  return guarded([&]() -> int {
+    if (!row_len || !last_col || !prev_col || !K || !nx || !nu || !dyn_rows) return HQPKKT_E_NULL;
+    if (n < 1 || rows < 1) return HQPKKT_E_FORMAT;
+    std::vector<int> st, ct, fc;
+    int nd = 0;
+    if (kktdev::stages_from_staircase(n, rows, row_len, last_col, prev_col, st, ct, fc, nd)) return HQPKKT_E_FORMAT;
+    const int k = (int)ct.size();
+    if (k > cap) return HQPKKT_E_SIZES;
+    *K = k, *dyn_rows = nd;
+    for (int i = 0; i <= k; i++) nx[i] = st[i];
+    for (int i = 0; i < k; i++) nu[i] = ct[i];
+    return 0;
+  });
+}
+
+int hqpkkt_stage_staging(hqpkkt_t *h, int which, double **buf, long long *elems) {
+  return guarded([&]() -> int {
+    if (!h || !buf || !elems || which < 0 || which > 1) return HQPKKT_E_NULL;
+    if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd || !h->sd->plan.dense_dyn) return HQPKKT_E_INTERN;
+    int e = ensure_device(h);
+    if (e) return e;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    long long mx = 1;
+    for (int k = 0; k < P.K; k++) mx = std::max(mx, (long long)P.nk[k + 1] * (P.nk[k] + P.mk[k]));
+    for (int b = 0; b < 2; b++)
+      if (!d.hblk[b] || d.hblk_elems < mx) {
+        if (d.hblk[b]) (void)hipHostFree(d.hblk[b]), d.hblk[b] = nullptr;
+        HIPCHK(hipHostMalloc((void **)&d.hblk[b], sizeof(double) * (size_t)mx, hipHostMallocDefault));
+      }
+    d.hblk_elems = mx;
+    // the copy that last read this buffer must be over before the caller refills it
+    if (d.hblk_ev[which]) HIPCHK(hipEventSynchronize(d.hblk_ev[which]));
+    *buf = d.hblk[which], *elems = mx;
+    return 0;
+  });
+}
+
+int hqpkkt_set_stage_block(hqpkkt_t *h, int k, const double *F, long long ldF) {
+  return guarded([&]() -> int {
+    if (!h || !F) return HQPKKT_E_NULL;
+    if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd || !h->sd->plan.dense_dyn) return HQPKKT_E_INTERN;
+    int e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    if (k < 0 || k >= P.K) return HQPKKT_E_RANGE;
+    const int nz = P.nk[k] + P.mk[k];
+    if (ldF < nz) return HQPKKT_E_SIZES;
+    HIPCHK(hipSetDevice(h->opts.device));
+    const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if ((e = staged_copy_block(h, k, F, ldF, kind))) return e;
+    for (int b = 0; b < 2; b++)
+      if (F == d.hblk[b]) {  // the library's own staging buffer: remember when it is free again
+        if (!d.hblk_ev[b]) HIPCHK(hipEventCreateWithFlags(&d.hblk_ev[b], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(d.hblk_ev[b], h->stream));
+      }
+    if ((int)d.blocks_set.size() != P.K) d.blocks_set.assign(P.K, 0);
+    d.blocks_set[k] = 1;
+    h->factored = false;
+    return 0;
+  });
+}
+
+// STAGED: rank and number of carried rows of every stage in the last factorisation
+// (2 ints per stage, K+1 stages); tests only
+int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap) {
+  if (!h || !out) return HQPKKT_E_NULL;
+  if (!h->sd || !h->uploaded) return HQPKKT_E_INTERN;
+  HIPCHK(hipSetDevice(h->opts.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const kktdev::StagedPlan &P = h->sd->plan;
+  for (int k = 0; k <= P.K && 2 * k + 1 < cap; k++)
+    HIPCHK(hipMemcpy(out + 2 * k, h->sd->dyn.p + P.dyn_off[k], 2 * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Micro-benchmark and self-check of the dense fp64 product the STAGED engine is made of
+// (k_dgemm_tn): C = A'B (+ lower / mirror) on pseudo-random operands, `reps` timed launches;
+// *ms = average device time per launch, *max_err = max |C - exact| over 4096 sampled entries
+// relative to sum |a||b|.  Used by tests/ and bench.py (roofline of the kernel on its own).
+namespace {
+__global__ void k_fill_rand(double *p, long long n, unsigned long long seed) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned long long x = (unsigned long long)i * 0x9E3779B97F4A7C15ULL + seed;
+  x ^= x >> 30, x *= 0xBF58476D1CE4E5B9ULL, x ^= x >> 27, x *= 0x94D049BB133111EBULL, x ^= x >> 31;
+  p[i] = (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+}
+__global__ void k_gemm_check(stg::GemmArgs g, int nsample, double *err) {
+  const int sidx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (sidx >= nsample) return;
+  unsigned long long x = (unsigned long long)sidx * 0x9E3779B97F4A7C15ULL + 12345;
+  x ^= x >> 29, x *= 0xBF58476D1CE4E5B9ULL, x ^= x >> 32;
+  int i = (int)(x % (unsigned long long)g.M), j = (int)((x >> 20) % (unsigned long long)g.N);
+  // lower: only i >= j is computed; mirror: C[j][i] is a copy of C[i][j] (the product is
+  // symmetric in the engine; here the operands are not, so the copy is what gets checked)
+  int ci = i, cj = j;
+  if (g.lower && i < j) {
+    const int t = i;
+    i = j, j = t;
+    if (!g.mirror) ci = i, cj = j;
+  }
+  double s = 0.0, sa = 0.0;
+  for (int k = 0; k < g.K; k++) {
+    const double a = g.A[(long long)k * g.lda + i], b = g.B[(long long)k * g.ldb + j];
+    s += a * b, sa += fabs(a * b);
+  }
+  const double e = fabs(g.C[(long long)ci * g.ldc + cj] - g.alpha * s) / (sa + 1e-300);
+  atomic_max_pos((unsigned long long *)err, e);
+}
+}  // namespace
+int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
+  if (M <= 0 || N <= 0 || K < 0 || reps <= 0) return HQPKKT_E_RANGE;
+  if (lower && M < N) return HQPKKT_E_RANGE;  // (M > N: the column strip of a lower triangle)
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  const long long lda = (M + 7) / 8 * 8, ldb = (N + 7) / 8 * 8, ldc = ldb;
+  double *A = nullptr, *B = nullptr, *Cm = nullptr, *err = nullptr, *zr = nullptr;
+  stg::SkUnit *sk_table_dev = nullptr;
+  auto fin = [&](int rc) {
+    (void)hipFree(A), (void)hipFree(B), (void)hipFree(Cm), (void)hipFree(err), (void)hipFree(zr), (void)hipFree(sk_table_dev);
+    return rc;
+  };
+  const size_t kk = K > 0 ? K : 1;
+  if (hipMalloc((void **)&A, sizeof(double) * kk * lda) != hipSuccess || hipMalloc((void **)&B, sizeof(double) * kk * ldb) != hipSuccess ||
+      hipMalloc((void **)&Cm, sizeof(double) * (size_t)std::max(M, N) * ldc) != hipSuccess || hipMalloc((void **)&err, 8) != hipSuccess)
+    return fin(HQPKKT_E_MEM);
+  k_fill_rand<<<nblk((long long)kk * lda), 256>>>(A, (long long)kk * lda, 1);
+  k_fill_rand<<<nblk((long long)kk * ldb), 256>>>(B, (long long)kk * ldb, 2);
+  (void)hipMemset(err, 0, 8);
+  (void)hipMemset(Cm, 0, sizeof(double) * (size_t)std::max(M, N) * ldc);
+  stg::GemmArgs g{A, lda, B, ldb, nullptr, 0, Cm, ldc, M, N, K, 1.0, 0.0, lower, mirror, nullptr, nullptr};
+  const int variant = stg::gemm_variant_from_env();
+  if (variant != stg::GEMM_REG4) {
+    if (hipMalloc((void **)&zr, sizeof(double) * 256) != hipSuccess) return fin(HQPKKT_E_MEM);
+    (void)hipMemset(zr, 0, sizeof(double) * 256);
+    g.zeros = zr;
+  }
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  const int skg = stg::gemm_wgs_per_cu(variant) * cus;
+  // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
+  const bool frac = !getenv("HQPKKT_DGEMM_FORCE_SPLIT") && stg::gemm_use_frac(M, N, K, lower, skg);
+  const bool use_sk = frac || stg::gemm_use_split(M, N, K, lower, skg) || getenv("HQPKKT_DGEMM_FORCE_SPLIT");
+  const bool big = use_sk || stg::gemm_big_tiles(M, N, lower, K);
+  const int b = big ? 128 : 64;
+  const long long tiles = stg::gemm_tiles(M, N, b, lower);
+  (void)stg::gemm_set_attributes();
+  // stream-K form where the engine would use it (staged_host.hip.h, st_gemm)
+  double *skws = nullptr;
+  unsigned *skcnt = nullptr;
+  if (use_sk) {
+    if (hipMalloc((void **)&skws, sizeof(double) * (size_t)std::max<long long>(16 * tiles + 8, 2LL * skg + 2) * 128 * 128) != hipSuccess ||
+        hipMalloc((void **)&skcnt, sizeof(unsigned) * (tiles + 4)) != hipSuccess) {
+      (void)hipFree(skws), (void)hipFree(skcnt);
+      return fin(HQPKKT_E_MEM);
+    }
+  }
+  // (the cut form by a table with unequal shares for the two workgroups of a CU: gemm_split_table; HQPKKT_SK_TABLE=0: equal shares)
+  stg::SplitTable sk_tab;
+  if (use_sk && !frac && stg::gemm_sk_table_from_env() && stg::gemm_split_table(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg, sk_tab) &&
+      sk_tab.pieces <= 16 * tiles + 8) {
+    const size_t nu = sk_tab.units.size();
+    if (hipMalloc((void **)&sk_table_dev, sizeof(stg::SkUnit) * nu) != hipSuccess ||
+        hipMemcpy(sk_table_dev, sk_tab.units.data(), sizeof(stg::SkUnit) * nu, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(skws), (void)hipFree(skcnt);
+      return fin(HQPKKT_E_MEM);
+    }
+  }
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0), (void)hipEventCreate(&e1);
+  for (int r = -1; r < reps; r++) {
+    if (r == 0) (void)hipEventRecord(e0, 0);
+    if (use_sk) {
+      (void)hipMemsetAsync(skcnt, 0, sizeof(unsigned) * (tiles + 4), 0);
+      stg::SplitPlan skk = frac ? stg::gemm_split_plan_frac(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg)
+                                : stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
+      skk.ws = skws, skk.cnt = skcnt;
+      if (sk_table_dev) skk.table = sk_table_dev, skk.stride = sk_tab.stride;
+      stg::gemm_launch_split(variant, skg, 0, g, skk);
+    } else if (big)
+      stg::gemm_launch_plain(variant, (unsigned)tiles, 0, g, cus);
+    else if (stg::gemm_tiles_6432(M, N, K, lower, mirror, cus))  // (as st_gemm chooses)
+      stg::k_dgemm_tn<64, 32><<<(unsigned)(((M + 63) / 64) * (long long)((N + 31) / 32)), 256, stg::gemm_lds_bytes(64, 32)>>>(g);
+    else
+      stg::k_dgemm_tn<64, 64><<<(unsigned)tiles, 256, stg::gemm_lds_bytes(64, 64)>>>(g);
+  }
+  (void)hipEventRecord(e1, 0);
+  hipError_t se = hipDeviceSynchronize();
+  (void)hipFree(skws), (void)hipFree(skcnt);
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
+  if (se != hipSuccess) return fin(HQPKKT_E_DEVICE);
+  if (getenv("HQPKKT_DGEMM_STAMPS") && use_sk && !frac) {
+    // the split form with time stamps: per workgroup its start and, per unit, the end of the k loop, of the
+    // parking / summing of partial tiles and of the epilogue (us after the first start)
+    unsigned long long *st = nullptr;
+    double *ws2 = nullptr;
+    unsigned *cnt2 = nullptr;
+    if (hipMalloc((void **)&st, sizeof(unsigned long long) * 32 * skg) == hipSuccess &&
+        hipMalloc((void **)&ws2, sizeof(double) * (size_t)(16 * tiles + 8) * 128 * 128) == hipSuccess &&
+        hipMalloc((void **)&cnt2, sizeof(unsigned) * (tiles + 4)) == hipSuccess) {
+      (void)hipMemset(st, 0, sizeof(unsigned long long) * 32 * skg);
+      (void)hipMemset(cnt2, 0, sizeof(unsigned) * (tiles + 4));
+      stg::GemmArgs gs = g;
+      gs.stamps = st;
+      stg::SplitPlan skk = stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
+      skk.ws = ws2, skk.cnt = cnt2;
+      if (sk_table_dev) skk.table = sk_table_dev, skk.stride = sk_tab.stride;
+      stg::gemm_launch_split(variant, skg, 0, gs, skk);
+      std::vector<unsigned long long> hs(32 * (size_t)skg);
+      if (hipMemcpy(hs.data(), st, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) == hipSuccess) {
+        unsigned long long tmin = ~0ULL;
+        for (int w = 0; w < skg; w++) tmin = std::min(tmin, hs[32 * (size_t)w]);
+        if (sk_table_dev)
+          fprintf(stderr, "table plan: %d / %d whole tiles per first / second workgroup of a CU, %lld parked pieces", sk_tab.nA, sk_tab.nB, sk_tab.pieces);
+        else {
+          fprintf(stderr, "split plan: %d whole tiles", skk.whole);
+          for (int q = 0; q < skk.nphase; q++) fprintf(stderr, ", %d tiles x %d pieces", skk.count[q], skk.split[q]);
+        }
+        fprintf(stderr, "; stamps of every %dth workgroup (us): start | per unit: k loop end, parked / summed, epilogue end\n", std::max(1, skg / 32));
+        const int nr = sk_table_dev ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
+        for (int w = 0; w < skg; w += std::max(1, skg / 32)) {
+          fprintf(stderr, "  wg %4d: %7.2f |", w, (hs[32 * (size_t)w] - tmin) * 0.01);
+          for (int r = 0; r < nr; r++) {
+            for (int c = 1; c <= 3; c++) {
+              const unsigned long long x = hs[32 * (size_t)w + 3 * r + c];
+              if (x) fprintf(stderr, " %8.2f", (x - tmin) * 0.01); else fprintf(stderr, "        -");
+            }
+            fprintf(stderr, " |");
+          }
+          fprintf(stderr, "\n");
+        }
+        // the end of every workgroup's last unit, per class (first / second half of the launch)
+        for (int c = 0; c < 2; c++) {
+          double lo = 1e30, hi = 0.0, sum = 0.0;
+          int n = 0;
+          for (int w = c * skg / 2; w < (c + 1) * skg / 2; w++) {
+            unsigned long long last = 0;
+            for (int r = 0; r < 10; r++) last = std::max(last, hs[32 * (size_t)w + 3 * r + 3]);
+            if (!last) continue;
+            const double e = (last - tmin) * 0.01;
+            lo = std::min(lo, e), hi = std::max(hi, e), sum += e, n++;
+          }
+          if (n) fprintf(stderr, "  class %c (blockIdx %s grid / 2): last epilogue ends at %.1f ... %.1f us, mean %.1f\n", c ? 'B' : 'A', c ? ">=" : "<", lo, hi, sum / n);
+        }
+      }
+    }
+    (void)hipFree(st), (void)hipFree(ws2), (void)hipFree(cnt2);
+  }
+  if (getenv("HQPKKT_DGEMM_STAMPS") && !use_sk && big) {
+    // one more launch with time stamps per workgroup (100 MHz constant clock): when it started, when its k loop
+    // ended, when its epilogue ended - relative to the first start; printed as a histogram over the workgroups
+    unsigned long long *st = nullptr;
+    if (hipMalloc((void **)&st, sizeof(unsigned long long) * 4 * tiles) == hipSuccess) {
+      stg::GemmArgs gs = g;
+      gs.stamps = st;
+      stg::gemm_launch_plain(variant, (unsigned)tiles, 0, gs);
+      std::vector<unsigned long long> hs(4 * tiles);
+      if (hipMemcpy(hs.data(), st, sizeof(unsigned long long) * 4 * tiles, hipMemcpyDeviceToHost) == hipSuccess) {
+        unsigned long long tmin = ~0ULL;
+        for (long long t = 0; t < tiles; t++) tmin = std::min(tmin, hs[4 * t]);
+        // workgroups in the order of their start
+        std::vector<long long> ord(tiles);
+        for (long long t = 0; t < tiles; t++) ord[t] = t;
+        std::sort(ord.begin(), ord.end(), [&](long long a, long long b) { return hs[4 * a] < hs[4 * b]; });
+        fprintf(stderr, "stamps (us after the first start; %lld workgroups, every %lldth in start order): start, k loop end, epilogue end, xcc, blockIdx\n", tiles,
+                std::max<long long>(1, tiles / 64));
+        for (long long q = 0; q < tiles; q += std::max<long long>(1, tiles / 64)) {
+          const long long t = ord[q];
+          fprintf(stderr, "  %8.2f %8.2f %8.2f  xcc %llu  wg %lld\n", (hs[4 * t] - tmin) * 0.01, (hs[4 * t + 2] - tmin) * 0.01, (hs[4 * t + 3] - tmin) * 0.01,
+                  hs[4 * t + 1], t);
+        }
+      }
+      (void)hipFree(st);
+    }
+  }
+  k_gemm_check<<<16, 256>>>(g, 4096, err);
+  double he = 0.0;
+  if (hipMemcpy(&he, err, 8, hipMemcpyDeviceToHost) != hipSuccess) return fin(HQPKKT_E_DEVICE);
+  if (ms) *ms = t / reps;
+  if (max_err) *max_err = he;
+  return fin(0);
+}
+
+int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {
+  stg::SplitTable t;
+  if (!stg::gemm_split_table(tiles, nslab, grid, t)) return 0;
+  if (pieces) *pieces = t.pieces;
+  if (whole_a) *whole_a = t.nA;
+  if (whole_b) *whole_b = t.nB;
+  if (units) {
+    if ((long long)t.units.size() * 6 > cap_ints) return 0;
+    for (size_t i = 0; i < t.units.size(); i++) {
+      const stg::SkUnit &u = t.units[i];
+      int *o = units + 6 * i;
+      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
+    }
+  }
+  return t.stride;
+}
+
+#ifdef HQPKKT_STAMPS
+int hqpkkt_debug_gj_stamps(int *out) {
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(stg::g_gj_stamps), sizeof(int) * 32));
+  return 0;
+}
+#endif
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 #include "hqpkkt_handle.hpp"
 
 char g_last_hip_error[512] = "";
+std::atomic<long long> g_live_bufs[2];
 
 namespace kktdev {
 // MFMA layout self-test: C(16x16) = A(16x16) * B(16x16), all row-major
@@ -57,18 +58,8 @@ int hqpkkt_destroy(hqpkkt_t *h) {
   if (h->own_stream) {
     (void)hipSetDevice(h->opts.device);
     (void)hipStreamSynchronize(h->own_stream);
-    h->release_device();
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipEventDestroy(h->evs0);
-    (void)hipEventDestroy(h->evs1);
-    (void)hipEventDestroy(h->evt0);
-    (void)hipEventDestroy(h->evt1);
-    h->prof.destroy();
-    (void)hipStreamDestroy(h->own_stream);
   }
-  staged_release(h->sd, true);
-  delete h;
+  delete h;  // (the members free what they own: buffers and graphs first, the stream last)
   return 0;
 }
 
@@ -166,24 +157,24 @@ int hqpkkt_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
     HIPCHK(hipSetDevice(h->opts.device));
     hipMemcpyKind kind =
         h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (an.nq) HIPCHK(hipMemcpyAsync(h->vals.p, Qx, sizeof(double) * an.nq, kind, h->stream));
-    if (an.na) HIPCHK(hipMemcpyAsync(h->vals.p + an.nq, Ax, sizeof(double) * an.na, kind, h->stream));
+    if (an.nq) HIPCHK(hipMemcpyAsync(h->td.vals.p, Qx, sizeof(double) * an.nq, kind, h->stream));
+    if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, h->stream));
     if (an.nc)
-      HIPCHK(hipMemcpyAsync(h->vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, h->stream));
-    for (CsrBuf *c : {&h->Qf, &h->A, &h->AT, &h->C, &h->CT})
+      HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, h->stream));
+    for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
       if (c->src.count)
-        k_gather_values<<<nblk((long long)c->src.count), 256, 0, h->stream>>>((int)c->src.count, c->src.p, h->vals.p, c->val.p);
+        k_gather_values<<<nblk((long long)c->src.count), 256, 0, h->stream>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
     if (h->opts.zd_policy < 0 && h->zd_used != 0) {
       // zd_policy -1: an x whose Hessian diagonal is weak against its coupling to an equality needs the
       // 2x2 pivot with that equality's multiplier inside its own pivot block.  Tested on EVERY update (the
       // values of an SQP run change: an identity Hessian may turn weak later), on the device: one pass
       // over Q's diagonal and the columns of A, one word read back.
       h->zd_decided = true;
-      int *flag = h->flags.p + 100;
+      int *flag = h->td.flags.p + 100;
       HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
       if (an.n > 0 && an.me > 0)
-        k_zd_weak<<<nblk(an.n), 256, 0, h->stream>>>(an.n, h->Qf.dev(), h->AT.dev(), flag);
-      int *hs = (int *)h->hpin;
+        k_zd_weak<<<nblk(an.n), 256, 0, h->stream>>>(an.n, h->td.Qf.dev(), h->td.AT.dev(), flag);
+      int *hs = (int *)h->kept.hpin.p;
       HIPCHK(hipMemcpyAsync(hs, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
       h->zd_weak = hs[0] != 0;
@@ -299,11 +290,11 @@ static int factor_once(hqpkkt_t *h, const double *z, const double *w) {
     // packed by the CPU, then ONE graph: the copy out of the pinned buffer, the factorisation, the posted status words
     const size_t used = stage_pack(h, z, w, nullptr, nullptr, nullptr, nullptr);
     const int m = h->an.m;
-    v.z = h->vin.p, v.w = h->vin.p + m;
+    v.z = h->td.vin.p, v.w = h->td.vin.p + m;
     h->factored = false;
     if ((e = graphed(h, h->ghost_factor, [&]() {
            if (used) {
-             CopyList L{{h->hstage_dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->vin.p, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
+             CopyList L{{h->td.hstage.dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->td.vin.p, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
              k_copy_vectors<<<copy_blocks(L), 256, 0, h->stream>>>(L, 1);
            }
            const int e2 = do_factor(h, v);
@@ -330,7 +321,7 @@ static int factor_once(hqpkkt_t *h, const double *z, const double *w) {
     return 0;
   }
   }
-  int *hs = (int *)h->hpin;
+  int *hs = (int *)h->kept.hpin.p;
   {  // the status words, posted (k_post_words) and waited for
     int ep = hostg ? 0 : post_words(h, nullptr, 0);
     if (ep || (ep = post_wait(h))) return ep;
@@ -383,8 +374,8 @@ static int step_once(hqpkkt_t *h, const double *z, const double *w, const double
   if ((e = do_step(h, v, 0))) return e;
   HIPCHK(hipEventRecord(h->evs1, h->stream));
   if ((e = stage_out(h, v, dx, dy, dz, dw))) return e;
-  int *hs = (int *)h->hpin;  // the give-up word of the polled sweeps comes back with the result
-  HIPCHK(hipMemcpyAsync(hs + XW_GAVE_UP, h->flags.p + XW_GAVE_UP, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  int *hs = (int *)h->kept.hpin.p;  // the give-up word of the polled sweeps comes back with the result
+  HIPCHK(hipMemcpyAsync(hs + XW_GAVE_UP, h->td.flags.p + XW_GAVE_UP, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (poll_fallback(h, hs)) return HQPKKT_E_POLL;
   unstage(h, dx, dy, dz, dw);
@@ -466,7 +457,7 @@ static int solve_once(hqpkkt_t *h, const double *z, const double *w, const doubl
     return e;
   }
   {
-    bool all = host_graphs_ok(h) && !direct_vectors(h) && h->hstage_out;
+    bool all = host_graphs_ok(h) && !direct_vectors(h) && h->td.hstage_out;
     for (int k = 0; k < 10; k++) all = all && (sp[k] != nullptr || sl[k] == 0);
     if (all) {
       // packed by the CPU, then ONE graph: the copy out of the pinned buffer, the sweeps, the residual, the result into
@@ -474,22 +465,22 @@ static int solve_once(hqpkkt_t *h, const double *z, const double *w, const doubl
       const auto wall0 = std::chrono::steady_clock::now();
       const size_t used = stage_pack(h, z, w, r1, r2, r3, r4);
       const int n = h->an.n, me = h->an.me, m = h->an.m;
-      double *b = h->vin.p;
+      double *b = h->td.vin.p;
       v.z = b, v.w = b + m, v.r1 = b + 2 * (size_t)m, v.r2 = v.r1 + n, v.r3 = v.r2 + me, v.r4 = v.r3 + m;
       stage_out_ptrs(h, v);
       if ((e = graphed(h, h->ghost_step, [&]() {
              if (used) {
-               CopyList L{{h->hstage_dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {b, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
+               CopyList L{{h->td.hstage.dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {b, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
                k_copy_vectors<<<copy_blocks(L), 256, 0, s>>>(L, 1);
              }
              int e2 = do_step(h, v, 0);
              if (e2 || (e2 = residual_launch(h, v))) return e2;
-             CopyList O{{v.dx, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->hstage_dev + h->hstage_in, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)h->hstage_out, 0, 0, 0, 0, 0}};
+             CopyList O{{v.dx, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->td.hstage.dev + h->td.hstage_in, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)h->td.hstage_out, 0, 0, 0, 0, 0}};
              k_copy_vectors<<<copy_blocks(O), 256, 0, s>>>(O, 1);
              return post_words(h, nullptr, 0, true);
            })))
         return e;
-      h->out_pending = h->hstage + h->hstage_in, h->out_by_kernel = true;
+      h->out_pending = h->td.hstage.p + h->td.hstage_in, h->out_by_kernel = true;
       double res = 0.0;
       if ((e = post_wait(h)) || (e = collect_residual(h, &res))) return e;
       h->host_graph_call = true;
@@ -526,8 +517,8 @@ int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const dou
   double res_acc_prev = HUGE_VAL;  // ... and before the last round
   // correction solve: rhs = residual vectors, result = vcor
   Vecs c = v;
-  c.r1 = h->vres.p, c.r2 = c.r1 + n, c.r3 = c.r2 + me, c.r4 = c.r3 + m;
-  c.dx = h->vcor.p, c.dy = c.dx + n, c.dz = c.dy + me, c.dw = c.dz + m;
+  c.r1 = h->td.vres.p, c.r2 = c.r1 + n, c.r3 = c.r2 + me, c.r4 = c.r3 + m;
+  c.dx = h->td.vcor.p, c.dy = c.dx + n, c.dz = c.dy + me, c.dw = c.dz + m;
   const int ntot = n + me + 2 * m;
   int rounds = 0;
   // (the reference makes at most five rounds, hqp/Hqp_IpMatrix.C:84: its factors come from a pivot search over the whole
@@ -593,8 +584,8 @@ int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const dou
   if (h->soft_tiny && !(res_acc <= 1e-4)) {
     double rnorm = 0.0;
     Vecs vz = v;
-    vz.dx = h->vcor.p, vz.dy = vz.dx + n, vz.dz = vz.dy + me, vz.dw = vz.dz + m;
-    HIPCHK(hipMemsetAsync(h->vcor.p, 0, sizeof(double) * (size_t)ntot, s));
+    vz.dx = h->td.vcor.p, vz.dy = vz.dx + n, vz.dz = vz.dy + me, vz.dw = vz.dz + m;
+    HIPCHK(hipMemsetAsync(h->td.vcor.p, 0, sizeof(double) * (size_t)ntot, s));
     if ((e = run_residual(h, vz, &rnorm))) return e;
     if (!(res_acc < rnorm)) return HQPKKT_E_SING;
   }
@@ -664,12 +655,9 @@ int hqpkkt_values_staging(hqpkkt_t *h, double **Qx, double **Ax, double **Cx) {
   if (e) return e;
   const Analysis &an = h->an;
   const size_t need = (size_t)an.nq + an.na + an.nc + 1;
-  if (h->hvals && h->hvals_elems != need) (void)hipHostFree(h->hvals), h->hvals = nullptr;  // (analysed again for another pattern)
-  if (!h->hvals) {
-    HIPCHK(hipHostMalloc((void **)&h->hvals, sizeof(double) * need, hipHostMallocDefault));
-    h->hvals_elems = need;
-  }
-  *Qx = h->hvals, *Ax = h->hvals + an.nq, *Cx = h->hvals + an.nq + an.na;
+  PinnedBuf<double> &hv = h->kept.hvals;
+  if (hv.count != need) HIPCHK(hv.alloc(need, hipHostMallocDefault));  // (none yet, or analysed again for another pattern)
+  *Qx = hv.p, *Ax = hv.p + an.nq, *Cx = hv.p + an.nq + an.na;
   return 0;
 }
 
@@ -713,7 +701,7 @@ const char *hqpkkt_strerror(int status) {
 
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len) {
   if (!h || !len) return HQPKKT_E_NULL;
-  if (!h->analyzed) return HQPKKT_E_INTERN;
+  if (!h->analyzed && what != 40) return HQPKKT_E_INTERN;
   const Analysis &an = h->an;
   const std::vector<int> *v = nullptr;
   std::vector<int> tmp;
@@ -747,6 +735,10 @@ int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len) {
       tmp = {h->top_n, h->top_n ? h->top_lt : h->an.nlevels, (int)h->top_lds, h->top_ns, h->small_tree ? 1 : 0, h->tree_factor ? 1 : 0, h->top_split ? 1 : 0};
       v = &tmp;
       break;
+    case 40:  // live device / pinned host buffers of the process (DBuf / PinnedBuf, over all handles)
+      tmp = {(int)g_live_bufs[0].load(), (int)g_live_bufs[1].load()};
+      v = &tmp;
+      break;
     default: return HQPKKT_E_RANGE;
   }
   *len = (long long)v->size();
@@ -757,7 +749,7 @@ int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len) {
 #ifdef HQPKKT_STAMPS
 extern "C" int hqpkkt_debug_stamps(hqpkkt_t *h, int *out) {
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, h->flags.p, sizeof(int) * 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, h->td.flags.p, sizeof(int) * 64, hipMemcpyDeviceToHost));
   return 0;
 }
 #endif
@@ -771,10 +763,10 @@ int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long ca
   const double *src = nullptr;
   long long n = 0;
   switch (what) {
-    case 0: src = h->panel.p + an.panel_off[node], n = (p + b) * p; break;
-    case 1: src = h->linv.p + an.linv_off[node], n = p * p; break;
-    case 2: src = h->xar.p + an.x_off[node], n = b * p; break;
-    case 3: src = h->upd.p + an.upd_off[node], n = b * b; break;
+    case 0: src = h->td.panel.p + an.panel_off[node], n = (p + b) * p; break;
+    case 1: src = h->td.linv.p + an.linv_off[node], n = p * p; break;
+    case 2: src = h->td.xar.p + an.x_off[node], n = b * p; break;
+    case 3: src = h->td.upd.p + an.upd_off[node], n = b * b; break;
     default: return HQPKKT_E_RANGE;
   }
   *len = n;
@@ -784,8 +776,8 @@ int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long ca
   HIPCHK(hipStreamSynchronize(h->stream));
   if (what == 3 && h->tree_factor) {  // the block is in the exchange copy of the last factorisation (lower triangle; the rest idle)
     int ep = 0;
-    HIPCHK(hipMemcpy(&ep, h->tree_words.p + 1, sizeof(int), hipMemcpyDeviceToHost));
-    src = h->tree_u.p + (long long)(ep & 1) * an.upd_elems + an.upd_off[node];
+    HIPCHK(hipMemcpy(&ep, h->td.tree_words.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+    src = h->td.tree_u.p + (long long)(ep & 1) * an.upd_elems + an.upd_off[node];
   }
   if (n) HIPCHK(hipMemcpy(out, src, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (what == 3 && h->tree_factor)
@@ -812,15 +804,12 @@ int hqpkkt_selftest_mfma(int device, double *max_err) {
       for (int k = 0; k < 16; k++) s += A[i * 16 + k] * B[k * 16 + j];
       Cx[i * 16 + j] = s;
     }
-  double *dA, *dB, *dC;
-  HIPCHK(hipMalloc((void **)&dA, sizeof(A)));
-  HIPCHK(hipMalloc((void **)&dB, sizeof(B)));
-  HIPCHK(hipMalloc((void **)&dC, sizeof(Cd)));
-  HIPCHK(hipMemcpy(dA, A, sizeof(A), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dB, B, sizeof(B), hipMemcpyHostToDevice));
-  k_mfma_selftest<<<1, 64>>>(dA, dB, dC);
-  HIPCHK(hipMemcpy(Cd, dC, sizeof(Cd), hipMemcpyDeviceToHost));
-  (void)hipFree(dA), (void)hipFree(dB), (void)hipFree(dC);
+  DBuf<double> dA, dB, dC;
+  if (dA.alloc(256) || dB.alloc(256) || dC.alloc(256)) return HQPKKT_E_MEM;
+  HIPCHK(hipMemcpy(dA.p, A, sizeof(A), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB.p, B, sizeof(B), hipMemcpyHostToDevice));
+  k_mfma_selftest<<<1, 64>>>(dA.p, dB.p, dC.p);
+  HIPCHK(hipMemcpy(Cd, dC.p, sizeof(Cd), hipMemcpyDeviceToHost));
   double err = 0;
   for (int i = 0; i < 256; i++) err = std::fmax(err, std::fabs(Cd[i] - Cx[i]));
   *max_err = err;

@@ -17,7 +17,9 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <memory>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "analysis.hpp"
@@ -54,17 +56,29 @@ extern char g_last_hip_error[512];  // the text of the last HIP error (hqpkkt_st
     }                                                                             \
   } while (0)
 
+// ---- owners of HIP resources: move-only, freed by their destructors.  An empty owner makes no HIP call (a handle that
+// never touched the device is created and destroyed without HIP).
+extern std::atomic<long long> g_live_bufs[2];  // live allocations of DBuf / PinnedBuf in the process (hqpkkt_debug_get 40)
+
 template <class T>
 struct DBuf {
   T *p = nullptr;
   size_t count = 0;
+  DBuf() = default;
+  DBuf(DBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), count(std::exchange(o.count, 0)) {}
+  DBuf &operator=(DBuf &&o) noexcept {
+    if (this != &o) release(), p = std::exchange(o.p, nullptr), count = std::exchange(o.count, 0);
+    return *this;
+  }
+  ~DBuf() { release(); }
   int alloc(size_t k) {
     release();
-    count = k;
     if (hipMalloc((void **)&p, sizeof(T) * (k ? k : 1)) != hipSuccess) {
       p = nullptr;
       return HQPKKT_E_MEM;
     }
+    count = k;
+    g_live_bufs[0]++;
     return 0;
   }
   int upload(const std::vector<T> &v) {
@@ -76,11 +90,68 @@ struct DBuf {
     return 0;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)hipFree(p), g_live_bufs[0]--;
     p = nullptr;
     count = 0;
   }
 };
+
+// pinned host memory (hipHostMalloc); dev: the device's address of mapped memory (map)
+template <class T>
+struct PinnedBuf {
+  T *p = nullptr, *dev = nullptr;
+  size_t count = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) noexcept
+      : p(std::exchange(o.p, nullptr)), dev(std::exchange(o.dev, nullptr)), count(std::exchange(o.count, 0)) {}
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept {
+    if (this != &o)
+      release(), p = std::exchange(o.p, nullptr), dev = std::exchange(o.dev, nullptr), count = std::exchange(o.count, 0);
+    return *this;
+  }
+  ~PinnedBuf() { release(); }
+  hipError_t alloc(size_t k, unsigned flags) {
+    release();
+    const hipError_t e = hipHostMalloc((void **)&p, sizeof(T) * k, flags);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    count = k;
+    g_live_bufs[1]++;
+    return hipSuccess;
+  }
+  hipError_t map() {
+    const hipError_t e = hipHostGetDevicePointer((void **)&dev, p, 0);
+    if (e != hipSuccess) dev = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p), g_live_bufs[1]--;
+    p = dev = nullptr;
+    count = 0;
+  }
+};
+
+// a stream, event or graph and the call that destroys it; create into &x.h
+template <class H, hipError_t (*Destroy)(H)>
+struct HipOwner {
+  H h = nullptr;
+  HipOwner() = default;
+  HipOwner(HipOwner &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  HipOwner &operator=(HipOwner &&o) noexcept {
+    if (this != &o) reset(), h = std::exchange(o.h, nullptr);
+    return *this;
+  }
+  ~HipOwner() { reset(); }
+  void reset() {
+    if (h) (void)Destroy(h);
+    h = nullptr;
+  }
+  operator H() const { return h; }
+};
+using StreamOwner = HipOwner<hipStream_t, hipStreamDestroy>;
+using EventOwner = HipOwner<hipEvent_t, hipEventDestroy>;
 
 struct CsrBuf {
   DBuf<int> ptr, col, src;
@@ -92,7 +163,6 @@ struct CsrBuf {
     return 0;
   }
   CsrDev dev() const { return CsrDev{ptr.p, col.p, src.p, val.p}; }
-  void release() { ptr.release(), col.release(), src.release(), val.release(); }
 };
 
 // per-kernel-class device timing (hqpkkt_set_profile): HIP events on the
@@ -105,16 +175,16 @@ static const char *const kc_names[KC_COUNT] = {"assemble", "factor_diag", "panel
                                                "exchange", "solve_top"};
 struct Prof {
   bool on = false;
-  std::vector<hipEvent_t> pool;
+  std::vector<EventOwner> pool;
   std::vector<int> cls;
   size_t used = 0;
   double ms[KC_COUNT] = {0};
   long long launches[KC_COUNT] = {0};
   hipEvent_t get() {
     if (used == pool.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return nullptr;
-      pool.push_back(e);
+      EventOwner e;
+      if (hipEventCreate(&e.h) != hipSuccess) return nullptr;
+      pool.push_back(std::move(e));
     }
     return pool[used++];
   }
@@ -144,10 +214,6 @@ struct Prof {
   void reset() {
     for (int c = 0; c < KC_COUNT; c++) ms[c] = 0, launches[c] = 0;
   }
-  void destroy() {
-    for (auto e : pool) (void)hipEventDestroy(e);
-    pool.clear();
-  }
 };
 #define KLAUNCH(h, c, ...)        \
   do {                            \
@@ -157,38 +223,23 @@ struct Prof {
   } while (0)
 
 struct StagedDev;  // (staged_host.hip.h)
-void staged_release(StagedDev *sd, bool destroy);
+struct StagedDevDelete {
+  void operator()(StagedDev *d) const;  // (staged_engine.hip, where StagedDev is complete)
+};
+void staged_reset(StagedDev &d);  // frees what the stage blocks hold on the device; the plan stays
 
-struct hqpkkt {
-  hqpkkt_opts opts;
-  Prof prof;
-  Analysis an;
-  StagedDev *sd = nullptr;  // HQPKKT_MODE_STAGED: the stage blocks (staged_host.hip.h)
-  double ge_tol = 1.0e-6;   // rank decision of the stage constraints (_ge_tol, hqp/Hqp_IpLQDOCP.C:113)
-  bool analyzed = false, uploaded = false, have_values = false, factored = false;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, evs0 = nullptr, evs1 = nullptr;
-  hipEvent_t evt0 = nullptr, evt1 = nullptr;  // total time of an interior-point run (hqpkkt_mehrotra / _franke)
-  hqpkkt_stats st;
-
+// What release_device frees: the device state of one analysis - the tree engine's structure and numeric arrays, and
+// the vectors, status words and pinned staging that both engines use
+struct TreeDev {
   // symbolic structure on the device
   DBuf<int> piv_start, npiv, nbor, parent, bidx, rel, child_ptr, child_idx, ent_a, ent_b,
       term_ptr, diag_ent, q2e, pinv;
   struct DevSched {  // device copy of an Analysis::Sched
     DBuf<int> level_nodes, upd_tiles, slabs, gslabs, cblks;
-    void release() {
-      level_nodes.release(), upd_tiles.release(), slabs.release();
-      gslabs.release(), cblks.release();
-    }
   } ds[2];
   DBuf<long long> zero_panel;  // (offset, length) pairs, sharded mode
   DBuf<int> simple_src, simple_wi;  // FULL: compact single-term records of the entries (k_assemble_simple)
   DBuf<signed char> keep_e;
-  // one system over several ranks: collectives are delegated to the caller
-  int shard_rank = 0, shard_count = 1;
-  hqpkkt_exchange_fn xchg_fn = nullptr;
-  hqpkkt_exchange_stream_fn xchg_sfn = nullptr;  // stream-ordered form (RCCL): nothing is drained
-  void *xchg_ctx = nullptr;
   DBuf<long long> bptr, panel_off, upd_off, x_off, cb_off, ent_dst, linv_off, pinv_off;
   DBuf<TermDev> terms;
   DBuf<signed char> esign;
@@ -197,35 +248,71 @@ struct hqpkkt {
   DBuf<double> vals, wt, sc, ent_val, panel, upd, xar, dinv, rhs, xsol, cb, ytmp, vtmp, linv;
   DBuf<int> ptype, lperm, flags;  // flags: [0] status, [1] n_2x2, [2] n_perturbed
   // [0] kmax, [1] residual max: inside the flags buffer (ints 120..123) so that status and
-  // maxima come back in ONE copy; hpin: pinned host memory those copies land in
+  // maxima come back in ONE copy; hqpkkt::Kept::hpin: pinned host memory those copies land in
   struct {
     unsigned long long *p = nullptr;
   } bits;
-  double *hpin = nullptr;  // 128 doubles: 0..63 status words (as ints), 64.. the IP loop's scalars
-  // Read-backs without a copy and without hipStreamSynchronize (round 6): hpin is mapped, coherent host memory; a
-  // one-wavefront kernel at the point of the stream where the words are final stores them there and a sequence number
-  // behind them (k_post_words, kernels.hip.h), the host spins on that number (post_wait).  Measured (tools/post_probe.hip):
-  // 6 us per read-back behind a queue of small kernels against 16 for hipMemcpyAsync + hipStreamSynchronize - the
-  // device-resident interior-point loops read back three times per iteration.
-  double *hpin_dev = nullptr;  // the device's address of hpin
-  unsigned post_seq = 0;       // the number the last posting kernel in the stream will store (hpin word HPIN_SEQ)
-  // host vectors of a small system: packed into / out of pinned memory by the CPU, ONE
-  // transfer each way instead of six + four staged copies from pageable memory
-  double *hvals = nullptr;   // pinned host staging of Qx | Ax | Cx (hqpkkt_values_staging), nq + na + nc doubles
-  size_t hvals_elems = 0;    // ... as allocated: a new analysis with another pattern allocates again
-  double *hstage = nullptr;
+  // host vectors of a small system: packed into / out of pinned memory by the CPU, ONE transfer each way instead of
+  // six + four staged copies from pageable memory; the tree engine maps it (dev: kernels copy in and out of it)
+  PinnedBuf<double> hstage;
   size_t hstage_in = 0, hstage_out = 0;  // doubles; 0 = system too large, copy vector by vector
-  const double *out_pending = nullptr;   // results wait in hstage + hstage_in for unstage()
-  bool out_by_kernel = false;            // ... written there by a kernel in front of the posting kernel (no stream synchronisation needed)
-  bool host_graph_call = false;          // inside a solve whose first part ran as hqpkkt::ghost_step (no timing events in the stream)
-  double *hstage_dev = nullptr;          // the device's address of hstage (pinned, coherent: kernels copy in and out of it)
   // vectors: staging for host pointers + refinement work vectors
   DBuf<double> vin;   // z w r1 r2 r3 r4
   DBuf<double> vout;  // dx dy dz dw
   DBuf<double> vres;  // residual vectors _r1.._r4
   DBuf<double> vcor;  // corrections _dx.._dw
   DBuf<double> tz;    // REDUCED temporary (m)
-  DBuf<double> ipv;   // interior-point driver: x y z w | r1..r4 | dxa..dwa | dx..dw | c b d | partials | scalars
+  DBuf<int> top_nodes, top_idx, top_bpos, top_up;  // the fused top of the solve (hqpkkt::top_n); top_up: the fronts leaves first (top_split)
+  // trees of small fronts only (hqpkkt::small_tree): the exchange arrays (2 x cb_elems, then 2 x dim)
+  DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
+  DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
+  DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
+
+  DevTree tree() const {
+    return DevTree{piv_start.p, npiv.p,     nbor.p,  parent.p, bptr.p,      bidx.p,     rel.p,
+                   panel_off.p, upd_off.p, x_off.p, cb_off.p, child_ptr.p, child_idx.p, pinv.p, pinv_off.p};
+  }
+};
+
+struct hqpkkt {
+  // the handle's own stream and its timing events: destroyed last (members go in reverse order)
+  StreamOwner own_stream;
+  hipStream_t stream = nullptr;
+  EventOwner ev0, ev1, evs0, evs1;
+  EventOwner evt0, evt1;  // total time of an interior-point run (hqpkkt_mehrotra / _franke)
+  hqpkkt_opts opts;
+  Prof prof;
+  Analysis an;
+  std::unique_ptr<StagedDev, StagedDevDelete> sd;  // HQPKKT_MODE_STAGED: the stage blocks (staged_host.hip.h)
+  double ge_tol = 1.0e-6;   // rank decision of the stage constraints (_ge_tol, hqp/Hqp_IpLQDOCP.C:113)
+  bool analyzed = false, uploaded = false, have_values = false, factored = false;
+  hqpkkt_stats st;
+  TreeDev td;
+  // What survives release_device(true) (the re-analysis inside hqpkkt_solve, switch_to_policy0): the pattern and with
+  // it the sizes stay, and a host may hold the pointers of hqpkkt_values_staging
+  struct Kept {
+    DBuf<double> ipv;  // interior-point driver: x y z w | r1..r4 | dxa..dwa | dx..dw | c b d | partials | scalars
+    // Read-backs without a copy and without hipStreamSynchronize (round 6): hpin is mapped, coherent host memory
+    // (hpin.dev: the device's address of it); a one-wavefront kernel at the point of the stream where the words are
+    // final stores them there and a sequence number behind them (k_post_words, kernels.hip.h), the host spins on that
+    // number (post_wait).  Measured (tools/post_probe.hip): 6 us per read-back behind a queue of small kernels against
+    // 16 for hipMemcpyAsync + hipStreamSynchronize - the device-resident interior-point loops read back three times per
+    // iteration.  128 doubles: 0..63 status words (as ints), 64.. the IP loop's scalars
+    PinnedBuf<double> hpin;
+    DBuf<unsigned> post_seq_dev;  // the sequence number of the posted read-backs, counted by k_post_words
+    // pinned host staging of Qx | Ax | Cx (hqpkkt_values_staging), nq + na + nc doubles; a new analysis with another
+    // pattern allocates again
+    PinnedBuf<double> hvals;
+  } kept;
+  unsigned post_seq = 0;       // the number the last posting kernel in the stream will store (hpin word HPIN_SEQ)
+  // one system over several ranks: collectives are delegated to the caller
+  int shard_rank = 0, shard_count = 1;
+  hqpkkt_exchange_fn xchg_fn = nullptr;
+  hqpkkt_exchange_stream_fn xchg_sfn = nullptr;  // stream-ordered form (RCCL): nothing is drained
+  void *xchg_ctx = nullptr;
+  const double *out_pending = nullptr;   // results wait in hstage + hstage_in for unstage()
+  bool out_by_kernel = false;            // ... written there by a kernel in front of the posting kernel (no stream synchronisation needed)
+  bool host_graph_call = false;          // inside a solve whose first part ran as hqpkkt::ghost_step (no timing events in the stream)
   size_t lds_panel = 0, lds_bwdb = 0;
   // per schedule and tree level the largest pivot count (and border) among the general fronts of the level (k_factor_blk)
   std::vector<int> level_maxp[2], level_maxb[2];
@@ -236,26 +323,18 @@ struct hqpkkt {
   // the top levels of the tree solved in one launch (solve_top.hip.h): fronts of the levels >= top_lt, root first
   int top_n = 0, top_lt = 1 << 30, top_ns = 3;  // top_ns: 3 = k_solve_top<3, 11>, 4 = <4, 10>
   size_t top_lds = 0;
-  DBuf<int> top_nodes, top_idx, top_bpos, top_up;  // top_up: the fronts leaves first (top_split)
   bool top_split = false;  // more fronts than one launch may hold at once: the two sweeps as launches of their own
   unsigned long long *top_stamps = nullptr;  // (hqpkkt_debug_solve_top_stamps)
   // trees of small fronts only (the double-integrator structure): each sweep of the solve is ONE launch over all levels
-  // (k_solve_fwd_small<true> / k_solve_bwd_small<true>); tree_x: the exchange arrays (2 x cb_elems, then 2 x dim)
+  // (k_solve_fwd_small<true> / k_solve_bwd_small<true>)
   bool small_tree = false, tree_factor = false;  // tree_factor: ... and the factorisation too (k_factor_diag_small<true, true>)
-  DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
-  DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
-  DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
   // captured kernel sequences (factor; step on the caller's vectors; step on the
   // refinement's residual vectors): replayed with hipGraphLaunch
   struct GraphSlot {
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
+    HipOwner<hipGraph_t, hipGraphDestroy> g;
+    HipOwner<hipGraphExec_t, hipGraphExecDestroy> ge;  // (destroyed before g)
     unsigned n_posts = 0;  // posted read-backs inside (k_post_words counts on the device; the host counts along at every replay)
-    void drop() {
-      if (ge) (void)hipGraphExecDestroy(ge);
-      if (g) (void)hipGraphDestroy(g);
-      ge = nullptr, g = nullptr, n_posts = 0;
-    }
+    void drop() { ge.reset(), g.reset(), n_posts = 0; }
   } gfactor[2], gstep[2][3];  // [phase], [caller's / refinement's vectors][phase]
   // A caller with HOST vectors (the reference's solvers through the shim): the packed vectors are read out of the pinned
   // staging buffer by a kernel, the results written into it by a kernel, and the status words posted - a whole call is
@@ -277,17 +356,14 @@ struct hqpkkt {
   GraphSlot &direct_slot(std::vector<DirectGraph> &cache, const void *const (&key)[10]) {
     for (auto &d : cache)
       if (std::memcmp(d.key, key, sizeof(key)) == 0) return d.g;
-    if (cache.size() >= 6) {  // (Mehrotra's loop has two sets + the refinement's, Franke's one + the refinement's)
-      cache.front().g.drop();
-      cache.erase(cache.begin());
-    }
+    if (cache.size() >= 6)  // (Mehrotra's loop has two sets + the refinement's, Franke's one + the refinement's)
+      cache.erase(cache.begin());  // (the oldest graph is dropped)
     cache.emplace_back();
     std::memcpy(cache.back().key, key, sizeof(key));
     return cache.back().g;
   }
   bool use_graphs = true, capturing = false;
   unsigned cap_posts = 0;  // posted read-backs of the capture in progress
-  DBuf<unsigned> post_seq_dev;  // the sequence number of the posted read-backs, counted by k_post_words
   // inside hqpkkt_mehrotra: factor() returns without waiting for its status (read with the
   // residual of the solve that follows), solve() leaves its result in the stream
   bool lazy = false, factor_unchecked = false;
@@ -324,39 +400,12 @@ struct hqpkkt {
     ghost_factor.drop(), ghost_step.drop();
     for (auto &gs : gstep)
       for (auto &g : gs) g.drop();
-    for (auto &d : gdirect_step) d.g.drop();
-    for (auto &d : gdirect_factor) d.g.drop();
-    for (auto &d : gdirect_seg) d.g.drop();
-    for (auto &d : gdirect_call) d.g.drop();
     gdirect_step.clear(), gdirect_factor.clear(), gdirect_seg.clear(), gdirect_call.clear();
   }
-
-  DevTree tree() const {
-    return DevTree{piv_start.p, npiv.p,     nbor.p,  parent.p, bptr.p,      bidx.p,     rel.p,
-                   panel_off.p, upd_off.p, x_off.p, cb_off.p, child_ptr.p, child_idx.p, pinv.p, pinv_off.p};
-  }
-  void release_device(bool keep_ip = false) {  // keep_ip: hqpkkt_mehrotra's vectors and the pinned words stay
-    DBuf<int> *ib[] = {&piv_start, &npiv, &nbor, &parent, &bidx, &rel, &child_ptr, &child_idx,
-                       &ent_a, &ent_b, &term_ptr, &diag_ent, &q2e, &pinv, &ptype, &lperm, &flags,
-                       &top_nodes, &top_idx, &top_bpos, &top_up, &tree_words, &tree_down};
-    for (auto b : ib) b->release();
-    ds[0].release(), ds[1].release(), keep_e.release(), simple_src.release(), simple_wi.release();
-    DBuf<long long> *lb[] = {&bptr, &panel_off, &upd_off, &x_off, &cb_off, &ent_dst, &linv_off, &pinv_off,
-                             &zero_panel};
-    for (auto b : lb) b->release();
-    DBuf<double> *db[] = {&vals, &wt, &sc, &ent_val, &panel, &upd, &xar, &dinv, &rhs, &xsol,
-                          &cb, &vin, &vout, &vres, &vcor, &tz, &ytmp, &vtmp, &linv, &top_x, &tree_x, &tree_u};
-    for (auto b : db) b->release();
-    if (!keep_ip) ipv.release();
-    terms.release(), esign.release(), bits.p = nullptr;
-    if (hpin && !keep_ip) (void)hipHostFree(hpin), hpin = nullptr, hpin_dev = nullptr, post_seq_dev.release(), post_seq = 0;
-    if (hstage) (void)hipHostFree(hstage), hstage = nullptr, hstage_dev = nullptr;
-    // (keep_ip = the re-analysis inside hqpkkt_solve, switch_to_policy0: the pattern and with it the sizes of the
-    // pinned value staging stay, and a host may hold the pointers of hqpkkt_values_staging)
-    if (hvals && !keep_ip) (void)hipHostFree(hvals), hvals = nullptr, hvals_elems = 0;
-    hstage_in = hstage_out = 0;
-    Qf.release(), A.release(), AT.release(), C.release(), CT.release();
-    if (sd) staged_release(sd, false);
+  void release_device(bool keep_ip = false) {  // keep_ip: hqpkkt_mehrotra's vectors and the pinned words stay (Kept)
+    td = TreeDev();
+    if (!keep_ip) kept = Kept();
+    if (sd) staged_reset(*sd);
     drop_graphs();
     uploaded = have_values = factored = false;
   }
@@ -390,22 +439,14 @@ static int graphed(hqpkkt_t *h, hqpkkt::GraphSlot &slot, F body) {
     h->capturing = true, h->cap_posts = 0;
     int e = body();
     h->capturing = false;
-    hipGraph_t g = nullptr;
-    hipError_t ce = hipStreamEndCapture(h->stream, &g);
+    const hipError_t ce = hipStreamEndCapture(h->stream, &slot.g.h);
     if (e) {
-      if (g) (void)hipGraphDestroy(g);
+      slot.drop();
       h->post_seq -= h->cap_posts;  // (nothing was posted)
       return e;
     }
-    if (ce != hipSuccess || !g) {  // capture not possible: run eagerly from now on
-      h->use_graphs = false;
-      (void)hipGetLastError();
-      h->post_seq -= h->cap_posts;
-      return body();
-    }
-    slot.g = g;
-    if (hipGraphInstantiate(&slot.ge, g, nullptr, nullptr, 0) != hipSuccess) {
-      slot.drop();
+    if (ce != hipSuccess || !slot.g || hipGraphInstantiate(&slot.ge.h, slot.g, nullptr, nullptr, 0) != hipSuccess) {
+      slot.drop();  // capture not possible: run eagerly from now on
       h->use_graphs = false;
       (void)hipGetLastError();
       h->post_seq -= h->cap_posts;

@@ -63,7 +63,7 @@ struct IpCtx {
   int n, me, m;
   double *x, *y, *z, *w, *r1, *r2, *r3, *r4, *dxa, *dya, *dza, *dwa, *dx, *dy, *dz, *dw, *c, *b, *d, *part, *out;
   double *zh, *wh;  // hot-start candidates (hqp/Hqp_IpsMehrotra.C:475-478)
-  double *hout;  // pinned (h->hpin + 64)
+  double *hout;  // pinned (h->kept.hpin.p + 64)
   int reduce(const int (&ops)[IP_SLOTS], int nout) {
     IpOps o;
     for (int k = 0; k < IP_SLOTS; k++) o.op[k] = ops[k];
@@ -105,14 +105,14 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
     const size_t nv = (size_t)n + me + 2 * (size_t)m;
     const size_t need = 4 * nv + (size_t)n + me + m + (size_t)IP_BLOCKS * IP_SLOTS + 64 + 2 * (size_t)m;
     int e;
-    if (h->ipv.count < need) {
-      if ((e = h->ipv.alloc(need))) return e;
+    if (h->kept.ipv.count < need) {
+      if ((e = h->kept.ipv.alloc(need))) return e;
       h->ip_hot_valid = false;
     }
     h->fr_hot_valid = false;  // the arena is shared with hqpkkt_franke
     IpCtx C;
-    C.h = h, C.n = n, C.me = me, C.m = m, C.hout = h->hpin + 64;
-    double *q = h->ipv.p;
+    C.h = h, C.n = n, C.me = me, C.m = m, C.hout = h->kept.hpin.p + 64;
+    double *q = h->kept.ipv.p;
     auto take = [&](size_t k) { double *r = q; q += k; return r; };
     C.x = take(n), C.y = take(me), C.z = take(m), C.w = take(m);
     C.r1 = take(n), C.r2 = take(me), C.r3 = take(m), C.r4 = take(m);
@@ -136,7 +136,7 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
       int loc;
       ~Restore() {
         h->opts.loc = loc, h->lazy = false, h->factor_unchecked = false;
-        (void)hipMemsetAsync(h->flags.p + TINY_REPLACE_WORD, 0, sizeof(int), h->stream);  // (kernels.hip.h: cancelled pivots are replaced inside the loop only)
+        (void)hipMemsetAsync(h->td.flags.p + TINY_REPLACE_WORD, 0, sizeof(int), h->stream);  // (kernels.hip.h: cancelled pivots are replaced inside the loop only)
       }
     } restore{h, saved_loc};
     h->opts.loc = HQPKKT_LOC_DEVICE;
@@ -272,12 +272,12 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
     };
     auto enqueue_head = [&]() -> int {
       if (h->short_rows)
-        k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(),
-                                              h->vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
+        k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
+                                              h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
                                               C.part, dx1, dx2, dndyn);
       else
-        k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(),
-                                               h->vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
+        k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
+                                               h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
                                                C.part, dx1, dx2, dndyn);
       if (m == 0) return 0;
       // the reductions of this iterate and what the step before left behind, one round trip
@@ -346,7 +346,7 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
     // the cold start's factorisation has succeeded (or a hot start carries on): the matrix is regular, cancelled multiplier
     // pivots are replaced from here on (kernels.hip.h, TINY_REPLACE_WORD)
     // (2: exactly zero pivots as well - only where the factorisation just checked met no cancelled multiplier pivot: kernels.hip.h)
-    if (h->tiny_replace_in_loop) HIPCHK(hipMemsetAsync(h->flags.p + TINY_REPLACE_WORD, (!hot && !h->soft_tiny) ? 2 : 1, sizeof(int), s));
+    if (h->tiny_replace_in_loop) HIPCHK(hipMemsetAsync(h->td.flags.p + TINY_REPLACE_WORD, (!hot && !h->soft_tiny) ? 2 : 1, sizeof(int), s));
     bool restart_cold = false;
     while (true) {
       double phi = 0.0;
@@ -578,14 +578,14 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
     // same arena as hqpkkt_mehrotra (its hot-start data does not survive this call)
     const size_t need = 5 * nv + (size_t)n + me + m + (size_t)IP_BLOCKS * IP_SLOTS + 64 + 2 * (size_t)m;  // (+ nv: the iterate before a step)
     int e;
-    if (h->ipv.count < need) {
-      if ((e = h->ipv.alloc(need))) return e;
+    if (h->kept.ipv.count < need) {
+      if ((e = h->kept.ipv.alloc(need))) return e;
       h->fr_hot_valid = false;
     }
     h->ip_hot_valid = false;
     IpCtx C;
-    C.h = h, C.n = n, C.me = me, C.m = m, C.hout = h->hpin + 64;
-    double *q = h->ipv.p;
+    C.h = h, C.n = n, C.me = me, C.m = m, C.hout = h->kept.hpin.p + 64;
+    double *q = h->kept.ipv.p;
     auto take = [&](size_t k) { double *r = q; q += k; return r; };
     C.x = take(n), C.y = take(me), C.z = take(m), C.w = take(m);
     C.r1 = take(n), C.r2 = take(me), C.r3 = take(m), C.r4 = take(m);
@@ -607,7 +607,7 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
       int loc;
       ~Restore() {
         h->opts.loc = loc, h->lazy = false, h->factor_unchecked = false, h->defer_residual = false, h->residual_pending = false;
-        (void)hipMemsetAsync(h->flags.p + TINY_REPLACE_WORD, 0, sizeof(int), h->stream);
+        (void)hipMemsetAsync(h->td.flags.p + TINY_REPLACE_WORD, 0, sizeof(int), h->stream);
       }
     } restore{h, saved_loc};
     h->opts.loc = HQPKKT_LOC_DEVICE;
@@ -654,11 +654,11 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
       k_ip_shift<<<nblk(m), 256, 0, s>>>(m, C.z, C.w, 0.0, 1e-10, C.z, C.w);
       if ((e = dyn_products())) return e;
       if (h->short_rows)
-        k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(),
-                                              h->vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
+        k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
+                                              h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
       else
-        k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(),
-                                               h->vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
+        k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
+                                               h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
       if ((e = C.reduce(OPS_SUM, 3))) return e;
       gap = C.hout[2] + 1.0;  // in_prod(z, w) + 1 (:248)
       if (rhomin == 0.0) rhomin = h->fr_rhomin;
@@ -680,9 +680,9 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
       }
     }
     if (h->short_rows)
-      k_fr_cold<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->CT.dev(), Ltilde, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.part);
+      k_fr_cold<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.CT.dev(), Ltilde, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.part);
     else
-      k_fr_cold<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->CT.dev(), Ltilde, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.part);
+      k_fr_cold<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.CT.dev(), Ltilde, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.part);
     gap = 0.0;
     if (m > 0) {
       if ((e = C.reduce(OPS_SUM, 1))) return e;
@@ -694,7 +694,7 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
     while (true) {
       if (iter == 0) alphabar = 1.0;
       if (iter == 1 && h->tiny_replace_in_loop)
-        HIPCHK(hipMemsetAsync(h->flags.p + TINY_REPLACE_WORD, h->soft_tiny ? 1 : 2, sizeof(int), s));  // (the first factorisation + solve has succeeded; 2: exact zeros too, kernels.hip.h)
+        HIPCHK(hipMemsetAsync(h->td.flags.p + TINY_REPLACE_WORD, h->soft_tiny ? 1 : 2, sizeof(int), s));  // (the first factorisation + solve has succeeded; 2: exact zeros too, kernels.hip.h)
       double mu;
       if (1.0 / gap < rhomin || alpha < 1.0) {
         mu = alphabar * gap / rhomin;             // potential reduction
@@ -702,13 +702,13 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
       } else
         mu = gap * gap;  // quadratic convergence
       if (m == 0) mu = 0.0;
-      h->hpin[HPIN_ZM] = zeta, h->hpin[HPIN_ZM + 1] = mu;
+      h->kept.hpin.p[HPIN_ZM] = zeta, h->kept.hpin.p[HPIN_ZM + 1] = mu;
       std::atomic_thread_fence(std::memory_order_release);
       // The whole step - right-hand sides, factorisation, solve, its residual, the step length, the update, the new gap,
       // both posts - as ONE captured graph (the launches take nothing from the host that changes from step to step)
       const bool seg_ok = h->use_graphs && !h->prof.on && h->opts.mode != HQPKKT_MODE_STAGED && h->an.shard_count <= 1 &&
                           !getenv("HQPKKT_NO_IP_SEGMENTS") && !getenv("HQPKKT_FRANKE_TWO_READS");
-      if (!seg_ok) k_fr_rhs<<<nblk(total), 256, 0, s>>>(n, me, m, h->hpin_dev + HPIN_ZM, a1, a2, a3, C.z, C.w, C.r1, C.r2, C.r3, C.r4);
+      if (!seg_ok) k_fr_rhs<<<nblk(total), 256, 0, s>>>(n, me, m, h->kept.hpin.dev + HPIN_ZM, a1, a2, a3, C.z, C.w, C.r1, C.r2, C.r3, C.r4);
       double resid = 0.0;
       n_factor++, n_solve++;
       // The step length below compares dw = C dx - r3 with w, whose active components are of the
@@ -751,7 +751,7 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
           std::memcpy(&kb, &beta, sizeof(kb));
           const void *key[10] = {(const void *)(intptr_t)4, (const void *)(uintptr_t)kb, C.x, C.z, C.r1, C.dx, keep, C.out, a1, nullptr};
           e = graphed(h, h->direct_slot(h->gdirect_seg, key), [&]() {
-            k_fr_rhs<<<nblk(total), 256, 0, s>>>(n, me, m, h->hpin_dev + HPIN_ZM, a1, a2, a3, C.z, C.w, C.r1, C.r2, C.r3, C.r4);
+            k_fr_rhs<<<nblk(total), 256, 0, s>>>(n, me, m, h->kept.hpin.dev + HPIN_ZM, a1, a2, a3, C.z, C.w, C.r1, C.r2, C.r3, C.r4);
             int e2 = hqpkkt_factor(h, C.z, C.w);
             if (!e2) e2 = hqpkkt_solve(h, C.z, C.w, C.r1, C.r2, C.r3, C.r4, C.dx, C.dy, C.dz, C.dw, &resid);
             if (e2) return e2;

@@ -55,10 +55,11 @@ int staged_step(hqpkkt_t *h, const Vecs &v, int which) {
 // hqpkkt_analyze / hqpkkt_set_values of a handle in HQPKKT_MODE_STAGED: the CSR hand-over of the dynamics
 int staged_analyze_csr(hqpkkt_t *h, int n, int me, int m) { return staged_analyze(h, n, me, m); }
 int staged_set_values_csr(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx) { return staged_set_values(h, Qx, Ax, Cx); }
-void staged_release(StagedDev *sd, bool destroy) {
-  if (!sd) return;
-  sd->release();
-  if (destroy) delete sd;
+void StagedDevDelete::operator()(StagedDev *d) const { delete d; }
+void staged_reset(StagedDev &d) {
+  kktdev::StagedPlan plan = std::move(d.plan);
+  d = StagedDev();
+  d.plan = std::move(plan);
 }
 
 // hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 34); the handle is in HQPKKT_MODE_STAGED and analysed
@@ -90,7 +91,7 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       break;
     case 28:  // [0] stages whose blocked elimination ran, [1] those of them that fell back to the one-workgroup form
       out.assign(2, 0);
-      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out.data(), h->flags.p + 6, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out.data(), h->td.flags.p + 6, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
         return HQPKKT_E_DEVICE;
       break;
     case 32:  // free initial state of many components: [0] blocked inverse ran, [1] fell back to the LU factors
@@ -98,7 +99,7 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       // (floats as their bit patterns; the words of the blocked sweep's scratch area as the LAST factorisation left them)
       out.assign(6, 0);
       if (hipDeviceSynchronize() != hipSuccess ||
-          hipMemcpy(out.data(), h->flags.p + stg::X0_BLOCKED, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
+          hipMemcpy(out.data(), h->td.flags.p + stg::X0_BLOCKED, sizeof(int) * 2, hipMemcpyDeviceToHost) != hipSuccess)
         return HQPKKT_E_DEVICE;
       if (P.big0 &&
           hipMemcpy(out.data() + 2, stg::big_scratch(h->sd->misc.p + P.oScr, P.q0max).flags + 1, sizeof(int) * 4,
@@ -116,8 +117,7 @@ int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu) {
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
     if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
-    if (!h->sd) h->sd = new (std::nothrow) StagedDev;
-    if (!h->sd) return HQPKKT_E_MEM;
+    if (!h->sd) h->sd.reset(new StagedDev);
     kktdev::StagedPlan &P = h->sd->plan;
     P.given_nx.clear(), P.given_nu.clear();
     if (K <= 0) return 0;  // back to detection from the staircase of A
@@ -209,15 +209,11 @@ int hqpkkt_stage_staging(hqpkkt_t *h, int which, double **buf, long long *elems)
     const kktdev::StagedPlan &P = d.plan;
     long long mx = 1;
     for (int k = 0; k < P.K; k++) mx = std::max(mx, (long long)P.nk[k + 1] * (P.nk[k] + P.mk[k]));
-    for (int b = 0; b < 2; b++)
-      if (!d.hblk[b] || d.hblk_elems < mx) {
-        if (d.hblk[b]) (void)hipHostFree(d.hblk[b]), d.hblk[b] = nullptr;
-        HIPCHK(hipHostMalloc((void **)&d.hblk[b], sizeof(double) * (size_t)mx, hipHostMallocDefault));
-      }
-    d.hblk_elems = mx;
+    for (auto &b : d.hblk)
+      if (b.count < (size_t)mx) HIPCHK(b.alloc((size_t)mx, hipHostMallocDefault));
     // the copy that last read this buffer must be over before the caller refills it
     if (d.hblk_ev[which]) HIPCHK(hipEventSynchronize(d.hblk_ev[which]));
-    *buf = d.hblk[which], *elems = mx;
+    *buf = d.hblk[which].p, *elems = mx;
     return 0;
   });
 }
@@ -237,8 +233,8 @@ int hqpkkt_set_stage_block(hqpkkt_t *h, int k, const double *F, long long ldF) {
     const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if ((e = staged_copy_block(h, k, F, ldF, kind))) return e;
     for (int b = 0; b < 2; b++)
-      if (F == d.hblk[b]) {  // the library's own staging buffer: remember when it is free again
-        if (!d.hblk_ev[b]) HIPCHK(hipEventCreateWithFlags(&d.hblk_ev[b], hipEventDisableTiming));
+      if (F == d.hblk[b].p) {  // the library's own staging buffer: remember when it is free again
+        if (!d.hblk_ev[b]) HIPCHK(hipEventCreateWithFlags(&d.hblk_ev[b].h, hipEventDisableTiming));
         HIPCHK(hipEventRecord(d.hblk_ev[b], h->stream));
       }
     if ((int)d.blocks_set.size() != P.K) d.blocks_set.assign(P.K, 0);
@@ -303,26 +299,21 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
   HIPCHK(hipSetDevice(device));
   const long long lda = (M + 7) / 8 * 8, ldb = (N + 7) / 8 * 8, ldc = ldb;
-  double *A = nullptr, *B = nullptr, *Cm = nullptr, *err = nullptr, *zr = nullptr;
-  stg::SkUnit *sk_table_dev = nullptr;
-  auto fin = [&](int rc) {
-    (void)hipFree(A), (void)hipFree(B), (void)hipFree(Cm), (void)hipFree(err), (void)hipFree(zr), (void)hipFree(sk_table_dev);
-    return rc;
-  };
+  DBuf<double> A, B, Cm, err, zr, skws;
+  DBuf<unsigned> skcnt;
+  DBuf<stg::SkUnit> sk_table_dev;
   const size_t kk = K > 0 ? K : 1;
-  if (hipMalloc((void **)&A, sizeof(double) * kk * lda) != hipSuccess || hipMalloc((void **)&B, sizeof(double) * kk * ldb) != hipSuccess ||
-      hipMalloc((void **)&Cm, sizeof(double) * (size_t)std::max(M, N) * ldc) != hipSuccess || hipMalloc((void **)&err, 8) != hipSuccess)
-    return fin(HQPKKT_E_MEM);
-  k_fill_rand<<<nblk((long long)kk * lda), 256>>>(A, (long long)kk * lda, 1);
-  k_fill_rand<<<nblk((long long)kk * ldb), 256>>>(B, (long long)kk * ldb, 2);
-  (void)hipMemset(err, 0, 8);
-  (void)hipMemset(Cm, 0, sizeof(double) * (size_t)std::max(M, N) * ldc);
-  stg::GemmArgs g{A, lda, B, ldb, nullptr, 0, Cm, ldc, M, N, K, 1.0, 0.0, lower, mirror, nullptr, nullptr};
+  if (A.alloc(kk * lda) || B.alloc(kk * ldb) || Cm.alloc((size_t)std::max(M, N) * ldc) || err.alloc(1)) return HQPKKT_E_MEM;
+  k_fill_rand<<<nblk((long long)kk * lda), 256>>>(A.p, (long long)kk * lda, 1);
+  k_fill_rand<<<nblk((long long)kk * ldb), 256>>>(B.p, (long long)kk * ldb, 2);
+  (void)hipMemset(err.p, 0, 8);
+  (void)hipMemset(Cm.p, 0, sizeof(double) * (size_t)std::max(M, N) * ldc);
+  stg::GemmArgs g{A.p, lda, B.p, ldb, nullptr, 0, Cm.p, ldc, M, N, K, 1.0, 0.0, lower, mirror, nullptr, nullptr};
   const int variant = stg::gemm_variant_from_env();
   if (variant != stg::GEMM_REG4) {
-    if (hipMalloc((void **)&zr, sizeof(double) * 256) != hipSuccess) return fin(HQPKKT_E_MEM);
-    (void)hipMemset(zr, 0, sizeof(double) * 256);
-    g.zeros = zr;
+    if (zr.alloc(256)) return HQPKKT_E_MEM;
+    (void)hipMemset(zr.p, 0, sizeof(double) * 256);
+    g.zeros = zr.p;
   }
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -335,36 +326,24 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   const long long tiles = stg::gemm_tiles(M, N, b, lower);
   (void)stg::gemm_set_attributes();
   // stream-K form where the engine would use it (staged_host.hip.h, st_gemm)
-  double *skws = nullptr;
-  unsigned *skcnt = nullptr;
-  if (use_sk) {
-    if (hipMalloc((void **)&skws, sizeof(double) * (size_t)std::max<long long>(16 * tiles + 8, 2LL * skg + 2) * 128 * 128) != hipSuccess ||
-        hipMalloc((void **)&skcnt, sizeof(unsigned) * (tiles + 4)) != hipSuccess) {
-      (void)hipFree(skws), (void)hipFree(skcnt);
-      return fin(HQPKKT_E_MEM);
-    }
-  }
+  if (use_sk && (skws.alloc((size_t)std::max<long long>(16 * tiles + 8, 2LL * skg + 2) * 128 * 128) || skcnt.alloc(tiles + 4)))
+    return HQPKKT_E_MEM;
   // (the cut form by a table with unequal shares for the two workgroups of a CU: gemm_split_table; HQPKKT_SK_TABLE=0: equal shares)
   stg::SplitTable sk_tab;
   if (use_sk && !frac && stg::gemm_sk_table_from_env() && stg::gemm_split_table(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg, sk_tab) &&
       sk_tab.pieces <= 16 * tiles + 8) {
-    const size_t nu = sk_tab.units.size();
-    if (hipMalloc((void **)&sk_table_dev, sizeof(stg::SkUnit) * nu) != hipSuccess ||
-        hipMemcpy(sk_table_dev, sk_tab.units.data(), sizeof(stg::SkUnit) * nu, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(skws), (void)hipFree(skcnt);
-      return fin(HQPKKT_E_MEM);
-    }
+    if (sk_table_dev.upload(sk_tab.units)) return HQPKKT_E_MEM;
   }
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0), (void)hipEventCreate(&e1);
+  EventOwner e0, e1;
+  (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
     if (r == 0) (void)hipEventRecord(e0, 0);
     if (use_sk) {
-      (void)hipMemsetAsync(skcnt, 0, sizeof(unsigned) * (tiles + 4), 0);
+      (void)hipMemsetAsync(skcnt.p, 0, sizeof(unsigned) * (tiles + 4), 0);
       stg::SplitPlan skk = frac ? stg::gemm_split_plan_frac(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg)
                                 : stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
-      skk.ws = skws, skk.cnt = skcnt;
-      if (sk_table_dev) skk.table = sk_table_dev, skk.stride = sk_tab.stride;
+      skk.ws = skws.p, skk.cnt = skcnt.p;
+      if (sk_table_dev.p) skk.table = sk_table_dev.p, skk.stride = sk_tab.stride;
       stg::gemm_launch_split(variant, skg, 0, g, skk);
     } else if (big)
       stg::gemm_launch_plain(variant, (unsigned)tiles, 0, g, cus);
@@ -375,40 +354,37 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   }
   (void)hipEventRecord(e1, 0);
   hipError_t se = hipDeviceSynchronize();
-  (void)hipFree(skws), (void)hipFree(skcnt);
+  skws.release(), skcnt.release();
   float t = 0.f;
   (void)hipEventElapsedTime(&t, e0, e1);
-  (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-  if (se != hipSuccess) return fin(HQPKKT_E_DEVICE);
+  if (se != hipSuccess) return HQPKKT_E_DEVICE;
   if (getenv("HQPKKT_DGEMM_STAMPS") && use_sk && !frac) {
     // the split form with time stamps: per workgroup its start and, per unit, the end of the k loop, of the
     // parking / summing of partial tiles and of the epilogue (us after the first start)
-    unsigned long long *st = nullptr;
-    double *ws2 = nullptr;
-    unsigned *cnt2 = nullptr;
-    if (hipMalloc((void **)&st, sizeof(unsigned long long) * 32 * skg) == hipSuccess &&
-        hipMalloc((void **)&ws2, sizeof(double) * (size_t)(16 * tiles + 8) * 128 * 128) == hipSuccess &&
-        hipMalloc((void **)&cnt2, sizeof(unsigned) * (tiles + 4)) == hipSuccess) {
-      (void)hipMemset(st, 0, sizeof(unsigned long long) * 32 * skg);
-      (void)hipMemset(cnt2, 0, sizeof(unsigned) * (tiles + 4));
+    DBuf<unsigned long long> st;
+    DBuf<double> ws2;
+    DBuf<unsigned> cnt2;
+    if (!st.alloc(32 * (size_t)skg) && !ws2.alloc((size_t)(16 * tiles + 8) * 128 * 128) && !cnt2.alloc(tiles + 4)) {
+      (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 32 * skg);
+      (void)hipMemset(cnt2.p, 0, sizeof(unsigned) * (tiles + 4));
       stg::GemmArgs gs = g;
-      gs.stamps = st;
+      gs.stamps = st.p;
       stg::SplitPlan skk = stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
-      skk.ws = ws2, skk.cnt = cnt2;
-      if (sk_table_dev) skk.table = sk_table_dev, skk.stride = sk_tab.stride;
+      skk.ws = ws2.p, skk.cnt = cnt2.p;
+      if (sk_table_dev.p) skk.table = sk_table_dev.p, skk.stride = sk_tab.stride;
       stg::gemm_launch_split(variant, skg, 0, gs, skk);
       std::vector<unsigned long long> hs(32 * (size_t)skg);
-      if (hipMemcpy(hs.data(), st, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) == hipSuccess) {
+      if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) == hipSuccess) {
         unsigned long long tmin = ~0ULL;
         for (int w = 0; w < skg; w++) tmin = std::min(tmin, hs[32 * (size_t)w]);
-        if (sk_table_dev)
+        if (sk_table_dev.p)
           fprintf(stderr, "table plan: %d / %d whole tiles per first / second workgroup of a CU, %lld parked pieces", sk_tab.nA, sk_tab.nB, sk_tab.pieces);
         else {
           fprintf(stderr, "split plan: %d whole tiles", skk.whole);
           for (int q = 0; q < skk.nphase; q++) fprintf(stderr, ", %d tiles x %d pieces", skk.count[q], skk.split[q]);
         }
         fprintf(stderr, "; stamps of every %dth workgroup (us): start | per unit: k loop end, parked / summed, epilogue end\n", std::max(1, skg / 32));
-        const int nr = sk_table_dev ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
+        const int nr = sk_table_dev.p ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
         for (int w = 0; w < skg; w += std::max(1, skg / 32)) {
           fprintf(stderr, "  wg %4d: %7.2f |", w, (hs[32 * (size_t)w] - tmin) * 0.01);
           for (int r = 0; r < nr; r++) {
@@ -435,18 +411,17 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
         }
       }
     }
-    (void)hipFree(st), (void)hipFree(ws2), (void)hipFree(cnt2);
   }
   if (getenv("HQPKKT_DGEMM_STAMPS") && !use_sk && big) {
     // one more launch with time stamps per workgroup (100 MHz constant clock): when it started, when its k loop
     // ended, when its epilogue ended - relative to the first start; printed as a histogram over the workgroups
-    unsigned long long *st = nullptr;
-    if (hipMalloc((void **)&st, sizeof(unsigned long long) * 4 * tiles) == hipSuccess) {
+    DBuf<unsigned long long> st;
+    if (!st.alloc(4 * (size_t)tiles)) {
       stg::GemmArgs gs = g;
-      gs.stamps = st;
+      gs.stamps = st.p;
       stg::gemm_launch_plain(variant, (unsigned)tiles, 0, gs);
       std::vector<unsigned long long> hs(4 * tiles);
-      if (hipMemcpy(hs.data(), st, sizeof(unsigned long long) * 4 * tiles, hipMemcpyDeviceToHost) == hipSuccess) {
+      if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 4 * tiles, hipMemcpyDeviceToHost) == hipSuccess) {
         unsigned long long tmin = ~0ULL;
         for (long long t = 0; t < tiles; t++) tmin = std::min(tmin, hs[4 * t]);
         // workgroups in the order of their start
@@ -461,15 +436,14 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
                   hs[4 * t + 1], t);
         }
       }
-      (void)hipFree(st);
     }
   }
-  k_gemm_check<<<16, 256>>>(g, 4096, err);
+  k_gemm_check<<<16, 256>>>(g, 4096, err.p);
   double he = 0.0;
-  if (hipMemcpy(&he, err, 8, hipMemcpyDeviceToHost) != hipSuccess) return fin(HQPKKT_E_DEVICE);
+  if (hipMemcpy(&he, err.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return HQPKKT_E_DEVICE;
   if (ms) *ms = t / reps;
   if (max_err) *max_err = he;
-  return fin(0);
+  return 0;
 }
 
 int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {

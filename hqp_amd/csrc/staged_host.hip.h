@@ -14,9 +14,8 @@ struct StagedDev {
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
   DBuf<double> dyn_part;        // row sums of A_dyn dx per block of 256 columns (k_st_dyn_both): ndyn x dyn_part_cols
   int dyn_part_cols = 0;
-  double *hblk[2] = {nullptr, nullptr};  // pinned staging of one stage block each (hqpkkt_stage_staging)
-  long long hblk_elems = 0;
-  hipEvent_t hblk_ev[2] = {nullptr, nullptr};
+  PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging)
+  EventOwner hblk_ev[2];
   std::vector<char> blocks_set;         // dense hand-over block by block: which stages have arrived since the analysis
   // one system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
   // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack; the local dynamics blocks of
@@ -34,8 +33,8 @@ struct StagedDev {
   // the exchanges of a stage in the stream-ordered form (RCCL) go to a stream of their own, so that the gather of the
   // NEXT stage's F blocks travels beside this stage's products: ev_w[i] "the first stream is ready for exchange i",
   // ev_x[i] "exchange i has arrived" (i = 0, 1: the gathered F in buffer i, 2: the blocks of G_xx)
-  hipStream_t stream_x = nullptr;
-  hipEvent_t ev_x1 = nullptr, ev_w[3] = {nullptr, nullptr, nullptr}, ev_x[3] = {nullptr, nullptr, nullptr};
+  StreamOwner stream_x;
+  EventOwner ev_x1, ev_w[3], ev_x[3];
   // The solve's products with V that stand outside its two chains, many stages per launch (k_st_symv_*_batch; not
   // sharded): [0] g_k = V_{k+1} f_k ahead of the backward sweep, [1] the dynamics rows' multipliers behind the forward
   // sweep.  A launch holds the stages whose partial sums fit StagedPlan::symb_elems; stages that do not take the
@@ -59,15 +58,15 @@ struct StagedDev {
   // second stream: the control-sized chain of a stage (G_u strip, H's control part, carried rows, K^-1, Y, Rm)
   // runs beside the large product G_xx = fx'W_x instead of behind it (fork / join by events; inside a
   // captured sequence these are parallel branches of the graph)
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  StreamOwner stream2;
+  EventOwner ev_fork, ev_join;
   bool overlap = false;
   int overlap_mode = 0;  // 0 never, 1 every stage, 2 stages of 1280 .. 4096 states
   // order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map), by T
-  std::vector<std::pair<int, DBuf<int> *>> tri_maps;
+  std::vector<std::pair<int, DBuf<int>>> tri_maps;
   const int *tri_map(int T, bool create = false) {
     for (auto &e : tri_maps)
-      if (e.first == T) return e.second->p;
+      if (e.first == T) return e.second.p;
     if (!create) return nullptr;  // (made at upload time: no allocation inside a captured sequence)
     std::vector<int> m;
     m.reserve((size_t)T * (T + 1) / 2);
@@ -76,13 +75,10 @@ struct StagedDev {
       for (int J = 0; J <= I; J++)
         for (int tn = J * S; tn < std::min(T, (J + 1) * S); tn++)
           for (int tm = std::max(I * S, tn); tm < std::min(T, (I + 1) * S); tm++) m.push_back(tm << 16 | tn);
-    DBuf<int> *b = new (std::nothrow) DBuf<int>;
-    if (!b || b->upload(m)) {
-      delete b;
-      return nullptr;
-    }
-    tri_maps.push_back({T, b});
-    return b->p;
+    DBuf<int> b;
+    if (b.upload(m)) return nullptr;
+    tri_maps.emplace_back(T, std::move(b));
+    return tri_maps.back().second.p;
   }
   // work lists of the cut form of the large products (stg::gemm_split_table: unequal shares for the two workgroups of a
   // CU), by (tiles, k-slabs); made at upload time for the shapes of the recursion - a shape without one (or
@@ -90,26 +86,25 @@ struct StagedDev {
   struct SkTab {
     long long tiles, nslab, pieces;
     int stride;
-    DBuf<stg::SkUnit> *units;
+    DBuf<stg::SkUnit> units;
   };
   std::vector<SkTab> sk_tabs;
   bool sk_tables_on = true;
   const SkTab *sk_tab(long long tiles, long long nslab, bool create = false) {
     if (!sk_tables_on || sk_grid <= 0) return nullptr;
     for (auto &e : sk_tabs)
-      if (e.tiles == tiles && e.nslab == nslab) return e.units ? &e : nullptr;
+      if (e.tiles == tiles && e.nslab == nslab) return e.units.p ? &e : nullptr;
     if (!create) return nullptr;  // (no allocation inside a captured sequence)
     stg::SplitTable t;
-    SkTab e{tiles, nslab, 0, 0, nullptr};
+    SkTab e{tiles, nslab, 0, 0, {}};
     if (stg::gemm_split_table(tiles, nslab, sk_grid, t) && t.pieces * 128LL * 128 <= sk_ws_elems && tiles <= sk_tiles) {
-      DBuf<stg::SkUnit> *b = new (std::nothrow) DBuf<stg::SkUnit>;
-      if (b && !b->upload(t.units))
-        e.units = b, e.stride = t.stride, e.pieces = t.pieces;
+      if (!e.units.upload(t.units))
+        e.stride = t.stride, e.pieces = t.pieces;
       else
-        delete b;
+        e.units.release();
     }
-    sk_tabs.push_back(e);
-    return e.units ? &sk_tabs.back() : nullptr;
+    sk_tabs.push_back(std::move(e));
+    return sk_tabs.back().units.p ? &sk_tabs.back() : nullptr;
   }
   // (the shape of a product as st_gemm launches it)
   void sk_tab_prepare(int M, int N, int K, int lower) {
@@ -119,30 +114,6 @@ struct StagedDev {
   }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
   long long sk_ws_elems = 0, sk_cnt_elems = 0;
-  void release() {
-    F.release(), V.release(), misc.release();
-    dyn.release(), eq_rows.release(), fix_rows.release(), fix_src.release(), h_tptr.release();
-    chk_idx.release(), chk_kind.release(), h_dst.release(), a_dst.release(), h_terms.release();
-    dyn_desc.release(), dyn_x1.release(), dyn_x2.release(), dyn_part.release(), sk_ws.release(), ks_ws2.release(), sk_cnt.release(), zeros.release();
-    wtabs.release(), rtabs.release(), gtile.release(), gowned.release(), prects.release(), dyn_loc.release(), dyn_sum.release();
-    if (stream_x) (void)hipStreamDestroy(stream_x), stream_x = nullptr;
-    for (hipEvent_t *ev : {&ev_w[0], &ev_w[1], &ev_w[2], &ev_x[0], &ev_x[1], &ev_x[2]})
-      if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
-    if (ev_x1) (void)hipEventDestroy(ev_x1), ev_x1 = nullptr;
-    for (int b = 0; b < 2; b++) {
-      if (hblk[b]) (void)hipHostFree(hblk[b]), hblk[b] = nullptr;
-      if (hblk_ev[b]) (void)hipEventDestroy(hblk_ev[b]), hblk_ev[b] = nullptr;
-    }
-    hblk_elems = 0, blocks_set.clear();
-    for (auto &e : tri_maps) e.second->release(), delete e.second;
-    tri_maps.clear();
-    for (auto &e : sk_tabs)
-      if (e.units) e.units->release(), delete e.units;
-    sk_tabs.clear();
-    if (stream2) (void)hipStreamDestroy(stream2), stream2 = nullptr;
-    if (ev_fork) (void)hipEventDestroy(ev_fork), ev_fork = nullptr;
-    if (ev_join) (void)hipEventDestroy(ev_join), ev_join = nullptr;
-  }
 };
 
 namespace {
@@ -173,7 +144,7 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
 // C = alpha A'B + beta Cin on the handle's stream; 128 x 128 tiles for large products, 64 x 64 below
 int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true) {
   if (g.M <= 0 || g.N <= 0) return 0;
-  StagedDev *d = h->sd;
+  StagedDev *d = h->sd.get();
   // operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd
   // column (the control columns F + nn of a stage with an odd number of states) is staged through registers
   const bool al16 = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0);
@@ -199,7 +170,7 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
     stg::SplitPlan sk = frac ? stg::gemm_split_plan_frac(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, d->sk_grid)
                              : stg::gemm_split_plan(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, d->sk_grid);
     const StagedDev::SkTab *tab = frac ? nullptr : d->sk_tab(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, !h->capturing);
-    if (tab) sk.table = tab->units->p, sk.stride = tab->stride;
+    if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
     if (frac || tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d->sk_ws_elems) {
       sk.ws = d->sk_ws.p, sk.cnt = d->sk_cnt.p;
       KLAUNCH(h, cls, stg::gemm_launch_split(d->gemm_variant, d->sk_grid, h->stream, g, sk));
@@ -418,8 +389,7 @@ static int st_rm(hqpkkt_t *h, StagedDev &d, const StagePtr &sp, int k, bool allo
 }
 
 static int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn = false) {
-  if (!h->sd) h->sd = new (std::nothrow) StagedDev;
-  if (!h->sd) return HQPKKT_E_MEM;
+  if (!h->sd) h->sd.reset(new StagedDev);
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
@@ -478,30 +448,30 @@ static int staged_upload(hqpkkt_t *h) {
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   const int n = an.n, me = an.me, m = an.m;
-  if ((e = h->Qf.upload(an.Qfull)) || (e = h->A.upload(an.A)) || (e = h->AT.upload(an.AT)) ||
-      (e = h->C.upload(an.C)) || (e = h->CT.upload(an.CT)))
+  if ((e = h->td.Qf.upload(an.Qfull)) || (e = h->td.A.upload(an.A)) || (e = h->td.AT.upload(an.AT)) ||
+      (e = h->td.C.upload(an.C)) || (e = h->td.CT.upload(an.CT)))
     return e;
   const size_t nv = (size_t)an.nq + an.na + an.nc + 1;
-  if ((e = h->vals.alloc(nv)) || (e = h->wt.alloc(m + 1)) || (e = h->flags.alloc(128)) ||
-      (e = h->vin.alloc(2 * (size_t)m + n + me + 2 * (size_t)m)) ||
-      (e = h->vout.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->vres.alloc((size_t)n + me + 2 * (size_t)m)) ||
-      (e = h->vcor.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->tz.alloc(m)))
+  if ((e = h->td.vals.alloc(nv)) || (e = h->td.wt.alloc(m + 1)) || (e = h->td.flags.alloc(128)) ||
+      (e = h->td.vin.alloc(2 * (size_t)m + n + me + 2 * (size_t)m)) ||
+      (e = h->td.vout.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->td.vres.alloc((size_t)n + me + 2 * (size_t)m)) ||
+      (e = h->td.vcor.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->td.tz.alloc(m)))
     return e;
-  h->bits.p = (unsigned long long *)(h->flags.p + 120);
+  h->td.bits.p = (unsigned long long *)(h->td.flags.p + 120);
   if ((e = alloc_hpin(h))) return e;
-  if (h->hstage) (void)hipHostFree(h->hstage), h->hstage = nullptr;
-  h->hstage_in = h->hstage_out = 0;
+  h->td.hstage.release();
+  h->td.hstage_in = h->td.hstage_out = 0;
   {
     const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
     if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
-      HIPCHK(hipHostMalloc((void **)&h->hstage, sizeof(double) * (nin + nout), hipHostMallocDefault));
-      h->hstage_in = nin, h->hstage_out = nout;
+      HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocDefault));
+      h->td.hstage_in = nin, h->td.hstage_out = nout;
     }
   }
   {
     const double one = 1.0;
-    HIPCHK(hipMemcpy(h->vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
     const double rows = 2.0 * n + me + m;
     const double nnz = (double)an.Qfull.col.size() + 2.0 * an.A.col.size() + 2.0 * an.C.col.size();
     h->short_rows = rows > 0 && nnz / rows < 8.0;
@@ -602,10 +572,10 @@ static int staged_upload(hqpkkt_t *h) {
         // a launch that fills every CU otherwise waits a whole tile time for each of its launches)
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&d.stream2, hipStreamNonBlocking, hi));
+        HIPCHK(hipStreamCreateWithPriority(&d.stream2.h, hipStreamNonBlocking, hi));
       }
-      HIPCHK(hipEventCreateWithFlags(&d.ev_fork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&d.ev_fork.h, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&d.ev_join.h, hipEventDisableTiming));
     }
     d.overlap = d.stream2 != nullptr && d.overlap_mode != 0;
     d.ks_ws2_elems = 0;
@@ -674,11 +644,11 @@ static int staged_upload(hqpkkt_t *h) {
     if ((e = d.wtabs.upload(wt)) || (e = d.rtabs.upload(rt)) || (e = d.prects.upload(pr)) || (e = d.gtile.upload(gt)) ||
         (e = d.gowned.upload(ow)))
       return e;
-    if (!d.ev_x1) HIPCHK(hipEventCreateWithFlags(&d.ev_x1, hipEventDisableTiming));
+    if (!d.ev_x1) HIPCHK(hipEventCreateWithFlags(&d.ev_x1.h, hipEventDisableTiming));
     if (h->xchg_sfn && !d.stream_x) {
-      HIPCHK(hipStreamCreateWithFlags(&d.stream_x, hipStreamNonBlocking));
-      for (hipEvent_t *ev : {&d.ev_w[0], &d.ev_w[1], &d.ev_w[2], &d.ev_x[0], &d.ev_x[1], &d.ev_x[2]})
-        HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      HIPCHK(hipStreamCreateWithFlags(&d.stream_x.h, hipStreamNonBlocking));
+      for (EventOwner *ev : {&d.ev_w[0], &d.ev_w[1], &d.ev_w[2], &d.ev_x[0], &d.ev_x[1], &d.ev_x[2]})
+        HIPCHK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
     }
   }
   // orders of the tiles of the triangular products (G, V)
@@ -791,19 +761,19 @@ static int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, co
       if (!Fblk[k] || ldF[k] < nz) return HQPKKT_E_SIZES;
       if ((e = staged_copy_block(h, k, Fblk[k], ldF[k], kind))) return e;
     }
-  if (an.nq) HIPCHK(hipMemcpyAsync(h->vals.p, Qx, sizeof(double) * an.nq, kind, s));
-  if (an.na) HIPCHK(hipMemcpyAsync(h->vals.p + an.nq, Ax, sizeof(double) * an.na, kind, s));
-  if (an.nc) HIPCHK(hipMemcpyAsync(h->vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, s));
-  for (CsrBuf *c : {&h->Qf, &h->A, &h->AT, &h->C, &h->CT})
+  if (an.nq) HIPCHK(hipMemcpyAsync(h->td.vals.p, Qx, sizeof(double) * an.nq, kind, s));
+  if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, s));
+  if (an.nc) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, s));
+  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
     if (c->src.count)
-      k_gather_values<<<nblk((long long)c->src.count), 256, 0, s>>>((int)c->src.count, c->src.p, h->vals.p, c->val.p);
-  HIPCHK(hipMemsetAsync(h->flags.p, 0, sizeof(int) * 128, s));
+      k_gather_values<<<nblk((long long)c->src.count), 256, 0, s>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
+  HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
   if (an.na)
-    stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.a_dst.p, h->vals.p + an.nq, d.F.p, d.misc.p);
+    stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
   const int nchk = (int)P.chk_idx.size();
-  if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.chk_idx.p, d.chk_kind.p, h->vals.p, h->flags.p);
-  int *hs = (int *)h->hpin;
-  HIPCHK(hipMemcpyAsync(hs, h->flags.p, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
+  if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.chk_idx.p, d.chk_kind.p, h->td.vals.p, h->td.flags.p);
+  int *hs = (int *)h->kept.hpin.p;
+  HIPCHK(hipMemcpyAsync(hs, h->td.flags.p, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (hs[0]) return HQPKKT_E_FORMAT;  // not the -1.0 staircase (hqp/Hqp_IpLQDOCP.C:214-215) / a zero that fixes x_0
   h->have_values = true;
@@ -815,7 +785,7 @@ static int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, co
 // cut when they do not fill the chip (k_dgemm_tn_sk), one plain round otherwise
 static int st_gemm_tiles(hqpkkt_t *h, stg::GemmArgs g, int ntiles, int cls) {
   if (ntiles <= 0 || g.M <= 0 || g.N <= 0) return 0;
-  StagedDev *d = h->sd;
+  StagedDev *d = h->sd.get();
   const bool al16 = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && ((g.lda & 1) == 0);
   if (d->zeros.p && al16) g.zeros = d->zeros.p;
   const int variant = g.zeros ? d->gemm_variant : stg::GEMM_REG4;
@@ -823,7 +793,7 @@ static int st_gemm_tiles(hqpkkt_t *h, stg::GemmArgs g, int ntiles, int cls) {
   if (d->sk_grid > 0 && ntiles % d->sk_grid != 0 && ntiles < 16LL * d->sk_grid && nslab >= 32 && ntiles <= d->sk_tiles) {
     stg::SplitPlan sk = stg::gemm_split_plan(ntiles, nslab, d->sk_grid);
     const StagedDev::SkTab *tab = d->sk_tab(ntiles, nslab, !h->capturing);
-    if (tab) sk.table = tab->units->p, sk.stride = tab->stride;
+    if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
     if (tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d->sk_ws_elems) {
       sk.ws = d->sk_ws.p, sk.cnt = d->sk_cnt.p;
       KLAUNCH(h, cls, stg::gemm_launch_split(variant, d->sk_grid, h->stream, g, sk));
@@ -903,7 +873,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   auto add_h = [&](int first, int count) {
     if (count)
       KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
-                                                                                 h->vals.p, h->wt.p, G, 1));
+                                                                                 h->td.vals.p, h->td.wt.p, G, 1));
   };
   // the next stage's F blocks travel while this stage is computed (its buffer's last readers, the stage before this one,
   // are behind us in the first stream)
@@ -946,7 +916,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   add_h(P.h_mid[k], ne_u);
   {
     stg::SmallArgs sa{G, ldg, nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
-                      P.capn[k], P.cap[k], q, h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->flags.p,
+                      P.capn[k], P.cap[k], q, h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->td.flags.p,
                       P.big[k] ? d.misc.p + P.oScr : nullptr};
     if (P.big[k]) {
       if ((e = st_small_big(h, d, sa, !two))) return e;
@@ -973,7 +943,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   }
   if (ne_x)  // H_xx into the rank's own tiles only (everything else in G is left over from earlier stages and read by nobody)
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_owned<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
-                                                                                  h->vals.p, h->wt.p, G, ldg, d.gowned.p + d.gowned_off[k], (nn + 127) / 128));
+                                                                                  h->td.vals.p, h->td.wt.p, G, ldg, d.gowned.p + d.gowned_off[k], (nn + 127) / 128));
   const int npk = d.prect_ptr[k + 1] - d.prect_ptr[k];
   if (npk > 0)
     KLAUNCH(h, KC_ST_VEC, stg::k_st_pack_rects<<<dim3(512, npk), 256, 0, sA>>>(d.prects.p + d.prect_ptr[k], G, ldg, xb + (long long)RK * P.xslot[k]));
@@ -1012,10 +982,10 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   int e;
   {  // the status words and V_K cleared by one kernel (no memset nodes in the captured sequence: kernels.hip.h, k_clear)
     const long long vk = (long long)P.nk[K] * P.ldv[K];
-    kktdev::k_clear<<<(int)std::max<long long>(1, std::min<long long>(4096, (vk / 2 + 1023) / 1024)), 256, 0, s>>>(stage_ptr(d, K).V, vk, h->flags.p);
+    kktdev::k_clear<<<(int)std::max<long long>(1, std::min<long long>(4096, (vk / 2 + 1023) / 1024)), 256, 0, s>>>(stage_ptr(d, K).V, vk, h->td.flags.p);
   }
   if (!h->capturing) HIPCHK(hipEventRecord(h->ev0, s));
-  if (m > 0) KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(1, m, an.n + an.me, z, w, h->wt.p, nullptr, h->flags.p));
+  if (m > 0) KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(1, m, an.n + an.me, z, w, h->td.wt.p, nullptr, h->td.flags.p));
   if (!h->capturing) HIPCHK(hipEventRecord(h->ev1, s));
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
   {  // last stage: V_K = H_K, all its equality rows are carried
@@ -1024,7 +994,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     const int ne = P.h_ptr[K + 1] - P.h_ptr[K];
     if (ne)
       KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(ne), 256, 0, s>>>(ne, d.h_dst.p + P.h_ptr[K], d.h_tptr.p + P.h_ptr[K], d.h_terms.p,
-                                                                       h->vals.p, h->wt.p, sp.V, 0));
+                                                                       h->td.vals.p, h->td.wt.p, sp.V, 0));
     KLAUNCH(h, KC_ST_SMALL, stg::k_st_last<<<nblk(std::max(nK, 1)), 256, 0, s>>>(nK, eK, P.cap[K], sp.N, P.ldn[K], sp.BT, P.ldb[K], sp.dyn));
     if (P.sharded) {  // this rank's rows of V_K for the solve
       const int c0 = P.xcut[(size_t)K * (P.shard_count + 1) + P.shard_rank], wd = P.xcut[(size_t)K * (P.shard_count + 1) + P.shard_rank + 1] - c0;
@@ -1057,7 +1027,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     auto add_h = [&](int first, int count) {
       if (count)
         KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
-                                                                                   h->vals.p, h->wt.p, G, 1));
+                                                                                   h->td.vals.p, h->td.wt.p, G, 1));
     };
     // ---- W
     if ((e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}))) return e;
@@ -1086,7 +1056,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
                                       P.cap[k + 1], nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, !ovl)))
       return e;
     stg::SmallArgs sa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
-                      P.capn[k], P.cap[k], P.qmax[k], h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->flags.p,
+                      P.capn[k], P.cap[k], P.qmax[k], h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->td.flags.p,
                       P.big[k] ? d.misc.p + P.oScr : nullptr};
     if (P.big[k]) {
       if ((e = st_small_big(h, d, sa, !ovl))) return e;
@@ -1113,7 +1083,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   {
     StagePtr s0 = stage_ptr(d, 0);
     if (P.fixed_x0)
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_check_fixed<<<1, 64, 0, s>>>(s0.dyn, h->flags.p));
+      KLAUNCH(h, KC_ST_SMALL, stg::k_st_check_fixed<<<1, 64, 0, s>>>(s0.dyn, h->td.flags.p));
     else if (P.big0) {
       // the inverse by the blocked sweep on the whole chip, checked against K0; the LU factorisation by one workgroup
       // behind it runs only where the sweep gave up (decided on the device)
@@ -1123,7 +1093,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
       const int q = P.q0max;
       if (!legacy0) {
         const stg::X0Args xa{P.nk[0], q, s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn, d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s,
-                             P.ldq0, scr, h->flags.p};
+                             P.ldq0, scr, h->td.flags.p};
         KLAUNCH(h, KC_ST_SMALL, stg::k_x0_prepare<<<nblk((long long)q * q), 256, 0, s>>>(xa));
         if ((e = st_blk_sweep(h, scr, q, true))) return e;
         KLAUNCH(h, KC_ST_SMALL, stg::k_x0_final<<<nblk((long long)q * q), 256, 0, s>>>(xa));
@@ -1133,11 +1103,11 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
         KLAUNCH(h, KC_ST_SMALL, stg::k_x0_check<<<1, 1024, 0, s>>>(xa, tol0));
       }
       KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<1024><<<1, 1024, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
-                                                                                    d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->flags.p,
+                                                                                    d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p,
                                                                                     scr, legacy0 ? nullptr : stg::big_scratch(scr, q).flags));
     } else
       KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<256><<<1, 256, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
-                                                                                  d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->flags.p, nullptr, nullptr));
+                                                                                  d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p, nullptr, nullptr));
   }
   if (!h->capturing) HIPCHK(hipEventRecord(h->evs1, s));
   HIPCHK(hipGetLastError());
@@ -1162,8 +1132,8 @@ static int staged_run_step_sharded(hqpkkt_t *h, const Vecs &v) {
   int e;
   const long long ndx = (long long)P.ndyn + (P.fixed_x0 ? P.nk[0] : 0);
   KLAUNCH(h, KC_ST_VEC, stg::k_st_zero<<<nblk(std::max<long long>(ndx, 1)), 256, 0, s>>>(ndx, dyx));
-  if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->wt.p, v.r3, v.r4, h->tz.p));
-  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->CT.ptr.p, h->CT.col.p, h->CT.src.p, h->vals.p, h->tz.p, v.r1, qv));
+  if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
+  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->td.CT.ptr.p, h->td.CT.col.p, h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv));
   {  // last stage
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
@@ -1194,7 +1164,7 @@ static int staged_run_step_sharded(hqpkkt_t *h, const Vecs &v) {
     StagePtr s0 = stage_ptr(d, 0);
     const int n0 = P.nk[0];
     if (P.fixed_x0)
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->vals.p, v.r2, S,
+      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, v.r2, S,
                                                                                          s0.eta, P.cap[0]));
     else {
       // the free initial state needs v_0 in full: gathered
@@ -1253,11 +1223,11 @@ static int staged_run_step_sharded(hqpkkt_t *h, const Vecs &v) {
       return e;
     if (ndx > 0 && (e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, dyx, ndx, 1, nullptr))) return e;
     if (P.ndyn > 0) KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(P.ndyn), 256, 0, s>>>(P.ndyn, dyx, v.dy));
-    if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->vals.p, dyx + P.ndyn, v.dy));
+    if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, dyx + P.ndyn, v.dy));
   }
   KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
   if (m > 0)
-    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->C.ptr.p, h->C.col.p, h->C.src.p, h->vals.p, v.dx, h->wt.p, h->tz.p,
+    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p,
                                                              v.r3, v.dz, v.dw));
   HIPCHK(hipGetLastError());
   return 0;
@@ -1274,8 +1244,8 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   double *M = d.misc.p;
   double *S = M + P.oS, *qv = M + P.oQv, *gam = M + P.oGam, *tt = M + P.oTT, *tmp = M + P.oTmp;
   int e;
-  if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->wt.p, v.r3, v.r4, h->tz.p));
-  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->CT.ptr.p, h->CT.col.p, h->CT.src.p, h->vals.p, h->tz.p, v.r1, qv));
+  if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
+  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->td.CT.ptr.p, h->td.CT.col.p, h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv));
   // The products with V are not part of the sweeps' chains: V+ f (f: the dynamics' right-hand side) is known before the
   // backward sweep starts, the dynamics rows' multipliers are wanted by nobody before the forward sweep is over - both
   // for many stages per launch (staged_symv_group), which leaves the F products and the control-sized kernels in the
@@ -1314,7 +1284,7 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     StagePtr s0 = stage_ptr(d, 0);
     const int n0 = P.nk[0];
     if (P.fixed_x0)
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->vals.p, v.r2, S,
+      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, v.r2, S,
                                                                                          s0.eta, P.cap[0]));
     else {
       if (P.big0) {
@@ -1361,12 +1331,12 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     if (P.fixed_x0) {
       const int n0 = P.nk[0];
       if ((e = st_symv(h, d, stg::GemvRows{s0.V, P.ldv[0], n0, n0, S, s0.v, nullptr, 0, nullptr, nullptr, tmp, 1.0}))) return e;
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->vals.p, tmp, v.dy));
+      KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, tmp, v.dy));
     }
   }
   KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
   if (m > 0)
-    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->C.ptr.p, h->C.col.p, h->C.src.p, h->vals.p, v.dx, h->wt.p, h->tz.p,
+    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p,
                                                              v.r3, v.dz, v.dw));
   HIPCHK(hipGetLastError());
   return 0;

@@ -18,13 +18,8 @@ int ensure_device(hqpkkt_t *h) {
   }
   HIPCHK(hipSetDevice(h->opts.device));
   if (!h->own_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&h->ev0));
-    HIPCHK(hipEventCreate(&h->ev1));
-    HIPCHK(hipEventCreate(&h->evs0));
-    HIPCHK(hipEventCreate(&h->evs1));
-    HIPCHK(hipEventCreate(&h->evt0));
-    HIPCHK(hipEventCreate(&h->evt1));
+    HIPCHK(hipStreamCreateWithFlags(&h->own_stream.h, hipStreamNonBlocking));
+    for (EventOwner *ev : {&h->ev0, &h->ev1, &h->evs0, &h->evs1, &h->evt0, &h->evt1}) HIPCHK(hipEventCreate(&ev->h));
   }
   if (!h->stream) h->stream = h->own_stream;
   return 0;
@@ -33,7 +28,7 @@ int ensure_device(hqpkkt_t *h) {
 // the exchange arrays of k_solve_top in their idle state: every word the sentinel, counters zero
 static int reset_solve_top(hqpkkt_t *h) {
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->tree_words.p) HIPCHK(hipMemset(h->tree_words.p, 0, sizeof(int) * 2));
+  if (h->td.tree_words.p) HIPCHK(hipMemset(h->td.tree_words.p, 0, sizeof(int) * 2));
   auto fill = [&](DBuf<double> &buf, size_t count) -> int {
     std::vector<double> f(count);
     for (auto &x : f) std::memcpy(&x, &XW_SENTINEL, sizeof(double));
@@ -42,11 +37,11 @@ static int reset_solve_top(hqpkkt_t *h) {
   };
   int e;
   if (h->top_n > 0) {
-    if ((e = fill(h->top_x, 2 * (size_t)h->top_n * (ST_CS + ST_XS)))) return e;
+    if ((e = fill(h->td.top_x, 2 * (size_t)h->top_n * (ST_CS + ST_XS)))) return e;
   }
   if (h->small_tree) {
-    if ((e = fill(h->tree_x, 2 * (size_t)(h->an.cb_elems + h->an.dim)))) return e;
-    if (h->tree_factor && (e = fill(h->tree_u, 2 * (size_t)std::max<long long>(h->an.upd_elems, 1)))) return e;
+    if ((e = fill(h->td.tree_x, 2 * (size_t)(h->an.cb_elems + h->an.dim)))) return e;
+    if (h->tree_factor && (e = fill(h->td.tree_u, 2 * (size_t)std::max<long long>(h->an.upd_elems, 1)))) return e;
 
   }
   return 0;
@@ -55,7 +50,7 @@ static int reset_solve_top(hqpkkt_t *h) {
 bool poll_fallback(hqpkkt_t *h, const int *hs) {
   if (!hs[XW_GAVE_UP]) return false;
   (void)reset_solve_top(h);
-  (void)hipMemsetAsync(h->flags.p + XW_GAVE_UP, 0, sizeof(int), h->stream);
+  (void)hipMemsetAsync(h->td.flags.p + XW_GAVE_UP, 0, sizeof(int), h->stream);
   (void)hipStreamSynchronize(h->stream);
   h->top_n = 0, h->small_tree = false, h->tree_factor = false, h->no_polled = true;  // (no_polled: a later upload stays there)
   h->drop_graphs();
@@ -64,16 +59,17 @@ bool poll_fallback(hqpkkt_t *h, const int *hs) {
   return true;
 }
 
-// the mapped, coherent host words of the read-backs (hqpkkt::hpin; both engines)
+// the mapped, coherent host words of the read-backs (hqpkkt::Kept::hpin; both engines)
 int alloc_hpin(hqpkkt_t *h) {
-  if (h->hpin) return 0;
-  HIPCHK(hipHostMalloc((void **)&h->hpin, sizeof(double) * HPIN_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(h->hpin, 0, sizeof(double) * HPIN_DOUBLES);
-  HIPCHK(hipHostGetDevicePointer((void **)&h->hpin_dev, h->hpin, 0));
+  PinnedBuf<double> &hp = h->kept.hpin;
+  if (hp.p) return 0;
+  HIPCHK(hp.alloc(HPIN_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(hp.p, 0, sizeof(double) * HPIN_DOUBLES);
+  HIPCHK(hp.map());
   h->post_seq = 0;
-  int e = h->post_seq_dev.alloc(1);
+  int e = h->kept.post_seq_dev.alloc(1);
   if (e) return e;
-  HIPCHK(hipMemset(h->post_seq_dev.p, 0, sizeof(unsigned)));
+  HIPCHK(hipMemset(h->kept.post_seq_dev.p, 0, sizeof(unsigned)));
   return 0;
 }
 int upload(hqpkkt_t *h) {
@@ -81,7 +77,7 @@ int upload(hqpkkt_t *h) {
   if (e) return e;
   Analysis &an = h->an;
 #define UP(buf, vec) \
-  if ((e = h->buf.upload(an.vec))) return e
+  if ((e = h->td.buf.upload(an.vec))) return e
   UP(piv_start, piv_start);
   UP(npiv, npiv);
   UP(nbor, nbor);
@@ -118,7 +114,7 @@ int upload(hqpkkt_t *h) {
     std::vector<TermDev> t(an.terms.size());
     for (size_t k = 0; k < t.size(); k++)
       t[k] = TermDev{an.terms[k].s1, an.terms[k].s2, an.terms[k].wi, an.terms[k].sgn};
-    if ((e = h->terms.upload(t))) return e;
+    if ((e = h->td.terms.upload(t))) return e;
     // all entries single terms sgn * vals[s1] * wt[wi] with s2 = the constant 1 (FULL plugin)?
     const int one = an.nq + an.na + an.nc;
     bool simple = an.mode == 0 && an.terms.size() == an.ent_a.size();
@@ -127,7 +123,7 @@ int upload(hqpkkt_t *h) {
     if (simple) {
       std::vector<int> ss(t.size()), ww(t.size());
       for (size_t k = 0; k < t.size(); k++) ss[k] = t[k].s1 | (t[k].sgn < 0 ? (int)0x80000000 : 0), ww[k] = t[k].wi;
-      if ((e = h->simple_src.upload(ss)) || (e = h->simple_wi.upload(ww))) return e;
+      if ((e = h->td.simple_src.upload(ss)) || (e = h->td.simple_wi.upload(ww))) return e;
     }
     // sign a perturbed pivot takes: x rows belong to the -Q block, y / slack rows
     // to the zero / +W/Z blocks
@@ -143,46 +139,45 @@ int upload(hqpkkt_t *h) {
       if (!diag) sg[an.q2e[q]] = -2;
     }
     for (int q = an.n; q < an.n + an.me; q++) sg[an.q2e[q]] = 2;
-    if ((e = h->esign.upload(sg))) return e;
+    if ((e = h->td.esign.upload(sg))) return e;
   }
-  if ((e = h->Qf.upload(an.Qfull)) || (e = h->A.upload(an.A)) || (e = h->AT.upload(an.AT)) ||
-      (e = h->C.upload(an.C)) || (e = h->CT.upload(an.CT)))
+  if ((e = h->td.Qf.upload(an.Qfull)) || (e = h->td.A.upload(an.A)) || (e = h->td.AT.upload(an.AT)) ||
+      (e = h->td.C.upload(an.C)) || (e = h->td.CT.upload(an.CT)))
     return e;
   const int n = an.n, me = an.me, m = an.m, dim = an.dim;
   const size_t nv = (size_t)an.nq + an.na + an.nc + 1;
-  if ((e = h->vals.alloc(nv)) || (e = h->wt.alloc(m + 1)) || (e = h->sc.alloc(dim)) ||
-      (e = h->ent_val.alloc(an.ent_a.size())) || (e = h->panel.alloc(an.panel_elems)) ||
-      (e = h->upd.alloc(an.upd_elems)) || (e = h->xar.alloc(an.x_elems)) ||
-      (e = h->dinv.alloc(2 * (size_t)dim)) || (e = h->rhs.alloc(dim)) ||
-      (e = h->xsol.alloc(dim)) || (e = h->cb.alloc(an.cb_elems)) || (e = h->ytmp.alloc(std::max(dim, 8))) ||
-      (e = h->vtmp.alloc(dim)) || (e = h->linv.alloc(an.linv_elems)) || (e = h->ptype.alloc(dim)) ||
-      (e = h->lperm.alloc(dim)) || (e = h->flags.alloc(128)) ||
-      (e = h->vin.alloc(2 * (size_t)m + n + me + 2 * (size_t)m)) ||
-      (e = h->vout.alloc((size_t)n + me + 2 * (size_t)m)) ||
-      (e = h->vres.alloc((size_t)n + me + 2 * (size_t)m)) ||
-      (e = h->vcor.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->tz.alloc(m)))
+  if ((e = h->td.vals.alloc(nv)) || (e = h->td.wt.alloc(m + 1)) || (e = h->td.sc.alloc(dim)) ||
+      (e = h->td.ent_val.alloc(an.ent_a.size())) || (e = h->td.panel.alloc(an.panel_elems)) ||
+      (e = h->td.upd.alloc(an.upd_elems)) || (e = h->td.xar.alloc(an.x_elems)) ||
+      (e = h->td.dinv.alloc(2 * (size_t)dim)) || (e = h->td.rhs.alloc(dim)) ||
+      (e = h->td.xsol.alloc(dim)) || (e = h->td.cb.alloc(an.cb_elems)) || (e = h->td.ytmp.alloc(std::max(dim, 8))) ||
+      (e = h->td.vtmp.alloc(dim)) || (e = h->td.linv.alloc(an.linv_elems)) || (e = h->td.ptype.alloc(dim)) ||
+      (e = h->td.lperm.alloc(dim)) || (e = h->td.flags.alloc(128)) ||
+      (e = h->td.vin.alloc(2 * (size_t)m + n + me + 2 * (size_t)m)) ||
+      (e = h->td.vout.alloc((size_t)n + me + 2 * (size_t)m)) ||
+      (e = h->td.vres.alloc((size_t)n + me + 2 * (size_t)m)) ||
+      (e = h->td.vcor.alloc((size_t)n + me + 2 * (size_t)m)) || (e = h->td.tz.alloc(m)))
     return e;
-  h->bits.p = (unsigned long long *)(h->flags.p + 120);
-  HIPCHK(hipMemset(h->flags.p, 0, sizeof(int) * 128));
+  h->td.bits.p = (unsigned long long *)(h->td.flags.p + 120);
+  HIPCHK(hipMemset(h->td.flags.p, 0, sizeof(int) * 128));
   h->res_read = 122;
   if ((e = alloc_hpin(h))) return e;
-  if (h->hstage) (void)hipHostFree(h->hstage), h->hstage = nullptr, h->hstage_dev = nullptr;
-  h->hstage_in = h->hstage_out = 0;
+  h->td.hstage.release();
+  h->td.hstage_in = h->td.hstage_out = 0;
   {
     const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
     if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
-      HIPCHK(hipHostMalloc((void **)&h->hstage, sizeof(double) * (nin + nout), hipHostMallocMapped | hipHostMallocCoherent));
-      h->hstage_in = nin, h->hstage_out = nout;
-      h->hstage_dev = nullptr;
-      if (hipHostGetDevicePointer((void **)&h->hstage_dev, h->hstage, 0) != hipSuccess) h->hstage_dev = nullptr, (void)hipGetLastError();
+      HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocMapped | hipHostMallocCoherent));
+      h->td.hstage_in = nin, h->td.hstage_out = nout;
+      if (h->td.hstage.map() != hipSuccess) (void)hipGetLastError();
     }
   }
   {
     std::vector<double> ones(dim, 1.0);
-    HIPCHK(hipMemcpy(h->sc.p, ones.data(), sizeof(double) * dim, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->td.sc.p, ones.data(), sizeof(double) * dim, hipMemcpyHostToDevice));
     const double one = 1.0;
-    HIPCHK(hipMemcpy(h->vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
   }
   // dynamic LDS budgets
   const size_t mp = an.max_npiv;
@@ -201,7 +196,7 @@ int upload(hqpkkt_t *h) {
   }
   {  // the counters of the polled exchanges: [0] solves, [1] factorisations so far (k_rhs_*, the assembly kernels count)
     std::vector<int> two(2, 0);
-    if ((e = h->tree_words.upload(two))) return e;
+    if ((e = h->td.tree_words.upload(two))) return e;
   }
   {  // tries before a poll gives up (HQPKKT_POLL_LIMIT: a test hook that forces the fall-back of poll_fallback)
     const char *pl = getenv("HQPKKT_POLL_LIMIT");
@@ -220,10 +215,10 @@ int upload(hqpkkt_t *h) {
       std::vector<int> down, one(2, 0);
       for (int l = an.nlevels - 1; l >= 0; l--)
         for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; q++) down.push_back(S.level_nodes[q]);
-      if ((e = h->tree_down.upload(down)) || (e = h->tree_x.alloc(2 * (size_t)(an.cb_elems + an.dim)))) return e;
+      if ((e = h->td.tree_down.upload(down)) || (e = h->td.tree_x.alloc(2 * (size_t)(an.cb_elems + an.dim)))) return e;
       h->small_tree = true;
       h->tree_factor = !an.upd_pingpong;
-      if (h->tree_factor && (e = h->tree_u.alloc(2 * (size_t)std::max<long long>(an.upd_elems, 1)))) return e;
+      if (h->tree_factor && (e = h->td.tree_u.alloc(2 * (size_t)std::max<long long>(an.upd_elems, 1)))) return e;
       if ((e = reset_solve_top(h))) return e;
     }
   }
@@ -270,8 +265,8 @@ int upload(hqpkkt_t *h) {
       // split one - a front waits only for fronts before it - and the fused launch is an option (HQPKKT_SOLVE_TOP_FUSED,
       // 17 us less per solve: M and L21 are read once).
       h->top_split = (int)nodes.size() > ST_MAXFRONTS || getenv("HQPKKT_SOLVE_TOP_FUSED") == nullptr;
-      if ((e = h->top_nodes.upload(nodes)) || (e = h->top_idx.upload(idx)) || (e = h->top_bpos.upload(bpos)) || (e = h->top_up.upload(up)) ||
-          (e = h->top_x.alloc(2 * nodes.size() * (size_t)(ST_CS + ST_XS))))
+      if ((e = h->td.top_nodes.upload(nodes)) || (e = h->td.top_idx.upload(idx)) || (e = h->td.top_bpos.upload(bpos)) || (e = h->td.top_up.upload(up)) ||
+          (e = h->td.top_x.alloc(2 * nodes.size() * (size_t)(ST_CS + ST_XS))))
         return e;
       h->top_n = (int)nodes.size(), h->top_lt = lt, h->top_ns = ok3 ? 3 : 4, h->top_lds = st_top_lds_bytes(maxp, h->top_ns);
       if ((e = reset_solve_top(h))) return e;
@@ -334,13 +329,13 @@ static bool host_kernel_copies(const hqpkkt_t *) {
 // A call with host vectors as one graph (hqpkkt::ghost_factor / ghost_step): the tree engine on one GPU, vectors that
 // fit the pinned staging buffer.  (HQPKKT_NO_HOST_GRAPHS=1: launch by launch.)
 bool host_graphs_ok(const hqpkkt_t *h) {
-  return getenv("HQPKKT_NO_HOST_GRAPHS") == nullptr && host_kernel_copies(h) && !h->lazy && h->opts.loc != HQPKKT_LOC_DEVICE && h->hstage_in && h->hstage_dev && h->use_graphs &&
+  return getenv("HQPKKT_NO_HOST_GRAPHS") == nullptr && host_kernel_copies(h) && !h->lazy && h->opts.loc != HQPKKT_LOC_DEVICE && h->td.hstage_in && h->td.hstage.dev && h->use_graphs &&
          !h->prof.on && h->opts.mode != HQPKKT_MODE_STAGED && h->an.shard_count <= 1;
 }
 // the caller's vectors packed into the pinned buffer by the CPU (stage_in's layout); returns the doubles in use
 size_t stage_pack(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3, const double *r4) {
   const int n = h->an.n, me = h->an.me, m = h->an.m;
-  double *q = h->hstage;
+  double *q = h->td.hstage.p;
   const double *src[6] = {z, w, r1, r2, r3, r4};
   const int len[6] = {m, m, n, me, m, m};
   size_t used = 0, off = 0;
@@ -353,14 +348,14 @@ size_t stage_pack(hqpkkt_t *h, const double *z, const double *w, const double *r
 int stage_in(hqpkkt_t *h, const double *z, const double *w, const double *r1,
              const double *r2, const double *r3, const double *r4, Vecs &v) {
   const int n = h->an.n, me = h->an.me, m = h->an.m;
-  double *b = h->vin.p;
+  double *b = h->td.vin.p;
   double *dz_ = b, *dw_ = b + m, *d1 = b + 2 * (size_t)m, *d2 = d1 + n, *d3 = d2 + me, *d4 = d3 + m;
   if (h->opts.loc == HQPKKT_LOC_DEVICE) {
     CopyList L{{z, w, r1, r2, r3, r4}, {dz_, dw_, d1, d2, d3, d4}, {m, m, n, me, m, m}};
     k_copy_vectors<<<copy_blocks(L), 256, 0, h->stream>>>(L, 6);
-  } else if (h->hstage_in) {
+  } else if (h->td.hstage_in) {
     // packed by the CPU; the prefix up to the last vector the caller passes
-    double *q = h->hstage;
+    double *q = h->td.hstage.p;
     const double *src[6] = {z, w, r1, r2, r3, r4};
     const int len[6] = {m, m, n, me, m, m};
     size_t used = 0, off = 0;
@@ -368,8 +363,8 @@ int stage_in(hqpkkt_t *h, const double *z, const double *w, const double *r1,
       if (src[k] && len[k] > 0) std::memcpy(q + off, src[k], sizeof(double) * len[k]), used = off + len[k];
       off += len[k];
     }
-    if (used && h->hstage_dev && host_kernel_copies(h)) {  // read out of the pinned buffer by a kernel: no copy engine in the chain
-      CopyList L{{h->hstage_dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {b, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
+    if (used && h->td.hstage.dev && host_kernel_copies(h)) {  // read out of the pinned buffer by a kernel: no copy engine in the chain
+      CopyList L{{h->td.hstage.dev, nullptr, nullptr, nullptr, nullptr, nullptr}, {b, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)used, 0, 0, 0, 0, 0}};
       k_copy_vectors<<<copy_blocks(L), 256, 0, h->stream>>>(L, 1);
     } else if (used)
       HIPCHK(hipMemcpyAsync(b, q, sizeof(double) * used, hipMemcpyHostToDevice, h->stream));
@@ -390,7 +385,7 @@ int stage_in(hqpkkt_t *h, const double *z, const double *w, const double *r1,
 
 void stage_out_ptrs(hqpkkt_t *h, Vecs &v) {
   const int n = h->an.n, me = h->an.me, m = h->an.m;
-  v.dx = h->vout.p, v.dy = v.dx + n, v.dz = v.dy + me, v.dw = v.dz + m;
+  v.dx = h->td.vout.p, v.dy = v.dx + n, v.dz = v.dy + me, v.dw = v.dz + m;
 }
 
 int stage_out(hqpkkt_t *h, const Vecs &v, double *dx, double *dy, double *dz, double *dw) {
@@ -400,17 +395,17 @@ int stage_out(hqpkkt_t *h, const Vecs &v, double *dx, double *dy, double *dz, do
     k_copy_vectors<<<copy_blocks(L), 256, 0, h->stream>>>(L, 4);
     return 0;
   }
-  if (h->hstage_out) {  // one transfer into pinned memory; unstage() hands it out after the sync
-    if (h->hstage_dev && host_kernel_copies(h)) {  // ... written by a kernel (coherent host memory: there when the next kernel of the stream starts)
-      CopyList L{{v.dx, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->hstage_dev + h->hstage_in, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)h->hstage_out, 0, 0, 0, 0, 0}};
+  if (h->td.hstage_out) {  // one transfer into pinned memory; unstage() hands it out after the sync
+    if (h->td.hstage.dev && host_kernel_copies(h)) {  // ... written by a kernel (coherent host memory: there when the next kernel of the stream starts)
+      CopyList L{{v.dx, nullptr, nullptr, nullptr, nullptr, nullptr}, {h->td.hstage.dev + h->td.hstage_in, nullptr, nullptr, nullptr, nullptr, nullptr}, {(int)h->td.hstage_out, 0, 0, 0, 0, 0}};
       k_copy_vectors<<<copy_blocks(L), 256, 0, h->stream>>>(L, 1);
       h->out_by_kernel = true;
     } else {
-      HIPCHK(hipMemcpyAsync(h->hstage + h->hstage_in, v.dx, sizeof(double) * h->hstage_out, hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(h->td.hstage.p + h->td.hstage_in, v.dx, sizeof(double) * h->td.hstage_out, hipMemcpyDeviceToHost,
                             h->stream));
       h->out_by_kernel = false;
     }
-    h->out_pending = h->hstage + h->hstage_in;
+    h->out_pending = h->td.hstage.p + h->td.hstage_in;
     return 0;
   }
 #define D2H(dst, src, k) \
@@ -448,41 +443,41 @@ static int run_factor(hqpkkt_t *h, const double *z, const double *w, int phases)
   Analysis &an = h->an;
   hipStream_t s = h->stream;
   const int m = an.m, nent = (int)an.ent_a.size();
-  DevTree T = h->tree();
+  DevTree T = h->td.tree();
   if (phases & 1) {
     if (an.shard_count <= 1) {  // the panel arena, and the status words, counters and the two maxima
-      KLAUNCH(h, KC_ASSEMBLE, k_clear<<<(int)std::max<long long>(1, std::min<long long>(2048, (an.panel_elems / 2 + 1023) / 1024)), 256, 0, s>>>(h->panel.p, an.panel_elems, h->flags.p));
+      KLAUNCH(h, KC_ASSEMBLE, k_clear<<<(int)std::max<long long>(1, std::min<long long>(2048, (an.panel_elems / 2 + 1023) / 1024)), 256, 0, s>>>(h->td.panel.p, an.panel_elems, h->td.flags.p));
     } else {  // only the blocks this rank writes
       const int np = (int)an.zero_panel.size() / 2;
-      if (np) k_zero_ranges<<<dim3(512, np), 256, 0, s>>>(h->panel.p, h->zero_panel.p);
-      k_clear<<<1, 256, 0, s>>>(nullptr, 0, h->flags.p);
+      if (np) k_zero_ranges<<<dim3(512, np), 256, 0, s>>>(h->td.panel.p, h->td.zero_panel.p);
+      k_clear<<<1, 256, 0, s>>>(nullptr, 0, h->td.flags.p);
     }
     if (!h->capturing) HIPCHK(hipEventRecord(h->ev0, s));
-    if (m > 0 && (h->simple_src.count || no_fused_vectors()))
-      KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(an.mode, m, an.n + an.me, z, w, h->wt.p, h->sc.p, h->flags.p));
-    if (h->simple_src.count) {  // FULL: one pass
+    if (m > 0 && (h->td.simple_src.count || no_fused_vectors()))
+      KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(an.mode, m, an.n + an.me, z, w, h->td.wt.p, h->td.sc.p, h->td.flags.p));
+    if (h->td.simple_src.count) {  // FULL: one pass
       KLAUNCH(h, KC_ASSEMBLE, k_assemble_simple<<<std::min(nblk(nent), 2048), 256, 0, s>>>(
-                                  nent, h->simple_src.p, h->simple_wi.p, h->ent_a.p, h->ent_b.p, h->ent_dst.p,
-                                  h->vals.p, h->wt.p, h->sc.p, h->panel.p, h->bits.p, h->tree_words.p + 1));
+                                  nent, h->td.simple_src.p, h->td.simple_wi.p, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p,
+                                  h->td.vals.p, h->td.wt.p, h->td.sc.p, h->td.panel.p, h->td.bits.p, h->td.tree_words.p + 1));
     } else {
       // weights + entry values, scales + scatter: one launch each (kernels.hip.h, k_wt_entry / k_scale_scatter)
       if (no_fused_vectors()) {
-        KLAUNCH(h, KC_ASSEMBLE, k_entry_values<<<nblk(nent), 256, 0, s>>>(nent, h->term_ptr.p, h->terms.p, h->vals.p, h->wt.p,
-                                                  h->ent_val.p, h->tree_words.p + 1));
+        KLAUNCH(h, KC_ASSEMBLE, k_entry_values<<<nblk(nent), 256, 0, s>>>(nent, h->td.term_ptr.p, h->td.terms.p, h->td.vals.p, h->td.wt.p,
+                                                  h->td.ent_val.p, h->td.tree_words.p + 1));
         if (an.mode == 1 && an.n > 0)
-          KLAUNCH(h, KC_ASSEMBLE, k_red_scale<<<nblk(an.n), 256, 0, s>>>(an.n, h->diag_ent.p, h->ent_val.p, h->sc.p));
-        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<std::min(nblk(nent), 2048), 256, 0, s>>>(nent, h->ent_a.p, h->ent_b.p, h->ent_dst.p, h->ent_val.p,
-                                             h->sc.p, h->panel.p, h->bits.p));
+          KLAUNCH(h, KC_ASSEMBLE, k_red_scale<<<nblk(an.n), 256, 0, s>>>(an.n, h->td.diag_ent.p, h->td.ent_val.p, h->td.sc.p));
+        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<std::min(nblk(nent), 2048), 256, 0, s>>>(nent, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p, h->td.ent_val.p,
+                                             h->td.sc.p, h->td.panel.p, h->td.bits.p));
       } else {
-      KLAUNCH(h, KC_ASSEMBLE, k_wt_entry<<<nblk(nent) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(an.mode, m, an.n + an.me, nent, nblk(nent), z, w, h->wt.p, h->sc.p,
-                                                h->flags.p, h->term_ptr.p, h->terms.p, h->vals.p, h->ent_val.p, h->tree_words.p + 1));
+      KLAUNCH(h, KC_ASSEMBLE, k_wt_entry<<<nblk(nent) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(an.mode, m, an.n + an.me, nent, nblk(nent), z, w, h->td.wt.p, h->td.sc.p,
+                                                h->td.flags.p, h->td.term_ptr.p, h->td.terms.p, h->td.vals.p, h->td.ent_val.p, h->td.tree_words.p + 1));
       const int nsc = std::min(nblk(nent), 2048);
       if (an.mode == 1 && an.n > 0)
-        KLAUNCH(h, KC_ASSEMBLE, k_scale_scatter<<<nsc + nblk(an.n), 256, 0, s>>>(an.n, nent, nsc, h->diag_ent.p, h->ent_a.p, h->ent_b.p, h->ent_dst.p,
-                                                 h->ent_val.p, h->sc.p, h->panel.p, h->bits.p));
+        KLAUNCH(h, KC_ASSEMBLE, k_scale_scatter<<<nsc + nblk(an.n), 256, 0, s>>>(an.n, nent, nsc, h->td.diag_ent.p, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p,
+                                                 h->td.ent_val.p, h->td.sc.p, h->td.panel.p, h->td.bits.p));
       else
-        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<nsc, 256, 0, s>>>(nent, h->ent_a.p, h->ent_b.p, h->ent_dst.p, h->ent_val.p,
-                                             h->sc.p, h->panel.p, h->bits.p));
+        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<nsc, 256, 0, s>>>(nent, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p, h->td.ent_val.p,
+                                             h->td.sc.p, h->td.panel.p, h->td.bits.p));
       }
     }
     if (!h->capturing) HIPCHK(hipEventRecord(h->ev1, s));
@@ -491,51 +486,51 @@ static int run_factor(hqpkkt_t *h, const double *z, const double *w, int phases)
   for (int which = 0; which < 2; which++) {
     if (!(phases & (1 << which))) continue;
     const Analysis::Sched &S = an.sched[which];
-    const hqpkkt::DevSched &D = h->ds[which];
+    const TreeDev::DevSched &D = h->td.ds[which];
     if (S.nnodes == 0) continue;
-    const TreeXchgF txf{h->tree_u.p, an.upd_elems, h->tree_words.p + 1};
+    const TreeXchgF txf{h->td.tree_u.p, an.upd_elems, h->td.tree_words.p + 1};
     if (which == 0 && h->tree_factor) {  // a tree of small fronts: all levels in one launch
       int ldp = 1, ldb = 1;
       for (int l = 0; l < an.nlevels; l++) ldp = std::max(ldp, S.level_fs_p[l] | 1), ldb = std::max(ldb, S.level_fs_b[l]);
-      KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_diag_small<true, true><<<S.nnodes, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p, h->panel.p,
-                                               h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                               h->flags.p + 1, h->upd.p, h->xar.p, ldp, ldb, txf)));
+      KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_diag_small<true, true><<<S.nnodes, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p, h->td.panel.p,
+                                               h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                               h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, ldb, txf)));
       continue;
     }
     for (int l = 0; l < an.nlevels; l++) {
       const int nn = S.level_ptr[l + 1] - S.level_ptr[l], nfs = S.level_fsmall[l], nsm = S.level_small[l];
       if (nfs > 0) {  // small fronts: extend-add, pivot block, panel and update in one kernel
         const int ldp = S.level_fs_p[l] | 1, ldb = S.level_fs_b[l];
-        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<true><<<nfs, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p + S.level_ptr[l], h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p, h->xar.p, ldp, ldb, txf));
+        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<true><<<nfs, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, ldb, txf));
       }
       if (nsm > 0) {
         const int ldp = S.level_sm_p[l] | 1;
-        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<false><<<nsm, 64, fs_lds_bytes(false, ldp, 1), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p, h->xar.p, ldp, 1, txf));
+        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<false><<<nsm, 64, fs_lds_bytes(false, ldp, 1), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, 1, txf));
       }
       if (nn > nfs + nsm) {
         // the pivot blocks on the matrix pipe: 8 wavefronts (two workgroups per CU) for levels of <= 128 pivots, 12
         // wavefronts beyond, each holding as many 16 x 16 blocks of the triangle as the level's largest front needs
         const int lmp = h->level_maxp[which][l];
         if (lmp <= 128)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<8, 6, 144, 2, FB_OWNSIMD><<<nn - nfs - nsm, 512, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p)));
+          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<8, 6, 144, 2, FB_OWNSIMD><<<nn - nfs - nsm, 512, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p)));
         else if (lmp <= 160)  // (55 blocks on 11 wavefronts: five per wavefront)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p)));
+          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p)));
         else if (lmp <= 176)  // (66 blocks of the triangle on 11 wavefronts: six per wavefront - 16 registers fewer than with eight, no scratch)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 6, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p)));
+          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 6, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p)));
         else
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 8, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->panel.p,
-                                                 h->dinv.p, h->ptype.p, h->lperm.p, h->esign.p, h->linv.p, h->linv_off.p, alpha, h->opts.pivot_eps, h->bits.p,
-                                                 h->flags.p + 1, h->upd.p)));
+          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 8, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
+                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
+                                                 h->td.flags.p + 1, h->td.upd.p)));
       }
       const int ns = S.slab_ptr[l + 1] - S.slab_ptr[l];
       // the work lists go over the XCDs in chunks of about half a front's items (kernels.hip.h, xcd_order; measured on C2:
@@ -545,19 +540,19 @@ static int run_factor(hqpkkt_t *h, const double *z, const double *w, int phases)
       const int xtt = (lmb + 63) / 64, xsu = std::max(1, xtt * (xtt + 1) / 4);
       if (ns > 0)  // (the schedule lists 32-row slabs; the kernel takes 16 rows per workgroup)
         KLAUNCH(h, KC_PANEL_SOLVE, k_panel_solve<<<2 * ns, 256, h->lds_panel, s>>>(T, D.slabs.p + 2 * (size_t)S.slab_ptr[l],
-                                                    h->panel.p, h->xar.p, h->dinv.p, h->ptype.p,
-                                                    h->lperm.p, h->linv.p, h->linv_off.p, h->upd.p, xps));
+                                                    h->td.panel.p, h->td.xar.p, h->td.dinv.p, h->td.ptype.p,
+                                                    h->td.lperm.p, h->td.linv.p, h->td.linv_off.p, h->td.upd.p, xps));
       const int nt = S.upd_big_ptr[l] - S.upd_tile_ptr[l], ntb = S.upd_tile_ptr[l + 1] - S.upd_big_ptr[l];
       // a wave holds 32 x 32 of a tile while a level fills the chip; 32 x 16 (two workgroups per tile) on the thin levels above
       if (nt > 0 && nt > SU1_MAX)
         KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<2><<<nt, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_tile_ptr[l],
-                                          h->panel.p, h->xar.p, h->upd.p, xsu));
+                                          h->td.panel.p, h->td.xar.p, h->td.upd.p, xsu));
       else if (nt > 0)
         KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<1><<<2 * nt, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_tile_ptr[l],
-                                          h->panel.p, h->xar.p, h->upd.p, 2 * xsu));
+                                          h->td.panel.p, h->td.xar.p, h->td.upd.p, 2 * xsu));
       if (ntb > 0)
         KLAUNCH(h, KC_SCHUR_UPDATE, (k_schur_update_big<2, 2, 4, 4, 2, 2><<<ntb, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_big_ptr[l],
-                                          h->panel.p, h->xar.p, h->upd.p)));
+                                          h->td.panel.p, h->td.xar.p, h->td.upd.p)));
     }
   }
   if (!h->capturing) HIPCHK(hipEventRecord(h->evs1, s));
@@ -572,15 +567,15 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
   Analysis &an = h->an;
   hipStream_t s = h->stream;
   const int n = an.n, me = an.me, m = an.m, dim = an.dim;
-  DevTree T = h->tree();
+  DevTree T = h->td.tree();
   auto forward = [&](int which) -> int {
     const Analysis::Sched &S = an.sched[which];
-    const hqpkkt::DevSched &D = h->ds[which];
-    const TreeXchg tx{h->tree_x.p, h->tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->tree_words.p, h->flags.p};
+    const TreeDev::DevSched &D = h->td.ds[which];
+    const TreeXchg tx{h->td.tree_x.p, h->td.tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->td.tree_words.p, h->td.flags.p};
     if (which == 0 && h->small_tree) {  // all levels in one launch
       KLAUNCH(h, KC_SOLVE_FWD,
-              k_solve_fwd_small<true><<<S.nnodes, 64, 0, s>>>(T, D.level_nodes.p, h->panel.p, h->linv.p, h->linv_off.p, h->dinv.p, h->ptype.p,
-                                                              h->lperm.p, h->rhs.p, h->xsol.p, h->ytmp.p, h->cb.p, tx));
+              k_solve_fwd_small<true><<<S.nnodes, 64, 0, s>>>(T, D.level_nodes.p, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p,
+                                                              h->td.lperm.p, h->td.rhs.p, h->td.xsol.p, h->td.ytmp.p, h->td.cb.p, tx));
       return 0;
     }
     const int lend = which == 0 && h->top_n > 0 ? h->top_lt : an.nlevels;  // (the levels above: k_solve_top)
@@ -588,34 +583,34 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
       const int nn = S.level_ptr[l + 1] - S.level_ptr[l], nfs = S.level_fsmall[l];
       if (nfs > 0)
         KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->panel.p, h->linv.p,
-                                                     h->linv_off.p, h->dinv.p, h->ptype.p, h->lperm.p, h->rhs.p,
-                                                     h->xsol.p, h->ytmp.p, h->cb.p, tx));
+                k_solve_fwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p, h->td.linv.p,
+                                                     h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p,
+                                                     h->td.xsol.p, h->td.ytmp.p, h->td.cb.p, tx));
       const int ng = S.gslab_ptr[l + 1] - S.gslab_ptr[l];  // (front, 64-row slab), at least one per front
       if (ng > 0 && ng <= FWD_FUSED_MAX_SLABS)  // a handful of fronts: the launch is what costs
         KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->panel.p, h->linv.p,
-                                               h->linv_off.p, h->dinv.p, h->ptype.p, h->lperm.p, h->rhs.p,
-                                               h->xsol.p, h->ytmp.p, h->cb.p));
+                k_solve_fwd<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->td.panel.p, h->td.linv.p,
+                                               h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p,
+                                               h->td.xsol.p, h->td.ytmp.p, h->td.cb.p));
       else if (ng > 0) {  // thousands of slabs: M once per front, then the slabs
         KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->linv.p,
-                                                 h->linv_off.p, h->dinv.p, h->ptype.p, h->lperm.p,
-                                                 h->rhs.p, h->xsol.p, h->ytmp.p, h->cb.p));
+                k_solve_fwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.linv.p,
+                                                 h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p,
+                                                 h->td.rhs.p, h->td.xsol.p, h->td.ytmp.p, h->td.cb.p));
         KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_b<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->panel.p,
-                                                 h->ytmp.p, h->cb.p));
+                k_solve_fwd_b<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->td.panel.p,
+                                                 h->td.ytmp.p, h->td.cb.p));
       }
     }
     return 0;
   };
   auto backward = [&](int which) -> int {
     const Analysis::Sched &S = an.sched[which];
-    const hqpkkt::DevSched &D = h->ds[which];
-    const TreeXchg tx{h->tree_x.p, h->tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->tree_words.p, h->flags.p};
+    const TreeDev::DevSched &D = h->td.ds[which];
+    const TreeXchg tx{h->td.tree_x.p, h->td.tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->td.tree_words.p, h->td.flags.p};
     if (which == 0 && h->small_tree) {
-      KLAUNCH(h, KC_SOLVE_BWD, k_solve_bwd_small<true><<<S.nnodes, 64, 0, s>>>(T, h->tree_down.p, h->panel.p, h->linv.p, h->linv_off.p, h->lperm.p,
-                                                                               h->xsol.p, tx));
+      KLAUNCH(h, KC_SOLVE_BWD, k_solve_bwd_small<true><<<S.nnodes, 64, 0, s>>>(T, h->td.tree_down.p, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, h->td.lperm.p,
+                                                                               h->td.xsol.p, tx));
       return 0;
     }
     const int lbeg = which == 0 && h->top_n > 0 ? h->top_lt - 1 : an.nlevels - 1;
@@ -625,51 +620,51 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
       if (nn <= 0) continue;
       if (nfs > 0)
         KLAUNCH(h, KC_SOLVE_BWD,
-                k_solve_bwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->panel.p, h->linv.p,
-                                                     h->linv_off.p, h->lperm.p, h->xsol.p, tx));
+                k_solve_bwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p, h->td.linv.p,
+                                                     h->td.linv_off.p, h->td.lperm.p, h->td.xsol.p, tx));
       if (nn <= nfs) continue;
       // (one workgroup per front doing both steps was measured slower: L21' x needs the
       // column blocks spread over the chip)
       KLAUNCH(h, KC_SOLVE_BWD,
               k_solve_bwd_b<<<ncb, 256, h->lds_bwdb, s>>>(T, D.cblks.p + 2 * (size_t)S.cblk_ptr[l],
-                                                          h->panel.p, h->xsol.p, h->vtmp.p));
+                                                          h->td.panel.p, h->td.xsol.p, h->td.vtmp.p));
       KLAUNCH(h, KC_SOLVE_BWD,
-              k_solve_bwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->linv.p,
-                                               h->linv_off.p, h->lperm.p, h->vtmp.p, h->xsol.p));
+              k_solve_bwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.linv.p,
+                                               h->td.linv_off.p, h->td.lperm.p, h->td.vtmp.p, h->td.xsol.p));
     }
     return 0;
   };
   if (phases & 1) {
     if (an.mode == 0) {
-      KLAUNCH(h, KC_VECTOR, k_rhs_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->q2e.p, h->sc.p, v.z, v.r1, v.r2, v.r3, v.r4,
-                                           h->rhs.p, h->tree_words.p));
+      KLAUNCH(h, KC_VECTOR, k_rhs_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->td.q2e.p, h->td.sc.p, v.z, v.r1, v.r2, v.r3, v.r4,
+                                           h->td.rhs.p, h->td.tree_words.p));
     } else {
       // (tz and the right-hand side that needs it in one launch: kernels.hip.h, k_rhs_red_t; HQPKKT_NO_FUSED_VECTORS=1: two)
       if (no_fused_vectors()) {
-        if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->wt.p, v.r3, v.r4, h->tz.p));
-        KLAUNCH(h, KC_VECTOR, k_rhs_red<<<nblk(dim), 256, 0, s>>>(n, me, h->q2e.p, h->sc.p, h->CT.ptr.p, h->CT.col.p,
-                                            h->CT.src.p, h->vals.p, h->tz.p, v.r1, v.r2, h->rhs.p,
-                                            h->tree_words.p));
+        if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
+        KLAUNCH(h, KC_VECTOR, k_rhs_red<<<nblk(dim), 256, 0, s>>>(n, me, h->td.q2e.p, h->td.sc.p, h->td.CT.ptr.p, h->td.CT.col.p,
+                                            h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, v.r2, h->td.rhs.p,
+                                            h->td.tree_words.p));
       } else
-        KLAUNCH(h, KC_VECTOR, k_rhs_red_t<<<nblk(dim) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(n, me, m, nblk(dim), h->q2e.p, h->sc.p, h->CT.ptr.p, h->CT.col.p,
-                                            h->CT.src.p, h->vals.p, v.w, h->wt.p, v.r3, v.r4, h->tz.p, v.r1, v.r2, h->rhs.p,
-                                            h->tree_words.p));
+        KLAUNCH(h, KC_VECTOR, k_rhs_red_t<<<nblk(dim) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(n, me, m, nblk(dim), h->td.q2e.p, h->td.sc.p, h->td.CT.ptr.p, h->td.CT.col.p,
+                                            h->td.CT.src.p, h->td.vals.p, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p, v.r1, v.r2, h->td.rhs.p,
+                                            h->td.tree_words.p));
     }
     forward(0);
   }
   if (phases & 2) {
     forward(1);
     if (h->top_n > 0) {  // the top levels, up and down: one launch, or one per sweep (k_solve_top)
-      TopArgs ta{h->top_nodes.p, h->top_idx.p, h->top_bpos.p, h->top_x.p, h->top_x.p + 2 * (size_t)h->top_n * ST_CS, h->tree_words.p, h->top_n, h->top_stamps};
+      TopArgs ta{h->td.top_nodes.p, h->td.top_idx.p, h->td.top_bpos.p, h->td.top_x.p, h->td.top_x.p + 2 * (size_t)h->top_n * ST_CS, h->td.tree_words.p, h->top_n, h->top_stamps};
 #define TOP_LAUNCH(NS, NU, MODE)                                                                                                          \
-  KLAUNCH(h, KC_SOLVE_TOP, (k_solve_top<NS, NU, MODE><<<h->top_n, ST_THREADS, h->top_lds, s>>>(T, ta, h->panel.p, h->linv.p, h->linv_off.p, \
-                                                            h->dinv.p, h->ptype.p, h->lperm.p, h->rhs.p, h->xsol.p, h->cb.p, h->flags.p)))
+  KLAUNCH(h, KC_SOLVE_TOP, (k_solve_top<NS, NU, MODE><<<h->top_n, ST_THREADS, h->top_lds, s>>>(T, ta, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, \
+                                                            h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p, h->td.xsol.p, h->td.cb.p, h->td.flags.p)))
       if (!h->top_split) {
         if (h->top_ns == 3) TOP_LAUNCH(3, 11, 0); else TOP_LAUNCH(4, 10, 0);
       } else {
-        ta.nodes = h->top_up.p;
+        ta.nodes = h->td.top_up.p;
         if (h->top_ns == 3) TOP_LAUNCH(3, 11, 1); else TOP_LAUNCH(4, 10, 1);
-        ta.nodes = h->top_nodes.p;
+        ta.nodes = h->td.top_nodes.p;
         if (h->top_ns == 3) TOP_LAUNCH(3, 11, 2); else TOP_LAUNCH(4, 10, 2);
       }
 #undef TOP_LAUNCH
@@ -677,26 +672,26 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
     backward(1);
     backward(0);
     if (an.shard_count > 1)  // leave only this rank's share for the all-reduce
-      KLAUNCH(h, KC_VECTOR, k_mask_vector<<<nblk(dim), 256, 0, s>>>(dim, h->keep_e.p, h->xsol.p));
+      KLAUNCH(h, KC_VECTOR, k_mask_vector<<<nblk(dim), 256, 0, s>>>(dim, h->td.keep_e.p, h->td.xsol.p));
   }
   if (phases & 4) {
     if (an.mode == 0) {
-      KLAUNCH(h, KC_VECTOR, k_unpack_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->q2e.p, h->sc.p, h->xsol.p, v.dx, v.dy,
+      KLAUNCH(h, KC_VECTOR, k_unpack_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy,
                                               v.dz));
       if (m > 0)
-        KLAUNCH(h, KC_VECTOR, k_dw<<<nblk(m), 256, 0, s>>>(m, h->C.ptr.p, h->C.col.p, h->C.src.p, h->vals.p, v.dx, v.r3,
+        KLAUNCH(h, KC_VECTOR, k_dw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, v.r3,
                                      v.z, v.w, v.r4, v.dz, v.dw));
     } else {
       // (dx, dy and the dz, dw that need dx in one launch: kernels.hip.h, k_unpack_dzdw)
       const int nb_dzdw = m > 0 ? nblk(m) : 0;
       if (no_fused_vectors()) {
-        KLAUNCH(h, KC_VECTOR, k_unpack_red<<<nblk(dim), 256, 0, s>>>(n, me, h->q2e.p, h->sc.p, h->xsol.p, v.dx, v.dy));
+        KLAUNCH(h, KC_VECTOR, k_unpack_red<<<nblk(dim), 256, 0, s>>>(n, me, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy));
         if (m > 0)
-          KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->C.ptr.p, h->C.col.p, h->C.src.p, h->vals.p, v.dx,
-                                             h->wt.p, h->tz.p, v.r3, v.dz, v.dw));
+          KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx,
+                                             h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));
       } else
-      KLAUNCH(h, KC_VECTOR, k_unpack_dzdw<<<nb_dzdw + nblk(dim), 256, 0, s>>>(n, me, m, nb_dzdw, h->q2e.p, h->sc.p, h->xsol.p, v.dx, v.dy, h->C.ptr.p,
-                                           h->C.col.p, h->C.src.p, h->vals.p, h->wt.p, h->tz.p, v.r3, v.dz, v.dw));
+      KLAUNCH(h, KC_VECTOR, k_unpack_dzdw<<<nb_dzdw + nblk(dim), 256, 0, s>>>(n, me, m, nb_dzdw, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy, h->td.C.ptr.p,
+                                           h->td.C.col.p, h->td.C.src.p, h->td.vals.p, h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));
     }
   }
   HIPCHK(hipGetLastError());
@@ -708,7 +703,7 @@ int do_factor(hqpkkt_t *h, const Vecs &v) {
   int e;
   if (h->opts.mode == HQPKKT_MODE_STAGED) return staged_factor(h, v);
   if (an.shard_count <= 1) {
-    if (an.m > 0 && v.z != h->vin.p) {  // the caller's device vectors themselves (direct_vectors)
+    if (an.m > 0 && v.z != h->td.vin.p) {  // the caller's device vectors themselves (direct_vectors)
       const void *key[10] = {v.z, v.w};
       return graphed(h, h->direct_slot(h->gdirect_factor, key), [&]() { return run_factor(h, v.z, v.w, 3); });
     }
@@ -716,14 +711,14 @@ int do_factor(hqpkkt_t *h, const Vecs &v) {
   }
   if ((e = graphed(h, h->gfactor[0], [&]() { return run_factor(h, v.z, v.w, 1); }))) return e;
   if (an.upd_x_slot > 0 &&
-      (e = exchange(h, HQPKKT_XCHG_ALLGATHER, h->upd.p + an.upd_x_off, an.upd_x_slot, an.shard_count)))
+      (e = exchange(h, HQPKKT_XCHG_ALLGATHER, h->td.upd.p + an.upd_x_off, an.upd_x_slot, an.shard_count)))
     return e;
   if ((e = graphed(h, h->gfactor[1], [&]() { return run_factor(h, v.z, v.w, 2); }))) return e;
   // A zero pivot inside a subtree is seen by its owner only: agree on the status words (one small
   // all-reduce), so that every rank returns the same code and nobody waits in a collective alone
-  k_status_pack<<<1, 64, 0, h->stream>>>(h->flags.p, h->bits.p, h->ytmp.p);
-  if ((e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, h->ytmp.p, 4, 1))) return e;
-  k_status_unpack<<<1, 64, 0, h->stream>>>(h->ytmp.p, h->flags.p, h->bits.p);
+  k_status_pack<<<1, 64, 0, h->stream>>>(h->td.flags.p, h->td.bits.p, h->td.ytmp.p);
+  if ((e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, h->td.ytmp.p, 4, 1))) return e;
+  k_status_unpack<<<1, 64, 0, h->stream>>>(h->td.ytmp.p, h->td.flags.p, h->td.bits.p);
   return 0;
 }
 
@@ -734,7 +729,7 @@ int do_step(hqpkkt_t *h, const Vecs &v, int which) {
   if (an.shard_count <= 1) {
     // the caller's device vectors themselves (direct_vectors): also the refinement's sequence (which == 1: residual and
     // correction vectors are the handle's, z and w the caller's)
-    if ((which == 0 && v.dx != h->vout.p) || (an.m > 0 && v.z != h->vin.p)) {
+    if ((which == 0 && v.dx != h->td.vout.p) || (an.m > 0 && v.z != h->td.vin.p)) {
       const void *key[10] = {v.z, v.w, v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw};
       return graphed(h, h->direct_slot(h->gdirect_step, key), [&]() { return run_step(h, v, 7); });
     }
@@ -742,27 +737,27 @@ int do_step(hqpkkt_t *h, const Vecs &v, int which) {
   }
   if ((e = graphed(h, h->gstep[which][0], [&]() { return run_step(h, v, 1); }))) return e;
   if (an.cb_x_slot > 0 &&
-      (e = exchange(h, HQPKKT_XCHG_ALLGATHER, h->cb.p + an.cb_x_off, an.cb_x_slot, an.shard_count)))
+      (e = exchange(h, HQPKKT_XCHG_ALLGATHER, h->td.cb.p + an.cb_x_off, an.cb_x_slot, an.shard_count)))
     return e;
   if ((e = graphed(h, h->gstep[which][1], [&]() { return run_step(h, v, 2); }))) return e;
-  if ((e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, h->xsol.p, an.dim, 1))) return e;
+  if ((e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, h->td.xsol.p, an.dim, 1))) return e;
   return graphed(h, h->gstep[which][2], [&]() { return run_step(h, v, 4); });
 }
 
-// residual of (d) for rhs (r); leaves the residual vectors in h->vres
+// residual of (d) for rhs (r); leaves the residual vectors in h->td.vres
 // out != nullptr: the caller's copy of (d) is put into the stream before the read-back, so
 // that a solve that needs no refinement round is over with this one round trip
-// ---- read-backs through mapped host memory (hqpkkt::hpin_dev)
+// ---- read-backs through mapped host memory (hqpkkt::Kept::hpin)
 // the status words (and, with `out`, n_out <= 40 of the IP loop's scalars) as they stand at this point of the stream
 int post_words(hqpkkt_t *h, const double *out, int n_out, bool residual) {
   h->post_seq++;
   if (h->capturing) h->cap_posts++;
-  k_post_words<<<1, 64, 0, h->stream>>>(h->flags.p, out, n_out, h->hpin_dev, h->post_seq_dev.p, residual ? 1 : 0);
+  k_post_words<<<1, 64, 0, h->stream>>>(h->td.flags.p, out, n_out, h->kept.hpin.dev, h->kept.post_seq_dev.p, residual ? 1 : 0);
   return 0;
 }
 // waits until the last posted words have arrived (every earlier post of the stream has then arrived as well)
 int post_wait(hqpkkt_t *h) {
-  volatile unsigned *seq = (volatile unsigned *)(h->hpin + HPIN_SEQ);
+  volatile unsigned *seq = (volatile unsigned *)(h->kept.hpin.p + HPIN_SEQ);
   for (long long spin = 0;; spin++) {
     if (*seq == h->post_seq) break;
     if ((spin & 0xfffff) == 0xfffff) {  // (about every millisecond: has the stream died or drained without the word?)
@@ -785,11 +780,11 @@ int residual_launch(hqpkkt_t *h, const Vecs &v) {
   Analysis &an = h->an;
   hipStream_t s = h->stream;
   const int n = an.n, me = an.me, m = an.m;
-  double *o1 = h->vres.p, *o2 = o1 + n, *o3 = o2 + me, *o4 = o3 + m;
+  double *o1 = h->td.vres.p, *o2 = o1 + n, *o3 = o2 + me, *o4 = o3 + m;
   // the maximum is accumulated in the ints 122-123 of the flags buffer; the posting kernel behind every residual kernel
   // clears it (and a factorisation clears the whole buffer).  (rb_next: the word the kernel zeroes for its successor - a
   // spare one since the posting kernel does that.)
-  unsigned long long *const rb_now = h->bits.p + 1, *const rb_next = h->bits.p - 1;
+  unsigned long long *const rb_now = h->td.bits.p + 1, *const rb_next = h->td.bits.p - 1;
   const double *x1 = nullptr, *x2 = nullptr;  // STAGED, dense dynamics: their share of A dx and A'dy
   int ndyn = 0;
   if (h->opts.mode == HQPKKT_MODE_STAGED) {
@@ -798,11 +793,11 @@ int residual_launch(hqpkkt_t *h, const Vecs &v) {
   }
   if (h->short_rows)
     KLAUNCH(h, KC_RESIDUAL, k_residual<4><<<std::min(nblk(4LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(), h->vals.p, v.z, v.w,
+        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p, v.z, v.w,
         v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn));
   else
     KLAUNCH(h, KC_RESIDUAL, k_residual<16><<<std::min(nblk(16LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->Qf.dev(), h->AT.dev(), h->CT.dev(), h->A.dev(), h->C.dev(), h->vals.p, v.z, v.w,
+        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p, v.z, v.w,
         v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn));
   return 0;
 }
@@ -833,7 +828,7 @@ int run_residual(hqpkkt_t *h, const Vecs &v, double *res, const OutPtrs *out) {
 int collect_residual(hqpkkt_t *h, double *res) {
   h->residual_pending = false;
   const bool check = h->factor_unchecked;
-  int *hs = (int *)h->hpin;
+  int *hs = (int *)h->kept.hpin.p;
   int flags[4] = {hs[0], hs[1], hs[2], hs[3]};
   if (poll_fallback(h, hs)) {  // a polled launch gave up waiting for a word: no result, and per-level launches from now on
     if (h->factor_unchecked) h->factor_unchecked = false, h->factored = false;  // (the factorisation may be the one that gave up)
@@ -871,15 +866,15 @@ int hqpkkt_debug_solve_top_stamps(hqpkkt_t *h, double *out, int cap) {
   if (!h->factored || h->top_n <= 0) return HQPKKT_E_INTERN;
   if (cap < h->top_n * 8) return HQPKKT_E_SIZES;
   HIPCHK(hipSetDevice(h->opts.device));
-  unsigned long long *st = nullptr;
-  HIPCHK(hipMalloc((void **)&st, sizeof(unsigned long long) * 8 * h->top_n));
-  (void)hipMemset(st, 0, sizeof(unsigned long long) * 8 * h->top_n);
+  DBuf<unsigned long long> st;
+  if (st.alloc(8 * (size_t)h->top_n)) return HQPKKT_E_MEM;
+  (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 8 * h->top_n);
   const bool graphs = h->use_graphs;
-  h->use_graphs = false, h->top_stamps = st;
+  h->use_graphs = false, h->top_stamps = st.p;
   Vecs v{};
   {  // the staged vectors of the last solve (the layout of stage_in)
     const int n = h->an.n, me = h->an.me, m = h->an.m;
-    double *b = h->vin.p;
+    double *b = h->td.vin.p;
     v.z = b, v.w = b + m, v.r1 = b + 2 * (size_t)m, v.r2 = v.r1 + n, v.r3 = v.r2 + me, v.r4 = v.r3 + m;
   }
   stage_out_ptrs(h, v);
@@ -888,14 +883,13 @@ int hqpkkt_debug_solve_top_stamps(hqpkkt_t *h, double *out, int cap) {
   h->use_graphs = graphs, h->top_stamps = nullptr;
   if (!e) {  // stamps of a sweep that gave up on a poll mean nothing
     int gave_up[XW_GAVE_UP + 1] = {};
-    if (hipMemcpy(gave_up + XW_GAVE_UP, h->flags.p + XW_GAVE_UP, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || poll_fallback(h, gave_up)) e = HQPKKT_E_DEVICE;
+    if (hipMemcpy(gave_up + XW_GAVE_UP, h->td.flags.p + XW_GAVE_UP, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || poll_fallback(h, gave_up)) e = HQPKKT_E_DEVICE;
   }
   std::vector<unsigned long long> hs(8 * (size_t)h->top_n);
-  if (!e && hipMemcpy(hs.data(), st, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost) != hipSuccess) e = HQPKKT_E_DEVICE;
-  (void)hipFree(st);
+  if (!e && hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost) != hipSuccess) e = HQPKKT_E_DEVICE;
   if (e) return e;
   std::vector<int> nodes(h->top_n);
-  HIPCHK(hipMemcpy(nodes.data(), h->top_nodes.p, sizeof(int) * h->top_n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nodes.data(), h->td.top_nodes.p, sizeof(int) * h->top_n, hipMemcpyDeviceToHost));
   unsigned long long t0 = ~0ULL;
   for (int t = 0; t < h->top_n; t++) t0 = std::min(t0, hs[8 * (size_t)t]);
   for (int t = 0; t < h->top_n; t++) {
@@ -977,9 +971,9 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
   HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 8, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
   HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 6, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
   HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  EventOwner e0, e1;
+  HIPCHK(hipEventCreate(&e0.h));
+  HIPCHK(hipEventCreate(&e1.h));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipEventRecord(e0, 0));
   for (int rp = 0; rp < reps; rp++) {
@@ -1004,7 +998,6 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
   HIPCHK(hipGetLastError());
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
   if (ms_out) *ms_out = ms / reps;
   const size_t last = (size_t)(reps - 1);
   if (Lout) HIPCHK(hipMemcpy(Lout, d_P.p + pp2 * last, sizeof(double) * pp2, hipMemcpyDeviceToHost));
@@ -1013,9 +1006,6 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
   if (ptype_out) HIPCHK(hipMemcpy(ptype_out, d_pt.p + (size_t)p * last, sizeof(int) * p, hipMemcpyDeviceToHost));
   if (lperm_out) HIPCHK(hipMemcpy(lperm_out, d_lp.p + (size_t)p * last, sizeof(int) * p, hipMemcpyDeviceToHost));
   if (counters_out) HIPCHK(hipMemcpy(counters_out, d_flags.p, sizeof(int) * 128, hipMemcpyDeviceToHost));
-  DBuf<int> *ib[] = {&d_ps, &d_np, &d_nb, &d_par, &d_cp, &d_nodes, &d_pt, &d_lp, &d_flags, &d_one};
-  for (auto b : ib) b->release();
-  d_zero.release(), d_poff.release(), d_loff.release(), d_P.release(), d_dinv.release(), d_W.release(), d_upd.release(), d_sg.release();
   return 0;
 }
 

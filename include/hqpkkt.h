@@ -439,7 +439,8 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * the last factorisation: stages whose K was inverted by the blocked elimination, and those of them that fell back to the
  * one-workgroup elimination (device -> host copy); 30 (zero-diagonal policy in use, last
  * values have weak Hessian diagonals), 31 (fronts of the tree's top that the solve handles in one launch, first
- * such level, LDS bytes of that launch).
+ * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
+ * process, over all handles: answered on any handle, analysed or not).
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

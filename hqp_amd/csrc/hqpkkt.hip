@@ -90,7 +90,7 @@ int hqpkkt_analyze(hqpkkt_t *h, int n, int me, int m, const int *Qp, const int *
     h->zd_weak = false;
     if (h->opts.mode == HQPKKT_MODE_STAGED) {
       h->zd_decided = true;
-      int es = staged_analyze_csr(h, n, me, m);
+      int es = staged_analyze(h, n, me, m);
       if (es) return es;
       if (sbw) *sbw = -1;
       return 0;
@@ -152,7 +152,7 @@ int hqpkkt_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
     Analysis &an = h->an;
     if ((an.nq && !Qx) || (an.na && !Ax) || (an.nc && !Cx)) return HQPKKT_E_NULL;
     int e;
-    if (h->opts.mode == HQPKKT_MODE_STAGED) return staged_set_values_csr(h, Qx, Ax, Cx);
+    if (h->opts.mode == HQPKKT_MODE_STAGED) return staged_set_values(h, Qx, Ax, Cx);
     if (!h->uploaded && (e = upload(h))) return e;
     HIPCHK(hipSetDevice(h->opts.device));
     hipMemcpyKind kind =

@@ -2,7 +2,7 @@
 // per-class timing, graph capture, and the functions one unit calls in another.  The units:
 //   tree.hip           device residency and kernel sequencing of the tree engine (kernels.hip.h, factor_blk.hip.h,
 //                      solve_top.hip.h), the vector staging of a call, the residual and the posted read-backs
-//   staged_engine.hip  the STAGED engine (staged.hip.h, staged_host.hip.h)
+//   staged_engine.hip  the STAGED engine (staged.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
 //   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
 //   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
 #pragma once
@@ -459,27 +459,6 @@ static int graphed(hqpkkt_t *h, hqpkkt::GraphSlot &slot, F body) {
   return 0;
 }
 
-// The exchange steps of a sharded system: the handle's stream is
-// drained, the caller's collective runs, and the next phase starts afterwards.
-// (Defined here and static: staged_host.hip.h, which the STAGED unit includes as it is, declares it static.)
-static int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on = nullptr) {
-  // (profiled as the class "exchange": in the stream-ordered form the time between the collective's place in
-  // the stream and its completion - the wait for the slowest rank and the transfer)
-  if (h->xchg_sfn) {  // the collective is put into the handle's stream (or `on`) behind the kernels that fill `buf`
-    hipStream_t st = on ? on : h->stream;
-    h->prof.begin(KC_XCHG, st);
-    const int rc = h->xchg_sfn(h->xchg_ctx, op, buf, slot, nslots, (void *)st);
-    h->prof.end(st);
-    return rc ? HQPKKT_E_DEVICE : 0;
-  }
-  if (!h->xchg_fn) return HQPKKT_E_INTERN;
-  h->prof.begin(KC_XCHG, h->stream);
-  HIPCHK(hipStreamSynchronize(h->stream));
-  const int rc = h->xchg_fn(h->xchg_ctx, op, buf, slot, nslots);
-  h->prof.end(h->stream);
-  return rc ? HQPKKT_E_DEVICE : 0;
-}
-
 // The C ABI promises that nothing is thrown across it (the shim's callers longjmp through Meschach
 // frames): every entry point that allocates with the standard library runs inside this guard.
 template <class F>
@@ -503,6 +482,7 @@ static inline float elapsed(hipEvent_t a, hipEvent_t b) {
 
 // ---- what one unit calls in another
 // tree.hip
+int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on = nullptr);
 int ensure_device(hqpkkt_t *h);
 int alloc_hpin(hqpkkt_t *h);
 int upload(hqpkkt_t *h);
@@ -522,8 +502,9 @@ int residual_launch(hqpkkt_t *h, const Vecs &v);
 int run_residual(hqpkkt_t *h, const Vecs &v, double *res, const OutPtrs *out = nullptr);
 int collect_residual(hqpkkt_t *h, double *res);
 // staged_engine.hip
-int staged_analyze_csr(hqpkkt_t *h, int n, int me, int m);
-int staged_set_values_csr(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx);
+int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn = false);
+int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx, const double *const *Fblk = nullptr,
+                      const long long *ldF = nullptr, bool dense = false);  // (Fblk / dense: the dense hand-over of the dynamics)
 int staged_factor(hqpkkt_t *h, const Vecs &v);
 int staged_step(hqpkkt_t *h, const Vecs &v, int which);
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn);

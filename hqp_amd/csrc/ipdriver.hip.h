@@ -140,7 +140,7 @@ k_ip_rhs(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDev 
          double *__restrict__ r2, double *__restrict__ r3, double *__restrict__ r4,
          double *__restrict__ part,
          // STAGED with dense dynamics: x1 = A_dyn' y (n), x2 = A_dyn x (the first ndyn rows of A, empty in
-         // the CSR block), from k_st_dyn_aty / k_st_dyn_ax
+         // the CSR block), from k_st_dyn_both / k_st_dyn_ax_finish (staged_dense_products)
          const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0) {
   __shared__ double red[4];
   const int sub = threadIdx.x & (LPR - 1);

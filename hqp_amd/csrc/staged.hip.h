@@ -21,6 +21,7 @@
 
 #include "staged_plan.hpp"
 #include "sk_table.hpp"
+#include "gemm_form.hpp"
 
 namespace stg {
 
@@ -84,32 +85,8 @@ struct GemmArgs {
                                // the k loop, end of the epilogue; null in every product of the engine
 };
 
-static const int GEMM_BK = 16;
-
-// number of b x b tiles of an M x N product; lower: only tiles with tile row >= tile column (M >= N: a triangle of
-// ceil(N / b) tile columns on top of a rectangle - the column strip of a lower triangle that one rank computes)
-static inline long long gemm_tiles(int M, int N, int b, int lower) {
-  const long long tm = (M + b - 1) / b, tn = (N + b - 1) / b;
-  return lower ? tn * (tn + 1) / 2 + (tm > tn ? (tm - tn) * tn : 0) : tm * tn;
-}
 static inline size_t gemm_lds_bytes(int bm, int bn, int nbuf = 2) { return sizeof(double) * nbuf * GEMM_BK * (size_t)(bm + 16 + bn + 16); }
 
-// 128 x 128 tiles from 384 tiles on (the grid of 2 x 256 workgroups three quarters full).  Below that the 64 x 64
-// kernel with four times the tiles is faster (same-box comparisons of round 3: 2000 x 2050 x 2000
-// 0.41 against 0.50 ms, 1500 x 1540 x 1500 0.19 against 0.21) with one exception: a deep rectangular product of 160 -
-// 256 tiles - the column strip of W when a C4 system is sharded over 8 ranks, 5000 x 640 x 5000 - as ONE round of one
-// workgroup per CU (gemm_launch_plain): 0.71 against 0.83 ms.
-static inline bool gemm_big_tiles(int M, int N, int lower, int K = 0) {
-  const long long t = gemm_tiles(M, N, 128, lower);
-  return t >= 384 || (!lower && t >= 160 && t <= 256 && K >= 256 * GEMM_BK);
-}
-
-// The split form (k_dgemm_tn_sk, below) pays where whole rounds of 128 x 128 tiles would leave slots idle
-// and the product is deep enough to be cut.  Returns true when the launch should use it with the whole
-// `grid` (two workgroups per CU): more than one tile, not a multiple of the grid, and either more tiles
-// than half the grid or a plan that puts at least a quarter of the grid to work (below that the 64 x 64
-// tiles fill the chip better).
-static inline bool gemm_use_split(int M, int N, int K, int lower, int grid);
 // blockIdx -> position in a sequence in which the workgroups of one XCD (blockIdx % 8) are
 // neighbours (each XCD has its own L2; neighbouring tiles share operand panels)
 __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
@@ -660,28 +637,6 @@ static inline long long gemm_split_plan_depth(const SplitPlan &sp, long long nsl
   for (int q = 0; q < sp.nphase; q++) d += (nslab + sp.split[q] - 1) / sp.split[q];
   return d;
 }
-static inline bool gemm_use_split(int M, int N, int K, int lower, int grid) {
-  if (grid <= 0 || (long long)M * N < 256LL * 256) return false;
-  const long long tiles = gemm_tiles(M, N, 128, lower);
-  const long long nslab = (K + GEMM_BK - 1) / GEMM_BK;
-  if (nslab < 32) return false;                                 // too shallow to cut
-  if (tiles % grid == 0 || tiles >= 16LL * grid) return false;  // even, or the tail does not matter
-  // (a CU with one workgroup reaches 92 % of what it does with two: up to 5/8 of the grid one plain round of one
-  // or two workgroups per CU is as fast as cut pieces, without their parked partial sums)
-  if (tiles > grid * 5 / 8) return true;
-  // (few tiles - a stage of ~1000 states: 72 - run on 64 x 64 tiles; cut pieces for them were measured slower)
-  return false;
-}
-// The fractional form pays for a few hundred tiles - between 5/16 and 5/8 of the grid, where neither whole rounds nor
-// the 64 x 64 tiles fill the chip (measured, one MI355X, tools/dgemm_shapes.py: W of a stage of 2000 states, 272 tiles:
-// 367 us against 413; G of 3000 states, 300 lower tiles: 532 against 609; a 640-column strip of the headline's W, 200
-// tiles: 611 against 652).  Its workgroups are at different k at any moment, so they share less of the operands in L2
-// than the rounds of the plan above: with more tiles (the headline's 1600: 4.13 against 3.90 ms) the plan stays.
-static inline bool gemm_use_frac(int M, int N, int K, int lower, int grid) {
-  if (grid <= 0) return false;
-  const long long tiles = gemm_tiles(M, N, 128, lower), nslab = (K + GEMM_BK - 1) / GEMM_BK;
-  return nslab >= 64 && tiles * 16 >= grid * 5LL && tiles * 8 <= grid * 5LL;
-}
 template <bool DMA, int WGM = 2, int WGN = 2, int NBUF = 2, int BM = 128, int BN = 128>
 __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WGM * WGN / 2) k_dgemm_tn_sk(GemmArgs g, SplitPlan sk) {
   using T = GemmTile<BM, BN, WGM, WGN>;
@@ -961,10 +916,6 @@ static inline void gemm_launch_split(int variant, int grid, hipStream_t s, const
 }
 // 64 x 64 tiles (register-staged loop) with their k ranges cut: products of a few hundred small tiles, where one
 // workgroup per CU leaves the matrix pipe two thirds idle (a stage of ~1000 states: 272 tiles of 63 slabs, 91 us)
-// the rule for 64 x 32 tiles (st_gemm, hqpkkt_debug_dgemm): a rectangular product of at most two 64 x 64 tiles per CU, deep
-static inline bool gemm_tiles_6432(int M, int N, int K, int lower, int mirror, int cus) {
-  return cus > 0 && !lower && !mirror && gemm_tiles(M, N, 64, 0) <= 2LL * cus && K >= 16 * GEMM_BK;
-}
 static inline hipError_t gemm_set_attributes() {
   hipError_t e = hipSuccess;
   auto set = [&](const void *f, size_t bytes) {
@@ -2976,18 +2927,6 @@ struct DynDesc {
   int ldf, np, nz, col0, row0, ncur;  // F block, its sizes, first column / dynamics row, states of the stage
 };
 // out2[row0 + li] = F_k[li][:] dx_k - dx_{k+1}[li]
-__global__ void __launch_bounds__(256) k_st_dyn_ax(const DynDesc *__restrict__ desc, const double *__restrict__ F,
-                                                   const double *__restrict__ dx, double *__restrict__ out2) {
-  const DynDesc d = desc[blockIdx.y];
-  const int lane = threadIdx.x & 63;
-  for (int li = blockIdx.x * 4 + (threadIdx.x >> 6); li < d.np; li += gridDim.x * 4) {
-    const double *fr = F + d.oF + (long long)li * d.ldf;
-    double s = 0.0;
-    for (int j = lane; j < d.nz; j += 64) s += fr[j] * dx[d.col0 + j];
-    s = kktdev::wave_sum(s);
-    if (lane == 0) out2[d.row0 + li] = s - dx[d.col0 + d.nz + li];
-  }
-}
 // out1[c] = sum_li F_k[li][lc] dy[row0 + li] - dy[row of x_k's dynamics equation]   (c in stage k;
 // the last stage has no F: np = 0)
 // Both products of residuum() with the dense dynamics rows in ONE pass over the F blocks (two passes: 80 GB at the
@@ -3067,19 +3006,6 @@ __global__ void k_st_dyn_ax_finish(const DynDesc *__restrict__ desc, const doubl
   double s = 0.0;
   for (int b = 0; b < nb; b++) s += part[(long long)(d.row0 + li) * nblk_cols + b];
   out2[d.row0 + li] = s - dx[d.col0 + d.nz + li];
-}
-__global__ void __launch_bounds__(256) k_st_dyn_aty(const DynDesc *__restrict__ desc, const double *__restrict__ F,
-                                                    const double *__restrict__ dy, double *__restrict__ out1) {
-  const DynDesc d = desc[blockIdx.y];
-  const int ncols = d.np > 0 ? d.nz : d.ncur;
-  for (int lc = blockIdx.x * blockDim.x + threadIdx.x; lc < ncols; lc += gridDim.x * blockDim.x) {
-    double s = 0.0;
-    const double *fc = F + d.oF + lc;
-    for (int li = 0; li < d.np; li++) s += fc[(long long)li * d.ldf] * dy[d.row0 + li];
-    // x_k is the state the previous stage's dynamics produce: -1.0 in that row
-    if (blockIdx.y > 0 && lc < d.ncur) s -= dy[d.row0 - d.ncur + lc];
-    out1[d.col0 + lc] = s;
-  }
 }
 
 // The same two products when the F blocks are the LOCAL ones of a rank (Floc_k = [F_p | F_u], staged_plan.hpp): the rank

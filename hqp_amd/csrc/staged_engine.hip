@@ -26,20 +26,12 @@ int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const d
     *x1 = d.dyn_sum.p, *x2 = d.dyn_sum.p + d.dyn_sum_x2, *ndyn = P.ndyn;
     return 0;
   }
-  const bool two_passes = false;  // (one pass over F for both products; the two-pass kernels stay for blocks the fused one does not take)
-  const int nbc = (nzmax + 255) / 256;
-  if (!two_passes && d.dyn_part.p && d.dyn_part_cols == nbc) {
-    // one pass over F for both products (k_st_dyn_both), then the row sums' column blocks
-    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_both<<<dim3(nbc, P.K + 1), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dx, v.dy, d.dyn_x1.p,
-                                                                                        d.dyn_part.p, nbc));
-    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_ax_finish<<<dim3((npmax + 255) / 256, P.K), 256, 0, h->stream>>>(d.dyn_desc.p, d.dyn_part.p, nbc,
-                                                                                                     v.dx, d.dyn_x2.p));
-  } else {
-    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_ax<<<dim3(std::min((npmax + 3) / 4, 2048), P.K), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dx,
-                                                                                                          d.dyn_x2.p));
-    KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_aty<<<dim3((nzmax + 255) / 256, P.K + 1), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dy,
-                                                                                                   d.dyn_x1.p));
-  }
+  // one pass over F for both products (k_st_dyn_both), then the row sums' column blocks (dyn_part: staged_upload)
+  const int nbc = d.dyn_part_cols;
+  KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_both<<<dim3(nbc, P.K + 1), 256, 0, h->stream>>>(d.dyn_desc.p, d.F.p, v.dx, v.dy, d.dyn_x1.p,
+                                                                                      d.dyn_part.p, nbc));
+  KLAUNCH(h, KC_RESIDUAL, stg::k_st_dyn_ax_finish<<<dim3((npmax + 255) / 256, P.K), 256, 0, h->stream>>>(d.dyn_desc.p, d.dyn_part.p, nbc,
+                                                                                                   v.dx, d.dyn_x2.p));
   *x1 = d.dyn_x1.p, *x2 = d.dyn_x2.p, *ndyn = P.ndyn;
   return 0;
 }
@@ -52,9 +44,6 @@ int staged_step(hqpkkt_t *h, const Vecs &v, int which) {
   if (staged_is_sharded(h)) return staged_run_step(h, v);  // exchanges inside the sweeps: not captured
   return graphed(h, h->gstep[which][0], [&]() { return staged_run_step(h, v); });
 }
-// hqpkkt_analyze / hqpkkt_set_values of a handle in HQPKKT_MODE_STAGED: the CSR hand-over of the dynamics
-int staged_analyze_csr(hqpkkt_t *h, int n, int me, int m) { return staged_analyze(h, n, me, m); }
-int staged_set_values_csr(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx) { return staged_set_values(h, Qx, Ax, Cx); }
 void StagedDevDelete::operator()(StagedDev *d) const { delete d; }
 void staged_reset(StagedDev &d) {
   kktdev::StagedPlan plan = std::move(d.plan);
@@ -291,6 +280,83 @@ __global__ void k_gemm_check(stg::GemmArgs g, int nsample, double *err) {
   const double e = fabs(g.C[(long long)ci * g.ldc + cj] - g.alpha * s) / (sa + 1e-300);
   atomic_max_pos((unsigned long long *)err, e);
 }
+// HQPKKT_DGEMM_STAMPS: one more launch of the product with time stamps (100 MHz constant clock), printed to stderr
+static void dgemm_stamps_split(const stg::GemmArgs &g, const stg::GemmForm &f, int variant, int skg, const stg::SplitTable &sk_tab, const stg::SkUnit *tab_dev) {
+  // the split form with time stamps: per workgroup its start and, per unit, the end of the k loop, of the
+  // parking / summing of partial tiles and of the epilogue (us after the first start)
+  DBuf<unsigned long long> st;
+  DBuf<double> ws2;
+  DBuf<unsigned> cnt2;
+  if (st.alloc(32 * (size_t)skg) || ws2.alloc((size_t)(16 * f.tiles + 8) * 128 * 128) || cnt2.alloc(f.tiles + 4)) return;
+  (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 32 * skg);
+  (void)hipMemset(cnt2.p, 0, sizeof(unsigned) * (f.tiles + 4));
+  stg::GemmArgs gs = g;
+  gs.stamps = st.p;
+  stg::SplitPlan skk = stg::gemm_split_plan(f.tiles, stg::gemm_slabs(g.K), skg);
+  skk.ws = ws2.p, skk.cnt = cnt2.p;
+  if (tab_dev) skk.table = tab_dev, skk.stride = sk_tab.stride;
+  stg::gemm_launch_split(variant, skg, 0, gs, skk);
+  std::vector<unsigned long long> hs(32 * (size_t)skg);
+  if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) != hipSuccess) return;
+  unsigned long long tmin = ~0ULL;
+  for (int w = 0; w < skg; w++) tmin = std::min(tmin, hs[32 * (size_t)w]);
+  if (tab_dev)
+    fprintf(stderr, "table plan: %d / %d whole tiles per first / second workgroup of a CU, %lld parked pieces", sk_tab.nA, sk_tab.nB, sk_tab.pieces);
+  else {
+    fprintf(stderr, "split plan: %d whole tiles", skk.whole);
+    for (int q = 0; q < skk.nphase; q++) fprintf(stderr, ", %d tiles x %d pieces", skk.count[q], skk.split[q]);
+  }
+  fprintf(stderr, "; stamps of every %dth workgroup (us): start | per unit: k loop end, parked / summed, epilogue end\n", std::max(1, skg / 32));
+  const int nr = tab_dev ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
+  for (int w = 0; w < skg; w += std::max(1, skg / 32)) {
+    fprintf(stderr, "  wg %4d: %7.2f |", w, (hs[32 * (size_t)w] - tmin) * 0.01);
+    for (int r = 0; r < nr; r++) {
+      for (int c = 1; c <= 3; c++) {
+        const unsigned long long x = hs[32 * (size_t)w + 3 * r + c];
+        if (x) fprintf(stderr, " %8.2f", (x - tmin) * 0.01); else fprintf(stderr, "        -");
+      }
+      fprintf(stderr, " |");
+    }
+    fprintf(stderr, "\n");
+  }
+  // the end of every workgroup's last unit, per class (first / second half of the launch)
+  for (int c = 0; c < 2; c++) {
+    double lo = 1e30, hi = 0.0, sum = 0.0;
+    int n = 0;
+    for (int w = c * skg / 2; w < (c + 1) * skg / 2; w++) {
+      unsigned long long last = 0;
+      for (int r = 0; r < 10; r++) last = std::max(last, hs[32 * (size_t)w + 3 * r + 3]);
+      if (!last) continue;
+      const double e = (last - tmin) * 0.01;
+      lo = std::min(lo, e), hi = std::max(hi, e), sum += e, n++;
+    }
+    if (n) fprintf(stderr, "  class %c (blockIdx %s grid / 2): last epilogue ends at %.1f ... %.1f us, mean %.1f\n", c ? 'B' : 'A', c ? ">=" : "<", lo, hi, sum / n);
+  }
+}
+static void dgemm_stamps_plain(const stg::GemmArgs &g, long long tiles, int variant) {
+  // one more launch with time stamps per workgroup (100 MHz constant clock): when it started, when its k loop
+  // ended, when its epilogue ended - relative to the first start; printed as a histogram over the workgroups
+  DBuf<unsigned long long> st;
+  if (st.alloc(4 * (size_t)tiles)) return;
+  stg::GemmArgs gs = g;
+  gs.stamps = st.p;
+  stg::gemm_launch_plain(variant, (unsigned)tiles, 0, gs);
+  std::vector<unsigned long long> hs(4 * tiles);
+  if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 4 * tiles, hipMemcpyDeviceToHost) != hipSuccess) return;
+  unsigned long long tmin = ~0ULL;
+  for (long long t = 0; t < tiles; t++) tmin = std::min(tmin, hs[4 * t]);
+  // workgroups in the order of their start
+  std::vector<long long> ord(tiles);
+  for (long long t = 0; t < tiles; t++) ord[t] = t;
+  std::sort(ord.begin(), ord.end(), [&](long long a, long long b) { return hs[4 * a] < hs[4 * b]; });
+  fprintf(stderr, "stamps (us after the first start; %lld workgroups, every %lldth in start order): start, k loop end, epilogue end, xcc, blockIdx\n", tiles,
+          std::max<long long>(1, tiles / 64));
+  for (long long q = 0; q < tiles; q += std::max<long long>(1, tiles / 64)) {
+    const long long t = ord[q];
+    fprintf(stderr, "  %8.2f %8.2f %8.2f  xcc %llu  wg %lld\n", (hs[4 * t] - tmin) * 0.01, (hs[4 * t + 2] - tmin) * 0.01, (hs[4 * t + 3] - tmin) * 0.01,
+            hs[4 * t + 1], t);
+  }
+}
 }  // namespace
 int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
   if (M <= 0 || N <= 0 || K < 0 || reps <= 0) return HQPKKT_E_RANGE;
@@ -315,42 +381,40 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
     (void)hipMemset(zr.p, 0, sizeof(double) * 256);
     g.zeros = zr.p;
   }
+  // The engine's rule (gemm_form.hpp) with what this entry point has always done differently: no thin product cut in k, no
+  // tile order for large triangles, never sharded, and a workspace of its own - 16 parked pieces per tile
+  // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   const int skg = stg::gemm_wgs_per_cu(variant) * cus;
-  // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
-  const bool frac = !getenv("HQPKKT_DGEMM_FORCE_SPLIT") && stg::gemm_use_frac(M, N, K, lower, skg);
-  const bool use_sk = frac || stg::gemm_use_split(M, N, K, lower, skg) || getenv("HQPKKT_DGEMM_FORCE_SPLIT");
-  const bool big = use_sk || stg::gemm_big_tiles(M, N, lower, K);
-  const int b = big ? 128 : 64;
-  const long long tiles = stg::gemm_tiles(M, N, b, lower);
+  const long long t128 = stg::gemm_tiles(M, N, 128, lower), nslab = stg::gemm_slabs(K);
+  const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
+  const stg::GemmForm f = stg::gemm_form(M, N, K, lower, mirror, cus, skg, t128, ws_elems, 0, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP |
+                                         (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0));
+  const bool frac = f.kind == stg::GEMM_FORM_FRAC, use_sk = frac || f.kind == stg::GEMM_FORM_CUT;
   (void)stg::gemm_set_attributes();
-  // stream-K form where the engine would use it (staged_host.hip.h, st_gemm)
-  if (use_sk && (skws.alloc((size_t)std::max<long long>(16 * tiles + 8, 2LL * skg + 2) * 128 * 128) || skcnt.alloc(tiles + 4)))
-    return HQPKKT_E_MEM;
+  if (use_sk && (skws.alloc((size_t)ws_elems) || skcnt.alloc(f.tiles + 4))) return HQPKKT_E_MEM;
   // (the cut form by a table with unequal shares for the two workgroups of a CU: gemm_split_table; HQPKKT_SK_TABLE=0: equal shares)
   stg::SplitTable sk_tab;
-  if (use_sk && !frac && stg::gemm_sk_table_from_env() && stg::gemm_split_table(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg, sk_tab) &&
-      sk_tab.pieces <= 16 * tiles + 8) {
-    if (sk_table_dev.upload(sk_tab.units)) return HQPKKT_E_MEM;
-  }
+  if (f.kind == stg::GEMM_FORM_CUT && stg::gemm_sk_table_from_env() && stg::gemm_split_table(f.tiles, nslab, skg, sk_tab) && sk_tab.pieces <= 16 * f.tiles + 8 &&
+      sk_table_dev.upload(sk_tab.units))
+    return HQPKKT_E_MEM;
   EventOwner e0, e1;
   (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
     if (r == 0) (void)hipEventRecord(e0, 0);
     if (use_sk) {
-      (void)hipMemsetAsync(skcnt.p, 0, sizeof(unsigned) * (tiles + 4), 0);
-      stg::SplitPlan skk = frac ? stg::gemm_split_plan_frac(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg)
-                                : stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
+      (void)hipMemsetAsync(skcnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
+      stg::SplitPlan skk = frac ? stg::gemm_split_plan_frac(f.tiles, nslab, skg) : stg::gemm_split_plan(f.tiles, nslab, skg);
       skk.ws = skws.p, skk.cnt = skcnt.p;
       if (sk_table_dev.p) skk.table = sk_table_dev.p, skk.stride = sk_tab.stride;
       stg::gemm_launch_split(variant, skg, 0, g, skk);
-    } else if (big)
-      stg::gemm_launch_plain(variant, (unsigned)tiles, 0, g, cus);
-    else if (stg::gemm_tiles_6432(M, N, K, lower, mirror, cus))  // (as st_gemm chooses)
-      stg::k_dgemm_tn<64, 32><<<(unsigned)(((M + 63) / 64) * (long long)((N + 31) / 32)), 256, stg::gemm_lds_bytes(64, 32)>>>(g);
+    } else if (f.kind == stg::GEMM_FORM_PLAIN)
+      stg::gemm_launch_plain(variant, (unsigned)f.tiles, 0, g, cus);
+    else if (f.kind == stg::GEMM_FORM_6432)
+      stg::k_dgemm_tn<64, 32><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 32)>>>(g);
     else
-      stg::k_dgemm_tn<64, 64><<<(unsigned)tiles, 256, stg::gemm_lds_bytes(64, 64)>>>(g);
+      stg::k_dgemm_tn<64, 64><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 64)>>>(g);
   }
   (void)hipEventRecord(e1, 0);
   hipError_t se = hipDeviceSynchronize();
@@ -358,85 +422,9 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   float t = 0.f;
   (void)hipEventElapsedTime(&t, e0, e1);
   if (se != hipSuccess) return HQPKKT_E_DEVICE;
-  if (getenv("HQPKKT_DGEMM_STAMPS") && use_sk && !frac) {
-    // the split form with time stamps: per workgroup its start and, per unit, the end of the k loop, of the
-    // parking / summing of partial tiles and of the epilogue (us after the first start)
-    DBuf<unsigned long long> st;
-    DBuf<double> ws2;
-    DBuf<unsigned> cnt2;
-    if (!st.alloc(32 * (size_t)skg) && !ws2.alloc((size_t)(16 * tiles + 8) * 128 * 128) && !cnt2.alloc(tiles + 4)) {
-      (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 32 * skg);
-      (void)hipMemset(cnt2.p, 0, sizeof(unsigned) * (tiles + 4));
-      stg::GemmArgs gs = g;
-      gs.stamps = st.p;
-      stg::SplitPlan skk = stg::gemm_split_plan(tiles, (K + stg::GEMM_BK - 1) / stg::GEMM_BK, skg);
-      skk.ws = ws2.p, skk.cnt = cnt2.p;
-      if (sk_table_dev.p) skk.table = sk_table_dev.p, skk.stride = sk_tab.stride;
-      stg::gemm_launch_split(variant, skg, 0, gs, skk);
-      std::vector<unsigned long long> hs(32 * (size_t)skg);
-      if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) == hipSuccess) {
-        unsigned long long tmin = ~0ULL;
-        for (int w = 0; w < skg; w++) tmin = std::min(tmin, hs[32 * (size_t)w]);
-        if (sk_table_dev.p)
-          fprintf(stderr, "table plan: %d / %d whole tiles per first / second workgroup of a CU, %lld parked pieces", sk_tab.nA, sk_tab.nB, sk_tab.pieces);
-        else {
-          fprintf(stderr, "split plan: %d whole tiles", skk.whole);
-          for (int q = 0; q < skk.nphase; q++) fprintf(stderr, ", %d tiles x %d pieces", skk.count[q], skk.split[q]);
-        }
-        fprintf(stderr, "; stamps of every %dth workgroup (us): start | per unit: k loop end, parked / summed, epilogue end\n", std::max(1, skg / 32));
-        const int nr = sk_table_dev.p ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
-        for (int w = 0; w < skg; w += std::max(1, skg / 32)) {
-          fprintf(stderr, "  wg %4d: %7.2f |", w, (hs[32 * (size_t)w] - tmin) * 0.01);
-          for (int r = 0; r < nr; r++) {
-            for (int c = 1; c <= 3; c++) {
-              const unsigned long long x = hs[32 * (size_t)w + 3 * r + c];
-              if (x) fprintf(stderr, " %8.2f", (x - tmin) * 0.01); else fprintf(stderr, "        -");
-            }
-            fprintf(stderr, " |");
-          }
-          fprintf(stderr, "\n");
-        }
-        // the end of every workgroup's last unit, per class (first / second half of the launch)
-        for (int c = 0; c < 2; c++) {
-          double lo = 1e30, hi = 0.0, sum = 0.0;
-          int n = 0;
-          for (int w = c * skg / 2; w < (c + 1) * skg / 2; w++) {
-            unsigned long long last = 0;
-            for (int r = 0; r < 10; r++) last = std::max(last, hs[32 * (size_t)w + 3 * r + 3]);
-            if (!last) continue;
-            const double e = (last - tmin) * 0.01;
-            lo = std::min(lo, e), hi = std::max(hi, e), sum += e, n++;
-          }
-          if (n) fprintf(stderr, "  class %c (blockIdx %s grid / 2): last epilogue ends at %.1f ... %.1f us, mean %.1f\n", c ? 'B' : 'A', c ? ">=" : "<", lo, hi, sum / n);
-        }
-      }
-    }
-  }
-  if (getenv("HQPKKT_DGEMM_STAMPS") && !use_sk && big) {
-    // one more launch with time stamps per workgroup (100 MHz constant clock): when it started, when its k loop
-    // ended, when its epilogue ended - relative to the first start; printed as a histogram over the workgroups
-    DBuf<unsigned long long> st;
-    if (!st.alloc(4 * (size_t)tiles)) {
-      stg::GemmArgs gs = g;
-      gs.stamps = st.p;
-      stg::gemm_launch_plain(variant, (unsigned)tiles, 0, gs);
-      std::vector<unsigned long long> hs(4 * tiles);
-      if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 4 * tiles, hipMemcpyDeviceToHost) == hipSuccess) {
-        unsigned long long tmin = ~0ULL;
-        for (long long t = 0; t < tiles; t++) tmin = std::min(tmin, hs[4 * t]);
-        // workgroups in the order of their start
-        std::vector<long long> ord(tiles);
-        for (long long t = 0; t < tiles; t++) ord[t] = t;
-        std::sort(ord.begin(), ord.end(), [&](long long a, long long b) { return hs[4 * a] < hs[4 * b]; });
-        fprintf(stderr, "stamps (us after the first start; %lld workgroups, every %lldth in start order): start, k loop end, epilogue end, xcc, blockIdx\n", tiles,
-                std::max<long long>(1, tiles / 64));
-        for (long long q = 0; q < tiles; q += std::max<long long>(1, tiles / 64)) {
-          const long long t = ord[q];
-          fprintf(stderr, "  %8.2f %8.2f %8.2f  xcc %llu  wg %lld\n", (hs[4 * t] - tmin) * 0.01, (hs[4 * t + 2] - tmin) * 0.01, (hs[4 * t + 3] - tmin) * 0.01,
-                  hs[4 * t + 1], t);
-        }
-      }
-    }
+  if (getenv("HQPKKT_DGEMM_STAMPS")) {
+    if (f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, f, variant, skg, sk_tab, sk_table_dev.p);
+    if (f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(g, f.tiles, variant);
   }
   k_gemm_check<<<16, 256>>>(g, 4096, err.p);
   double he = 0.0;
@@ -444,6 +432,16 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   if (ms) *ms = t / reps;
   if (max_err) *max_err = he;
   return 0;
+}
+
+int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,
+                           long long ws2_elems, int flags, long long *tiles, int *table, int *tile_map, int *nsplit) {
+  const stg::GemmForm f = stg::gemm_form(M, N, K, lower, mirror, cus, grid, sk_tiles, ws_elems, ws2_elems, flags);
+  if (tiles) *tiles = f.tiles;
+  if (table) *table = f.kind == stg::GEMM_FORM_CUT;
+  if (tile_map) *tile_map = f.tile_map;
+  if (nsplit) *nsplit = f.nsplit;
+  return f.kind;
 }
 
 int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {

@@ -1,6 +1,7 @@
 // Host side of the STAGED engine: device residency of the stage blocks and the kernel
 // sequences of factor (backward recursion over the stages) and step (backward vector sweep,
-// initial state, forward sweep).  Included by hqpkkt.hip after struct hqpkkt.
+// initial state, forward sweep).  Included by staged_engine.hip alone, behind hqpkkt_handle.hpp and staged.hip.h; what
+// the other units call of it is declared in hqpkkt_handle.hpp.
 // Reference counterpart: Hqp_IpLQDOCP::update / factor / step (hqp/Hqp_IpLQDOCP.C:722-976).
 #pragma once
 
@@ -10,7 +11,7 @@ struct StagedDev {
   DBuf<int> dyn, eq_rows, fix_rows, fix_src, h_tptr, chk_idx, chk_kind;
   DBuf<long long> h_dst, a_dst;
   DBuf<stg::HTerm> h_terms;
-  DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_ax / _aty need
+  DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
   DBuf<double> dyn_part;        // row sums of A_dyn dx per block of 256 columns (k_st_dyn_both): ndyn x dyn_part_cols
   int dyn_part_cols = 0;
@@ -106,17 +107,34 @@ struct StagedDev {
     sk_tabs.push_back(std::move(e));
     return sk_tabs.back().units.p ? &sk_tabs.back() : nullptr;
   }
-  // (the shape of a product as st_gemm launches it)
+  // the form the launch rule (gemm_form.hpp) gives a product of this handle
+  stg::GemmForm gemm_form(int M, int N, int K, int lower, int mirror, bool first_stream = true) const {
+    return stg::gemm_form(M, N, K, lower, mirror, cus, sk_grid, sk_tiles, sk_ws_elems, ks_ws2_elems,
+                          (plan.sharded ? stg::GEMM_SHARDED : 0) | (first_stream ? 0 : stg::GEMM_SECOND_STREAM));
+  }
+  // (the shape of a product as st_gemm launches it on the first stream)
   void sk_tab_prepare(int M, int N, int K, int lower) {
-    if (M <= 0 || N <= 0 || K <= 0 || sk_grid <= 0 || (lower && M < N)) return;
-    if (!stg::gemm_use_split(M, N, K, lower, sk_grid) || (!plan.sharded && stg::gemm_use_frac(M, N, K, lower, sk_grid))) return;
-    (void)sk_tab(stg::gemm_tiles(M, N, 128, lower), (K + stg::GEMM_BK - 1) / stg::GEMM_BK, true);
+    const stg::GemmForm f = gemm_form(M, N, K, lower, 0);
+    if (f.kind == stg::GEMM_FORM_CUT) (void)sk_tab(f.tiles, stg::gemm_slabs(K), true);
   }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
   long long sk_ws_elems = 0, sk_cnt_elems = 0;
 };
 
 namespace {
+
+// the unit's environment switches that are read once per process, each at its first use (HQPKKT_NO_LDSDMA,
+// HQPKKT_DGEMM_WAVES and HQPKKT_SK_TABLE are read at every upload: stg::gemm_variant_from_env, gemm_sk_table_from_env)
+bool env_no_symv() { static const bool v = getenv("HQPKKT_NO_SYMV") != nullptr; return v; }  // the rows form of the solve's products with V
+int env_symv_from() { static const int v = getenv("HQPKKT_SYMV_FROM") ? atoi(getenv("HQPKKT_SYMV_FROM")) : 2048; return v; }
+double env_block_gj_tol() { static const double v = getenv("HQPKKT_BLOCK_GJ_TOL") ? atof(getenv("HQPKKT_BLOCK_GJ_TOL")) : 1e-6; return v; }
+bool env_spd_test_fail() { static const bool v = getenv("HQPKKT_SPD_TEST_FAIL") != nullptr; return v; }  // tests: k_st_small<1024, false> refuses
+// launches go to h->stream: back to the first stream on every way out
+struct StreamGuard {
+  hqpkkt_t *h;
+  hipStream_t s;
+  ~StreamGuard() { h->stream = s; }
+};
 
 // per-stage pointers into the arenas
 struct StagePtr {
@@ -141,64 +159,49 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
   return s;
 }
 
-// C = alpha A'B + beta Cin on the handle's stream; 128 x 128 tiles for large products, 64 x 64 below
-int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true) {
+// C = alpha A'B + beta Cin on the handle's stream, in the form the launch rule gives the shape (gemm_form.hpp)
+// (allow_sk false: launches of the second stream).  ntiles > 0: the tiles g.tile_map[0 .. ntiles) of the product only
+// (128 x 128 tiles; the blocks of G_xx one rank owns)
+int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true, int ntiles = 0) {
   if (g.M <= 0 || g.N <= 0) return 0;
-  StagedDev *d = h->sd.get();
+  StagedDev &d = *h->sd;
+  const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, g.K, d.sk_grid, d.sk_tiles) : d.gemm_form(g.M, g.N, g.K, g.lower, g.mirror, allow_sk);
+  if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_INTERN;
+  if (f.tile_map) g.tile_map = d.tri_map((g.M + 127) / 128);
   // operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd
   // column (the control columns F + nn of a stage with an odd number of states) is staged through registers
-  const bool al16 = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0);
-  // (allow_sk false: launches of the second stream - the workspace of the split form belongs to the first)
-  const bool no_frac = false;
-  // (not for one system over several ranks: there the strip product W_p = V+ F_p - 200 tiles at eight ranks - runs beside
-  // the second stream's control-sized products, and a launch whose 512 workgroups hold every CU for its whole duration
-  // starves them: 1.46 against 1.32 ms per stage, tools/shard_pieces.py 8 0)
-  const bool frac = d && allow_sk && d->sk_grid > 0 && !no_frac && !d->plan.sharded && stg::gemm_use_frac(g.M, g.N, g.K, g.lower, d->sk_grid) &&
-                    2LL * d->sk_grid * 128 * 128 <= d->sk_ws_elems;
-  const bool split = frac || (d && allow_sk && d->sk_grid > 0 && stg::gemm_use_split(g.M, g.N, g.K, g.lower, d->sk_grid));
-  const bool big = split || stg::gemm_big_tiles(g.M, g.N, g.lower, g.K);
-  const int b = big ? 128 : 64;
-  const long long tm = (g.M + b - 1) / b;
-  const long long tiles = stg::gemm_tiles(g.M, g.N, b, g.lower);
-  if (g.lower && g.M < g.N) return HQPKKT_E_INTERN;  // (lower: a triangle, or the column strip of one)
-  if (g.lower && g.M == g.N && big && d && tm >= 16 && tm < 32768) g.tile_map = d->tri_map((int)tm);
-  if (d && d->zeros.p && al16) g.zeros = d->zeros.p;
-  if (split && tiles <= d->sk_tiles) {
-    // tile count that does not fill the chip evenly: whole rounds, then the k ranges of the rest cut (k_dgemm_tn_sk)
-    // (the arrival counters are zero between launches: the last arriver of a tile resets its counter)
-    // (a few hundred tiles: the k-slabs of all tiles in one sequence, an equal share per workgroup - gemm_use_frac)
-    stg::SplitPlan sk = frac ? stg::gemm_split_plan_frac(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, d->sk_grid)
-                             : stg::gemm_split_plan(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, d->sk_grid);
-    const StagedDev::SkTab *tab = frac ? nullptr : d->sk_tab(tiles, (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK, !h->capturing);
-    if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
-    if (frac || tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d->sk_ws_elems) {
-      sk.ws = d->sk_ws.p, sk.cnt = d->sk_cnt.p;
-      KLAUNCH(h, cls, stg::gemm_launch_split(d->gemm_variant, d->sk_grid, h->stream, g, sk));
-      return 0;
+  if (d.zeros.p && ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0)) g.zeros = d.zeros.p;
+  const int variant = ntiles && !g.zeros ? stg::GEMM_REG4 : d.gemm_variant;
+  double *ws = allow_sk ? d.sk_ws.p : d.ks_ws2.p;
+  switch (f.kind) {
+    case stg::GEMM_FORM_FRAC:
+    case stg::GEMM_FORM_CUT: {
+      // whole rounds, then the k ranges of the rest cut - by the shape's work table where there is one -, or the k-slabs
+      // of all tiles in one sequence (the arrival counters are zero between launches: the last arriver of a tile resets its)
+      const long long nslab = stg::gemm_slabs(g.K);
+      const bool frac = f.kind == stg::GEMM_FORM_FRAC;
+      stg::SplitPlan sk = frac ? stg::gemm_split_plan_frac(f.tiles, nslab, d.sk_grid) : stg::gemm_split_plan(f.tiles, nslab, d.sk_grid);
+      const StagedDev::SkTab *tab = frac ? nullptr : d.sk_tab(f.tiles, nslab, !h->capturing);
+      if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
+      if (frac || tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d.sk_ws_elems) {
+        sk.ws = d.sk_ws.p, sk.cnt = d.sk_cnt.p;
+        KLAUNCH(h, cls, stg::gemm_launch_split(variant, d.sk_grid, h->stream, g, sk));
+        break;
+      }
+      [[fallthrough]];  // (the workspace does not hold the plan's pieces: a plain round)
     }
-  }
-  if (big)
-    KLAUNCH(h, cls, stg::gemm_launch_plain(d ? d->gemm_variant : stg::GEMM_REG4, (unsigned)tiles, h->stream, g, d ? d->cus : 0));
-  else if (d && d->cus > 0 && !g.lower && !g.mirror && g.K >= 512 && tiles * 2 <= d->cus &&
-           (long long)g.M * g.N * 4 <= (allow_sk ? d->sk_ws_elems : d->ks_ws2_elems)) {
-    // a thin, deep product: its k range cut over the chip (k_dgemm_tn_ks), the pieces added in their order (the
-    // launches of the second stream have a workspace of their own)
-    double *ws = allow_sk ? d->sk_ws.p : d->ks_ws2.p;
-    const long long wse = allow_sk ? d->sk_ws_elems : d->ks_ws2_elems;
-    const int nslab = (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK;
-    int nsplit = (int)std::min<long long>(nslab / 4, std::max<long long>(1, (2LL * d->cus) / tiles));
-    nsplit = (int)std::max<long long>(1, std::min<long long>(nsplit, wse / std::max<long long>(1, (long long)g.M * g.N)));
-    KLAUNCH(h, cls, (stg::k_dgemm_tn_ks<64, 64><<<dim3((unsigned)tiles, nsplit), 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g, ws, nsplit)));
-    KLAUNCH(h, cls, stg::k_dgemm_ks_finish<<<nblk((long long)g.M * g.N), 256, 0, h->stream>>>(g, ws, nsplit));
-  } else {
-    // few tiles of a deep rectangular product (W of a stage of ~1000 states: 272): 64 x 32 tiles, so that a CU holds two
-    // workgroups and one multiplies while the other waits at its barrier: 81 -> 73 us
-    if (stg::gemm_tiles_6432(g.M, g.N, g.K, g.lower, g.mirror, d ? d->cus : 0)) {
-      const long long t2 = ((g.M + 63) / 64) * (long long)((g.N + 31) / 32);
-      KLAUNCH(h, cls, (stg::k_dgemm_tn<64, 32><<<(unsigned)t2, 256, stg::gemm_lds_bytes(64, 32), h->stream>>>(g)));
-      return 0;
-    }
-    KLAUNCH(h, cls, stg::k_dgemm_tn<64, 64><<<(unsigned)tiles, 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g));
+    case stg::GEMM_FORM_PLAIN:
+      KLAUNCH(h, cls, stg::gemm_launch_plain(variant, (unsigned)f.tiles, h->stream, g, d.cus));
+      break;
+    case stg::GEMM_FORM_KS:
+      KLAUNCH(h, cls, (stg::k_dgemm_tn_ks<64, 64><<<dim3((unsigned)f.tiles, f.nsplit), 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g, ws, f.nsplit)));
+      KLAUNCH(h, cls, stg::k_dgemm_ks_finish<<<nblk((long long)g.M * g.N), 256, 0, h->stream>>>(g, ws, f.nsplit));
+      break;
+    case stg::GEMM_FORM_6432:
+      KLAUNCH(h, cls, (stg::k_dgemm_tn<64, 32><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 32), h->stream>>>(g)));
+      break;
+    default:
+      KLAUNCH(h, cls, stg::k_dgemm_tn<64, 64><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g));
   }
   return 0;
 }
@@ -211,9 +214,7 @@ int st_gemv_rows(hqpkkt_t *h, stg::GemvRows g) {
 // y = scale (add + V x + A2 x2) with the symmetric V of a stage: from 2048 states on only the tiles on and below the
 // diagonal are read (k_st_symv_tiles + k_st_symv_finish; HQPKKT_NO_SYMV: the rows form throughout)
 bool symv_tiles_form(const stg::GemvRows &g) {
-  static const bool off = getenv("HQPKKT_NO_SYMV") != nullptr;
-  static const int from = getenv("HQPKKT_SYMV_FROM") ? atoi(getenv("HQPKKT_SYMV_FROM")) : 2048;
-  return !(off || g.M != g.N || g.N < from || (g.lda & 1) || (((size_t)g.A) & 15));
+  return !(env_no_symv() || g.M != g.N || g.N < env_symv_from() || (g.lda & 1) || (((size_t)g.A) & 15));
 }
 long long symv_tiles(int N) {
   const int nrt = (N + stg::SV_R - 1) / stg::SV_R;
@@ -341,13 +342,6 @@ static int st_blk_sweep(hqpkkt_t *h, double *scratch, int q, bool allow_sk) {
   return 0;
 }
 static int st_small_big(hqpkkt_t *h, StagedDev &d, stg::SmallArgs sa, bool allow_sk) {
-  const bool legacy = false;  // (the one-workgroup inverse: the fall-back of the blocked sweep only)
-  static const double tol = getenv("HQPKKT_BLOCK_GJ_TOL") ? atof(getenv("HQPKKT_BLOCK_GJ_TOL")) : 1e-6;
-  if (legacy) {
-    sa.mode = 0;
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds_small_big, h->stream>>>(sa));
-    return 0;
-  }
   int e;
   sa.mode = 1;
   KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds_small_big, h->stream>>>(sa));
@@ -357,18 +351,40 @@ static int st_small_big(hqpkkt_t *h, StagedDev &d, stg::SmallArgs sa, bool allow
   KLAUNCH(h, KC_ST_SMALL, stg::k_blk_final<<<nblk((long long)q * q), 256, 0, h->stream>>>(sa));
   if ((e = st_gemm(h, stg::GemmArgs{sa.Kmat, sa.ldq, sa.Kinv, sa.ldq, nullptr, 0, bs.Ks, bs.ldk, q, q, q, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, allow_sk)))
     return e;
-  KLAUNCH(h, KC_ST_SMALL, stg::k_blk_check<<<1, 1024, 0, h->stream>>>(sa, tol));
+  KLAUNCH(h, KC_ST_SMALL, stg::k_blk_check<<<1, 1024, 0, h->stream>>>(sa, env_block_gj_tol()));
   sa.mode = 2;
   KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds_small_big, h->stream>>>(sa));
   return 0;
 }
 
-// Rm = K^-1 Y, refined against K: one launch for K of order <= 64 (k_st_rm), three products above
-// (wa: the arguments of k_st_wide - Y and the carried rows B_k; with K of order 1 .. 64 they are formed inside k_st_rm)
-static int st_rm(hqpkkt_t *h, StagedDev &d, const StagePtr &sp, int k, bool allow_sk, const stg::WideArgs &wa) {
+// ---- the steps of a stage that the single-GPU and the sharded sequence share; all on h->stream
+
+// H's entries first .. first + count of the plan's list added into the work block G
+static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G, int add = 1) {
+  if (count)
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
+                                                                               h->td.vals.p, h->td.wt.p, G, add));
+}
+// the control-sized elimination of stage k on the work block G: rank decision and K^-1 (k_st_small, or the blocked sweep
+// for matrices that live in global memory), Y and the carried rows, Rm = K^-1 Y (allow_sk: as in st_gemm)
+static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, double *G, bool allow_sk) {
   const kktdev::StagedPlan &P = d.plan;
-  const int q = P.qmax[k], nn = P.nk[k];
+  const int nn = P.nk[k], mm = P.mk[k], ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
+  stg::SmallArgs sa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
+                    P.capn[k], P.cap[k], P.qmax[k], h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->td.flags.p,
+                    P.big[k] ? d.misc.p + P.oScr : nullptr};
+  if (P.big[k]) {
+    if (int e2 = st_small_big(h, d, sa, allow_sk)) return e2;
+  } else if (P.qmax[k] > 64) {
+    if (env_spd_test_fail()) sa.mode = 100;
+    KLAUNCH(h, KC_ST_SMALL, (stg::k_st_small<1024, false><<<1, 1024, d.lds_small, h->stream>>>(sa)));
+  } else
+    KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<256><<<1, 256, d.lds_small, h->stream>>>(sa));
+  // Rm = K^-1 Y, refined against K: one launch for K of order <= 64 (k_st_rm), three products above
+  // (wa: the arguments of k_st_wide - Y and the carried rows B_k; with K of order 1 .. 64 they are formed inside k_st_rm)
+  const int q = P.qmax[k];
   const long long ldy = P.ldy[k];
+  stg::WideArgs wa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], P.capn[k], P.cap[k], q, sp.T, P.ldt[k], sp.dyn, sp.Y, ldy, sp.BT, P.ldb[k]};
   if (q > 0 && q <= 64) {
     stg::RmArgs ra{sp.Kinv, sp.Kmat, P.ldq[k], sp.Y, sp.Rm, ldy, q, nn, 1, wa};
     KLAUNCH(h, KC_ST_GEMM_UPD, stg::k_st_rm<<<(nn + stg::RM_COLS - 1) / stg::RM_COLS, 256, stg::st_rm_lds(q), h->stream>>>(ra));
@@ -387,8 +403,68 @@ static int st_rm(hqpkkt_t *h, StagedDev &d, const StagePtr &sp, int k, bool allo
     return e;
   return 0;
 }
+// sharded: this rank's rows of V_k for the solve
+static void st_keep_rows(hqpkkt_t *h, StagedDev &d, int k) {
+  const kktdev::StagedPlan &P = d.plan;
+  const StagePtr sp = stage_ptr(d, k);
+  const int c0 = P.xcut[(size_t)k * (P.shard_count + 1) + P.shard_rank], wd = P.xcut[(size_t)k * (P.shard_count + 1) + P.shard_rank + 1] - c0;
+  if (wd > 0)
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(wd, 2048), 256, 0, h->stream>>>(sp.V + (long long)c0 * P.ldv[k], P.ldv[k], sp.Vs, P.ldv[k], wd, P.nk[k]));
+}
+// backward sweep of the solve, stage k: the control-sized part (gam: q_k + F' tt)
+static void st_bwd_small(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, const double *r2, const double *gam) {
+  const kktdev::StagedPlan &P = d.plan;
+  stg::BwdSmall ba{P.nk[k], P.mk[k], P.nk[k + 1], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], d.eq_rows.p + P.eq_ptr[k], r2,
+                   P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr, sn.beta, sn.BT, P.ldb[k + 1], r2 + P.nks[k], gam, sp.Kinv, sp.Kmat, P.ldq[k], sp.T, P.ldt[k],
+                   sp.dyn, sp.rho, sp.beta};
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_bwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 3 * P.qmax[k] + 4 + 256), h->stream>>>(ba));
+}
+// the initial state x_0 (into S) and the multipliers of its constraints
+static int st_initial_state(hqpkkt_t *h, StagedDev &d, const double *r2) {
+  const kktdev::StagedPlan &P = d.plan;
+  hipStream_t s = h->stream;
+  double *M = d.misc.p, *S = M + P.oS;
+  const StagePtr s0 = stage_ptr(d, 0);
+  const int n0 = P.nk[0];
+  if (P.fixed_x0) {
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, r2, S,
+                                                                                       s0.eta, P.cap[0]));
+    return 0;
+  }
+  if (P.big0) {
+    // with the inverse of the blocked sweep (K0s[3 q]: which form the area holds; decided on the device): three
+    // products over the whole chip; k_st_x0_free behind them works only where the factors are in use
+    const int q = P.q0max, l8 = (q + 7) / 8 * 8;
+    double *vec = M + P.oK0s + 3 * (long long)q + 8, *nb = vec, *pb = vec + l8, *y = vec + 2 * l8, *r = vec + 3 * l8;
+    const stg::X0Vec xv{n0, P.cap[0], q, s0.dyn, M + P.oK0s, s0.v, s0.beta, nb, pb, pb, S, s0.eta};
+    int e;
+    KLAUNCH(h, KC_ST_VEC, stg::k_x0_rhs<<<nblk(q), 256, 0, s>>>(xv));
+    if ((e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, nb, nullptr, nullptr, 0, nullptr, nullptr, y, 1.0})) ||
+        (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0m, P.ldq0, q, q, y, pb, nullptr, 0, nullptr, nullptr, r, -1.0})) ||
+        (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, r, y, nullptr, 0, nullptr, nullptr, pb, 1.0})))
+      return e;
+    KLAUNCH(h, KC_ST_VEC, stg::k_x0_out<<<nblk(n0 + P.cap[0]), 256, 0, s>>>(xv));
+  }
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_x0_free<<<1, 256, d.lds_x0, s>>>(n0, P.cap[0], P.q0max, M + P.oK0, M + P.oK0m, M + P.oK0s, P.ldq0, s0.dyn, s0.v,
+                                                            s0.beta, S, s0.eta));
+  return 0;
+}
+// forward sweep, stage k: [u ; yhat] = -(Rm x + rho), then the controls and the stage constraints' multipliers
+static void st_fwd_small(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, double *dy) {
+  const kktdev::StagedPlan &P = d.plan;
+  hipStream_t s = h->stream;
+  const int nn = P.nk[k];
+  double *xk = d.misc.p + P.oS + P.nmk[k], *uy = d.misc.p + P.oUy;
+  if (P.qmax[k] > 0) {
+    stg::GemvRows gr{sp.Rm, P.ldy[k], P.qmax[k], nn, xk, sp.rho, nullptr, 0, nullptr, nullptr, uy, -1.0};
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_wide<<<P.qmax[k], 256, 0, s>>>(gr));
+  }
+  stg::FwdSmall fa{nn, P.mk[k], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], uy, sp.T, P.ldt[k],
+                   sp.dyn, sp.eta, d.eq_rows.p + P.eq_ptr[k], xk + nn, dy, sn.eta, P.cap[k + 1]};
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_fwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 4), s>>>(fa));
+}
 
-static int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn = false) {
+int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   if (!h->sd) h->sd.reset(new StagedDev);
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
@@ -548,7 +624,7 @@ static int staged_upload(hqpkkt_t *h) {
     pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
     d.sk_grid = 0, d.sk_tiles = (int)tmax;
     if (cus > 0) {
-      d.sk_grid = stg::gemm_wgs_per_cu(stg::gemm_variant_from_env()) * cus;
+      d.sk_grid = stg::gemm_wgs_per_cu(d.gemm_variant) * cus;
       // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
       d.sk_ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
       d.sk_cnt_elems = d.sk_tiles + 4;
@@ -685,39 +761,24 @@ static int staged_upload(hqpkkt_t *h) {
   {
     std::lock_guard<std::mutex> lk(attr_mutex);
     PerDev &pd = per_dev[h->opts.device];
-    size_t &attr_small = pd.small, &attr_small_big = pd.small_big, &attr_init = pd.init, &attr_init_big = pd.init_big, &attr_x0 = pd.x0;
-    bool &attr_gemm = pd.gemm;
-    if (!attr_gemm) {
+    if (!pd.gemm) {
       HIPCHK(stg::gemm_set_attributes());
       HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_rm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stg::st_rm_lds(64)));
-      attr_gemm = true;
+      pd.gemm = true;
     }
-    if (d.lds_small > attr_small) {
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_small<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)d.lds_small));
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_small<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)d.lds_small));
-      attr_small = d.lds_small;
-    }
-    if (d.lds_small_big > attr_small_big) {
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_small<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)d.lds_small_big));
-      attr_small_big = d.lds_small_big;
-    }
-    if (!P.big0 && d.lds_init > attr_init) {
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_init_factor<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)d.lds_init));
-      attr_init = d.lds_init;
-    }
-    if (d.lds_x0 > attr_x0) {
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_x0_free, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds_x0));
-      attr_x0 = d.lds_x0;
-    }
-    if (P.big0 && d.lds_init > attr_init_big) {
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_init_factor<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)d.lds_init));
-      attr_init_big = d.lds_init;
-    }
+    // the LDS limit of a kernel goes up when a handle needs more than any before it on the device
+    auto raise = [](size_t &have, size_t want, std::initializer_list<const void *> kernels) -> hipError_t {
+      if (want <= have) return hipSuccess;
+      for (const void *k : kernels)
+        if (hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)) return r;
+      have = want;
+      return hipSuccess;
+    };
+    HIPCHK(raise(pd.small, d.lds_small, {(const void *)stg::k_st_small<256>, (const void *)stg::k_st_small<1024, false>}));
+    HIPCHK(raise(pd.small_big, d.lds_small_big, {(const void *)stg::k_st_small<1024>}));
+    if (!P.big0) HIPCHK(raise(pd.init, d.lds_init, {(const void *)stg::k_st_init_factor<256>}));
+    HIPCHK(raise(pd.x0, d.lds_x0, {(const void *)stg::k_st_x0_free}));
+    if (P.big0) HIPCHK(raise(pd.init_big, d.lds_init, {(const void *)stg::k_st_init_factor<1024>}));
   }
   if ((e = staged_build_symv_tables(d))) return e;
   h->uploaded = true;
@@ -744,8 +805,8 @@ static int staged_copy_block(hqpkkt_t *h, int k, const double *F, long long ldF,
   return 0;
 }
 
-static int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx,
-                             const double *const *Fblk = nullptr, const long long *ldF = nullptr, bool dense = false) {
+int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx, const double *const *Fblk,
+                      const long long *ldF, bool dense) {
   Analysis &an = h->an;
   int e;
   if (!h->uploaded && (e = staged_upload(h))) return e;
@@ -781,29 +842,6 @@ static int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, co
   return 0;
 }
 
-// the tiles g.tile_map[0 .. ntiles) of a product (128 x 128 tiles; the blocks of G_xx one rank owns): their k ranges
-// cut when they do not fill the chip (k_dgemm_tn_sk), one plain round otherwise
-static int st_gemm_tiles(hqpkkt_t *h, stg::GemmArgs g, int ntiles, int cls) {
-  if (ntiles <= 0 || g.M <= 0 || g.N <= 0) return 0;
-  StagedDev *d = h->sd.get();
-  const bool al16 = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && ((g.lda & 1) == 0);
-  if (d->zeros.p && al16) g.zeros = d->zeros.p;
-  const int variant = g.zeros ? d->gemm_variant : stg::GEMM_REG4;
-  const long long nslab = (g.K + stg::GEMM_BK - 1) / stg::GEMM_BK;
-  if (d->sk_grid > 0 && ntiles % d->sk_grid != 0 && ntiles < 16LL * d->sk_grid && nslab >= 32 && ntiles <= d->sk_tiles) {
-    stg::SplitPlan sk = stg::gemm_split_plan(ntiles, nslab, d->sk_grid);
-    const StagedDev::SkTab *tab = d->sk_tab(ntiles, nslab, !h->capturing);
-    if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
-    if (tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d->sk_ws_elems) {
-      sk.ws = d->sk_ws.p, sk.cnt = d->sk_cnt.p;
-      KLAUNCH(h, cls, stg::gemm_launch_split(variant, d->sk_grid, h->stream, g, sk));
-      return 0;
-    }
-  }
-  KLAUNCH(h, cls, stg::gemm_launch_plain(variant, (unsigned)ntiles, h->stream, g, d->cus));
-  return 0;
-}
-
 // One stage of the backward recursion when ONE system is sharded over several ranks (DESIGN.md section 7,
 // staged_plan.hpp).  Rank p owns the state columns [c0, c1) of the stage: its memory holds those columns of F_k (and the
 // control columns), its products are the strip W_p = V+ F_p and the blocks of G_xx the plan gives it - as W_p' F_q, with
@@ -816,7 +854,6 @@ static int st_gemm_tiles(hqpkkt_t *h, stg::GemmArgs g, int ntiles, int cls) {
 //       gathered strips, cut in k), rank decision, K^-1 (k_st_small), Y (k_st_wide), Rm = K^-1 Y - beside the large products
 // and, joined: V_k = G_xx - Y' Rm over the WHOLE lower triangle, mirrored, with G_xx read straight from the blocks in
 // the exchange buffer (GemmArgs::rects) into the transient full block; the rank keeps its row strip for the solve.
-static int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on);
 // the gather of the ranks' local blocks of stage k into buffer k & 1: stream-ordered transport: on the exchanges' own
 // stream behind `after` (the first stream's position when the buffer's last readers are done); otherwise here and now
 static int staged_gather_f(hqpkkt_t *h, int k) {
@@ -854,11 +891,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   double *fg = d.misc.p + P.oFg[k & 1];  // the gathered local blocks of THIS stage (requested a stage ago)
   hipStream_t sA = h->stream, sB = d.stream2 ? d.stream2 : h->stream;
   hipStream_t sX = (h->xchg_sfn && d.stream_x) ? d.stream_x : nullptr;  // the exchanges' own stream (stream-ordered transport)
-  struct StreamGuard {  // launches go to h->stream: back to the first stream on every way out
-    hqpkkt_t *h;
-    hipStream_t s;
-    ~StreamGuard() { h->stream = s; }
-  } guard{h, sA};
+  StreamGuard guard{h, sA};
   const bool two = sB != sA;
   int e;
   struct JoinGuard {  // an error between fork and join must not leave the second stream forked
@@ -870,11 +903,6 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
     }
   } join{false, sA, sB, d.ev_join};
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
-  auto add_h = [&](int first, int count) {
-    if (count)
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
-                                                                                 h->td.vals.p, h->td.wt.p, G, 1));
-  };
   // the next stage's F blocks travel while this stage is computed (its buffer's last readers, the stage before this one,
   // are behind us in the first stream)
   if (k > 0 && (e = staged_gather_f(h, k - 1))) return e;
@@ -913,23 +941,8 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
     HIPCHK(hipStreamWaitEvent(sB, d.ev_x1, 0));
   }
   h->stream = sB;
-  add_h(P.h_mid[k], ne_u);
-  {
-    stg::SmallArgs sa{G, ldg, nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
-                      P.capn[k], P.cap[k], q, h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->td.flags.p,
-                      P.big[k] ? d.misc.p + P.oScr : nullptr};
-    if (P.big[k]) {
-      if ((e = st_small_big(h, d, sa, !two))) return e;
-    } else if (P.qmax[k] > 64) {
-      static const bool spd_test_fail = getenv("HQPKKT_SPD_TEST_FAIL") != nullptr;
-      if (spd_test_fail) sa.mode = 100;
-      KLAUNCH(h, KC_ST_SMALL, (stg::k_st_small<1024, false><<<1, 1024, d.lds_small, h->stream>>>(sa)));
-    }
-    else
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<256><<<1, 256, d.lds_small, h->stream>>>(sa));
-    stg::WideArgs wa{G, ldg, nn, mm, sp.N, P.ldn[k], P.capn[k], P.cap[k], q, sp.T, P.ldt[k], sp.dyn, sp.Y, ldy, sp.BT, P.ldb[k]};
-    if ((e = st_rm(h, d, sp, k, !two, wa))) return e;
-  }
+  st_add_h(h, d, P.h_mid[k], ne_u, G);
+  if ((e = st_eliminate(h, d, k, sp, sn, G, !two))) return e;
   if (two) HIPCHK(hipEventRecord(d.ev_join, sB));
   // ---- sA: the strip of W, the rank's blocks of G_xx (rows = its strip) in one launch, H_xx, pack, the gather of the blocks
   h->stream = sA;
@@ -939,7 +952,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   if (wd > 0 && ntile > 0) {
     stg::GemmArgs gg{Wl, ldwl, fg, 0, nullptr, 0, G + (long long)c0 * ldg, ldg, wd, nn, np, 1.0, 0.0, 0, 0};
     gg.tile_map = d.gtile.p + P.gtile_ptr[k], gg.bstrips = d.wtabs.p + k;
-    if ((e = st_gemm_tiles(h, gg, ntile, KC_ST_GEMM))) return e;
+    if ((e = st_gemm(h, gg, KC_ST_GEMM, true, ntile))) return e;
   }
   if (ne_x)  // H_xx into the rank's own tiles only (everything else in G is left over from earlier stages and read by nobody)
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_owned<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
@@ -966,8 +979,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   stg::GemmArgs gu{sp.Y, ldy, sp.Rm, ldy, xb, 0, sp.V, ldv, nn, nn, q, -1.0, 1.0, 1, 1};
   gu.rects = d.rtabs.p + k;
   if ((e = st_gemm(h, gu, KC_ST_GEMM_UPD))) return e;  // (q = 0, a stage without controls: V_k = G_xx, the k loop is empty)
-  if (wd > 0)
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(wd, 2048), 256, 0, sA>>>(sp.V + (long long)c0 * ldv, ldv, sp.Vs, ldv, wd, nn));
+  st_keep_rows(h, d, k);
   return 0;
 }
 
@@ -991,16 +1003,9 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   {  // last stage: V_K = H_K, all its equality rows are carried
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
-    const int ne = P.h_ptr[K + 1] - P.h_ptr[K];
-    if (ne)
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(ne), 256, 0, s>>>(ne, d.h_dst.p + P.h_ptr[K], d.h_tptr.p + P.h_ptr[K], d.h_terms.p,
-                                                                       h->td.vals.p, h->td.wt.p, sp.V, 0));
+    st_add_h(h, d, P.h_ptr[K], P.h_ptr[K + 1] - P.h_ptr[K], sp.V, 0);
     KLAUNCH(h, KC_ST_SMALL, stg::k_st_last<<<nblk(std::max(nK, 1)), 256, 0, s>>>(nK, eK, P.cap[K], sp.N, P.ldn[K], sp.BT, P.ldb[K], sp.dyn));
-    if (P.sharded) {  // this rank's rows of V_K for the solve
-      const int c0 = P.xcut[(size_t)K * (P.shard_count + 1) + P.shard_rank], wd = P.xcut[(size_t)K * (P.shard_count + 1) + P.shard_rank + 1] - c0;
-      if (wd > 0)
-        KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(wd, 2048), 256, 0, s>>>(sp.V + (long long)c0 * P.ldv[K], P.ldv[K], sp.Vs, P.ldv[K], wd, nK));
-    }
+    if (P.sharded) st_keep_rows(h, d, K);
   }
   if (P.sharded && K > 0 && (e = staged_gather_f(h, K - 1))) return e;  // (stage k requests stage k - 1's)
   for (int k = K - 1; k >= 0; k--) {
@@ -1016,19 +1021,8 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     // control columns to start at an even column: 16-byte loads of W + n)
     const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096));
     hipStream_t sA = h->stream, sB = ovl ? d.stream2 : h->stream;
-    struct StreamGuard {  // launches go to h->stream: back to the first stream on every way out
-      hqpkkt_t *h;
-      hipStream_t s;
-      ~StreamGuard() { h->stream = s; }
-    } guard{h, sA};
-    auto on_b = [&]() { h->stream = sB; };
-    auto on_a = [&]() { h->stream = sA; };
+    StreamGuard guard{h, sA};
     const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
-    auto add_h = [&](int first, int count) {
-      if (count)
-        KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
-                                                                                   h->td.vals.p, h->td.wt.p, G, 1));
-    };
     // ---- W
     if ((e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}))) return e;
     if (ovl) {
@@ -1039,38 +1033,24 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     if (!ovl) {
       // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
       if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
-      add_h(P.h_ptr[k], ne_x + ne_u);
+      st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
     } else {
       if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
-      add_h(P.h_ptr[k], ne_x);
+      st_add_h(h, d, P.h_ptr[k], ne_x, G);
       // ... the control rows of G (Gux, Guu) = W_u' F and H's control part on the second
-      on_b();
+      h->stream = sB;
       if (mm > 0 && (e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM, !ovl)))
         return e;
-      add_h(P.h_mid[k], ne_u);
+      st_add_h(h, d, P.h_mid[k], ne_u, G);
     }
-    on_b();
+    h->stream = sB;
     // carried rows: N_k[e..] = B+ F
     if (P.cap[k + 1] > 0 &&
         (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, P.ldf[k], nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k],
                                       P.cap[k + 1], nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, !ovl)))
       return e;
-    stg::SmallArgs sa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
-                      P.capn[k], P.cap[k], P.qmax[k], h->ge_tol, sp.Kinv, P.ldq[k], sp.Kmat, sp.T, P.ldt[k], sp.dyn, h->td.flags.p,
-                      P.big[k] ? d.misc.p + P.oScr : nullptr};
-    if (P.big[k]) {
-      if ((e = st_small_big(h, d, sa, !ovl))) return e;
-    } else if (P.qmax[k] > 64) {
-      static const bool spd_test_fail = getenv("HQPKKT_SPD_TEST_FAIL") != nullptr;
-      if (spd_test_fail) sa.mode = 100;
-      KLAUNCH(h, KC_ST_SMALL, (stg::k_st_small<1024, false><<<1, 1024, d.lds_small, h->stream>>>(sa)));
-    }
-    else
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<256><<<1, 256, d.lds_small, h->stream>>>(sa));
-    stg::WideArgs wa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], P.capn[k], P.cap[k], P.qmax[k], sp.T, P.ldt[k], sp.dyn,
-                     sp.Y, P.ldy[k], sp.BT, P.ldb[k]};
-    if ((e = st_rm(h, d, sp, k, !ovl, wa))) return e;
-    on_a();
+    if ((e = st_eliminate(h, d, k, sp, sn, G, !ovl))) return e;
+    h->stream = sA;
     if (ovl) {
       HIPCHK(hipEventRecord(d.ev_join, sB));
       HIPCHK(hipStreamWaitEvent(sA, d.ev_join, 0));
@@ -1087,24 +1067,20 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     else if (P.big0) {
       // the inverse by the blocked sweep on the whole chip, checked against K0; the LU factorisation by one workgroup
       // behind it runs only where the sweep gave up (decided on the device)
-      const bool legacy0 = false;
-      static const double tol0 = getenv("HQPKKT_BLOCK_GJ_TOL") ? atof(getenv("HQPKKT_BLOCK_GJ_TOL")) : 1e-6;
       double *scr = d.misc.p + P.oScr;
       const int q = P.q0max;
-      if (!legacy0) {
-        const stg::X0Args xa{P.nk[0], q, s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn, d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s,
-                             P.ldq0, scr, h->td.flags.p};
-        KLAUNCH(h, KC_ST_SMALL, stg::k_x0_prepare<<<nblk((long long)q * q), 256, 0, s>>>(xa));
-        if ((e = st_blk_sweep(h, scr, q, true))) return e;
-        KLAUNCH(h, KC_ST_SMALL, stg::k_x0_final<<<nblk((long long)q * q), 256, 0, s>>>(xa));
-        const stg::BigScratch bs = stg::big_scratch(scr, q);
-        if ((e = st_gemm(h, stg::GemmArgs{xa.K0mat, P.ldq0, xa.K0inv, P.ldq0, nullptr, 0, bs.Ks, bs.ldk, q, q, q, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, true)))
-          return e;
-        KLAUNCH(h, KC_ST_SMALL, stg::k_x0_check<<<1, 1024, 0, s>>>(xa, tol0));
-      }
+      const stg::X0Args xa{P.nk[0], q, s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn, d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s,
+                           P.ldq0, scr, h->td.flags.p};
+      KLAUNCH(h, KC_ST_SMALL, stg::k_x0_prepare<<<nblk((long long)q * q), 256, 0, s>>>(xa));
+      if ((e = st_blk_sweep(h, scr, q, true))) return e;
+      KLAUNCH(h, KC_ST_SMALL, stg::k_x0_final<<<nblk((long long)q * q), 256, 0, s>>>(xa));
+      const stg::BigScratch bs = stg::big_scratch(scr, q);
+      if ((e = st_gemm(h, stg::GemmArgs{xa.K0mat, P.ldq0, xa.K0inv, P.ldq0, nullptr, 0, bs.Ks, bs.ldk, q, q, q, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, true)))
+        return e;
+      KLAUNCH(h, KC_ST_SMALL, stg::k_x0_check<<<1, 1024, 0, s>>>(xa, env_block_gj_tol()));
       KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<1024><<<1, 1024, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
                                                                                     d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p,
-                                                                                    scr, legacy0 ? nullptr : stg::big_scratch(scr, q).flags));
+                                                                                    scr, bs.flags));
     } else
       KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<256><<<1, 256, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
                                                                                   d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p, nullptr, nullptr));
@@ -1114,93 +1090,90 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   return 0;
 }
 
-// The same sweeps when ONE system is sharded over several ranks (staged_plan.hpp): the products with V_k run on the
+// Hqp_IpLQDOCP::step (hqp/Hqp_IpLQDOCP.C:869-976) with ExRiccatiSolveSc (:2007-2182).
+// When ONE system is sharded over several ranks (staged_plan.hpp) the products with V_k run on the
 // rank's ROW strip, those with F_k on its COLUMN strip (and the control columns); everything control-sized is computed
 // by every rank.  Per stage one gather of a state-sized vector in the backward sweep (tt = v+ + V+ f, by rows) and one
 // of the ranks' partial sums in the forward sweep (x+ = F s + f, by columns); the multipliers of the dynamics rows
 // (V+ x+ + v+ + B+' eta+, by rows) are summed over the ranks once, at the end.  Not captured: the exchanges are calls.
-static int staged_run_step_sharded(hqpkkt_t *h, const Vecs &v) {
+static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   Analysis &an = h->an;
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   hipStream_t s = h->stream;
+  const bool sh = P.sharded;
   const int n = an.n, m = an.m, K = P.K, NR = P.shard_count, RK = P.shard_rank;
   double *M = d.misc.p;
-  double *S = M + P.oS, *qv = M + P.oQv, *gam = M + P.oGam, *tt = M + P.oTT, *xv = M + P.oXV, *xp = M + P.oXP, *dyx = M + P.oDyx;
-  auto cut0 = [&](int k) { return P.xcut[(size_t)k * (NR + 1) + RK]; };
-  auto width = [&](int k) { return P.xcut[(size_t)k * (NR + 1) + RK + 1] - P.xcut[(size_t)k * (NR + 1) + RK]; };
+  double *S = M + P.oS, *qv = M + P.oQv, *gam = M + P.oGam, *tt = M + P.oTT, *tmp = M + P.oTmp, *gv = M + P.oGv;
+  double *xv = M + P.oXV, *xp = M + P.oXP, *dyx = M + P.oDyx;  // (sharded)
+  auto cut0 = [&](int k) { return sh ? P.xcut[(size_t)k * (NR + 1) + RK] : 0; };
+  auto width = [&](int k) { return sh ? P.xcut[(size_t)k * (NR + 1) + RK + 1] - P.xcut[(size_t)k * (NR + 1) + RK] : 0; };
   int e;
   const long long ndx = (long long)P.ndyn + (P.fixed_x0 ? P.nk[0] : 0);
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_zero<<<nblk(std::max<long long>(ndx, 1)), 256, 0, s>>>(ndx, dyx));
+  if (sh) KLAUNCH(h, KC_ST_VEC, stg::k_st_zero<<<nblk(std::max<long long>(ndx, 1)), 256, 0, s>>>(ndx, dyx));
   if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
   KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->td.CT.ptr.p, h->td.CT.col.p, h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv));
-  {  // last stage
+  // One GPU: the products with V are not part of the sweeps' chains: V+ f (f: the dynamics' right-hand side) is known before the
+  // backward sweep starts, the dynamics rows' multipliers are wanted by nobody before the forward sweep is over - both
+  // for many stages per launch (staged_symv_group), which leaves the F products and the control-sized kernels in the
+  // chains.
+  // (on a stream of their own beside the chains - lowest priority, or a few workgroups that take the tiles in a stride -
+  // the launches gained nothing: 35.8 - 37.4 ms per solve against 35.5; what the chains leave idle of HBM they lose again
+  // when they share it)
+  if (!sh) {
+    for (int gi = (int)d.symv_groups[0].size() - 1; gi >= 0; gi--)
+      if ((e = staged_symv_group(h, d, 0, gi, v.r2, nullptr))) return e;
+    if ((e = staged_symv_rows(h, d, 0, v.r2, nullptr))) return e;
+  }
+  {  // last stage: v_K, and (one GPU) tt = v_K + V_K f_{K-1} for the stage before
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v));
+    if (!sh && K > 0)
+      KLAUNCH(h, KC_ST_VEC, stg::k_st_copy_add<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v, gv + P.nks[K - 1], tt));
+    else
+      KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v));
     if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_gather<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], v.r2, sp.beta));
   }
   for (int k = K - 1; k >= 0; k--) {
     StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
     const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1];
     const int c0 = cut0(k), wd = width(k), c0n = cut0(k + 1), wdn = width(k + 1);
-    const double *f = v.r2 + P.nks[k];
-    // tt = v+ + V+ f by rows: the ranks' strips side by side (strip p starts at p xw), gathered
-    if (wdn > 0 && (e = st_gemv_rows(h, stg::GemvRows{sn.Vs, P.ldv[k + 1], wdn, np, f, sn.v + c0n, nullptr, 0, nullptr, nullptr,
-                                                        xv + (long long)RK * P.xw[k + 1], 1.0})))
+    if (sh) {
+      // tt = v+ + V+ f by rows: the ranks' strips side by side (strip p starts at p xw), gathered
+      if (wdn > 0 && (e = st_gemv_rows(h, stg::GemvRows{sn.Vs, P.ldv[k + 1], wdn, np, v.r2 + P.nks[k], sn.v + c0n, nullptr, 0, nullptr, nullptr,
+                                                          xv + (long long)RK * P.xw[k + 1], 1.0})))
+        return e;
+      if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xv, P.xw[k + 1], NR, nullptr))) return e;
+      // gam = q_k + F' tt: the own state columns and the control columns
+      if (wd > 0 && (e = st_gemv_cols(h, d, sp.F, P.ldfl[k], np, wd, xv, qv + P.nmk[k] + c0, 1.0, gam + c0))) return e;
+      if (mm > 0 && (e = st_gemv_cols(h, d, sp.F + wd, P.ldfl[k], np, mm, xv, qv + P.nmk[k] + nn, 1.0, gam + nn))) return e;
+    } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
-    if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xv, P.xw[k + 1], NR, nullptr))) return e;
-    // gam = q_k + F' tt: the own state columns and the control columns
-    if (wd > 0 && (e = st_gemv_cols(h, d, sp.F, P.ldfl[k], np, wd, xv, qv + P.nmk[k] + c0, 1.0, gam + c0))) return e;
-    if (mm > 0 && (e = st_gemv_cols(h, d, sp.F + wd, P.ldfl[k], np, mm, xv, qv + P.nmk[k] + nn, 1.0, gam + nn))) return e;
-    stg::BwdSmall ba{nn, mm, np, P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], d.eq_rows.p + P.eq_ptr[k], v.r2,
-                     P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr, sn.beta, sn.BT, P.ldb[k + 1], f, gam, sp.Kinv, sp.Kmat, P.ldq[k], sp.T, P.ldt[k],
-                     sp.dyn, sp.rho, sp.beta};
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_bwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 3 * P.qmax[k] + 4 + 256), s>>>(ba));
-    // v_k = gam_x - Y' rho: the own entries (all a later product needs)
-    if (wd > 0 && (e = st_gemv_cols(h, d, sp.Y + c0, P.ldy[k], P.qmax[k], wd, sp.rho, gam + c0, -1.0, sp.v + c0))) return e;
+    st_bwd_small(h, d, k, sp, sn, v.r2, gam);
+    // v_k = gam_x - Y' rho: sharded the own entries (all a later product needs); one GPU with tt = v_k + V_k f_{k-1} for the next stage of the sweep
+    if (sh ? wd > 0 && (e = st_gemv_cols(h, d, sp.Y + c0, P.ldy[k], P.qmax[k], wd, sp.rho, gam + c0, -1.0, sp.v + c0))
+           : (e = st_gemv_cols(h, d, sp.Y, P.ldy[k], P.qmax[k], nn, sp.rho, gam, -1.0, sp.v, k > 0 ? gv + P.nks[k - 1] : nullptr, k > 0 ? tt : nullptr)))
+      return e;
   }
-  {
+  if (sh && !P.fixed_x0) {  // the free initial state needs v_0 in full: gathered
     StagePtr s0 = stage_ptr(d, 0);
-    const int n0 = P.nk[0];
-    if (P.fixed_x0)
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, v.r2, S,
-                                                                                         s0.eta, P.cap[0]));
-    else {
-      // the free initial state needs v_0 in full: gathered
-      const int c0 = cut0(0), wd = width(0);
-      if (wd > 0) KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(wd), 256, 0, s>>>(wd, s0.v + c0, xv + (long long)RK * P.xw[0]));
-      if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xv, P.xw[0], NR, nullptr))) return e;
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(n0), 256, 0, s>>>(n0, xv, s0.v));
-      if (P.big0) {
-        const int q = P.q0max, l8 = (q + 7) / 8 * 8;
-        double *vec = M + P.oK0s + 3 * (long long)q + 8, *nb = vec, *pb = vec + l8, *y = vec + 2 * l8, *r = vec + 3 * l8;
-        const stg::X0Vec xv0{n0, P.cap[0], q, s0.dyn, M + P.oK0s, s0.v, s0.beta, nb, pb, pb, S, s0.eta};
-        KLAUNCH(h, KC_ST_VEC, stg::k_x0_rhs<<<nblk(q), 256, 0, s>>>(xv0));
-        if ((e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, nb, nullptr, nullptr, 0, nullptr, nullptr, y, 1.0})) ||
-            (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0m, P.ldq0, q, q, y, pb, nullptr, 0, nullptr, nullptr, r, -1.0})) ||
-            (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, r, y, nullptr, 0, nullptr, nullptr, pb, 1.0})))
-          return e;
-        KLAUNCH(h, KC_ST_VEC, stg::k_x0_out<<<nblk(n0 + P.cap[0]), 256, 0, s>>>(xv0));
-      }
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_x0_free<<<1, 256, d.lds_x0, s>>>(n0, P.cap[0], P.q0max, M + P.oK0, M + P.oK0m, M + P.oK0s, P.ldq0, s0.dyn, s0.v,
-                                                                s0.beta, S, s0.eta));
-    }
+    const int n0 = P.nk[0], c0 = cut0(0), wd = width(0);
+    if (wd > 0) KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(wd), 256, 0, s>>>(wd, s0.v + c0, xv + (long long)RK * P.xw[0]));
+    if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xv, P.xw[0], NR, nullptr))) return e;
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(n0), 256, 0, s>>>(n0, xv, s0.v));
   }
+  if ((e = st_initial_state(h, d, v.r2))) return e;
   for (int k = 0; k < K; k++) {
     StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
     const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1];
     const int c0 = cut0(k), wd = width(k), c0n = cut0(k + 1), wdn = width(k + 1);
     double *xk = S + P.nmk[k];
-    // [u ; yhat] = -(Rm x + rho)
-    double *uy = M + P.oUy;
-    if (P.qmax[k] > 0) {
-      stg::GemvRows gr{sp.Rm, P.ldy[k], P.qmax[k], nn, xk, sp.rho, nullptr, 0, nullptr, nullptr, uy, -1.0};
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_wide<<<P.qmax[k], 256, 0, s>>>(gr));
+    st_fwd_small(h, d, k, sp, sn, v.dy);
+    if (!sh) {  // x+ = F s + f (the multipliers p = V+ x+ + v+ + B+' eta+ behind the sweep)
+      if ((e = st_gemv_rows(h, stg::GemvRows{sp.F, P.ldf[k], np, nn + mm, xk, v.r2 + P.nks[k], nullptr, 0, nullptr, nullptr, S + P.nmk[k + 1], 1.0})))
+        return e;
+      continue;
     }
-    stg::FwdSmall fa{nn, mm, P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], uy, sp.T, P.ldt[k],
-                     sp.dyn, sp.eta, d.eq_rows.p + P.eq_ptr[k], xk + nn, v.dy, sn.eta, P.cap[k + 1]};
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_fwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 4), s>>>(fa));
     // x+ = F s + f: the own columns' share of every row, gathered, and added in the order of the ranks to f_u u + f
     if ((e = st_gemv_rows(h, stg::GemvRows{sp.F, P.ldfl[k], np, wd, xk + c0, nullptr, nullptr, 0, nullptr, nullptr, xp + (long long)RK * P.xpslot, 1.0})))
       return e;
@@ -1214,126 +1187,23 @@ static int staged_run_step_sharded(hqpkkt_t *h, const Vecs &v) {
                                            dyx + P.nks[k] + c0n, 1.0})))
       return e;
   }
-  {
-    StagePtr sK = stage_ptr(d, K), s0 = stage_ptr(d, 0);
-    const int eK = P.eq_ptr[K + 1] - P.eq_ptr[K], n0 = P.nk[0];
-    if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_last<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], sK.eta, v.dy));
+  if (!sh) {
+    for (int gi = 0; gi < (int)d.symv_groups[1].size(); gi++)
+      if ((e = staged_symv_group(h, d, 1, gi, nullptr, v.dy))) return e;
+    if ((e = staged_symv_rows(h, d, 1, nullptr, v.dy))) return e;
+  }
+  StagePtr sK = stage_ptr(d, K), s0 = stage_ptr(d, 0);
+  const int eK = P.eq_ptr[K + 1] - P.eq_ptr[K], n0 = P.nk[0];
+  if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_last<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], sK.eta, v.dy));
+  if (sh) {
     if (P.fixed_x0 && width(0) > 0 &&
         (e = st_gemv_rows(h, stg::GemvRows{s0.Vs, P.ldv[0], width(0), n0, S, s0.v + cut0(0), nullptr, 0, nullptr, nullptr, dyx + P.ndyn + cut0(0), 1.0})))
       return e;
     if (ndx > 0 && (e = exchange(h, HQPKKT_XCHG_ALLREDUCE_SUM, dyx, ndx, 1, nullptr))) return e;
     if (P.ndyn > 0) KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(P.ndyn), 256, 0, s>>>(P.ndyn, dyx, v.dy));
-    if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, dyx + P.ndyn, v.dy));
-  }
-  KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
-  if (m > 0)
-    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p,
-                                                             v.r3, v.dz, v.dw));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// Hqp_IpLQDOCP::step (hqp/Hqp_IpLQDOCP.C:869-976) with ExRiccatiSolveSc (:2007-2182)
-static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
-  if (h->sd->plan.sharded) return staged_run_step_sharded(h, v);
-  Analysis &an = h->an;
-  StagedDev &d = *h->sd;
-  kktdev::StagedPlan &P = d.plan;
-  hipStream_t s = h->stream;
-  const int n = an.n, m = an.m, K = P.K;
-  double *M = d.misc.p;
-  double *S = M + P.oS, *qv = M + P.oQv, *gam = M + P.oGam, *tt = M + P.oTT, *tmp = M + P.oTmp;
-  int e;
-  if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
-  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->td.CT.ptr.p, h->td.CT.col.p, h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv));
-  // The products with V are not part of the sweeps' chains: V+ f (f: the dynamics' right-hand side) is known before the
-  // backward sweep starts, the dynamics rows' multipliers are wanted by nobody before the forward sweep is over - both
-  // for many stages per launch (staged_symv_group), which leaves the F products and the control-sized kernels in the
-  // chains.
-  double *gv = M + P.oGv;
-  // (on a stream of their own beside the chains - lowest priority, or a few workgroups that take the tiles in a stride -
-  // the launches gained nothing: 35.8 - 37.4 ms per solve against 35.5; what the chains leave idle of HBM they lose again
-  // when they share it)
-  for (int gi = (int)d.symv_groups[0].size() - 1; gi >= 0; gi--)
-    if ((e = staged_symv_group(h, d, 0, gi, v.r2, nullptr))) return e;
-  if ((e = staged_symv_rows(h, d, 0, v.r2, nullptr))) return e;
-  {  // last stage: v_K, and tt = v_K + V_K f_{K-1} for the stage before
-    StagePtr sp = stage_ptr(d, K);
-    const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
-    if (K > 0)
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_copy_add<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v, gv + P.nks[K - 1], tt));
-    else
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v));
-    if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_gather<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], v.r2, sp.beta));
-  }
-  for (int k = K - 1; k >= 0; k--) {
-    StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
-    const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
-    const double *f = v.r2 + P.nks[k];
-    // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
-    if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nz, tt, qv + P.nmk[k], 1.0, gam))) return e;
-    stg::BwdSmall ba{nn, mm, np, P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], d.eq_rows.p + P.eq_ptr[k], v.r2,
-                     P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr, sn.beta, sn.BT, P.ldb[k + 1], f, gam, sp.Kinv, sp.Kmat, P.ldq[k], sp.T, P.ldt[k],
-                     sp.dyn, sp.rho, sp.beta};
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_bwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 3 * P.qmax[k] + 4 + 256), s>>>(ba));
-    // v_k = gam_x - Y' rho (and tt = v_k + V_k f_{k-1} for the next stage of the sweep)
-    if ((e = st_gemv_cols(h, d, sp.Y, P.ldy[k], P.qmax[k], nn, sp.rho, gam, -1.0, sp.v, k > 0 ? gv + P.nks[k - 1] : nullptr, k > 0 ? tt : nullptr)))
-      return e;
-  }
-  {
-    StagePtr s0 = stage_ptr(d, 0);
-    const int n0 = P.nk[0];
-    if (P.fixed_x0)
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, v.r2, S,
-                                                                                         s0.eta, P.cap[0]));
-    else {
-      if (P.big0) {
-        // with the inverse of the blocked sweep (K0s[3 q]: which form the area holds; decided on the device): three
-        // products over the whole chip; k_st_x0_free behind them works only where the factors are in use
-        const int q = P.q0max, l8 = (q + 7) / 8 * 8;
-        double *vec = M + P.oK0s + 3 * (long long)q + 8, *nb = vec, *pb = vec + l8, *y = vec + 2 * l8, *r = vec + 3 * l8;
-        const stg::X0Vec xv{n0, P.cap[0], q, s0.dyn, M + P.oK0s, s0.v, s0.beta, nb, pb, pb, S, s0.eta};
-        KLAUNCH(h, KC_ST_VEC, stg::k_x0_rhs<<<nblk(q), 256, 0, s>>>(xv));
-        if ((e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, nb, nullptr, nullptr, 0, nullptr, nullptr, y, 1.0})) ||
-            (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0m, P.ldq0, q, q, y, pb, nullptr, 0, nullptr, nullptr, r, -1.0})) ||
-            (e = st_gemv_rows(h, stg::GemvRows{M + P.oK0, P.ldq0, q, q, r, y, nullptr, 0, nullptr, nullptr, pb, 1.0})))
-          return e;
-        KLAUNCH(h, KC_ST_VEC, stg::k_x0_out<<<nblk(n0 + P.cap[0]), 256, 0, s>>>(xv));
-      }
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_x0_free<<<1, 256, d.lds_x0, s>>>(n0, P.cap[0], P.q0max, M + P.oK0, M + P.oK0m, M + P.oK0s, P.ldq0, s0.dyn, s0.v,
-                                                                s0.beta, S, s0.eta));
-    }
-  }
-  for (int k = 0; k < K; k++) {
-    StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
-    const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
-    double *xk = S + P.nmk[k];
-    // [u ; yhat] = -(Rm x + rho)
-    double *uy = M + P.oUy;
-    if (P.qmax[k] > 0) {
-      stg::GemvRows gr{sp.Rm, P.ldy[k], P.qmax[k], nn, xk, sp.rho, nullptr, 0, nullptr, nullptr, uy, -1.0};
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_wide<<<P.qmax[k], 256, 0, s>>>(gr));
-    }
-    stg::FwdSmall fa{nn, mm, P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], uy, sp.T, P.ldt[k],
-                     sp.dyn, sp.eta, d.eq_rows.p + P.eq_ptr[k], xk + nn, v.dy, sn.eta, P.cap[k + 1]};
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_fwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 4), s>>>(fa));
-    // x+ = F s + f (the multipliers p = V+ x+ + v+ + B+' eta+ behind the sweep)
-    if ((e = st_gemv_rows(h, stg::GemvRows{sp.F, P.ldf[k], np, nz, xk, v.r2 + P.nks[k], nullptr, 0, nullptr, nullptr, S + P.nmk[k + 1], 1.0})))
-      return e;
-  }
-  for (int gi = 0; gi < (int)d.symv_groups[1].size(); gi++)
-    if ((e = staged_symv_group(h, d, 1, gi, nullptr, v.dy))) return e;
-  if ((e = staged_symv_rows(h, d, 1, nullptr, v.dy))) return e;
-  {
-    StagePtr sK = stage_ptr(d, K), s0 = stage_ptr(d, 0);
-    const int eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
-    if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_last<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], sK.eta, v.dy));
-    if (P.fixed_x0) {
-      const int n0 = P.nk[0];
-      if ((e = st_symv(h, d, stg::GemvRows{s0.V, P.ldv[0], n0, n0, S, s0.v, nullptr, 0, nullptr, nullptr, tmp, 1.0}))) return e;
-      KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, tmp, v.dy));
-    }
-  }
+  } else if (P.fixed_x0 && (e = st_symv(h, d, stg::GemvRows{s0.V, P.ldv[0], n0, n0, S, s0.v, nullptr, 0, nullptr, nullptr, tmp, 1.0})))
+    return e;
+  if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, sh ? dyx + P.ndyn : tmp, v.dy));
   KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
   if (m > 0)
     KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p,

@@ -698,6 +698,26 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
   return 0;
 }
 
+// The exchange steps of a sharded system: the handle's stream is
+// drained, the caller's collective runs, and the next phase starts afterwards.
+int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on) {
+  // (profiled as the class "exchange": in the stream-ordered form the time between the collective's place in
+  // the stream and its completion - the wait for the slowest rank and the transfer)
+  if (h->xchg_sfn) {  // the collective is put into the handle's stream (or `on`) behind the kernels that fill `buf`
+    hipStream_t st = on ? on : h->stream;
+    h->prof.begin(KC_XCHG, st);
+    const int rc = h->xchg_sfn(h->xchg_ctx, op, buf, slot, nslots, (void *)st);
+    h->prof.end(st);
+    return rc ? HQPKKT_E_DEVICE : 0;
+  }
+  if (!h->xchg_fn) return HQPKKT_E_INTERN;
+  h->prof.begin(KC_XCHG, h->stream);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int rc = h->xchg_fn(h->xchg_ctx, op, buf, slot, nslots);
+  h->prof.end(h->stream);
+  return rc ? HQPKKT_E_DEVICE : 0;
+}
+
 int do_factor(hqpkkt_t *h, const Vecs &v) {
   Analysis &an = h->an;
   int e;

@@ -438,6 +438,19 @@ def sk_table(tiles, nslab, grid=512):
     return u, pieces.value, wa.value, wb.value
 
 
+GEMM_FORMS = ("frac", "cut", "plain", "ks", "6432", "6464")
+
+
+def gemm_form(M, N, K, lower=False, mirror=False, cus=256, grid=512, sk_tiles=1 << 30, ws_elems=1 << 40, ws2_elems=8 << 20,
+              sharded=False, first_stream=True, no_ks=False, no_tile_map=False, force_split=False):
+    """The launch rule of the STAGED engine's fp64 product (host only): (form or None, tiles, table wanted, tile order wanted, pieces of k)."""
+    flags = sharded * 1 | (not first_stream) * 2 | no_ks * 8 | no_tile_map * 16 | force_split * 32
+    tiles, table, tmap, nsplit = C.c_longlong(), C.c_int(), C.c_int(), C.c_int()
+    kind = _lib.lib().hqpkkt_debug_gemm_form(M, N, K, int(lower), int(mirror), cus, grid, sk_tiles, ws_elems, ws2_elems, flags,
+                                             C.byref(tiles), C.byref(table), C.byref(tmap), C.byref(nsplit))
+    return (GEMM_FORMS[kind] if kind >= 0 else None), tiles.value, bool(table.value), bool(tmap.value), nsplit.value
+
+
 def selftest_mfma(device=0):
     err = C.c_double()
     _check(_lib.lib().hqpkkt_selftest_mfma(device, C.byref(err)), "selftest_mfma")

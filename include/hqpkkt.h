@@ -356,6 +356,17 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
  * *pieces: parking slots; *whole_a / *whole_b: whole tiles per workgroup of the first / second half of the launch. */
 int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b);
 
+/* Test hook, host only: the form the STAGED engine's launch rule (gemm_form.hpp) gives an M x N x K product on a device
+ * of `cus` CUs with a split grid of `grid` workgroups (0: none), arrival counters for sk_tiles tiles and workspaces of
+ * ws_elems / ws2_elems doubles (first / second stream).  flags: 1 one system over several ranks, 2 a launch of the
+ * second stream, 8 never the product cut in k, 16 never a tile order, 32 the cut form forced (8, 16, 32: what
+ * hqpkkt_debug_dgemm sets).  Returns -1 (nothing to launch / lower with M < N), 0 fractional
+ * cut, 1 planned or table cut, 2 plain 128 x 128 round, 3 thin-deep cut in k, 4 64 x 32 tiles, 5 64 x 64 tiles;
+ * *tiles: tiles of the launch; *table / *tile_map: a work table / a tile order of the triangle is wanted; *nsplit: pieces
+ * of the k range of the thin-deep form (1 otherwise). */
+int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,
+                           long long ws2_elems, int flags, long long *tiles, int *table, int *tile_map, int *nsplit);
+
 /* Per-kernel-class device timing for bench.py's roofline line: with on != 0
  * every kernel launch is bracketed by HIP events on the handle's stream and the
  * elapsed times are summed per class (hqpkkt_profile_class_name(c), c = 0..) at

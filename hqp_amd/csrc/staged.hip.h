@@ -83,7 +83,20 @@ struct GemmArgs {
   unsigned long long *stamps;  // diagnostic builds of the plain kernel only (hqpkkt_debug_dgemm): 4 constant-clock
                                // (100 MHz) time stamps per workgroup: start, operands of the first slab in LDS, end of
                                // the k loop, end of the epilogue; null in every product of the engine
+  // A second k segment (the 128 x 128 LDS-DMA kernels only): C = alpha (A'B + A2'B2) + beta Cin, with the slabs of
+  // A2 / B2 (K2 x M / K2 x N) behind the zero-padded slabs of the first pair in the same accumulators - a launch has
+  // gemm_slabs(K) + gemm_slabs(K2) slabs, and a cut piece's range may span the boundary.  V_k = F_x'W_x - Y'Rm of a
+  // stage comes out of one launch this way, with B2 = -Rm (k_st_rm writes it beside Rm, so the difference is exact)
+  const double *A2;
+  long long lda2;
+  const double *B2;
+  long long ldb2;
+  int K2;
 };
+// k-slabs of a launch (both segments)
+static __host__ __device__ __forceinline__ int gemm_slabs_of(const GemmArgs &g) {
+  return (g.K + GEMM_BK - 1) / GEMM_BK + (g.K2 > 0 ? (g.K2 + GEMM_BK - 1) / GEMM_BK : 0);
+}
 
 static inline size_t gemm_lds_bytes(int bm, int bn, int nbuf = 2) { return sizeof(double) * nbuf * GEMM_BK * (size_t)(bm + 16 + bn + 16); }
 
@@ -266,8 +279,18 @@ struct GemmTile {
   // loop, the others a copy of it with a (wave-uniform, scalar) test in front of every MFMA.  The operands are staged
   // and the barriers kept as always; what is saved is the matrix pipe's time, which the partner workgroup of the CU
   // gets (3.8 % of W's and 5.3 % of G's multiplications at the C4 shapes).
+  // The k-rows of one operand of a launch: rows [0, K) from the first segment (leading dimension ld), rows [k0, k1) -
+  // k0 = the first segment's slabs x BK - from the second (GemmArgs::K2; row k at offset o2 + k ld2 from the first's
+  // origin), every other row from the zero row.  Without a second segment k0 = k1.
+  struct Rows {
+    int K, k0, k1;
+    long long ld, o2, ld2;
+  };
+  static __device__ __forceinline__ const double *row_of(const Rows &r, const double *p, const double *zr, int k) {
+    return k < r.K ? p + (long long)k * r.ld : (k >= r.k0 && k < r.k1) ? p + (r.o2 + (long long)k * r.ld2) : zr;
+  }
   template <bool MASKED>
-  static __device__ __forceinline__ void slabs_dma(const GemmArgs &g, const double *pa, const double *pb, const double *zr, int wave,
+  static __device__ __forceinline__ void slabs_dma(const Rows &ra, const Rows &rb, const double *pa, const double *pb, const double *zr, int wave,
                                                    int wm, int wn, int lr, int lk, int s0, int s1, unsigned mask,
                                                    double4_t (&acc)[TM][TN], double *As, double *Bs) {
     constexpr int RPW = BK / NW;  // rows of each panel per wave and slab
@@ -275,9 +298,9 @@ struct GemmTile {
     auto dma = [&](int buf, int k0, int p) {
       const int r = wave + NW * (p % RPW), k = k0 + r;
       if (p < RPW)
-        glds16(k < g.K ? pa + (long long)k * g.lda : zr, As + (buf * BK + r) * LDA);
+        glds16(row_of(ra, pa, zr, k), As + (buf * BK + r) * LDA);
       else
-        glds16(k < g.K ? pb + (long long)k * g.ldb : zr, Bs + (buf * BK + r) * LDB);
+        glds16(row_of(rb, pb, zr, k), Bs + (buf * BK + r) * LDB);
     };
     if (s1 > s0) {
 #pragma unroll
@@ -289,7 +312,7 @@ struct GemmTile {
     // 90.8 -> 88.3 % of peak)
     for (int s = s0; s < s1; s++) {
       const int buf = (s - s0) & 1;
-      const int knext = s + 1 < s1 ? (s + 1) * BK : g.K;  // behind the last slab: zero rows
+      const int knext = s + 1 < s1 ? (s + 1) * BK : ra.k1;  // behind the last slab: zero rows
       const double *Ab = As + buf * BK * LDA + wm * WM + lr;
       const double *Bb = Bs + buf * BK * LDB + wn * WN + lr;
 #pragma unroll
@@ -316,7 +339,7 @@ struct GemmTile {
   // 1.7 us a slab takes a workgroup that has the CU to itself.  Counted wait: vmcnt(2 RPW) leaves the newest slab's
   // pieces in flight across the barrier (raw s_barrier: __syncthreads() would drain them).  As / Bs: 3 BK rows each.
   template <bool MASKED>
-  static __device__ __forceinline__ void slabs_dma3(const GemmArgs &g, const double *pa, const double *pb, const double *zr, int wave,
+  static __device__ __forceinline__ void slabs_dma3(const Rows &ra, const Rows &rb, const double *pa, const double *pb, const double *zr, int wave,
                                                     int wm, int wn, int lr, int lk, int s0, int s1, unsigned mask,
                                                     double4_t (&acc)[TM][TN], double *As, double *Bs) {
     constexpr int RPW = BK / NW;
@@ -324,9 +347,9 @@ struct GemmTile {
     auto dma = [&](int buf, int k0, int p) {
       const int r = wave + NW * (p % RPW), k = k0 + r;
       if (p < RPW)
-        glds16(k < g.K ? pa + (long long)k * g.lda : zr, As + (buf * BK + r) * LDA);
+        glds16(row_of(ra, pa, zr, k), As + (buf * BK + r) * LDA);
       else
-        glds16(k < g.K ? pb + (long long)k * g.ldb : zr, Bs + (buf * BK + r) * LDB);
+        glds16(row_of(rb, pb, zr, k), Bs + (buf * BK + r) * LDB);
     };
     auto wait_all_but_newest_slab = [&]() {
       if constexpr (2 * RPW == 4)
@@ -336,15 +359,15 @@ struct GemmTile {
     };
     // slabs s0 and s0 + 1 (zero rows where the range is shorter) -> buffers 0 and 1
 #pragma unroll
-    for (int p = 0; p < 2 * RPW; p++) dma(0, s1 > s0 ? s0 * BK : g.K, p);
+    for (int p = 0; p < 2 * RPW; p++) dma(0, s1 > s0 ? s0 * BK : ra.k1, p);
 #pragma unroll
-    for (int p = 0; p < 2 * RPW; p++) dma(1, s0 + 1 < s1 ? (s0 + 1) * BK : g.K, p);
+    for (int p = 0; p < 2 * RPW; p++) dma(1, s0 + 1 < s1 ? (s0 + 1) * BK : ra.k1, p);
     wait_all_but_newest_slab();
     constexpr int GAP = TM * TN / (2 * RPW);
     int buf = 0;
     for (int s = s0; s < s1; s++) {
       const int bnext = buf >= 1 ? buf - 1 : 2;  // (buf + 2) % 3
-      const int knext = s + 2 < s1 ? (s + 2) * BK : g.K;
+      const int knext = s + 2 < s1 ? (s + 2) * BK : ra.k1;
       const double *Ab = As + buf * BK * LDA + wm * WM + lr;
       const double *Bb = Bs + buf * BK * LDB + wn * WN + lr;
 #pragma unroll
@@ -376,16 +399,6 @@ struct GemmTile {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
     const int lr = lane & 15, lk = lane >> 4;
-    // a 16-byte load is inside its row when its first column is < ld (ld even)
-    GemmArgs gl = g;  // (B and its leading dimension: the strip of the tile's columns)
-    int jb = j0;
-    if (g.bstrips) {
-      const int q = strip_of(g.bstrips->cut, g.bstrips->nranks, j0);
-      gl.B = g.B + g.bstrips->off[q], gl.ldb = g.bstrips->ld[q], jb = j0 - g.bstrips->cut[q];
-    }
-    const double *pa = g.A + ((i0 + 2 * lane < g.lda) ? i0 + 2 * lane : 0);
-    const double *pb = gl.B + ((jb + 2 * lane < gl.ldb) ? jb + 2 * lane : 0);
-    const double *zr = g.zeros + 2 * lane;
     unsigned mask = 0;
 #pragma unroll
     for (int x = 0; x < TM; x++)
@@ -397,15 +410,33 @@ struct GemmTile {
       }
     mask = __builtin_amdgcn_readfirstlane(mask);
     const bool all = mask == (TM * TN == 32 ? 0xffffffffu : (1u << (TM * TN)) - 1u);
+    // a 16-byte load is inside its row when its first column is < ld (ld even)
+    const double *B = g.B;
+    long long ldb = g.ldb;  // (B and its leading dimension: the strip of the tile's columns)
+    int jb = j0;
+    if (g.bstrips) {
+      const int q = strip_of(g.bstrips->cut, g.bstrips->nranks, j0);
+      B = g.B + g.bstrips->off[q], ldb = g.bstrips->ld[q], jb = j0 - g.bstrips->cut[q];
+    }
+    const double *pa = g.A + ((i0 + 2 * lane < g.lda) ? i0 + 2 * lane : 0);
+    const double *pb = B + ((jb + 2 * lane < ldb) ? jb + 2 * lane : 0);
+    const double *zr = g.zeros + 2 * lane;
+    // (the second segment's rows are addressed from the first's origin: the same column of the tile in both; not with bstrips)
+    const int k0 = (g.K + BK - 1) / BK * BK, k1 = k0 + (g.K2 > 0 ? g.K2 : 0);
+    Rows ra{g.K, k0, k1, g.lda, 0, 0}, rb{g.K, k0, k1, ldb, 0, 0};
+    if (g.K2 > 0) {
+      ra.ld2 = g.lda2, ra.o2 = (g.A2 - g.A) - (long long)k0 * g.lda2;
+      rb.ld2 = g.ldb2, rb.o2 = (g.B2 - g.B) - (long long)k0 * g.ldb2;
+    }
     if (nbuf == 3) {
       if (all)
-        slabs_dma3<false>(gl, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+        slabs_dma3<false>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
       else
-        slabs_dma3<true>(gl, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+        slabs_dma3<true>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
     } else if (all)
-      slabs_dma<false>(gl, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+      slabs_dma<false>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
     else
-      slabs_dma<true>(gl, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+      slabs_dma<true>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
   }
 
   // `lds`: the workgroup's LDS (free after accumulate's last barrier), used to write the MIRROR image of an
@@ -504,7 +535,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, gemm_waves_per_simd(WGM * WGN,
 #pragma unroll
     for (int y = 0; y < T::TN; y++) acc[x][y] = (double4_t){0.0, 0.0, 0.0, 0.0};
   if constexpr (DMA)
-    T::accumulate_dma(g, tm * BM, tn * BN, 0, (g.K + T::BK - 1) / T::BK, acc, As, Bs, g.lower && tm == tn, NBUF);
+    T::accumulate_dma(g, tm * BM, tn * BN, 0, gemm_slabs_of(g), acc, As, Bs, g.lower && tm == tn, NBUF);
   else
     T::accumulate(g, tm * BM, tn * BN, 0, (g.K + T::BK - 1) / T::BK, acc, As, Bs);
   const unsigned long long t2 = g.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -644,7 +675,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
   double *As = lds, *Bs = lds + NBUF * T::BK * T::LDA;
   unsigned *s_old = (unsigned *)(lds + NBUF * T::BK * (T::LDA + T::LDB));
   const int G = gridDim.x, v = xcd_swizzle(blockIdx.x, G);
-  const int nslab = (g.K + T::BK - 1) / T::BK;
+  const int nslab = DMA ? gemm_slabs_of(g) : (g.K + T::BK - 1) / T::BK;
   constexpr int SLOT = BM * BN;
   unsigned long long *stamp = g.stamps ? g.stamps + 32 * (long long)blockIdx.x : nullptr;  // (diagnostic launches only)
   if (stamp && threadIdx.x == 0) stamp[0] = __builtin_amdgcn_s_memrealtime();
@@ -964,6 +995,24 @@ __global__ void k_st_add_h(int nent, const long long *__restrict__ dst, const in
     G[dst[e]] += s;
   else
     G[dst[e]] = s;
+}
+
+// The state part of H added into V_k where the product's launch has written G_xx - Y'Rm straight into V (lower tiles and
+// their mirror image): the entry on or below the diagonal and its image get the identical value, so V stays exactly
+// symmetric.  dst: offsets in a block of leading dimension ldg (the plan's list); entries above the diagonal have
+// their image in the list and are left to it
+__global__ void k_st_add_h_sym(int nent, const long long *__restrict__ dst, const int *__restrict__ tptr,
+                               const HTerm *__restrict__ terms, const double *__restrict__ vals,
+                               const double *__restrict__ wt, double *__restrict__ V, long long ldg, long long ldv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nent) return;
+  const long long i = dst[e] / ldg, j = dst[e] % ldg;
+  if (i < j) return;
+  double s = 0.0;
+  for (int k = tptr[e]; k < tptr[e + 1]; k++) s += vals[terms[k].s1] * vals[terms[k].s2] * wt[terms[k].wi];
+  const double v = V[i * ldv + j] + s;
+  V[i * ldv + j] = v;
+  if (i != j) V[j * ldv + i] = v;
 }
 
 // The same for a system sharded over ranks: a rank computes only ITS tiles of the work block G (the plan's tile list);
@@ -1899,6 +1948,7 @@ struct RmArgs {
   int q, n;
   int wide;  // 1: Y and the carried rows B_k are formed here too, from w (k_st_wide's work: one launch less)
   WideArgs w;
+  double *nRm;  // not null: -Rm as well (leading dimension ldy): the second B operand of the launch that forms V_k
 };
 static const int RM_COLS = 32;
 // K^-1 and K zero-padded to a multiple of 16 (rows of QP + 1 doubles), three QP x 32 panels
@@ -2010,6 +2060,8 @@ __global__ void __launch_bounds__(256) k_st_rm(RmArgs a) {
         const int jj = blockIdx.x * RM_COLS + lr;
         if (m < q && jj < a.n) out[(long long)m * a.ldy + jj] = acc0[rg];
         if (m < q && jj + 16 < a.n) out[(long long)m * a.ldy + jj + 16] = acc1[rg];
+        if (a.nRm && m < q && jj < a.n) a.nRm[(long long)m * a.ldy + jj] = -acc0[rg];
+        if (a.nRm && m < q && jj + 16 < a.n) a.nRm[(long long)m * a.ldy + jj + 16] = -acc1[rg];
       } else {
         out[m * RM_COLS + lr] = acc0[rg];
         out[m * RM_COLS + 16 + lr] = acc1[rg];

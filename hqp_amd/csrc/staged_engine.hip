@@ -51,7 +51,7 @@ void staged_reset(StagedDev &d) {
   d.plan = std::move(plan);
 }
 
-// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 34); the handle is in HQPKKT_MODE_STAGED and analysed
+// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 35); the handle is in HQPKKT_MODE_STAGED and analysed
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
   if (!h->sd) return HQPKKT_E_INTERN;
   const kktdev::StagedPlan &P = h->sd->plan;
@@ -94,6 +94,10 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
           hipMemcpy(out.data() + 2, stg::big_scratch(h->sd->misc.p + P.oScr, P.q0max).flags + 1, sizeof(int) * 4,
                     hipMemcpyDeviceToHost) != hipSuccess)
         return HQPKKT_E_DEVICE;
+      break;
+    case 35:  // per stage: 1 where V_k comes out of the G_xx launch (staged_stage_fused); decided at the upload
+      out.assign(P.K + 1, 0);
+      for (size_t k = 0; k < h->sd->fused.size() && k < out.size(); k++) out[k] = h->sd->fused[k];
       break;
     default: return HQPKKT_E_RANGE;
   }
@@ -246,6 +250,21 @@ int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap) {
   return 0;
 }
 
+int hqpkkt_debug_stage_block(hqpkkt_t *h, int k, double *out, long long cap, long long *len) {
+  if (!h || !len) return HQPKKT_E_NULL;
+  if (!h->sd || !h->uploaded || h->sd->plan.sharded) return HQPKKT_E_INTERN;
+  const kktdev::StagedPlan &P = h->sd->plan;
+  if (k < 0 || k > P.K) return HQPKKT_E_RANGE;
+  const long long n = P.nk[k];
+  *len = n * n;
+  if (!out) return 0;
+  if (cap < n * n) return HQPKKT_E_SIZES;
+  HIPCHK(hipSetDevice(h->opts.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (n) HIPCHK(hipMemcpy2D(out, sizeof(double) * n, h->sd->V.p + P.oV[k], sizeof(double) * P.ldv[k], sizeof(double) * n, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Micro-benchmark and self-check of the dense fp64 product the STAGED engine is made of
 // (k_dgemm_tn): C = A'B (+ lower / mirror) on pseudo-random operands, `reps` timed launches;
 // *ms = average device time per launch, *max_err = max |C - exact| over 4096 sampled entries
@@ -277,8 +296,24 @@ __global__ void k_gemm_check(stg::GemmArgs g, int nsample, double *err) {
     const double a = g.A[(long long)k * g.lda + i], b = g.B[(long long)k * g.ldb + j];
     s += a * b, sa += fabs(a * b);
   }
+  for (int k = 0; k < g.K2; k++) {  // (the second k segment)
+    const double a = g.A2[(long long)k * g.lda2 + i], b = g.B2[(long long)k * g.ldb2 + j];
+    s += a * b, sa += fabs(a * b);
+  }
   const double e = fabs(g.C[(long long)ci * g.ldc + cj] - g.alpha * s) / (sa + 1e-300);
   atomic_max_pos((unsigned long long *)err, e);
+}
+__global__ void k_negate_into(long long n, const double *__restrict__ x, double *__restrict__ y) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = -x[i];
+}
+// entries of a mirrored result that differ in a bit from their image
+__global__ void k_gemm_count_asym(stg::GemmArgs g, unsigned long long *count) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)g.M * g.N) return;
+  const int i = (int)(e / g.N), j = (int)(e % g.N);
+  if (i <= j || i >= g.N) return;
+  if (__double_as_longlong(g.C[(long long)i * g.ldc + j]) != __double_as_longlong(g.C[(long long)j * g.ldc + i])) atomicAdd(count, 1ULL);
 }
 // HQPKKT_DGEMM_STAMPS: one more launch of the product with time stamps (100 MHz constant clock), printed to stderr
 static void dgemm_stamps_split(const stg::GemmArgs &g, const stg::GemmForm &f, int variant, int skg, const stg::SplitTable &sk_tab, const stg::SkUnit *tab_dev) {
@@ -358,14 +393,17 @@ static void dgemm_stamps_plain(const stg::GemmArgs &g, long long tiles, int vari
   }
 }
 }  // namespace
-int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
-  if (M <= 0 || N <= 0 || K < 0 || reps <= 0) return HQPKKT_E_RANGE;
+// K2 > 0: C = A'B - A2'B2 by a launch with a second k segment (operands A2, -B2); asym: entries of a mirrored result
+// that are not bit-identical to their image
+static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym) {
+  if (M <= 0 || N <= 0 || K < 0 || K2 < 0 || reps <= 0) return HQPKKT_E_RANGE;
   if (lower && M < N) return HQPKKT_E_RANGE;  // (M > N: the column strip of a lower triangle)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
   HIPCHK(hipSetDevice(device));
   const long long lda = (M + 7) / 8 * 8, ldb = (N + 7) / 8 * 8, ldc = ldb;
-  DBuf<double> A, B, Cm, err, zr, skws;
+  DBuf<double> A, B, Cm, err, zr, skws, A2, B2, nB2;
+  DBuf<unsigned long long> nasym;
   DBuf<unsigned> skcnt;
   DBuf<stg::SkUnit> sk_table_dev;
   const size_t kk = K > 0 ? K : 1;
@@ -381,17 +419,26 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
     (void)hipMemset(zr.p, 0, sizeof(double) * 256);
     g.zeros = zr.p;
   }
+  if (K2 > 0) {
+    if (!g.zeros) return HQPKKT_E_RANGE;  // (the LDS-DMA kernels alone)
+    if (A2.alloc((size_t)K2 * lda) || B2.alloc((size_t)K2 * ldb) || nB2.alloc((size_t)K2 * ldb)) return HQPKKT_E_MEM;
+    k_fill_rand<<<nblk((long long)K2 * lda), 256>>>(A2.p, (long long)K2 * lda, 3);
+    k_fill_rand<<<nblk((long long)K2 * ldb), 256>>>(B2.p, (long long)K2 * ldb, 4);
+    k_negate_into<<<nblk((long long)K2 * ldb), 256>>>((long long)K2 * ldb, B2.p, nB2.p);
+    g.A2 = A2.p, g.lda2 = lda, g.B2 = nB2.p, g.ldb2 = ldb, g.K2 = K2;  // (the check sums what the launch was given: A'B + A2'(-B2))
+  }
   // The engine's rule (gemm_form.hpp) with what this entry point has always done differently: no thin product cut in k, no
   // tile order for large triangles, never sharded, and a workspace of its own - 16 parked pieces per tile
   // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   const int skg = stg::gemm_wgs_per_cu(variant) * cus;
-  const long long t128 = stg::gemm_tiles(M, N, 128, lower), nslab = stg::gemm_slabs(K);
+  const long long t128 = stg::gemm_tiles(M, N, 128, lower), nslab = stg::gemm_slabs(K) + (K2 > 0 ? stg::gemm_slabs(K2) : 0);
   const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
-  const stg::GemmForm f = stg::gemm_form(M, N, K, lower, mirror, cus, skg, t128, ws_elems, 0, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP |
+  const stg::GemmForm f = stg::gemm_form(M, N, K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K, lower, mirror, cus, skg, t128, ws_elems, 0, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP |
                                          (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0));
   const bool frac = f.kind == stg::GEMM_FORM_FRAC, use_sk = frac || f.kind == stg::GEMM_FORM_CUT;
+  if (K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
   (void)stg::gemm_set_attributes();
   if (use_sk && (skws.alloc((size_t)ws_elems) || skcnt.alloc(f.tiles + 4))) return HQPKKT_E_MEM;
   // (the cut form by a table with unequal shares for the two workgroups of a CU: gemm_split_table; HQPKKT_SK_TABLE=0: equal shares)
@@ -429,9 +476,23 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
   k_gemm_check<<<16, 256>>>(g, 4096, err.p);
   double he = 0.0;
   if (hipMemcpy(&he, err.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return HQPKKT_E_DEVICE;
+  if (asym) {
+    unsigned long long na = 0;
+    if (nasym.alloc(1)) return HQPKKT_E_MEM;
+    (void)hipMemset(nasym.p, 0, 8);
+    if (lower && mirror) k_gemm_count_asym<<<nblk((long long)M * N), 256>>>(g, nasym.p);
+    if (hipMemcpy(&na, nasym.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return HQPKKT_E_DEVICE;
+    *asym = (long long)na;
+  }
   if (ms) *ms = t / reps;
   if (max_err) *max_err = he;
   return 0;
+}
+int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
+  return debug_dgemm(device, M, N, K, 0, lower, mirror, reps, ms, max_err, nullptr);
+}
+int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym) {
+  return debug_dgemm(device, M, N, K, K2, lower, mirror, reps, ms, max_err, asym);
 }
 
 int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,

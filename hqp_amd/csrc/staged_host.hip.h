@@ -63,6 +63,10 @@ struct StagedDev {
   EventOwner ev_fork, ev_join;
   bool overlap = false;
   int overlap_mode = 0;  // 0 never, 1 every stage, 2 stages of 1280 .. 4096 states
+  // Stages that form V_k in the G_xx launch (GemmArgs::K2), chosen at upload time (staged_stage_fused, HQPKKT_FUSED_V),
+  // and -Rm (k_st_rm) of the stage in work
+  std::vector<char> fused;
+  DBuf<double> fv_nrm;
   // order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map), by T
   std::vector<std::pair<int, DBuf<int>>> tri_maps;
   const int *tri_map(int T, bool create = false) {
@@ -113,9 +117,11 @@ struct StagedDev {
                           (plan.sharded ? stg::GEMM_SHARDED : 0) | (first_stream ? 0 : stg::GEMM_SECOND_STREAM));
   }
   // (the shape of a product as st_gemm launches it on the first stream)
-  void sk_tab_prepare(int M, int N, int K, int lower) {
-    const stg::GemmForm f = gemm_form(M, N, K, lower, 0);
-    if (f.kind == stg::GEMM_FORM_CUT) (void)sk_tab(f.tiles, stg::gemm_slabs(K), true);
+  // (K2: the second k segment of the launch that forms V_k)
+  void sk_tab_prepare(int M, int N, int K, int lower, int K2 = 0) {
+    const long long nslab = stg::gemm_slabs(K) + (K2 > 0 ? stg::gemm_slabs(K2) : 0);
+    const stg::GemmForm f = gemm_form(M, N, K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K, lower, K2 > 0);
+    if (f.kind == stg::GEMM_FORM_CUT) (void)sk_tab(f.tiles, nslab, true);
   }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
   long long sk_ws_elems = 0, sk_cnt_elems = 0;
@@ -128,6 +134,11 @@ namespace {
 bool env_no_symv() { static const bool v = getenv("HQPKKT_NO_SYMV") != nullptr; return v; }  // the rows form of the solve's products with V
 int env_symv_from() { static const int v = getenv("HQPKKT_SYMV_FROM") ? atoi(getenv("HQPKKT_SYMV_FROM")) : 2048; return v; }
 double env_block_gj_tol() { static const double v = getenv("HQPKKT_BLOCK_GJ_TOL") ? atof(getenv("HQPKKT_BLOCK_GJ_TOL")) : 1e-6; return v; }
+// Narrowest stage that forms V_k in the G_xx launch unasked: none.  At 5000 states the sequence takes exactly as long as
+// the one with the separate update (the thin product for the control rows of G, 77 us, and the extra slabs cost what the
+// update, 109 us, saves: profiles/r08_stage_order.txt), and up to 4096 states the chain beside G_xx
+// (StagedDev::overlap_mode) has its measured gain.  HQPKKT_FUSED_V=1 runs it wherever it can
+const int FUSED_V_MIN_STATES = 1 << 30;
 bool env_spd_test_fail() { static const bool v = getenv("HQPKKT_SPD_TEST_FAIL") != nullptr; return v; }  // tests: k_st_small<1024, false> refuses
 // launches go to h->stream: back to the first stream on every way out
 struct StreamGuard {
@@ -165,12 +176,18 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
 int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true, int ntiles = 0) {
   if (g.M <= 0 || g.N <= 0) return 0;
   StagedDev &d = *h->sd;
-  const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, g.K, d.sk_grid, d.sk_tiles) : d.gemm_form(g.M, g.N, g.K, g.lower, g.mirror, allow_sk);
+  // (a launch with a second k segment counts as one of the depth of both: a multiple of the slab)
+  const long long nslab = stg::gemm_slabs(g.K) + (g.K2 > 0 ? stg::gemm_slabs(g.K2) : 0);
+  const int Kf = g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K;
+  const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, Kf, d.sk_grid, d.sk_tiles) : d.gemm_form(g.M, g.N, Kf, g.lower, g.mirror, allow_sk);
   if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_INTERN;
   if (f.tile_map) g.tile_map = d.tri_map((g.M + 127) / 128);
   // operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd
   // column (the control columns F + nn of a stage with an odd number of states) is staged through registers
-  if (d.zeros.p && ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0)) g.zeros = d.zeros.p;
+  if (d.zeros.p && ((((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) == 0) && (((g.lda | g.ldb | g.lda2 | g.ldb2) & 1) == 0))
+    g.zeros = d.zeros.p;
+  // (the second segment exists in the 128 x 128 LDS-DMA kernels alone: StagedDev::fused holds only stages that get them)
+  if (g.K2 > 0 && !(g.zeros && (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT || f.kind == stg::GEMM_FORM_PLAIN))) return HQPKKT_E_INTERN;
   const int variant = ntiles && !g.zeros ? stg::GEMM_REG4 : d.gemm_variant;
   double *ws = allow_sk ? d.sk_ws.p : d.ks_ws2.p;
   switch (f.kind) {
@@ -178,7 +195,6 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
     case stg::GEMM_FORM_CUT: {
       // whole rounds, then the k ranges of the rest cut - by the shape's work table where there is one -, or the k-slabs
       // of all tiles in one sequence (the arrival counters are zero between launches: the last arriver of a tile resets its)
-      const long long nslab = stg::gemm_slabs(g.K);
       const bool frac = f.kind == stg::GEMM_FORM_FRAC;
       stg::SplitPlan sk = frac ? stg::gemm_split_plan_frac(f.tiles, nslab, d.sk_grid) : stg::gemm_split_plan(f.tiles, nslab, d.sk_grid);
       const StagedDev::SkTab *tab = frac ? nullptr : d.sk_tab(f.tiles, nslab, !h->capturing);
@@ -367,7 +383,8 @@ static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G,
 }
 // the control-sized elimination of stage k on the work block G: rank decision and K^-1 (k_st_small, or the blocked sweep
 // for matrices that live in global memory), Y and the carried rows, Rm = K^-1 Y (allow_sk: as in st_gemm)
-static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, double *G, bool allow_sk) {
+// (nRm: -Rm as well, K of order 1 .. 64)
+static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, double *G, bool allow_sk, double *nRm = nullptr) {
   const kktdev::StagedPlan &P = d.plan;
   const int nn = P.nk[k], mm = P.mk[k], ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
   stg::SmallArgs sa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], ek, P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr,
@@ -386,7 +403,7 @@ static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, co
   const long long ldy = P.ldy[k];
   stg::WideArgs wa{G, P.ldg[k], nn, mm, sp.N, P.ldn[k], P.capn[k], P.cap[k], q, sp.T, P.ldt[k], sp.dyn, sp.Y, ldy, sp.BT, P.ldb[k]};
   if (q > 0 && q <= 64) {
-    stg::RmArgs ra{sp.Kinv, sp.Kmat, P.ldq[k], sp.Y, sp.Rm, ldy, q, nn, 1, wa};
+    stg::RmArgs ra{sp.Kinv, sp.Kmat, P.ldq[k], sp.Y, sp.Rm, ldy, q, nn, 1, wa, nRm};
     KLAUNCH(h, KC_ST_GEMM_UPD, stg::k_st_rm<<<(nn + stg::RM_COLS - 1) / stg::RM_COLS, 256, stg::st_rm_lds(q), h->stream>>>(ra));
     return 0;
   }
@@ -632,6 +649,30 @@ static int staged_upload(hqpkkt_t *h) {
       HIPCHK(hipMemset(d.sk_cnt.p, 0, sizeof(unsigned) * (size_t)d.sk_cnt_elems));
     }
   }
+  // Which stages form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can
+  // (the tests), unset: those of at least FUSED_V_MIN_STATES states.  A stage can when its K has order 1 .. 64 (k_st_rm
+  // writes -Rm), its control columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA
+  {
+    const char *fv = getenv("HQPKKT_FUSED_V");
+    const int mode = fv ? atoi(fv) : 2;
+    d.fused.assign(P.K + 1, 0);
+    long long nrm = 0;
+    if (mode != 0 && !P.sharded && d.zeros.p)
+      for (int k = 0; k < P.K; k++) {
+        const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
+        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0 || (mode != 1 && nn < FUSED_V_MIN_STATES)) continue;
+        const long long nslab = stg::gemm_slabs(np) + stg::gemm_slabs(q);
+        const stg::GemmForm f = d.gemm_form(nn, nn, (int)(nslab * stg::GEMM_BK), 1, 1);
+        if (f.kind != stg::GEMM_FORM_FRAC && f.kind != stg::GEMM_FORM_CUT && f.kind != stg::GEMM_FORM_PLAIN) continue;
+        d.fused[k] = 1;
+        nrm = std::max(nrm, (long long)q * P.ldy[k]);
+      }
+    d.fv_nrm.release();
+    if (nrm > 0) {  // (slack: the operand loads of the last tile column read a tile's width past a row)
+      if ((e = d.fv_nrm.alloc((size_t)nrm + 8192))) return e;
+      HIPCHK(hipMemset(d.fv_nrm.p, 0, sizeof(double) * ((size_t)nrm + 8192)));
+    }
+  }
   // The control-sized chain of a stage on a second stream beside its large product G_xx.  Measured on one MI355X (same
   // box, tools/c4_bench.py): stages of 1500 / 2000 / 2500 / 3000 states + 2.7 / 2.5 / 3.5 / 2.7 %, 5000 states - 1.1 % (the
   // separate skinny product for the control rows of G and the contention cost more than the hidden chain), 1000 states
@@ -741,6 +782,7 @@ static int staged_upload(hqpkkt_t *h) {
       const int np = P.nk[k + 1], nn = P.nk[k], nz = nn + P.mk[k];
       d.sk_tab_prepare(np, nz, np, 0), d.sk_tab_prepare(np, nn, np, 0);
       d.sk_tab_prepare(nz, nz, np, 1), d.sk_tab_prepare(nn, nn, np, 1);
+      if (d.fused[k]) d.sk_tab_prepare(nn, nn, np, 1, P.qmax[k]);
     }
   d.lds_small = 0, d.lds_small_big = 0;
   for (int k = 0; k < P.K; k++) {
@@ -983,6 +1025,44 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   return 0;
 }
 
+
+// One stage of the backward recursion with V_k formed in the G_xx launch.  The rank-q update V = G_xx - Y'Rm is nothing
+// but memory traffic as a launch of its own (G_xx written, read back, V written with its image: 300 MB for 0.25 GFlop);
+// as gemm_slabs(q) more k-slabs of the product G_xx = F_x'W_x (GemmArgs::K2: A2 = Y, B2 = -Rm) G_xx never goes to memory.
+// That needs Y and Rm BEFORE the large product, and the control-sized chain that makes them needs only the control rows
+// of G: G_u = W_u'F, a thin product (k_dgemm_tn_ks) with W's control columns.  All on the first stream: with the chain
+// on a second stream beside W (W_u = V+ f_u as a thin product of its own) the stage was slower in every placement that
+// was measured - profiles/r08_stage_order.txt.
+static int staged_stage_fused(hqpkkt_t *h, int k) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm, q = P.qmax[k];
+  const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
+  const long long ldf = P.ldf[k], ldg = P.ldg[k], ldy = P.ldy[k];
+  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW, *nRm = d.fv_nrm.p;
+  const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
+  int e;
+  // W = V+ F; the control rows of G = W_u'F with H's control part; the carried rows N_k[e..] = B+ F
+  if ((e = st_gemm(h, stg::GemmArgs{sn.V, P.ldv[k + 1], sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}))) return e;
+  if (mm > 0 && (e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD)))
+    return e;
+  st_add_h(h, d, P.h_mid[k], ne_u, G);
+  if (P.cap[k + 1] > 0 &&
+      (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, ldf, nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], P.cap[k + 1], nz, np, 1.0, 0.0, 0, 0},
+                   KC_ST_GEMM_UPD)))
+    return e;
+  if ((e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
+  // V = F_x'W_x - Y'Rm (lower tiles, mirrored), then H_xx into the entry and its image
+  stg::GemmArgs g{sp.F, ldf, W, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, np, 1.0, 0.0, 1, 1};
+  g.A2 = sp.Y, g.lda2 = ldy, g.B2 = nRm, g.ldb2 = ldy, g.K2 = q;
+  if ((e = st_gemm(h, g))) return e;
+  if (ne_x)
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
+                                                                                 h->td.vals.p, h->td.wt.p, sp.V, ldg, P.ldv[k]));
+  return 0;
+}
+
 // Hqp_IpLQDOCP::factor (hqp/Hqp_IpLQDOCP.C:796-862): W^-1 Z, C'(W^-1 Z)C, then the backward
 // recursion over the stages (ExRiccatiFactorSc, :1794-1999)
 static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
@@ -1011,6 +1091,10 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   for (int k = K - 1; k >= 0; k--) {
     if (P.sharded) {
       if ((e = staged_stage_sharded(h, k))) return e;
+      continue;
+    }
+    if (d.fused[k]) {
+      if ((e = staged_stage_fused(h, k))) return e;
       continue;
     }
     StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);

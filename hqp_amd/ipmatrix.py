@@ -393,6 +393,19 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         names = {"nk": 20, "mk": 21, "nmk": 22, "eq_ptr": 23, "eq_rows": 24, "fix_rows": 25, "cap": 26}
         return {nm: self.debug(i) for nm, i in names.items()}
 
+    def stage_block(self, k):
+        """V_k of the last factorisation (tests)."""
+        n = C.c_longlong()
+        _check(self._L.hqpkkt_debug_stage_block(self._h, k, None, 0, C.byref(n)), "stage_block")
+        out = np.zeros(max(n.value, 1))
+        _check(self._L.hqpkkt_debug_stage_block(self._h, k, C.c_void_p(out.ctypes.data), n.value, C.byref(n)), "stage_block")
+        nk = int(round(n.value ** 0.5))
+        return out[: n.value].reshape(nk, nk)
+
+    def stages_fused(self):
+        """Per stage whether V_k comes out of the G_xx launch (HQPKKT_FUSED_V)."""
+        return self.debug(35)
+
     def stage_ranks(self):
         """(rank, carried rows) per stage of the last factorisation (tests)."""
         K1 = len(self.debug(20))
@@ -422,6 +435,14 @@ def bench_dgemm(M, N, K, lower=False, mirror=False, reps=5, device=0):
     _check(_lib.lib().hqpkkt_debug_dgemm(device, M, N, K, int(lower), int(mirror), reps, C.byref(ms), C.byref(err)), "debug_dgemm")
     flops = (1.0 if lower else 2.0) * M * N * K
     return ms.value, flops / (ms.value * 1e-3) / 1e12, err.value
+
+
+def bench_dgemm2(M, N, K, K2, lower=True, mirror=True, reps=1, device=0):
+    """The product with a second k segment, C = A'B - A2'B2 out of one launch: (ms per launch, max relative error, entries of
+    a mirrored result that differ in a bit from their image)."""
+    ms, err, asym = C.c_double(), C.c_double(), C.c_longlong()
+    _check(_lib.lib().hqpkkt_debug_dgemm2(device, M, N, K, K2, int(lower), int(mirror), reps, C.byref(ms), C.byref(err), C.byref(asym)), "debug_dgemm2")
+    return ms.value, err.value, asym.value
 
 
 def sk_table(tiles, nslab, grid=512):

@@ -340,6 +340,8 @@ int hqpkkt_set_values_staged(hqpkkt_t *h, const double *Qx, const double *const 
                              const double *Ex, const double *Cx);
 /* tests: rank and number of carried rows per stage (2 ints each, K+1 stages) of the last factor */
 int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap);
+/* tests: V_k of the last factor (n_k x n_k, row-major); one GPU.  out null: *len alone */
+int hqpkkt_debug_stage_block(hqpkkt_t *h, int k, double *out, long long cap, long long *len);
 
 /* Micro-benchmark and self-check of the dense fp64 MFMA product the STAGED engine is made of:
  * C (M x N) = A'B for pseudo-random k-major operands (K x M, K x N), `reps` timed launches
@@ -347,6 +349,10 @@ int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap);
  * *ms: average device time of a launch; *max_err: largest |C_ij - exact| / sum_k |a_ki b_kj|
  * over 4096 sampled entries. */
 int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err);
+/* The same with a second k segment: C = A'B - A2'B2 (A2: K2 x M, B2: K2 x N) out of ONE launch of the 128 x 128 LDS-DMA
+ * kernels (HQPKKT_E_RANGE for a shape or a variant that does not take them); asym: entries of a lower + mirror result
+ * that are not bit-identical to their mirror image. */
+int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym);
 
 /* Test hook, host only (no device needed): the work list of the cut form of that product (k_dgemm_tn_sk) for `tiles`
  * tiles of `nslab` k-slabs on `grid` workgroups - unequal shares for the two workgroups of a CU, sk_table.hpp.

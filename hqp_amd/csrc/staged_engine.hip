@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "staged.hip.h"
+#include "staged_sparse.hip.h"
 #include "staged_host.hip.h"
 
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn) {
@@ -51,7 +52,7 @@ void staged_reset(StagedDev &d) {
   d.plan = std::move(plan);
 }
 
-// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 35); the handle is in HQPKKT_MODE_STAGED and analysed
+// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 37); the handle is in HQPKKT_MODE_STAGED and analysed
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
   if (!h->sd) return HQPKKT_E_INTERN;
   const kktdev::StagedPlan &P = h->sd->plan;
@@ -99,12 +100,40 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       out.assign(P.K + 1, 0);
       for (size_t k = 0; k < h->sd->fused.size() && k < out.size(); k++) out[k] = h->sd->fused[k];
       break;
+    case 36:  // per stage k < K: stored entries of F_k, and 1 where the stage runs the sparse sequence (staged_stage_sparse)
+      for (int k = 0; k < P.K; k++) {
+        long long nnz = 0;
+        if (P.sparse_dyn)
+          nnz = P.sp_nnz[k];
+        else if (!P.dense_dyn)
+          nnz = (long long)(h->pAp[P.nks[k + 1]] - h->pAp[P.nks[k]]) - P.nk[k + 1];
+        else
+          nnz = (long long)P.nk[k + 1] * (P.nk[k] + P.mk[k]);  // (dense hand-over: the whole block)
+        out.push_back((int)std::min<long long>(nnz, 0x7fffffff)), out.push_back(P.sparse_dyn ? 1 : 0);
+      }
+      break;
+    case 37:  // the sparse form's ranges (host only): [first, end) into A's CSR arrays per dynamics row, then [first, end) into
+              // the CSR arrays of A' (rows ascending inside a column) per column of the stages k < K; empty on a dense-form handle
+      out = P.sp_arow;
+      out.insert(out.end(), P.sp_tcol.begin(), P.sp_tcol.end());
+      break;
     default: return HQPKKT_E_RANGE;
   }
   return 0;
 }
 
 extern "C" {
+
+int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (form != HQPKKT_DYN_DENSE && form != HQPKKT_DYN_SPARSE) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_sparse = form == HQPKKT_DYN_SPARSE;  // (the next hqpkkt_analyze picks it up)
+    return 0;
+  });
+}
 
 int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu) {
   return guarded([&]() -> int {
@@ -129,6 +158,7 @@ int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int 
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
     if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (h->sd && h->sd->plan.want_sparse) return HQPKKT_E_INTERN;  // (HQPKKT_DYN_SPARSE: the CSR hand-over alone)
     int e = hqpkkt_set_stages(h, K, nx, nu);
     if (e) return e;
     if (K < 1) return HQPKKT_E_RANGE;

@@ -13,6 +13,7 @@ struct StagedDev {
   DBuf<stg::HTerm> h_terms;
   DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
+  DBuf<int> sp_arow, sp_tcol;   // the sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A'
   DBuf<double> dyn_part;        // row sums of A_dyn dx per block of 256 columns (k_st_dyn_both): ndyn x dyn_part_cols
   int dyn_part_cols = 0;
   PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging)
@@ -486,17 +487,21 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
+  const bool want_sparse = P.want_sparse;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu;
+  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
   P.sharded = h->shard_count > 1 || h->xchg_fn || h->xchg_sfn;
+  if (want_sparse && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over
+  if (want_sparse && P.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
   h->an.shard_rank = h->shard_rank, h->an.shard_count = 1;  // (the tree engine's exchange plan is not used)
   int e = h->an.setup_blocks(1, n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(),
                              h->pCp.data(), h->pCi.data());
   if (e) return e;
-  e = P.run(n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(), h->pCp.data(), h->pCi.data());
+  e = P.run(n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(), h->pCp.data(), h->pCi.data(), h->an.AT.ptr.data(),
+            h->an.AT.col.data());
   if (e) return e;
   h->an.sbw = -1;
   h->analyzed = true;
@@ -580,6 +585,7 @@ static int staged_upload(hqpkkt_t *h) {
     for (size_t k = 0; k < t.size(); k++) t[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
     if ((e = d.h_terms.upload(t))) return e;
   }
+  if (P.sparse_dyn && ((e = d.sp_arow.upload(P.sp_arow)) || (e = d.sp_tcol.upload(P.sp_tcol)))) return e;
   if (P.dense_dyn && P.sharded) {
     // the local blocks: own state columns [c0, c0 + wd) and the control columns; rank 0 adds what belongs to nobody's strip
     const int NR = P.shard_count, RK = P.shard_rank;
@@ -657,7 +663,7 @@ static int staged_upload(hqpkkt_t *h) {
     const int mode = fv ? atoi(fv) : 2;
     d.fused.assign(P.K + 1, 0);
     long long nrm = 0;
-    if (mode != 0 && !P.sharded && d.zeros.p)
+    if (mode != 0 && !P.sharded && !P.sparse_dyn && d.zeros.p)
       for (int k = 0; k < P.K; k++) {
         const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
         if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0 || (mode != 1 && nn < FUSED_V_MIN_STATES)) continue;
@@ -681,7 +687,7 @@ static int staged_upload(hqpkkt_t *h) {
   {
     d.overlap_mode = 2;  // by stage width
     bool any = d.overlap_mode == 1 || P.sharded;
-    if (d.overlap_mode == 2)
+    if (d.overlap_mode == 2 && !P.sparse_dyn)  // (the sparse form has no large product to run the chain beside)
       for (int k = 0; k < P.K; k++) any = any || (P.nk[k] >= 1280 && P.nk[k] <= 4096);
     if (!d.stream2 && any) {
       {
@@ -694,7 +700,7 @@ static int staged_upload(hqpkkt_t *h) {
       HIPCHK(hipEventCreateWithFlags(&d.ev_fork.h, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&d.ev_join.h, hipEventDisableTiming));
     }
-    d.overlap = d.stream2 != nullptr && d.overlap_mode != 0;
+    d.overlap = d.stream2 != nullptr && d.overlap_mode != 0 && !P.sparse_dyn;
     d.ks_ws2_elems = 0;
     if (d.stream2 && d.cus > 0) {
       d.ks_ws2_elems = 8LL << 20;
@@ -1063,6 +1069,40 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   return 0;
 }
 
+// the entries of the columns [c0, c0 + ncols) of F_k out of the CSR arrays of A' (staged_sparse.hip.h)
+static stg::SpCols sp_cols(hqpkkt_t *h, StagedDev &d, int k, int c0, int ncols) {
+  const kktdev::StagedPlan &P = d.plan;
+  return stg::SpCols{d.sp_tcol.p + 2 * ((long long)P.nmk[k] + c0), h->td.AT.col.p, h->td.AT.val.p, P.nks[k], ncols};
+}
+// One stage of the backward recursion in the sparse form (StagedPlan::sparse_dyn; Hqp_IpLQDOCP's FormGxxSp,
+// hqp/Hqp_IpLQDOCP.C:1119-1220): T = F'V+ in W's place and G = T F with its mirror image by k_sp_gather, the carried
+// rows by k_sp_carried; everything behind them is the dense sequence's - H, the control-sized elimination, the rank-q
+// update V = G_xx - Y'Rm (still an MFMA product).  One stream: nothing large is left to run the chain beside.
+static int staged_stage_sparse(hqpkkt_t *h, int k) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
+  const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k], cx = P.cap[k + 1];
+  const long long ldt = P.ldv[k + 1], ldg = P.ldg[k];
+  double *G = d.misc.p + P.oG, *T = d.misc.p + P.oW;
+  const stg::SpCols f = sp_cols(h, d, k, 0, nz);
+  const unsigned cb = (unsigned)((nz + 255) / 256);
+  int e;
+  if (np > 0 && nz > 0) {
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_gather<<<dim3(cb, (np + stg::SP_RB - 1) / stg::SP_RB), 256, 0, h->stream>>>(
+                                 stg::SpGather{f, sn.V, P.ldv[k + 1], np, nullptr, 0, T, ldt, 0}));
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_gather<<<dim3(cb, (nz + stg::SP_RB - 1) / stg::SP_RB), 256, 0, h->stream>>>(
+                                 stg::SpGather{f, T, ldt, nz, G, ldg, G, ldg, 1}));
+  }
+  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
+  if (cx > 0 && nz > 0)  // carried rows: N_k[e..] = B+ F
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_carried<<<dim3(cb, (cx + 7) / 8), 256, 0, h->stream>>>(
+                                 stg::SpCarried{f, sn.BT, P.ldb[k + 1], cx, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
+  if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
+  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+}
+
 // Hqp_IpLQDOCP::factor (hqp/Hqp_IpLQDOCP.C:796-862): W^-1 Z, C'(W^-1 Z)C, then the backward
 // recursion over the stages (ExRiccatiFactorSc, :1794-1999)
 static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
@@ -1091,6 +1131,10 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   for (int k = K - 1; k >= 0; k--) {
     if (P.sharded) {
       if ((e = staged_stage_sharded(h, k))) return e;
+      continue;
+    }
+    if (P.sparse_dyn) {
+      if ((e = staged_stage_sparse(h, k))) return e;
       continue;
     }
     if (d.fused[k]) {
@@ -1231,6 +1275,10 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       // gam = q_k + F' tt: the own state columns and the control columns
       if (wd > 0 && (e = st_gemv_cols(h, d, sp.F, P.ldfl[k], np, wd, xv, qv + P.nmk[k] + c0, 1.0, gam + c0))) return e;
       if (mm > 0 && (e = st_gemv_cols(h, d, sp.F + wd, P.ldfl[k], np, mm, xv, qv + P.nmk[k] + nn, 1.0, gam + nn))) return e;
+    } else if (P.sparse_dyn) {  // gam = q_k + F' tt over the columns' entries
+      if (nn + mm > 0)
+        KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_cols<<<nblk(nn + mm), 256, 0, s>>>(
+                                         stg::SpGemvCols{sp_cols(h, d, k, 0, nn + mm), tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
     } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
     st_bwd_small(h, d, k, sp, sn, v.r2, gam);
@@ -1253,6 +1301,12 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     const int c0 = cut0(k), wd = width(k), c0n = cut0(k + 1), wdn = width(k + 1);
     double *xk = S + P.nmk[k];
     st_fwd_small(h, d, k, sp, sn, v.dy);
+    if (P.sparse_dyn) {  // x+ = F s + f over the rows' entries
+      if (np > 0)
+        KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_rows<<<(np + 15) / 16, 256, 0, s>>>(stg::SpGemvRows{
+                                         d.sp_arow.p + 2 * (long long)P.nks[k], h->td.A.col.p, h->td.A.val.p, P.nmk[k], np, xk, v.r2 + P.nks[k], S + P.nmk[k + 1], 1.0}));
+      continue;
+    }
     if (!sh) {  // x+ = F s + f (the multipliers p = V+ x+ + v+ + B+' eta+ behind the sweep)
       if ((e = st_gemv_rows(h, stg::GemvRows{sp.F, P.ldf[k], np, nn + mm, xk, v.r2 + P.nks[k], nullptr, 0, nullptr, nullptr, S + P.nmk[k + 1], 1.0})))
         return e;

@@ -59,8 +59,10 @@ int stages_from_staircase(int n, int rows, const int *row_len, const int *last_c
 }
 
 int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const int *Ap, const int *Ai,
-                    const int *Cp, const int *Ci) {
+                    const int *Cp, const int *Ci, const int *ATp, const int *ATi) {
   n = n_, m = m_;
+  sparse_dyn = want_sparse;
+  if (sparse_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
   nq = n ? Qp[n] : 0, nc = m ? Cp[m] : 0;
   const int arows = me_;  // rows of the A that was handed over
   na = arows ? Ap[arows] : 0;
@@ -233,7 +235,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     oVec[k] = mo, mo += up16((long long)nk[k] + 2LL * std::max(cap[k], 1) + std::max(qmax[k], 1) + 8);
     if (k < K) {
       ldf[k] = up8(nz), ldg[k] = up8(nz);
-      oF[k] = fo, fo += up16((long long)nk[k + 1] * ldf[k]);
+      if (!sparse_dyn) oF[k] = fo, fo += up16((long long)nk[k + 1] * ldf[k]);
       ldy[k] = up8(std::max(nk[k], 1)), ldq[k] = up8(std::max(qmax[k], 1)), ldt[k] = up8(std::max(mk[k], 1));
       oY[k] = mo, mo += up16((long long)std::max(qmax[k], 1) * ldy[k]);
       oR[k] = mo, mo += up16((long long)std::max(qmax[k], 1) * ldy[k]);
@@ -242,6 +244,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
       resmax = std::max(resmax, (long long)std::max(qmax[k], 1) * ldy[k]);
       oT[k] = mo, mo += up16((long long)std::max(cap[k], 1) * ldt[k]);
       if (!sharded) wmax = std::max(wmax, (long long)nk[k + 1] * ldf[k]);  // (sharded: W_p goes straight into its exchange slot)
+      if (sparse_dyn) wmax = std::max(wmax, (long long)nz * up8(nk[k + 1]));  // (T = F'V+ in W's place: rows of n+ doubles)
       gmax = std::max(gmax, (long long)nz * ldg[k]);
     }
   }
@@ -382,7 +385,9 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
         const int li = i - nks[k];
         for (int p = Ap[i]; p < Ap[i + 1] - 1; p++) {
           const int lc = Ai[p] - nmk[k];
-          if (!sharded)
+          if (sparse_dyn)
+            continue;  // (no dense block: the kernels read the row lists)
+          else if (!sharded)
             a_dst[p] = oF[k] + (long long)li * ldf[k] + lc;
           else {  // the local block: own state columns, then the control columns
             const int c0 = xcut[(size_t)k * (shard_count + 1) + shard_rank], c1 = xcut[(size_t)k * (shard_count + 1) + shard_rank + 1];
@@ -450,15 +455,37 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     for (int k = 0; k <= K; k++) h_mid[k] = h_ptr[k] + nstate[k];
   }
 
+  // ------------------------------------------------------------------ the sparse form's row ranges
+  sp_arow.clear(), sp_tcol.clear(), sp_nnz.clear();
+  if (sparse_dyn) {
+    sp_arow.assign(2 * (size_t)ndyn, 0), sp_tcol.assign(2 * (size_t)nmk[K], 0), sp_nnz.assign(K, 0);
+    for (int k = 0; k < K; k++) {
+      for (int i = nks[k]; i < nks[k + 1]; i++) sp_arow[2 * i] = Ap[i], sp_arow[2 * i + 1] = Ap[i + 1] - 1, sp_nnz[k] += Ap[i + 1] - 1 - Ap[i];
+      // (the rows of A' are in ascending order of A's rows: the dynamics rows of the stage are one range)
+      for (int c = nmk[k]; c < nmk[k + 1]; c++) {
+        const int *b = ATi + ATp[c], *e = ATi + ATp[c + 1];
+        sp_tcol[2 * c] = (int)(std::lower_bound(b, e, nks[k]) - ATi), sp_tcol[2 * c + 1] = (int)(std::lower_bound(b, e, nks[k + 1]) - ATi);
+      }
+    }
+  }
+
   // ------------------------------------------------------------------ work counts
   flops_factor = 0, bytes_step = 0;
   for (int k = 0; k < K; k++) {
     const long long nn = nk[k], mm = mk[k], np = nk[k + 1], nz = nn + mm, q = qmax[k];
-    flops_factor += 2 * np * np * nz;       // W = V+ F
-    flops_factor += np * nz * nz;           // G = F' W, lower half
-    flops_factor += 2 * (long long)cap[k + 1] * np * nz;  // carried rows
+    if (sparse_dyn) {
+      // two flops per (entry of F_k) x (row length): T = F'V+ (rows of n+), G = T F (lower half: rows of n_k + m_k on
+      // average halved), the carried rows
+      const long long nnz = sp_nnz[k];
+      flops_factor += 2 * nnz * np + nnz * nz + 2 * nnz * cap[k + 1];
+      bytes_step += 8 * (2 * np * np + 4 * nnz + 2 * q * nn);
+    } else {
+      flops_factor += 2 * np * np * nz;       // W = V+ F
+      flops_factor += np * nz * nz;           // G = F' W, lower half
+      flops_factor += 2 * (long long)cap[k + 1] * np * nz;  // carried rows
+      bytes_step += 8 * (2 * np * np + 2 * np * nz + 2 * q * nn);
+    }
     flops_factor += 2 * q * q * nn + q * nn * nn;         // Rm, V update (lower half)
-    bytes_step += 8 * (2 * np * np + 2 * np * nz + 2 * q * nn);
   }
   return 0;
 }

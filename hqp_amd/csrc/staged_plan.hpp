@@ -29,6 +29,15 @@ struct StagedPlan {
   bool fixed_x0 = false;
   std::vector<int> fix_rows, fix_src;  // per x_0 component: its row of A and the index of its value in vals
   bool dense_dyn = false;  // dynamics handed over as dense blocks: their rows of A are empty
+  // The sparse form of the stage products (hqpkkt_set_dynamics_form, Hqp_IpLQDOCP's mat_a_sparse,
+  // hqp/Hqp_IpLQDOCP.C:1119-1273): F_k stays the row lists of A and A' - no dense block, f_elems = 0.  Per dynamics row
+  // i of A the entries sp_arow[2 i] .. sp_arow[2 i + 1] of A's CSR arrays (the row without its trailing -1); per column
+  // c < nmk[K] the entries sp_tcol[2 c] .. sp_tcol[2 c + 1] of the CSR arrays of A' that lie in the dynamics rows of c's
+  // stage (a row of A' also holds the -1 of the stage before and the other equality rows: skipped, as FormGxxSp skips
+  // its first entry).  The values stay in `vals` behind the CSR blocks' src.  want_sparse: the form the next analysis takes
+  bool want_sparse = false, sparse_dyn = false;
+  std::vector<int> sp_arow, sp_tcol;
+  std::vector<int> sp_nnz;  // stored entries of F_k (K)
 
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;
@@ -127,8 +136,9 @@ struct StagedPlan {
 
   // returns 0, or a HQPKKT_E_* code: 6 the pattern is not a staircase / rows leave their stage,
   // 1 a stage exceeds what the one-workgroup kernels hold
+  // (ATp, ATi: the CSR arrays of A' as Analysis::setup_blocks builds them, rows ascending; read by the sparse form alone)
   int run(int n, int me, int m, const int *Qp, const int *Qi, const int *Ap, const int *Ai, const int *Cp,
-          const int *Ci);
+          const int *Ci, const int *ATp = nullptr, const int *ATi = nullptr);
 };
 
 }  // namespace kktdev

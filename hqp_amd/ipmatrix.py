@@ -337,9 +337,25 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     """The multistage plugin hqp/Hqp_IpLQDOCP.C: stage structure found from the staircase of
     A (Get_Dim, :201-287), dense per-stage blocks, the extended Riccati recursion as fp64
     MFMA products (HQPKKT_MODE_STAGED).  ``set_stages(nx, nu)`` before init() gives the stage
-    sizes explicitly."""
+    sizes explicitly.  ``a_sparse=True`` (the reference's mat_a_sparse, hqp/Hqp_IpLQDOCP.C:178) or
+    ``set_dynamics_form("sparse")`` before init(): the stage products walk the row lists of A instead of
+    dense blocks F_k - for dynamics with a few entries per column (hqpkkt_set_dynamics_form)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
+
+    def __init__(self, *args, a_sparse=False, **kw):
+        super().__init__(*args, **kw)
+        if a_sparse:
+            self.set_dynamics_form("sparse")
+
+    def set_dynamics_form(self, form):
+        """"dense" (default) or "sparse"; holds from the next init() on."""
+        code = {"dense": _lib.DYN_DENSE, "sparse": _lib.DYN_SPARSE}.get(form, form)
+        _check(self._L.hqpkkt_set_dynamics_form(self._h, int(code)), "set_dynamics_form")
+
+    def dynamics_entries(self):
+        """Per stage k < K: (stored entries of F_k, 1 where the stage runs the sparse sequence)."""
+        return self.debug(36).reshape(-1, 2)
 
     def set_stages(self, nx, nu):
         nx, nu = _i32(nx), _i32(nu)

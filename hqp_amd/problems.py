@@ -196,6 +196,105 @@ def lq_docp(K, nx, nu, seed=3, density=1.0, x0_fixed=True, final_eq=0, path_eq=0
     return Program(n, me, m, Q, A, C, c=rng.uniform(-0.1, 0.1, n), b=b, d=np.ones(m))
 
 
+def sparse_docp(K, nx, nu, band=5, seed=3, x0_fixed=True, final_eq=0, path_eq=0, path_eq_every=1, x_bounds=0,
+                fu_nnz=3, empty_col=None, empty_row=None, dense=False, low_rank=True):
+    """Multistage QP with SPARSE dynamics in the layout of :func:`lq_docp` (Hqp_Docp::setup_qp), the workload of the
+    sparse form of the stage products (``Hqp_IpLQDOCP(a_sparse=True)``, the reference's mat_a_sparse): discretised PDEs,
+    networks, chains of subsystems.  ``fx_k`` has ``band`` entries either side of its diagonal (rectangular where the
+    stages differ: the diagonal runs from corner to corner), scaled to spectral radius about 0.9; ``fu_k`` has
+    ``fu_nnz`` entries per control column; ``Q`` is diagonal plus the rank-2 term of lq_docp (its pattern is dense per
+    stage: the cost-to-go Hessians are).  ``nx`` may be a list of K + 1 stage widths (the staircase detection reads
+    x_0's width off the first stage: nx[0] must equal nx[1]), ``nu`` a list of K.  ``empty_col = (k, j)`` leaves
+    state column j of F_k without entries, ``empty_row = (k, i)`` row i of fx_k (the row keeps its fu entries and gets
+    one if it has none).  ``dense`` fills fx_k and fu_k completely; ``low_rank=False`` leaves Q diagonal (stages of
+    thousands of states: the rank-2 term alone makes nx^2 / 2 entries per stage).  Same options as lq_docp otherwise."""
+    rng = np.random.default_rng(seed)
+    nxs = [int(nx)] * (K + 1) if np.isscalar(nx) else [int(v) for v in nx]
+    nus = [int(nu)] * K if np.isscalar(nu) else [int(v) for v in nu]
+    assert len(nxs) == K + 1 and len(nus) == K and min(nus) >= 1 and nxs[0] == nxs[1]
+    off = np.concatenate([[0], np.cumsum([nxs[k] + nus[k] for k in range(K)])]).astype(np.int64)
+    n = int(off[K] + nxs[K])
+    xi = lambda k: int(off[k])
+    ui = lambda k: int(off[k] + nxs[k])
+    roff = np.concatenate([[0], np.cumsum(nxs[1:])]).astype(np.int64)
+    # Q: diagonal + low rank on every x_k, 0.1 I on u_k
+    qr, qc, qv = [], [], []
+    for k in range(K + 1):
+        nk = nxs[k]
+        if low_rank:
+            low = rng.uniform(-0.3, 0.3, (nk, 2))
+            Lxx = np.diag(rng.uniform(0.8, 1.2, nk)) + low @ low.T
+            iu, ju = np.triu_indices(nk)
+            qr.append(xi(k) + iu), qc.append(xi(k) + ju), qv.append(Lxx[iu, ju])
+        else:
+            qr.append(xi(k) + np.arange(nk)), qc.append(xi(k) + np.arange(nk)), qv.append(rng.uniform(0.8, 1.2, nk))
+        if k < K:
+            qr.append(ui(k) + np.arange(nus[k])), qc.append(ui(k) + np.arange(nus[k])), qv.append(np.full(nus[k], 0.1))
+    Q = _csr(np.concatenate(qr), np.concatenate(qc), np.concatenate(qv), n)
+    ar, ac, av = [], [], []
+    for k in range(K):
+        nk, mk, nn = nxs[k], nus[k], nxs[k + 1]
+        i, j = np.meshgrid(np.arange(nn), np.arange(nk), indexing="ij")
+        centre = (i * nk) // max(nn, 1)
+        mask = np.ones((nn, nk), bool) if dense else np.abs(j - centre) <= band
+        fx = np.where(mask, rng.uniform(-1, 1, (nn, nk)), 0.0)
+        if empty_col is not None and empty_col[0] == k:
+            fx[:, empty_col[1]] = 0.0
+        if empty_row is not None and empty_row[0] == k:
+            fx[empty_row[1], :] = 0.0
+        sq = min(nn, nk)
+        rho = np.abs(np.linalg.eigvals(fx[:sq, :sq])).max() if sq <= 600 else np.abs(fx).sum(1).max()
+        fx *= 0.9 / max(rho, 1e-12)
+        fu = np.zeros((nn, mk))
+        if dense:
+            fu = rng.uniform(-1, 1, (nn, mk))
+        else:
+            for c in range(mk):
+                fu[rng.choice(nn, size=min(fu_nnz, nn), replace=False), c] = rng.uniform(-1, 1, min(fu_nnz, nn))
+        if empty_row is not None and empty_row[0] == k and not fu[empty_row[1]].any():
+            fu[empty_row[1], 0] = 0.5
+        for i0 in np.flatnonzero(~(fx.any(1) | fu.any(1))):  # (a dynamics row holds an entry besides its -1)
+            fu[i0, 0] = 0.25
+        r, c = np.nonzero(fx)
+        ar.append(roff[k] + r), ac.append(xi(k) + c), av.append(fx[r, c])
+        r, c = np.nonzero(fu)
+        ar.append(roff[k] + r), ac.append(ui(k) + c), av.append(fu[r, c])
+        ar.append(roff[k] + np.arange(nn)), ac.append(xi(k + 1) + np.arange(nn)), av.append(np.full(nn, -1.0))
+    me = int(roff[K])
+    bvals = [np.zeros(me)]
+    if x0_fixed:
+        rows = np.arange(nxs[0])
+        ar.append(me + rows), ac.append(xi(0) + rows), av.append(np.ones(nxs[0]))
+        bvals.append(-rng.uniform(-1, 1, nxs[0]))
+        me += nxs[0]
+    if path_eq:
+        for k in range(0, K, path_eq_every):
+            nz = nxs[k] + nus[k]
+            for _ in range(path_eq):
+                ar.append(np.full(nz, me)), ac.append(np.arange(xi(k), xi(k) + nz)), av.append(rng.uniform(-1, 1, nz))
+                bvals.append(rng.uniform(-0.1, 0.1, 1))
+                me += 1
+    if final_eq:
+        fr = np.arange(final_eq)
+        ar.append(me + fr), ac.append(xi(K) + fr), av.append(np.ones(final_eq))
+        bvals.append(rng.uniform(-0.1, 0.1, final_eq))
+        me += final_eq
+    A = _csr(np.concatenate(ar), np.concatenate(ac), np.concatenate(av), me)
+    # C: -1 <= u <= 1 (+ upper bounds on the first components of x_k, k >= 1)
+    ucols = np.concatenate([ui(k) + np.arange(nus[k]) for k in range(K)])
+    cc = np.concatenate([np.concatenate([ui(k) + np.arange(nus[k])] * 2) for k in range(K)])
+    cv = np.concatenate([np.concatenate([np.ones(nus[k]), -np.ones(nus[k])]) for k in range(K)])
+    m = 2 * ucols.size
+    if x_bounds:
+        xb = np.concatenate([xi(k) + np.arange(min(x_bounds, nxs[k])) for k in range(1, K + 1)])
+        cc, cv = np.concatenate([cc, xb]), np.concatenate([cv, -np.ones(xb.size)])
+        m += xb.size
+    C = _csr(np.arange(m), cc, cv, m)
+    prog = Program(n, me, m, Q, A, C, c=rng.uniform(-0.1, 0.1, n), b=np.concatenate(bvals), d=np.ones(m))
+    prog.nx, prog.nu = nxs, nus
+    return prog
+
+
 class DenseDocp:
     """A multistage QP whose dynamics rows are handed over as dense blocks
     (hqpkkt_analyze_staged / hqpkkt_set_values_staged): ``F[k]`` = [fx_k fu_k], row-major

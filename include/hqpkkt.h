@@ -46,7 +46,8 @@ extern "C" {
 #define HQPKKT_MODE_FULL 0    /* Hqp_IpSpBKP    (hqp/Hqp_IpSpBKP.C:76-218)    */
 #define HQPKKT_MODE_REDUCED 1 /* Hqp_IpRedSpBKP (hqp/Hqp_IpRedSpBKP.C:184-368) */
 #define HQPKKT_MODE_STAGED 2  /* Hqp_IpLQDOCP    (hqp/Hqp_IpLQDOCP.C:693-976): multistage (DOCP)
-                                 structure, dense per-stage blocks, see hqpkkt_set_stages */
+                                 structure, dense per-stage blocks - or, for sparse dynamics, the
+                                 row lists of A (hqpkkt_set_dynamics_form) -, see hqpkkt_set_stages */
 
 /* where the vectors z,w,r1..r4,dx..dw (and Qx,Ax,Cx) live */
 #define HQPKKT_LOC_HOST 0   /* Meschach VEC::ve pointers; copied H2D / D2H per call */
@@ -304,6 +305,20 @@ int hqpkkt_set_shard_stream(hqpkkt_t *h, int rank, int count, hqpkkt_exchange_st
  * elimination runs out of global memory (one workgroup: correct and slow, ~20 ms per stage at 300
  * controls).  mat_sbw is -1. */
 int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu);
+/* The form of the stage products with the dynamics F_k = [fx_k fu_k] - Hqp_IpLQDOCP's interface variable mat_a_sparse
+ * (hqp/Hqp_IpLQDOCP.C:178; FormGxxSp / FormGxSp, :1119-1273).  HQPKKT_DYN_DENSE (default): the dynamics rows of A are
+ * scattered into dense blocks and every stage runs W = V+ F, G = F'W as fp64 MFMA products.  HQPKKT_DYN_SPARSE: F_k stays
+ * the row lists of A and A' the handle holds anyway; T = F'V+ and G = T F walk them (two flops per stored entry and row
+ * element, no F arena: hqpkkt_stats.bytes_panels shrinks by it), as do the solve's two products with F_k; everything
+ * control-sized and the rank-q update of V_k are unchanged.  Host-only; call it before hqpkkt_analyze, like
+ * hqpkkt_set_stages: the form holds until it is set again and the next hqpkkt_analyze picks it up.  HQPKKT_E_RANGE: unknown
+ * form; HQPKKT_E_INTERN: the handle's mode is not STAGED.  With HQPKKT_DYN_SPARSE set hqpkkt_analyze_staged (the dense
+ * hand-over) returns HQPKKT_E_INTERN, and hqpkkt_analyze on a handle with hqpkkt_set_shard / hqpkkt_set_shard_stream
+ * returns HQPKKT_E_RANGE: one system over several ranks stays dense.  There is no automatic choice; the sparse form pays
+ * while a column of F_k holds few entries against the number of states (DESIGN.md section 3 has the measured times). */
+#define HQPKKT_DYN_DENSE 0   /* default: dense blocks F_k, MFMA products           */
+#define HQPKKT_DYN_SPARSE 1  /* Hqp_IpLQDOCP's mat_a_sparse: F_k stays row lists   */
+int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense
@@ -454,7 +469,11 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * per stage, 21 controls, 22 first column, 23 / 24 own equality rows (ptr / rows), 25 rows
  * that fix x_0, 26 capacity of carried rows, 27 column cuts of the ranks ((K+1) x (ranks+1)), 28 two counters of
  * the last factorisation: stages whose K was inverted by the blocked elimination, and those of them that fell back to the
- * one-workgroup elimination (device -> host copy); 30 (zero-diagonal policy in use, last
+ * one-workgroup elimination (device -> host copy); 32 - 35 further STAGED diagnostics (staged_engine.hip); 36 per stage
+ * k < K two ints: the stored entries of F_k and 1 where the stage runs the sparse sequence (hqpkkt_set_dynamics_form);
+ * 37 the sparse form's ranges: per dynamics row [first, end) into A's CSR arrays (the row without its -1), then per column
+ * of the stages k < K [first, end) into the CSR arrays of A' (rows ascending) - the column's entries in the dynamics rows
+ * of its stage; empty on a dense-form handle; 30 (zero-diagonal policy in use, last
  * values have weak Hessian diagonals), 31 (fronts of the tree's top that the solve handles in one launch, first
  * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
  * process, over all handles: answered on any handle, analysed or not).

@@ -365,12 +365,14 @@ int Hqp_IpMatrixHip::create_handle(int mode)
   return HQPKKT_OK;
 }
 
-int Hqp_IpMatrixHip::open(int mode)
+int Hqp_IpMatrixHip::open(int mode, bool sparse_dyn)
 {
   int e;
   if ((e = create_handle(mode)))
     return e;
   _dense = false;
+  if (sparse_dyn && (e = hqpkkt_set_dynamics_form(_h, HQPKKT_DYN_SPARSE)))
+    return e;
   if ((e = hqpkkt_analyze(_h, _n, _me, _m,
                           _Qp->ive, _Qi->ive, _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive,
                           &_sbw)))
@@ -390,8 +392,14 @@ void Hqp_IpMatrixHip::init(const Hqp_Program *qp)
 
   // the handle is created here: mat_tol / mat_eps / mat_device may have been set
   if (_mode == HQPKKT_MODE_STAGED) {
-    // the dynamics as dense stage blocks straight from the row lists (no CSR copy of them: open_dense)
-    e = open_dense(qp);
+    // the dynamics as dense stage blocks straight from the row lists (no CSR copy of them: open_dense); with
+    // mat_a_sparse (hqp/Hqp_IpLQDOCP.C:178) as CSR rows, which the sparse form of the stage products walks
+    const bool sparse_dyn = _a_sparse != 0 && _ngpu <= 1;
+    if (sparse_dyn) {
+      extract(qp, changed);
+      e = open(HQPKKT_MODE_STAGED, true);
+    } else
+      e = open_dense(qp);
     const char *why = NULL;
     if (e == HQPKKT_E_FORMAT || e == HQPKKT_E_SIZES) {
       // not the staircase of a DOCP (where Hqp_IpLQDOCP::init asserts, hqp/Hqp_IpLQDOCP.C:700-707), or a stage with
@@ -410,7 +418,9 @@ void Hqp_IpMatrixHip::init(const Hqp_Program *qp)
     }
     if (_logging > 0) {
       fprintf(stderr, "LQDOCPHip: n %d me %d m %d", _n, _me, _m);
-      if (_dense)
+      if (sparse_dyn && _mode_used == HQPKKT_MODE_STAGED)
+        fprintf(stderr, ": STAGED engine, sparse form of the stage products (mat_a_sparse)\n");
+      else if (_dense)
         fprintf(stderr, ", %d stages (x_0: %d states; widest stage %d states + %d controls), %d dynamics rows as dense "
                 "blocks: STAGED engine\n", _K, _nx->ive[0], _nx->ive[_K], _K ? _nu->ive[0] : 0, _ndyn);
       else
@@ -501,13 +511,12 @@ void Hqp_IpMatrixHip::factor(const Hqp_Program *qp, const VEC *z, const VEC *w)
 {
   int e;
   assert((int)z->dim == _m && (int)w->dim == _m);
-  if (_mode == HQPKKT_MODE_STAGED && !_told_ignored && (_wz_tol != HUGE_VAL || _a_sparse != 0)) {
-    // hqp/Hqp_IpLQDOCP.C:850-853 would take ExRiccatiFactor() instead of ExRiccatiFactorSc() with mat_wz_tol set,
-    // :437, 738, 1357-1368 the sparse forms of fx, fu with mat_a_sparse: neither exists here (one recursion on dense
-    // blocks, same solution up to the residual contract) - said once, never silently
+  if (_mode == HQPKKT_MODE_STAGED && !_told_ignored && _wz_tol != HUGE_VAL) {
+    // hqp/Hqp_IpLQDOCP.C:850-853 would take ExRiccatiFactor() instead of ExRiccatiFactorSc() with mat_wz_tol set: that
+    // recursion does not exist here (one recursion, same solution up to the residual contract) - said once, never silently
     _told_ignored = true;
-    fprintf(stderr, "LQDOCPHip: mat_wz_tol (%g) / mat_a_sparse (%d) are set to non-default values; this plugin has one "
-            "recursion (the scaled form of ExRiccatiFactorSc) on dense stage blocks and ignores both\n", (double)_wz_tol, _a_sparse);
+    fprintf(stderr, "LQDOCPHip: mat_wz_tol (%g) is set to a non-default value; this plugin has one recursion (the scaled "
+            "form of ExRiccatiFactorSc) and ignores it\n", (double)_wz_tol);
   }
   hqpkkt_set_tol(_h, _tol);
   e = hqpkkt_factor(_h, z->ve, w->ve);

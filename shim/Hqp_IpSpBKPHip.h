@@ -36,10 +36,11 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
   int _ordering;      // mat_ordering: 0 nested dissection of the RCM band, 1 of the graph itself
   int _staged_min_front; // mat_staged_min_front: LQDOCPHip uses the STAGED engine from this stage width on
   int _update_threads; // mat_update_threads: host threads of update()'s walk over the row lists
-  // LQDOCPHip (hqp/Hqp_IpLQDOCP.C:177-179 registers the same three): mat_wz_tol and mat_a_sparse are accepted and
-  // not used - factor() says so once on stderr when either is set to a non-default value (the first selects the reference's other recursion, off by default: HUGE_VAL, :111, 850-853; the
-  // second its sparse products with fx, fu, which have no counterpart on dense MFMA blocks), mat_logging > 0 prints
-  // the stage structure and the engine chosen at init()
+  // LQDOCPHip (hqp/Hqp_IpLQDOCP.C:177-179 registers the same three): mat_wz_tol is accepted and not used - factor() says
+  // so once on stderr when it is set to a non-default value (it selects the reference's other recursion, off by default:
+  // HUGE_VAL, :111, 850-853); mat_a_sparse != 0 takes the CSR hand-over with the sparse form of the stage products
+  // (hqpkkt_set_dynamics_form; one system over several GPUs stays dense), mat_logging > 0 prints the stage structure
+  // and the engine chosen at init()
   Real _wz_tol;
   int _a_sparse, _logging;
   bool _told_ignored;
@@ -56,7 +57,7 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
 
   void extract(const Hqp_Program *qp, bool &pattern_changed);
   int create_handle(int mode);
-  int open(int mode);
+  int open(int mode, bool sparse_dyn = false);
   int open_dense(const Hqp_Program *qp);
   int dense_values(const Hqp_Program *qp);
   void check(int status, const char *where);

@@ -142,7 +142,7 @@ def lib():
     L.hqpkkt_debug_dgemm.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_double)] * 2
     L.hqpkkt_debug_stage_block.argtypes = [vp, C.c_int, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_dgemm2.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_double)] * 2 + [C.POINTER(C.c_longlong)]
-    L.hqpkkt_debug_sk_table.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong),
+    L.hqpkkt_debug_sk_table.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]

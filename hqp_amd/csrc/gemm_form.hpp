@@ -1,7 +1,8 @@
-// The launch rule of the STAGED engine's dense fp64 product C = A'B (staged.hip.h): which of its six forms an
-// M x N x K product takes, with how many tiles, and whether it wants a work table / a tile order.  Plain C++ (no device
-// code, no HIP call, no allocation): st_gemm, StagedDev::sk_tab_prepare and hqpkkt_debug_dgemm all decide here, and the
-// CPU tests see the decision through hqpkkt_debug_gemm_form.
+// The launch rule of the STAGED engine's dense fp64 product C = A'B (staged_gemm.hip.h): which of its six forms an
+// M x N x K product takes, with how many tiles, and whether it wants a tile order.  Plain C++ (no device code, no HIP
+// call, no allocation): st_gemm, StagedDev::sk_tab_prepare and hqpkkt_debug_dgemm all decide here, and the CPU tests see
+// the decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a work list; which one is
+// sk_table.hpp's decision (gemm_choose_list), made for the engine's shapes at upload.
 #pragma once
 #include <algorithm>
 
@@ -61,9 +62,9 @@ static inline bool gemm_tiles_6432(int M, int N, int K, int lower, int mirror, i
   return cus > 0 && !lower && !mirror && gemm_tiles(M, N, 64, 0) <= 2LL * cus && K >= 16 * GEMM_BK;
 }
 
-// NONE: nothing to launch, or lower with M < N (lower: a triangle, or the column strip of one).  FRAC: k_dgemm_tn_sk, the
-// k-slabs of all tiles in one sequence, an equal share per workgroup; CUT: k_dgemm_tn_sk by a work table, or whole rounds and
-// the k ranges of the rest cut; PLAIN: one 128 x 128 tile per workgroup (gemm_launch_plain); KS: a thin, deep product on
+// NONE: nothing to launch, or lower with M < N (lower: a triangle, or the column strip of one).  FRAC: k_dgemm_tn_sk by the
+// fractional list, the k-slabs of all tiles in one sequence, an equal share per workgroup; CUT: k_dgemm_tn_sk by a list of
+// whole tiles and cut ones, unequal or equal shares; PLAIN: one 128 x 128 tile per workgroup (gemm_launch_plain); KS: a thin, deep product on
 // 64 x 64 tiles, its k range cut over the chip (k_dgemm_tn_ks); 6432, 6464: 64 x 32 and 64 x 64 tiles
 enum GemmFormKind { GEMM_FORM_NONE = -1, GEMM_FORM_FRAC, GEMM_FORM_CUT, GEMM_FORM_PLAIN, GEMM_FORM_KS, GEMM_FORM_6432, GEMM_FORM_6464 };
 // What the rule depends on besides the shape and the device: one system over several ranks; a launch of the second stream
@@ -99,7 +100,7 @@ static inline GemmForm gemm_form(int M, int N, int K, int lower, int mirror, int
   f.tile_map = !(flags & GEMM_NO_TILE_MAP) && lower && M == N && big && tm >= 16 && tm < 32768;
   if (split && f.tiles <= sk_tiles) {
     // tile count that does not fill the chip evenly: whole rounds, then the k ranges of the rest cut (k_dgemm_tn_sk)
-    f.kind = frac ? GEMM_FORM_FRAC : GEMM_FORM_CUT;  // (CUT: a work table of (tiles, k-slabs) is wanted, StagedDev::sk_tab)
+    f.kind = frac ? GEMM_FORM_FRAC : GEMM_FORM_CUT;  // (both walk a work list of (tiles, k-slabs), StagedDev::sk_tab)
   } else if (big)
     f.kind = GEMM_FORM_PLAIN;
   else if (!(flags & GEMM_NO_KS) && cus > 0 && !lower && !mirror && K >= 512 && f.tiles * 2 <= cus &&

@@ -2,7 +2,7 @@
 // per-class timing, graph capture, and the functions one unit calls in another.  The units:
 //   tree.hip           device residency and kernel sequencing of the tree engine (kernels.hip.h, factor_blk.hip.h,
 //                      solve_top.hip.h), the vector staging of a call, the residual and the posted read-backs
-//   staged_engine.hip  the STAGED engine (staged.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
+//   staged_engine.hip  the STAGED engine (staged.hip.h, staged_gemm.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
 //   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
 //   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
 #pragma once

@@ -1,6 +1,8 @@
-// Host side of the cut form of the STAGED engine's fp64 product (k_dgemm_tn_sk, staged.hip.h): the units of work of
-// every workgroup as a table.  Plain C++ (no device code): used by staged.hip.h and, through hqpkkt_debug_sk_table, by
-// the CPU tests.
+// Host side of the cut form of the STAGED engine's fp64 product (k_dgemm_tn_sk, staged_gemm.hip.h): the kernel walks a
+// list of units of work per workgroup, and every schedule is such a list, made here - unequal shares for the two
+// workgroups of a CU (gemm_split_table), equal shares in whole rounds and cut phases (gemm_equal_table), the k-slabs of
+// all tiles as one sequence (gemm_frac_table) - and chosen in one place (gemm_choose_list).  Plain C++ (no device code):
+// used by staged_gemm.hip.h and the engine's host code and, through hqpkkt_debug_sk_table, by the CPU tests.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -20,7 +22,7 @@ static_assert(sizeof(SkUnit) == 16, "SkUnit is read as one 16-byte word");
 // (profiles/r03_dgemm_stamps.txt, r06_sk_stamps.txt; tiles of 313 k-slabs): of the two workgroups a CU holds, the one
 // dispatched first (class A: blockIdx.x < grid / 2) finishes a tile in ~1000 us and the second (class B) in ~1530 us
 // while both run - the older wavefronts win the arbitration for the matrix pipe -, and a workgroup alone on its CU
-// takes ~700 us.  With equal shares (gemm_split_plan: W = 3 whole tiles + an eighth for everybody) class A is done at
+// takes ~700 us.  With equal shares (gemm_equal_table: W = 3 whole tiles + an eighth for everybody) class A is done at
 // 3090 us and the launch ends when class B is, at 3870 us.  And cut tiles are dear: a plan with 2560 parked pieces
 // instead of 256 takes 4.4 instead of 3.76 ms (tools/sk_sweep.py, profiles/r06_sk_sweep.txt) - the pieces' pipeline
 // fills, their parked sums and workgroups that no longer walk the same k.  So: WHOLE tiles as far as they go, more of
@@ -132,5 +134,127 @@ static inline bool gemm_split_table(long long tiles, long long nslab, int grid, 
   for (int b = 0; b < grid; b++)
     for (size_t i = 0; i < per[b].size(); i++) best.units[(size_t)b * stride + i] = per[b][i];
   return true;
+}
+
+// EQUAL shares: the plan for `tiles` tiles of `nslab` k-slabs on `grid` workgroups.  The remainder R of the whole
+// rounds is cut floor(grid / R) ways; a remainder of more than half a round first gives grid / 2 tiles to
+// two workgroups each (a full phase of half the depth) and cuts the rest after that.  A piece holds at
+// least 16 slabs (below that the pipeline fill of a piece and the parked partial sums cost more than the
+// balance gains) and a tile has at most 16 pieces (the last arriver reads them one after the other).
+struct EqualPlan {
+  int whole;  // the first `whole` tiles (whole rounds of the grid) are computed whole
+  int nphase;
+  int begin[2], count[2], split[2];  // phase q: count[q] tiles from begin[q] on, the k range of each in split[q] pieces
+};
+static inline EqualPlan gemm_split_plan(long long tiles, long long nslab, int grid) {
+  EqualPlan sp{};
+  const long long smax = std::max<long long>(1, std::min<long long>(16, nslab / 16));
+  long long begin = tiles / grid * grid, R = tiles - begin;
+  sp.whole = (int)begin;
+  while (R > 0 && sp.nphase < 2) {
+    long long s = std::min<long long>(smax, grid / R), r = R;
+    if (s <= 1) {
+      s = 1;
+      // (the half round needs an even grid: with an odd one workgroup grid - 1 would start on the next phase's first
+      // unit, which workgroup 0 takes as well)
+      if (sp.nphase == 0 && smax >= 2 && R > grid / 2 && grid % 2 == 0) s = 2, r = grid / 2;
+    }
+    sp.begin[sp.nphase] = (int)begin, sp.count[sp.nphase] = (int)r, sp.split[sp.nphase] = (int)s;
+    sp.nphase++, begin += r, R -= r;
+  }
+  return sp;
+}
+// parked pieces of the plan: the slots of its list (the handle's workspace is sized by this).  A phase that cuts nothing
+// (split 1: an odd grid, or too few k-slabs for two pieces) parks nothing
+static inline long long gemm_split_plan_pieces(const EqualPlan &sp) {
+  long long n = 0;
+  for (int q = 0; q < sp.nphase; q++) n += sp.split[q] > 1 ? (long long)sp.count[q] * sp.split[q] : 0;
+  return n;
+}
+// rows of workgroups (by blockIdx.x) -> a table with an end mark behind every row
+static inline void sk_table_pack(const std::vector<std::vector<SkUnit>> &per, long long pieces, SplitTable &out) {
+  size_t stride = 1;
+  for (const auto &row : per) stride = std::max(stride, row.size() + 1);
+  out = SplitTable{};
+  out.stride = (int)stride, out.pieces = pieces;
+  out.units.assign(per.size() * stride, SkUnit{-1, 0, 0, 0, 0, 0});
+  for (size_t b = 0; b < per.size(); b++) std::copy(per[b].begin(), per[b].end(), out.units.begin() + b * stride);
+}
+// The plan as a list.  Units: the whole tiles of the rounds (unit u = tile u), then the pieces of the cut phases (phase q:
+// unit j * count[q] + ti = piece j of its tile ti).  The workgroup at position v (after the XCD swizzle) does unit v of
+// every round and phase: its neighbours in the XCD work on the neighbouring tiles at the same k and share their operand
+// panels in that XCD's L2 (a contiguous range of (tile, k-slab) units per workgroup balances as well but leaves the
+// workgroups at as many different k, and the launch then runs at the speed of its operand reads).
+static inline bool gemm_equal_table(long long tiles, long long nslab, int grid, SplitTable &out) {
+  if (grid < 1 || nslab < 1 || nslab >= 65536 || tiles <= 0) return false;
+  const EqualPlan sp = gemm_split_plan(tiles, nslab, grid);
+  std::vector<std::vector<SkUnit>> per(grid);
+  for (int b = 0; b < grid; b++) {
+    const int v = xcd_swizzle_host(b, grid);
+    for (long long u = v; u < sp.whole; u += grid) per[b].push_back(SkUnit{(int)u, 0, (unsigned short)nslab, 0, 1, 0});
+    long long slots = 0;  // (of the phases before q)
+    for (int q = 0; q < sp.nphase; q++) {
+      const long long cnt = sp.count[q], pieces = sp.split[q], slot_q = slots;
+      if (pieces > 1) slots += cnt * pieces;
+      if (v >= cnt * pieces) continue;
+      const long long ti = v % cnt, j = v / cnt, L = (nslab + pieces - 1) / pieces;
+      const long long s0 = std::min(nslab, j * L), s1 = std::min(nslab, s0 + L);
+      per[b].push_back(SkUnit{sp.begin[q] + (int)ti, (unsigned short)s0, (unsigned short)s1, (int)(pieces > 1 ? slot_q + ti * pieces : 0),
+                              (unsigned short)pieces, (unsigned short)j});
+    }
+  }
+  sk_table_pack(per, gemm_split_plan_pieces(sp), out);
+  return true;
+}
+// The FRACTIONAL cut: the tiles' k-slabs in one sequence (tile t holds the units t nslab ...), cut into `per` units per
+// workgroup - the workgroup at position v takes [v per, (v + 1) per): the end of one tile, whole tiles, the start of
+// another.  A tile that several workgroups share is summed by its last arriver in the order of the workgroups; a
+// workgroup parks at most two partial tiles, so the list has at most 2 grid slots.  For products of a few hundred tiles
+// (stages of 1000 - 3000 states), where whole rounds and cut remainders leave a large part of the chip idle.
+static inline bool gemm_frac_table(long long tiles, long long nslab, int grid, SplitTable &out) {
+  if (grid < 1 || nslab < 1 || nslab >= 65536 || tiles <= 0) return false;
+  const long long U = tiles * nslab, share = (U + grid - 1) / grid;
+  auto sharers = [&](long long t, long long &first) {  // the workgroups whose ranges meet tile t
+    first = t * nslab / share;
+    return ((t + 1) * nslab - 1) / share - first + 1;
+  };
+  std::vector<long long> slot0(tiles, 0);
+  long long slots = 0, first;
+  for (long long t = 0; t < tiles; t++) {
+    const long long pieces = sharers(t, first);
+    if (pieces > 1) slot0[t] = slots, slots += pieces;
+  }
+  std::vector<std::vector<SkUnit>> per(grid);
+  for (int b = 0; b < grid; b++) {
+    const long long v = xcd_swizzle_host(b, grid), lo = std::min(U, v * share), hi = std::min(U, lo + share);
+    for (long long x = lo; x < hi;) {
+      const long long t = x / nslab, s0 = x - t * nslab, s1 = std::min(nslab, s0 + (hi - x)), pieces = sharers(t, first);
+      per[b].push_back(SkUnit{(int)t, (unsigned short)s0, (unsigned short)s1, (int)slot0[t], (unsigned short)pieces, (unsigned short)(v - first)});
+      x += s1 - s0;
+    }
+  }
+  sk_table_pack(per, slots, out);
+  return true;
+}
+
+// Which list a launch of the cut forms walks - decided here alone, for the engine (StagedDev::sk_tab_prepare, at upload)
+// and for the self-test (hqpkkt_debug_dgemm).  SK_LIST_NONE: no list whose parked pieces fit the workspace of `ws_elems`
+// doubles - the launch is a plain round of whole tiles instead.
+// `frac`: the launch rule gave the fractional form (gemm_form.hpp).  Otherwise the unequal shares, unless they are
+// switched off (HQPKKT_SK_TABLE=0), the system is sharded over several ranks - there the strip's product runs beside the
+// second stream's control-sized chain, and the pace of the two workgroups of a CU that the shares are fitted to is not
+// the one measured for a launch that has the chip to itself - or they do not build or fit; then the equal shares.
+enum SkList { SK_LIST_NONE = -1, SK_LIST_UNEQUAL = 0, SK_LIST_EQUAL = 1, SK_LIST_FRAC = 2 };
+static inline bool gemm_list_table(int list, long long tiles, long long nslab, int grid, SplitTable &t) {
+  return list == SK_LIST_UNEQUAL ? gemm_split_table(tiles, nslab, grid, t)
+         : list == SK_LIST_EQUAL ? gemm_equal_table(tiles, nslab, grid, t)
+                                 : list == SK_LIST_FRAC && gemm_frac_table(tiles, nslab, grid, t);
+}
+static inline int gemm_choose_list(bool frac, bool unequal, long long tiles, long long nslab, int grid, long long sk_tiles, long long ws_elems,
+                                   SplitTable &t) {
+  const long long slot = 128LL * 128;
+  if (frac) return gemm_frac_table(tiles, nslab, grid, t) && t.pieces * slot <= ws_elems ? SK_LIST_FRAC : SK_LIST_NONE;
+  if (unequal && gemm_split_table(tiles, nslab, grid, t) && t.pieces * slot <= ws_elems && tiles <= sk_tiles) return SK_LIST_UNEQUAL;
+  return gemm_equal_table(tiles, nslab, grid, t) && t.pieces * slot <= ws_elems ? SK_LIST_EQUAL : SK_LIST_NONE;
 }
 }  // namespace stg

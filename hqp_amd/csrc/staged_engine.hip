@@ -346,33 +346,26 @@ __global__ void k_gemm_count_asym(stg::GemmArgs g, unsigned long long *count) {
   if (__double_as_longlong(g.C[(long long)i * g.ldc + j]) != __double_as_longlong(g.C[(long long)j * g.ldc + i])) atomicAdd(count, 1ULL);
 }
 // HQPKKT_DGEMM_STAMPS: one more launch of the product with time stamps (100 MHz constant clock), printed to stderr
-static void dgemm_stamps_split(const stg::GemmArgs &g, const stg::GemmForm &f, int variant, int skg, const stg::SplitTable &sk_tab, const stg::SkUnit *tab_dev) {
+static void dgemm_stamps_split(const stg::GemmArgs &g, const stg::GemmForm &f, int variant, int skg, int list, const stg::SplitTable &sk_tab, const stg::SkUnit *tab_dev) {
   // the split form with time stamps: per workgroup its start and, per unit, the end of the k loop, of the
   // parking / summing of partial tiles and of the epilogue (us after the first start)
   DBuf<unsigned long long> st;
   DBuf<double> ws2;
   DBuf<unsigned> cnt2;
-  if (st.alloc(32 * (size_t)skg) || ws2.alloc((size_t)(16 * f.tiles + 8) * 128 * 128) || cnt2.alloc(f.tiles + 4)) return;
+  if (st.alloc(32 * (size_t)skg) || ws2.alloc((size_t)std::max<long long>(sk_tab.pieces, 1) * 128 * 128) || cnt2.alloc(f.tiles + 4)) return;
   (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 32 * skg);
   (void)hipMemset(cnt2.p, 0, sizeof(unsigned) * (f.tiles + 4));
   stg::GemmArgs gs = g;
   gs.stamps = st.p;
-  stg::SplitPlan skk = stg::gemm_split_plan(f.tiles, stg::gemm_slabs(g.K), skg);
-  skk.ws = ws2.p, skk.cnt = cnt2.p;
-  if (tab_dev) skk.table = tab_dev, skk.stride = sk_tab.stride;
-  stg::gemm_launch_split(variant, skg, 0, gs, skk);
+  stg::gemm_launch_split(variant, skg, 0, gs, stg::SplitPlan{ws2.p, cnt2.p, tab_dev, sk_tab.stride});
   std::vector<unsigned long long> hs(32 * (size_t)skg);
   if (hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * 32 * skg, hipMemcpyDeviceToHost) != hipSuccess) return;
   unsigned long long tmin = ~0ULL;
   for (int w = 0; w < skg; w++) tmin = std::min(tmin, hs[32 * (size_t)w]);
-  if (tab_dev)
-    fprintf(stderr, "table plan: %d / %d whole tiles per first / second workgroup of a CU, %lld parked pieces", sk_tab.nA, sk_tab.nB, sk_tab.pieces);
-  else {
-    fprintf(stderr, "split plan: %d whole tiles", skk.whole);
-    for (int q = 0; q < skk.nphase; q++) fprintf(stderr, ", %d tiles x %d pieces", skk.count[q], skk.split[q]);
-  }
+  fprintf(stderr, "%s shares: %lld parked pieces", list == stg::SK_LIST_UNEQUAL ? "unequal" : "equal", sk_tab.pieces);
+  if (list == stg::SK_LIST_UNEQUAL) fprintf(stderr, ", %d / %d whole tiles per first / second workgroup of a CU", sk_tab.nA, sk_tab.nB);
   fprintf(stderr, "; stamps of every %dth workgroup (us): start | per unit: k loop end, parked / summed, epilogue end\n", std::max(1, skg / 32));
-  const int nr = tab_dev ? std::min(10, sk_tab.stride - 1) : std::min(5, skk.dp_rounds + skk.nphase);
+  const int nr = std::min(10, sk_tab.stride - 1);
   for (int w = 0; w < skg; w += std::max(1, skg / 32)) {
     fprintf(stderr, "  wg %4d: %7.2f |", w, (hs[32 * (size_t)w] - tmin) * 0.01);
     for (int r = 0; r < nr; r++) {
@@ -471,21 +464,21 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   if (K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
   (void)stg::gemm_set_attributes();
   if (use_sk && (skws.alloc((size_t)ws_elems) || skcnt.alloc(f.tiles + 4))) return HQPKKT_E_MEM;
-  // (the cut form by a table with unequal shares for the two workgroups of a CU: gemm_split_table; HQPKKT_SK_TABLE=0: equal shares)
+  // (its one list by the engine's chooser: unequal shares for the two workgroups of a CU, HQPKKT_SK_TABLE=0: equal shares)
   stg::SplitTable sk_tab;
-  if (f.kind == stg::GEMM_FORM_CUT && stg::gemm_sk_table_from_env() && stg::gemm_split_table(f.tiles, nslab, skg, sk_tab) && sk_tab.pieces <= 16 * f.tiles + 8 &&
-      sk_table_dev.upload(sk_tab.units))
-    return HQPKKT_E_MEM;
+  int list = stg::SK_LIST_NONE;
+  if (use_sk) {
+    list = stg::gemm_choose_list(frac, stg::gemm_sk_table_from_env(), f.tiles, nslab, skg, t128, ws_elems, sk_tab);
+    if (list == stg::SK_LIST_NONE) return HQPKKT_E_RANGE;
+    if (sk_table_dev.upload(sk_tab.units)) return HQPKKT_E_MEM;
+  }
   EventOwner e0, e1;
   (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
     if (r == 0) (void)hipEventRecord(e0, 0);
     if (use_sk) {
       (void)hipMemsetAsync(skcnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
-      stg::SplitPlan skk = frac ? stg::gemm_split_plan_frac(f.tiles, nslab, skg) : stg::gemm_split_plan(f.tiles, nslab, skg);
-      skk.ws = skws.p, skk.cnt = skcnt.p;
-      if (sk_table_dev.p) skk.table = sk_table_dev.p, skk.stride = sk_tab.stride;
-      stg::gemm_launch_split(variant, skg, 0, g, skk);
+      stg::gemm_launch_split(variant, skg, 0, g, stg::SplitPlan{skws.p, skcnt.p, sk_table_dev.p, sk_tab.stride});
     } else if (f.kind == stg::GEMM_FORM_PLAIN)
       stg::gemm_launch_plain(variant, (unsigned)f.tiles, 0, g, cus);
     else if (f.kind == stg::GEMM_FORM_6432)
@@ -500,7 +493,7 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   (void)hipEventElapsedTime(&t, e0, e1);
   if (se != hipSuccess) return HQPKKT_E_DEVICE;
   if (getenv("HQPKKT_DGEMM_STAMPS")) {
-    if (f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, f, variant, skg, sk_tab, sk_table_dev.p);
+    if (f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, f, variant, skg, list, sk_tab, sk_table_dev.p);
     if (f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(g, f.tiles, variant);
   }
   k_gemm_check<<<16, 256>>>(g, 4096, err.p);
@@ -535,9 +528,9 @@ int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, 
   return f.kind;
 }
 
-int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {
+int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int kind, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {
   stg::SplitTable t;
-  if (!stg::gemm_split_table(tiles, nslab, grid, t)) return 0;
+  if (!stg::gemm_list_table(kind, tiles, nslab, grid, t)) return 0;
   if (pieces) *pieces = t.pieces;
   if (whole_a) *whole_a = t.nA;
   if (whole_b) *whole_b = t.nB;

@@ -53,7 +53,7 @@ struct StagedDev {
   int cus = 0;
   DBuf<double> ks_ws2;          // the pieces of a thin product cut in k (k_dgemm_tn_ks) launched on the SECOND stream
   long long ks_ws2_elems = 0;
-  DBuf<double> sk_ws;           // stream-K dgemm: two partial tiles per workgroup
+  DBuf<double> sk_ws;           // the cut forms of the dgemm: parked partial tiles (SkUnit::slot0)
   DBuf<unsigned> sk_cnt;
   int sk_grid = 0;              // workgroups of the stream-K grid (2 per CU); 0: not used
   int sk_tiles = 0;             // most tiles a product of this handle has (size of the counter array)
@@ -86,43 +86,44 @@ struct StagedDev {
     tri_maps.emplace_back(T, std::move(b));
     return tri_maps.back().second.p;
   }
-  // work lists of the cut form of the large products (stg::gemm_split_table: unequal shares for the two workgroups of a
-  // CU), by (tiles, k-slabs); made at upload time for the shapes of the recursion - a shape without one (or
-  // HQPKKT_SK_TABLE=0) runs the equal-share plan
+  // work lists of the cut forms of the large products (sk_table.hpp), by (tiles, k-slabs, form): made at upload for every
+  // shape the recursion launches on the first stream (staged_prepare_products) and only looked up at launch, so an
+  // eager and a captured run of a handle take the same schedule.  list: which one stg::gemm_choose_list gave the shape;
+  // SK_LIST_NONE: no list fits the workspace - the launch is a plain round of whole tiles
   struct SkTab {
-    long long tiles, nslab, pieces;
-    int stride;
+    long long tiles, nslab;
+    int form, list, stride;
     DBuf<stg::SkUnit> units;
   };
   std::vector<SkTab> sk_tabs;
-  bool sk_tables_on = true;
-  const SkTab *sk_tab(long long tiles, long long nslab, bool create = false) {
-    if (!sk_tables_on || sk_grid <= 0) return nullptr;
+  bool sk_tables_on = true;  // HQPKKT_SK_TABLE
+  const SkTab *sk_tab(long long tiles, long long nslab, int form) const {
     for (auto &e : sk_tabs)
-      if (e.tiles == tiles && e.nslab == nslab) return e.units.p ? &e : nullptr;
-    if (!create) return nullptr;  // (no allocation inside a captured sequence)
-    stg::SplitTable t;
-    SkTab e{tiles, nslab, 0, 0, {}};
-    if (stg::gemm_split_table(tiles, nslab, sk_grid, t) && t.pieces * 128LL * 128 <= sk_ws_elems && tiles <= sk_tiles) {
-      if (!e.units.upload(t.units))
-        e.stride = t.stride, e.pieces = t.pieces;
-      else
-        e.units.release();
-    }
-    sk_tabs.push_back(std::move(e));
-    return sk_tabs.back().units.p ? &sk_tabs.back() : nullptr;
+      if (e.tiles == tiles && e.nslab == nslab && e.form == form) return &e;
+    return nullptr;
   }
   // the form the launch rule (gemm_form.hpp) gives a product of this handle
   stg::GemmForm gemm_form(int M, int N, int K, int lower, int mirror, bool first_stream = true) const {
     return stg::gemm_form(M, N, K, lower, mirror, cus, sk_grid, sk_tiles, sk_ws_elems, ks_ws2_elems,
                           (plan.sharded ? stg::GEMM_SHARDED : 0) | (first_stream ? 0 : stg::GEMM_SECOND_STREAM));
   }
-  // (the shape of a product as st_gemm launches it on the first stream)
-  // (K2: the second k segment of the launch that forms V_k)
-  void sk_tab_prepare(int M, int N, int K, int lower, int K2 = 0) {
+  // the list of a product as st_gemm launches it on the first stream, where its form walks one
+  // (K2: the second k segment of the launch that forms V_k; ntiles > 0: a launch of that many tiles out of a list)
+  int sk_tab_prepare(int M, int N, int K, int lower, int K2 = 0, int ntiles = 0) {
+    if (M <= 0 || N <= 0) return 0;
     const long long nslab = stg::gemm_slabs(K) + (K2 > 0 ? stg::gemm_slabs(K2) : 0);
-    const stg::GemmForm f = gemm_form(M, N, K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K, lower, K2 > 0);
-    if (f.kind == stg::GEMM_FORM_CUT) (void)sk_tab(f.tiles, nslab, true);
+    const int Kf = K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K;
+    const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, Kf, sk_grid, sk_tiles) : gemm_form(M, N, Kf, lower, K2 > 0);
+    if ((f.kind != stg::GEMM_FORM_CUT && f.kind != stg::GEMM_FORM_FRAC) || sk_tab(f.tiles, nslab, f.kind)) return 0;
+    stg::SplitTable t;
+    SkTab e{f.tiles, nslab, f.kind, 0, 0, {}};
+    e.list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles, nslab, sk_grid, sk_tiles, sk_ws_elems, t);
+    if (e.list != stg::SK_LIST_NONE) {
+      if (int err = e.units.upload(t.units)) return err;
+      e.stride = t.stride;
+    }
+    sk_tabs.push_back(std::move(e));
+    return 0;
   }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
   long long sk_ws_elems = 0, sk_cnt_elems = 0;
@@ -194,18 +195,17 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
   switch (f.kind) {
     case stg::GEMM_FORM_FRAC:
     case stg::GEMM_FORM_CUT: {
-      // whole rounds, then the k ranges of the rest cut - by the shape's work table where there is one -, or the k-slabs
-      // of all tiles in one sequence (the arrival counters are zero between launches: the last arriver of a tile resets its)
-      const bool frac = f.kind == stg::GEMM_FORM_FRAC;
-      stg::SplitPlan sk = frac ? stg::gemm_split_plan_frac(f.tiles, nslab, d.sk_grid) : stg::gemm_split_plan(f.tiles, nslab, d.sk_grid);
-      const StagedDev::SkTab *tab = frac ? nullptr : d.sk_tab(f.tiles, nslab, !h->capturing);
-      if (tab) sk.table = tab->units.p, sk.stride = tab->stride;
-      if (frac || tab || stg::gemm_split_plan_pieces(sk) * 128LL * 128 <= d.sk_ws_elems) {
-        sk.ws = d.sk_ws.p, sk.cnt = d.sk_cnt.p;
+      // the list the shape was given at upload (the arrival counters are zero between launches: the last arriver of a
+      // tile resets its).  A shape that upload did not prepare is a hole in staged_prepare_products, not a reason to
+      // take another schedule
+      const StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
+      if (!tab) return HQPKKT_E_INTERN;
+      if (tab->list != stg::SK_LIST_NONE) {
+        const stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, tab->units.p, tab->stride};
         KLAUNCH(h, cls, stg::gemm_launch_split(variant, d.sk_grid, h->stream, g, sk));
         break;
       }
-      [[fallthrough]];  // (the workspace does not hold the plan's pieces: a plain round)
+      [[fallthrough]];  // (the workspace holds no list's pieces: a plain round)
     }
     case stg::GEMM_FORM_PLAIN:
       KLAUNCH(h, cls, stg::gemm_launch_plain(variant, (unsigned)f.tiles, h->stream, g, d.cus));
@@ -539,6 +539,7 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   return 0;
 }
 
+static int staged_prepare_products(StagedDev &d);  // (beside the sequences it mirrors, below)
 static int staged_upload(hqpkkt_t *h) {
   int e = ensure_device(h);
   if (e) return e;
@@ -641,9 +642,9 @@ static int staged_upload(hqpkkt_t *h) {
     }
     if (P.sharded)
       for (int k = 0; k < P.K; k++) tmax = std::max<long long>(tmax, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
-    // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every launch
-    // checks its pieces against the workspace.  Until round 5 the workspace was sized 16 pieces per tile of the largest
-    // product - 3.4 GB at the headline width, per handle, sharded or not)
+    // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every list
+    // is checked against the workspace when it is made, gemm_choose_list.  Until round 5 the workspace was sized 16
+    // pieces per tile of the largest product - 3.4 GB at the headline width, per handle, sharded or not)
     pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
     d.sk_grid = 0, d.sk_tiles = (int)tmax;
     if (cus > 0) {
@@ -780,16 +781,9 @@ static int staged_upload(hqpkkt_t *h) {
       const int T = (sz + 127) / 128;
       if (T >= 16) (void)d.tri_map(T, true);
     }
-  // work lists of the cut form of W = V+ F and G = F'W (staged_stage: the products over all columns, over the state
-  // columns alone when the control-sized chain runs beside them)
+  // work lists of the cut forms of the recursion's products
   d.sk_tables_on = stg::gemm_sk_table_from_env();
-  if (!P.sharded)
-    for (int k = 0; k < P.K; k++) {
-      const int np = P.nk[k + 1], nn = P.nk[k], nz = nn + P.mk[k];
-      d.sk_tab_prepare(np, nz, np, 0), d.sk_tab_prepare(np, nn, np, 0);
-      d.sk_tab_prepare(nz, nz, np, 1), d.sk_tab_prepare(nn, nn, np, 1);
-      if (d.fused[k]) d.sk_tab_prepare(nn, nn, np, 1, P.qmax[k]);
-    }
+  if ((e = staged_prepare_products(d))) return e;
   d.lds_small = 0, d.lds_small_big = 0;
   for (int k = 0; k < P.K; k++) {
     if (P.big[k])
@@ -1101,6 +1095,46 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
                                  stg::SpCarried{f, sn.BT, P.ldb[k + 1], cx, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
   if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+}
+
+// The products of the sequences above and of staged_run_factor below, shape by shape, for StagedDev::sk_tab_prepare (at
+// upload): a launch of a cut form walks the list made here, and st_gemm refuses a shape that has none.  Every st_gemm that
+// can run on the first stream appears, whatever form the rule (gemm_form.hpp) gives it today - also those a stage puts on
+// the second stream when its chain runs beside the large product -, so a product added to a sequence is added here.
+static int staged_prepare_products(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  int e = 0;
+  auto prep = [&](int M, int N, int K, int lower = 0, int K2 = 0, int ntiles = 0) {
+    if (!e) e = d.sk_tab_prepare(M, N, K, lower, K2, ntiles);
+  };
+  // st_blk_sweep over a control-sized matrix of order q, and the product that checks its inverse
+  auto sweep = [&](int q) { prep(64, q, 64), prep(q, q, 64), prep(q, q, q); };
+  d.sk_tabs.clear();
+  for (int k = 0; k < P.K; k++) {
+    const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm, q = P.qmax[k], cx = P.cap[k + 1];
+    if (P.sharded) {  // staged_stage_sharded
+      const int *cut = &P.xcut[(size_t)k * (P.shard_count + 1)];
+      const int wd = cut[P.shard_rank + 1] - cut[P.shard_rank];
+      prep(np, mm, np);                                         // W_u
+      for (int M : {mm, cx}) prep(M, nn, np), prep(M, mm, np);  // `thin`: the control rows of G, the carried rows
+      prep(np, wd, np);                                         // the strip of W
+      prep(wd, nn, np, 0, 0, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);  // the rank's blocks of G_xx: a tile list
+    } else if (!P.sparse_dyn) {  // staged_stage_fused, the stage of staged_run_factor
+      prep(np, nz, np);  // W
+      prep(mm, nz, np);  // the control rows of G
+      prep(cx, nz, np);  // the carried rows
+      if (d.fused[k])
+        prep(nn, nn, np, 1, q);  // V_k in the G_xx launch
+      else
+        prep(nz, nz, np, 1), prep(nn, nn, np, 1);  // G; G_xx when the chain runs beside it
+    }
+    // st_eliminate: the blocked sweep, Rm and its refinement for K of order > 64
+    if (P.big[k]) sweep(q);
+    if (q > 64) prep(q, nn, q);
+    if (!d.fused[k]) prep(nn, nn, q, 1);  // the rank-q update V = G_xx - Y'Rm (lower, mirrored)
+  }
+  if (P.big0) sweep(P.q0max);  // the initial state's matrix (staged_run_factor)
+  return e;
 }
 
 // Hqp_IpLQDOCP::factor (hqp/Hqp_IpLQDOCP.C:796-862): W^-1 Z, C'(W^-1 Z)C, then the backward

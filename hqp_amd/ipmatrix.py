@@ -461,16 +461,21 @@ def bench_dgemm2(M, N, K, K2, lower=True, mirror=True, reps=1, device=0):
     return ms.value, err.value, asym.value
 
 
-def sk_table(tiles, nslab, grid=512):
-    """The work lists of the cut form of the fp64 product (host only): (units[grid, stride, 6], pieces, whole_a, whole_b),
-    a unit = (tile or -1, first k-slab, one past the last, first parking slot of the tile, pieces of the tile, piece)."""
+SK_KINDS = ("unequal", "equal", "frac")
+
+
+def sk_table(tiles, nslab, grid=512, kind="unequal"):
+    """A work list of the cut forms of the fp64 product (host only): (units[grid, stride, 6], pieces, whole_a, whole_b),
+    a unit = (tile or -1, first k-slab, one past the last, first parking slot of the tile, pieces of the tile, piece).
+    kind: unequal shares for the two workgroups of a CU, equal shares in rounds and phases, or the fractional cut."""
     import numpy as np
+    k = SK_KINDS.index(kind)
     pieces, wa, wb = C.c_longlong(), C.c_int(), C.c_int()
-    stride = _lib.lib().hqpkkt_debug_sk_table(tiles, nslab, grid, None, 0, C.byref(pieces), C.byref(wa), C.byref(wb))
+    stride = _lib.lib().hqpkkt_debug_sk_table(tiles, nslab, grid, k, None, 0, C.byref(pieces), C.byref(wa), C.byref(wb))
     if stride <= 0:
         return None
     u = np.zeros((grid, stride, 6), dtype=np.int32)
-    got = _lib.lib().hqpkkt_debug_sk_table(tiles, nslab, grid, u.ctypes.data_as(C.POINTER(C.c_int)), u.size, C.byref(pieces), C.byref(wa), C.byref(wb))
+    got = _lib.lib().hqpkkt_debug_sk_table(tiles, nslab, grid, k, u.ctypes.data_as(C.POINTER(C.c_int)), u.size, C.byref(pieces), C.byref(wa), C.byref(wb))
     assert got == stride
     return u, pieces.value, wa.value, wb.value
 

@@ -369,13 +369,16 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
  * that are not bit-identical to their mirror image. */
 int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym);
 
-/* Test hook, host only (no device needed): the work list of the cut form of that product (k_dgemm_tn_sk) for `tiles`
- * tiles of `nslab` k-slabs on `grid` workgroups - unequal shares for the two workgroups of a CU, sk_table.hpp.
- * units (or NULL): six ints per unit, (b * stride + i) * 6 for unit i of workgroup b: tile (-1: end of the list),
- * first and one-past-last k-slab, first parking slot of the tile, pieces of the tile, number of this piece.
- * Returns the stride (units per workgroup incl. the end mark), or 0 (no table for these sizes; cap_ints too small).
- * *pieces: parking slots; *whole_a / *whole_b: whole tiles per workgroup of the first / second half of the launch. */
-int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b);
+/* Test hook, host only (no device needed): a work list of the cut forms of that product (k_dgemm_tn_sk walks one list
+ * per workgroup, whatever the schedule) for `tiles` tiles of `nslab` k-slabs on `grid` workgroups, sk_table.hpp.
+ * kind 0: unequal shares for the two workgroups of a CU; 1: equal shares, whole rounds and cut phases; 2: the fractional
+ * cut, the k-slabs of all tiles as one sequence.
+ * units (or NULL): six ints per unit, (b * stride + i) * 6 for unit i of workgroup b (blockIdx.x): tile (-1: end of the
+ * list), first and one-past-last k-slab, first parking slot of the tile, pieces of the tile, number of this piece.
+ * Returns the stride (units per workgroup incl. the end mark), or 0 (no list for these sizes; cap_ints too small).
+ * *pieces: parking slots; *whole_a / *whole_b (kind 0; else 0): whole tiles per workgroup of the first / second half of
+ * the launch. */
+int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int kind, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b);
 
 /* Test hook, host only: the form the STAGED engine's launch rule (gemm_form.hpp) gives an M x N x K product on a device
  * of `cus` CUs with a split grid of `grid` workgroups (0: none), arrival counters for sk_tiles tiles and workspaces of

@@ -477,6 +477,41 @@ def test_large_dgemm_kernels_against_exact_products(waves, monkeypatch):
         assert err <= 1e-14, (waves, M, N, K, lower, mirror, err)
 
 
+@pytest.mark.parametrize("table", ["1", "0"])
+def test_every_schedule_of_the_cut_product_walks_its_list(table, monkeypatch):
+    """k_dgemm_tn_sk has one body, which walks the list the host made for the launch (sk_table.hpp): the smallest shapes that
+    take each schedule on a grid of two workgroups per CU - the fractional cut (169 tiles of 64 k-slabs); the cut form (380
+    tiles of 33 slabs, the last one ragged) by unequal shares and, HQPKKT_SK_TABLE=0, by equal ones; the same lower and
+    mirrored (406 tiles), exactly symmetric; and that with a second k segment, a cut piece across the boundary.  Criterion of
+    the tests above: 4096 sample entries against exactly accumulated sums."""
+    import torch
+    monkeypatch.setenv("HQPKKT_SK_TABLE", table)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def form(M, N, K, lower, mirror):
+        return ipmatrix.gemm_form(M, N, K, lower, mirror, cus=cus, grid=2 * cus, no_ks=True, no_tile_map=True)[0]
+
+    if table == "1":  # (the fractional list does not depend on the switch)
+        assert form(1664, 1664, 1024, 0, 0) == "frac"
+        ms, tf, err = ipmatrix.bench_dgemm(1664, 1664, 1024, 0, 0, reps=1)
+        print(f"frac 1664 x 1664 x 1024: err {err:.2e}")
+        assert err <= 1e-14, err
+    assert form(2432, 2560, 520, 0, 0) == "cut"
+    ms, tf, err = ipmatrix.bench_dgemm(2432, 2560, 520, 0, 0, reps=1)
+    print(f"cut 2432 x 2560 x 520, HQPKKT_SK_TABLE={table}: err {err:.2e}")
+    assert err <= 1e-14, (table, err)
+    for k2 in (0, 40):
+        nslab = 33 + (k2 + 15) // 16
+        assert form(3500, 3500, 16 * nslab, 1, 1) == "cut"
+        if k2 and table == "0":  # (equal shares cut every tile in two; the unequal ones may leave all 406 whole)
+            units = ipmatrix.sk_table(406, nslab, 2 * cus, kind="equal")[0].reshape(-1, 6)
+            assert ((units[:, 0] >= 0) & (units[:, 4] > 1) & (units[:, 1] < 33) & (units[:, 2] > 33)).any()
+        ms, err, asym = ipmatrix.bench_dgemm2(3500, 3500, 528, k2, lower=True, mirror=True, reps=1)
+        print(f"cut 3500 x 3500 x 528 + {k2}, lower + mirror, HQPKKT_SK_TABLE={table}: err {err:.2e}, asymmetric entries {asym}")
+        assert err <= 1e-14, (table, k2, err)
+        assert asym == 0, (table, k2, asym)
+
+
 def test_staged_mehrotra_loop():
     """The device-resident interior-point loop on top of the STAGED engine: same optimiser as
     with the reduced full-system engine."""

@@ -175,11 +175,12 @@ def test_column_cuts_of_a_sharded_system(world):
 
 
 def test_fractional_cut_partition_properties():
-    """The index arithmetic of the fractional cut (k_dgemm_tn_sk with SplitPlan::frac, hqp_amd/csrc/staged.hip.h) restated in
-    Python: the k-slabs of all tiles as one sequence, `per` units per workgroup.  Every unit is computed exactly once; a
-    tile's sharers are consecutive workgroups w_first .. w_last and their k ranges follow each other in that order (the
-    order in which the last arriver adds the parked pieces); a workgroup parks at most two partial tiles and no two
-    pieces share a slot (2 w: the tile its range starts in, 2 w + 1: the tile it ends in)."""
+    """The index arithmetic of the fractional cut (gemm_frac_table, hqp_amd/csrc/sk_table.hpp) restated in Python: the
+    k-slabs of all tiles as one sequence, `per` units per workgroup.  Every unit is computed exactly once; a tile's sharers
+    are consecutive workgroups w_first .. w_last and their k ranges follow each other in that order (the order in which the
+    last arriver adds the parked pieces); a workgroup parks at most two partial tiles, so 2 grid slots hold every piece -
+    shown here with the slots 2 w (the tile its range starts in) and 2 w + 1 (the tile it ends in); the list itself numbers
+    a tile's pieces one after the other (tests/test_sk_table_cpu.py)."""
     for tiles, nslab, grid in ((272, 125, 512), (300, 188, 512), (200, 313, 512), (160, 64, 512), (320, 400, 512), (7, 64, 512), (45, 63, 512)):
         U = tiles * nslab
         per = (U + grid - 1) // grid

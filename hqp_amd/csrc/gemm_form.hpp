@@ -1,8 +1,8 @@
 // The launch rule of the STAGED engine's dense fp64 product C = A'B (staged_gemm.hip.h): which of its six forms an
 // M x N x K product takes, with how many tiles, and whether it wants a tile order.  Plain C++ (no device code, no HIP
-// call, no allocation): st_gemm, StagedDev::sk_tab_prepare and hqpkkt_debug_dgemm all decide here, and the CPU tests see
-// the decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a work list; which one is
-// sk_table.hpp's decision (gemm_choose_list), made for the engine's shapes at upload.
+// call, no allocation): st_gemm - at a launch and in upload's dry walk of the factor sequence - and hqpkkt_debug_dgemm
+// decide here, and the CPU tests see the decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a
+// work list; which one is sk_table.hpp's decision (gemm_choose_list), made for the engine's shapes at upload.
 #pragma once
 #include <algorithm>
 

@@ -218,6 +218,7 @@ struct Prof {
 };
 #define KLAUNCH(h, c, ...)        \
   do {                            \
+    if ((h)->listing) break;      \
     (h)->prof.begin(c, (h)->stream); \
     __VA_ARGS__;                  \
     (h)->prof.end((h)->stream);   \
@@ -364,6 +365,9 @@ struct hqpkkt {
     return cache.back().g;
   }
   bool use_graphs = true, capturing = false;
+  // staged_upload's dry walk of the factor sequence: st_gemm makes the work lists and tile orders its launches will look
+  // up; KLAUNCH, the stream pairs, the timing records and exchange() do nothing
+  bool listing = false;
   unsigned cap_posts = 0;  // posted read-backs of the capture in progress
   // inside hqpkkt_mehrotra: factor() returns without waiting for its status (read with the
   // residual of the solve that follows), solve() leaves its result in the stream

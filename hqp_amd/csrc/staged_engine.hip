@@ -52,7 +52,7 @@ void staged_reset(StagedDev &d) {
   d.plan = std::move(plan);
 }
 
-// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 37); the handle is in HQPKKT_MODE_STAGED and analysed
+// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 38); the handle is in HQPKKT_MODE_STAGED and analysed
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
   if (!h->sd) return HQPKKT_E_INTERN;
   const kktdev::StagedPlan &P = h->sd->plan;
@@ -116,6 +116,11 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
               // the CSR arrays of A' (rows ascending inside a column) per column of the stages k < K; empty on a dense-form handle
       out = P.sp_arow;
       out.insert(out.end(), P.sp_tcol.begin(), P.sp_tcol.end());
+      break;
+    case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
+              // (stg::SK_LIST_*), launches that looked it up since
+      for (const StagedDev::SkTab &t : h->sd->sk_tabs)
+        for (int val : {(int)t.tiles, (int)t.nslab, t.form, t.list, t.hits}) out.push_back(val);
       break;
     default: return HQPKKT_E_RANGE;
   }

@@ -86,18 +86,19 @@ struct StagedDev {
     tri_maps.emplace_back(T, std::move(b));
     return tri_maps.back().second.p;
   }
-  // work lists of the cut forms of the large products (sk_table.hpp), by (tiles, k-slabs, form): made at upload for every
-  // shape the recursion launches on the first stream (staged_prepare_products) and only looked up at launch, so an
-  // eager and a captured run of a handle take the same schedule.  list: which one stg::gemm_choose_list gave the shape;
-  // SK_LIST_NONE: no list fits the workspace - the launch is a plain round of whole tiles
+  // work lists of the cut forms of the large products (sk_table.hpp), by (tiles, k-slabs, form): made at upload by a
+  // dry walk of the factor sequence itself (hqpkkt::listing), in which st_gemm makes the list of every cut form it would
+  // launch, and only looked up at launch, so an eager and a captured run of a handle take the same schedule.  list:
+  // which one stg::gemm_choose_list gave the shape; SK_LIST_NONE: no list fits the workspace - the launch is a plain
+  // round of whole tiles.  hits: launches that looked the list up since the upload (hqpkkt_debug_get 38)
   struct SkTab {
     long long tiles, nslab;
-    int form, list, stride;
+    int form, list, stride, hits;
     DBuf<stg::SkUnit> units;
   };
   std::vector<SkTab> sk_tabs;
   bool sk_tables_on = true;  // HQPKKT_SK_TABLE
-  const SkTab *sk_tab(long long tiles, long long nslab, int form) const {
+  SkTab *sk_tab(long long tiles, long long nslab, int form) {
     for (auto &e : sk_tabs)
       if (e.tiles == tiles && e.nslab == nslab && e.form == form) return &e;
     return nullptr;
@@ -107,16 +108,11 @@ struct StagedDev {
     return stg::gemm_form(M, N, K, lower, mirror, cus, sk_grid, sk_tiles, sk_ws_elems, ks_ws2_elems,
                           (plan.sharded ? stg::GEMM_SHARDED : 0) | (first_stream ? 0 : stg::GEMM_SECOND_STREAM));
   }
-  // the list of a product as st_gemm launches it on the first stream, where its form walks one
-  // (K2: the second k segment of the launch that forms V_k; ntiles > 0: a launch of that many tiles out of a list)
-  int sk_tab_prepare(int M, int N, int K, int lower, int K2 = 0, int ntiles = 0) {
-    if (M <= 0 || N <= 0) return 0;
-    const long long nslab = stg::gemm_slabs(K) + (K2 > 0 ? stg::gemm_slabs(K2) : 0);
-    const int Kf = K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K;
-    const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, Kf, sk_grid, sk_tiles) : gemm_form(M, N, Kf, lower, K2 > 0);
-    if ((f.kind != stg::GEMM_FORM_CUT && f.kind != stg::GEMM_FORM_FRAC) || sk_tab(f.tiles, nslab, f.kind)) return 0;
+  // the list of a cut form f of nslab k-slabs, unless it exists
+  int sk_tab_prepare(const stg::GemmForm &f, long long nslab) {
+    if (sk_tab(f.tiles, nslab, f.kind)) return 0;
     stg::SplitTable t;
-    SkTab e{f.tiles, nslab, f.kind, 0, 0, {}};
+    SkTab e{f.tiles, nslab, f.kind, 0, 0, 0, {}};
     e.list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles, nslab, sk_grid, sk_tiles, sk_ws_elems, t);
     if (e.list != stg::SK_LIST_NONE) {
       if (int err = e.units.upload(t.units)) return err;
@@ -147,6 +143,32 @@ struct StreamGuard {
   hqpkkt_t *h;
   hipStream_t s;
   ~StreamGuard() { h->stream = s; }
+};
+// stream `to` goes on when `from` has come as far as it is now (nothing to do on one stream, and in upload's dry walk)
+int stream_after(hqpkkt_t *h, hipEvent_t ev, hipStream_t from, hipStream_t to) {
+  if (h->listing || from == to) return 0;
+  HIPCHK(hipEventRecord(ev, from));
+  HIPCHK(hipStreamWaitEvent(to, ev, 0));
+  return 0;
+}
+// stream b works beside a between fork and join; an error in between must not leave it forked
+struct StreamFork {
+  hqpkkt_t *h;
+  hipStream_t a, b;
+  hipEvent_t ev_fork, ev_join;
+  bool forked = false;
+  int fork() {
+    if (int e = stream_after(h, ev_fork, a, b)) return e;
+    forked = true;
+    return 0;
+  }
+  int join() {
+    forked = false;
+    return stream_after(h, ev_join, b, a);
+  }
+  ~StreamFork() {
+    if (forked) (void)join();
+  }
 };
 
 // per-stage pointers into the arenas
@@ -190,16 +212,20 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
     g.zeros = d.zeros.p;
   // (the second segment exists in the 128 x 128 LDS-DMA kernels alone: StagedDev::fused holds only stages that get them)
   if (g.K2 > 0 && !(g.zeros && (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT || f.kind == stg::GEMM_FORM_PLAIN))) return HQPKKT_E_INTERN;
+  if (h->listing) {  // upload's dry walk: what this launch will look up is made, nothing is launched
+    if (f.tile_map && !d.tri_map((g.M + 127) / 128, true)) return HQPKKT_E_MEM;
+    return f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT ? d.sk_tab_prepare(f, nslab) : 0;
+  }
   const int variant = ntiles && !g.zeros ? stg::GEMM_REG4 : d.gemm_variant;
   double *ws = allow_sk ? d.sk_ws.p : d.ks_ws2.p;
   switch (f.kind) {
     case stg::GEMM_FORM_FRAC:
     case stg::GEMM_FORM_CUT: {
       // the list the shape was given at upload (the arrival counters are zero between launches: the last arriver of a
-      // tile resets its).  A shape that upload did not prepare is a hole in staged_prepare_products, not a reason to
-      // take another schedule
-      const StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
+      // tile resets its).  A shape without one is no reason to take another schedule
+      StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
       if (!tab) return HQPKKT_E_INTERN;
+      tab->hits++;
       if (tab->list != stg::SK_LIST_NONE) {
         const stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, tab->units.p, tab->stride};
         KLAUNCH(h, cls, stg::gemm_launch_split(variant, d.sk_grid, h->stream, g, sk));
@@ -382,6 +408,13 @@ static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G,
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
                                                                                h->td.vals.p, h->td.wt.p, G, add));
 }
+// the carried rows of stage k: N_k[e..] = B+ F (nothing where stage k + 1 carries none)
+static int st_carried_rows(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, bool allow_sk) {
+  const kktdev::StagedPlan &P = d.plan;
+  const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
+  return st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, P.ldf[k], nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], P.cap[k + 1], P.nk[k] + P.mk[k],
+                                  P.nk[k + 1], 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, allow_sk);
+}
 // the control-sized elimination of stage k on the work block G: rank decision and K^-1 (k_st_small, or the blocked sweep
 // for matrices that live in global memory), Y and the carried rows, Rm = K^-1 Y (allow_sk: as in st_gemm)
 // (nRm: -Rm as well, K of order 1 .. 64)
@@ -539,7 +572,7 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   return 0;
 }
 
-static int staged_prepare_products(StagedDev &d);  // (beside the sequences it mirrors, below)
+static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w);
 static int staged_upload(hqpkkt_t *h) {
   int e = ensure_device(h);
   if (e) return e;
@@ -775,15 +808,22 @@ static int staged_upload(hqpkkt_t *h) {
         HIPCHK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
     }
   }
-  // orders of the tiles of the triangular products (G, V)
-  for (int k = 0; k < P.K; k++)
-    for (int sz : {P.nk[k] + P.mk[k], P.nk[k]}) {
-      const int T = (sz + 127) / 128;
-      if (T >= 16) (void)d.tri_map(T, true);
-    }
-  // work lists of the cut forms of the recursion's products
+  // The work lists of the recursion's cut products and the tile orders of its triangular ones (G, V): a dry walk of the
+  // factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
   d.sk_tables_on = stg::gemm_sk_table_from_env();
-  if ((e = staged_prepare_products(d))) return e;
+  d.sk_tabs.clear();
+  {
+    struct Listing {
+      hqpkkt_t *h;
+      ~Listing() { h->listing = false; }
+    } walk{h};
+    const auto t0 = std::chrono::steady_clock::now();
+    h->listing = true;
+    if ((e = staged_run_factor(h, nullptr, nullptr))) return e;
+    if (getenv("HQPKKT_TIMING"))
+      fprintf(stderr, "staged_upload: listing walk over %d stages %.3f ms (%zu work lists, %zu tile orders)\n", P.K,
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), d.sk_tabs.size(), d.tri_maps.size());
+  }
   d.lds_small = 0, d.lds_small_big = 0;
   for (int k = 0; k < P.K; k++) {
     if (P.big[k])
@@ -904,18 +944,13 @@ static int staged_gather_f(hqpkkt_t *h, int k) {
   const int NR = P.shard_count, RK = P.shard_rank, i = k & 1;
   const int wd = P.xcut[(size_t)k * (NR + 1) + RK + 1] - P.xcut[(size_t)k * (NR + 1) + RK], nloc = wd + P.mk[k], np = P.nk[k + 1];
   double *fg = d.misc.p + P.oFg[i], *mine = fg + (long long)RK * P.fgslot[k];
-  hipStream_t sA = h->stream, sX = (h->xchg_sfn && d.stream_x) ? d.stream_x : nullptr;
+  hipStream_t sA = h->stream, sX = (h->xchg_sfn && d.stream_x && !h->listing) ? d.stream_x : nullptr;
   hipStream_t on = sX ? sX : sA;
-  if (sX) {
-    HIPCHK(hipEventRecord(d.ev_w[i], sA));
-    HIPCHK(hipStreamWaitEvent(sX, d.ev_w[i], 0));
-  }
+  int e;
+  if (sX && (e = stream_after(h, d.ev_w[i], sA, sX))) return e;
   if (nloc > 0 && np > 0)
     KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(np, 2048), 256, 0, on>>>(stage_ptr(d, k).F, P.ldfl[k], mine, P.ldfl[k], np, nloc));
-  if (P.fgslot[k] > 0) {
-    const int e = exchange(h, HQPKKT_XCHG_ALLGATHER, fg, P.fgslot[k], NR, sX);
-    if (e) return e;
-  }
+  if (P.fgslot[k] > 0 && (e = exchange(h, HQPKKT_XCHG_ALLGATHER, fg, P.fgslot[k], NR, sX))) return e;
   if (sX) HIPCHK(hipEventRecord(d.ev_x[i], sX));
   return 0;
 }
@@ -932,27 +967,17 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   double *G = d.misc.p + P.oG, *Wl = d.misc.p + P.oWl, *Wu = d.misc.p + P.oWu, *xb = d.misc.p + P.oX;
   double *fg = d.misc.p + P.oFg[k & 1];  // the gathered local blocks of THIS stage (requested a stage ago)
   hipStream_t sA = h->stream, sB = d.stream2 ? d.stream2 : h->stream;
-  hipStream_t sX = (h->xchg_sfn && d.stream_x) ? d.stream_x : nullptr;  // the exchanges' own stream (stream-ordered transport)
+  // the exchanges' own stream (stream-ordered transport; none in upload's dry walk, which enqueues nothing)
+  hipStream_t sX = (h->xchg_sfn && d.stream_x && !h->listing) ? d.stream_x : nullptr;
   StreamGuard guard{h, sA};
+  StreamFork chain{h, sA, sB, d.ev_fork, d.ev_join};
   const bool two = sB != sA;
   int e;
-  struct JoinGuard {  // an error between fork and join must not leave the second stream forked
-    bool armed = false;
-    hipStream_t a, b;
-    hipEvent_t ev;
-    ~JoinGuard() {
-      if (armed && hipEventRecord(ev, b) == hipSuccess) (void)hipStreamWaitEvent(a, ev, 0);
-    }
-  } join{false, sA, sB, d.ev_join};
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
   // the next stage's F blocks travel while this stage is computed (its buffer's last readers, the stage before this one,
   // are behind us in the first stream)
   if (k > 0 && (e = staged_gather_f(h, k - 1))) return e;
-  if (two) {
-    HIPCHK(hipEventRecord(d.ev_fork, sA));
-    HIPCHK(hipStreamWaitEvent(sB, d.ev_fork, 0));
-    join.armed = true;
-  }
+  if ((e = chain.fork())) return e;
   // ---- the control-sized chain, from the gathered F (identical on all ranks: the control columns out of rank 0's slot).
   // Its thin products are launches of hundreds of small workgroups: beside a product that fills every workgroup slot of
   // the chip (the cut form: strips of >= 1024 columns, up to four ranks at the headline width) each of them waits for
@@ -978,14 +1003,10 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
     }
     if (cx > 0 && (e = thin(sn.BT, P.ldb[k + 1], cx, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], KC_ST_GEMM_UPD))) return e;
   }
-  if (thin_first && two) {  // the rest of the chain beside the large products
-    HIPCHK(hipEventRecord(d.ev_x1, sA));
-    HIPCHK(hipStreamWaitEvent(sB, d.ev_x1, 0));
-  }
+  if (thin_first && (e = stream_after(h, d.ev_x1, sA, sB))) return e;  // the rest of the chain beside the large products
   h->stream = sB;
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_eliminate(h, d, k, sp, sn, G, !two))) return e;
-  if (two) HIPCHK(hipEventRecord(d.ev_join, sB));
   // ---- sA: the strip of W, the rank's blocks of G_xx (rows = its strip) in one launch, H_xx, pack, the gather of the blocks
   h->stream = sA;
   if (wd > 0 && (e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldfl, nullptr, 0, Wl, ldwl, np, wd, np, 1.0, 0.0, 0, 0}))) return e;
@@ -1003,20 +1024,11 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   if (npk > 0)
     KLAUNCH(h, KC_ST_VEC, stg::k_st_pack_rects<<<dim3(512, npk), 256, 0, sA>>>(d.prects.p + d.prect_ptr[k], G, ldg, xb + (long long)RK * P.xslot[k]));
   if (P.xslot[k] > 0) {
-    if (sX) {
-      HIPCHK(hipEventRecord(d.ev_w[2], sA));
-      HIPCHK(hipStreamWaitEvent(sX, d.ev_w[2], 0));
-    }
+    if (sX && (e = stream_after(h, d.ev_w[2], sA, sX))) return e;
     if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xb, P.xslot[k], NR, sX))) return e;
-    if (sX) {
-      HIPCHK(hipEventRecord(d.ev_x[2], sX));
-      HIPCHK(hipStreamWaitEvent(sA, d.ev_x[2], 0));
-    }
+    if (sX && (e = stream_after(h, d.ev_x[2], sX, sA))) return e;
   }
-  if (two) {
-    HIPCHK(hipStreamWaitEvent(sA, d.ev_join, 0));
-    join.armed = false;
-  }
+  if ((e = chain.join())) return e;  // (the chain ended with st_eliminate: nothing has gone to sB since)
   // V_k = G_xx - Y' Rm: lower tiles, mirrored; G_xx from the blocks
   stg::GemmArgs gu{sp.Y, ldy, sp.Rm, ldy, xb, 0, sp.V, ldv, nn, nn, q, -1.0, 1.0, 1, 1};
   gu.rects = d.rtabs.p + k;
@@ -1038,7 +1050,6 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   const kktdev::StagedPlan &P = d.plan;
   StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
   const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm, q = P.qmax[k];
-  const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
   const long long ldf = P.ldf[k], ldg = P.ldg[k], ldy = P.ldy[k];
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW, *nRm = d.fv_nrm.p;
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
@@ -1048,11 +1059,7 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   if (mm > 0 && (e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD)))
     return e;
   st_add_h(h, d, P.h_mid[k], ne_u, G);
-  if (P.cap[k + 1] > 0 &&
-      (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, ldf, nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], P.cap[k + 1], nz, np, 1.0, 0.0, 0, 0},
-                   KC_ST_GEMM_UPD)))
-    return e;
-  if ((e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
+  if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
   // V = F_x'W_x - Y'Rm (lower tiles, mirrored), then H_xx into the entry and its image
   stg::GemmArgs g{sp.F, ldf, W, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, np, 1.0, 0.0, 1, 1};
   g.A2 = sp.Y, g.lda2 = ldy, g.B2 = nRm, g.ldb2 = ldy, g.K2 = q;
@@ -1061,6 +1068,47 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
                                                                                  h->td.vals.p, h->td.wt.p, sp.V, ldg, P.ldv[k]));
   return 0;
+}
+
+// One stage of the backward recursion in the dense form on one GPU: W = V+ F, G = F'W with H, the carried rows, the
+// control-sized elimination, the rank-q update V = G_xx - Y'Rm.  Stages of the widths that gain by it
+// (StagedDev::overlap_mode) run the control-sized chain on the second stream, beside the large product G_xx.
+static int staged_stage_dense(hqpkkt_t *h, int k) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
+  const long long ldf = P.ldf[k], ldg = P.ldg[k], ldvn = P.ldv[k + 1];
+  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
+  // The control-sized chain of the stage on the second stream, beside the large product G_xx (needs the
+  // control columns to start at an even column: 16-byte loads of W + n)
+  const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096));
+  hipStream_t sA = h->stream, sB = ovl ? d.stream2 : h->stream;
+  StreamGuard guard{h, sA};
+  StreamFork chain{h, sA, sB, d.ev_fork, d.ev_join};
+  const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
+  int e;
+  // ---- W
+  if ((e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0})) || (e = chain.fork())) return e;
+  // ---- G: the state part (large) on the first stream ...
+  if (!ovl) {
+    // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
+    if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
+    st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
+  } else {
+    if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
+    st_add_h(h, d, P.h_ptr[k], ne_x, G);
+    // ... the control rows of G (Gux, Guu) = W_u' F and H's control part on the second
+    h->stream = sB;
+    if ((e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM, false))) return e;
+    st_add_h(h, d, P.h_mid[k], ne_u, G);
+  }
+  h->stream = sB;
+  if ((e = st_carried_rows(h, d, k, sp, sn, !ovl)) || (e = st_eliminate(h, d, k, sp, sn, G, !ovl))) return e;
+  h->stream = sA;
+  if ((e = chain.join())) return e;
+  // V = Gxx - Y'Rm (lower tiles, mirrored)
+  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
 
 // the entries of the columns [c0, c0 + ncols) of F_k out of the CSR arrays of A' (staged_sparse.hip.h)
@@ -1097,46 +1145,6 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
 
-// The products of the sequences above and of staged_run_factor below, shape by shape, for StagedDev::sk_tab_prepare (at
-// upload): a launch of a cut form walks the list made here, and st_gemm refuses a shape that has none.  Every st_gemm that
-// can run on the first stream appears, whatever form the rule (gemm_form.hpp) gives it today - also those a stage puts on
-// the second stream when its chain runs beside the large product -, so a product added to a sequence is added here.
-static int staged_prepare_products(StagedDev &d) {
-  const kktdev::StagedPlan &P = d.plan;
-  int e = 0;
-  auto prep = [&](int M, int N, int K, int lower = 0, int K2 = 0, int ntiles = 0) {
-    if (!e) e = d.sk_tab_prepare(M, N, K, lower, K2, ntiles);
-  };
-  // st_blk_sweep over a control-sized matrix of order q, and the product that checks its inverse
-  auto sweep = [&](int q) { prep(64, q, 64), prep(q, q, 64), prep(q, q, q); };
-  d.sk_tabs.clear();
-  for (int k = 0; k < P.K; k++) {
-    const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm, q = P.qmax[k], cx = P.cap[k + 1];
-    if (P.sharded) {  // staged_stage_sharded
-      const int *cut = &P.xcut[(size_t)k * (P.shard_count + 1)];
-      const int wd = cut[P.shard_rank + 1] - cut[P.shard_rank];
-      prep(np, mm, np);                                         // W_u
-      for (int M : {mm, cx}) prep(M, nn, np), prep(M, mm, np);  // `thin`: the control rows of G, the carried rows
-      prep(np, wd, np);                                         // the strip of W
-      prep(wd, nn, np, 0, 0, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);  // the rank's blocks of G_xx: a tile list
-    } else if (!P.sparse_dyn) {  // staged_stage_fused, the stage of staged_run_factor
-      prep(np, nz, np);  // W
-      prep(mm, nz, np);  // the control rows of G
-      prep(cx, nz, np);  // the carried rows
-      if (d.fused[k])
-        prep(nn, nn, np, 1, q);  // V_k in the G_xx launch
-      else
-        prep(nz, nz, np, 1), prep(nn, nn, np, 1);  // G; G_xx when the chain runs beside it
-    }
-    // st_eliminate: the blocked sweep, Rm and its refinement for K of order > 64
-    if (P.big[k]) sweep(q);
-    if (q > 64) prep(q, nn, q);
-    if (!d.fused[k]) prep(nn, nn, q, 1);  // the rank-q update V = G_xx - Y'Rm (lower, mirrored)
-  }
-  if (P.big0) sweep(P.q0max);  // the initial state's matrix (staged_run_factor)
-  return e;
-}
-
 // Hqp_IpLQDOCP::factor (hqp/Hqp_IpLQDOCP.C:796-862): W^-1 Z, C'(W^-1 Z)C, then the backward
 // recursion over the stages (ExRiccatiFactorSc, :1794-1999)
 static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
@@ -1145,15 +1153,15 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   kktdev::StagedPlan &P = d.plan;
   hipStream_t s = h->stream;
   const int m = an.m, K = P.K;
+  const bool timed = !h->capturing && !h->listing;  // (listing: upload's dry walk of this sequence, staged_upload)
   int e;
-  {  // the status words and V_K cleared by one kernel (no memset nodes in the captured sequence: kernels.hip.h, k_clear)
+  if (!h->listing) {  // the status words and V_K cleared by one kernel (no memset nodes in the captured sequence: kernels.hip.h, k_clear)
     const long long vk = (long long)P.nk[K] * P.ldv[K];
     kktdev::k_clear<<<(int)std::max<long long>(1, std::min<long long>(4096, (vk / 2 + 1023) / 1024)), 256, 0, s>>>(stage_ptr(d, K).V, vk, h->td.flags.p);
   }
-  if (!h->capturing) HIPCHK(hipEventRecord(h->ev0, s));
+  if (timed) HIPCHK(hipEventRecord(h->ev0, s));
   if (m > 0) KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(1, m, an.n + an.me, z, w, h->td.wt.p, nullptr, h->td.flags.p));
-  if (!h->capturing) HIPCHK(hipEventRecord(h->ev1, s));
-  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
+  if (timed) HIPCHK(hipEventRecord(h->ev1, s));
   {  // last stage: V_K = H_K, all its equality rows are carried
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
@@ -1162,66 +1170,9 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     if (P.sharded) st_keep_rows(h, d, K);
   }
   if (P.sharded && K > 0 && (e = staged_gather_f(h, K - 1))) return e;  // (stage k requests stage k - 1's)
-  for (int k = K - 1; k >= 0; k--) {
-    if (P.sharded) {
-      if ((e = staged_stage_sharded(h, k))) return e;
-      continue;
-    }
-    if (P.sparse_dyn) {
-      if ((e = staged_stage_sparse(h, k))) return e;
-      continue;
-    }
-    if (d.fused[k]) {
-      if ((e = staged_stage_fused(h, k))) return e;
-      continue;
-    }
-    StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
-    const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
-    const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
-    const long long ldf = P.ldf[k], ldg = P.ldg[k], ldvn = P.ldv[k + 1];
-    // The control-sized chain of the stage on the second stream, beside the large product G_xx (needs the
-    // control columns to start at an even column: 16-byte loads of W + n)
-    const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096));
-    hipStream_t sA = h->stream, sB = ovl ? d.stream2 : h->stream;
-    StreamGuard guard{h, sA};
-    const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
-    // ---- W
-    if ((e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}))) return e;
-    if (ovl) {
-      HIPCHK(hipEventRecord(d.ev_fork, sA));
-      HIPCHK(hipStreamWaitEvent(sB, d.ev_fork, 0));
-    }
-    // ---- G: the state part (large) on the first stream ...
-    if (!ovl) {
-      // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
-      if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
-      st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
-    } else {
-      if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
-      st_add_h(h, d, P.h_ptr[k], ne_x, G);
-      // ... the control rows of G (Gux, Guu) = W_u' F and H's control part on the second
-      h->stream = sB;
-      if (mm > 0 && (e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM, !ovl)))
-        return e;
-      st_add_h(h, d, P.h_mid[k], ne_u, G);
-    }
-    h->stream = sB;
-    // carried rows: N_k[e..] = B+ F
-    if (P.cap[k + 1] > 0 &&
-        (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, P.ldf[k], nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k],
-                                      P.cap[k + 1], nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, !ovl)))
+  for (int k = K - 1; k >= 0; k--)
+    if ((e = P.sharded ? staged_stage_sharded(h, k) : P.sparse_dyn ? staged_stage_sparse(h, k) : d.fused[k] ? staged_stage_fused(h, k) : staged_stage_dense(h, k)))
       return e;
-    if ((e = st_eliminate(h, d, k, sp, sn, G, !ovl))) return e;
-    h->stream = sA;
-    if (ovl) {
-      HIPCHK(hipEventRecord(d.ev_join, sB));
-      HIPCHK(hipStreamWaitEvent(sA, d.ev_join, 0));
-    }
-    // V = Gxx - Y'Rm (lower tiles, mirrored)
-    if ((e = st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1},
-                     KC_ST_GEMM_UPD)))
-      return e;
-  }
   {
     StagePtr s0 = stage_ptr(d, 0);
     if (P.fixed_x0)
@@ -1247,8 +1198,8 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
       KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<256><<<1, 256, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
                                                                                   d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p, nullptr, nullptr));
   }
-  if (!h->capturing) HIPCHK(hipEventRecord(h->evs1, s));
-  HIPCHK(hipGetLastError());
+  if (timed) HIPCHK(hipEventRecord(h->evs1, s));
+  if (!h->listing) HIPCHK(hipGetLastError());
   return 0;
 }
 

@@ -703,6 +703,7 @@ static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
 int exchange(hqpkkt_t *h, int op, double *buf, long long slot, int nslots, hipStream_t on) {
   // (profiled as the class "exchange": in the stream-ordered form the time between the collective's place in
   // the stream and its completion - the wait for the slowest rank and the transfer)
+  if (h->listing) return 0;
   if (h->xchg_sfn) {  // the collective is put into the handle's stream (or `on`) behind the kernels that fill `buf`
     hipStream_t st = on ? on : h->stream;
     h->prof.begin(KC_XCHG, st);

@@ -476,7 +476,10 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * k < K two ints: the stored entries of F_k and 1 where the stage runs the sparse sequence (hqpkkt_set_dynamics_form);
  * 37 the sparse form's ranges: per dynamics row [first, end) into A's CSR arrays (the row without its -1), then per column
  * of the stages k < K [first, end) into the CSR arrays of A' (rows ascending) - the column's entries in the dynamics rows
- * of its stage; empty on a dense-form handle; 30 (zero-diagonal policy in use, last
+ * of its stage; empty on a dense-form handle; 38 the work lists the upload made for the cut forms of the stage products,
+ * five ints each: tiles, k-slabs, form (0 fractional, 1 cut), list (0 unequal shares, 1 equal, 2 fractional, -1 none fits
+ * the workspace) and the launches that looked the list up since the upload (a captured sequence looks up once, at its
+ * capture); empty before the upload; 30 (zero-diagonal policy in use, last
  * values have weak Hessian diagonals), 31 (fronts of the tree's top that the solve handles in one launch, first
  * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
  * process, over all handles: answered on any handle, analysed or not).

@@ -188,7 +188,9 @@ def main():
         if kind == "LQDOCP":
             cuts = M.debug(27).reshape(-1, world + 1)
             rec = dict(case=case, rank=rank, res=res, staged=True, cuts=cuts[0].tolist(), flops_local=s["flops_local"],
-                       bytes_factor=s["bytes_exchange_factor"], ranks=s["shard_count"], bytes_panels=s["bytes_panels"])
+                       bytes_factor=s["bytes_exchange_factor"], ranks=s["shard_count"], bytes_panels=s["bytes_panels"],
+                       # the work lists the rank's upload made (tiles, k-slabs, form, list, hits), and the grid they are for
+                       lists=M.debug(38).reshape(-1, 5).tolist(), grid=2 * torch.cuda.get_device_properties(dev).multi_processor_count)
         else:
             owner = M.debug(10)
             rec = dict(case=case, rank=rank, res=res, n_top=s["n_top"], xblocks=s["n_exchange_blocks"],

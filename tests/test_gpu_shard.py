@@ -85,15 +85,18 @@ def test_sharded_system_switches_the_zero_diagonal_placement_on_every_rank():
         assert r[0]["same_as_rank0"] and r[0]["res"] <= 10 * r0["res_single"] + 1e-10, r[0]
 
 
-# (the third: 200 controls per stage - the blocked elimination of K on the second stream, beside the strips' products)
-STAGED_CASES = [["docp", 5, 300, 6, "LQDOCP"], ["docp", 3, 520, 20, "LQDOCP"], ["docp", 3, 400, 200, "LQDOCP"]]
+# (the third: 200 controls per stage - the blocked elimination of K on the second stream, beside the strips' products;
+# the fourth: stages of 1100 states, 69 k-slabs - deep enough for the cut form of a rank's tile-list launch)
+STAGED_CASES = [["docp", 5, 300, 6, "LQDOCP"], ["docp", 3, 520, 20, "LQDOCP"], ["docp", 3, 400, 200, "LQDOCP"], ["docp", 2, 1100, 4, "LQDOCP"]]
 
 
 @pytest.mark.parametrize("world,port", [(2, 29571), (3, 29572)])
 def test_sharded_staged_system_matches_single(world, port):
     """STAGED engine over several ranks: the state columns of a stage's three products cut into one
     range per rank, ONE all-gather per stage (the strips of V_k).  Same solution as the unsharded
-    handle, identical vectors on all ranks."""
+    handle, identical vectors on all ranks.  Every work list a rank's upload made by its dry walk of the sharded
+    sequence was looked up by a launch of its factorisation (hqpkkt_debug_get 38); with 1100 states the rank's launch of
+    its G_xx blocks out of a tile list is a cut form: 69 k-slabs and a tile count that is no multiple of the grid."""
     env = dict(os.environ, SHARD_BACKEND="gloo", SHARD_CASES=json.dumps(STAGED_CASES), MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port),
@@ -110,6 +113,10 @@ def test_sharded_staged_system_matches_single(world, port):
         assert all(c % 128 == 0 or c == case[2] for c in cuts) and sum(1 for a, b in zip(cuts, cuts[1:]) if b > a) >= 2
         for r in recs:
             assert r["res"] <= 1e-10 and r["same_as_rank0"] and r["ranks"] == world, (case, r)
+            assert all(hits >= 1 for (_tiles, _nslab, _form, _list, hits) in r["lists"]), (case, r["lists"])
+            if case[2] == 1100:
+                print(f"rank {r['rank']} of {world}, grid {r['grid']}: lists (tiles, k-slabs, form, list, hits) {r['lists']}")
+                assert any(nslab == 69 and form == 1 and tiles % r["grid"] != 0 for (tiles, nslab, form, _list, _hits) in r["lists"]), r["lists"]
 
 
 # the stage shapes of the recursion: final-state rows carried back through the stages (the carried rows' columns travel

@@ -5,6 +5,7 @@ against the full-system HIP engine, on multistage QPs with and without stage equ
 (fixed / free initial state, final-state constraints that are carried back through the
 stages, path equalities, state bounds), and at K = 200 through size-independent properties.
 """
+import functools
 import os
 import sys
 
@@ -427,19 +428,116 @@ def test_unstable_closed_loops_reach_the_reference_residual(K, nx, nu, seed, sta
     assert r <= bound, (r, bound)
 
 
+@functools.lru_cache(maxsize=1)
+def _mid_size_case(nx, nu, K):
+    """A QP of K wide stages (staged_lists_worker.make), its interior-point state, and the solution and residual of the
+    full-system (tree) engine on it: computed once for the tests that follow each other on the same case."""
+    import staged_lists_worker
+    prog, st, _dq = staged_lists_worker.make(nx, nu, K)
+    df, rf = _solve(ipmatrix.IpLQDOCPFull(), prog, st)
+    return prog, st, df, rf
+
+
 @pytest.mark.parametrize("nx,nu,K", [(1000, 8, 3), (1500, 40, 2), (2304, 16, 2)])
 def test_staged_mid_size_stages_against_the_tree_engine(nx, nu, K):
     """Stage widths between the small cases (nx <= 400: reference, oracle) and the headline (nx = 5000: properties):
     72 ... 324 tiles of 128 x 128 per product - the cut few-tile launches, plain rounds and the 64 x 64 kernel all
     occur - against the full-system (tree) engine on the same QP: same solution to 1e-8, residual of the refined
     solve below mat_eps on both."""
-    prog = problems.lq_docp(K, nx, nu, final_eq=2, seed=21)
-    st = problems.ip_state(prog, 8, 1.0)
-    S, F = ipmatrix.IpLQDOCP(), ipmatrix.IpLQDOCPFull()
-    ds, rs = _solve(S, prog, st)
-    df, rf = _solve(F, prog, st)
+    prog, st, df, rf = _mid_size_case(nx, nu, K)
+    ds, rs = _solve(ipmatrix.IpLQDOCP(), prog, st)
     assert rs <= RES_TOL and rf <= RES_TOL, (rs, rf)
     assert rel_err(ds, df) <= SOL_TOL
+
+
+FRAC, CUT = 0, 1  # stg::GemmFormKind, as item 38 of hqpkkt_debug_get reports it
+
+
+def _forms_or_skip(*expected):
+    """(form, tiles, M, N, K, lower, mirror, first_stream) of the launch rule with the device's own CU count: the sizes
+    of the tests below were worked out from gemm_form.hpp for 256 CUs and a grid of 512 workgroups."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    got = [ipmatrix.gemm_form(M, N, K, lower, mirror, cus=cus, grid=2 * cus, first_stream=first)[:2] for (_f, _t, M, N, K, lower, mirror, first) in expected]
+    if got != [e[:2] for e in expected]:
+        pytest.skip(f"{cus} CUs: the launch rule gives {got}, the test is built for {[e[:2] for e in expected]}")
+
+
+@functools.lru_cache(maxsize=None)
+def _lists_run(nx, nu):
+    """One factor + solve of K = 2 stages through the dense hand-over in the default environment, with the work lists of
+    the handle (staged_lists_worker.py); shared by the tests below and left unchanged."""
+    import staged_lists_worker
+    _prog, st, dq = staged_lists_worker.make(nx, nu, 2)
+    return staged_lists_worker.run(dq, st)
+
+
+def _rows(run):
+    return {tuple(int(v) for v in r[:3]) for r in run["lists"]}
+
+
+def _d(run):
+    return [run[k] for k in ("dx", "dy", "dz", "dw")]
+
+
+def test_upload_lists_exactly_what_the_stages_launch():
+    """Stages of 2304 states, 16 controls: the control-sized chain runs beside G_xx.  W takes the cut form (342 tiles), G_xx
+    the fractional one (171 lower tiles, with a tile order), the control rows of G go to the second stream as a thin
+    product cut in k.  The lists that upload's dry walk of the factor sequence made (hqpkkt_debug_get 38) are those two,
+    and every list was looked up by a launch of the real run: the walk and the run launch the same products.  The
+    solution is the tree engine's; a handle that launches one by one (per-class timing on) instead of replaying a
+    captured graph gives the same bits and the same lists."""
+    import staged_lists_worker
+    nx, nu = 2304, 16
+    _forms_or_skip(("cut", 342, nx, nx + nu, nx, 0, 0, True), ("frac", 171, nx, nx, nx, 1, 0, True), ("ks", 37, nu, nx + nu, nx, 0, 0, False))
+    a = _lists_run(nx, nu)
+    print("lists (tiles, k-slabs, form, list, hits):", a["lists"].tolist())
+    assert len(a["lists"]) > 0 and {(342, 144, CUT), (171, 144, FRAC)} <= _rows(a), a["lists"]
+    assert (a["lists"][:, 4] >= 1).all(), a["lists"]
+    assert not a["fused"].any()
+    _prog, st, df, rf = _mid_size_case(nx, nu, 2)
+    assert a["res"] <= RES_TOL and rf <= RES_TOL, (a["res"], rf)
+    assert rel_err(_d(a), df) <= SOL_TOL
+    b = staged_lists_worker.run(staged_lists_worker.make(nx, nu, 2)[2], st, profile=True)
+    for x, y in zip(_d(a), _d(b)):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a["lists"][:, :4], b["lists"][:, :4]) and (b["lists"][:, 4] >= 1).all(), b["lists"]
+
+
+def test_upload_lists_the_two_segment_launch(tmp_path):
+    """The same stages under HQPKKT_FUSED_V=1 (read at upload: a fresh child process, as tests/test_gpu_staged_fused_v.py
+    does): V_k comes out of the G_xx launch, whose second k segment adds 2 slabs to the 144 - the list of (171 tiles, 146
+    slabs, fractional) exists and every list is hit.  The result is the unfused sequence's within the bound of
+    test_ineligible_stage_keeps_the_separate_update_and_its_bits."""
+    import pickle
+    import subprocess
+    import staged_lists_worker
+    nx, nu = 2304, 16
+    _forms_or_skip(("cut", 342, nx, nx + nu, nx, 0, 0, True), ("frac", 171, nx, nx, 16 * 146, 1, 1, True))
+    unfused = _lists_run(nx, nu)
+    case, out = str(tmp_path / "case.pkl"), str(tmp_path / "fused.npz")
+    _prog, st, dq = staged_lists_worker.make(nx, nu, 2)
+    with open(case, "wb") as f:
+        pickle.dump((dq, st), f)
+    subprocess.run([sys.executable, staged_lists_worker.__file__, case, out], env=dict(os.environ, HQPKKT_FUSED_V="1"), check=True, timeout=600)
+    f = np.load(out)
+    print("lists (tiles, k-slabs, form, list, hits):", f["lists"].tolist())
+    assert list(f["fused"][:2]) == [1, 1], f["fused"]
+    assert (171, 146, FRAC) in _rows(f), f["lists"]
+    assert (f["lists"][:, 4] >= 1).all(), f["lists"]
+    assert rel_err(_d(f), _d(unfused)) <= 1e-9
+
+
+def test_upload_lists_one_fractional_product():
+    """Stages of 1600 states: W takes the fractional form (169 tiles of 100 k-slabs) and is the only product of the
+    recursion with a list."""
+    nx, nu = 1600, 16
+    _forms_or_skip(("frac", 169, nx, nx + nu, nx, 0, 0, True), ("6464", 325, nx, nx, nx, 1, 0, True))
+    a = _lists_run(nx, nu)
+    print("lists (tiles, k-slabs, form, list, hits):", a["lists"].tolist())
+    assert a["res"] <= RES_TOL, a["res"]
+    assert len(a["lists"]) == 1 and _rows(a) == {(169, 100, FRAC)}, a["lists"]
+    assert a["lists"][0, 4] >= 1, a["lists"]
 
 
 def test_dgemm_kernel_against_exact_products():

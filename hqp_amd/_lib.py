@@ -30,7 +30,7 @@ SYMBOLS = [
     "hqpkkt_set_stages", "hqpkkt_debug_stage_ranks", "hqpkkt_debug_stage_block", "hqpkkt_debug_dgemm", "hqpkkt_debug_dgemm2", "hqpkkt_debug_sk_table", "hqpkkt_debug_gemm_form",
     "hqpkkt_analyze_staged", "hqpkkt_set_values_staged", "hqpkkt_set_shard_stream",
     "hqpkkt_values_staging", "hqpkkt_detect_stages", "hqpkkt_stage_staging", "hqpkkt_set_stage_block",
-    "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form",
+    "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -134,6 +134,7 @@ def lib():
     L.hqpkkt_franke.argtypes = [vp, C.POINTER(IpOpts)] + [dp] * 7 + [C.POINTER(IpResult)]
     L.hqpkkt_set_stages.argtypes = [vp, C.c_int, vp, vp]
     L.hqpkkt_set_dynamics_form.argtypes = [vp, C.c_int]
+    L.hqpkkt_set_dense_columns.argtypes = [vp, C.c_int]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

@@ -52,7 +52,7 @@ void staged_reset(StagedDev &d) {
   d.plan = std::move(plan);
 }
 
-// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 38); the handle is in HQPKKT_MODE_STAGED and analysed
+// hqpkkt_debug_get's STAGED items (20 .. 28, 32 .. 39); the handle is in HQPKKT_MODE_STAGED and analysed
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
   if (!h->sd) return HQPKKT_E_INTERN;
   const kktdev::StagedPlan &P = h->sd->plan;
@@ -117,6 +117,11 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       out = P.sp_arow;
       out.insert(out.end(), P.sp_tcol.begin(), P.sp_tcol.end());
       break;
+    case 39:  // the sparse form's heavy columns (hqpkkt_set_dense_columns; host only): K + 1 pointers, then the columns of every stage,
+              // local to the stage (states, then controls), ascending; empty on a dense-form handle
+      out = P.hv_ptr;
+      out.insert(out.end(), P.hv_cols.begin(), P.hv_cols.end());
+      break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
       for (const StagedDev::SkTab &t : h->sd->sk_tabs)
@@ -136,6 +141,17 @@ int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form) {
     if (form != HQPKKT_DYN_DENSE && form != HQPKKT_DYN_SPARSE) return HQPKKT_E_RANGE;
     if (!h->sd) h->sd.reset(new StagedDev);
     h->sd->plan.want_sparse = form == HQPKKT_DYN_SPARSE;  // (the next hqpkkt_analyze picks it up)
+    return 0;
+  });
+}
+
+int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (min_entries < -1) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_heavy = min_entries;  // (the next hqpkkt_analyze picks it up; read by the sparse form alone)
     return 0;
   });
 }

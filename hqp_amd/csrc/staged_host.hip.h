@@ -14,6 +14,8 @@ struct StagedDev {
   DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
   DBuf<int> sp_arow, sp_tcol;   // the sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A'
+  DBuf<int> sp_tcol_light, hv_cols, hv_of;  // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per
+                                            // stage, and per column of A its position among its stage's heavy ones or -1
   DBuf<double> dyn_part;        // row sums of A_dyn dx per block of 256 columns (k_st_dyn_both): ndyn x dyn_part_cols
   int dyn_part_cols = 0;
   PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging)
@@ -521,8 +523,9 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   kktdev::StagedPlan &P = d.plan;
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
   const bool want_sparse = P.want_sparse;
+  const int want_heavy = P.want_heavy;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse;
+  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_heavy = want_heavy;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
@@ -620,6 +623,12 @@ static int staged_upload(hqpkkt_t *h) {
     if ((e = d.h_terms.upload(t))) return e;
   }
   if (P.sparse_dyn && ((e = d.sp_arow.upload(P.sp_arow)) || (e = d.sp_tcol.upload(P.sp_tcol)))) return e;
+  if (P.sparse_dyn && !P.hv_cols.empty()) {
+    std::vector<int> of(P.nmk[P.K], -1);
+    for (int k = 0; k < P.K; k++)
+      for (int q = P.hv_ptr[k]; q < P.hv_ptr[k + 1]; q++) of[P.nmk[k] + P.hv_cols[q]] = q - P.hv_ptr[k];
+    if ((e = d.sp_tcol_light.upload(P.sp_tcol_light)) || (e = d.hv_cols.upload(P.hv_cols)) || (e = d.hv_of.upload(of))) return e;
+  }
   if (P.dense_dyn && P.sharded) {
     // the local blocks: own state columns [c0, c0 + wd) and the control columns; rank 0 adds what belongs to nobody's strip
     const int NR = P.shard_count, RK = P.shard_rank;
@@ -1112,14 +1121,23 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
 }
 
 // the entries of the columns [c0, c0 + ncols) of F_k out of the CSR arrays of A' (staged_sparse.hip.h)
-static stg::SpCols sp_cols(hqpkkt_t *h, StagedDev &d, int k, int c0, int ncols) {
+// (light: the ranges in which the stage's heavy columns are empty, where it has some)
+static stg::SpCols sp_cols(hqpkkt_t *h, StagedDev &d, int k, int c0, int ncols, bool light = false) {
   const kktdev::StagedPlan &P = d.plan;
-  return stg::SpCols{d.sp_tcol.p + 2 * ((long long)P.nmk[k] + c0), h->td.AT.col.p, h->td.AT.val.p, P.nks[k], ncols};
+  const int *ent = light && P.heavy_count(k) ? d.sp_tcol_light.p : d.sp_tcol.p;
+  return stg::SpCols{ent + 2 * ((long long)P.nmk[k] + c0), h->td.AT.col.p, h->td.AT.val.p, P.nks[k], ncols};
 }
 // One stage of the backward recursion in the sparse form (StagedPlan::sparse_dyn; Hqp_IpLQDOCP's FormGxxSp,
 // hqp/Hqp_IpLQDOCP.C:1119-1220): T = F'V+ in W's place and G = T F with its mirror image by k_sp_gather, the carried
 // rows by k_sp_carried; everything behind them is the dense sequence's - H, the control-sized elimination, the rank-q
 // update V = G_xx - Y'Rm (still an MFMA product).  One stream: nothing large is left to run the chain beside.
+// A stage with heavy columns (hqpkkt_set_dense_columns; D = D_k, nd columns) runs the same walks over the light ranges,
+// which leave zeros in the heavy columns' rows and columns of T, G and N, and beside them
+//   W_h = V+ D (thin product)  ->  T_h = W_h' (k_sp_heavy_transpose)  ->  G_h = T_h F over the light ranges (k_sp_gather,
+//   not lower: the heavy rows of G against every light column)  ->  G_hh = D'W_h  ->  N_h = B+ D
+// and k_sp_heavy_place writes row and column h of G from one register and the heavy columns of N, before H is added.
+// Every sum has a fixed order: a second factorisation gives the same bits.  A stage without heavy columns runs the
+// launches it always has.
 static int staged_stage_sparse(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
@@ -1128,19 +1146,35 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
   const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k], cx = P.cap[k + 1];
   const long long ldt = P.ldv[k + 1], ldg = P.ldg[k];
   double *G = d.misc.p + P.oG, *T = d.misc.p + P.oW;
-  const stg::SpCols f = sp_cols(h, d, k, 0, nz);
+  const stg::SpCols f = sp_cols(h, d, k, 0, nz, true);
   const unsigned cb = (unsigned)((nz + 255) / 256);
+  const int nd = np > 0 ? P.heavy_count(k) : 0;
+  const long long ldd = P.ldd[k];
+  const double *D = d.F.p + P.oD[k];
+  double *Wh = d.misc.p + P.oWh, *Th = d.misc.p + P.oTh, *Gh = d.misc.p + P.oGh, *Ghh = d.misc.p + P.oGhh, *Nh = d.misc.p + P.oNh;
   int e;
+  if (nd > 0) {
+    if ((e = st_gemm(h, stg::GemmArgs{sn.V, ldt, D, ldd, nullptr, 0, Wh, ldd, np, nd, np, 1.0, 0.0, 0, 0}))) return e;
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_heavy_transpose<<<nblk(np), 256, 0, h->stream>>>(np, nd, Wh, ldd, Th, ldt));
+  }
   if (np > 0 && nz > 0) {
     KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_gather<<<dim3(cb, (np + stg::SP_RB - 1) / stg::SP_RB), 256, 0, h->stream>>>(
                                  stg::SpGather{f, sn.V, P.ldv[k + 1], np, nullptr, 0, T, ldt, 0}));
     KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_gather<<<dim3(cb, (nz + stg::SP_RB - 1) / stg::SP_RB), 256, 0, h->stream>>>(
                                  stg::SpGather{f, T, ldt, nz, G, ldg, G, ldg, 1}));
   }
-  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
   if (cx > 0 && nz > 0)  // carried rows: N_k[e..] = B+ F
     KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_carried<<<dim3(cb, (cx + 7) / 8), 256, 0, h->stream>>>(
                                  stg::SpCarried{f, sn.BT, P.ldb[k + 1], cx, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
+  if (nd > 0) {
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_gather<<<dim3(cb, (nd + stg::SP_RB - 1) / stg::SP_RB), 256, 0, h->stream>>>(
+                                 stg::SpGather{f, Th, ldt, nd, Gh, ldg, nullptr, 0, 0}));
+    if ((e = st_gemm(h, stg::GemmArgs{D, ldd, Wh, ldd, nullptr, 0, Ghh, ldd, nd, nd, np, 1.0, 0.0, 0, 0}))) return e;
+    if (cx > 0 && (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], D, ldd, nullptr, 0, Nh, ldd, cx, nd, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD))) return e;
+    KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_heavy_place<<<dim3((unsigned)((std::max(nz, cx) + 255) / 256), nd), 256, 0, h->stream>>>(stg::SpHeavyPlace{
+                                 nz, nd, cx, d.hv_cols.p + P.hv_ptr[k], d.hv_of.p + P.nmk[k], Gh, ldg, Ghh, ldd, G, ldg, Nh, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
+  }
+  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
   if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
@@ -1263,7 +1297,10 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     } else if (P.sparse_dyn) {  // gam = q_k + F' tt over the columns' entries
       if (nn + mm > 0)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_cols<<<nblk(nn + mm), 256, 0, s>>>(
-                                         stg::SpGemvCols{sp_cols(h, d, k, 0, nn + mm), tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
+                                         stg::SpGemvCols{sp_cols(h, d, k, 0, nn + mm, true), tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
+      if (const int nd = P.heavy_count(k))  // (the heavy columns: a wavefront each)
+        KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_heavy<<<(nd + 3) / 4, 256, 0, s>>>(stg::SpGemvHeavy{
+                                         sp_cols(h, d, k, 0, nn + mm), d.hv_cols.p + P.hv_ptr[k], nd, tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
     } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
     st_bwd_small(h, d, k, sp, sn, v.r2, gam);

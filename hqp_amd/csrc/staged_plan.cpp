@@ -167,6 +167,34 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     eq_ptr[k + 1] = (int)eq_rows.size();
   }
 
+  // ------------------------------------------------------------------ the sparse form's row ranges
+  sp_arow.clear(), sp_tcol.clear(), sp_nnz.clear();
+  hv_ptr.clear(), hv_cols.clear(), hv_nnz.clear(), sp_tcol_light.clear(), heavy_min = 0;
+  if (sparse_dyn) {
+    sp_arow.assign(2 * (size_t)ndyn, 0), sp_tcol.assign(2 * (size_t)nmk[K], 0), sp_nnz.assign(K, 0);
+    for (int k = 0; k < K; k++) {
+      for (int i = nks[k]; i < nks[k + 1]; i++) sp_arow[2 * i] = Ap[i], sp_arow[2 * i + 1] = Ap[i + 1] - 1, sp_nnz[k] += Ap[i + 1] - 1 - Ap[i];
+      // (the rows of A' are in ascending order of A's rows: the dynamics rows of the stage are one range)
+      for (int c = nmk[k]; c < nmk[k + 1]; c++) {
+        const int *b = ATi + ATp[c], *e = ATi + ATp[c + 1];
+        sp_tcol[2 * c] = (int)(std::lower_bound(b, e, nks[k]) - ATi), sp_tcol[2 * c + 1] = (int)(std::lower_bound(b, e, nks[k + 1]) - ATi);
+      }
+    }
+    // heavy columns: by the length of the column's range, per stage
+    heavy_min = want_heavy < 0 ? HEAVY_DEFAULT : want_heavy;
+    hv_ptr.assign(K + 1, 0), hv_nnz.assign(K, 0);
+    sp_tcol_light = sp_tcol;
+    for (int k = 0; k < K; k++) {
+      if (heavy_min > 0)
+        for (int c = nmk[k]; c < nmk[k + 1]; c++)
+          if (sp_tcol[2 * c + 1] - sp_tcol[2 * c] >= heavy_min) {
+            hv_cols.push_back(c - nmk[k]), hv_nnz[k] += sp_tcol[2 * c + 1] - sp_tcol[2 * c];
+            sp_tcol_light[2 * c + 1] = sp_tcol[2 * c];
+          }
+      hv_ptr[k + 1] = (int)hv_cols.size();
+    }
+  }
+
   // ------------------------------------------------------------------ capacities
   cap.assign(K + 1, 0), capn.assign(K + 1, 0), qmax.assign(K + 1, 0);
   cap[K] = capn[K] = (int)eq[K].size();
@@ -220,8 +248,10 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   oF.assign(K + 1, 0), oV.assign(K + 1, 0);
   oY.assign(K + 1, 0), oR.assign(K + 1, 0), oK.assign(K + 1, 0), oKm.assign(K + 1, 0), oN.assign(K + 1, 0);
   oBT.assign(K + 1, 0), oT.assign(K + 1, 0), oVec.assign(K + 1, 0);
+  ldd.assign(K + 1, 8), oD.assign(K + 1, 0);
   long long fo = 0, vo = 0, mo = 0;
   long long wmax = 0, gmax = 0, resmax = 0;
+  long long whmax = 0, thmax = 0, ghmax = 0, ghhmax = 0, nhmax = 0;
   int nzmax = 0, nmax = 0;
   for (int k = 0; k <= K; k++) {
     const int nz = k < K ? nk[k] + mk[k] : nk[k];
@@ -236,6 +266,13 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     if (k < K) {
       ldf[k] = up8(nz), ldg[k] = up8(nz);
       if (!sparse_dyn) oF[k] = fo, fo += up16((long long)nk[k + 1] * ldf[k]);
+      if (const int nd = heavy_count(k)) {  // (the sparse form's dense block of heavy columns and its work blocks)
+        ldd[k] = up8(nd);
+        oD[k] = fo, fo += up16((long long)nk[k + 1] * ldd[k]);
+        whmax = std::max(whmax, (long long)nk[k + 1] * ldd[k]), thmax = std::max(thmax, (long long)nd * up8(nk[k + 1]));
+        ghmax = std::max(ghmax, (long long)nd * ldg[k]), ghhmax = std::max(ghhmax, (long long)nd * ldd[k]);
+        nhmax = std::max(nhmax, (long long)std::max(cap[k + 1], 1) * ldd[k]);
+      }
       ldy[k] = up8(std::max(nk[k], 1)), ldq[k] = up8(std::max(qmax[k], 1)), ldt[k] = up8(std::max(mk[k], 1));
       oY[k] = mo, mo += up16((long long)std::max(qmax[k], 1) * ldy[k]);
       oR[k] = mo, mo += up16((long long)std::max(qmax[k], 1) * ldy[k]);
@@ -250,6 +287,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   }
   oW = mo, mo += up16(wmax);
   oG = mo, mo += up16(gmax);
+  oWh = mo, mo += up16(whmax), oTh = mo, mo += up16(thmax), oGh = mo, mo += up16(ghmax), oGhh = mo, mo += up16(ghhmax), oNh = mo, mo += up16(nhmax);
   ldq0 = up8(std::max(q0max, 1));
   oK0 = mo, mo += up16((long long)std::max(q0max, 1) * ldq0);
   oK0m = mo, mo += up16((long long)std::max(q0max, 1) * ldq0);
@@ -379,15 +417,20 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   // ------------------------------------------------------------------ scatter of A
   a_dst.assign(na, -1);
   chk_idx.clear(), chk_kind.clear();
+  std::vector<int> hv_of;  // (sparse form: position of a column of the stage among its heavy ones, or -1)
   if (!dense_dyn)
-    for (int k = 0; k < K; k++)
+    for (int k = 0; k < K; k++) {
+      if (sparse_dyn) {
+        hv_of.assign(nk[k] + mk[k], -1);
+        for (int q = hv_ptr[k]; q < hv_ptr[k + 1]; q++) hv_of[hv_cols[q]] = q - hv_ptr[k];
+      }
       for (int i = nks[k]; i < nks[k + 1]; i++) {
         const int li = i - nks[k];
         for (int p = Ap[i]; p < Ap[i + 1] - 1; p++) {
           const int lc = Ai[p] - nmk[k];
-          if (sparse_dyn)
-            continue;  // (no dense block: the kernels read the row lists)
-          else if (!sharded)
+          if (sparse_dyn) {  // (no dense block but D_k: the kernels read the row lists)
+            if (hv_of[lc] >= 0) a_dst[p] = oD[k] + (long long)li * ldd[k] + hv_of[lc];
+          } else if (!sharded)
             a_dst[p] = oF[k] + (long long)li * ldf[k] + lc;
           else {  // the local block: own state columns, then the control columns
             const int c0 = xcut[(size_t)k * (shard_count + 1) + shard_rank], c1 = xcut[(size_t)k * (shard_count + 1) + shard_rank + 1];
@@ -399,6 +442,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
         }
         chk_idx.push_back(nq + Ap[i + 1] - 1), chk_kind.push_back(0);
       }
+    }
   for (int k = 0; k <= K; k++)
     for (int li = 0; li < (int)eq[k].size(); li++) {
       const int i = eq[k][li];
@@ -455,30 +499,18 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     for (int k = 0; k <= K; k++) h_mid[k] = h_ptr[k] + nstate[k];
   }
 
-  // ------------------------------------------------------------------ the sparse form's row ranges
-  sp_arow.clear(), sp_tcol.clear(), sp_nnz.clear();
-  if (sparse_dyn) {
-    sp_arow.assign(2 * (size_t)ndyn, 0), sp_tcol.assign(2 * (size_t)nmk[K], 0), sp_nnz.assign(K, 0);
-    for (int k = 0; k < K; k++) {
-      for (int i = nks[k]; i < nks[k + 1]; i++) sp_arow[2 * i] = Ap[i], sp_arow[2 * i + 1] = Ap[i + 1] - 1, sp_nnz[k] += Ap[i + 1] - 1 - Ap[i];
-      // (the rows of A' are in ascending order of A's rows: the dynamics rows of the stage are one range)
-      for (int c = nmk[k]; c < nmk[k + 1]; c++) {
-        const int *b = ATi + ATp[c], *e = ATi + ATp[c + 1];
-        sp_tcol[2 * c] = (int)(std::lower_bound(b, e, nks[k]) - ATi), sp_tcol[2 * c + 1] = (int)(std::lower_bound(b, e, nks[k + 1]) - ATi);
-      }
-    }
-  }
-
   // ------------------------------------------------------------------ work counts
   flops_factor = 0, bytes_step = 0;
   for (int k = 0; k < K; k++) {
     const long long nn = nk[k], mm = mk[k], np = nk[k + 1], nz = nn + mm, q = qmax[k];
     if (sparse_dyn) {
       // two flops per (entry of F_k) x (row length): T = F'V+ (rows of n+), G = T F (lower half: rows of n_k + m_k on
-      // average halved), the carried rows
-      const long long nnz = sp_nnz[k];
+      // average halved), the carried rows; the heavy columns (nd of them) as dense products instead: V+ D, D'(V+ D)
+      // and B+ D, and their rows of G against the light columns' entries
+      const long long nd = heavy_count(k), nnz = sp_nnz[k] - hv_nnz[k];
       flops_factor += 2 * nnz * np + nnz * nz + 2 * nnz * cap[k + 1];
-      bytes_step += 8 * (2 * np * np + 4 * nnz + 2 * q * nn);
+      flops_factor += 2 * np * np * nd + 2 * np * nd * nd + 2 * (long long)cap[k + 1] * np * nd + 2 * nnz * nd;
+      bytes_step += 8 * (2 * np * np + 4 * (long long)sp_nnz[k] + 2 * q * nn);
     } else {
       flops_factor += 2 * np * np * nz;       // W = V+ F
       flops_factor += np * nz * nz;           // G = F' W, lower half

@@ -38,6 +38,22 @@ struct StagedPlan {
   bool want_sparse = false, sparse_dyn = false;
   std::vector<int> sp_arow, sp_tcol;
   std::vector<int> sp_nnz;  // stored entries of F_k (K)
+  std::vector<int> hv_nnz;  // ... those of them in heavy columns (K)
+  // Heavy columns of the sparse form (hqpkkt_set_dense_columns): a column of F_k with at least heavy_min stored entries
+  // (0: none) leaves the column walks and is kept as a column of the dense block D_k = n_{k+1} rows of ldd[k] = up8(nd_k)
+  // doubles at oD[k] in the F arena (k-major: either operand of the MFMA product), filled by the scatter of A's values.
+  // hv_cols[hv_ptr[k] .. hv_ptr[k + 1]): the heavy columns of stage k, local to the stage, ascending.  sp_tcol_light:
+  // sp_tcol with the heavy columns' ranges empty - what the column walks take where a stage has heavy columns.  The work
+  // blocks of the stage in the misc arena, sized for the largest stage: oWh = V+ D (n+ x ldd), oTh its transpose (nd rows of
+  // up8(n+)), oGh = the heavy rows of G (nd x ldg), oGhh = D'V+D (nd x ldd), oNh = B+ D (carried rows x ldd).
+  // want_heavy: what the next analysis takes (-1: HEAVY_DEFAULT, the smallest count of the sweep from which taking
+  // sixteen columns out of the walks won at 2000 and at 5000 states, profiles/r12_dense_columns.txt)
+  static const int HEAVY_DEFAULT = 32;
+  int want_heavy = 0, heavy_min = 0;
+  std::vector<int> hv_ptr, hv_cols, sp_tcol_light, ldd;
+  std::vector<long long> oD;
+  long long oWh = 0, oTh = 0, oGh = 0, oGhh = 0, oNh = 0;
+  int heavy_count(int k) const { return hv_ptr.empty() ? 0 : hv_ptr[k + 1] - hv_ptr[k]; }
 
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;

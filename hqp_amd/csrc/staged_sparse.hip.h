@@ -161,4 +161,73 @@ __global__ void __launch_bounds__(256) k_sp_gemv_rows(SpGemvRows g) {
   if (i < g.M && sub == 0) g.y[i] = g.scale * ((g.add ? g.add[i] : 0.0) + s);
 }
 
+// ---- heavy columns (hqpkkt_set_dense_columns; StagedPlan::hv_cols): the nd columns of F_k with many entries are the
+// dense block D (n+ rows of ldd doubles) and go through the MFMA product as thin products - W_h = V+ D, G_hh = D'W_h,
+// N_h = B+ D - while the column walks above run over ranges in which those columns are empty.  What is left is moving
+// the compact results to where the stage sequence reads them.
+
+// Th[h][j] = Wh[j][h], h < nd, j < np: the rows of T = F'V+ that belong to the heavy columns, for the gather that forms
+// their rows of G against the light columns (V+ is exactly symmetric, so D'V+ is the transpose of V+ D)
+__global__ void __launch_bounds__(256) k_sp_heavy_transpose(int np, int nd, const double *__restrict__ Wh, long long ldd, double *__restrict__ Th,
+                                                            long long ldt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= np) return;
+  const double *w = Wh + (long long)j * ldd;
+  for (int h = 0; h < nd; h++) Th[(long long)h * ldt + j] = w[h];
+}
+// Row and column hv[a] of G, both images from one register, so G stays exactly symmetric: against a light column c the
+// gathered Gh[a][c], against the heavy column hv[b] the lower half of Ghh = D'V+D (max(a, b), min(a, b)).  hv_of[c]:
+// position of column c among the heavy ones or -1.  The carried rows ride along: N[r][hv[a]] = Nh[r][a], r < R
+struct SpHeavyPlace {
+  int nz, nd, R;
+  const int *hv, *hv_of;
+  const double *Gh;
+  long long ldgh;
+  const double *Ghh;
+  long long ldd;
+  double *G;
+  long long ldg;
+  const double *Nh;
+  double *N;
+  long long ldn;
+};
+__global__ void __launch_bounds__(256) k_sp_heavy_place(SpHeavyPlace g) {
+  const int c = blockIdx.x * 256 + threadIdx.x, a = blockIdx.y;
+  const int h = g.hv[a];
+  if (c < g.nz) {
+    const int b = g.hv_of[c];
+    const double v = b < 0 ? g.Gh[(long long)a * g.ldgh + c] : g.Ghh[(long long)max(a, b) * g.ldd + min(a, b)];
+    g.G[(long long)h * g.ldg + c] = v;
+    g.G[(long long)c * g.ldg + h] = v;
+  }
+  if (c < g.R) g.N[(long long)c * g.ldn + h] = g.Nh[(long long)c * g.ldd + a];
+}
+// the solve's gam = q + F'tt for the heavy columns, behind k_sp_gemv_cols on the light ranges (which left y[c] = add[c]
+// there): one wavefront per heavy column, the lanes stride over the column's entries in the CSR arrays of A' (coalesced),
+// the lanes' sums by a fixed tree.  add, alpha, y2 as in k_sp_gemv_cols
+struct SpGemvHeavy {
+  SpCols f;       // (the FULL ranges of the stage's columns)
+  const int *hv;  // the heavy columns
+  int nd;
+  const double *x;
+  const double *add;
+  double alpha;
+  double *y;
+  const double *add2;
+  double *y2;
+};
+__global__ void __launch_bounds__(256) k_sp_gemv_heavy(SpGemvHeavy g) {
+  const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a >= g.nd) return;  // (whole wavefronts leave)
+  const int c = g.hv[a];
+  double s = 0.0;
+  for (int t = g.f.ent[2 * c] + lane; t < g.f.ent[2 * c + 1]; t += 64) s += g.f.val[t] * g.x[g.f.row[t] - g.f.row0];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) {
+    const double r = (g.add ? g.add[c] : 0.0) + g.alpha * s;
+    g.y[c] = r;
+    if (g.y2) g.y2[c] = r + g.add2[c];
+  }
+}
+
 }  // namespace stg

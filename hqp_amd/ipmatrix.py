@@ -339,19 +339,37 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     MFMA products (HQPKKT_MODE_STAGED).  ``set_stages(nx, nu)`` before init() gives the stage
     sizes explicitly.  ``a_sparse=True`` (the reference's mat_a_sparse, hqp/Hqp_IpLQDOCP.C:178) or
     ``set_dynamics_form("sparse")`` before init(): the stage products walk the row lists of A instead of
-    dense blocks F_k - for dynamics with a few entries per column (hqpkkt_set_dynamics_form)."""
+    dense blocks F_k - for dynamics with a few entries per column (hqpkkt_set_dynamics_form).  ``dense_columns=n``
+    or ``set_dense_columns(n)`` with it: the columns of F_k with at least n entries go through the MFMA products as
+    a small dense block (hqpkkt_set_dense_columns; -1: the library's threshold, 0: none)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, **kw):
         super().__init__(*args, **kw)
         if a_sparse:
             self.set_dynamics_form("sparse")
+        if dense_columns:
+            self.set_dense_columns(dense_columns)
 
     def set_dynamics_form(self, form):
         """"dense" (default) or "sparse"; holds from the next init() on."""
         code = {"dense": _lib.DYN_DENSE, "sparse": _lib.DYN_SPARSE}.get(form, form)
         _check(self._L.hqpkkt_set_dynamics_form(self._h, int(code)), "set_dynamics_form")
+
+    def set_dense_columns(self, min_entries):
+        """Columns of F_k with at least ``min_entries`` entries are heavy (sparse form; holds from the next init() on)."""
+        _check(self._L.hqpkkt_set_dense_columns(self._h, int(min_entries)), "set_dense_columns")
+
+    def dense_columns(self):
+        """Per stage k < K the heavy columns, local to the stage (states, then controls), ascending; [] unless the
+        sparse form is set."""
+        d = self.debug(39)
+        if d.size == 0:
+            return []
+        K = len(self.debug(21))
+        ptr, cols = d[: K + 1], d[K + 1:]
+        return [cols[ptr[k]: ptr[k + 1]].tolist() for k in range(K)]
 
     def dynamics_entries(self):
         """Per stage k < K: (stored entries of F_k, 1 where the stage runs the sparse sequence)."""

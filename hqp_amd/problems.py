@@ -295,6 +295,36 @@ def sparse_docp(K, nx, nu, band=5, seed=3, x0_fixed=True, final_eq=0, path_eq=0,
     return prog
 
 
+def with_dense_columns(prog, cols, seed=99, scale=0.05):
+    """A copy of a :func:`sparse_docp` program in which the columns ``cols`` of the dynamics are full: for every
+    ``(k, j)`` (``j`` local to stage k, states then controls) the empty places of that column in the stage's dynamics rows
+    are filled with ``scale * U(-1, 1)``, in row order, from ``default_rng(seed)``; existing entries stay.  The workload
+    of the sparse form's heavy columns (``Hqp_IpLQDOCP(a_sparse=True, dense_columns=n)``): sparse state coupling with a
+    few global states or actuators that act on every state."""
+    rng = np.random.default_rng(seed)
+    nxs, nus = prog.nx, prog.nu
+    K = len(nus)
+    off = np.concatenate([[0], np.cumsum([nxs[k] + nus[k] for k in range(K)])]).astype(np.int64)
+    roff = np.concatenate([[0], np.cumsum(nxs[1:])]).astype(np.int64)
+    p, i, x = (np.asarray(a) for a in prog.A)
+    rows = np.repeat(np.arange(prog.me), np.diff(p))
+    ar, ac, av = [rows], [i], [np.asarray(x, dtype=float)]
+    done = set()
+    for k, j in cols:
+        assert 0 <= j < nxs[k] + nus[k]
+        if (k, j) in done:
+            continue
+        done.add((k, j))
+        col = int(off[k]) + int(j)
+        stage = np.arange(int(roff[k]), int(roff[k + 1]))
+        missing = np.setdiff1d(stage, rows[(i == col) & (rows >= stage[0]) & (rows <= stage[-1])])
+        ar.append(missing), ac.append(np.full(missing.size, col)), av.append(scale * rng.uniform(-1, 1, missing.size))
+    A = _csr(np.concatenate(ar), np.concatenate(ac), np.concatenate(av), prog.me)
+    out = Program(prog.n, prog.me, prog.m, prog.Q, A, prog.C, c=prog.c, b=prog.b, d=prog.d)
+    out.nx, out.nu = nxs, nus
+    return out
+
+
 class DenseDocp:
     """A multistage QP whose dynamics rows are handed over as dense blocks
     (hqpkkt_analyze_staged / hqpkkt_set_values_staged): ``F[k]`` = [fx_k fu_k], row-major

@@ -314,11 +314,25 @@ int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu);
  * hqpkkt_set_stages: the form holds until it is set again and the next hqpkkt_analyze picks it up.  HQPKKT_E_RANGE: unknown
  * form; HQPKKT_E_INTERN: the handle's mode is not STAGED.  With HQPKKT_DYN_SPARSE set hqpkkt_analyze_staged (the dense
  * hand-over) returns HQPKKT_E_INTERN, and hqpkkt_analyze on a handle with hqpkkt_set_shard / hqpkkt_set_shard_stream
- * returns HQPKKT_E_RANGE: one system over several ranks stays dense.  There is no automatic choice; the sparse form pays
- * while a column of F_k holds few entries against the number of states (DESIGN.md section 3 has the measured times). */
+ * returns HQPKKT_E_RANGE: one system over several ranks stays dense.  There is no automatic choice between the two forms;
+ * the sparse form pays while a column of F_k holds few entries against the number of states (DESIGN.md section 3 has the
+ * measured times), and a few full columns among them can be taken out of the walks (hqpkkt_set_dense_columns). */
 #define HQPKKT_DYN_DENSE 0   /* default: dense blocks F_k, MFMA products           */
 #define HQPKKT_DYN_SPARSE 1  /* Hqp_IpLQDOCP's mat_a_sparse: F_k stays row lists   */
 int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form);
+/* Heavy columns of the sparse form.  Its column walks give one lane one column of F_k, so a stage takes as long as its
+ * longest column: a dense control column or a global state among banded ones costs a serial loop over every state.  With
+ * min_entries = n > 0 a column of F_k that holds at least n stored entries in its stage's dynamics rows is "heavy": the
+ * heavy columns of a stage are kept as a small dense block D_k (n_{k+1} rows of up8(columns) doubles in the F arena,
+ * hqpkkt_stats.bytes_panels counts it) and go through the fp64 MFMA product as thin products (V+ D_k, D_k'V+ D_k, B+ D_k),
+ * all other columns stay on the walks; in the solve a wavefront takes each heavy column.  0 (default): none, the sparse
+ * form as it was.  -1: the library's threshold (32 entries; DESIGN.md section 3 has the measurements).  Heaviness is a
+ * property of the pattern, decided per stage at the analysis; a stage without heavy columns runs the launches it always has.
+ * The choice between the dense and the sparse form stays the caller's.  Host-only; call it before hqpkkt_analyze, like
+ * hqpkkt_set_dynamics_form: it holds until set again and the next hqpkkt_analyze picks it up.  It has an effect only
+ * together with HQPKKT_DYN_SPARSE: on a dense-form handle it is accepted and ignored.  HQPKKT_E_INTERN: the handle's mode
+ * is not STAGED; HQPKKT_E_RANGE: min_entries < -1. */
+int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense
@@ -479,7 +493,9 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * of its stage; empty on a dense-form handle; 38 the work lists the upload made for the cut forms of the stage products,
  * five ints each: tiles, k-slabs, form (0 fractional, 1 cut), list (0 unequal shares, 1 equal, 2 fractional, -1 none fits
  * the workspace) and the launches that looked the list up since the upload (a captured sequence looks up once, at its
- * capture); empty before the upload; 30 (zero-diagonal policy in use, last
+ * capture); empty before the upload; 39 the sparse form's heavy columns (hqpkkt_set_dense_columns): K + 1 pointers, then the
+ * heavy columns of every stage as column indices local to the stage (states first, then controls), ascending; empty
+ * unless the sparse form is set; valid after hqpkkt_analyze, without a device; 30 (zero-diagonal policy in use, last
  * values have weak Hessian diagonals), 31 (fronts of the tree's top that the solve handles in one launch, first
  * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
  * process, over all handles: answered on any handle, analysed or not).

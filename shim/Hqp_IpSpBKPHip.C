@@ -50,11 +50,13 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
   _nx = _nu = IVNULL;
   _wz_tol = HUGE_VAL;
   _a_sparse = 0;
+  _a_heavy = 0;
   _told_ignored = false;
   _logging = getenv("HQPKKT_SHIM_LOGGING") ? atoi(getenv("HQPKKT_SHIM_LOGGING")) : 0;
   if (mode == HQPKKT_MODE_STAGED) {
     _ifList.append(new If_Real("mat_wz_tol", &_wz_tol));
     _ifList.append(new If_Int("mat_a_sparse", &_a_sparse));
+    _ifList.append(new If_Int("mat_a_heavy", &_a_heavy));
     _ifList.append(new If_Int("mat_logging", &_logging));
   }
 
@@ -371,7 +373,7 @@ int Hqp_IpMatrixHip::open(int mode, bool sparse_dyn)
   if ((e = create_handle(mode)))
     return e;
   _dense = false;
-  if (sparse_dyn && (e = hqpkkt_set_dynamics_form(_h, HQPKKT_DYN_SPARSE)))
+  if (sparse_dyn && ((e = hqpkkt_set_dynamics_form(_h, HQPKKT_DYN_SPARSE)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy))))
     return e;
   if ((e = hqpkkt_analyze(_h, _n, _me, _m,
                           _Qp->ive, _Qi->ive, _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive,

@@ -40,9 +40,11 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
   // so once on stderr when it is set to a non-default value (it selects the reference's other recursion, off by default:
   // HUGE_VAL, :111, 850-853); mat_a_sparse != 0 takes the CSR hand-over with the sparse form of the stage products
   // (hqpkkt_set_dynamics_form; one system over several GPUs stays dense), mat_logging > 0 prints the stage structure
-  // and the engine chosen at init()
+  // and the engine chosen at init().  mat_a_heavy (no counterpart in the reference) goes to hqpkkt_set_dense_columns
+  // when mat_a_sparse != 0: columns of F_k with at least that many entries take the MFMA products (0 none, -1 the
+  // library's threshold)
   Real _wz_tol;
-  int _a_sparse, _logging;
+  int _a_sparse, _a_heavy, _logging;
   bool _told_ignored;
   struct hqpkkt *_h;
   // STAGED engine with the dynamics handed over as dense blocks (hqpkkt_analyze_staged): stage sizes, the number of

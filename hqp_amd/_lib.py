@@ -27,7 +27,7 @@ SYMBOLS = [
     "hqpkkt_selftest_mfma", "hqpkkt_set_profile", "hqpkkt_get_profile",
     "hqpkkt_profile_class_name", "hqpkkt_set_shard", "hqpkkt_debug_read",
     "hqpkkt_default_ip_opts", "hqpkkt_mehrotra", "hqpkkt_franke",
-    "hqpkkt_set_stages", "hqpkkt_debug_stage_ranks", "hqpkkt_debug_stage_block", "hqpkkt_debug_dgemm", "hqpkkt_debug_dgemm2", "hqpkkt_debug_sk_table", "hqpkkt_debug_gemm_form",
+    "hqpkkt_set_stages", "hqpkkt_debug_stage_ranks", "hqpkkt_debug_stage_block", "hqpkkt_debug_dgemm", "hqpkkt_debug_dgemm2", "hqpkkt_debug_dgemm_full", "hqpkkt_debug_sk_table", "hqpkkt_debug_gemm_form",
     "hqpkkt_analyze_staged", "hqpkkt_set_values_staged", "hqpkkt_set_shard_stream",
     "hqpkkt_values_staging", "hqpkkt_detect_stages", "hqpkkt_stage_staging", "hqpkkt_set_stage_block",
     "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
@@ -72,6 +72,20 @@ class IpOpts(C.Structure):
                 ("norm_data", C.c_double), ("hot_start", C.c_int), ("max_warm_iters", C.c_int),
                 ("init_method", C.c_int), ("reserved", C.c_int * 1),
                 ("norm_Q", C.c_double), ("norm_C", C.c_double), ("norm_d", C.c_double), ("qp_mu0", C.c_double)]
+
+
+class DgemmOperand(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("rows", C.c_longlong), ("ld", C.c_longlong), ("col0", C.c_longlong)]
+
+
+class DgemmCase(C.Structure):
+    """hqpkkt_dgemm_case (include/hqpkkt.h)"""
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("K2", C.c_int),
+                ("lower", C.c_int), ("mirror", C.c_int), ("flags", C.c_int), ("cin_is_c", C.c_int),
+                ("alpha", C.c_double), ("beta", C.c_double),
+                ("A", DgemmOperand), ("B", DgemmOperand), ("A2", DgemmOperand), ("B2", DgemmOperand), ("Cin", DgemmOperand),
+                ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong), ("c_row0", C.c_longlong), ("c_col0", C.c_longlong),
+                ("form", C.c_int), ("tile_map", C.c_int), ("ldsdma", C.c_int), ("nsplit", C.c_int), ("tiles", C.c_longlong)]
 
 
 class IpResult(C.Structure):
@@ -143,6 +157,7 @@ def lib():
     L.hqpkkt_debug_dgemm.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_double)] * 2
     L.hqpkkt_debug_stage_block.argtypes = [vp, C.c_int, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_dgemm2.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_double)] * 2 + [C.POINTER(C.c_longlong)]
+    L.hqpkkt_debug_dgemm_full.argtypes = [C.c_int, C.POINTER(DgemmCase)]
     L.hqpkkt_debug_sk_table.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3

@@ -437,6 +437,63 @@ static void dgemm_stamps_plain(const stg::GemmArgs &g, long long tiles, int vari
   }
 }
 }  // namespace
+// One launch of the product outside a handle, for hqpkkt_debug_dgemm and hqpkkt_debug_dgemm_full: the engine's rule
+// (gemm_form.hpp) and the engine's launch (stg::gemm_launch_form) with a workspace, arrival counters, a work list, a tile
+// order and a zero row of its own.  The rule sees the capacity the self-test has always stated - counters for the tiles
+// of this product, 16 parked pieces per tile - and the buffers hold what the chosen list and form need.
+struct DebugGemm {
+  DBuf<double> zr, ws;
+  DBuf<unsigned> cnt;
+  DBuf<stg::SkUnit> units;
+  DBuf<int> order;
+  stg::GemmForm f;
+  stg::SplitTable tab;
+  stg::SplitPlan sk{};
+  stg::GemmLaunch L{};
+  int list = stg::SK_LIST_NONE, cus = 0, skg = 0;
+  bool use_sk = false;
+  // completes g (zeros, tile_map) and makes what its launch looks up; flags: stg::GEMM_SHARDED, GEMM_NO_KS, GEMM_NO_TILE_MAP, GEMM_FORCE_SPLIT
+  int prepare(int device, stg::GemmArgs &g, int flags) {
+    const int variant = stg::gemm_variant_from_env();
+    if (variant != stg::GEMM_REG4 && stg::gemm_operands_dma_ok(g)) {
+      if (zr.alloc(256)) return HQPKKT_E_MEM;
+      (void)hipMemset(zr.p, 0, sizeof(double) * 256);
+      g.zeros = zr.p;
+    }
+    if (g.K2 > 0 && !g.zeros) return HQPKKT_E_RANGE;  // (the LDS-DMA kernels alone)
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    skg = stg::gemm_wgs_per_cu(variant) * cus;
+    const long long t128 = stg::gemm_tiles(g.M, g.N, 128, g.lower), nslab = stg::gemm_slabs_of(g);
+    const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
+    f = stg::gemm_form(g.M, g.N, g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K, g.lower, g.mirror, cus, skg, t128, ws_elems, 0, flags);
+    if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_RANGE;
+    use_sk = f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT;
+    if (g.K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
+    (void)stg::gemm_set_attributes();
+    if (f.tile_map) {
+      if (order.upload(stg::gemm_tri_order((g.M + 127) / 128))) return HQPKKT_E_MEM;
+      g.tile_map = order.p;
+    }
+    L = stg::GemmLaunch{stg::gemm_variant_for(g, variant), cus, skg, nullptr, nullptr};
+    if (use_sk) {
+      // (its one list by the engine's chooser: unequal shares for the two workgroups of a CU; HQPKKT_SK_TABLE=0 or one system over
+      // several ranks: equal shares)
+      list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, stg::gemm_sk_table_from_env() && !(flags & stg::GEMM_SHARDED), f.tiles, nslab, skg, t128, ws_elems, tab);
+      if (list == stg::SK_LIST_NONE) return HQPKKT_E_RANGE;
+      if (units.upload(tab.units) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 4)) return HQPKKT_E_MEM;
+      sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
+      L.sk = &sk;
+    } else if (f.kind == stg::GEMM_FORM_KS) {
+      if (ws.alloc((size_t)stg::gemm_ks_ws_elems(g, f))) return HQPKKT_E_MEM;
+      L.ks_ws = ws.p;
+    }
+    return 0;
+  }
+  void launch(const stg::GemmArgs &g) {
+    if (use_sk) (void)hipMemsetAsync(cnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
+    stg::gemm_launch_form(f, L, 0, g, [](auto &&kernel) { kernel(); });
+  }
+};
 // K2 > 0: C = A'B - A2'B2 by a launch with a second k segment (operands A2, -B2); asym: entries of a mirrored result
 // that are not bit-identical to their image
 static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym) {
@@ -446,10 +503,8 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
   HIPCHK(hipSetDevice(device));
   const long long lda = (M + 7) / 8 * 8, ldb = (N + 7) / 8 * 8, ldc = ldb;
-  DBuf<double> A, B, Cm, err, zr, skws, A2, B2, nB2;
+  DBuf<double> A, B, Cm, err, A2, B2, nB2;
   DBuf<unsigned long long> nasym;
-  DBuf<unsigned> skcnt;
-  DBuf<stg::SkUnit> sk_table_dev;
   const size_t kk = K > 0 ? K : 1;
   if (A.alloc(kk * lda) || B.alloc(kk * ldb) || Cm.alloc((size_t)std::max(M, N) * ldc) || err.alloc(1)) return HQPKKT_E_MEM;
   k_fill_rand<<<nblk((long long)kk * lda), 256>>>(A.p, (long long)kk * lda, 1);
@@ -457,14 +512,7 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   (void)hipMemset(err.p, 0, 8);
   (void)hipMemset(Cm.p, 0, sizeof(double) * (size_t)std::max(M, N) * ldc);
   stg::GemmArgs g{A.p, lda, B.p, ldb, nullptr, 0, Cm.p, ldc, M, N, K, 1.0, 0.0, lower, mirror, nullptr, nullptr};
-  const int variant = stg::gemm_variant_from_env();
-  if (variant != stg::GEMM_REG4) {
-    if (zr.alloc(256)) return HQPKKT_E_MEM;
-    (void)hipMemset(zr.p, 0, sizeof(double) * 256);
-    g.zeros = zr.p;
-  }
   if (K2 > 0) {
-    if (!g.zeros) return HQPKKT_E_RANGE;  // (the LDS-DMA kernels alone)
     if (A2.alloc((size_t)K2 * lda) || B2.alloc((size_t)K2 * ldb) || nB2.alloc((size_t)K2 * ldb)) return HQPKKT_E_MEM;
     k_fill_rand<<<nblk((long long)K2 * lda), 256>>>(A2.p, (long long)K2 * lda, 3);
     k_fill_rand<<<nblk((long long)K2 * ldb), 256>>>(B2.p, (long long)K2 * ldb, 4);
@@ -472,50 +520,25 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
     g.A2 = A2.p, g.lda2 = lda, g.B2 = nB2.p, g.ldb2 = ldb, g.K2 = K2;  // (the check sums what the launch was given: A'B + A2'(-B2))
   }
   // The engine's rule (gemm_form.hpp) with what this entry point has always done differently: no thin product cut in k, no
-  // tile order for large triangles, never sharded, and a workspace of its own - 16 parked pieces per tile
+  // tile order for large triangles, never sharded, and a workspace of its own
   // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
-  int cus = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  const int skg = stg::gemm_wgs_per_cu(variant) * cus;
-  const long long t128 = stg::gemm_tiles(M, N, 128, lower), nslab = stg::gemm_slabs(K) + (K2 > 0 ? stg::gemm_slabs(K2) : 0);
-  const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
-  const stg::GemmForm f = stg::gemm_form(M, N, K2 > 0 ? (int)(nslab * stg::GEMM_BK) : K, lower, mirror, cus, skg, t128, ws_elems, 0, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP |
-                                         (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0));
-  const bool frac = f.kind == stg::GEMM_FORM_FRAC, use_sk = frac || f.kind == stg::GEMM_FORM_CUT;
-  if (K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
-  (void)stg::gemm_set_attributes();
-  if (use_sk && (skws.alloc((size_t)ws_elems) || skcnt.alloc(f.tiles + 4))) return HQPKKT_E_MEM;
-  // (its one list by the engine's chooser: unequal shares for the two workgroups of a CU, HQPKKT_SK_TABLE=0: equal shares)
-  stg::SplitTable sk_tab;
-  int list = stg::SK_LIST_NONE;
-  if (use_sk) {
-    list = stg::gemm_choose_list(frac, stg::gemm_sk_table_from_env(), f.tiles, nslab, skg, t128, ws_elems, sk_tab);
-    if (list == stg::SK_LIST_NONE) return HQPKKT_E_RANGE;
-    if (sk_table_dev.upload(sk_tab.units)) return HQPKKT_E_MEM;
-  }
+  DebugGemm run;
+  if (int e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP | (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0))) return e;
   EventOwner e0, e1;
   (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
     if (r == 0) (void)hipEventRecord(e0, 0);
-    if (use_sk) {
-      (void)hipMemsetAsync(skcnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
-      stg::gemm_launch_split(variant, skg, 0, g, stg::SplitPlan{skws.p, skcnt.p, sk_table_dev.p, sk_tab.stride});
-    } else if (f.kind == stg::GEMM_FORM_PLAIN)
-      stg::gemm_launch_plain(variant, (unsigned)f.tiles, 0, g, cus);
-    else if (f.kind == stg::GEMM_FORM_6432)
-      stg::k_dgemm_tn<64, 32><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 32)>>>(g);
-    else
-      stg::k_dgemm_tn<64, 64><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 64)>>>(g);
+    run.launch(g);
   }
   (void)hipEventRecord(e1, 0);
   hipError_t se = hipDeviceSynchronize();
-  skws.release(), skcnt.release();
+  run.ws.release(), run.cnt.release();
   float t = 0.f;
   (void)hipEventElapsedTime(&t, e0, e1);
   if (se != hipSuccess) return HQPKKT_E_DEVICE;
   if (getenv("HQPKKT_DGEMM_STAMPS")) {
-    if (f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, f, variant, skg, list, sk_tab, sk_table_dev.p);
-    if (f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(g, f.tiles, variant);
+    if (run.f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, run.f, run.L.variant, run.skg, run.list, run.tab, run.units.p);
+    if (run.f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(g, run.f.tiles, run.L.variant);
   }
   k_gemm_check<<<16, 256>>>(g, 4096, err.p);
   double he = 0.0;
@@ -532,11 +555,60 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   if (max_err) *max_err = he;
   return 0;
 }
+// One product on the caller's operands, all of C back (include/hqpkkt.h): launches and copies, compares nothing
+static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
+  if (!c || !c->C) return HQPKKT_E_NULL;
+  const int M = c->M, N = c->N, K = c->K, K2 = c->K2;
+  if (M <= 0 || N <= 0 || K < 0 || K2 < 0) return HQPKKT_E_RANGE;
+  if ((c->lower && M < N) || (c->mirror && !c->lower)) return HQPKKT_E_RANGE;  // (the image of a triangle, or of the column strip of one)
+  if (c->flags & ~(stg::GEMM_SHARDED | stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP | stg::GEMM_FORCE_SPLIT)) return HQPKKT_E_RANGE;
+  // an operand of k rows and w columns: inside its rows, and one row allocated behind those read (a 16-byte load of the
+  // register-staged loop reaches one column past an odd leading dimension)
+  auto operand_ok = [](const hqpkkt_dgemm_operand &o, int k, int w) {
+    return k == 0 || (o.p && o.ld >= 1 && o.col0 >= 0 && o.col0 + w <= o.ld && o.rows >= (long long)k + 1);
+  };
+  if (!operand_ok(c->A, K, M) || !operand_ok(c->B, K, N) || !operand_ok(c->A2, K2, M) || !operand_ok(c->B2, K2, N)) return HQPKKT_E_RANGE;
+  const int wc = c->mirror ? std::max(M, N) : N;  // (the image of a column strip reaches column M)
+  if (c->ldc < 1 || c->c_row0 < 0 || c->c_col0 < 0 || c->c_col0 + wc > c->ldc || c->c_row0 + M > c->c_rows) return HQPKKT_E_RANGE;
+  const bool beta = c->beta != 0.0, cin_own = beta && !c->cin_is_c;
+  if (cin_own && !(c->Cin.p && c->Cin.ld >= 1 && c->Cin.col0 >= 0 && c->Cin.col0 + N <= c->Cin.ld && c->Cin.rows >= M)) return HQPKKT_E_RANGE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  DBuf<double> dA, dB, dA2, dB2, dCin, dC;
+  auto up = [](DBuf<double> &d, const double *p, long long elems) -> int {
+    if (d.alloc((size_t)elems)) return HQPKKT_E_MEM;
+    HIPCHK(hipMemcpy(d.p, p, sizeof(double) * (size_t)elems, hipMemcpyHostToDevice));
+    return 0;
+  };
+  int e;
+  if (K > 0 && ((e = up(dA, c->A.p, c->A.rows * c->A.ld)) || (e = up(dB, c->B.p, c->B.rows * c->B.ld)))) return e;
+  if (K2 > 0 && ((e = up(dA2, c->A2.p, c->A2.rows * c->A2.ld)) || (e = up(dB2, c->B2.p, c->B2.rows * c->B2.ld)))) return e;
+  if (cin_own && (e = up(dCin, c->Cin.p, c->Cin.rows * c->Cin.ld))) return e;
+  if ((e = up(dC, c->C, c->c_rows * c->ldc))) return e;
+  stg::GemmArgs g{};
+  if (K > 0) g.A = dA.p + c->A.col0, g.lda = c->A.ld, g.B = dB.p + c->B.col0, g.ldb = c->B.ld;
+  if (K2 > 0) g.A2 = dA2.p + c->A2.col0, g.lda2 = c->A2.ld, g.B2 = dB2.p + c->B2.col0, g.ldb2 = c->B2.ld, g.K2 = K2;
+  g.C = dC.p + c->c_row0 * c->ldc + c->c_col0, g.ldc = c->ldc;
+  if (beta) g.Cin = cin_own ? dCin.p + c->Cin.col0 : g.C, g.ldcin = cin_own ? c->Cin.ld : c->ldc;
+  g.M = M, g.N = N, g.K = K, g.alpha = c->alpha, g.beta = c->beta, g.lower = c->lower ? 1 : 0, g.mirror = c->mirror ? 1 : 0;
+  DebugGemm run;
+  if ((e = run.prepare(device, g, c->flags))) return e;
+  run.launch(g);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(c->C, dC.p, sizeof(double) * (size_t)(c->c_rows * c->ldc), hipMemcpyDeviceToHost));
+  c->form = run.f.kind, c->tile_map = g.tile_map != nullptr, c->ldsdma = g.zeros != nullptr, c->nsplit = run.f.nsplit;
+  c->tiles = run.f.tiles;
+  return 0;
+}
 int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
   return debug_dgemm(device, M, N, K, 0, lower, mirror, reps, ms, max_err, nullptr);
 }
 int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym) {
   return debug_dgemm(device, M, N, K, K2, lower, mirror, reps, ms, max_err, asym);
+}
+int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
+  return guarded([&]() -> int { return debug_dgemm_full(device, c); });
 }
 
 int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,

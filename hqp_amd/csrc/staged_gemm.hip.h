@@ -738,4 +738,67 @@ static inline int gemm_variant_from_env() {
   if (w && atoi(w) == 4) return GEMM_DMA4;
   return GEMM_DMA8;
 }
+
+// What st_gemm (staged_host.hip.h), hqpkkt_debug_dgemm and hqpkkt_debug_dgemm_full (staged_engine.hip) share besides the
+// launch rule: when the operands may be staged by LDS-DMA, the tile order of a triangle, and the launch of a form.
+
+// Operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd column
+// (the control columns F + nn of a stage with an odd number of states) or has an odd leading dimension is staged
+// through registers (GemmArgs::zeros stays null)
+static inline bool gemm_operands_dma_ok(const GemmArgs &g) {
+  return ((((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) == 0) && (((g.lda | g.ldb | g.lda2 | g.ldb2) & 1) == 0);
+}
+// The 128 x 128 kernel of a launch: the handle's variant, and the register-staged one for operands without a zero row -
+// the LDS-DMA kernels read GemmArgs::zeros for every row k >= K and behind the last slab
+static inline int gemm_variant_for(const GemmArgs &g, int variant) { return g.zeros ? variant : GEMM_REG4; }
+// Order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map): super-blocks of 8 x 8 tiles,
+// row by row; inside a block column by column
+static inline std::vector<int> gemm_tri_order(int T) {
+  std::vector<int> m;
+  m.reserve((size_t)T * (T + 1) / 2);
+  const int S = 8;
+  for (int I = 0; I < (T + S - 1) / S; I++)
+    for (int J = 0; J <= I; J++)
+      for (int tn = J * S; tn < std::min(T, (J + 1) * S); tn++)
+        for (int tm = std::max(I * S, tn); tm < std::min(T, (I + 1) * S); tm++) m.push_back(tm << 16 | tn);
+  return m;
+}
+// Workspace of the thin product cut in k (GEMM_FORM_KS): its pieces' raw sums, M x N each
+static inline long long gemm_ks_ws_elems(const GemmArgs &g, const GemmForm &f) { return (long long)f.nsplit * g.M * g.N; }
+// What the launch of a form needs besides the product: the 128 x 128 variant, the CUs (plain rounds of at most that many
+// tiles take the three-buffer kernel; 0: never), the grid of the cut forms with their list (sk null: a cut form whose
+// list's pieces the workspace does not hold runs as a plain round of whole tiles) and the pieces of a product cut in k
+struct GemmLaunch {
+  int variant, cus, grid;
+  const SplitPlan *sk;
+  double *ks_ws;
+};
+// Launches form f of g on stream s.  `around(launch)` runs every kernel launch (st_gemm: inside the handle's profile
+// brackets; the test hooks: as it is)
+template <class Around>
+static inline void gemm_launch_form(const GemmForm &f, const GemmLaunch &L, hipStream_t s, const GemmArgs &g, Around &&around) {
+  switch (f.kind) {
+    case GEMM_FORM_FRAC:
+    case GEMM_FORM_CUT:
+      if (L.sk) {
+        around([&]() { gemm_launch_split(L.variant, L.grid, s, g, *L.sk); });
+        break;
+      }
+      [[fallthrough]];
+    case GEMM_FORM_PLAIN:
+      around([&]() { gemm_launch_plain(L.variant, (unsigned)f.tiles, s, g, L.cus); });
+      break;
+    case GEMM_FORM_KS:
+      around([&]() { k_dgemm_tn_ks<64, 64><<<dim3((unsigned)f.tiles, f.nsplit), 256, gemm_lds_bytes(64, 64), s>>>(g, L.ks_ws, f.nsplit); });
+      around([&]() { k_dgemm_ks_finish<<<(unsigned)(((long long)g.M * g.N + 255) / 256), 256, 0, s>>>(g, L.ks_ws, f.nsplit); });
+      break;
+    case GEMM_FORM_6432:
+      around([&]() { k_dgemm_tn<64, 32><<<(unsigned)f.tiles, 256, gemm_lds_bytes(64, 32), s>>>(g); });
+      break;
+    case GEMM_FORM_6464:
+      around([&]() { k_dgemm_tn<64, 64><<<(unsigned)f.tiles, 256, gemm_lds_bytes(64, 64), s>>>(g); });
+      break;
+    default: break;  // (GEMM_FORM_NONE: nothing to launch)
+  }
+}
 }  // namespace stg

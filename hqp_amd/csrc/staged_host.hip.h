@@ -76,13 +76,7 @@ struct StagedDev {
     for (auto &e : tri_maps)
       if (e.first == T) return e.second.p;
     if (!create) return nullptr;  // (made at upload time: no allocation inside a captured sequence)
-    std::vector<int> m;
-    m.reserve((size_t)T * (T + 1) / 2);
-    const int S = 8;  // super-blocks of 8 x 8 tiles, row by row; inside a block column by column
-    for (int I = 0; I < (T + S - 1) / S; I++)
-      for (int J = 0; J <= I; J++)
-        for (int tn = J * S; tn < std::min(T, (J + 1) * S); tn++)
-          for (int tm = std::max(I * S, tn); tm < std::min(T, (I + 1) * S); tm++) m.push_back(tm << 16 | tn);
+    const std::vector<int> m = stg::gemm_tri_order(T);
     DBuf<int> b;
     if (b.upload(m)) return nullptr;
     tri_maps.emplace_back(T, std::move(b));
@@ -208,46 +202,26 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
   const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, Kf, d.sk_grid, d.sk_tiles) : d.gemm_form(g.M, g.N, Kf, g.lower, g.mirror, allow_sk);
   if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_INTERN;
   if (f.tile_map) g.tile_map = d.tri_map((g.M + 127) / 128);
-  // operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd
-  // column (the control columns F + nn of a stage with an odd number of states) is staged through registers
-  if (d.zeros.p && ((((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) == 0) && (((g.lda | g.ldb | g.lda2 | g.ldb2) & 1) == 0))
-    g.zeros = d.zeros.p;
+  // operands by LDS-DMA only from 16-byte aligned rows; the others are staged through registers
+  if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
   // (the second segment exists in the 128 x 128 LDS-DMA kernels alone: StagedDev::fused holds only stages that get them)
   if (g.K2 > 0 && !(g.zeros && (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT || f.kind == stg::GEMM_FORM_PLAIN))) return HQPKKT_E_INTERN;
   if (h->listing) {  // upload's dry walk: what this launch will look up is made, nothing is launched
     if (f.tile_map && !d.tri_map((g.M + 127) / 128, true)) return HQPKKT_E_MEM;
     return f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT ? d.sk_tab_prepare(f, nslab) : 0;
   }
-  const int variant = ntiles && !g.zeros ? stg::GEMM_REG4 : d.gemm_variant;
-  double *ws = allow_sk ? d.sk_ws.p : d.ks_ws2.p;
-  switch (f.kind) {
-    case stg::GEMM_FORM_FRAC:
-    case stg::GEMM_FORM_CUT: {
-      // the list the shape was given at upload (the arrival counters are zero between launches: the last arriver of a
-      // tile resets its).  A shape without one is no reason to take another schedule
-      StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
-      if (!tab) return HQPKKT_E_INTERN;
-      tab->hits++;
-      if (tab->list != stg::SK_LIST_NONE) {
-        const stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, tab->units.p, tab->stride};
-        KLAUNCH(h, cls, stg::gemm_launch_split(variant, d.sk_grid, h->stream, g, sk));
-        break;
-      }
-      [[fallthrough]];  // (the workspace holds no list's pieces: a plain round)
-    }
-    case stg::GEMM_FORM_PLAIN:
-      KLAUNCH(h, cls, stg::gemm_launch_plain(variant, (unsigned)f.tiles, h->stream, g, d.cus));
-      break;
-    case stg::GEMM_FORM_KS:
-      KLAUNCH(h, cls, (stg::k_dgemm_tn_ks<64, 64><<<dim3((unsigned)f.tiles, f.nsplit), 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g, ws, f.nsplit)));
-      KLAUNCH(h, cls, stg::k_dgemm_ks_finish<<<nblk((long long)g.M * g.N), 256, 0, h->stream>>>(g, ws, f.nsplit));
-      break;
-    case stg::GEMM_FORM_6432:
-      KLAUNCH(h, cls, (stg::k_dgemm_tn<64, 32><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 32), h->stream>>>(g)));
-      break;
-    default:
-      KLAUNCH(h, cls, stg::k_dgemm_tn<64, 64><<<(unsigned)f.tiles, 256, stg::gemm_lds_bytes(64, 64), h->stream>>>(g));
+  // (the arrival counters of the cut forms are zero between launches: the last arriver of a tile resets its)
+  stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, nullptr, 0};
+  stg::GemmLaunch L{stg::gemm_variant_for(g, d.gemm_variant), d.cus, d.sk_grid, nullptr, allow_sk ? d.sk_ws.p : d.ks_ws2.p};
+  if (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT) {
+    // the list the shape was given at upload.  A shape without one is no reason to take another schedule; a list of
+    // SK_LIST_NONE - the workspace holds no list's pieces - is a plain round
+    StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
+    if (!tab) return HQPKKT_E_INTERN;
+    tab->hits++;
+    if (tab->list != stg::SK_LIST_NONE) sk.table = tab->units.p, sk.stride = tab->stride, L.sk = &sk;
   }
+  stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
   return 0;
 }
 

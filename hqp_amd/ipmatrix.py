@@ -479,6 +479,34 @@ def bench_dgemm2(M, N, K, K2, lower=True, mirror=True, reps=1, device=0):
     return ms.value, err.value, asym.value
 
 
+def dgemm_full(M, N, K, C_buf, c_row0, c_col0, A=None, a_col0=0, B=None, b_col0=0, alpha=1.0, beta=0.0, Cin=None, cin_col0=0,
+               cin_is_c=False, lower=False, mirror=False, K2=0, A2=None, a2_col0=0, B2=None, b2_col0=0,
+               sharded=False, no_ks=False, no_tile_map=False, force_split=False, device=0):
+    """One launch of the STAGED engine's fp64 product on the caller's operands (hqpkkt_debug_dgemm_full): C_buf's block at
+    (c_row0, c_col0) = alpha (A'B + A2'B2) + beta Cin.  Every array is a C-contiguous float64 matrix, rows x leading
+    dimension; an operand's block starts at its column *_col0 and its rows behind K (K2) are the caller's to poison.
+    C_buf is overwritten with the whole device buffer after the launch.  Returns (form, tiles, tile order used, operands
+    staged by LDS-DMA, pieces of k)."""
+    import numpy as np
+
+    def operand(x, col0):
+        if x is None:
+            return _lib.DgemmOperand(None, 0, 0, 0)
+        assert x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous
+        return _lib.DgemmOperand(x.ctypes.data, x.shape[0], x.shape[1], col0)
+
+    assert C_buf.dtype == np.float64 and C_buf.ndim == 2 and C_buf.flags.c_contiguous and C_buf.flags.writeable
+    c = _lib.DgemmCase()
+    c.M, c.N, c.K, c.K2 = M, N, K, K2
+    c.lower, c.mirror, c.cin_is_c = int(lower), int(mirror), int(cin_is_c)
+    c.flags = sharded * 1 | no_ks * 8 | no_tile_map * 16 | force_split * 32
+    c.alpha, c.beta = alpha, beta
+    c.A, c.B, c.A2, c.B2, c.Cin = operand(A, a_col0), operand(B, b_col0), operand(A2, a2_col0), operand(B2, b2_col0), operand(Cin, cin_col0)
+    c.C, c.c_rows, c.ldc, c.c_row0, c.c_col0 = C_buf.ctypes.data, C_buf.shape[0], C_buf.shape[1], c_row0, c_col0
+    _check(_lib.lib().hqpkkt_debug_dgemm_full(device, C.byref(c)), "debug_dgemm_full")
+    return GEMM_FORMS[c.form], c.tiles, bool(c.tile_map), bool(c.ldsdma), c.nsplit
+
+
 SK_KINDS = ("unequal", "equal", "frac")
 
 

@@ -383,6 +383,37 @@ int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, i
  * that are not bit-identical to their mirror image. */
 int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int mirror, int reps, double *ms, double *max_err, long long *asym);
 
+/* Test hook: ONE launch of that product on the caller's operands, in the form the engine's launch rule gives the shape and
+ * through the engine's own launch code, and the whole of the C buffer back.  Nothing is compared in the library: it
+ * copies, launches and copies.  C (M x N) = alpha (A'B + A2'B2) + beta Cin.
+ * An operand is a host buffer of rows x ld doubles, row-major; the kernel's pointer is p + col0 and its leading dimension
+ * ld (both may be odd: such operands are staged through registers instead of by LDS-DMA).  A, A2: K, K2 rows of M
+ * columns; B, B2: K, K2 rows of N columns; rows must be at least K + 1 (K2 + 1): the caller may fill the rows behind K,
+ * which no result may depend on, and a 16-byte load may reach one element past row K - 1.  Cin: M rows of N columns, read
+ * when beta != 0; cin_is_c != 0: the product is in place, Cin is the C block itself.
+ * C: c_rows x ldc doubles, the block starts at row c_row0, column c_col0.  The whole buffer goes to the device before the
+ * launch and comes back after it, so the caller sees every element the launch wrote, inside the block or not.
+ * flags: as hqpkkt_debug_gemm_form's 1, 8, 16, 32; 0 is the engine's rule on one GPU.  HQPKKT_NO_LDSDMA, HQPKKT_DGEMM_WAVES and
+ * HQPKKT_SK_TABLE are honoured as by hqpkkt_debug_dgemm.
+ * Out: form (hqpkkt_debug_gemm_form's numbering), tiles, nsplit (pieces of the k range of the thin-deep form), tile_map
+ * (the launch walked the tile order of a large triangle), ldsdma (the operands were staged by LDS-DMA).
+ * HQPKKT_E_RANGE: a shape, an operand layout or a form the kernels do not take; HQPKKT_E_MEM: an allocation failed. */
+typedef struct hqpkkt_dgemm_operand {
+  const double *p;
+  long long rows, ld, col0;
+} hqpkkt_dgemm_operand;
+typedef struct hqpkkt_dgemm_case {
+  int M, N, K, K2;
+  int lower, mirror, flags, cin_is_c;
+  double alpha, beta;
+  hqpkkt_dgemm_operand A, B, A2, B2, Cin;
+  double *C;
+  long long c_rows, ldc, c_row0, c_col0;
+  int form, tile_map, ldsdma, nsplit; /* out */
+  long long tiles;                    /* out */
+} hqpkkt_dgemm_case;
+int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c);
+
 /* Test hook, host only (no device needed): a work list of the cut forms of that product (k_dgemm_tn_sk walks one list
  * per workgroup, whatever the schedule) for `tiles` tiles of `nslab` k-slabs on `grid` workgroups, sk_table.hpp.
  * kind 0: unequal shares for the two workgroups of a CU; 1: equal shares, whole rounds and cut phases; 2: the fractional

@@ -51,8 +51,5 @@ def test_c4_shape_has_pieces_across_the_boundary():
 
 def test_not_lower_and_not_mirrored():
     for (m, n, k1, k2, lower, mirror) in [(5000, 5050, 1000, 50, 0, 0), (5050, 5050, 500, 33, 1, 0)]:
-        ms = ipmatrix.C.c_double()
-        err = ipmatrix.C.c_double()
-        asym = ipmatrix.C.c_longlong()
-        rc = ipmatrix._lib.lib().hqpkkt_debug_dgemm2(0, m, n, k1, k2, lower, mirror, 1, ipmatrix.C.byref(ms), ipmatrix.C.byref(err), ipmatrix.C.byref(asym))
-        assert rc == 0 and err.value <= 1e-14, (m, n, k1, k2, rc, err.value)
+        ms, err, asym = ipmatrix.bench_dgemm2(m, n, k1, k2, lower=bool(lower), mirror=bool(mirror), reps=1)  # (raises unless the status is 0)
+        assert err <= 1e-14, (m, n, k1, k2, err)

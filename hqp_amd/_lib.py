@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("HQPKKT_LIB") or os.path.join(_HERE, "libhqpkkt.so")  
 OK, E_SIZES, E_MEM, E_SING, E_FORMAT, E_NULL, E_RANGE, E_INTERN, E_DEVICE = 0, 1, 3, 4, 6, 8, 10, 17, 100
 MODE_FULL, MODE_REDUCED, MODE_STAGED = 0, 1, 2
 LOC_HOST, LOC_DEVICE = 0, 1
-DYN_DENSE, DYN_SPARSE = 0, 1
+DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
 
 # every symbol include/hqpkkt.h declares
 SYMBOLS = [
@@ -31,6 +31,7 @@ SYMBOLS = [
     "hqpkkt_analyze_staged", "hqpkkt_set_values_staged", "hqpkkt_set_shard_stream",
     "hqpkkt_values_staging", "hqpkkt_detect_stages", "hqpkkt_stage_staging", "hqpkkt_set_stage_block",
     "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
+    "hqpkkt_debug_sk_profile", "hqpkkt_debug_gemv_profile",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -85,7 +86,8 @@ class DgemmCase(C.Structure):
                 ("alpha", C.c_double), ("beta", C.c_double),
                 ("A", DgemmOperand), ("B", DgemmOperand), ("A2", DgemmOperand), ("B2", DgemmOperand), ("Cin", DgemmOperand),
                 ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong), ("c_row0", C.c_longlong), ("c_col0", C.c_longlong),
-                ("form", C.c_int), ("tile_map", C.c_int), ("ldsdma", C.c_int), ("nsplit", C.c_int), ("tiles", C.c_longlong)]
+                ("form", C.c_int), ("tile_map", C.c_int), ("ldsdma", C.c_int), ("nsplit", C.c_int), ("tiles", C.c_longlong),
+                ("krange", C.c_void_p), ("krange_by", C.c_int)]
 
 
 class IpResult(C.Structure):
@@ -160,6 +162,8 @@ def lib():
     L.hqpkkt_debug_dgemm_full.argtypes = [C.c_int, C.POINTER(DgemmCase)]
     L.hqpkkt_debug_sk_table.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hqpkkt_debug_sk_profile.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong)]
+    L.hqpkkt_debug_gemv_profile.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, C.c_longlong, vp, vp, vp, C.c_double, vp]
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_debug_factor_block.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 7

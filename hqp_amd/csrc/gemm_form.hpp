@@ -1,4 +1,4 @@
-// The launch rule of the STAGED engine's dense fp64 product C = A'B (staged_gemm.hip.h): which of its six forms an
+// The launch rule of the STAGED engine's dense fp64 product C = A'B (staged_gemm.hip.h): which of its forms an
 // M x N x K product takes, with how many tiles, and whether it wants a tile order.  Plain C++ (no device code, no HIP
 // call, no allocation): st_gemm - at a launch and in upload's dry walk of the factor sequence - and hqpkkt_debug_dgemm
 // decide here, and the CPU tests see the decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a
@@ -65,8 +65,10 @@ static inline bool gemm_tiles_6432(int M, int N, int K, int lower, int mirror, i
 // NONE: nothing to launch, or lower with M < N (lower: a triangle, or the column strip of one).  FRAC: k_dgemm_tn_sk by the
 // fractional list, the k-slabs of all tiles in one sequence, an equal share per workgroup; CUT: k_dgemm_tn_sk by a list of
 // whole tiles and cut ones, unequal or equal shares; PLAIN: one 128 x 128 tile per workgroup (gemm_launch_plain); KS: a thin, deep product on
-// 64 x 64 tiles, its k range cut over the chip (k_dgemm_tn_ks); 6432, 6464: 64 x 32 and 64 x 64 tiles
-enum GemmFormKind { GEMM_FORM_NONE = -1, GEMM_FORM_FRAC, GEMM_FORM_CUT, GEMM_FORM_PLAIN, GEMM_FORM_KS, GEMM_FORM_6432, GEMM_FORM_6464 };
+// 64 x 64 tiles, its k range cut over the chip (k_dgemm_tn_ks); 6432, 6464: 64 x 32 and 64 x 64 tiles; PROFILE: k_dgemm_tn_sk
+// on 128 x 128 tiles by a list in which every tile takes a k range of its own (gemm_profile_table) - never the rule's
+// answer: the profile form of the stage products asks for it (gemm_form_profile)
+enum GemmFormKind { GEMM_FORM_NONE = -1, GEMM_FORM_FRAC, GEMM_FORM_CUT, GEMM_FORM_PLAIN, GEMM_FORM_KS, GEMM_FORM_6432, GEMM_FORM_6464, GEMM_FORM_PROFILE };
 // What the rule depends on besides the shape and the device: one system over several ranks; a launch of the second stream
 // (the split forms' workspace belongs to the first).  The last three are off in every launch of the engine; the self-test
 // (hqpkkt_debug_dgemm) sets them so that it launches what it always has: never the thin product cut in k, never a tile
@@ -125,6 +127,17 @@ static inline GemmForm gemm_form_tiles(long long ntiles, int K, int grid, long l
   GemmForm f;
   f.tiles = ntiles;
   f.kind = gemm_use_split_tiles(ntiles, gemm_slabs(K), grid) && ntiles <= sk_tiles ? GEMM_FORM_CUT : GEMM_FORM_PLAIN;
+  return f;
+}
+// ... and a product whose tiles take k ranges of their own (the profile form): 128 x 128 tiles whatever their number,
+// the tile order of a large triangle as the rule above wants it
+static inline GemmForm gemm_form_profile(int M, int N, int lower, int flags = 0) {
+  GemmForm f;
+  if (M <= 0 || N <= 0 || (lower && M < N)) return f;
+  const long long tm = (M + 127) / 128;
+  f.kind = GEMM_FORM_PROFILE;
+  f.tiles = gemm_tiles(M, N, 128, lower);
+  f.tile_map = !(flags & GEMM_NO_TILE_MAP) && lower && M == N && tm >= 16 && tm < 32768;
   return f;
 }
 }  // namespace stg

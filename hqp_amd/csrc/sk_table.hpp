@@ -1,7 +1,8 @@
 // Host side of the cut form of the STAGED engine's fp64 product (k_dgemm_tn_sk, staged_gemm.hip.h): the kernel walks a
 // list of units of work per workgroup, and every schedule is such a list, made here - unequal shares for the two
 // workgroups of a CU (gemm_split_table), equal shares in whole rounds and cut phases (gemm_equal_table), the k-slabs of
-// all tiles as one sequence (gemm_frac_table) - and chosen in one place (gemm_choose_list).  Plain C++ (no device code):
+// all tiles as one sequence (gemm_frac_table), the same for tiles of unequal length (gemm_profile_table) - and chosen in
+// one place (gemm_choose_list).  Plain C++ (no device code):
 // used by staged_gemm.hip.h and the engine's host code and, through hqpkkt_debug_sk_table, by the CPU tests.
 #pragma once
 #include <algorithm>
@@ -233,6 +234,44 @@ static inline bool gemm_frac_table(long long tiles, long long nslab, int grid, S
       x += s1 - s0;
     }
   }
+  sk_table_pack(per, slots, out);
+  return true;
+}
+// The same for tiles of UNEQUAL length (the profile form of the stage products, staged_plan.hpp: a tile of W = V+ F or
+// G = F'W takes only the k-slabs that hold the stored entries of its panel of F_k): tile t takes the slabs
+// [ranges[2 t], ranges[2 t + 1]).  The slabs of all tiles form one sequence in the launch's tile order, every workgroup
+// gets an equal, contiguous share of it (the workgroup at position v after the XCD swizzle the v-th), a tile that several
+// workgroups share is parked and summed by its last arriver in the order of k, and a workgroup parks at most two
+// tiles: at most 2 grid slots.  A tile without slabs is still one unit (s0 = s1, pieces = 1) of the workgroup at whose
+// position in the sequence it stands: its zeros must be written.
+// A tile weighs its slabs and nothing else: no constant for its pipeline fill and epilogue (none was measured; with
+// one a workgroup's share of slabs is no longer bounded by ceil(total / grid)).
+static inline bool gemm_profile_table(const int *ranges, long long tiles, int grid, SplitTable &out) {
+  if (grid < 1 || tiles <= 0 || !ranges) return false;
+  std::vector<long long> pre(tiles + 1, 0);
+  for (long long t = 0; t < tiles; t++) {
+    const long long lo = ranges[2 * t], hi = ranges[2 * t + 1];
+    if (lo < 0 || hi < lo || hi >= 65536) return false;
+    pre[t + 1] = pre[t] + (hi - lo);
+  }
+  const long long U = pre[tiles], share = std::max<long long>(1, (U + grid - 1) / grid);
+  std::vector<std::vector<SkUnit>> pos(grid), per(grid);
+  long long slots = 0;
+  for (long long t = 0; t < tiles; t++) {
+    const long long lo = ranges[2 * t], len = pre[t + 1] - pre[t];
+    if (len == 0) {
+      pos[std::min<long long>(grid - 1, pre[t] / share)].push_back(SkUnit{(int)t, (unsigned short)lo, (unsigned short)lo, 0, 1, 0});
+      continue;
+    }
+    const long long first = pre[t] / share, last = (pre[t + 1] - 1) / share, pieces = last - first + 1;
+    for (long long v = first; v <= last; v++) {
+      const long long x0 = std::max(pre[t], v * share), x1 = std::min(pre[t + 1], (v + 1) * share);
+      pos[v].push_back(SkUnit{(int)t, (unsigned short)(lo + x0 - pre[t]), (unsigned short)(lo + x1 - pre[t]), (int)(pieces > 1 ? slots : 0),
+                              (unsigned short)pieces, (unsigned short)(v - first)});
+    }
+    if (pieces > 1) slots += pieces;
+  }
+  for (int b = 0; b < grid; b++) per[b] = pos[xcd_swizzle_host(b, grid)];
   sk_table_pack(per, slots, out);
   return true;
 }

@@ -6,6 +6,7 @@
 
 #include "staged.hip.h"
 #include "staged_sparse.hip.h"
+#include "staged_profile.hip.h"
 #include "staged_host.hip.h"
 
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn) {
@@ -100,7 +101,7 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       out.assign(P.K + 1, 0);
       for (size_t k = 0; k < h->sd->fused.size() && k < out.size(); k++) out[k] = h->sd->fused[k];
       break;
-    case 36:  // per stage k < K: stored entries of F_k, and 1 where the stage runs the sparse sequence (staged_stage_sparse)
+    case 36:  // per stage k < K: stored entries of F_k, and 1 where the stage runs the sparse sequence (staged_stage_sparse), 2: the profile sequence
       for (int k = 0; k < P.K; k++) {
         long long nnz = 0;
         if (P.sparse_dyn)
@@ -109,7 +110,7 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
           nnz = (long long)(h->pAp[P.nks[k + 1]] - h->pAp[P.nks[k]]) - P.nk[k + 1];
         else
           nnz = (long long)P.nk[k + 1] * (P.nk[k] + P.mk[k]);  // (dense hand-over: the whole block)
-        out.push_back((int)std::min<long long>(nnz, 0x7fffffff)), out.push_back(P.sparse_dyn ? 1 : 0);
+        out.push_back((int)std::min<long long>(nnz, 0x7fffffff)), out.push_back(P.sparse_dyn ? 1 : P.profile_dyn && P.pf_stage[k] ? 2 : 0);
       }
       break;
     case 37:  // the sparse form's ranges (host only): [first, end) into A's CSR arrays per dynamics row, then [first, end) into
@@ -121,6 +122,11 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
               // local to the stage (states, then controls), ascending; empty on a dense-form handle
       out = P.hv_ptr;
       out.insert(out.end(), P.hv_cols.begin(), P.hv_cols.end());
+      break;
+    case 41:  // the profile form's ranges (host only): K + 1 pointers, then the (lo, hi) k-slab pairs of every stage's 128-column
+              // panels of F_k; empty unless the profile form is set
+      out = P.pf_ptr;
+      out.insert(out.end(), P.pf_rng.begin(), P.pf_rng.end());
       break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
@@ -138,9 +144,10 @@ int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form) {
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
     if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
-    if (form != HQPKKT_DYN_DENSE && form != HQPKKT_DYN_SPARSE) return HQPKKT_E_RANGE;
+    if (form != HQPKKT_DYN_DENSE && form != HQPKKT_DYN_SPARSE && form != HQPKKT_DYN_PROFILE) return HQPKKT_E_RANGE;
     if (!h->sd) h->sd.reset(new StagedDev);
     h->sd->plan.want_sparse = form == HQPKKT_DYN_SPARSE;  // (the next hqpkkt_analyze picks it up)
+    h->sd->plan.want_profile = form == HQPKKT_DYN_PROFILE;
     return 0;
   });
 }
@@ -179,7 +186,7 @@ int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int 
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
     if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
-    if (h->sd && h->sd->plan.want_sparse) return HQPKKT_E_INTERN;  // (HQPKKT_DYN_SPARSE: the CSR hand-over alone)
+    if (h->sd && (h->sd->plan.want_sparse || h->sd->plan.want_profile)) return HQPKKT_E_INTERN;  // (HQPKKT_DYN_SPARSE, _PROFILE: the CSR hand-over alone)
     int e = hqpkkt_set_stages(h, K, nx, nu);
     if (e) return e;
     if (K < 1) return HQPKKT_E_RANGE;
@@ -453,7 +460,8 @@ struct DebugGemm {
   int list = stg::SK_LIST_NONE, cus = 0, skg = 0;
   bool use_sk = false;
   // completes g (zeros, tile_map) and makes what its launch looks up; flags: stg::GEMM_SHARDED, GEMM_NO_KS, GEMM_NO_TILE_MAP, GEMM_FORCE_SPLIT
-  int prepare(int device, stg::GemmArgs &g, int flags) {
+  // krange / krange_by: the profile form (hqpkkt_dgemm_case): two ints per 128-wide panel of B (1) or A (2)
+  int prepare(int device, stg::GemmArgs &g, int flags, const int *krange = nullptr, int krange_by = 0) {
     const int variant = stg::gemm_variant_from_env();
     if (variant != stg::GEMM_REG4 && stg::gemm_operands_dma_ok(g)) {
       if (zr.alloc(256)) return HQPKKT_E_MEM;
@@ -465,7 +473,14 @@ struct DebugGemm {
     skg = stg::gemm_wgs_per_cu(variant) * cus;
     const long long t128 = stg::gemm_tiles(g.M, g.N, 128, g.lower), nslab = stg::gemm_slabs_of(g);
     const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
-    f = stg::gemm_form(g.M, g.N, g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K, g.lower, g.mirror, cus, skg, t128, ws_elems, 0, flags);
+    if (krange_by) {
+      const int npanel = ((krange_by == 2 ? g.M : g.N) + 127) / 128;
+      if (!krange || (krange_by != 1 && krange_by != 2) || g.K2 > 0 || skg <= 0) return HQPKKT_E_RANGE;
+      for (int p = 0; p < npanel; p++)
+        if (krange[2 * p] < 0 || krange[2 * p + 1] < krange[2 * p] || krange[2 * p + 1] > nslab) return HQPKKT_E_RANGE;
+      f = stg::gemm_form_profile(g.M, g.N, g.lower, flags);
+    } else
+      f = stg::gemm_form(g.M, g.N, g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K, g.lower, g.mirror, cus, skg, t128, ws_elems, 0, flags);
     if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_RANGE;
     use_sk = f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT;
     if (g.K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
@@ -475,7 +490,16 @@ struct DebugGemm {
       g.tile_map = order.p;
     }
     L = stg::GemmLaunch{stg::gemm_variant_for(g, variant), cus, skg, nullptr, nullptr};
-    if (use_sk) {
+    if (f.kind == stg::GEMM_FORM_PROFILE) {
+      std::vector<int> ord;
+      if (f.tile_map) ord = stg::gemm_tri_order((g.M + 127) / 128);
+      const std::vector<int> r = stg::gemm_profile_tile_ranges(g.M, g.N, g.lower, f.tile_map ? ord.data() : nullptr, krange, krange_by);
+      if (!stg::gemm_profile_table(r.data(), f.tiles, skg, tab)) return HQPKKT_E_RANGE;
+      if (units.upload(tab.units) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 4)) return HQPKKT_E_MEM;
+      sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
+      L.sk = &sk;
+      use_sk = true;  // (launch() clears the arrival counters)
+    } else if (use_sk) {
       // (its one list by the engine's chooser: unequal shares for the two workgroups of a CU; HQPKKT_SK_TABLE=0 or one system over
       // several ranks: equal shares)
       list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, stg::gemm_sk_table_from_env() && !(flags & stg::GEMM_SHARDED), f.tiles, nslab, skg, t128, ws_elems, tab);
@@ -593,7 +617,7 @@ static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
   if (beta) g.Cin = cin_own ? dCin.p + c->Cin.col0 : g.C, g.ldcin = cin_own ? c->Cin.ld : c->ldc;
   g.M = M, g.N = N, g.K = K, g.alpha = c->alpha, g.beta = c->beta, g.lower = c->lower ? 1 : 0, g.mirror = c->mirror ? 1 : 0;
   DebugGemm run;
-  if ((e = run.prepare(device, g, c->flags))) return e;
+  if ((e = run.prepare(device, g, c->flags, c->krange, c->krange_by))) return e;
   run.launch(g);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(c->C, dC.p, sizeof(double) * (size_t)(c->c_rows * c->ldc), hipMemcpyDeviceToHost));
@@ -636,6 +660,61 @@ int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int kind, int *u
     }
   }
   return t.stride;
+}
+
+int hqpkkt_debug_sk_profile(const int *ranges, long long tiles, int grid, int *units, long long cap_ints, long long *pieces) {
+  stg::SplitTable t;
+  if (!stg::gemm_profile_table(ranges, tiles, grid, t)) return 0;
+  if (pieces) *pieces = t.pieces;
+  if (units) {
+    if ((long long)t.units.size() * 6 > cap_ints) return 0;
+    for (size_t i = 0; i < t.units.size(); i++) {
+      const stg::SkUnit &u = t.units[i];
+      int *o = units + 6 * i;
+      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
+    }
+  }
+  return t.stride;
+}
+
+// One launch of a product of the profile form's solve (staged_profile.hip.h) on the caller's host arrays
+static int debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
+                              const double *x, const double *add, double alpha, double *y) {
+  if (!A || !ranges || !x || !y) return HQPKKT_E_NULL;
+  if (K <= 0 || N <= 0 || a_rows < K || ld < N || (ld & 7)) return HQPKKT_E_RANGE;
+  const int np = (N + 127) / 128, nx = rows_form ? N : K, ny = rows_form ? K : N;
+  for (int p = 0; p < np; p++)
+    if (ranges[2 * p] < 0 || ranges[2 * p + 1] < ranges[2 * p] || ranges[2 * p + 1] > (K + 15) / 16) return HQPKKT_E_RANGE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  DBuf<double> dA, dx, dadd, dy, part;
+  DBuf<int> dr;
+  const int chunks = stg::pf_chunks(ranges, np, K);
+  const int guard = 64;  // doubles behind y on the device, checked after the launch: nothing may be written past y
+  const std::vector<double> mark(guard, -12345.678);
+  if (dA.alloc((size_t)(a_rows * ld)) || dx.alloc(nx) || dy.alloc(ny + guard) || (add && dadd.alloc(ny)) || part.alloc((size_t)chunks * N) ||
+      dr.upload(std::vector<int>(ranges, ranges + 2 * np)))
+    return HQPKKT_E_MEM;
+  HIPCHK(hipMemcpy(dA.p, A, sizeof(double) * (size_t)(a_rows * ld), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dx.p, x, sizeof(double) * nx, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dy.p, y, sizeof(double) * ny, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dy.p + ny, mark.data(), sizeof(double) * guard, hipMemcpyHostToDevice));
+  if (add) HIPCHK(hipMemcpy(dadd.p, add, sizeof(double) * ny, hipMemcpyHostToDevice));
+  const stg::PfGemv g{dA.p, ld, K, N, dr.p, dx.p, add ? dadd.p : nullptr, alpha, dy.p, part.p};
+  if (rows_form)
+    stg::pf_launch_rows(g, 0, [](auto &&kernel) { kernel(); });
+  else
+    stg::pf_launch_cols(g, ranges, 0, [](auto &&kernel) { kernel(); });
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(y, dy.p, sizeof(double) * ny, hipMemcpyDeviceToHost));
+  std::vector<double> back(guard);
+  HIPCHK(hipMemcpy(back.data(), dy.p + ny, sizeof(double) * guard, hipMemcpyDeviceToHost));
+  return std::memcmp(back.data(), mark.data(), sizeof(double) * guard) ? HQPKKT_E_INTERN : 0;
+}
+int hqpkkt_debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
+                              const double *x, const double *add, double alpha, double *y) {
+  return guarded([&]() -> int { return debug_gemv_profile(device, rows_form, K, N, A, a_rows, ld, ranges, x, add, alpha, y); });
 }
 
 #ifdef HQPKKT_STAMPS

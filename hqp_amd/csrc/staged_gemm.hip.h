@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "sk_table.hpp"
 #include "gemm_form.hpp"
@@ -763,6 +764,39 @@ static inline std::vector<int> gemm_tri_order(int T) {
         for (int tm = std::max(I * S, tn); tm < std::min(T, (I + 1) * S); tm++) m.push_back(tm << 16 | tn);
   return m;
 }
+// GemmTile<128, 128>::tile_of on the host: tile index -> (tile row, tile column) of an M x N product on 128 x 128 tiles,
+// row by row in groups of eight tile rows, the rows of a triangle, or by the tile order `order` (gemm_tri_order)
+static inline void gemm_tile_of_host(int M, int N, int lower, const int *order, long long t, int &tm, int &tn) {
+  if (order) {
+    tm = order[t] >> 16, tn = order[t] & 0xffff;
+  } else if (lower) {
+    const long long tcols = (N + 127) / 128, tri = tcols * (tcols + 1) / 2;
+    if (t < tri) {
+      tm = 0;
+      while ((long long)(tm + 1) * (tm + 2) / 2 <= t) tm++;
+      tn = (int)(t - (long long)tm * (tm + 1) / 2);
+    } else
+      tm = (int)(tcols + (t - tri) / tcols), tn = (int)((t - tri) % tcols);
+  } else {
+    const long long tiles_n = (N + 127) / 128, tiles_m = (M + 127) / 128, GM = 8;
+    const long long grp = t / (GM * tiles_n), first = grp * GM, rows = std::min(GM, tiles_m - first), in = t - grp * GM * tiles_n;
+    tm = (int)(first + in % rows), tn = (int)(in / rows);
+  }
+}
+// The k ranges of the tiles of a product in the profile form, two ints per tile in the launch's tile order: `panel`
+// holds the k-slab range [lo, hi) of every 128-wide column panel of the ranged operand, by = 1: B's (tile (tm, tn)
+// takes panel tn: W = V+ F), by = 2: A's (panel tm: G = F'W)
+static inline std::vector<int> gemm_profile_tile_ranges(int M, int N, int lower, const int *order, const int *panel, int by) {
+  const long long tiles = gemm_tiles(M, N, 128, lower);
+  std::vector<int> r(2 * (size_t)tiles);
+  for (long long t = 0; t < tiles; t++) {
+    int tm, tn;
+    gemm_tile_of_host(M, N, lower, order, t, tm, tn);
+    const int p = by == 2 ? tm : tn;
+    r[2 * t] = panel[2 * p], r[2 * t + 1] = panel[2 * p + 1];
+  }
+  return r;
+}
 // Workspace of the thin product cut in k (GEMM_FORM_KS): its pieces' raw sums, M x N each
 static inline long long gemm_ks_ws_elems(const GemmArgs &g, const GemmForm &f) { return (long long)f.nsplit * g.M * g.N; }
 // What the launch of a form needs besides the product: the 128 x 128 variant, the CUs (plain rounds of at most that many
@@ -787,6 +821,9 @@ static inline void gemm_launch_form(const GemmForm &f, const GemmLaunch &L, hipS
       [[fallthrough]];
     case GEMM_FORM_PLAIN:
       around([&]() { gemm_launch_plain(L.variant, (unsigned)f.tiles, s, g, L.cus); });
+      break;
+    case GEMM_FORM_PROFILE:  // (only by its list: a round of whole tiles would read what the ranges leave out)
+      if (L.sk) around([&]() { gemm_launch_split(L.variant, L.grid, s, g, *L.sk); });
       break;
     case GEMM_FORM_KS:
       around([&]() { k_dgemm_tn_ks<64, 64><<<dim3((unsigned)f.tiles, f.nsplit), 256, gemm_lds_bytes(64, 64), s>>>(g, L.ks_ws, f.nsplit); });

@@ -117,6 +117,34 @@ struct StagedDev {
     sk_tabs.push_back(std::move(e));
     return 0;
   }
+  // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device, the partial sums of the solve's
+  // columns product (stg::pf_chunks x columns of the widest stage), and the work lists of its two large products
+  // (stg::gemm_profile_table) by shape and range vector: equal vectors share a list - a time-invariant pattern has one
+  // for W and one for G.  Made in upload's dry walk and only looked up at a launch, like sk_tabs
+  DBuf<int> pf_rng;
+  DBuf<double> pf_part;
+  struct PfTab {
+    int M, N, lower, by, stride, hits;
+    std::vector<int> panel;  // the ranged operand's panels, two ints each
+    DBuf<stg::SkUnit> units;
+  };
+  std::vector<PfTab> pf_tabs;
+  PfTab *pf_tab(int M, int N, int lower, int by, const int *panel, int npanel) {
+    for (auto &e : pf_tabs)
+      if (e.M == M && e.N == N && e.lower == lower && e.by == by && (int)e.panel.size() == 2 * npanel && std::equal(e.panel.begin(), e.panel.end(), panel))
+        return &e;
+    return nullptr;
+  }
+  int pf_tab_prepare(const stg::GemmForm &f, int M, int N, int lower, int by, const int *order, const int *panel, int npanel) {
+    if (pf_tab(M, N, lower, by, panel, npanel)) return 0;
+    const std::vector<int> r = stg::gemm_profile_tile_ranges(M, N, lower, order, panel, by);
+    stg::SplitTable t;
+    if (f.tiles > sk_cnt_elems - 4 || !stg::gemm_profile_table(r.data(), f.tiles, sk_grid, t) || t.pieces * 128LL * 128 > sk_ws_elems) return HQPKKT_E_INTERN;
+    PfTab e{M, N, lower, by, t.stride, 0, std::vector<int>(panel, panel + 2 * npanel), {}};
+    if (int err = e.units.upload(t.units)) return err;
+    pf_tabs.push_back(std::move(e));
+    return 0;
+  }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
   long long sk_ws_elems = 0, sk_cnt_elems = 0;
 };
@@ -221,6 +249,34 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
     tab->hits++;
     if (tab->list != stg::SK_LIST_NONE) sk.table = tab->units.p, sk.stride = tab->stride, L.sk = &sk;
   }
+  stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
+  return 0;
+}
+
+// The same product in the profile form (gemm_form.hpp, GEMM_FORM_PROFILE): always k_dgemm_tn_sk on 128 x 128 tiles, every
+// tile over the k-slabs of its panel of the ranged operand alone - `panel`: stage k's ranges (host), by = 1: B's column
+// panels (W = V+ F), 2: A's (G = F'W).  The list is made in upload's dry walk and looked up here
+int st_gemm_profile(hqpkkt_t *h, stg::GemmArgs g, int k, int by, int cls = KC_ST_GEMM) {
+  if (g.M <= 0 || g.N <= 0) return 0;
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  const int *panel = P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], npanel = P.panels(k);
+  const stg::GemmForm f = stg::gemm_form_profile(g.M, g.N, g.lower);
+  if (f.kind != stg::GEMM_FORM_PROFILE || d.sk_grid <= 0 || npanel != ((by == 2 ? g.M : g.N) + 127) / 128) return HQPKKT_E_INTERN;
+  if (h->listing) {
+    const int T = (g.M + 127) / 128;
+    if (f.tile_map && !d.tri_map(T, true)) return HQPKKT_E_MEM;
+    std::vector<int> order;
+    if (f.tile_map) order = stg::gemm_tri_order(T);
+    return d.pf_tab_prepare(f, g.M, g.N, g.lower, by, f.tile_map ? order.data() : nullptr, panel, npanel);
+  }
+  if (f.tile_map && !(g.tile_map = d.tri_map((g.M + 127) / 128))) return HQPKKT_E_INTERN;
+  if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
+  StagedDev::PfTab *tab = d.pf_tab(g.M, g.N, g.lower, by, panel, npanel);
+  if (!tab) return HQPKKT_E_INTERN;
+  tab->hits++;
+  const stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, tab->units.p, tab->stride};
+  const stg::GemmLaunch L{stg::gemm_variant_for(g, d.gemm_variant), d.cus, d.sk_grid, &sk, nullptr};
   stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
   return 0;
 }
@@ -496,16 +552,16 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
-  const bool want_sparse = P.want_sparse;
+  const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
   const int want_heavy = P.want_heavy;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_heavy = want_heavy;
+  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
   P.sharded = h->shard_count > 1 || h->xchg_fn || h->xchg_sfn;
-  if (want_sparse && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over
-  if (want_sparse && P.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
+  if ((want_sparse || want_profile) && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over, the profile form reads its ranges off them
+  if ((want_sparse || want_profile) && P.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
   h->an.shard_rank = h->shard_rank, h->an.shard_count = 1;  // (the tree engine's exchange plan is not used)
   int e = h->an.setup_blocks(1, n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(),
                              h->pCp.data(), h->pCi.data());
@@ -668,6 +724,13 @@ static int staged_upload(hqpkkt_t *h) {
       // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
       d.sk_ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
       d.sk_cnt_elems = d.sk_tiles + 4;
+      // (the profile form's lists: a counter per tile of W and of the whole lower block G, at most two parked tiles per
+      // workgroup - 2 x grid slots, which the workspace above holds: pmax >= 4 cus + 64)
+      for (int k = 0; k < P.K && P.profile_dyn; k++)
+        if (P.pf_stage[k]) {
+          const long long t2 = (P.nk[k] + P.mk[k] + 127) / 128;
+          d.sk_cnt_elems = std::max(d.sk_cnt_elems, t2 * (t2 + 1) / 2 + 4);
+        }
       if ((e = d.sk_ws.alloc((size_t)d.sk_ws_elems)) || (e = d.sk_cnt.alloc((size_t)d.sk_cnt_elems))) return e;
       HIPCHK(hipMemset(d.sk_cnt.p, 0, sizeof(unsigned) * (size_t)d.sk_cnt_elems));
     }
@@ -683,6 +746,7 @@ static int staged_upload(hqpkkt_t *h) {
     if (mode != 0 && !P.sharded && !P.sparse_dyn && d.zeros.p)
       for (int k = 0; k < P.K; k++) {
         const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
+        if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
         if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0 || (mode != 1 && nn < FUSED_V_MIN_STATES)) continue;
         const long long nslab = stg::gemm_slabs(np) + stg::gemm_slabs(q);
         const stg::GemmForm f = d.gemm_form(nn, nn, (int)(nslab * stg::GEMM_BK), 1, 1);
@@ -795,6 +859,14 @@ static int staged_upload(hqpkkt_t *h) {
   // factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
   d.sk_tables_on = stg::gemm_sk_table_from_env();
   d.sk_tabs.clear();
+  d.pf_tabs.clear(), d.pf_rng.release(), d.pf_part.release();
+  if (P.profile_dyn && !P.pf_rng.empty()) {
+    long long part = 1;
+    for (int k = 0; k < P.K; k++)
+      if (P.pf_stage[k])
+        part = std::max(part, (long long)stg::pf_chunks(P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.panels(k), P.nk[k + 1]) * (P.nk[k] + P.mk[k]));
+    if ((e = d.pf_rng.upload(P.pf_rng)) || (e = d.pf_part.alloc((size_t)part))) return e;
+  }
   {
     struct Listing {
       hqpkkt_t *h;
@@ -1094,6 +1166,28 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
 
+// One stage of the backward recursion in the profile form (StagedPlan::pf_stage): the dense sequence on one stream with
+// its two large products by lists in which a tile takes only the k-slabs that hold its panel's stored entries of F_k -
+// W = V+ F (tile (tm, tn): the range of panel tn) and the whole lower block G = F'W (the range of panel tm) - and no V
+// formed in the G_xx launch.  The thin products (carried rows, the elimination's) stay full-depth dense products: they
+// read the arena's zeros.
+static int staged_stage_profile(hqpkkt_t *h, int k) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
+  const long long ldf = P.ldf[k], ldg = P.ldg[k], ldvn = P.ldv[k + 1];
+  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
+  int e;
+  if ((e = st_gemm_profile(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}, k, 1)) ||
+      (e = st_gemm_profile(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}, k, 2)))
+    return e;
+  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
+  if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
+  // V = Gxx - Y'Rm (lower tiles, mirrored)
+  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+}
+
 // the entries of the columns [c0, c0 + ncols) of F_k out of the CSR arrays of A' (staged_sparse.hip.h)
 // (light: the ranges in which the stage's heavy columns are empty, where it has some)
 static stg::SpCols sp_cols(hqpkkt_t *h, StagedDev &d, int k, int c0, int ncols, bool light = false) {
@@ -1179,7 +1273,11 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   }
   if (P.sharded && K > 0 && (e = staged_gather_f(h, K - 1))) return e;  // (stage k requests stage k - 1's)
   for (int k = K - 1; k >= 0; k--)
-    if ((e = P.sharded ? staged_stage_sharded(h, k) : P.sparse_dyn ? staged_stage_sparse(h, k) : d.fused[k] ? staged_stage_fused(h, k) : staged_stage_dense(h, k)))
+    if ((e = P.sharded                            ? staged_stage_sharded(h, k)
+             : P.sparse_dyn                       ? staged_stage_sparse(h, k)
+             : P.profile_dyn && P.pf_stage[k]     ? staged_stage_profile(h, k)
+             : d.fused[k]                         ? staged_stage_fused(h, k)
+                                                  : staged_stage_dense(h, k)))
       return e;
   {
     StagePtr s0 = stage_ptr(d, 0);
@@ -1275,6 +1373,9 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       if (const int nd = P.heavy_count(k))  // (the heavy columns: a wavefront each)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_heavy<<<(nd + 3) / 4, 256, 0, s>>>(stg::SpGemvHeavy{
                                          sp_cols(h, d, k, 0, nn + mm), d.hv_cols.p + P.hv_ptr[k], nd, tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
+    } else if (P.profile_dyn && P.pf_stage[k]) {  // gam = q_k + F' tt over the panels' slab ranges
+      stg::pf_launch_cols(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], tt, qv + P.nmk[k], 1.0, gam, d.pf_part.p},
+                          P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
     } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
     st_bwd_small(h, d, k, sp, sn, v.r2, gam);
@@ -1301,6 +1402,11 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       if (np > 0)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_rows<<<(np + 15) / 16, 256, 0, s>>>(stg::SpGemvRows{
                                          d.sp_arow.p + 2 * (long long)P.nks[k], h->td.A.col.p, h->td.A.val.p, P.nmk[k], np, xk, v.r2 + P.nks[k], S + P.nmk[k + 1], 1.0}));
+      continue;
+    }
+    if (P.profile_dyn && P.pf_stage[k]) {  // x+ = F s + f over the panels whose range holds the row
+      stg::pf_launch_rows(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], xk, v.r2 + P.nks[k], 1.0, S + P.nmk[k + 1], nullptr}, s,
+                          [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
       continue;
     }
     if (!sh) {  // x+ = F s + f (the multipliers p = V+ x+ + v+ + B+' eta+ behind the sweep)

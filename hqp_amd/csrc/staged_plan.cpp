@@ -63,6 +63,8 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   n = n_, m = m_;
   sparse_dyn = want_sparse;
   if (sparse_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
+  profile_dyn = want_profile && !want_sparse;
+  if (profile_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
   nq = n ? Qp[n] : 0, nc = m ? Cp[m] : 0;
   const int arows = me_;  // rows of the A that was handed over
   na = arows ? Ap[arows] : 0;
@@ -192,6 +194,32 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
             sp_tcol_light[2 * c + 1] = sp_tcol[2 * c];
           }
       hv_ptr[k + 1] = (int)hv_cols.size();
+    }
+  }
+
+  // ------------------------------------------------------------------ the profile form's slab ranges
+  pf_ptr.clear(), pf_rng.clear(), pf_stage.clear();
+  if (profile_dyn) {
+    pf_ptr.assign(K + 1, 0), pf_stage.assign(K, 0);
+    for (int k = 0; k < K; k++) {
+      const int nz = nk[k] + mk[k], np = (nz + 127) / 128, all = (nk[k + 1] + 15) / 16;
+      bool shorter = false;
+      for (int p = 0; p < np; p++) {
+        int first = -1, last = -1;  // dynamics rows of the stage, local
+        for (int c = nmk[k] + 128 * p; c < std::min(nmk[k] + 128 * (p + 1), nmk[k + 1]); c++) {
+          // (the rows of A' ascend: the stage's dynamics rows are one range of the column's entries)
+          const int *b = ATi + ATp[c], *e = ATi + ATp[c + 1];
+          const int *r0 = std::lower_bound(b, e, nks[k]), *r1 = std::lower_bound(b, e, nks[k + 1]);
+          if (r0 == r1) continue;
+          const int f = *r0 - nks[k], l = *(r1 - 1) - nks[k];
+          first = first < 0 ? f : std::min(first, f), last = std::max(last, l);
+        }
+        const int lo = first < 0 ? 0 : first / 16, hi = first < 0 ? 0 : last / 16 + 1;
+        pf_rng.push_back(lo), pf_rng.push_back(hi);
+        shorter = shorter || hi - lo < all;
+      }
+      pf_ptr[k + 1] = pf_ptr[k] + np;
+      pf_stage[k] = np >= 2 && shorter;
     }
   }
 

@@ -54,6 +54,18 @@ struct StagedPlan {
   std::vector<long long> oD;
   long long oWh = 0, oTh = 0, oGh = 0, oGhh = 0, oNh = 0;
   int heavy_count(int k) const { return hv_ptr.empty() ? 0 : hv_ptr[k + 1] - hv_ptr[k]; }
+  // The profile form (HQPKKT_DYN_PROFILE): F_k is stored as in the dense form - same arena, same scatter -, and the
+  // analysis records per stage k < K and per 128-column panel p of F_k = [fx_k fu_k] the range of 16-row k-slabs that
+  // holds the panel's stored entries: pf_rng[2 (pf_ptr[k] + p)] = lo = (first dynamics row of the stage with an entry in
+  // the panel's columns) / 16, pf_rng[2 (pf_ptr[k] + p) + 1] = hi = (last such row) / 16 + 1; lo = hi = 0 for a panel
+  // without entries.  A property of the pattern, read off the CSR arrays of A'.  The large products of a stage and the
+  // solve's two products with F_k then take only these slabs (staged_stage_profile).  pf_stage[k]: the stage runs that
+  // sequence - at least two panels and a range shorter than all slabs of n_{k+1}; every other stage runs the dense
+  // sequence.  want_profile: the form the next analysis takes
+  bool want_profile = false, profile_dyn = false;
+  std::vector<int> pf_ptr, pf_rng;
+  std::vector<char> pf_stage;
+  int panels(int k) const { return pf_ptr.empty() ? 0 : pf_ptr[k + 1] - pf_ptr[k]; }
 
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;

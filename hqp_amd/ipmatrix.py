@@ -341,20 +341,24 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     ``set_dynamics_form("sparse")`` before init(): the stage products walk the row lists of A instead of
     dense blocks F_k - for dynamics with a few entries per column (hqpkkt_set_dynamics_form).  ``dense_columns=n``
     or ``set_dense_columns(n)`` with it: the columns of F_k with at least n entries go through the MFMA products as
-    a small dense block (hqpkkt_set_dense_columns; -1: the library's threshold, 0: none)."""
+    a small dense block (hqpkkt_set_dense_columns; -1: the library's threshold, 0: none).  ``a_profile=True`` or
+    ``set_dynamics_form("profile")``: dense blocks F_k, the large products and the solve over the k-slabs that hold each
+    128-column panel's stored entries - for banded and block-banded dynamics (HQPKKT_DYN_PROFILE)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, dense_columns=0, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, **kw):
         super().__init__(*args, **kw)
         if a_sparse:
             self.set_dynamics_form("sparse")
+        if a_profile:
+            self.set_dynamics_form("profile")
         if dense_columns:
             self.set_dense_columns(dense_columns)
 
     def set_dynamics_form(self, form):
-        """"dense" (default) or "sparse"; holds from the next init() on."""
-        code = {"dense": _lib.DYN_DENSE, "sparse": _lib.DYN_SPARSE}.get(form, form)
+        """"dense" (default), "sparse" or "profile"; holds from the next init() on."""
+        code = {"dense": _lib.DYN_DENSE, "sparse": _lib.DYN_SPARSE, "profile": _lib.DYN_PROFILE}.get(form, form)
         _check(self._L.hqpkkt_set_dynamics_form(self._h, int(code)), "set_dynamics_form")
 
     def set_dense_columns(self, min_entries):
@@ -372,8 +376,18 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         return [cols[ptr[k]: ptr[k + 1]].tolist() for k in range(K)]
 
     def dynamics_entries(self):
-        """Per stage k < K: (stored entries of F_k, 1 where the stage runs the sparse sequence)."""
+        """Per stage k < K: (stored entries of F_k, 1 where the stage runs the sparse sequence, 2 the profile sequence)."""
         return self.debug(36).reshape(-1, 2)
+
+    def profile_ranges(self):
+        """Per stage k < K the (lo, hi) k-slab ranges of the 128-column panels of F_k, an int array of shape (panels, 2);
+        [] unless the profile form is set."""
+        d = self.debug(41)
+        if d.size == 0:
+            return []
+        K = len(self.debug(21))
+        ptr, rng = d[: K + 1], d[K + 1:].reshape(-1, 2)
+        return [rng[ptr[k]: ptr[k + 1]].copy() for k in range(K)]
 
     def set_stages(self, nx, nu):
         nx, nu = _i32(nx), _i32(nu)
@@ -481,12 +495,13 @@ def bench_dgemm2(M, N, K, K2, lower=True, mirror=True, reps=1, device=0):
 
 def dgemm_full(M, N, K, C_buf, c_row0, c_col0, A=None, a_col0=0, B=None, b_col0=0, alpha=1.0, beta=0.0, Cin=None, cin_col0=0,
                cin_is_c=False, lower=False, mirror=False, K2=0, A2=None, a2_col0=0, B2=None, b2_col0=0,
-               sharded=False, no_ks=False, no_tile_map=False, force_split=False, device=0):
+               sharded=False, no_ks=False, no_tile_map=False, force_split=False, device=0, krange=None, krange_by=0):
     """One launch of the STAGED engine's fp64 product on the caller's operands (hqpkkt_debug_dgemm_full): C_buf's block at
     (c_row0, c_col0) = alpha (A'B + A2'B2) + beta Cin.  Every array is a C-contiguous float64 matrix, rows x leading
     dimension; an operand's block starts at its column *_col0 and its rows behind K (K2) are the caller's to poison.
     C_buf is overwritten with the whole device buffer after the launch.  Returns (form, tiles, tile order used, operands
-    staged by LDS-DMA, pieces of k)."""
+    staged by LDS-DMA, pieces of k).  krange with krange_by 1 / 2: the profile form - (lo, hi) k-slabs per 128-wide column
+    panel of B / of A; the form comes back as "profile"."""
     import numpy as np
 
     def operand(x, col0):
@@ -503,8 +518,11 @@ def dgemm_full(M, N, K, C_buf, c_row0, c_col0, A=None, a_col0=0, B=None, b_col0=
     c.alpha, c.beta = alpha, beta
     c.A, c.B, c.A2, c.B2, c.Cin = operand(A, a_col0), operand(B, b_col0), operand(A2, a2_col0), operand(B2, b2_col0), operand(Cin, cin_col0)
     c.C, c.c_rows, c.ldc, c.c_row0, c.c_col0 = C_buf.ctypes.data, C_buf.shape[0], C_buf.shape[1], c_row0, c_col0
+    if krange_by:
+        kr = np.ascontiguousarray(krange, dtype=np.int32)
+        c.krange, c.krange_by = kr.ctypes.data, int(krange_by)
     _check(_lib.lib().hqpkkt_debug_dgemm_full(device, C.byref(c)), "debug_dgemm_full")
-    return GEMM_FORMS[c.form], c.tiles, bool(c.tile_map), bool(c.ldsdma), c.nsplit
+    return (GEMM_FORMS + ("profile",))[c.form], c.tiles, bool(c.tile_map), bool(c.ldsdma), c.nsplit
 
 
 SK_KINDS = ("unequal", "equal", "frac")
@@ -526,7 +544,39 @@ def sk_table(tiles, nslab, grid=512, kind="unequal"):
     return u, pieces.value, wa.value, wb.value
 
 
-GEMM_FORMS = ("frac", "cut", "plain", "ks", "6432", "6464")
+def sk_profile(ranges, grid=512):
+    """The work list of the profile form (host only) for tiles of which tile t takes the k-slabs [ranges[t, 0],
+    ranges[t, 1]): (units[grid, stride, 6], pieces), units as in :func:`sk_table`."""
+    import numpy as np
+    r = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
+    rp, pieces = r.ctypes.data_as(C.POINTER(C.c_int)), C.c_longlong()
+    stride = _lib.lib().hqpkkt_debug_sk_profile(rp, len(r), grid, None, 0, C.byref(pieces))
+    if stride <= 0:
+        return None
+    u = np.zeros((grid, stride, 6), dtype=np.int32)
+    got = _lib.lib().hqpkkt_debug_sk_profile(rp, len(r), grid, u.ctypes.data_as(C.POINTER(C.c_int)), u.size, C.byref(pieces))
+    assert got == stride
+    return u, pieces.value
+
+
+def gemv_profile(A, ranges, x, add=None, alpha=1.0, rows_form=False, K=None, N=None, y=None, device=0):
+    """One launch of a product of the profile form's solve (hqpkkt_debug_gemv_profile) on a C-contiguous float64 matrix A
+    (rows x leading dimension, a multiple of 8): rows_form False: y (N) = add + alpha A[:K, :N]' x over the rows of every
+    128-column panel's k-slab range; True: y (K) = add + alpha A[:K, :N] x over the panels whose range holds the row."""
+    import numpy as np
+    assert A.dtype == np.float64 and A.ndim == 2 and A.flags.c_contiguous
+    K, N = A.shape[0] if K is None else K, A.shape[1] if N is None else N
+    r = np.ascontiguousarray(ranges, dtype=np.int32)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    add = None if add is None else np.ascontiguousarray(add, dtype=np.float64)
+    y = np.zeros(K if rows_form else N) if y is None else y
+    assert x.size == (N if rows_form else K) and y.size == (K if rows_form else N) and r.size == 2 * ((N + 127) // 128)
+    _check(_lib.lib().hqpkkt_debug_gemv_profile(device, int(rows_form), K, N, A.ctypes.data, A.shape[0], A.shape[1], r.ctypes.data, x.ctypes.data,
+                                                None if add is None else add.ctypes.data, float(alpha), y.ctypes.data), "debug_gemv_profile")
+    return y
+
+
+GEMM_FORMS = ("frac", "cut", "plain", "ks", "6432", "6464")  # (what the launch rule can answer; the profile form is asked for)
 
 
 def gemm_form(M, N, K, lower=False, mirror=False, cus=256, grid=512, sk_tiles=1 << 30, ws_elems=1 << 40, ws2_elems=8 << 20,

@@ -316,9 +316,17 @@ int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu);
  * hand-over) returns HQPKKT_E_INTERN, and hqpkkt_analyze on a handle with hqpkkt_set_shard / hqpkkt_set_shard_stream
  * returns HQPKKT_E_RANGE: one system over several ranks stays dense.  There is no automatic choice between the two forms;
  * the sparse form pays while a column of F_k holds few entries against the number of states (DESIGN.md section 3 has the
- * measured times), and a few full columns among them can be taken out of the walks (hqpkkt_set_dense_columns). */
+ * measured times), and a few full columns among them can be taken out of the walks (hqpkkt_set_dense_columns).
+ * HQPKKT_DYN_PROFILE: for banded and block-banded dynamics.  F_k is stored as in the dense form (same arena, same
+ * hqpkkt_stats.bytes_panels); the analysis records per stage and per 128-column panel of F_k the range of 16-row k-slabs
+ * that holds the panel's stored entries, and a stage with at least two panels and a range shorter than all slabs runs
+ * its two large MFMA products W = V+ F and G = F'W, and the solve's two products with F_k, over those slabs alone; every
+ * other stage runs the dense sequence and gives the dense form's bits.  The rules of HQPKKT_DYN_SPARSE hold:
+ * hqpkkt_analyze_staged returns HQPKKT_E_INTERN, a sharded handle HQPKKT_E_RANGE at hqpkkt_analyze;
+ * hqpkkt_set_dense_columns is accepted and ignored.  No form is chosen automatically. */
 #define HQPKKT_DYN_DENSE 0   /* default: dense blocks F_k, MFMA products           */
 #define HQPKKT_DYN_SPARSE 1  /* Hqp_IpLQDOCP's mat_a_sparse: F_k stays row lists   */
+#define HQPKKT_DYN_PROFILE 3 /* dense blocks F_k, products over the panels' k-slabs (2 is not a form: HQPKKT_E_RANGE) */
 int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form);
 /* Heavy columns of the sparse form.  Its column walks give one lane one column of F_k, so a stage takes as long as its
  * longest column: a dense control column or a global state among banded ones costs a serial loop over every state.  With
@@ -397,6 +405,10 @@ int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int 
  * HQPKKT_SK_TABLE are honoured as by hqpkkt_debug_dgemm.
  * Out: form (hqpkkt_debug_gemm_form's numbering), tiles, nsplit (pieces of the k range of the thin-deep form), tile_map
  * (the launch walked the tile order of a large triangle), ldsdma (the operands were staged by LDS-DMA).
+ * krange, krange_by (the profile form): krange_by 0: as above.  1 / 2: krange holds two ints (lo, hi) per 128-wide column
+ * panel of B (1: tile (tm, tn) takes the k-slabs [lo, hi) of panel tn, as W = V+ F) or of A (2: panel tm, as G = F'W); the
+ * launch is k_dgemm_tn_sk by a profile list and reports form 6.  No entry of the ranged operand outside its panels' ranges
+ * is read as a value that counts.  K2 must be 0, 0 <= lo <= hi <= ceil(K / 16).
  * HQPKKT_E_RANGE: a shape, an operand layout or a form the kernels do not take; HQPKKT_E_MEM: an allocation failed. */
 typedef struct hqpkkt_dgemm_operand {
   const double *p;
@@ -411,6 +423,8 @@ typedef struct hqpkkt_dgemm_case {
   long long c_rows, ldc, c_row0, c_col0;
   int form, tile_map, ldsdma, nsplit; /* out */
   long long tiles;                    /* out */
+  const int *krange;                  /* in: the profile form's ranges, or NULL */
+  int krange_by;                      /* in: 0 none, 1 B's column panels, 2 A's */
 } hqpkkt_dgemm_case;
 int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c);
 
@@ -424,6 +438,19 @@ int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c);
  * *pieces: parking slots; *whole_a / *whole_b (kind 0; else 0): whole tiles per workgroup of the first / second half of
  * the launch. */
 int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int kind, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b);
+
+/* Test hook, host only: the work list of the profile form (gemm_profile_table, sk_table.hpp) for `tiles` tiles of which
+ * tile t takes the k-slabs [ranges[2 t], ranges[2 t + 1]), on `grid` workgroups.  units, cap_ints, *pieces and the
+ * returned stride as in hqpkkt_debug_sk_table. */
+int hqpkkt_debug_sk_profile(const int *ranges, long long tiles, int grid, int *units, long long cap_ints, long long *pieces);
+
+/* Test hook: one launch of either product of the profile form's solve on the caller's host arrays.  A: a_rows >= K rows
+ * of ld doubles (ld >= N, a multiple of 8), ranges: two ints (lo, hi) per 128-column panel, 0 <= lo <= hi <= ceil(K / 16).
+ * rows_form 0: y (N) = add + alpha A'x (x: K entries), panel p summed over the rows [16 lo_p, min(K, 16 hi_p));
+ * rows_form 1: y (K) = add + alpha A x (x: N entries), row r over the panels with lo_p <= r / 16 < hi_p.  add may be NULL.
+ * HQPKKT_E_INTERN: the launch wrote behind y. */
+int hqpkkt_debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
+                              const double *x, const double *add, double alpha, double *y);
 
 /* Test hook, host only: the form the STAGED engine's launch rule (gemm_form.hpp) gives an M x N x K product on a device
  * of `cus` CUs with a split grid of `grid` workgroups (0: none), arrival counters for sk_tiles tiles and workspaces of
@@ -518,7 +545,8 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * that fix x_0, 26 capacity of carried rows, 27 column cuts of the ranks ((K+1) x (ranks+1)), 28 two counters of
  * the last factorisation: stages whose K was inverted by the blocked elimination, and those of them that fell back to the
  * one-workgroup elimination (device -> host copy); 32 - 35 further STAGED diagnostics (staged_engine.hip); 36 per stage
- * k < K two ints: the stored entries of F_k and 1 where the stage runs the sparse sequence (hqpkkt_set_dynamics_form);
+ * k < K two ints: the stored entries of F_k and 1 where the stage runs the sparse sequence, 2 the profile sequence
+ * (hqpkkt_set_dynamics_form);
  * 37 the sparse form's ranges: per dynamics row [first, end) into A's CSR arrays (the row without its -1), then per column
  * of the stages k < K [first, end) into the CSR arrays of A' (rows ascending) - the column's entries in the dynamics rows
  * of its stage; empty on a dense-form handle; 38 the work lists the upload made for the cut forms of the stage products,
@@ -529,7 +557,9 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * unless the sparse form is set; valid after hqpkkt_analyze, without a device; 30 (zero-diagonal policy in use, last
  * values have weak Hessian diagonals), 31 (fronts of the tree's top that the solve handles in one launch, first
  * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
- * process, over all handles: answered on any handle, analysed or not).
+ * process, over all handles: answered on any handle, analysed or not); 41 the profile form's ranges: K + 1 pointers, then
+ * the (lo, hi) k-slab pairs of the 128-column panels of every stage's F_k; empty unless HQPKKT_DYN_PROFILE is set; valid
+ * after hqpkkt_analyze, without a device.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

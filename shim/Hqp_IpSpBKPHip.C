@@ -51,12 +51,14 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
   _wz_tol = HUGE_VAL;
   _a_sparse = 0;
   _a_heavy = 0;
+  _a_profile = 0;
   _told_ignored = false;
   _logging = getenv("HQPKKT_SHIM_LOGGING") ? atoi(getenv("HQPKKT_SHIM_LOGGING")) : 0;
   if (mode == HQPKKT_MODE_STAGED) {
     _ifList.append(new If_Real("mat_wz_tol", &_wz_tol));
     _ifList.append(new If_Int("mat_a_sparse", &_a_sparse));
     _ifList.append(new If_Int("mat_a_heavy", &_a_heavy));
+    _ifList.append(new If_Int("mat_a_profile", &_a_profile));
     _ifList.append(new If_Int("mat_logging", &_logging));
   }
 
@@ -367,13 +369,13 @@ int Hqp_IpMatrixHip::create_handle(int mode)
   return HQPKKT_OK;
 }
 
-int Hqp_IpMatrixHip::open(int mode, bool sparse_dyn)
+int Hqp_IpMatrixHip::open(int mode, int dyn_form)
 {
   int e;
   if ((e = create_handle(mode)))
     return e;
   _dense = false;
-  if (sparse_dyn && ((e = hqpkkt_set_dynamics_form(_h, HQPKKT_DYN_SPARSE)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy))))
+  if (dyn_form != HQPKKT_DYN_DENSE && ((e = hqpkkt_set_dynamics_form(_h, dyn_form)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy))))
     return e;
   if ((e = hqpkkt_analyze(_h, _n, _me, _m,
                           _Qp->ive, _Qi->ive, _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive,
@@ -395,11 +397,12 @@ void Hqp_IpMatrixHip::init(const Hqp_Program *qp)
   // the handle is created here: mat_tol / mat_eps / mat_device may have been set
   if (_mode == HQPKKT_MODE_STAGED) {
     // the dynamics as dense stage blocks straight from the row lists (no CSR copy of them: open_dense); with
-    // mat_a_sparse (hqp/Hqp_IpLQDOCP.C:178) as CSR rows, which the sparse form of the stage products walks
-    const bool sparse_dyn = _a_sparse != 0 && _ngpu <= 1;
-    if (sparse_dyn) {
+    // mat_a_sparse (hqp/Hqp_IpLQDOCP.C:178) as CSR rows, which the sparse form of the stage products walks, and with
+    // mat_a_profile as CSR rows from which the profile form reads the k-slab ranges of its panels
+    const bool sparse_dyn = _a_sparse != 0 && _ngpu <= 1, profile_dyn = !sparse_dyn && _a_profile != 0 && _ngpu <= 1;
+    if (sparse_dyn || profile_dyn) {
       extract(qp, changed);
-      e = open(HQPKKT_MODE_STAGED, true);
+      e = open(HQPKKT_MODE_STAGED, sparse_dyn ? HQPKKT_DYN_SPARSE : HQPKKT_DYN_PROFILE);
     } else
       e = open_dense(qp);
     const char *why = NULL;
@@ -422,6 +425,8 @@ void Hqp_IpMatrixHip::init(const Hqp_Program *qp)
       fprintf(stderr, "LQDOCPHip: n %d me %d m %d", _n, _me, _m);
       if (sparse_dyn && _mode_used == HQPKKT_MODE_STAGED)
         fprintf(stderr, ": STAGED engine, sparse form of the stage products (mat_a_sparse)\n");
+      else if (profile_dyn && _mode_used == HQPKKT_MODE_STAGED)
+        fprintf(stderr, ": STAGED engine, profile form of the stage products (mat_a_profile)\n");
       else if (_dense)
         fprintf(stderr, ", %d stages (x_0: %d states; widest stage %d states + %d controls), %d dynamics rows as dense "
                 "blocks: STAGED engine\n", _K, _nx->ive[0], _nx->ive[_K], _K ? _nu->ive[0] : 0, _ndyn);

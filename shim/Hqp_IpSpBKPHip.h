@@ -42,9 +42,11 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
   // (hqpkkt_set_dynamics_form; one system over several GPUs stays dense), mat_logging > 0 prints the stage structure
   // and the engine chosen at init().  mat_a_heavy (no counterpart in the reference) goes to hqpkkt_set_dense_columns
   // when mat_a_sparse != 0: columns of F_k with at least that many entries take the MFMA products (0 none, -1 the
-  // library's threshold)
+  // library's threshold).  mat_a_profile (no counterpart in the reference) != 0 takes the CSR hand-over with the profile
+  // form (HQPKKT_DYN_PROFILE: dense blocks, the large products and the solve over the k-slabs that hold each panel's
+  // entries - banded dynamics) on one GPU; mat_a_sparse goes first where both are set
   Real _wz_tol;
-  int _a_sparse, _a_heavy, _logging;
+  int _a_sparse, _a_heavy, _a_profile, _logging;
   bool _told_ignored;
   struct hqpkkt *_h;
   // STAGED engine with the dynamics handed over as dense blocks (hqpkkt_analyze_staged): stage sizes, the number of
@@ -59,7 +61,7 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
 
   void extract(const Hqp_Program *qp, bool &pattern_changed);
   int create_handle(int mode);
-  int open(int mode, bool sparse_dyn = false);
+  int open(int mode, int dyn_form = 0);  // (dyn_form: HQPKKT_DYN_*, 0 dense)
   int open_dense(const Hqp_Program *qp);
   int dense_values(const Hqp_Program *qp);
   void check(int status, const char *where);

@@ -32,6 +32,7 @@ SYMBOLS = [
     "hqpkkt_values_staging", "hqpkkt_detect_stages", "hqpkkt_stage_staging", "hqpkkt_set_stage_block",
     "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
     "hqpkkt_debug_sk_profile", "hqpkkt_debug_gemv_profile",
+    "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -151,6 +152,7 @@ def lib():
     L.hqpkkt_set_stages.argtypes = [vp, C.c_int, vp, vp]
     L.hqpkkt_set_dynamics_form.argtypes = [vp, C.c_int]
     L.hqpkkt_set_dense_columns.argtypes = [vp, C.c_int]
+    L.hqpkkt_set_packed_panels.argtypes = [vp, C.c_int]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]
@@ -164,6 +166,9 @@ def lib():
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hqpkkt_debug_sk_profile.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_gemv_profile.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, C.c_longlong, vp, vp, vp, C.c_double, vp]
+    L.hqpkkt_debug_dgemm_packed.argtypes = [C.c_int, C.POINTER(DgemmCase), vp, C.c_longlong, vp]
+    L.hqpkkt_debug_gemv_packed.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, vp, vp, vp, vp, C.c_double, vp]
+    L.hqpkkt_debug_carried_packed.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, C.c_longlong, vp, C.c_longlong, vp, vp, vp] + [C.c_longlong] * 4
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_debug_factor_block.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 7

@@ -128,6 +128,13 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       out = P.pf_ptr;
       out.insert(out.end(), P.pf_rng.begin(), P.pf_rng.end());
       break;
+    case 42:  // the packed panels (host only): item 41's K + 1 pointers, then per panel (offset in doubles from the stage's first
+              // panel, leading dimension); (-1, 0) for the panels of a stage that keeps its dense block; empty unless the
+              // profile form is set
+      out = P.pf_ptr;
+      for (size_t q = 0; q < P.pf_rng.size() / 2; q++)
+        out.push_back(P.packed ? (int)P.pk_off[q] : -1), out.push_back(P.packed ? P.pk_ld[q] : 0);
+      break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
       for (const StagedDev::SkTab &t : h->sd->sk_tabs)
@@ -159,6 +166,17 @@ int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries) {
     if (min_entries < -1) return HQPKKT_E_RANGE;
     if (!h->sd) h->sd.reset(new StagedDev);
     h->sd->plan.want_heavy = min_entries;  // (the next hqpkkt_analyze picks it up; read by the sparse form alone)
+    return 0;
+  });
+}
+
+int hqpkkt_set_packed_panels(hqpkkt_t *h, int on) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (on != 0 && on != 1) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_packed = on != 0;  // (the next hqpkkt_analyze picks it up; read by the profile form alone)
     return 0;
   });
 }
@@ -579,9 +597,28 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   if (max_err) *max_err = he;
   return 0;
 }
+// The packed panels a test hook was given (include/hqpkkt.h, hqpkkt_debug_dgemm_packed): `panel` holds (offset, ld) per
+// 128-column panel of a K x W operand, `ranges` its (lo, hi) k-slabs.  Every panel's rows must lie inside the buffer of
+// `elems` doubles, on 16-byte boundaries.  Out: the kernels' table (offsets less 16 lo ld)
+static int debug_pack_table(int K, int W, const long long *panel, const int *ranges, long long elems, std::vector<stg::PackPanel> &tab) {
+  const int np = (W + 127) / 128;
+  tab.resize(np);
+  for (int p = 0; p < np; p++) {
+    const long long off = panel[2 * p], ld = panel[2 * p + 1];
+    const int lo = ranges[2 * p], hi = ranges[2 * p + 1];
+    if (lo < 0 || hi < lo || hi > (K + 15) / 16) return HQPKKT_E_RANGE;
+    const long long rows = std::min(16 * hi, K) - 16 * lo;
+    if (ld < std::min(128, W - 128 * p) || (ld & 7) || off < 0 || (off & 1) || off + rows * ld > elems) return HQPKKT_E_RANGE;
+    tab[p] = stg::PackPanel{off - 16LL * lo * ld, ld};
+  }
+  return 0;
+}
 // One product on the caller's operands, all of C back (include/hqpkkt.h): launches and copies, compares nothing
-static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
+// pk: the ranged operand (c->krange_by) comes from this buffer of packed panels instead (hqpkkt_debug_dgemm_packed)
+static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c, const double *pk = nullptr, long long pk_elems = 0, const long long *pk_panel = nullptr) {
   if (!c || !c->C) return HQPKKT_E_NULL;
+  if (pk && (!pk_panel || !c->krange || (c->krange_by != 1 && c->krange_by != 2) || c->K2 > 0 || c->K <= 0 || pk_elems <= 0)) return HQPKKT_E_RANGE;
+  const bool pkA = pk && c->krange_by == 2, pkB = pk && c->krange_by == 1;
   const int M = c->M, N = c->N, K = c->K, K2 = c->K2;
   if (M <= 0 || N <= 0 || K < 0 || K2 < 0) return HQPKKT_E_RANGE;
   if ((c->lower && M < N) || (c->mirror && !c->lower)) return HQPKKT_E_RANGE;  // (the image of a triangle, or of the column strip of one)
@@ -591,7 +628,9 @@ static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
   auto operand_ok = [](const hqpkkt_dgemm_operand &o, int k, int w) {
     return k == 0 || (o.p && o.ld >= 1 && o.col0 >= 0 && o.col0 + w <= o.ld && o.rows >= (long long)k + 1);
   };
-  if (!operand_ok(c->A, K, M) || !operand_ok(c->B, K, N) || !operand_ok(c->A2, K2, M) || !operand_ok(c->B2, K2, N)) return HQPKKT_E_RANGE;
+  if ((!pkA && !operand_ok(c->A, K, M)) || (!pkB && !operand_ok(c->B, K, N)) || !operand_ok(c->A2, K2, M) || !operand_ok(c->B2, K2, N)) return HQPKKT_E_RANGE;
+  std::vector<stg::PackPanel> ptab;
+  if (pk && debug_pack_table(K, pkA ? M : N, pk_panel, c->krange, pk_elems, ptab)) return HQPKKT_E_RANGE;
   const int wc = c->mirror ? std::max(M, N) : N;  // (the image of a column strip reaches column M)
   if (c->ldc < 1 || c->c_row0 < 0 || c->c_col0 < 0 || c->c_col0 + wc > c->ldc || c->c_row0 + M > c->c_rows) return HQPKKT_E_RANGE;
   const bool beta = c->beta != 0.0, cin_own = beta && !c->cin_is_c;
@@ -600,18 +639,23 @@ static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
   HIPCHK(hipSetDevice(device));
   DBuf<double> dA, dB, dA2, dB2, dCin, dC;
+  DBuf<stg::PackPanel> dtab;
   auto up = [](DBuf<double> &d, const double *p, long long elems) -> int {
     if (d.alloc((size_t)elems)) return HQPKKT_E_MEM;
     HIPCHK(hipMemcpy(d.p, p, sizeof(double) * (size_t)elems, hipMemcpyHostToDevice));
     return 0;
   };
   int e;
-  if (K > 0 && ((e = up(dA, c->A.p, c->A.rows * c->A.ld)) || (e = up(dB, c->B.p, c->B.rows * c->B.ld)))) return e;
+  if (K > 0 && ((e = pkA ? up(dA, pk, pk_elems) : up(dA, c->A.p, c->A.rows * c->A.ld)) || (e = pkB ? up(dB, pk, pk_elems) : up(dB, c->B.p, c->B.rows * c->B.ld))))
+    return e;
+  if (pk && dtab.upload(ptab)) return HQPKKT_E_MEM;
   if (K2 > 0 && ((e = up(dA2, c->A2.p, c->A2.rows * c->A2.ld)) || (e = up(dB2, c->B2.p, c->B2.rows * c->B2.ld)))) return e;
   if (cin_own && (e = up(dCin, c->Cin.p, c->Cin.rows * c->Cin.ld))) return e;
   if ((e = up(dC, c->C, c->c_rows * c->ldc))) return e;
   stg::GemmArgs g{};
   if (K > 0) g.A = dA.p + c->A.col0, g.lda = c->A.ld, g.B = dB.p + c->B.col0, g.ldb = c->B.ld;
+  if (pkA) g.A = dA.p, g.lda = 8, g.apack = dtab.p;  // (the panels' own leading dimensions count)
+  if (pkB) g.B = dB.p, g.ldb = 8, g.bpack = dtab.p;
   if (K2 > 0) g.A2 = dA2.p + c->A2.col0, g.lda2 = c->A2.ld, g.B2 = dB2.p + c->B2.col0, g.ldb2 = c->B2.ld, g.K2 = K2;
   g.C = dC.p + c->c_row0 * c->ldc + c->c_col0, g.ldc = c->ldc;
   if (beta) g.Cin = cin_own ? dCin.p + c->Cin.col0 : g.C, g.ldcin = cin_own ? c->Cin.ld : c->ldc;
@@ -633,6 +677,9 @@ int hqpkkt_debug_dgemm2(int device, int M, int N, int K, int K2, int lower, int 
 }
 int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
   return guarded([&]() -> int { return debug_dgemm_full(device, c); });
+}
+int hqpkkt_debug_dgemm_packed(int device, hqpkkt_dgemm_case *c, const double *packed, long long packed_elems, const long long *panel) {
+  return guarded([&]() -> int { return packed ? debug_dgemm_full(device, c, packed, packed_elems, panel) : HQPKKT_E_NULL; });
 }
 
 int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,
@@ -678,10 +725,13 @@ int hqpkkt_debug_sk_profile(const int *ranges, long long tiles, int grid, int *u
 }
 
 // One launch of a product of the profile form's solve (staged_profile.hip.h) on the caller's host arrays
+// (panel: A is a buffer of a_rows x ld doubles that holds packed panels, (offset, ld) per panel: hqpkkt_debug_gemv_packed)
 static int debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
-                              const double *x, const double *add, double alpha, double *y) {
+                              const double *x, const double *add, double alpha, double *y, const long long *panel = nullptr) {
   if (!A || !ranges || !x || !y) return HQPKKT_E_NULL;
-  if (K <= 0 || N <= 0 || a_rows < K || ld < N || (ld & 7)) return HQPKKT_E_RANGE;
+  if (K <= 0 || N <= 0 || (!panel && (a_rows < K || ld < N || (ld & 7)))) return HQPKKT_E_RANGE;
+  std::vector<stg::PackPanel> ptab;
+  if (panel && (a_rows < 1 || ld < 1 || debug_pack_table(K, N, panel, ranges, a_rows * ld, ptab))) return HQPKKT_E_RANGE;
   const int np = (N + 127) / 128, nx = rows_form ? N : K, ny = rows_form ? K : N;
   for (int p = 0; p < np; p++)
     if (ranges[2 * p] < 0 || ranges[2 * p + 1] < ranges[2 * p] || ranges[2 * p + 1] > (K + 15) / 16) return HQPKKT_E_RANGE;
@@ -690,6 +740,8 @@ static int debug_gemv_profile(int device, int rows_form, int K, int N, const dou
   HIPCHK(hipSetDevice(device));
   DBuf<double> dA, dx, dadd, dy, part;
   DBuf<int> dr;
+  DBuf<stg::PackPanel> dtab;
+  if (panel && dtab.upload(ptab)) return HQPKKT_E_MEM;
   const int chunks = stg::pf_chunks(ranges, np, K);
   const int guard = 64;  // doubles behind y on the device, checked after the launch: nothing may be written past y
   const std::vector<double> mark(guard, -12345.678);
@@ -701,7 +753,7 @@ static int debug_gemv_profile(int device, int rows_form, int K, int N, const dou
   HIPCHK(hipMemcpy(dy.p, y, sizeof(double) * ny, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dy.p + ny, mark.data(), sizeof(double) * guard, hipMemcpyHostToDevice));
   if (add) HIPCHK(hipMemcpy(dadd.p, add, sizeof(double) * ny, hipMemcpyHostToDevice));
-  const stg::PfGemv g{dA.p, ld, K, N, dr.p, dx.p, add ? dadd.p : nullptr, alpha, dy.p, part.p};
+  const stg::PfGemv g{dA.p, ld, K, N, dr.p, dx.p, add ? dadd.p : nullptr, alpha, dy.p, part.p, panel ? dtab.p : nullptr};
   if (rows_form)
     stg::pf_launch_rows(g, 0, [](auto &&kernel) { kernel(); });
   else
@@ -715,6 +767,51 @@ static int debug_gemv_profile(int device, int rows_form, int K, int N, const dou
 int hqpkkt_debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
                               const double *x, const double *add, double alpha, double *y) {
   return guarded([&]() -> int { return debug_gemv_profile(device, rows_form, K, N, A, a_rows, ld, ranges, x, add, alpha, y); });
+}
+
+int hqpkkt_debug_gemv_packed(int device, int rows_form, int K, int N, const double *packed, long long packed_elems, const long long *panel,
+                             const int *ranges, const double *x, const double *add, double alpha, double *y) {
+  return guarded([&]() -> int {
+    if (!panel) return HQPKKT_E_NULL;
+    return debug_gemv_profile(device, rows_form, K, N, packed, 1, packed_elems, ranges, x, add, alpha, y, panel);
+  });
+}
+
+// One launch of the carried rows of a packed stage (k_pk_carried) on the caller's host arrays
+static int debug_carried_packed(int device, int K, int N, int R, const double *BT, long long bt_rows, long long ldb, const double *packed,
+                                long long packed_elems, const long long *panel, const int *ranges, double *Cbuf, long long c_rows, long long ldc,
+                                long long c_row0, long long c_col0) {
+  if (!BT || !packed || !panel || !ranges || !Cbuf) return HQPKKT_E_NULL;
+  if (K <= 0 || N <= 0 || R <= 0 || bt_rows < K || ldb < R || packed_elems < 1 || ldc < 1 || c_row0 < 0 || c_col0 < 0 || c_col0 + N > ldc ||
+      c_row0 + R > c_rows)
+    return HQPKKT_E_RANGE;
+  std::vector<stg::PackPanel> ptab;
+  if (debug_pack_table(K, N, panel, ranges, packed_elems, ptab)) return HQPKKT_E_RANGE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  const int np = (N + 127) / 128;
+  DBuf<double> dB, dA, dC, part;
+  DBuf<int> dr;
+  DBuf<stg::PackPanel> dtab;
+  if (dB.alloc((size_t)(bt_rows * ldb)) || dA.alloc((size_t)packed_elems) || dC.alloc((size_t)(c_rows * ldc)) ||
+      part.alloc((size_t)stg::pk_chunks(ranges, np, K) * R * N) || dr.upload(std::vector<int>(ranges, ranges + 2 * np)) || dtab.upload(ptab))
+    return HQPKKT_E_MEM;
+  HIPCHK(hipMemcpy(dB.p, BT, sizeof(double) * (size_t)(bt_rows * ldb), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dA.p, packed, sizeof(double) * (size_t)packed_elems, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dC.p, Cbuf, sizeof(double) * (size_t)(c_rows * ldc), hipMemcpyHostToDevice));
+  stg::pk_launch_carried(stg::PkCarried{dB.p, ldb, dA.p, dtab.p, dr.p, K, N, R, 0, dC.p + c_row0 * ldc + c_col0, ldc, part.p}, ranges, 0,
+                         [](auto &&kernel) { kernel(); });
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(Cbuf, dC.p, sizeof(double) * (size_t)(c_rows * ldc), hipMemcpyDeviceToHost));
+  return 0;
+}
+int hqpkkt_debug_carried_packed(int device, int K, int N, int R, const double *BT, long long bt_rows, long long ldb, const double *packed,
+                                long long packed_elems, const long long *panel, const int *ranges, double *C, long long c_rows, long long ldc,
+                                long long c_row0, long long c_col0) {
+  return guarded([&]() -> int {
+    return debug_carried_packed(device, K, N, R, BT, bt_rows, ldb, packed, packed_elems, panel, ranges, C, c_rows, ldc, c_row0, c_col0);
+  });
 }
 
 #ifdef HQPKKT_STAMPS

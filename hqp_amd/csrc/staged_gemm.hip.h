@@ -47,6 +47,12 @@ static __device__ __forceinline__ int strip_of(const int *cut, int nranks, int j
   return p;
 }
 
+// A ranged operand of a product in the profile form that is stored as packed panels (StagedPlan::pk_off): per 128-column
+// panel p its rows [16 lo_p, ...) alone, row-major with leading dimension ld.  off: the panel's first element from the
+// operand's pointer, less 16 lo_p ld - row k of the product is row k of the panel's addressing, as in a dense block
+struct PackPanel {
+  long long off, ld;
+};
 struct GemmArgs {
   const double *A;
   long long lda;  // K x M, row-major (k-major)
@@ -81,6 +87,9 @@ struct GemmArgs {
   const double *B2;
   long long ldb2;
   int K2;
+  // packed panels of A / of B (k_dgemm_tn_sk<.., PACKED = true>, a GEMM_FORM_PROFILE launch alone): the tile at tile row
+  // tm / tile column tn takes entry tm / tn; null: the operand is one block
+  const PackPanel *apack, *bpack;
 };
 // k-slabs of a launch (both segments)
 static __host__ __device__ __forceinline__ int gemm_slabs_of(const GemmArgs &g) {
@@ -142,6 +151,7 @@ struct GemmTile {
   }
 
   // acc += sum over the slabs [s0, s1) of the tile at (i0, j0); ends with a barrier (LDS free again)
+  template <bool PACKED = false>
   static __device__ __forceinline__ void accumulate(const GemmArgs &g, int i0, int j0, int s0, int s1,
                                                     double4_t (&acc)[TM][TN], double *As, double *Bs) {
     static_assert(NT == 256, "the register-staged loop is written for 256 threads");
@@ -152,7 +162,9 @@ struct GemmTile {
     const int ca = 2 * (tid % (BM / 2)), ra = tid / (BM / 2);
     const int cb = 2 * (tid % (BN / 2)), rb = tid / (BN / 2);
     // a 16-byte load is inside its row when its first column is < ld (ld even)
-    const long long acol = (i0 + ca < g.lda) ? i0 + ca : 0;
+    const double *Ap = g.A;
+    long long lda = g.lda;
+    int ia = i0;  // first column of the tile inside its A block
     const double *Bp = g.B;
     long long ldb = g.ldb;
     int jb = j0;  // first column of the tile inside its B block
@@ -160,6 +172,12 @@ struct GemmTile {
       const int q = strip_of(g.bstrips->cut, g.bstrips->nranks, j0);
       Bp = g.B + g.bstrips->off[q], ldb = g.bstrips->ld[q], jb = j0 - g.bstrips->cut[q];
     }
+    if constexpr (PACKED) {  // (a panel is a tile wide: the tile starts at its column 0)
+      static_assert(BM == 128 && BN == 128, "a packed panel is one 128-wide tile column");
+      if (g.apack) Ap = g.A + g.apack[i0 / BM].off, lda = g.apack[i0 / BM].ld, ia = 0;
+      if (g.bpack) Bp = g.B + g.bpack[j0 / BN].off, ldb = g.bpack[j0 / BN].ld, jb = 0;
+    }
+    const long long acol = (ia + ca < lda) ? ia + ca : 0;
     const long long bcol = (jb + cb < ldb) ? jb + cb : 0;
     // D register sets: the loads of slab t + D are issued before the multiplications of slab t and consumed (masked
     // for k >= K, stored to LDS) after those of slab t + D - 1.  With 64 x 64 tiles a slab is 16 multiplications per
@@ -177,7 +195,7 @@ struct GemmTile {
 #pragma unroll
       for (int p = 0; p < LA; p++) {
         const int k = k0 + ra + p * RA, kc = k < g.K ? k : g.K - 1;
-        xa[p] = *(const double2_t *)(g.A + (long long)kc * g.lda + acol);
+        xa[p] = *(const double2_t *)(Ap + (long long)kc * lda + acol);
       }
 #pragma unroll
       for (int p = 0; p < LB; p++) {
@@ -380,6 +398,7 @@ struct GemmTile {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the zero rows behind the range: LDS is reused after this)
     __syncthreads();
   }
+  template <bool PACKED = false>
   static __device__ __forceinline__ void accumulate_dma(const GemmArgs &g, int i0, int j0, int s0, int s1,
                                                         double4_t (&acc)[TM][TN], double *As, double *Bs, bool skip_upper = false, int nbuf = 2) {
     static_assert(BM == 128 && BN == 128, "one k-row of a panel must be one 1-KiB wave-instruction");
@@ -407,12 +426,19 @@ struct GemmTile {
       const int q = strip_of(g.bstrips->cut, g.bstrips->nranks, j0);
       B = g.B + g.bstrips->off[q], ldb = g.bstrips->ld[q], jb = j0 - g.bstrips->cut[q];
     }
-    const double *pa = g.A + ((i0 + 2 * lane < g.lda) ? i0 + 2 * lane : 0);
+    const double *A = g.A;
+    long long lda = g.lda;
+    int ia = i0;
+    if constexpr (PACKED) {  // (a panel is a tile wide: the tile starts at its column 0)
+      if (g.apack) A = g.A + g.apack[i0 / BM].off, lda = g.apack[i0 / BM].ld, ia = 0;
+      if (g.bpack) B = g.B + g.bpack[j0 / BN].off, ldb = g.bpack[j0 / BN].ld, jb = 0;
+    }
+    const double *pa = A + ((ia + 2 * lane < lda) ? ia + 2 * lane : 0);
     const double *pb = B + ((jb + 2 * lane < ldb) ? jb + 2 * lane : 0);
     const double *zr = g.zeros + 2 * lane;
     // (the second segment's rows are addressed from the first's origin: the same column of the tile in both; not with bstrips)
     const int k0 = (g.K + BK - 1) / BK * BK, k1 = k0 + (g.K2 > 0 ? g.K2 : 0);
-    Rows ra{g.K, k0, k1, g.lda, 0, 0}, rb{g.K, k0, k1, ldb, 0, 0};
+    Rows ra{g.K, k0, k1, lda, 0, 0}, rb{g.K, k0, k1, ldb, 0, 0};
     if (g.K2 > 0) {
       ra.ld2 = g.lda2, ra.o2 = (g.A2 - g.A) - (long long)k0 * g.lda2;
       rb.ld2 = g.ldb2, rb.o2 = (g.B2 - g.B) - (long long)k0 * g.ldb2;
@@ -596,7 +622,9 @@ struct SplitPlan {
   const SkUnit *table;  // workgroup b (blockIdx.x) does table[b * stride + i], i = 0 ... until a tile < 0
   int stride;
 };
-template <bool DMA, int WGM = 2, int WGN = 2, int NBUF = 2, int BM = 128, int BN = 128>
+// PACKED: the ranged operand of a profile launch comes from packed panels (GemmArgs::apack / bpack) - instances of
+// their own: the others take every operand as one block
+template <bool DMA, int WGM = 2, int WGN = 2, int NBUF = 2, int BM = 128, int BN = 128, bool PACKED = false>
 __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WGM * WGN / 2) k_dgemm_tn_sk(GemmArgs g, SplitPlan sk) {
   using T = GemmTile<BM, BN, WGM, WGN>;
   extern __shared__ __attribute__((aligned(16))) double lds[];  // tiles + one word for the arrival order
@@ -616,9 +644,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
 #pragma unroll
       for (int y = 0; y < T::TN; y++) acc[x][y] = (double4_t){0.0, 0.0, 0.0, 0.0};
     if constexpr (DMA)
-      T::accumulate_dma(g, tm * BM, tn * BN, s0, s1, acc, As, Bs, g.lower && tm == tn, NBUF);
+      T::template accumulate_dma<PACKED>(g, tm * BM, tn * BN, s0, s1, acc, As, Bs, g.lower && tm == tn, NBUF);
     else
-      T::accumulate(g, tm * BM, tn * BN, s0, s1, acc, As, Bs);
+      T::template accumulate<PACKED>(g, tm * BM, tn * BN, s0, s1, acc, As, Bs);
     bool finish = true;
     if (stamp && threadIdx.x == 0 && r < 10) stamp[1 + 3 * r] = __builtin_amdgcn_s_memrealtime();
     if (pieces > 1) {
@@ -698,6 +726,17 @@ static inline void gemm_launch_plain(int variant, unsigned tiles, hipStream_t s,
     k_dgemm_tn<128, 128><<<tiles, 256, gemm_lds_bytes(128, 128), s>>>(g);
 }
 static inline void gemm_launch_split(int variant, int grid, hipStream_t s, const GemmArgs &g, const SplitPlan &sk) {
+  if (g.apack || g.bpack) {  // (packed panels: the same kernels with the packed addressing)
+    if (variant == GEMM_DMA8X3)
+      k_dgemm_tn_sk<true, 2, 4, 3, 128, 128, true><<<grid, 512, gemm_sk_lds_bytes(3), s>>>(g, sk);
+    else if (variant == GEMM_DMA8)
+      k_dgemm_tn_sk<true, 2, 4, 2, 128, 128, true><<<grid, 512, gemm_sk_lds_bytes(), s>>>(g, sk);
+    else if (variant == GEMM_DMA4)
+      k_dgemm_tn_sk<true, 2, 2, 2, 128, 128, true><<<grid, 256, gemm_sk_lds_bytes(), s>>>(g, sk);
+    else
+      k_dgemm_tn_sk<false, 2, 2, 2, 128, 128, true><<<grid, 256, gemm_sk_lds_bytes(), s>>>(g, sk);
+    return;
+  }
   if (variant == GEMM_DMA8X3)
     k_dgemm_tn_sk<true, 2, 4, 3><<<grid, 512, gemm_sk_lds_bytes(3), s>>>(g, sk);
   else if (variant == GEMM_DMA8)
@@ -726,6 +765,10 @@ static inline hipError_t gemm_set_attributes() {
   set((const void *)k_dgemm_tn_sk<true, 2, 4>, gemm_sk_lds_bytes());
   set((const void *)k_dgemm_tn<128, 128, true, 2, 4, 3>, gemm_lds_bytes(128, 128, 3));
   set((const void *)k_dgemm_tn_sk<true, 2, 4, 3>, gemm_sk_lds_bytes(3));
+  set((const void *)k_dgemm_tn_sk<false, 2, 2, 2, 128, 128, true>, gemm_sk_lds_bytes());
+  set((const void *)k_dgemm_tn_sk<true, 2, 2, 2, 128, 128, true>, gemm_sk_lds_bytes());
+  set((const void *)k_dgemm_tn_sk<true, 2, 4, 2, 128, 128, true>, gemm_sk_lds_bytes());
+  set((const void *)k_dgemm_tn_sk<true, 2, 4, 3, 128, 128, true>, gemm_sk_lds_bytes(3));
   return e;
 }
 // (HQPKKT_SK_TABLE=0: the cut form with equal shares, gemm_equal_table, for same-box comparisons)

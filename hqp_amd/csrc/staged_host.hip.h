@@ -123,6 +123,10 @@ struct StagedDev {
   // for W and one for G.  Made in upload's dry walk and only looked up at a launch, like sk_tabs
   DBuf<int> pf_rng;
   DBuf<double> pf_part;
+  // packed panels (StagedPlan::packed): per panel of every stage its block for the kernels (offset from the stage's F
+  // less 16 lo ld, leading dimension; indexed like pf_rng's pairs), and the partial sums of the carried rows (k_pk_carried)
+  DBuf<stg::PackPanel> pk_tab;
+  DBuf<double> pk_part;
   struct PfTab {
     int M, N, lower, by, stride, hits;
     std::vector<int> panel;  // the ranged operand's panels, two ints each
@@ -223,6 +227,7 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
 // (128 x 128 tiles; the blocks of G_xx one rank owns)
 int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true, int ntiles = 0) {
   if (g.M <= 0 || g.N <= 0) return 0;
+  if (g.apack || g.bpack) return HQPKKT_E_INTERN;  // (packed panels: the profile form's launches alone)
   StagedDev &d = *h->sd;
   // (a launch with a second k segment counts as one of the depth of both: a multiple of the slab)
   const long long nslab = stg::gemm_slabs(g.K) + (g.K2 > 0 ? stg::gemm_slabs(g.K2) : 0);
@@ -272,6 +277,7 @@ int st_gemm_profile(hqpkkt_t *h, stg::GemmArgs g, int k, int by, int cls = KC_ST
   }
   if (f.tile_map && !(g.tile_map = d.tri_map((g.M + 127) / 128))) return HQPKKT_E_INTERN;
   if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
+  if (P.pk_stage(k)) (by == 2 ? g.apack : g.bpack) = d.pk_tab.p + P.pf_ptr[k];  // (the ranged operand: F_k's packed panels)
   StagedDev::PfTab *tab = d.pf_tab(g.M, g.N, g.lower, by, panel, npanel);
   if (!tab) return HQPKKT_E_INTERN;
   tab->hits++;
@@ -554,8 +560,9 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
   const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
   const int want_heavy = P.want_heavy;
+  const bool want_packed = P.want_packed;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy;
+  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
@@ -859,13 +866,23 @@ static int staged_upload(hqpkkt_t *h) {
   // factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
   d.sk_tables_on = stg::gemm_sk_table_from_env();
   d.sk_tabs.clear();
-  d.pf_tabs.clear(), d.pf_rng.release(), d.pf_part.release();
+  d.pf_tabs.clear(), d.pf_rng.release(), d.pf_part.release(), d.pk_tab.release(), d.pk_part.release();
   if (P.profile_dyn && !P.pf_rng.empty()) {
     long long part = 1;
     for (int k = 0; k < P.K; k++)
       if (P.pf_stage[k])
         part = std::max(part, (long long)stg::pf_chunks(P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.panels(k), P.nk[k + 1]) * (P.nk[k] + P.mk[k]));
     if ((e = d.pf_rng.upload(P.pf_rng)) || (e = d.pf_part.alloc((size_t)part))) return e;
+    if (P.packed) {
+      std::vector<stg::PackPanel> tab(P.pk_off.size(), stg::PackPanel{0, 0});
+      long long cpart = 1;
+      for (int k = 0; k < P.K; k++) {
+        if (!P.pk_stage(k)) continue;
+        for (int q = P.pf_ptr[k]; q < P.pf_ptr[k + 1]; q++) tab[q] = stg::PackPanel{P.pk_off[q] - 16LL * P.pf_rng[2 * q] * P.pk_ld[q], P.pk_ld[q]};
+        cpart = std::max(cpart, (long long)stg::pk_chunks(P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.panels(k), P.nk[k + 1]) * P.cap[k + 1] * (P.nk[k] + P.mk[k]));
+      }
+      if ((e = d.pk_tab.upload(tab)) || (e = d.pk_part.alloc((size_t)cpart))) return e;
+    }
   }
   {
     struct Listing {
@@ -1170,7 +1187,8 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
 // its two large products by lists in which a tile takes only the k-slabs that hold its panel's stored entries of F_k -
 // W = V+ F (tile (tm, tn): the range of panel tn) and the whole lower block G = F'W (the range of panel tm) - and no V
 // formed in the G_xx launch.  The thin products (carried rows, the elimination's) stay full-depth dense products: they
-// read the arena's zeros.
+// read the arena's zeros.  A stage with packed panels (StagedPlan::pk_stage) runs the same launches by the same lists
+// with F_k's panels addressed through StagedDev::pk_tab, and its carried rows by k_pk_carried over the ranges alone.
 static int staged_stage_profile(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
@@ -1183,7 +1201,14 @@ static int staged_stage_profile(hqpkkt_t *h, int k) {
       (e = st_gemm_profile(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}, k, 2)))
     return e;
   st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
-  if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
+  if (P.pk_stage(k)) {
+    const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
+    stg::pk_launch_carried(stg::PkCarried{sn.BT, P.ldb[k + 1], sp.F, d.pk_tab.p + P.pf_ptr[k], d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], np, nz, P.cap[k + 1], 0,
+                                          sp.N + (size_t)ek * P.ldn[k], P.ldn[k], d.pk_part.p},
+                           P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_GEMM_UPD, launch()); });
+  } else if ((e = st_carried_rows(h, d, k, sp, sn, true)))
+    return e;
+  if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
   // V = Gxx - Y'Rm (lower tiles, mirrored)
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
@@ -1374,7 +1399,8 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_heavy<<<(nd + 3) / 4, 256, 0, s>>>(stg::SpGemvHeavy{
                                          sp_cols(h, d, k, 0, nn + mm), d.hv_cols.p + P.hv_ptr[k], nd, tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
     } else if (P.profile_dyn && P.pf_stage[k]) {  // gam = q_k + F' tt over the panels' slab ranges
-      stg::pf_launch_cols(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], tt, qv + P.nmk[k], 1.0, gam, d.pf_part.p},
+      stg::pf_launch_cols(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], tt, qv + P.nmk[k], 1.0, gam, d.pf_part.p,
+                                      P.pk_stage(k) ? d.pk_tab.p + P.pf_ptr[k] : nullptr},
                           P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
     } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
@@ -1405,7 +1431,8 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       continue;
     }
     if (P.profile_dyn && P.pf_stage[k]) {  // x+ = F s + f over the panels whose range holds the row
-      stg::pf_launch_rows(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], xk, v.r2 + P.nks[k], 1.0, S + P.nmk[k + 1], nullptr}, s,
+      stg::pf_launch_rows(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], xk, v.r2 + P.nks[k], 1.0, S + P.nmk[k + 1], nullptr,
+                                      P.pk_stage(k) ? d.pk_tab.p + P.pf_ptr[k] : nullptr}, s,
                           [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
       continue;
     }

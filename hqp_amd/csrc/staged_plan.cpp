@@ -274,6 +274,8 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   ldf.assign(K + 1, 8), ldv.assign(K + 1, 8), ldy.assign(K + 1, 8), ldn.assign(K + 1, 8);
   ldb.assign(K + 1, 8), ldq.assign(K + 1, 8), ldt.assign(K + 1, 8), ldg.assign(K + 1, 8);
   oF.assign(K + 1, 0), oV.assign(K + 1, 0);
+  packed = profile_dyn && want_packed;
+  pk_off.assign(packed ? pf_rng.size() / 2 : 0, -1), pk_ld.assign(pk_off.size(), 0);
   oY.assign(K + 1, 0), oR.assign(K + 1, 0), oK.assign(K + 1, 0), oKm.assign(K + 1, 0), oN.assign(K + 1, 0);
   oBT.assign(K + 1, 0), oT.assign(K + 1, 0), oVec.assign(K + 1, 0);
   ldd.assign(K + 1, 8), oD.assign(K + 1, 0);
@@ -293,7 +295,17 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     oVec[k] = mo, mo += up16((long long)nk[k] + 2LL * std::max(cap[k], 1) + std::max(qmax[k], 1) + 8);
     if (k < K) {
       ldf[k] = up8(nz), ldg[k] = up8(nz);
-      if (!sparse_dyn) oF[k] = fo, fo += up16((long long)nk[k + 1] * ldf[k]);
+      if (pk_stage(k)) {  // (packed panels: the rows of every panel's range, back to back)
+        long long po = 0;
+        for (int p = 0; p < panels(k); p++) {
+          const size_t q = (size_t)pf_ptr[k] + p;
+          const int rows = std::min(16 * pf_rng[2 * q + 1], nk[k + 1]) - 16 * pf_rng[2 * q];
+          pk_ld[q] = p + 1 < panels(k) ? 128 : up8(nz - 128 * p);
+          pk_off[q] = po, po += (long long)rows * pk_ld[q];
+        }
+        oF[k] = fo, fo += up16(po);
+      } else if (!sparse_dyn)
+        oF[k] = fo, fo += up16((long long)nk[k + 1] * ldf[k]);
       if (const int nd = heavy_count(k)) {  // (the sparse form's dense block of heavy columns and its work blocks)
         ldd[k] = up8(nd);
         oD[k] = fo, fo += up16((long long)nk[k + 1] * ldd[k]);
@@ -458,7 +470,9 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
           const int lc = Ai[p] - nmk[k];
           if (sparse_dyn) {  // (no dense block but D_k: the kernels read the row lists)
             if (hv_of[lc] >= 0) a_dst[p] = oD[k] + (long long)li * ldd[k] + hv_of[lc];
-          } else if (!sharded)
+          } else if (pk_stage(k))
+            a_dst[p] = oF[k] + pk_at(k, li, lc);
+          else if (!sharded)
             a_dst[p] = oF[k] + (long long)li * ldf[k] + lc;
           else {  // the local block: own state columns, then the control columns
             const int c0 = xcut[(size_t)k * (shard_count + 1) + shard_rank], c1 = xcut[(size_t)k * (shard_count + 1) + shard_rank + 1];

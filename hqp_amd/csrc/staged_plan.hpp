@@ -4,6 +4,7 @@
 // constraint rows, storage plan of the dense stage blocks, term lists of the reduced
 // Hessian H = Q + C'(Z/W)C and the scatter maps of the CSR values.  Integer work only.
 #pragma once
+#include <cstddef>
 #include <vector>
 
 namespace kktdev {
@@ -66,6 +67,21 @@ struct StagedPlan {
   std::vector<int> pf_ptr, pf_rng;
   std::vector<char> pf_stage;
   int panels(int k) const { return pf_ptr.empty() ? 0 : pf_ptr[k + 1] - pf_ptr[k]; }
+  // Packed panels (hqpkkt_set_packed_panels, with the profile form only): a stage that runs the profile sequence stores
+  // F_k panel by panel, back to back from oF[k] - panel p the rows [16 lo_p, min(16 hi_p, n_{k+1})) of its columns,
+  // row-major with leading dimension pk_ld = 128 (the last panel: up8 of its columns); an empty panel takes no room, the
+  // stage's total is rounded up to 16 doubles.  pk_off[pf_ptr[k] + p]: the panel's first element, in doubles from oF[k];
+  // -1 (pk_ld 0) for the panels of a stage that keeps its dense block.  Never larger than the dense block: with exact
+  // row counts sum_p rows_p ld_p <= n_{k+1} up8(n_k + m_k).  want_packed: what the next analysis takes
+  bool want_packed = false, packed = false;
+  std::vector<long long> pk_off;
+  std::vector<int> pk_ld;
+  bool pk_stage(int k) const { return packed && pf_stage[k]; }
+  // element (row li, column lc) of F_k of a packed stage, from oF[k]
+  long long pk_at(int k, int li, int lc) const {
+    const size_t q = (size_t)pf_ptr[k] + lc / 128;
+    return pk_off[q] + (long long)(li - 16 * pf_rng[2 * q]) * pk_ld[q] + lc % 128;
+  }
 
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;

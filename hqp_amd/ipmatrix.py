@@ -343,11 +343,13 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     or ``set_dense_columns(n)`` with it: the columns of F_k with at least n entries go through the MFMA products as
     a small dense block (hqpkkt_set_dense_columns; -1: the library's threshold, 0: none).  ``a_profile=True`` or
     ``set_dynamics_form("profile")``: dense blocks F_k, the large products and the solve over the k-slabs that hold each
-    128-column panel's stored entries - for banded and block-banded dynamics (HQPKKT_DYN_PROFILE)."""
+    128-column panel's stored entries - for banded and block-banded dynamics (HQPKKT_DYN_PROFILE).  ``a_packed=True`` or
+    ``set_packed_panels(True)`` with it: the stages that run the profile sequence store F_k as packed panels, the rows of
+    every panel's range alone (hqpkkt_set_packed_panels)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, **kw):
         super().__init__(*args, **kw)
         if a_sparse:
             self.set_dynamics_form("sparse")
@@ -355,6 +357,8 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
             self.set_dynamics_form("profile")
         if dense_columns:
             self.set_dense_columns(dense_columns)
+        if a_packed:
+            self.set_packed_panels(True)
 
     def set_dynamics_form(self, form):
         """"dense" (default), "sparse" or "profile"; holds from the next init() on."""
@@ -388,6 +392,21 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         K = len(self.debug(21))
         ptr, rng = d[: K + 1], d[K + 1:].reshape(-1, 2)
         return [rng[ptr[k]: ptr[k + 1]].copy() for k in range(K)]
+
+    def set_packed_panels(self, on):
+        """Packed panels of the profile form (hqpkkt_set_packed_panels); holds from the next init() on."""
+        _check(self._L.hqpkkt_set_packed_panels(self._h, int(on)), "set_packed_panels")
+
+    def packed_panels(self):
+        """Per stage k < K an int array of shape (panels, 2): per 128-column panel of F_k its offset in doubles from the
+        stage's first panel and its leading dimension, (-1, 0) where the stage keeps its dense block; [] unless the
+        profile form is set."""
+        d = self.debug(42)
+        if d.size == 0:
+            return []
+        K = len(self.debug(21))
+        ptr, pan = d[: K + 1], d[K + 1:].reshape(-1, 2)
+        return [pan[ptr[k]: ptr[k + 1]].copy() for k in range(K)]
 
     def set_stages(self, nx, nu):
         nx, nu = _i32(nx), _i32(nu)
@@ -495,7 +514,7 @@ def bench_dgemm2(M, N, K, K2, lower=True, mirror=True, reps=1, device=0):
 
 def dgemm_full(M, N, K, C_buf, c_row0, c_col0, A=None, a_col0=0, B=None, b_col0=0, alpha=1.0, beta=0.0, Cin=None, cin_col0=0,
                cin_is_c=False, lower=False, mirror=False, K2=0, A2=None, a2_col0=0, B2=None, b2_col0=0,
-               sharded=False, no_ks=False, no_tile_map=False, force_split=False, device=0, krange=None, krange_by=0):
+               sharded=False, no_ks=False, no_tile_map=False, force_split=False, device=0, krange=None, krange_by=0, packed=None, panel=None):
     """One launch of the STAGED engine's fp64 product on the caller's operands (hqpkkt_debug_dgemm_full): C_buf's block at
     (c_row0, c_col0) = alpha (A'B + A2'B2) + beta Cin.  Every array is a C-contiguous float64 matrix, rows x leading
     dimension; an operand's block starts at its column *_col0 and its rows behind K (K2) are the caller's to poison.
@@ -521,8 +540,55 @@ def dgemm_full(M, N, K, C_buf, c_row0, c_col0, A=None, a_col0=0, B=None, b_col0=
     if krange_by:
         kr = np.ascontiguousarray(krange, dtype=np.int32)
         c.krange, c.krange_by = kr.ctypes.data, int(krange_by)
-    _check(_lib.lib().hqpkkt_debug_dgemm_full(device, C.byref(c)), "debug_dgemm_full")
+    if packed is not None:
+        pk, pan = _packed_args(packed, panel)
+        _check(_lib.lib().hqpkkt_debug_dgemm_packed(device, C.byref(c), pk.ctypes.data, pk.size, pan.ctypes.data), "debug_dgemm_packed")
+    else:
+        _check(_lib.lib().hqpkkt_debug_dgemm_full(device, C.byref(c)), "debug_dgemm_full")
     return (GEMM_FORMS + ("profile",))[c.form], c.tiles, bool(c.tile_map), bool(c.ldsdma), c.nsplit
+
+
+def _packed_args(packed, panel):
+    import numpy as np
+    assert packed.dtype == np.float64 and packed.ndim == 1 and packed.flags.c_contiguous
+    return packed, np.ascontiguousarray(panel, dtype=np.int64)
+
+
+def dgemm_packed(M, N, K, C_buf, c_row0, c_col0, packed, panel, krange, krange_by, **kw):
+    """:func:`dgemm_full` with the ranged operand (krange_by 1: B, 2: A) given as packed panels
+    (hqpkkt_debug_dgemm_packed): ``packed`` a flat float64 buffer, ``panel`` (offset, ld) per 128-column panel of the
+    operand, ``krange`` its (lo, hi) k-slabs.  The other operand and C_buf as in dgemm_full."""
+    return dgemm_full(M, N, K, C_buf, c_row0, c_col0, krange=krange, krange_by=krange_by, packed=packed, panel=panel, **kw)
+
+
+def gemv_packed(packed, panel, ranges, x, K, N, add=None, alpha=1.0, rows_form=False, y=None, device=0):
+    """:func:`gemv_profile` on packed panels (hqpkkt_debug_gemv_packed): A is K x N, given as a flat float64 buffer and
+    (offset, ld) per 128-column panel."""
+    import numpy as np
+    pk, pan = _packed_args(packed, panel)
+    r = np.ascontiguousarray(ranges, dtype=np.int32)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    add = None if add is None else np.ascontiguousarray(add, dtype=np.float64)
+    y = np.zeros(K if rows_form else N) if y is None else y
+    assert x.size == (N if rows_form else K) and y.size == (K if rows_form else N) and r.size == 2 * ((N + 127) // 128) == pan.size
+    _check(_lib.lib().hqpkkt_debug_gemv_packed(device, int(rows_form), K, N, pk.ctypes.data, pk.size, pan.ctypes.data, r.ctypes.data, x.ctypes.data,
+                                               None if add is None else add.ctypes.data, float(alpha), y.ctypes.data), "debug_gemv_packed")
+    return y
+
+
+def carried_packed(BT, R, packed, panel, ranges, K, N, C_buf, c_row0, c_col0, device=0):
+    """The carried rows of a packed stage (hqpkkt_debug_carried_packed, k_pk_carried): C_buf's block at (c_row0, c_col0)
+    = BT[:K, :R]' F over every panel's range, F (K x N) given as packed panels.  BT and C_buf are C-contiguous float64
+    matrices; C_buf is overwritten with the whole device buffer after the launch."""
+    import numpy as np
+    pk, pan = _packed_args(packed, panel)
+    r = np.ascontiguousarray(ranges, dtype=np.int32)
+    for a in (BT, C_buf):
+        assert a.dtype == np.float64 and a.ndim == 2 and a.flags.c_contiguous
+    assert r.size == 2 * ((N + 127) // 128) == pan.size
+    _check(_lib.lib().hqpkkt_debug_carried_packed(device, K, N, R, BT.ctypes.data, BT.shape[0], BT.shape[1], pk.ctypes.data, pk.size, pan.ctypes.data,
+                                                  r.ctypes.data, C_buf.ctypes.data, C_buf.shape[0], C_buf.shape[1], c_row0, c_col0), "debug_carried_packed")
+    return C_buf
 
 
 SK_KINDS = ("unequal", "equal", "frac")

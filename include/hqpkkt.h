@@ -323,11 +323,25 @@ int hqpkkt_set_stages(hqpkkt_t *h, int K, const int *nx, const int *nu);
  * its two large MFMA products W = V+ F and G = F'W, and the solve's two products with F_k, over those slabs alone; every
  * other stage runs the dense sequence and gives the dense form's bits.  The rules of HQPKKT_DYN_SPARSE hold:
  * hqpkkt_analyze_staged returns HQPKKT_E_INTERN, a sharded handle HQPKKT_E_RANGE at hqpkkt_analyze;
- * hqpkkt_set_dense_columns is accepted and ignored.  No form is chosen automatically. */
+ * hqpkkt_set_dense_columns is accepted and ignored.  No form is chosen automatically.
+ * Where the arena of dense blocks does not fit the device (hqpkkt_stats.bytes_panels; a band of 50 under 5000 states
+ * is almost all zeros), set the sparse form for dynamics of a few entries per column, and HQPKKT_DYN_PROFILE with
+ * hqpkkt_set_packed_panels for banded and block-banded ones. */
 #define HQPKKT_DYN_DENSE 0   /* default: dense blocks F_k, MFMA products           */
 #define HQPKKT_DYN_SPARSE 1  /* Hqp_IpLQDOCP's mat_a_sparse: F_k stays row lists   */
 #define HQPKKT_DYN_PROFILE 3 /* dense blocks F_k, products over the panels' k-slabs (2 is not a form: HQPKKT_E_RANGE) */
 int hqpkkt_set_dynamics_form(hqpkkt_t *h, int form);
+/* Packed panels of the profile form.  With on = 1 a stage that runs the profile sequence stores F_k panel by panel
+ * instead of as a dense block: panel p holds the rows [16 lo_p, min(16 hi_p, n_{k+1})) of its 128 columns, row-major with
+ * leading dimension 128 (the last panel: its columns rounded up to 8), the panels back to back, an empty one taking no
+ * room, the stage's total rounded up to 16 doubles.  hqpkkt_stats.bytes_panels shrinks accordingly - never grows - and
+ * the stage runs the same launches by the same work lists with the panels addressed through a table, the carried rows
+ * N = B+ F over the ranges alone (k_pk_carried).  Every other stage keeps its dense block.  Host only; call it before
+ * hqpkkt_analyze; it holds until set again.  It has an effect only together with HQPKKT_DYN_PROFILE and is accepted and
+ * ignored on any other form; the profile form's rules stand (no dense hand-over, no sharded handle).  0 (default): the
+ * arena, launches and bits of a handle that never asked.  HQPKKT_E_NULL; HQPKKT_E_INTERN: not a STAGED handle;
+ * HQPKKT_E_RANGE: on is neither 0 nor 1.  hqpkkt_debug_get 42 reports the layout. */
+int hqpkkt_set_packed_panels(hqpkkt_t *h, int on);
 /* Heavy columns of the sparse form.  Its column walks give one lane one column of F_k, so a stage takes as long as its
  * longest column: a dense control column or a global state among banded ones costs a serial loop over every state.  With
  * min_entries = n > 0 a column of F_k that holds at least n stored entries in its stage's dynamics rows is "heavy": the
@@ -452,6 +466,24 @@ int hqpkkt_debug_sk_profile(const int *ranges, long long tiles, int grid, int *u
 int hqpkkt_debug_gemv_profile(int device, int rows_form, int K, int N, const double *A, long long a_rows, long long ld, const int *ranges,
                               const double *x, const double *add, double alpha, double *y);
 
+/* Test hooks of the packed panels (hqpkkt_set_packed_panels).  The caller packs: `packed` is a host buffer of
+ * packed_elems doubles, `panel` holds two long longs per 128-column panel of the K-row operand - the offset of the
+ * panel's first element (even) and its leading dimension (a multiple of 8, at least the panel's columns) - and the ranges
+ * are (lo, hi) k-slab pairs as in hqpkkt_dgemm_case.  Panel p's rows [16 lo_p, min(16 hi_p, K)) must lie inside the buffer
+ * (HQPKKT_E_RANGE otherwise); nothing outside them is read as a value that counts.
+ * hqpkkt_debug_dgemm_packed: hqpkkt_debug_dgemm_full with c->krange_by 1 / 2 and c->krange set, in which operand B / A
+ * of the case is not read and comes from the packed buffer (K2 must be 0); both staging paths take it.
+ * hqpkkt_debug_gemv_packed: hqpkkt_debug_gemv_profile on packed panels.
+ * hqpkkt_debug_carried_packed: the carried rows of a packed stage, C[c_row0 + r][c_col0 + c] = sum over the rows k of
+ * panel(c)'s range of BT[k][r] F[k][c] for r < R, c < N; BT: bt_rows >= K rows of ldb >= R doubles; C: a host buffer of
+ * c_rows x ldc doubles that goes to the device whole and comes back whole after the launch. */
+int hqpkkt_debug_dgemm_packed(int device, hqpkkt_dgemm_case *c, const double *packed, long long packed_elems, const long long *panel);
+int hqpkkt_debug_gemv_packed(int device, int rows_form, int K, int N, const double *packed, long long packed_elems, const long long *panel,
+                             const int *ranges, const double *x, const double *add, double alpha, double *y);
+int hqpkkt_debug_carried_packed(int device, int K, int N, int R, const double *BT, long long bt_rows, long long ldb, const double *packed,
+                                long long packed_elems, const long long *panel, const int *ranges, double *C, long long c_rows, long long ldc,
+                                long long c_row0, long long c_col0);
+
 /* Test hook, host only: the form the STAGED engine's launch rule (gemm_form.hpp) gives an M x N x K product on a device
  * of `cus` CUs with a split grid of `grid` workgroups (0: none), arrival counters for sk_tiles tiles and workspaces of
  * ws_elems / ws2_elems doubles (first / second stream).  flags: 1 one system over several ranks, 2 a launch of the
@@ -559,7 +591,9 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * such level, LDS bytes of that launch); 40 (device buffers and pinned host buffers the library holds in this
  * process, over all handles: answered on any handle, analysed or not); 41 the profile form's ranges: K + 1 pointers, then
  * the (lo, hi) k-slab pairs of the 128-column panels of every stage's F_k; empty unless HQPKKT_DYN_PROFILE is set; valid
- * after hqpkkt_analyze, without a device.
+ * after hqpkkt_analyze, without a device; 42 the packed panels (hqpkkt_set_packed_panels): the same K + 1 pointers, then
+ * per panel two ints, its offset in doubles from the stage's first panel and its leading dimension, (-1, 0) for the
+ * panels of a stage that keeps its dense block; empty unless HQPKKT_DYN_PROFILE is set.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

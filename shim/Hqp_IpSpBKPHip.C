@@ -52,6 +52,7 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
   _a_sparse = 0;
   _a_heavy = 0;
   _a_profile = 0;
+  _a_packed = 0;
   _told_ignored = false;
   _logging = getenv("HQPKKT_SHIM_LOGGING") ? atoi(getenv("HQPKKT_SHIM_LOGGING")) : 0;
   if (mode == HQPKKT_MODE_STAGED) {
@@ -59,6 +60,7 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
     _ifList.append(new If_Int("mat_a_sparse", &_a_sparse));
     _ifList.append(new If_Int("mat_a_heavy", &_a_heavy));
     _ifList.append(new If_Int("mat_a_profile", &_a_profile));
+    _ifList.append(new If_Int("mat_a_packed", &_a_packed));
     _ifList.append(new If_Int("mat_logging", &_logging));
   }
 
@@ -375,7 +377,8 @@ int Hqp_IpMatrixHip::open(int mode, int dyn_form)
   if ((e = create_handle(mode)))
     return e;
   _dense = false;
-  if (dyn_form != HQPKKT_DYN_DENSE && ((e = hqpkkt_set_dynamics_form(_h, dyn_form)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy))))
+  if (dyn_form != HQPKKT_DYN_DENSE && ((e = hqpkkt_set_dynamics_form(_h, dyn_form)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy)) ||
+                                       (e = hqpkkt_set_packed_panels(_h, _a_packed != 0))))
     return e;
   if ((e = hqpkkt_analyze(_h, _n, _me, _m,
                           _Qp->ive, _Qi->ive, _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive,
@@ -426,7 +429,8 @@ void Hqp_IpMatrixHip::init(const Hqp_Program *qp)
       if (sparse_dyn && _mode_used == HQPKKT_MODE_STAGED)
         fprintf(stderr, ": STAGED engine, sparse form of the stage products (mat_a_sparse)\n");
       else if (profile_dyn && _mode_used == HQPKKT_MODE_STAGED)
-        fprintf(stderr, ": STAGED engine, profile form of the stage products (mat_a_profile)\n");
+        fprintf(stderr, ": STAGED engine, profile form of the stage products (mat_a_profile)%s\n",
+                _a_packed ? ", F_k in packed panels (mat_a_packed)" : "");
       else if (_dense)
         fprintf(stderr, ", %d stages (x_0: %d states; widest stage %d states + %d controls), %d dynamics rows as dense "
                 "blocks: STAGED engine\n", _K, _nx->ive[0], _nx->ive[_K], _K ? _nu->ive[0] : 0, _ndyn);

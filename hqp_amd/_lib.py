@@ -33,6 +33,7 @@ SYMBOLS = [
     "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
     "hqpkkt_debug_sk_profile", "hqpkkt_debug_gemv_profile",
     "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
+    "hqpkkt_set_dense_rows",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -153,6 +154,7 @@ def lib():
     L.hqpkkt_set_dynamics_form.argtypes = [vp, C.c_int]
     L.hqpkkt_set_dense_columns.argtypes = [vp, C.c_int]
     L.hqpkkt_set_packed_panels.argtypes = [vp, C.c_int]
+    L.hqpkkt_set_dense_rows.argtypes = [vp, C.c_int]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

@@ -7,6 +7,7 @@
 #include "staged.hip.h"
 #include "staged_sparse.hip.h"
 #include "staged_profile.hip.h"
+#include "staged_rows.hip.h"
 #include "staged_host.hip.h"
 
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn) {
@@ -135,6 +136,16 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       for (size_t q = 0; q < P.pf_rng.size() / 2; q++)
         out.push_back(P.packed ? (int)P.pk_off[q] : -1), out.push_back(P.packed ? P.pk_ld[q] : 0);
       break;
+    case 43:  // the wide rows of C (hqpkkt_set_dense_rows; host only): K + 2 pointers, then the wide rows of every stage 0 .. K as row
+              // indices of C, ascending, then per stage the H terms the plan kept and the terms its wide rows would have added,
+              // each a 64-bit count as (low, high) ints; empty unless the analysis had a threshold
+      if (P.rows_min > 0) {
+        out = P.wr_ptr;
+        out.insert(out.end(), P.wr_rows.begin(), P.wr_rows.end());
+        for (int k = 0; k <= P.K; k++)
+          for (long long c : {P.h_kept[k], P.h_cut[k]}) out.push_back((int)(unsigned)(c & 0xffffffffLL)), out.push_back((int)(c >> 32));
+      }
+      break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
       for (const StagedDev::SkTab &t : h->sd->sk_tabs)
@@ -166,6 +177,18 @@ int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries) {
     if (min_entries < -1) return HQPKKT_E_RANGE;
     if (!h->sd) h->sd.reset(new StagedDev);
     h->sd->plan.want_heavy = min_entries;  // (the next hqpkkt_analyze picks it up; read by the sparse form alone)
+    return 0;
+  });
+}
+
+int hqpkkt_set_dense_rows(hqpkkt_t *h, int min_entries) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    // (-1, the library's threshold: none has been measured yet)
+    if (min_entries < -1 || (min_entries == -1 && kktdev::StagedPlan::ROWS_DEFAULT <= 0)) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_rows = min_entries;  // (the next analysis picks it up; a sharded handle keeps its term lists)
     return 0;
   });
 }

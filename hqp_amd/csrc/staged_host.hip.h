@@ -10,6 +10,8 @@ struct StagedDev {
   DBuf<double> F, V, misc;
   DBuf<int> dyn, eq_rows, fix_rows, fix_src, h_tptr, chk_idx, chk_kind;
   DBuf<long long> h_dst, a_dst;
+  DBuf<long long> c_dst;  // the wide rows of C (StagedPlan::wr_rows): where k_st_scatter puts C's values, and the rows
+  DBuf<int> wr_rows;
   DBuf<stg::HTerm> h_terms;
   DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
@@ -446,6 +448,19 @@ static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G,
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
                                                                                h->td.vals.p, h->td.wt.p, G, add));
 }
+// ... and the share of the stage's wide rows of C (StagedPlan::wr_rows, r of them): G += S'S over the lower tiles with
+// S = diag(sqrt(z / w)) E_k (k_st_rows_scale), a product of depth r in place; stage K: into V_K with its mirror image.
+// Both operands are S, so entry (i, j) and its image are the same sum of the same products
+static int st_add_h_wide(hqpkkt_t *h, StagedDev &d, int k, double *G, long long ldg) {
+  const kktdev::StagedPlan &P = d.plan;
+  const int r = P.wide_count(k), nz = k < P.K ? P.nk[k] + P.mk[k] : P.nk[k];
+  if (r <= 0 || nz <= 0) return 0;
+  const long long ld = P.ldE[k];
+  double *S = d.misc.p + P.oSr;
+  KLAUNCH(h, KC_ASSEMBLE, stg::k_st_rows_scale<<<nblk(r * (ld / 2)), 256, 0, h->stream>>>(
+                              stg::RowsScale{d.F.p + P.oE[k], S, d.wr_rows.p + P.wr_ptr[k], h->td.wt.p, r, ld}));
+  return st_gemm(h, stg::GemmArgs{S, ld, S, ld, G, ldg, G, ldg, nz, nz, r, 1.0, 1.0, 1, k == P.K ? 1 : 0}, KC_ST_GEMM_UPD);
+}
 // the carried rows of stage k: N_k[e..] = B+ F (nothing where stage k + 1 carries none)
 static int st_carried_rows(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, bool allow_sk) {
   const kktdev::StagedPlan &P = d.plan;
@@ -559,10 +574,10 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   kktdev::StagedPlan &P = d.plan;
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
   const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
-  const int want_heavy = P.want_heavy;
+  const int want_heavy = P.want_heavy, want_rows = P.want_rows;
   const bool want_packed = P.want_packed;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed;
+  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed, P.want_rows = want_rows;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
@@ -654,6 +669,7 @@ static int staged_upload(hqpkkt_t *h) {
       (e = d.fix_src.upload(P.fix_src)) || (e = d.h_tptr.upload(P.h_tptr)) || (e = d.chk_idx.upload(P.chk_idx)) ||
       (e = d.chk_kind.upload(P.chk_kind)) || (e = d.h_dst.upload(P.h_dst)) || (e = d.a_dst.upload(P.a_dst)))
     return e;
+  if (!P.wr_rows.empty() && ((e = d.c_dst.upload(P.c_dst)) || (e = d.wr_rows.upload(P.wr_rows)))) return e;
   {
     std::vector<stg::HTerm> t(P.h_terms.size());
     for (size_t k = 0; k < t.size(); k++) t[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
@@ -754,6 +770,7 @@ static int staged_upload(hqpkkt_t *h) {
       for (int k = 0; k < P.K; k++) {
         const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
         if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
+        if (P.wide_count(k)) continue;                  // (the wide rows' product goes into the work block G)
         if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0 || (mode != 1 && nn < FUSED_V_MIN_STATES)) continue;
         const long long nslab = stg::gemm_slabs(np) + stg::gemm_slabs(q);
         const stg::GemmForm f = d.gemm_form(nn, nn, (int)(nslab * stg::GEMM_BK), 1, 1);
@@ -985,6 +1002,8 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
   HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
   if (an.na)
     stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
+  if (!P.wr_rows.empty())  // the wide rows of C into their blocks E_k
+    stg::k_st_scatter<<<nblk(an.nc), 256, 0, s>>>(an.nc, d.c_dst.p, h->td.vals.p + an.nq + an.na, d.F.p, d.misc.p);
   const int nchk = (int)P.chk_idx.size();
   if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.chk_idx.p, d.chk_kind.p, h->td.vals.p, h->td.flags.p);
   int *hs = (int *)h->kept.hpin.p;
@@ -1154,7 +1173,8 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
   // The control-sized chain of the stage on the second stream, beside the large product G_xx (needs the
   // control columns to start at an even column: 16-byte loads of W + n)
-  const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096));
+  // (not a stage with wide rows of C: their product adds into the whole lower block of G)
+  const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096)) && !P.wide_count(k);
   hipStream_t sA = h->stream, sB = ovl ? d.stream2 : h->stream;
   StreamGuard guard{h, sA};
   StreamFork chain{h, sA, sB, d.ev_fork, d.ev_join};
@@ -1167,6 +1187,7 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
     // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
     st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
+    if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
   } else {
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
     st_add_h(h, d, P.h_ptr[k], ne_x, G);
@@ -1201,6 +1222,7 @@ static int staged_stage_profile(hqpkkt_t *h, int k) {
       (e = st_gemm_profile(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}, k, 2)))
     return e;
   st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
+  if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
   if (P.pk_stage(k)) {
     const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
     stg::pk_launch_carried(stg::PkCarried{sn.BT, P.ldb[k + 1], sp.F, d.pk_tab.p + P.pf_ptr[k], d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], np, nz, P.cap[k + 1], 0,
@@ -1268,7 +1290,7 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
                                  nz, nd, cx, d.hv_cols.p + P.hv_ptr[k], d.hv_of.p + P.nmk[k], Gh, ldg, Ghh, ldd, G, ldg, Nh, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
   }
   st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
-  if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
+  if ((e = st_add_h_wide(h, d, k, G, ldg)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
 }
 
@@ -1293,6 +1315,7 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
     st_add_h(h, d, P.h_ptr[K], P.h_ptr[K + 1] - P.h_ptr[K], sp.V, 0);
+    if (!P.sharded && (e = st_add_h_wide(h, d, K, sp.V, P.ldv[K]))) return e;
     KLAUNCH(h, KC_ST_SMALL, stg::k_st_last<<<nblk(std::max(nK, 1)), 256, 0, s>>>(nK, eK, P.cap[K], sp.N, P.ldn[K], sp.BT, P.ldb[K], sp.dyn));
     if (P.sharded) st_keep_rows(h, d, K);
   }

@@ -223,6 +223,20 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     }
   }
 
+  // ------------------------------------------------------------------ wide rows of C
+  rows_min = sharded ? 0 : want_rows < 0 ? ROWS_DEFAULT : want_rows;
+  wr_ptr.clear(), wr_rows.clear(), ldE.clear(), oE.clear(), c_dst.clear(), oSr = 0;
+  if (rows_min > 0) {
+    std::vector<std::vector<int>> wide(K + 1);
+    for (int r = 0; r < m; r++)
+      if (Cp[r + 1] - Cp[r] >= rows_min) wide[stage_of[Ci[Cp[r]]]].push_back(r);
+    wr_ptr.assign(K + 2, 0);
+    for (int k = 0; k <= K; k++) {
+      wr_rows.insert(wr_rows.end(), wide[k].begin(), wide[k].end());
+      wr_ptr[k + 1] = (int)wr_rows.size();
+    }
+  }
+
   // ------------------------------------------------------------------ capacities
   cap.assign(K + 1, 0), capn.assign(K + 1, 0), qmax.assign(K + 1, 0);
   cap[K] = capn[K] = (int)eq[K].size();
@@ -357,6 +371,16 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   oS = mo, mo += up16(n + 8);
   oQv = mo, mo += up16(n + 8);
   oScr = mo, mo += up16(scratch_elems);
+  ldE.assign(K + 1, 8), oE.assign(K + 1, 0);
+  if (!wr_rows.empty()) {  // (the blocks E_k behind every dynamics block; the work block S for the largest of them)
+    long long smax = 0;
+    for (int k = 0; k <= K; k++) {
+      ldE[k] = up8(std::max(k < K ? nk[k] + mk[k] : nk[k], 1));
+      oE[k] = fo, fo += (long long)wide_count(k) * ldE[k];
+      smax = std::max(smax, (long long)wide_count(k) * ldE[k]);
+    }
+    oSr = mo, mo += up16(smax);
+  }
   // ------------------------------------------------------------------ one system over several ranks (staged_plan.hpp)
   xcut.clear(), xw.clear(), ldfl.clear(), oFl.clear(), oVs.clear(), fgslot.clear(), ldwl.clear(), xslot.clear();
   xrects.clear(), xrect_ptr.clear(), gtile.clear(), gtile_ptr.clear();
@@ -491,15 +515,36 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
       for (int p = Ap[i]; p < Ap[i + 1]; p++) a_dst[p] = -(oN[k] + (long long)li * ldn[k] + lcol(Ai[p]) + 2);
     }
   for (int s : fix_src) chk_idx.push_back(s), chk_kind.push_back(1);
+  if (!wr_rows.empty()) {  // ... and of the wide rows of C
+    c_dst.assign(nc, -1);
+    for (int k = 0; k <= K; k++)
+      for (int q = wr_ptr[k]; q < wr_ptr[k + 1]; q++)
+        for (int p = Cp[wr_rows[q]]; p < Cp[wr_rows[q] + 1]; p++) c_dst[p] = oE[k] + (long long)(q - wr_ptr[k]) * ldE[k] + lcol(Ci[p]);
+  }
 
   // ------------------------------------------------------------------ H term lists
+  // the terms are counted before anything is reserved for them: h_tptr and the device lists index them with ints, and
+  // a row of C with L entries holds L^2 of them
+  h_kept.assign(K + 1, 0), h_cut.assign(K + 1, 0);
   {
+    std::vector<char> is_wide(m, 0);
+    for (int r : wr_rows) is_wide[r] = 1;
+    for (int i = 0; i < n; i++)
+      for (int p = Qp[i]; p < Qp[i + 1]; p++)
+        if (Qi[p] >= i) h_kept[stage_of[i]] += Qi[p] > i ? 2 : 1;
+    long long kept = 0;
+    for (int r = 0; r < m; r++) {
+      const long long L = Cp[r + 1] - Cp[r];
+      (is_wide[r] ? h_cut : h_kept)[stage_of[Ci[Cp[r]]]] += L * L;
+    }
+    for (int k = 0; k <= K; k++) kept += h_kept[k];
+    if (kept > 0x7fffffffLL) return 1;
     struct Raw {
       long long key;  // stage << 45 | (touches a control row / column) << 44 | li * ld + lj
       Term t;
     };
     std::vector<Raw> raw;
-    raw.reserve((size_t)nq * 2 + (size_t)nc * 2);
+    raw.reserve(wr_rows.empty() ? (size_t)nq * 2 + (size_t)nc * 2 : (size_t)kept);
     const int ONE = nq + na + nc, WONE = m;
     auto ldof = [&](int k) { return k < K ? ldg[k] : ldv[K]; };
     auto push = [&](int k, int li, int lj, Term t) {
@@ -515,6 +560,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
         if (j != i) push(k, lcol(j), lcol(i), Term{p, ONE, WONE});
       }
     for (int r = 0; r < m; r++) {
+      if (is_wide[r]) continue;  // (the block E_k holds it: st_add_h_wide)
       const int k = stage_of[Ci[Cp[r]]];
       for (int pa = Cp[r]; pa < Cp[r + 1]; pa++)
         for (int pb = Cp[r]; pb < Cp[r + 1]; pb++)
@@ -560,6 +606,10 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
       bytes_step += 8 * (2 * np * np + 2 * np * nz + 2 * q * nn);
     }
     flops_factor += 2 * q * q * nn + q * nn * nn;         // Rm, V update (lower half)
+  }
+  for (int k = 0; k <= K; k++) {  // the wide rows' products S'S, lower half
+    const long long nz = k < K ? nk[k] + mk[k] : nk[k];
+    flops_factor += wide_count(k) * nz * nz;
   }
   return 0;
 }

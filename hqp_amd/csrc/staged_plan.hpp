@@ -83,6 +83,24 @@ struct StagedPlan {
     return pk_off[q] + (long long)(li - 16 * pf_rng[2 * q]) * pk_ld[q] + lc % 128;
   }
 
+  // Wide rows of C (hqpkkt_set_dense_rows): a row of the inequality block with at least rows_min stored entries (0: none)
+  // leaves the H term lists - L entries are L^2 terms there - and is kept as a row of the dense block E_k of its stage
+  // k = 0..K: wide_count(k) rows of ldE[k] = up8(n_k + m_k) doubles (stage K: up8(n_K)) at oE[k] in the F arena, row-major
+  // (k-major: either operand of the MFMA product), behind every stage's dynamics blocks.  wr_rows[wr_ptr[k] ..
+  // wr_ptr[k + 1]): the wide rows of stage k as row indices of C, ascending.  c_dst: per stored entry of C its place in
+  // the F arena or -1 (k_st_scatter runs it as it runs a_dst; the arena is cleared at upload and nothing else writes
+  // the blocks: the padding stays zero); empty without wide rows.  oSr: the work block S = diag(sqrt(z / w)) E_k of the
+  // stage in work, in the misc arena, sized for the largest stage.  Everything else of the rows stays in C / C'.
+  // h_kept[k] / h_cut[k]: H terms of stage k in the lists / the terms its wide rows would have added.
+  // want_rows: what the next analysis takes (-1: ROWS_DEFAULT; 0 there: no threshold has been measured and the setter
+  // refuses -1); a sharded handle keeps its term lists (rows_min = 0)
+  static const int ROWS_DEFAULT = 0;
+  int want_rows = 0, rows_min = 0;
+  std::vector<int> wr_ptr, wr_rows, ldE;
+  std::vector<long long> oE, c_dst, h_kept, h_cut;
+  long long oSr = 0;
+  int wide_count(int k) const { return wr_ptr.empty() ? 0 : wr_ptr[k + 1] - wr_ptr[k]; }
+
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;
   int q0max = 0, ldq0 = 8;  // free initial state: order of [V_0 B_0'; B_0 0]
@@ -179,7 +197,7 @@ struct StagedPlan {
   std::vector<int> given_nx, given_nu;
 
   // returns 0, or a HQPKKT_E_* code: 6 the pattern is not a staircase / rows leave their stage,
-  // 1 a stage exceeds what the one-workgroup kernels hold
+  // 1 a stage exceeds what the one-workgroup kernels hold, or the H term lists would hold more than 2^31 - 1 terms
   // (ATp, ATi: the CSR arrays of A' as Analysis::setup_blocks builds them, rows ascending; read by the sparse form alone)
   int run(int n, int me, int m, const int *Qp, const int *Qi, const int *Ap, const int *Ai, const int *Cp,
           const int *Ci, const int *ATp = nullptr, const int *ATi = nullptr);

@@ -345,11 +345,13 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     ``set_dynamics_form("profile")``: dense blocks F_k, the large products and the solve over the k-slabs that hold each
     128-column panel's stored entries - for banded and block-banded dynamics (HQPKKT_DYN_PROFILE).  ``a_packed=True`` or
     ``set_packed_panels(True)`` with it: the stages that run the profile sequence store F_k as packed panels, the rows of
-    every panel's range alone (hqpkkt_set_packed_panels)."""
+    every panel's range alone (hqpkkt_set_packed_panels).  ``dense_rows=n`` or ``set_dense_rows(n)``, with any form of
+    the dynamics: the rows of C with at least n entries leave the H term lists and go through the MFMA product as a
+    dense block per stage (hqpkkt_set_dense_rows; 0: none)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, dense_rows=0, **kw):
         super().__init__(*args, **kw)
         if a_sparse:
             self.set_dynamics_form("sparse")
@@ -359,6 +361,8 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
             self.set_dense_columns(dense_columns)
         if a_packed:
             self.set_packed_panels(True)
+        if dense_rows:
+            self.set_dense_rows(dense_rows)
 
     def set_dynamics_form(self, form):
         """"dense" (default), "sparse" or "profile"; holds from the next init() on."""
@@ -378,6 +382,30 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         K = len(self.debug(21))
         ptr, cols = d[: K + 1], d[K + 1:]
         return [cols[ptr[k]: ptr[k + 1]].tolist() for k in range(K)]
+
+    def set_dense_rows(self, min_entries):
+        """Rows of C with at least ``min_entries`` entries are wide (holds from the next init() on)."""
+        _check(self._L.hqpkkt_set_dense_rows(self._h, int(min_entries)), "set_dense_rows")
+
+    def dense_rows(self):
+        """Per stage k = 0 .. K the wide rows of C (row indices of C, ascending); [] unless the analysis had a threshold."""
+        d = self.debug(43)
+        if d.size == 0:
+            return []
+        K = len(self.debug(21))
+        ptr, rows = d[: K + 2], d[K + 2:]
+        return [rows[ptr[k]: ptr[k + 1]].tolist() for k in range(K + 1)]
+
+    def h_terms(self):
+        """(kept, removed): per stage k = 0 .. K the H terms in the plan's lists and the terms the stage's wide rows
+        would have added, as int64 arrays; ([], []) unless the analysis had a threshold."""
+        d = self.debug(43)
+        if d.size == 0:
+            return [], []
+        K = len(self.debug(21))
+        c = d[K + 2 + d[K + 1]:].astype(np.int64).reshape(K + 1, 2, 2)
+        c = (c[..., 0] & 0xFFFFFFFF) | (c[..., 1] << 32)
+        return c[:, 0].copy(), c[:, 1].copy()
 
     def dynamics_entries(self):
         """Per stage k < K: (stored entries of F_k, 1 where the stage runs the sparse sequence, 2 the profile sequence)."""

@@ -193,7 +193,9 @@ def lq_docp(K, nx, nu, seed=3, density=1.0, x0_fixed=True, final_eq=0, path_eq=0
         cv = np.concatenate([cv, -np.ones(xb.size)])
         m += xb.size
     C = _csr(cr, cc, cv, m)
-    return Program(n, me, m, Q, A, C, c=rng.uniform(-0.1, 0.1, n), b=b, d=np.ones(m))
+    prog = Program(n, me, m, Q, A, C, c=rng.uniform(-0.1, 0.1, n), b=b, d=np.ones(m))
+    prog.nx, prog.nu = [nx] * (K + 1), [nu] * K
+    return prog
 
 
 def sparse_docp(K, nx, nu, band=5, seed=3, x0_fixed=True, final_eq=0, path_eq=0, path_eq_every=1, x_bounds=0,
@@ -321,6 +323,39 @@ def with_dense_columns(prog, cols, seed=99, scale=0.05):
         ar.append(missing), ac.append(np.full(missing.size, col)), av.append(scale * rng.uniform(-1, 1, missing.size))
     A = _csr(np.concatenate(ar), np.concatenate(ac), np.concatenate(av), prog.me)
     out = Program(prog.n, prog.me, prog.m, prog.Q, A, prog.C, c=prog.c, b=prog.b, d=prog.d)
+    out.nx, out.nu = nxs, nus
+    return out
+
+
+def with_wide_rows(prog, rows, seed=77, scale=0.05):
+    """A copy of an :func:`lq_docp` / :func:`sparse_docp` program with extra inequality rows of many entries, appended
+    behind the existing rows of ``C``: for every ``(k, L, controls)`` one row with L entries ``scale * U(-1, 1)`` in
+    random columns of stage k's states (``k = K``: the terminal stage); with ``controls`` the L columns are drawn from
+    the stage's states and controls together, at least one of them a control.  Columns and values come from
+    ``default_rng(seed)`` in the order of ``rows``.  The row's offset in ``d`` is 1, like the bounds of lq_docp: x = 0
+    is strictly inside.  The workload of ``Hqp_IpLQDOCP(dense_rows=n)``: output constraints with a dense c, sums over
+    the states of a discretised PDE, polytopic terminal sets."""
+    rng = np.random.default_rng(seed)
+    nxs, nus = list(prog.nx), list(prog.nu)
+    K = len(nus)
+    off = np.concatenate([[0], np.cumsum([nxs[k] + nus[k] for k in range(K)])]).astype(np.int64)
+    p, i, x = (np.asarray(a) for a in prog.C)
+    cr, cc, cv = [np.repeat(np.arange(prog.m), np.diff(p))], [i], [np.asarray(x, dtype=float)]
+    m = prog.m
+    for k, L, controls in rows:
+        assert 0 <= k <= K and not (controls and k == K)
+        if controls:
+            nctl = min(nus[k], max(1, (L * nus[k]) // (nxs[k] + nus[k])))
+            assert nctl <= L <= nxs[k] + nus[k] and L - nctl <= nxs[k]
+            cols = np.concatenate([rng.choice(nxs[k], size=L - nctl, replace=False),
+                                   nxs[k] + rng.choice(nus[k], size=nctl, replace=False)])
+        else:
+            assert 1 <= L <= nxs[k]
+            cols = rng.choice(nxs[k], size=L, replace=False)
+        cr.append(np.full(L, m)), cc.append(int(off[k]) + np.sort(cols)), cv.append(scale * rng.uniform(-1, 1, L))
+        m += 1
+    C = _csr(np.concatenate(cr), np.concatenate(cc), np.concatenate(cv), m)
+    out = Program(prog.n, prog.me, m, prog.Q, prog.A, C, c=prog.c, b=prog.b, d=np.concatenate([prog.d, np.ones(m - prog.m)]))
     out.nx, out.nu = nxs, nus
     return out
 

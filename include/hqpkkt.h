@@ -355,6 +355,25 @@ int hqpkkt_set_packed_panels(hqpkkt_t *h, int on);
  * together with HQPKKT_DYN_SPARSE: on a dense-form handle it is accepted and ignored.  HQPKKT_E_INTERN: the handle's mode
  * is not STAGED; HQPKKT_E_RANGE: min_entries < -1. */
 int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries);
+/* Wide rows of the inequality block C.  H_k = Q_k + C_k'(Z/W)C_k is assembled from term lists in which a row of C with L
+ * stored entries holds L^2 terms (24 bytes each at the analysis, 12 on the device): right for bound rows, out of reach for
+ * an output constraint over every state, a sum over the states of a discretised PDE or a polytopic terminal set.  With
+ * min_entries = n > 0 a row of C with at least n stored entries is "wide" (rows of C stay inside one stage; the terminal
+ * stage K counts): the r_k wide rows of stage k leave the term lists and are kept as a dense block E_k - r_k rows of
+ * up8(n_k + m_k) doubles in the F arena (stage K: up8(n_K)), hqpkkt_stats.bytes_panels counts it - and every factorisation
+ * adds S'S with S = diag(sqrt(z / w)) E_k into the stage's work block as ONE fp64 MFMA product of depth r_k: one pass over
+ * the block, whatever r_k L^2 is.  The square root goes into both operands, so V_k stays bit-for-bit symmetric; it asks for
+ * z / w > 0, which an interior-point iterate gives.  Everything else of the rows - the right-hand sides, dz, dw, the
+ * residual, the interior-point loops - walks C as before.  A stage with wide rows runs its control-sized chain on the
+ * first stream and forms V_k by the separate update; every other stage runs exactly the launches it always has.
+ * 0 (default): none - the plan, arenas, launches and bits of a handle that never asked.  -1, the library's threshold: no
+ * threshold has been measured yet, HQPKKT_E_RANGE.  Host only; call it before hqpkkt_analyze or
+ * hqpkkt_analyze_staged; it holds until it is set again.  It works with every form of the dynamics.  On a handle with
+ * hqpkkt_set_shard / hqpkkt_set_shard_stream it is accepted and ignored: such a handle keeps its term lists.
+ * Whatever the setting, an analysis whose term lists would hold more than 2^31 - 1 terms returns HQPKKT_E_SIZES (the lists
+ * are indexed by ints; one row of 46 341 entries is enough).  HQPKKT_E_NULL; HQPKKT_E_INTERN: the handle's mode is not
+ * STAGED; HQPKKT_E_RANGE: min_entries < -1.  hqpkkt_debug_get 43 reports the rows and the term counts. */
+int hqpkkt_set_dense_rows(hqpkkt_t *h, int min_entries);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense
@@ -593,7 +612,10 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * the (lo, hi) k-slab pairs of the 128-column panels of every stage's F_k; empty unless HQPKKT_DYN_PROFILE is set; valid
  * after hqpkkt_analyze, without a device; 42 the packed panels (hqpkkt_set_packed_panels): the same K + 1 pointers, then
  * per panel two ints, its offset in doubles from the stage's first panel and its leading dimension, (-1, 0) for the
- * panels of a stage that keeps its dense block; empty unless HQPKKT_DYN_PROFILE is set.
+ * panels of a stage that keeps its dense block; empty unless HQPKKT_DYN_PROFILE is set; 43 the wide rows of C
+ * (hqpkkt_set_dense_rows): K + 2 pointers, then the wide rows of every stage 0 .. K as row indices of C, ascending, then per
+ * stage two 64-bit counts as (low, high) int pairs - the H terms the plan kept and the terms the stage's wide rows would
+ * have added; empty unless the analysis had a threshold > 0; valid after the analysis, without a device.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

@@ -51,6 +51,7 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
   _wz_tol = HUGE_VAL;
   _a_sparse = 0;
   _a_heavy = 0;
+  _c_heavy = 0;
   _a_profile = 0;
   _a_packed = 0;
   _told_ignored = false;
@@ -59,6 +60,7 @@ Hqp_IpMatrixHip::Hqp_IpMatrixHip(int mode)
     _ifList.append(new If_Real("mat_wz_tol", &_wz_tol));
     _ifList.append(new If_Int("mat_a_sparse", &_a_sparse));
     _ifList.append(new If_Int("mat_a_heavy", &_a_heavy));
+    _ifList.append(new If_Int("mat_c_heavy", &_c_heavy));
     _ifList.append(new If_Int("mat_a_profile", &_a_profile));
     _ifList.append(new If_Int("mat_a_packed", &_a_packed));
     _ifList.append(new If_Int("mat_logging", &_logging));
@@ -321,6 +323,8 @@ int Hqp_IpMatrixHip::open_dense(const Hqp_Program *qp)
   if ((e = create_handle(HQPKKT_MODE_STAGED)))
     return e;
   _sbw = -1;
+  if ((e = hqpkkt_set_dense_rows(_h, _c_heavy)))
+    return e;
   if ((e = hqpkkt_analyze_staged(_h, K, _nx->ive, _nu->ive, _n, _me - ndyn, _m, _Qp->ive, _Qi->ive,
                                  _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive)))
     return e;
@@ -379,6 +383,8 @@ int Hqp_IpMatrixHip::open(int mode, int dyn_form)
   _dense = false;
   if (dyn_form != HQPKKT_DYN_DENSE && ((e = hqpkkt_set_dynamics_form(_h, dyn_form)) || (e = hqpkkt_set_dense_columns(_h, _a_heavy)) ||
                                        (e = hqpkkt_set_packed_panels(_h, _a_packed != 0))))
+    return e;
+  if (mode == HQPKKT_MODE_STAGED && (e = hqpkkt_set_dense_rows(_h, _c_heavy)))
     return e;
   if ((e = hqpkkt_analyze(_h, _n, _me, _m,
                           _Qp->ive, _Qi->ive, _Ap->ive, _Ai->ive, _Cp->ive, _Ci->ive,

@@ -45,9 +45,11 @@ class Hqp_IpMatrixHip : public Hqp_IpMatrix {
   // library's threshold).  mat_a_profile (no counterpart in the reference) != 0 takes the CSR hand-over with the profile
   // form (HQPKKT_DYN_PROFILE: dense blocks, the large products and the solve over the k-slabs that hold each panel's
   // entries - banded dynamics) on one GPU; mat_a_sparse goes first where both are set.  mat_a_packed != 0 with it: the
-  // stages of the profile sequence store F_k as packed panels (hqpkkt_set_packed_panels)
+  // stages of the profile sequence store F_k as packed panels (hqpkkt_set_packed_panels).  mat_c_heavy (no counterpart in
+  // the reference) goes to hqpkkt_set_dense_rows with either hand-over: rows of C with at least that many entries leave the
+  // H term lists and take the MFMA product (0 none)
   Real _wz_tol;
-  int _a_sparse, _a_heavy, _a_profile, _a_packed, _logging;
+  int _a_sparse, _a_heavy, _c_heavy, _a_profile, _a_packed, _logging;
   bool _told_ignored;
   struct hqpkkt *_h;
   // STAGED engine with the dynamics handed over as dense blocks (hqpkkt_analyze_staged): stage sizes, the number of

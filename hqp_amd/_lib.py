@@ -33,7 +33,7 @@ SYMBOLS = [
     "hqpkkt_debug_factor_block", "hqpkkt_debug_solve_top_stamps", "hqpkkt_set_dynamics_form", "hqpkkt_set_dense_columns",
     "hqpkkt_debug_sk_profile", "hqpkkt_debug_gemv_profile",
     "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
-    "hqpkkt_set_dense_rows",
+    "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -90,6 +90,14 @@ class DgemmCase(C.Structure):
                 ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong), ("c_row0", C.c_longlong), ("c_col0", C.c_longlong),
                 ("form", C.c_int), ("tile_map", C.c_int), ("ldsdma", C.c_int), ("nsplit", C.c_int), ("tiles", C.c_longlong),
                 ("krange", C.c_void_p), ("krange_by", C.c_int)]
+
+
+class CtrlRowsCase(C.Structure):
+    """hqpkkt_ctrl_rows_case (include/hqpkkt.h)"""
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("mu", C.c_int), ("grid", C.c_int), ("A", DgemmOperand), ("B", DgemmOperand),
+                ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong),
+                ("Cu", C.c_void_p), ("cu_rows", C.c_longlong), ("ldcu", C.c_longlong),
+                ("taken", C.c_int), ("fallbacks", C.c_int), ("form", C.c_int), ("tiles", C.c_longlong)]
 
 
 class IpResult(C.Structure):
@@ -166,6 +174,8 @@ def lib():
     L.hqpkkt_debug_dgemm_full.argtypes = [C.c_int, C.POINTER(DgemmCase)]
     L.hqpkkt_debug_sk_table.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hqpkkt_debug_dgemm_ctrl_rows.argtypes = [C.c_int, C.POINTER(CtrlRowsCase)]
+    L.hqpkkt_debug_sk_ctrl_rows.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_sk_profile.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_gemv_profile.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, C.c_longlong, vp, vp, vp, C.c_double, vp]
     L.hqpkkt_debug_dgemm_packed.argtypes = [C.c_int, C.POINTER(DgemmCase), vp, C.c_longlong, vp]

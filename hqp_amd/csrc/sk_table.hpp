@@ -296,4 +296,79 @@ static inline int gemm_choose_list(bool frac, bool unequal, long long tiles, lon
   if (unequal && gemm_split_table(tiles, nslab, grid, t) && t.pieces * slot <= ws_elems && tiles <= sk_tiles) return SK_LIST_UNEQUAL;
   return gemm_equal_table(tiles, nslab, grid, t) && t.pieces * slot <= ws_elems ? SK_LIST_EQUAL : SK_LIST_NONE;
 }
+
+// The control-row segment of a product whose last tile row is ragged (k_dgemm_tn_sk<.., AUG>, GemmArgs::Au): the tiles
+// of the last tile ROW (r = M - 128 tm_last valid rows of 128) also multiply the columns [c0, c0 + mu) of C itself - which
+// the tiles of the last tile COLUMN of the same launch write - from the free rows of their A panel.  So the launch has
+// one more unit of work than tiles, the corner tile twice (early in plain form, late in augmented form), and an order:
+//   - the tiles of the last tile column stand at the START of their workgroups' lists (every unit of such a tile has
+//     only units of such tiles in front of it),
+//   - the augmented tiles at the END of theirs (behind every unit of such a tile come only units of such tiles).
+// With fewer of them than workgroups - the headline's W: 40 and 40 on 512 - that is the first and the last unit.
+// Nothing else about a list changes: it is built as always for tiles + 1 logical tiles, and only which tile of C a
+// logical tile is (GemmArgs::tile_map, bit 31: augmented) is decided here - the logical tiles that end earliest are the
+// last tile column, those that start latest the augmented row, all others keep the launch's order (groups of eight tile
+// rows, column by column).  Returns false where the list has no such order (a tile count that puts a cut piece of a
+// late tile in front of a whole one); the caller then forms the control rows by a product of their own.
+static const int SK_TILE_AUG = (int)0x80000000;
+static inline bool gemm_ctrl_rows_order(const SplitTable &t, int grid, int tiles_m, int tiles_n, std::vector<int> &map) {
+  const long long T = (long long)tiles_m * tiles_n + 1;
+  if (tiles_m < 1 || tiles_n < 1 || tiles_m >= 32768 || tiles_n >= 65536 || grid < 1 || t.stride < 1 || (long long)t.units.size() != (long long)grid * t.stride) return false;
+  std::vector<int> len(grid, 0), head(T, 0), tail(T, 0), seen(T, 0);
+  for (int b = 0; b < grid; b++)
+    while (len[b] < t.stride && t.units[(size_t)b * t.stride + len[b]].tile >= 0) len[b]++;
+  for (int b = 0; b < grid; b++)
+    for (int i = 0; i < len[b]; i++) {
+      const int id = t.units[(size_t)b * t.stride + i].tile;
+      if (id >= T) return false;
+      seen[id] = 1, head[id] = std::max(head[id], i), tail[id] = std::max(tail[id], len[b] - 1 - i);
+    }
+  std::vector<int> ids(T), role(T, 0);  // role 1: last tile column, 2: augmented
+  for (long long i = 0; i < T; i++) {
+    if (!seen[i]) return false;
+    ids[i] = (int)i;
+  }
+  std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return head[a] < head[b]; });
+  for (int i = 0; i < tiles_m; i++) role[ids[i]] = 1;
+  for (long long i = 0; i < T; i++) ids[i] = (int)(T - 1 - i);
+  std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return tail[a] < tail[b]; });
+  for (int i = 0; i < tiles_n; i++) {
+    if (role[ids[i]]) return false;
+    role[ids[i]] = 2;
+  }
+  for (int b = 0; b < grid; b++) {
+    int first_other = len[b], last_other = -1;
+    for (int i = 0; i < len[b]; i++)
+      if (role[t.units[(size_t)b * t.stride + i].tile] != 1) {
+        first_other = i;
+        break;
+      }
+    for (int i = len[b] - 1; i >= 0; i--)
+      if (role[t.units[(size_t)b * t.stride + i].tile] != 2) {
+        last_other = i;
+        break;
+      }
+    for (int i = 0; i < len[b]; i++) {
+      const int ro = role[t.units[(size_t)b * t.stride + i].tile];
+      if ((ro == 1 && i > first_other) || (ro == 2 && i < last_other)) return false;
+    }
+  }
+  map.assign(T, 0);
+  const int GM = 8;
+  long long next = 0;  // the launch's own order of the tiles outside the last row and column
+  auto next_inner = [&]() {
+    for (;; next++) {
+      const long long grp = next / ((long long)GM * tiles_n), first = grp * GM, rows = std::min<long long>(GM, tiles_m - first), in = next - grp * GM * tiles_n;
+      const int tm = (int)(first + in % rows), tn = (int)(in / rows);
+      if (tm != tiles_m - 1 && tn != tiles_n - 1) {
+        next++;
+        return tm << 16 | tn;
+      }
+    }
+  };
+  int col = 0, row = 0;
+  for (long long i = 0; i < T; i++)
+    map[i] = role[i] == 1 ? (col++) << 16 | (tiles_n - 1) : role[i] == 2 ? (SK_TILE_AUG | (tiles_m - 1) << 16 | (row++)) : next_inner();
+  return true;
+}
 }  // namespace stg

@@ -146,6 +146,16 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
           for (long long c : {P.h_kept[k], P.h_cut[k]}) out.push_back((int)(unsigned)(c & 0xffffffffLL)), out.push_back((int)(c >> 32));
       }
       break;
+    case 44:  // the control-row segment: [0] W launches whose augmented tiles found the control columns unfinished (the guarded
+              // thin product formed the control rows of G) since the upload, then per stage 1 where the W launch takes the segment
+      out.assign(P.K + 2, 0);
+      if (h->sd->ctl.p) {
+        unsigned w[3] = {0, 0, 0};
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(w, h->sd->ctl.p, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return HQPKKT_E_DEVICE;
+        out[0] = (int)(w[1] + (w[2] ? 1 : 0));
+      }
+      for (size_t k = 0; k < h->sd->ctrl_rows.size() && k + 1 < out.size(); k++) out[k + 1] = h->sd->ctrl_rows[k];
+      break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
       for (const StagedDev::SkTab &t : h->sd->sk_tabs)
@@ -557,6 +567,52 @@ struct DebugGemm {
   void launch(const stg::GemmArgs &g) {
     if (use_sk) (void)hipMemsetAsync(cnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
     stg::gemm_launch_form(f, L, 0, g, [](auto &&kernel) { kernel(); });
+    if (thin.M > 0) {  // the control rows as the engine's fused stage forms them: guarded behind a launch with the segment
+      stg::k_dgemm_tn_ks<64, 64><<<dim3((unsigned)stg::gemm_tiles(thin.M, thin.N, 64, 0), thin_split), 256, stg::gemm_lds_bytes(64, 64), 0>>>(thin, thin_ws.p, thin_split);
+      stg::k_dgemm_ks_finish<<<(unsigned)(((long long)thin.M * thin.N + 255) / 256), 256, 0, 0>>>(thin, thin_ws.p, thin_split);
+      if (thin.guard) stg::k_ctrl_rows_end<<<1, 64, 0, 0>>>(ctl.p);
+    }
+  }
+  // The control-row segment (GemmArgs::Au / mu / Cu set by the caller; prepare() has run): the launch takes it where the
+  // engine would - a cut form, gemm_ctrl_rows_ok, a list in the segment's order on `grid` workgroups (0: the device's) - and
+  // the product Cu = Au'B cut in k runs behind it, guarded; otherwise that product alone forms Cu.  Returns whether the
+  // segment is taken (< 0: an error)
+  DBuf<int> cmap;
+  DBuf<unsigned> ctl;
+  DBuf<double> thin_ws;
+  stg::GemmArgs thin{};
+  int thin_split = 1;
+  int prepare_ctrl_rows(stg::GemmArgs &g, int grid) {
+    if (ctl.alloc(8)) return HQPKKT_E_MEM;
+    (void)hipMemset(ctl.p, 0, sizeof(unsigned) * 8);
+    g.ctl = ctl.p;
+    thin = stg::GemmArgs{g.Au, g.ldau, g.B, g.ldb, nullptr, 0, g.Cu, g.ldcu, g.mu, g.N, g.K, g.alpha, 0.0, 0, 0};
+    thin_split = (int)std::max<long long>(1, std::min<long long>(8, stg::gemm_slabs(g.K) / 4));
+    if (thin_ws.alloc((size_t)thin_split * g.mu * g.N)) return HQPKKT_E_MEM;
+    const int wgs = grid > 0 ? grid : skg;
+    bool taken = use_sk && f.kind != stg::GEMM_FORM_PROFILE && wgs > 0 && stg::gemm_ctrl_rows_ok(g, L.variant);
+    if (taken) {
+      const int tiles_m = (g.M + 127) / 128;
+      const long long nslab = stg::gemm_slabs_of(g);
+      std::vector<int> map;
+      const int l = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, stg::gemm_sk_table_from_env(), f.tiles + 1, nslab, wgs, f.tiles + 1, 1LL << 40, tab);
+      taken = l != stg::SK_LIST_NONE && stg::gemm_ctrl_rows_order(tab, wgs, tiles_m, (int)(f.tiles / tiles_m), map);
+      if (taken) {
+        list = l;
+        if (units.upload(tab.units) || cmap.upload(map) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 5)) return HQPKKT_E_MEM;
+        (void)hipMemset(cnt.p, 0, sizeof(unsigned) * (f.tiles + 5));
+        sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
+        L.sk = &sk, L.grid = wgs;
+        g.tile_map = cmap.p, thin.guard = ctl.p + 2;
+      }
+    }
+    if (!taken) g.Au = nullptr, g.Cu = nullptr, g.mu = 0, g.ctl = nullptr;
+    return taken ? 1 : 0;
+  }
+  int fallbacks() {
+    unsigned w[3] = {0, 0, 0};
+    if (hipMemcpy(w, ctl.p, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int)(w[1] + (w[2] ? 1 : 0));
   }
 };
 // K2 > 0: C = A'B - A2'B2 by a launch with a second k segment (operands A2, -B2); asym: entries of a mirrored result
@@ -589,6 +645,17 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
   DebugGemm run;
   if (int e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP | (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0))) return e;
+  // (HQPKKT_DGEMM_CTRL_ROWS=mu, M == K: the launch with the control-row segment for the last mu columns of C and the
+  // guarded product behind it, as a fused stage runs W - same-box comparisons with the plain launch)
+  DBuf<double> Cu;
+  const int mu = getenv("HQPKKT_DGEMM_CTRL_ROWS") ? atoi(getenv("HQPKKT_DGEMM_CTRL_ROWS")) : 0;
+  if (mu > 0 && mu <= N && M == K && K2 == 0 && !lower) {
+    if (Cu.alloc((size_t)mu * ldc)) return HQPKKT_E_MEM;
+    g.Au = Cm.p + (N - mu), g.ldau = ldc, g.mu = mu, g.Cu = Cu.p, g.ldcu = ldc;
+    const int taken = run.prepare_ctrl_rows(g, 0);
+    if (taken < 0) return taken;
+    fprintf(stderr, "control-row segment: %s\n", taken ? "taken" : "not taken (the thin product alone)");
+  }
   EventOwner e0, e1;
   (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
@@ -597,6 +664,7 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   }
   (void)hipEventRecord(e1, 0);
   hipError_t se = hipDeviceSynchronize();
+  if (mu > 0 && run.ctl.p) fprintf(stderr, "control-row segment: %d of %d launches fell back\n", run.fallbacks(), reps + 1);
   run.ws.release(), run.cnt.release();
   float t = 0.f;
   (void)hipEventElapsedTime(&t, e0, e1);
@@ -703,6 +771,66 @@ int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c) {
 }
 int hqpkkt_debug_dgemm_packed(int device, hqpkkt_dgemm_case *c, const double *packed, long long packed_elems, const long long *panel) {
   return guarded([&]() -> int { return packed ? debug_dgemm_full(device, c, packed, packed_elems, panel) : HQPKKT_E_NULL; });
+}
+
+// One launch with the control-row segment on the caller's operands (include/hqpkkt.h)
+static int debug_dgemm_ctrl_rows(int device, hqpkkt_ctrl_rows_case *c) {
+  if (!c || !c->C || !c->Cu || !c->A.p || !c->B.p) return HQPKKT_E_NULL;
+  const int M = c->M, N = c->N, K = c->M, mu = c->mu;
+  if (M <= 0 || N <= 0 || mu < 0 || mu > N || c->grid < 0) return HQPKKT_E_RANGE;
+  auto operand_ok = [](const hqpkkt_dgemm_operand &o, int k, int w) { return o.ld >= 1 && o.col0 >= 0 && o.col0 + w <= o.ld && o.rows >= (long long)k + 1; };
+  if (!operand_ok(c->A, K, M) || !operand_ok(c->B, K, N) || c->ldc < N + 1 || c->c_rows < M + 1 || c->ldcu < N || c->cu_rows < mu) return HQPKKT_E_RANGE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  DBuf<double> dA, dB, dC, dCu;
+  auto up = [](DBuf<double> &d, const double *p, long long elems) -> int {
+    if (d.alloc((size_t)elems)) return HQPKKT_E_MEM;
+    HIPCHK(hipMemcpy(d.p, p, sizeof(double) * (size_t)elems, hipMemcpyHostToDevice));
+    return 0;
+  };
+  int e;
+  if ((e = up(dA, c->A.p, c->A.rows * c->A.ld)) || (e = up(dB, c->B.p, c->B.rows * c->B.ld)) || (e = up(dC, c->C, c->c_rows * c->ldc)) ||
+      (e = up(dCu, c->Cu, std::max<long long>(1, c->cu_rows * c->ldcu))))
+    return e;
+  stg::GemmArgs g{dA.p + c->A.col0, c->A.ld, dB.p + c->B.col0, c->B.ld, nullptr, 0, dC.p, c->ldc, M, N, K, 1.0, 0.0, 0, 0};
+  DebugGemm run;
+  if ((e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_FORCE_SPLIT))) return e;
+  c->taken = 0, c->fallbacks = 0;
+  if (mu > 0) {
+    g.Au = g.C + (N - mu), g.ldau = c->ldc, g.mu = mu, g.Cu = dCu.p, g.ldcu = c->ldcu;
+    if ((e = run.prepare_ctrl_rows(g, c->grid)) < 0) return e;
+    c->taken = e;
+  }
+  run.launch(g);
+  HIPCHK(hipDeviceSynchronize());
+  if (mu > 0 && (c->fallbacks = run.fallbacks()) < 0) return HQPKKT_E_DEVICE;
+  HIPCHK(hipMemcpy(c->C, dC.p, sizeof(double) * (size_t)(c->c_rows * c->ldc), hipMemcpyDeviceToHost));
+  if (c->cu_rows > 0) HIPCHK(hipMemcpy(c->Cu, dCu.p, sizeof(double) * (size_t)(c->cu_rows * c->ldcu), hipMemcpyDeviceToHost));
+  c->form = run.f.kind, c->tiles = run.f.tiles;
+  return 0;
+}
+int hqpkkt_debug_dgemm_ctrl_rows(int device, hqpkkt_ctrl_rows_case *c) {
+  return guarded([&]() -> int { return debug_dgemm_ctrl_rows(device, c); });
+}
+int hqpkkt_debug_sk_ctrl_rows(int tiles_m, int tiles_n, int nslab, int grid, int kind, int *units, long long cap_ints, int *tile_map, long long *pieces) {
+  stg::SplitTable t;
+  std::vector<int> map;
+  const long long tiles = (long long)tiles_m * tiles_n + 1;
+  if (tiles_m < 1 || tiles_n < 1) return 0;
+  if (kind < 0 ? stg::gemm_choose_list(false, true, tiles, nslab, grid, tiles, 1LL << 40, t) == stg::SK_LIST_NONE : !stg::gemm_list_table(kind, tiles, nslab, grid, t)) return 0;
+  if (!stg::gemm_ctrl_rows_order(t, grid, tiles_m, tiles_n, map)) return 0;
+  if (pieces) *pieces = t.pieces;
+  if (units) {
+    if ((long long)t.units.size() * 6 > cap_ints) return 0;
+    for (size_t i = 0; i < t.units.size(); i++) {
+      const stg::SkUnit &u = t.units[i];
+      int *o = units + 6 * i;
+      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
+    }
+  }
+  if (tile_map) std::copy(map.begin(), map.end(), tile_map);
+  return t.stride;
 }
 
 int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,

@@ -90,7 +90,22 @@ struct GemmArgs {
   // packed panels of A / of B (k_dgemm_tn_sk<.., PACKED = true>, a GEMM_FORM_PROFILE launch alone): the tile at tile row
   // tm / tile column tn takes entry tm / tn; null: the operand is one block
   const PackPanel *apack, *bpack;
+  // The control-row segment (k_dgemm_tn_sk<.., AUG = true>, a launch by a list ordered by gemm_ctrl_rows_order alone;
+  // gemm_ctrl_rows_ok): Cu = Au'B, mu rows of N columns, out of the free rows of the ragged last tile row's A panels -
+  // rows [0, r) of such a panel are A's, rows [r, r + mu) the columns of Au (k-major, K rows; here the columns of C that
+  // the last tile column of this launch writes), the rest zero.  ctl: [0] finished tiles of the last tile column,
+  // [1] launches whose segment was not ready (the guarded product behind the launch formed Cu), [2] this launch's was
+  // not.  guard: a product cut in k (k_dgemm_tn_ks and its finish) returns at once while *guard is 0
+  const double *Au;
+  long long ldau;
+  int mu;
+  double *Cu;
+  long long ldcu;
+  unsigned *ctl;
+  const unsigned *guard;
 };
+// the valid rows of the last tile row
+static __host__ __device__ __forceinline__ int gemm_last_rows(int M) { return M - (M - 1) / 128 * 128; }
 // k-slabs of a launch (both segments)
 static __host__ __device__ __forceinline__ int gemm_slabs_of(const GemmArgs &g) {
   return (g.K + GEMM_BK - 1) / GEMM_BK + (g.K2 > 0 ? (g.K2 + GEMM_BK - 1) / GEMM_BK : 0);
@@ -454,6 +469,62 @@ struct GemmTile {
       slabs_dma<true>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
   }
 
+  // A tile of the ragged last tile row with the control-row segment (GemmArgs::Au): the same loops, with the row of
+  // the A panel chosen per LANE - the lanes of the panel columns < r read A as always, those of the columns
+  // [r, r + mu) row k of Au (`ready`: the tiles that write it have finished; otherwise the zero row), the others the
+  // zero row.  mu odd: the lane of columns r + mu - 1, r + mu brings one value from beyond Au's columns into panel row
+  // r + mu, whose products nobody writes.  Always the masked loop: the blocks of the rows [0, r + mu)
+  static __device__ __forceinline__ void accumulate_dma_aug(const GemmArgs &g, int i0, int j0, int s0, int s1, bool ready,
+                                                            double4_t (&acc)[TM][TN], double *As, double *Bs, int nbuf) {
+    static_assert(BM == 128 && BN == 128, "one k-row of a panel must be one 1-KiB wave-instruction");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int r = g.M - i0, rows = ready ? r + g.mu : r;
+    unsigned mask = 0;
+#pragma unroll
+    for (int x = 0; x < TM; x++)
+#pragma unroll
+      for (int y = 0; y < TN; y++) {
+        const int rb = wm * TM + x, cb = wn * TN + y;
+        mask |= ((16 * rb < rows && j0 + 16 * cb < g.N) ? 1u : 0u) << (x * TN + y);
+      }
+    mask = __builtin_amdgcn_readfirstlane(mask);
+    const double *zr = g.zeros + 2 * lane;
+    const int c = 2 * lane;
+    const bool mine = c < r, theirs = !mine && c < rows;
+    const double *pa = mine ? g.A + ((i0 + c < g.lda) ? i0 + c : 0) : theirs ? g.Au + (c - r) : zr;
+    const double *pb = g.B + ((j0 + c < g.ldb) ? j0 + c : 0);
+    const int k0 = (g.K + BK - 1) / BK * BK;
+    const Rows ra{g.K, k0, k0, mine ? g.lda : theirs ? g.ldau : 0, 0, 0}, rb{g.K, k0, k0, g.ldb, 0, 0};
+    if (nbuf == 3)
+      slabs_dma3<true>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+    else
+      slabs_dma<true>(ra, rb, pa, pb, zr, wave, wm, wn, lr, lk, s0, s1, mask, acc, As, Bs);
+  }
+  // ... and its epilogue: rows [0, r) of the tile to C (`plain`), rows [r, r + mu) to Cu (`ctrl`), nothing else (alpha
+  // alone: a launch with the segment has beta = 0)
+  static __device__ __forceinline__ void epilogue_aug(const GemmArgs &g, int tm, int tn, const double4_t (&acc)[TM][TN], bool plain, bool ctrl) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int i0 = tm * BM, j0 = tn * BN, r = g.M - i0;
+#pragma unroll
+    for (int x = 0; x < TM; x++)
+#pragma unroll
+      for (int y = 0; y < TN; y++)
+#pragma unroll
+        for (int rg = 0; rg < 4; rg++) {
+          const int ii = wm * WM + 16 * x + lk + 4 * rg, j = j0 + wn * WN + 16 * y + lr;
+          if (j >= g.N) continue;
+          const double v = g.alpha * acc[x][y][rg];
+          if (ii < r) {
+            if (plain) g.C[(long long)(i0 + ii) * g.ldc + j] = v;
+          } else if (ii < r + g.mu && ctrl)
+            g.Cu[(long long)(ii - r) * g.ldcu + j] = v;
+        }
+  }
+
   // `lds`: the workgroup's LDS (free after accumulate's last barrier), used to write the MIRROR image of an
   // off-diagonal tile in whole rows: the values of 64 tile columns at a time go to LDS transposed ([column][row],
   // leading dimension BM + 2: conflict-free), and every wave then writes rows of the mirrored block in 1-KiB (BM = 128)
@@ -572,6 +643,7 @@ template <int BM, int BN>
 __global__ void __launch_bounds__(256) k_dgemm_tn_ks(GemmArgs g, double *__restrict__ part, int nsplit) {
   using T = GemmTile<BM, BN, 2, 2>;
   extern __shared__ __attribute__((aligned(16))) double lds[];
+  if (g.guard && *g.guard == 0) return;  // (uniform: a guarded product whose result exists already)
   double *As = lds, *Bs = lds + 2 * T::BK * T::LDA;
   int tm, tn;
   T::tile_of(g, blockIdx.x, tm, tn);
@@ -597,7 +669,7 @@ __global__ void __launch_bounds__(256) k_dgemm_tn_ks(GemmArgs g, double *__restr
 }
 __global__ void k_dgemm_ks_finish(GemmArgs g, const double *__restrict__ part, int nsplit) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x, tot = (long long)g.M * g.N;
-  if (e >= tot) return;
+  if (e >= tot || (g.guard && *g.guard == 0)) return;
   double s = 0.0;
   for (int y = 0; y < nsplit; y++) s += part[(long long)y * tot + e];
   const int i = (int)(e / g.N), j = (int)(e % g.N);
@@ -624,7 +696,15 @@ struct SplitPlan {
 };
 // PACKED: the ranged operand of a profile launch comes from packed panels (GemmArgs::apack / bpack) - instances of
 // their own: the others take every operand as one block
-template <bool DMA, int WGM = 2, int WGN = 2, int NBUF = 2, int BM = 128, int BN = 128, bool PACKED = false>
+// AUG: the launch carries the control-row segment (GemmArgs::Au; the list and tile order of gemm_ctrl_rows_order) -
+// instances of their own, so that every other launch runs the code it always has.  A tile of the last tile column adds
+// one to ctl[0] behind its epilogue, with the release the parked sums use.  An augmented tile reads ctl[0] ONCE, with the
+// matching acquire, before its first operand load: all tiles of the last tile column done - the columns of Au are
+// complete and visible, the tile takes them into its A panel and writes their rows of Cu; otherwise it computes its
+// plain rows alone and raises ctl[2], and the guarded product behind the launch forms Cu.  Nobody waits.  The pieces of
+// a cut augmented tile each decide for themselves and say so in the high half of what they add to the tile's arrival
+// counter: the last arriver writes Cu only if every piece was ready.
+template <bool DMA, int WGM = 2, int WGN = 2, int NBUF = 2, int BM = 128, int BN = 128, bool PACKED = false, bool AUG = false>
 __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WGM * WGN / 2) k_dgemm_tn_sk(GemmArgs g, SplitPlan sk) {
   using T = GemmTile<BM, BN, WGM, WGN>;
   extern __shared__ __attribute__((aligned(16))) double lds[];  // tiles + one word for the arrival order
@@ -637,15 +717,33 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
   auto unit = [&](const SkUnit u, int r) {
     const int t = u.tile, s0 = u.s0, s1 = u.s1, pieces = u.pieces, j = u.j;
     int tm, tn;
-    T::tile_of(g, t, tm, tn);
+    bool aug = false, ready = false;
+    if constexpr (AUG) {
+      const int e = g.tile_map[t];
+      aug = e < 0, tm = (e >> 16) & 0x7fff, tn = e & 0xffff;
+      if (aug) {  // (uniform)
+        if (threadIdx.x == 0) {
+          const unsigned done = __hip_atomic_load(g.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          *s_old = done;
+        }
+        __syncthreads();
+        ready = *s_old == (unsigned)((g.M + BM - 1) / BM);
+        __syncthreads();
+      }
+    } else
+      T::tile_of(g, t, tm, tn);
     double4_t acc[T::TM][T::TN];
 #pragma unroll
     for (int x = 0; x < T::TM; x++)
 #pragma unroll
       for (int y = 0; y < T::TN; y++) acc[x][y] = (double4_t){0.0, 0.0, 0.0, 0.0};
-    if constexpr (DMA)
-      T::template accumulate_dma<PACKED>(g, tm * BM, tn * BN, s0, s1, acc, As, Bs, g.lower && tm == tn, NBUF);
-    else
+    if constexpr (DMA) {
+      if (AUG && aug)
+        T::accumulate_dma_aug(g, tm * BM, tn * BN, s0, s1, ready, acc, As, Bs, NBUF);
+      else
+        T::template accumulate_dma<PACKED>(g, tm * BM, tn * BN, s0, s1, acc, As, Bs, g.lower && tm == tn, NBUF);
+    } else
       T::template accumulate<PACKED>(g, tm * BM, tn * BN, s0, s1, acc, As, Bs);
     bool finish = true;
     if (stamp && threadIdx.x == 0 && r < 10) stamp[1 + 3 * r] = __builtin_amdgcn_s_memrealtime();
@@ -662,10 +760,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
       if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        *s_old = __hip_atomic_fetch_add(sk.cnt + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_old = __hip_atomic_fetch_add(sk.cnt + t, (AUG && aug && !ready) ? 0x10001u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       __syncthreads();
-      finish = *s_old == (unsigned)(pieces - 1);
+      finish = (AUG ? (*s_old & 0xffffu) : *s_old) == (unsigned)(pieces - 1);
+      if (AUG && (*s_old >> 16)) ready = false;
       if (finish) {
         if (threadIdx.x == 0) {
           sk.cnt[t] = 0;  // (every piece of the tile has arrived: the counter is ready for the next launch)
@@ -690,7 +789,21 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
       __syncthreads();  // s_old is rewritten at the next shared tile
     }
     if (stamp && threadIdx.x == 0 && r < 10) stamp[2 + 3 * r] = __builtin_amdgcn_s_memrealtime();
-    if (finish) T::epilogue(g, tm, tn, acc, lds);  // (uniform: the whole workgroup)
+    if (AUG && aug) {
+      // (the corner tile's plain rows were written by its plain form, early in the launch)
+      if (finish) T::epilogue_aug(g, tm, tn, acc, tn != (g.N + BN - 1) / BN - 1, ready);
+      if (finish && !ready && threadIdx.x == 0) g.ctl[2] = 1u;
+    } else if (finish)
+      T::epilogue(g, tm, tn, acc, lds);  // (uniform: the whole workgroup)
+    if (AUG && finish && !aug && tn == (g.N + BN - 1) / BN - 1) {  // a tile of the last tile column is in memory
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_fetch_add(g.ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
     if (stamp && threadIdx.x == 0 && r < 10) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       stamp[3 + 3 * r] = __builtin_amdgcn_s_memrealtime();
@@ -737,6 +850,13 @@ static inline void gemm_launch_split(int variant, int grid, hipStream_t s, const
       k_dgemm_tn_sk<false, 2, 2, 2, 128, 128, true><<<grid, 256, gemm_sk_lds_bytes(), s>>>(g, sk);
     return;
   }
+  if (g.Au) {  // (the control-row segment: the 2 x 4 LDS-DMA kernels alone, gemm_ctrl_rows_ok)
+    if (variant == GEMM_DMA8X3)
+      k_dgemm_tn_sk<true, 2, 4, 3, 128, 128, false, true><<<grid, 512, gemm_sk_lds_bytes(3), s>>>(g, sk);
+    else
+      k_dgemm_tn_sk<true, 2, 4, 2, 128, 128, false, true><<<grid, 512, gemm_sk_lds_bytes(), s>>>(g, sk);
+    return;
+  }
   if (variant == GEMM_DMA8X3)
     k_dgemm_tn_sk<true, 2, 4, 3><<<grid, 512, gemm_sk_lds_bytes(3), s>>>(g, sk);
   else if (variant == GEMM_DMA8)
@@ -769,6 +889,8 @@ static inline hipError_t gemm_set_attributes() {
   set((const void *)k_dgemm_tn_sk<true, 2, 2, 2, 128, 128, true>, gemm_sk_lds_bytes());
   set((const void *)k_dgemm_tn_sk<true, 2, 4, 2, 128, 128, true>, gemm_sk_lds_bytes());
   set((const void *)k_dgemm_tn_sk<true, 2, 4, 3, 128, 128, true>, gemm_sk_lds_bytes(3));
+  set((const void *)k_dgemm_tn_sk<true, 2, 4, 2, 128, 128, false, true>, gemm_sk_lds_bytes());
+  set((const void *)k_dgemm_tn_sk<true, 2, 4, 3, 128, 128, false, true>, gemm_sk_lds_bytes(3));
   return e;
 }
 // (HQPKKT_SK_TABLE=0: the cut form with equal shares, gemm_equal_table, for same-box comparisons)
@@ -795,6 +917,25 @@ static inline bool gemm_operands_dma_ok(const GemmArgs &g) {
 // The 128 x 128 kernel of a launch: the handle's variant, and the register-staged one for operands without a zero row -
 // the LDS-DMA kernels read GemmArgs::zeros for every row k >= K and behind the last slab
 static inline int gemm_variant_for(const GemmArgs &g, int variant) { return g.zeros ? variant : GEMM_REG4; }
+// The control-row segment of g (GemmArgs::Au) can be taken by a launch of the cut forms: a ragged last tile row with an
+// even number r of rows and room for the mu rows, no other special of a launch, and Au = the columns [c0, c0 + mu) of C
+// inside the last tile column (so the tiles whose completion the augmented tiles ask for are the ones that write it);
+// every 16-byte load of a row of Au lies inside a row of C
+static inline bool gemm_ctrl_rows_ok(const GemmArgs &g, int variant) {
+  if (!g.Au || !g.Cu || !g.ctl || g.mu <= 0 || g.M <= 0 || !g.zeros || (variant != GEMM_DMA8 && variant != GEMM_DMA8X3)) return false;
+  const int r = gemm_last_rows(g.M);
+  const long long c0 = g.Au - g.C;
+  return !(r & 1) && r + g.mu <= 128 && (((uintptr_t)g.Au) & 15) == 0 && !(g.ldau & 1) && g.ldau == g.ldc && c0 >= (g.N - 1) / 128 * 128LL &&
+         c0 + g.mu <= g.N && c0 + g.mu + (g.mu & 1) <= g.ldc && !g.lower && !g.mirror && g.K2 == 0 && g.beta == 0.0 && !g.bstrips && !g.rects && !g.apack &&
+         !g.bpack && !g.tile_map && !g.stamps;
+}
+// the end of a stage's use of the segment: the launch's fall-back counted, its words ready for the next launch
+__global__ void k_ctrl_rows_end(unsigned *ctl) {
+  if (threadIdx.x == 0) {
+    if (ctl[2]) ctl[1]++;
+    ctl[0] = 0, ctl[2] = 0;
+  }
+}
 // Order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map): super-blocks of 8 x 8 tiles,
 // row by row; inside a block column by column
 static inline std::vector<int> gemm_tri_order(int T) {

@@ -93,7 +93,9 @@ struct StagedDev {
     long long tiles, nslab;
     int form, list, stride, hits;
     DBuf<stg::SkUnit> units;
+    DBuf<int> map;  // the lists of launches with the control-row segment (form + SK_TAB_CTRL): their tile order
   };
+  static const int SK_TAB_CTRL = 100;
   std::vector<SkTab> sk_tabs;
   bool sk_tables_on = true;  // HQPKKT_SK_TABLE
   SkTab *sk_tab(long long tiles, long long nslab, int form) {
@@ -110,7 +112,7 @@ struct StagedDev {
   int sk_tab_prepare(const stg::GemmForm &f, long long nslab) {
     if (sk_tab(f.tiles, nslab, f.kind)) return 0;
     stg::SplitTable t;
-    SkTab e{f.tiles, nslab, f.kind, 0, 0, 0, {}};
+    SkTab e{f.tiles, nslab, f.kind, 0, 0, 0, {}, {}};
     e.list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles, nslab, sk_grid, sk_tiles, sk_ws_elems, t);
     if (e.list != stg::SK_LIST_NONE) {
       if (int err = e.units.upload(t.units)) return err;
@@ -119,6 +121,26 @@ struct StagedDev {
     sk_tabs.push_back(std::move(e));
     return 0;
   }
+  // ... and of a launch of form f with the control-row segment (stg::gemm_ctrl_rows_order): tiles + 1 logical tiles
+  // in the list the chooser gives that count, and the tile order that puts the last tile column first and the augmented
+  // row last.  list SK_LIST_NONE: no such list - the caller forms the control rows by a product of their own
+  int ctrl_tab_prepare(const stg::GemmForm &f, long long nslab, int tiles_m) {
+    if (sk_tab(f.tiles, nslab, f.kind + SK_TAB_CTRL)) return 0;
+    stg::SplitTable t;
+    std::vector<int> map;
+    SkTab e{f.tiles, nslab, f.kind + SK_TAB_CTRL, stg::SK_LIST_NONE, 0, 0, {}, {}};
+    const int list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles + 1, nslab, sk_grid, sk_tiles + 1, sk_ws_elems, t);
+    if (list != stg::SK_LIST_NONE && f.tiles + 1 <= sk_cnt_elems && stg::gemm_ctrl_rows_order(t, sk_grid, tiles_m, (int)(f.tiles / tiles_m), map)) {
+      if (int err = e.units.upload(t.units)) return err;
+      if (int err = e.map.upload(map)) return err;
+      e.list = list, e.stride = t.stride;
+    }
+    sk_tabs.push_back(std::move(e));
+    return 0;
+  }
+  // words of the control-row segment (GemmArgs::ctl), and per stage whether its W launch takes the segment
+  DBuf<unsigned> ctl;
+  std::vector<char> ctrl_rows;
   // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device, the partial sums of the solve's
   // columns product (stg::pf_chunks x columns of the widest stage), and the work lists of its two large products
   // (stg::gemm_profile_table) by shape and range vector: equal vectors share a list - a time-invariant pattern has one
@@ -162,11 +184,6 @@ namespace {
 bool env_no_symv() { static const bool v = getenv("HQPKKT_NO_SYMV") != nullptr; return v; }  // the rows form of the solve's products with V
 int env_symv_from() { static const int v = getenv("HQPKKT_SYMV_FROM") ? atoi(getenv("HQPKKT_SYMV_FROM")) : 2048; return v; }
 double env_block_gj_tol() { static const double v = getenv("HQPKKT_BLOCK_GJ_TOL") ? atof(getenv("HQPKKT_BLOCK_GJ_TOL")) : 1e-6; return v; }
-// Narrowest stage that forms V_k in the G_xx launch unasked: none.  At 5000 states the sequence takes exactly as long as
-// the one with the separate update (the thin product for the control rows of G, 77 us, and the extra slabs cost what the
-// update, 109 us, saves: profiles/r08_stage_order.txt), and up to 4096 states the chain beside G_xx
-// (StagedDev::overlap_mode) has its measured gain.  HQPKKT_FUSED_V=1 runs it wherever it can
-const int FUSED_V_MIN_STATES = 1 << 30;
 bool env_spd_test_fail() { static const bool v = getenv("HQPKKT_SPD_TEST_FAIL") != nullptr; return v; }  // tests: k_st_small<1024, false> refuses
 // launches go to h->stream: back to the first stream on every way out
 struct StreamGuard {
@@ -224,6 +241,19 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
   return s;
 }
 
+// W = V+ F of stage k as a launch; seg: with the control-row segment - the control rows of G = W_u'F out of the free rows
+// of W's ragged last tile row (GemmArgs::Au: W's control columns, which the last tile column of the same launch writes)
+inline stg::GemmArgs staged_w_args(StagedDev &d, int k, bool seg) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1];
+  const long long ldf = P.ldf[k], ldg = P.ldg[k];
+  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
+  stg::GemmArgs g{sn.V, P.ldv[k + 1], sp.F, ldf, nullptr, 0, W, ldf, np, nn + mm, np, 1.0, 0.0, 0, 0};
+  if (seg) g.Au = W + nn, g.ldau = ldf, g.mu = mm, g.Cu = G + nn * ldg, g.ldcu = ldg, g.ctl = d.ctl.p;
+  return g;
+}
+
 // C = alpha A'B + beta Cin on the handle's stream, in the form the launch rule gives the shape (gemm_form.hpp)
 // (allow_sk false: launches of the second stream).  ntiles > 0: the tiles g.tile_map[0 .. ntiles) of the product only
 // (128 x 128 tiles; the blocks of G_xx one rank owns)
@@ -241,8 +271,13 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
   if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
   // (the second segment exists in the 128 x 128 LDS-DMA kernels alone: StagedDev::fused holds only stages that get them)
   if (g.K2 > 0 && !(g.zeros && (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT || f.kind == stg::GEMM_FORM_PLAIN))) return HQPKKT_E_INTERN;
+  // (the control-row segment: only where the upload found the launch a list, StagedDev::ctrl_rows)
+  const bool seg = g.Au != nullptr;
+  if (seg && !((f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT) && stg::gemm_ctrl_rows_ok(g, stg::gemm_variant_for(g, d.gemm_variant))))
+    return HQPKKT_E_INTERN;
   if (h->listing) {  // upload's dry walk: what this launch will look up is made, nothing is launched
     if (f.tile_map && !d.tri_map((g.M + 127) / 128, true)) return HQPKKT_E_MEM;
+    if (seg) return d.ctrl_tab_prepare(f, nslab, (g.M + 127) / 128);
     return f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT ? d.sk_tab_prepare(f, nslab) : 0;
   }
   // (the arrival counters of the cut forms are zero between launches: the last arriver of a tile resets its)
@@ -251,9 +286,10 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
   if (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT) {
     // the list the shape was given at upload.  A shape without one is no reason to take another schedule; a list of
     // SK_LIST_NONE - the workspace holds no list's pieces - is a plain round
-    StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind);
-    if (!tab) return HQPKKT_E_INTERN;
+    StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind + (seg ? StagedDev::SK_TAB_CTRL : 0));
+    if (!tab || (seg && tab->list == stg::SK_LIST_NONE)) return HQPKKT_E_INTERN;
     tab->hits++;
+    if (seg) g.tile_map = tab->map.p;
     if (tab->list != stg::SK_LIST_NONE) sk.table = tab->units.p, sk.stride = tab->stride, L.sk = &sk;
   }
   stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
@@ -759,9 +795,16 @@ static int staged_upload(hqpkkt_t *h) {
     }
   }
   // Which stages form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can
-  // (the tests), unset: those of at least FUSED_V_MIN_STATES states.  A stage can when its K has order 1 .. 64 (k_st_rm
+  // (the tests), unset: those whose W launch also delivers the control rows of G (StagedDev::ctrl_rows: the control-row
+  // segment, staged_w_args) and whose width is not one of those that run the chain beside G_xx (overlap_mode) - with
+  // the thin product for the control rows the sequence only takes as long as the one with the separate update
+  // (profiles/r08_stage_order.txt).  A stage can when its K has order 1 .. 64 (k_st_rm
   // writes -Rm), its control columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA
   {
+    d.ctl.release();
+    if ((e = d.ctl.alloc(8))) return e;
+    HIPCHK(hipMemset(d.ctl.p, 0, sizeof(unsigned) * 8));
+    d.ctrl_rows.assign(P.K + 1, 0);
     const char *fv = getenv("HQPKKT_FUSED_V");
     const int mode = fv ? atoi(fv) : 2;
     d.fused.assign(P.K + 1, 0);
@@ -771,10 +814,27 @@ static int staged_upload(hqpkkt_t *h) {
         const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
         if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
         if (P.wide_count(k)) continue;                  // (the wide rows' product goes into the work block G)
-        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0 || (mode != 1 && nn < FUSED_V_MIN_STATES)) continue;
+        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0) continue;
         const long long nslab = stg::gemm_slabs(np) + stg::gemm_slabs(q);
         const stg::GemmForm f = d.gemm_form(nn, nn, (int)(nslab * stg::GEMM_BK), 1, 1);
         if (f.kind != stg::GEMM_FORM_FRAC && f.kind != stg::GEMM_FORM_CUT && f.kind != stg::GEMM_FORM_PLAIN) continue;
+        // the control rows of G out of the W launch: a cut form with a list in the segment's order, and the guarded
+        // product behind it one cut in k (the kernels that know the guard)
+        {
+          stg::GemmArgs gw = staged_w_args(d, k, true);
+          gw.zeros = stg::gemm_operands_dma_ok(gw) ? d.zeros.p : nullptr;
+          const stg::GemmForm fw = d.gemm_form(gw.M, gw.N, gw.K, 0, 0), ft = d.gemm_form(P.mk[k], nn + P.mk[k], np, 0, 0);
+          if ((fw.kind == stg::GEMM_FORM_FRAC || fw.kind == stg::GEMM_FORM_CUT) && ft.kind == stg::GEMM_FORM_KS &&
+              stg::gemm_ctrl_rows_ok(gw, stg::gemm_variant_for(gw, d.gemm_variant))) {
+            if ((e = d.ctrl_tab_prepare(fw, stg::gemm_slabs(gw.K), (gw.M + 127) / 128))) return e;
+            const StagedDev::SkTab *tab = d.sk_tab(fw.tiles, stg::gemm_slabs(gw.K), fw.kind + StagedDev::SK_TAB_CTRL);
+            d.ctrl_rows[k] = tab && tab->list != stg::SK_LIST_NONE;
+          }
+        }
+        if (mode != 1 && (!d.ctrl_rows[k] || (nn >= 1280 && nn <= 4096))) {
+          d.ctrl_rows[k] = 0;
+          continue;
+        }
         d.fused[k] = 1;
         nrm = std::max(nrm, (long long)q * P.ldy[k]);
       }
@@ -1135,7 +1195,9 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
 // That needs Y and Rm BEFORE the large product, and the control-sized chain that makes them needs only the control rows
 // of G: G_u = W_u'F, a thin product (k_dgemm_tn_ks) with W's control columns.  All on the first stream: with the chain
 // on a second stream beside W (W_u = V+ f_u as a thin product of its own) the stage was slower in every placement that
-// was measured - profiles/r08_stage_order.txt.
+// was measured - profiles/r08_stage_order.txt.  Where the W launch takes the control-row segment (StagedDev::ctrl_rows) it
+// delivers G_u itself, and the thin product behind it is guarded: it runs only if an augmented tile of that launch found
+// W's control columns unfinished (GemmArgs::ctl, counted: hqpkkt_debug_get 44), and returns at once otherwise.
 static int staged_stage_fused(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
@@ -1146,9 +1208,12 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
   int e;
   // W = V+ F; the control rows of G = W_u'F with H's control part; the carried rows N_k[e..] = B+ F
-  if ((e = st_gemm(h, stg::GemmArgs{sn.V, P.ldv[k + 1], sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}))) return e;
-  if (mm > 0 && (e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD)))
-    return e;
+  const bool seg = d.ctrl_rows[k];
+  if ((e = st_gemm(h, staged_w_args(d, k, seg)))) return e;
+  stg::GemmArgs gu{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0};
+  if (seg) gu.guard = d.ctl.p + 2;
+  if (mm > 0 && (e = st_gemm(h, gu, KC_ST_GEMM_UPD))) return e;
+  if (seg && !h->listing) KLAUNCH(h, KC_ST_SMALL, stg::k_ctrl_rows_end<<<1, 64, 0, h->stream>>>(d.ctl.p));
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
   // V = F_x'W_x - Y'Rm (lower tiles, mirrored), then H_xx into the entry and its image

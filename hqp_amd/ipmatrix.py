@@ -501,6 +501,12 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         """Per stage whether V_k comes out of the G_xx launch (HQPKKT_FUSED_V)."""
         return self.debug(35)
 
+    def ctrl_rows(self):
+        """(W launches that fell back to the thin product since the upload, per stage whether the W launch takes the
+        control-row segment)."""
+        d = self.debug(44)
+        return int(d[0]), d[1:]
+
     def stage_ranks(self):
         """(rank, carried rows) per stage of the last factorisation (tests)."""
         K1 = len(self.debug(20))
@@ -636,6 +642,41 @@ def sk_table(tiles, nslab, grid=512, kind="unequal"):
     got = _lib.lib().hqpkkt_debug_sk_table(tiles, nslab, grid, k, u.ctypes.data_as(C.POINTER(C.c_int)), u.size, C.byref(pieces), C.byref(wa), C.byref(wb))
     assert got == stride
     return u, pieces.value, wa.value, wb.value
+
+
+def sk_ctrl_rows(tiles_m, tiles_n, nslab, grid=512, kind=None):
+    """The work list and tile order of a launch with the control-row segment (host only): (units[grid, stride, 6],
+    tile_map[tiles_m tiles_n + 1], pieces) or None.  kind None: the list the engine's chooser gives; tile_map: logical tile
+    -> tile row << 16 | tile column, negative: the augmented form."""
+    import numpy as np
+    k = -1 if kind is None else SK_KINDS.index(kind)
+    pieces = C.c_longlong()
+    stride = _lib.lib().hqpkkt_debug_sk_ctrl_rows(tiles_m, tiles_n, nslab, grid, k, None, 0, None, C.byref(pieces))
+    if stride <= 0:
+        return None
+    u = np.zeros((grid, stride, 6), dtype=np.int32)
+    m = np.zeros(tiles_m * tiles_n + 1, dtype=np.int32)
+    got = _lib.lib().hqpkkt_debug_sk_ctrl_rows(tiles_m, tiles_n, nslab, grid, k, u.ctypes.data_as(C.POINTER(C.c_int)), u.size,
+                                               m.ctypes.data_as(C.POINTER(C.c_int)), C.byref(pieces))
+    assert got == stride
+    return u, m, pieces.value
+
+
+def dgemm_ctrl_rows(M, N, mu, A, B, C_buf, Cu_buf, grid=0, a_col0=0, b_col0=0, device=0):
+    """One launch of C (M x N) = A'B (K = M) with the control-row segment for its last mu columns, and the guarded thin
+    product behind it (hqpkkt_debug_dgemm_ctrl_rows): C_buf's block at (0, 0) and Cu_buf's first mu rows = C[:, N - mu:]'B.
+    Both buffers are overwritten with the whole device buffers.  Returns (segment taken, fallbacks, form, tiles)."""
+    import numpy as np
+    for x in (A, B, C_buf, Cu_buf):
+        assert x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous
+    c = _lib.CtrlRowsCase()
+    c.M, c.N, c.mu, c.grid = M, N, mu, grid
+    c.A = _lib.DgemmOperand(A.ctypes.data, A.shape[0], A.shape[1], a_col0)
+    c.B = _lib.DgemmOperand(B.ctypes.data, B.shape[0], B.shape[1], b_col0)
+    c.C, c.c_rows, c.ldc = C_buf.ctypes.data, C_buf.shape[0], C_buf.shape[1]
+    c.Cu, c.cu_rows, c.ldcu = Cu_buf.ctypes.data, Cu_buf.shape[0], Cu_buf.shape[1]
+    _check(_lib.lib().hqpkkt_debug_dgemm_ctrl_rows(device, C.byref(c)), "debug_dgemm_ctrl_rows")
+    return bool(c.taken), c.fallbacks, GEMM_FORMS[c.form], c.tiles
 
 
 def sk_profile(ranges, grid=512):

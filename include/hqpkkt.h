@@ -461,6 +461,34 @@ typedef struct hqpkkt_dgemm_case {
 } hqpkkt_dgemm_case;
 int hqpkkt_debug_dgemm_full(int device, hqpkkt_dgemm_case *c);
 
+/* Test hook: ONE launch of the product C (M x N) = A'B, K = M, with the control-row segment for the last mu columns of
+ * C - Cu (mu x N) = C[:, N - mu : N]'B out of the free rows of the ragged last tile row - followed, as in the engine's
+ * fused stage, by the guarded thin product for Cu and the end of the segment's use.  The launch is the cut form on 128 x
+ * 128 tiles whatever the rule says, by the chooser's list for tiles + 1 units on `grid` workgroups (0: two per CU) in the
+ * segment's order.  taken: 1 where the launch took the segment (M mod 128 even and > 0, M mod 128 + mu <= 128, the
+ * operands staged by LDS-DMA, a list with that order); 0: the thin product alone formed Cu.  fallbacks: launches whose
+ * augmented tiles found C's last columns unfinished (the guarded product ran).  A, B as in hqpkkt_dgemm_case; C: c_rows
+ * (> M) x ldc (> N), the block at row 0, column 0; Cu: cu_rows (>= mu) x ldcu (>= N); both whole buffers go to the device
+ * and come back.  mu = 0: no segment, no thin product. */
+typedef struct hqpkkt_ctrl_rows_case {
+  int M, N, mu, grid;
+  hqpkkt_dgemm_operand A, B;
+  double *C;
+  long long c_rows, ldc;
+  double *Cu;
+  long long cu_rows, ldcu;
+  int taken, fallbacks, form; /* out */
+  long long tiles;            /* out */
+} hqpkkt_ctrl_rows_case;
+int hqpkkt_debug_dgemm_ctrl_rows(int device, hqpkkt_ctrl_rows_case *c);
+
+/* Test hook, host only: the work list and tile order of a launch with the control-row segment (gemm_ctrl_rows_order,
+ * sk_table.hpp) for tiles_m x tiles_n tiles of nslab k-slabs on `grid` workgroups: a list for tiles_m tiles_n + 1 logical
+ * tiles (kind as hqpkkt_debug_sk_table; -1: the list the engine's chooser gives), units as there, and tile_map (or NULL;
+ * tiles_m tiles_n + 1 ints): logical tile -> tile row << 16 | tile column, bit 31: the augmented form.  Returns the
+ * stride, or 0: no list, or none with that order. */
+int hqpkkt_debug_sk_ctrl_rows(int tiles_m, int tiles_n, int nslab, int grid, int kind, int *units, long long cap_ints, int *tile_map, long long *pieces);
+
 /* Test hook, host only (no device needed): a work list of the cut forms of that product (k_dgemm_tn_sk walks one list
  * per workgroup, whatever the schedule) for `tiles` tiles of `nslab` k-slabs on `grid` workgroups, sk_table.hpp.
  * kind 0: unequal shares for the two workgroups of a CU; 1: equal shares, whole rounds and cut phases; 2: the fractional
@@ -615,7 +643,10 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * panels of a stage that keeps its dense block; empty unless HQPKKT_DYN_PROFILE is set; 43 the wide rows of C
  * (hqpkkt_set_dense_rows): K + 2 pointers, then the wide rows of every stage 0 .. K as row indices of C, ascending, then per
  * stage two 64-bit counts as (low, high) int pairs - the H terms the plan kept and the terms the stage's wide rows would
- * have added; empty unless the analysis had a threshold > 0; valid after the analysis, without a device.
+ * have added; empty unless the analysis had a threshold > 0; valid after the analysis, without a device; 44 the
+ * control-row segment of the fused stages: [0] W launches since the upload whose augmented tiles found W's control
+ * columns unfinished, so that the guarded thin product formed the control rows of G, then per stage 1 where the W launch
+ * takes the segment (decided at the upload).
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

@@ -17,6 +17,7 @@ OK, E_SIZES, E_MEM, E_SING, E_FORMAT, E_NULL, E_RANGE, E_INTERN, E_DEVICE = 0, 1
 MODE_FULL, MODE_REDUCED, MODE_STAGED = 0, 1, 2
 LOC_HOST, LOC_DEVICE = 0, 1
 DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
+HESS_CSR, HESS_DENSE = 0, 1
 
 # every symbol include/hqpkkt.h declares
 SYMBOLS = [
@@ -34,6 +35,7 @@ SYMBOLS = [
     "hqpkkt_debug_sk_profile", "hqpkkt_debug_gemv_profile",
     "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
     "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
+    "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -163,6 +165,10 @@ def lib():
     L.hqpkkt_set_dense_columns.argtypes = [vp, C.c_int]
     L.hqpkkt_set_packed_panels.argtypes = [vp, C.c_int]
     L.hqpkkt_set_dense_rows.argtypes = [vp, C.c_int]
+    L.hqpkkt_set_hessian_form.argtypes = [vp, C.c_int]
+    L.hqpkkt_set_stage_hessian.argtypes = [vp, C.c_int, vp, C.c_longlong]
+    L.hqpkkt_debug_stage_hessian.argtypes = [vp, C.c_int, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.hqpkkt_debug_hess_symv.argtypes = [vp, vp, vp]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

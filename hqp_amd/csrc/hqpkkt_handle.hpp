@@ -512,7 +512,8 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
                       const long long *ldF = nullptr, bool dense = false);  // (Fblk / dense: the dense hand-over of the dynamics)
 int staged_factor(hqpkkt_t *h, const Vecs &v);
 int staged_step(hqpkkt_t *h, const Vecs &v, int which);
-int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn);
+// (xq: Q dx with dense stage Hessians, hqpkkt_set_hessian_form; left alone otherwise)
+int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn, const double **xq);
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out);
 // hqpkkt.hip
 int solve_vecs(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3,

@@ -142,13 +142,13 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
     h->opts.loc = HQPKKT_LOC_DEVICE;
     h->lazy = true;  // no host round trip where the loop does not need the answer at once
     // STAGED with dense dynamics: their share of A x and A'y for the right-hand sides (k_ip_rhs)
-    const double *dx1 = nullptr, *dx2 = nullptr;
+    const double *dx1 = nullptr, *dx2 = nullptr, *dxq = nullptr;  // (dxq: Q x with dense stage Hessians)
     int dndyn = 0;
     auto dyn_products = [&]() -> int {
       if (h->opts.mode != HQPKKT_MODE_STAGED) return 0;
       Vecs vv{};
       vv.dx = C.x, vv.dy = C.y;
-      return staged_dense_products(h, vv, &dx1, &dx2, &dndyn);
+      return staged_dense_products(h, vv, &dx1, &dx2, &dndyn, &dxq);
     };
     hipEvent_t t0 = h->ev0;  // total time: own pair of events (the plugin calls reuse the handle's)
     const hipEvent_t tb = h->evt0, te = h->evt1;  // owned by the handle: no early return can leak them
@@ -274,11 +274,11 @@ int hqpkkt_mehrotra(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, co
       if (h->short_rows)
         k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
                                               h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
-                                              C.part, dx1, dx2, dndyn);
+                                              C.part, dx1, dx2, dndyn, dxq);
       else
         k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
                                                h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, C.r1, C.r2, C.r3, C.r4,
-                                               C.part, dx1, dx2, dndyn);
+                                               C.part, dx1, dx2, dndyn, dxq);
       if (m == 0) return 0;
       // the reductions of this iterate and what the step before left behind, one round trip
       const int ops2[IP_SLOTS] = {IP_SUM, IP_SUM, IP_SUM, IP_MAX, IP_MIN, IP_MIN, IP_SUM, IP_SUM};
@@ -613,13 +613,13 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
     h->opts.loc = HQPKKT_LOC_DEVICE;
     h->lazy = true;
     // STAGED with dense dynamics: their share of A x and A'y for the right-hand sides (k_ip_rhs)
-    const double *dx1 = nullptr, *dx2 = nullptr;
+    const double *dx1 = nullptr, *dx2 = nullptr, *dxq = nullptr;  // (dxq: Q x with dense stage Hessians)
     int dndyn = 0;
     auto dyn_products = [&]() -> int {
       if (h->opts.mode != HQPKKT_MODE_STAGED) return 0;
       Vecs vv{};
       vv.dx = C.x, vv.dy = C.y;
-      return staged_dense_products(h, vv, &dx1, &dx2, &dndyn);
+      return staged_dense_products(h, vv, &dx1, &dx2, &dndyn, &dxq);
     };
     const hipEvent_t tb = h->evt0, te = h->evt1;  // owned by the handle: no early return can leak them
     HIPCHK(hipEventRecord(tb, s));
@@ -655,10 +655,10 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
       if ((e = dyn_products())) return e;
       if (h->short_rows)
         k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
-                                              h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
+                                              h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn, dxq);
       else
         k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
-                                               h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn);
+                                               h->td.vals.p, C.c, C.b, C.d, C.x, C.y, C.z, C.w, a1, a2, a3, C.r4, C.part, dx1, dx2, dndyn, dxq);
       if ((e = C.reduce(OPS_SUM, 3))) return e;
       gap = C.hout[2] + 1.0;  // in_prod(z, w) + 1 (:248)
       if (rhomin == 0.0) rhomin = h->fr_rhomin;

@@ -141,7 +141,9 @@ k_ip_rhs(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDev 
          double *__restrict__ part,
          // STAGED with dense dynamics: x1 = A_dyn' y (n), x2 = A_dyn x (the first ndyn rows of A, empty in
          // the CSR block), from k_st_dyn_both / k_st_dyn_ax_finish (staged_dense_products)
-         const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0) {
+         const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0,
+         // STAGED with dense stage Hessians: xq = Q x (n) from k_hs_symv, in place of the walk over Q's rows
+         const double *__restrict__ xq = nullptr) {
   __shared__ double red[4];
   const int sub = threadIdx.x & (LPR - 1);
   constexpr int RPB = 256 / LPR;
@@ -149,7 +151,7 @@ k_ip_rhs(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDev 
   double gap = 0.0, pc = 0.0, zw = 0.0, nr = 0.0, zmin = 1e300, wmin = 1e300;
   for (int q = blockIdx.x * RPB + threadIdx.x / LPR; q < total; q += gridDim.x * RPB) {
     if (q < n) {
-      const double qx = row_dot<LPR>(Q, vals, x, q, sub);
+      const double qx = xq ? xq[q] : row_dot<LPR>(Q, vals, x, q, sub);
       const double g = qx + c[q];
       const double s = g - row_dot<LPR>(AT, vals, y, q, sub) - row_dot<LPR>(CT, vals, z, q, sub) - (x1 ? x1[q] : 0.0);
       if (sub == 0) {

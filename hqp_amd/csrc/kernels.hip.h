@@ -2791,7 +2791,9 @@ k_residual(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDe
            // (resbits_next: the word the NEXT residual accumulates into, zeroed here - no memset between residuals)
            // STAGED with dense dynamics: x1 = A_dyn' dy (n), x2 = A_dyn dx (first ndyn rows of A,
            // which are empty in the CSR block), computed by the dense kernels of staged.hip.h
-           const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0) {
+           const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0,
+           // STAGED with dense stage Hessians: xq = Q dx (n) from k_hs_symv, in place of the walk over Q's rows
+           const double *__restrict__ xq = nullptr) {
   __shared__ double red[4];
   if (blockIdx.x == 0 && threadIdx.x == 0) *resbits_next = 0ULL;
   const int sub = threadIdx.x & (LPR - 1);
@@ -2800,7 +2802,7 @@ k_residual(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDe
   constexpr int RPB = 256 / LPR;  // rows per block and trip
   for (int q = blockIdx.x * RPB + threadIdx.x / LPR; q < total; q += gridDim.x * RPB) {
     if (q < n) {
-      double s = row_dot<LPR>(Q, vals, dx, q, sub);
+      double s = xq ? xq[q] : row_dot<LPR>(Q, vals, dx, q, sub);
       s += -1.0 * row_dot<LPR>(AT, vals, dy, q, sub);
       s += -1.0 * row_dot<LPR>(CT, vals, dz, q, sub);
       if (x1) s -= x1[q];

@@ -8,11 +8,23 @@
 #include "staged_sparse.hip.h"
 #include "staged_profile.hip.h"
 #include "staged_rows.hip.h"
+#include "staged_hess.hip.h"
 #include "staged_host.hip.h"
 
-int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn) {
+// y = Q x over the dense stage Hessians of all stages, one launch (k_hs_symv)
+static void staged_hess_symv(hqpkkt_t *h, StagedDev &d, const double *x, double *y) {
+  const kktdev::StagedPlan &P = d.plan;
+  int nzmax = 1;
+  for (int k = 0; k <= P.K; k++) nzmax = std::max(nzmax, P.hess_order(k));
+  KLAUNCH(h, KC_RESIDUAL, stg::k_hs_symv<<<dim3(std::min((nzmax + 3) / 4, 1024), P.K + 1), 256, 0, h->stream>>>(d.hess_desc.p, d.Qd.p, x, y));
+}
+int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn, const double **xq) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
+  if (P.hess_dense) {  // dense stage Hessians: Q dx in place of the walk over Q's rows
+    staged_hess_symv(h, d, v.dx, d.hess_y.p);
+    *xq = d.hess_y.p;
+  }
   if (!P.dense_dyn) return 0;
   int nzmax = 1, npmax = 1;
   for (int k = 0; k < P.K; k++) nzmax = std::max(nzmax, P.nk[k] + P.mk[k]), npmax = std::max(npmax, P.nk[k + 1]);
@@ -156,6 +168,13 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       }
       for (size_t k = 0; k < h->sd->ctrl_rows.size() && k + 1 < out.size(); k++) out[k + 1] = h->sd->ctrl_rows[k];
       break;
+    case 45:  // the dense stage Hessians (hqpkkt_set_hessian_form; host only): per stage 0 .. K the block's order, its leading
+              // dimension and the H terms left in the lists as (low, high) ints; empty unless the dense form is set
+      for (int k = 0; k <= P.K && P.hess_dense; k++) {
+        out.push_back(P.hess_order(k)), out.push_back(P.ldQ[k]);
+        out.push_back((int)(unsigned)(P.h_kept[k] & 0xffffffffLL)), out.push_back((int)(P.h_kept[k] >> 32));
+      }
+      break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
       for (const StagedDev::SkTab &t : h->sd->sk_tabs)
@@ -203,6 +222,17 @@ int hqpkkt_set_dense_rows(hqpkkt_t *h, int min_entries) {
   });
 }
 
+int hqpkkt_set_hessian_form(hqpkkt_t *h, int form) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (form != HQPKKT_HESS_CSR && form != HQPKKT_HESS_DENSE) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_hess_dense = form == HQPKKT_HESS_DENSE;  // (the next analysis picks it up)
+    return 0;
+  });
+}
+
 int hqpkkt_set_packed_panels(hqpkkt_t *h, int on) {
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
@@ -245,7 +275,8 @@ int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int 
     for (int k = 0; k < K; k++) n += (long long)nx[k] + nu[k], ndyn += nx[k + 1];
     if (n > 0x7fffffffLL || ndyn + me_rest > 0x7fffffffLL || me_rest < 0 || m < 0) return HQPKKT_E_RANGE;
     if (n != n_total) return HQPKKT_E_SIZES;  // Q, E, C were built for another number of variables
-    if ((n > 0 && (!Qp || (Qp[n] > 0 && !Qi))) || (me_rest > 0 && (!Ep || (Ep[me_rest] > 0 && !Ei))) ||
+    const bool hess_dense = h->sd && h->sd->plan.want_hess_dense;  // (the blocks come through hqpkkt_set_stage_hessian: Qp / Qi are not read)
+    if ((n > 0 && !hess_dense && (!Qp || (Qp[n] > 0 && !Qi))) || (me_rest > 0 && (!Ep || (Ep[me_rest] > 0 && !Ei))) ||
         (m > 0 && (!Cp || (Cp[m] > 0 && !Ci))))
       return HQPKKT_E_NULL;
     if (h->uploaded) {
@@ -256,7 +287,10 @@ int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int 
     h->analyzed = false;
     h->ip_hot_valid = h->fr_hot_valid = false;
     const int me = (int)ndyn + me_rest;
-    h->pQp.assign(Qp, Qp + n + 1), h->pQi.assign(Qi, Qi + Qp[n]);
+    if (hess_dense)
+      h->pQp.assign((size_t)n + 1, 0), h->pQi.clear();
+    else
+      h->pQp.assign(Qp, Qp + n + 1), h->pQi.assign(Qi, Qi + Qp[n]);
     h->pAp.assign((size_t)me + 1, 0);  // the dynamics rows are empty: they come as dense blocks
     for (int i = 0; i <= me_rest; i++) h->pAp[ndyn + i] = me_rest ? Ep[i] : 0;
     h->pAi.clear();
@@ -279,6 +313,10 @@ int hqpkkt_set_values_staged(hqpkkt_t *h, const double *Qx, const double *const 
     if (!F) {  // the blocks came one by one (hqpkkt_set_stage_block): every one of them, since the analysis
       const std::vector<char> &bs = h->sd->blocks_set;
       if ((int)bs.size() != h->sd->plan.K || std::find(bs.begin(), bs.end(), 0) != bs.end()) return HQPKKT_E_INTERN;
+    }
+    if (h->sd->plan.hess_dense) {  // ... and every Hessian block (hqpkkt_set_stage_hessian)
+      const std::vector<char> &qs = h->sd->hess_set;
+      if ((int)qs.size() != h->sd->plan.K + 1 || std::find(qs.begin(), qs.end(), 0) != qs.end()) return HQPKKT_E_INTERN;
     }
     return staged_set_values(h, Qx, Ex, Cx, F, ldF, true);
   });
@@ -311,6 +349,8 @@ int hqpkkt_stage_staging(hqpkkt_t *h, int which, double **buf, long long *elems)
     const kktdev::StagedPlan &P = d.plan;
     long long mx = 1;
     for (int k = 0; k < P.K; k++) mx = std::max(mx, (long long)P.nk[k + 1] * (P.nk[k] + P.mk[k]));
+    // (dense stage Hessians: a block Q_k comes through the same buffers, hqpkkt_set_stage_hessian)
+    for (int k = 0; k <= P.K && P.hess_dense; k++) mx = std::max(mx, (long long)P.hess_order(k) * P.hess_order(k));
     for (auto &b : d.hblk)
       if (b.count < (size_t)mx) HIPCHK(b.alloc((size_t)mx, hipHostMallocDefault));
     // the copy that last read this buffer must be over before the caller refills it
@@ -342,6 +382,73 @@ int hqpkkt_set_stage_block(hqpkkt_t *h, int k, const double *F, long long ldF) {
     if ((int)d.blocks_set.size() != P.K) d.blocks_set.assign(P.K, 0);
     d.blocks_set[k] = 1;
     h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_set_stage_hessian(hqpkkt_t *h, int k, const double *Q, long long ldQ) {
+  return guarded([&]() -> int {
+    if (!h || !Q) return HQPKKT_E_NULL;
+    if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd || !h->sd->plan.dense_dyn || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    int e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    if (k < 0 || k > P.K) return HQPKKT_E_RANGE;
+    const int nz = P.hess_order(k);
+    if (ldQ < nz) return HQPKKT_E_SIZES;
+    HIPCHK(hipSetDevice(h->opts.device));
+    const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (nz > 0) {  // the caller's nz columns of every row, then the strict lower triangle from the upper one
+      double *dst = d.Qd.p + P.oQ[k];
+      HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * P.ldQ[k], Q, sizeof(double) * ldQ, sizeof(double) * nz, nz, kind, h->stream));
+      const unsigned T = (unsigned)((nz + stg::HS_TILE - 1) / stg::HS_TILE);
+      stg::k_hs_mirror<<<T * (T + 1) / 2, 256, 0, h->stream>>>(dst, P.ldQ[k], nz, (int)T);
+    }
+    for (int b = 0; b < 2; b++)
+      if (Q == d.hblk[b].p) {  // the library's own staging buffer: remember when it is free again
+        if (!d.hblk_ev[b]) HIPCHK(hipEventCreateWithFlags(&d.hblk_ev[b].h, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(d.hblk_ev[b], h->stream));
+      }
+    if ((int)d.hess_set.size() != P.K + 1) d.hess_set.assign(P.K + 1, 0);
+    d.hess_set[k] = 1;
+    h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_debug_stage_hessian(hqpkkt_t *h, int k, double *out, long long cap, long long *len) {
+  return guarded([&]() -> int {
+    if (!h || !len) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    const kktdev::StagedPlan &P = h->sd->plan;
+    if (k < 0 || k > P.K) return HQPKKT_E_RANGE;
+    const long long elems = (long long)P.hess_order(k) * P.ldQ[k];
+    *len = elems;
+    if (!out) return 0;
+    if (cap < elems) return HQPKKT_E_SIZES;
+    HIPCHK(hipSetDevice(h->opts.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (elems) HIPCHK(hipMemcpy(out, h->sd->Qd.p + P.oQ[k], sizeof(double) * elems, hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+int hqpkkt_debug_hess_symv(hqpkkt_t *h, const double *x, double *y) {
+  return guarded([&]() -> int {
+    if (!h || !x || !y) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    const size_t n = (size_t)d.plan.n;
+    HIPCHK(hipSetDevice(h->opts.device));
+    int e;
+    if (!d.hess_x.p && (e = d.hess_x.alloc(n + 1))) return e;  // (the tests' operand: made here, outside every capture)
+    // hess_y is the buffer the residual's launches read: everything here goes to the handle's stream, behind whatever
+    // residual is still in it, and is over when this call returns
+    HIPCHK(hipMemcpyAsync(d.hess_x.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    staged_hess_symv(h, d, d.hess_x.p, d.hess_y.p);
+    HIPCHK(hipMemcpyAsync(y, d.hess_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
   });
 }

@@ -23,6 +23,13 @@ struct StagedDev {
   PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging)
   EventOwner hblk_ev[2];
   std::vector<char> blocks_set;         // dense hand-over block by block: which stages have arrived since the analysis
+  // dense stage Hessians (StagedPlan::hess_dense): the arena of the blocks Q_k, the scatter map of the CSR hand-over, per
+  // stage what k_hs_symv needs, y = Q x of the residual products (n) and the operand of hqpkkt_debug_hess_symv (n; made by
+  // its first call)
+  DBuf<double> Qd, hess_y, hess_x;
+  DBuf<long long> q_dst;
+  DBuf<stg::HessDesc> hess_desc;
+  std::vector<char> hess_set;           // dense hand-over: which blocks Q_k have arrived since the analysis
   // one system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
   // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack; the local dynamics blocks of
   // residuum()'s products and their summed results (A_dyn' dy: n, A_dyn dx: ndyn)
@@ -484,6 +491,15 @@ static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G,
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
                                                                                h->td.vals.p, h->td.wt.p, G, add));
 }
+// Q's share with dense stage Hessians (StagedPlan::hess_dense; the lists hold C'(Z/W)C alone and go behind it): the rows
+// [r0, r1) and the columns [0, c1) of Q_k added into the block G (k_hs_add; lower: the 128 x 128 tiles on and below the diagonal)
+static void st_add_q(hqpkkt_t *h, StagedDev &d, int k, int r0, int r1, int c1, int lower, double *G, long long ldg) {
+  const kktdev::StagedPlan &P = d.plan;
+  if (!P.hess_dense || r1 <= r0 || c1 <= 0) return;
+  const dim3 grid((unsigned)nblk((c1 + 1) / 2), (unsigned)std::min(r1 - r0, 1024));
+  KLAUNCH(h, KC_ASSEMBLE, stg::k_hs_add<<<grid, 256, 0, h->stream>>>(
+                              stg::HsAdd{d.Qd.p + P.oQ[k], P.ldQ[k], G, ldg, r0, r1, c1, lower}));
+}
 // ... and the share of the stage's wide rows of C (StagedPlan::wr_rows, r of them): G += S'S over the lower tiles with
 // S = diag(sqrt(z / w)) E_k (k_st_rows_scale), a product of depth r in place; stage K: into V_K with its mirror image.
 // Both operands are S, so entry (i, j) and its image are the same sum of the same products
@@ -611,15 +627,17 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
   const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
   const int want_heavy = P.want_heavy, want_rows = P.want_rows;
-  const bool want_packed = P.want_packed;
+  const bool want_packed = P.want_packed, want_hess_dense = P.want_hess_dense;
   P = kktdev::StagedPlan();
   P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed, P.want_rows = want_rows;
+  P.want_hess_dense = want_hess_dense;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
   P.sharded = h->shard_count > 1 || h->xchg_fn || h->xchg_sfn;
   if ((want_sparse || want_profile) && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over, the profile form reads its ranges off them
   if ((want_sparse || want_profile) && P.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
+  if (want_hess_dense && P.sharded) return HQPKKT_E_RANGE;                   // ... and keeps its term lists
   h->an.shard_rank = h->shard_rank, h->an.shard_count = 1;  // (the tree engine's exchange plan is not used)
   int e = h->an.setup_blocks(1, n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(),
                              h->pCp.data(), h->pCi.data());
@@ -638,7 +656,7 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   h->st.nnz_kkt = (long long)P.nq + P.na + P.nc;
   h->st.nnz_factor = P.v_elems + P.misc_elems;
   h->st.flops_factor = P.flops_factor;
-  h->st.bytes_panels = (long long)sizeof(double) * (P.f_elems + P.v_elems);
+  h->st.bytes_panels = (long long)sizeof(double) * (P.f_elems + P.v_elems + P.q_elems);
   h->st.bytes_updates = (long long)sizeof(double) * P.misc_elems;
   h->st.shard_rank = P.shard_rank, h->st.shard_count = P.shard_count;
   if (P.sharded) {
@@ -710,6 +728,14 @@ static int staged_upload(hqpkkt_t *h) {
     std::vector<stg::HTerm> t(P.h_terms.size());
     for (size_t k = 0; k < t.size(); k++) t[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
     if ((e = d.h_terms.upload(t))) return e;
+  }
+  if (P.hess_dense) {  // the blocks Q_k, cleared once: the scatter and the store write the entries alone
+    std::vector<stg::HessDesc> hd(P.K + 1);
+    for (int k = 0; k <= P.K; k++) hd[k] = stg::HessDesc{P.oQ[k], P.ldQ[k], P.hess_order(k), P.nmk[k], 0};
+    if ((e = d.Qd.alloc((size_t)P.q_elems + 16)) || (e = d.hess_desc.upload(hd)) || (e = d.hess_y.alloc((size_t)n + 1)) ||
+        (!P.q_dst.empty() && (e = d.q_dst.upload(P.q_dst))))
+      return e;
+    HIPCHK(hipMemset(d.Qd.p, 0, sizeof(double) * ((size_t)P.q_elems + 16)));
   }
   if (P.sparse_dyn && ((e = d.sp_arow.upload(P.sp_arow)) || (e = d.sp_tcol.upload(P.sp_tcol)))) return e;
   if (P.sparse_dyn && !P.hv_cols.empty()) {
@@ -1062,6 +1088,8 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
   HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
   if (an.na)
     stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
+  if (P.hess_dense && an.nq)  // Q's values into the blocks Q_k (CSR hand-over)
+    stg::k_hs_scatter<<<nblk(an.nq), 256, 0, s>>>(an.nq, d.q_dst.p, h->td.vals.p, d.Qd.p);
   if (!P.wr_rows.empty())  // the wide rows of C into their blocks E_k
     stg::k_st_scatter<<<nblk(an.nc), 256, 0, s>>>(an.nc, d.c_dst.p, h->td.vals.p + an.nq + an.na, d.F.p, d.misc.p);
   const int nchk = (int)P.chk_idx.size();
@@ -1214,12 +1242,14 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   if (seg) gu.guard = d.ctl.p + 2;
   if (mm > 0 && (e = st_gemm(h, gu, KC_ST_GEMM_UPD))) return e;
   if (seg && !h->listing) KLAUNCH(h, KC_ST_SMALL, stg::k_ctrl_rows_end<<<1, 64, 0, h->stream>>>(d.ctl.p));
+  st_add_q(h, d, k, nn, nz, nz, 0, G, ldg);
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
   // V = F_x'W_x - Y'Rm (lower tiles, mirrored), then H_xx into the entry and its image
   stg::GemmArgs g{sp.F, ldf, W, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, np, 1.0, 0.0, 1, 1};
   g.A2 = sp.Y, g.lda2 = ldy, g.B2 = nRm, g.ldb2 = ldy, g.K2 = q;
   if ((e = st_gemm(h, g))) return e;
+  st_add_q(h, d, k, 0, nn, nn, 0, sp.V, P.ldv[k]);  // (the whole of Q_xx, which is its own image bit for bit)
   if (ne_x)
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
                                                                                  h->td.vals.p, h->td.wt.p, sp.V, ldg, P.ldv[k]));
@@ -1251,14 +1281,17 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
   if (!ovl) {
     // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
+    st_add_q(h, d, k, 0, nz, nz, 1, G, ldg);
     st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
     if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
   } else {
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
+    st_add_q(h, d, k, 0, nn, nn, 1, G, ldg);
     st_add_h(h, d, P.h_ptr[k], ne_x, G);
     // ... the control rows of G (Gux, Guu) = W_u' F and H's control part on the second
     h->stream = sB;
     if ((e = st_gemm(h, stg::GemmArgs{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM, false))) return e;
+    st_add_q(h, d, k, nn, nz, nz, 0, G, ldg);
     st_add_h(h, d, P.h_mid[k], ne_u, G);
   }
   h->stream = sB;
@@ -1286,6 +1319,7 @@ static int staged_stage_profile(hqpkkt_t *h, int k) {
   if ((e = st_gemm_profile(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}, k, 1)) ||
       (e = st_gemm_profile(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}, k, 2)))
     return e;
+  st_add_q(h, d, k, 0, nz, nz, 1, G, ldg);
   st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
   if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
   if (P.pk_stage(k)) {
@@ -1354,6 +1388,7 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
     KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_heavy_place<<<dim3((unsigned)((std::max(nz, cx) + 255) / 256), nd), 256, 0, h->stream>>>(stg::SpHeavyPlace{
                                  nz, nd, cx, d.hv_cols.p + P.hv_ptr[k], d.hv_of.p + P.nmk[k], Gh, ldg, Ghh, ldd, G, ldg, Nh, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
   }
+  st_add_q(h, d, k, 0, nz, nz, 0, G, ldg);  // (k_sp_gather writes the block with its mirror image)
   st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
   if ((e = st_add_h_wide(h, d, k, G, ldg)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
   return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
@@ -1379,7 +1414,8 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
   {  // last stage: V_K = H_K, all its equality rows are carried
     StagePtr sp = stage_ptr(d, K);
     const int nK = P.nk[K], eK = P.eq_ptr[K + 1] - P.eq_ptr[K];
-    st_add_h(h, d, P.h_ptr[K], P.h_ptr[K + 1] - P.h_ptr[K], sp.V, 0);
+    st_add_q(h, d, K, 0, nK, nK, 0, sp.V, P.ldv[K]);  // (into the cleared block: V_K = Q_K with its image, then the lists add)
+    st_add_h(h, d, P.h_ptr[K], P.h_ptr[K + 1] - P.h_ptr[K], sp.V, P.hess_dense ? 1 : 0);
     if (!P.sharded && (e = st_add_h_wide(h, d, K, sp.V, P.ldv[K]))) return e;
     KLAUNCH(h, KC_ST_SMALL, stg::k_st_last<<<nblk(std::max(nK, 1)), 256, 0, s>>>(nK, eK, P.cap[K], sp.N, P.ldn[K], sp.BT, P.ldb[K], sp.dyn));
     if (P.sharded) st_keep_rows(h, d, K);

@@ -66,6 +66,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   profile_dyn = want_profile && !want_sparse;
   if (profile_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
   nq = n ? Qp[n] : 0, nc = m ? Cp[m] : 0;
+  hess_dense = want_hess_dense;
   const int arows = me_;  // rows of the A that was handed over
   na = arows ? Ap[arows] : 0;
   nk.clear(), mk.clear(), nmk.clear(), nks.clear();
@@ -381,6 +382,23 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     }
     oSr = mo, mo += up16(smax);
   }
+  // ------------------------------------------------------------------ dense stage Hessians
+  ldQ.clear(), oQ.clear(), q_dst.clear(), q_elems = 0;
+  if (hess_dense) {
+    ldQ.assign(K + 1, 8), oQ.assign(K + 1, 0);
+    for (int k = 0; k <= K; k++) {
+      ldQ[k] = up8(hess_order(k));
+      oQ[k] = q_elems, q_elems += (long long)hess_order(k) * ldQ[k];
+    }
+    q_dst.assign(2 * (size_t)nq, -1);
+    for (int i = 0; i < n; i++)
+      for (int p = Qp[i]; p < Qp[i + 1]; p++) {
+        const int j = Qi[p], k = stage_of[i];
+        if (j < i) continue;  // only col >= row is read
+        q_dst[2 * (size_t)p] = oQ[k] + (long long)lcol(i) * ldQ[k] + lcol(j);
+        if (j != i) q_dst[2 * (size_t)p + 1] = oQ[k] + (long long)lcol(j) * ldQ[k] + lcol(i);
+      }
+  }
   // ------------------------------------------------------------------ one system over several ranks (staged_plan.hpp)
   xcut.clear(), xw.clear(), ldfl.clear(), oFl.clear(), oVs.clear(), fgslot.clear(), ldwl.clear(), xslot.clear();
   xrects.clear(), xrect_ptr.clear(), gtile.clear(), gtile_ptr.clear();
@@ -529,7 +547,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   {
     std::vector<char> is_wide(m, 0);
     for (int r : wr_rows) is_wide[r] = 1;
-    for (int i = 0; i < n; i++)
+    for (int i = 0; i < n && !hess_dense; i++)  // (dense Hessians: Q's entries are in the blocks Q_k)
       for (int p = Qp[i]; p < Qp[i + 1]; p++)
         if (Qi[p] >= i) h_kept[stage_of[i]] += Qi[p] > i ? 2 : 1;
     long long kept = 0;
@@ -544,14 +562,14 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
       Term t;
     };
     std::vector<Raw> raw;
-    raw.reserve(wr_rows.empty() ? (size_t)nq * 2 + (size_t)nc * 2 : (size_t)kept);
+    raw.reserve(wr_rows.empty() && !hess_dense ? (size_t)nq * 2 + (size_t)nc * 2 : (size_t)kept);
     const int ONE = nq + na + nc, WONE = m;
     auto ldof = [&](int k) { return k < K ? ldg[k] : ldv[K]; };
     auto push = [&](int k, int li, int lj, Term t) {
       const long long ctl = (li >= nk[k] || lj >= nk[k]) ? 1 : 0;
       raw.push_back({((long long)k << 45) | (ctl << 44) | ((long long)li * ldof(k) + lj), t});
     };
-    for (int i = 0; i < n; i++)
+    for (int i = 0; i < n && !hess_dense; i++)
       for (int p = Qp[i]; p < Qp[i + 1]; p++) {
         const int j = Qi[p];
         if (j < i) continue;  // only col >= row is read (meschach/addon2_hqp.c:1078-1086)

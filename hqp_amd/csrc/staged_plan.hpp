@@ -101,6 +101,17 @@ struct StagedPlan {
   long long oSr = 0;
   int wide_count(int k) const { return wr_ptr.empty() ? 0 : wr_ptr[k + 1] - wr_ptr[k]; }
 
+  // Dense stage Hessians (hqpkkt_set_hessian_form): Q_k of stage k = 0..K, order n_k + m_k (stage K: n_K), kept in full -
+  // exactly symmetric - as rows of ldQ[k] = up8(order) doubles at oQ[k] in an arena of its own (q_elems doubles, blocks back
+  // to back: a row is 64 bytes or a multiple); Q's terms are not in the H lists.  q_dst: CSR hand-over - per stored entry p
+  // of Q its two places in the arena (2 p: row i, column j; 2 p + 1: the image, -1 on the diagonal; both -1 for an entry
+  // with col < row, which nobody reads).  want_hess_dense: what the next analysis takes
+  bool want_hess_dense = false, hess_dense = false;
+  std::vector<int> ldQ;
+  std::vector<long long> oQ, q_dst;
+  long long q_elems = 0;
+  int hess_order(int k) const { return k < K ? nk[k] + mk[k] : nk[k]; }
+
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;
   int q0max = 0, ldq0 = 8;  // free initial state: order of [V_0 B_0'; B_0 0]

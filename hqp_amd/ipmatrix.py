@@ -347,12 +347,16 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     ``set_packed_panels(True)`` with it: the stages that run the profile sequence store F_k as packed panels, the rows of
     every panel's range alone (hqpkkt_set_packed_panels).  ``dense_rows=n`` or ``set_dense_rows(n)``, with any form of
     the dynamics: the rows of C with at least n entries leave the H term lists and go through the MFMA product as a
-    dense block per stage (hqpkkt_set_dense_rows; 0: none)."""
+    dense block per stage (hqpkkt_set_dense_rows; 0: none).  ``q_dense=True`` or ``set_hessian_form("dense")``, with any
+    form of the dynamics: the stage Hessians Q_k are kept as dense blocks instead of entries of the H term lists
+    (hqpkkt_set_hessian_form); init() scatters the CSR values into them, init_dense() takes ``DenseDocp.Qd``."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, dense_rows=0, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, dense_rows=0, q_dense=False, **kw):
         super().__init__(*args, **kw)
+        if q_dense:
+            self.set_hessian_form("dense")
         if a_sparse:
             self.set_dynamics_form("sparse")
         if a_profile:
@@ -421,6 +425,54 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         ptr, rng = d[: K + 1], d[K + 1:].reshape(-1, 2)
         return [rng[ptr[k]: ptr[k + 1]].copy() for k in range(K)]
 
+    def set_hessian_form(self, form):
+        """"csr" (default: term lists) or "dense" (a dense block Q_k per stage); holds from the next init() on."""
+        code = {"csr": _lib.HESS_CSR, "dense": _lib.HESS_DENSE}.get(form, form)
+        _check(self._L.hqpkkt_set_hessian_form(self._h, int(code)), "set_hessian_form")
+
+    def hessian_layout(self):
+        """Per stage k = 0 .. K (order of Q_k, leading dimension, H terms left in the lists), an int64 array of shape
+        (K + 1, 3); [] unless the dense form of the Hessians is set."""
+        d = self.debug(45)
+        if d.size == 0:
+            return []
+        d = d.astype(np.int64).reshape(-1, 4)
+        return np.stack([d[:, 0], d[:, 1], (d[:, 2] & 0xFFFFFFFF) | (d[:, 3] << 32)], axis=1)
+
+    def set_stage_hessian(self, k, Q):
+        """Block k of the dense Hessians (dense hand-over): a row-major matrix of which the entries j >= i are read; a
+        numpy array, or a torch CUDA tensor with device_vectors=True."""
+        if hasattr(Q, "data_ptr"):
+            if not self._device_vectors or Q.stride(1) != 1:
+                raise TypeError("Q blocks: row-major torch CUDA tensors need device_vectors=True")
+            ptr, ld, keep = Q.data_ptr(), Q.stride(0), None  # (a device block is the caller's to keep until the stream has read it)
+        else:
+            if self._device_vectors:
+                raise TypeError("device_vectors=True needs torch CUDA Q blocks")
+            keep = np.ascontiguousarray(Q, dtype=np.float64)
+            ptr, ld = keep.ctypes.data, keep.shape[1]
+        _check(self._L.hqpkkt_set_stage_hessian(self._h, int(k), C.c_void_p(ptr), ld), "set_stage_hessian")
+        # (the copy is asynchronous in the handle's stream: the block stays alive until the hand-over ends)
+        if keep is not None:
+            self._keep_q = getattr(self, "_keep_q", []) + [keep]
+
+    def stage_hessian(self, k):
+        """Q_k as it lies in the arena (tests): order x leading dimension, padding included."""
+        n = C.c_longlong()
+        _check(self._L.hqpkkt_debug_stage_hessian(self._h, k, None, 0, C.byref(n)), "stage_hessian")
+        out = np.zeros(max(n.value, 1))
+        _check(self._L.hqpkkt_debug_stage_hessian(self._h, k, C.c_void_p(out.ctypes.data), n.value, C.byref(n)), "stage_hessian")
+        lay = self.hessian_layout()
+        return out[: n.value].reshape(int(lay[k][0]), int(lay[k][1]))
+
+    def hess_symv(self, x):
+        """y = Q x over the dense stage Hessians by the kernel of the residual products (tests); x of length n."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == self.n
+        y = np.zeros(self.n)
+        _check(self._L.hqpkkt_debug_hess_symv(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data)), "hess_symv")
+        return y
+
     def set_packed_panels(self, on):
         """Packed panels of the profile form (hqpkkt_set_packed_panels); holds from the next init() on."""
         _check(self._L.hqpkkt_set_packed_panels(self._h, int(on)), "set_packed_panels")
@@ -447,7 +499,9 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         self.n, self.me, self.m = dq.dims
         nx, nu = _i32(dq.nx), _i32(dq.nu)
         arrs = []
-        for (p, i, _x) in (dq.Q, dq.E, dq.C):
+        qd = getattr(dq, "Qd", None) is not None  # (dense stage Hessians: Q's pattern is not read)
+        empty = (np.zeros(0, dtype=np.int32),) * 3
+        for (p, i, _x) in (empty if qd else dq.Q, dq.E, dq.C):
             arrs += [_i32(p), _i32(i)]
         self._keep = arrs + [nx, nu]
         ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in arrs]
@@ -457,7 +511,13 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
 
     def update_dense(self, dq):
         vals, keep = [], []
-        for (_p, _i, x) in (dq.Q, dq.E, dq.C):
+        qd = getattr(dq, "Qd", None)
+        if qd is not None:  # the blocks Q_k first; the values of Q's CSR form are not read
+            assert len(qd) == dq.K + 1
+            self._keep_q = []
+            for k, blk in enumerate(qd):
+                self.set_stage_hessian(k, blk)
+        for (_p, _i, x) in ((None, None, np.zeros(0)) if qd is not None else dq.Q, dq.E, dq.C):
             if self._device_vectors and not hasattr(x, "data_ptr"):
                 import torch
                 x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda()
@@ -483,6 +543,7 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
                 fp[k], ld[k] = a.ctypes.data, a.shape[1]
                 keep.append(a)
         _check(self._L.hqpkkt_set_values_staged(self._h, vals[0], fp, ld, vals[1], vals[2]), "update_dense")
+        self._keep_q = []  # (set_values_staged has waited for the stream)
 
     def stage_structure(self):
         names = {"nk": 20, "mk": 21, "nmk": 22, "eq_ptr": 23, "eq_rows": 24, "fix_rows": 25, "cap": 26}

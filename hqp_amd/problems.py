@@ -360,20 +360,66 @@ def with_wide_rows(prog, rows, seed=77, scale=0.05):
     return out
 
 
+def with_dense_hessian(prog, seed=55):
+    """A copy of an :func:`lq_docp` / :func:`sparse_docp` program in which every stage block of ``Q`` (stage k: its
+    states and controls, stage K: its states) is the dense SPD matrix ``M M' / nz + diag(U(0.5, 1.5))`` with
+    ``M ~ U(-1, 1)`` of order nz, drawn stage by stage (M, then the diagonal) from ``default_rng(seed)``; the upper
+    triangle is stored.  What a block-BFGS update hands the multistage plugin (hqp/Hqp_HL_BFGS.C): the workload of
+    ``Hqp_IpLQDOCP(q_dense=True)``."""
+    rng = np.random.default_rng(seed)
+    nxs, nus = list(prog.nx), list(prog.nu)
+    K = len(nus)
+    off = 0
+    qr, qc, qv = [], [], []
+    for k in range(K + 1):
+        nz = nxs[k] + (nus[k] if k < K else 0)
+        M = rng.uniform(-1.0, 1.0, (nz, nz))
+        B = M @ M.T / nz + np.diag(rng.uniform(0.5, 1.5, nz))
+        i, j = np.triu_indices(nz)
+        qr.append(off + i), qc.append(off + j), qv.append(B[i, j])
+        off += nz
+    assert off == prog.n
+    Q = _csr(np.concatenate(qr), np.concatenate(qc), np.concatenate(qv), prog.n)
+    out = Program(prog.n, prog.me, prog.m, Q, prog.A, prog.C, c=prog.c, b=prog.b, d=prog.d)
+    out.nx, out.nu = nxs, nus
+    return out
+
+
+def stage_hessians(Q, nx, nu):
+    """The stage blocks of a block-diagonal ``Q`` in CSR form (upper triangle stored) as full symmetric matrices, K + 1 of them."""
+    K = len(nu)
+    p, i, x = (np.asarray(a) for a in Q)
+    rows = np.repeat(np.arange(len(p) - 1), np.diff(p))
+    up = i >= rows  # (only col >= row is read)
+    rows, cols, vals = rows[up], i[up], np.asarray(x, dtype=float)[up]
+    out, off = [], 0
+    for k in range(K + 1):
+        nz = nx[k] + (nu[k] if k < K else 0)
+        sel = (rows >= off) & (rows < off + nz)
+        assert np.all(cols[sel] < off + nz)
+        B = np.zeros((nz, nz))
+        B[rows[sel] - off, cols[sel] - off] = vals[sel]
+        out.append(np.triu(B) + np.triu(B, 1).T)
+        off += nz
+    return out
+
+
 class DenseDocp:
     """A multistage QP whose dynamics rows are handed over as dense blocks
     (hqpkkt_analyze_staged / hqpkkt_set_values_staged): ``F[k]`` = [fx_k fu_k], row-major
     nx[k+1] x (nx[k] + nu[k]) (numpy arrays, or torch CUDA tensors for device hand-over);
     ``E`` = the other equality rows (me_rest x n CSR).  Vectors of length ``me`` keep the
-    reference's order: dynamics rows first."""
+    reference's order: dynamics rows first.  ``Qd``: None, or the stage Hessians as a list of K + 1 dense blocks of
+    order nx[k] + nu[k] (the last: nx[K]) of which the upper triangle is read - for ``Hqp_IpLQDOCP(q_dense=True)``, which
+    then does not read ``Q``."""
 
-    def __init__(self, nx, nu, Q, E, C, F, me_rest, m, c=None, b=None, d=None):
+    def __init__(self, nx, nu, Q, E, C, F, me_rest, m, c=None, b=None, d=None, Qd=None):
         self.nx, self.nu = [int(v) for v in nx], [int(v) for v in nu]
         self.K = len(self.nu)
         self.n = sum(self.nx) + sum(self.nu)
         self.ndyn = sum(self.nx[1:])
         self.me_rest, self.me, self.m = int(me_rest), self.ndyn + int(me_rest), int(m)
-        self.Q, self.E, self.C, self.F = Q, E, C, F
+        self.Q, self.E, self.C, self.F, self.Qd = Q, E, C, F, Qd
         self.c = np.zeros(self.n) if c is None else c
         self.b = np.zeros(self.me) if b is None else b
         self.d = np.zeros(self.m) if d is None else d
@@ -383,9 +429,9 @@ class DenseDocp:
         return self.n, self.me, self.m
 
 
-def dense_docp_from_program(prog, nx, nu):
+def dense_docp_from_program(prog, nx, nu, dense_hessian=False):
     """The dense-dynamics form of a Program in Hqp_Docp's layout (tests: both hand-overs must
-    give the same results)."""
+    give the same results).  ``dense_hessian``: with the stage blocks of Q as ``DenseDocp.Qd``."""
     K = len(nu)
     p, i, x = prog.A
     nmk = np.concatenate([[0], np.cumsum([nx[k] + nu[k] for k in range(K)])])
@@ -402,7 +448,8 @@ def dense_docp_from_program(prog, nx, nu):
     ndyn = row
     Ep = (p[ndyn:] - p[ndyn]).astype(np.int32)
     E = (Ep, i[p[ndyn]:].astype(np.int32), x[p[ndyn]:].copy())
-    return DenseDocp(nx, nu, prog.Q, E, prog.C, F, prog.me - ndyn, prog.m, c=prog.c, b=prog.b, d=prog.d)
+    return DenseDocp(nx, nu, prog.Q, E, prog.C, F, prog.me - ndyn, prog.m, c=prog.c, b=prog.b, d=prog.d,
+                     Qd=stage_hessians(prog.Q, nx, nu) if dense_hessian else None)
 
 
 def random_sparse_qp(n, me, m, row_nnz=4, seed=7):

@@ -374,6 +374,37 @@ int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries);
  * are indexed by ints; one row of 46 341 entries is enough).  HQPKKT_E_NULL; HQPKKT_E_INTERN: the handle's mode is not
  * STAGED; HQPKKT_E_RANGE: min_entries < -1.  hqpkkt_debug_get 43 reports the rows and the term counts. */
 int hqpkkt_set_dense_rows(hqpkkt_t *h, int min_entries);
+/* The stage Hessians Q_k as dense blocks.  With HQPKKT_HESS_CSR every stored entry of Q becomes entries of the H term
+ * lists: right for a diagonal or banded Q, out of reach for the dense (n_k + m_k)^2 block per stage that a block-BFGS
+ * update hands over (hqp/Hqp_HL_BFGS.C:150-248; Hqp_IpLQDOCP extracts exactly these blocks, hqp/Hqp_IpLQDOCP.C:1084-1105).
+ * With HQPKKT_HESS_DENSE block k = 0 .. K of order nz_k = n_k + m_k (stage K: n_K) is kept row-major with leading
+ * dimension up8(nz_k), in full, exactly symmetric, zero padded, in an arena of its own that hqpkkt_stats.bytes_panels
+ * counts (+ sum of nz_k up8(nz_k) 8 bytes).  Q's terms leave the H lists (those of C'(Z/W)C stay); every factorisation adds
+ * the block into the stage's work block by a streaming kernel, Q first, then the lists; the products Q x of
+ * hqpkkt_residual, of hqpkkt_solve's refinement and of the interior-point loops run over the blocks in one launch with a
+ * fixed order of the sums.
+ *   CSR hand-over (hqpkkt_analyze + hqpkkt_set_values): Q is given as always - only col >= row is read, rows stay inside
+ *   their stage - and every hqpkkt_set_values scatters its values into the blocks, an off-diagonal entry to both of its
+ *   places; what the pattern does not hold stays zero.
+ *   Dense hand-over (hqpkkt_analyze_staged): Qp / Qi are ignored and may be NULL; block k comes through
+ *   hqpkkt_set_stage_hessian - nz_k rows of ldQ >= nz_k doubles, pointer per opts.loc, of which only the entries j >= i are
+ *   read (the strict lower triangle and the columns behind nz_k are the caller's) -, asynchronously in the handle's
+ *   stream; a host block may come out of the hqpkkt_stage_staging buffers.  hqpkkt_set_values_staged with Qx = NULL ends the
+ *   hand-over: HQPKKT_E_INTERN unless every Hessian block has been set since the analysis.  On the CSR hand-over
+ *   hqpkkt_set_stage_hessian returns HQPKKT_E_INTERN.
+ * Host only; call hqpkkt_set_hessian_form before the analysis; it holds until it is set again.  It works with every form
+ * of the dynamics and with hqpkkt_set_dense_rows.  On a handle with hqpkkt_set_shard / hqpkkt_set_shard_stream the analysis
+ * returns HQPKKT_E_RANGE, as for the sparse form.  HQPKKT_HESS_CSR (default) is the plan, arenas, launches and bits of a
+ * handle that never asked.  HQPKKT_E_NULL; HQPKKT_E_INTERN: the handle's mode is not STAGED; HQPKKT_E_RANGE: unknown form.
+ * hqpkkt_debug_get 45 reports the layout. */
+#define HQPKKT_HESS_CSR 0   /* default: term lists */
+#define HQPKKT_HESS_DENSE 1 /* Q_k kept as a dense block per stage 0 .. K */
+int hqpkkt_set_hessian_form(hqpkkt_t *h, int form);
+int hqpkkt_set_stage_hessian(hqpkkt_t *h, int k, const double *Q, long long ldQ);
+/* tests: block k of the dense Hessians as it lies in the arena (nz_k rows of up8(nz_k) doubles); out null: *len alone */
+int hqpkkt_debug_stage_hessian(hqpkkt_t *h, int k, double *out, long long cap, long long *len);
+/* tests: y = Q x over all stage blocks by the kernel of the residual; x, y host arrays of n */
+int hqpkkt_debug_hess_symv(hqpkkt_t *h, const double *x, double *y);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense
@@ -400,7 +431,7 @@ int hqpkkt_analyze_staged(hqpkkt_t *h, int K, const int *nx, const int *nu, int 
                           const int *Qi, const int *Ep, const int *Ei, const int *Cp, const int *Ci);
 /* The dense blocks one at a time, for hosts that extract them from row lists stage by stage (two stage-sized pinned
  * buffers instead of K of them): hqpkkt_stage_staging returns pinned buffer `which` (0 / 1; large enough for the
- * largest block; it waits until the copy that last read the buffer is over), hqpkkt_set_stage_block copies block k =
+ * largest block - with HQPKKT_HESS_DENSE for the largest Q_k too, nz_k * nz_k doubles; it waits until the copy that last read the buffer is over), hqpkkt_set_stage_block copies block k =
  * [fx_k fu_k] (nx[k+1] x (nx[k] + nu[k]), row-major, leading dimension ldF; any pointer per opts.loc) into the engine's
  * arena, asynchronously in the handle's stream.  hqpkkt_set_values_staged with F = NULL then takes the other values
  * and ends the hand-over (HQPKKT_E_INTERN unless every block has been set since the analysis). */
@@ -646,7 +677,9 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * have added; empty unless the analysis had a threshold > 0; valid after the analysis, without a device; 44 the
  * control-row segment of the fused stages: [0] W launches since the upload whose augmented tiles found W's control
  * columns unfinished, so that the guarded thin product formed the control rows of G, then per stage 1 where the W launch
- * takes the segment (decided at the upload).
+ * takes the segment (decided at the upload); 45 the dense Hessians (hqpkkt_set_hessian_form): per stage 0 .. K four ints -
+ * the block's order, its leading dimension, and the H terms left in the lists as a (low, high) pair; empty unless
+ * HQPKKT_HESS_DENSE is set; valid after the analysis, without a device.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

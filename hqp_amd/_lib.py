@@ -36,6 +36,7 @@ SYMBOLS = [
     "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
     "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
+    "hqpkkt_debug_gemm_schedule",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -100,6 +101,26 @@ class CtrlRowsCase(C.Structure):
                 ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong),
                 ("Cu", C.c_void_p), ("cu_rows", C.c_longlong), ("ldcu", C.c_longlong),
                 ("taken", C.c_int), ("fallbacks", C.c_int), ("form", C.c_int), ("tiles", C.c_longlong)]
+
+
+class GemmCaps(C.Structure):
+    """hqpkkt_gemm_caps (include/hqpkkt.h)"""
+    _fields_ = [(k, C.c_int) for k in ("variant", "cus", "grid", "unequal", "flags")] + \
+               [(k, C.c_longlong) for k in ("sk_tiles", "cnt_elems", "ws_elems", "ws2_elems")]
+
+
+class GemmLaunch(C.Structure):
+    """hqpkkt_gemm_launch (include/hqpkkt.h)"""
+    _fields_ = [(k, C.c_int) for k in ("M", "N", "K", "K2", "lower", "mirror", "second_stream", "ntiles")] + \
+               [(k, C.c_ulonglong) for k in ("a", "b", "a2", "b2", "c")] + \
+               [(k, C.c_longlong) for k in ("lda", "ldb", "lda2", "ldb2", "ldc", "c0")] + \
+               [("mu", C.c_int), ("by", C.c_int), ("panel", C.c_void_p)]
+
+
+class GemmScheduleOut(C.Structure):
+    """hqpkkt_gemm_schedule_out (include/hqpkkt.h)"""
+    _fields_ = [(k, C.c_int) for k in ("form", "nsplit", "variant", "list", "stride", "seg", "same_key")] + \
+               [(k, C.c_longlong) for k in ("tiles", "nslab", "pieces", "order_len")]
 
 
 class IpResult(C.Structure):
@@ -188,6 +209,8 @@ def lib():
     L.hqpkkt_debug_gemv_packed.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, vp, vp, vp, vp, C.c_double, vp]
     L.hqpkkt_debug_carried_packed.argtypes = [C.c_int] * 4 + [vp, C.c_longlong, C.c_longlong, vp, C.c_longlong, vp, vp, vp] + [C.c_longlong] * 4
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3
+    L.hqpkkt_debug_gemm_schedule.argtypes = [C.POINTER(GemmCaps), C.POINTER(GemmLaunch), C.POINTER(GemmLaunch), C.POINTER(GemmScheduleOut),
+                                             C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_int), C.c_longlong]
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_debug_factor_block.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 7
     _lib = L

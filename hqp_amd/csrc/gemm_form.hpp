@@ -1,8 +1,9 @@
 // The launch rule of the STAGED engine's dense fp64 product C = A'B (staged_gemm.hip.h): which of its forms an
 // M x N x K product takes, with how many tiles, and whether it wants a tile order.  Plain C++ (no device code, no HIP
-// call, no allocation): st_gemm - at a launch and in upload's dry walk of the factor sequence - and hqpkkt_debug_dgemm
-// decide here, and the CPU tests see the decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a
-// work list; which one is sk_table.hpp's decision (gemm_choose_list), made for the engine's shapes at upload.
+// call, no allocation): the schedule of a launch (gemm_schedule.hpp) - asked by st_gemm at a launch and in upload's dry
+// walk of the factor sequence, and by the hooks hqpkkt_debug_dgemm* - decides the form here, and the CPU tests see the
+// decision through hqpkkt_debug_gemm_form.  The two cut forms (FRAC, CUT) walk a work list; which one is sk_table.hpp's
+// decision (gemm_choose_list), made for the engine's shapes at upload.
 #pragma once
 #include <algorithm>
 
@@ -78,7 +79,7 @@ struct GemmForm {
   int kind = GEMM_FORM_NONE;
   long long tiles = 0;     // workgroups of the plain forms / tiles of the split ones
   int nsplit = 1;          // GEMM_FORM_KS: pieces of the k range
-  bool tile_map = false;   // the tile order of a large triangle is wanted (StagedDev::tri_map)
+  bool tile_map = false;   // the tile order of a large triangle is wanted (GemmSchedule::order)
 };
 // cus: CUs of the device; grid: workgroups of the split forms (0: not used); sk_tiles: most tiles the arrival counters
 // hold; ws_elems: workspace of the first stream (parked partial tiles; the pieces of a product cut in k), ws2_elems: of the
@@ -102,7 +103,7 @@ static inline GemmForm gemm_form(int M, int N, int K, int lower, int mirror, int
   f.tile_map = !(flags & GEMM_NO_TILE_MAP) && lower && M == N && big && tm >= 16 && tm < 32768;
   if (split && f.tiles <= sk_tiles) {
     // tile count that does not fill the chip evenly: whole rounds, then the k ranges of the rest cut (k_dgemm_tn_sk)
-    f.kind = frac ? GEMM_FORM_FRAC : GEMM_FORM_CUT;  // (both walk a work list of (tiles, k-slabs), StagedDev::sk_tab)
+    f.kind = frac ? GEMM_FORM_FRAC : GEMM_FORM_CUT;  // (both walk a work list of (tiles, k-slabs), GemmSchedule::tab)
   } else if (big)
     f.kind = GEMM_FORM_PLAIN;
   else if (!(flags & GEMM_NO_KS) && cus > 0 && !lower && !mirror && K >= 512 && f.tiles * 2 <= cus &&

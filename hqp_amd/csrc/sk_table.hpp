@@ -276,8 +276,8 @@ static inline bool gemm_profile_table(const int *ranges, long long tiles, int gr
   return true;
 }
 
-// Which list a launch of the cut forms walks - decided here alone, for the engine (StagedDev::sk_tab_prepare, called by
-// st_gemm in upload's dry walk of the factor sequence) and for the self-test (hqpkkt_debug_dgemm).  SK_LIST_NONE: no list whose parked pieces fit the workspace of `ws_elems`
+// Which list a launch of the cut forms walks - decided here alone, for the schedule of a launch (gemm_schedule.hpp: the
+// engine in upload's dry walk of the factor sequence, and the self-test hqpkkt_debug_dgemm).  SK_LIST_NONE: no list whose parked pieces fit the workspace of `ws_elems`
 // doubles - the launch is a plain round of whole tiles instead.
 // `frac`: the launch rule gave the fractional form (gemm_form.hpp).  Otherwise the unequal shares, unless they are
 // switched off (HQPKKT_SK_TABLE=0), the system is sharded over several ranks - there the strip's product runs beside the

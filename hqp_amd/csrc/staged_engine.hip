@@ -177,8 +177,16 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
               // (stg::SK_LIST_*), launches that looked it up since
-      for (const StagedDev::SkTab &t : h->sd->sk_tabs)
-        for (int val : {(int)t.tiles, (int)t.nslab, t.form, t.list, t.hits}) out.push_back(val);
+              // (the cut forms' entries of StagedDev::gemms in the order they were made, requests with the same list as one; a
+              // launch with the control-row segment: form + 100; the profile form's lists are not reported)
+      for (const GemmCache::Entry &t : h->sd->gemms.entries) {
+        if (!t.s.cut()) continue;
+        const int row[3] = {(int)t.s.f.tiles, (int)t.s.nslab, t.s.f.kind + (t.s.seg ? 100 : 0)};
+        size_t q = 0;
+        while (q < out.size() && !std::equal(row, row + 3, out.begin() + q)) q += 5;
+        if (q == out.size()) out.insert(out.end(), {row[0], row[1], row[2], t.s.list, 0});
+        out[q + 4] += t.hits;
+      }
       break;
     default: return HQPKKT_E_RANGE;
   }
@@ -602,119 +610,73 @@ static void dgemm_stamps_plain(const stg::GemmArgs &g, long long tiles, int vari
   }
 }
 }  // namespace
-// One launch of the product outside a handle, for hqpkkt_debug_dgemm and hqpkkt_debug_dgemm_full: the engine's rule
-// (gemm_form.hpp) and the engine's launch (stg::gemm_launch_form) with a workspace, arrival counters, a work list, a tile
-// order and a zero row of its own.  The rule sees the capacity the self-test has always stated - counters for the tiles
-// of this product, 16 parked pieces per tile - and the buffers hold what the chosen list and form need.
+// One launch of the product outside a handle, for the hooks hqpkkt_debug_dgemm*: the engine's schedule
+// (stg::gemm_schedule through a GemmCache of its own) and the engine's launch (stg::gemm_run) with a workspace, arrival
+// counters and a zero row of its own.  The schedule sees the capacity the self-test has always stated - counters for
+// the tiles of this product, 16 parked pieces per tile - and the buffers hold what the chosen list and form need.
 struct DebugGemm {
-  DBuf<double> zr, ws;
-  DBuf<unsigned> cnt;
-  DBuf<stg::SkUnit> units;
-  DBuf<int> order;
-  stg::GemmForm f;
-  stg::SplitTable tab;
-  stg::SplitPlan sk{};
-  stg::GemmLaunch L{};
-  int list = stg::SK_LIST_NONE, cus = 0, skg = 0;
-  bool use_sk = false;
-  // completes g (zeros, tile_map) and makes what its launch looks up; flags: stg::GEMM_SHARDED, GEMM_NO_KS, GEMM_NO_TILE_MAP, GEMM_FORCE_SPLIT
+  DBuf<double> zr, ws, thin_ws;
+  DBuf<unsigned> cnt, ctl;
+  stg::GemmCaps caps;
+  GemmCache cache;
+  GemmCache::Entry local, *e = nullptr;
+  stg::GemmArgs thin{};
+  int thin_split = 1;
+  // makes what the launch of g looks up; flags: stg::GEMM_SHARDED, GEMM_NO_KS, GEMM_NO_TILE_MAP, GEMM_FORCE_SPLIT
   // krange / krange_by: the profile form (hqpkkt_dgemm_case): two ints per 128-wide panel of B (1) or A (2)
-  int prepare(int device, stg::GemmArgs &g, int flags, const int *krange = nullptr, int krange_by = 0) {
-    const int variant = stg::gemm_variant_from_env();
-    if (variant != stg::GEMM_REG4 && stg::gemm_operands_dma_ok(g)) {
-      if (zr.alloc(256)) return HQPKKT_E_MEM;
-      (void)hipMemset(zr.p, 0, sizeof(double) * 256);
-      g.zeros = zr.p;
-    }
-    if (g.K2 > 0 && !g.zeros) return HQPKKT_E_RANGE;  // (the LDS-DMA kernels alone)
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    skg = stg::gemm_wgs_per_cu(variant) * cus;
+  // g.Au / mu / Cu set: the control-row segment is asked for, on `grid` workgroups (0: the device's); taken() says
+  // whether the launch takes it, as the engine would.  The product Cu = Au'B cut in k runs behind it, guarded, as in the
+  // engine's fused stage; not taken: that product alone forms Cu
+  int prepare(int device, stg::GemmArgs &g, int flags, const int *krange = nullptr, int krange_by = 0, int grid = 0) {
     const long long t128 = stg::gemm_tiles(g.M, g.N, 128, g.lower), nslab = stg::gemm_slabs_of(g);
-    const long long ws_elems = std::max<long long>(16 * t128 + 8, 2LL * skg + 2) * 128 * 128;
+    caps.variant = stg::gemm_variant_from_env();
+    (void)hipDeviceGetAttribute(&caps.cus, hipDeviceAttributeMultiprocessorCount, device);
+    caps.grid = grid > 0 ? grid : stg::gemm_wgs_per_cu(caps.variant) * caps.cus;
+    caps.sk_tiles = t128, caps.cnt_elems = t128 + 5;
+    caps.ws_elems = std::max<long long>(16 * t128 + 8, 2LL * caps.grid + 2) * 128 * 128;
+    caps.unequal = stg::gemm_sk_table_from_env() && !(flags & stg::GEMM_SHARDED), caps.flags = flags;
     if (krange_by) {
       const int npanel = ((krange_by == 2 ? g.M : g.N) + 127) / 128;
-      if (!krange || (krange_by != 1 && krange_by != 2) || g.K2 > 0 || skg <= 0) return HQPKKT_E_RANGE;
+      if (!krange || (krange_by != 1 && krange_by != 2)) return HQPKKT_E_RANGE;
       for (int p = 0; p < npanel; p++)
         if (krange[2 * p] < 0 || krange[2 * p + 1] < krange[2 * p] || krange[2 * p + 1] > nslab) return HQPKKT_E_RANGE;
-      f = stg::gemm_form_profile(g.M, g.N, g.lower, flags);
-    } else
-      f = stg::gemm_form(g.M, g.N, g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K, g.lower, g.mirror, cus, skg, t128, ws_elems, 0, flags);
-    if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_RANGE;
-    use_sk = f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT;
-    if (g.K2 > 0 && !use_sk && f.kind != stg::GEMM_FORM_PLAIN) return HQPKKT_E_RANGE;  // (128 x 128 tiles alone)
+    }
+    if (g.Au) {
+      if (ctl.alloc(8)) return HQPKKT_E_MEM;
+      (void)hipMemset(ctl.p, 0, sizeof(unsigned) * 8);
+      g.ctl = ctl.p;
+      thin = stg::GemmArgs{g.Au, g.ldau, g.B, g.ldb, nullptr, 0, g.Cu, g.ldcu, g.mu, g.N, g.K, g.alpha, 0.0, 0, 0};
+      thin_split = (int)std::max<long long>(1, std::min<long long>(8, stg::gemm_slabs(g.K) / 4));
+      if (thin_ws.alloc((size_t)thin_split * g.mu * g.N)) return HQPKKT_E_MEM;
+    }
+    const stg::PackPanel *apack = g.apack, *bpack = g.bpack;
+    g.apack = g.bpack = nullptr;  // (the request is that of the operands as blocks, as the engine's)
+    const stg::GemmRequest rq = stg::gemm_request(g, false, 0, krange_by, krange);
+    g.apack = apack, g.bpack = bpack;
+    if (int err = cache.get(caps, rq, true, local, e)) return err == HQPKKT_E_MEM ? err : HQPKKT_E_RANGE;
     (void)stg::gemm_set_attributes();
-    if (f.tile_map) {
-      if (order.upload(stg::gemm_tri_order((g.M + 127) / 128))) return HQPKKT_E_MEM;
-      g.tile_map = order.p;
+    const stg::GemmSchedule &s = e->s;
+    if (s.variant != stg::GEMM_REG4) {
+      if (zr.alloc(256)) return HQPKKT_E_MEM;
+      (void)hipMemset(zr.p, 0, sizeof(double) * 256);
     }
-    L = stg::GemmLaunch{stg::gemm_variant_for(g, variant), cus, skg, nullptr, nullptr};
-    if (f.kind == stg::GEMM_FORM_PROFILE) {
-      std::vector<int> ord;
-      if (f.tile_map) ord = stg::gemm_tri_order((g.M + 127) / 128);
-      const std::vector<int> r = stg::gemm_profile_tile_ranges(g.M, g.N, g.lower, f.tile_map ? ord.data() : nullptr, krange, krange_by);
-      if (!stg::gemm_profile_table(r.data(), f.tiles, skg, tab)) return HQPKKT_E_RANGE;
-      if (units.upload(tab.units) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 4)) return HQPKKT_E_MEM;
-      sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
-      L.sk = &sk;
-      use_sk = true;  // (launch() clears the arrival counters)
-    } else if (use_sk) {
-      // (its one list by the engine's chooser: unequal shares for the two workgroups of a CU; HQPKKT_SK_TABLE=0 or one system over
-      // several ranks: equal shares)
-      list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, stg::gemm_sk_table_from_env() && !(flags & stg::GEMM_SHARDED), f.tiles, nslab, skg, t128, ws_elems, tab);
-      if (list == stg::SK_LIST_NONE) return HQPKKT_E_RANGE;
-      if (units.upload(tab.units) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 4)) return HQPKKT_E_MEM;
-      sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
-      L.sk = &sk;
-    } else if (f.kind == stg::GEMM_FORM_KS) {
-      if (ws.alloc((size_t)stg::gemm_ks_ws_elems(g, f))) return HQPKKT_E_MEM;
-      L.ks_ws = ws.p;
-    }
+    const long long ws_elems = s.f.kind == stg::GEMM_FORM_KS ? stg::gemm_ks_ws_elems(g, s.f) : std::max<long long>(s.tab.pieces, 1) * 128 * 128;
+    if (ws.alloc((size_t)ws_elems) || cnt.alloc((size_t)caps.cnt_elems)) return HQPKKT_E_MEM;
+    if (s.seg) thin.guard = ctl.p + 2;
     return 0;
   }
+  bool taken() const { return e->s.seg; }
   void launch(const stg::GemmArgs &g) {
-    if (use_sk) (void)hipMemsetAsync(cnt.p, 0, sizeof(unsigned) * (f.tiles + 4), 0);
-    stg::gemm_launch_form(f, L, 0, g, [](auto &&kernel) { kernel(); });
-    if (thin.M > 0) {  // the control rows as the engine's fused stage forms them: guarded behind a launch with the segment
+    // (its own counters: cleared ahead of every launch)
+    if (e->s.list != stg::SK_LIST_NONE) (void)hipMemsetAsync(cnt.p, 0, sizeof(unsigned) * (size_t)caps.cnt_elems, 0);
+    stg::gemm_run(e->s, caps, stg::GemmBufs{e->units.p, e->order.p, ws.p, cnt.p, ws.p, zr.p}, 0, g, [](auto &&kernel) { kernel(); });
+    if (thin.M > 0) {
+      // The control rows as the engine's fused stage forms them: guarded behind a launch with the segment.  A direct launch:
+      // the rule does not give the hooks' small shapes the form cut in k (GEMM_FORM_KS), and only that form knows the guard
       stg::k_dgemm_tn_ks<64, 64><<<dim3((unsigned)stg::gemm_tiles(thin.M, thin.N, 64, 0), thin_split), 256, stg::gemm_lds_bytes(64, 64), 0>>>(thin, thin_ws.p, thin_split);
       stg::k_dgemm_ks_finish<<<(unsigned)(((long long)thin.M * thin.N + 255) / 256), 256, 0, 0>>>(thin, thin_ws.p, thin_split);
       if (thin.guard) stg::k_ctrl_rows_end<<<1, 64, 0, 0>>>(ctl.p);
     }
-  }
-  // The control-row segment (GemmArgs::Au / mu / Cu set by the caller; prepare() has run): the launch takes it where the
-  // engine would - a cut form, gemm_ctrl_rows_ok, a list in the segment's order on `grid` workgroups (0: the device's) - and
-  // the product Cu = Au'B cut in k runs behind it, guarded; otherwise that product alone forms Cu.  Returns whether the
-  // segment is taken (< 0: an error)
-  DBuf<int> cmap;
-  DBuf<unsigned> ctl;
-  DBuf<double> thin_ws;
-  stg::GemmArgs thin{};
-  int thin_split = 1;
-  int prepare_ctrl_rows(stg::GemmArgs &g, int grid) {
-    if (ctl.alloc(8)) return HQPKKT_E_MEM;
-    (void)hipMemset(ctl.p, 0, sizeof(unsigned) * 8);
-    g.ctl = ctl.p;
-    thin = stg::GemmArgs{g.Au, g.ldau, g.B, g.ldb, nullptr, 0, g.Cu, g.ldcu, g.mu, g.N, g.K, g.alpha, 0.0, 0, 0};
-    thin_split = (int)std::max<long long>(1, std::min<long long>(8, stg::gemm_slabs(g.K) / 4));
-    if (thin_ws.alloc((size_t)thin_split * g.mu * g.N)) return HQPKKT_E_MEM;
-    const int wgs = grid > 0 ? grid : skg;
-    bool taken = use_sk && f.kind != stg::GEMM_FORM_PROFILE && wgs > 0 && stg::gemm_ctrl_rows_ok(g, L.variant);
-    if (taken) {
-      const int tiles_m = (g.M + 127) / 128;
-      const long long nslab = stg::gemm_slabs_of(g);
-      std::vector<int> map;
-      const int l = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, stg::gemm_sk_table_from_env(), f.tiles + 1, nslab, wgs, f.tiles + 1, 1LL << 40, tab);
-      taken = l != stg::SK_LIST_NONE && stg::gemm_ctrl_rows_order(tab, wgs, tiles_m, (int)(f.tiles / tiles_m), map);
-      if (taken) {
-        list = l;
-        if (units.upload(tab.units) || cmap.upload(map) || ws.alloc((size_t)std::max<long long>(tab.pieces, 1) * 128 * 128) || cnt.alloc(f.tiles + 5)) return HQPKKT_E_MEM;
-        (void)hipMemset(cnt.p, 0, sizeof(unsigned) * (f.tiles + 5));
-        sk = stg::SplitPlan{ws.p, cnt.p, units.p, tab.stride};
-        L.sk = &sk, L.grid = wgs;
-        g.tile_map = cmap.p, thin.guard = ctl.p + 2;
-      }
-    }
-    if (!taken) g.Au = nullptr, g.Cu = nullptr, g.mu = 0, g.ctl = nullptr;
-    return taken ? 1 : 0;
   }
   int fallbacks() {
     unsigned w[3] = {0, 0, 0};
@@ -750,19 +712,18 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   // The engine's rule (gemm_form.hpp) with what this entry point has always done differently: no thin product cut in k, no
   // tile order for large triangles, never sharded, and a workspace of its own
   // (HQPKKT_DGEMM_FORCE_SPLIT: the cut form whatever the launch rules say - same-box comparisons of the two forms)
-  DebugGemm run;
-  if (int e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP | (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0))) return e;
   // (HQPKKT_DGEMM_CTRL_ROWS=mu, M == K: the launch with the control-row segment for the last mu columns of C and the
   // guarded product behind it, as a fused stage runs W - same-box comparisons with the plain launch)
   DBuf<double> Cu;
   const int mu = getenv("HQPKKT_DGEMM_CTRL_ROWS") ? atoi(getenv("HQPKKT_DGEMM_CTRL_ROWS")) : 0;
-  if (mu > 0 && mu <= N && M == K && K2 == 0 && !lower) {
+  const bool seg = mu > 0 && mu <= N && M == K && K2 == 0 && !lower;
+  if (seg) {
     if (Cu.alloc((size_t)mu * ldc)) return HQPKKT_E_MEM;
     g.Au = Cm.p + (N - mu), g.ldau = ldc, g.mu = mu, g.Cu = Cu.p, g.ldcu = ldc;
-    const int taken = run.prepare_ctrl_rows(g, 0);
-    if (taken < 0) return taken;
-    fprintf(stderr, "control-row segment: %s\n", taken ? "taken" : "not taken (the thin product alone)");
   }
+  DebugGemm run;
+  if (int e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_NO_TILE_MAP | (getenv("HQPKKT_DGEMM_FORCE_SPLIT") ? stg::GEMM_FORCE_SPLIT : 0))) return e;
+  if (seg) fprintf(stderr, "control-row segment: %s\n", run.taken() ? "taken" : "not taken (the thin product alone)");
   EventOwner e0, e1;
   (void)hipEventCreate(&e0.h), (void)hipEventCreate(&e1.h);
   for (int r = -1; r < reps; r++) {
@@ -777,8 +738,10 @@ static int debug_dgemm(int device, int M, int N, int K, int K2, int lower, int m
   (void)hipEventElapsedTime(&t, e0, e1);
   if (se != hipSuccess) return HQPKKT_E_DEVICE;
   if (getenv("HQPKKT_DGEMM_STAMPS")) {
-    if (run.f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(g, run.f, run.L.variant, run.skg, run.list, run.tab, run.units.p);
-    if (run.f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(g, run.f.tiles, run.L.variant);
+    const stg::GemmSchedule &sc = run.e->s;
+    const stg::GemmArgs gc = stg::gemm_complete(sc, stg::GemmBufs{nullptr, run.e->order.p, nullptr, nullptr, nullptr, run.zr.p}, g);
+    if (sc.f.kind == stg::GEMM_FORM_CUT) dgemm_stamps_split(gc, sc.f, sc.variant, run.caps.grid, sc.list, sc.tab, run.e->units.p);
+    if (sc.f.kind == stg::GEMM_FORM_PLAIN) dgemm_stamps_plain(gc, sc.f.tiles, sc.variant);
   }
   k_gemm_check<<<16, 256>>>(g, 4096, err.p);
   double he = 0.0;
@@ -863,8 +826,9 @@ static int debug_dgemm_full(int device, hqpkkt_dgemm_case *c, const double *pk =
   run.launch(g);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(c->C, dC.p, sizeof(double) * (size_t)(c->c_rows * c->ldc), hipMemcpyDeviceToHost));
-  c->form = run.f.kind, c->tile_map = g.tile_map != nullptr, c->ldsdma = g.zeros != nullptr, c->nsplit = run.f.nsplit;
-  c->tiles = run.f.tiles;
+  const stg::GemmSchedule &sc = run.e->s;
+  c->form = sc.f.kind, c->tile_map = !sc.order.empty(), c->ldsdma = sc.variant != stg::GEMM_REG4, c->nsplit = sc.f.nsplit;
+  c->tiles = sc.f.tiles;
   return 0;
 }
 int hqpkkt_debug_dgemm(int device, int M, int N, int K, int lower, int mirror, int reps, double *ms, double *max_err) {
@@ -901,24 +865,31 @@ static int debug_dgemm_ctrl_rows(int device, hqpkkt_ctrl_rows_case *c) {
       (e = up(dCu, c->Cu, std::max<long long>(1, c->cu_rows * c->ldcu))))
     return e;
   stg::GemmArgs g{dA.p + c->A.col0, c->A.ld, dB.p + c->B.col0, c->B.ld, nullptr, 0, dC.p, c->ldc, M, N, K, 1.0, 0.0, 0, 0};
+  if (mu > 0) g.Au = g.C + (N - mu), g.ldau = c->ldc, g.mu = mu, g.Cu = dCu.p, g.ldcu = c->ldcu;
   DebugGemm run;
-  if ((e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_FORCE_SPLIT))) return e;
-  c->taken = 0, c->fallbacks = 0;
-  if (mu > 0) {
-    g.Au = g.C + (N - mu), g.ldau = c->ldc, g.mu = mu, g.Cu = dCu.p, g.ldcu = c->ldcu;
-    if ((e = run.prepare_ctrl_rows(g, c->grid)) < 0) return e;
-    c->taken = e;
-  }
+  if ((e = run.prepare(device, g, stg::GEMM_NO_KS | stg::GEMM_FORCE_SPLIT, nullptr, 0, c->grid))) return e;
+  c->taken = run.taken(), c->fallbacks = 0;
   run.launch(g);
   HIPCHK(hipDeviceSynchronize());
   if (mu > 0 && (c->fallbacks = run.fallbacks()) < 0) return HQPKKT_E_DEVICE;
   HIPCHK(hipMemcpy(c->C, dC.p, sizeof(double) * (size_t)(c->c_rows * c->ldc), hipMemcpyDeviceToHost));
   if (c->cu_rows > 0) HIPCHK(hipMemcpy(c->Cu, dCu.p, sizeof(double) * (size_t)(c->cu_rows * c->ldcu), hipMemcpyDeviceToHost));
-  c->form = run.f.kind, c->tiles = run.f.tiles;
+  c->form = run.e->s.f.kind, c->tiles = run.e->s.f.tiles;
   return 0;
 }
 int hqpkkt_debug_dgemm_ctrl_rows(int device, hqpkkt_ctrl_rows_case *c) {
   return guarded([&]() -> int { return debug_dgemm_ctrl_rows(device, c); });
+}
+// a work list for the host-only hooks: six ints per unit (include/hqpkkt.h, hqpkkt_debug_sk_table); false: cap_ints too small
+static bool units_out(const stg::SplitTable &t, int *units, long long cap_ints) {
+  if (!units) return true;
+  if ((long long)t.units.size() * 6 > cap_ints) return false;
+  for (size_t i = 0; i < t.units.size(); i++) {
+    const stg::SkUnit &u = t.units[i];
+    int *o = units + 6 * i;
+    o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
+  }
+  return true;
 }
 int hqpkkt_debug_sk_ctrl_rows(int tiles_m, int tiles_n, int nslab, int grid, int kind, int *units, long long cap_ints, int *tile_map, long long *pieces) {
   stg::SplitTable t;
@@ -928,14 +899,7 @@ int hqpkkt_debug_sk_ctrl_rows(int tiles_m, int tiles_n, int nslab, int grid, int
   if (kind < 0 ? stg::gemm_choose_list(false, true, tiles, nslab, grid, tiles, 1LL << 40, t) == stg::SK_LIST_NONE : !stg::gemm_list_table(kind, tiles, nslab, grid, t)) return 0;
   if (!stg::gemm_ctrl_rows_order(t, grid, tiles_m, tiles_n, map)) return 0;
   if (pieces) *pieces = t.pieces;
-  if (units) {
-    if ((long long)t.units.size() * 6 > cap_ints) return 0;
-    for (size_t i = 0; i < t.units.size(); i++) {
-      const stg::SkUnit &u = t.units[i];
-      int *o = units + 6 * i;
-      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
-    }
-  }
+  if (!units_out(t, units, cap_ints)) return 0;
   if (tile_map) std::copy(map.begin(), map.end(), tile_map);
   return t.stride;
 }
@@ -950,20 +914,38 @@ int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, 
   return f.kind;
 }
 
+// the request of a launch described by numbers (include/hqpkkt.h): through a GemmArgs, as the engine makes it
+static stg::GemmRequest debug_request(const hqpkkt_gemm_launch *l) {
+  stg::GemmArgs g{};
+  g.A = (const double *)l->a, g.lda = l->lda, g.B = (const double *)l->b, g.ldb = l->ldb, g.C = (double *)l->c, g.ldc = l->ldc;
+  g.A2 = (const double *)l->a2, g.lda2 = l->lda2, g.B2 = (const double *)l->b2, g.ldb2 = l->ldb2;
+  g.M = l->M, g.N = l->N, g.K = l->K, g.K2 = l->K2, g.lower = l->lower, g.mirror = l->mirror, g.alpha = 1.0;
+  if (l->mu > 0) g.Au = g.C + l->c0, g.ldau = l->ldc, g.mu = l->mu, g.Cu = (double *)l->c, g.ldcu = l->ldc, g.ctl = (unsigned *)l->c;
+  return stg::gemm_request(g, l->second_stream != 0, l->ntiles, l->panel ? l->by : 0, l->panel);
+}
+int hqpkkt_debug_gemm_schedule(const hqpkkt_gemm_caps *caps, const hqpkkt_gemm_launch *launch, const hqpkkt_gemm_launch *other,
+                               hqpkkt_gemm_schedule_out *out, int *units, long long cap_ints, int *order, long long cap_order) {
+  return guarded([&]() -> int {
+    if (!caps || !launch || !out) return -1;
+    const stg::GemmCaps c{caps->variant, caps->cus, caps->grid, caps->sk_tiles, caps->cnt_elems, caps->ws_elems, caps->ws2_elems, caps->unequal != 0, caps->flags};
+    const stg::GemmRequest rq = debug_request(launch);
+    stg::GemmSchedule s;
+    const int status = stg::gemm_schedule(c, rq, s);
+    *out = hqpkkt_gemm_schedule_out{s.f.kind, s.f.nsplit, s.variant, s.list, s.tab.stride, s.seg, other && rq == debug_request(other), s.f.tiles, s.nslab, s.tab.pieces,
+                                    (long long)s.order.size()};
+    if (status == stg::GEMM_SCHED_OK && (!units_out(s.tab, units, cap_ints) || (order && (long long)s.order.size() > cap_order))) return -1;
+    if (status == stg::GEMM_SCHED_OK && order) std::copy(s.order.begin(), s.order.end(), order);
+    return status;
+  });
+}
+
 int hqpkkt_debug_sk_table(long long tiles, int nslab, int grid, int kind, int *units, long long cap_ints, long long *pieces, int *whole_a, int *whole_b) {
   stg::SplitTable t;
   if (!stg::gemm_list_table(kind, tiles, nslab, grid, t)) return 0;
   if (pieces) *pieces = t.pieces;
   if (whole_a) *whole_a = t.nA;
   if (whole_b) *whole_b = t.nB;
-  if (units) {
-    if ((long long)t.units.size() * 6 > cap_ints) return 0;
-    for (size_t i = 0; i < t.units.size(); i++) {
-      const stg::SkUnit &u = t.units[i];
-      int *o = units + 6 * i;
-      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
-    }
-  }
+  if (!units_out(t, units, cap_ints)) return 0;
   return t.stride;
 }
 
@@ -971,14 +953,7 @@ int hqpkkt_debug_sk_profile(const int *ranges, long long tiles, int grid, int *u
   stg::SplitTable t;
   if (!stg::gemm_profile_table(ranges, tiles, grid, t)) return 0;
   if (pieces) *pieces = t.pieces;
-  if (units) {
-    if ((long long)t.units.size() * 6 > cap_ints) return 0;
-    for (size_t i = 0; i < t.units.size(); i++) {
-      const stg::SkUnit &u = t.units[i];
-      int *o = units + 6 * i;
-      o[0] = u.tile, o[1] = u.s0, o[2] = u.s1, o[3] = u.slot0, o[4] = u.pieces, o[5] = u.j;
-    }
-  }
+  if (!units_out(t, units, cap_ints)) return 0;
   return t.stride;
 }
 

@@ -9,8 +9,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "sk_table.hpp"
-#include "gemm_form.hpp"
+#include "gemm_schedule.hpp"
 
 namespace stg {
 
@@ -820,9 +819,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, NBUF == 3 ? WGM * WGN / 4 : WG
 // (+ 16 bytes: the word for the arrival order, and the size the launches have always had - LDS per workgroup decides how many a CU holds)
 static inline size_t gemm_sk_lds_bytes(int nbuf = 2) { return gemm_lds_bytes(128, 128, nbuf) + 16; }
 
-// Host: the variants of the 128 x 128 product.  0: operands staged through registers, 4 waves (round 2's loop, kept
-// for comparisons: HQPKKT_NO_LDSDMA); 1: LDS-DMA, 2 x 2 waves of 64 x 64; 2: LDS-DMA, 2 x 4 waves of 64 x 32 (default)
-enum { GEMM_REG4 = 0, GEMM_DMA4 = 1, GEMM_DMA8 = 2, GEMM_DMA8X3 = 3 };  // X3: three LDS buffers, one workgroup per CU
+// Host: the variants of the 128 x 128 product (gemm_schedule.hpp)
 static inline int gemm_wgs_per_cu(int variant) { return variant == GEMM_DMA8X3 ? 1 : 2; }
 // cus > 0: a launch of at most that many tiles takes the three-buffer kernel, whose 110 KB of LDS admit ONE workgroup
 // per CU - the dispatcher otherwise puts two workgroups on some CUs and none on others, and a pair takes twice as long
@@ -905,8 +902,8 @@ static inline int gemm_variant_from_env() {
   return GEMM_DMA8;
 }
 
-// What st_gemm (staged_host.hip.h), hqpkkt_debug_dgemm and hqpkkt_debug_dgemm_full (staged_engine.hip) share besides the
-// launch rule: when the operands may be staged by LDS-DMA, the tile order of a triangle, and the launch of a form.
+// What st_gemm (staged_host.hip.h) and the test hooks hqpkkt_debug_dgemm* (staged_engine.hip) share besides the schedule
+// of a launch (gemm_schedule.hpp): the request of a GemmArgs, and the launch of a schedule.
 
 // Operands by LDS-DMA (global_load_lds_dwordx4) only from 16-byte aligned rows: an operand that starts at an odd column
 // (the control columns F + nn of a stage with an odd number of states) or has an odd leading dimension is staged
@@ -914,15 +911,13 @@ static inline int gemm_variant_from_env() {
 static inline bool gemm_operands_dma_ok(const GemmArgs &g) {
   return ((((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) == 0) && (((g.lda | g.ldb | g.lda2 | g.ldb2) & 1) == 0);
 }
-// The 128 x 128 kernel of a launch: the handle's variant, and the register-staged one for operands without a zero row -
-// the LDS-DMA kernels read GemmArgs::zeros for every row k >= K and behind the last slab
-static inline int gemm_variant_for(const GemmArgs &g, int variant) { return g.zeros ? variant : GEMM_REG4; }
 // The control-row segment of g (GemmArgs::Au) can be taken by a launch of the cut forms: a ragged last tile row with an
 // even number r of rows and room for the mu rows, no other special of a launch, and Au = the columns [c0, c0 + mu) of C
 // inside the last tile column (so the tiles whose completion the augmented tiles ask for are the ones that write it);
-// every 16-byte load of a row of Au lies inside a row of C
-static inline bool gemm_ctrl_rows_ok(const GemmArgs &g, int variant) {
-  if (!g.Au || !g.Cu || !g.ctl || g.mu <= 0 || g.M <= 0 || !g.zeros || (variant != GEMM_DMA8 && variant != GEMM_DMA8X3)) return false;
+// every 16-byte load of a row of Au lies inside a row of C.  (The kernels it needs - 2 x 4 waves, LDS-DMA - and the list
+// are the schedule's to ask for.)
+static inline bool gemm_ctrl_rows_ok(const GemmArgs &g) {
+  if (!g.Au || !g.Cu || !g.ctl || g.mu <= 0 || g.M <= 0) return false;
   const int r = gemm_last_rows(g.M);
   const long long c0 = g.Au - g.C;
   return !(r & 1) && r + g.mu <= 128 && (((uintptr_t)g.Au) & 15) == 0 && !(g.ldau & 1) && g.ldau == g.ldc && c0 >= (g.N - 1) / 128 * 128LL &&
@@ -936,49 +931,14 @@ __global__ void k_ctrl_rows_end(unsigned *ctl) {
     ctl[0] = 0, ctl[2] = 0;
   }
 }
-// Order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map): super-blocks of 8 x 8 tiles,
-// row by row; inside a block column by column
-static inline std::vector<int> gemm_tri_order(int T) {
-  std::vector<int> m;
-  m.reserve((size_t)T * (T + 1) / 2);
-  const int S = 8;
-  for (int I = 0; I < (T + S - 1) / S; I++)
-    for (int J = 0; J <= I; J++)
-      for (int tn = J * S; tn < std::min(T, (J + 1) * S); tn++)
-        for (int tm = std::max(I * S, tn); tm < std::min(T, (I + 1) * S); tm++) m.push_back(tm << 16 | tn);
-  return m;
-}
-// GemmTile<128, 128>::tile_of on the host: tile index -> (tile row, tile column) of an M x N product on 128 x 128 tiles,
-// row by row in groups of eight tile rows, the rows of a triangle, or by the tile order `order` (gemm_tri_order)
-static inline void gemm_tile_of_host(int M, int N, int lower, const int *order, long long t, int &tm, int &tn) {
-  if (order) {
-    tm = order[t] >> 16, tn = order[t] & 0xffff;
-  } else if (lower) {
-    const long long tcols = (N + 127) / 128, tri = tcols * (tcols + 1) / 2;
-    if (t < tri) {
-      tm = 0;
-      while ((long long)(tm + 1) * (tm + 2) / 2 <= t) tm++;
-      tn = (int)(t - (long long)tm * (tm + 1) / 2);
-    } else
-      tm = (int)(tcols + (t - tri) / tcols), tn = (int)((t - tri) % tcols);
-  } else {
-    const long long tiles_n = (N + 127) / 128, tiles_m = (M + 127) / 128, GM = 8;
-    const long long grp = t / (GM * tiles_n), first = grp * GM, rows = std::min(GM, tiles_m - first), in = t - grp * GM * tiles_n;
-    tm = (int)(first + in % rows), tn = (int)(in / rows);
-  }
-}
-// The k ranges of the tiles of a product in the profile form, two ints per tile in the launch's tile order: `panel`
-// holds the k-slab range [lo, hi) of every 128-wide column panel of the ranged operand, by = 1: B's (tile (tm, tn)
-// takes panel tn: W = V+ F), by = 2: A's (panel tm: G = F'W)
-static inline std::vector<int> gemm_profile_tile_ranges(int M, int N, int lower, const int *order, const int *panel, int by) {
-  const long long tiles = gemm_tiles(M, N, 128, lower);
-  std::vector<int> r(2 * (size_t)tiles);
-  for (long long t = 0; t < tiles; t++) {
-    int tm, tn;
-    gemm_tile_of_host(M, N, lower, order, t, tm, tn);
-    const int p = by == 2 ? tm : tn;
-    r[2 * t] = panel[2 * p], r[2 * t + 1] = panel[2 * p + 1];
-  }
+// The request of a launch of g (gemm_schedule.hpp): no pointer or leading dimension of g counts beyond what they admit.
+// second: on the second stream; ntiles: the tiles g.tile_map[0 .. ntiles) only; by, panel: the profile form
+static inline GemmRequest gemm_request(const GemmArgs &g, bool second = false, int ntiles = 0, int by = 0, const int *panel = nullptr) {
+  GemmRequest r;
+  r.M = g.M, r.N = g.N, r.K = g.K, r.K2 = g.K2, r.lower = g.lower, r.mirror = g.mirror, r.ntiles = ntiles;
+  r.second = second, r.dma = gemm_operands_dma_ok(g);
+  if (g.Au && g.mu > 0) r.mu = g.mu, r.seg_ok = gemm_ctrl_rows_ok(g);
+  if (by) r.by = by, r.panel.assign(panel, panel + 2 * (((by == 2 ? g.M : g.N) + 127) / 128));
   return r;
 }
 // Workspace of the thin product cut in k (GEMM_FORM_KS): its pieces' raw sums, M x N each
@@ -1021,5 +981,32 @@ static inline void gemm_launch_form(const GemmForm &f, const GemmLaunch &L, hipS
       break;
     default: break;  // (GEMM_FORM_NONE: nothing to launch)
   }
+}
+// What a launch by a schedule takes from its holder: the schedule's list and tile order on the device (null: none), the
+// parked partial tiles and the arrival counters of the cut forms, the pieces of a product cut in k, the zero row of the
+// LDS-DMA staging
+struct GemmBufs {
+  const SkUnit *units;
+  const int *order;
+  double *sk_ws;
+  unsigned *sk_cnt;
+  double *ks_ws;
+  const double *zeros;
+};
+// g as schedule sc of its request launches it: zeros, tile_map; a segment that is not taken is dropped
+static inline GemmArgs gemm_complete(const GemmSchedule &sc, const GemmBufs &b, GemmArgs g) {
+  if (sc.variant != GEMM_REG4) g.zeros = b.zeros;
+  if (b.order) g.tile_map = b.order;
+  if (!sc.seg) g.Au = nullptr, g.Cu = nullptr, g.mu = 0, g.ctl = nullptr;
+  return g;
+}
+// Launches g by schedule sc of its request.  `around` as in gemm_launch_form
+template <class Around>
+static inline void gemm_run(const GemmSchedule &sc, const GemmCaps &c, const GemmBufs &b, hipStream_t s, const GemmArgs &g0, Around &&around) {
+  const GemmArgs g = gemm_complete(sc, b, g0);
+  // (the arrival counters of the cut forms are zero between launches: the last arriver of a tile resets its)
+  const SplitPlan sk{b.sk_ws, b.sk_cnt, b.units, sc.tab.stride};
+  const GemmLaunch L{sc.variant, c.cus, c.grid, sc.list != SK_LIST_NONE ? &sk : nullptr, b.ks_ws};
+  gemm_launch_form(sc.f, L, s, g, around);
 }
 }  // namespace stg

@@ -5,6 +5,41 @@
 // Reference counterpart: Hqp_IpLQDOCP::update / factor / step (hqp/Hqp_IpLQDOCP.C:722-976).
 #pragma once
 
+// The schedules of a holder's launches of the dense product (stg::gemm_schedule) with what they look up on the device:
+// one entry per request whose launch walks a work list or a tile order (GemmSchedule::kept).  get() with `create` makes
+// the entry unless it exists - the engine in upload's dry walk of the factor sequence (hqpkkt::listing), so an eager and
+// a captured run of a handle take the same schedule and nothing is allocated inside a captured sequence; without it
+// get() only finds, as at every launch.  hits: launches that looked the entry up since it was made (hqpkkt_debug_get 38)
+struct GemmCache {
+  struct Entry {
+    stg::GemmRequest rq;
+    stg::GemmSchedule s;
+    DBuf<stg::SkUnit> units;
+    DBuf<int> order;
+    int hits = 0;
+  };
+  std::vector<Entry> entries;
+  Entry *find(const stg::GemmRequest &rq) {
+    for (Entry &e : entries)
+      if (e.rq == rq) return &e;
+    return nullptr;
+  }
+  // the schedule of rq in *out: its entry; `local` where the schedule keeps nothing; a kept one without an entry is made
+  // if `create`, and is HQPKKT_E_INTERN otherwise - no reason to take another schedule.  So is a request no form takes
+  int get(const stg::GemmCaps &caps, const stg::GemmRequest &rq, bool create, Entry &local, Entry *&out) {
+    if ((out = find(rq))) return 0;
+    if (stg::gemm_schedule(caps, rq, local.s) != stg::GEMM_SCHED_OK) return HQPKKT_E_INTERN;
+    out = &local;
+    if (!local.s.kept()) return 0;
+    if (!create) return HQPKKT_E_INTERN;
+    local.rq = rq;
+    if ((!local.s.tab.units.empty() && local.units.upload(local.s.tab.units)) || (!local.s.order.empty() && local.order.upload(local.s.order))) return HQPKKT_E_MEM;
+    entries.push_back(std::move(local));
+    out = &entries.back();
+    return 0;
+  }
+};
+
 struct StagedDev {
   kktdev::StagedPlan plan;
   DBuf<double> F, V, misc;
@@ -60,14 +95,13 @@ struct StagedDev {
   std::vector<SymvGroup> symv_groups[2];
   std::vector<int> symv_rows_stage[2];
   DBuf<double> zeros;           // 256 zero doubles: the operand rows k >= K of the LDS-DMA staging (GemmArgs::zeros)
-  int gemm_variant = stg::GEMM_DMA8;
-  int cus = 0;
+  // The launches of the dense product (st_gemm): what the handle offers them (filled in one block of staged_upload) and
+  // their schedules with the work lists and tile orders on the device, made in upload's dry walk of the factor sequence
+  stg::GemmCaps caps;
+  GemmCache gemms;
   DBuf<double> ks_ws2;          // the pieces of a thin product cut in k (k_dgemm_tn_ks) launched on the SECOND stream
-  long long ks_ws2_elems = 0;
   DBuf<double> sk_ws;           // the cut forms of the dgemm: parked partial tiles (SkUnit::slot0)
   DBuf<unsigned> sk_cnt;
-  int sk_grid = 0;              // workgroups of the stream-K grid (2 per CU); 0: not used
-  int sk_tiles = 0;             // most tiles a product of this handle has (size of the counter array)
   // second stream: the control-sized chain of a stage (G_u strip, H's control part, carried rows, K^-1, Y, Rm)
   // runs beside the large product G_xx = fx'W_x instead of behind it (fork / join by events; inside a
   // captured sequence these are parallel branches of the graph)
@@ -79,109 +113,18 @@ struct StagedDev {
   // and -Rm (k_st_rm) of the stage in work
   std::vector<char> fused;
   DBuf<double> fv_nrm;
-  // order of the tiles of a lower-triangular product with T tile rows (GemmArgs::tile_map), by T
-  std::vector<std::pair<int, DBuf<int>>> tri_maps;
-  const int *tri_map(int T, bool create = false) {
-    for (auto &e : tri_maps)
-      if (e.first == T) return e.second.p;
-    if (!create) return nullptr;  // (made at upload time: no allocation inside a captured sequence)
-    const std::vector<int> m = stg::gemm_tri_order(T);
-    DBuf<int> b;
-    if (b.upload(m)) return nullptr;
-    tri_maps.emplace_back(T, std::move(b));
-    return tri_maps.back().second.p;
-  }
-  // work lists of the cut forms of the large products (sk_table.hpp), by (tiles, k-slabs, form): made at upload by a
-  // dry walk of the factor sequence itself (hqpkkt::listing), in which st_gemm makes the list of every cut form it would
-  // launch, and only looked up at launch, so an eager and a captured run of a handle take the same schedule.  list:
-  // which one stg::gemm_choose_list gave the shape; SK_LIST_NONE: no list fits the workspace - the launch is a plain
-  // round of whole tiles.  hits: launches that looked the list up since the upload (hqpkkt_debug_get 38)
-  struct SkTab {
-    long long tiles, nslab;
-    int form, list, stride, hits;
-    DBuf<stg::SkUnit> units;
-    DBuf<int> map;  // the lists of launches with the control-row segment (form + SK_TAB_CTRL): their tile order
-  };
-  static const int SK_TAB_CTRL = 100;
-  std::vector<SkTab> sk_tabs;
-  bool sk_tables_on = true;  // HQPKKT_SK_TABLE
-  SkTab *sk_tab(long long tiles, long long nslab, int form) {
-    for (auto &e : sk_tabs)
-      if (e.tiles == tiles && e.nslab == nslab && e.form == form) return &e;
-    return nullptr;
-  }
-  // the form the launch rule (gemm_form.hpp) gives a product of this handle
-  stg::GemmForm gemm_form(int M, int N, int K, int lower, int mirror, bool first_stream = true) const {
-    return stg::gemm_form(M, N, K, lower, mirror, cus, sk_grid, sk_tiles, sk_ws_elems, ks_ws2_elems,
-                          (plan.sharded ? stg::GEMM_SHARDED : 0) | (first_stream ? 0 : stg::GEMM_SECOND_STREAM));
-  }
-  // the list of a cut form f of nslab k-slabs, unless it exists
-  int sk_tab_prepare(const stg::GemmForm &f, long long nslab) {
-    if (sk_tab(f.tiles, nslab, f.kind)) return 0;
-    stg::SplitTable t;
-    SkTab e{f.tiles, nslab, f.kind, 0, 0, 0, {}, {}};
-    e.list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles, nslab, sk_grid, sk_tiles, sk_ws_elems, t);
-    if (e.list != stg::SK_LIST_NONE) {
-      if (int err = e.units.upload(t.units)) return err;
-      e.stride = t.stride;
-    }
-    sk_tabs.push_back(std::move(e));
-    return 0;
-  }
-  // ... and of a launch of form f with the control-row segment (stg::gemm_ctrl_rows_order): tiles + 1 logical tiles
-  // in the list the chooser gives that count, and the tile order that puts the last tile column first and the augmented
-  // row last.  list SK_LIST_NONE: no such list - the caller forms the control rows by a product of their own
-  int ctrl_tab_prepare(const stg::GemmForm &f, long long nslab, int tiles_m) {
-    if (sk_tab(f.tiles, nslab, f.kind + SK_TAB_CTRL)) return 0;
-    stg::SplitTable t;
-    std::vector<int> map;
-    SkTab e{f.tiles, nslab, f.kind + SK_TAB_CTRL, stg::SK_LIST_NONE, 0, 0, {}, {}};
-    const int list = stg::gemm_choose_list(f.kind == stg::GEMM_FORM_FRAC, sk_tables_on && !plan.sharded, f.tiles + 1, nslab, sk_grid, sk_tiles + 1, sk_ws_elems, t);
-    if (list != stg::SK_LIST_NONE && f.tiles + 1 <= sk_cnt_elems && stg::gemm_ctrl_rows_order(t, sk_grid, tiles_m, (int)(f.tiles / tiles_m), map)) {
-      if (int err = e.units.upload(t.units)) return err;
-      if (int err = e.map.upload(map)) return err;
-      e.list = list, e.stride = t.stride;
-    }
-    sk_tabs.push_back(std::move(e));
-    return 0;
-  }
   // words of the control-row segment (GemmArgs::ctl), and per stage whether its W launch takes the segment
   DBuf<unsigned> ctl;
   std::vector<char> ctrl_rows;
-  // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device, the partial sums of the solve's
-  // columns product (stg::pf_chunks x columns of the widest stage), and the work lists of its two large products
-  // (stg::gemm_profile_table) by shape and range vector: equal vectors share a list - a time-invariant pattern has one
-  // for W and one for G.  Made in upload's dry walk and only looked up at a launch, like sk_tabs
+  // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device and the partial sums of the
+  // solve's columns product (stg::pf_chunks x columns of the widest stage)
   DBuf<int> pf_rng;
   DBuf<double> pf_part;
   // packed panels (StagedPlan::packed): per panel of every stage its block for the kernels (offset from the stage's F
   // less 16 lo ld, leading dimension; indexed like pf_rng's pairs), and the partial sums of the carried rows (k_pk_carried)
   DBuf<stg::PackPanel> pk_tab;
   DBuf<double> pk_part;
-  struct PfTab {
-    int M, N, lower, by, stride, hits;
-    std::vector<int> panel;  // the ranged operand's panels, two ints each
-    DBuf<stg::SkUnit> units;
-  };
-  std::vector<PfTab> pf_tabs;
-  PfTab *pf_tab(int M, int N, int lower, int by, const int *panel, int npanel) {
-    for (auto &e : pf_tabs)
-      if (e.M == M && e.N == N && e.lower == lower && e.by == by && (int)e.panel.size() == 2 * npanel && std::equal(e.panel.begin(), e.panel.end(), panel))
-        return &e;
-    return nullptr;
-  }
-  int pf_tab_prepare(const stg::GemmForm &f, int M, int N, int lower, int by, const int *order, const int *panel, int npanel) {
-    if (pf_tab(M, N, lower, by, panel, npanel)) return 0;
-    const std::vector<int> r = stg::gemm_profile_tile_ranges(M, N, lower, order, panel, by);
-    stg::SplitTable t;
-    if (f.tiles > sk_cnt_elems - 4 || !stg::gemm_profile_table(r.data(), f.tiles, sk_grid, t) || t.pieces * 128LL * 128 > sk_ws_elems) return HQPKKT_E_INTERN;
-    PfTab e{M, N, lower, by, t.stride, 0, std::vector<int>(panel, panel + 2 * npanel), {}};
-    if (int err = e.units.upload(t.units)) return err;
-    pf_tabs.push_back(std::move(e));
-    return 0;
-  }
   size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
-  long long sk_ws_elems = 0, sk_cnt_elems = 0;
 };
 
 namespace {
@@ -261,75 +204,46 @@ inline stg::GemmArgs staged_w_args(StagedDev &d, int k, bool seg) {
   return g;
 }
 
-// C = alpha A'B + beta Cin on the handle's stream, in the form the launch rule gives the shape (gemm_form.hpp)
-// (allow_sk false: launches of the second stream).  ntiles > 0: the tiles g.tile_map[0 .. ntiles) of the product only
-// (128 x 128 tiles; the blocks of G_xx one rank owns)
-int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true, int ntiles = 0) {
+// V_k = F_x'W_x - Y'Rm of a fused stage k as one launch (lower tiles, mirrored): the rank-q update as a second k segment
+inline stg::GemmArgs staged_v_args(StagedDev &d, int k) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagePtr sp = stage_ptr(d, k);
+  const int nn = P.nk[k];
+  const long long ldf = P.ldf[k], ldy = P.ldy[k];
+  stg::GemmArgs g{sp.F, ldf, d.misc.p + P.oW, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, P.nk[k + 1], 1.0, 0.0, 1, 1};
+  g.A2 = sp.Y, g.lda2 = ldy, g.B2 = d.fv_nrm.p, g.ldb2 = ldy, g.K2 = P.qmax[k];
+  return g;
+}
+
+// C = alpha A'B + beta Cin on the handle's stream by the schedule of its request (gemm_schedule.hpp): made in upload's dry
+// walk, where nothing is launched, and only found at a launch.  allow_sk false: launches of the second stream.
+// ntiles > 0: the tiles g.tile_map[0 .. ntiles) of the product only (128 x 128 tiles; the blocks of G_xx one rank owns).
+// by 1 / 2: the profile form (GEMM_FORM_PROFILE) - every tile over the k-slabs of its panel of the ranged operand alone,
+// `panel`: the stage's ranges (host) of B's column panels (W = V+ F) / of A's (G = F'W), `pack`: that operand's packed
+// panels or null
+int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = true, int ntiles = 0, int by = 0, const int *panel = nullptr,
+            const stg::PackPanel *pack = nullptr) {
   if (g.M <= 0 || g.N <= 0) return 0;
   if (g.apack || g.bpack) return HQPKKT_E_INTERN;  // (packed panels: the profile form's launches alone)
   StagedDev &d = *h->sd;
-  // (a launch with a second k segment counts as one of the depth of both: a multiple of the slab)
-  const long long nslab = stg::gemm_slabs(g.K) + (g.K2 > 0 ? stg::gemm_slabs(g.K2) : 0);
-  const int Kf = g.K2 > 0 ? (int)(nslab * stg::GEMM_BK) : g.K;
-  const stg::GemmForm f = ntiles ? stg::gemm_form_tiles(ntiles, Kf, d.sk_grid, d.sk_tiles) : d.gemm_form(g.M, g.N, Kf, g.lower, g.mirror, allow_sk);
-  if (f.kind == stg::GEMM_FORM_NONE) return HQPKKT_E_INTERN;
-  if (f.tile_map) g.tile_map = d.tri_map((g.M + 127) / 128);
-  // operands by LDS-DMA only from 16-byte aligned rows; the others are staged through registers
-  if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
-  // (the second segment exists in the 128 x 128 LDS-DMA kernels alone: StagedDev::fused holds only stages that get them)
-  if (g.K2 > 0 && !(g.zeros && (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT || f.kind == stg::GEMM_FORM_PLAIN))) return HQPKKT_E_INTERN;
+  const stg::GemmRequest rq = stg::gemm_request(g, !allow_sk, ntiles, by, panel);
+  GemmCache::Entry local, *e;
+  if (int err = d.gemms.get(d.caps, rq, h->listing, local, e)) return err;
   // (the control-row segment: only where the upload found the launch a list, StagedDev::ctrl_rows)
-  const bool seg = g.Au != nullptr;
-  if (seg && !((f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT) && stg::gemm_ctrl_rows_ok(g, stg::gemm_variant_for(g, d.gemm_variant))))
-    return HQPKKT_E_INTERN;
-  if (h->listing) {  // upload's dry walk: what this launch will look up is made, nothing is launched
-    if (f.tile_map && !d.tri_map((g.M + 127) / 128, true)) return HQPKKT_E_MEM;
-    if (seg) return d.ctrl_tab_prepare(f, nslab, (g.M + 127) / 128);
-    return f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT ? d.sk_tab_prepare(f, nslab) : 0;
-  }
-  // (the arrival counters of the cut forms are zero between launches: the last arriver of a tile resets its)
-  stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, nullptr, 0};
-  stg::GemmLaunch L{stg::gemm_variant_for(g, d.gemm_variant), d.cus, d.sk_grid, nullptr, allow_sk ? d.sk_ws.p : d.ks_ws2.p};
-  if (f.kind == stg::GEMM_FORM_FRAC || f.kind == stg::GEMM_FORM_CUT) {
-    // the list the shape was given at upload.  A shape without one is no reason to take another schedule; a list of
-    // SK_LIST_NONE - the workspace holds no list's pieces - is a plain round
-    StagedDev::SkTab *tab = d.sk_tab(f.tiles, nslab, f.kind + (seg ? StagedDev::SK_TAB_CTRL : 0));
-    if (!tab || (seg && tab->list == stg::SK_LIST_NONE)) return HQPKKT_E_INTERN;
-    tab->hits++;
-    if (seg) g.tile_map = tab->map.p;
-    if (tab->list != stg::SK_LIST_NONE) sk.table = tab->units.p, sk.stride = tab->stride, L.sk = &sk;
-  }
-  stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
+  if (g.Au && !e->s.seg) return HQPKKT_E_INTERN;
+  if (h->listing) return 0;
+  e->hits++;
+  (by == 2 ? g.apack : g.bpack) = pack;
+  const stg::GemmBufs bufs{e->units.p, e->order.p, d.sk_ws.p, d.sk_cnt.p, allow_sk ? d.sk_ws.p : d.ks_ws2.p, d.zeros.p};
+  stg::gemm_run(e->s, d.caps, bufs, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
   return 0;
 }
-
-// The same product in the profile form (gemm_form.hpp, GEMM_FORM_PROFILE): always k_dgemm_tn_sk on 128 x 128 tiles, every
-// tile over the k-slabs of its panel of the ranged operand alone - `panel`: stage k's ranges (host), by = 1: B's column
-// panels (W = V+ F), 2: A's (G = F'W).  The list is made in upload's dry walk and looked up here
-int st_gemm_profile(hqpkkt_t *h, stg::GemmArgs g, int k, int by, int cls = KC_ST_GEMM) {
+// ... of stage k in the profile form
+int st_gemm_profile(hqpkkt_t *h, const stg::GemmArgs &g, int k, int by, int cls = KC_ST_GEMM) {
+  const kktdev::StagedPlan &P = h->sd->plan;
   if (g.M <= 0 || g.N <= 0) return 0;
-  StagedDev &d = *h->sd;
-  const kktdev::StagedPlan &P = d.plan;
-  const int *panel = P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], npanel = P.panels(k);
-  const stg::GemmForm f = stg::gemm_form_profile(g.M, g.N, g.lower);
-  if (f.kind != stg::GEMM_FORM_PROFILE || d.sk_grid <= 0 || npanel != ((by == 2 ? g.M : g.N) + 127) / 128) return HQPKKT_E_INTERN;
-  if (h->listing) {
-    const int T = (g.M + 127) / 128;
-    if (f.tile_map && !d.tri_map(T, true)) return HQPKKT_E_MEM;
-    std::vector<int> order;
-    if (f.tile_map) order = stg::gemm_tri_order(T);
-    return d.pf_tab_prepare(f, g.M, g.N, g.lower, by, f.tile_map ? order.data() : nullptr, panel, npanel);
-  }
-  if (f.tile_map && !(g.tile_map = d.tri_map((g.M + 127) / 128))) return HQPKKT_E_INTERN;
-  if (d.zeros.p && stg::gemm_operands_dma_ok(g)) g.zeros = d.zeros.p;
-  if (P.pk_stage(k)) (by == 2 ? g.apack : g.bpack) = d.pk_tab.p + P.pf_ptr[k];  // (the ranged operand: F_k's packed panels)
-  StagedDev::PfTab *tab = d.pf_tab(g.M, g.N, g.lower, by, panel, npanel);
-  if (!tab) return HQPKKT_E_INTERN;
-  tab->hits++;
-  const stg::SplitPlan sk{d.sk_ws.p, d.sk_cnt.p, tab->units.p, tab->stride};
-  const stg::GemmLaunch L{stg::gemm_variant_for(g, d.gemm_variant), d.cus, d.sk_grid, &sk, nullptr};
-  stg::gemm_launch_form(f, L, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
-  return 0;
+  if (P.panels(k) != ((by == 2 ? g.M : g.N) + 127) / 128) return HQPKKT_E_INTERN;
+  return st_gemm(h, g, cls, true, 0, by, P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.pk_stage(k) ? h->sd->pk_tab.p + P.pf_ptr[k] : nullptr);
 }
 
 int st_gemv_rows(hqpkkt_t *h, stg::GemvRows g) {
@@ -774,102 +688,10 @@ static int staged_upload(hqpkkt_t *h) {
       if ((e = d.dyn_part.alloc((size_t)std::max(P.ndyn, 1) * d.dyn_part_cols))) return e;
     }
   }
-  d.gemm_variant = stg::gemm_variant_from_env();
-  if (d.gemm_variant != stg::GEMM_REG4) {  // (the register-staged loop stays selectable for comparisons)
-    if ((e = d.zeros.alloc(256))) return e;
-    HIPCHK(hipMemset(d.zeros.p, 0, sizeof(double) * 256));
-  } else
-    d.zeros.release();
   HIPCHK(hipMemset(d.F.p, 0, sizeof(double) * std::max<long long>(P.f_elems, 1)));
   HIPCHK(hipMemset(d.V.p, 0, sizeof(double) * std::max<long long>(P.v_elems, 1)));
   HIPCHK(hipMemset(d.misc.p, 0, sizeof(double) * std::max<long long>(P.misc_elems, 1)));
   HIPCHK(hipMemset(d.dyn.p, 0, sizeof(int) * std::max(P.dyn_ints, 1)));
-  {  // stream-K grid: two workgroups per CU, if some product of the recursion has more tiles than that
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
-    d.cus = cus;
-    long long tmax = 0, pmax = 0;  // most tiles / most cut pieces of a product of this handle (column slices have fewer)
-    for (int k = 0; k < P.K; k++) {
-      const long long t1 = (P.nk[k + 1] + 127) / 128, t2 = (P.nk[k] + P.mk[k] + 127) / 128;
-      tmax = std::max(tmax, t1 * t2);
-      if (cus > 0)
-        for (long long t : {t1 * t2, t2 * (t2 + 1) / 2, t1 * (t1 + 1) / 2})
-          for (int grid : {2 * cus, cus})
-            pmax = std::max(pmax, stg::gemm_split_plan_pieces(stg::gemm_split_plan(t, (std::max(P.nk[k + 1], P.nk[k]) + stg::GEMM_BK - 1) / stg::GEMM_BK, grid)));
-    }
-    if (P.sharded)
-      for (int k = 0; k < P.K; k++) tmax = std::max<long long>(tmax, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
-    // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every list
-    // is checked against the workspace when it is made, gemm_choose_list.  Until round 5 the workspace was sized 16
-    // pieces per tile of the largest product - 3.4 GB at the headline width, per handle, sharded or not)
-    pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
-    d.sk_grid = 0, d.sk_tiles = (int)tmax;
-    if (cus > 0) {
-      d.sk_grid = stg::gemm_wgs_per_cu(d.gemm_variant) * cus;
-      // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
-      d.sk_ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
-      d.sk_cnt_elems = d.sk_tiles + 4;
-      // (the profile form's lists: a counter per tile of W and of the whole lower block G, at most two parked tiles per
-      // workgroup - 2 x grid slots, which the workspace above holds: pmax >= 4 cus + 64)
-      for (int k = 0; k < P.K && P.profile_dyn; k++)
-        if (P.pf_stage[k]) {
-          const long long t2 = (P.nk[k] + P.mk[k] + 127) / 128;
-          d.sk_cnt_elems = std::max(d.sk_cnt_elems, t2 * (t2 + 1) / 2 + 4);
-        }
-      if ((e = d.sk_ws.alloc((size_t)d.sk_ws_elems)) || (e = d.sk_cnt.alloc((size_t)d.sk_cnt_elems))) return e;
-      HIPCHK(hipMemset(d.sk_cnt.p, 0, sizeof(unsigned) * (size_t)d.sk_cnt_elems));
-    }
-  }
-  // Which stages form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can
-  // (the tests), unset: those whose W launch also delivers the control rows of G (StagedDev::ctrl_rows: the control-row
-  // segment, staged_w_args) and whose width is not one of those that run the chain beside G_xx (overlap_mode) - with
-  // the thin product for the control rows the sequence only takes as long as the one with the separate update
-  // (profiles/r08_stage_order.txt).  A stage can when its K has order 1 .. 64 (k_st_rm
-  // writes -Rm), its control columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA
-  {
-    d.ctl.release();
-    if ((e = d.ctl.alloc(8))) return e;
-    HIPCHK(hipMemset(d.ctl.p, 0, sizeof(unsigned) * 8));
-    d.ctrl_rows.assign(P.K + 1, 0);
-    const char *fv = getenv("HQPKKT_FUSED_V");
-    const int mode = fv ? atoi(fv) : 2;
-    d.fused.assign(P.K + 1, 0);
-    long long nrm = 0;
-    if (mode != 0 && !P.sharded && !P.sparse_dyn && d.zeros.p)
-      for (int k = 0; k < P.K; k++) {
-        const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
-        if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
-        if (P.wide_count(k)) continue;                  // (the wide rows' product goes into the work block G)
-        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0) continue;
-        const long long nslab = stg::gemm_slabs(np) + stg::gemm_slabs(q);
-        const stg::GemmForm f = d.gemm_form(nn, nn, (int)(nslab * stg::GEMM_BK), 1, 1);
-        if (f.kind != stg::GEMM_FORM_FRAC && f.kind != stg::GEMM_FORM_CUT && f.kind != stg::GEMM_FORM_PLAIN) continue;
-        // the control rows of G out of the W launch: a cut form with a list in the segment's order, and the guarded
-        // product behind it one cut in k (the kernels that know the guard)
-        {
-          stg::GemmArgs gw = staged_w_args(d, k, true);
-          gw.zeros = stg::gemm_operands_dma_ok(gw) ? d.zeros.p : nullptr;
-          const stg::GemmForm fw = d.gemm_form(gw.M, gw.N, gw.K, 0, 0), ft = d.gemm_form(P.mk[k], nn + P.mk[k], np, 0, 0);
-          if ((fw.kind == stg::GEMM_FORM_FRAC || fw.kind == stg::GEMM_FORM_CUT) && ft.kind == stg::GEMM_FORM_KS &&
-              stg::gemm_ctrl_rows_ok(gw, stg::gemm_variant_for(gw, d.gemm_variant))) {
-            if ((e = d.ctrl_tab_prepare(fw, stg::gemm_slabs(gw.K), (gw.M + 127) / 128))) return e;
-            const StagedDev::SkTab *tab = d.sk_tab(fw.tiles, stg::gemm_slabs(gw.K), fw.kind + StagedDev::SK_TAB_CTRL);
-            d.ctrl_rows[k] = tab && tab->list != stg::SK_LIST_NONE;
-          }
-        }
-        if (mode != 1 && (!d.ctrl_rows[k] || (nn >= 1280 && nn <= 4096))) {
-          d.ctrl_rows[k] = 0;
-          continue;
-        }
-        d.fused[k] = 1;
-        nrm = std::max(nrm, (long long)q * P.ldy[k]);
-      }
-    d.fv_nrm.release();
-    if (nrm > 0) {  // (slack: the operand loads of the last tile column read a tile's width past a row)
-      if ((e = d.fv_nrm.alloc((size_t)nrm + 8192))) return e;
-      HIPCHK(hipMemset(d.fv_nrm.p, 0, sizeof(double) * ((size_t)nrm + 8192)));
-    }
-  }
   // The control-sized chain of a stage on a second stream beside its large product G_xx.  Measured on one MI355X (same
   // box, tools/c4_bench.py): stages of 1500 / 2000 / 2500 / 3000 states + 2.7 / 2.5 / 3.5 / 2.7 %, 5000 states - 1.1 % (the
   // separate skinny product for the control rows of G and the contention cost more than the hidden chain), 1000 states
@@ -892,10 +714,106 @@ static int staged_upload(hqpkkt_t *h) {
       HIPCHK(hipEventCreateWithFlags(&d.ev_join.h, hipEventDisableTiming));
     }
     d.overlap = d.stream2 != nullptr && d.overlap_mode != 0 && !P.sparse_dyn;
-    d.ks_ws2_elems = 0;
-    if (d.stream2 && d.cus > 0) {
-      d.ks_ws2_elems = 8LL << 20;
-      if ((e = d.ks_ws2.alloc((size_t)d.ks_ws2_elems))) return e;
+  }
+  {  // What the handle offers the launches of the dense product (stg::GemmCaps) - all of it here
+    stg::GemmCaps &c = d.caps;
+    c = stg::GemmCaps{};
+    c.variant = stg::gemm_variant_from_env();
+    if (c.variant != stg::GEMM_REG4) {  // (the register-staged loop stays selectable for comparisons)
+      if ((e = d.zeros.alloc(256))) return e;
+      HIPCHK(hipMemset(d.zeros.p, 0, sizeof(double) * 256));
+    } else
+      d.zeros.release();
+    c.unequal = stg::gemm_sk_table_from_env() && !P.sharded;
+    c.flags = P.sharded ? stg::GEMM_SHARDED : 0;
+    // stream-K grid: two workgroups per CU, if some product of the recursion has more tiles than that
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+    c.cus = cus;
+    long long tmax = 0, pmax = 0;  // most tiles / most cut pieces of a product of this handle (column slices have fewer)
+    for (int k = 0; k < P.K; k++) {
+      const long long t1 = (P.nk[k + 1] + 127) / 128, t2 = (P.nk[k] + P.mk[k] + 127) / 128;
+      tmax = std::max(tmax, t1 * t2);
+      if (cus > 0)
+        for (long long t : {t1 * t2, t2 * (t2 + 1) / 2, t1 * (t1 + 1) / 2})
+          for (int grid : {2 * cus, cus})
+            pmax = std::max(pmax, stg::gemm_split_plan_pieces(stg::gemm_split_plan(t, (std::max(P.nk[k + 1], P.nk[k]) + stg::GEMM_BK - 1) / stg::GEMM_BK, grid)));
+    }
+    if (P.sharded)
+      for (int k = 0; k < P.K; k++) tmax = std::max<long long>(tmax, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
+    // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every list
+    // is checked against the workspace when it is made, gemm_choose_list.  Until round 5 the workspace was sized 16
+    // pieces per tile of the largest product - 3.4 GB at the headline width, per handle, sharded or not)
+    pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
+    c.sk_tiles = (int)tmax;
+    if (cus > 0) {
+      c.grid = stg::gemm_wgs_per_cu(c.variant) * cus;
+      // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
+      c.ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
+      c.cnt_elems = c.sk_tiles + 4;
+      // (the profile form's lists: a counter per tile of W and of the whole lower block G, at most two parked tiles per
+      // workgroup - 2 x grid slots, which the workspace above holds: pmax >= 4 cus + 64)
+      for (int k = 0; k < P.K && P.profile_dyn; k++)
+        if (P.pf_stage[k]) {
+          const long long t2 = (P.nk[k] + P.mk[k] + 127) / 128;
+          c.cnt_elems = std::max(c.cnt_elems, t2 * (t2 + 1) / 2 + 4);
+        }
+      if ((e = d.sk_ws.alloc((size_t)c.ws_elems)) || (e = d.sk_cnt.alloc((size_t)c.cnt_elems))) return e;
+      HIPCHK(hipMemset(d.sk_cnt.p, 0, sizeof(unsigned) * (size_t)c.cnt_elems));
+      if (d.stream2) {  // (the second stream's products cut in k)
+        c.ws2_elems = 8LL << 20;
+        if ((e = d.ks_ws2.alloc((size_t)c.ws2_elems))) return e;
+      }
+    }
+  }
+  // Which stages form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can
+  // (the tests), unset: those whose W launch also delivers the control rows of G (StagedDev::ctrl_rows: the control-row
+  // segment, staged_w_args) and whose width is not one of those that run the chain beside G_xx (overlap_mode) - with
+  // the thin product for the control rows the sequence only takes as long as the one with the separate update
+  // (profiles/r08_stage_order.txt).  A stage can when its K has order 1 .. 64 (k_st_rm
+  // writes -Rm), its control columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA
+  {
+    d.ctl.release();
+    if ((e = d.ctl.alloc(8))) return e;
+    HIPCHK(hipMemset(d.ctl.p, 0, sizeof(unsigned) * 8));
+    d.ctrl_rows.assign(P.K + 1, 0);
+    const char *fv = getenv("HQPKKT_FUSED_V");
+    const int mode = fv ? atoi(fv) : 2;
+    d.fused.assign(P.K + 1, 0);
+    long long nrm = 0;
+    // the schedule of a stage's launch, asked of the launches' own rule (form NONE: refused); equal requests - the stages
+    // of a time-invariant system - are answered once.  Nothing is kept: the dry walk below makes what the launches look up
+    std::vector<std::pair<stg::GemmRequest, stg::GemmSchedule>> asked;
+    auto ask = [&](const stg::GemmRequest &rq) -> const stg::GemmSchedule & {
+      for (const auto &a : asked)
+        if (a.first == rq) return a.second;
+      asked.emplace_back(rq, stg::GemmSchedule{});
+      if (stg::gemm_schedule(d.caps, rq, asked.back().second)) asked.back().second = stg::GemmSchedule{};
+      return asked.back().second;
+    };
+    if (mode != 0 && !P.sharded && !P.sparse_dyn && d.zeros.p)
+      for (int k = 0; k < P.K; k++) {
+        const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
+        if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
+        if (P.wide_count(k)) continue;                  // (the wide rows' product goes into the work block G)
+        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0) continue;
+        stg::GemmRequest rt;  // the thin product for the control rows of G behind the W launch
+        rt.M = P.mk[k], rt.N = nn + P.mk[k], rt.K = np;
+        if (ask(stg::gemm_request(staged_v_args(d, k))).f.kind == stg::GEMM_FORM_NONE) continue;
+        // the control rows of G out of the W launch: a cut form with a list in the segment's order, and the guarded
+        // product behind it one cut in k (the kernels that know the guard)
+        d.ctrl_rows[k] = ask(rt).f.kind == stg::GEMM_FORM_KS && ask(stg::gemm_request(staged_w_args(d, k, true))).seg;
+        if (mode != 1 && (!d.ctrl_rows[k] || (nn >= 1280 && nn <= 4096))) {
+          d.ctrl_rows[k] = 0;
+          continue;
+        }
+        d.fused[k] = 1;
+        nrm = std::max(nrm, (long long)q * P.ldy[k]);
+      }
+    d.fv_nrm.release();
+    if (nrm > 0) {  // (slack: the operand loads of the last tile column read a tile's width past a row)
+      if ((e = d.fv_nrm.alloc((size_t)nrm + 8192))) return e;
+      HIPCHK(hipMemset(d.fv_nrm.p, 0, sizeof(double) * ((size_t)nrm + 8192)));
     }
   }
   if (P.sharded) {
@@ -967,9 +885,8 @@ static int staged_upload(hqpkkt_t *h) {
   }
   // The work lists of the recursion's cut products and the tile orders of its triangular ones (G, V): a dry walk of the
   // factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
-  d.sk_tables_on = stg::gemm_sk_table_from_env();
-  d.sk_tabs.clear();
-  d.pf_tabs.clear(), d.pf_rng.release(), d.pf_part.release(), d.pk_tab.release(), d.pk_part.release();
+  d.gemms.entries.clear();
+  d.pf_rng.release(), d.pf_part.release(), d.pk_tab.release(), d.pk_part.release();
   if (P.profile_dyn && !P.pf_rng.empty()) {
     long long part = 1;
     for (int k = 0; k < P.K; k++)
@@ -996,8 +913,8 @@ static int staged_upload(hqpkkt_t *h) {
     h->listing = true;
     if ((e = staged_run_factor(h, nullptr, nullptr))) return e;
     if (getenv("HQPKKT_TIMING"))
-      fprintf(stderr, "staged_upload: listing walk over %d stages %.3f ms (%zu work lists, %zu tile orders)\n", P.K,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), d.sk_tabs.size(), d.tri_maps.size());
+      fprintf(stderr, "staged_upload: listing walk over %d stages %.3f ms (%zu schedules with a work list or a tile order)\n", P.K,
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), d.gemms.entries.size());
   }
   d.lds_small = 0, d.lds_small_big = 0;
   for (int k = 0; k < P.K; k++) {
@@ -1230,8 +1147,8 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
   StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
-  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm, q = P.qmax[k];
-  const long long ldf = P.ldf[k], ldg = P.ldg[k], ldy = P.ldy[k];
+  const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
+  const long long ldf = P.ldf[k], ldg = P.ldg[k];
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW, *nRm = d.fv_nrm.p;
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
   int e;
@@ -1246,9 +1163,7 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
   // V = F_x'W_x - Y'Rm (lower tiles, mirrored), then H_xx into the entry and its image
-  stg::GemmArgs g{sp.F, ldf, W, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, np, 1.0, 0.0, 1, 1};
-  g.A2 = sp.Y, g.lda2 = ldy, g.B2 = nRm, g.ldb2 = ldy, g.K2 = q;
-  if ((e = st_gemm(h, g))) return e;
+  if ((e = st_gemm(h, staged_v_args(d, k)))) return e;
   st_add_q(h, d, k, 0, nn, nn, 0, sp.V, P.ldv[k]);  // (the whole of Q_xx, which is its own image bit for bit)
   if (ne_x)
     KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,

@@ -785,6 +785,54 @@ def gemm_form(M, N, K, lower=False, mirror=False, cus=256, grid=512, sk_tiles=1 
     return (GEMM_FORMS[kind] if kind >= 0 else None), tiles.value, bool(table.value), bool(tmap.value), nsplit.value
 
 
+SK_LISTS = {-1: None, 0: "unequal", 1: "equal", 2: "frac", 3: "profile"}
+
+
+def gemm_caps(cus=256, grid=512, sk_tiles=1 << 30, cnt_elems=None, ws_elems=1 << 40, ws2_elems=8 << 20, variant=2, unequal=True,
+              sharded=False, no_ks=False, no_tile_map=False, force_split=False):
+    """What the holder of a launch offers :func:`gemm_schedule` (hqpkkt_gemm_caps); cnt_elems None: sk_tiles + 4."""
+    return _lib.GemmCaps(variant, cus, grid, int(unequal), sharded * 1 | no_ks * 8 | no_tile_map * 16 | force_split * 32,
+                         sk_tiles, sk_tiles + 4 if cnt_elems is None else cnt_elems, ws_elems, ws2_elems)
+
+
+def gemm_launch(M, N, K, K2=0, lower=False, mirror=False, second_stream=False, ntiles=0, a=0x1000, lda=None, b=0x2000, ldb=None,
+                a2=0, lda2=0, b2=0, ldb2=0, mu=0, c=0x4000, ldc=None, c0=None, by=0, panel=None):
+    """A launch of the fp64 product described by numbers (hqpkkt_gemm_launch): the addresses are never read.  Defaults: aligned
+    operands with even leading dimensions; the segment's columns are the last mu of C."""
+    import numpy as np
+    up8 = lambda x: (x + 7) // 8 * 8
+    ldc = up8(N) if ldc is None else ldc
+    l = _lib.GemmLaunch(M, N, K, K2, int(lower), int(mirror), int(second_stream), ntiles, a, b, a2, b2, c,
+                        up8(M) if lda is None else lda, up8(N) if ldb is None else ldb, lda2, ldb2, ldc, N - mu if c0 is None else c0, mu, by, None)
+    if by:
+        l._panel = np.ascontiguousarray(panel, dtype=np.int32).reshape(-1)  # (kept alive with the structure)
+        l.panel = l._panel.ctypes.data
+    return l
+
+
+def gemm_schedule(caps, launch, other=None):
+    """The schedule of one launch of the STAGED engine's fp64 product (host only, hqpkkt_debug_gemm_schedule): (status, dict)
+    with status 0, 1 (no form takes the launch) or 2 (the profile form's list does not fit); the dict holds form, tiles,
+    nslab, nsplit, variant, list (None: a plain round), stride, pieces, seg, units[grid, stride, 6] or None, order (int32
+    array or None: the kernel's own) and, with `other`, same_key: the two launches share a schedule."""
+    import numpy as np
+    out = _lib.GemmScheduleOut()
+    op = None if other is None else C.byref(other)
+    st = _lib.lib().hqpkkt_debug_gemm_schedule(C.byref(caps), C.byref(launch), op, C.byref(out), None, 0, None, 0)
+    assert st >= 0
+    units = order = None
+    if st == 0 and (out.stride > 0 or out.order_len > 0):
+        units = np.zeros((caps.grid if out.stride > 0 else 0, out.stride, 6), dtype=np.int32)
+        order = np.zeros(out.order_len, dtype=np.int32)
+        got = _lib.lib().hqpkkt_debug_gemm_schedule(C.byref(caps), C.byref(launch), op, C.byref(out), units.ctypes.data_as(C.POINTER(C.c_int)), units.size,
+                                                    order.ctypes.data_as(C.POINTER(C.c_int)), order.size)
+        assert got == 0
+    d = {k: getattr(out, k) for k in ("nsplit", "variant", "stride", "tiles", "nslab", "pieces")}
+    d.update(form=(GEMM_FORMS + ("profile",))[out.form] if out.form >= 0 else None, list=SK_LISTS[out.list], seg=bool(out.seg),
+             same_key=bool(out.same_key), units=units if out.stride > 0 else None, order=order if out.order_len > 0 else None)
+    return st, d
+
+
 def selftest_mfma(device=0):
     err = C.c_double()
     _check(_lib.lib().hqpkkt_selftest_mfma(device, C.byref(err)), "selftest_mfma")

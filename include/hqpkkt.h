@@ -573,6 +573,40 @@ int hqpkkt_debug_carried_packed(int device, int K, int N, int R, const double *B
 int hqpkkt_debug_gemm_form(int M, int N, int K, int lower, int mirror, int cus, int grid, long long sk_tiles, long long ws_elems,
                            long long ws2_elems, int flags, long long *tiles, int *table, int *tile_map, int *nsplit);
 
+/* Test hook, host only: the schedule of ONE launch of that product (gemm_schedule.hpp) - what the engine's launches and
+ * the hooks hqpkkt_debug_dgemm* look up and run - for what a holder offers (caps) and a launch described by numbers.
+ * caps: the 128 x 128 variant (0 register-staged, 1 / 2 LDS-DMA on 4 / 8 waves), CUs, workgroups of the cut forms,
+ * tiles the rule may give a cut form, size of the arrival counters' array, workspaces of the first / second stream in
+ * doubles, whether unequal shares are allowed, hqpkkt_debug_gemm_form's flags 1, 8, 16, 32.
+ * launch: the shape; second_stream; ntiles > 0: that many 128 x 128 tiles out of the caller's list; the operands'
+ * addresses and leading dimensions (a, lda, ...: never read - they decide whether the operands may be staged by
+ * LDS-DMA); mu > 0: the control-row segment for the columns [c0, c0 + mu) of C (address c, leading dimension ldc);
+ * panel with by 1 / 2: the profile form, (lo, hi) k-slabs per 128-column panel of B / of A.
+ * other (or NULL): a second launch; out->same_key says whether the two share a schedule (the cache key's equality).
+ * out: form (hqpkkt_debug_gemm_form's numbering, 6 profile), nsplit, the variant launched, list (-1 none - a plain round
+ * -, 0 unequal, 1 equal, 2 fractional, 3 profile), its stride and parked pieces, segment taken, tiles, k-slabs per tile,
+ * length of the tile order (0: the kernel's own).  units (or NULL; six ints per unit as hqpkkt_debug_sk_table's, grid x
+ * stride of them) and order (or NULL; tile row << 16 | tile column, bit 31: the augmented form).
+ * Returns 0; 1: no form takes the launch; 2: the profile form's list does not fit the counters or the workspace; -1: a
+ * NULL argument, or units / order too small. */
+typedef struct hqpkkt_gemm_caps {
+  int variant, cus, grid, unequal, flags;
+  long long sk_tiles, cnt_elems, ws_elems, ws2_elems;
+} hqpkkt_gemm_caps;
+typedef struct hqpkkt_gemm_launch {
+  int M, N, K, K2, lower, mirror, second_stream, ntiles;
+  unsigned long long a, b, a2, b2, c;
+  long long lda, ldb, lda2, ldb2, ldc, c0;
+  int mu, by;
+  const int *panel;
+} hqpkkt_gemm_launch;
+typedef struct hqpkkt_gemm_schedule_out {
+  int form, nsplit, variant, list, stride, seg, same_key;
+  long long tiles, nslab, pieces, order_len;
+} hqpkkt_gemm_schedule_out;
+int hqpkkt_debug_gemm_schedule(const hqpkkt_gemm_caps *caps, const hqpkkt_gemm_launch *launch, const hqpkkt_gemm_launch *other,
+                               hqpkkt_gemm_schedule_out *out, int *units, long long cap_ints, int *order, long long cap_order);
+
 /* Per-kernel-class device timing for bench.py's roofline line: with on != 0
  * every kernel launch is bracketed by HIP events on the handle's stream and the
  * elapsed times are summed per class (hqpkkt_profile_class_name(c), c = 0..) at

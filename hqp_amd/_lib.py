@@ -37,6 +37,7 @@ SYMBOLS = [
     "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
     "hqpkkt_debug_gemm_schedule",
+    "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -101,6 +102,14 @@ class CtrlRowsCase(C.Structure):
                 ("C", C.c_void_p), ("c_rows", C.c_longlong), ("ldc", C.c_longlong),
                 ("Cu", C.c_void_p), ("cu_rows", C.c_longlong), ("ldcu", C.c_longlong),
                 ("taken", C.c_int), ("fallbacks", C.c_int), ("form", C.c_int), ("tiles", C.c_longlong)]
+
+
+class GemvCase(C.Structure):
+    """hqpkkt_gemv_case (include/hqpkkt.h)"""
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("A", DgemmOperand), ("A2", DgemmOperand), ("n2", C.c_int), ("part_chunks", C.c_int),
+                ("x", C.c_void_p), ("x_len", C.c_longlong), ("x2", C.c_void_p), ("x2_len", C.c_longlong), ("add", C.c_void_p), ("add2", C.c_void_p),
+                ("scale", C.c_double), ("y", C.c_void_p), ("y2", C.c_void_p), ("xoff", C.c_longlong), ("yoff", C.c_longlong),
+                ("chunks", C.c_int), ("vec16", C.c_int)]
 
 
 class GemmCaps(C.Structure):
@@ -211,6 +220,11 @@ def lib():
     L.hqpkkt_debug_gemm_form.argtypes = [C.c_int] * 7 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3
     L.hqpkkt_debug_gemm_schedule.argtypes = [C.POINTER(GemmCaps), C.POINTER(GemmLaunch), C.POINTER(GemmLaunch), C.POINTER(GemmScheduleOut),
                                              C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_int), C.c_longlong]
+    L.hqpkkt_debug_gemv_dense.argtypes = [C.c_int, C.c_int, C.POINTER(GemvCase)]
+    L.hqpkkt_debug_symv.argtypes = [C.c_int, C.POINTER(GemvCase)]
+    L.hqpkkt_debug_symv_batch.argtypes = [C.c_int, C.c_int, C.POINTER(GemvCase), vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_int]
+    L.hqpkkt_debug_symv_map.restype = C.c_longlong
+    L.hqpkkt_debug_symv_map.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_longlong]
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_debug_factor_block.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 7
     _lib = L

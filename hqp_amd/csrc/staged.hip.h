@@ -1383,14 +1383,21 @@ struct SymvArgs {
 // (measured on the 5000 x 5000 V of the headline, tools/symv_probe.hip: 22.8 us for the 113 MB of the triangle's tiles
 // against 37.1 us for the rows form over the whole matrix; tiles of 64 x 256, 32 x 512, 96 x 512, 128 x 512 and 2 / 8
 // rows in flight: 22.2 - 32 us; the row sums by DPP, 1 us less than by ds_bpermute)
-__device__ __forceinline__ void symv_tile(const SymvArgs &g, const int t, double (*red)[SV_C]) {
-  // tile number -> (row tile bi, column tile bj) over the tiles on and below the diagonal: the RT = SV_C / SV_R row tiles
-  // RT g .. RT g + RT - 1 have g + 1 column tiles each, RT g (g + 1) / 2 tiles stand before them
+// tile number -> (row tile bi, column tile bj) over the tiles on and below the diagonal: the RT = SV_C / SV_R row tiles
+// RT g .. RT g + RT - 1 have g + 1 column tiles each, RT g (g + 1) / 2 tiles stand before them (the host evaluates the
+// same code: hqpkkt_debug_symv_map)
+__host__ __device__ __forceinline__ void symv_tile_pair(const int t, int &bi, int &bj) {
   constexpr int RT = SV_C / SV_R;
   int gq = (int)((sqrt(1.0 + 8.0 * t / RT) - 1.0) * 0.5);
   while (RT * gq * (gq + 1) / 2 > t) gq--;
   while (RT * (gq + 1) * (gq + 2) / 2 <= t) gq++;
-  const int rem = t - RT * gq * (gq + 1) / 2, bi = RT * gq + rem / (gq + 1), bj = rem % (gq + 1), r0 = bi * SV_R, c0 = bj * SV_C;
+  const int rem = t - RT * gq * (gq + 1) / 2;
+  bi = RT * gq + rem / (gq + 1), bj = rem % (gq + 1);
+}
+__device__ __forceinline__ void symv_tile(const SymvArgs &g, const int t, double (*red)[SV_C]) {
+  int bi, bj;
+  symv_tile_pair(t, bi, bj);
+  const int r0 = bi * SV_R, c0 = bj * SV_C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool diag = c0 + SV_C - 1 >= r0;  // the tile meets the diagonal: element masks
   int jj[SV_P];                           // this lane's column pairs (jj, jj + 1)
@@ -1664,6 +1671,64 @@ __global__ void k_st_cols_finish(int N, int nchunk, const double *__restrict__ p
   const double r = (add ? add[j] : 0.0) + alpha * s;
   y[j] = r;
   if (y2) y2[j] = r + add2[j];
+}
+
+// The launches of these products on stream s, for the engine (staged_host.hip.h) and for the test hooks
+// (hqpkkt_debug_gemv_dense, hqpkkt_debug_symv, hqpkkt_debug_symv_batch); `around` as in pf_launch_rows.
+template <class Around>
+static inline void gemv_launch_rows(const GemvRows &g, hipStream_t s, Around &&around) {
+  if (g.M <= 0) return;
+  around([&]() { k_st_gemv_rows<<<(g.M + 3) / 4, 256, 0, s>>>(g); });
+}
+// (k_st_gemv_wide has no guard `row >= M`: exactly M workgroups)
+template <class Around>
+static inline void gemv_launch_wide(const GemvRows &g, hipStream_t s, Around &&around) {
+  if (g.M <= 0) return;
+  around([&]() { k_st_gemv_wide<<<g.M, 256, 0, s>>>(g); });
+}
+// chunks of the columns form: at least 64 rows each, at most the plan's part_chunks; g.part holds part_chunks x N
+// doubles, g.rows_per_chunk is set here.  Returns the chunks launched.
+static inline int gemv_cols_chunks(int part_chunks, int K) { return std::max(1, std::min(part_chunks, K / 64)); }
+template <class Around>
+static inline int gemv_launch_cols(GemvCols g, int part_chunks, hipStream_t s, Around &&around) {
+  if (g.N <= 0) return 0;
+  const int chunks = gemv_cols_chunks(part_chunks, g.K);
+  g.rows_per_chunk = (g.K + chunks - 1) / chunks;
+  around([&]() { k_st_gemv_cols<<<dim3((g.N + 511) / 512, chunks), 256, 0, s>>>(g); });
+  if (chunks > 1) around([&]() { k_st_cols_finish<<<(g.N + 255) / 256, 256, 0, s>>>(g.N, chunks, g.part, g.add, g.alpha, g.y, g.add2, g.y2); });
+  return chunks;
+}
+// triangle form: tiles on and below the diagonal of an N x N matrix, and where the partial sums of one product lie in
+// a scratch area of StagedPlan::symv_need(N) doubles (the row parts first, the mirrored parts behind ceil(N / SV_C) N)
+static inline long long symv_tiles(int N) {
+  const int nrt = (N + SV_R - 1) / SV_R;
+  long long tiles = 0;
+  for (int bi = 0; bi < nrt; bi++) tiles += bi / (SV_C / SV_R) + 1;
+  return tiles;
+}
+static inline void symv_parts(double *scratch, int N, double *&rowpart, double *&colpart) {
+  static_assert(SV_R == 64 && SV_C == 512, "StagedPlan::symv_need is sized for these tiles");
+  rowpart = scratch, colpart = scratch + (long long)((N + SV_C - 1) / SV_C) * N;
+}
+// y = scale (add + V x + A2 x2), g as for the rows form with M = N, an even lda and a 16-byte aligned A
+template <class Around>
+static inline void symv_launch(const GemvRows &g, double *scratch, hipStream_t s, Around &&around) {
+  const int N = g.N;
+  if (N <= 0) return;
+  double *rowpart, *colpart;
+  symv_parts(scratch, N, rowpart, colpart);
+  const long long tiles = symv_tiles(N);
+  around([&]() { k_st_symv_tiles<<<(unsigned)tiles, 256, 0, s>>>(SymvArgs{g.A, g.lda, N, g.x, rowpart, colpart}); });
+  around([&]() { k_st_symv_finish<<<(N + 63) / 64, 256, 0, s>>>(SymvFinish{N, rowpart, colpart, g.add, g.A2, g.lda2, g.n2, g.x2, g.y, g.scale}); });
+}
+// many products per launch: `count` items (device) of `tiles` tiles and `fins` finishing blocks in all, on grid_tiles /
+// grid_fins workgroups (0: one per tile / per block)
+template <class Around>
+static inline void symv_launch_batch(const SymvItem *items, int count, int tiles, int fins, int grid_tiles, int grid_fins, const double *xbase,
+                                     double *ybase, hipStream_t s, Around &&around) {
+  if (count <= 0 || tiles <= 0 || fins <= 0) return;
+  around([&]() { k_st_symv_tiles_batch<<<(unsigned)(grid_tiles > 0 ? grid_tiles : tiles), 256, 0, s>>>(items, count, tiles, xbase); });
+  around([&]() { k_st_symv_finish_batch<<<(unsigned)(grid_fins > 0 ? grid_fins : fins), 256, 0, s>>>(items, count, fins, ybase); });
 }
 
 // q = -(r1 - C' tz)   (the reference's gx, gu: hqp/Hqp_IpLQDOCP.C:884-918)

@@ -3,6 +3,7 @@
 #include "hqpkkt_handle.hpp"
 
 #include <algorithm>
+#include <limits>
 
 #include "staged.hip.h"
 #include "staged_sparse.hip.h"
@@ -1045,6 +1046,242 @@ int hqpkkt_debug_carried_packed(int device, int K, int N, int R, const double *B
   return guarded([&]() -> int {
     return debug_carried_packed(device, K, N, R, BT, bt_rows, ldb, packed, packed_elems, panel, ranges, C, c_rows, ldc, c_row0, c_col0);
   });
+}
+
+// ---- the solve's dense vector products on the caller's host arrays (include/hqpkkt.h): one launch through the engine's
+// launch functions (stg::gemv_launch_*, symv_launch, symv_launch_batch); nothing is compared here
+namespace {
+constexpr int DBG_GUARD = 64;  // marked doubles behind every result vector and scratch area on the device
+// a vector the launch writes: the caller's n doubles and the marks behind them
+struct DebugOut {
+  DBuf<double> d;
+  long long n = 0;
+  int up(const double *host, long long len) {
+    n = len;
+    const std::vector<double> mark(DBG_GUARD, -12345.678);
+    if (d.alloc((size_t)(n + DBG_GUARD))) return HQPKKT_E_MEM;
+    HIPCHK(hipMemcpy(d.p, host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.p + n, mark.data(), sizeof(double) * DBG_GUARD, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int down(double *host) {  // HQPKKT_E_INTERN: a mark has changed
+    const std::vector<double> mark(DBG_GUARD, -12345.678);
+    std::vector<double> back(DBG_GUARD);
+    HIPCHK(hipMemcpy(host, d.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(back.data(), d.p + n, sizeof(double) * DBG_GUARD, hipMemcpyDeviceToHost));
+    return std::memcmp(back.data(), mark.data(), sizeof(double) * DBG_GUARD) ? HQPKKT_E_INTERN : 0;
+  }
+};
+// partial sums: `elems` doubles as the plan sizes them and the marks, all NaN before the launch (a partial that is read
+// but never written shows in y); whatever lies outside the parts in use must come back untouched
+struct DebugScratch {
+  DBuf<double> d;
+  std::vector<double> fill;
+  int make(long long elems) {
+    fill.assign((size_t)(elems + DBG_GUARD), std::numeric_limits<double>::quiet_NaN());
+    if (d.alloc(fill.size())) return HQPKKT_E_MEM;
+    HIPCHK(hipMemcpy(d.p, fill.data(), sizeof(double) * fill.size(), hipMemcpyHostToDevice));
+    return 0;
+  }
+  // used: (first, one past last) pairs, ascending, of the doubles the launch may write
+  int check(const std::vector<std::pair<long long, long long>> &used) {
+    std::vector<double> back(fill.size());
+    HIPCHK(hipMemcpy(back.data(), d.p, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
+    long long at = 0;
+    auto same = [&](long long a, long long b) { return b <= a || !std::memcmp(back.data() + a, fill.data() + a, sizeof(double) * (size_t)(b - a)); };
+    for (const auto &u : used) {
+      if (!same(at, u.first)) return HQPKKT_E_INTERN;
+      at = u.second;
+    }
+    return same(at, (long long)back.size()) ? 0 : HQPKKT_E_INTERN;
+  }
+};
+int debug_up(DBuf<double> &d, const double *p, long long elems) {
+  if (d.alloc((size_t)elems)) return HQPKKT_E_MEM;
+  if (elems > 0) HIPCHK(hipMemcpy(d.p, p, sizeof(double) * (size_t)elems, hipMemcpyHostToDevice));
+  return 0;
+}
+// an operand of `rows` rows and w columns inside its buffer
+bool debug_block_ok(const hqpkkt_dgemm_operand &o, long long rows, long long w) {
+  return o.p && o.ld >= 1 && o.col0 >= 0 && w >= 0 && o.col0 + w <= o.ld && o.rows >= rows && rows >= 1;
+}
+// the carried rows' block of a case with `rows` rows: 0 fine (or none), else the code
+int debug_a2_check(const hqpkkt_gemv_case &c, long long rows) {
+  if (!c.A2.p) return 0;
+  if (!c.x2) return HQPKKT_E_NULL;
+  if (c.n2 < 0 || !debug_block_ok(c.A2, rows, c.n2) || c.x2_len < c.n2) return HQPKKT_E_RANGE;
+  return 0;
+}
+// what a case's second block needs on the device
+struct DebugA2 {
+  DBuf<double> A, x;
+  DBuf<int> n;
+  int up(const hqpkkt_gemv_case &c) {
+    if (!c.A2.p) return 0;
+    int e;
+    if ((e = debug_up(A, c.A2.p, c.A2.rows * c.A2.ld)) || (e = debug_up(x, c.x2, c.x2_len))) return e;
+    return n.upload(std::vector<int>(1, c.n2));
+  }
+};
+int debug_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  return 0;
+}
+const auto debug_plain = [](auto &&kernel) { kernel(); };
+}  // namespace
+
+static int debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c) {
+  if (!c || !c->A.p || !c->x || !c->y) return HQPKKT_E_NULL;
+  if (form < 0 || form > 2) return HQPKKT_E_RANGE;
+  const bool cols = form == 2;
+  const int M = c->M, N = c->N, nx = cols ? M : N, ny = cols ? N : M;
+  if (M <= 0 || N <= 0 || !debug_block_ok(c->A, M, N) || c->x_len < nx) return HQPKKT_E_RANGE;
+  if (form == 0) {
+    if (int e = debug_a2_check(*c, M)) return e;
+  } else if (c->A2.p)
+    return HQPKKT_E_RANGE;
+  if (cols ? (c->part_chunks < 1 || !c->add2 != !c->y2) : (c->add2 || c->y2)) return HQPKKT_E_RANGE;
+  int e;
+  if ((e = debug_device(device))) return e;
+  DBuf<double> dA, dx, dadd, dadd2;
+  DebugA2 a2;
+  DebugOut y, y2;
+  DebugScratch part;
+  if ((e = debug_up(dA, c->A.p, c->A.rows * c->A.ld)) || (e = debug_up(dx, c->x, c->x_len)) || (c->add && (e = debug_up(dadd, c->add, ny))) ||
+      (c->add2 && (e = debug_up(dadd2, c->add2, ny))) || (e = a2.up(*c)) || (e = y.up(c->y, ny)) || (c->y2 && (e = y2.up(c->y2, ny))))
+    return e;
+  const double *A = dA.p + c->A.col0;
+  std::vector<std::pair<long long, long long>> used;
+  if (cols) {
+    if ((e = part.make((long long)c->part_chunks * (N + 8)))) return e;
+    const stg::GemvCols g{A, c->A.ld, M, N, dx.p, c->add ? dadd.p : nullptr, c->scale, y.d.p, part.d.p, 0, c->add2 ? dadd2.p : nullptr, c->y2 ? y2.d.p : nullptr};
+    c->chunks = stg::gemv_launch_cols(g, c->part_chunks, 0, debug_plain);
+    c->vec16 = (((size_t)A) & 15) == 0 && (c->A.ld & 1) == 0;
+    if (c->chunks > 1) used.push_back({0, (long long)c->chunks * N});
+  } else {
+    const stg::GemvRows g{A, c->A.ld, M, N, dx.p, c->add ? dadd.p : nullptr, c->A2.p ? a2.A.p + c->A2.col0 : nullptr, c->A2.ld, c->A2.p ? a2.n.p : nullptr,
+                          c->A2.p ? a2.x.p : nullptr, y.d.p, c->scale};
+    if (form == 0)
+      stg::gemv_launch_rows(g, 0, debug_plain);
+    else
+      stg::gemv_launch_wide(g, 0, debug_plain);
+    c->chunks = 1, c->vec16 = 0;
+    for (int i = 0; i < M; i++) c->vec16 += (((size_t)(A + (long long)i * c->A.ld)) & 15) == 0;  // (rows that take the 16-byte loads)
+  }
+  HIPCHK(hipDeviceSynchronize());
+  e = y.down(c->y);
+  if (c->y2)
+    if (int e2 = y2.down(c->y2)) e = e2;
+  if (cols)
+    if (int e2 = part.check(used)) e = e2;
+  return e;
+}
+int hqpkkt_debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c) {
+  return guarded([&]() -> int { return debug_gemv_dense(device, form, c); });
+}
+
+// what the triangle form asks of a case: NULL / RANGE, 0 fine.  vec: the case brings x / y of its own
+static int debug_symv_check(const hqpkkt_gemv_case &c, bool own_x, bool own_y) {
+  if (!c.A.p || (own_x && !c.x) || (own_y && !c.y)) return HQPKKT_E_NULL;
+  if (c.N <= 0 || !debug_block_ok(c.A, c.N, c.N) || (own_x && c.x_len < c.N)) return HQPKKT_E_RANGE;
+  if ((c.A.ld & 1) || (c.A.col0 & 1)) return HQPKKT_E_RANGE;  // (what symv_tiles_form refuses: 16-byte loads of every row)
+  return debug_a2_check(c, c.N);
+}
+static int debug_symv(int device, hqpkkt_gemv_case *c) {
+  if (!c) return HQPKKT_E_NULL;
+  int e;
+  if ((e = debug_symv_check(*c, true, true)) || (e = debug_device(device))) return e;
+  const int N = c->N;
+  DBuf<double> dV, dx, dadd;
+  DebugA2 a2;
+  DebugOut y;
+  DebugScratch part;
+  if ((e = debug_up(dV, c->A.p, c->A.rows * c->A.ld)) || (e = debug_up(dx, c->x, c->x_len)) || (c->add && (e = debug_up(dadd, c->add, N))) || (e = a2.up(*c)) ||
+      (e = y.up(c->y, N)) || (e = part.make(kktdev::StagedPlan::symv_need(N))))
+    return e;
+  const stg::GemvRows g{dV.p + c->A.col0, c->A.ld, N, N, dx.p, c->add ? dadd.p : nullptr, c->A2.p ? a2.A.p + c->A2.col0 : nullptr, c->A2.ld,
+                        c->A2.p ? a2.n.p : nullptr, c->A2.p ? a2.x.p : nullptr, y.d.p, c->scale};
+  stg::symv_launch(g, part.d.p, 0, debug_plain);
+  HIPCHK(hipDeviceSynchronize());
+  c->chunks = (int)stg::symv_tiles(N), c->vec16 = 1;
+  e = y.down(c->y);
+  const long long parts = (N + stg::SV_R - 1) / stg::SV_R + (N + stg::SV_C - 1) / stg::SV_C;
+  if (int e2 = part.check({{0, parts * N}})) e = e2;
+  return e;
+}
+int hqpkkt_debug_symv(int device, hqpkkt_gemv_case *c) {
+  return guarded([&]() -> int { return debug_symv(device, c); });
+}
+
+static int debug_symv_batch(int device, int count, hqpkkt_gemv_case *cs, const double *xbase, long long xbase_len, double *ybase, long long ybase_len,
+                            int grid_tiles, int grid_fins) {
+  if (!cs) return HQPKKT_E_NULL;
+  if (count < 1 || grid_tiles < 0 || grid_fins < 0 || xbase_len < 0 || ybase_len < 0) return HQPKKT_E_RANGE;
+  auto up16 = [](long long x) { return (x + 15) / 16 * 16; };
+  long long arena = 0;
+  for (int i = 0; i < count; i++) {
+    const hqpkkt_gemv_case &c = cs[i];
+    if (int e = debug_symv_check(c, !xbase, !ybase)) return e;
+    if (xbase && (c.xoff < 0 || c.xoff + c.N > xbase_len)) return HQPKKT_E_RANGE;
+    if (ybase && (c.yoff < 0 || c.yoff + c.N > ybase_len)) return HQPKKT_E_RANGE;
+    arena += up16(kktdev::StagedPlan::symv_need(c.N));
+  }
+  int e;
+  if ((e = debug_device(device))) return e;
+  std::vector<DBuf<double>> dV(count), dx(count), dadd(count);
+  std::vector<DebugA2> a2(count);
+  std::vector<DebugOut> y(count);
+  DBuf<double> dxb;
+  DebugOut yb;
+  DebugScratch part;
+  DBuf<stg::SymvItem> ditems;
+  if ((e = part.make(arena)) || (xbase && (e = debug_up(dxb, xbase, xbase_len))) || (ybase && (e = yb.up(ybase, ybase_len)))) return e;
+  std::vector<stg::SymvItem> items(count);
+  std::vector<std::pair<long long, long long>> used;
+  int tiles = 0, fins = 0;
+  long long at = 0;
+  for (int i = 0; i < count; i++) {
+    const hqpkkt_gemv_case &c = cs[i];
+    const int N = c.N;
+    if ((e = debug_up(dV[i], c.A.p, c.A.rows * c.A.ld)) || (!xbase && (e = debug_up(dx[i], c.x, c.x_len))) || (c.add && (e = debug_up(dadd[i], c.add, N))) ||
+        (e = a2[i].up(c)) || (!ybase && (e = y[i].up(c.y, N))))
+      return e;
+    double *rowpart, *colpart;
+    stg::symv_parts(part.d.p + at, N, rowpart, colpart);
+    stg::SymvItem &it = items[i];
+    it.a = stg::SymvArgs{dV[i].p + c.A.col0, c.A.ld, N, xbase ? nullptr : dx[i].p, rowpart, colpart};
+    it.f = stg::SymvFinish{N, rowpart, colpart, c.add ? dadd[i].p : nullptr, c.A2.p ? a2[i].A.p + c.A2.col0 : nullptr, c.A2.ld, c.A2.p ? a2[i].n.p : nullptr,
+                           c.A2.p ? a2[i].x.p : nullptr, ybase ? nullptr : y[i].d.p, c.scale};
+    it.tile0 = tiles, it.fin0 = fins;
+    it.xrel = xbase != nullptr, it.yrel = ybase != nullptr, it.xoff = c.xoff, it.yoff = c.yoff;
+    tiles += (int)stg::symv_tiles(N), fins += (N + 63) / 64;
+    used.push_back({at, at + ((N + stg::SV_R - 1) / stg::SV_R + (N + stg::SV_C - 1) / stg::SV_C) * (long long)N});
+    at += up16(kktdev::StagedPlan::symv_need(N));
+  }
+  if ((e = ditems.upload(items))) return e;
+  stg::symv_launch_batch(ditems.p, count, tiles, fins, grid_tiles, grid_fins, dxb.p, yb.d.p, 0, debug_plain);
+  HIPCHK(hipDeviceSynchronize());
+  e = 0;
+  if (ybase) e = yb.down(ybase);
+  for (int i = 0; i < count && !ybase; i++)
+    if (int e2 = y[i].down(cs[i].y)) e = e2;
+  if (int e2 = part.check(used)) e = e2;
+  cs[0].chunks = tiles;
+  return e;
+}
+int hqpkkt_debug_symv_batch(int device, int count, hqpkkt_gemv_case *cases, const double *xbase, long long xbase_len, double *ybase, long long ybase_len,
+                            int grid_tiles, int grid_fins) {
+  return guarded([&]() -> int { return debug_symv_batch(device, count, cases, xbase, xbase_len, ybase, ybase_len, grid_tiles, grid_fins); });
+}
+
+long long hqpkkt_debug_symv_map(int N, int *pairs, long long cap) {
+  if (N <= 0) return 0;
+  const long long tiles = stg::symv_tiles(N);
+  if (pairs && cap >= 2 * tiles)
+    for (long long t = 0; t < tiles; t++) stg::symv_tile_pair((int)t, pairs[2 * t], pairs[2 * t + 1]);
+  return tiles;
 }
 
 #ifdef HQPKKT_STAMPS

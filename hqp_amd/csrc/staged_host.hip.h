@@ -247,8 +247,7 @@ int st_gemm_profile(hqpkkt_t *h, const stg::GemmArgs &g, int k, int by, int cls 
 }
 
 int st_gemv_rows(hqpkkt_t *h, stg::GemvRows g) {
-  if (g.M <= 0) return 0;
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_rows<<<(g.M + 3) / 4, 256, 0, h->stream>>>(g));
+  stg::gemv_launch_rows(g, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   return 0;
 }
 // y = scale (add + V x + A2 x2) with the symmetric V of a stage: from 2048 states on only the tiles on and below the
@@ -256,22 +255,9 @@ int st_gemv_rows(hqpkkt_t *h, stg::GemvRows g) {
 bool symv_tiles_form(const stg::GemvRows &g) {
   return !(env_no_symv() || g.M != g.N || g.N < env_symv_from() || (g.lda & 1) || (((size_t)g.A) & 15));
 }
-long long symv_tiles(int N) {
-  const int nrt = (N + stg::SV_R - 1) / stg::SV_R;
-  long long tiles = 0;
-  for (int bi = 0; bi < nrt; bi++) tiles += bi / (stg::SV_C / stg::SV_R) + 1;
-  return tiles;
-}
 int st_symv(hqpkkt_t *h, StagedDev &d, stg::GemvRows g) {
   if (!symv_tiles_form(g)) return st_gemv_rows(h, g);
-  const kktdev::StagedPlan &P = d.plan;
-  const int N = g.N, nct = (N + stg::SV_C - 1) / stg::SV_C;
-  double *rowpart = d.misc.p + P.oSym, *colpart = rowpart + (long long)nct * N;
-  static_assert(stg::SV_R == 64 && stg::SV_C == 512, "StagedPlan::oSym is sized for these tiles");
-  const long long tiles = symv_tiles(N);
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_symv_tiles<<<(unsigned)tiles, 256, 0, h->stream>>>(stg::SymvArgs{g.A, g.lda, N, g.x, rowpart, colpart}));
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_symv_finish<<<(N + 63) / 64, 256, 0, h->stream>>>(
-                            stg::SymvFinish{N, rowpart, colpart, g.add, g.A2, g.lda2, g.n2, g.x2, g.y, g.scale}));
+  stg::symv_launch(g, d.misc.p + d.plan.oSym, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   return 0;
 }
 // y = add + alpha A'x over a K x N row-major block
@@ -280,12 +266,8 @@ int st_gemv_cols(hqpkkt_t *h, StagedDev &d, const double *A, long long lda, int 
                  const double *add, double alpha, double *y, const double *add2 = nullptr, double *y2 = nullptr) {
   if (N <= 0) return 0;
   const kktdev::StagedPlan &P = d.plan;
-  int chunks = std::max(1, std::min(P.part_chunks, K / 64));
-  stg::GemvCols g{A, lda, K, N, x, add, alpha, y, d.misc.p + P.oPart, (K + chunks - 1) / chunks, add2, y2};
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_cols<<<dim3((N + 511) / 512, chunks), 256, 0, h->stream>>>(g));
-  if (chunks > 1)
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_cols_finish<<<(N + 255) / 256, 256, 0, h->stream>>>(N, chunks, d.misc.p + P.oPart, add,
-                                                                                       alpha, y, add2, y2));
+  const stg::GemvCols g{A, lda, K, N, x, add, alpha, y, d.misc.p + P.oPart, 0, add2, y2};
+  stg::gemv_launch_cols(g, P.part_chunks, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   return 0;
 }
 
@@ -316,8 +298,8 @@ int staged_build_symv_tables(StagedDev &d) {
       }
       if (g.count == 0) g.kfirst = k;
       g.klast = k;
-      const int nct = (np + stg::SV_C - 1) / stg::SV_C;
-      double *rowpart = M + P.oSymB + used, *colpart = rowpart + (long long)nct * np;
+      double *rowpart, *colpart;
+      stg::symv_parts(M + P.oSymB + used, np, rowpart, colpart);
       stg::SymvItem it{};
       it.a = stg::SymvArgs{sn.V, P.ldv[k + 1], np, dir == 0 ? nullptr : S + P.nmk[k + 1], rowpart, colpart};
       if (dir == 0)
@@ -327,7 +309,7 @@ int staged_build_symv_tables(StagedDev &d) {
       it.tile0 = g.tiles, it.fin0 = g.fins;
       it.xrel = dir == 0, it.yrel = dir == 1, it.xoff = it.yoff = P.nks[k];
       items.push_back(it);
-      g.tiles += (int)symv_tiles(np), g.fins += (np + 63) / 64, g.count++, used += need;
+      g.tiles += (int)stg::symv_tiles(np), g.fins += (np + 63) / 64, g.count++, used += need;
     }
     if (g.count > 0) d.symv_groups[dir].push_back(g);
     if (!items.empty())
@@ -339,8 +321,7 @@ int staged_build_symv_tables(StagedDev &d) {
 // the plan's oGv; dir 1: the dynamics rows of dy = V+ x+ + v+ + B+' eta+
 int staged_symv_group(hqpkkt_t *h, StagedDev &d, int dir, int gi, const double *r2, double *dy) {
   const StagedDev::SymvGroup &g = d.symv_groups[dir][gi];
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_symv_tiles_batch<<<(unsigned)g.tiles, 256, 0, h->stream>>>(d.symv_items[dir].p + g.first, g.count, g.tiles, r2));
-  KLAUNCH(h, KC_ST_VEC, stg::k_st_symv_finish_batch<<<(unsigned)g.fins, 256, 0, h->stream>>>(d.symv_items[dir].p + g.first, g.count, g.fins, dy));
+  stg::symv_launch_batch(d.symv_items[dir].p + g.first, g.count, g.tiles, g.fins, 0, 0, r2, dy, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   return 0;
 }
 // ... and the stages outside the groups (no triangle form: few states), one launch each
@@ -526,8 +507,8 @@ static void st_fwd_small(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, c
   const int nn = P.nk[k];
   double *xk = d.misc.p + P.oS + P.nmk[k], *uy = d.misc.p + P.oUy;
   if (P.qmax[k] > 0) {
-    stg::GemvRows gr{sp.Rm, P.ldy[k], P.qmax[k], nn, xk, sp.rho, nullptr, 0, nullptr, nullptr, uy, -1.0};
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_gemv_wide<<<P.qmax[k], 256, 0, s>>>(gr));
+    const stg::GemvRows gr{sp.Rm, P.ldy[k], P.qmax[k], nn, xk, sp.rho, nullptr, 0, nullptr, nullptr, uy, -1.0};
+    stg::gemv_launch_wide(gr, s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   }
   stg::FwdSmall fa{nn, P.mk[k], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], uy, sp.T, P.ldt[k],
                    sp.dyn, sp.eta, d.eq_rows.p + P.eq_ptr[k], xk + nn, dy, sn.eta, P.cap[k + 1]};

@@ -772,6 +772,100 @@ def gemv_profile(A, ranges, x, add=None, alpha=1.0, rows_form=False, K=None, N=N
     return y
 
 
+GEMV_FORMS = ("rows", "wide", "cols")
+
+
+def _gemv_case(A, M, N, x, ny, col0=0, add=None, scale=1.0, A2=None, a2_col0=0, n2=0, x2=None, add2=None, y=None, y2=None, part_chunks=1,
+               xoff=0, yoff=0, own_x=True, own_y=True):
+    """A hqpkkt_gemv_case over the caller's arrays and the arrays that must outlive the call: (case, y, y2, kept)."""
+    import numpy as np
+
+    def vec(v):
+        return None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+
+    def operand(a, c0):
+        if a is None:
+            return _lib.DgemmOperand(None, 0, 0, 0)
+        assert a.dtype == np.float64 and a.ndim == 2 and a.flags.c_contiguous
+        return _lib.DgemmOperand(a.ctypes.data, a.shape[0], a.shape[1], c0)
+
+    x, x2, add, add2 = vec(x), vec(x2), vec(add), vec(add2)
+    if own_y and y is None:
+        y = np.full(ny, np.nan)
+    if add2 is not None and y2 is None:
+        y2 = np.full(ny, np.nan)
+    for v in (add, add2, y, y2):
+        assert v is None or (v.dtype == np.float64 and v.size == ny and v.flags.c_contiguous)
+    c = _lib.GemvCase()
+    c.M, c.N, c.A, c.A2, c.n2, c.part_chunks = M, N, operand(A, col0), operand(A2, a2_col0), n2, part_chunks
+    if own_x and x is not None:
+        c.x, c.x_len = x.ctypes.data, x.size
+    if x2 is not None:
+        c.x2, c.x2_len = x2.ctypes.data, x2.size
+    c.add = None if add is None else add.ctypes.data
+    c.add2 = None if add2 is None else add2.ctypes.data
+    c.scale, c.xoff, c.yoff = float(scale), xoff, yoff
+    c.y = None if y is None else y.ctypes.data
+    c.y2 = None if y2 is None else y2.ctypes.data
+    return c, y, y2, (A, A2, x, x2, add, add2)
+
+
+def gemv_dense(form, A, M, N, x, device=0, **kw):
+    """One launch of a dense vector product of the STAGED solve (hqpkkt_debug_gemv_dense) on a C-contiguous float64
+    matrix A (rows x leading dimension; the block starts at column col0).  form "rows" / "wide": y (M) = scale (add +
+    A[:M, :N] x + A2[:M, :n2] x2) (A2 on the rows form alone); "cols": y (N) = add + scale A[:M, :N]' x, y2 = y + add2,
+    part_chunks in place of the plan's.  x, x2 are uploaded whole.  Returns (y, y2 or None, chunks launched, rows - "cols":
+    whether the block - that took the 16-byte loads)."""
+    f = GEMV_FORMS.index(form)
+    c, y, y2, _kept = _gemv_case(A, M, N, x, N if f == 2 else M, **kw)
+    _check(_lib.lib().hqpkkt_debug_gemv_dense(device, f, C.byref(c)), "debug_gemv_dense")
+    return y, y2, c.chunks, c.vec16
+
+
+def symv(V, N, x, device=0, **kw):
+    """y (N) = scale (add + V x + A2 x2) for a symmetric V by the triangle form (hqpkkt_debug_symv): only V's elements on
+    and below the diagonal are read.  V: C-contiguous float64, even leading dimension, even col0.  Returns (y, tiles)."""
+    c, y, _y2, _kept = _gemv_case(V, N, N, x, N, **kw)
+    _check(_lib.lib().hqpkkt_debug_symv(device, C.byref(c)), "debug_symv")
+    return y, c.chunks
+
+
+def symv_batch(items, xbase=None, ybase=None, grid_tiles=0, grid_fins=0, device=0):
+    """Several products of :func:`symv` in one launch pair (hqpkkt_debug_symv_batch).  items: dicts of symv's arguments (V,
+    N, x and the keywords) plus xoff / yoff; xbase: every item reads xbase[xoff: xoff + N] instead of its x; ybase: every
+    item writes ybase[yoff: yoff + N] (ybase comes back whole).  grid_tiles / grid_fins: workgroups of the two launches,
+    0: one per tile / finishing block.  Returns (list of the items' y - views of ybase where given -, tiles of all items)."""
+    import numpy as np
+    cs = (_lib.GemvCase * len(items))()
+    ys, kept = [], []
+    if xbase is not None:
+        xbase = np.ascontiguousarray(xbase, dtype=np.float64)
+    if ybase is not None:
+        assert ybase.dtype == np.float64 and ybase.ndim == 1 and ybase.flags.c_contiguous and ybase.flags.writeable
+    for i, it in enumerate(items):
+        it = dict(it)
+        V, N, x = it.pop("V"), it.pop("N"), it.pop("x", None)
+        c, y, _y2, k = _gemv_case(V, N, N, x, N, own_x=xbase is None, own_y=ybase is None, **it)
+        cs[i] = c
+        kept.append(k)
+        ys.append(y if ybase is None else ybase[c.yoff: c.yoff + N])
+    _check(_lib.lib().hqpkkt_debug_symv_batch(device, len(items), cs, None if xbase is None else xbase.ctypes.data, 0 if xbase is None else xbase.size,
+                                              None if ybase is None else ybase.ctypes.data, 0 if ybase is None else ybase.size, grid_tiles, grid_fins),
+           "debug_symv_batch")
+    return ys, cs[0].chunks
+
+
+def symv_map(N):
+    """(row tile, column tile) of every tile of the triangle form of order N, in the kernel's tile order (host only,
+    hqpkkt_debug_symv_map): an int32 array of tiles x 2."""
+    import numpy as np
+    tiles = _lib.lib().hqpkkt_debug_symv_map(N, None, 0)
+    pairs = np.full((tiles, 2), -1, dtype=np.int32)
+    got = _lib.lib().hqpkkt_debug_symv_map(N, pairs.ctypes.data_as(C.POINTER(C.c_int)), pairs.size)
+    assert got == tiles
+    return pairs
+
+
 GEMM_FORMS = ("frac", "cut", "plain", "ks", "6432", "6464")  # (what the launch rule can answer; the profile form is asked for)
 
 

@@ -562,6 +562,55 @@ int hqpkkt_debug_carried_packed(int device, int K, int N, int R, const double *B
                                 long long packed_elems, const long long *panel, const int *ranges, double *C, long long c_rows, long long ldc,
                                 long long c_row0, long long c_col0);
 
+/* Test hooks of the solve's dense vector products (staged.hip.h: k_st_gemv_rows, k_st_gemv_wide, k_st_gemv_cols with
+ * k_st_cols_finish, k_st_symv_tiles with k_st_symv_finish and their _batch forms): ONE launch on the caller's host arrays
+ * through the launch functions the engine's sweeps call, host arrays back, nothing compared in the library.
+ * A case: A and A2 are operands as hqpkkt_dgemm_case's - a buffer of rows x ld doubles, the kernel's pointer is p + col0:
+ * ld and col0 may be odd, which decides between the 16-byte and the scalar loads -; x, x2: host vectors of x_len, x2_len
+ * doubles, uploaded whole (the caller may poison what lies behind the entries that count); add, add2: NULL or as long
+ * as the result; y, y2: go to the device before the launch and come back after it.  On the device every result vector
+ * and every scratch area has 64 marked doubles behind it, and the scratch areas - sized as the plan sizes them,
+ * StagedPlan::symv_need(N) and part_chunks (N + 8) doubles - are NaN before the launch: HQPKKT_E_INTERN where a mark, or
+ * scratch outside the partial sums in use, has changed.
+ * hqpkkt_debug_gemv_dense, form 0 (rows form): y (M) = scale (add + A x + A2 x2), A: M x N, A2 (or p NULL): M rows of which
+ *   the first n2 columns count (n2 is read on the device, as the engine's live carried rows), x2: n2 entries.
+ *   form 1 (wide form, a workgroup per row): the same without A2.
+ *   form 2 (columns form): y (N) = add + scale A'x over the M rows of A (x: M entries), y2 = y + add2 (both or neither);
+ *   part_chunks stands for the plan's value: min(part_chunks, M / 64) chunks of rows, at least one.
+ *   Out: chunks (launched; forms 0, 1: 1); vec16: forms 0 and 1 the rows whose pointer takes the 16-byte loads, form 2
+ *   whether the block takes them (aligned start, even ld).
+ * hqpkkt_debug_symv: y (N) = scale (add + V x + A2 x2) with V = A, N x N, by the triangle form whatever HQPKKT_SYMV_FROM /
+ *   HQPKKT_NO_SYMV say: no element of V above the diagonal is read as a value that counts.  HQPKKT_E_RANGE: odd ld or
+ *   odd col0, which the engine gives to the rows form.  Out: chunks = tiles launched.
+ * hqpkkt_debug_symv_batch: `count` such products in one launch pair.  xbase non-NULL: item i reads xbase + xoff (its x is
+ *   ignored), else its own x; ybase non-NULL: item i writes ybase + yoff, and the whole of ybase (ybase_len doubles)
+ *   travels both ways.  The items' partial sums lie in one area, at steps of symv_need(N) rounded up to 16.  grid_tiles
+ *   / grid_fins: workgroups of the two launches, each striding over the tiles / finishing blocks of all items; 0: one
+ *   per tile / block, as the engine launches.  Out: cases[0].chunks = tiles of all items.
+ * HQPKKT_E_NULL, HQPKKT_E_RANGE (sizes, an operand outside its buffer), HQPKKT_E_DEVICE (no such device), HQPKKT_E_MEM. */
+typedef struct hqpkkt_gemv_case {
+  int M, N;
+  hqpkkt_dgemm_operand A, A2;
+  int n2, part_chunks;
+  const double *x;
+  long long x_len;
+  const double *x2;
+  long long x2_len;
+  const double *add, *add2;
+  double scale;
+  double *y, *y2;
+  long long xoff, yoff; /* hqpkkt_debug_symv_batch */
+  int chunks, vec16;    /* out */
+} hqpkkt_gemv_case;
+int hqpkkt_debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c);
+int hqpkkt_debug_symv(int device, hqpkkt_gemv_case *c);
+int hqpkkt_debug_symv_batch(int device, int count, hqpkkt_gemv_case *cases, const double *xbase, long long xbase_len, double *ybase, long long ybase_len,
+                            int grid_tiles, int grid_fins);
+/* Host only: the (row tile, column tile) of tile t = 0 .. tiles - 1 of the triangle form of order N, by the code the
+ * kernel runs (64-row, 512-column tiles on and below the diagonal); pairs (or NULL): 2 ints per tile, written where
+ * cap >= 2 tiles.  Returns the number of tiles. */
+long long hqpkkt_debug_symv_map(int N, int *pairs, long long cap);
+
 /* Test hook, host only: the form the STAGED engine's launch rule (gemm_form.hpp) gives an M x N x K product on a device
  * of `cus` CUs with a split grid of `grid` workgroups (0: none), arrival counters for sk_tiles tiles and workspaces of
  * ws_elems / ws2_elems doubles (first / second stream).  flags: 1 one system over several ranks, 2 a launch of the

@@ -371,7 +371,9 @@ def test_symmetric_products_of_the_solve_read_one_triangle():
     """From 2048 states on the products with V in the two sweeps of the solve read the tiles on and below the diagonal
     only (k_st_symv_tiles, k_st_symv_finish).  Same stage matrices, same solve with HQPKKT_NO_SYMV (the rows form): equal
     to rounding, both below the residual tolerance, and reproducible from run to run.  (With HQPKKT_SYMV_FROM=16 the
-    whole of this file runs through the triangle form; profiles/r04_symv.txt.)"""
+    whole of this file runs through the triangle form; profiles/r04_symv.txt.)  The kernels on their own, entry by
+    entry on chosen operands with NaN above the diagonal, at every stage width that takes another branch:
+    tests/test_gpu_staged_gemv.py."""
     import subprocess, sys, os, textwrap
     code = textwrap.dedent("""
         import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)

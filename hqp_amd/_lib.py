@@ -38,6 +38,7 @@ SYMBOLS = [
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
+    "hqpkkt_debug_rows_gemv",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -110,6 +111,12 @@ class GemvCase(C.Structure):
                 ("x", C.c_void_p), ("x_len", C.c_longlong), ("x2", C.c_void_p), ("x2_len", C.c_longlong), ("add", C.c_void_p), ("add2", C.c_void_p),
                 ("scale", C.c_double), ("y", C.c_void_p), ("y2", C.c_void_p), ("xoff", C.c_longlong), ("yoff", C.c_longlong),
                 ("chunks", C.c_int), ("vec16", C.c_int)]
+
+
+class RowsCase(C.Structure):
+    """hqpkkt_rows_case (include/hqpkkt.h)"""
+    _fields_ = [("nblocks", C.c_int)] + [(k, C.c_void_p) for k in ("rows", "cols", "ld", "col0", "off", "E")] + [("e_len", C.c_longlong), ("row_index", C.c_void_p),
+                ("n", C.c_int), ("m", C.c_int)] + [(k, C.c_void_p) for k in ("x", "t", "tz", "zw", "r3", "y", "dz", "dw", "xc")]
 
 
 class GemmCaps(C.Structure):
@@ -221,6 +228,7 @@ def lib():
     L.hqpkkt_debug_gemm_schedule.argtypes = [C.POINTER(GemmCaps), C.POINTER(GemmLaunch), C.POINTER(GemmLaunch), C.POINTER(GemmScheduleOut),
                                              C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_int), C.c_longlong]
     L.hqpkkt_debug_gemv_dense.argtypes = [C.c_int, C.c_int, C.POINTER(GemvCase)]
+    L.hqpkkt_debug_rows_gemv.argtypes = [C.c_int, C.c_int, C.POINTER(RowsCase)]
     L.hqpkkt_debug_symv.argtypes = [C.c_int, C.POINTER(GemvCase)]
     L.hqpkkt_debug_symv_batch.argtypes = [C.c_int, C.c_int, C.POINTER(GemvCase), vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_int]
     L.hqpkkt_debug_symv_map.restype = C.c_longlong

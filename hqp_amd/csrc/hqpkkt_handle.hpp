@@ -169,11 +169,13 @@ struct CsrBuf {
 // handle's stream around every launch, summed per class after the call
 enum { KC_ASSEMBLE = 0, KC_FACTOR_DIAG, KC_PANEL_SOLVE, KC_SCHUR_UPDATE,
        KC_SOLVE_FWD, KC_SOLVE_BWD, KC_VECTOR, KC_RESIDUAL, KC_ST_GEMM, KC_ST_SMALL, KC_ST_VEC, KC_ST_GEMM_UPD, KC_XCHG, KC_SOLVE_TOP,
-       KC_ST_SPARSE, KC_ST_SPARSE_VEC, KC_COUNT };  // (the sparse form of the stage products: the factorisation's passes, the solve's)
+       KC_ST_SPARSE, KC_ST_SPARSE_VEC,  // (the sparse form of the stage products: the factorisation's passes, the solve's)
+       KC_ST_ROWS_VEC,                  // (the wide rows of C in step and residual: staged_rows.hip.h)
+       KC_COUNT };
 static const char *const kc_names[KC_COUNT] = {"assemble", "factor_diag", "panel_solve",
                                                "schur_update", "solve_fwd", "solve_bwd", "vector",
                                                "residual", "staged_gemm", "staged_small", "staged_gemv", "staged_gemm_upd",
-                                               "exchange", "solve_top", "staged_sparse", "staged_sparse_gemv"};
+                                               "exchange", "solve_top", "staged_sparse", "staged_sparse_gemv", "staged_rows_gemv"};
 struct Prof {
   bool on = false;
   std::vector<EventOwner> pool;
@@ -514,6 +516,9 @@ int staged_factor(hqpkkt_t *h, const Vecs &v);
 int staged_step(hqpkkt_t *h, const Vecs &v, int which);
 // (xq: Q dx with dense stage Hessians, hqpkkt_set_hessian_form; left alone otherwise)
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn, const double **xq);
+// the residual's share of the wide rows of C (hqpkkt_set_dense_rows): *xcw = C_wide' dz, *cw = the wide rows' C dx, and the
+// narrow copies of C' and C in *CT, *C; leaves all four as they are on a handle without wide rows
+void staged_rows_products(hqpkkt_t *h, const Vecs &v, const double **xcw, const double **cw, CsrDev *CT, CsrDev *C);
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out);
 // hqpkkt.hip
 int solve_vecs(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3,

@@ -2793,7 +2793,10 @@ k_residual(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDe
            // which are empty in the CSR block), computed by the dense kernels of staged.hip.h
            const double *__restrict__ x1 = nullptr, const double *__restrict__ x2 = nullptr, int ndyn = 0,
            // STAGED with dense stage Hessians: xq = Q dx (n) from k_hs_symv, in place of the walk over Q's rows
-           const double *__restrict__ xq = nullptr) {
+           const double *__restrict__ xq = nullptr,
+           // STAGED with wide rows of C, which CT and C then do not hold: xcw = C_wide' dz (n), and cw = C dx of the wide rows
+           // (m, zero in every other row) from k_st_rows_gemv_t / k_st_rows_gemv
+           const double *__restrict__ xcw = nullptr, const double *__restrict__ cw = nullptr) {
   __shared__ double red[4];
   if (blockIdx.x == 0 && threadIdx.x == 0) *resbits_next = 0ULL;
   const int sub = threadIdx.x & (LPR - 1);
@@ -2805,6 +2808,7 @@ k_residual(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDe
       double s = xq ? xq[q] : row_dot<LPR>(Q, vals, dx, q, sub);
       s += -1.0 * row_dot<LPR>(AT, vals, dy, q, sub);
       s += -1.0 * row_dot<LPR>(CT, vals, dz, q, sub);
+      if (xcw) s -= xcw[q];
       if (x1) s -= x1[q];
       s = r1[q] + s;
       if (sub == 0) o1[q] = s;
@@ -2816,7 +2820,8 @@ k_residual(int n, int me, int m, CsrDev Q, CsrDev AT, CsrDev CT, CsrDev A, CsrDe
       mag = fmax(mag, fabs(s) == fabs(s) ? fabs(s) : __longlong_as_double(0x7ff0000000000000LL));
     } else {
       const int j = q - n - me;
-      const double cdx = row_dot<LPR>(C, vals, dx, j, sub);
+      double cdx = row_dot<LPR>(C, vals, dx, j, sub);
+      if (cw) cdx += cw[j];  // (a wide row's walk is empty)
       const double s3 = r3[j] - (cdx - dw[j]);
       const double s4 = r4[j] - (z[j] * dw[j] + w[j] * dz[j]);
       if (sub == 0) o3[j] = s3, o4[j] = s4;

@@ -1732,13 +1732,15 @@ static inline void symv_launch_batch(const SymvItem *items, int count, int tiles
 }
 
 // q = -(r1 - C' tz)   (the reference's gx, gu: hqp/Hqp_IpLQDOCP.C:884-918)
+// xc (or NULL): the share of the wide rows of C, which the arrays of C' then do not hold (k_st_rows_gemv_t)
 __global__ void k_st_q(int n, const int *__restrict__ CTp, const int *__restrict__ CTc, const int *__restrict__ CTs,
                        const double *__restrict__ vals, const double *__restrict__ tz, const double *__restrict__ r1,
-                       double *__restrict__ q) {
+                       double *__restrict__ q, const double *__restrict__ xc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double s = 0.0;
   for (int k = CTp[i]; k < CTp[i + 1]; k++) s += vals[CTs[k]] * tz[CTc[k]];
+  if (xc) s += xc[i];
   q[i] = s - r1[i];
 }
 

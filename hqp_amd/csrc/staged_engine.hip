@@ -51,6 +51,13 @@ int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const d
   *x1 = d.dyn_x1.p, *x2 = d.dyn_x2.p, *ndyn = P.ndyn;
   return 0;
 }
+void staged_rows_products(hqpkkt_t *h, const Vecs &v, const double **xcw, const double **cw, CsrDev *CT, CsrDev *C) {
+  StagedDev &d = *h->sd;
+  if (!d.plan.rows_vec()) return;
+  st_rows_cols(h, d, v.dz);
+  st_rows_rows(h, d, stg::RowsGemv{nullptr, nullptr, 0, nullptr, nullptr, v.dx, nullptr, nullptr, nullptr, nullptr, nullptr, d.wr_cdx.p});
+  *xcw = d.wr_xc.p, *cw = d.wr_cdx.p, *CT = d.CTn.dev(), *C = d.Cn.dev();
+}
 static bool staged_is_sharded(hqpkkt_t *h) { return h->sd && h->sd->plan.sharded; }
 int staged_factor(hqpkkt_t *h, const Vecs &v) {
   if (staged_is_sharded(h)) return staged_run_factor(h, v.z, v.w);  // an exchange per stage: not captured
@@ -174,6 +181,14 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
       for (int k = 0; k <= P.K && P.hess_dense; k++) {
         out.push_back(P.hess_order(k)), out.push_back(P.ldQ[k]);
         out.push_back((int)(unsigned)(P.h_kept[k] & 0xffffffffLL)), out.push_back((int)(P.h_kept[k] >> 32));
+      }
+      break;
+    case 46:  // the wide rows' vector products (host only): 1 where step and residual take the wide rows through the blocks E_k, the
+              // number of wide rows, then the stored entries of C left in the narrow copy of the CSR walks and the entries taken
+              // out, each as (low, high) ints; empty unless the analysis found wide rows
+      if (!P.wr_rows.empty()) {
+        out.push_back(P.rows_vec() ? 1 : 0), out.push_back((int)P.wr_rows.size());
+        for (long long c : {P.c_kept, P.c_cut}) out.push_back((int)(unsigned)(c & 0xffffffffLL)), out.push_back((int)(c >> 32));
       }
       break;
     case 38:  // the work lists upload made for the cut products, 5 ints each: tiles, k-slabs, form (stg::GemmFormKind), list
@@ -1180,6 +1195,66 @@ static int debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c) {
 }
 int hqpkkt_debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c) {
   return guarded([&]() -> int { return debug_gemv_dense(device, form, c); });
+}
+
+// a vector the kernel reads: its n entries and DBG_GUARD NaN doubles behind them
+static int debug_up_nan(DBuf<double> &d, const double *p, long long n) {
+  std::vector<double> v((size_t)(n + DBG_GUARD), std::numeric_limits<double>::quiet_NaN());
+  std::copy(p, p + n, v.begin());
+  return d.upload(v);
+}
+static int debug_rows_gemv(int device, int form, hqpkkt_rows_case *c) {
+  if (!c || !c->rows || !c->cols || !c->ld || !c->col0 || !c->off || !c->E || !c->row_index) return HQPKKT_E_NULL;
+  if (form < 0 || form > 2) return HQPKKT_E_RANGE;
+  if (form == 2 ? (!c->t || !c->xc) : (!c->x || (form == 0 ? !c->y : (!c->tz || !c->zw || !c->r3 || !c->dz || !c->dw)))) return HQPKKT_E_NULL;
+  if (c->nblocks < 1 || c->n < 1 || c->m < 1 || c->e_len < 1) return HQPKKT_E_RANGE;
+  std::vector<stg::RowsBlock> rb(c->nblocks);
+  std::vector<int> of;
+  int pairs_max = 0;
+  for (int b = 0; b < c->nblocks; b++) {
+    const long long r = c->rows[b], nz = c->cols[b], ld = c->ld[b], off = c->off[b], col0 = c->col0[b];
+    // (what the kernels take: rows of whole 16-byte pairs - the plan's blocks have ld = up8 - inside E, columns inside x)
+    if (r < 0 || nz < 1 || ld < nz || ld % 8 || off < 0 || (off & 1) || off + r * ld > c->e_len || col0 < 0 || col0 + nz > c->n) return HQPKKT_E_RANGE;
+    rb[b] = stg::RowsBlock{off, (int)ld, (int)nz, (int)col0, (int)of.size(), (int)r};
+    of.insert(of.end(), (size_t)r, b);
+    pairs_max = std::max(pairs_max, (int)((nz + 1) / 2));
+  }
+  const int R = (int)of.size();
+  {
+    std::vector<char> seen(c->m, 0);
+    for (int q = 0; q < R; q++) {
+      if (c->row_index[q] < 0 || c->row_index[q] >= c->m || seen[c->row_index[q]]) return HQPKKT_E_RANGE;
+      seen[c->row_index[q]] = 1;
+    }
+  }
+  int e;
+  if ((e = debug_device(device))) return e;
+  DBuf<stg::RowsBlock> dblk;
+  DBuf<int> dof, drows;
+  DBuf<double> dE, dx, dt, dtz, dzw, dr3;
+  DebugOut y, dz, dw, xc;
+  if ((e = dblk.upload(rb)) || (e = dof.upload(of)) || (e = drows.upload(std::vector<int>(c->row_index, c->row_index + R))) || (e = debug_up(dE, c->E, c->e_len)))
+    return e;
+  if (form == 2) {
+    if ((e = debug_up_nan(dt, c->t, c->m)) || (e = xc.up(c->xc, c->n))) return e;
+    stg::rows_launch_t(stg::RowsGemvT{dblk.p, dE.p, drows.p, dt.p, xc.d.p}, c->nblocks, pairs_max, 0, debug_plain);
+  } else {
+    if ((e = debug_up_nan(dx, c->x, c->n))) return e;
+    if (form == 0 ? (e = y.up(c->y, c->m))
+                  : ((e = debug_up_nan(dtz, c->tz, c->m)) || (e = debug_up_nan(dzw, c->zw, c->m)) || (e = debug_up_nan(dr3, c->r3, c->m)) || (e = dz.up(c->dz, c->m)) ||
+                     (e = dw.up(c->dw, c->m))))
+      return e;
+    stg::rows_launch(stg::RowsGemv{dblk.p, dof.p, R, dE.p, drows.p, dx.p, form == 1 ? dtz.p : nullptr, dzw.p, dr3.p, dz.d.p, dw.d.p, y.d.p}, 0, debug_plain);
+  }
+  HIPCHK(hipDeviceSynchronize());
+  if (form == 2) return xc.down(c->xc);
+  if (form == 0) return y.down(c->y);
+  e = dz.down(c->dz);
+  if (int e2 = dw.down(c->dw)) e = e2;
+  return e;
+}
+int hqpkkt_debug_rows_gemv(int device, int form, hqpkkt_rows_case *c) {
+  return guarded([&]() -> int { return debug_rows_gemv(device, form, c); });
 }
 
 // what the triangle form asks of a case: NULL / RANGE, 0 fine.  vec: the case brings x / y of its own

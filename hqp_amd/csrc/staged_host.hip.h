@@ -47,6 +47,14 @@ struct StagedDev {
   DBuf<long long> h_dst, a_dst;
   DBuf<long long> c_dst;  // the wide rows of C (StagedPlan::wr_rows): where k_st_scatter puts C's values, and the rows
   DBuf<int> wr_rows;
+  // ... and their vector products in step and residual (StagedPlan::rows_vec; staged_rows.hip.h): the table of the blocks
+  // E_k, per wide row its block, the narrow copies of C and C' for the CSR walks, C_wide' t (n) and the wide rows' C dx
+  // (m; zero in every other row: nothing else writes it)
+  DBuf<stg::RowsBlock> wr_blk;
+  DBuf<int> wr_blk_of;
+  CsrBuf Cn, CTn;
+  DBuf<double> wr_xc, wr_cdx;
+  int wr_pairs_max = 0;
   DBuf<stg::HTerm> h_terms;
   DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
   DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
@@ -408,6 +416,17 @@ static int st_add_h_wide(hqpkkt_t *h, StagedDev &d, int k, double *G, long long 
                               stg::RowsScale{d.F.p + P.oE[k], S, d.wr_rows.p + P.wr_ptr[k], h->td.wt.p, r, ld}));
   return st_gemm(h, stg::GemmArgs{S, ld, S, ld, G, ldg, G, ldg, nz, nz, r, 1.0, 1.0, 1, k == P.K ? 1 : 0}, KC_ST_GEMM_UPD);
 }
+// The vector products of the wide rows of C over all stages, one launch each (staged_rows.hip.h):
+// d.wr_xc = C_wide' t (the whole n-vector; t by rows of C) ...
+static void st_rows_cols(hqpkkt_t *h, StagedDev &d, const double *t) {
+  stg::rows_launch_t(stg::RowsGemvT{d.wr_blk.p, d.F.p, d.wr_rows.p, t, d.wr_xc.p}, d.plan.K + 1, d.wr_pairs_max, h->stream,
+                     [&](auto &&launch) { KLAUNCH(h, KC_ST_ROWS_VEC, launch()); });
+}
+// ... and C_wide x with the epilogue of g (x and the epilogue's vectors: the caller's; the table, E, the rows: filled in here)
+static void st_rows_rows(hqpkkt_t *h, StagedDev &d, stg::RowsGemv g) {
+  g.blk = d.wr_blk.p, g.blk_of = d.wr_blk_of.p, g.R = (int)d.plan.wr_rows.size(), g.E = d.F.p, g.rows = d.wr_rows.p;
+  stg::rows_launch(g, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_ROWS_VEC, launch()); });
+}
 // the carried rows of stage k: N_k[e..] = B+ F (nothing where stage k + 1 carries none)
 static int st_carried_rows(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, bool allow_sk) {
   const kktdev::StagedPlan &P = d.plan;
@@ -540,6 +559,7 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   e = P.run(n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(), h->pCp.data(), h->pCi.data(), h->an.AT.ptr.data(),
             h->an.AT.col.data());
   if (e) return e;
+  P.narrow_copies(h->an.C.ptr.data(), h->an.C.col.data(), h->an.C.src.data(), h->an.CT.ptr.data(), h->an.CT.col.data(), h->an.CT.src.data());
   h->an.sbw = -1;
   h->analyzed = true;
   std::memset(&h->st, 0, sizeof(h->st));
@@ -619,6 +639,23 @@ static int staged_upload(hqpkkt_t *h) {
       (e = d.chk_kind.upload(P.chk_kind)) || (e = d.h_dst.upload(P.h_dst)) || (e = d.a_dst.upload(P.a_dst)))
     return e;
   if (!P.wr_rows.empty() && ((e = d.c_dst.upload(P.c_dst)) || (e = d.wr_rows.upload(P.wr_rows)))) return e;
+  if (P.rows_vec()) {
+    std::vector<stg::RowsBlock> rb(P.K + 1);
+    std::vector<int> of(P.wr_rows.size());
+    d.wr_pairs_max = 0;
+    for (int k = 0; k <= P.K; k++) {
+      rb[k] = stg::RowsBlock{P.oE[k], P.ldE[k], P.hess_order(k), P.nmk[k], P.wr_ptr[k], P.wide_count(k)};
+      for (int q = P.wr_ptr[k]; q < P.wr_ptr[k + 1]; q++) of[q] = k;
+      d.wr_pairs_max = std::max(d.wr_pairs_max, (P.hess_order(k) + 1) / 2);
+    }
+    Analysis::Csr cn, ctn;
+    cn.rows = m, cn.ptr = P.cn.ptr, cn.col = P.cn.col, cn.src = P.cn.src;
+    ctn.rows = n, ctn.ptr = P.ctn.ptr, ctn.col = P.ctn.col, ctn.src = P.ctn.src;
+    if ((e = d.wr_blk.upload(rb)) || (e = d.wr_blk_of.upload(of)) || (e = d.Cn.upload(cn)) || (e = d.CTn.upload(ctn)) || (e = d.wr_xc.alloc((size_t)n + 1)) ||
+        (e = d.wr_cdx.alloc((size_t)m + 1)))
+      return e;
+    HIPCHK(hipMemset(d.wr_cdx.p, 0, sizeof(double) * ((size_t)m + 1)));
+  }
   {
     std::vector<stg::HTerm> t(P.h_terms.size());
     for (size_t k = 0; k < t.size(); k++) t[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
@@ -980,7 +1017,7 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
   if (an.nq) HIPCHK(hipMemcpyAsync(h->td.vals.p, Qx, sizeof(double) * an.nq, kind, s));
   if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, s));
   if (an.nc) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, s));
-  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
+  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT, &d.Cn, &d.CTn})
     if (c->src.count)
       k_gather_values<<<nblk((long long)c->src.count), 256, 0, s>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
   HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
@@ -1376,7 +1413,11 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   const long long ndx = (long long)P.ndyn + (P.fixed_x0 ? P.nk[0] : 0);
   if (sh) KLAUNCH(h, KC_ST_VEC, stg::k_st_zero<<<nblk(std::max<long long>(ndx, 1)), 256, 0, s>>>(ndx, dyx));
   if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
-  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, h->td.CT.ptr.p, h->td.CT.col.p, h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv));
+  // q = C'tz - r1; with wide rows of C (StagedPlan::rows_vec) their share out of the blocks E_k, the walk over the narrow C'
+  const bool wide = P.rows_vec();
+  const CsrBuf &CT = wide ? d.CTn : h->td.CT, &C = wide ? d.Cn : h->td.C;
+  if (wide) st_rows_cols(h, d, h->td.tz.p);
+  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, CT.ptr.p, CT.col.p, CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv, wide ? d.wr_xc.p : nullptr));
   // One GPU: the products with V are not part of the sweeps' chains: V+ f (f: the dynamics' right-hand side) is known before the
   // backward sweep starts, the dynamics rows' multipliers are wanted by nobody before the forward sweep is over - both
   // for many stages per launch (staged_symv_group), which leaves the F products and the control-sized kernels in the
@@ -1493,8 +1534,9 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, sh ? dyx + P.ndyn : tmp, v.dy));
   KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
   if (m > 0)
-    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p,
-                                                             v.r3, v.dz, v.dw));
+    KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, C.ptr.p, C.col.p, C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));
+  // (the wide rows are empty in the narrow C: k_red_dzdw has left tz and -r3 there, and the rows form writes dz and dw)
+  if (wide) st_rows_rows(h, d, stg::RowsGemv{nullptr, nullptr, 0, nullptr, nullptr, v.dx, h->td.tz.p, h->td.wt.p, v.r3, v.dz, v.dw, nullptr});
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -632,4 +632,23 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   return 0;
 }
 
+// the narrow copies of C (m rows) and C' (n rows) for the CSR walks of step and residual (staged_plan.hpp)
+void StagedPlan::narrow_copies(const int *Cp, const int *Ci, const int *Cs, const int *CTp, const int *CTi, const int *CTs) {
+  cn = Narrow(), ctn = Narrow(), c_kept = c_cut = 0;
+  if (wr_rows.empty()) return;
+  std::vector<char> is_wide(m, 0);
+  for (int r : wr_rows) is_wide[r] = 1;
+  cn.ptr.assign(m + 1, 0), ctn.ptr.assign(n + 1, 0);
+  for (int r = 0; r < m; r++) {
+    for (int p = Cp[r]; p < Cp[r + 1] && !is_wide[r]; p++) cn.col.push_back(Ci[p]), cn.src.push_back(Cs[p]);
+    cn.ptr[r + 1] = (int)cn.col.size();
+  }
+  for (int c = 0; c < n; c++) {
+    for (int p = CTp[c]; p < CTp[c + 1]; p++)
+      if (!is_wide[CTi[p]]) ctn.col.push_back(CTi[p]), ctn.src.push_back(CTs[p]);
+    ctn.ptr[c + 1] = (int)ctn.col.size();
+  }
+  c_kept = (long long)cn.col.size(), c_cut = (long long)Cp[m] - c_kept;
+}
+
 }  // namespace kktdev

@@ -90,7 +90,12 @@ struct StagedPlan {
   // wr_ptr[k + 1]): the wide rows of stage k as row indices of C, ascending.  c_dst: per stored entry of C its place in
   // the F arena or -1 (k_st_scatter runs it as it runs a_dst; the arena is cleared at upload and nothing else writes
   // the blocks: the padding stays zero); empty without wide rows.  oSr: the work block S = diag(sqrt(z / w)) E_k of the
-  // stage in work, in the misc arena, sized for the largest stage.  Everything else of the rows stays in C / C'.
+  // stage in work, in the misc arena, sized for the largest stage.
+  // The vector products of the wide rows (step and residual; k_st_rows_gemv, k_st_rows_gemv_t) read the blocks too, and
+  // the CSR walks of these products take narrow copies of C and C' (cn, ctn: ptr / col / src as Analysis::Csr holds
+  // them, the entries in their order) in which the wide rows are empty and the wide rows' entries are missing from the
+  // columns; c_kept / c_cut: stored entries of C in cn / taken out.  Built by narrow_copies() behind run(), empty without
+  // wide rows.  The interior-point loops' own right-hand-side kernels keep the full arrays.
   // h_kept[k] / h_cut[k]: H terms of stage k in the lists / the terms its wide rows would have added.
   // want_rows: what the next analysis takes (-1: ROWS_DEFAULT; 0 there: no threshold has been measured and the setter
   // refuses -1); a sharded handle keeps its term lists (rows_min = 0)
@@ -99,6 +104,13 @@ struct StagedPlan {
   std::vector<int> wr_ptr, wr_rows, ldE;
   std::vector<long long> oE, c_dst, h_kept, h_cut;
   long long oSr = 0;
+  struct Narrow {
+    std::vector<int> ptr, col, src;
+  };
+  Narrow cn, ctn;
+  long long c_kept = 0, c_cut = 0;
+  bool rows_vec() const { return !wr_rows.empty(); }  // step and residual take the wide rows through the blocks
+  void narrow_copies(const int *Cp, const int *Ci, const int *Cs, const int *CTp, const int *CTi, const int *CTs);
   int wide_count(int k) const { return wr_ptr.empty() ? 0 : wr_ptr[k + 1] - wr_ptr[k]; }
 
   // Dense stage Hessians (hqpkkt_set_hessian_form): Q_k of stage k = 0..K, order n_k + m_k (stage K: n_K), kept in full -

@@ -808,19 +808,23 @@ int residual_launch(hqpkkt_t *h, const Vecs &v) {
   unsigned long long *const rb_now = h->td.bits.p + 1, *const rb_next = h->td.bits.p - 1;
   const double *x1 = nullptr, *x2 = nullptr;  // STAGED, dense dynamics: their share of A dx and A'dy
   const double *xq = nullptr;                  // STAGED, dense stage Hessians: Q dx
+  // STAGED, wide rows of C: C_wide' dz and the wide rows' C dx, with the narrow copies of C' and C for the walks
+  const double *xcw = nullptr, *cw = nullptr;
+  CsrDev CT = h->td.CT.dev(), C = h->td.C.dev();
   int ndyn = 0;
   if (h->opts.mode == HQPKKT_MODE_STAGED) {
     int e1 = staged_dense_products(h, v, &x1, &x2, &ndyn, &xq);
     if (e1) return e1;
+    staged_rows_products(h, v, &xcw, &cw, &CT, &C);
   }
   if (h->short_rows)
     KLAUNCH(h, KC_RESIDUAL, k_residual<4><<<std::min(nblk(4LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p, v.z, v.w,
-        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq));
+        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), CT, h->td.A.dev(), C, h->td.vals.p, v.z, v.w,
+        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq, xcw, cw));
   else
     KLAUNCH(h, KC_RESIDUAL, k_residual<16><<<std::min(nblk(16LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p, v.z, v.w,
-        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq));
+        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), CT, h->td.A.dev(), C, h->td.vals.p, v.z, v.w,
+        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq, xcw, cw));
   return 0;
 }
 int run_residual(hqpkkt_t *h, const Vecs &v, double *res, const OutPtrs *out) {

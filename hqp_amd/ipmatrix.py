@@ -235,9 +235,9 @@ class Hqp_IpMatrix:
 
     def profile(self):
         """{kernel class: (summed device ms, launches)} since set_profile()."""
-        ms = (C.c_double * 16)()
-        ln = (C.c_longlong * 16)()
-        k = self._L.hqpkkt_get_profile(self._h, 16, ms, ln)
+        ms = (C.c_double * 64)()
+        ln = (C.c_longlong * 64)()
+        k = min(self._L.hqpkkt_get_profile(self._h, 64, ms, ln), 64)
         return {self._L.hqpkkt_profile_class_name(c).decode(): (ms[c], ln[c]) for c in range(k)}
 
     def set_stream(self, hip_stream):
@@ -347,7 +347,8 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     ``set_packed_panels(True)`` with it: the stages that run the profile sequence store F_k as packed panels, the rows of
     every panel's range alone (hqpkkt_set_packed_panels).  ``dense_rows=n`` or ``set_dense_rows(n)``, with any form of
     the dynamics: the rows of C with at least n entries leave the H term lists and go through the MFMA product as a
-    dense block per stage (hqpkkt_set_dense_rows; 0: none).  ``q_dense=True`` or ``set_hessian_form("dense")``, with any
+    dense block per stage, and step() and residuum() take them through the same block (hqpkkt_set_dense_rows; 0: none;
+    dense_row_products() reports the split).  ``q_dense=True`` or ``set_hessian_form("dense")``, with any
     form of the dynamics: the stage Hessians Q_k are kept as dense blocks instead of entries of the H term lists
     (hqpkkt_set_hessian_form); init() scatters the CSR values into them, init_dense() takes ``DenseDocp.Qd``."""
     _mode = _lib.MODE_STAGED
@@ -399,6 +400,16 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         K = len(self.debug(21))
         ptr, rows = d[: K + 2], d[K + 2:]
         return [rows[ptr[k]: ptr[k + 1]].tolist() for k in range(K + 1)]
+
+    def dense_row_products(self):
+        """How step() and residuum() take the wide rows of C (hqpkkt_debug_get 46): {"on": they go through the dense
+        blocks E_k, "rows": wide rows, "kept": stored entries of C left to the CSR walks, "removed": entries the blocks
+        hold instead}; {} unless the analysis found wide rows."""
+        d = self.debug(46).astype(np.int64)
+        if d.size == 0:
+            return {}
+        c = (d[2::2] & 0xFFFFFFFF) | (d[3::2] << 32)
+        return {"on": bool(d[0]), "rows": int(d[1]), "kept": int(c[0]), "removed": int(c[1])}
 
     def h_terms(self):
         """(kept, removed): per stage k = 0 .. K the H terms in the plan's lists and the terms the stage's wide rows
@@ -820,6 +831,47 @@ def gemv_dense(form, A, M, N, x, device=0, **kw):
     c, y, y2, _kept = _gemv_case(A, M, N, x, N if f == 2 else M, **kw)
     _check(_lib.lib().hqpkkt_debug_gemv_dense(device, f, C.byref(c)), "debug_gemv_dense")
     return y, y2, c.chunks, c.vec16
+
+
+ROWS_GEMV_FORMS = ("rows", "rows_step", "cols")
+
+
+def rows_gemv(form, blocks, E, row_index, n, m, x=None, t=None, tz=None, zw=None, r3=None, y=None, dz=None, dw=None, xc=None, device=0):
+    """One launch of a vector product of the wide rows of C (hqpkkt_debug_rows_gemv) on the caller's arrays.  blocks: per
+    block (rows, columns that count, leading dimension, offset into E, first entry of x of its column 0); E: float64, all
+    blocks; row_index: per row of every block, in their order, its index into the m-vectors.  form "rows": y[row] = E_b[i]
+    . x[col0:col0 + cols] (x: n, y: m); "rows_step": dz[row] = tz[row] - zw[row] cdx, dw[row] = -r3[row] + cdx; "cols":
+    xc[col0 + c] = sum_i E_b[i][c] t[row of i] (t: m, xc: n).  Results start from the arrays given (NaN where none is) and
+    keep every entry the launch does not own.  Returns y, (dz, dw) or xc."""
+    import numpy as np
+    f = ROWS_GEMV_FORMS.index(form)
+
+    def vec(v, k, fill=None):
+        if v is None:
+            return None if fill is None else np.full(k, fill)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert v.size == k
+        return v
+
+    ints = [np.ascontiguousarray([b[q] for b in blocks], dtype=np.int32) for q in (0, 1, 2, 4)]
+    off = np.ascontiguousarray([b[3] for b in blocks], dtype=np.int64)
+    E = np.ascontiguousarray(E, dtype=np.float64).ravel()
+    ri = np.ascontiguousarray(row_index, dtype=np.int32)
+    assert ri.size == int(ints[0].sum())
+    if ri.size == 0:
+        ri = np.zeros(1, np.int32)
+    x, t, tz, zw, r3 = vec(x, n), vec(t, m), vec(tz, m), vec(zw, m), vec(r3, m)
+    out = {"y": vec(y, m, np.nan) if f == 0 else None, "dz": vec(dz, m, np.nan) if f == 1 else None, "dw": vec(dw, m, np.nan) if f == 1 else None,
+           "xc": vec(xc, n, np.nan) if f == 2 else None}
+    out = {k: (None if v is None else v.copy()) for k, v in out.items()}
+    c = _lib.RowsCase()
+    c.nblocks, c.e_len, c.n, c.m = len(blocks), E.size, n, m
+    c.rows, c.cols, c.ld, c.col0 = (a.ctypes.data for a in ints)
+    c.off, c.E, c.row_index = off.ctypes.data, E.ctypes.data, ri.ctypes.data
+    for name, v in (("x", x), ("t", t), ("tz", tz), ("zw", zw), ("r3", r3), ("y", out["y"]), ("dz", out["dz"]), ("dw", out["dw"]), ("xc", out["xc"])):
+        setattr(c, name, None if v is None else v.ctypes.data)
+    _check(_lib.lib().hqpkkt_debug_rows_gemv(device, f, C.byref(c)), "debug_rows_gemv")
+    return out["y"] if f == 0 else (out["dz"], out["dw"]) if f == 1 else out["xc"]
 
 
 def symv(V, N, x, device=0, **kw):

@@ -363,8 +363,13 @@ int hqpkkt_set_dense_columns(hqpkkt_t *h, int min_entries);
  * up8(n_k + m_k) doubles in the F arena (stage K: up8(n_K)), hqpkkt_stats.bytes_panels counts it - and every factorisation
  * adds S'S with S = diag(sqrt(z / w)) E_k into the stage's work block as ONE fp64 MFMA product of depth r_k: one pass over
  * the block, whatever r_k L^2 is.  The square root goes into both operands, so V_k stays bit-for-bit symmetric; it asks for
- * z / w > 0, which an interior-point iterate gives.  Everything else of the rows - the right-hand sides, dz, dw, the
- * residual, the interior-point loops - walks C as before.  A stage with wide rows runs its control-sized chain on the
+ * z / w > 0, which an interior-point iterate gives.  The vector work of the wide rows goes through the blocks too:
+ * hqpkkt_step / hqpkkt_solve form q = C'tz - r1, dz and dw, and hqpkkt_residual (with the solve's refinement) forms C dx
+ * and C'dz, with the wide rows' share from two streaming kernels over E_k - a wavefront per wide row with 16-byte loads,
+ * and a thread per pair of columns for the transposed product; one launch over all stages each, sums in a fixed order -,
+ * while the CSR walks of these products take narrow copies of C and C' that do not hold the wide rows.  The
+ * interior-point loops' own right-hand-side kernels walk the whole of C as before; the solves they call take the
+ * blocks.  hqpkkt_debug_get 46 reports the split.  A stage with wide rows runs its control-sized chain on the
  * first stream and forms V_k by the separate update; every other stage runs exactly the launches it always has.
  * 0 (default): none - the plan, arenas, launches and bits of a handle that never asked.  -1, the library's threshold: no
  * threshold has been measured yet, HQPKKT_E_RANGE.  Host only; call it before hqpkkt_analyze or
@@ -606,6 +611,37 @@ int hqpkkt_debug_gemv_dense(int device, int form, hqpkkt_gemv_case *c);
 int hqpkkt_debug_symv(int device, hqpkkt_gemv_case *c);
 int hqpkkt_debug_symv_batch(int device, int count, hqpkkt_gemv_case *cases, const double *xbase, long long xbase_len, double *ybase, long long ybase_len,
                             int grid_tiles, int grid_fins);
+/* Test hook of the wide rows' vector products (hqpkkt_set_dense_rows; staged_rows.hip.h: k_st_rows_gemv, k_st_rows_gemv_t):
+ * ONE launch of either kernel on the caller's host arrays through the launch function the engine's step and residual
+ * call, host arrays back, nothing compared in the library.
+ * A case: nblocks blocks in one buffer E of e_len doubles.  Block b has rows[b] >= 0 rows of ld[b] doubles (a multiple of
+ * 8) from E + off[b] (even), of which the first cols[b] >= 1 columns count and meet x[col0[b] .. col0[b] + cols[b]); its
+ * rows are the next rows[b] entries of row_index (indices < m into the vectors that go by rows of C, no index twice).
+ *   form 0 (rows form, the residual's epilogue): y[row] = sum_c E_b[i][c] x[col0[b] + c] for every row of every block.
+ *     x: n doubles; y: m doubles, to the device before the launch and back after it.
+ *   form 1 (rows form, the step's epilogue): dz[row] = tz[row] - zw[row] cdx, dw[row] = -1.0 r3[row] + cdx with the same
+ *     cdx.  tz, zw, r3: m doubles; dz, dw: m doubles, both ways.
+ *   form 2 (columns form): xc[col0[b] + c] = sum_i E_b[i][c] t[row_index of row i], i ascending, for every c < cols[b] of
+ *     every block; zero where rows[b] = 0.  t: m doubles; xc: n doubles, both ways.
+ * On the device every vector the kernel reads (x, t, tz, zw, r3) has 64 NaN doubles behind its counted entries and every
+ * result 64 marked doubles: HQPKKT_E_INTERN where a mark has changed.  HQPKKT_E_NULL; HQPKKT_E_RANGE: an unknown form, a
+ * block outside E or x, ld no multiple of 8 or below cols, an odd off, a row index outside m; HQPKKT_E_DEVICE; HQPKKT_E_MEM. */
+typedef struct hqpkkt_rows_case {
+  int nblocks;
+  const int *rows, *cols, *ld, *col0;
+  const long long *off;
+  const double *E;
+  long long e_len;
+  const int *row_index;
+  int n, m;
+  const double *x;             /* forms 0, 1 */
+  const double *t;             /* form 2 */
+  const double *tz, *zw, *r3;  /* form 1 */
+  double *y;                   /* form 0 */
+  double *dz, *dw;             /* form 1 */
+  double *xc;                  /* form 2 */
+} hqpkkt_rows_case;
+int hqpkkt_debug_rows_gemv(int device, int form, hqpkkt_rows_case *c);
 /* Host only: the (row tile, column tile) of tile t = 0 .. tiles - 1 of the triangle form of order N, by the code the
  * kernel runs (64-row, 512-column tiles on and below the diagonal); pairs (or NULL): 2 ints per tile, written where
  * cap >= 2 tiles.  Returns the number of tiles. */
@@ -762,7 +798,11 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * columns unfinished, so that the guarded thin product formed the control rows of G, then per stage 1 where the W launch
  * takes the segment (decided at the upload); 45 the dense Hessians (hqpkkt_set_hessian_form): per stage 0 .. K four ints -
  * the block's order, its leading dimension, and the H terms left in the lists as a (low, high) pair; empty unless
- * HQPKKT_HESS_DENSE is set; valid after the analysis, without a device.
+ * HQPKKT_HESS_DENSE is set; valid after the analysis, without a device; 46 the wide rows' vector products
+ * (hqpkkt_set_dense_rows): six ints - 1 where hqpkkt_step and hqpkkt_residual take the wide rows through the blocks E_k
+ * (0: they walk C), the number of wide rows, and two 64-bit counts as (low, high) int pairs: the stored entries of C left
+ * in the narrow copy the CSR walks take, and the entries taken out; empty unless the analysis found wide rows; valid after
+ * the analysis, without a device.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

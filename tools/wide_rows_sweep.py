@@ -28,7 +28,8 @@ MAX_TERMS = 2 ** 31 - 1
 
 def time_handles(prog, handles, rounds=3):
     """{name: [ms_factor of `rounds` replayed factorisations]}, the handles taking turns; each one's residuum() and the
-    seconds its init() took."""
+    seconds its init() took; {name: {"step" / "residuum": [ms of `rounds` calls], "classes": {class: ms of one profiled
+    step + residuum}}}."""
     st = problems.ip_state(prog, 3, 1.0)
     res, init_s = {}, {}
     for name, M in handles.items():
@@ -45,7 +46,25 @@ def time_handles(prog, handles, rounds=3):
             M.factor(prog, st[0], st[1])
             if M.stats()["ms_factor"] > 0:  # (-1: the events gave no time)
                 ms[name].append(M.stats()["ms_factor"])
-    return ms, res, init_s
+    vec = {name: {"step": [], "residuum": [], "classes": {}} for name in handles}
+    d = {name: [np.zeros(k) for k in (prog.n, prog.me, prog.m, prog.m)] for name in handles}
+    for name, M in handles.items():  # (the first call captures the sequence)
+        M.step(prog, *st, *d[name])
+        M.residuum(prog, *st, *d[name])
+    for _ in range(rounds):
+        for name, M in handles.items():
+            M.step(prog, *st, *d[name])
+            vec[name]["step"].append(M.stats()["ms_step"])
+            M.residuum(prog, *st, *d[name])
+            vec[name]["residuum"].append(M.stats()["ms_residual"])
+    for name, M in handles.items():
+        M.set_profile(True)
+        M.step(prog, *st, *d[name])
+        M.residuum(prog, *st, *d[name])
+        prof = M.profile()
+        M.set_profile(False)
+        vec[name]["classes"] = {c: prof.get(c, (0.0, 0))[0] for c in ("vector", "residual", "staged_rows_gemv")}
+    return ms, res, init_s, vec
 
 
 def sweep(nx, K, entries=ENTRIES):
@@ -61,7 +80,7 @@ def sweep(nx, K, entries=ENTRIES):
             print(f"  {L:5d} | the lists would hold {terms:.2e} terms: HQPKKT_E_SIZES without the split")
             continue
         H = {"unsplit": ipmatrix.IpLQDOCP(), "split": ipmatrix.IpLQDOCP(dense_rows=L)}
-        ms, res, init_s = time_handles(prog, H)
+        ms, res, init_s, vec = time_handles(prog, H)
         assert [len(r) for r in H["split"].dense_rows()] == [16] * K + [0], H["split"].dense_rows()
         kept = int(H["split"].h_terms()[0].sum())
         entries_h = K * min(16 * L, nx) ** 2  # (at most: the rows' columns overlap)
@@ -69,6 +88,10 @@ def sweep(nx, K, entries=ENTRIES):
         print(f"  {L:5d} | {min(u) / K:8.3f} ({max(u) / K:7.3f}) | {min(s) / K:8.3f} ({max(s) / K:7.3f}) | {min(s) / min(u):6.3f}"
               f"          | {init_s['unsplit']:7.2f} {init_s['split']:7.2f}        | <= {(12 * (kept + terms) + 12 * entries_h) / 1e6:9.1f} {12 * kept / 1e6:7.1f}"
               f"   res {res['unsplit']:.1e} {res['split']:.1e}", flush=True)
+        for name in ("unsplit", "split"):
+            v = vec[name]
+            print(f"        {name:8s} ms: step {min(v['step']):8.3f} residuum {min(v['residuum']):8.3f} | profiled once, device ms by class: "
+                  + " ".join(f"{c} {t:.3f}" for c, t in v["classes"].items()), flush=True)
         del H
 
 

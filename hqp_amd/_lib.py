@@ -36,6 +36,7 @@ SYMBOLS = [
     "hqpkkt_set_packed_panels", "hqpkkt_debug_dgemm_packed", "hqpkkt_debug_gemv_packed", "hqpkkt_debug_carried_packed",
     "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
+    "hqpkkt_set_packed_hessians", "hqpkkt_debug_hess_symv_timed",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
@@ -206,6 +207,8 @@ def lib():
     L.hqpkkt_set_stage_hessian.argtypes = [vp, C.c_int, vp, C.c_longlong]
     L.hqpkkt_debug_stage_hessian.argtypes = [vp, C.c_int, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_hess_symv.argtypes = [vp, vp, vp]
+    L.hqpkkt_set_packed_hessians.argtypes = [vp, C.c_int]
+    L.hqpkkt_debug_hess_symv_timed.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

@@ -721,7 +721,7 @@ int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len) {
     case 9: v = &an.ent_ec; break;
     case 10: v = &an.node_owner; break;
     case 11: v = &an.xroots; break;
-    case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39: case 41: case 42: case 43: case 44: case 45: case 46: {  // STAGED
+    case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39: case 41: case 42: case 43: case 44: case 45: case 46: case 47: {  // STAGED
       const int e = staged_debug_get(h, what, tmp);
       if (e) return e;
       v = &tmp;

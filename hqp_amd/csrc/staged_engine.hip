@@ -12,12 +12,18 @@
 #include "staged_hess.hip.h"
 #include "staged_host.hip.h"
 
-// y = Q x over the dense stage Hessians of all stages, one launch (k_hs_symv)
+// y = Q x over the dense stage Hessians of all stages: one launch (k_hs_symv) for the stages that keep their dense block,
+// a launch pair (k_hp_symv_tiles, k_hp_symv_finish) for those stored as packed lower tiles
 static void staged_hess_symv(hqpkkt_t *h, StagedDev &d, const double *x, double *y) {
   const kktdev::StagedPlan &P = d.plan;
-  int nzmax = 1;
-  for (int k = 0; k <= P.K; k++) nzmax = std::max(nzmax, P.hess_order(k));
-  KLAUNCH(h, KC_RESIDUAL, stg::k_hs_symv<<<dim3(std::min((nzmax + 3) / 4, 1024), P.K + 1), 256, 0, h->stream>>>(d.hess_desc.p, d.Qd.p, x, y));
+  if (d.hs_nz_max > 0 || !P.hess_packed) {
+    const int nzmax = std::max(d.hs_nz_max, 1);
+    KLAUNCH(h, KC_RESIDUAL, stg::k_hs_symv<<<dim3(std::min((nzmax + 3) / 4, 1024), P.K + 1), 256, 0, h->stream>>>(d.hess_desc.p, d.Qd.p, x, y));
+  }
+  if (d.hp_chunks_max > 0) {
+    KLAUNCH(h, KC_RESIDUAL, stg::k_hp_symv_tiles<<<dim3(d.hp_chunks_max, P.K + 1), 256, 0, h->stream>>>(d.hp_desc.p, d.Qd.p, x, d.hess_scr.p));
+    KLAUNCH(h, KC_RESIDUAL, stg::k_hp_symv_finish<<<dim3(d.hp_nt_max, P.K + 1), stg::HP_T, 0, h->stream>>>(d.hp_desc.p, d.hess_scr.p, y));
+  }
 }
 int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const double **x2, int *ndyn, const double **xq) {
   StagedDev &d = *h->sd;
@@ -183,6 +189,19 @@ int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out) {
         out.push_back((int)(unsigned)(P.h_kept[k] & 0xffffffffLL)), out.push_back((int)(P.h_kept[k] >> 32));
       }
       break;
+    case 47:  // the packed lower tiles of the dense Hessians (hqpkkt_set_packed_hessians; host only): per stage 0 .. K eight ints -
+              // the tile edge (0: the stage keeps its dense block), the tiles stored, then as (low, high) ints the stage's arena
+              // elements, the doubles one dense hand-over of it moves from the caller, its share of the product's scratch;
+              // empty unless packing was analysed with the dense form
+      for (int k = 0; k <= P.K && P.hess_packed; k++) {
+        const int nz = P.hess_order(k);
+        const bool pk = P.stage_packed(k);
+        const long long nt = (nz + P.HESS_T - 1) / P.HESS_T, tiles = pk ? P.hess_tiles(nz) : 0;
+        out.push_back(pk ? P.HESS_T : 0), out.push_back((int)tiles);
+        for (long long c : {pk ? tiles * P.HESS_T * P.HESS_T : (long long)nz * P.ldQ[k], P.hess_handover(nz, pk), pk ? P.hess_slots(nt) * P.HESS_T : 0LL})
+          out.push_back((int)(unsigned)(c & 0xffffffffLL)), out.push_back((int)(c >> 32));
+      }
+      break;
     case 46:  // the wide rows' vector products (host only): 1 where step and residual take the wide rows through the blocks E_k, the
               // number of wide rows, then the stored entries of C left in the narrow copy of the CSR walks and the entries taken
               // out, each as (low, high) ints; empty unless the analysis found wide rows
@@ -253,6 +272,17 @@ int hqpkkt_set_hessian_form(hqpkkt_t *h, int form) {
     if (form != HQPKKT_HESS_CSR && form != HQPKKT_HESS_DENSE) return HQPKKT_E_RANGE;
     if (!h->sd) h->sd.reset(new StagedDev);
     h->sd->plan.want_hess_dense = form == HQPKKT_HESS_DENSE;  // (the next analysis picks it up)
+    return 0;
+  });
+}
+
+int hqpkkt_set_packed_hessians(hqpkkt_t *h, int on) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (h->opts.mode != HQPKKT_MODE_STAGED) return HQPKKT_E_INTERN;
+    if (on != 0 && on != 1) return HQPKKT_E_RANGE;
+    if (!h->sd) h->sd.reset(new StagedDev);
+    h->sd->plan.want_hess_packed = on != 0;  // (the next analysis picks it up; read with HQPKKT_HESS_DENSE alone)
     return 0;
   });
 }
@@ -423,7 +453,20 @@ int hqpkkt_set_stage_hessian(hqpkkt_t *h, int k, const double *Q, long long ldQ)
     if (ldQ < nz) return HQPKKT_E_SIZES;
     HIPCHK(hipSetDevice(h->opts.device));
     const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (nz > 0) {  // the caller's nz columns of every row, then the strict lower triangle from the upper one
+    if (nz > 0 && P.stage_packed(k)) {
+      // packed lower tiles: k_hp_pack reads a device block where it lies; of a host block the rows come in groups of
+      // HESS_COPY_ROWS, every group from its first column on, into the staging block (reused in stream order)
+      const double *src = Q;
+      long long lds = ldQ;
+      if (kind == hipMemcpyHostToDevice) {
+        if (d.hess_stage.count < (size_t)P.q_stage_elems && (e = d.hess_stage.alloc((size_t)P.q_stage_elems))) return e;
+        lds = P.ldQ[k], src = d.hess_stage.p;
+        for (int r = 0; r < nz; r += P.HESS_COPY_ROWS)
+          HIPCHK(hipMemcpy2DAsync(d.hess_stage.p + (long long)r * lds + r, sizeof(double) * lds, Q + (long long)r * ldQ + r, sizeof(double) * ldQ,
+                                  sizeof(double) * (nz - r), std::min(P.HESS_COPY_ROWS, nz - r), kind, h->stream));
+      }
+      stg::k_hp_pack<<<dim3((unsigned)P.hess_tiles(nz), 16), 256, 0, h->stream>>>(src, lds, nz, d.Qd.p + P.oQ[k]);
+    } else if (nz > 0) {  // the caller's nz columns of every row, then the strict lower triangle from the upper one
       double *dst = d.Qd.p + P.oQ[k];
       HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * P.ldQ[k], Q, sizeof(double) * ldQ, sizeof(double) * nz, nz, kind, h->stream));
       const unsigned T = (unsigned)((nz + stg::HS_TILE - 1) / stg::HS_TILE);
@@ -453,6 +496,19 @@ int hqpkkt_debug_stage_hessian(hqpkkt_t *h, int k, double *out, long long cap, l
     if (cap < elems) return HQPKKT_E_SIZES;
     HIPCHK(hipSetDevice(h->opts.device));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (elems && P.stage_packed(k)) {  // the unpacked view: entry (i, j) out of its stored tile, zero padding
+      const int T = P.HESS_T, nz = P.hess_order(k);
+      std::vector<double> t((size_t)P.hess_tiles(nz) * T * T);
+      HIPCHK(hipMemcpy(t.data(), h->sd->Qd.p + P.oQ[k], sizeof(double) * t.size(), hipMemcpyDeviceToHost));
+      std::fill(out, out + elems, 0.0);
+      for (int i = 0; i < nz; i++)
+        for (int j = 0; j < nz; j++) {
+          const int a = std::max(i, j) / T, b = std::min(i, j) / T;
+          const size_t tile = ((size_t)a * (a + 1) / 2 + b) * T * T;
+          out[(long long)i * P.ldQ[k] + j] = i / T >= j / T ? t[tile + (size_t)(i % T) * T + j % T] : t[tile + (size_t)(j % T) * T + i % T];
+        }
+      return 0;
+    }
     if (elems) HIPCHK(hipMemcpy(out, h->sd->Qd.p + P.oQ[k], sizeof(double) * elems, hipMemcpyDeviceToHost));
     return 0;
   });
@@ -473,6 +529,33 @@ int hqpkkt_debug_hess_symv(hqpkkt_t *h, const double *x, double *y) {
     staged_hess_symv(h, d, d.hess_x.p, d.hess_y.p);
     HIPCHK(hipMemcpyAsync(y, d.hess_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int hqpkkt_debug_hess_symv_timed(hqpkkt_t *h, const double *x, double *y, int reps, double *ms) {
+  return guarded([&]() -> int {
+    if (!h || !x || !y || !ms) return HQPKKT_E_NULL;
+    if (reps < 1) return HQPKKT_E_RANGE;
+    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    const size_t n = (size_t)d.plan.n;
+    HIPCHK(hipSetDevice(h->opts.device));
+    int e;
+    if (!d.hess_x.p && (e = d.hess_x.alloc(n + 1))) return e;
+    EventOwner t0, t1;
+    HIPCHK(hipEventCreate(&t0.h));
+    HIPCHK(hipEventCreate(&t1.h));
+    HIPCHK(hipMemcpyAsync(d.hess_x.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    staged_hess_symv(h, d, d.hess_x.p, d.hess_y.p);  // (one product ahead of the timed ones)
+    HIPCHK(hipEventRecord(t0, h->stream));
+    for (int r = 0; r < reps; r++) staged_hess_symv(h, d, d.hess_x.p, d.hess_y.p);
+    HIPCHK(hipEventRecord(t1, h->stream));
+    HIPCHK(hipMemcpyAsync(y, d.hess_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, t0, t1));
+    *ms = (double)t / reps;
     return 0;
   });
 }

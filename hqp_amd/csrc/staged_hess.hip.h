@@ -116,3 +116,5 @@ __global__ void __launch_bounds__(256) k_hs_symv(const HessDesc *__restrict__ de
 }
 
 }  // namespace stg
+
+#include "staged_hess_packed.hip.h"  // (the same blocks stored as packed lower tiles)

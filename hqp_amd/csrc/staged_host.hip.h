@@ -73,6 +73,12 @@ struct StagedDev {
   DBuf<long long> q_dst;
   DBuf<stg::HessDesc> hess_desc;
   std::vector<char> hess_set;           // dense hand-over: which blocks Q_k have arrived since the analysis
+  // ... as packed lower tiles (StagedPlan::hess_packed): per stage what k_hp_symv_tiles needs, the slots of that product, the
+  // staging block of a dense hand-over from host memory (made by its first call; reused in stream order); the launches'
+  // extents: most chunks of tiles and tile rows of a packed stage, largest order of a stage that keeps its dense block (0: none)
+  DBuf<stg::HpDesc> hp_desc;
+  DBuf<double> hess_scr, hess_stage;
+  int hp_chunks_max = 0, hp_nt_max = 0, hs_nz_max = 0;
   // one system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
   // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack; the local dynamics blocks of
   // residuum()'s products and their summed results (A_dyn' dy: n, A_dyn dx: ndyn)
@@ -399,6 +405,12 @@ static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G,
 static void st_add_q(hqpkkt_t *h, StagedDev &d, int k, int r0, int r1, int c1, int lower, double *G, long long ldg) {
   const kktdev::StagedPlan &P = d.plan;
   if (!P.hess_dense || r1 <= r0 || c1 <= 0) return;
+  if (P.stage_packed(k)) {  // the stored tiles of the tile rows the request or its image reaches (k_hp_add)
+    const int T = stg::HP_T, a0 = r0 / T, a1 = lower ? (r1 - 1) / T : std::max(r1 - 1, c1 - 1) / T;
+    const unsigned tiles = (unsigned)((a1 + 1) * (a1 + 2) / 2 - a0 * (a0 + 1) / 2);
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_hp_add<<<dim3(tiles, 16), 256, 0, h->stream>>>(stg::HpAdd{d.Qd.p + P.oQ[k], G, ldg, r0, r1, c1, lower, a0}));
+    return;
+  }
   const dim3 grid((unsigned)nblk((c1 + 1) / 2), (unsigned)std::min(r1 - r0, 1024));
   KLAUNCH(h, KC_ASSEMBLE, stg::k_hs_add<<<grid, 256, 0, h->stream>>>(
                               stg::HsAdd{d.Qd.p + P.oQ[k], P.ldQ[k], G, ldg, r0, r1, c1, lower}));
@@ -541,10 +553,10 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
   const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
   const int want_heavy = P.want_heavy, want_rows = P.want_rows;
-  const bool want_packed = P.want_packed, want_hess_dense = P.want_hess_dense;
+  const bool want_packed = P.want_packed, want_hess_dense = P.want_hess_dense, want_hess_packed = P.want_hess_packed;
   P = kktdev::StagedPlan();
   P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed, P.want_rows = want_rows;
-  P.want_hess_dense = want_hess_dense;
+  P.want_hess_dense = want_hess_dense, P.want_hess_packed = want_hess_packed;
   P.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
   P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
@@ -663,7 +675,22 @@ static int staged_upload(hqpkkt_t *h) {
   }
   if (P.hess_dense) {  // the blocks Q_k, cleared once: the scatter and the store write the entries alone
     std::vector<stg::HessDesc> hd(P.K + 1);
-    for (int k = 0; k <= P.K; k++) hd[k] = stg::HessDesc{P.oQ[k], P.ldQ[k], P.hess_order(k), P.nmk[k], 0};
+    for (int k = 0; k <= P.K; k++) hd[k] = stg::HessDesc{P.oQ[k], P.ldQ[k], P.stage_packed(k) ? 0 : P.hess_order(k), P.nmk[k], 0};
+    d.hp_chunks_max = d.hp_nt_max = d.hs_nz_max = 0;
+    for (int k = 0; k <= P.K; k++)
+      if (!P.stage_packed(k)) d.hs_nz_max = std::max(d.hs_nz_max, P.hess_order(k));
+    if (P.hess_packed) {  // (packed stages: nz = 0 in k_hs_symv's list; the others: no tiles in k_hp_symv_tiles')
+      std::vector<stg::HpDesc> pd(P.K + 1);
+      for (int k = 0; k <= P.K; k++) {
+        const int nt = P.stage_packed(k) ? (P.hess_order(k) + stg::HP_T - 1) / stg::HP_T : 0;
+        int nchunks = 0;
+        for (int a = 0; a < nt; a++) nchunks += stg::hp_chunks(a);
+        pd[k] = stg::HpDesc{P.oQ[k], P.oQs[k], nt, P.hess_order(k), P.nmk[k], nchunks};
+        d.hp_nt_max = std::max(d.hp_nt_max, nt), d.hp_chunks_max = std::max(d.hp_chunks_max, nchunks);
+      }
+      static_assert(stg::HP_T == kktdev::StagedPlan::HESS_T && stg::HP_CHUNK == kktdev::StagedPlan::HESS_CHUNK, "the plan sizes the tiles and the scratch");
+      if ((e = d.hp_desc.upload(pd)) || (e = d.hess_scr.alloc((size_t)P.qs_elems + 16))) return e;
+    }
     if ((e = d.Qd.alloc((size_t)P.q_elems + 16)) || (e = d.hess_desc.upload(hd)) || (e = d.hess_y.alloc((size_t)n + 1)) ||
         (!P.q_dst.empty() && (e = d.q_dst.upload(P.q_dst))))
       return e;

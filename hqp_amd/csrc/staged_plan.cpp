@@ -67,6 +67,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   if (profile_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
   nq = n ? Qp[n] : 0, nc = m ? Cp[m] : 0;
   hess_dense = want_hess_dense;
+  hess_packed = hess_dense && want_hess_packed;
   const int arows = me_;  // rows of the A that was handed over
   na = arows ? Ap[arows] : 0;
   nk.clear(), mk.clear(), nmk.clear(), nks.clear();
@@ -384,19 +385,37 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   }
   // ------------------------------------------------------------------ dense stage Hessians
   ldQ.clear(), oQ.clear(), q_dst.clear(), q_elems = 0;
+  q_packed.clear(), oQs.clear(), qs_elems = q_stage_elems = 0;
   if (hess_dense) {
     ldQ.assign(K + 1, 8), oQ.assign(K + 1, 0);
+    if (hess_packed) q_packed.assign(K + 1, 0), oQs.assign(K + 1, 0);
     for (int k = 0; k <= K; k++) {
-      ldQ[k] = up8(hess_order(k));
-      oQ[k] = q_elems, q_elems += (long long)hess_order(k) * ldQ[k];
+      const int nz = hess_order(k);
+      ldQ[k] = up8(nz);
+      oQ[k] = q_elems;
+      if (hess_packed && hess_packs(nz)) {  // the tiles on and below the diagonal, back to back
+        const long long nt = (nz + HESS_T - 1) / HESS_T;
+        q_packed[k] = 1, q_elems += hess_tiles(nz) * HESS_T * HESS_T;
+        oQs[k] = qs_elems, qs_elems += hess_slots(nt) * HESS_T;
+        q_stage_elems = std::max(q_stage_elems, (long long)nz * ldQ[k]);
+      } else
+        q_elems += (long long)nz * ldQ[k];
     }
     q_dst.assign(2 * (size_t)nq, -1);
     for (int i = 0; i < n; i++)
       for (int p = Qp[i]; p < Qp[i + 1]; p++) {
         const int j = Qi[p], k = stage_of[i];
         if (j < i) continue;  // only col >= row is read
-        q_dst[2 * (size_t)p] = oQ[k] + (long long)lcol(i) * ldQ[k] + lcol(j);
-        if (j != i) q_dst[2 * (size_t)p + 1] = oQ[k] + (long long)lcol(j) * ldQ[k] + lcol(i);
+        const int li = lcol(i), lj = lcol(j);
+        if (stage_packed(k)) {  // (i, j), j >= i, lies in tile (j / T, i / T) at (j % T, i % T); a diagonal tile holds its image too
+          const int T = HESS_T, a = lj / T, b = li / T;
+          const long long tile = oQ[k] + ((long long)a * (a + 1) / 2 + b) * T * T;
+          q_dst[2 * (size_t)p] = tile + (long long)(lj % T) * T + li % T;
+          if (a == b && j != i) q_dst[2 * (size_t)p + 1] = tile + (long long)(li % T) * T + lj % T;
+          continue;
+        }
+        q_dst[2 * (size_t)p] = oQ[k] + (long long)li * ldQ[k] + lj;
+        if (j != i) q_dst[2 * (size_t)p + 1] = oQ[k] + (long long)lj * ldQ[k] + li;
       }
   }
   // ------------------------------------------------------------------ one system over several ranks (staged_plan.hpp)

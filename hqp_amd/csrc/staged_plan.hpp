@@ -4,6 +4,7 @@
 // constraint rows, storage plan of the dense stage blocks, term lists of the reduced
 // Hessian H = Q + C'(Z/W)C and the scatter maps of the CSR values.  Integer work only.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <vector>
 
@@ -123,6 +124,38 @@ struct StagedPlan {
   std::vector<long long> oQ, q_dst;
   long long q_elems = 0;
   int hess_order(int k) const { return k < K ? nk[k] + mk[k] : nk[k]; }
+  // ... stored as packed lower tiles (hqpkkt_set_packed_hessians; with hess_dense alone): stage k with q_packed[k] keeps, at
+  // oQ[k], the tiles (a, b), b <= a < nt = ceil(order / HESS_T), each HESS_T rows of HESS_T doubles, zero padded, tile
+  // (a, b) at (a (a + 1) / 2 + b) HESS_T^2; a diagonal tile holds both of its triangles.  A stage packs only where that is
+  // fewer doubles than its dense block - not monotone in the order: 220 .. 256 pack, 257 .. 312 do not, 313 .. 384 do, 385 does not, 402 does.
+  // q_dst then holds the packed places (the image: inside a diagonal tile alone).  oQs[k]: the stage's hess_slots(nt) HESS_T
+  // doubles of the product's scratch (qs_elems in all) - per row tile r one slot per HESS_CHUNK tiles of its own row and one
+  // per tile (a, r) below it, a little over nt^2 / 2 slots (staged_hess_packed.hip.h); q_stage_elems: the staging block of the dense hand-over from host
+  // memory, order x up8(order) of the largest packed stage.  want_hess_packed: what the next analysis takes
+  static const int HESS_T = 128, HESS_COPY_ROWS = 64, HESS_CHUNK = 8;
+  static long long hess_slots(long long nt) {
+    long long s = 0;
+    for (long long r = 0; r < nt; r++) s += (r + HESS_CHUNK) / HESS_CHUNK + nt - 1 - r;
+    return s;
+  }
+  bool want_hess_packed = false, hess_packed = false;
+  std::vector<char> q_packed;
+  std::vector<long long> oQs;
+  long long qs_elems = 0, q_stage_elems = 0;
+  bool stage_packed(int k) const { return hess_packed && q_packed[k]; }
+  static long long hess_tiles(int order) {
+    const long long nt = (order + HESS_T - 1) / HESS_T;
+    return nt * (nt + 1) / 2;
+  }
+  static bool hess_packs(int order) { return hess_tiles(order) * HESS_T * HESS_T < (long long)order * ((order + 7) / 8 * 8); }
+  // doubles one dense hand-over of a block moves from host memory: a packed stage's rows in groups of HESS_COPY_ROWS,
+  // every group from its first column on (order (order + HESS_COPY_ROWS) / 2, about); order^2 where the block stays dense
+  static long long hess_handover(int order, bool packed_) {
+    if (!packed_) return (long long)order * order;
+    long long c = 0;
+    for (int r = 0; r < order; r += HESS_COPY_ROWS) c += (long long)std::min(HESS_COPY_ROWS, order - r) * (order - r);
+    return c;
+  }
 
   // static bounds: cap[k] carried rows leaving stage k, capn[k] rows of N_k, qmax[k] order of K_k
   std::vector<int> cap, capn, qmax;

@@ -350,12 +350,16 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     dense block per stage, and step() and residuum() take them through the same block (hqpkkt_set_dense_rows; 0: none;
     dense_row_products() reports the split).  ``q_dense=True`` or ``set_hessian_form("dense")``, with any
     form of the dynamics: the stage Hessians Q_k are kept as dense blocks instead of entries of the H term lists
-    (hqpkkt_set_hessian_form); init() scatters the CSR values into them, init_dense() takes ``DenseDocp.Qd``."""
+    (hqpkkt_set_hessian_form); init() scatters the CSR values into them, init_dense() takes ``DenseDocp.Qd``.
+    ``q_packed=True`` or ``set_packed_hessians(True)`` with it: the blocks are stored as their 128 x 128 tiles on and below
+    the diagonal wherever that is smaller (hqpkkt_set_packed_hessians; hessian_packing() reports the layout)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
-    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, dense_rows=0, q_dense=False, **kw):
+    def __init__(self, *args, a_sparse=False, dense_columns=0, a_profile=False, a_packed=False, dense_rows=0, q_dense=False, q_packed=False, **kw):
         super().__init__(*args, **kw)
+        if q_packed:
+            self.set_packed_hessians(True)
         if q_dense:
             self.set_hessian_form("dense")
         if a_sparse:
@@ -483,6 +487,30 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         y = np.zeros(self.n)
         _check(self._L.hqpkkt_debug_hess_symv(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data)), "hess_symv")
         return y
+
+    def hess_symv_timed(self, x, reps):
+        """(y, ms): y = Q x and the average device time in ms of ``reps`` such products as the residual launches them."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == self.n
+        y, ms = np.zeros(self.n), C.c_double()
+        _check(self._L.hqpkkt_debug_hess_symv_timed(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data), int(reps), C.byref(ms)),
+               "hess_symv_timed")
+        return y, ms.value
+
+    def set_packed_hessians(self, on):
+        """Dense stage Hessians stored as packed lower tiles (hqpkkt_set_packed_hessians); holds from the next init() on."""
+        _check(self._L.hqpkkt_set_packed_hessians(self._h, int(on)), "set_packed_hessians")
+
+    def hessian_packing(self):
+        """Per stage k = 0 .. K (tile edge or 0 where the stage keeps its dense block, tiles stored, arena elements, doubles
+        one dense hand-over moves from the caller's host block, doubles of the product's scratch), an int64 array of shape
+        (K + 1, 5); [] unless packing was analysed with the dense form of the Hessians."""
+        d = self.debug(47)
+        if d.size == 0:
+            return []
+        d = d.astype(np.int64).reshape(-1, 8)
+        c = (d[:, 2::2] & 0xFFFFFFFF) | (d[:, 3::2] << 32)
+        return np.concatenate([d[:, :2], c], axis=1)
 
     def set_packed_panels(self, on):
         """Packed panels of the profile form (hqpkkt_set_packed_panels); holds from the next init() on."""

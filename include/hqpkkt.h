@@ -406,10 +406,37 @@ int hqpkkt_set_dense_rows(hqpkkt_t *h, int min_entries);
 #define HQPKKT_HESS_DENSE 1 /* Q_k kept as a dense block per stage 0 .. K */
 int hqpkkt_set_hessian_form(hqpkkt_t *h, int form);
 int hqpkkt_set_stage_hessian(hqpkkt_t *h, int k, const double *Q, long long ldQ);
-/* tests: block k of the dense Hessians as it lies in the arena (nz_k rows of up8(nz_k) doubles); out null: *len alone */
+/* tests: block k of the dense Hessians as it lies in the arena (nz_k rows of up8(nz_k) doubles; of a stage stored as packed
+ * tiles the same view, unpacked); out null: *len alone */
 int hqpkkt_debug_stage_hessian(hqpkkt_t *h, int k, double *out, long long cap, long long *len);
-/* tests: y = Q x over all stage blocks by the kernel of the residual; x, y host arrays of n */
+/* tests: y = Q x over all stage blocks by the kernels of the handle's residual; x, y host arrays of n */
 int hqpkkt_debug_hess_symv(hqpkkt_t *h, const double *x, double *y);
+/* tests and measurement: the average device time in ms, by HIP events on the handle's stream, of `reps` (>= 1:
+ * HQPKKT_E_RANGE otherwise) products Q x as the residual launches them, one untimed product ahead; x, y host arrays of n,
+ * y the product; on packed and unpacked handles alike */
+int hqpkkt_debug_hess_symv_timed(hqpkkt_t *h, const double *x, double *y, int reps, double *ms);
+/* The dense stage Hessians stored as packed lower tiles.  hqpkkt_set_hessian_form(HQPKKT_HESS_DENSE) keeps both triangles of
+ * every Q_k although the caller hands over the entries j >= i alone; with on = 1 a stage keeps of its block the tiles (a, b),
+ * b <= a < nt = ceil(nz_k / 128), of edge T = 128 - the tile of the stage products -, each T rows of T doubles, row-major,
+ * zero padded past nz_k, back to back in the order a (a + 1) / 2 + b; a diagonal tile holds both of its triangles, bit for
+ * bit symmetric.  A stage is packed only where that is smaller, nt (nt + 1) / 2 T^2 < nz_k up8(nz_k); every other stage
+ * keeps its dense block exactly as without the call, so hqpkkt_stats.bytes_panels never grows.  The rule is not monotone in
+ * nz_k: the orders 220 .. 256 pack (three tiles), 257 .. 312 do not, 313 is the first order of three tile rows that packs,
+ * 384 packs, 385 does not, 402 does; a block of order 5050 takes 0.526 of its dense arena, large ones tend to one
+ * half.  Every user of the blocks works from the tiles: the dense hand-over packs the
+ * caller's block (of a host block only the rows' columns from the first column of their group of 64 rows on are moved,
+ * about nz_k (nz_k + 64) / 2 doubles, through one device staging block of the largest packed stage's size;
+ * hqpkkt_stage_staging keeps its size and meaning), the CSR hand-over scatters to the packed places, the factorisation
+ * adds the tiles and, where the dense form adds an upper tile, their transposes - every entry of the work block receives
+ * the one add of the value the dense form adds, so factor and step are bit-identical to the unpacked dense form -, and
+ * the products Q x load every stored element once for its row's and its column's sum, with a scratch of a little over nt^2 / 2
+ * slots of T doubles per packed stage and a fixed order of the sums (not the order of the unpacked form: the products agree to rounding).
+ * Host only; call it before the analysis; it holds until it is set again.  It has an effect together with
+ * HQPKKT_HESS_DENSE alone: with HQPKKT_HESS_CSR it is accepted and ignored.  0 (default) is the plan, arenas, launches and
+ * bits of a handle that never asked.  HQPKKT_E_NULL; HQPKKT_E_INTERN: the handle's mode is not STAGED; HQPKKT_E_RANGE: on is
+ * neither 0 nor 1.  hqpkkt_debug_get 47 reports the layout; 45 keeps reporting the order and up8(order), and
+ * hqpkkt_debug_stage_hessian returns the unpacked view of a packed stage. */
+int hqpkkt_set_packed_hessians(hqpkkt_t *h, int on);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense
@@ -802,7 +829,11 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * (hqpkkt_set_dense_rows): six ints - 1 where hqpkkt_step and hqpkkt_residual take the wide rows through the blocks E_k
  * (0: they walk C), the number of wide rows, and two 64-bit counts as (low, high) int pairs: the stored entries of C left
  * in the narrow copy the CSR walks take, and the entries taken out; empty unless the analysis found wide rows; valid after
- * the analysis, without a device.
+ * the analysis, without a device; 47 the packed lower tiles of the dense Hessians (hqpkkt_set_packed_hessians): per stage
+ * 0 .. K eight ints - the tile edge T (0 where the stage keeps its dense block), the tiles stored, and three 64-bit counts
+ * as (low, high) int pairs: the arena elements of the stage, the doubles one dense hand-over of the stage moves from the
+ * caller's host block, the stage's share of the product's scratch; empty unless packing was analysed together with
+ * HQPKKT_HESS_DENSE; valid after the analysis, without a device.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

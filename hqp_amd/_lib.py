@@ -18,6 +18,7 @@ MODE_FULL, MODE_REDUCED, MODE_STAGED = 0, 1, 2
 LOC_HOST, LOC_DEVICE = 0, 1
 DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
 HESS_CSR, HESS_DENSE = 0, 1
+HQPKKT_HESS_UPDATE_RANK = 4
 
 # every symbol include/hqpkkt.h declares
 SYMBOLS = [
@@ -37,6 +38,7 @@ SYMBOLS = [
     "hqpkkt_set_dense_rows", "hqpkkt_debug_dgemm_ctrl_rows", "hqpkkt_debug_sk_ctrl_rows",
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
     "hqpkkt_set_packed_hessians", "hqpkkt_debug_hess_symv_timed",
+    "hqpkkt_update_stage_hessians", "hqpkkt_hessian_product",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
@@ -56,6 +58,10 @@ class Opts(C.Structure):
                 ("max_pivots", C.c_int), ("zd_policy", C.c_int), ("slack_policy", C.c_int),
                 ("no_small_fronts", C.c_int), ("upd_pingpong_mb", C.c_int), ("amalgamation", C.c_int),
                 ("ordering", C.c_int)]
+
+
+class HessUpdate(C.Structure):  # hqpkkt_hess_update
+    _fields_ = [("r", C.c_int), ("U", C.POINTER(C.c_void_p)), ("coef", C.c_void_p), ("beta", C.c_void_p), ("diag", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -209,6 +215,8 @@ def lib():
     L.hqpkkt_debug_hess_symv.argtypes = [vp, vp, vp]
     L.hqpkkt_set_packed_hessians.argtypes = [vp, C.c_int]
     L.hqpkkt_debug_hess_symv_timed.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
+    L.hqpkkt_update_stage_hessians.argtypes = [vp, C.POINTER(HessUpdate)]
+    L.hqpkkt_hessian_product.argtypes = [vp, vp, vp]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

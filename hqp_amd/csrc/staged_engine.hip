@@ -560,6 +560,95 @@ int hqpkkt_debug_hess_symv_timed(hqpkkt_t *h, const double *x, double *y, int re
   });
 }
 
+int hqpkkt_hessian_product(hqpkkt_t *h, const double *x, double *y) {
+  if (h && h->opts.loc != HQPKKT_LOC_DEVICE) return hqpkkt_debug_hess_symv(h, x, y);  // (host vectors: the hook's own path)
+  return guarded([&]() -> int {
+    if (!h || !x || !y) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    HIPCHK(hipSetDevice(h->opts.device));
+    staged_hess_symv(h, *h->sd, x, y);  // (the same launches on the caller's vectors)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u) {
+  return guarded([&]() -> int {
+    if (!h || !u) return HQPKKT_E_NULL;
+    static_assert(stg::HU_RANK == HQPKKT_HESS_UPDATE_RANK, "the kernel's descriptor holds the coefficients");
+    const int r = u->r;
+    if (r < 0 || r > HQPKKT_HESS_UPDATE_RANK) return HQPKKT_E_RANGE;
+    if (r > 0 && (!u->U || !u->coef)) return HQPKKT_E_NULL;
+    for (int j = 0; j < r; j++)
+      if (!u->U[j]) return HQPKKT_E_NULL;
+    if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd || !h->sd->plan.dense_dyn || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    const int K1 = P.K + 1;
+    for (int k = 0; k < K1; k++) {
+      if (u->beta && !std::isfinite(u->beta[k])) return HQPKKT_E_RANGE;
+      for (int j = 0; j < r; j++)
+        if (!std::isfinite(u->coef[(size_t)k * r + j])) return HQPKKT_E_RANGE;
+    }
+    // the launch's descriptors; a stage with beta = 1, every coefficient 0 and no diagonal is left alone (units = 0)
+    std::vector<stg::HuDesc> hd(K1);
+    int units_max = 0;
+    for (int k = 0; k < K1; k++) {
+      const double beta = u->beta ? u->beta[k] : 1.0;
+      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
+      const bool packed = P.stage_packed(k);
+      stg::HuDesc &q = hd[k];
+      q = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, 0, beta == 0.0 ? 0 : beta == 1.0 ? 1 : 2, 0, beta, {0.0, 0.0, 0.0, 0.0}};
+      bool touched = beta != 1.0 || u->diag;
+      for (int j = 0; j < r; j++) q.c[j] = u->coef[(size_t)k * r + j], touched = touched || q.c[j] != 0.0;
+      if (!touched || nz == 0) continue;
+      // (the hand-over rule: what is kept of a block must have arrived since the analysis)
+      if (beta != 0.0 && ((int)d.hess_set.size() != K1 || !d.hess_set[k])) return HQPKKT_E_INTERN;
+      q.units = packed ? (int)P.hess_tiles(nz) : nt * nt;
+      units_max = std::max(units_max, q.units);
+    }
+    int e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    if (units_max > 0) {
+      const size_t n = (size_t)P.n;
+      stg::HuVecs V{};
+      V.r = r;
+      if (h->opts.loc == HQPKKT_LOC_DEVICE) {
+        for (int j = 0; j < r; j++) V.u[j] = u->U[j];
+        V.diag = u->diag;
+      } else {  // a host caller's vectors through the handle's own buffer
+        if (!d.hu_vec.p && (e = d.hu_vec.alloc((size_t)(stg::HU_RANK + 1) * n + 1))) return e;
+        for (int j = 0; j < r; j++) {
+          HIPCHK(hipMemcpyAsync(d.hu_vec.p + j * n, u->U[j], sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+          V.u[j] = d.hu_vec.p + j * n;
+        }
+        if (u->diag) {
+          HIPCHK(hipMemcpyAsync(d.hu_vec.p + stg::HU_RANK * n, u->diag, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+          V.diag = d.hu_vec.p + stg::HU_RANK * n;
+        }
+      }
+      if (!d.hu_desc.p) {
+        if ((e = d.hu_desc.alloc((size_t)K1))) return e;
+        HIPCHK(d.hu_hdesc.alloc((size_t)K1, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&d.hu_ev.h, hipEventDisableTiming));
+      } else
+        HIPCHK(hipEventSynchronize(d.hu_ev));  // (the copy of the last call's descriptors out of the pinned words)
+      std::copy(hd.begin(), hd.end(), d.hu_hdesc.p);
+      HIPCHK(hipMemcpyAsync(d.hu_desc.p, d.hu_hdesc.p, sizeof(stg::HuDesc) * K1, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipEventRecord(d.hu_ev, h->stream));
+      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hu_desc.p, d.Qd.p, V));
+      HIPCHK(hipGetLastError());
+      if (h->opts.loc != HQPKKT_LOC_DEVICE) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vectors are free again)
+    }
+    if ((int)d.hess_set.size() != K1) d.hess_set.assign(K1, 0);
+    for (int k = 0; k < K1; k++)
+      if (hd[k].mode == 0) d.hess_set[k] = 1;  // (beta = 0: the block has been made here)
+    h->factored = false;
+    return 0;
+  });
+}
+
 // STAGED: rank and number of carried rows of every stage in the last factorisation
 // (2 ints per stage, K+1 stages); tests only
 int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap) {

@@ -5,6 +5,7 @@
 //   assembly  k_hs_add: a rectangle of Q_k added into the stage's work block G or into V_k, one read of Q and one
 //             read-modify-write of the target, 16 bytes per lane
 //   products  k_hs_symv: y = Q x over all stages in one launch, a wavefront per row, a fixed order of the sums
+//   update    k_hu_update (staged_hess_update.hip.h): Q_k <- beta_k Q_k + diag(d_k) + sum_j c_kj u_j u_j' in place
 // Plain loads and stores: no polled words, no waits between workgroups, no atomics.  Included by staged_engine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -118,3 +119,4 @@ __global__ void __launch_bounds__(256) k_hs_symv(const HessDesc *__restrict__ de
 }  // namespace stg
 
 #include "staged_hess_packed.hip.h"  // (the same blocks stored as packed lower tiles)
+#include "staged_hess_update.hip.h"  // (both layouts updated in place: hqpkkt_update_stage_hessians)

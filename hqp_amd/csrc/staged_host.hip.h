@@ -79,6 +79,13 @@ struct StagedDev {
   DBuf<stg::HpDesc> hp_desc;
   DBuf<double> hess_scr, hess_stage;
   int hp_chunks_max = 0, hp_nt_max = 0, hs_nz_max = 0;
+  // ... updated in place (hqpkkt_update_stage_hessians; all made by its first call): the per-stage descriptors of the launch,
+  // written to pinned memory and copied from there in the handle's stream (hu_ev: that copy is over, the pinned words may be
+  // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n)
+  PinnedBuf<stg::HuDesc> hu_hdesc;
+  DBuf<stg::HuDesc> hu_desc;
+  EventOwner hu_ev;
+  DBuf<double> hu_vec;
   // one system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
   // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack; the local dynamics blocks of
   // residuum()'s products and their summed results (A_dyn' dy: n, A_dyn dx: ndyn)

@@ -352,7 +352,10 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     form of the dynamics: the stage Hessians Q_k are kept as dense blocks instead of entries of the H term lists
     (hqpkkt_set_hessian_form); init() scatters the CSR values into them, init_dense() takes ``DenseDocp.Qd``.
     ``q_packed=True`` or ``set_packed_hessians(True)`` with it: the blocks are stored as their 128 x 128 tiles on and below
-    the diagonal wherever that is smaller (hqpkkt_set_packed_hessians; hessian_packing() reports the layout)."""
+    the diagonal wherever that is smaller (hqpkkt_set_packed_hessians; hessian_packing() reports the layout).
+    After a dense hand-over the blocks live on the device: update_stage_hessians() changes them in place (scale, diagonal,
+    up to four rank-one terms per stage), hessian_product() gives Q x, and bfgs_update() is the reference's damped block-BFGS
+    step made of the two (hqpkkt_update_stage_hessians, hqpkkt_hessian_product)."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
@@ -496,6 +499,94 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         _check(self._L.hqpkkt_debug_hess_symv_timed(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data), int(reps), C.byref(ms)),
                "hess_symv_timed")
         return y, ms.value
+
+    def _hess_vec(self, a, what):
+        """(pointer, what keeps it alive) of a vector of n: numpy, or a torch CUDA tensor with device_vectors=True."""
+        if hasattr(a, "data_ptr"):
+            if not self._device_vectors or not a.is_cuda:
+                raise TypeError(f"{what}: torch CUDA tensors need device_vectors=True")
+            if a.numel() != self.n or str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                raise KktError(_lib.E_SIZES, what)
+            return C.c_void_p(a.data_ptr()), a
+        if self._device_vectors:
+            raise TypeError(f"{what}: device_vectors=True needs torch CUDA float64 tensors")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != self.n:
+            raise KktError(_lib.E_SIZES, what)
+        return C.c_void_p(a.ctypes.data), a
+
+    def _torch_sync(self):
+        """Device vectors are read in the handle's stream: what torch has queued for them is over first."""
+        if self._device_vectors:
+            import torch
+            torch.cuda.current_stream(self._dev).synchronize()
+
+    def hessian_product(self, x):
+        """y = Q x over the dense stage Hessians (hqpkkt_hessian_product): x of length n, numpy - or a torch CUDA tensor with
+        device_vectors=True, and y is one then.  The launches and the bits of the residual's product."""
+        px, kx = self._hess_vec(x, "x")
+        if self._device_vectors:
+            import torch
+            y = torch.zeros(self.n, dtype=torch.float64, device=kx.device)
+            py = C.c_void_p(y.data_ptr())
+            self._torch_sync()
+        else:
+            y = np.zeros(self.n)
+            py = C.c_void_p(y.ctypes.data)
+        _check(self._L.hqpkkt_hessian_product(self._h, px, py), "hessian_product")
+        return y
+
+    def update_stage_hessians(self, U, coef, beta=None, diag=None):
+        """Every stage Hessian updated in place on the device (hqpkkt_update_stage_hessians):
+        Q_k <- beta_k Q_k + diag(d_k) + sum_j coef[k, j] u_jk u_jk'.  ``U``: a list of r <= 4 vectors of n, ``diag``: a
+        vector of n or None - numpy, or torch CUDA tensors with device_vectors=True (read asynchronously: they are kept
+        alive here until the next call); ``coef``: host array of shape (K + 1, r); ``beta``: K + 1 host values or None
+        (all 1).  beta_k = 0 makes block k on the device - ``diag`` alone is a scaled identity or a restart -, and a
+        diagonal shift, the effect of the reference's eigenvalue control (which is not built), is ``diag`` with beta = 1."""
+        U = list(U)
+        r = len(U)
+        K1 = len(self.debug(20))
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(K1, r)
+        keep = [coef]
+        up = (C.c_void_p * max(r, 1))()
+        for j, v in enumerate(U):
+            p, k = self._hess_vec(v, f"U[{j}]")
+            up[j] = p.value
+            keep.append(k)
+        u = _lib.HessUpdate()
+        u.r = r
+        u.U = C.cast(up, C.POINTER(C.c_void_p)) if r else None
+        u.coef = coef.ctypes.data if r else None
+        if beta is not None:
+            beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(K1)
+            u.beta = beta.ctypes.data
+        if diag is not None:
+            p, k = self._hess_vec(diag, "diag")
+            u.diag = p.value
+            keep.append(k)
+        self._torch_sync()
+        _check(self._L.hqpkkt_update_stage_hessians(self._h, C.byref(u)), "update_stage_hessians")
+        self._keep_u = keep
+
+    def bfgs_update(self, s, y, gamma=0.1, alpha=1.0):
+        """The reference's damped BFGS update of every stage Hessian (Hqp_HL_BFGS::update_b_Q without its eigenvalue
+        control) for the step ``s`` and the change ``y`` of the Lagrangian's gradient, numpy vectors of n: Q s by
+        hessian_product, the terms by hessian_update.bfgs_terms on the host, the rank-2 update on the device.  Returns
+        (U, coef) as applied."""
+        from .hessian_update import bfgs_terms
+        lay = self.hessian_layout()
+        offsets = np.concatenate([[0], np.cumsum(lay[:, 0])])
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        if self._device_vectors:
+            import torch
+            dev = torch.device("cuda", self._dev)
+            Qs = self.hessian_product(torch.as_tensor(s).to(dev)).cpu().numpy()
+            U, coef = bfgs_terms(s, y, Qs, offsets, gamma, alpha)
+            self.update_stage_hessians([torch.as_tensor(v).to(dev) for v in U], coef)
+        else:
+            U, coef = bfgs_terms(s, y, self.hessian_product(s), offsets, gamma, alpha)
+            self.update_stage_hessians(U, coef)
+        return U, coef
 
     def set_packed_hessians(self, on):
         """Dense stage Hessians stored as packed lower tiles (hqpkkt_set_packed_hessians); holds from the next init() on."""

@@ -437,6 +437,54 @@ int hqpkkt_debug_hess_symv_timed(hqpkkt_t *h, const double *x, double *y, int re
  * neither 0 nor 1.  hqpkkt_debug_get 47 reports the layout; 45 keeps reporting the order and up8(order), and
  * hqpkkt_debug_stage_hessian returns the unpacked view of a packed stage. */
 int hqpkkt_set_packed_hessians(hqpkkt_t *h, int on);
+/* The dense stage Hessians updated in place on the device.  A block-BFGS caller changes every Q_k a little in every SQP
+ * iteration (hqp/Hqp_HL_BFGS.C:150-248: Q - Qs (Qs)'/s'Qs + v v'/s'v, block by block); without this entry the change reaches
+ * the engine only as a new hand-over of every block.  hqpkkt_update_stage_hessians applies to every stage k = 0 .. K
+ *     Q_k <- beta_k Q_k + diag(d_k) + sum_{j < r} c_kj u_jk u_jk'
+ * where u_jk and d_k are the entries of U[j] and diag that belong to the variables of stage k - the contiguous range the
+ * block covers, [x_k, u_k], x_K for stage K.  U[j] and diag hold n doubles, pointers per opts.loc; coef ((K + 1) r doubles,
+ * coef[k r + j] = c_kj), beta (K + 1 doubles, or NULL: all 1.0) and the array U itself are HOST arrays; diag NULL: none.
+ * It works on both layouts of the blocks, the dense block (both triangles) and the packed lower tiles (the stored tiles), in
+ * one launch over all stages (staged_hess_update.hip.h): one read and one write of the arena.
+ *   Values.  The value written to (i, j) is a function of Q_ij, beta_k, d_i (i = j only), the c_kj and the ROUNDED products
+ *   fl(u_i u_j), evaluated in the fixed order scale, diagonal, terms 0 .. r - 1, every step rounded once (a term is one
+ *   fused multiply-add of c_kj and the rounded product).  fl(u_i u_j) does not depend on the order of its factors: a dense
+ *   block and a diagonal tile stay symmetric bit for bit, and a packed and an unpacked handle given the same update hold
+ *   bit-identical blocks (hqpkkt_debug_stage_hessian).
+ *   Skips.  beta_k == 1 exactly: no scaling.  beta_k == 0 exactly: the block is not read - what it held, NaN included, does
+ *   not enter.  A term with c_kj == 0 exactly is skipped for that stage: its vector's entries, NaN or Inf included, do not
+ *   enter.  A stage with beta_k == 1, every c_kj == 0 and diag == NULL is not touched at all (the reference leaves a block
+ *   alone when s'v or s'Qs is zero).
+ *   Padding stays +0.0: the columns [nz_k, up8(nz_k)) of a dense block, the rows and columns past nz_k of a packed tile.
+ *   Vector entries past the stage's order belong to the next stage: they count as 0 and are never read as values.
+ *   Hand-over.  beta_k == 0 counts as the arrival of block k for hqpkkt_set_values_staged's rule, so a caller can create
+ *   every Hessian on the device - diag alone for a scaled identity or a restart - and never hand over a block.  beta_k != 0
+ *   on a stage the call touches whose block has not arrived since the analysis returns HQPKKT_E_INTERN.
+ *   Checks, all before anything is launched (a call applies to every stage or to none): HQPKKT_E_NULL - h or u null, r > 0
+ *   with U, U[j] or coef null; HQPKKT_E_RANGE - r outside 0 .. HQPKKT_HESS_UPDATE_RANK, a beta or a coefficient that is not
+ *   finite; HQPKKT_E_INTERN - the handle is not STAGED, not analysed, not HQPKKT_HESS_DENSE, or analysed for the CSR hand-over
+ *   (whose hqpkkt_set_values rewrites the blocks anyway: the rule of hqpkkt_set_stage_hessian), or the hand-over rule above;
+ *   then, without a gfx950 device, HQPKKT_E_DEVICE.
+ *   After the call h is not factored (as after hqpkkt_set_stage_hessian); the dynamics and their hand-over state are left
+ *   alone, and a later hqpkkt_set_values_staged(Qx = NULL, ..) keeps the updated blocks.
+ *   Host vectors are copied through buffers the handle owns (made by the first call, outside any capture), and the call
+ *   returns when the stream has read them.  Device vectors are read asynchronously in the handle's stream: the caller keeps
+ *   them alive and unchanged until the stream has passed the update.  coef and beta are read before the call returns.
+ * Not built: the reference's eigenvalue control (a diagonal shift is diag with beta = 1) and the row maxima of restart_Q.
+ * hqpkkt_hessian_product: y = Q x over all stage blocks, x and y of n doubles, pointers per opts.loc, by the launches of
+ * the handle's residual - the public form of hqpkkt_debug_hess_symv and the same bits; on any uploaded HQPKKT_HESS_DENSE
+ * handle, either hand-over (HQPKKT_E_INTERN otherwise); the result is complete when it returns.  It gives a BFGS caller
+ * Q s without a host copy of Q. */
+#define HQPKKT_HESS_UPDATE_RANK 4
+typedef struct hqpkkt_hess_update {
+  int r;                  /* 0 .. HQPKKT_HESS_UPDATE_RANK terms */
+  const double *const *U; /* host array of r pointers; U[j]: n doubles, pointer per opts.loc */
+  const double *coef;     /* HOST array, (K + 1) * r doubles: coef[k * r + j] = c_kj */
+  const double *beta;     /* HOST array of K + 1 doubles, or NULL = all 1.0 */
+  const double *diag;     /* n doubles, pointer per opts.loc, or NULL = none */
+} hqpkkt_hess_update;
+int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u);
+int hqpkkt_hessian_product(hqpkkt_t *h, const double *x, double *y);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense

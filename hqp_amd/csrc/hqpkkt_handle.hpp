@@ -288,6 +288,7 @@ struct hqpkkt {
   Prof prof;
   Analysis an;
   std::unique_ptr<StagedDev, StagedDevDelete> sd;  // HQPKKT_MODE_STAGED: the stage blocks (staged_host.hip.h)
+  kktdev::StagedRequest staged_rq;                 // ... and what its setters ask of the next analysis (staged_plan.hpp)
   double ge_tol = 1.0e-6;   // rank decision of the stage constraints (_ge_tol, hqp/Hqp_IpLQDOCP.C:113)
   bool analyzed = false, uploaded = false, have_values = false, factored = false;
   hqpkkt_stats st;

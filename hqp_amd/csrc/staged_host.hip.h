@@ -40,112 +40,151 @@ struct GemmCache {
   }
 };
 
+// The device state of one analysis: the plan, the three arenas, the staging buffers of the block-by-block hand-over, and
+// one group per form.  Every group is built by its step of staged_upload (upload_* below) unless it says otherwise
 struct StagedDev {
   kktdev::StagedPlan plan;
   DBuf<double> F, V, misc;
-  DBuf<int> dyn, eq_rows, fix_rows, fix_src, h_tptr, chk_idx, chk_kind;
-  DBuf<long long> h_dst, a_dst;
-  DBuf<long long> c_dst;  // the wide rows of C (StagedPlan::wr_rows): where k_st_scatter puts C's values, and the rows
-  DBuf<int> wr_rows;
+  PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging, which makes them)
+  EventOwner hblk_ev[2];
+  std::vector<char> blocks_set;  // dense hand-over block by block: which stages have arrived since the analysis
+  // the plan's tables that every sequence reads, and the int arena
+  struct Tables {
+    DBuf<int> dyn, eq_rows, fix_rows, fix_src, h_tptr, chk_idx, chk_kind;
+    DBuf<long long> h_dst, a_dst;
+    DBuf<stg::HTerm> h_terms;
+  } tab;
+  // The wide rows of C (StagedPlan::wr_rows): where k_st_scatter puts C's values, and the rows ...
   // ... and their vector products in step and residual (StagedPlan::rows_vec; staged_rows.hip.h): the table of the blocks
   // E_k, per wide row its block, the narrow copies of C and C' for the CSR walks, C_wide' t (n) and the wide rows' C dx
   // (m; zero in every other row: nothing else writes it)
-  DBuf<stg::RowsBlock> wr_blk;
-  DBuf<int> wr_blk_of;
-  CsrBuf Cn, CTn;
-  DBuf<double> wr_xc, wr_cdx;
-  int wr_pairs_max = 0;
-  DBuf<stg::HTerm> h_terms;
-  DBuf<stg::DynDesc> dyn_desc;  // dense dynamics: per stage (K+1) what k_st_dyn_both / k_st_dyn_ax_finish need
-  DBuf<double> dyn_x1, dyn_x2;  // A_dyn' dy (n), A_dyn dx (ndyn)
-  DBuf<int> sp_arow, sp_tcol;   // the sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A'
-  DBuf<int> sp_tcol_light, hv_cols, hv_of;  // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per
-                                            // stage, and per column of A its position among its stage's heavy ones or -1
-  DBuf<double> dyn_part;        // row sums of A_dyn dx per block of 256 columns (k_st_dyn_both): ndyn x dyn_part_cols
-  int dyn_part_cols = 0;
-  PinnedBuf<double> hblk[2];  // pinned staging of one stage block each (hqpkkt_stage_staging)
-  EventOwner hblk_ev[2];
-  std::vector<char> blocks_set;         // dense hand-over block by block: which stages have arrived since the analysis
-  // dense stage Hessians (StagedPlan::hess_dense): the arena of the blocks Q_k, the scatter map of the CSR hand-over, per
-  // stage what k_hs_symv needs, y = Q x of the residual products (n) and the operand of hqpkkt_debug_hess_symv (n; made by
-  // its first call)
-  DBuf<double> Qd, hess_y, hess_x;
-  DBuf<long long> q_dst;
-  DBuf<stg::HessDesc> hess_desc;
-  std::vector<char> hess_set;           // dense hand-over: which blocks Q_k have arrived since the analysis
-  // ... as packed lower tiles (StagedPlan::hess_packed): per stage what k_hp_symv_tiles needs, the slots of that product, the
-  // staging block of a dense hand-over from host memory (made by its first call; reused in stream order); the launches'
-  // extents: most chunks of tiles and tile rows of a packed stage, largest order of a stage that keeps its dense block (0: none)
-  DBuf<stg::HpDesc> hp_desc;
-  DBuf<double> hess_scr, hess_stage;
-  int hp_chunks_max = 0, hp_nt_max = 0, hs_nz_max = 0;
-  // ... updated in place (hqpkkt_update_stage_hessians; all made by its first call): the per-stage descriptors of the launch,
-  // written to pinned memory and copied from there in the handle's stream (hu_ev: that copy is over, the pinned words may be
+  struct WideRows {
+    DBuf<long long> c_dst;
+    DBuf<int> rows;
+    DBuf<stg::RowsBlock> blk;
+    DBuf<int> blk_of;
+    CsrBuf Cn, CTn;
+    DBuf<double> xc, cdx;
+    int pairs_max = 0;
+  } wr;
+  // Dense stage Hessians (StagedPlan::hess_dense): the arena of the blocks Q_k, the scatter map of the CSR hand-over, per
+  // stage what k_hs_symv needs, y = Q x of the residual products (n), which blocks Q_k have arrived since the analysis
+  // (dense hand-over) ...
+  // ... as packed lower tiles (StagedPlan::hess_packed): per stage what k_hp_symv_tiles needs, the slots of that product; the
+  // launches' extents: most chunks of tiles and tile rows of a packed stage, largest order of a stage that keeps its dense
+  // block (0: none) ...
+  // ... and what the entry points make at their first call, because only their callers need it: x, the operand of
+  // hqpkkt_debug_hess_symv (n); stage, the staging block of a packed stage's dense hand-over from host memory (reused in
+  // stream order); of the update in place (hqpkkt_update_stage_hessians) the per-stage descriptors of the launch, written
+  // to pinned memory and copied from there in the handle's stream (hu_ev: that copy is over, the pinned words may be
   // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n)
-  PinnedBuf<stg::HuDesc> hu_hdesc;
-  DBuf<stg::HuDesc> hu_desc;
-  EventOwner hu_ev;
-  DBuf<double> hu_vec;
-  // one system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
-  // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack; the local dynamics blocks of
-  // residuum()'s products and their summed results (A_dyn' dy: n, A_dyn dx: ndyn)
-  DBuf<stg::StripTab> wtabs;  // (the strips of the gathered F: offsets inside one of the two buffers)
-  DBuf<stg::RectTab> rtabs;
-  DBuf<int> gtile;
-  DBuf<unsigned> gowned;             // per stage: bitmap of the 128 x 128 tiles of G this rank computes (k_st_add_h_owned)
-  std::vector<long long> gowned_off;  // stage k's words start at gowned_off[k]
-  DBuf<stg::PackRect> prects;
-  std::vector<int> prect_ptr;
-  DBuf<stg::DynLoc> dyn_loc;
-  DBuf<double> dyn_sum;
-  long long dyn_sum_x2 = 0;  // offset of A_dyn dx in dyn_sum
-  // the exchanges of a stage in the stream-ordered form (RCCL) go to a stream of their own, so that the gather of the
+  struct Hessians {
+    DBuf<double> Q, y;
+    DBuf<long long> q_dst;
+    DBuf<stg::HessDesc> desc;
+    std::vector<char> set;
+    DBuf<stg::HpDesc> hp_desc;
+    DBuf<double> scr;
+    int hp_chunks_max = 0, hp_nt_max = 0, hs_nz_max = 0;
+    DBuf<double> x, stage;
+    PinnedBuf<stg::HuDesc> hu_hdesc;
+    DBuf<stg::HuDesc> hu_desc;
+    EventOwner hu_ev;
+    DBuf<double> hu_vec;
+  } hess;
+  // The sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A' ...
+  // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per stage, and per column of A its
+  // position among its stage's heavy ones or -1
+  struct Sparse {
+    DBuf<int> arow, tcol;
+    DBuf<int> tcol_light, hv_cols, hv_of;
+  } sp;
+  // Dense dynamics in the residual (staged_dense_products), one GPU: per stage (K+1) what k_st_dyn_both /
+  // k_st_dyn_ax_finish need, A_dyn' dy (n), A_dyn dx (ndyn), and the row sums of A_dyn dx per block of 256 columns
+  // (k_st_dyn_both): ndyn x part_cols ...
+  struct DynResidual {
+    DBuf<stg::DynDesc> desc;
+    DBuf<double> x1, x2, part;
+    int part_cols = 0;
+  } dres;
+  // ... and over several ranks: the local dynamics blocks and the products' summed results (A_dyn' dy: n, A_dyn dx: ndyn
+  // from sum_x2 on)
+  struct DynResidualSharded {
+    DBuf<stg::DynLoc> loc;
+    DBuf<double> sum;
+    long long sum_x2 = 0;
+  } dres_sh;
+  // One system over several ranks (staged_plan.hpp): per stage where the ranks' strips of W / blocks of G_xx lie in the
+  // exchange buffers, this rank's tiles of its blocks' products and its blocks to pack
+  // The exchanges of a stage in the stream-ordered form (RCCL) go to a stream of their own, so that the gather of the
   // NEXT stage's F blocks travels beside this stage's products: ev_w[i] "the first stream is ready for exchange i",
   // ev_x[i] "exchange i has arrived" (i = 0, 1: the gathered F in buffer i, 2: the blocks of G_xx)
-  StreamOwner stream_x;
-  EventOwner ev_x1, ev_w[3], ev_x[3];
+  struct Sharded {
+    DBuf<stg::StripTab> wtabs;  // (the strips of the gathered F: offsets inside one of the two buffers)
+    DBuf<stg::RectTab> rtabs;
+    DBuf<int> gtile;
+    DBuf<unsigned> gowned;              // per stage: bitmap of the 128 x 128 tiles of G this rank computes (k_st_add_h_owned)
+    std::vector<long long> gowned_off;  // stage k's words start at gowned_off[k]
+    DBuf<stg::PackRect> prects;
+    std::vector<int> prect_ptr;
+    StreamOwner stream;
+    EventOwner ev_x1, ev_w[3], ev_x[3];
+  } sh;
+  // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device and the partial sums of the
+  // solve's columns product (stg::pf_chunks x columns of the widest stage)
+  // packed panels (StagedPlan::packed): per panel of every stage its block for the kernels (offset from the stage's F
+  // less 16 lo ld, leading dimension; indexed like rng's pairs), and the partial sums of the carried rows (k_pk_carried)
+  struct Profile {
+    DBuf<int> rng;
+    DBuf<double> part;
+    DBuf<stg::PackPanel> pk_tab;
+    DBuf<double> pk_part;
+    const int *ranges(const kktdev::StagedPlan &P, int k) const { return rng.p + 2 * (size_t)P.pf_ptr[k]; }
+    const stg::PackPanel *panels(const kktdev::StagedPlan &P, int k) const { return P.pk_stage(k) ? pk_tab.p + P.pf_ptr[k] : nullptr; }
+  } pf;
+  // The second stream: the control-sized chain of a stage (G_u strip, H's control part, carried rows, K^-1, Y, Rm)
+  // runs beside the large product G_xx = fx'W_x instead of behind it (fork / join by events; inside a
+  // captured sequence these are parallel branches of the graph).  Made where a stage can take it (upload_second_stream)
+  struct SecondStream {
+    StreamOwner stream;
+    EventOwner fork, join;
+  } s2;
+  // The launches of the dense product (st_gemm): what the handle offers them (upload_product_caps) and their schedules
+  // with the work lists and tile orders on the device, made in upload's dry walk of the factor sequence
+  struct Product {
+    stg::GemmCaps caps;
+    GemmCache gemms;
+    DBuf<double> zeros;    // 256 zero doubles: the operand rows k >= K of the LDS-DMA staging (GemmArgs::zeros)
+    DBuf<double> ks_ws2;   // the pieces of a thin product cut in k (k_dgemm_tn_ks) launched on the SECOND stream
+    DBuf<double> sk_ws;    // the cut forms of the dgemm: parked partial tiles (SkUnit::slot0)
+    DBuf<unsigned> sk_cnt;
+    // What staged_run_factor and staged_run_step branch on, per stage k < K, chosen at upload (upload_sequences): the
+    // plan's answer (StagedPlan::stage_seq) with the dense stages that form V_k in the G_xx launch (SEQ_FUSED:
+    // GemmArgs::K2; `fused` says the same per stage) or run the chain on the second stream (SEQ_DENSE_CHAIN2) told apart
+    std::vector<kktdev::StageSeq> seq;
+    std::vector<char> fused;
+    DBuf<double> fv_nrm;  // -Rm (k_st_rm) of the fused stage in work
+    // words of the control-row segment (GemmArgs::ctl), and per stage whether its W launch takes the segment
+    DBuf<unsigned> ctl;
+    std::vector<char> ctrl_rows;
+  } prod;
   // The solve's products with V that stand outside its two chains, many stages per launch (k_st_symv_*_batch; not
   // sharded): [0] g_k = V_{k+1} f_k ahead of the backward sweep, [1] the dynamics rows' multipliers behind the forward
   // sweep.  A launch holds the stages whose partial sums fit StagedPlan::symb_elems; stages that do not take the
   // triangle form (st_symv) go through k_st_gemv_rows one by one.
-  struct SymvGroup {
-    int first, count, tiles, fins;
-    int kfirst, klast;  // the stages k (products with V_{k+1}) of the launch
-  };
-  DBuf<stg::SymvItem> symv_items[2];
-  std::vector<SymvGroup> symv_groups[2];
-  std::vector<int> symv_rows_stage[2];
-  DBuf<double> zeros;           // 256 zero doubles: the operand rows k >= K of the LDS-DMA staging (GemmArgs::zeros)
-  // The launches of the dense product (st_gemm): what the handle offers them (filled in one block of staged_upload) and
-  // their schedules with the work lists and tile orders on the device, made in upload's dry walk of the factor sequence
-  stg::GemmCaps caps;
-  GemmCache gemms;
-  DBuf<double> ks_ws2;          // the pieces of a thin product cut in k (k_dgemm_tn_ks) launched on the SECOND stream
-  DBuf<double> sk_ws;           // the cut forms of the dgemm: parked partial tiles (SkUnit::slot0)
-  DBuf<unsigned> sk_cnt;
-  // second stream: the control-sized chain of a stage (G_u strip, H's control part, carried rows, K^-1, Y, Rm)
-  // runs beside the large product G_xx = fx'W_x instead of behind it (fork / join by events; inside a
-  // captured sequence these are parallel branches of the graph)
-  StreamOwner stream2;
-  EventOwner ev_fork, ev_join;
-  bool overlap = false;
-  int overlap_mode = 0;  // 0 never, 1 every stage, 2 stages of 1280 .. 4096 states
-  // Stages that form V_k in the G_xx launch (GemmArgs::K2), chosen at upload time (staged_stage_fused, HQPKKT_FUSED_V),
-  // and -Rm (k_st_rm) of the stage in work
-  std::vector<char> fused;
-  DBuf<double> fv_nrm;
-  // words of the control-row segment (GemmArgs::ctl), and per stage whether its W launch takes the segment
-  DBuf<unsigned> ctl;
-  std::vector<char> ctrl_rows;
-  // The profile form (StagedPlan::profile_dyn): the panels' k-slab ranges on the device and the partial sums of the
-  // solve's columns product (stg::pf_chunks x columns of the widest stage)
-  DBuf<int> pf_rng;
-  DBuf<double> pf_part;
-  // packed panels (StagedPlan::packed): per panel of every stage its block for the kernels (offset from the stage's F
-  // less 16 lo ld, leading dimension; indexed like pf_rng's pairs), and the partial sums of the carried rows (k_pk_carried)
-  DBuf<stg::PackPanel> pk_tab;
-  DBuf<double> pk_part;
-  size_t lds_small = 0, lds_small_big = 0, lds_init = 0, lds_x0 = 0;
+  struct Symv {
+    struct Group {
+      int first, count, tiles, fins;
+      int kfirst, klast;  // the stages k (products with V_{k+1}) of the launch
+    };
+    DBuf<stg::SymvItem> items[2];
+    std::vector<Group> groups[2];
+    std::vector<int> rows_stage[2];
+  } symv;
+  // dynamic LDS of the one-workgroup kernels, as this handle's stages need it (upload_lds_limits)
+  struct Lds {
+    size_t small = 0, small_big = 0, init = 0, x0 = 0;
+  } lds;
 };
 
 namespace {
@@ -204,7 +243,7 @@ inline StagePtr stage_ptr(StagedDev &d, int k) {
   s.BT = M + P.oBT[k], s.N = M + P.oN[k];
   const int capx = std::max(P.cap[k], 1);
   s.v = M + P.oVec[k], s.beta = s.v + P.nk[k], s.eta = s.beta + capx, s.rho = s.eta + capx;
-  s.dyn = d.dyn.p + P.dyn_off[k];
+  s.dyn = d.tab.dyn.p + P.dyn_off[k];
   if (k < P.K) {
     s.F = d.F.p + (P.sharded ? P.oFl[k] : P.oF[k]);
     s.Y = M + P.oY[k], s.Rm = M + P.oR[k], s.Kinv = M + P.oK[k], s.Kmat = M + P.oKm[k], s.T = M + P.oT[k];
@@ -221,7 +260,7 @@ inline stg::GemmArgs staged_w_args(StagedDev &d, int k, bool seg) {
   const long long ldf = P.ldf[k], ldg = P.ldg[k];
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
   stg::GemmArgs g{sn.V, P.ldv[k + 1], sp.F, ldf, nullptr, 0, W, ldf, np, nn + mm, np, 1.0, 0.0, 0, 0};
-  if (seg) g.Au = W + nn, g.ldau = ldf, g.mu = mm, g.Cu = G + nn * ldg, g.ldcu = ldg, g.ctl = d.ctl.p;
+  if (seg) g.Au = W + nn, g.ldau = ldf, g.mu = mm, g.Cu = G + nn * ldg, g.ldcu = ldg, g.ctl = d.prod.ctl.p;
   return g;
 }
 
@@ -232,7 +271,7 @@ inline stg::GemmArgs staged_v_args(StagedDev &d, int k) {
   const int nn = P.nk[k];
   const long long ldf = P.ldf[k], ldy = P.ldy[k];
   stg::GemmArgs g{sp.F, ldf, d.misc.p + P.oW, ldf, nullptr, 0, sp.V, P.ldv[k], nn, nn, P.nk[k + 1], 1.0, 0.0, 1, 1};
-  g.A2 = sp.Y, g.lda2 = ldy, g.B2 = d.fv_nrm.p, g.ldb2 = ldy, g.K2 = P.qmax[k];
+  g.A2 = sp.Y, g.lda2 = ldy, g.B2 = d.prod.fv_nrm.p, g.ldb2 = ldy, g.K2 = P.qmax[k];
   return g;
 }
 
@@ -249,14 +288,14 @@ int st_gemm(hqpkkt_t *h, stg::GemmArgs g, int cls = KC_ST_GEMM, bool allow_sk = 
   StagedDev &d = *h->sd;
   const stg::GemmRequest rq = stg::gemm_request(g, !allow_sk, ntiles, by, panel);
   GemmCache::Entry local, *e;
-  if (int err = d.gemms.get(d.caps, rq, h->listing, local, e)) return err;
-  // (the control-row segment: only where the upload found the launch a list, StagedDev::ctrl_rows)
+  if (int err = d.prod.gemms.get(d.prod.caps, rq, h->listing, local, e)) return err;
+  // (the control-row segment: only where the upload found the launch a list, StagedDev::Product::ctrl_rows)
   if (g.Au && !e->s.seg) return HQPKKT_E_INTERN;
   if (h->listing) return 0;
   e->hits++;
   (by == 2 ? g.apack : g.bpack) = pack;
-  const stg::GemmBufs bufs{e->units.p, e->order.p, d.sk_ws.p, d.sk_cnt.p, allow_sk ? d.sk_ws.p : d.ks_ws2.p, d.zeros.p};
-  stg::gemm_run(e->s, d.caps, bufs, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
+  const stg::GemmBufs bufs{e->units.p, e->order.p, d.prod.sk_ws.p, d.prod.sk_cnt.p, allow_sk ? d.prod.sk_ws.p : d.prod.ks_ws2.p, d.prod.zeros.p};
+  stg::gemm_run(e->s, d.prod.caps, bufs, h->stream, g, [&](auto &&launch) { KLAUNCH(h, cls, launch()); });
   return 0;
 }
 // ... of stage k in the profile form
@@ -264,7 +303,7 @@ int st_gemm_profile(hqpkkt_t *h, const stg::GemmArgs &g, int k, int by, int cls 
   const kktdev::StagedPlan &P = h->sd->plan;
   if (g.M <= 0 || g.N <= 0) return 0;
   if (P.panels(k) != ((by == 2 ? g.M : g.N) + 127) / 128) return HQPKKT_E_INTERN;
-  return st_gemm(h, g, cls, true, 0, by, P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.pk_stage(k) ? h->sd->pk_tab.p + P.pf_ptr[k] : nullptr);
+  return st_gemm(h, g, cls, true, 0, by, P.stage_ranges(k), h->sd->pf.panels(P, k));
 }
 
 int st_gemv_rows(hqpkkt_t *h, stg::GemvRows g) {
@@ -292,16 +331,16 @@ int st_gemv_cols(hqpkkt_t *h, StagedDev &d, const double *A, long long lda, int 
   return 0;
 }
 
-// the two tables of StagedDev::symv_items (at upload time: the arenas' addresses are final)
+// the two tables of StagedDev::Symv::items (at upload time: the arenas' addresses are final)
 int staged_build_symv_tables(StagedDev &d) {
   const kktdev::StagedPlan &P = d.plan;
-  for (int dir = 0; dir < 2; dir++) d.symv_items[dir].release(), d.symv_groups[dir].clear(), d.symv_rows_stage[dir].clear();
+  for (int dir = 0; dir < 2; dir++) d.symv.items[dir].release(), d.symv.groups[dir].clear(), d.symv.rows_stage[dir].clear();
   if (P.sharded) return 0;
   double *M = d.misc.p, *S = M + P.oS, *gv = M + P.oGv;
   auto up16 = [](long long x) { return (x + 15) / 16 * 16; };
   for (int dir = 0; dir < 2; dir++) {
     std::vector<stg::SymvItem> items;
-    StagedDev::SymvGroup g{0, 0, 0, 0, 0, 0};
+    StagedDev::Symv::Group g{0, 0, 0, 0, 0, 0};
     long long used = 0;
     for (int k = 0; k < P.K; k++) {
       const StagePtr sn = stage_ptr(d, k + 1);
@@ -309,13 +348,13 @@ int staged_build_symv_tables(StagedDev &d) {
       if (np <= 0) continue;
       const stg::GemvRows gr{sn.V, P.ldv[k + 1], np, np, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1.0};
       if (!symv_tiles_form(gr)) {
-        d.symv_rows_stage[dir].push_back(k);
+        d.symv.rows_stage[dir].push_back(k);
         continue;
       }
       const long long need = up16(kktdev::StagedPlan::symv_need(np));
       if (g.count > 0 && used + need > P.symb_elems) {
-        d.symv_groups[dir].push_back(g);
-        g = StagedDev::SymvGroup{(int)items.size(), 0, 0, 0, k, k}, used = 0;
+        d.symv.groups[dir].push_back(g);
+        g = StagedDev::Symv::Group{(int)items.size(), 0, 0, 0, k, k}, used = 0;
       }
       if (g.count == 0) g.kfirst = k;
       g.klast = k;
@@ -332,24 +371,24 @@ int staged_build_symv_tables(StagedDev &d) {
       items.push_back(it);
       g.tiles += (int)stg::symv_tiles(np), g.fins += (np + 63) / 64, g.count++, used += need;
     }
-    if (g.count > 0) d.symv_groups[dir].push_back(g);
+    if (g.count > 0) d.symv.groups[dir].push_back(g);
     if (!items.empty())
-      if (int e = d.symv_items[dir].upload(items)) return e;
+      if (int e = d.symv.items[dir].upload(items)) return e;
   }
   return 0;
 }
-// one launch pair of StagedDev::symv_groups[dir] on h->stream.  dir 0: g_k = V_{k+1} f_k (f: the dynamics rows of r2) into
+// one launch pair of StagedDev::Symv::groups[dir] on h->stream.  dir 0: g_k = V_{k+1} f_k (f: the dynamics rows of r2) into
 // the plan's oGv; dir 1: the dynamics rows of dy = V+ x+ + v+ + B+' eta+
 int staged_symv_group(hqpkkt_t *h, StagedDev &d, int dir, int gi, const double *r2, double *dy) {
-  const StagedDev::SymvGroup &g = d.symv_groups[dir][gi];
-  stg::symv_launch_batch(d.symv_items[dir].p + g.first, g.count, g.tiles, g.fins, 0, 0, r2, dy, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
+  const StagedDev::Symv::Group &g = d.symv.groups[dir][gi];
+  stg::symv_launch_batch(d.symv.items[dir].p + g.first, g.count, g.tiles, g.fins, 0, 0, r2, dy, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   return 0;
 }
 // ... and the stages outside the groups (no triangle form: few states), one launch each
 int staged_symv_rows(hqpkkt_t *h, StagedDev &d, int dir, const double *r2, double *dy) {
   const kktdev::StagedPlan &P = d.plan;
   double *M = d.misc.p, *S = M + P.oS, *gv = M + P.oGv;
-  for (int k : d.symv_rows_stage[dir]) {
+  for (int k : d.symv.rows_stage[dir]) {
     const StagePtr sn = stage_ptr(d, k + 1);
     const int np = P.nk[k + 1];
     int e;
@@ -386,7 +425,7 @@ static int st_blk_sweep(hqpkkt_t *h, double *scratch, int q, bool allow_sk) {
 static int st_small_big(hqpkkt_t *h, StagedDev &d, stg::SmallArgs sa, bool allow_sk) {
   int e;
   sa.mode = 1;
-  KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds_small_big, h->stream>>>(sa));
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds.small_big, h->stream>>>(sa));
   const stg::BigScratch bs = stg::big_scratch(sa.scratch, sa.qmax);
   const int q = sa.qmax;
   if ((e = st_blk_sweep(h, sa.scratch, q, allow_sk))) return e;
@@ -395,7 +434,7 @@ static int st_small_big(hqpkkt_t *h, StagedDev &d, stg::SmallArgs sa, bool allow
     return e;
   KLAUNCH(h, KC_ST_SMALL, stg::k_blk_check<<<1, 1024, 0, h->stream>>>(sa, env_block_gj_tol()));
   sa.mode = 2;
-  KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds_small_big, h->stream>>>(sa));
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<1024><<<1, 1024, d.lds.small_big, h->stream>>>(sa));
   return 0;
 }
 
@@ -404,7 +443,7 @@ static int st_small_big(hqpkkt_t *h, StagedDev &d, stg::SmallArgs sa, bool allow
 // H's entries first .. first + count of the plan's list added into the work block G
 static void st_add_h(hqpkkt_t *h, StagedDev &d, int first, int count, double *G, int add = 1) {
   if (count)
-    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.h_dst.p + first, d.h_tptr.p + first, d.h_terms.p,
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h<<<nblk(count), 256, 0, h->stream>>>(count, d.tab.h_dst.p + first, d.tab.h_tptr.p + first, d.tab.h_terms.p,
                                                                                h->td.vals.p, h->td.wt.p, G, add));
 }
 // Q's share with dense stage Hessians (StagedPlan::hess_dense; the lists hold C'(Z/W)C alone and go behind it): the rows
@@ -415,42 +454,51 @@ static void st_add_q(hqpkkt_t *h, StagedDev &d, int k, int r0, int r1, int c1, i
   if (P.stage_packed(k)) {  // the stored tiles of the tile rows the request or its image reaches (k_hp_add)
     const int T = stg::HP_T, a0 = r0 / T, a1 = lower ? (r1 - 1) / T : std::max(r1 - 1, c1 - 1) / T;
     const unsigned tiles = (unsigned)((a1 + 1) * (a1 + 2) / 2 - a0 * (a0 + 1) / 2);
-    KLAUNCH(h, KC_ASSEMBLE, stg::k_hp_add<<<dim3(tiles, 16), 256, 0, h->stream>>>(stg::HpAdd{d.Qd.p + P.oQ[k], G, ldg, r0, r1, c1, lower, a0}));
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_hp_add<<<dim3(tiles, 16), 256, 0, h->stream>>>(stg::HpAdd{d.hess.Q.p + P.oQ[k], G, ldg, r0, r1, c1, lower, a0}));
     return;
   }
   const dim3 grid((unsigned)nblk((c1 + 1) / 2), (unsigned)std::min(r1 - r0, 1024));
   KLAUNCH(h, KC_ASSEMBLE, stg::k_hs_add<<<grid, 256, 0, h->stream>>>(
-                              stg::HsAdd{d.Qd.p + P.oQ[k], P.ldQ[k], G, ldg, r0, r1, c1, lower}));
+                              stg::HsAdd{d.hess.Q.p + P.oQ[k], P.ldQ[k], G, ldg, r0, r1, c1, lower}));
 }
 // ... and the share of the stage's wide rows of C (StagedPlan::wr_rows, r of them): G += S'S over the lower tiles with
 // S = diag(sqrt(z / w)) E_k (k_st_rows_scale), a product of depth r in place; stage K: into V_K with its mirror image.
 // Both operands are S, so entry (i, j) and its image are the same sum of the same products
 static int st_add_h_wide(hqpkkt_t *h, StagedDev &d, int k, double *G, long long ldg) {
   const kktdev::StagedPlan &P = d.plan;
-  const int r = P.wide_count(k), nz = k < P.K ? P.nk[k] + P.mk[k] : P.nk[k];
+  const int r = P.wide_count(k), nz = P.hess_order(k);
   if (r <= 0 || nz <= 0) return 0;
   const long long ld = P.ldE[k];
   double *S = d.misc.p + P.oSr;
   KLAUNCH(h, KC_ASSEMBLE, stg::k_st_rows_scale<<<nblk(r * (ld / 2)), 256, 0, h->stream>>>(
-                              stg::RowsScale{d.F.p + P.oE[k], S, d.wr_rows.p + P.wr_ptr[k], h->td.wt.p, r, ld}));
+                              stg::RowsScale{d.F.p + P.oE[k], S, d.wr.rows.p + P.wr_ptr[k], h->td.wt.p, r, ld}));
   return st_gemm(h, stg::GemmArgs{S, ld, S, ld, G, ldg, G, ldg, nz, nz, r, 1.0, 1.0, 1, k == P.K ? 1 : 0}, KC_ST_GEMM_UPD);
 }
+// What every sequence that forms the whole work block G of stage k adds behind the product: Q_k's share, the H lists,
+// the wide rows' product (lower: as st_add_q takes it)
+static int st_add_block(hqpkkt_t *h, StagedDev &d, int k, int lower, double *G, long long ldg) {
+  const kktdev::StagedPlan &P = d.plan;
+  const int nz = P.hess_order(k);
+  st_add_q(h, d, k, 0, nz, nz, lower, G, ldg);
+  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
+  return st_add_h_wide(h, d, k, G, ldg);
+}
 // The vector products of the wide rows of C over all stages, one launch each (staged_rows.hip.h):
-// d.wr_xc = C_wide' t (the whole n-vector; t by rows of C) ...
+// d.wr.xc = C_wide' t (the whole n-vector; t by rows of C) ...
 static void st_rows_cols(hqpkkt_t *h, StagedDev &d, const double *t) {
-  stg::rows_launch_t(stg::RowsGemvT{d.wr_blk.p, d.F.p, d.wr_rows.p, t, d.wr_xc.p}, d.plan.K + 1, d.wr_pairs_max, h->stream,
+  stg::rows_launch_t(stg::RowsGemvT{d.wr.blk.p, d.F.p, d.wr.rows.p, t, d.wr.xc.p}, d.plan.K + 1, d.wr.pairs_max, h->stream,
                      [&](auto &&launch) { KLAUNCH(h, KC_ST_ROWS_VEC, launch()); });
 }
 // ... and C_wide x with the epilogue of g (x and the epilogue's vectors: the caller's; the table, E, the rows: filled in here)
 static void st_rows_rows(hqpkkt_t *h, StagedDev &d, stg::RowsGemv g) {
-  g.blk = d.wr_blk.p, g.blk_of = d.wr_blk_of.p, g.R = (int)d.plan.wr_rows.size(), g.E = d.F.p, g.rows = d.wr_rows.p;
+  g.blk = d.wr.blk.p, g.blk_of = d.wr.blk_of.p, g.R = (int)d.plan.wr_rows.size(), g.E = d.F.p, g.rows = d.wr.rows.p;
   stg::rows_launch(g, h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_ROWS_VEC, launch()); });
 }
 // the carried rows of stage k: N_k[e..] = B+ F (nothing where stage k + 1 carries none)
 static int st_carried_rows(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, bool allow_sk) {
   const kktdev::StagedPlan &P = d.plan;
   const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
-  return st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, P.ldf[k], nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], P.cap[k + 1], P.nk[k] + P.mk[k],
+  return st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], sp.F, P.ldf[k], nullptr, 0, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], P.cap[k + 1], P.hess_order(k),
                                   P.nk[k + 1], 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, allow_sk);
 }
 // the control-sized elimination of stage k on the work block G: rank decision and K^-1 (k_st_small, or the blocked sweep
@@ -466,9 +514,9 @@ static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, co
     if (int e2 = st_small_big(h, d, sa, allow_sk)) return e2;
   } else if (P.qmax[k] > 64) {
     if (env_spd_test_fail()) sa.mode = 100;
-    KLAUNCH(h, KC_ST_SMALL, (stg::k_st_small<1024, false><<<1, 1024, d.lds_small, h->stream>>>(sa)));
+    KLAUNCH(h, KC_ST_SMALL, (stg::k_st_small<1024, false><<<1, 1024, d.lds.small, h->stream>>>(sa)));
   } else
-    KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<256><<<1, 256, d.lds_small, h->stream>>>(sa));
+    KLAUNCH(h, KC_ST_SMALL, stg::k_st_small<256><<<1, 256, d.lds.small, h->stream>>>(sa));
   // Rm = K^-1 Y, refined against K: one launch for K of order <= 64 (k_st_rm), three products above
   // (wa: the arguments of k_st_wide - Y and the carried rows B_k; with K of order 1 .. 64 they are formed inside k_st_rm)
   const int q = P.qmax[k];
@@ -492,18 +540,23 @@ static int st_eliminate(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, co
     return e;
   return 0;
 }
+// the rank-q update V_k = G_xx - Y'Rm (lower tiles, mirrored)
+static int st_update_v(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, double *G) {
+  const kktdev::StagedPlan &P = d.plan;
+  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], P.nk[k], P.nk[k], P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+}
 // sharded: this rank's rows of V_k for the solve
 static void st_keep_rows(hqpkkt_t *h, StagedDev &d, int k) {
   const kktdev::StagedPlan &P = d.plan;
   const StagePtr sp = stage_ptr(d, k);
-  const int c0 = P.xcut[(size_t)k * (P.shard_count + 1) + P.shard_rank], wd = P.xcut[(size_t)k * (P.shard_count + 1) + P.shard_rank + 1] - c0;
+  const int c0 = P.strip_first(k), wd = P.strip_width(k);
   if (wd > 0)
     KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(wd, 2048), 256, 0, h->stream>>>(sp.V + (long long)c0 * P.ldv[k], P.ldv[k], sp.Vs, P.ldv[k], wd, P.nk[k]));
 }
 // backward sweep of the solve, stage k: the control-sized part (gam: q_k + F' tt)
 static void st_bwd_small(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, const StagePtr &sn, const double *r2, const double *gam) {
   const kktdev::StagedPlan &P = d.plan;
-  stg::BwdSmall ba{P.nk[k], P.mk[k], P.nk[k + 1], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], d.eq_rows.p + P.eq_ptr[k], r2,
+  stg::BwdSmall ba{P.nk[k], P.mk[k], P.nk[k + 1], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], d.tab.eq_rows.p + P.eq_ptr[k], r2,
                    P.cap[k + 1] > 0 ? sn.dyn + 1 : nullptr, sn.beta, sn.BT, P.ldb[k + 1], r2 + P.nks[k], gam, sp.Kinv, sp.Kmat, P.ldq[k], sp.T, P.ldt[k],
                    sp.dyn, sp.rho, sp.beta};
   KLAUNCH(h, KC_ST_SMALL, stg::k_st_bwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 3 * P.qmax[k] + 4 + 256), h->stream>>>(ba));
@@ -516,7 +569,7 @@ static int st_initial_state(hqpkkt_t *h, StagedDev &d, const double *r2) {
   const StagePtr s0 = stage_ptr(d, 0);
   const int n0 = P.nk[0];
   if (P.fixed_x0) {
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, r2, S,
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_x0_fixed<<<nblk(std::max(n0, P.cap[0])), 256, 0, s>>>(n0, d.tab.fix_rows.p, d.tab.fix_src.p, h->td.vals.p, r2, S,
                                                                                        s0.eta, P.cap[0]));
     return 0;
   }
@@ -534,7 +587,7 @@ static int st_initial_state(hqpkkt_t *h, StagedDev &d, const double *r2) {
       return e;
     KLAUNCH(h, KC_ST_VEC, stg::k_x0_out<<<nblk(n0 + P.cap[0]), 256, 0, s>>>(xv));
   }
-  KLAUNCH(h, KC_ST_SMALL, stg::k_st_x0_free<<<1, 256, d.lds_x0, s>>>(n0, P.cap[0], P.q0max, M + P.oK0, M + P.oK0m, M + P.oK0s, P.ldq0, s0.dyn, s0.v,
+  KLAUNCH(h, KC_ST_SMALL, stg::k_st_x0_free<<<1, 256, d.lds.x0, s>>>(n0, P.cap[0], P.q0max, M + P.oK0, M + P.oK0m, M + P.oK0s, P.ldq0, s0.dyn, s0.v,
                                                             s0.beta, S, s0.eta));
   return 0;
 }
@@ -549,33 +602,27 @@ static void st_fwd_small(hqpkkt_t *h, StagedDev &d, int k, const StagePtr &sp, c
     stg::gemv_launch_wide(gr, s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
   }
   stg::FwdSmall fa{nn, P.mk[k], P.eq_ptr[k + 1] - P.eq_ptr[k], P.capn[k], P.cap[k], P.qmax[k], uy, sp.T, P.ldt[k],
-                   sp.dyn, sp.eta, d.eq_rows.p + P.eq_ptr[k], xk + nn, dy, sn.eta, P.cap[k + 1]};
+                   sp.dyn, sp.eta, d.tab.eq_rows.p + P.eq_ptr[k], xk + nn, dy, sn.eta, P.cap[k + 1]};
   KLAUNCH(h, KC_ST_SMALL, stg::k_st_fwd_small<<<1, 256, sizeof(double) * (P.capn[k] + 4), s>>>(fa));
 }
 
 int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   if (!h->sd) h->sd.reset(new StagedDev);
-  StagedDev &d = *h->sd;
-  kktdev::StagedPlan &P = d.plan;
-  std::vector<int> gnx = P.given_nx, gnu = P.given_nu;
-  const bool want_sparse = P.want_sparse, want_profile = P.want_profile;
-  const int want_heavy = P.want_heavy, want_rows = P.want_rows;
-  const bool want_packed = P.want_packed, want_hess_dense = P.want_hess_dense, want_hess_packed = P.want_hess_packed;
+  kktdev::StagedPlan &P = h->sd->plan;
+  kktdev::StagedRequest &rq = h->staged_rq;
   P = kktdev::StagedPlan();
-  P.given_nx = gnx, P.given_nu = gnu, P.want_sparse = want_sparse, P.want_profile = want_profile, P.want_heavy = want_heavy, P.want_packed = want_packed, P.want_rows = want_rows;
-  P.want_hess_dense = want_hess_dense, P.want_hess_packed = want_hess_packed;
-  P.dense_dyn = dense_dyn;
+  rq.dense_dyn = dense_dyn;
   if (h->shard_count > 16) return HQPKKT_E_RANGE;
-  P.shard_rank = h->shard_rank, P.shard_count = h->shard_count;
-  P.sharded = h->shard_count > 1 || h->xchg_fn || h->xchg_sfn;
-  if ((want_sparse || want_profile) && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over, the profile form reads its ranges off them
-  if ((want_sparse || want_profile) && P.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
-  if (want_hess_dense && P.sharded) return HQPKKT_E_RANGE;                   // ... and keeps its term lists
+  rq.shard_rank = h->shard_rank, rq.shard_count = h->shard_count;
+  rq.sharded = h->shard_count > 1 || h->xchg_fn || h->xchg_sfn;
+  if ((rq.want_sparse || rq.want_profile) && dense_dyn) return HQPKKT_E_INTERN;  // the sparse form walks the row lists of the CSR hand-over, the profile form reads its ranges off them
+  if ((rq.want_sparse || rq.want_profile) && rq.sharded) return HQPKKT_E_RANGE;   // one system over several ranks stays dense
+  if (rq.want_hess_dense && rq.sharded) return HQPKKT_E_RANGE;                   // ... and keeps its term lists
   h->an.shard_rank = h->shard_rank, h->an.shard_count = 1;  // (the tree engine's exchange plan is not used)
   int e = h->an.setup_blocks(1, n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(),
                              h->pCp.data(), h->pCi.data());
   if (e) return e;
-  e = P.run(n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(), h->pCp.data(), h->pCi.data(), h->an.AT.ptr.data(),
+  e = P.run(rq, n, me, m, h->pQp.data(), h->pQi.data(), h->pAp.data(), h->pAi.data(), h->pCp.data(), h->pCi.data(), h->an.AT.ptr.data(),
             h->an.AT.col.data());
   if (e) return e;
   P.narrow_copies(h->an.C.ptr.data(), h->an.C.col.data(), h->an.C.src.data(), h->an.CT.ptr.data(), h->an.CT.col.data(), h->an.CT.src.data());
@@ -585,7 +632,7 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   h->st.dim = n + me, h->st.sbw = -1;
   h->st.n_supernodes = P.K + 1, h->st.n_levels = P.K + 1;
   int mf = 0;
-  for (int k = 0; k < P.K; k++) mf = std::max(mf, P.nk[k] + P.mk[k] + P.nk[k + 1]);
+  for (int k = 0; k < P.K; k++) mf = std::max(mf, P.hess_order(k) + P.nk[k + 1]);
   h->st.max_front = mf;
   h->st.nnz_kkt = (long long)P.nq + P.na + P.nc;
   h->st.nnz_factor = P.v_elems + P.misc_elems;
@@ -595,11 +642,10 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   h->st.shard_rank = P.shard_rank, h->st.shard_count = P.shard_count;
   if (P.sharded) {
     long long bytes = 0, fl = 0;
-    const int NR = P.shard_count, RK = P.shard_rank;
+    const int NR = P.shard_count;
     for (int k = 0; k < P.K; k++) {
       bytes += (long long)sizeof(double) * (P.fgslot[k] + P.xslot[k]) * NR;  // (the gathered F: static, requested a stage ahead)
-      const int *cut = &P.xcut[(size_t)k * (NR + 1)];
-      const long long wd = cut[RK + 1] - cut[RK];
+      const long long wd = P.strip_width(k);
       const long long np = P.nk[k + 1], mm = P.mk[k], nn = P.nk[k], q = P.qmax[k], cx = P.cap[k + 1];
       // own: the strip of W, its columns of the control rows of G and of the carried rows, the tiles of its blocks of
       // G_xx; by every rank: the control columns, the rank-q update of the whole block
@@ -615,14 +661,13 @@ int staged_analyze(hqpkkt_t *h, int n, int me, int m, bool dense_dyn) {
   return 0;
 }
 
-static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w);
-static int staged_upload(hqpkkt_t *h) {
-  int e = ensure_device(h);
-  if (e) return e;
+// ---- the steps of staged_upload, in its order: each builds one group of StagedDev from the plan
+
+// what both engines keep in the handle: the CSR blocks, the values, the vectors and their pinned staging
+static int upload_handle_vectors(hqpkkt_t *h) {
   Analysis &an = h->an;
-  StagedDev &d = *h->sd;
-  kktdev::StagedPlan &P = d.plan;
   const int n = an.n, me = an.me, m = an.m;
+  int e;
   if ((e = h->td.Qf.upload(an.Qfull)) || (e = h->td.A.upload(an.A)) || (e = h->td.AT.upload(an.AT)) ||
       (e = h->td.C.upload(an.C)) || (e = h->td.CT.upload(an.CT)))
     return e;
@@ -636,380 +681,453 @@ static int staged_upload(hqpkkt_t *h) {
   if ((e = alloc_hpin(h))) return e;
   h->td.hstage.release();
   h->td.hstage_in = h->td.hstage_out = 0;
-  {
-    const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
-    if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
-      HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocDefault));
-      h->td.hstage_in = nin, h->td.hstage_out = nout;
-    }
+  const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
+  if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
+    HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocDefault));
+    h->td.hstage_in = nin, h->td.hstage_out = nout;
   }
-  {
-    const double one = 1.0;
-    HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
-    const double rows = 2.0 * n + me + m;
-    const double nnz = (double)an.Qfull.col.size() + 2.0 * an.A.col.size() + 2.0 * an.C.col.size();
-    h->short_rows = rows > 0 && nnz / rows < 8.0;
-  }
-  // (slack: 16-byte operand loads of column slices may read a tile's width past a block's last row)
+  const double one = 1.0;
+  HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
+  const double rows = 2.0 * n + me + m;
+  const double nnz = (double)an.Qfull.col.size() + 2.0 * an.A.col.size() + 2.0 * an.C.col.size();
+  h->short_rows = rows > 0 && nnz / rows < 8.0;
+  return 0;
+}
+// the arenas (slack: 16-byte operand loads of column slices may read a tile's width past a block's last row) and the
+// plan's tables; the arenas are cleared by upload_clear_arenas, behind the forms' allocations
+static int upload_arenas_tables(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Tables &t = d.tab;
+  int e;
   if ((e = d.F.alloc(P.f_elems + 8192)) || (e = d.V.alloc(P.v_elems + 8192)) || (e = d.misc.alloc(P.misc_elems + 8192)) ||
-      (e = d.dyn.alloc(P.dyn_ints)) || (e = d.eq_rows.upload(P.eq_rows)) || (e = d.fix_rows.upload(P.fix_rows)) ||
-      (e = d.fix_src.upload(P.fix_src)) || (e = d.h_tptr.upload(P.h_tptr)) || (e = d.chk_idx.upload(P.chk_idx)) ||
-      (e = d.chk_kind.upload(P.chk_kind)) || (e = d.h_dst.upload(P.h_dst)) || (e = d.a_dst.upload(P.a_dst)))
+      (e = t.dyn.alloc(P.dyn_ints)) || (e = t.eq_rows.upload(P.eq_rows)) || (e = t.fix_rows.upload(P.fix_rows)) ||
+      (e = t.fix_src.upload(P.fix_src)) || (e = t.h_tptr.upload(P.h_tptr)) || (e = t.chk_idx.upload(P.chk_idx)) ||
+      (e = t.chk_kind.upload(P.chk_kind)) || (e = t.h_dst.upload(P.h_dst)) || (e = t.a_dst.upload(P.a_dst)))
     return e;
-  if (!P.wr_rows.empty() && ((e = d.c_dst.upload(P.c_dst)) || (e = d.wr_rows.upload(P.wr_rows)))) return e;
-  if (P.rows_vec()) {
-    std::vector<stg::RowsBlock> rb(P.K + 1);
-    std::vector<int> of(P.wr_rows.size());
-    d.wr_pairs_max = 0;
-    for (int k = 0; k <= P.K; k++) {
-      rb[k] = stg::RowsBlock{P.oE[k], P.ldE[k], P.hess_order(k), P.nmk[k], P.wr_ptr[k], P.wide_count(k)};
-      for (int q = P.wr_ptr[k]; q < P.wr_ptr[k + 1]; q++) of[q] = k;
-      d.wr_pairs_max = std::max(d.wr_pairs_max, (P.hess_order(k) + 1) / 2);
-    }
-    Analysis::Csr cn, ctn;
-    cn.rows = m, cn.ptr = P.cn.ptr, cn.col = P.cn.col, cn.src = P.cn.src;
-    ctn.rows = n, ctn.ptr = P.ctn.ptr, ctn.col = P.ctn.col, ctn.src = P.ctn.src;
-    if ((e = d.wr_blk.upload(rb)) || (e = d.wr_blk_of.upload(of)) || (e = d.Cn.upload(cn)) || (e = d.CTn.upload(ctn)) || (e = d.wr_xc.alloc((size_t)n + 1)) ||
-        (e = d.wr_cdx.alloc((size_t)m + 1)))
-      return e;
-    HIPCHK(hipMemset(d.wr_cdx.p, 0, sizeof(double) * ((size_t)m + 1)));
-  }
-  {
-    std::vector<stg::HTerm> t(P.h_terms.size());
-    for (size_t k = 0; k < t.size(); k++) t[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
-    if ((e = d.h_terms.upload(t))) return e;
-  }
-  if (P.hess_dense) {  // the blocks Q_k, cleared once: the scatter and the store write the entries alone
-    std::vector<stg::HessDesc> hd(P.K + 1);
-    for (int k = 0; k <= P.K; k++) hd[k] = stg::HessDesc{P.oQ[k], P.ldQ[k], P.stage_packed(k) ? 0 : P.hess_order(k), P.nmk[k], 0};
-    d.hp_chunks_max = d.hp_nt_max = d.hs_nz_max = 0;
-    for (int k = 0; k <= P.K; k++)
-      if (!P.stage_packed(k)) d.hs_nz_max = std::max(d.hs_nz_max, P.hess_order(k));
-    if (P.hess_packed) {  // (packed stages: nz = 0 in k_hs_symv's list; the others: no tiles in k_hp_symv_tiles')
-      std::vector<stg::HpDesc> pd(P.K + 1);
-      for (int k = 0; k <= P.K; k++) {
-        const int nt = P.stage_packed(k) ? (P.hess_order(k) + stg::HP_T - 1) / stg::HP_T : 0;
-        int nchunks = 0;
-        for (int a = 0; a < nt; a++) nchunks += stg::hp_chunks(a);
-        pd[k] = stg::HpDesc{P.oQ[k], P.oQs[k], nt, P.hess_order(k), P.nmk[k], nchunks};
-        d.hp_nt_max = std::max(d.hp_nt_max, nt), d.hp_chunks_max = std::max(d.hp_chunks_max, nchunks);
-      }
-      static_assert(stg::HP_T == kktdev::StagedPlan::HESS_T && stg::HP_CHUNK == kktdev::StagedPlan::HESS_CHUNK, "the plan sizes the tiles and the scratch");
-      if ((e = d.hp_desc.upload(pd)) || (e = d.hess_scr.alloc((size_t)P.qs_elems + 16))) return e;
-    }
-    if ((e = d.Qd.alloc((size_t)P.q_elems + 16)) || (e = d.hess_desc.upload(hd)) || (e = d.hess_y.alloc((size_t)n + 1)) ||
-        (!P.q_dst.empty() && (e = d.q_dst.upload(P.q_dst))))
-      return e;
-    HIPCHK(hipMemset(d.Qd.p, 0, sizeof(double) * ((size_t)P.q_elems + 16)));
-  }
-  if (P.sparse_dyn && ((e = d.sp_arow.upload(P.sp_arow)) || (e = d.sp_tcol.upload(P.sp_tcol)))) return e;
-  if (P.sparse_dyn && !P.hv_cols.empty()) {
-    std::vector<int> of(P.nmk[P.K], -1);
-    for (int k = 0; k < P.K; k++)
-      for (int q = P.hv_ptr[k]; q < P.hv_ptr[k + 1]; q++) of[P.nmk[k] + P.hv_cols[q]] = q - P.hv_ptr[k];
-    if ((e = d.sp_tcol_light.upload(P.sp_tcol_light)) || (e = d.hv_cols.upload(P.hv_cols)) || (e = d.hv_of.upload(of))) return e;
-  }
-  if (P.dense_dyn && P.sharded) {
-    // the local blocks: own state columns [c0, c0 + wd) and the control columns; rank 0 adds what belongs to nobody's strip
-    const int NR = P.shard_count, RK = P.shard_rank;
-    std::vector<stg::DynLoc> dl(P.K + 1);
-    for (int k = 0; k <= P.K; k++) {
-      stg::DynLoc &x = dl[k];
-      x.oF = k < P.K ? P.oFl[k] : 0, x.ldf = k < P.K ? P.ldfl[k] : 0;
-      x.np = k < P.K ? P.nk[k + 1] : 0, x.nz = k < P.K ? P.nk[k] + P.mk[k] : P.nk[k];
-      x.col0 = P.nmk[k], x.row0 = k < P.K ? P.nks[k] : P.ndyn, x.ncur = P.nk[k];
-      x.c0 = P.xcut[(size_t)k * (NR + 1) + RK], x.wd = P.xcut[(size_t)k * (NR + 1) + RK + 1] - x.c0;
-      x.m = k < P.K ? P.mk[k] : 0, x.with_controls = RK == 0;
-    }
-    d.dyn_sum_x2 = ((long long)n + 15) / 16 * 16;
-    if ((e = d.dyn_loc.upload(dl)) || (e = d.dyn_sum.alloc((size_t)(d.dyn_sum_x2 + P.ndyn + 16)))) return e;
-  } else if (P.dense_dyn) {
-    std::vector<stg::DynDesc> dd(P.K + 1);
-    for (int k = 0; k <= P.K; k++) {
-      dd[k].oF = k < P.K ? P.oF[k] : 0, dd[k].ldf = k < P.K ? P.ldf[k] : 0;
-      dd[k].np = k < P.K ? P.nk[k + 1] : 0, dd[k].nz = k < P.K ? P.nk[k] + P.mk[k] : P.nk[k];
-      dd[k].col0 = P.nmk[k], dd[k].row0 = k < P.K ? P.nks[k] : P.ndyn, dd[k].ncur = P.nk[k];
-    }
-    if ((e = d.dyn_desc.upload(dd)) || (e = d.dyn_x1.alloc(n)) || (e = d.dyn_x2.alloc(P.ndyn))) return e;
-    {
-      int nzmax = 1;
-      for (int k = 0; k < P.K; k++) nzmax = std::max(nzmax, P.nk[k] + P.mk[k]);
-      nzmax = std::max(nzmax, P.nk[P.K]);
-      d.dyn_part_cols = (nzmax + 255) / 256;
-      if ((e = d.dyn_part.alloc((size_t)std::max(P.ndyn, 1) * d.dyn_part_cols))) return e;
-    }
-  }
+  std::vector<stg::HTerm> ht(P.h_terms.size());
+  for (size_t k = 0; k < ht.size(); k++) ht[k] = stg::HTerm{P.h_terms[k].s1, P.h_terms[k].s2, P.h_terms[k].wi};
+  return t.h_terms.upload(ht);
+}
+static int upload_clear_arenas(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
   HIPCHK(hipMemset(d.F.p, 0, sizeof(double) * std::max<long long>(P.f_elems, 1)));
   HIPCHK(hipMemset(d.V.p, 0, sizeof(double) * std::max<long long>(P.v_elems, 1)));
   HIPCHK(hipMemset(d.misc.p, 0, sizeof(double) * std::max<long long>(P.misc_elems, 1)));
-  HIPCHK(hipMemset(d.dyn.p, 0, sizeof(int) * std::max(P.dyn_ints, 1)));
-  // The control-sized chain of a stage on a second stream beside its large product G_xx.  Measured on one MI355X (same
-  // box, tools/c4_bench.py): stages of 1500 / 2000 / 2500 / 3000 states + 2.7 / 2.5 / 3.5 / 2.7 %, 5000 states - 1.1 % (the
-  // separate skinny product for the control rows of G and the contention cost more than the hidden chain), 1000 states
-  // - 13 %.  So: on for stages of 1280 .. 4096 states.  When sharded the
-  // separate product exists anyway (staged_stage_sharded).
-  {
-    d.overlap_mode = 2;  // by stage width
-    bool any = d.overlap_mode == 1 || P.sharded;
-    if (d.overlap_mode == 2 && !P.sparse_dyn)  // (the sparse form has no large product to run the chain beside)
-      for (int k = 0; k < P.K; k++) any = any || (P.nk[k] >= 1280 && P.nk[k] <= 4096);
-    if (!d.stream2 && any) {
-      {
-        // (the control-sized chain ahead of the large products' waiting workgroups: a chain of a few small kernels behind
-        // a launch that fills every CU otherwise waits a whole tile time for each of its launches)
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&d.stream2.h, hipStreamNonBlocking, hi));
-      }
-      HIPCHK(hipEventCreateWithFlags(&d.ev_fork.h, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&d.ev_join.h, hipEventDisableTiming));
-    }
-    d.overlap = d.stream2 != nullptr && d.overlap_mode != 0 && !P.sparse_dyn;
+  HIPCHK(hipMemset(d.tab.dyn.p, 0, sizeof(int) * std::max(P.dyn_ints, 1)));
+  return 0;
+}
+static int upload_wide_rows(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::WideRows &w = d.wr;
+  int e;
+  if (!P.wr_rows.empty() && ((e = w.c_dst.upload(P.c_dst)) || (e = w.rows.upload(P.wr_rows)))) return e;
+  if (!P.rows_vec()) return 0;
+  std::vector<stg::RowsBlock> rb(P.K + 1);
+  std::vector<int> of(P.wr_rows.size());
+  w.pairs_max = 0;
+  for (int k = 0; k <= P.K; k++) {
+    rb[k] = stg::RowsBlock{P.oE[k], P.ldE[k], P.hess_order(k), P.nmk[k], P.wr_ptr[k], P.wide_count(k)};
+    for (int q = P.wr_ptr[k]; q < P.wr_ptr[k + 1]; q++) of[q] = k;
+    w.pairs_max = std::max(w.pairs_max, (P.hess_order(k) + 1) / 2);
   }
-  {  // What the handle offers the launches of the dense product (stg::GemmCaps) - all of it here
-    stg::GemmCaps &c = d.caps;
-    c = stg::GemmCaps{};
-    c.variant = stg::gemm_variant_from_env();
-    if (c.variant != stg::GEMM_REG4) {  // (the register-staged loop stays selectable for comparisons)
-      if ((e = d.zeros.alloc(256))) return e;
-      HIPCHK(hipMemset(d.zeros.p, 0, sizeof(double) * 256));
-    } else
-      d.zeros.release();
-    c.unequal = stg::gemm_sk_table_from_env() && !P.sharded;
-    c.flags = P.sharded ? stg::GEMM_SHARDED : 0;
-    // stream-K grid: two workgroups per CU, if some product of the recursion has more tiles than that
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
-    c.cus = cus;
-    long long tmax = 0, pmax = 0;  // most tiles / most cut pieces of a product of this handle (column slices have fewer)
-    for (int k = 0; k < P.K; k++) {
-      const long long t1 = (P.nk[k + 1] + 127) / 128, t2 = (P.nk[k] + P.mk[k] + 127) / 128;
-      tmax = std::max(tmax, t1 * t2);
-      if (cus > 0)
-        for (long long t : {t1 * t2, t2 * (t2 + 1) / 2, t1 * (t1 + 1) / 2})
-          for (int grid : {2 * cus, cus})
-            pmax = std::max(pmax, stg::gemm_split_plan_pieces(stg::gemm_split_plan(t, (std::max(P.nk[k + 1], P.nk[k]) + stg::GEMM_BK - 1) / stg::GEMM_BK, grid)));
+  Analysis::Csr cn, ctn;
+  cn.rows = P.m, cn.ptr = P.cn.ptr, cn.col = P.cn.col, cn.src = P.cn.src;
+  ctn.rows = P.n, ctn.ptr = P.ctn.ptr, ctn.col = P.ctn.col, ctn.src = P.ctn.src;
+  if ((e = w.blk.upload(rb)) || (e = w.blk_of.upload(of)) || (e = w.Cn.upload(cn)) || (e = w.CTn.upload(ctn)) || (e = w.xc.alloc((size_t)P.n + 1)) ||
+      (e = w.cdx.alloc((size_t)P.m + 1)))
+    return e;
+  HIPCHK(hipMemset(w.cdx.p, 0, sizeof(double) * ((size_t)P.m + 1)));
+  return 0;
+}
+// (the blocks Q_k, cleared once: the scatter and the store write the entries alone)
+static int upload_hessians(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Hessians &q = d.hess;
+  if (!P.hess_dense) return 0;
+  int e;
+  std::vector<stg::HessDesc> hd(P.K + 1);
+  for (int k = 0; k <= P.K; k++) hd[k] = stg::HessDesc{P.oQ[k], P.ldQ[k], P.stage_packed(k) ? 0 : P.hess_order(k), P.nmk[k], 0};
+  q.hp_chunks_max = q.hp_nt_max = q.hs_nz_max = 0;
+  for (int k = 0; k <= P.K; k++)
+    if (!P.stage_packed(k)) q.hs_nz_max = std::max(q.hs_nz_max, P.hess_order(k));
+  if (P.hess_packed) {  // (packed stages: nz = 0 in k_hs_symv's list; the others: no tiles in k_hp_symv_tiles')
+    std::vector<stg::HpDesc> pd(P.K + 1);
+    for (int k = 0; k <= P.K; k++) {
+      const int nt = P.stage_packed(k) ? (P.hess_order(k) + stg::HP_T - 1) / stg::HP_T : 0;
+      int nchunks = 0;
+      for (int a = 0; a < nt; a++) nchunks += stg::hp_chunks(a);
+      pd[k] = stg::HpDesc{P.oQ[k], P.oQs[k], nt, P.hess_order(k), P.nmk[k], nchunks};
+      q.hp_nt_max = std::max(q.hp_nt_max, nt), q.hp_chunks_max = std::max(q.hp_chunks_max, nchunks);
     }
-    if (P.sharded)
-      for (int k = 0; k < P.K; k++) tmax = std::max<long long>(tmax, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
-    // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every list
-    // is checked against the workspace when it is made, gemm_choose_list.  Until round 5 the workspace was sized 16
-    // pieces per tile of the largest product - 3.4 GB at the headline width, per handle, sharded or not)
-    pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
-    c.sk_tiles = (int)tmax;
-    if (cus > 0) {
-      c.grid = stg::gemm_wgs_per_cu(c.variant) * cus;
-      // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
-      c.ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
-      c.cnt_elems = c.sk_tiles + 4;
-      // (the profile form's lists: a counter per tile of W and of the whole lower block G, at most two parked tiles per
-      // workgroup - 2 x grid slots, which the workspace above holds: pmax >= 4 cus + 64)
-      for (int k = 0; k < P.K && P.profile_dyn; k++)
-        if (P.pf_stage[k]) {
-          const long long t2 = (P.nk[k] + P.mk[k] + 127) / 128;
-          c.cnt_elems = std::max(c.cnt_elems, t2 * (t2 + 1) / 2 + 4);
-        }
-      if ((e = d.sk_ws.alloc((size_t)c.ws_elems)) || (e = d.sk_cnt.alloc((size_t)c.cnt_elems))) return e;
-      HIPCHK(hipMemset(d.sk_cnt.p, 0, sizeof(unsigned) * (size_t)c.cnt_elems));
-      if (d.stream2) {  // (the second stream's products cut in k)
-        c.ws2_elems = 8LL << 20;
-        if ((e = d.ks_ws2.alloc((size_t)c.ws2_elems))) return e;
+    static_assert(stg::HP_T == kktdev::StagedPlan::HESS_T && stg::HP_CHUNK == kktdev::StagedPlan::HESS_CHUNK, "the plan sizes the tiles and the scratch");
+    if ((e = q.hp_desc.upload(pd)) || (e = q.scr.alloc((size_t)P.qs_elems + 16))) return e;
+  }
+  if ((e = q.Q.alloc((size_t)P.q_elems + 16)) || (e = q.desc.upload(hd)) || (e = q.y.alloc((size_t)P.n + 1)) ||
+      (!P.q_dst.empty() && (e = q.q_dst.upload(P.q_dst))))
+    return e;
+  HIPCHK(hipMemset(q.Q.p, 0, sizeof(double) * ((size_t)P.q_elems + 16)));
+  return 0;
+}
+static int upload_sparse(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Sparse &s = d.sp;
+  if (!P.sparse_dyn) return 0;
+  int e;
+  if ((e = s.arow.upload(P.sp_arow)) || (e = s.tcol.upload(P.sp_tcol))) return e;
+  if (P.hv_cols.empty()) return 0;
+  std::vector<int> of(P.nmk[P.K], -1);
+  for (int k = 0; k < P.K; k++)
+    for (int q = P.hv_ptr[k]; q < P.hv_ptr[k + 1]; q++) of[P.nmk[k] + P.hv_cols[q]] = q - P.hv_ptr[k];
+  if ((e = s.tcol_light.upload(P.sp_tcol_light)) || (e = s.hv_cols.upload(P.hv_cols)) || (e = s.hv_of.upload(of))) return e;
+  return 0;
+}
+// the dense dynamics' tables of the residual products: over several ranks ...
+static int upload_dyn_residual_sharded(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  // the local blocks: own state columns [c0, c0 + wd) and the control columns; rank 0 adds what belongs to nobody's strip
+  std::vector<stg::DynLoc> dl(P.K + 1);
+  for (int k = 0; k <= P.K; k++) {
+    stg::DynLoc &x = dl[k];
+    x.oF = k < P.K ? P.oFl[k] : 0, x.ldf = k < P.K ? P.ldfl[k] : 0;
+    x.np = k < P.K ? P.nk[k + 1] : 0, x.nz = P.hess_order(k);
+    x.col0 = P.nmk[k], x.row0 = k < P.K ? P.nks[k] : P.ndyn, x.ncur = P.nk[k];
+    x.c0 = P.strip_first(k), x.wd = P.strip_width(k);
+    x.m = k < P.K ? P.mk[k] : 0, x.with_controls = P.shard_rank == 0;
+  }
+  d.dres_sh.sum_x2 = ((long long)P.n + 15) / 16 * 16;
+  int e;
+  if ((e = d.dres_sh.loc.upload(dl)) || (e = d.dres_sh.sum.alloc((size_t)(d.dres_sh.sum_x2 + P.ndyn + 16)))) return e;
+  return 0;
+}
+// ... and on one GPU
+static int upload_dyn_residual(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::DynResidual &r = d.dres;
+  std::vector<stg::DynDesc> dd(P.K + 1);
+  int nzmax = 1;
+  for (int k = 0; k <= P.K; k++) {
+    dd[k].oF = k < P.K ? P.oF[k] : 0, dd[k].ldf = k < P.K ? P.ldf[k] : 0;
+    dd[k].np = k < P.K ? P.nk[k + 1] : 0, dd[k].nz = P.hess_order(k);
+    dd[k].col0 = P.nmk[k], dd[k].row0 = k < P.K ? P.nks[k] : P.ndyn, dd[k].ncur = P.nk[k];
+    nzmax = std::max(nzmax, P.hess_order(k));
+  }
+  int e;
+  if ((e = r.desc.upload(dd)) || (e = r.x1.alloc(P.n)) || (e = r.x2.alloc(P.ndyn))) return e;
+  r.part_cols = (nzmax + 255) / 256;
+  return r.part.alloc((size_t)std::max(P.ndyn, 1) * r.part_cols);
+}
+
+// The control-sized chain of a stage on a second stream beside its large product G_xx.  Measured on one MI355X (same
+// box, tools/c4_bench.py): stages of 1500 / 2000 / 2500 / 3000 states + 2.7 / 2.5 / 3.5 / 2.7 %, 5000 states - 1.1 % (the
+// separate skinny product for the control rows of G and the contention cost more than the hidden chain), 1000 states
+// - 13 %.  So: on for stages of 1280 .. 4096 states - the one place that says so.  When sharded the separate product
+// exists anyway (staged_stage_sharded).
+static bool chain_beside_gxx(int nn) { return nn >= 1280 && nn <= 4096; }
+static int upload_second_stream(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  bool any = P.sharded;
+  if (!P.sparse_dyn)  // (the sparse form has no large product to run the chain beside)
+    for (int k = 0; k < P.K; k++) any = any || chain_beside_gxx(P.nk[k]);
+  if (d.s2.stream || !any) return 0;
+  // (the control-sized chain ahead of the large products' waiting workgroups: a chain of a few small kernels behind
+  // a launch that fills every CU otherwise waits a whole tile time for each of its launches)
+  int lo = 0, hi = 0;
+  HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  HIPCHK(hipStreamCreateWithPriority(&d.s2.stream.h, hipStreamNonBlocking, hi));
+  HIPCHK(hipEventCreateWithFlags(&d.s2.fork.h, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&d.s2.join.h, hipEventDisableTiming));
+  return 0;
+}
+// What the handle offers the launches of the dense product (stg::GemmCaps) - all of it here
+static int upload_product_caps(hqpkkt_t *h) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Product &pr = d.prod;
+  int e;
+  stg::GemmCaps &c = pr.caps;
+  c = stg::GemmCaps{};
+  c.variant = stg::gemm_variant_from_env();
+  if (c.variant != stg::GEMM_REG4) {  // (the register-staged loop stays selectable for comparisons)
+    if ((e = pr.zeros.alloc(256))) return e;
+    HIPCHK(hipMemset(pr.zeros.p, 0, sizeof(double) * 256));
+  } else
+    pr.zeros.release();
+  c.unequal = stg::gemm_sk_table_from_env() && !P.sharded;
+  c.flags = P.sharded ? stg::GEMM_SHARDED : 0;
+  // stream-K grid: two workgroups per CU, if some product of the recursion has more tiles than that
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+  c.cus = cus;
+  long long tmax = 0, pmax = 0;  // most tiles / most cut pieces of a product of this handle (column slices have fewer)
+  for (int k = 0; k < P.K; k++) {
+    const long long t1 = (P.nk[k + 1] + 127) / 128, t2 = (P.hess_order(k) + 127) / 128;
+    tmax = std::max(tmax, t1 * t2);
+    if (cus > 0)
+      for (long long t : {t1 * t2, t2 * (t2 + 1) / 2, t1 * (t1 + 1) / 2})
+        for (int grid : {2 * cus, cus})
+          pmax = std::max(pmax, stg::gemm_split_plan_pieces(stg::gemm_split_plan(t, (std::max(P.nk[k + 1], P.nk[k]) + stg::GEMM_BK - 1) / stg::GEMM_BK, grid)));
+  }
+  if (P.sharded)
+    for (int k = 0; k < P.K; k++) tmax = std::max<long long>(tmax, P.gtile_ptr[k + 1] - P.gtile_ptr[k]);
+  // (a plan has at most two cut phases of at most one unit per workgroup of the grid each: gemm_split_plan; every list
+  // is checked against the workspace when it is made, gemm_choose_list.  Until round 5 the workspace was sized 16
+  // pieces per tile of the largest product - 3.4 GB at the headline width, per handle, sharded or not)
+  pmax = std::max(pmax * 5 / 4 + 64, 4LL * cus + 64);
+  c.sk_tiles = (int)tmax;
+  if (cus <= 0) return 0;
+  c.grid = stg::gemm_wgs_per_cu(c.variant) * cus;
+  // (the cut form of the 64 x 64 tiles: at most two phases of one unit per workgroup, up to 3/4 of its grid in tiles)
+  c.ws_elems = std::max<long long>(pmax, 1) * 128 * 128;
+  c.cnt_elems = c.sk_tiles + 4;
+  // (the profile form's lists: a counter per tile of W and of the whole lower block G, at most two parked tiles per
+  // workgroup - 2 x grid slots, which the workspace above holds: pmax >= 4 cus + 64)
+  for (int k = 0; k < P.K; k++)
+    if (P.stage_seq(k) == kktdev::SEQ_PROFILE) {
+      const long long t2 = (P.hess_order(k) + 127) / 128;
+      c.cnt_elems = std::max(c.cnt_elems, t2 * (t2 + 1) / 2 + 4);
+    }
+  if ((e = pr.sk_ws.alloc((size_t)c.ws_elems)) || (e = pr.sk_cnt.alloc((size_t)c.cnt_elems))) return e;
+  HIPCHK(hipMemset(pr.sk_cnt.p, 0, sizeof(unsigned) * (size_t)c.cnt_elems));
+  if (d.s2.stream) {  // (the second stream's products cut in k)
+    c.ws2_elems = 8LL << 20;
+    if ((e = pr.ks_ws2.alloc((size_t)c.ws2_elems))) return e;
+  }
+  return 0;
+}
+// Which sequence every stage runs (StagedDev::Product::seq): the plan's answer, and of its dense stages
+// - which form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can (the
+//   tests), unset: those whose W launch also delivers the control rows of G (Product::ctrl_rows: the control-row
+//   segment, staged_w_args) and whose width is not one of those that run the chain beside G_xx - with the thin product
+//   for the control rows the sequence only takes as long as the one with the separate update
+//   (profiles/r08_stage_order.txt).  A stage can when its K has order 1 .. 64 (k_st_rm writes -Rm), its control
+//   columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA;
+// - which of the others run the control-sized chain on the second stream (staged_stage_dense): the widths that gain by
+//   it, with controls that start at an even column (16-byte loads of W + n), and no wide rows of C, whose product adds
+//   into the whole lower block of G.
+static int upload_sequences(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Product &pr = d.prod;
+  int e;
+  pr.ctl.release();
+  if ((e = pr.ctl.alloc(8))) return e;
+  HIPCHK(hipMemset(pr.ctl.p, 0, sizeof(unsigned) * 8));
+  pr.ctrl_rows.assign(P.K + 1, 0);
+  const char *fv = getenv("HQPKKT_FUSED_V");
+  const int mode = fv ? atoi(fv) : 2;
+  pr.fused.assign(P.K + 1, 0);
+  pr.seq.resize(P.K);
+  long long nrm = 0;
+  // the schedule of a stage's launch, asked of the launches' own rule (form NONE: refused); equal requests - the stages
+  // of a time-invariant system - are answered once.  Nothing is kept: the dry walk makes what the launches look up
+  std::vector<std::pair<stg::GemmRequest, stg::GemmSchedule>> asked;
+  auto ask = [&](const stg::GemmRequest &rq) -> const stg::GemmSchedule & {
+    for (const auto &a : asked)
+      if (a.first == rq) return a.second;
+    asked.emplace_back(rq, stg::GemmSchedule{});
+    if (stg::gemm_schedule(pr.caps, rq, asked.back().second)) asked.back().second = stg::GemmSchedule{};
+    return asked.back().second;
+  };
+  auto can_fuse = [&](int k) -> bool {
+    const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
+    if (mode == 0 || !pr.zeros.p) return false;
+    if (P.wide_count(k)) return false;  // (the wide rows' product goes into the work block G)
+    if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0) return false;
+    stg::GemmRequest rt;  // the thin product for the control rows of G behind the W launch
+    rt.M = P.mk[k], rt.N = nn + P.mk[k], rt.K = np;
+    if (ask(stg::gemm_request(staged_v_args(d, k))).f.kind == stg::GEMM_FORM_NONE) return false;
+    // the control rows of G out of the W launch: a cut form with a list in the segment's order, and the guarded
+    // product behind it one cut in k (the kernels that know the guard)
+    pr.ctrl_rows[k] = ask(rt).f.kind == stg::GEMM_FORM_KS && ask(stg::gemm_request(staged_w_args(d, k, true))).seg;
+    if (mode == 1 || (pr.ctrl_rows[k] && !chain_beside_gxx(nn))) return true;
+    pr.ctrl_rows[k] = 0;
+    return false;
+  };
+  const bool chain2 = d.s2.stream != nullptr;
+  for (int k = 0; k < P.K; k++) {
+    pr.seq[k] = P.stage_seq(k);
+    if (pr.seq[k] != kktdev::SEQ_DENSE) continue;  // (sharded, sparse, profile: the sequence forms V_k by the separate update)
+    if (can_fuse(k)) {
+      pr.seq[k] = kktdev::SEQ_FUSED, pr.fused[k] = 1;
+      nrm = std::max(nrm, (long long)P.qmax[k] * P.ldy[k]);
+    } else if (chain2 && P.mk[k] > 0 && P.nk[k] % 2 == 0 && chain_beside_gxx(P.nk[k]) && !P.wide_count(k))
+      pr.seq[k] = kktdev::SEQ_DENSE_CHAIN2;
+  }
+  pr.fv_nrm.release();
+  if (nrm > 0) {  // (slack: the operand loads of the last tile column read a tile's width past a row)
+    if ((e = pr.fv_nrm.alloc((size_t)nrm + 8192))) return e;
+    HIPCHK(hipMemset(pr.fv_nrm.p, 0, sizeof(double) * ((size_t)nrm + 8192)));
+  }
+  return 0;
+}
+static int upload_sharded(hqpkkt_t *h) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Sharded &sh = d.sh;
+  if (!P.sharded) return 0;
+  int e;
+  const int NR = P.shard_count, RK = P.shard_rank;
+  std::vector<stg::StripTab> wt(P.K + 1);
+  std::vector<stg::RectTab> rt(P.K + 1);
+  std::vector<stg::PackRect> pr;
+  sh.prect_ptr.assign(P.K + 1, 0);
+  for (int k = 0; k < P.K; k++) {
+    const int *cut = &P.xcut[(size_t)k * (NR + 1)];
+    stg::StripTab &t = wt[k];
+    stg::RectTab &r = rt[k];
+    t.nranks = r.nranks = NR;
+    for (int p = 0; p <= NR; p++) {
+      t.cut[p] = r.cut[p] = cut[p];
+      if (p < NR) t.off[p] = (long long)p * P.fgslot[k], t.ld[p] = (cut[p + 1] - cut[p] + P.mk[k] + 7) / 8 * 8;
+    }
+    for (auto &b : r.blk) b.off[0] = b.off[1] = 0, b.rsplit = 1 << 30, b.pad = 0;
+    sh.prect_ptr[k] = (int)pr.size();
+    for (int q = P.xrect_ptr[k]; q < P.xrect_ptr[k + 1]; q++) {
+      const kktdev::StagedPlan::XRect &x = P.xrects[q];
+      stg::RectTab::Block &b = r.blk[x.a * 16 + x.b];
+      const long long off = (long long)x.owner * P.xslot[k] + x.off;
+      if (x.r0 == cut[x.a])
+        b.off[0] = off;
+      else
+        b.off[1] = off, b.rsplit = x.r0;
+      if (x.owner == RK) {
+        stg::PackRect pk{};
+        if (x.mine_rows)
+          pk.r0 = x.r0, pk.c0 = x.c0, pk.rows = x.r1 - x.r0, pk.cols = x.c1 - x.c0, pk.transpose = 0;
+        else  // computed for the partner's rows in the own row strip of G: rows = own columns
+          pk.r0 = x.c0, pk.c0 = x.r0, pk.rows = x.c1 - x.c0, pk.cols = x.r1 - x.r0, pk.transpose = 1;
+        pk.off = x.off;
+        pr.push_back(pk);
       }
     }
   }
-  // Which stages form V_k in the G_xx launch (staged_stage_fused).  HQPKKT_FUSED_V=0: none, 1: every stage that can
-  // (the tests), unset: those whose W launch also delivers the control rows of G (StagedDev::ctrl_rows: the control-row
-  // segment, staged_w_args) and whose width is not one of those that run the chain beside G_xx (overlap_mode) - with
-  // the thin product for the control rows the sequence only takes as long as the one with the separate update
-  // (profiles/r08_stage_order.txt).  A stage can when its K has order 1 .. 64 (k_st_rm
-  // writes -Rm), its control columns start at an even column and the launch gets 128 x 128 tiles staged by LDS-DMA
-  {
-    d.ctl.release();
-    if ((e = d.ctl.alloc(8))) return e;
-    HIPCHK(hipMemset(d.ctl.p, 0, sizeof(unsigned) * 8));
-    d.ctrl_rows.assign(P.K + 1, 0);
-    const char *fv = getenv("HQPKKT_FUSED_V");
-    const int mode = fv ? atoi(fv) : 2;
-    d.fused.assign(P.K + 1, 0);
-    long long nrm = 0;
-    // the schedule of a stage's launch, asked of the launches' own rule (form NONE: refused); equal requests - the stages
-    // of a time-invariant system - are answered once.  Nothing is kept: the dry walk below makes what the launches look up
-    std::vector<std::pair<stg::GemmRequest, stg::GemmSchedule>> asked;
-    auto ask = [&](const stg::GemmRequest &rq) -> const stg::GemmSchedule & {
-      for (const auto &a : asked)
-        if (a.first == rq) return a.second;
-      asked.emplace_back(rq, stg::GemmSchedule{});
-      if (stg::gemm_schedule(d.caps, rq, asked.back().second)) asked.back().second = stg::GemmSchedule{};
-      return asked.back().second;
-    };
-    if (mode != 0 && !P.sharded && !P.sparse_dyn && d.zeros.p)
-      for (int k = 0; k < P.K; k++) {
-        const int nn = P.nk[k], q = P.qmax[k], np = P.nk[k + 1];
-        if (P.profile_dyn && P.pf_stage[k]) continue;  // (the profile sequence forms V_k by the separate update)
-        if (P.wide_count(k)) continue;                  // (the wide rows' product goes into the work block G)
-        if (P.big[k] || q <= 0 || q > 64 || (nn & 1) || np <= 0) continue;
-        stg::GemmRequest rt;  // the thin product for the control rows of G behind the W launch
-        rt.M = P.mk[k], rt.N = nn + P.mk[k], rt.K = np;
-        if (ask(stg::gemm_request(staged_v_args(d, k))).f.kind == stg::GEMM_FORM_NONE) continue;
-        // the control rows of G out of the W launch: a cut form with a list in the segment's order, and the guarded
-        // product behind it one cut in k (the kernels that know the guard)
-        d.ctrl_rows[k] = ask(rt).f.kind == stg::GEMM_FORM_KS && ask(stg::gemm_request(staged_w_args(d, k, true))).seg;
-        if (mode != 1 && (!d.ctrl_rows[k] || (nn >= 1280 && nn <= 4096))) {
-          d.ctrl_rows[k] = 0;
-          continue;
-        }
-        d.fused[k] = 1;
-        nrm = std::max(nrm, (long long)q * P.ldy[k]);
+  sh.prect_ptr[P.K] = (int)pr.size();
+  if (pr.empty()) pr.push_back(stg::PackRect{});
+  std::vector<int> gt = P.gtile;
+  if (gt.empty()) gt.push_back(0);
+  // which tiles of the work block G of a stage this rank computes (rows: its strip from c0 on)
+  std::vector<unsigned> ow;
+  sh.gowned_off.assign(P.K + 1, 0);
+  for (int k = 0; k < P.K; k++) {
+    sh.gowned_off[k] = (long long)ow.size();
+    const int ntc = (P.nk[k] + 127) / 128, r0 = P.strip_first(k) / 128;
+    ow.resize(ow.size() + ((size_t)ntc * ntc + 31) / 32, 0u);
+    for (int t = P.gtile_ptr[k]; t < P.gtile_ptr[k + 1]; t++) {
+      const int tr = r0 + (P.gtile[t] >> 16), tc = P.gtile[t] & 0xffff;
+      if (tr < ntc && tc < ntc) {
+        const size_t bit = (size_t)tr * ntc + tc;
+        ow[sh.gowned_off[k] + bit / 32] |= 1u << (bit % 32);
       }
-    d.fv_nrm.release();
-    if (nrm > 0) {  // (slack: the operand loads of the last tile column read a tile's width past a row)
-      if ((e = d.fv_nrm.alloc((size_t)nrm + 8192))) return e;
-      HIPCHK(hipMemset(d.fv_nrm.p, 0, sizeof(double) * ((size_t)nrm + 8192)));
     }
   }
-  if (P.sharded) {
-    const int NR = P.shard_count, RK = P.shard_rank;
-    std::vector<stg::StripTab> wt(P.K + 1);
-    std::vector<stg::RectTab> rt(P.K + 1);
-    std::vector<stg::PackRect> pr;
-    d.prect_ptr.assign(P.K + 1, 0);
-    for (int k = 0; k < P.K; k++) {
-      const int *cut = &P.xcut[(size_t)k * (NR + 1)];
-      stg::StripTab &t = wt[k];
-      stg::RectTab &r = rt[k];
-      t.nranks = r.nranks = NR;
-      for (int p = 0; p <= NR; p++) {
-        t.cut[p] = r.cut[p] = cut[p];
-        if (p < NR) t.off[p] = (long long)p * P.fgslot[k], t.ld[p] = (cut[p + 1] - cut[p] + P.mk[k] + 7) / 8 * 8;
-      }
-      for (auto &b : r.blk) b.off[0] = b.off[1] = 0, b.rsplit = 1 << 30, b.pad = 0;
-      d.prect_ptr[k] = (int)pr.size();
-      for (int q = P.xrect_ptr[k]; q < P.xrect_ptr[k + 1]; q++) {
-        const kktdev::StagedPlan::XRect &x = P.xrects[q];
-        stg::RectTab::Block &b = r.blk[x.a * 16 + x.b];
-        const long long off = (long long)x.owner * P.xslot[k] + x.off;
-        if (x.r0 == cut[x.a])
-          b.off[0] = off;
-        else
-          b.off[1] = off, b.rsplit = x.r0;
-        if (x.owner == RK) {
-          stg::PackRect pk{};
-          if (x.mine_rows)
-            pk.r0 = x.r0, pk.c0 = x.c0, pk.rows = x.r1 - x.r0, pk.cols = x.c1 - x.c0, pk.transpose = 0;
-          else  // computed for the partner's rows in the own row strip of G: rows = own columns
-            pk.r0 = x.c0, pk.c0 = x.r0, pk.rows = x.c1 - x.c0, pk.cols = x.r1 - x.r0, pk.transpose = 1;
-          pk.off = x.off;
-          pr.push_back(pk);
-        }
-      }
-    }
-    d.prect_ptr[P.K] = (int)pr.size();
-    if (pr.empty()) pr.push_back(stg::PackRect{});
-    std::vector<int> gt = P.gtile;
-    if (gt.empty()) gt.push_back(0);
-    // which tiles of the work block G of a stage this rank computes (rows: its strip from c0 on)
-    std::vector<unsigned> ow;
-    d.gowned_off.assign(P.K + 1, 0);
-    for (int k = 0; k < P.K; k++) {
-      d.gowned_off[k] = (long long)ow.size();
-      const int ntc = (P.nk[k] + 127) / 128, r0 = P.xcut[(size_t)k * (NR + 1) + RK] / 128;
-      ow.resize(ow.size() + ((size_t)ntc * ntc + 31) / 32, 0u);
-      for (int t = P.gtile_ptr[k]; t < P.gtile_ptr[k + 1]; t++) {
-        const int tr = r0 + (P.gtile[t] >> 16), tc = P.gtile[t] & 0xffff;
-        if (tr < ntc && tc < ntc) {
-          const size_t bit = (size_t)tr * ntc + tc;
-          ow[d.gowned_off[k] + bit / 32] |= 1u << (bit % 32);
-        }
-      }
-    }
-    d.gowned_off[P.K] = (long long)ow.size();
-    if (ow.empty()) ow.push_back(0u);
-    if ((e = d.wtabs.upload(wt)) || (e = d.rtabs.upload(rt)) || (e = d.prects.upload(pr)) || (e = d.gtile.upload(gt)) ||
-        (e = d.gowned.upload(ow)))
-      return e;
-    if (!d.ev_x1) HIPCHK(hipEventCreateWithFlags(&d.ev_x1.h, hipEventDisableTiming));
-    if (h->xchg_sfn && !d.stream_x) {
-      HIPCHK(hipStreamCreateWithFlags(&d.stream_x.h, hipStreamNonBlocking));
-      for (EventOwner *ev : {&d.ev_w[0], &d.ev_w[1], &d.ev_w[2], &d.ev_x[0], &d.ev_x[1], &d.ev_x[2]})
-        HIPCHK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
-    }
+  sh.gowned_off[P.K] = (long long)ow.size();
+  if (ow.empty()) ow.push_back(0u);
+  if ((e = sh.wtabs.upload(wt)) || (e = sh.rtabs.upload(rt)) || (e = sh.prects.upload(pr)) || (e = sh.gtile.upload(gt)) ||
+      (e = sh.gowned.upload(ow)))
+    return e;
+  if (!sh.ev_x1) HIPCHK(hipEventCreateWithFlags(&sh.ev_x1.h, hipEventDisableTiming));
+  if (h->xchg_sfn && !sh.stream) {
+    HIPCHK(hipStreamCreateWithFlags(&sh.stream.h, hipStreamNonBlocking));
+    for (EventOwner *ev : {&sh.ev_w[0], &sh.ev_w[1], &sh.ev_w[2], &sh.ev_x[0], &sh.ev_x[1], &sh.ev_x[2]})
+      HIPCHK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
   }
-  // The work lists of the recursion's cut products and the tile orders of its triangular ones (G, V): a dry walk of the
-  // factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
-  d.gemms.entries.clear();
-  d.pf_rng.release(), d.pf_part.release(), d.pk_tab.release(), d.pk_part.release();
-  if (P.profile_dyn && !P.pf_rng.empty()) {
-    long long part = 1;
-    for (int k = 0; k < P.K; k++)
-      if (P.pf_stage[k])
-        part = std::max(part, (long long)stg::pf_chunks(P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.panels(k), P.nk[k + 1]) * (P.nk[k] + P.mk[k]));
-    if ((e = d.pf_rng.upload(P.pf_rng)) || (e = d.pf_part.alloc((size_t)part))) return e;
-    if (P.packed) {
-      std::vector<stg::PackPanel> tab(P.pk_off.size(), stg::PackPanel{0, 0});
-      long long cpart = 1;
-      for (int k = 0; k < P.K; k++) {
-        if (!P.pk_stage(k)) continue;
-        for (int q = P.pf_ptr[k]; q < P.pf_ptr[k + 1]; q++) tab[q] = stg::PackPanel{P.pk_off[q] - 16LL * P.pf_rng[2 * q] * P.pk_ld[q], P.pk_ld[q]};
-        cpart = std::max(cpart, (long long)stg::pk_chunks(P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], P.panels(k), P.nk[k + 1]) * P.cap[k + 1] * (P.nk[k] + P.mk[k]));
-      }
-      if ((e = d.pk_tab.upload(tab)) || (e = d.pk_part.alloc((size_t)cpart))) return e;
-    }
+  return 0;
+}
+static int upload_profile(StagedDev &d) {
+  const kktdev::StagedPlan &P = d.plan;
+  StagedDev::Profile &pf = d.pf;
+  int e;
+  pf.rng.release(), pf.part.release(), pf.pk_tab.release(), pf.pk_part.release();
+  if (!P.profile_dyn || P.pf_rng.empty()) return 0;
+  long long part = 1;
+  for (int k = 0; k < P.K; k++)
+    if (P.pf_stage[k]) part = std::max(part, (long long)stg::pf_chunks(P.stage_ranges(k), P.panels(k), P.nk[k + 1]) * P.hess_order(k));
+  if ((e = pf.rng.upload(P.pf_rng)) || (e = pf.part.alloc((size_t)part))) return e;
+  if (!P.packed) return 0;
+  std::vector<stg::PackPanel> tab(P.pk_off.size(), stg::PackPanel{0, 0});
+  long long cpart = 1;
+  for (int k = 0; k < P.K; k++) {
+    if (!P.pk_stage(k)) continue;
+    for (int q = P.pf_ptr[k]; q < P.pf_ptr[k + 1]; q++) tab[q] = stg::PackPanel{P.pk_off[q] - 16LL * P.pf_rng[2 * q] * P.pk_ld[q], P.pk_ld[q]};
+    cpart = std::max(cpart, (long long)stg::pk_chunks(P.stage_ranges(k), P.panels(k), P.nk[k + 1]) * P.cap[k + 1] * P.hess_order(k));
   }
-  {
-    struct Listing {
-      hqpkkt_t *h;
-      ~Listing() { h->listing = false; }
-    } walk{h};
-    const auto t0 = std::chrono::steady_clock::now();
-    h->listing = true;
-    if ((e = staged_run_factor(h, nullptr, nullptr))) return e;
-    if (getenv("HQPKKT_TIMING"))
-      fprintf(stderr, "staged_upload: listing walk over %d stages %.3f ms (%zu schedules with a work list or a tile order)\n", P.K,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), d.gemms.entries.size());
-  }
-  d.lds_small = 0, d.lds_small_big = 0;
+  if ((e = pf.pk_tab.upload(tab)) || (e = pf.pk_part.alloc((size_t)cpart))) return e;
+  return 0;
+}
+// The work lists of the recursion's cut products and the tile orders of its triangular ones (G, V): a dry walk of the
+// factor sequence, in which st_gemm makes what it will look up and nothing is launched (hqpkkt::listing)
+static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w);
+static int upload_dry_walk(hqpkkt_t *h) {
+  StagedDev &d = *h->sd;
+  d.prod.gemms.entries.clear();
+  struct Listing {
+    hqpkkt_t *h;
+    ~Listing() { h->listing = false; }
+  } walk{h};
+  const auto t0 = std::chrono::steady_clock::now();
+  h->listing = true;
+  if (int e = staged_run_factor(h, nullptr, nullptr)) return e;
+  if (getenv("HQPKKT_TIMING"))
+    fprintf(stderr, "staged_upload: listing walk over %d stages %.3f ms (%zu schedules with a work list or a tile order)\n", d.plan.K,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), d.prod.gemms.entries.size());
+  return 0;
+}
+// the dynamic LDS this handle's one-workgroup kernels ask for, and the kernels' limits raised to it
+static int upload_lds_limits(hqpkkt_t *h) {
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  d.lds.small = 0, d.lds.small_big = 0;
   for (int k = 0; k < P.K; k++) {
     if (P.big[k])
-      d.lds_small_big = std::max(d.lds_small_big, stg::st_small_lds(P.mk[k], P.capn[k], true));
+      d.lds.small_big = std::max(d.lds.small_big, stg::st_small_lds(P.mk[k], P.capn[k], true));
     else
-      d.lds_small = std::max(d.lds_small, stg::st_small_lds(P.mk[k], P.capn[k]));
+      d.lds.small = std::max(d.lds.small, stg::st_small_lds(P.mk[k], P.capn[k]));
   }
-  {
-    const size_t q = (size_t)P.q0max;
-    d.lds_init = (size_t)kktdev::gj_lds_bytes((long long)q) - (P.big0 ? q * (q | 1) * 8 : 0);
-    d.lds_x0 = sizeof(double) * (3 * q + 64 * 65 + 8);
-  }
+  const size_t q = (size_t)P.q0max;
+  d.lds.init = (size_t)kktdev::gj_lds_bytes((long long)q) - (P.big0 ? q * (q | 1) * 8 : 0);
+  d.lds.x0 = sizeof(double) * (3 * q + 64 * 65 + 8);
   static std::mutex attr_mutex;  // function attributes are process state, shared by all handles - per DEVICE
   struct PerDev { size_t small = 0, small_big = 0, init = 0, init_big = 0, x0 = 0; bool gemm = false; };
   static PerDev per_dev[64];
   if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
-  {
-    std::lock_guard<std::mutex> lk(attr_mutex);
-    PerDev &pd = per_dev[h->opts.device];
-    if (!pd.gemm) {
-      HIPCHK(stg::gemm_set_attributes());
-      HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_rm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stg::st_rm_lds(64)));
-      pd.gemm = true;
-    }
-    // the LDS limit of a kernel goes up when a handle needs more than any before it on the device
-    auto raise = [](size_t &have, size_t want, std::initializer_list<const void *> kernels) -> hipError_t {
-      if (want <= have) return hipSuccess;
-      for (const void *k : kernels)
-        if (hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)) return r;
-      have = want;
-      return hipSuccess;
-    };
-    HIPCHK(raise(pd.small, d.lds_small, {(const void *)stg::k_st_small<256>, (const void *)stg::k_st_small<1024, false>}));
-    HIPCHK(raise(pd.small_big, d.lds_small_big, {(const void *)stg::k_st_small<1024>}));
-    if (!P.big0) HIPCHK(raise(pd.init, d.lds_init, {(const void *)stg::k_st_init_factor<256>}));
-    HIPCHK(raise(pd.x0, d.lds_x0, {(const void *)stg::k_st_x0_free}));
-    if (P.big0) HIPCHK(raise(pd.init_big, d.lds_init, {(const void *)stg::k_st_init_factor<1024>}));
+  std::lock_guard<std::mutex> lk(attr_mutex);
+  PerDev &pd = per_dev[h->opts.device];
+  if (!pd.gemm) {
+    HIPCHK(stg::gemm_set_attributes());
+    HIPCHK(hipFuncSetAttribute((const void *)stg::k_st_rm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stg::st_rm_lds(64)));
+    pd.gemm = true;
   }
-  if ((e = staged_build_symv_tables(d))) return e;
+  // the LDS limit of a kernel goes up when a handle needs more than any before it on the device
+  auto raise = [](size_t &have, size_t want, std::initializer_list<const void *> kernels) -> hipError_t {
+    if (want <= have) return hipSuccess;
+    for (const void *k : kernels)
+      if (hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)) return r;
+    have = want;
+    return hipSuccess;
+  };
+  HIPCHK(raise(pd.small, d.lds.small, {(const void *)stg::k_st_small<256>, (const void *)stg::k_st_small<1024, false>}));
+  HIPCHK(raise(pd.small_big, d.lds.small_big, {(const void *)stg::k_st_small<1024>}));
+  if (!P.big0) HIPCHK(raise(pd.init, d.lds.init, {(const void *)stg::k_st_init_factor<256>}));
+  HIPCHK(raise(pd.x0, d.lds.x0, {(const void *)stg::k_st_x0_free}));
+  if (P.big0) HIPCHK(raise(pd.init_big, d.lds.init, {(const void *)stg::k_st_init_factor<1024>}));
+  return 0;
+}
+
+static int staged_upload(hqpkkt_t *h) {
+  int e = ensure_device(h);
+  if (e) return e;
+  StagedDev &d = *h->sd;
+  const kktdev::StagedPlan &P = d.plan;
+  if ((e = upload_handle_vectors(h)) || (e = upload_arenas_tables(d)) || (e = upload_wide_rows(d)) || (e = upload_hessians(d)) || (e = upload_sparse(d))) return e;
+  if (P.dense_dyn && (e = P.sharded ? upload_dyn_residual_sharded(d) : upload_dyn_residual(d))) return e;
+  if ((e = upload_clear_arenas(d)) || (e = upload_second_stream(d)) || (e = upload_product_caps(h)) || (e = upload_sequences(d)) ||
+      (e = upload_sharded(h)) || (e = upload_profile(d)) || (e = upload_dry_walk(h)) || (e = upload_lds_limits(h)) ||
+      (e = staged_build_symv_tables(d)))
+    return e;
   h->uploaded = true;
   return 0;
 }
+
 
 // the dynamics block of stage k from the caller's F (n+ rows of n_k + m_k values) into the F arena: the whole block,
 // or - one system over several ranks - this rank's state columns and the control columns
@@ -1023,8 +1141,7 @@ static int staged_copy_block(hqpkkt_t *h, int k, const double *F, long long ldF,
       HIPCHK(hipMemcpy2DAsync(d.F.p + P.oF[k], sizeof(double) * P.ldf[k], F, sizeof(double) * ldF, sizeof(double) * (nn + mm), np, kind, h->stream));
     return 0;
   }
-  const int *cut = &P.xcut[(size_t)k * (P.shard_count + 1)];
-  const int c0 = cut[P.shard_rank], wd = cut[P.shard_rank + 1] - c0;
+  const int c0 = P.strip_first(k), wd = P.strip_width(k);
   double *dst = d.F.p + P.oFl[k];
   if (wd > 0) HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * P.ldfl[k], F + c0, sizeof(double) * ldF, sizeof(double) * wd, np, kind, h->stream));
   if (mm > 0) HIPCHK(hipMemcpy2DAsync(dst + wd, sizeof(double) * P.ldfl[k], F + nn, sizeof(double) * ldF, sizeof(double) * mm, np, kind, h->stream));
@@ -1044,25 +1161,24 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
   hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (Fblk)
     for (int k = 0; k < P.K; k++) {
-      const int nz = P.nk[k] + P.mk[k];
-      if (!Fblk[k] || ldF[k] < nz) return HQPKKT_E_SIZES;
+      if (!Fblk[k] || ldF[k] < P.hess_order(k)) return HQPKKT_E_SIZES;
       if ((e = staged_copy_block(h, k, Fblk[k], ldF[k], kind))) return e;
     }
   if (an.nq) HIPCHK(hipMemcpyAsync(h->td.vals.p, Qx, sizeof(double) * an.nq, kind, s));
   if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, s));
   if (an.nc) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, s));
-  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT, &d.Cn, &d.CTn})
+  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT, &d.wr.Cn, &d.wr.CTn})
     if (c->src.count)
       k_gather_values<<<nblk((long long)c->src.count), 256, 0, s>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
   HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
   if (an.na)
-    stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
+    stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.tab.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
   if (P.hess_dense && an.nq)  // Q's values into the blocks Q_k (CSR hand-over)
-    stg::k_hs_scatter<<<nblk(an.nq), 256, 0, s>>>(an.nq, d.q_dst.p, h->td.vals.p, d.Qd.p);
+    stg::k_hs_scatter<<<nblk(an.nq), 256, 0, s>>>(an.nq, d.hess.q_dst.p, h->td.vals.p, d.hess.Q.p);
   if (!P.wr_rows.empty())  // the wide rows of C into their blocks E_k
-    stg::k_st_scatter<<<nblk(an.nc), 256, 0, s>>>(an.nc, d.c_dst.p, h->td.vals.p + an.nq + an.na, d.F.p, d.misc.p);
+    stg::k_st_scatter<<<nblk(an.nc), 256, 0, s>>>(an.nc, d.wr.c_dst.p, h->td.vals.p + an.nq + an.na, d.F.p, d.misc.p);
   const int nchk = (int)P.chk_idx.size();
-  if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.chk_idx.p, d.chk_kind.p, h->td.vals.p, h->td.flags.p);
+  if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.tab.chk_idx.p, d.tab.chk_kind.p, h->td.vals.p, h->td.flags.p);
   int *hs = (int *)h->kept.hpin.p;
   HIPCHK(hipMemcpyAsync(hs, h->td.flags.p, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1090,16 +1206,16 @@ static int staged_gather_f(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   kktdev::StagedPlan &P = d.plan;
   const int NR = P.shard_count, RK = P.shard_rank, i = k & 1;
-  const int wd = P.xcut[(size_t)k * (NR + 1) + RK + 1] - P.xcut[(size_t)k * (NR + 1) + RK], nloc = wd + P.mk[k], np = P.nk[k + 1];
+  const int wd = P.strip_width(k), nloc = wd + P.mk[k], np = P.nk[k + 1];
   double *fg = d.misc.p + P.oFg[i], *mine = fg + (long long)RK * P.fgslot[k];
-  hipStream_t sA = h->stream, sX = (h->xchg_sfn && d.stream_x && !h->listing) ? d.stream_x : nullptr;
+  hipStream_t sA = h->stream, sX = (h->xchg_sfn && d.sh.stream && !h->listing) ? d.sh.stream : nullptr;
   hipStream_t on = sX ? sX : sA;
   int e;
-  if (sX && (e = stream_after(h, d.ev_w[i], sA, sX))) return e;
+  if (sX && (e = stream_after(h, d.sh.ev_w[i], sA, sX))) return e;
   if (nloc > 0 && np > 0)
     KLAUNCH(h, KC_ST_VEC, stg::k_st_copy2d<<<std::min(np, 2048), 256, 0, on>>>(stage_ptr(d, k).F, P.ldfl[k], mine, P.ldfl[k], np, nloc));
   if (P.fgslot[k] > 0 && (e = exchange(h, HQPKKT_XCHG_ALLGATHER, fg, P.fgslot[k], NR, sX))) return e;
-  if (sX) HIPCHK(hipEventRecord(d.ev_x[i], sX));
+  if (sX) HIPCHK(hipEventRecord(d.sh.ev_x[i], sX));
   return 0;
 }
 static int staged_stage_sharded(hqpkkt_t *h, int k) {
@@ -1114,11 +1230,11 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   const long long ldfl = P.ldfl[k], ldg = P.ldg[k], ldvn = P.ldv[k + 1], ldy = P.ldy[k], ldv = P.ldv[k], ldwl = P.ldwl[k], ldwu = P.ldwu;
   double *G = d.misc.p + P.oG, *Wl = d.misc.p + P.oWl, *Wu = d.misc.p + P.oWu, *xb = d.misc.p + P.oX;
   double *fg = d.misc.p + P.oFg[k & 1];  // the gathered local blocks of THIS stage (requested a stage ago)
-  hipStream_t sA = h->stream, sB = d.stream2 ? d.stream2 : h->stream;
+  hipStream_t sA = h->stream, sB = d.s2.stream ? d.s2.stream : h->stream;
   // the exchanges' own stream (stream-ordered transport; none in upload's dry walk, which enqueues nothing)
-  hipStream_t sX = (h->xchg_sfn && d.stream_x && !h->listing) ? d.stream_x : nullptr;
+  hipStream_t sX = (h->xchg_sfn && d.sh.stream && !h->listing) ? d.sh.stream : nullptr;
   StreamGuard guard{h, sA};
-  StreamFork chain{h, sA, sB, d.ev_fork, d.ev_join};
+  StreamFork chain{h, sA, sB, d.s2.fork, d.s2.join};
   const bool two = sB != sA;
   int e;
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
@@ -1133,9 +1249,9 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
   // stream there (0.2 ms), and beside the strip's product only where that one leaves CUs idle (one round of <= 256 tiles).
   const bool thin_first = wd >= 1024;
   h->stream = thin_first ? sA : sB;
-  if (sX) HIPCHK(hipStreamWaitEvent(h->stream, d.ev_x[k & 1], 0));
+  if (sX) HIPCHK(hipStreamWaitEvent(h->stream, d.sh.ev_x[k & 1], 0));
   {
-    const stg::StripTab *tab = d.wtabs.p + k;
+    const stg::StripTab *tab = d.sh.wtabs.p + k;
     const long long ld0 = (cut[1] - cut[0] + mm + 7) / 8 * 8;  // rank 0's local block: [F_0 | F_u]
     const double *Fu = fg + (cut[1] - cut[0]);
     auto thin = [&](const double *A, long long lda, int M, double *C, long long ldc, int cls) -> int {  // C = A' [F_x | F_u]
@@ -1151,35 +1267,35 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
     }
     if (cx > 0 && (e = thin(sn.BT, P.ldb[k + 1], cx, sp.N + (size_t)ek * P.ldn[k], P.ldn[k], KC_ST_GEMM_UPD))) return e;
   }
-  if (thin_first && (e = stream_after(h, d.ev_x1, sA, sB))) return e;  // the rest of the chain beside the large products
+  if (thin_first && (e = stream_after(h, d.sh.ev_x1, sA, sB))) return e;  // the rest of the chain beside the large products
   h->stream = sB;
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_eliminate(h, d, k, sp, sn, G, !two))) return e;
   // ---- sA: the strip of W, the rank's blocks of G_xx (rows = its strip) in one launch, H_xx, pack, the gather of the blocks
   h->stream = sA;
   if (wd > 0 && (e = st_gemm(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldfl, nullptr, 0, Wl, ldwl, np, wd, np, 1.0, 0.0, 0, 0}))) return e;
-  if (sX) HIPCHK(hipStreamWaitEvent(sA, d.ev_x[k & 1], 0));
+  if (sX) HIPCHK(hipStreamWaitEvent(sA, d.sh.ev_x[k & 1], 0));
   const int ntile = P.gtile_ptr[k + 1] - P.gtile_ptr[k];
   if (wd > 0 && ntile > 0) {
     stg::GemmArgs gg{Wl, ldwl, fg, 0, nullptr, 0, G + (long long)c0 * ldg, ldg, wd, nn, np, 1.0, 0.0, 0, 0};
-    gg.tile_map = d.gtile.p + P.gtile_ptr[k], gg.bstrips = d.wtabs.p + k;
+    gg.tile_map = d.sh.gtile.p + P.gtile_ptr[k], gg.bstrips = d.sh.wtabs.p + k;
     if ((e = st_gemm(h, gg, KC_ST_GEMM, true, ntile))) return e;
   }
   if (ne_x)  // H_xx into the rank's own tiles only (everything else in G is left over from earlier stages and read by nobody)
-    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_owned<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
-                                                                                  h->td.vals.p, h->td.wt.p, G, ldg, d.gowned.p + d.gowned_off[k], (nn + 127) / 128));
-  const int npk = d.prect_ptr[k + 1] - d.prect_ptr[k];
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_owned<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.tab.h_dst.p + P.h_ptr[k], d.tab.h_tptr.p + P.h_ptr[k], d.tab.h_terms.p,
+                                                                                  h->td.vals.p, h->td.wt.p, G, ldg, d.sh.gowned.p + d.sh.gowned_off[k], (nn + 127) / 128));
+  const int npk = d.sh.prect_ptr[k + 1] - d.sh.prect_ptr[k];
   if (npk > 0)
-    KLAUNCH(h, KC_ST_VEC, stg::k_st_pack_rects<<<dim3(512, npk), 256, 0, sA>>>(d.prects.p + d.prect_ptr[k], G, ldg, xb + (long long)RK * P.xslot[k]));
+    KLAUNCH(h, KC_ST_VEC, stg::k_st_pack_rects<<<dim3(512, npk), 256, 0, sA>>>(d.sh.prects.p + d.sh.prect_ptr[k], G, ldg, xb + (long long)RK * P.xslot[k]));
   if (P.xslot[k] > 0) {
-    if (sX && (e = stream_after(h, d.ev_w[2], sA, sX))) return e;
+    if (sX && (e = stream_after(h, d.sh.ev_w[2], sA, sX))) return e;
     if ((e = exchange(h, HQPKKT_XCHG_ALLGATHER, xb, P.xslot[k], NR, sX))) return e;
-    if (sX && (e = stream_after(h, d.ev_x[2], sX, sA))) return e;
+    if (sX && (e = stream_after(h, d.sh.ev_x[2], sX, sA))) return e;
   }
   if ((e = chain.join())) return e;  // (the chain ended with st_eliminate: nothing has gone to sB since)
   // V_k = G_xx - Y' Rm: lower tiles, mirrored; G_xx from the blocks
   stg::GemmArgs gu{sp.Y, ldy, sp.Rm, ldy, xb, 0, sp.V, ldv, nn, nn, q, -1.0, 1.0, 1, 1};
-  gu.rects = d.rtabs.p + k;
+  gu.rects = d.sh.rtabs.p + k;
   if ((e = st_gemm(h, gu, KC_ST_GEMM_UPD))) return e;  // (q = 0, a stage without controls: V_k = G_xx, the k loop is empty)
   st_keep_rows(h, d, k);
   return 0;
@@ -1192,7 +1308,7 @@ static int staged_stage_sharded(hqpkkt_t *h, int k) {
 // That needs Y and Rm BEFORE the large product, and the control-sized chain that makes them needs only the control rows
 // of G: G_u = W_u'F, a thin product (k_dgemm_tn_ks) with W's control columns.  All on the first stream: with the chain
 // on a second stream beside W (W_u = V+ f_u as a thin product of its own) the stage was slower in every placement that
-// was measured - profiles/r08_stage_order.txt.  Where the W launch takes the control-row segment (StagedDev::ctrl_rows) it
+// was measured - profiles/r08_stage_order.txt.  Where the W launch takes the control-row segment (StagedDev::Product::ctrl_rows) it
 // delivers G_u itself, and the thin product behind it is guarded: it runs only if an augmented tile of that launch found
 // W's control columns unfinished (GemmArgs::ctl, counted: hqpkkt_debug_get 44), and returns at once otherwise.
 static int staged_stage_fused(hqpkkt_t *h, int k) {
@@ -1201,16 +1317,16 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
   const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
   const long long ldf = P.ldf[k], ldg = P.ldg[k];
-  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW, *nRm = d.fv_nrm.p;
+  double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW, *nRm = d.prod.fv_nrm.p;
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
   int e;
   // W = V+ F; the control rows of G = W_u'F with H's control part; the carried rows N_k[e..] = B+ F
-  const bool seg = d.ctrl_rows[k];
+  const bool seg = d.prod.ctrl_rows[k];
   if ((e = st_gemm(h, staged_w_args(d, k, seg)))) return e;
   stg::GemmArgs gu{W + nn, ldf, sp.F, ldf, nullptr, 0, G + nn * ldg, ldg, mm, nz, np, 1.0, 0.0, 0, 0};
-  if (seg) gu.guard = d.ctl.p + 2;
+  if (seg) gu.guard = d.prod.ctl.p + 2;
   if (mm > 0 && (e = st_gemm(h, gu, KC_ST_GEMM_UPD))) return e;
-  if (seg && !h->listing) KLAUNCH(h, KC_ST_SMALL, stg::k_ctrl_rows_end<<<1, 64, 0, h->stream>>>(d.ctl.p));
+  if (seg && !h->listing) KLAUNCH(h, KC_ST_SMALL, stg::k_ctrl_rows_end<<<1, 64, 0, h->stream>>>(d.prod.ctl.p));
   st_add_q(h, d, k, nn, nz, nz, 0, G, ldg);
   st_add_h(h, d, P.h_mid[k], ne_u, G);
   if ((e = st_carried_rows(h, d, k, sp, sn, true)) || (e = st_eliminate(h, d, k, sp, sn, G, true, nRm))) return e;
@@ -1218,28 +1334,24 @@ static int staged_stage_fused(hqpkkt_t *h, int k) {
   if ((e = st_gemm(h, staged_v_args(d, k)))) return e;
   st_add_q(h, d, k, 0, nn, nn, 0, sp.V, P.ldv[k]);  // (the whole of Q_xx, which is its own image bit for bit)
   if (ne_x)
-    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.h_dst.p + P.h_ptr[k], d.h_tptr.p + P.h_ptr[k], d.h_terms.p,
+    KLAUNCH(h, KC_ASSEMBLE, stg::k_st_add_h_sym<<<nblk(ne_x), 256, 0, h->stream>>>(ne_x, d.tab.h_dst.p + P.h_ptr[k], d.tab.h_tptr.p + P.h_ptr[k], d.tab.h_terms.p,
                                                                                  h->td.vals.p, h->td.wt.p, sp.V, ldg, P.ldv[k]));
   return 0;
 }
 
 // One stage of the backward recursion in the dense form on one GPU: W = V+ F, G = F'W with H, the carried rows, the
-// control-sized elimination, the rank-q update V = G_xx - Y'Rm.  Stages of the widths that gain by it
-// (StagedDev::overlap_mode) run the control-sized chain on the second stream, beside the large product G_xx.
-static int staged_stage_dense(hqpkkt_t *h, int k) {
+// control-sized elimination, the rank-q update V = G_xx - Y'Rm.  ovl (SEQ_DENSE_CHAIN2, upload_sequences): the stage
+// runs the control-sized chain on the second stream, beside the large product G_xx.
+static int staged_stage_dense(hqpkkt_t *h, int k, bool ovl) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
   StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
   const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1], nz = nn + mm;
   const long long ldf = P.ldf[k], ldg = P.ldg[k], ldvn = P.ldv[k + 1];
   double *G = d.misc.p + P.oG, *W = d.misc.p + P.oW;
-  // The control-sized chain of the stage on the second stream, beside the large product G_xx (needs the
-  // control columns to start at an even column: 16-byte loads of W + n)
-  // (not a stage with wide rows of C: their product adds into the whole lower block of G)
-  const bool ovl = d.overlap && mm > 0 && (nn % 2 == 0) && (d.overlap_mode == 1 || (nn >= 1280 && nn <= 4096)) && !P.wide_count(k);
-  hipStream_t sA = h->stream, sB = ovl ? d.stream2 : h->stream;
+  hipStream_t sA = h->stream, sB = ovl ? d.s2.stream : h->stream;
   StreamGuard guard{h, sA};
-  StreamFork chain{h, sA, sB, d.ev_fork, d.ev_join};
+  StreamFork chain{h, sA, sB, d.s2.fork, d.s2.join};
   const int ne_x = P.h_mid[k] - P.h_ptr[k], ne_u = P.h_ptr[k + 1] - P.h_mid[k];
   int e;
   // ---- W
@@ -1248,9 +1360,7 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
   if (!ovl) {
     // G = F'W (lower tiles of the whole (n+m) x (n+m) block)
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}))) return e;
-    st_add_q(h, d, k, 0, nz, nz, 1, G, ldg);
-    st_add_h(h, d, P.h_ptr[k], ne_x + ne_u, G);
-    if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
+    if ((e = st_add_block(h, d, k, 1, G, ldg))) return e;
   } else {
     if ((e = st_gemm(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nn, nn, np, 1.0, 0.0, 1, 0}))) return e;
     st_add_q(h, d, k, 0, nn, nn, 1, G, ldg);
@@ -1265,8 +1375,7 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
   if ((e = st_carried_rows(h, d, k, sp, sn, !ovl)) || (e = st_eliminate(h, d, k, sp, sn, G, !ovl))) return e;
   h->stream = sA;
   if ((e = chain.join())) return e;
-  // V = Gxx - Y'Rm (lower tiles, mirrored)
-  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+  return st_update_v(h, d, k, sp, G);
 }
 
 // One stage of the backward recursion in the profile form (StagedPlan::pf_stage): the dense sequence on one stream with
@@ -1274,7 +1383,7 @@ static int staged_stage_dense(hqpkkt_t *h, int k) {
 // W = V+ F (tile (tm, tn): the range of panel tn) and the whole lower block G = F'W (the range of panel tm) - and no V
 // formed in the G_xx launch.  The thin products (carried rows, the elimination's) stay full-depth dense products: they
 // read the arena's zeros.  A stage with packed panels (StagedPlan::pk_stage) runs the same launches by the same lists
-// with F_k's panels addressed through StagedDev::pk_tab, and its carried rows by k_pk_carried over the ranges alone.
+// with F_k's panels addressed through StagedDev::Profile::pk_tab, and its carried rows by k_pk_carried over the ranges alone.
 static int staged_stage_profile(hqpkkt_t *h, int k) {
   StagedDev &d = *h->sd;
   const kktdev::StagedPlan &P = d.plan;
@@ -1286,26 +1395,23 @@ static int staged_stage_profile(hqpkkt_t *h, int k) {
   if ((e = st_gemm_profile(h, stg::GemmArgs{sn.V, ldvn, sp.F, ldf, nullptr, 0, W, ldf, np, nz, np, 1.0, 0.0, 0, 0}, k, 1)) ||
       (e = st_gemm_profile(h, stg::GemmArgs{sp.F, ldf, W, ldf, nullptr, 0, G, ldg, nz, nz, np, 1.0, 0.0, 1, 0}, k, 2)))
     return e;
-  st_add_q(h, d, k, 0, nz, nz, 1, G, ldg);
-  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
-  if ((e = st_add_h_wide(h, d, k, G, ldg))) return e;
+  if ((e = st_add_block(h, d, k, 1, G, ldg))) return e;
   if (P.pk_stage(k)) {
     const int ek = P.eq_ptr[k + 1] - P.eq_ptr[k];
-    stg::pk_launch_carried(stg::PkCarried{sn.BT, P.ldb[k + 1], sp.F, d.pk_tab.p + P.pf_ptr[k], d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], np, nz, P.cap[k + 1], 0,
-                                          sp.N + (size_t)ek * P.ldn[k], P.ldn[k], d.pk_part.p},
-                           P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_GEMM_UPD, launch()); });
+    stg::pk_launch_carried(stg::PkCarried{sn.BT, P.ldb[k + 1], sp.F, d.pf.panels(P, k), d.pf.ranges(P, k), np, nz, P.cap[k + 1], 0,
+                                          sp.N + (size_t)ek * P.ldn[k], P.ldn[k], d.pf.pk_part.p},
+                           P.stage_ranges(k), h->stream, [&](auto &&launch) { KLAUNCH(h, KC_ST_GEMM_UPD, launch()); });
   } else if ((e = st_carried_rows(h, d, k, sp, sn, true)))
     return e;
   if ((e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
-  // V = Gxx - Y'Rm (lower tiles, mirrored)
-  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, ldg, sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+  return st_update_v(h, d, k, sp, G);
 }
 
 // the entries of the columns [c0, c0 + ncols) of F_k out of the CSR arrays of A' (staged_sparse.hip.h)
 // (light: the ranges in which the stage's heavy columns are empty, where it has some)
 static stg::SpCols sp_cols(hqpkkt_t *h, StagedDev &d, int k, int c0, int ncols, bool light = false) {
   const kktdev::StagedPlan &P = d.plan;
-  const int *ent = light && P.heavy_count(k) ? d.sp_tcol_light.p : d.sp_tcol.p;
+  const int *ent = light && P.heavy_count(k) ? d.sp.tcol_light.p : d.sp.tcol.p;
   return stg::SpCols{ent + 2 * ((long long)P.nmk[k] + c0), h->td.AT.col.p, h->td.AT.val.p, P.nks[k], ncols};
 }
 // One stage of the backward recursion in the sparse form (StagedPlan::sparse_dyn; Hqp_IpLQDOCP's FormGxxSp,
@@ -1353,12 +1459,11 @@ static int staged_stage_sparse(hqpkkt_t *h, int k) {
     if ((e = st_gemm(h, stg::GemmArgs{D, ldd, Wh, ldd, nullptr, 0, Ghh, ldd, nd, nd, np, 1.0, 0.0, 0, 0}))) return e;
     if (cx > 0 && (e = st_gemm(h, stg::GemmArgs{sn.BT, P.ldb[k + 1], D, ldd, nullptr, 0, Nh, ldd, cx, nd, np, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD))) return e;
     KLAUNCH(h, KC_ST_SPARSE, stg::k_sp_heavy_place<<<dim3((unsigned)((std::max(nz, cx) + 255) / 256), nd), 256, 0, h->stream>>>(stg::SpHeavyPlace{
-                                 nz, nd, cx, d.hv_cols.p + P.hv_ptr[k], d.hv_of.p + P.nmk[k], Gh, ldg, Ghh, ldd, G, ldg, Nh, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
+                                 nz, nd, cx, d.sp.hv_cols.p + P.hv_ptr[k], d.sp.hv_of.p + P.nmk[k], Gh, ldg, Ghh, ldd, G, ldg, Nh, sp.N + (size_t)ek * P.ldn[k], P.ldn[k]}));
   }
-  st_add_q(h, d, k, 0, nz, nz, 0, G, ldg);  // (k_sp_gather writes the block with its mirror image)
-  st_add_h(h, d, P.h_ptr[k], P.h_ptr[k + 1] - P.h_ptr[k], G);
-  if ((e = st_add_h_wide(h, d, k, G, ldg)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
-  return st_gemm(h, stg::GemmArgs{sp.Y, P.ldy[k], sp.Rm, P.ldy[k], G, P.ldg[k], sp.V, P.ldv[k], nn, nn, P.qmax[k], -1.0, 1.0, 1, 1}, KC_ST_GEMM_UPD);
+  // (not lower: k_sp_gather writes the block with its mirror image)
+  if ((e = st_add_block(h, d, k, 0, G, ldg)) || (e = st_eliminate(h, d, k, sp, sn, G, true))) return e;
+  return st_update_v(h, d, k, sp, G);
 }
 
 // Hqp_IpLQDOCP::factor (hqp/Hqp_IpLQDOCP.C:796-862): W^-1 Z, C'(W^-1 Z)C, then the backward
@@ -1388,13 +1493,18 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
     if (P.sharded) st_keep_rows(h, d, K);
   }
   if (P.sharded && K > 0 && (e = staged_gather_f(h, K - 1))) return e;  // (stage k requests stage k - 1's)
-  for (int k = K - 1; k >= 0; k--)
-    if ((e = P.sharded                            ? staged_stage_sharded(h, k)
-             : P.sparse_dyn                       ? staged_stage_sparse(h, k)
-             : P.profile_dyn && P.pf_stage[k]     ? staged_stage_profile(h, k)
-             : d.fused[k]                         ? staged_stage_fused(h, k)
-                                                  : staged_stage_dense(h, k)))
-      return e;
+  for (int k = K - 1; k >= 0; k--) {
+    e = 0;
+    switch (d.prod.seq[k]) {
+      case kktdev::SEQ_SHARDED: e = staged_stage_sharded(h, k); break;
+      case kktdev::SEQ_SPARSE: e = staged_stage_sparse(h, k); break;
+      case kktdev::SEQ_PROFILE: e = staged_stage_profile(h, k); break;
+      case kktdev::SEQ_FUSED: e = staged_stage_fused(h, k); break;
+      case kktdev::SEQ_DENSE: e = staged_stage_dense(h, k, false); break;
+      case kktdev::SEQ_DENSE_CHAIN2: e = staged_stage_dense(h, k, true); break;
+    }
+    if (e) return e;
+  }
   {
     StagePtr s0 = stage_ptr(d, 0);
     if (P.fixed_x0)
@@ -1413,11 +1523,11 @@ static int staged_run_factor(hqpkkt_t *h, const double *z, const double *w) {
       if ((e = st_gemm(h, stg::GemmArgs{xa.K0mat, P.ldq0, xa.K0inv, P.ldq0, nullptr, 0, bs.Ks, bs.ldk, q, q, q, 1.0, 0.0, 0, 0}, KC_ST_GEMM_UPD, true)))
         return e;
       KLAUNCH(h, KC_ST_SMALL, stg::k_x0_check<<<1, 1024, 0, s>>>(xa, env_block_gj_tol()));
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<1024><<<1, 1024, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
+      KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<1024><<<1, 1024, d.lds.init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
                                                                                     d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p,
                                                                                     scr, bs.flags));
     } else
-      KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<256><<<1, 256, d.lds_init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
+      KLAUNCH(h, KC_ST_SMALL, stg::k_st_init_factor<256><<<1, 256, d.lds.init, s>>>(P.nk[0], P.cap[0], s0.V, P.ldv[0], s0.BT, P.ldb[0], s0.dyn,
                                                                                   d.misc.p + P.oK0, d.misc.p + P.oK0m, d.misc.p + P.oK0s, P.ldq0, P.q0max, h->td.flags.p, nullptr, nullptr));
   }
   if (timed) HIPCHK(hipEventRecord(h->evs1, s));
@@ -1441,17 +1551,17 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   double *M = d.misc.p;
   double *S = M + P.oS, *qv = M + P.oQv, *gam = M + P.oGam, *tt = M + P.oTT, *tmp = M + P.oTmp, *gv = M + P.oGv;
   double *xv = M + P.oXV, *xp = M + P.oXP, *dyx = M + P.oDyx;  // (sharded)
-  auto cut0 = [&](int k) { return sh ? P.xcut[(size_t)k * (NR + 1) + RK] : 0; };
-  auto width = [&](int k) { return sh ? P.xcut[(size_t)k * (NR + 1) + RK + 1] - P.xcut[(size_t)k * (NR + 1) + RK] : 0; };
+  auto cut0 = [&](int k) { return sh ? P.strip_first(k) : 0; };
+  auto width = [&](int k) { return sh ? P.strip_width(k) : 0; };
   int e;
   const long long ndx = (long long)P.ndyn + (P.fixed_x0 ? P.nk[0] : 0);
   if (sh) KLAUNCH(h, KC_ST_VEC, stg::k_st_zero<<<nblk(std::max<long long>(ndx, 1)), 256, 0, s>>>(ndx, dyx));
   if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
   // q = C'tz - r1; with wide rows of C (StagedPlan::rows_vec) their share out of the blocks E_k, the walk over the narrow C'
   const bool wide = P.rows_vec();
-  const CsrBuf &CT = wide ? d.CTn : h->td.CT, &C = wide ? d.Cn : h->td.C;
+  const CsrBuf &CT = wide ? d.wr.CTn : h->td.CT, &C = wide ? d.wr.Cn : h->td.C;
   if (wide) st_rows_cols(h, d, h->td.tz.p);
-  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, CT.ptr.p, CT.col.p, CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv, wide ? d.wr_xc.p : nullptr));
+  KLAUNCH(h, KC_VECTOR, stg::k_st_q<<<nblk(n), 256, 0, s>>>(n, CT.ptr.p, CT.col.p, CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, qv, wide ? d.wr.xc.p : nullptr));
   // One GPU: the products with V are not part of the sweeps' chains: V+ f (f: the dynamics' right-hand side) is known before the
   // backward sweep starts, the dynamics rows' multipliers are wanted by nobody before the forward sweep is over - both
   // for many stages per launch (staged_symv_group), which leaves the F products and the control-sized kernels in the
@@ -1460,7 +1570,7 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
   // the launches gained nothing: 35.8 - 37.4 ms per solve against 35.5; what the chains leave idle of HBM they lose again
   // when they share it)
   if (!sh) {
-    for (int gi = (int)d.symv_groups[0].size() - 1; gi >= 0; gi--)
+    for (int gi = (int)d.symv.groups[0].size() - 1; gi >= 0; gi--)
       if ((e = staged_symv_group(h, d, 0, gi, v.r2, nullptr))) return e;
     if ((e = staged_symv_rows(h, d, 0, v.r2, nullptr))) return e;
   }
@@ -1471,12 +1581,13 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       KLAUNCH(h, KC_ST_VEC, stg::k_st_copy_add<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v, gv + P.nks[K - 1], tt));
     else
       KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(nK), 256, 0, s>>>(nK, qv + P.nmk[K], sp.v));
-    if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_gather<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], v.r2, sp.beta));
+    if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_gather<<<nblk(eK), 256, 0, s>>>(eK, d.tab.eq_rows.p + P.eq_ptr[K], v.r2, sp.beta));
   }
   for (int k = K - 1; k >= 0; k--) {
     StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
     const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1];
     const int c0 = cut0(k), wd = width(k), c0n = cut0(k + 1), wdn = width(k + 1);
+    const kktdev::StageSeq seq = d.prod.seq[k];
     if (sh) {
       // tt = v+ + V+ f by rows: the ranks' strips side by side (strip p starts at p xw), gathered
       if (wdn > 0 && (e = st_gemv_rows(h, stg::GemvRows{sn.Vs, P.ldv[k + 1], wdn, np, v.r2 + P.nks[k], sn.v + c0n, nullptr, 0, nullptr, nullptr,
@@ -1486,17 +1597,16 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       // gam = q_k + F' tt: the own state columns and the control columns
       if (wd > 0 && (e = st_gemv_cols(h, d, sp.F, P.ldfl[k], np, wd, xv, qv + P.nmk[k] + c0, 1.0, gam + c0))) return e;
       if (mm > 0 && (e = st_gemv_cols(h, d, sp.F + wd, P.ldfl[k], np, mm, xv, qv + P.nmk[k] + nn, 1.0, gam + nn))) return e;
-    } else if (P.sparse_dyn) {  // gam = q_k + F' tt over the columns' entries
+    } else if (seq == kktdev::SEQ_SPARSE) {  // gam = q_k + F' tt over the columns' entries
       if (nn + mm > 0)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_cols<<<nblk(nn + mm), 256, 0, s>>>(
                                          stg::SpGemvCols{sp_cols(h, d, k, 0, nn + mm, true), tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
       if (const int nd = P.heavy_count(k))  // (the heavy columns: a wavefront each)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_heavy<<<(nd + 3) / 4, 256, 0, s>>>(stg::SpGemvHeavy{
-                                         sp_cols(h, d, k, 0, nn + mm), d.hv_cols.p + P.hv_ptr[k], nd, tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
-    } else if (P.profile_dyn && P.pf_stage[k]) {  // gam = q_k + F' tt over the panels' slab ranges
-      stg::pf_launch_cols(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], tt, qv + P.nmk[k], 1.0, gam, d.pf_part.p,
-                                      P.pk_stage(k) ? d.pk_tab.p + P.pf_ptr[k] : nullptr},
-                          P.pf_rng.data() + 2 * (size_t)P.pf_ptr[k], s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
+                                         sp_cols(h, d, k, 0, nn + mm), d.sp.hv_cols.p + P.hv_ptr[k], nd, tt, qv + P.nmk[k], 1.0, gam, nullptr, nullptr}));
+    } else if (seq == kktdev::SEQ_PROFILE) {  // gam = q_k + F' tt over the panels' slab ranges
+      stg::pf_launch_cols(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf.ranges(P, k), tt, qv + P.nmk[k], 1.0, gam, d.pf.part.p, d.pf.panels(P, k)},
+                          P.stage_ranges(k), s, [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
     } else if ((e = st_gemv_cols(h, d, sp.F, P.ldf[k], np, nn + mm, tt, qv + P.nmk[k], 1.0, gam)))  // gam = q_k + F' tt with tt = v+ + V+ f (from the stage behind)
       return e;
     st_bwd_small(h, d, k, sp, sn, v.r2, gam);
@@ -1517,17 +1627,17 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     StagePtr sp = stage_ptr(d, k), sn = stage_ptr(d, k + 1);
     const int nn = P.nk[k], mm = P.mk[k], np = P.nk[k + 1];
     const int c0 = cut0(k), wd = width(k), c0n = cut0(k + 1), wdn = width(k + 1);
+    const kktdev::StageSeq seq = d.prod.seq[k];
     double *xk = S + P.nmk[k];
     st_fwd_small(h, d, k, sp, sn, v.dy);
-    if (P.sparse_dyn) {  // x+ = F s + f over the rows' entries
+    if (seq == kktdev::SEQ_SPARSE) {  // x+ = F s + f over the rows' entries
       if (np > 0)
         KLAUNCH(h, KC_ST_SPARSE_VEC, stg::k_sp_gemv_rows<<<(np + 15) / 16, 256, 0, s>>>(stg::SpGemvRows{
-                                         d.sp_arow.p + 2 * (long long)P.nks[k], h->td.A.col.p, h->td.A.val.p, P.nmk[k], np, xk, v.r2 + P.nks[k], S + P.nmk[k + 1], 1.0}));
+                                         d.sp.arow.p + 2 * (long long)P.nks[k], h->td.A.col.p, h->td.A.val.p, P.nmk[k], np, xk, v.r2 + P.nks[k], S + P.nmk[k + 1], 1.0}));
       continue;
     }
-    if (P.profile_dyn && P.pf_stage[k]) {  // x+ = F s + f over the panels whose range holds the row
-      stg::pf_launch_rows(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf_rng.p + 2 * (size_t)P.pf_ptr[k], xk, v.r2 + P.nks[k], 1.0, S + P.nmk[k + 1], nullptr,
-                                      P.pk_stage(k) ? d.pk_tab.p + P.pf_ptr[k] : nullptr}, s,
+    if (seq == kktdev::SEQ_PROFILE) {  // x+ = F s + f over the panels whose range holds the row
+      stg::pf_launch_rows(stg::PfGemv{sp.F, P.ldf[k], np, nn + mm, d.pf.ranges(P, k), xk, v.r2 + P.nks[k], 1.0, S + P.nmk[k + 1], nullptr, d.pf.panels(P, k)}, s,
                           [&](auto &&launch) { KLAUNCH(h, KC_ST_VEC, launch()); });
       continue;
     }
@@ -1550,13 +1660,13 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
       return e;
   }
   if (!sh) {
-    for (int gi = 0; gi < (int)d.symv_groups[1].size(); gi++)
+    for (int gi = 0; gi < (int)d.symv.groups[1].size(); gi++)
       if ((e = staged_symv_group(h, d, 1, gi, nullptr, v.dy))) return e;
     if ((e = staged_symv_rows(h, d, 1, nullptr, v.dy))) return e;
   }
   StagePtr sK = stage_ptr(d, K), s0 = stage_ptr(d, 0);
   const int eK = P.eq_ptr[K + 1] - P.eq_ptr[K], n0 = P.nk[0];
-  if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_last<<<nblk(eK), 256, 0, s>>>(eK, d.eq_rows.p + P.eq_ptr[K], sK.eta, v.dy));
+  if (eK) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_last<<<nblk(eK), 256, 0, s>>>(eK, d.tab.eq_rows.p + P.eq_ptr[K], sK.eta, v.dy));
   if (sh) {
     if (P.fixed_x0 && width(0) > 0 &&
         (e = st_gemv_rows(h, stg::GemvRows{s0.Vs, P.ldv[0], width(0), n0, S, s0.v + cut0(0), nullptr, 0, nullptr, nullptr, dyx + P.ndyn + cut0(0), 1.0})))
@@ -1565,7 +1675,7 @@ static int staged_run_step(hqpkkt_t *h, const Vecs &v) {
     if (P.ndyn > 0) KLAUNCH(h, KC_ST_VEC, stg::k_st_copy<<<nblk(P.ndyn), 256, 0, s>>>(P.ndyn, dyx, v.dy));
   } else if (P.fixed_x0 && (e = st_symv(h, d, stg::GemvRows{s0.V, P.ldv[0], n0, n0, S, s0.v, nullptr, 0, nullptr, nullptr, tmp, 1.0})))
     return e;
-  if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.fix_rows.p, d.fix_src.p, h->td.vals.p, sh ? dyx + P.ndyn : tmp, v.dy));
+  if (P.fixed_x0) KLAUNCH(h, KC_ST_VEC, stg::k_st_y_fixed<<<nblk(n0), 256, 0, s>>>(n0, d.tab.fix_rows.p, d.tab.fix_src.p, h->td.vals.p, sh ? dyx + P.ndyn : tmp, v.dy));
   KLAUNCH(h, KC_VECTOR, stg::k_st_negate<<<nblk(n), 256, 0, s>>>(n, S, v.dx));
   if (m > 0)
     KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, C.ptr.p, C.col.p, C.src.p, h->td.vals.p, v.dx, h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));

@@ -58,26 +58,27 @@ int stages_from_staircase(int n, int rows, const int *row_len, const int *last_c
   return 0;
 }
 
-int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const int *Ap, const int *Ai,
+int StagedPlan::run(const StagedRequest &rq, int n_, int me_, int m_, const int *Qp, const int *Qi, const int *Ap, const int *Ai,
                     const int *Cp, const int *Ci, const int *ATp, const int *ATi) {
   n = n_, m = m_;
-  sparse_dyn = want_sparse;
+  dense_dyn = rq.dense_dyn, shard_rank = rq.shard_rank, shard_count = rq.shard_count, sharded = rq.sharded;
+  sparse_dyn = rq.want_sparse;
   if (sparse_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
-  profile_dyn = want_profile && !want_sparse;
+  profile_dyn = rq.want_profile && !rq.want_sparse;
   if (profile_dyn && (dense_dyn || sharded || !ATp || (me_ > 0 && Ap[me_] > 0 && !ATi))) return 1;
   nq = n ? Qp[n] : 0, nc = m ? Cp[m] : 0;
-  hess_dense = want_hess_dense;
-  hess_packed = hess_dense && want_hess_packed;
+  hess_dense = rq.want_hess_dense;
+  hess_packed = hess_dense && rq.want_hess_packed;
   const int arows = me_;  // rows of the A that was handed over
   na = arows ? Ap[arows] : 0;
   nk.clear(), mk.clear(), nmk.clear(), nks.clear();
 
   // ------------------------------------------------------------------ stage sizes
-  if (!given_nx.empty()) {
-    K = (int)given_nx.size() - 1;
-    if (K < 1 || (int)given_nu.size() != K) return 6;
-    nk = given_nx;
-    mk = given_nu;
+  if (!rq.given_nx.empty()) {
+    K = (int)rq.given_nx.size() - 1;
+    if (K < 1 || (int)rq.given_nu.size() != K) return 6;
+    nk = rq.given_nx;
+    mk = rq.given_nu;
     nmk.assign(K + 1, 0);
     for (int k = 0; k < K; k++) nmk[k + 1] = nmk[k] + nk[k] + mk[k];
     if (nmk[K] + nk[K] != n) return 6;
@@ -185,7 +186,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
       }
     }
     // heavy columns: by the length of the column's range, per stage
-    heavy_min = want_heavy < 0 ? HEAVY_DEFAULT : want_heavy;
+    heavy_min = rq.want_heavy < 0 ? HEAVY_DEFAULT : rq.want_heavy;
     hv_ptr.assign(K + 1, 0), hv_nnz.assign(K, 0);
     sp_tcol_light = sp_tcol;
     for (int k = 0; k < K; k++) {
@@ -226,7 +227,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   }
 
   // ------------------------------------------------------------------ wide rows of C
-  rows_min = sharded ? 0 : want_rows < 0 ? ROWS_DEFAULT : want_rows;
+  rows_min = sharded ? 0 : rq.want_rows < 0 ? ROWS_DEFAULT : rq.want_rows;
   wr_ptr.clear(), wr_rows.clear(), ldE.clear(), oE.clear(), c_dst.clear(), oSr = 0;
   if (rows_min > 0) {
     std::vector<std::vector<int>> wide(K + 1);
@@ -290,7 +291,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   ldf.assign(K + 1, 8), ldv.assign(K + 1, 8), ldy.assign(K + 1, 8), ldn.assign(K + 1, 8);
   ldb.assign(K + 1, 8), ldq.assign(K + 1, 8), ldt.assign(K + 1, 8), ldg.assign(K + 1, 8);
   oF.assign(K + 1, 0), oV.assign(K + 1, 0);
-  packed = profile_dyn && want_packed;
+  packed = profile_dyn && rq.want_packed;
   pk_off.assign(packed ? pf_rng.size() / 2 : 0, -1), pk_ld.assign(pk_off.size(), 0);
   oY.assign(K + 1, 0), oR.assign(K + 1, 0), oK.assign(K + 1, 0), oKm.assign(K + 1, 0), oN.assign(K + 1, 0);
   oBT.assign(K + 1, 0), oT.assign(K + 1, 0), oVec.assign(K + 1, 0);
@@ -300,7 +301,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   long long whmax = 0, thmax = 0, ghmax = 0, ghhmax = 0, nhmax = 0;
   int nzmax = 0, nmax = 0;
   for (int k = 0; k <= K; k++) {
-    const int nz = k < K ? nk[k] + mk[k] : nk[k];
+    const int nz = hess_order(k);
     nzmax = std::max(nzmax, nz), nmax = std::max(nmax, nk[k]);
     ldv[k] = up8(nk[k]);
     oV[k] = vo, vo += up16((long long)nk[k] * ldv[k]);
@@ -377,7 +378,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
   if (!wr_rows.empty()) {  // (the blocks E_k behind every dynamics block; the work block S for the largest of them)
     long long smax = 0;
     for (int k = 0; k <= K; k++) {
-      ldE[k] = up8(std::max(k < K ? nk[k] + mk[k] : nk[k], 1));
+      ldE[k] = up8(std::max(hess_order(k), 1));
       oE[k] = fo, fo += (long long)wide_count(k) * ldE[k];
       smax = std::max(smax, (long long)wide_count(k) * ldE[k]);
     }
@@ -536,7 +537,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
           else if (!sharded)
             a_dst[p] = oF[k] + (long long)li * ldf[k] + lc;
           else {  // the local block: own state columns, then the control columns
-            const int c0 = xcut[(size_t)k * (shard_count + 1) + shard_rank], c1 = xcut[(size_t)k * (shard_count + 1) + shard_rank + 1];
+            const int c0 = strip_first(k), c1 = c0 + strip_width(k);
             if (lc >= nk[k])
               a_dst[p] = oFl[k] + (long long)li * ldfl[k] + (c1 - c0) + (lc - nk[k]);
             else if (lc >= c0 && lc < c1)
@@ -645,7 +646,7 @@ int StagedPlan::run(int n_, int me_, int m_, const int *Qp, const int *Qi, const
     flops_factor += 2 * q * q * nn + q * nn * nn;         // Rm, V update (lower half)
   }
   for (int k = 0; k <= K; k++) {  // the wide rows' products S'S, lower half
-    const long long nz = k < K ? nk[k] + mk[k] : nk[k];
+    const long long nz = hess_order(k);
     flops_factor += wide_count(k) * nz * nz;
   }
   return 0;

@@ -21,8 +21,28 @@ inline long long gj_lds_bytes(long long q) {
 int stages_from_staircase(int n, int rows, const int *row_len, const int *last_col, const int *prev_col,
                           std::vector<int> &states, std::vector<int> &controls, std::vector<int> &first_col, int &dyn_rows);
 
+// What the caller asks of the next analysis (the setters of the C ABI write it, the handle keeps it from one analysis to
+// the next) with the other inputs of StagedPlan::run that are not the pattern.  The plan holds only what came of it
+struct StagedRequest {
+  bool want_sparse = false, want_profile = false;  // hqpkkt_set_dynamics_form: the sparse / the profile form of the stage products
+  int want_heavy = 0;                              // hqpkkt_set_dense_columns (-1: StagedPlan::HEAVY_DEFAULT; read by the sparse form alone)
+  int want_rows = 0;                               // hqpkkt_set_dense_rows (-1: StagedPlan::ROWS_DEFAULT; a sharded handle keeps its term lists)
+  bool want_packed = false;                        // hqpkkt_set_packed_panels (read by the profile form alone)
+  bool want_hess_dense = false, want_hess_packed = false;  // hqpkkt_set_hessian_form, hqpkkt_set_packed_hessians (the second with the first alone)
+  std::vector<int> given_nx, given_nu;             // explicit stage sizes (hqpkkt_set_stages): nx[K+1], nu[K]; empty: detect from A
+  bool dense_dyn = false;                          // dynamics handed over as dense blocks: their rows of A are empty
+  int shard_rank = 0, shard_count = 1;             // one system over several ranks (hqpkkt_set_shard)
+  bool sharded = false;                            // several ranks, or one rank with a transport set (tests the exchange path)
+};
+
+// The kernel sequence stage k < K of the factorisation runs, one function each in staged_host.hip.h; the solve's sweeps
+// branch on it too.  StagedPlan::stage_seq answers with one of the first four, which the plan alone decides; the upload
+// tells the dense stages apart by the launches' schedules and the stage's width (StagedDev::Product::seq)
+enum StageSeq : char { SEQ_SHARDED, SEQ_SPARSE, SEQ_PROFILE, SEQ_DENSE, SEQ_FUSED, SEQ_DENSE_CHAIN2 };
+
 struct StagedPlan {
   int n = 0, me = 0, m = 0, K = 0;
+  StageSeq stage_seq(int k) const { return sharded ? SEQ_SHARDED : sparse_dyn ? SEQ_SPARSE : profile_dyn && pf_stage[k] ? SEQ_PROFILE : SEQ_DENSE; }
   int nq = 0, na = 0, nc = 0;
   std::vector<int> nk, mk, nmk;  // states (K+1), controls (K), first column of a stage (K+1)
   std::vector<int> nks;          // first dynamics row of stage k (K+1 entries, nks[K] = ndyn)
@@ -30,14 +50,14 @@ struct StagedPlan {
   std::vector<int> eq_ptr, eq_rows;  // own equality rows per stage (QP row indices), K+2 / total
   bool fixed_x0 = false;
   std::vector<int> fix_rows, fix_src;  // per x_0 component: its row of A and the index of its value in vals
-  bool dense_dyn = false;  // dynamics handed over as dense blocks: their rows of A are empty
+  bool dense_dyn = false;  // dynamics handed over as dense blocks: their rows of A are empty (StagedRequest::dense_dyn)
   // The sparse form of the stage products (hqpkkt_set_dynamics_form, Hqp_IpLQDOCP's mat_a_sparse,
   // hqp/Hqp_IpLQDOCP.C:1119-1273): F_k stays the row lists of A and A' - no dense block, f_elems = 0.  Per dynamics row
   // i of A the entries sp_arow[2 i] .. sp_arow[2 i + 1] of A's CSR arrays (the row without its trailing -1); per column
   // c < nmk[K] the entries sp_tcol[2 c] .. sp_tcol[2 c + 1] of the CSR arrays of A' that lie in the dynamics rows of c's
   // stage (a row of A' also holds the -1 of the stage before and the other equality rows: skipped, as FormGxxSp skips
-  // its first entry).  The values stay in `vals` behind the CSR blocks' src.  want_sparse: the form the next analysis takes
-  bool want_sparse = false, sparse_dyn = false;
+  // its first entry).  The values stay in `vals` behind the CSR blocks' src.
+  bool sparse_dyn = false;
   std::vector<int> sp_arow, sp_tcol;
   std::vector<int> sp_nnz;  // stored entries of F_k (K)
   std::vector<int> hv_nnz;  // ... those of them in heavy columns (K)
@@ -48,10 +68,10 @@ struct StagedPlan {
   // sp_tcol with the heavy columns' ranges empty - what the column walks take where a stage has heavy columns.  The work
   // blocks of the stage in the misc arena, sized for the largest stage: oWh = V+ D (n+ x ldd), oTh its transpose (nd rows of
   // up8(n+)), oGh = the heavy rows of G (nd x ldg), oGhh = D'V+D (nd x ldd), oNh = B+ D (carried rows x ldd).
-  // want_heavy: what the next analysis takes (-1: HEAVY_DEFAULT, the smallest count of the sweep from which taking
-  // sixteen columns out of the walks won at 2000 and at 5000 states, profiles/r12_dense_columns.txt)
+  // HEAVY_DEFAULT: the smallest count of the sweep from which taking sixteen columns out of the walks won at 2000 and at
+  // 5000 states, profiles/r12_dense_columns.txt
   static const int HEAVY_DEFAULT = 32;
-  int want_heavy = 0, heavy_min = 0;
+  int heavy_min = 0;
   std::vector<int> hv_ptr, hv_cols, sp_tcol_light, ldd;
   std::vector<long long> oD;
   long long oWh = 0, oTh = 0, oGh = 0, oGhh = 0, oNh = 0;
@@ -63,8 +83,8 @@ struct StagedPlan {
   // without entries.  A property of the pattern, read off the CSR arrays of A'.  The large products of a stage and the
   // solve's two products with F_k then take only these slabs (staged_stage_profile).  pf_stage[k]: the stage runs that
   // sequence - at least two panels and a range shorter than all slabs of n_{k+1}; every other stage runs the dense
-  // sequence.  want_profile: the form the next analysis takes
-  bool want_profile = false, profile_dyn = false;
+  // sequence.
+  bool profile_dyn = false;
   std::vector<int> pf_ptr, pf_rng;
   std::vector<char> pf_stage;
   int panels(int k) const { return pf_ptr.empty() ? 0 : pf_ptr[k + 1] - pf_ptr[k]; }
@@ -73,8 +93,8 @@ struct StagedPlan {
   // row-major with leading dimension pk_ld = 128 (the last panel: up8 of its columns); an empty panel takes no room, the
   // stage's total is rounded up to 16 doubles.  pk_off[pf_ptr[k] + p]: the panel's first element, in doubles from oF[k];
   // -1 (pk_ld 0) for the panels of a stage that keeps its dense block.  Never larger than the dense block: with exact
-  // row counts sum_p rows_p ld_p <= n_{k+1} up8(n_k + m_k).  want_packed: what the next analysis takes
-  bool want_packed = false, packed = false;
+  // row counts sum_p rows_p ld_p <= n_{k+1} up8(n_k + m_k).
+  bool packed = false;
   std::vector<long long> pk_off;
   std::vector<int> pk_ld;
   bool pk_stage(int k) const { return packed && pf_stage[k]; }
@@ -98,10 +118,10 @@ struct StagedPlan {
   // columns; c_kept / c_cut: stored entries of C in cn / taken out.  Built by narrow_copies() behind run(), empty without
   // wide rows.  The interior-point loops' own right-hand-side kernels keep the full arrays.
   // h_kept[k] / h_cut[k]: H terms of stage k in the lists / the terms its wide rows would have added.
-  // want_rows: what the next analysis takes (-1: ROWS_DEFAULT; 0 there: no threshold has been measured and the setter
-  // refuses -1); a sharded handle keeps its term lists (rows_min = 0)
+  // ROWS_DEFAULT 0: no threshold has been measured and the setter refuses -1; a sharded handle keeps its term lists
+  // (rows_min = 0)
   static const int ROWS_DEFAULT = 0;
-  int want_rows = 0, rows_min = 0;
+  int rows_min = 0;
   std::vector<int> wr_ptr, wr_rows, ldE;
   std::vector<long long> oE, c_dst, h_kept, h_cut;
   long long oSr = 0;
@@ -118,8 +138,8 @@ struct StagedPlan {
   // exactly symmetric - as rows of ldQ[k] = up8(order) doubles at oQ[k] in an arena of its own (q_elems doubles, blocks back
   // to back: a row is 64 bytes or a multiple); Q's terms are not in the H lists.  q_dst: CSR hand-over - per stored entry p
   // of Q its two places in the arena (2 p: row i, column j; 2 p + 1: the image, -1 on the diagonal; both -1 for an entry
-  // with col < row, which nobody reads).  want_hess_dense: what the next analysis takes
-  bool want_hess_dense = false, hess_dense = false;
+  // with col < row, which nobody reads).
+  bool hess_dense = false;
   std::vector<int> ldQ;
   std::vector<long long> oQ, q_dst;
   long long q_elems = 0;
@@ -131,14 +151,14 @@ struct StagedPlan {
   // q_dst then holds the packed places (the image: inside a diagonal tile alone).  oQs[k]: the stage's hess_slots(nt) HESS_T
   // doubles of the product's scratch (qs_elems in all) - per row tile r one slot per HESS_CHUNK tiles of its own row and one
   // per tile (a, r) below it, a little over nt^2 / 2 slots (staged_hess_packed.hip.h); q_stage_elems: the staging block of the dense hand-over from host
-  // memory, order x up8(order) of the largest packed stage.  want_hess_packed: what the next analysis takes
+  // memory, order x up8(order) of the largest packed stage.
   static const int HESS_T = 128, HESS_COPY_ROWS = 64, HESS_CHUNK = 8;
   static long long hess_slots(long long nt) {
     long long s = 0;
     for (long long r = 0; r < nt; r++) s += (r + HESS_CHUNK) / HESS_CHUNK + nt - 1 - r;
     return s;
   }
-  bool want_hess_packed = false, hess_packed = false;
+  bool hess_packed = false;
   std::vector<char> q_packed;
   std::vector<long long> oQs;
   long long qs_elems = 0, q_stage_elems = 0;
@@ -249,13 +269,16 @@ struct StagedPlan {
   std::vector<int> gtile;         // this rank's tiles of its blocks' products: (tile row in the strip) << 16 | global tile column
   std::vector<int> gtile_ptr;     // per stage
 
-  // explicit stage sizes (hqpkkt_set_stages): K, nx[K+1], nu[K]; empty: detect from A
-  std::vector<int> given_nx, given_nu;
+  // the entries of xcut that every sharded step needs: this rank's first state column of stage k and its strip's width
+  int strip_first(int k) const { return xcut[(size_t)k * (shard_count + 1) + shard_rank]; }
+  int strip_width(int k) const { return xcut[(size_t)k * (shard_count + 1) + shard_rank + 1] - strip_first(k); }
+  // the profile form's (lo, hi) k-slab pairs of stage k's panels
+  const int *stage_ranges(int k) const { return pf_rng.data() + 2 * (size_t)pf_ptr[k]; }
 
   // returns 0, or a HQPKKT_E_* code: 6 the pattern is not a staircase / rows leave their stage,
   // 1 a stage exceeds what the one-workgroup kernels hold, or the H term lists would hold more than 2^31 - 1 terms
   // (ATp, ATi: the CSR arrays of A' as Analysis::setup_blocks builds them, rows ascending; read by the sparse form alone)
-  int run(int n, int me, int m, const int *Qp, const int *Qi, const int *Ap, const int *Ai, const int *Cp,
+  int run(const StagedRequest &rq, int n, int me, int m, const int *Qp, const int *Qi, const int *Ap, const int *Ai, const int *Cp,
           const int *Ci, const int *ATp = nullptr, const int *ATi = nullptr);
 };
 

@@ -101,9 +101,10 @@ int main() {
                         Case{12, 130, 16, 0, 120, true}}) {
     docp(c.K, c.nx, c.nu, c.path, c.fin, c.fixed0, Q, A, C, n, me, m);
     for (int shards : {1, 2, 3}) {
+      kktdev::StagedRequest rq;
+      rq.shard_count = shards, rq.shard_rank = shards - 1, rq.sharded = shards > 1;
       kktdev::StagedPlan P;
-      P.shard_count = shards, P.shard_rank = shards - 1, P.sharded = shards > 1;
-      const int e = P.run(n, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data());
+      const int e = P.run(rq, n, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data());
       if (shards > 1 && (c.nx & 1)) {  // (a sharded system needs an even number of states per stage)
         if (e != 1) return 40;
         continue;
@@ -112,22 +113,23 @@ int main() {
       checks++;
     }
     // explicit stage sizes + dense hand-over: the dynamics rows are empty
+    kktdev::StagedRequest dq;
+    dq.given_nx.assign(c.K + 1, c.nx), dq.given_nu.assign(c.K, c.nu), dq.dense_dyn = true;
     kktdev::StagedPlan D;
-    D.given_nx.assign(c.K + 1, c.nx), D.given_nu.assign(c.K, c.nu), D.dense_dyn = true;
     std::vector<int> Ap2(me + 1, 0), Ai2;
     const int ndyn = c.K * c.nx;
     for (int r = ndyn; r < me; r++) {
       for (int p = A.p[r]; p < A.p[r + 1]; p++) Ai2.push_back(A.i[p]);
       Ap2[r + 1] = (int)Ai2.size();
     }
-    if (D.run(n, me, m, Q.p.data(), Q.i.data(), Ap2.data(), Ai2.data(), C.p.data(), C.i.data())) return 50;
+    if (D.run(dq, n, me, m, Q.p.data(), Q.i.data(), Ap2.data(), Ai2.data(), C.p.data(), C.i.data())) return 50;
     checks++;
   }
   // not a staircase
   banded(200, 6, Q, A, C, me, m);
   {
     kktdev::StagedPlan P;
-    if (P.run(200, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data()) != 6) return 60;
+    if (P.run(kktdev::StagedRequest(), 200, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data()) != 6) return 60;
     checks++;
   }
   printf("sanitize_host ok: %d structures analysed\n", checks);

@@ -19,6 +19,7 @@ LOC_HOST, LOC_DEVICE = 0, 1
 DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
 HESS_CSR, HESS_DENSE = 0, 1
 HQPKKT_HESS_UPDATE_RANK = 4
+HQPKKT_BFGS_REPORT = 8
 
 # every symbol include/hqpkkt.h declares
 SYMBOLS = [
@@ -39,6 +40,7 @@ SYMBOLS = [
     "hqpkkt_set_hessian_form", "hqpkkt_set_stage_hessian", "hqpkkt_debug_stage_hessian", "hqpkkt_debug_hess_symv",
     "hqpkkt_set_packed_hessians", "hqpkkt_debug_hess_symv_timed",
     "hqpkkt_update_stage_hessians", "hqpkkt_hessian_product",
+    "hqpkkt_bfgs_update_stage_hessians", "hqpkkt_bfgs_report",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
@@ -62,6 +64,10 @@ class Opts(C.Structure):
 
 class HessUpdate(C.Structure):  # hqpkkt_hess_update
     _fields_ = [("r", C.c_int), ("U", C.POINTER(C.c_void_p)), ("coef", C.c_void_p), ("beta", C.c_void_p), ("diag", C.c_void_p)]
+
+
+class BfgsUpdate(C.Structure):  # hqpkkt_bfgs_update
+    _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("alpha", C.c_double), ("v", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -217,6 +223,8 @@ def lib():
     L.hqpkkt_debug_hess_symv_timed.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.hqpkkt_update_stage_hessians.argtypes = [vp, C.POINTER(HessUpdate)]
     L.hqpkkt_hessian_product.argtypes = [vp, vp, vp]
+    L.hqpkkt_bfgs_update_stage_hessians.argtypes = [vp, C.POINTER(BfgsUpdate)]
+    L.hqpkkt_bfgs_report.argtypes = [vp, vp]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

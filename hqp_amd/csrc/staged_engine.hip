@@ -258,6 +258,29 @@ static int staged_staging_used(hqpkkt_t *h, const double *src) {
     }
   return 0;
 }
+// the per-stage descriptors of an update launch (k_hu_update) to the device: through the pinned words, in the handle's
+// stream; buffers and event are made by the first call
+static int staged_hu_descriptors(hqpkkt_t *h, StagedDev &d, const std::vector<stg::HuDesc> &hd) {
+  int e;
+  if (!d.hess.hu_desc.p) {
+    if ((e = d.hess.hu_desc.alloc(hd.size()))) return e;
+    HIPCHK(d.hess.hu_hdesc.alloc(hd.size(), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&d.hess.hu_ev.h, hipEventDisableTiming));
+  } else
+    HIPCHK(hipEventSynchronize(d.hess.hu_ev));  // (the copy of the last call's descriptors out of the pinned words)
+  std::copy(hd.begin(), hd.end(), d.hess.hu_hdesc.p);
+  HIPCHK(hipMemcpyAsync(d.hess.hu_desc.p, d.hess.hu_hdesc.p, sizeof(stg::HuDesc) * hd.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipEventRecord(d.hess.hu_ev, h->stream));
+  return 0;
+}
+// the damping factor of the BFGS update as hessian_update.bfgs_terms forms it, operation by operation (no contraction)
+static double bfgs_gamma_eff(double gamma, double alpha) {
+#pragma clang fp contract(off)
+  if (gamma >= 0.0) return gamma;
+  const double g = -gamma, omg = 1.0 + gamma, oma = 1.0 - alpha;
+  const double t = omg * oma;
+  return g + t;
+}
 
 extern "C" {
 
@@ -608,15 +631,7 @@ int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u) {
           V.diag = d.hess.hu_vec.p + stg::HU_RANK * n;
         }
       }
-      if (!d.hess.hu_desc.p) {
-        if ((e = d.hess.hu_desc.alloc((size_t)K1))) return e;
-        HIPCHK(d.hess.hu_hdesc.alloc((size_t)K1, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&d.hess.hu_ev.h, hipEventDisableTiming));
-      } else
-        HIPCHK(hipEventSynchronize(d.hess.hu_ev));  // (the copy of the last call's descriptors out of the pinned words)
-      std::copy(hd.begin(), hd.end(), d.hess.hu_hdesc.p);
-      HIPCHK(hipMemcpyAsync(d.hess.hu_desc.p, d.hess.hu_hdesc.p, sizeof(stg::HuDesc) * K1, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipEventRecord(d.hess.hu_ev, h->stream));
+      if ((e = staged_hu_descriptors(h, d, hd))) return e;
       KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
       HIPCHK(hipGetLastError());
       if (h->opts.loc != HQPKKT_LOC_DEVICE) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vectors are free again)
@@ -625,6 +640,72 @@ int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u) {
     for (int k = 0; k < K1; k++)
       if (hd[k].mode == 0) d.hess.set[k] = 1;  // (beta = 0: the block has been made here)
     h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_bfgs_update_stage_hessians(hqpkkt_t *h, const hqpkkt_bfgs_update *b) {
+  return guarded([&]() -> int {
+    if (!h || !b || !b->s || !b->y) return HQPKKT_E_NULL;
+    static_assert(stg::HB_REPORT == HQPKKT_BFGS_REPORT, "the kernel writes the report's words");
+    if (!std::isfinite(b->gamma) || (b->gamma < 0.0 && !std::isfinite(b->alpha))) return HQPKKT_E_RANGE;
+    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    const int K1 = P.K + 1;
+    // the base descriptors of the update launch: beta = 1, every stage as if touched - k_hb_terms writes the coefficients
+    // and takes the stages it leaves alone out (units = 0); every block is kept, so every block must have arrived
+    std::vector<stg::HuDesc> hd(K1);
+    int units_max = 0;
+    for (int k = 0; k < K1; k++) {
+      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
+      const bool packed = P.stage_packed(k);
+      if (nz > 0 && ((int)d.hess.set.size() != K1 || !d.hess.set[k])) return HQPKKT_E_INTERN;
+      hd[k] = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, packed ? (int)P.hess_tiles(nz) : nt * nt, 1, 0, 1.0, {0.0, 0.0, 0.0, 0.0}};
+      units_max = std::max(units_max, hd[k].units);
+    }
+    const double gamma_eff = bfgs_gamma_eff(b->gamma, b->alpha);
+    int e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    const size_t n = (size_t)P.n;
+    const bool host = h->opts.loc != HQPKKT_LOC_DEVICE;
+    if (d.hess.hb_vec.count < (host ? 4 : 2) * n + 1 && (e = d.hess.hb_vec.alloc((host ? 4 : 2) * n + 1))) return e;
+    if (!d.hess.hb_rep.p && (e = d.hess.hb_rep.alloc((size_t)K1 * stg::HB_REPORT))) return e;
+    double *Qs = d.hess.hb_vec.p, *v = b->v && !host ? b->v : d.hess.hb_vec.p + n;
+    const double *s = b->s, *y = b->y;
+    if (host) {  // a host caller's vectors through the handle's own buffer
+      HIPCHK(hipMemcpyAsync(d.hess.hb_vec.p + 2 * n, b->s, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(d.hess.hb_vec.p + 3 * n, b->y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+      s = d.hess.hb_vec.p + 2 * n, y = d.hess.hb_vec.p + 3 * n;
+    }
+    if ((e = staged_hu_descriptors(h, d, hd))) return e;
+    staged_hess_symv(h, d, s, Qs);
+    KLAUNCH(h, KC_VECTOR, stg::k_hb_terms<<<(unsigned)K1, 256, 0, h->stream>>>(d.hess.hu_desc.p, s, y, Qs, v, gamma_eff, d.hess.hb_rep.p));
+    if (units_max > 0) {
+      stg::HuVecs V{};
+      V.r = 2, V.u[0] = v, V.u[1] = Qs;
+      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
+    }
+    HIPCHK(hipGetLastError());
+    d.hess.hb_done = true;
+    h->factored = false;
+    if (host) {
+      if (b->v) HIPCHK(hipMemcpyAsync(b->v, v, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vectors are free again, v is complete)
+    }
+    return 0;
+  });
+}
+
+int hqpkkt_bfgs_report(hqpkkt_t *h, double *out) {
+  return guarded([&]() -> int {
+    if (!h || !out) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->hess.hb_done) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    HIPCHK(hipSetDevice(h->opts.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, d.hess.hb_rep.p, sizeof(double) * d.hess.hb_rep.count, hipMemcpyDeviceToHost));
     return 0;
   });
 }

@@ -77,7 +77,10 @@ struct StagedDev {
   // hqpkkt_debug_hess_symv (n); stage, the staging block of a packed stage's dense hand-over from host memory (reused in
   // stream order); of the update in place (hqpkkt_update_stage_hessians) the per-stage descriptors of the launch, written
   // to pinned memory and copied from there in the handle's stream (hu_ev: that copy is over, the pinned words may be
-  // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n)
+  // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n); of the BFGS update on the
+  // device (hqpkkt_bfgs_update_stage_hessians) Q s and v, behind them the copies of a host caller's s and y (hb_vec: 2 n
+  // or 4 n - never hess.y, which the residual reads), the report words of k_hb_terms (8 per stage), and whether an
+  // update has written them since the analysis
   struct Hessians {
     DBuf<double> Q, y;
     DBuf<long long> q_dst;
@@ -91,6 +94,8 @@ struct StagedDev {
     DBuf<stg::HuDesc> hu_desc;
     EventOwner hu_ev;
     DBuf<double> hu_vec;
+    DBuf<double> hb_vec, hb_rep;
+    bool hb_done = false;
   } hess;
   // The sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A' ...
   // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per stage, and per column of A its

@@ -14,6 +14,9 @@ variables, the reference's damped BFGS update (Hqp_HL_BFGS::update_b_Q) is
 
 The eigenvalue control that the reference can run after it (an eigenvalue decomposition per block, then a shift of the
 diagonal) is not built; its effect, a diagonal shift, is ``update_stage_hessians(..., diag=shift)`` with beta = 1.
+
+``IpLQDOCP.bfgs_update_device`` (hqpkkt_bfgs_update_stage_hessians) forms the same terms on the device; ``bfgs_replay`` is its
+numpy model, operation by operation from the sums the device reports.
 """
 from __future__ import annotations
 
@@ -43,3 +46,33 @@ def bfgs_terms(s, y, Qs, offsets, gamma=0.1, alpha=1.0):
         if sv != 0.0 and sQs != 0.0 and np.isfinite(sv) and np.isfinite(sQs):
             coef[k] = 1.0 / sv, -1.0 / sQs
     return [v, Qs], coef
+
+
+def bfgs_replay(report, s, y, Qs, offsets):
+    """(v, coef) of ``IpLQDOCP.bfgs_update_device`` (hqpkkt_bfgs_update_stage_hessians) repeated in numpy from the sums the
+    device REPORTED: ``report`` is ``IpLQDOCP.bfgs_report()``, (blocks, 8), of which sy (0), sQs (1), gamma_eff (2) and sv
+    (4) are read.  One numpy operation per rounded operation of k_hb_terms (staged_hess_bfgs.hip.h): the test
+    sy < fl(gamma_eff sQs), theta = fl(fl((1 - gamma_eff) sQs) / fl(sQs - sy)), omt = fl(1 - theta),
+    v_i = fl(fl(theta y_i) + fl(omt Qs_i)), c0 = fl(1 / sv), c1 = -fl(1 / sQs); v = y on a block that is not damped, both
+    coefficients exactly 0 where sv or sQs is zero or not finite.  ``s`` is not read: the sums come from the report."""
+    report = np.asarray(report, dtype=np.float64)
+    y, Qs = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, Qs))
+    offsets = np.asarray(offsets, dtype=np.int64)
+    if report.shape != (offsets.size - 1, 8) or not (y.shape == Qs.shape == (int(offsets[-1]),)):
+        raise ValueError("bfgs_replay: report of (blocks, 8), y and Qs vectors of offsets[-1] entries")
+    v = y.copy()
+    coef = np.zeros((offsets.size - 1, 2))
+    one = np.float64(1.0)
+    with np.errstate(all="ignore"):
+        for k in range(offsets.size - 1):
+            b = slice(int(offsets[k]), int(offsets[k + 1]))
+            sy, sQs, gamma, sv = (np.float64(report[k, j]) for j in (0, 1, 2, 4))
+            if sy < gamma * sQs:
+                theta = ((one - gamma) * sQs) / (sQs - sy)
+                omt = one - theta
+                v[b] = theta * y[b] + omt * Qs[b]
+            else:
+                sv = sy
+            if sv != 0.0 and sQs != 0.0 and np.isfinite(sv) and np.isfinite(sQs):
+                coef[k] = one / sv, -(one / sQs)
+    return v, coef

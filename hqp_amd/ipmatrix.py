@@ -355,7 +355,8 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
     the diagonal wherever that is smaller (hqpkkt_set_packed_hessians; hessian_packing() reports the layout).
     After a dense hand-over the blocks live on the device: update_stage_hessians() changes them in place (scale, diagonal,
     up to four rank-one terms per stage), hessian_product() gives Q x, and bfgs_update() is the reference's damped block-BFGS
-    step made of the two (hqpkkt_update_stage_hessians, hqpkkt_hessian_product)."""
+    step made of the two (hqpkkt_update_stage_hessians, hqpkkt_hessian_product) with its terms formed on the host;
+    bfgs_update_device() forms them on the device too (hqpkkt_bfgs_update_stage_hessians), bfgs_report() reads what it did."""
     _mode = _lib.MODE_STAGED
     _name = "LQDOCP"
 
@@ -587,6 +588,40 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
             U, coef = bfgs_terms(s, y, self.hessian_product(s), offsets, gamma, alpha)
             self.update_stage_hessians(U, coef)
         return U, coef
+
+    def bfgs_update_device(self, s, y, gamma=0.1, alpha=1.0, want_v=False):
+        """The same update with its terms formed on the device as well (hqpkkt_bfgs_update_stage_hessians): Q s, the
+        scalars, Powell's test, v and the coefficients never reach the host.  ``s``, ``y``: numpy vectors of n - or torch
+        CUDA tensors with device_vectors=True: no host copy is made, the call returns with the work enqueued in the
+        handle's stream, and the tensors are kept alive here until the next call.  ``gamma`` < 0: damping adapted to the
+        step length ``alpha``.  ``want_v``: returns v as applied (a tensor with device_vectors=True), else None.
+        bfgs_report() tells what every stage did."""
+        ps, ks = self._hess_vec(s, "s")
+        py, ky = self._hess_vec(y, "y")
+        b = _lib.BfgsUpdate()
+        b.s, b.y, b.gamma, b.alpha = ps.value, py.value, float(gamma), float(alpha)
+        v = None
+        if want_v:
+            if self._device_vectors:
+                import torch
+                v = torch.zeros(self.n, dtype=torch.float64, device=ks.device)
+                b.v = v.data_ptr()
+            else:
+                v = np.zeros(self.n)
+                b.v = v.ctypes.data
+        self._torch_sync()
+        _check(self._L.hqpkkt_bfgs_update_stage_hessians(self._h, C.byref(b)), "bfgs_update_device")
+        self._keep_b = [ks, ky, v]
+        return v
+
+    def bfgs_report(self):
+        """Per stage k = 0 .. K what the last bfgs_update_device() did (hqpkkt_bfgs_report), an array of shape (K + 1, 8):
+        s'y, s'Qs, the damping factor used, theta (1 where not damped), s'v as used, the coefficients 1 / s'v and
+        -1 / s'Qs (0 where the stage was left alone), and the outcome - 0 updated, 1 updated with damping, 2 left alone
+        (s'v or s'Qs is zero), 3 left alone (s'v or s'Qs is not finite).  Waits for the handle's stream."""
+        out = np.zeros((len(self.debug(20)), _lib.HQPKKT_BFGS_REPORT))
+        _check(self._L.hqpkkt_bfgs_report(self._h, C.c_void_p(out.ctypes.data)), "bfgs_report")
+        return out
 
     def set_packed_hessians(self, on):
         """Dense stage Hessians stored as packed lower tiles (hqpkkt_set_packed_hessians); holds from the next init() on."""

@@ -485,6 +485,56 @@ typedef struct hqpkkt_hess_update {
 } hqpkkt_hess_update;
 int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u);
 int hqpkkt_hessian_product(hqpkkt_t *h, const double *x, double *y);
+/* The reference's damped BFGS update of every dense stage Hessian (Hqp_HL_BFGS::update_b_Q, hqp/Hqp_HL_BFGS.C:150-248,
+ * without its eigenvalue control) with nothing of it on the host: the step between hqpkkt_hessian_product and
+ * hqpkkt_update_stage_hessians - the scalars s'y and s'Qs, Powell's test, the vector v, the two coefficients - runs on the
+ * device too, so a caller whose s and y live there never leaves it.  Per stage k = 0 .. K, over the stage's variables:
+ *     sy = s'y,  sQs = s'(Q s);  damped where sy < gamma_eff sQs:
+ *         theta = (1 - gamma_eff) sQs / (sQs - sy),  v = theta y + (1 - theta) Q s,  sv = s'v;   otherwise v = y, sv = sy
+ *     Q_k <- Q_k + v v' / sv - (Q s)(Q s)' / sQs
+ * s, y and v (optional: v as applied, y where a stage is not damped) hold n doubles, pointers per opts.loc.  gamma is the
+ * reference's sqp_hela_gamma: gamma >= 0 is the damping factor gamma_eff itself, gamma < 0 adapts it to the step length,
+ * gamma_eff = g + (1 - g)(1 - alpha) with g = -gamma; alpha is read only then.  gamma_eff is formed on the host.
+ *   Launches, all in the handle's stream, on both layouts of the blocks: Q s by the launches of hqpkkt_hessian_product
+ *   into a buffer of this entry (not the residual's); k_hb_terms (staged_hess_bfgs.hip.h), one workgroup per stage, which
+ *   writes v, the coefficients c0 = 1 / sv, c1 = -1 / sQs and the skips into the device descriptors of the update launch;
+ *   then the launch of hqpkkt_update_stage_hessians, unchanged, with U = [v, Q s], r = 2, beta = 1, no diagonal: the bits of
+ *   Q+ are those that entry gives for the same v, Q s, c0 and c1.
+ *   Values.  The sums run in an order fixed by the stage's order alone (a thread's entries t, t + 256, .. by fused
+ *   multiply-adds, the 64 lanes of a wavefront by a butterfly, the four wavefronts in their order): the same bits from run to
+ *   run and on a packed and an unpacked handle given the same Q s.  The test, theta, 1 - theta, every v_i = fl(fl(theta y_i)
+ *   + fl((1 - theta) (Qs)_i)) and the reciprocals are single operations, each rounded once: hessian_update.bfgs_replay
+ *   repeats them in numpy from the reported sums.
+ *   Skips.  A stage whose sv or sQs is zero is left alone, as in the reference (a stage of order 0 counts as such).  A stage
+ *   whose sv or sQs is not finite is left alone too: that follows hessian_update.bfgs_terms, NOT the reference, which
+ *   would write NaN into the block.  Entries past a stage's order belong to the next stage and are never read as values:
+ *   a NaN in one stage's y reaches no other stage.
+ *   Checks, all before anything is launched (a call applies to every stage or to none): HQPKKT_E_NULL - h, b, b->s or b->y
+ *   null; HQPKKT_E_RANGE - gamma not finite, or gamma < 0 with an alpha that is not finite; HQPKKT_E_INTERN - the handle is
+ *   not STAGED, not analysed, not HQPKKT_HESS_DENSE or analysed for the CSR hand-over, or a block of nonzero order has not
+ *   arrived since the analysis (the hand-over rule of hqpkkt_update_stage_hessians with beta = 1 on every stage); then,
+ *   without a gfx950 device, HQPKKT_E_DEVICE.
+ *   Host vectors are copied through buffers the handle owns, v is copied back, and the call returns when the stream is
+ *   done.  Device vectors: nothing is read back, the call waits for nothing but the descriptor words of the call before
+ *   it, and returns with the work enqueued; the caller keeps s, y and v alive and unchanged until the stream has passed,
+ *   and v overlaps neither s nor y.  All buffers are made by the first call, outside any capture.
+ *   After the call h is not factored; the dynamics and the hand-over state are left alone.
+ * hqpkkt_bfgs_report waits for the stream and copies out what k_hb_terms left of the last update, HQPKKT_BFGS_REPORT doubles
+ * per stage: 0 sy; 1 sQs; 2 gamma_eff; 3 theta (1.0 where not damped); 4 sv as used (s'v after damping, else sy); 5 c0;
+ * 6 c1 (both 0.0 where the stage was left alone); 7 the outcome - 0 updated without damping, 1 updated with damping, 2 left
+ * alone because sv or sQs is zero, 3 left alone because sv or sQs is not finite.  HQPKKT_E_NULL; HQPKKT_E_INTERN before
+ * the first update since the analysis.
+ * Not built: the reference's eigenvalue control (an eigendecomposition per block) and restart_Q. */
+typedef struct hqpkkt_bfgs_update {
+  const double *s; /* n doubles, pointer per opts.loc: the step */
+  const double *y; /* n doubles, pointer per opts.loc: change of the Lagrangian's gradient */
+  double gamma;    /* the reference's sqp_hela_gamma: >= 0 standard damping, < 0 adapted to alpha */
+  double alpha;    /* step length; read only when gamma < 0 */
+  double *v;       /* optional, n doubles per opts.loc: the vector v as applied (y where no damping) */
+} hqpkkt_bfgs_update;
+int hqpkkt_bfgs_update_stage_hessians(hqpkkt_t *h, const hqpkkt_bfgs_update *b);
+#define HQPKKT_BFGS_REPORT 8
+int hqpkkt_bfgs_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * 8 doubles */);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense

@@ -44,13 +44,10 @@
 #define FB_OWNSIMD false  // true: the elimination wavefront of k_factor_blk shares its SIMD with no block-holding wavefront (measured slower)
 #endif
 
+#include "tree_sizes.hpp"  // fb_ld_of, fb_img_of, fb_lds_bytes
+
 namespace kktdev {
 
-// leading dimension of the 16-row LDS images: = 16 mod 32 doubles, so that the four
-// k-rows a wavefront reads with one ds_read_b64 fall into different halves of the banks
-// (a compile-time constant of the two instantiations: 144 for blocks of up to 128 pivots, 208 up to 192 - the
-// k-rows of an operand are immediate offsets of one address then)
-__host__ __device__ inline int fb_ld_of(int p) { return p <= 128 ? 144 : 208; }
 // Where k-row k of a 16-row operand image starts (round 6): rows 2 j and 2 j + 1 are skewed by j doubles.  The reads of
 // the matrix products (ds_read_b64: a half-wave touches k-rows k and k + 1 with k even, 16 consecutive doubles of
 // each) stay conflict-free - ld = 16 mod 32 keeps the pair in different halves of the banks, the pair shares its
@@ -58,12 +55,6 @@ __host__ __device__ inline int fb_ld_of(int p) { return p <= 128 ? 144 : 208; }
 // rows times N, N itself) spread over eight bank pairs instead of hitting ONE (16-way conflicts: they were the 52 %
 // of profiles/r05_pmc_tree.txt).  An image takes 16 ld + 8 doubles.
 #define FBROW(k) ((k) * ld + ((k) >> 1))
-__host__ __device__ inline int fb_img_of(int ld) { return 16 * ld + 8; }
-__host__ __device__ inline size_t fb_lds_bytes(int p) {
-  const int pp = ((p + 15) / 16) * 16, ld = fb_ld_of(p);
-  // Op, Lb, Yb, Xq | Tb, Ld (two each), Gb | Ab, G2 | dvals, dinvs, cmaxf, flags (two each) | rm0 | dv | lp, pt (ints)
-  return sizeof(double) * ((size_t)4 * fb_img_of(ld) + 5 * 272 + 512 + 96 + (size_t)pp + 2 * (size_t)pp + (size_t)pp + 16);
-}
 
 // Barrier of the panel loop: waits for this wavefront's LDS operations only.  __syncthreads() also waits for the
 // global stores in flight (the finished columns of L11 and rows of M leave all the time; nobody in the

@@ -731,10 +731,26 @@ int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len) {
       tmp = {h->zd_used, h->zd_weak ? 1 : 0};
       v = &tmp;
       break;
-    case 31:  // the solve's fused top (k_solve_top): number of fronts, first fused level, LDS bytes
-      tmp = {h->top_n, h->top_n ? h->top_lt : h->an.nlevels, (int)h->top_lds, h->top_ns, h->small_tree ? 1 : 0, h->tree_factor ? 1 : 0, h->top_split ? 1 : 0};
+    case 31: case 48: {  // what the handle launches (tree_plan.hpp): the plan in use, or before the upload the one the switches give now
+      TreePlan fly;
+      if (!h->uploaded && h->opts.mode != HQPKKT_MODE_STAGED) fly = tree_plan(an, tree_switches(h));
+      const TreePlan &P = h->uploaded ? h->plan : fly;
+      if (P.err) return P.err;
+      tmp = {P.top.n, P.top.n ? P.top.lt : an.nlevels, (int)P.top.lds, P.top.ns, P.small_tree ? 1 : 0, P.tree_factor ? 1 : 0, P.top.split ? 1 : 0};
+      if (what == 31) {  // the solve's fused top (k_solve_top): number of fronts, first fused level, LDS bytes, ...
+        v = &tmp;
+        break;
+      }
+      for (int x : {P.tree_ldp, P.tree_ldb, (int)P.lds_panel, (int)P.lds_bwdb, (int)P.lds_blk, an.nlevels, LEVEL_PLAN_INTS, an.sched[0].nnodes, an.sched[1].nnodes}) tmp.push_back(x);
+      for (int w = 0; w < 2; w++)
+        for (int l = 0; l < an.nlevels; l++) {
+          const LevelPlan R = l < (int)P.levels[w].size() ? P.levels[w][l] : LevelPlan();
+          const int *r = (const int *)&R;
+          tmp.insert(tmp.end(), r, r + LEVEL_PLAN_INTS);
+        }
       v = &tmp;
       break;
+    }
     case 40:  // live device / pinned host buffers of the process (DBuf / PinnedBuf, over all handles)
       tmp = {(int)g_live_bufs[0].load(), (int)g_live_bufs[1].load()};
       v = &tmp;
@@ -774,13 +790,13 @@ int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long ca
   if (cap < n) return HQPKKT_E_SIZES;
   HIPCHK(hipSetDevice(h->opts.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (what == 3 && h->tree_factor) {  // the block is in the exchange copy of the last factorisation (lower triangle; the rest idle)
+  if (what == 3 && h->plan.tree_factor) {  // the block is in the exchange copy of the last factorisation (lower triangle; the rest idle)
     int ep = 0;
     HIPCHK(hipMemcpy(&ep, h->td.tree_words.p + 1, sizeof(int), hipMemcpyDeviceToHost));
     src = h->td.tree_u.p + (long long)(ep & 1) * an.upd_elems + an.upd_off[node];
   }
   if (n) HIPCHK(hipMemcpy(out, src, sizeof(double) * n, hipMemcpyDeviceToHost));
-  if (what == 3 && h->tree_factor)
+  if (what == 3 && h->plan.tree_factor)
     for (long long t = 0; t < n; t++)
       if (std::memcmp(out + t, &XW_SENTINEL, sizeof(double)) == 0) out[t] = 0.0;
   return 0;

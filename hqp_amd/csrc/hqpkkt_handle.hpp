@@ -1,7 +1,8 @@
 // Internal header of the C-ABI library (include/hqpkkt.h): the handle and what the units share - device buffers,
 // per-class timing, graph capture, and the functions one unit calls in another.  The units:
 //   tree.hip           device residency and kernel sequencing of the tree engine (kernels.hip.h, factor_blk.hip.h,
-//                      solve_top.hip.h), the vector staging of a call, the residual and the posted read-backs
+//                      solve_top.hip.h; launch rule: tree_plan.hpp), the vector staging of a call, the residual and the
+//                      posted read-backs
 //   staged_engine.hip  the STAGED engine (staged.hip.h, staged_gemm.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
 //   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
 //   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
@@ -24,6 +25,7 @@
 
 #include "analysis.hpp"
 #include "staged_plan.hpp"
+#include "tree_plan.hpp"
 #include "device_common.hip.h"
 
 // The kernels that more than one unit launches: defined once (kernels.hip.h, compiled into tree.hip)
@@ -266,8 +268,8 @@ struct TreeDev {
   DBuf<double> vres;  // residual vectors _r1.._r4
   DBuf<double> vcor;  // corrections _dx.._dw
   DBuf<double> tz;    // REDUCED temporary (m)
-  DBuf<int> top_nodes, top_idx, top_bpos, top_up;  // the fused top of the solve (hqpkkt::top_n); top_up: the fronts leaves first (top_split)
-  // trees of small fronts only (hqpkkt::small_tree): the exchange arrays (2 x cb_elems, then 2 x dim)
+  DBuf<int> top_nodes, top_idx, top_bpos, top_up;  // the fused top of the solve (TreePlan::top); top_up: the fronts leaves first (its split form)
+  // trees of small fronts only (TreePlan::small_tree): the exchange arrays (2 x cb_elems, then 2 x dim)
   DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
   DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
   DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
@@ -318,21 +320,12 @@ struct hqpkkt {
   const double *out_pending = nullptr;   // results wait in hstage + hstage_in for unstage()
   bool out_by_kernel = false;            // ... written there by a kernel in front of the posting kernel (no stream synchronisation needed)
   bool host_graph_call = false;          // inside a solve whose first part ran as hqpkkt::ghost_step (no timing events in the stream)
-  size_t lds_panel = 0, lds_bwdb = 0;
-  // per schedule and tree level the largest pivot count (and border) among the general fronts of the level (k_factor_blk)
-  std::vector<int> level_maxp[2], level_maxb[2];
+  kktdev::TreePlan plan;  // what run_factor and run_step launch, level by level (tree_plan.hpp; built by upload)
   // the device-resident interior-point loops: cancelled multiplier pivots are replaced (kernels.hip.h, TINY_REPLACE_WORD)
   // only in the SECOND attempt of a run whose first attempt - without the replacement, i.e. with the factors the
   // reference's own loop gets from this plugin through the shim - ended "degenerate" or singular
   bool tiny_replace_in_loop = false;
-  // the top levels of the tree solved in one launch (solve_top.hip.h): fronts of the levels >= top_lt, root first
-  int top_n = 0, top_lt = 1 << 30, top_ns = 3;  // top_ns: 3 = k_solve_top<3, 11>, 4 = <4, 10>
-  size_t top_lds = 0;
-  bool top_split = false;  // more fronts than one launch may hold at once: the two sweeps as launches of their own
   unsigned long long *top_stamps = nullptr;  // (hqpkkt_debug_solve_top_stamps)
-  // trees of small fronts only (the double-integrator structure): each sweep of the solve is ONE launch over all levels
-  // (k_solve_fwd_small<true> / k_solve_bwd_small<true>)
-  bool small_tree = false, tree_factor = false;  // tree_factor: ... and the factorisation too (k_factor_diag_small<true, true>)
   // captured kernel sequences (factor; step on the caller's vectors; step on the
   // refinement's residual vectors): replayed with hipGraphLaunch
   struct GraphSlot {
@@ -495,6 +488,7 @@ int ensure_device(hqpkkt_t *h);
 int alloc_hpin(hqpkkt_t *h);
 int upload(hqpkkt_t *h);
 bool poll_fallback(hqpkkt_t *h, const int *hs);
+TreeSwitches tree_switches(const hqpkkt_t *h);  // the environment as it stands, and h->no_polled
 bool host_graphs_ok(const hqpkkt_t *h);
 size_t stage_pack(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3, const double *r4);
 int stage_in(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3, const double *r4,

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "device_common.hip.h"
+#include "tree_sizes.hpp"  // fs_lds_bytes, PS_LD
 namespace kktdev {
 
 // Sum of the children's update blocks at front position (fi, fj), fi >= fj, of `node`:
@@ -1067,13 +1068,7 @@ struct TreeXchgF {
 // launches per tree level become one.
 #define FS_MAXP 32
 #define FS_MAXB 16
-// LDS bytes of one front for the leading dimensions of a launch: ldp odd and >= the largest p,
-// ldb >= the largest b of the fronts in the launch (a level of a narrow-band tree has
-// fronts of 5..20 pivots, a quarter of the room the limits would need)
-__host__ __device__ inline size_t fs_lds_bytes(bool front, int ldp, int ldb) {
-  const size_t d = (size_t)ldp * ldp + 2 * (size_t)ldp + (front ? 2 * (size_t)ldb * ldp + (size_t)ldb * ldb : 0);
-  return 8 * d + 8 * (size_t)ldp;
-}
+// (LDS bytes of one front for the leading dimensions of a launch: fs_lds_bytes, tree_sizes.hpp)
 // value of a lane's double in a uniform lane
 __device__ __forceinline__ double rdlane(double v, int l) {
   const long long b = __double_as_longlong(v);
@@ -1825,7 +1820,7 @@ k_solve_bwd_small(DevTree T, const int *__restrict__ level_nodes, const double *
 // MFMA operand layout (verified by hqpkkt_selftest_mfma): A: lane l holds
 // A[l&15][l>>4]; B: B[l>>4][l&15]; C/D: col = l&15, row = (l>>4) + 4*reg.
 
-static const int PS_LD = 33;  // doubles per column of the RESULT slab in LDS (what the launch sizes its LDS by)
+// (PS_LD doubles per column of the RESULT slab in LDS - what the launch sizes its LDS by: tree_sizes.hpp)
 #ifdef HQPKKT_STAMPS
 // instrumented build: s_memtime of lane 0 of every wavefront of workgroup 0 (the last launch wins: the top level)
 __device__ int g_ps_stamps[64];

@@ -29,19 +29,13 @@
 // bit-identical to the per-level kernels (different order of summation).
 #pragma once
 
+#include "tree_sizes.hpp"  // ST_THREADS, ST_MAXFRONTS, ST_MAXSPLIT, ST_XS, ST_CS, st_top_fits, st_top_lds_bytes
+
 namespace kktdev {
 
-static const int ST_THREADS = 1024, ST_MAXFRONTS = 128, ST_MAXSPLIT = 1 << 15;  // fronts of one fused launch / of the split form
-static const int ST_XS = 192, ST_CS = 256;  // words per front in the exchange arrays: solution (pivots), contribution (border rows)
 static const int ST_GAVE_UP = XW_GAVE_UP;    // index into the handle's flags buffer
 static const unsigned long long ST_SENTINEL = XW_SENTINEL;
 
-// the two instances: <3, 11> fronts of up to 176 pivots and 192 border rows, <4, 10> up to 160 pivots and 256 border rows
-static inline bool st_top_fits(int p, int b, int ns, int nu) { return p <= 16 * nu && b <= 64 * ns; }
-static inline size_t st_top_lds_bytes(int maxp, int ns) {
-  const size_t mlen = ((size_t)maxp * (maxp + 1) / 2 + 1) & ~(size_t)1;
-  return sizeof(double) * (mlen + 8 * 64 * ns + 16 * 64 * ns);
-}
 __device__ __forceinline__ void st_post(double *p, double v) { xw_post(p, v); }
 __device__ __forceinline__ double st_take(const double *p, int *flags) { return xw_take(p, flags); }
 

@@ -1,6 +1,9 @@
-// The tree engine (HQPKKT_MODE_FULL / _REDUCED): device residency of the symbolic structure and the kernel
-// sequencing of assemble -> factor -> step -> residual; the vector staging of a call and the posted read-backs
-// (both engines use them), and the debug entry points that launch the tree's kernels or read its device arrays.
+// The tree engine (HQPKKT_MODE_FULL / _REDUCED): device residency of the symbolic structure (upload, a sequence of named
+// steps) and the kernel sequencing of assemble -> factor -> step -> residual; the vector staging of a call and the posted
+// read-backs (both engines use them), and the debug entry points that launch the tree's kernels or read its device arrays.
+// WHAT is launched for a tree level is decided once per upload by tree_plan() (tree_plan.hpp, plain host code) and kept in
+// hqpkkt::plan; run_factor and run_step walk it.  The instances of the templated kernels stand in one table per family
+// (fb_kernels, top_kernels), the pointer lists the kernels share in one launch function each (launch_factor, launch_fwd).
 #include "hqpkkt_handle.hpp"
 
 #include "kernels.hip.h"
@@ -35,16 +38,17 @@ static int reset_solve_top(hqpkkt_t *h) {
     HIPCHK(hipMemcpy(buf.p, f.data(), sizeof(double) * count, hipMemcpyHostToDevice));
     return 0;
   };
+  const TreePlan &P = h->plan;
   int e;
-  if (h->top_n > 0) {
-    if ((e = fill(h->td.top_x, 2 * (size_t)h->top_n * (ST_CS + ST_XS)))) return e;
-  }
-  if (h->small_tree) {
-    if ((e = fill(h->td.tree_x, 2 * (size_t)(h->an.cb_elems + h->an.dim)))) return e;
-    if (h->tree_factor && (e = fill(h->td.tree_u, 2 * (size_t)std::max<long long>(h->an.upd_elems, 1)))) return e;
-
-  }
+  if (P.top.n > 0 && (e = fill(h->td.top_x, 2 * (size_t)P.top.n * (ST_CS + ST_XS)))) return e;
+  if (P.small_tree && (e = fill(h->td.tree_x, 2 * (size_t)(h->an.cb_elems + h->an.dim)))) return e;
+  if (P.tree_factor && (e = fill(h->td.tree_u, 2 * (size_t)std::max<long long>(h->an.upd_elems, 1)))) return e;
   return 0;
+}
+
+TreeSwitches tree_switches(const hqpkkt_t *h) {
+  return TreeSwitches{getenv("HQPKKT_NO_TREE_SWEEPS") != nullptr, getenv("HQPKKT_NO_SOLVE_TOP") != nullptr,
+                      getenv("HQPKKT_SOLVE_TOP_FUSED") != nullptr, h->no_polled};
 }
 
 bool poll_fallback(hqpkkt_t *h, const int *hs) {
@@ -52,7 +56,10 @@ bool poll_fallback(hqpkkt_t *h, const int *hs) {
   (void)reset_solve_top(h);
   (void)hipMemsetAsync(h->td.flags.p + XW_GAVE_UP, 0, sizeof(int), h->stream);
   (void)hipStreamSynchronize(h->stream);
-  h->top_n = 0, h->small_tree = false, h->tree_factor = false, h->no_polled = true;  // (no_polled: a later upload stays there)
+  h->no_polled = true;  // (a later upload stays there)
+  TreeSwitches sw = h->plan.sw;
+  sw.no_polled = true;
+  h->plan = tree_plan(h->an, sw);  // per-level launches from now on
   h->drop_graphs();
   h->st.n_poll_fallbacks++;
   if (getenv("HQPKKT_TRACE_SOLVE")) fprintf(stderr, "a polled launch gave up: per-level launches from now on\n");
@@ -72,10 +79,32 @@ int alloc_hpin(hqpkkt_t *h) {
   HIPCHK(hipMemset(h->kept.post_seq_dev.p, 0, sizeof(unsigned)));
   return 0;
 }
-int upload(hqpkkt_t *h) {
-  int e = ensure_device(h);
-  if (e) return e;
+// ------------------------------------------------------------ one table per templated kernel family
+// the instances of k_factor_blk, in the order of fb_instances (tree_plan.hpp: pivots held and threads of each)
+using FactorBlkFn = decltype(&k_factor_blk<8, 6, 144, 2, FB_OWNSIMD>);
+static const FactorBlkFn fb_kernels[FB_INSTANCES] = {k_factor_blk<8, 6, 144, 2, FB_OWNSIMD>, k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD>,
+                                                     k_factor_blk<12, 6, 208, 3, FB_OWNSIMD>, k_factor_blk<12, 8, 208, 3, FB_OWNSIMD>};
+// the instances of k_solve_top by [ns - 3][mode], and the pivots an instance holds (16 nu)
+using SolveTopFn = decltype(&k_solve_top<3, 11, 0>);
+static const SolveTopFn top_kernels[2][3] = {{k_solve_top<3, 11, 0>, k_solve_top<3, 11, 1>, k_solve_top<3, 11, 2>},
+                                             {k_solve_top<4, 10, 0>, k_solve_top<4, 10, 1>, k_solve_top<4, 10, 2>}};
+static const int top_maxp[2] = {176, 160};
+
+static int set_max_lds(const void *kernel, size_t bytes) {
+  HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return 0;
+}
+// every instance of k_factor_blk may launch with `want` bytes of LDS, or with what its largest front needs
+static int raise_fb_lds(size_t want) {
+  int e = 0;
+  for (int i = 0; i < FB_INSTANCES && !e; i++) e = set_max_lds((const void *)fb_kernels[i], std::min(want, fb_lds_bytes(fb_instances[i].maxp)));
+  return e;
+}
+
+// ------------------------------------------------------------ upload, step by step
+static int upload_structure(hqpkkt_t *h) {
   Analysis &an = h->an;
+  int e;
 #define UP(buf, vec) \
   if ((e = h->td.buf.upload(an.vec))) return e
   UP(piv_start, piv_start);
@@ -110,37 +139,48 @@ int upload(hqpkkt_t *h) {
   UP(cb_off, cb_off);
   UP(ent_dst, ent_dst);
 #undef UP
-  {
-    std::vector<TermDev> t(an.terms.size());
-    for (size_t k = 0; k < t.size(); k++)
-      t[k] = TermDev{an.terms[k].s1, an.terms[k].s2, an.terms[k].wi, an.terms[k].sgn};
-    if ((e = h->td.terms.upload(t))) return e;
-    // all entries single terms sgn * vals[s1] * wt[wi] with s2 = the constant 1 (FULL plugin)?
-    const int one = an.nq + an.na + an.nc;
-    bool simple = an.mode == 0 && an.terms.size() == an.ent_a.size();
-    for (size_t k = 0; simple && k < t.size(); k++)
-      simple = t[k].s2 == one && (t[k].sgn == 1.0 || t[k].sgn == -1.0);
-    if (simple) {
-      std::vector<int> ss(t.size()), ww(t.size());
-      for (size_t k = 0; k < t.size(); k++) ss[k] = t[k].s1 | (t[k].sgn < 0 ? (int)0x80000000 : 0), ww[k] = t[k].wi;
-      if ((e = h->td.simple_src.upload(ss)) || (e = h->td.simple_wi.upload(ww))) return e;
-    }
-    // sign a perturbed pivot takes: x rows belong to the -Q block, y / slack rows
-    // to the zero / +W/Z blocks
-    std::vector<signed char> sg(an.dim);
-    for (int q = 0; q < an.dim; q++) sg[an.q2e[q]] = q < an.n ? -1 : 1;
-    // +-2: no diagonal of its own (see zero_pivot_slot in kernels.hip.h)
-    std::vector<char> in_c(an.n, 0);  // REDUCED: C' (Z/W) C gives x_i a diagonal as well
-    if (an.mode != 0)
-      for (int c : h->pCi) in_c[c] = 1;
-    for (int q = 0; q < an.n; q++) {
-      bool diag = in_c[q] != 0;
-      for (int k = h->pQp[q]; k < h->pQp[q + 1]; k++) diag = diag || h->pQi[k] == q;
-      if (!diag) sg[an.q2e[q]] = -2;
-    }
-    for (int q = an.n; q < an.n + an.me; q++) sg[an.q2e[q]] = 2;
-    if ((e = h->td.esign.upload(sg))) return e;
+  return 0;
+}
+
+// the terms of the entries, and the sign a perturbed pivot takes
+static int upload_terms_and_signs(hqpkkt_t *h) {
+  Analysis &an = h->an;
+  int e;
+  std::vector<TermDev> t(an.terms.size());
+  for (size_t k = 0; k < t.size(); k++)
+    t[k] = TermDev{an.terms[k].s1, an.terms[k].s2, an.terms[k].wi, an.terms[k].sgn};
+  if ((e = h->td.terms.upload(t))) return e;
+  // all entries single terms sgn * vals[s1] * wt[wi] with s2 = the constant 1 (FULL plugin)?
+  const int one = an.nq + an.na + an.nc;
+  bool simple = an.mode == 0 && an.terms.size() == an.ent_a.size();
+  for (size_t k = 0; simple && k < t.size(); k++)
+    simple = t[k].s2 == one && (t[k].sgn == 1.0 || t[k].sgn == -1.0);
+  if (simple) {
+    std::vector<int> ss(t.size()), ww(t.size());
+    for (size_t k = 0; k < t.size(); k++) ss[k] = t[k].s1 | (t[k].sgn < 0 ? (int)0x80000000 : 0), ww[k] = t[k].wi;
+    if ((e = h->td.simple_src.upload(ss)) || (e = h->td.simple_wi.upload(ww))) return e;
   }
+  // sign a perturbed pivot takes: x rows belong to the -Q block, y / slack rows
+  // to the zero / +W/Z blocks
+  std::vector<signed char> sg(an.dim);
+  for (int q = 0; q < an.dim; q++) sg[an.q2e[q]] = q < an.n ? -1 : 1;
+  // +-2: no diagonal of its own (see zero_pivot_slot in kernels.hip.h)
+  std::vector<char> in_c(an.n, 0);  // REDUCED: C' (Z/W) C gives x_i a diagonal as well
+  if (an.mode != 0)
+    for (int c : h->pCi) in_c[c] = 1;
+  for (int q = 0; q < an.n; q++) {
+    bool diag = in_c[q] != 0;
+    for (int k = h->pQp[q]; k < h->pQp[q + 1]; k++) diag = diag || h->pQi[k] == q;
+    if (!diag) sg[an.q2e[q]] = -2;
+  }
+  for (int q = an.n; q < an.n + an.me; q++) sg[an.q2e[q]] = 2;
+  return h->td.esign.upload(sg);
+}
+
+// the SpMV blocks, the arenas of the factors and the vectors, the status words
+static int alloc_numeric(hqpkkt_t *h) {
+  Analysis &an = h->an;
+  int e;
   if ((e = h->td.Qf.upload(an.Qfull)) || (e = h->td.A.upload(an.A)) || (e = h->td.AT.upload(an.AT)) ||
       (e = h->td.C.upload(an.C)) || (e = h->td.CT.upload(an.CT)))
     return e;
@@ -161,39 +201,37 @@ int upload(hqpkkt_t *h) {
   h->td.bits.p = (unsigned long long *)(h->td.flags.p + 120);
   HIPCHK(hipMemset(h->td.flags.p, 0, sizeof(int) * 128));
   h->res_read = 122;
+  std::vector<double> ones(dim, 1.0);
+  HIPCHK(hipMemcpy(h->td.sc.p, ones.data(), sizeof(double) * dim, hipMemcpyHostToDevice));
+  const double one = 1.0;
+  HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// the mapped words of the read-backs, and the pinned buffer the vectors of a small system go through
+static int alloc_staging(hqpkkt_t *h) {
+  const int n = h->an.n, me = h->an.me, m = h->an.m;
+  int e;
   if ((e = alloc_hpin(h))) return e;
   h->td.hstage.release();
   h->td.hstage_in = h->td.hstage_out = 0;
-  {
-    const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
-    if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
-      HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocMapped | hipHostMallocCoherent));
-      h->td.hstage_in = nin, h->td.hstage_out = nout;
-      if (h->td.hstage.map() != hipSuccess) (void)hipGetLastError();
-    }
+  const size_t nin = 4 * (size_t)m + n + me, nout = (size_t)n + me + 2 * (size_t)m;
+  if ((nin + nout) * sizeof(double) <= (size_t)512 * 1024 && nin + nout > 0) {
+    HIPCHK(h->td.hstage.alloc(nin + nout, hipHostMallocMapped | hipHostMallocCoherent));
+    h->td.hstage_in = nin, h->td.hstage_out = nout;
+    if (h->td.hstage.map() != hipSuccess) (void)hipGetLastError();
   }
-  {
-    std::vector<double> ones(dim, 1.0);
-    HIPCHK(hipMemcpy(h->td.sc.p, ones.data(), sizeof(double) * dim, hipMemcpyHostToDevice));
-    const double one = 1.0;
-    HIPCHK(hipMemcpy(h->td.vals.p + (nv - 1), &one, sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->td.wt.p + m, &one, sizeof(double), hipMemcpyHostToDevice));
-  }
-  // dynamic LDS budgets
-  const size_t mp = an.max_npiv;
-  h->lds_panel = (PS_LD * mp + 1 + 2 * mp) * sizeof(double) + mp * sizeof(int);
-  h->lds_bwdb = ((size_t)an.max_nbor + 2) * sizeof(double);
-  const size_t lds_blk = fb_lds_bytes((int)mp);
-  if (h->lds_bwdb > 160 * 1024 || lds_blk > 160 * 1024) return HQPKKT_E_MEM;
-  for (int w = 0; w < 2; w++) {
-    const Analysis::Sched &S = an.sched[w];
-    h->level_maxp[w].assign(an.nlevels, 0), h->level_maxb[w].assign(an.nlevels, 0);
-    for (int l = 0; l < an.nlevels && S.nnodes; l++)
-      for (int q = S.level_ptr[l] + S.level_fsmall[l] + S.level_small[l]; q < S.level_ptr[l + 1]; q++) {
-        h->level_maxp[w][l] = std::max(h->level_maxp[w][l], an.npiv[S.level_nodes[q]]);
-        h->level_maxb[w][l] = std::max(h->level_maxb[w][l], an.nbor[S.level_nodes[q]]);
-      }
-  }
+  return 0;
+}
+
+// what the handle launches (tree_plan.hpp), the device arrays of its polled launches and their idle state
+static int upload_plan(hqpkkt_t *h) {
+  Analysis &an = h->an;
+  int e;
+  h->plan = tree_plan(an, tree_switches(h));
+  const TreePlan &P = h->plan;
+  if (P.err) return P.err;
   {  // the counters of the polled exchanges: [0] solves, [1] factorisations so far (k_rhs_*, the assembly kernels count)
     std::vector<int> two(2, 0);
     if ((e = h->td.tree_words.upload(two))) return e;
@@ -205,121 +243,66 @@ int upload(hqpkkt_t *h) {
     const double spp = 1e-6;  // (kernels.hip.h, soft_pivot_pert)
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(soft_pivot_pert), &spp, sizeof(double)));
   }
-  // a tree of small fronts only: whole-tree sweeps
-  h->small_tree = false, h->tree_factor = false;
-  if (!getenv("HQPKKT_NO_TREE_SWEEPS") && !h->no_polled && an.shard_count == 1 && an.sched[0].nnodes > 1 && an.sched[1].nnodes == 0) {
-    const Analysis::Sched &S = an.sched[0];
-    bool all = true;
-    for (int l = 0; l < an.nlevels && all; l++) all = S.level_fsmall[l] == S.level_ptr[l + 1] - S.level_ptr[l];
-    if (all) {
-      std::vector<int> down, one(2, 0);
-      for (int l = an.nlevels - 1; l >= 0; l--)
-        for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; q++) down.push_back(S.level_nodes[q]);
-      if ((e = h->td.tree_down.upload(down)) || (e = h->td.tree_x.alloc(2 * (size_t)(an.cb_elems + an.dim)))) return e;
-      h->small_tree = true;
-      h->tree_factor = !an.upd_pingpong;
-      if (h->tree_factor && (e = h->td.tree_u.alloc(2 * (size_t)std::max<long long>(an.upd_elems, 1)))) return e;
-      if ((e = reset_solve_top(h))) return e;
-    }
+  if (P.small_tree) {
+    if ((e = h->td.tree_down.upload(P.tree_down)) || (e = h->td.tree_x.alloc(2 * (size_t)(an.cb_elems + an.dim)))) return e;
+    if (P.tree_factor && (e = h->td.tree_u.alloc(2 * (size_t)std::max<long long>(an.upd_elems, 1)))) return e;
   }
-  // the fused top of the solve sweeps: the highest levels whose fronts all fit one instance of k_solve_top, at most
-  // ST_MAXFRONTS fronts (single rank: with a sharded tree the two sweeps of a schedule are not adjacent)
-  h->top_n = 0, h->top_lt = 1 << 30, h->top_lds = 0;
-  if (!getenv("HQPKKT_NO_SOLVE_TOP") && !h->no_polled && an.shard_count == 1 && an.sched[0].nnodes > 0) {
-    const Analysis::Sched &S = an.sched[0];
-    int lt = an.nlevels, cnt = 0, maxp = 0;
-    bool ok3 = true, ok4 = true;  // the instances <3, 11> and <4, 10>
-    for (int l = an.nlevels - 1; l >= 0; l--) {
-      const int nn = S.level_ptr[l + 1] - S.level_ptr[l];
-      bool f3 = ok3, f4 = ok4;
-      int mp2 = maxp;
-      for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; q++) {
-        const int v = S.level_nodes[q];
-        f3 = f3 && st_top_fits(an.npiv[v], an.nbor[v], 3, 11), f4 = f4 && st_top_fits(an.npiv[v], an.nbor[v], 4, 10);
-        mp2 = std::max(mp2, an.npiv[v]);
-      }
-      // (levels of small fronts stay with their one-wavefront kernels: a step of k_solve_top costs 16 wavefronts'
-      // worth of barriers and reductions whatever the size of the front - measured slower on the DID tree)
-      if (cnt + nn > ST_MAXSPLIT || !(f3 || f4) || S.level_fsmall[l] > 0) break;
-      cnt += nn, lt = l, maxp = mp2, ok3 = f3, ok4 = f4;
-    }
-    if (an.nlevels - lt >= 2 && cnt >= 2) {
-      std::vector<int> nodes, idx(an.nnodes, -1), owner(an.dim, -1);
-      for (int l = an.nlevels - 1; l >= lt; l--)
-        for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; q++) idx[S.level_nodes[q]] = (int)nodes.size(), nodes.push_back(S.level_nodes[q]);
-      for (size_t t = 0; t < nodes.size(); t++)
-        for (int k = 0; k < an.npiv[nodes[t]]; k++) owner[an.piv_start[nodes[t]] + k] = (int)t;
-      std::vector<int> bpos(nodes.size() * ST_CS, 0);
-      for (size_t t = 0; t < nodes.size(); t++)
-        for (int i = 0; i < an.nbor[nodes[t]]; i++) {
-          const int ei = an.bidx[an.bptr[nodes[t]] + i], o = owner[ei];
-          if (o < 0) return HQPKKT_E_INTERN;  // (a border row of a fused front belongs to a fused ancestor)
-          bpos[t * ST_CS + i] = o * ST_XS + (ei - an.piv_start[nodes[o]]);
-        }
-      std::vector<int> up;  // level by level, leaves first; inside a level the largest fronts first, as in `nodes`
-      for (int l = lt; l < an.nlevels; l++)
-        for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; q++) up.push_back(S.level_nodes[q]);
-      // One launch for both sweeps needs ALL its fronts resident at once (the forward sweep of a front waits for
-      // fronts behind it in the launch): safe only while nothing else competes for the CUs.  Several systems in flight
-      // on one GPU (bench.py's concurrent systems, scenario trees) could starve each other, so the form in use is the
-      // split one - a front waits only for fronts before it - and the fused launch is an option (HQPKKT_SOLVE_TOP_FUSED,
-      // 17 us less per solve: M and L21 are read once).
-      h->top_split = (int)nodes.size() > ST_MAXFRONTS || getenv("HQPKKT_SOLVE_TOP_FUSED") == nullptr;
-      if ((e = h->td.top_nodes.upload(nodes)) || (e = h->td.top_idx.upload(idx)) || (e = h->td.top_bpos.upload(bpos)) || (e = h->td.top_up.upload(up)) ||
-          (e = h->td.top_x.alloc(2 * nodes.size() * (size_t)(ST_CS + ST_XS))))
-        return e;
-      h->top_n = (int)nodes.size(), h->top_lt = lt, h->top_ns = ok3 ? 3 : 4, h->top_lds = st_top_lds_bytes(maxp, h->top_ns);
-      if ((e = reset_solve_top(h))) return e;
-    }
+  if (P.top.n > 0 &&
+      ((e = h->td.top_nodes.upload(P.top.nodes)) || (e = h->td.top_idx.upload(P.top.idx)) || (e = h->td.top_bpos.upload(P.top.bpos)) ||
+       (e = h->td.top_up.upload(P.top.up)) || (e = h->td.top_x.alloc(2 * (size_t)P.top.n * (ST_CS + ST_XS)))))
+    return e;
+  return P.small_tree || P.top.n > 0 ? reset_solve_top(h) : 0;
+}
+
+// The dynamic-LDS limits of the kernels.  The attribute is state of the PROCESS, not of the handle: a second handle with
+// smaller fronts must not lower the limit under one that still launches with more (several plugins in one host, the
+// bench's concurrent systems): keep the largest value ever asked for, under a mutex ... and hipFuncSetAttribute acts on
+// the CURRENT device: the largest values are kept per device
+static int raise_lds_limits(hqpkkt_t *h) {
+  static std::mutex attr_mutex;
+  struct PerDev { size_t panel = 0, bwdb = 0, blk = 0, top = 0; };
+  static PerDev per_dev[64];
+  if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
+  std::lock_guard<std::mutex> lk(attr_mutex);
+  PerDev &a = per_dev[h->opts.device];
+  const TreePlan &P = h->plan;
+  int e;
+  if (P.top.lds > a.top) {
+    for (int i = 0; i < 2; i++)
+      for (int mode = 0; mode < 3; mode++)
+        if ((e = set_max_lds((const void *)top_kernels[i][mode], std::min(P.top.lds, st_top_lds_bytes(top_maxp[i], 3 + i))))) return e;
+    a.top = P.top.lds;
   }
-  {
-    // the attribute is state of the PROCESS, not of the handle: a second handle with smaller fronts must
-    // not lower the limit under one that still launches with more (several plugins in one host, the
-    // bench's concurrent systems): keep the largest value ever asked for, under a mutex
-    // ... and hipFuncSetAttribute acts on the CURRENT device: the largest values are kept per device
-    static std::mutex attr_mutex;
-    struct PerDev { size_t panel = 0, bwdb = 0, blk = 0, top = 0; };
-    static PerDev per_dev[64];
-    if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
-    std::lock_guard<std::mutex> lk(attr_mutex);
-    size_t &a_panel = per_dev[h->opts.device].panel, &a_bwdb = per_dev[h->opts.device].bwdb,
-           &a_blk = per_dev[h->opts.device].blk, &a_top = per_dev[h->opts.device].top;
-    if (h->top_lds > a_top) {
-      const int l3 = (int)std::min(h->top_lds, st_top_lds_bytes(176, 3)), l4 = (int)std::min(h->top_lds, st_top_lds_bytes(160, 4));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<3, 11, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, l3));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<3, 11, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, l3));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<3, 11, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, l3));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<4, 10, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, l4));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<4, 10, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, l4));
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_top<4, 10, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, l4));
-      a_top = h->top_lds;
-    }
-    if (lds_blk > a_blk) {
-      HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<8, 6, 144, 2, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(lds_blk, fb_lds_bytes(128))));
-      HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 8, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_blk));
-      HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 6, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(lds_blk, fb_lds_bytes(176))));
-      HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(lds_blk, fb_lds_bytes(160))));
-      a_blk = lds_blk;
-    }
-    if (h->lds_panel > a_panel) {
-      HIPCHK(hipFuncSetAttribute((const void *)k_panel_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_panel));
-      a_panel = h->lds_panel;
-    }
-    if (h->lds_bwdb > a_bwdb) {
-      HIPCHK(hipFuncSetAttribute((const void *)k_solve_bwd_b, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bwdb));
-      a_bwdb = h->lds_bwdb;
-    }
+  if (P.lds_blk > a.blk) {
+    if ((e = raise_fb_lds(P.lds_blk))) return e;
+    a.blk = P.lds_blk;
   }
-  {
-    const double rows = 2.0 * n + me + m;  // Q, A', C' per x row; A, C rows
-    const double nnz = (double)an.Qfull.col.size() + 2.0 * an.A.col.size() + 2.0 * an.C.col.size();
-    h->short_rows = rows > 0 && nnz / rows < 8.0;
+  if (P.lds_panel > a.panel) {
+    if ((e = set_max_lds((const void *)k_panel_solve, P.lds_panel))) return e;
+    a.panel = P.lds_panel;
   }
+  if (P.lds_bwdb > a.bwdb) {
+    if ((e = set_max_lds((const void *)k_solve_bwd_b, P.lds_bwdb))) return e;
+    a.bwdb = P.lds_bwdb;
+  }
+  return 0;
+}
+
+int upload(hqpkkt_t *h) {
+  int e;
+  if ((e = ensure_device(h)) || (e = upload_structure(h)) || (e = upload_terms_and_signs(h)) || (e = alloc_numeric(h)) ||
+      (e = alloc_staging(h)) || (e = upload_plan(h)) || (e = raise_lds_limits(h)))
+    return e;
+  const Analysis &an = h->an;
+  const double rows = 2.0 * an.n + an.me + an.m;  // Q, A', C' per x row; A, C rows
+  const double nnz = (double)an.Qfull.col.size() + 2.0 * an.A.col.size() + 2.0 * an.C.col.size();
+  h->short_rows = rows > 0 && nnz / rows < 8.0;
   h->st.bytes_panels = (long long)sizeof(double) * (an.panel_elems + an.x_elems);
   h->st.bytes_updates = (long long)sizeof(double) * an.upd_elems;
   h->uploaded = true;
   return 0;
 }
+
 
 
 // (HQPKKT_NO_HOST_KERNEL_COPIES=1: the copy engine as before, for same-box comparisons)
@@ -430,273 +413,260 @@ void unstage(hqpkkt_t *h, double *dx, double *dy, double *dz, double *dw) {
   if (dw && m) std::memcpy(dw, q + n + me + m, sizeof(double) * m);
 }
 
-static const int FWD_FUSED_MAX_SLABS = 1024;  // above: forward step of a level in two launches
-static const int SU1_MAX = 768;  // levels of at most this many 64 x 64 update tiles run k_schur_update with 32 x 16 per wave
 static_assert(FS_MAXP == kktdev::SMALL_PIVOTS && FS_MAXB == kktdev::SMALL_BORDER, "small-supernode kernels and schedule disagree");
 // ------------------------------------------------------------ numeric phases
-// phases: 1 = assemble + this rank's subtrees, 2 = replicated top of the tree
-// (3 = everything, the single-rank case)
+// run_factor and run_step walk the handle's plan (tree_plan.hpp): which kernel instance a level takes, its grid and LDS
+// were decided there.
 // (HQPKKT_NO_FUSED_VECTORS=1: the vector work around the sweeps and the assembly as the separate launches of round 5 - the
 // comparison the bit-identity test makes)
 static bool no_fused_vectors() { return getenv("HQPKKT_NO_FUSED_VECTORS") != nullptr; }
-static int run_factor(hqpkkt_t *h, const double *z, const double *w, int phases) {
+
+// The pointer list the factor kernels share (k_factor_blk, k_factor_diag, k_factor_diag_small), written once: `tail` is
+// what a kernel takes behind it.
+struct FactorArgs {
+  DevTree T;
+  double *panel, *dinv;
+  int *ptype, *lperm;
+  const signed char *esign;
+  double *linv;
+  const long long *linv_off;
+  double alpha, pivot_eps;
+  const unsigned long long *kmax_bits;
+  int *counters;
+  double *upd;
+};
+template <class K, class... Tail>
+static void launch_factor(K kernel, int grid, int block, size_t lds, hipStream_t s, const FactorArgs &a, const int *nodes, Tail... tail) {
+  kernel<<<grid, block, lds, s>>>(a.T, nodes, a.panel, a.dinv, a.ptype, a.lperm, a.esign, a.linv, a.linv_off, a.alpha, a.pivot_eps, a.kmax_bits,
+                                  a.counters, a.upd, tail...);
+}
+static FactorArgs factor_args(hqpkkt_t *h) {
+  const double alpha = h->opts.tol * 0.6403882032022076;  // tol (1+sqrt 17)/8, hqp/spBKP.C:392
+  return FactorArgs{h->td.tree(), h->td.panel.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p,
+                    alpha, h->opts.pivot_eps, h->td.bits.p, h->td.flags.p + 1, h->td.upd.p};
+}
+
+// clears the panel arena and the status words, then the entries of the matrix into the panels
+static int assemble(hqpkkt_t *h, const double *z, const double *w) {
   Analysis &an = h->an;
+  TreeDev &d = h->td;
   hipStream_t s = h->stream;
   const int m = an.m, nent = (int)an.ent_a.size();
-  DevTree T = h->td.tree();
-  if (phases & 1) {
-    if (an.shard_count <= 1) {  // the panel arena, and the status words, counters and the two maxima
-      KLAUNCH(h, KC_ASSEMBLE, k_clear<<<(int)std::max<long long>(1, std::min<long long>(2048, (an.panel_elems / 2 + 1023) / 1024)), 256, 0, s>>>(h->td.panel.p, an.panel_elems, h->td.flags.p));
-    } else {  // only the blocks this rank writes
-      const int np = (int)an.zero_panel.size() / 2;
-      if (np) k_zero_ranges<<<dim3(512, np), 256, 0, s>>>(h->td.panel.p, h->td.zero_panel.p);
-      k_clear<<<1, 256, 0, s>>>(nullptr, 0, h->td.flags.p);
-    }
-    if (!h->capturing) HIPCHK(hipEventRecord(h->ev0, s));
-    if (m > 0 && (h->td.simple_src.count || no_fused_vectors()))
-      KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(an.mode, m, an.n + an.me, z, w, h->td.wt.p, h->td.sc.p, h->td.flags.p));
-    if (h->td.simple_src.count) {  // FULL: one pass
-      KLAUNCH(h, KC_ASSEMBLE, k_assemble_simple<<<std::min(nblk(nent), 2048), 256, 0, s>>>(
-                                  nent, h->td.simple_src.p, h->td.simple_wi.p, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p,
-                                  h->td.vals.p, h->td.wt.p, h->td.sc.p, h->td.panel.p, h->td.bits.p, h->td.tree_words.p + 1));
-    } else {
-      // weights + entry values, scales + scatter: one launch each (kernels.hip.h, k_wt_entry / k_scale_scatter)
-      if (no_fused_vectors()) {
-        KLAUNCH(h, KC_ASSEMBLE, k_entry_values<<<nblk(nent), 256, 0, s>>>(nent, h->td.term_ptr.p, h->td.terms.p, h->td.vals.p, h->td.wt.p,
-                                                  h->td.ent_val.p, h->td.tree_words.p + 1));
-        if (an.mode == 1 && an.n > 0)
-          KLAUNCH(h, KC_ASSEMBLE, k_red_scale<<<nblk(an.n), 256, 0, s>>>(an.n, h->td.diag_ent.p, h->td.ent_val.p, h->td.sc.p));
-        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<std::min(nblk(nent), 2048), 256, 0, s>>>(nent, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p, h->td.ent_val.p,
-                                             h->td.sc.p, h->td.panel.p, h->td.bits.p));
-      } else {
-      KLAUNCH(h, KC_ASSEMBLE, k_wt_entry<<<nblk(nent) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(an.mode, m, an.n + an.me, nent, nblk(nent), z, w, h->td.wt.p, h->td.sc.p,
-                                                h->td.flags.p, h->td.term_ptr.p, h->td.terms.p, h->td.vals.p, h->td.ent_val.p, h->td.tree_words.p + 1));
-      const int nsc = std::min(nblk(nent), 2048);
-      if (an.mode == 1 && an.n > 0)
-        KLAUNCH(h, KC_ASSEMBLE, k_scale_scatter<<<nsc + nblk(an.n), 256, 0, s>>>(an.n, nent, nsc, h->td.diag_ent.p, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p,
-                                                 h->td.ent_val.p, h->td.sc.p, h->td.panel.p, h->td.bits.p));
-      else
-        KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<nsc, 256, 0, s>>>(nent, h->td.ent_a.p, h->td.ent_b.p, h->td.ent_dst.p, h->td.ent_val.p,
-                                             h->td.sc.p, h->td.panel.p, h->td.bits.p));
-      }
-    }
-    if (!h->capturing) HIPCHK(hipEventRecord(h->ev1, s));
+  if (an.shard_count <= 1) {  // the panel arena, and the status words, counters and the two maxima
+    KLAUNCH(h, KC_ASSEMBLE, k_clear<<<(int)std::max<long long>(1, std::min<long long>(2048, (an.panel_elems / 2 + 1023) / 1024)), 256, 0, s>>>(d.panel.p, an.panel_elems, d.flags.p));
+  } else {  // only the blocks this rank writes
+    const int np = (int)an.zero_panel.size() / 2;
+    if (np) k_zero_ranges<<<dim3(512, np), 256, 0, s>>>(d.panel.p, d.zero_panel.p);
+    k_clear<<<1, 256, 0, s>>>(nullptr, 0, d.flags.p);
   }
-  const double alpha = h->opts.tol * 0.6403882032022076;  // tol (1+sqrt 17)/8, hqp/spBKP.C:392
+  if (!h->capturing) HIPCHK(hipEventRecord(h->ev0, s));
+  if (m > 0 && (d.simple_src.count || no_fused_vectors()))
+    KLAUNCH(h, KC_ASSEMBLE, k_weights<<<nblk(m), 256, 0, s>>>(an.mode, m, an.n + an.me, z, w, d.wt.p, d.sc.p, d.flags.p));
+  const int nsc = std::min(nblk(nent), 2048);
+  if (d.simple_src.count) {  // FULL: one pass
+    KLAUNCH(h, KC_ASSEMBLE, k_assemble_simple<<<nsc, 256, 0, s>>>(nent, d.simple_src.p, d.simple_wi.p, d.ent_a.p, d.ent_b.p, d.ent_dst.p, d.vals.p, d.wt.p,
+                                                                  d.sc.p, d.panel.p, d.bits.p, d.tree_words.p + 1));
+  } else if (no_fused_vectors()) {
+    KLAUNCH(h, KC_ASSEMBLE, k_entry_values<<<nblk(nent), 256, 0, s>>>(nent, d.term_ptr.p, d.terms.p, d.vals.p, d.wt.p, d.ent_val.p, d.tree_words.p + 1));
+    if (an.mode == 1 && an.n > 0) KLAUNCH(h, KC_ASSEMBLE, k_red_scale<<<nblk(an.n), 256, 0, s>>>(an.n, d.diag_ent.p, d.ent_val.p, d.sc.p));
+    KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<nsc, 256, 0, s>>>(nent, d.ent_a.p, d.ent_b.p, d.ent_dst.p, d.ent_val.p, d.sc.p, d.panel.p, d.bits.p));
+  } else {
+    // weights + entry values, scales + scatter: one launch each (kernels.hip.h, k_wt_entry / k_scale_scatter)
+    KLAUNCH(h, KC_ASSEMBLE, k_wt_entry<<<nblk(nent) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(an.mode, m, an.n + an.me, nent, nblk(nent), z, w, d.wt.p, d.sc.p, d.flags.p,
+                                                                                       d.term_ptr.p, d.terms.p, d.vals.p, d.ent_val.p, d.tree_words.p + 1));
+    if (an.mode == 1 && an.n > 0)
+      KLAUNCH(h, KC_ASSEMBLE, k_scale_scatter<<<nsc + nblk(an.n), 256, 0, s>>>(an.n, nent, nsc, d.diag_ent.p, d.ent_a.p, d.ent_b.p, d.ent_dst.p, d.ent_val.p, d.sc.p,
+                                                                            d.panel.p, d.bits.p));
+    else
+      KLAUNCH(h, KC_ASSEMBLE, k_scatter<<<nsc, 256, 0, s>>>(nent, d.ent_a.p, d.ent_b.p, d.ent_dst.p, d.ent_val.p, d.sc.p, d.panel.p, d.bits.p));
+  }
+  if (!h->capturing) HIPCHK(hipEventRecord(h->ev1, s));
+  return 0;
+}
+
+// one level of schedule `which`: small fronts, small blocks, pivot blocks, panel solve, updates
+static void factor_level(hqpkkt_t *h, int which, const LevelPlan &R, const FactorArgs &a, const TreeXchgF &txf) {
+  const TreeDev::DevSched &D = h->td.ds[which];
+  TreeDev &d = h->td;
+  hipStream_t s = h->stream;
+  const int *nodes = D.level_nodes.p + R.nodes_off;
+  if (R.fs_n > 0)
+    KLAUNCH(h, KC_FACTOR_DIAG, launch_factor(k_factor_diag_small<true>, R.fs_n, 64, R.fs_lds, s, a, nodes, d.xar.p, R.fs_ldp, R.fs_ldb, txf));
+  if (R.sm_n > 0)
+    KLAUNCH(h, KC_FACTOR_DIAG, launch_factor(k_factor_diag_small<false>, R.sm_n, 64, R.sm_lds, s, a, nodes + R.fs_n, d.xar.p, R.sm_ldp, 1, txf));
+  if (R.blk_n > 0)
+    KLAUNCH(h, KC_FACTOR_DIAG, launch_factor(fb_kernels[R.blk_inst], R.blk_n, R.blk_threads, R.blk_lds, s, a, nodes + R.fs_n + R.sm_n));
+  if (R.ps_grid > 0)
+    KLAUNCH(h, KC_PANEL_SOLVE, k_panel_solve<<<R.ps_grid, 256, h->plan.lds_panel, s>>>(a.T, D.slabs.p + 2 * (size_t)R.slabs_off, d.panel.p, d.xar.p, d.dinv.p, d.ptype.p,
+                                                                                    d.lperm.p, d.linv.p, d.linv_off.p, d.upd.p, R.ps_xps));
+  const int *tiles = D.upd_tiles.p + 3 * (size_t)R.tiles_off;
+  if (R.su_variant == 2)
+    KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<2><<<R.su_grid, 256, 0, s>>>(a.T, tiles, d.panel.p, d.xar.p, d.upd.p, R.su_xsu));
+  else if (R.su_variant == 1)
+    KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<1><<<R.su_grid, 256, 0, s>>>(a.T, tiles, d.panel.p, d.xar.p, d.upd.p, R.su_xsu));
+  if (R.big_n > 0)
+    KLAUNCH(h, KC_SCHUR_UPDATE, (k_schur_update_big<2, 2, 4, 4, 2, 2><<<R.big_n, 256, 0, s>>>(a.T, D.upd_tiles.p + 3 * (size_t)R.big_off, d.panel.p, d.xar.p, d.upd.p)));
+}
+
+// phases: 1 = assemble + this rank's subtrees, 2 = replicated top of the tree
+// (3 = everything, the single-rank case)
+static int run_factor(hqpkkt_t *h, const double *z, const double *w, int phases) {
+  const TreePlan &P = h->plan;
+  int e;
+  if ((phases & 1) && (e = assemble(h, z, w))) return e;
+  const FactorArgs a = factor_args(h);
+  const TreeXchgF txf{h->td.tree_u.p, h->an.upd_elems, h->td.tree_words.p + 1};
   for (int which = 0; which < 2; which++) {
-    if (!(phases & (1 << which))) continue;
-    const Analysis::Sched &S = an.sched[which];
-    const TreeDev::DevSched &D = h->td.ds[which];
-    if (S.nnodes == 0) continue;
-    const TreeXchgF txf{h->td.tree_u.p, an.upd_elems, h->td.tree_words.p + 1};
-    if (which == 0 && h->tree_factor) {  // a tree of small fronts: all levels in one launch
-      int ldp = 1, ldb = 1;
-      for (int l = 0; l < an.nlevels; l++) ldp = std::max(ldp, S.level_fs_p[l] | 1), ldb = std::max(ldb, S.level_fs_b[l]);
-      KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_diag_small<true, true><<<S.nnodes, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p, h->td.panel.p,
-                                               h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                               h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, ldb, txf)));
-      continue;
-    }
-    for (int l = 0; l < an.nlevels; l++) {
-      const int nn = S.level_ptr[l + 1] - S.level_ptr[l], nfs = S.level_fsmall[l], nsm = S.level_small[l];
-      if (nfs > 0) {  // small fronts: extend-add, pivot block, panel and update in one kernel
-        const int ldp = S.level_fs_p[l] | 1, ldb = S.level_fs_b[l];
-        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<true><<<nfs, 64, fs_lds_bytes(true, ldp, ldb), s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, ldb, txf));
-      }
-      if (nsm > 0) {
-        const int ldp = S.level_sm_p[l] | 1;
-        KLAUNCH(h, KC_FACTOR_DIAG, k_factor_diag_small<false><<<nsm, 64, fs_lds_bytes(false, ldp, 1), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p, h->td.xar.p, ldp, 1, txf));
-      }
-      if (nn > nfs + nsm) {
-        // the pivot blocks on the matrix pipe: 8 wavefronts (two workgroups per CU) for levels of <= 128 pivots, 12
-        // wavefronts beyond, each holding as many 16 x 16 blocks of the triangle as the level's largest front needs
-        const int lmp = h->level_maxp[which][l];
-        if (lmp <= 128)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<8, 6, 144, 2, FB_OWNSIMD><<<nn - nfs - nsm, 512, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p)));
-        else if (lmp <= 160)  // (55 blocks on 11 wavefronts: five per wavefront)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p)));
-        else if (lmp <= 176)  // (66 blocks of the triangle on 11 wavefronts: six per wavefront - 16 registers fewer than with eight, no scratch)
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 6, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p)));
-        else
-          KLAUNCH(h, KC_FACTOR_DIAG, (k_factor_blk<12, 8, 208, 3, FB_OWNSIMD><<<nn - nfs - nsm, 768, fb_lds_bytes(lmp), s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs + nsm, h->td.panel.p,
-                                                 h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.esign.p, h->td.linv.p, h->td.linv_off.p, alpha, h->opts.pivot_eps, h->td.bits.p,
-                                                 h->td.flags.p + 1, h->td.upd.p)));
-      }
-      const int ns = S.slab_ptr[l + 1] - S.slab_ptr[l];
-      // the work lists go over the XCDs in chunks of about half a front's items (kernels.hip.h, xcd_order; measured on C2:
-      // 1.875 -> 1.826 ms per factor + solve; whole fronts per chunk 1.830, contiguous ranges per XCD 1.915)
-      const int lmb = h->level_maxb[which][l];
-      const int xps = std::max(1, (lmb + 31) / 32);
-      const int xtt = (lmb + 63) / 64, xsu = std::max(1, xtt * (xtt + 1) / 4);
-      if (ns > 0)  // (the schedule lists 32-row slabs; the kernel takes 16 rows per workgroup)
-        KLAUNCH(h, KC_PANEL_SOLVE, k_panel_solve<<<2 * ns, 256, h->lds_panel, s>>>(T, D.slabs.p + 2 * (size_t)S.slab_ptr[l],
-                                                    h->td.panel.p, h->td.xar.p, h->td.dinv.p, h->td.ptype.p,
-                                                    h->td.lperm.p, h->td.linv.p, h->td.linv_off.p, h->td.upd.p, xps));
-      const int nt = S.upd_big_ptr[l] - S.upd_tile_ptr[l], ntb = S.upd_tile_ptr[l + 1] - S.upd_big_ptr[l];
-      // a wave holds 32 x 32 of a tile while a level fills the chip; 32 x 16 (two workgroups per tile) on the thin levels above
-      if (nt > 0 && nt > SU1_MAX)
-        KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<2><<<nt, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_tile_ptr[l],
-                                          h->td.panel.p, h->td.xar.p, h->td.upd.p, xsu));
-      else if (nt > 0)
-        KLAUNCH(h, KC_SCHUR_UPDATE, k_schur_update<1><<<2 * nt, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_tile_ptr[l],
-                                          h->td.panel.p, h->td.xar.p, h->td.upd.p, 2 * xsu));
-      if (ntb > 0)
-        KLAUNCH(h, KC_SCHUR_UPDATE, (k_schur_update_big<2, 2, 4, 4, 2, 2><<<ntb, 256, 0, s>>>(T, D.upd_tiles.p + 3 * (size_t)S.upd_big_ptr[l],
-                                          h->td.panel.p, h->td.xar.p, h->td.upd.p)));
-    }
+    if (!(phases & (1 << which)) || h->an.sched[which].nnodes == 0) continue;
+    if (which == 0 && P.tree_factor)  // a tree of small fronts: all levels in one launch
+      KLAUNCH(h, KC_FACTOR_DIAG, launch_factor(k_factor_diag_small<true, true>, h->an.sched[0].nnodes, 64, fs_lds_bytes(true, P.tree_ldp, P.tree_ldb), h->stream, a,
+                                               h->td.ds[0].level_nodes.p, h->td.xar.p, P.tree_ldp, P.tree_ldb, txf));
+    else
+      for (const LevelPlan &R : P.levels[which]) factor_level(h, which, R, a, txf);
   }
-  if (!h->capturing) HIPCHK(hipEventRecord(h->evs1, s));
+  if (!h->capturing) HIPCHK(hipEventRecord(h->evs1, h->stream));
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// The pointer list the forward kernels share (k_solve_fwd_small, k_solve_fwd), written once: `tail` is the exchange
+// arrays of the one-wavefront kernel.
+template <class K, class... Tail>
+static void launch_fwd(hqpkkt_t *h, K kernel, int grid, int block, const int *list, Tail... tail) {
+  TreeDev &d = h->td;
+  kernel<<<grid, block, 0, h->stream>>>(d.tree(), list, d.panel.p, d.linv.p, d.linv_off.p, d.dinv.p, d.ptype.p, d.lperm.p, d.rhs.p, d.xsol.p, d.ytmp.p, d.cb.p,
+                                        tail...);
+}
+// ... and k_solve_bwd_small<TREE> of a level, or of the whole tree
+template <class K>
+static void launch_bwd_small(hqpkkt_t *h, K kernel, int grid, const int *nodes, const TreeXchg &tx) {
+  TreeDev &d = h->td;
+  kernel<<<grid, 64, 0, h->stream>>>(d.tree(), nodes, d.panel.p, d.linv.p, d.linv_off.p, d.lperm.p, d.xsol.p, tx);
+}
+static TreeXchg tree_xchg(hqpkkt_t *h) {
+  return TreeXchg{h->td.tree_x.p, h->td.tree_x.p + 2 * h->an.cb_elems, h->an.cb_elems, h->an.dim, h->td.tree_words.p, h->td.flags.p};
+}
+
+static void forward_level(hqpkkt_t *h, int which, const LevelPlan &R, const TreeXchg &tx) {
+  const TreeDev::DevSched &D = h->td.ds[which];
+  TreeDev &d = h->td;
+  hipStream_t s = h->stream;
+  const int *nodes = D.level_nodes.p + R.nodes_off, *gslabs = D.gslabs.p + 2 * (size_t)R.gslabs_off;
+  if (R.fwd_small_n > 0) KLAUNCH(h, KC_SOLVE_FWD, launch_fwd(h, k_solve_fwd_small<false>, R.fwd_small_n, 64, nodes, tx));
+  if (R.fwd_form == FWD_ONE) {
+    KLAUNCH(h, KC_SOLVE_FWD, launch_fwd(h, k_solve_fwd, R.fwd_grid, 256, gslabs));
+  } else if (R.fwd_form == FWD_AB) {
+    KLAUNCH(h, KC_SOLVE_FWD, k_solve_fwd_a<<<R.fwd_a_grid, 256, 0, s>>>(d.tree(), nodes + R.fwd_small_n, d.linv.p, d.linv_off.p, d.dinv.p, d.ptype.p, d.lperm.p, d.rhs.p,
+                                                                       d.xsol.p, d.ytmp.p, d.cb.p));
+    KLAUNCH(h, KC_SOLVE_FWD, k_solve_fwd_b<<<R.fwd_grid, 256, 0, s>>>(d.tree(), gslabs, d.panel.p, d.ytmp.p, d.cb.p));
+  }
+}
+static void backward_level(hqpkkt_t *h, int which, const LevelPlan &R, const TreeXchg &tx) {
+  const TreeDev::DevSched &D = h->td.ds[which];
+  TreeDev &d = h->td;
+  hipStream_t s = h->stream;
+  const int *nodes = D.level_nodes.p + R.nodes_off;
+  if (R.bwd_small_n > 0) KLAUNCH(h, KC_SOLVE_BWD, launch_bwd_small(h, k_solve_bwd_small<false>, R.bwd_small_n, nodes, tx));
+  if (R.bwd_a_grid <= 0) return;
+  // (one workgroup per front doing both steps was measured slower: L21' x needs the
+  // column blocks spread over the chip)
+  KLAUNCH(h, KC_SOLVE_BWD, k_solve_bwd_b<<<R.bwd_b_grid, 256, h->plan.lds_bwdb, s>>>(d.tree(), D.cblks.p + 2 * (size_t)R.cblks_off, d.panel.p, d.xsol.p, d.vtmp.p));
+  KLAUNCH(h, KC_SOLVE_BWD, k_solve_bwd_a<<<R.bwd_a_grid, 256, 0, s>>>(d.tree(), nodes + R.bwd_small_n, d.linv.p, d.linv_off.p, d.lperm.p, d.vtmp.p, d.xsol.p));
+}
+// the sweeps of schedule `which` below the fused top: one launch each for a tree of small fronts, else level by level
+static void forward(hqpkkt_t *h, int which) {
+  const TreeXchg tx = tree_xchg(h);
+  if (which == 0 && h->plan.small_tree)
+    KLAUNCH(h, KC_SOLVE_FWD, launch_fwd(h, k_solve_fwd_small<true>, h->an.sched[0].nnodes, 64, h->td.ds[0].level_nodes.p, tx));
+  else
+    for (const LevelPlan &R : h->plan.levels[which]) forward_level(h, which, R, tx);
+}
+static void backward(hqpkkt_t *h, int which) {
+  const TreeXchg tx = tree_xchg(h);
+  const std::vector<LevelPlan> &L = h->plan.levels[which];
+  if (which == 0 && h->plan.small_tree)
+    KLAUNCH(h, KC_SOLVE_BWD, launch_bwd_small(h, k_solve_bwd_small<true>, h->an.sched[0].nnodes, h->td.tree_down.p, tx));
+  else
+    for (size_t l = L.size(); l-- > 0;) backward_level(h, which, L[l], tx);
+}
+
+// the top levels, up and down: one launch, or one per sweep (k_solve_top)
+static void solve_top(hqpkkt_t *h) {
+  const TreePlan::Top &P = h->plan.top;
+  TreeDev &d = h->td;
+  TopArgs ta{d.top_nodes.p, d.top_idx.p, d.top_bpos.p, d.top_x.p, d.top_x.p + 2 * (size_t)P.n * ST_CS, d.tree_words.p, P.n, h->top_stamps};
+  auto launch = [&](int mode, const int *nodes) {
+    ta.nodes = nodes;
+    KLAUNCH(h, KC_SOLVE_TOP, top_kernels[P.ns - 3][mode]<<<P.n, ST_THREADS, P.lds, h->stream>>>(d.tree(), ta, d.panel.p, d.linv.p, d.linv_off.p, d.dinv.p, d.ptype.p, d.lperm.p,
+                                                                                            d.rhs.p, d.xsol.p, d.cb.p, d.flags.p));
+  };
+  if (!P.split)
+    launch(0, d.top_nodes.p);
+  else
+    launch(1, d.top_up.p), launch(2, d.top_nodes.p);
+}
+
+// the right-hand side in elimination order, scaled
+static void rhs(hqpkkt_t *h, const Vecs &v) {
+  Analysis &an = h->an;
+  TreeDev &d = h->td;
+  hipStream_t s = h->stream;
+  const int n = an.n, me = an.me, m = an.m, dim = an.dim;
+  if (an.mode == 0) {
+    KLAUNCH(h, KC_VECTOR, k_rhs_full<<<nblk(dim), 256, 0, s>>>(n, me, m, d.q2e.p, d.sc.p, v.z, v.r1, v.r2, v.r3, v.r4, d.rhs.p, d.tree_words.p));
+  } else if (no_fused_vectors()) {
+    if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, d.wt.p, v.r3, v.r4, d.tz.p));
+    KLAUNCH(h, KC_VECTOR, k_rhs_red<<<nblk(dim), 256, 0, s>>>(n, me, d.q2e.p, d.sc.p, d.CT.ptr.p, d.CT.col.p, d.CT.src.p, d.vals.p, d.tz.p, v.r1, v.r2, d.rhs.p,
+                                                             d.tree_words.p));
+  } else {
+    // (tz and the right-hand side that needs it in one launch: kernels.hip.h, k_rhs_red_t; HQPKKT_NO_FUSED_VECTORS=1: two)
+    KLAUNCH(h, KC_VECTOR, k_rhs_red_t<<<nblk(dim) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(n, me, m, nblk(dim), d.q2e.p, d.sc.p, d.CT.ptr.p, d.CT.col.p, d.CT.src.p, d.vals.p,
+                                                                                     v.w, d.wt.p, v.r3, v.r4, d.tz.p, v.r1, v.r2, d.rhs.p, d.tree_words.p));
+  }
+}
+
+// unscale + scatter of the solution into dx, dy; dz and dw from dx
+static void unpack(hqpkkt_t *h, const Vecs &v) {
+  Analysis &an = h->an;
+  TreeDev &d = h->td;
+  hipStream_t s = h->stream;
+  const int n = an.n, me = an.me, m = an.m, dim = an.dim;
+  if (an.mode == 0) {
+    KLAUNCH(h, KC_VECTOR, k_unpack_full<<<nblk(dim), 256, 0, s>>>(n, me, m, d.q2e.p, d.sc.p, d.xsol.p, v.dx, v.dy, v.dz));
+    if (m > 0) KLAUNCH(h, KC_VECTOR, k_dw<<<nblk(m), 256, 0, s>>>(m, d.C.ptr.p, d.C.col.p, d.C.src.p, d.vals.p, v.dx, v.r3, v.z, v.w, v.r4, v.dz, v.dw));
+  } else if (no_fused_vectors()) {
+    KLAUNCH(h, KC_VECTOR, k_unpack_red<<<nblk(dim), 256, 0, s>>>(n, me, d.q2e.p, d.sc.p, d.xsol.p, v.dx, v.dy));
+    if (m > 0)
+      KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, d.C.ptr.p, d.C.col.p, d.C.src.p, d.vals.p, v.dx, d.wt.p, d.tz.p, v.r3, v.dz, v.dw));
+  } else {
+    // (dx, dy and the dz, dw that need dx in one launch: kernels.hip.h, k_unpack_dzdw)
+    const int nb_dzdw = m > 0 ? nblk(m) : 0;
+    KLAUNCH(h, KC_VECTOR, k_unpack_dzdw<<<nb_dzdw + nblk(dim), 256, 0, s>>>(n, me, m, nb_dzdw, d.q2e.p, d.sc.p, d.xsol.p, v.dx, v.dy, d.C.ptr.p, d.C.col.p, d.C.src.p,
+                                                                          d.vals.p, d.wt.p, d.tz.p, v.r3, v.dz, v.dw));
+  }
 }
 
 // phases: 1 = right-hand side + forward sweep over this rank's subtrees,
 // 2 = forward / backward over the replicated top, backward over the subtrees,
 // 4 = unscale + scatter of the solution (7 = everything, the single-rank case)
 static int run_step(hqpkkt_t *h, const Vecs &v, int phases) {
-  Analysis &an = h->an;
-  hipStream_t s = h->stream;
-  const int n = an.n, me = an.me, m = an.m, dim = an.dim;
-  DevTree T = h->td.tree();
-  auto forward = [&](int which) -> int {
-    const Analysis::Sched &S = an.sched[which];
-    const TreeDev::DevSched &D = h->td.ds[which];
-    const TreeXchg tx{h->td.tree_x.p, h->td.tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->td.tree_words.p, h->td.flags.p};
-    if (which == 0 && h->small_tree) {  // all levels in one launch
-      KLAUNCH(h, KC_SOLVE_FWD,
-              k_solve_fwd_small<true><<<S.nnodes, 64, 0, s>>>(T, D.level_nodes.p, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p,
-                                                              h->td.lperm.p, h->td.rhs.p, h->td.xsol.p, h->td.ytmp.p, h->td.cb.p, tx));
-      return 0;
-    }
-    const int lend = which == 0 && h->top_n > 0 ? h->top_lt : an.nlevels;  // (the levels above: k_solve_top)
-    for (int l = 0; l < lend && S.nnodes; l++) {
-      const int nn = S.level_ptr[l + 1] - S.level_ptr[l], nfs = S.level_fsmall[l];
-      if (nfs > 0)
-        KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p, h->td.linv.p,
-                                                     h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p,
-                                                     h->td.xsol.p, h->td.ytmp.p, h->td.cb.p, tx));
-      const int ng = S.gslab_ptr[l + 1] - S.gslab_ptr[l];  // (front, 64-row slab), at least one per front
-      if (ng > 0 && ng <= FWD_FUSED_MAX_SLABS)  // a handful of fronts: the launch is what costs
-        KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->td.panel.p, h->td.linv.p,
-                                               h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p,
-                                               h->td.xsol.p, h->td.ytmp.p, h->td.cb.p));
-      else if (ng > 0) {  // thousands of slabs: M once per front, then the slabs
-        KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.linv.p,
-                                                 h->td.linv_off.p, h->td.dinv.p, h->td.ptype.p, h->td.lperm.p,
-                                                 h->td.rhs.p, h->td.xsol.p, h->td.ytmp.p, h->td.cb.p));
-        KLAUNCH(h, KC_SOLVE_FWD,
-                k_solve_fwd_b<<<ng, 256, 0, s>>>(T, D.gslabs.p + 2 * (size_t)S.gslab_ptr[l], h->td.panel.p,
-                                                 h->td.ytmp.p, h->td.cb.p));
-      }
-    }
-    return 0;
-  };
-  auto backward = [&](int which) -> int {
-    const Analysis::Sched &S = an.sched[which];
-    const TreeDev::DevSched &D = h->td.ds[which];
-    const TreeXchg tx{h->td.tree_x.p, h->td.tree_x.p + 2 * an.cb_elems, an.cb_elems, an.dim, h->td.tree_words.p, h->td.flags.p};
-    if (which == 0 && h->small_tree) {
-      KLAUNCH(h, KC_SOLVE_BWD, k_solve_bwd_small<true><<<S.nnodes, 64, 0, s>>>(T, h->td.tree_down.p, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, h->td.lperm.p,
-                                                                               h->td.xsol.p, tx));
-      return 0;
-    }
-    const int lbeg = which == 0 && h->top_n > 0 ? h->top_lt - 1 : an.nlevels - 1;
-    for (int l = lbeg; l >= 0 && S.nnodes; l--) {
-      const int nn = S.level_ptr[l + 1] - S.level_ptr[l], nfs = S.level_fsmall[l];
-      const int ncb = S.cblk_ptr[l + 1] - S.cblk_ptr[l];
-      if (nn <= 0) continue;
-      if (nfs > 0)
-        KLAUNCH(h, KC_SOLVE_BWD,
-                k_solve_bwd_small<false><<<nfs, 64, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l], h->td.panel.p, h->td.linv.p,
-                                                     h->td.linv_off.p, h->td.lperm.p, h->td.xsol.p, tx));
-      if (nn <= nfs) continue;
-      // (one workgroup per front doing both steps was measured slower: L21' x needs the
-      // column blocks spread over the chip)
-      KLAUNCH(h, KC_SOLVE_BWD,
-              k_solve_bwd_b<<<ncb, 256, h->lds_bwdb, s>>>(T, D.cblks.p + 2 * (size_t)S.cblk_ptr[l],
-                                                          h->td.panel.p, h->td.xsol.p, h->td.vtmp.p));
-      KLAUNCH(h, KC_SOLVE_BWD,
-              k_solve_bwd_a<<<nn - nfs, 256, 0, s>>>(T, D.level_nodes.p + S.level_ptr[l] + nfs, h->td.linv.p,
-                                               h->td.linv_off.p, h->td.lperm.p, h->td.vtmp.p, h->td.xsol.p));
-    }
-    return 0;
-  };
   if (phases & 1) {
-    if (an.mode == 0) {
-      KLAUNCH(h, KC_VECTOR, k_rhs_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->td.q2e.p, h->td.sc.p, v.z, v.r1, v.r2, v.r3, v.r4,
-                                           h->td.rhs.p, h->td.tree_words.p));
-    } else {
-      // (tz and the right-hand side that needs it in one launch: kernels.hip.h, k_rhs_red_t; HQPKKT_NO_FUSED_VECTORS=1: two)
-      if (no_fused_vectors()) {
-        if (m > 0) KLAUNCH(h, KC_VECTOR, k_red_t<<<nblk(m), 256, 0, s>>>(m, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p));
-        KLAUNCH(h, KC_VECTOR, k_rhs_red<<<nblk(dim), 256, 0, s>>>(n, me, h->td.q2e.p, h->td.sc.p, h->td.CT.ptr.p, h->td.CT.col.p,
-                                            h->td.CT.src.p, h->td.vals.p, h->td.tz.p, v.r1, v.r2, h->td.rhs.p,
-                                            h->td.tree_words.p));
-      } else
-        KLAUNCH(h, KC_VECTOR, k_rhs_red_t<<<nblk(dim) + (m > 0 ? nblk(m) : 0), 256, 0, s>>>(n, me, m, nblk(dim), h->td.q2e.p, h->td.sc.p, h->td.CT.ptr.p, h->td.CT.col.p,
-                                            h->td.CT.src.p, h->td.vals.p, v.w, h->td.wt.p, v.r3, v.r4, h->td.tz.p, v.r1, v.r2, h->td.rhs.p,
-                                            h->td.tree_words.p));
-    }
-    forward(0);
+    rhs(h, v);
+    forward(h, 0);
   }
   if (phases & 2) {
-    forward(1);
-    if (h->top_n > 0) {  // the top levels, up and down: one launch, or one per sweep (k_solve_top)
-      TopArgs ta{h->td.top_nodes.p, h->td.top_idx.p, h->td.top_bpos.p, h->td.top_x.p, h->td.top_x.p + 2 * (size_t)h->top_n * ST_CS, h->td.tree_words.p, h->top_n, h->top_stamps};
-#define TOP_LAUNCH(NS, NU, MODE)                                                                                                          \
-  KLAUNCH(h, KC_SOLVE_TOP, (k_solve_top<NS, NU, MODE><<<h->top_n, ST_THREADS, h->top_lds, s>>>(T, ta, h->td.panel.p, h->td.linv.p, h->td.linv_off.p, \
-                                                            h->td.dinv.p, h->td.ptype.p, h->td.lperm.p, h->td.rhs.p, h->td.xsol.p, h->td.cb.p, h->td.flags.p)))
-      if (!h->top_split) {
-        if (h->top_ns == 3) TOP_LAUNCH(3, 11, 0); else TOP_LAUNCH(4, 10, 0);
-      } else {
-        ta.nodes = h->td.top_up.p;
-        if (h->top_ns == 3) TOP_LAUNCH(3, 11, 1); else TOP_LAUNCH(4, 10, 1);
-        ta.nodes = h->td.top_nodes.p;
-        if (h->top_ns == 3) TOP_LAUNCH(3, 11, 2); else TOP_LAUNCH(4, 10, 2);
-      }
-#undef TOP_LAUNCH
-    }
-    backward(1);
-    backward(0);
-    if (an.shard_count > 1)  // leave only this rank's share for the all-reduce
-      KLAUNCH(h, KC_VECTOR, k_mask_vector<<<nblk(dim), 256, 0, s>>>(dim, h->td.keep_e.p, h->td.xsol.p));
+    forward(h, 1);
+    if (h->plan.top.n > 0) solve_top(h);
+    backward(h, 1);
+    backward(h, 0);
+    if (h->an.shard_count > 1)  // leave only this rank's share for the all-reduce
+      KLAUNCH(h, KC_VECTOR, k_mask_vector<<<nblk(h->an.dim), 256, 0, h->stream>>>(h->an.dim, h->td.keep_e.p, h->td.xsol.p));
   }
-  if (phases & 4) {
-    if (an.mode == 0) {
-      KLAUNCH(h, KC_VECTOR, k_unpack_full<<<nblk(dim), 256, 0, s>>>(n, me, m, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy,
-                                              v.dz));
-      if (m > 0)
-        KLAUNCH(h, KC_VECTOR, k_dw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx, v.r3,
-                                     v.z, v.w, v.r4, v.dz, v.dw));
-    } else {
-      // (dx, dy and the dz, dw that need dx in one launch: kernels.hip.h, k_unpack_dzdw)
-      const int nb_dzdw = m > 0 ? nblk(m) : 0;
-      if (no_fused_vectors()) {
-        KLAUNCH(h, KC_VECTOR, k_unpack_red<<<nblk(dim), 256, 0, s>>>(n, me, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy));
-        if (m > 0)
-          KLAUNCH(h, KC_VECTOR, k_red_dzdw<<<nblk(m), 256, 0, s>>>(m, h->td.C.ptr.p, h->td.C.col.p, h->td.C.src.p, h->td.vals.p, v.dx,
-                                             h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));
-      } else
-      KLAUNCH(h, KC_VECTOR, k_unpack_dzdw<<<nb_dzdw + nblk(dim), 256, 0, s>>>(n, me, m, nb_dzdw, h->td.q2e.p, h->td.sc.p, h->td.xsol.p, v.dx, v.dy, h->td.C.ptr.p,
-                                           h->td.C.col.p, h->td.C.src.p, h->td.vals.p, h->td.wt.p, h->td.tz.p, v.r3, v.dz, v.dw));
-    }
-  }
+  if (phases & 4) unpack(h, v);
   HIPCHK(hipGetLastError());
   return 0;
 }
+
 
 // The exchange steps of a sharded system: the handle's stream is
 // drained, the caller's collective runs, and the next phase starts afterwards.
@@ -817,14 +787,11 @@ int residual_launch(hqpkkt_t *h, const Vecs &v) {
     if (e1) return e1;
     staged_rows_products(h, v, &xcw, &cw, &CT, &C);
   }
-  if (h->short_rows)
-    KLAUNCH(h, KC_RESIDUAL, k_residual<4><<<std::min(nblk(4LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), CT, h->td.A.dev(), C, h->td.vals.p, v.z, v.w,
-        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq, xcw, cw));
-  else
-    KLAUNCH(h, KC_RESIDUAL, k_residual<16><<<std::min(nblk(16LL * ((long long)n + me + m)), 1024), 256, 0, s>>>(
-        n, me, m, h->td.Qf.dev(), h->td.AT.dev(), CT, h->td.A.dev(), C, h->td.vals.p, v.z, v.w,
-        v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq, xcw, cw));
+  const long long lpr = h->short_rows ? 4 : 16;  // lanes per CSR row
+  const auto kernel = h->short_rows ? &k_residual<4> : &k_residual<16>;
+  KLAUNCH(h, KC_RESIDUAL, kernel<<<std::min(nblk(lpr * ((long long)n + me + m)), 1024), 256, 0, s>>>(
+      n, me, m, h->td.Qf.dev(), h->td.AT.dev(), CT, h->td.A.dev(), C, h->td.vals.p, v.z, v.w,
+      v.r1, v.r2, v.r3, v.r4, v.dx, v.dy, v.dz, v.dw, o1, o2, o3, o4, rb_now, rb_next, x1, x2, ndyn, xq, xcw, cw));
   return 0;
 }
 int run_residual(hqpkkt_t *h, const Vecs &v, double *res, const OutPtrs *out) {
@@ -889,12 +856,13 @@ extern "C" {
 // forward done, border solution arrived, backward done (out: top_n x 8 doubles, [0] = tree level, [1..6] the times)
 int hqpkkt_debug_solve_top_stamps(hqpkkt_t *h, double *out, int cap) {
   if (!h || !out) return HQPKKT_E_NULL;
-  if (!h->factored || h->top_n <= 0) return HQPKKT_E_INTERN;
-  if (cap < h->top_n * 8) return HQPKKT_E_SIZES;
+  const int ntop = h->plan.top.n;  // (as it stands now: a poll that gives up below drops the top from the plan)
+  if (!h->factored || ntop <= 0) return HQPKKT_E_INTERN;
+  if (cap < ntop * 8) return HQPKKT_E_SIZES;
   HIPCHK(hipSetDevice(h->opts.device));
   DBuf<unsigned long long> st;
-  if (st.alloc(8 * (size_t)h->top_n)) return HQPKKT_E_MEM;
-  (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 8 * h->top_n);
+  if (st.alloc(8 * (size_t)ntop)) return HQPKKT_E_MEM;
+  (void)hipMemset(st.p, 0, sizeof(unsigned long long) * 8 * ntop);
   const bool graphs = h->use_graphs;
   h->use_graphs = false, h->top_stamps = st.p;
   Vecs v{};
@@ -911,14 +879,14 @@ int hqpkkt_debug_solve_top_stamps(hqpkkt_t *h, double *out, int cap) {
     int gave_up[XW_GAVE_UP + 1] = {};
     if (hipMemcpy(gave_up + XW_GAVE_UP, h->td.flags.p + XW_GAVE_UP, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || poll_fallback(h, gave_up)) e = HQPKKT_E_DEVICE;
   }
-  std::vector<unsigned long long> hs(8 * (size_t)h->top_n);
+  std::vector<unsigned long long> hs(8 * (size_t)ntop);
   if (!e && hipMemcpy(hs.data(), st.p, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost) != hipSuccess) e = HQPKKT_E_DEVICE;
   if (e) return e;
-  std::vector<int> nodes(h->top_n);
-  HIPCHK(hipMemcpy(nodes.data(), h->td.top_nodes.p, sizeof(int) * h->top_n, hipMemcpyDeviceToHost));
+  std::vector<int> nodes(ntop);
+  HIPCHK(hipMemcpy(nodes.data(), h->td.top_nodes.p, sizeof(int) * ntop, hipMemcpyDeviceToHost));
   unsigned long long t0 = ~0ULL;
-  for (int t = 0; t < h->top_n; t++) t0 = std::min(t0, hs[8 * (size_t)t]);
-  for (int t = 0; t < h->top_n; t++) {
+  for (int t = 0; t < ntop; t++) t0 = std::min(t0, hs[8 * (size_t)t]);
+  for (int t = 0; t < ntop; t++) {
     out[8 * t] = h->an.level[nodes[t]];
     // split form: the backward launch has its own start (slot 6) and static-data (slot 7) stamps; they are returned in
     // place of nothing - out[7] = start of the backward launch of this front
@@ -942,9 +910,9 @@ int hqpkkt_debug_ps_stamps(int *out) {
 #endif
 
 // One dense symmetric p x p block through the pivot-block kernel on its own (tests, tools): A row-major;
-// variant 0 = k_factor_blk as run_factor launches it (8 wavefronts for p <= 128, 12 beyond: five blocks per wavefront up to
-// 160 pivots, six up to 176, eight up to 192), 1 = k_factor_diag (p <= 128), 2 = the 12-wavefront instance with eight blocks whatever p,
-// 3 = the 12-wavefront instance with six blocks (p <= 176).  Out: the block's panel (p x p column-major: unit lower L11
+// variant 0 = k_factor_blk as run_factor launches it (the instance fb_instance(p) of tree_plan.hpp), 1 = k_factor_diag
+// (p <= 128), 2 = the 12-wavefront instance with eight blocks whatever p, 3 = the 12-wavefront instance with six blocks
+// (where it holds p).  Out: the block's panel (p x p column-major: unit lower L11
 // below the diagonal), D^-1 (2 p), pivot types, pivot order, M = L11^-1 (p x p column-major), the counters
 // (2x2 pivots, perturbed, slow pivots, ...), and the average time of `reps` launches of one workgroup.
 int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, double pivot_eps, int variant,
@@ -993,10 +961,12 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
   const size_t lds_old = (std::max<size_t>(ldm * mpd, 2 * FD_PLD * FD_PANEL) + 5 * 128 + 2 * mpd) * sizeof(double) + 2 * mpd * sizeof(int) + 16;
   if (variant == 1)
     HIPCHK(hipFuncSetAttribute((const void *)k_factor_diag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds_old, 64 * 1024)));
-  HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<8, 6, 144, 2, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(128)));
-  HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 8, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
-  HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, 6, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
-  HIPCHK(hipFuncSetAttribute((const void *)k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(192)));
+  if ((e = raise_fb_lds(fb_lds_bytes(fb_instances[FB_INSTANCES - 1].maxp)))) return e;
+  // variant 0: the rule's choice; 3: the six-block instance where it holds p; 2 (and 3 beyond): the eight-block instance.
+  // (The 12-wavefront instances lay their images out with the leading dimension of more than fb_instances[0].maxp pivots.)
+  const int inst = variant == 0 ? fb_instance(p) : variant == 3 && p <= fb_instances[2].maxp ? 2 : 3;
+  const size_t lds_blk = fb_lds_bytes(inst == 0 ? p : std::max(p, fb_instances[0].maxp + 1));
+  const FactorArgs a{T, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p, d_loff.p, alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p};
   EventOwner e0, e1;
   HIPCHK(hipEventCreate(&e0.h));
   HIPCHK(hipEventCreate(&e1.h));
@@ -1004,20 +974,9 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
   HIPCHK(hipEventRecord(e0, 0));
   for (int rp = 0; rp < reps; rp++) {
     if (variant == 1)
-      k_factor_diag<<<1, FD_THREADS, lds_old, 0>>>(T, d_nodes.p + rp, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p, d_loff.p,
-                                                  alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p);
-    else if (variant == 0 && p <= 128)
-      k_factor_blk<8, 6, 144, 2, FB_OWNSIMD><<<1, 512, fb_lds_bytes(p), 0>>>(T, d_nodes.p + rp, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p,
-                                                        d_loff.p, alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p);
-    else if (variant == 0 && p <= 160)  // (as run_factor chooses: five blocks per wavefront up to 160 pivots, six up to 176)
-      k_factor_blk<12, FB_NS160, 208, 3, FB_OWNSIMD><<<1, 768, fb_lds_bytes(std::max(p, 129)), 0>>>(T, d_nodes.p + rp, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p,
-                                                          d_loff.p, alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p);
-    else if ((variant == 0 || variant == 3) && p <= 176)
-      k_factor_blk<12, 6, 208, 3, FB_OWNSIMD><<<1, 768, fb_lds_bytes(std::max(p, 129)), 0>>>(T, d_nodes.p + rp, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p,
-                                                          d_loff.p, alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p);
+      launch_factor(k_factor_diag, 1, FD_THREADS, lds_old, 0, a, d_nodes.p + rp);
     else
-      k_factor_blk<12, 8, 208, 3, FB_OWNSIMD><<<1, 768, fb_lds_bytes(std::max(p, 129)), 0>>>(T, d_nodes.p + rp, d_P.p, d_dinv.p, d_pt.p, d_lp.p, d_sg.p, d_W.p,
-                                                          d_loff.p, alpha, pivot_eps, kb, d_flags.p + 1, d_upd.p);
+      launch_factor(fb_kernels[inst], 1, fb_instances[inst].threads, lds_blk, 0, a, d_nodes.p + rp);
   }
   HIPCHK(hipEventRecord(e1, 0));
   HIPCHK(hipDeviceSynchronize());

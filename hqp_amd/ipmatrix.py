@@ -168,6 +168,11 @@ class Hqp_IpMatrix:
     # -- the plugin interface ----------------------------------------------------
     def init(self, qp):
         """Hqp_IpSpBKP::init (hqp/Hqp_IpSpBKP.C:76-114): analyse, then update."""
+        self.analyze(qp)
+        self.update(qp)
+
+    def analyze(self, qp):
+        """The symbolic phase alone (hqpkkt_analyze): host work, no device."""
         self.n, self.me, self.m = qp.dims
         arrs = []
         for (p, i, _x) in (qp.Q, qp.A, qp.C):
@@ -176,7 +181,6 @@ class Hqp_IpMatrix:
         sbw = C.c_int()
         ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in arrs]
         _check(self._L.hqpkkt_analyze(self._h, self.n, self.me, self.m, *ptrs, C.byref(sbw)), "init")
-        self.update(qp)
 
     def update(self, qp):
         """Hqp_IpSpBKP::update (hqp/Hqp_IpSpBKP.C:117-136)."""
@@ -319,6 +323,26 @@ class Hqp_IpMatrix:
         names = ["elim", "piv_start", "npiv", "nborder", "parent", "level", "border_ptr",
                  "border_idx", "entry_row", "entry_col", "node_owner", "exchange_roots"]
         return {nm: self.debug(i) for i, nm in enumerate(names)}
+
+    PLAN_HEADER = ("top_n", "top_lt", "top_lds", "top_ns", "small_tree", "tree_factor", "top_split", "tree_ldp", "tree_ldb",
+                   "lds_panel", "lds_bwdb", "lds_blk", "nlevels", "record_ints", "nnodes0", "nnodes1")
+    PLAN_RECORD = ("n", "nodes_off", "fs_n", "fs_ldp", "fs_ldb", "fs_lds", "sm_n", "sm_ldp", "sm_lds", "blk_n", "blk_inst",
+                   "blk_threads", "blk_lds", "ps_grid", "ps_xps", "slabs_off", "su_n", "su_variant", "su_grid", "su_xsu", "tiles_off",
+                   "big_n", "big_off", "fwd_form", "fwd_small_n", "fwd_grid", "fwd_a_grid", "gslabs_off", "bwd_small_n", "bwd_b_grid",
+                   "bwd_a_grid", "cblks_off")
+    FWD_NONE, FWD_ONE, FWD_AB, FWD_TOP, FWD_TREE = range(5)
+
+    def launch_plan(self):
+        """What this handle of the tree engine launches (hqpkkt_debug_get 48, csrc/tree_plan.hpp): the header's values by
+        name and ``levels``: per schedule (this rank's subtrees, the replicated top) one dict per tree level.  After
+        the analysis, with or without a device; before the upload it is the plan the environment gives now."""
+        raw = [int(x) for x in self.debug(48)]
+        plan = dict(zip(self.PLAN_HEADER, raw))
+        assert plan["record_ints"] == len(self.PLAN_RECORD)
+        h, r, nl = len(self.PLAN_HEADER), len(self.PLAN_RECORD), plan["nlevels"]
+        plan["levels"] = [[dict(zip(self.PLAN_RECORD, raw[h + (w * nl + l) * r: h + (w * nl + l + 1) * r])) for l in range(nl)]
+                          for w in range(2)]
+        return plan
 
 
 class Hqp_IpSpBKP(Hqp_IpMatrix):

@@ -931,7 +931,24 @@ int hqpkkt_franke(hqpkkt_t *h, const hqpkkt_ip_opts *opts, const double *c, cons
  * 0 .. K eight ints - the tile edge T (0 where the stage keeps its dense block), the tiles stored, and three 64-bit counts
  * as (low, high) int pairs: the arena elements of the stage, the doubles one dense hand-over of the stage moves from the
  * caller's host block, the stage's share of the product's scratch; empty unless packing was analysed together with
- * HQPKKT_HESS_DENSE; valid after the analysis, without a device.
+ * HQPKKT_HESS_DENSE; valid after the analysis, without a device; 48 what a handle of the tree engine launches
+ * (csrc/tree_plan.hpp): the plan in use, or before the upload - without a device - the plan that the environment
+ * (HQPKKT_NO_TREE_SWEEPS, HQPKKT_NO_SOLVE_TOP, HQPKKT_SOLVE_TOP_FUSED) gives at the time of the call; 31 is answered from
+ * the same plan.  A header of 16 ints: [0..6] the seven ints of 31 (fronts of the fused top, its first level or the
+ * number of levels, its LDS bytes, ns of its instance, 1 for whole-tree sweeps of the solve, 1 for a whole-tree
+ * factorisation, 1 for the top's split form), [7] [8] ldp and ldb of the whole-tree factorisation, [9..11] dynamic LDS
+ * bytes of k_panel_solve, k_solve_bwd_b and the largest k_factor_blk launch, [12] tree levels L, [13] ints per record R
+ * (32), [14] [15] the fronts of the two schedules.  Then 2 L records of R ints, schedule 0 (this rank's subtrees) level
+ * 0 .. L-1, then schedule 1 (the replicated top); a count or grid of 0 means no launch:
+ *   [0] fronts of the level, [1] their offset in the schedule's level_nodes;
+ *   [2..5] k_factor_diag_small<true>: fronts, ldp, ldb, LDS bytes;  [6..8] k_factor_diag_small<false>: blocks, ldp, LDS bytes;
+ *   [9..12] k_factor_blk: fronts, instance (0 .. 3: up to 128, 160, 176, 192 pivots), threads, LDS bytes;
+ *   [13..15] k_panel_solve: grid, XCD chunk, offset (pairs) in slabs;
+ *   [16..20] k_schur_update: 64-tiles, variant (1 or 2), grid, XCD chunk as passed, offset (triples) in upd_tiles;
+ *   [21] [22] k_schur_update_big: 128-tiles, offset (triples) in upd_tiles;
+ *   [23..27] forward sweep: form (0 none, 1 k_solve_fwd, 2 k_solve_fwd_a + _b, 3 the level belongs to the fused top, 4 to
+ *   the whole-tree launches), fronts of k_solve_fwd_small, grid of k_solve_fwd or _b, grid of _a, offset (pairs) in gslabs;
+ *   [28..31] backward sweep: fronts of k_solve_bwd_small, grid of k_solve_bwd_b, grid of _a, offset (pairs) in cblks.
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_get(const hqpkkt_t *h, int what, int *out, long long *len);
 /* diagnostics of the solve's fused top (k_solve_top): one solve on the vectors of the last one with time stamps inside

@@ -1,6 +1,6 @@
 // CPU sanitizer target ("ASan/UBSan on the CPU backend"): the host-side C++ of the product -
 // analysis.cpp (RCM, nested dissection, symbolic fronts, shard plans) and staged_plan.cpp (stage detection, storage
-// plan, column cuts) - compiled with -fsanitize=address,undefined and run over generated structures: banded KKT
+// plan, column cuts) and tree_plan.hpp (the tree engine's launch rule) - compiled with -fsanitize=address,undefined and run over generated structures: banded KKT
 // systems (both plugins, three orderings, sharded over 1 / 3 / 8 ranks), the Prg_DID staircase, multistage DOCPs with
 // final / path constraints and a free initial state, dense hand-over, sharded STAGED plans.  tests/test_c_host.py
 // builds and runs it; any report of the sanitizers ends the process with a non-zero status.
@@ -10,6 +10,7 @@
 
 #include "../../hqp_amd/csrc/analysis.hpp"
 #include "../../hqp_amd/csrc/staged_plan.hpp"
+#include "../../hqp_amd/csrc/tree_plan.hpp"
 
 struct Csr {
   std::vector<int> p, i;
@@ -68,8 +69,37 @@ static void docp(int K, int nx, int nu, int path, int fin, bool fixed0, Csr &Q, 
     for (int j = 0; j < nu; j++) C.i.push_back(k * nz + nx + j), C.p.push_back((int)C.i.size()), m++;
 }
 
+// The launch plan of an analysed tree under every setting of the switches (tree_plan.hpp): the launches of a schedule
+// cover its fronts once per factorisation and once per sweep, and no launch asks for more LDS than the chip has.
+static int check_plans(const kktdev::Analysis &an) {
+  using namespace kktdev;
+  for (int bits = 0; bits < 16; bits++) {
+    const TreePlan P = tree_plan(an, TreeSwitches{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0});
+    if (P.err) return 1;
+    if ((bits & 8) && (P.small_tree || P.top.n)) return 2;
+    if (P.top.lds > LDS_LIMIT || P.lds_panel > LDS_LIMIT || P.lds_blk > LDS_LIMIT) return 3;
+    for (int w = 0; w < 2; w++) {
+      long long f = w == 0 && P.tree_factor ? an.sched[0].nnodes : 0, fw = w == 0 && P.small_tree ? an.sched[0].nnodes : 0, bw = fw;
+      if (w == 0) fw += P.top.n, bw += P.top.n;
+      for (const LevelPlan &R : P.levels[w]) {
+        f += R.fs_n + R.sm_n + R.blk_n;
+        fw += R.fwd_small_n + (R.fwd_form == FWD_ONE || R.fwd_form == FWD_AB ? R.n - R.fwd_small_n : 0);
+        bw += R.bwd_small_n + R.bwd_a_grid;
+        if (R.blk_n && (R.blk_inst < 0 || R.blk_inst >= FB_INSTANCES || (size_t)R.blk_lds > LDS_LIMIT)) return 4;
+      }
+      if (f != an.sched[w].nnodes || fw != f || bw != f) return 5;
+    }
+  }
+  return 0;
+}
+
 int main() {
   int checks = 0;
+  // the instance of k_factor_blk for p pivots holds them, and no smaller one does
+  for (int p = 1; p <= 192; p++) {
+    const int i = kktdev::fb_instance(p);
+    if (kktdev::fb_instances[i].maxp < p || (i > 0 && kktdev::fb_instances[i - 1].maxp >= p)) return 5;
+  }
   Csr Q, A, C;
   int n, me, m;
   for (int mode = 0; mode < 2; mode++)
@@ -81,6 +111,7 @@ int main() {
           an.ordering = ordering, an.shard_rank = rank, an.shard_count = shards;
           const int e = an.run(mode, 700, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data(), 0, 0, mode ? 0 : -1);
           if (e || an.nnodes < 1 || an.sbw < 1) return 10 + e;
+          if (check_plans(an)) return 20;
           checks++;
         }
       }
@@ -90,6 +121,7 @@ int main() {
     kktdev::Analysis an;
     an.amalgamation = amal != 0;
     if (an.run(1, n, me, m, Q.p.data(), Q.i.data(), A.p.data(), A.i.data(), C.p.data(), C.i.data(), 8, 16, 0)) return 30;
+    if (check_plans(an)) return 31;
     checks++;
   }
   // STAGED plans

@@ -20,6 +20,9 @@ DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
 HESS_CSR, HESS_DENSE = 0, 1
 HQPKKT_HESS_UPDATE_RANK = 4
 HQPKKT_BFGS_REPORT = 8
+HQPKKT_EIG_MAX_STEPS = 128
+HQPKKT_EIG_REPORT = 10
+HQPKKT_EIG_END_REL = 2.0 ** -40
 
 # every symbol include/hqpkkt.h declares
 SYMBOLS = [
@@ -41,6 +44,8 @@ SYMBOLS = [
     "hqpkkt_set_packed_hessians", "hqpkkt_debug_hess_symv_timed",
     "hqpkkt_update_stage_hessians", "hqpkkt_hessian_product",
     "hqpkkt_bfgs_update_stage_hessians", "hqpkkt_bfgs_report",
+    "hqpkkt_hessian_row_stats", "hqpkkt_restart_stage_hessians", "hqpkkt_gerschgorin_stage_hessians",
+    "hqpkkt_eigen_control_stage_hessians", "hqpkkt_eigen_report",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
@@ -68,6 +73,10 @@ class HessUpdate(C.Structure):  # hqpkkt_hess_update
 
 class BfgsUpdate(C.Structure):  # hqpkkt_bfgs_update
     _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("alpha", C.c_double), ("v", C.c_void_p)]
+
+
+class EigenControl(C.Structure):  # hqpkkt_eigen_control
+    _fields_ = [("eps", C.c_double), ("floor_from_bfgs", C.c_int), ("floor", C.c_void_p), ("max_steps", C.c_int)]
 
 
 class Stats(C.Structure):
@@ -225,6 +234,11 @@ def lib():
     L.hqpkkt_hessian_product.argtypes = [vp, vp, vp]
     L.hqpkkt_bfgs_update_stage_hessians.argtypes = [vp, C.POINTER(BfgsUpdate)]
     L.hqpkkt_bfgs_report.argtypes = [vp, vp]
+    L.hqpkkt_hessian_row_stats.argtypes = [vp, vp, vp]
+    L.hqpkkt_restart_stage_hessians.argtypes = [vp, C.c_double, vp]
+    L.hqpkkt_gerschgorin_stage_hessians.argtypes = [vp, C.c_double]
+    L.hqpkkt_eigen_control_stage_hessians.argtypes = [vp, C.POINTER(EigenControl)]
+    L.hqpkkt_eigen_report.argtypes = [vp, vp, vp]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

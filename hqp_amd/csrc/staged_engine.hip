@@ -281,6 +281,51 @@ static double bfgs_gamma_eff(double gamma, double alpha) {
   const double t = omg * oma;
   return g + t;
 }
+// what the safeguards of the dense stage Hessians (staged_hess_guard.hip.h) ask of the handle: the dense form with the
+// dense hand-over, and - they read the blocks - every block of nonzero order arrived since the analysis (need: of the
+// stages it marks alone)
+static int staged_hg_ready(const hqpkkt_t *h, const unsigned char *need) {
+  if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
+  const StagedDev &d = *h->sd;
+  const int K1 = d.plan.K + 1;
+  for (int k = 0; k < K1; k++)
+    if (d.plan.hess_order(k) > 0 && (!need || need[k]) && ((int)d.hess.set.size() != K1 || !d.hess.set[k])) return HQPKKT_E_INTERN;
+  return 0;
+}
+// ... their descriptors and buffers, made by the first call of any of them (outside every capture)
+static int staged_hg_prepare(StagedDev &d) {
+  StagedDev::Hessians &q = d.hess;
+  if (q.hg_desc.p) return 0;
+  const kktdev::StagedPlan &P = d.plan;
+  const int K1 = P.K + 1;
+  std::vector<stg::HgDesc> gd(K1);
+  q.hg_slots = 0, q.hg_tiles_max = q.hg_nz_max = 0;
+  for (int k = 0; k < K1; k++) {
+    const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
+    const bool packed = nz > 0 && P.stage_packed(k);
+    gd[k] = stg::HgDesc{P.oQ[k], q.hg_slots, P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, packed ? (int)P.hess_tiles(nz) : 0};
+    if (packed) q.hg_slots += (long long)nt * nt * stg::HP_T;
+    q.hg_tiles_max = std::max(q.hg_tiles_max, gd[k].tiles), q.hg_nz_max = std::max(q.hg_nz_max, nz);
+  }
+  int e;
+  if ((e = q.hg_scr.alloc((size_t)(2 * q.hg_slots) + 1)) || (e = q.hg_vec.alloc(4 * (size_t)P.n + 1)) || (e = q.he_st.alloc((size_t)K1 * stg::HE_STATE)) ||
+      (e = q.he_T.alloc((size_t)K1 * 2 * stg::HE_MAX_STEPS)) || (e = q.he_rep.alloc((size_t)K1 * stg::HE_REPORT)) || (e = q.he_floor.alloc(K1)))
+    return e;
+  HIPCHK(q.he_hfloor.alloc(K1, hipHostMallocDefault));
+  HIPCHK(hipEventCreateWithFlags(&q.he_ev.h, hipEventDisableTiming));
+  return q.hg_desc.upload(gd);
+}
+// ... and the row pass: rowmax and offsum (either may be null) of every stage, device vectors of n
+static void staged_hg_rows(hqpkkt_t *h, StagedDev &d, double *rowmax, double *offsum) {
+  StagedDev::Hessians &q = d.hess;
+  const unsigned K1 = (unsigned)d.plan.K + 1;
+  if (q.hs_nz_max > 0)
+    KLAUNCH(h, KC_VECTOR, stg::k_hg_rows<<<dim3((unsigned)std::min((q.hs_nz_max + 3) / 4, 1024), K1), 256, 0, h->stream>>>(q.hg_desc.p, q.Q.p, rowmax, offsum));
+  if (q.hg_tiles_max > 0) {
+    KLAUNCH(h, KC_VECTOR, stg::k_hg_tiles<<<dim3((unsigned)q.hg_tiles_max, K1), 256, 0, h->stream>>>(q.hg_desc.p, q.Q.p, q.hg_scr.p, q.hg_scr.p + q.hg_slots));
+    KLAUNCH(h, KC_VECTOR, stg::k_hg_finish<<<dim3((unsigned)q.hp_nt_max, K1), stg::HP_T, 0, h->stream>>>(q.hg_desc.p, q.hg_scr.p, q.hg_scr.p + q.hg_slots, rowmax, offsum));
+  }
+}
 
 extern "C" {
 
@@ -706,6 +751,152 @@ int hqpkkt_bfgs_report(hqpkkt_t *h, double *out) {
     HIPCHK(hipSetDevice(h->opts.device));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, d.hess.hb_rep.p, sizeof(double) * d.hess.hb_rep.count, hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+int hqpkkt_hessian_row_stats(hqpkkt_t *h, double *rowmax, double *offsum) {
+  return guarded([&]() -> int {
+    if (!h || (!rowmax && !offsum)) return HQPKKT_E_NULL;
+    int e;
+    if ((e = staged_hg_ready(h, nullptr))) return e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    StagedDev &d = *h->sd;
+    if ((e = staged_hg_prepare(d))) return e;
+    const size_t n = (size_t)d.plan.n;
+    const bool host = h->opts.loc != HQPKKT_LOC_DEVICE;
+    double *rm = !rowmax ? nullptr : host ? d.hess.hg_vec.p : rowmax, *os = !offsum ? nullptr : host ? d.hess.hg_vec.p + n : offsum;
+    staged_hg_rows(h, d, rm, os);
+    HIPCHK(hipGetLastError());
+    if (host) {
+      if (rm) HIPCHK(hipMemcpyAsync(rowmax, rm, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+      if (os) HIPCHK(hipMemcpyAsync(offsum, os, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+  });
+}
+
+int hqpkkt_restart_stage_hessians(hqpkkt_t *h, double eps, const unsigned char *stages) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
+    int e;
+    if ((e = staged_hg_ready(h, stages))) return e;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    const int K1 = P.K + 1;
+    // the update launch's descriptors: beta = 0 on the chosen stages, every other stage left alone (units = 0)
+    std::vector<stg::HuDesc> hd(K1);
+    int units_max = 0;
+    for (int k = 0; k < K1; k++) {
+      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
+      const bool packed = P.stage_packed(k), chosen = nz > 0 && (!stages || stages[k]);
+      hd[k] = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, 0, chosen ? 0 : 1, 0, chosen ? 0.0 : 1.0, {0.0, 0.0, 0.0, 0.0}};
+      if (chosen) hd[k].units = packed ? (int)P.hess_tiles(nz) : nt * nt;
+      units_max = std::max(units_max, hd[k].units);
+    }
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    if ((e = staged_hg_prepare(d))) return e;
+    if (units_max > 0) {
+      const size_t n = (size_t)P.n;
+      double *rm = d.hess.hg_vec.p, *dv = d.hess.hg_vec.p + 2 * n;
+      staged_hg_rows(h, d, rm, nullptr);
+      KLAUNCH(h, KC_VECTOR, stg::k_hg_clip<<<nblk((long long)n), 256, 0, h->stream>>>((long long)n, rm, eps, 1.0 / eps, dv));
+      if ((e = staged_hu_descriptors(h, d, hd))) return e;
+      stg::HuVecs V{};
+      V.r = 0, V.diag = dv;
+      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
+      HIPCHK(hipGetLastError());
+    }
+    h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
+    int e;
+    if ((e = staged_hg_ready(h, nullptr))) return e;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    StagedDev &d = *h->sd;
+    if ((e = staged_hg_prepare(d))) return e;
+    if (d.hess.hg_nz_max > 0) {
+      double *os = d.hess.hg_vec.p + (size_t)d.plan.n;
+      staged_hg_rows(h, d, nullptr, os);
+      KLAUNCH(h, KC_ASSEMBLE, stg::k_hg_diag<<<dim3((unsigned)((d.hess.hg_nz_max + 255) / 256), (unsigned)(d.plan.K + 1)), 256, 0, h->stream>>>(
+                                  d.hess.hg_desc.p, d.hess.Q.p, os, eps, nullptr, 0));
+      HIPCHK(hipGetLastError());
+    }
+    h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *c) {
+  return guarded([&]() -> int {
+    if (!h || !c) return HQPKKT_E_NULL;
+    static_assert(stg::HE_MAX_STEPS == HQPKKT_EIG_MAX_STEPS && stg::HE_REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
+    if (!std::isfinite(c->eps) || !(c->eps > 0.0) || c->max_steps < 0 || c->max_steps > HQPKKT_EIG_MAX_STEPS) return HQPKKT_E_RANGE;
+    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    const int K1 = P.K + 1;
+    for (int k = 0; k < K1 && c->floor; k++)
+      if (!std::isfinite(c->floor[k])) return HQPKKT_E_RANGE;
+    int e;
+    if ((e = staged_hg_ready(h, nullptr))) return e;
+    if (c->floor_from_bfgs && !d.hess.hb_done) return HQPKKT_E_INTERN;
+    if (!h->uploaded && (e = staged_upload(h))) return e;
+    HIPCHK(hipSetDevice(h->opts.device));
+    if ((e = staged_hg_prepare(d))) return e;
+    const size_t n = (size_t)P.n;
+    // the floors the caller gave, NaN where theta_k comes from eps: through the pinned words, in the handle's stream
+    HIPCHK(hipEventSynchronize(d.hess.he_ev));  // (the copy of the last call's floors out of the pinned words)
+    for (int k = 0; k < K1; k++) d.hess.he_hfloor.p[k] = c->floor ? c->floor[k] : std::numeric_limits<double>::quiet_NaN();
+    HIPCHK(hipMemcpyAsync(d.hess.he_floor.p, d.hess.he_hfloor.p, sizeof(double) * K1, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(d.hess.he_ev, h->stream));
+    double *os = d.hess.hg_vec.p + n, *w = d.hess.hg_vec.p + 3 * n;
+    const int steps = std::min(c->max_steps ? c->max_steps : 64, d.hess.hg_nz_max);
+    // the basis of the recurrence, `steps` vectors of n: grown here, outside every capture, and cleared - a stage that is
+    // done keeps v = 0 from there on
+    if (d.hess.he_V.count < (size_t)steps * n + 1 && (e = d.hess.he_V.alloc((size_t)steps * n + 1))) return e;
+    double *V = d.hess.he_V.p;
+    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, h->stream));
+    staged_hg_rows(h, d, nullptr, os);
+    KLAUNCH(h, KC_VECTOR, stg::k_he_start<<<(unsigned)K1, 256, 0, h->stream>>>(d.hess.hg_desc.p, d.hess.Q.p, os, d.hess.he_floor.p, c->eps * c->eps,
+                                                                             c->floor_from_bfgs ? d.hess.hb_rep.p : nullptr, d.hess.he_st.p,
+                                                                             d.hess.he_rep.p, d.hess.he_T.p, V));
+    for (int j = 0; j < steps; j++) {  // (nothing is read back: a stage that has ended returns from its workgroup at once)
+      staged_hess_symv(h, d, V + (size_t)j * n, w);
+      KLAUNCH(h, KC_VECTOR, stg::k_he_step<<<(unsigned)K1, stg::HE_STEP_THREADS, 0, h->stream>>>(d.hess.hg_desc.p, d.hess.he_st.p, d.hess.he_T.p, V, w, (long long)n, j,
+                                                                              j + 1 == steps ? 1 : 0));
+    }
+    KLAUNCH(h, KC_VECTOR, stg::k_he_ritz<<<(unsigned)K1, 64, 0, h->stream>>>(d.hess.he_st.p, d.hess.he_T.p, d.hess.he_rep.p));
+    if (d.hess.hg_nz_max > 0)
+      KLAUNCH(h, KC_ASSEMBLE, stg::k_hg_diag<<<dim3((unsigned)((d.hess.hg_nz_max + 255) / 256), (unsigned)K1), 256, 0, h->stream>>>(
+                                  d.hess.hg_desc.p, d.hess.Q.p, nullptr, 0.0, d.hess.he_rep.p, 1));
+    HIPCHK(hipGetLastError());
+    d.hess.he_done = true;
+    h->factored = false;
+    return 0;
+  });
+}
+
+int hqpkkt_eigen_report(hqpkkt_t *h, double *out, double *T) {
+  return guarded([&]() -> int {
+    if (!h || !out) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->hess.he_done) return HQPKKT_E_INTERN;
+    StagedDev &d = *h->sd;
+    HIPCHK(hipSetDevice(h->opts.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, d.hess.he_rep.p, sizeof(double) * d.hess.he_rep.count, hipMemcpyDeviceToHost));
+    if (T) HIPCHK(hipMemcpy(T, d.hess.he_T.p, sizeof(double) * d.hess.he_T.count, hipMemcpyDeviceToHost));
     return 0;
   });
 }

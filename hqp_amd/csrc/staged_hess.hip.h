@@ -7,6 +7,8 @@
 //   products  k_hs_symv: y = Q x over all stages in one launch, a wavefront per row, a fixed order of the sums
 //   update    k_hu_update (staged_hess_update.hip.h): Q_k <- beta_k Q_k + diag(d_k) + sum_j c_kj u_j u_j' in place
 //             k_hb_terms (staged_hess_bfgs.hip.h): the damped BFGS update's v and coefficients per stage, into that launch's descriptors
+//   guards    k_hg_* / k_he_* (staged_hess_guard.hip.h): row maxima and off-diagonal sums of every block, restart_Q, Gerschgorin's
+//             diagonal, and the eigenvalue control by a Lanczos recurrence over all stages
 // Plain loads and stores: no polled words, no waits between workgroups, no atomics.  Included by staged_engine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -122,3 +124,4 @@ __global__ void __launch_bounds__(256) k_hs_symv(const HessDesc *__restrict__ de
 #include "staged_hess_packed.hip.h"  // (the same blocks stored as packed lower tiles)
 #include "staged_hess_update.hip.h"  // (both layouts updated in place: hqpkkt_update_stage_hessians)
 #include "staged_hess_bfgs.hip.h"    // (the damped BFGS terms of that update on the device: hqpkkt_bfgs_update_stage_hessians)
+#include "staged_hess_guard.hip.h"   // (row statistics, restart_Q, Gerschgorin and the eigenvalue control: hqpkkt_hessian_row_stats ..)

@@ -80,7 +80,11 @@ struct StagedDev {
   // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n); of the BFGS update on the
   // device (hqpkkt_bfgs_update_stage_hessians) Q s and v, behind them the copies of a host caller's s and y (hb_vec: 2 n
   // or 4 n - never hess.y, which the residual reads), the report words of k_hb_terms (8 per stage), and whether an
-  // update has written them since the analysis
+  // update has written them since the analysis; of the safeguards (hqpkkt_hessian_row_stats and the entries behind it,
+  // staged_hess_guard.hip.h) per stage what their kernels need, the slots of the packed row pass (hg_slots doubles of
+  // maxima, then as many of sums - twice what the product's scratch holds, so it is not shared), four vectors of n (row
+  // maxima, off-diagonal sums, the restart's diagonal, w of the recurrence), the recurrence's basis (as many vectors of n as
+  // the control with the most steps asked for), its state, T and report per stage, the floors through pinned words (he_ev: copied), and whether a control has run since the analysis
   struct Hessians {
     DBuf<double> Q, y;
     DBuf<long long> q_dst;
@@ -96,6 +100,13 @@ struct StagedDev {
     DBuf<double> hu_vec;
     DBuf<double> hb_vec, hb_rep;
     bool hb_done = false;
+    DBuf<stg::HgDesc> hg_desc;
+    DBuf<double> hg_scr, hg_vec, he_V, he_st, he_T, he_rep, he_floor;
+    PinnedBuf<double> he_hfloor;
+    EventOwner he_ev;
+    long long hg_slots = 0;
+    int hg_tiles_max = 0, hg_nz_max = 0;
+    bool he_done = false;
   } hess;
   // The sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A' ...
   // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per stage, and per column of A its

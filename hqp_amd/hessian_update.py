@@ -12,11 +12,16 @@ variables, the reference's damped BFGS update (Hqp_HL_BFGS::update_b_Q) is
     otherwise v = y
     Q+ = Q - (Q s)(Q s)' / sQs + v v' / sv,            and Q+ = Q where sv or sQs is zero.
 
-The eigenvalue control that the reference can run after it (an eigenvalue decomposition per block, then a shift of the
-diagonal) is not built; its effect, a diagonal shift, is ``update_stage_hessians(..., diag=shift)`` with beta = 1.
-
 ``IpLQDOCP.bfgs_update_device`` (hqpkkt_bfgs_update_stage_hessians) forms the same terms on the device; ``bfgs_replay`` is its
 numpy model, operation by operation from the sums the device reports.
+
+The safeguards that read a block run on the device as well (staged_hess_guard.hip.h); their numpy models are here:
+``restart_model`` (restart_Q, ``IpLQDOCP.restart_hessians``), ``gerschgorin_model`` (Hqp_HL_Gerschgorin::update,
+``IpLQDOCP.gerschgorin_hessians``) and, of the eigenvalue control that the reference runs after the update
+(``IpLQDOCP.eigen_control``: the smallest eigenvalue lambda of the block, and q_ii -= lambda - theta where that is negative),
+``lanczos_model``, the device's recurrence in float64, and ``eigen_replay``, the device's evaluation of the tridiagonal T it
+REPORTED, operation by operation.  The device estimates lambda from below by lo - rho (a bracket of T's smallest eigenvalue
+and Lanczos' residual bound) where the reference calls symmeig.
 """
 from __future__ import annotations
 
@@ -76,3 +81,175 @@ def bfgs_replay(report, s, y, Qs, offsets):
             if sv != 0.0 and sQs != 0.0 and np.isfinite(sv) and np.isfinite(sQs):
                 coef[k] = one / sv, -(one / sQs)
     return v, coef
+
+
+EIG_MAX_STEPS = 128  # (HQPKKT_EIG_MAX_STEPS)
+EIG_END_REL = 2.0 ** -40  # (HQPKKT_EIG_END_REL)
+
+
+def restart_model(Q, eps):
+    """restart_Q (hqp/Hqp_HL_BFGS.C:125-146): diag(min(max(eps, max_j |Q_ij|), 1 / eps)), the two comparisons in the
+    reference's order."""
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.shape[0] == 0:
+        return Q.copy()
+    rm = np.abs(Q).max(axis=1)
+    inv = np.float64(1.0) / np.float64(eps)
+    t = np.where(eps > rm, np.float64(eps), rm)
+    return np.diag(np.where(t < inv, t, inv))
+
+
+def gerschgorin_model(Q, eps):
+    """Hqp_HL_Gerschgorin::update (hqp/Hqp_HL_Gerschgorin.C:66-106) on a block: q_ii <- max(q_ii, sum_{j != i} |q_ij| + eps);
+    every other entry stays."""
+    Q = np.array(Q, dtype=np.float64)
+    A = np.abs(Q)
+    off = A.sum(axis=1) - np.diag(A) if Q.shape[0] else np.zeros(0)
+    t = off + np.float64(eps)
+    dg = np.diag(Q).copy()
+    Q[np.diag_indices(Q.shape[0])] = np.where(t > dg, t, dg)
+    return Q
+
+
+def lanczos_start(order):
+    """The start vector of stage order ``order`` before it is normalised: 1 + ((37 i + 11) mod 64) / 64."""
+    i = np.arange(order, dtype=np.int64)
+    return 1.0 + ((37 * i + 11) % 64) / 64.0
+
+
+def lanczos_model(Q, theta, max_steps=0):
+    """The device's recurrence on one block in float64 (k_he_start, k_he_step; numpy's sums run in another order than the
+    device's).  Returns (g, steps, T): Gerschgorin's bound g = min_i (q_ii - sum_{j != i} |q_ij|), the steps taken - 0 where
+    g >= theta or the order is 0: no recurrence runs - and T of shape (2, 128), alpha then beta."""
+    Q = np.asarray(Q, dtype=np.float64)
+    nz = Q.shape[0]
+    T = np.zeros((2, EIG_MAX_STEPS))
+    if nz == 0:
+        return 0.0, 0, T
+    A = np.abs(Q)
+    g = float((np.diag(Q) - (A.sum(axis=1) - np.diag(A))).min())
+    if g >= theta:
+        return g, 0, T
+    f = lanczos_start(nz)
+    V = [f / np.sqrt(f @ f)]
+    bprev, scale, steps = 0.0, 0.0, 0
+    with np.errstate(all="ignore"):
+        for j in range(min(max_steps if max_steps else 64, nz)):
+            v = V[j]
+            w = Q @ v
+            alpha = float(v @ w)
+            w = w - alpha * v
+            if j > 0:
+                w = w - bprev * V[j - 1]
+            B = np.array(V)
+            w = w - B.T @ (B @ w)  # (orthogonal to the whole basis once more: no second copies of a converged eigenvalue)
+            beta = float(np.sqrt(w @ w))
+            T[0, j], T[1, j] = alpha, beta
+            steps = j + 1
+            scale = max(scale, abs(alpha))
+            if j + 1 >= nz or not beta > EIG_END_REL * scale:
+                break
+            scale = max(scale, beta)
+            V.append(w / beta)
+            bprev = beta
+    return g, steps, T
+
+
+def _nan_max(m, a):
+    return a if (a > m or a != a) else m
+
+
+def _nan_min(m, a):
+    return a if (a < m or a != a) else m
+
+
+def eigen_replay(order, g, theta, steps, T):
+    """What the device does with one stage's T (k_he_ritz, staged_hess_guard.hip.h) repeated in numpy, one operation per
+    device operation: from Gerschgorin's bound ``g``, the floor ``theta``, ``steps`` and ``T`` of shape (2, 128) as
+    ``IpLQDOCP.eigen_report(with_T=True)`` returns them.  Returns a dict: lo, hi (the bracket of T's smallest eigenvalue by the
+    Sturm count, 64 points per round), rho (Lanczos' residual bound from the twisted factorisation of T - lo I), lam = lo - rho, d (the shift),
+    normT and the outcome 0 .. 5."""
+    f8 = np.float64
+    out = dict(lo=0.0, hi=0.0, rho=0.0, lam=0.0, d=0.0, normT=0.0, outcome=-1)
+    if order == 0:
+        out["outcome"] = 5
+        return out
+    if g >= theta:
+        out["outcome"] = 0
+        return out
+    m = int(steps)
+    al, be = np.asarray(T[0][:m], dtype=f8), np.asarray(T[1][:m], dtype=f8)
+    with np.errstate(all="ignore"):
+        b2 = be * be
+        normT, gl, gu = f8(0.0), f8(np.inf), f8(-np.inf)
+        for i in range(m):
+            off = (abs(be[i - 1]) if i > 0 else f8(0.0)) + (abs(be[i]) if i < m - 1 else f8(0.0))
+            normT = _nan_max(normT, abs(al[i]) + off)
+            gl, gu = _nan_min(gl, al[i] - off), _nan_max(gu, al[i] + off)
+        out["normT"] = float(normT)
+        if not np.isfinite(normT):
+            out["outcome"] = 4
+            return out
+        tol = f8(2.0 ** -50) * normT
+        pivmin = max(f8(2.0 ** -104) * normT, f8(2.0 ** -1000))
+        lo, hi = gl - tol, gu + tol
+        c = np.arange(1, 65).astype(f8) / f8(65.0)
+        rounds = 0
+        while rounds < 32 and hi - lo > tol:
+            x = lo + (hi - lo) * c
+            p = al[0] - x
+            cnt = (p < 0).astype(np.int64)
+            for i in range(1, m):
+                p = np.where(np.abs(p) < pivmin, np.where(p < 0, -pivmin, pivmin), p)
+                p = (al[i] - x) - b2[i - 1] / p
+                cnt += p < 0
+            hit = cnt >= 1
+            if not hit.any():
+                lo = x[63]
+            else:
+                f = int(np.argmax(hit))
+                hi = x[f]
+                if f > 0:
+                    lo = x[f - 1]
+            rounds += 1
+        pv = np.zeros(m)
+        pv[0] = al[0] - lo
+        for i in range(1, m + 1):
+            p = pv[i - 1]
+            if abs(p) < pivmin:
+                p = -pivmin if p < 0 else pivmin
+            pv[i - 1] = p
+            if i < m:
+                pv[i] = (al[i] - lo) - b2[i - 1] / p
+        rv = np.zeros(m)
+        rv[m - 1] = al[m - 1] - lo
+        for i in range(m - 1, -1, -1):
+            p = rv[i]
+            if abs(p) < pivmin:
+                p = -pivmin if p < 0 else pivmin
+            rv[i] = p
+            if i > 0:
+                rv[i - 1] = (al[i - 1] - lo) - b2[i - 1] / p
+        t, gmin = 0, f8(np.inf)
+        for i in range(m):
+            gam = abs((pv[i] + rv[i]) - (al[i] - lo))
+            if gam < gmin:
+                gmin, t = gam, i
+        z = np.zeros(m)
+        z[t] = 1.0
+        for i in range(t - 1, -1, -1):
+            z[i] = -((be[i] / pv[i]) * z[i + 1])
+        for i in range(t, m - 1):
+            z[i + 1] = -((be[i] / rv[i + 1]) * z[i])
+        zz = f8(0.0)
+        for i in range(m):
+            zz = zz + z[i] * z[i]
+        rho = abs(be[m - 1]) * (abs(z[m - 1]) / np.sqrt(zz))
+        lam = lo - rho
+        d, outcome = f8(0.0), 1
+        if not np.isfinite(lam):
+            outcome = 4
+        elif lam < theta:
+            d, outcome = f8(theta) - lam, 2 if rho <= f8(EIG_END_REL) * normT else 3
+    out.update(lo=float(lo), hi=float(hi), rho=float(rho), lam=float(lam), d=float(d), outcome=outcome)
+    return out

@@ -566,8 +566,9 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         Q_k <- beta_k Q_k + diag(d_k) + sum_j coef[k, j] u_jk u_jk'.  ``U``: a list of r <= 4 vectors of n, ``diag``: a
         vector of n or None - numpy, or torch CUDA tensors with device_vectors=True (read asynchronously: they are kept
         alive here until the next call); ``coef``: host array of shape (K + 1, r); ``beta``: K + 1 host values or None
-        (all 1).  beta_k = 0 makes block k on the device - ``diag`` alone is a scaled identity or a restart -, and a
-        diagonal shift, the effect of the reference's eigenvalue control (which is not built), is ``diag`` with beta = 1."""
+        (all 1).  beta_k = 0 makes block k on the device - ``diag`` alone is a scaled identity -, and a diagonal shift is
+        ``diag`` with beta = 1.  The reference's restart and eigenvalue control, which read the blocks, are
+        restart_hessians() and eigen_control()."""
         U = list(U)
         r = len(U)
         K1 = len(self.debug(20))
@@ -613,13 +614,14 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
             self.update_stage_hessians(U, coef)
         return U, coef
 
-    def bfgs_update_device(self, s, y, gamma=0.1, alpha=1.0, want_v=False):
+    def bfgs_update_device(self, s, y, gamma=0.1, alpha=1.0, want_v=False, eigen_control=None):
         """The same update with its terms formed on the device as well (hqpkkt_bfgs_update_stage_hessians): Q s, the
         scalars, Powell's test, v and the coefficients never reach the host.  ``s``, ``y``: numpy vectors of n - or torch
         CUDA tensors with device_vectors=True: no host copy is made, the call returns with the work enqueued in the
         handle's stream, and the tensors are kept alive here until the next call.  ``gamma`` < 0: damping adapted to the
         step length ``alpha``.  ``want_v``: returns v as applied (a tensor with device_vectors=True), else None.
-        bfgs_report() tells what every stage did."""
+        ``eigen_control``: an eps - the reference's eigenvalue control runs behind the update in the same stream,
+        eigen_control(eps, from_bfgs=True); None (the default): the update alone.  bfgs_report() tells what every stage did."""
         ps, ks = self._hess_vec(s, "s")
         py, ky = self._hess_vec(y, "y")
         b = _lib.BfgsUpdate()
@@ -636,6 +638,8 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         self._torch_sync()
         _check(self._L.hqpkkt_bfgs_update_stage_hessians(self._h, C.byref(b)), "bfgs_update_device")
         self._keep_b = [ks, ky, v]
+        if eigen_control is not None:
+            self.eigen_control(eigen_control, from_bfgs=True)
         return v
 
     def bfgs_report(self):
@@ -646,6 +650,66 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         out = np.zeros((len(self.debug(20)), _lib.HQPKKT_BFGS_REPORT))
         _check(self._L.hqpkkt_bfgs_report(self._h, C.c_void_p(out.ctypes.data)), "bfgs_report")
         return out
+
+    def hessian_row_stats(self, want_max=True, want_sum=True):
+        """(rowmax, offsum) of every stage Hessian (hqpkkt_hessian_row_stats): per variable i of stage k the largest
+        |Q_k(i, j)| and the sum of |Q_k(i, j)| over j != i, vectors of n - numpy, or torch CUDA tensors with
+        device_vectors=True.  The entry writes device vectors asynchronously in the handle's stream, which torch's streams do
+        not wait for: this wrapper waits for the device before it returns the tensors.  None for the one not wanted."""
+        torch = None
+        if self._device_vectors:
+            import torch
+            dev = torch.device("cuda", self._dev)
+            out = [torch.zeros(self.n, dtype=torch.float64, device=dev) if w else None for w in (want_max, want_sum)]
+            ptr = [None if a is None else C.c_void_p(a.data_ptr()) for a in out]
+            self._torch_sync()
+        else:
+            out = [np.zeros(self.n) if w else None for w in (want_max, want_sum)]
+            ptr = [None if a is None else C.c_void_p(a.ctypes.data) for a in out]
+        _check(self._L.hqpkkt_hessian_row_stats(self._h, ptr[0], ptr[1]), "hessian_row_stats")
+        if torch is not None:
+            torch.cuda.synchronize(self._dev)
+        return out[0], out[1]
+
+    def restart_hessians(self, eps, stages=None):
+        """The reference's restart_Q on the device (hqpkkt_restart_stage_hessians): Q_k <- diag(min(max(eps, rowmax_i),
+        1 / eps)) on the stages whose entry of ``stages`` (K + 1 flags) is set; None: on all."""
+        flags = None
+        if stages is not None:
+            flags = np.ascontiguousarray(np.asarray(stages) != 0, dtype=np.uint8).reshape(len(self.debug(20)))
+        _check(self._L.hqpkkt_restart_stage_hessians(self._h, float(eps), None if flags is None else C.c_void_p(flags.ctypes.data)), "restart_hessians")
+
+    def gerschgorin_hessians(self, eps):
+        """Hqp_HL_Gerschgorin::update on the device (hqpkkt_gerschgorin_stage_hessians): q_ii <- max(q_ii, sum_{j != i}
+        |q_ij| + eps) on every stage; the diagonal entries alone are written."""
+        _check(self._L.hqpkkt_gerschgorin_stage_hessians(self._h, float(eps)), "gerschgorin_hessians")
+
+    def eigen_control(self, eps, floor=None, from_bfgs=False, max_steps=0):
+        """The eigenvalue control of Hqp_HL_BFGS::update_b_Q on the device (hqpkkt_eigen_control_stage_hessians): every
+        stage whose smallest eigenvalue, estimated from below by a Lanczos recurrence over all stages, lies under its
+        floor theta_k gets its diagonal shifted up by the difference.  theta_k = eps^2; ``from_bfgs``: lowered to s'Qs of
+        the last bfgs_update_device() where 0 <= s'Qs < eps^2 (the reference's rule, read on the device); ``floor``: K + 1
+        host values that override both.  ``max_steps``: 1 .. 128 Lanczos steps, 0: 64.  The call returns with the work
+        enqueued; eigen_report() tells what every stage did."""
+        c = _lib.EigenControl()
+        c.eps, c.floor_from_bfgs, c.max_steps = float(eps), int(bool(from_bfgs)), int(max_steps)
+        if floor is not None:
+            floor = np.ascontiguousarray(floor, dtype=np.float64).reshape(len(self.debug(20)))
+            c.floor = floor.ctypes.data
+        _check(self._L.hqpkkt_eigen_control_stage_hessians(self._h, C.byref(c)), "eigen_control")
+
+    def eigen_report(self, with_T=False):
+        """Per stage k = 0 .. K what the last eigen_control() did (hqpkkt_eigen_report), an array of shape (K + 1, 10):
+        Gerschgorin's bound g_k, the floor theta_k as used, the Lanczos steps, the bracket lo, hi of the smallest Ritz
+        value, the residual bound rho, the estimate lo - rho, the shift d_k, |T| and the outcome - 0 no shift by
+        Gerschgorin, 1 no shift by Lanczos, 2 shifted and converged, 3 shifted and not converged, 4 left alone (not
+        finite), 5 order 0.  ``with_T``: (report, T) with T of shape (K + 1, 2, 128), alpha then beta of every stage.
+        Waits for the handle's stream."""
+        K1 = len(self.debug(20))
+        out = np.zeros((K1, _lib.HQPKKT_EIG_REPORT))
+        T = np.zeros((K1, 2, _lib.HQPKKT_EIG_MAX_STEPS)) if with_T else None
+        _check(self._L.hqpkkt_eigen_report(self._h, C.c_void_p(out.ctypes.data), None if T is None else C.c_void_p(T.ctypes.data)), "eigen_report")
+        return (out, T) if with_T else out
 
     def set_packed_hessians(self, on):
         """Dense stage Hessians stored as packed lower tiles (hqpkkt_set_packed_hessians); holds from the next init() on."""

@@ -470,7 +470,8 @@ int hqpkkt_set_packed_hessians(hqpkkt_t *h, int on);
  *   Host vectors are copied through buffers the handle owns (made by the first call, outside any capture), and the call
  *   returns when the stream has read them.  Device vectors are read asynchronously in the handle's stream: the caller keeps
  *   them alive and unchanged until the stream has passed the update.  coef and beta are read before the call returns.
- * Not built: the reference's eigenvalue control (a diagonal shift is diag with beta = 1) and the row maxima of restart_Q.
+ * The reference's eigenvalue control and the row maxima of restart_Q, which read the blocks, are the entries behind
+ * hqpkkt_bfgs_report: hqpkkt_eigen_control_stage_hessians and hqpkkt_restart_stage_hessians.
  * hqpkkt_hessian_product: y = Q x over all stage blocks, x and y of n doubles, pointers per opts.loc, by the launches of
  * the handle's residual - the public form of hqpkkt_debug_hess_symv and the same bits; on any uploaded HQPKKT_HESS_DENSE
  * handle, either hand-over (HQPKKT_E_INTERN otherwise); the result is complete when it returns.  It gives a BFGS caller
@@ -524,7 +525,8 @@ int hqpkkt_hessian_product(hqpkkt_t *h, const double *x, double *y);
  * 6 c1 (both 0.0 where the stage was left alone); 7 the outcome - 0 updated without damping, 1 updated with damping, 2 left
  * alone because sv or sQs is zero, 3 left alone because sv or sQs is not finite.  HQPKKT_E_NULL; HQPKKT_E_INTERN before
  * the first update since the analysis.
- * Not built: the reference's eigenvalue control (an eigendecomposition per block) and restart_Q. */
+ * The reference's eigenvalue control and restart_Q follow as entries of their own (hqpkkt_eigen_control_stage_hessians,
+ * hqpkkt_restart_stage_hessians); a caller runs the control behind this update in the same stream. */
 typedef struct hqpkkt_bfgs_update {
   const double *s; /* n doubles, pointer per opts.loc: the step */
   const double *y; /* n doubles, pointer per opts.loc: change of the Lagrangian's gradient */
@@ -535,6 +537,86 @@ typedef struct hqpkkt_bfgs_update {
 int hqpkkt_bfgs_update_stage_hessians(hqpkkt_t *h, const hqpkkt_bfgs_update *b);
 #define HQPKKT_BFGS_REPORT 8
 int hqpkkt_bfgs_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * 8 doubles */);
+/* The safeguards of a block-BFGS caller on the device: the parts of the reference that READ a block Q_k - restart_Q
+ * (hqp/Hqp_HL_BFGS.C:125-146), Hqp_HL_Gerschgorin::update (hqp/Hqp_HL_Gerschgorin.C:66-106) and the eigenvalue control of
+ * Hqp_HL_BFGS::update_b_Q (:203-212, on by default there) - so that such a caller never reads a block back.  All of them
+ * work on HQPKKT_HESS_DENSE handles with the dense hand-over, on both layouts of the blocks, in the handle's stream, by plain
+ * loads and stores (staged_hess_guard.hip.h), and end in a change of the diagonal.
+ * The common rules are those of hqpkkt_update_stage_hessians and hqpkkt_bfgs_update_stage_hessians:
+ *   Checks, all before anything is launched (a call applies to every stage or to none), in this order: HQPKKT_E_NULL;
+ *   HQPKKT_E_RANGE - eps not finite or <= 0, max_steps outside 0 .. HQPKKT_EIG_MAX_STEPS; HQPKKT_E_INTERN - the handle is not
+ *   STAGED, not analysed, not HQPKKT_HESS_DENSE or analysed for the CSR hand-over; HQPKKT_E_RANGE - a floor that is not finite
+ *   (the floors are K + 1 values: the analysis says how many); HQPKKT_E_INTERN - a block of nonzero order that the call reads
+ *   has not arrived since the analysis, floor_from_bfgs without a hqpkkt_bfgs_update_stage_hessians since the analysis;
+ *   then, without a gfx950 device, HQPKKT_E_DEVICE.
+ *   After hqpkkt_restart_, hqpkkt_gerschgorin_ and hqpkkt_eigen_control_stage_hessians h is not factored; the dynamics and
+ *   the hand-over state are left alone.  Host vectors go through buffers the handle owns, made by the first call of any of
+ *   these entries, outside any capture; device vectors are read and written asynchronously in the handle's stream.
+ *   Entries past a stage's order belong to the next stage and padding is never read as a value.
+ * hqpkkt_hessian_row_stats: for variable i of stage k, rowmax[i] = max_j |Q_k(i,j)| and offsum[i] = sum_{j != i} |Q_k(i,j)|
+ * over the stage's order; n doubles each, pointers per opts.loc, either may be NULL but not both.  A NaN in a row gives NaN
+ * for that row and reaches no other row (with an entry off the diagonal its image's row as well: the blocks are symmetric).
+ *   Dense block: a wavefront per row, a lane the column pairs lane, lane + 64, .. in ascending order, then the wavefront's
+ *   butterfly.  Packed tiles: every stored element is loaded once and counts for its row and, off the diagonal tile, for its
+ *   column (the scheme of the packed product); per-tile partials over 128 columns go to slots of a scratch of this entry (two
+ *   statistics: twice the product's, so that one is not shared) and a second launch combines a row's slots in ascending
+ *   column order.  The order is fixed by the stage's order alone: the same bits from run to run.  The maxima are exact, so a
+ *   packed and an unpacked handle return the same bits; the sums agree to rounding, and exactly on integer operands.
+ * hqpkkt_restart_stage_hessians: Q_k <- diag(min(max(eps, rowmax_i), 1 / eps)) on the stages with stages[k] != 0 (HOST, K + 1
+ * bytes; NULL: all) - restart_Q's operations in their order (a row maximum that is NaN ends as 1 / eps).  The row pass, a
+ * kernel that forms the diagonal vector, then the launch of hqpkkt_update_stage_hessians, unchanged, with beta = 0 on the
+ * chosen stages and every other stage left alone: the bits are those of that entry with beta = 0 and diag = that vector.
+ * Unlike a beta = 0 update by the caller this READS the block: a chosen block must have arrived.
+ * hqpkkt_gerschgorin_stage_hessians: q_ii <- max(q_ii, fl(offsum_i + eps)) on every stage - the row pass and one kernel,
+ * k_hg_diag, that touches the diagonal entries alone (on a packed handle: in diagonal tile (a, a)); no pass over the arena.
+ * hqpkkt_eigen_control_stage_hessians: per stage, with lambda the smallest eigenvalue of Q_k and theta_k the floor, the
+ * reference's effect: where lambda - theta_k < 0, q_ii -= lambda - theta_k.  theta_k = eps eps; with floor_from_bfgs lowered
+ * to sQs_k where 0 <= sQs_k < eps eps, sQs_k read ON THE DEVICE from the words of the last hqpkkt_bfgs_update_stage_hessians
+ * (the reference's rule); floor, where given, overrides both per stage.  lambda is estimated, not computed (the reference
+ * calls symmeig per block): a Lanczos recurrence runs on all stages in lockstep.
+ *   Start.  The row pass gives Gerschgorin's bound g_k = min_i (q_ii - offsum_i).  A stage with g_k >= theta_k needs no
+ *   shift and is done (outcome 0), as is a stage of order 0 (outcome 5).  Every other stage starts from v = f / |f|,
+ *   f_i = 1 + ((37 i + 11) mod 64) / 64 for the index i inside the stage.
+ *   Steps.  min(max_steps, largest order) steps (max_steps 0: 64), each one product w = Q v over all stages by the launches of
+ *   hqpkkt_hessian_product into a buffer of this entry and one launch k_he_step, a workgroup per stage: alpha_j = v'w,
+ *   w <- w - alpha_j v - beta_{j-1} v_prev, then w made orthogonal to the whole basis v_0 .. v_j once more (the entry keeps
+ *   the basis, `steps` vectors of n, made or grown by the call that needs it; without that pass the recurrence grows second
+ *   copies of a converged eigenvalue and the residual bound below means nothing while one is on its way), beta_j = |w|,
+ *   v_{j+1} = w / beta_j; the sums in a fixed order (a thread's entries t, t + 1024, .. by fused multiply-adds, a wavefront's
+ *   butterfly, the sixteen wavefronts of the stage's workgroup in their order).  A stage
+ *   ends itself where j + 1 equals its order or where beta_j > HQPKKT_EIG_END_REL max(|alpha_0 .. alpha_j|, beta_0 ..
+ *   beta_{j-1}) does not hold (an invariant subspace; the value is a condition, not critical): its v becomes 0 and it
+ *   records its step count.  Nothing is read back inside the loop.
+ *   Ritz value.  k_he_ritz, a wavefront per stage, on the tridiagonal T of the recurrence: |T| its infinity norm; the
+ *   smallest eigenvalue bracketed by the Sturm count from T's Gerschgorin interval down to hi - lo <= 2^-50 |T|, 64 points
+ *   per round; rho = beta_m |last component of the unit eigenvector of T|, by one step of inverse iteration through the
+ *   twisted factorisation of T - lo I - Lanczos' residual bound.
+ *   The estimate is conservative, lambda_est = lo - rho (a Ritz value lies above the smallest eigenvalue), and the shift is
+ *   d_k = theta_k - lambda_est where lambda_est < theta_k, else 0.  Where T or lambda_est is not finite the stage is left alone
+ *   (outcome 4) - NOT the reference, which would write NaN into the block.
+ *   Shift.  k_hg_diag adds d_k to the stage's diagonal entries, fl(q_ii + d_k); stages with d_k == 0 are not touched: the
+ *   bits are those of hqpkkt_update_stage_hessians(r = 0, beta = 1, diag = d) on the touched stages.
+ * hqpkkt_eigen_report waits for the stream and copies out HQPKKT_EIG_REPORT doubles per stage: 0 g_k; 1 theta_k as used;
+ * 2 steps; 3 lo; 4 hi; 5 rho; 6 lambda_est; 7 d_k; 8 |T|; 9 the outcome - 0 no shift, by Gerschgorin; 1 no shift, by Lanczos;
+ * 2 shifted, converged (rho <= 2^-40 |T|); 3 shifted, not converged; 4 left alone, not finite; 5 order 0 - and, where T is
+ * given, per stage alpha_0 .. (HQPKKT_EIG_MAX_STEPS doubles), then beta_0 .. (as many); words past the steps are 0.
+ * hessian_update.eigen_replay repeats k_he_ritz in numpy from the reported T.  HQPKKT_E_INTERN before the first control
+ * since the analysis.
+ * Not built: sharded handles, the CSR hand-over, and the reference's Hqp_HL_DScale. */
+#define HQPKKT_EIG_MAX_STEPS 128
+#define HQPKKT_EIG_REPORT 10
+#define HQPKKT_EIG_END_REL 9.094947017729282e-13 /* 2^-40 */
+typedef struct hqpkkt_eigen_control {
+  double eps;          /* the reference's _eps: floor theta_k = eps * eps ... */
+  int floor_from_bfgs; /* 1: ... lowered to sQs_k where 0 <= sQs_k < eps * eps, read on the device from the last BFGS update */
+  const double *floor; /* HOST, K + 1 doubles or NULL: overrides both of the above per stage */
+  int max_steps;       /* 1 .. HQPKKT_EIG_MAX_STEPS; 0 = default 64 */
+} hqpkkt_eigen_control;
+int hqpkkt_hessian_row_stats(hqpkkt_t *h, double *rowmax, double *offsum);
+int hqpkkt_restart_stage_hessians(hqpkkt_t *h, double eps, const unsigned char *stages /* HOST, K + 1, or NULL = all */);
+int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps);
+int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *e);
+int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * HQPKKT_EIG_MAX_STEPS */);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense

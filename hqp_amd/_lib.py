@@ -20,6 +20,7 @@ DYN_DENSE, DYN_SPARSE, DYN_PROFILE = 0, 1, 3
 HESS_CSR, HESS_DENSE = 0, 1
 HQPKKT_HESS_UPDATE_RANK = 4
 HQPKKT_BFGS_REPORT = 8
+HQPKKT_DSCALE_REPORT = 8
 HQPKKT_EIG_MAX_STEPS = 128
 HQPKKT_EIG_REPORT = 10
 HQPKKT_EIG_END_REL = 2.0 ** -40
@@ -49,6 +50,8 @@ SYMBOLS = [
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
+    "hqpkkt_q_values", "hqpkkt_q_product", "hqpkkt_q_row_stats", "hqpkkt_q_set_diagonal", "hqpkkt_q_gerschgorin",
+    "hqpkkt_q_dscale_setup", "hqpkkt_q_dscale_update", "hqpkkt_q_dscale_report", "hqpkkt_lagrangian_gradient",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -73,6 +76,10 @@ class HessUpdate(C.Structure):  # hqpkkt_hess_update
 
 class BfgsUpdate(C.Structure):  # hqpkkt_bfgs_update
     _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("alpha", C.c_double), ("v", C.c_void_p)]
+
+
+class DScaleUpdate(C.Structure):  # hqpkkt_dscale_update
+    _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("bsize", C.c_int), ("v", C.c_void_p)]
 
 
 class EigenControl(C.Structure):  # hqpkkt_eigen_control
@@ -239,6 +246,15 @@ def lib():
     L.hqpkkt_gerschgorin_stage_hessians.argtypes = [vp, C.c_double]
     L.hqpkkt_eigen_control_stage_hessians.argtypes = [vp, C.POINTER(EigenControl)]
     L.hqpkkt_eigen_report.argtypes = [vp, vp, vp]
+    L.hqpkkt_q_values.argtypes = [vp, vp]
+    L.hqpkkt_q_product.argtypes = [vp, vp, vp]
+    L.hqpkkt_q_row_stats.argtypes = [vp, vp, vp]
+    L.hqpkkt_q_set_diagonal.argtypes = [vp, vp]
+    L.hqpkkt_q_gerschgorin.argtypes = [vp, C.c_double]
+    L.hqpkkt_q_dscale_setup.argtypes = [vp, C.c_double]
+    L.hqpkkt_q_dscale_update.argtypes = [vp, C.POINTER(DScaleUpdate)]
+    L.hqpkkt_q_dscale_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.hqpkkt_lagrangian_gradient.argtypes = [vp] * 6
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

@@ -3,6 +3,7 @@
 // and the interior-point loops are units of their own (hqpkkt_handle.hpp); the entry points here have C linkage by
 // their declarations in include/hqpkkt.h.
 #include "hqpkkt_handle.hpp"
+#include "q_values.hip.h"
 
 char g_last_hip_error[512] = "";
 std::atomic<long long> g_live_bufs[2];
@@ -145,6 +146,50 @@ static int run_analysis(hqpkkt_t *h, int n, int me, int m, int zd) {
   return 0;
 }
 
+// The values Qx | Ax | Cx are in the handle (tree engine): the CSR copies, the weak-diagonal test of zd_policy -1 and
+// the host copies it keeps.  Qx, Ax, Cx: the caller's arrays the values came from.  q_only (the hqpkkt_q_* entries that
+// write Q): A and C are as they were - of the copies Qf alone is gathered again, and the kept host copies come from
+// the device.
+static int values_changed(hqpkkt_t *h, bool q_only, const double *Qx, const double *Ax, const double *Cx) {
+  Analysis &an = h->an;
+  int e;
+  for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
+    if (c->src.count && (!q_only || c == &h->td.Qf))
+      k_gather_values<<<nblk((long long)c->src.count), 256, 0, h->stream>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
+  if (h->opts.zd_policy < 0 && h->zd_used != 0) {
+    // zd_policy -1: an x whose Hessian diagonal is weak against its coupling to an equality needs the
+    // 2x2 pivot with that equality's multiplier inside its own pivot block.  Tested on EVERY update (the
+    // values of an SQP run change: an identity Hessian may turn weak later), on the device: one pass
+    // over Q's diagonal and the columns of A, one word read back.
+    h->zd_decided = true;
+    int *flag = h->td.flags.p + 100;
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
+    if (an.n > 0 && an.me > 0)
+      k_zd_weak<<<nblk(an.n), 256, 0, h->stream>>>(an.n, h->td.Qf.dev(), h->td.AT.dev(), flag);
+    int *hs = (int *)h->kept.hpin.p;
+    HIPCHK(hipMemcpyAsync(hs, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->zd_weak = hs[0] != 0;
+    if (h->zd_weak) {  // what the switch to policy 0 will need: the values on the host
+      auto keep = [&](std::vector<double> &dst, const double *src, size_t k) -> int {
+        dst.resize(k);
+        if (!k) return 0;
+        if (h->opts.loc == HQPKKT_LOC_DEVICE || q_only)
+          HIPCHK(hipMemcpy(dst.data(), src, sizeof(double) * k, hipMemcpyDeviceToHost));
+        else
+          std::memcpy(dst.data(), src, sizeof(double) * k);
+        return 0;
+      };
+      if (q_only) Qx = h->td.vals.p, Ax = Qx + an.nq, Cx = Ax + an.na;
+      if ((e = keep(h->hQ, Qx, an.nq)) || (e = keep(h->hA, Ax, an.na)) || (e = keep(h->hC, Cx, an.nc))) return e;
+    }
+  }
+  if (!q_only || h->opts.loc != HQPKKT_LOC_DEVICE) HIPCHK(hipStreamSynchronize(h->stream));
+  h->have_values = true;
+  h->factored = false;
+  return 0;
+}
+
 int hqpkkt_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const double *Cx) {
   return guarded([&]() -> int {
     if (!h) return HQPKKT_E_NULL;
@@ -161,40 +206,7 @@ int hqpkkt_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
     if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, h->stream));
     if (an.nc)
       HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, h->stream));
-    for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
-      if (c->src.count)
-        k_gather_values<<<nblk((long long)c->src.count), 256, 0, h->stream>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
-    if (h->opts.zd_policy < 0 && h->zd_used != 0) {
-      // zd_policy -1: an x whose Hessian diagonal is weak against its coupling to an equality needs the
-      // 2x2 pivot with that equality's multiplier inside its own pivot block.  Tested on EVERY update (the
-      // values of an SQP run change: an identity Hessian may turn weak later), on the device: one pass
-      // over Q's diagonal and the columns of A, one word read back.
-      h->zd_decided = true;
-      int *flag = h->td.flags.p + 100;
-      HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
-      if (an.n > 0 && an.me > 0)
-        k_zd_weak<<<nblk(an.n), 256, 0, h->stream>>>(an.n, h->td.Qf.dev(), h->td.AT.dev(), flag);
-      int *hs = (int *)h->kept.hpin.p;
-      HIPCHK(hipMemcpyAsync(hs, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      h->zd_weak = hs[0] != 0;
-      if (h->zd_weak) {  // what the switch to policy 0 will need: the values on the host
-        auto keep = [&](std::vector<double> &dst, const double *src, size_t k) -> int {
-          dst.resize(k);
-          if (!k) return 0;
-          if (h->opts.loc == HQPKKT_LOC_DEVICE)
-            HIPCHK(hipMemcpy(dst.data(), src, sizeof(double) * k, hipMemcpyDeviceToHost));
-          else
-            std::memcpy(dst.data(), src, sizeof(double) * k);
-          return 0;
-        };
-        if ((e = keep(h->hQ, Qx, an.nq)) || (e = keep(h->hA, Ax, an.na)) || (e = keep(h->hC, Cx, an.nc))) return e;
-      }
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->have_values = true;
-    h->factored = false;
-    return 0;
+    return values_changed(h, false, Qx, Ax, Cx);
   });
 }
 
@@ -590,6 +602,268 @@ int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const dou
     if (!(res_acc < rnorm)) return HQPKKT_E_SING;
   }
   return 0;
+}
+
+// ---- the sparse Q where it lies: hqpkkt_q_values .. hqpkkt_lagrangian_gradient (q_values.hip.h)
+
+// The checks that follow an entry's own NULL and RANGE tests, in the header's order: call order and refused handles
+// (HQPKKT_E_INTERN), the diagonal rule of the entries that write a diagonal (HQPKKT_E_FORMAT; decided on the host from the
+// pattern the handle keeps, tables made once), the device, and what the first call makes on it.
+static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
+  if (!h->analyzed || !h->have_values) return HQPKKT_E_INTERN;
+  if (h->shard_count > 1 || h->an.shard_count > 1) return HQPKKT_E_INTERN;
+  if (h->opts.mode == HQPKKT_MODE_STAGED) {
+    const int f = staged_form(h);
+    if ((f & STAGED_FORM_SHARDED) || (f & (touches_q ? STAGED_FORM_HESS_DENSE : STAGED_FORM_DENSE_DYN))) return HQPKKT_E_INTERN;
+  }
+  const Analysis &an = h->an;
+  TreeDev::QVal &q = h->td.qv;
+  if (touches_q && !q.mapped) {
+    q.h_didx.assign((size_t)an.n, -1), q.h_kind.assign((size_t)an.nq, qv::QV_LOWER);
+    q.bad_diag = false;
+    for (int i = 0; i < an.n; i++) {
+      for (int k = h->pQp[i]; k < h->pQp[i + 1]; k++) {
+        const int c = h->pQi[k];
+        if (c > i) q.h_kind[k] = qv::QV_UPPER;
+        if (c != i) continue;
+        if (q.h_didx[i] >= 0) q.bad_diag = true;  // stored twice
+        q.h_didx[i] = k, q.h_kind[k] = i;
+      }
+      if (q.h_didx[i] < 0) q.bad_diag = true;
+    }
+    q.mapped = true;
+  }
+  if (writes_diag && q.bad_diag) return HQPKKT_E_FORMAT;
+  int e = ensure_device(h);
+  if (e) return e;
+  if (touches_q && !q.didx.p && ((e = q.didx.upload(q.h_didx)) || (e = q.kind.upload(q.h_kind)))) return e;
+  if (h->opts.loc != HQPKKT_LOC_DEVICE && !q.hin.p &&
+      ((e = q.hin.alloc(2 * (size_t)an.n + an.me + an.m + 1)) || (e = q.hout.alloc(2 * (size_t)an.n + 1))))
+    return e;
+  return 0;
+}
+
+// the vectors of one call: the caller's own (device), or copies in the handle's buffers (host)
+struct QvIo {
+  hqpkkt_t *h;
+  size_t in_used = 0, out_used = 0;
+  int nout = 0;
+  struct { double *host, *dev; size_t k; } outs[2];
+  bool host() const { return h->opts.loc != HQPKKT_LOC_DEVICE; }
+  int in(const double *p, size_t k, const double **dev) {
+    *dev = p;
+    if (!p || !host()) return 0;
+    double *b = h->td.qv.hin.p + in_used;
+    in_used += k;
+    if (k) HIPCHK(hipMemcpyAsync(b, p, sizeof(double) * k, hipMemcpyHostToDevice, h->stream));
+    *dev = b;
+    return 0;
+  }
+  void out(double *p, size_t k, double **dev) {
+    *dev = p;
+    if (!p || !host()) return;
+    *dev = h->td.qv.hout.p + out_used;
+    out_used += k;
+    outs[nout].host = p, outs[nout].dev = *dev, outs[nout].k = k, nout++;
+  }
+  int finish() {  // a host caller has its results, and its vectors back, when this returns
+    if (!host()) return 0;
+    for (int i = 0; i < nout; i++)
+      if (outs[i].k) HIPCHK(hipMemcpyAsync(outs[i].host, outs[i].dev, sizeof(double) * outs[i].k, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  }
+};
+
+// lanes per row of the walk over Qf, from its mean row length (as short_rows chooses for the residual's kernels)
+static bool qv_short_q(const hqpkkt_t *h) { return h->an.n > 0 && (double)h->an.Qfull.col.size() / h->an.n < 8.0; }
+static void qv_rows(hqpkkt_t *h, bool stats, const double *x, double *y, double *diag) {
+  const int n = h->an.n;
+  if (n <= 0) return;
+  const TreeDev::QVal &q = h->td.qv;
+  const bool sh = qv_short_q(h);
+  const int grid = nblk(n, sh ? 64 : 16);
+  if (stats && sh) qv::k_qv_rows<4, true><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
+  if (stats && !sh) qv::k_qv_rows<16, true><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
+  if (!stats && sh) qv::k_qv_rows<4, false><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
+  if (!stats && !sh) qv::k_qv_rows<16, false><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
+}
+// Q's values have been written on the device: the state hqpkkt_set_values would leave with them
+static int qv_written(hqpkkt_t *h) {
+  HIPCHK(hipGetLastError());
+  return h->opts.mode == HQPKKT_MODE_STAGED ? staged_values_changed(h, true) : values_changed(h, true, nullptr, nullptr, nullptr);
+}
+
+int hqpkkt_q_values(hqpkkt_t *h, double *Qx) {
+  return guarded([&]() -> int {
+    if (!h || !Qx) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (h->an.nq) HIPCHK(hipMemcpyAsync(Qx, h->td.vals.p, sizeof(double) * h->an.nq, kind, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int hqpkkt_q_product(hqpkkt_t *h, const double *x, double *y) {
+  return guarded([&]() -> int {
+    if (!h || !x || !y) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    QvIo io{h};
+    const double *dx;
+    double *dy;
+    if ((e = io.in(x, (size_t)h->an.n, &dx))) return e;
+    io.out(y, (size_t)h->an.n, &dy);
+    qv_rows(h, false, dx, dy, nullptr);
+    HIPCHK(hipGetLastError());
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_row_stats(hqpkkt_t *h, double *diag, double *offsum) {
+  return guarded([&]() -> int {
+    if (!h || (!diag && !offsum)) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    QvIo io{h};
+    double *dd, *ds;
+    io.out(diag, (size_t)h->an.n, &dd), io.out(offsum, (size_t)h->an.n, &ds);
+    qv_rows(h, true, nullptr, ds, dd);
+    HIPCHK(hipGetLastError());
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_set_diagonal(hqpkkt_t *h, const double *d) {
+  return guarded([&]() -> int {
+    if (!h || !d) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, true);
+    if (e) return e;
+    QvIo io{h};
+    const double *dd;
+    if ((e = io.in(d, (size_t)h->an.n, &dd))) return e;
+    if (h->an.nq) qv::k_qv_reset<<<nblk(h->an.nq), 256, 0, h->stream>>>(h->an.nq, h->td.qv.kind.p, h->td.vals.p, dd, 0.0, 0);
+    if ((e = qv_written(h))) return e;
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_dscale_setup(hqpkkt_t *h, double eps) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
+    int e = qv_prepare(h, true, true);
+    if (e) return e;
+    if (h->an.nq) qv::k_qv_reset<<<nblk(h->an.nq), 256, 0, h->stream>>>(h->an.nq, h->td.qv.kind.p, h->td.vals.p, nullptr, eps, 1);
+    return qv_written(h);
+  });
+}
+
+int hqpkkt_q_gerschgorin(hqpkkt_t *h, double eps) {
+  return guarded([&]() -> int {
+    if (!h) return HQPKKT_E_NULL;
+    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
+    int e = qv_prepare(h, true, true);
+    if (e) return e;
+    TreeDev::QVal &q = h->td.qv;
+    const int n = h->an.n;
+    if (!q.offsum.p && (e = q.offsum.alloc((size_t)n + 1))) return e;
+    qv_rows(h, true, nullptr, q.offsum.p, nullptr);
+    if (n) qv::k_qv_gerschgorin<<<nblk(n), 256, 0, h->stream>>>(n, q.didx.p, q.offsum.p, eps, h->td.vals.p);
+    return qv_written(h);
+  });
+}
+
+int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u) {
+  return guarded([&]() -> int {
+    if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
+    static_assert(qv::QV_REPORT == HQPKKT_DSCALE_REPORT, "the kernels write the report's words");
+    if (!std::isfinite(u->gamma) || u->gamma < 0.0) return HQPKKT_E_RANGE;
+    int e = qv_prepare(h, true, true);
+    if (e) return e;
+    TreeDev::QVal &q = h->td.qv;
+    const int n = h->an.n;
+    if (n <= 0) {
+      q.rep_blocks = 0;
+      return 0;
+    }
+    qv::DsGeom g;
+    g.n = n, g.B = (u->bsize > 0 && u->bsize < n) ? u->bsize : n;
+    g.cpb = (g.B + qv::QV_CHUNK - 1) / qv::QV_CHUNK;
+    g.nblocks = (int)(((long long)n + g.B - 1) / g.B);
+    g.nunits = (long long)g.nblocks * g.cpb;
+    if (q.part.count < 3 * (size_t)g.nunits || q.rep.count < (size_t)qv::QV_REPORT * g.nblocks) {
+      HIPCHK(hipStreamSynchronize(h->stream));  // (a report or an update still in the stream reads the old ones)
+      if ((e = q.part.alloc(3 * (size_t)g.nunits)) || (e = q.rep.alloc((size_t)qv::QV_REPORT * g.nblocks))) return e;
+    }
+    QvIo io{h};
+    const double *ds, *dy;
+    double *dv;
+    if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
+    io.out(u->v, (size_t)n, &dv);
+    double *part = q.part.p, *part2 = q.part.p + 2 * g.nunits;
+    hipStream_t s = h->stream;
+    const bool wave_units = g.B <= 64;  // a block per wavefront (q_values.hip.h)
+    const unsigned ugrid = (unsigned)(wave_units ? (g.nunits + 3) / 4 : g.nunits);
+    if (wave_units)
+      qv::k_qv_ds_sums<1><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
+    else
+      qv::k_qv_ds_sums<4><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
+    qv::k_qv_ds_decide<<<nblk(g.nblocks), 256, 0, s>>>(g, part, u->gamma, q.rep.p);
+    if (wave_units)
+      qv::k_qv_ds_damped<1><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
+    else
+      qv::k_qv_ds_damped<4><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
+    qv::k_qv_ds_outcome<<<nblk(g.nblocks), 256, 0, s>>>(g, part2, q.rep.p);
+    qv::k_qv_ds_apply<<<nblk(n), 256, 0, s>>>(g, q.didx.p, ds, dy, q.rep.p, h->td.vals.p);
+    q.rep_blocks = g.nblocks;
+    if ((e = qv_written(h))) return e;
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
+  return guarded([&]() -> int {
+    if (!h || !out || !n_blocks) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    const TreeDev::QVal &q = h->td.qv;
+    if (q.rep_blocks < 0) return HQPKKT_E_INTERN;
+    *n_blocks = q.rep_blocks;
+    if (cap_blocks < q.rep_blocks) return HQPKKT_E_RANGE;
+    if (q.rep_blocks)
+      HIPCHK(hipMemcpyAsync(out, q.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)q.rep_blocks, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, const double *z, const double *minus, double *out) {
+  return guarded([&]() -> int {
+    if (!h || !c || !out) return HQPKKT_E_NULL;
+    if (h->analyzed && ((h->an.me > 0 && !y) || (h->an.m > 0 && !z))) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, false, false);
+    if (e) return e;
+    const Analysis &an = h->an;
+    const int n = an.n;
+    QvIo io{h};
+    const double *dc, *dy, *dz, *dm;
+    double *dout;
+    if ((e = io.in(c, (size_t)n, &dc)) || (e = io.in(an.me > 0 ? y : nullptr, (size_t)an.me, &dy)) ||
+        (e = io.in(an.m > 0 ? z : nullptr, (size_t)an.m, &dz)) || (e = io.in(minus, (size_t)n, &dm)))
+      return e;
+    io.out(out, (size_t)n, &dout);
+    if (n > 0) {
+      if ((double)(an.na + an.nc) / n < 8.0)
+        qv::k_qv_grad_l<4><<<nblk(n, 64), 256, 0, h->stream>>>(n, h->td.AT.dev(), h->td.CT.dev(), dc, dy, dz, dm, dout);
+      else
+        qv::k_qv_grad_l<16><<<nblk(n, 16), 256, 0, h->stream>>>(n, h->td.AT.dev(), h->td.CT.dev(), dc, dy, dz, dm, dout);
+    }
+    HIPCHK(hipGetLastError());
+    return io.finish();
+  });
 }
 
 int hqpkkt_get_sbw(const hqpkkt_t *h, int *sbw) {

@@ -273,6 +273,15 @@ struct TreeDev {
   DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
   DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
   DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
+  // the entries on the sparse Q where it lies (hqpkkt_q_product .. hqpkkt_lagrangian_gradient; q_values.hip.h), both engines
+  struct QVal {
+    bool mapped = false, bad_diag = false;  // the host tables are made / a row without exactly one stored diagonal
+    std::vector<int> h_didx, h_kind;        // per row the index of its diagonal in Qx (-1: none); per entry its row, QV_UPPER or QV_LOWER
+    DBuf<int> didx, kind;
+    DBuf<double> hin, hout;                 // a host caller's vectors: in (2 n + me + m), out (2 n)
+    DBuf<double> offsum, part, rep;         // Gerschgorin's row pass; DScale's partial sums (3 per unit) and its report
+    long long rep_blocks = -1;              // blocks of the last DScale update since the analysis
+  } qv;
 
   DevTree tree() const {
     return DevTree{piv_start.p, npiv.p,     nbor.p,  parent.p, bptr.p,      bidx.p,     rel.p,
@@ -515,6 +524,10 @@ int staged_dense_products(hqpkkt_t *h, const Vecs &v, const double **x1, const d
 // narrow copies of C' and C in *CT, *C; leaves all four as they are on a handle without wide rows
 void staged_rows_products(hqpkkt_t *h, const Vecs &v, const double **xcw, const double **cw, CsrDev *CT, CsrDev *C);
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out);
+// what staged_set_values does behind its copies into the handle's values; q_only: Q's values alone have changed
+int staged_values_changed(hqpkkt_t *h, bool q_only);
+enum { STAGED_FORM_HESS_DENSE = 1, STAGED_FORM_DENSE_DYN = 2, STAGED_FORM_SHARDED = 4 };
+int staged_form(const hqpkkt_t *h);  // of an analysed STAGED handle
 // hqpkkt.hip
 int solve_vecs(hqpkkt_t *h, const double *z, const double *w, const double *r1, const double *r2, const double *r3,
                const double *r4, double *dx, double *dy, double *dz, double *dw, Vecs &v);

@@ -244,6 +244,12 @@ static int staged_set_request(hqpkkt_t *h, bool in_range, Set set) {
     return set(h->staged_rq);
   });
 }
+// the forms of an analysed STAGED handle that the entries on the sparse Q ask about (hqpkkt.hip, qv_prepare)
+int staged_form(const hqpkkt_t *h) {
+  if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd) return 0;
+  const kktdev::StagedPlan &P = h->sd->plan;
+  return (P.hess_dense ? STAGED_FORM_HESS_DENSE : 0) | (P.dense_dyn ? STAGED_FORM_DENSE_DYN : 0) | (P.sharded ? STAGED_FORM_SHARDED : 0);
+}
 // what the entry points of the dense hand-over ask of the handle (hess: of the dense stage Hessians' as well)
 static bool staged_dense_ready(const hqpkkt_t *h, bool hess = false) {
   return h->analyzed && h->opts.mode == HQPKKT_MODE_STAGED && h->sd && h->sd->plan.dense_dyn && (!hess || h->sd->plan.hess_dense);

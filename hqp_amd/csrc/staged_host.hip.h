@@ -1183,15 +1183,26 @@ int staged_set_values(hqpkkt_t *h, const double *Qx, const double *Ax, const dou
   if (an.nq) HIPCHK(hipMemcpyAsync(h->td.vals.p, Qx, sizeof(double) * an.nq, kind, s));
   if (an.na) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq, Ax, sizeof(double) * an.na, kind, s));
   if (an.nc) HIPCHK(hipMemcpyAsync(h->td.vals.p + an.nq + an.na, Cx, sizeof(double) * an.nc, kind, s));
+  return staged_values_changed(h, false);
+}
+
+// The values Qx | Ax | Cx are in the handle: the CSR copies, the blocks the values scatter into, the staircase check.
+// q_only (the hqpkkt_q_* entries that write Q): A and C are as they were - of the copies Qf alone is gathered again and
+// nothing is scattered (Q's entries are read where they lie: st_add_h; with dense stage Hessians those entries refuse).
+int staged_values_changed(hqpkkt_t *h, bool q_only) {
+  Analysis &an = h->an;
+  StagedDev &d = *h->sd;
+  kktdev::StagedPlan &P = d.plan;
+  hipStream_t s = h->stream;
   for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT, &d.wr.Cn, &d.wr.CTn})
-    if (c->src.count)
+    if (c->src.count && (!q_only || c == &h->td.Qf))
       k_gather_values<<<nblk((long long)c->src.count), 256, 0, s>>>((int)c->src.count, c->src.p, h->td.vals.p, c->val.p);
   HIPCHK(hipMemsetAsync(h->td.flags.p, 0, sizeof(int) * 128, s));
-  if (an.na)
+  if (an.na && !q_only)
     stg::k_st_scatter<<<nblk(an.na), 256, 0, s>>>(an.na, d.tab.a_dst.p, h->td.vals.p + an.nq, d.F.p, d.misc.p);
-  if (P.hess_dense && an.nq)  // Q's values into the blocks Q_k (CSR hand-over)
+  if (P.hess_dense && an.nq && !q_only)  // Q's values into the blocks Q_k (CSR hand-over)
     stg::k_hs_scatter<<<nblk(an.nq), 256, 0, s>>>(an.nq, d.hess.q_dst.p, h->td.vals.p, d.hess.Q.p);
-  if (!P.wr_rows.empty())  // the wide rows of C into their blocks E_k
+  if (!P.wr_rows.empty() && !q_only)  // the wide rows of C into their blocks E_k
     stg::k_st_scatter<<<nblk(an.nc), 256, 0, s>>>(an.nc, d.wr.c_dst.p, h->td.vals.p + an.nq + an.na, d.F.p, d.misc.p);
   const int nchk = (int)P.chk_idx.size();
   if (nchk) stg::k_st_check<<<nblk(nchk), 256, 0, s>>>(nchk, d.tab.chk_idx.p, d.tab.chk_kind.p, h->td.vals.p, h->td.flags.p);

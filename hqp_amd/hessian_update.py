@@ -22,6 +22,11 @@ The safeguards that read a block run on the device as well (staged_hess_guard.hi
 ``lanczos_model``, the device's recurrence in float64, and ``eigen_replay``, the device's evaluation of the tridiagonal T it
 REPORTED, operation by operation.  The device estimates lambda from below by lo - rho (a bracket of T's smallest eigenvalue
 and Lanczos' residual bound) where the reference calls symmeig.
+
+The approximations that work on the sparse Q of the program itself (``Hqp_IpMatrix.q_gerschgorin``, ``q_dscale_setup``,
+``q_dscale_update``; hqpkkt_q_*) have their models at the end: ``q_gerschgorin_model``, ``dscale_terms`` - Hqp_HL_DScale::update
+with the reference's operations and sequential sums - and ``dscale_replay``, the device's decision and update from the sums
+it REPORTED.
 """
 from __future__ import annotations
 
@@ -253,3 +258,99 @@ def eigen_replay(order, g, theta, steps, T):
             d, outcome = f8(theta) - lam, 2 if rho <= f8(EIG_END_REL) * normT else 3
     out.update(lo=float(lo), hi=float(hi), rho=float(rho), lam=float(lam), d=float(d), outcome=outcome)
     return out
+
+
+# ---- the approximations that work on the sparse Q of the program (Hqp_IpMatrix.q_gerschgorin, q_dscale_update) ----
+
+def q_gerschgorin_model(Q, eps):
+    """Hqp_HL_Gerschgorin::update = Hqp_HL::posdef on the sparse Q as ``Hqp_IpMatrix.q_gerschgorin`` applies it, on the CSR
+    triple ``Q`` = (indptr, indices, data) of which the entries with col >= row exist: returns the new data,
+    q_ii <- max(q_ii, fl(sum_{j != i} |q_ij| + eps)) with the reference's macro a > b ? a : b, the sum over row i of the
+    symmetric image; every other value stays."""
+    p, ix, x = (np.asarray(a) for a in Q)
+    x = np.array(x, dtype=np.float64)
+    n = p.size - 1
+    rows = np.repeat(np.arange(n), np.diff(p))
+    up = ix > rows
+    off = np.zeros(n)
+    np.add.at(off, rows[up], np.abs(x[up]))
+    np.add.at(off, ix[up], np.abs(x[up]))
+    t = off + np.float64(eps)
+    dg = np.flatnonzero(ix == rows)
+    q = x[dg]
+    x[dg] = np.where(q > t[rows[dg]], q, t[rows[dg]])
+    return x
+
+
+def _dscale_blocks(n, bsize):
+    B = int(bsize) if 0 < int(bsize) < n else n
+    return [(o, min(o + B, n)) for o in range(0, n, B)] if n else []
+
+
+def _dscale_apply(rep, s, y, q, blocks):
+    """decision, theta, v and both steps of q of every block from the sums in ``rep`` (columns 0 sy, 1 sqs, 2 gamma,
+    4 sv where damped): one numpy operation per rounded operation of Hqp_HL_DScale::update_b_Q, all blocks at once."""
+    nb = len(blocks)
+    if nb == 0:
+        return y.copy(), q.copy(), np.zeros(0, dtype=np.int64), np.ones(0), np.zeros(0)
+    of = np.repeat(np.arange(nb), [e - a for a, e in blocks])  # the block of every variable
+    one = np.float64(1.0)
+    with np.errstate(all="ignore"):
+        sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
+        damp = sy < gamma * sqs
+        theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
+        omt = one - theta
+        sq = s * q
+        v = np.where(damp[of], theta[of] * y + omt[of] * sq, y)
+        sv = np.where(damp, rep[:, 4], sy)
+        finite = np.isfinite(sv) & np.isfinite(sqs)
+        ok = finite & (sv != 0.0) & (sqs != 0.0)
+        outcome = np.where(~finite, 3, np.where(~ok, 2, np.where(damp, 1, 0))).astype(np.int64)
+        t = q - (sq * sq) / sqs[of]
+        qn = np.where(ok[of], t + (v * v) / sv[of], q)
+    return v, qn, outcome, theta, sv
+
+
+def _seq_sum(terms):
+    return np.float64(np.add.accumulate(terms)[-1]) if terms.size else np.float64(0.0)
+
+
+def dscale_terms(s, y, q, gamma=0.2, bsize=0):
+    """Hqp_HL_DScale::update (hqp/Hqp_HL_DScale.C:92-176) on the diagonal ``q`` for the step ``s`` and the change ``y`` of the
+    Lagrangian's gradient, block by block, with the reference's operations and its sequential sums (in_prod): returns
+    (report, v, q_new), ``report`` in the layout of ``Hqp_IpMatrix.q_dscale_report`` - sy, sqs, gamma, theta, sv as used,
+    first index, length, outcome.  As on the device a block whose sv or sqs is not finite is left alone (outcome 3; the
+    reference would write NaN)."""
+    s, y, q = (np.ascontiguousarray(a, dtype=np.float64) for a in (s, y, q))
+    blocks = _dscale_blocks(s.size, bsize)
+    rep = np.zeros((len(blocks), 8))
+    one, g = np.float64(1.0), np.float64(gamma)
+    with np.errstate(all="ignore"):
+        for k, (a, e) in enumerate(blocks):
+            sq = s[a:e] * q[a:e]
+            sy, sqs = _seq_sum(s[a:e] * y[a:e]), _seq_sum(sq * s[a:e])
+            sv = sy
+            if sy < g * sqs:
+                theta = ((one - g) * sqs) / (sqs - sy)
+                sv = _seq_sum(s[a:e] * (theta * y[a:e] + (one - theta) * sq))
+            rep[k, :3] = sy, sqs, g
+            rep[k, 4:7] = sv, a, e - a
+    v, qn, outcome, theta, sv = _dscale_apply(rep, s, y, q, blocks)
+    rep[:, 3], rep[:, 4], rep[:, 7] = theta, sv, outcome
+    return rep, v, qn
+
+
+def dscale_replay(report, s, y, q, bsize=0):
+    """(v, q_new, outcome) of ``Hqp_IpMatrix.q_dscale_update`` (hqpkkt_q_dscale_update) repeated in numpy from the sums the
+    device REPORTED: of ``report``, (blocks, 8), sy (0), sqs (1), gamma (2) and - on a damped block - sv (4) are read.  One
+    numpy operation per device operation: the test sy < fl(gamma sqs), theta = fl(fl((1 - gamma) sqs) / fl(sqs - sy)),
+    v_i = fl(fl(theta y_i) + fl(fl(1 - theta) fl(s_i q_i))), q_i <- fl(q_i - fl(fl(sq_i sq_i) / sqs)), then
+    q_i <- fl(q_i + fl(fl(v_i v_i) / sv)); v = y on a block that is not damped; q stays where sv or sqs is zero (outcome 2)
+    or not finite (3)."""
+    report = np.asarray(report, dtype=np.float64)
+    s, y, q = (np.ascontiguousarray(a, dtype=np.float64) for a in (s, y, q))
+    blocks = _dscale_blocks(s.size, bsize)
+    if report.shape != (len(blocks), 8) or not (s.shape == y.shape == q.shape):
+        raise ValueError("dscale_replay: report of (blocks, 8), s, y and q vectors of one length")
+    v, qn, outcome, _theta, _sv = _dscale_apply(report, s, y, q, blocks)
+    return v, qn, outcome

@@ -309,6 +309,131 @@ class Hqp_IpMatrix:
         _check(getattr(self._L, _entry)(self._h, C.byref(o), *ptrs, C.byref(res)), _entry)
         return x, y, z, w, res.asdict()
 
+    # -- the sparse Q where it lies on the device (hqpkkt_q_*, hqpkkt_lagrangian_gradient) ----------
+    def _q_in(self, a, size, what):
+        """(pointer, what keeps it alive) of an input vector: numpy, or a torch CUDA tensor with device_vectors=True."""
+        if a is None:
+            return None, None
+        if self._device_vectors:
+            if not (hasattr(a, "data_ptr") and a.is_cuda):
+                raise TypeError(f"{what}: device_vectors=True needs torch CUDA float64 tensors")
+            if a.numel() != size or str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                raise KktError(_lib.E_SIZES, what)
+            return C.c_void_p(a.data_ptr()), a
+        if hasattr(a, "data_ptr"):
+            raise TypeError(f"{what}: torch tensors need device_vectors=True")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != size:
+            raise KktError(_lib.E_SIZES, what)
+        return C.c_void_p(a.ctypes.data), a
+
+    def _q_out(self, size):
+        """(pointer, vector) of a result: a numpy array, or a torch CUDA tensor with device_vectors=True."""
+        if self._device_vectors:
+            import torch
+            v = torch.zeros(size, dtype=torch.float64, device=torch.device("cuda", self._dev))
+            return C.c_void_p(v.data_ptr()), v
+        v = np.zeros(size)
+        return C.c_void_p(v.ctypes.data), v
+
+    def _q_sync(self, after=False):
+        """Device vectors are read and written in the handle's stream: what torch has queued for them is over before the
+        call, and the handle's work before torch reads a result."""
+        if self._device_vectors:
+            import torch
+            if after:
+                torch.cuda.synchronize(self._dev)
+            else:
+                torch.cuda.current_stream(self._dev).synchronize()
+
+    def _q_nnz(self):
+        return int(self._keep[0][-1]) if self._keep and len(self._keep[0]) else 0
+
+    def q_values(self):
+        """Qx as it lies in the handle (hqpkkt_q_values): nnz(Q) values in the order of the analysed pattern."""
+        p, v = self._q_out(self._q_nnz())
+        self._q_sync()
+        _check(self._L.hqpkkt_q_values(self._h, p), "q_values")
+        return v
+
+    def q_product(self, x):
+        """y = Q x, Q symmetric from its stored upper entries (hqpkkt_q_product)."""
+        px, kx = self._q_in(x, self.n, "x")
+        py, y = self._q_out(self.n)
+        self._q_sync()
+        _check(self._L.hqpkkt_q_product(self._h, px, py), "q_product")
+        self._q_sync(after=True)
+        return y
+
+    def q_row_stats(self, want_diag=True, want_offsum=True):
+        """(diag, offsum) of Q (hqpkkt_q_row_stats): the stored q_ii (0.0 without one) and the sum of |q_ij| over j != i of
+        the symmetric image; None for the one not wanted."""
+        out = [self._q_out(self.n) if w else (None, None) for w in (want_diag, want_offsum)]
+        self._q_sync()
+        _check(self._L.hqpkkt_q_row_stats(self._h, out[0][0], out[1][0]), "q_row_stats")
+        self._q_sync(after=True)
+        return out[0][1], out[1][1]
+
+    def q_set_diagonal(self, d):
+        """Q <- diag(d) on the stored pattern (hqpkkt_q_set_diagonal): Hqp_HL::init, sp_ident, a restart."""
+        pd, kd = self._q_in(d, self.n, "d")
+        self._q_sync()
+        _check(self._L.hqpkkt_q_set_diagonal(self._h, pd), "q_set_diagonal")
+        self._keep_qv = [kd]
+
+    def q_gerschgorin(self, eps):
+        """Hqp_HL_Gerschgorin::update on the sparse Q (hqpkkt_q_gerschgorin): q_ii <- max(q_ii, sum_{j != i} |q_ij| + eps)."""
+        _check(self._L.hqpkkt_q_gerschgorin(self._h, float(eps)), "q_gerschgorin")
+
+    def q_dscale_setup(self, eps):
+        """Hqp_HL_DScale::setup (hqpkkt_q_dscale_setup): off-diagonals <- 0, q_ii <- max(q_ii, eps)."""
+        _check(self._L.hqpkkt_q_dscale_setup(self._h, float(eps)), "q_dscale_setup")
+
+    def q_dscale_update(self, s, y, gamma=0.2, bsize=0, want_v=False):
+        """Hqp_HL_DScale::update on the diagonal of the sparse Q (hqpkkt_q_dscale_update) for the step ``s`` and the change
+        ``y`` of the Lagrangian's gradient, in blocks of ``bsize`` variables (0: one block).  ``want_v``: returns v as
+        applied, else None.  q_dscale_report() tells what every block did."""
+        ps, ks = self._q_in(s, self.n, "s")
+        py, ky = self._q_in(y, self.n, "y")
+        u = _lib.DScaleUpdate()
+        u.s, u.y, u.gamma, u.bsize = ps.value, py.value, float(gamma), int(bsize)
+        v = None
+        if want_v:
+            pv, v = self._q_out(self.n)
+            u.v = pv.value
+        self._q_sync()
+        _check(self._L.hqpkkt_q_dscale_update(self._h, C.byref(u)), "q_dscale_update")
+        self._keep_qv = [ks, ky, v]
+        if want_v:
+            self._q_sync(after=True)
+        return v
+
+    def q_dscale_report(self):
+        """Per block of the last q_dscale_update() (hqpkkt_q_dscale_report), an array of shape (blocks, 8): sy, sqs, gamma,
+        theta (1 where not damped), sv as used, first index, length and the outcome - 0 updated, 1 updated with damping,
+        2 left alone (sv or sqs is zero), 3 left alone (sv or sqs is not finite).  Waits for the handle's stream."""
+        k = C.c_longlong()
+        out = np.zeros((1, _lib.HQPKKT_DSCALE_REPORT))
+        e = self._L.hqpkkt_q_dscale_report(self._h, C.c_void_p(out.ctypes.data), 1, C.byref(k))
+        if e == _lib.E_RANGE:
+            out = np.zeros((k.value, _lib.HQPKKT_DSCALE_REPORT))
+            e = self._L.hqpkkt_q_dscale_report(self._h, C.c_void_p(out.ctypes.data), k.value, C.byref(k))
+        _check(e, "q_dscale_report")
+        return out[: k.value]
+
+    def lagrangian_gradient(self, c, y, z, minus=None):
+        """Hqp_SqpSolver::grd_L (hqpkkt_lagrangian_gradient): c - A'y - C'z, and minus ``minus`` where given - the
+        difference of two gradients from the second call."""
+        pc, kc = self._q_in(c, self.n, "c")
+        py, ky = self._q_in(y if self.me else None, self.me, "y")
+        pz, kz = self._q_in(z if self.m else None, self.m, "z")
+        pm, km = self._q_in(minus, self.n, "minus")
+        po, out = self._q_out(self.n)
+        self._q_sync()
+        _check(self._L.hqpkkt_lagrangian_gradient(self._h, pc, py, pz, pm, po), "lagrangian_gradient")
+        self._q_sync(after=True)
+        return out
+
     def read_block(self, what, node):
         """Numeric block of a supernode after factor() (tests): 0 panel, 1 inverse of
         L11, 2 X, 3 update block; flat float64 array, column-major."""

@@ -602,7 +602,8 @@ int hqpkkt_bfgs_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * 8 doubles */)
  * given, per stage alpha_0 .. (HQPKKT_EIG_MAX_STEPS doubles), then beta_0 .. (as many); words past the steps are 0.
  * hessian_update.eigen_replay repeats k_he_ritz in numpy from the reported T.  HQPKKT_E_INTERN before the first control
  * since the analysis.
- * Not built: sharded handles, the CSR hand-over, and the reference's Hqp_HL_DScale. */
+ * Not built: sharded handles and the CSR hand-over.  (The reference's Hqp_HL_DScale works on the sparse Q: the hqpkkt_q_*
+ * entries below.) */
 #define HQPKKT_EIG_MAX_STEPS 128
 #define HQPKKT_EIG_REPORT 10
 #define HQPKKT_EIG_END_REL 9.094947017729282e-13 /* 2^-40 */
@@ -617,6 +618,77 @@ int hqpkkt_restart_stage_hessians(hqpkkt_t *h, double eps, const unsigned char *
 int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps);
 int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *e);
 int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * HQPKKT_EIG_MAX_STEPS */);
+/* ---- The sparse Q where it lies on the device: the reference's Hessian approximations that work on Hqp_Program::Q itself
+ * (Hqp_HL::init, Hqp_HL_Gerschgorin, Hqp_HL_DScale - what hqp_cute.tcl selects next to RedSpBKP) and grd_L of
+ * Hqp_SqpSolver, without a round trip of Qx | Ax | Cx through hqpkkt_set_values.  Kernels: csrc/q_values.hip.h.
+ * Handles: FULL, REDUCED and STAGED ones that have had values.  HQPKKT_E_INTERN otherwise, on a sharded handle, for every
+ * hqpkkt_q_* entry on a STAGED handle with HQPKKT_HESS_DENSE (its Hessians are the blocks: the stage-Hessian entries
+ * above), and for hqpkkt_lagrangian_gradient on a STAGED handle analysed by hqpkkt_analyze_staged (the dynamics are
+ * not in A then; not built).  hqpkkt_lagrangian_gradient does not touch Q and is accepted with dense stage Hessians.
+ * Vectors hold n doubles (y: me, z: m), pointers per opts.loc.  Host vectors go through buffers the handle owns (made
+ * by the first call) and the call returns when the stream has read or written them; device vectors are read and written
+ * asynchronously in the handle's stream.  Plain loads and stores, no atomics.
+ * Entries of Q: only the stored entries with col >= row exist, as for the whole library; entries with col < row are never
+ * read and never written.  The diagonal of row i is its stored (i, i).  The entries that write the diagonal
+ * (hqpkkt_q_set_diagonal, hqpkkt_q_gerschgorin, hqpkkt_q_dscale_setup, hqpkkt_q_dscale_update) return HQPKKT_E_FORMAT where a
+ * row has no stored diagonal or more than one - the reference inserts one; the pattern here is fixed - decided on the host
+ * from the analysed pattern, before any launch; the map row -> index of its diagonal is built once.
+ * Checks, before anything is launched, in this order: HQPKKT_E_NULL; HQPKKT_E_RANGE (eps not finite or <= 0, gamma not
+ * finite or < 0); HQPKKT_E_INTERN (not analysed, no values yet, a refused handle; hqpkkt_q_dscale_report: no update since the
+ * analysis - and its HQPKKT_E_RANGE for cap_blocks comes behind that, with *n_blocks set); HQPKKT_E_FORMAT; HQPKKT_E_DEVICE.
+ * Values: every operation named here is rounded once (kernels without contraction); max(a, b) is the reference's macro,
+ * a > b ? a : b.
+ *   hqpkkt_q_values     Qx out: nnz(Q) doubles as they lie in the handle; waits for the stream.
+ *   hqpkkt_q_product    y_i = sum_j q_ij x_j over row i of the symmetric image of the stored upper entries (sp_mv_symmlt);
+ *                       4 or 16 lanes a row by the mean row length, lane l takes the row's entries l, l + lanes, .. by
+ *                       fused multiply-adds, the lanes add up in a fixed tree: the order depends on the row alone.
+ *   hqpkkt_q_row_stats  diag_i = the stored q_ii (0.0 without one), offsum_i = sum |q_ij|, j != i, over the same row walk;
+ *                       either may be NULL, not both.  A NaN stays in its row and in its image's row.
+ *   hqpkkt_q_set_diagonal   every stored upper off-diagonal entry <- +0.0, q_ii <- d_i (Hqp_HL::init, sp_ident, a restart).
+ *   hqpkkt_q_gerschgorin    the row pass, then q_ii <- max(q_ii, fl(offsum_i + eps)): one kernel, a thread per variable, the
+ *                       diagonal entries alone (Hqp_HL_Gerschgorin::update = Hqp_HL::posdef).
+ *   hqpkkt_q_dscale_setup   off-diagonals <- +0.0, q_ii <- max(q_ii, eps) (Hqp_HL_DScale::setup).
+ *   hqpkkt_q_dscale_update  Hqp_HL_DScale::update / update_b_Q.  Block b: the variables [b B, min((b + 1) B, n)), B = bsize > 0 ?
+ *                       bsize : n.  Per block, q the diagonal: sq_i = fl(s_i q_i), sy = sum s_i y_i, sqs = sum sq_i s_i; damped
+ *                       where sy < fl(gamma sqs): theta = fl(fl((1 - gamma) sqs) / fl(sqs - sy)), v_i = fl(fl(theta y_i) +
+ *                       fl((1 - theta) sq_i)), sv = sum s_i v_i; otherwise v = y, sv = sy; then q_i <- fl(q_i - fl(fl(sq_i sq_i)
+ *                       / sqs)) and q_i <- fl(q_i + fl(fl(v_i v_i) / sv)) - divisions, as in the reference.  Off-diagonal
+ *                       entries are neither read nor written.  A block with sv or sqs zero is left alone (the reference),
+ *                       and so is one with sv or sqs not finite (the rule of hqpkkt_bfgs_update_stage_hessians; the reference
+ *                       writes NaN); a NaN in one block's y reaches no other block.  The sums: chunks of 4096 entries from
+ *                       the block's first index, a chunk by 256 threads - thread t takes t, t + 256, .. by fused
+ *                       multiply-adds, a wavefront's butterfly, the four wavefronts in order -, a block's chunks added in
+ *                       ascending order by one thread: fixed by the block's length alone, not by bsize, the number of
+ *                       blocks or the grid; the same bits from run to run and in all three modes.  v (optional): the
+ *                       vector as applied, y where a block is not damped.
+ *   hqpkkt_q_dscale_report  waits for the stream; HQPKKT_DSCALE_REPORT doubles per block of the last update: 0 sy, 1 sqs,
+ *                       2 gamma, 3 theta (1.0 undamped), 4 sv as used, 5 first index, 6 length, 7 outcome - 0 updated,
+ *                       1 updated with damping, 2 left alone (zero), 3 left alone (not finite).  out is a HOST array.
+ *                       hessian_update.dscale_replay repeats the decision and the update in numpy from the reported sums.
+ *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
+ *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
+ *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
+ *                       be NULL where me / m is 0.
+ * After an entry that writes Q the handle is in the state hqpkkt_set_values would leave with these values of Q and the A,
+ * C it has: not factored; of the CSR copies the image of Q alone is gathered again; with zd_policy < 0 the weak-diagonal
+ * test runs again, and the host copies kept for the switch of placement are refreshed from the device where it says weak. */
+int hqpkkt_q_values(hqpkkt_t *h, double *Qx);
+int hqpkkt_q_product(hqpkkt_t *h, const double *x, double *y);
+int hqpkkt_q_row_stats(hqpkkt_t *h, double *diag, double *offsum);
+int hqpkkt_q_set_diagonal(hqpkkt_t *h, const double *d);
+int hqpkkt_q_gerschgorin(hqpkkt_t *h, double eps);
+int hqpkkt_q_dscale_setup(hqpkkt_t *h, double eps);
+typedef struct hqpkkt_dscale_update {
+  const double *s, *y; /* the step and the change of the Lagrangian's gradient, n doubles each */
+  double gamma;        /* Powell's damping (the reference's _gamma, 0.2) */
+  int bsize;           /* the reference's _bsize; <= 0: one block of everything */
+  double *v;           /* optional, n doubles: the vector as applied */
+} hqpkkt_dscale_update;
+int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u);
+#define HQPKKT_DSCALE_REPORT 8
+int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
+int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, const double *z,
+                               const double *minus /* or NULL */, double *out);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of
  * 10^6 variables needs (K = 200 stages of 5000 states: the CSR form of fx alone would hold
  * 5*10^9 entries, beyond int32 row pointers; Hqp_IpLQDOCP::update extracts exactly these dense

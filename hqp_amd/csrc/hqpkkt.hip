@@ -637,56 +637,22 @@ static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
   int e = ensure_device(h);
   if (e) return e;
   if (touches_q && !q.didx.p && ((e = q.didx.upload(q.h_didx)) || (e = q.kind.upload(q.h_kind)))) return e;
-  if (h->opts.loc != HQPKKT_LOC_DEVICE && !q.hin.p &&
-      ((e = q.hin.alloc(2 * (size_t)an.n + an.me + an.m + 1)) || (e = q.hout.alloc(2 * (size_t)an.n + 1))))
-    return e;
-  return 0;
+  return CallerVecs{h}.ready();
 }
-
-// the vectors of one call: the caller's own (device), or copies in the handle's buffers (host)
-struct QvIo {
-  hqpkkt_t *h;
-  size_t in_used = 0, out_used = 0;
-  int nout = 0;
-  struct { double *host, *dev; size_t k; } outs[2];
-  bool host() const { return h->opts.loc != HQPKKT_LOC_DEVICE; }
-  int in(const double *p, size_t k, const double **dev) {
-    *dev = p;
-    if (!p || !host()) return 0;
-    double *b = h->td.qv.hin.p + in_used;
-    in_used += k;
-    if (k) HIPCHK(hipMemcpyAsync(b, p, sizeof(double) * k, hipMemcpyHostToDevice, h->stream));
-    *dev = b;
-    return 0;
-  }
-  void out(double *p, size_t k, double **dev) {
-    *dev = p;
-    if (!p || !host()) return;
-    *dev = h->td.qv.hout.p + out_used;
-    out_used += k;
-    outs[nout].host = p, outs[nout].dev = *dev, outs[nout].k = k, nout++;
-  }
-  int finish() {  // a host caller has its results, and its vectors back, when this returns
-    if (!host()) return 0;
-    for (int i = 0; i < nout; i++)
-      if (outs[i].k) HIPCHK(hipMemcpyAsync(outs[i].host, outs[i].dev, sizeof(double) * outs[i].k, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-};
 
 // lanes per row of the walk over Qf, from its mean row length (as short_rows chooses for the residual's kernels)
 static bool qv_short_q(const hqpkkt_t *h) { return h->an.n > 0 && (double)h->an.Qfull.col.size() / h->an.n < 8.0; }
+// the instances of k_qv_rows by [stats][short rows], of the DScale passes by [a block per wavefront]
+using QvRowsFn = decltype(&qv::k_qv_rows<4, true>);
+static const QvRowsFn qv_rows_kernels[2][2] = {{qv::k_qv_rows<16, false>, qv::k_qv_rows<4, false>}, {qv::k_qv_rows<16, true>, qv::k_qv_rows<4, true>}};
+static const decltype(&qv::k_qv_ds_sums<1>) qv_ds_sums_kernels[2] = {qv::k_qv_ds_sums<4>, qv::k_qv_ds_sums<1>};
+static const decltype(&qv::k_qv_ds_damped<1>) qv_ds_damped_kernels[2] = {qv::k_qv_ds_damped<4>, qv::k_qv_ds_damped<1>};
 static void qv_rows(hqpkkt_t *h, bool stats, const double *x, double *y, double *diag) {
   const int n = h->an.n;
   if (n <= 0) return;
   const TreeDev::QVal &q = h->td.qv;
   const bool sh = qv_short_q(h);
-  const int grid = nblk(n, sh ? 64 : 16);
-  if (stats && sh) qv::k_qv_rows<4, true><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
-  if (stats && !sh) qv::k_qv_rows<16, true><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
-  if (!stats && sh) qv::k_qv_rows<4, false><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
-  if (!stats && !sh) qv::k_qv_rows<16, false><<<grid, 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
+  qv_rows_kernels[stats][sh]<<<nblk(n, sh ? 64 : 16), 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
 }
 // Q's values have been written on the device: the state hqpkkt_set_values would leave with them
 static int qv_written(hqpkkt_t *h) {
@@ -711,7 +677,7 @@ int hqpkkt_q_product(hqpkkt_t *h, const double *x, double *y) {
     if (!h || !x || !y) return HQPKKT_E_NULL;
     int e = qv_prepare(h, true, false);
     if (e) return e;
-    QvIo io{h};
+    CallerVecs io{h};
     const double *dx;
     double *dy;
     if ((e = io.in(x, (size_t)h->an.n, &dx))) return e;
@@ -727,7 +693,7 @@ int hqpkkt_q_row_stats(hqpkkt_t *h, double *diag, double *offsum) {
     if (!h || (!diag && !offsum)) return HQPKKT_E_NULL;
     int e = qv_prepare(h, true, false);
     if (e) return e;
-    QvIo io{h};
+    CallerVecs io{h};
     double *dd, *ds;
     io.out(diag, (size_t)h->an.n, &dd), io.out(offsum, (size_t)h->an.n, &ds);
     qv_rows(h, true, nullptr, ds, dd);
@@ -741,7 +707,7 @@ int hqpkkt_q_set_diagonal(hqpkkt_t *h, const double *d) {
     if (!h || !d) return HQPKKT_E_NULL;
     int e = qv_prepare(h, true, true);
     if (e) return e;
-    QvIo io{h};
+    CallerVecs io{h};
     const double *dd;
     if ((e = io.in(d, (size_t)h->an.n, &dd))) return e;
     if (h->an.nq) qv::k_qv_reset<<<nblk(h->an.nq), 256, 0, h->stream>>>(h->an.nq, h->td.qv.kind.p, h->td.vals.p, dd, 0.0, 0);
@@ -798,7 +764,7 @@ int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u) {
       HIPCHK(hipStreamSynchronize(h->stream));  // (a report or an update still in the stream reads the old ones)
       if ((e = q.part.alloc(3 * (size_t)g.nunits)) || (e = q.rep.alloc((size_t)qv::QV_REPORT * g.nblocks))) return e;
     }
-    QvIo io{h};
+    CallerVecs io{h};
     const double *ds, *dy;
     double *dv;
     if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
@@ -807,15 +773,9 @@ int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u) {
     hipStream_t s = h->stream;
     const bool wave_units = g.B <= 64;  // a block per wavefront (q_values.hip.h)
     const unsigned ugrid = (unsigned)(wave_units ? (g.nunits + 3) / 4 : g.nunits);
-    if (wave_units)
-      qv::k_qv_ds_sums<1><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
-    else
-      qv::k_qv_ds_sums<4><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
+    qv_ds_sums_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
     qv::k_qv_ds_decide<<<nblk(g.nblocks), 256, 0, s>>>(g, part, u->gamma, q.rep.p);
-    if (wave_units)
-      qv::k_qv_ds_damped<1><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
-    else
-      qv::k_qv_ds_damped<4><<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
+    qv_ds_damped_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
     qv::k_qv_ds_outcome<<<nblk(g.nblocks), 256, 0, s>>>(g, part2, q.rep.p);
     qv::k_qv_ds_apply<<<nblk(n), 256, 0, s>>>(g, q.didx.p, ds, dy, q.rep.p, h->td.vals.p);
     q.rep_blocks = g.nblocks;
@@ -848,7 +808,7 @@ int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, co
     if (e) return e;
     const Analysis &an = h->an;
     const int n = an.n;
-    QvIo io{h};
+    CallerVecs io{h};
     const double *dc, *dy, *dz, *dm;
     double *dout;
     if ((e = io.in(c, (size_t)n, &dc)) || (e = io.in(an.me > 0 ? y : nullptr, (size_t)an.me, &dy)) ||

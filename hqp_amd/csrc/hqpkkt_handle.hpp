@@ -278,10 +278,13 @@ struct TreeDev {
     bool mapped = false, bad_diag = false;  // the host tables are made / a row without exactly one stored diagonal
     std::vector<int> h_didx, h_kind;        // per row the index of its diagonal in Qx (-1: none); per entry its row, QV_UPPER or QV_LOWER
     DBuf<int> didx, kind;
-    DBuf<double> hin, hout;                 // a host caller's vectors: in (2 n + me + m), out (2 n)
     DBuf<double> offsum, part, rep;         // Gerschgorin's row pass; DScale's partial sums (3 per unit) and its report
     long long rep_blocks = -1;              // blocks of the last DScale update since the analysis
   } qv;
+  // a host caller's vectors of those entries and of the entries on the dense stage Hessians (CallerVecs, which makes them)
+  struct CallerBufs {
+    DBuf<double> in, out;
+  } cv;
 
   DevTree tree() const {
     return DevTree{piv_start.p, npiv.p,     nbor.p,  parent.p, bptr.p,      bidx.p,     rel.p,
@@ -437,6 +440,53 @@ struct Vecs {
 
 struct OutPtrs {
   double *dx, *dy, *dz, *dw;
+};
+
+// The caller's vectors of one call of an entry on the sparse Q (hqpkkt.hip) or on the dense stage Hessians
+// (staged_hess_host.hip.h): device vectors are handed through where they lie and finish() does nothing; host vectors are
+// copied through the handle's two buffers (TreeDev::CallerBufs) in the handle's stream, and finish() copies the outputs
+// back and waits - a host caller has its results, and its vectors back, when it returns.  At most 5 inputs and 2 outputs,
+// a null vector takes no room.  ready() makes the buffers at the first host call, for the largest need of any entry, so
+// they are never regrown under work still in the stream; it is called outside every capture.
+// as_host: the vectors are host arrays whatever opts.loc says (the debug entries)
+struct CallerVecs {
+  hqpkkt_t *h;
+  bool as_host = false;
+  size_t in_used = 0, out_used = 0;
+  int nout = 0;
+  struct { double *host, *dev; size_t k; } outs[2];
+  bool host() const { return as_host || h->opts.loc != HQPKKT_LOC_DEVICE; }
+  int ready() {
+    TreeDev::CallerBufs &b = h->td.cv;
+    if (!host() || b.in.p) return 0;
+    const size_t n = (size_t)h->an.n;
+    int e;
+    if ((e = b.in.alloc(std::max((size_t)(HQPKKT_HESS_UPDATE_RANK + 1) * n, 2 * n + h->an.me + h->an.m) + 1)) || (e = b.out.alloc(2 * n + 1))) return e;
+    return 0;
+  }
+  int in(const double *p, size_t k, const double **dev) {
+    *dev = p;
+    if (!p || !host()) return 0;
+    double *b = h->td.cv.in.p + in_used;
+    in_used += k;
+    if (k) HIPCHK(hipMemcpyAsync(b, p, sizeof(double) * k, hipMemcpyHostToDevice, h->stream));
+    *dev = b;
+    return 0;
+  }
+  void out(double *p, size_t k, double **dev) {
+    *dev = p;
+    if (!p || !host()) return;
+    *dev = h->td.cv.out.p + out_used;
+    out_used += k;
+    outs[nout].host = p, outs[nout].dev = *dev, outs[nout].k = k, nout++;
+  }
+  int finish() {
+    if (!host()) return 0;
+    for (int i = 0; i < nout; i++)
+      if (outs[i].k) HIPCHK(hipMemcpyAsync(outs[i].host, outs[i].dev, sizeof(double) * outs[i].k, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  }
 };
 
 // replay (or first capture) of a kernel sequence as a hipGraph; falls back to

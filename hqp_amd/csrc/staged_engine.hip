@@ -1,6 +1,7 @@
 // The STAGED engine (HQPKKT_MODE_STAGED, staged.hip.h / staged_host.hip.h): its entry points of the C ABI, what the
 // other units call (factor, step, the dense dynamics' share of the residual products), and the debug entry points that
-// read a handle.  The hooks that stand outside a handle follow in staged_hooks.hip.h.
+// read a handle.  The entries on the dense stage Hessians are staged_hess_host.hip.h, the hooks that stand outside a
+// handle staged_hooks.hip.h: both parts of this unit.
 #include "hqpkkt_handle.hpp"
 
 #include <algorithm>
@@ -264,74 +265,8 @@ static int staged_staging_used(hqpkkt_t *h, const double *src) {
     }
   return 0;
 }
-// the per-stage descriptors of an update launch (k_hu_update) to the device: through the pinned words, in the handle's
-// stream; buffers and event are made by the first call
-static int staged_hu_descriptors(hqpkkt_t *h, StagedDev &d, const std::vector<stg::HuDesc> &hd) {
-  int e;
-  if (!d.hess.hu_desc.p) {
-    if ((e = d.hess.hu_desc.alloc(hd.size()))) return e;
-    HIPCHK(d.hess.hu_hdesc.alloc(hd.size(), hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&d.hess.hu_ev.h, hipEventDisableTiming));
-  } else
-    HIPCHK(hipEventSynchronize(d.hess.hu_ev));  // (the copy of the last call's descriptors out of the pinned words)
-  std::copy(hd.begin(), hd.end(), d.hess.hu_hdesc.p);
-  HIPCHK(hipMemcpyAsync(d.hess.hu_desc.p, d.hess.hu_hdesc.p, sizeof(stg::HuDesc) * hd.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipEventRecord(d.hess.hu_ev, h->stream));
-  return 0;
-}
-// the damping factor of the BFGS update as hessian_update.bfgs_terms forms it, operation by operation (no contraction)
-static double bfgs_gamma_eff(double gamma, double alpha) {
-#pragma clang fp contract(off)
-  if (gamma >= 0.0) return gamma;
-  const double g = -gamma, omg = 1.0 + gamma, oma = 1.0 - alpha;
-  const double t = omg * oma;
-  return g + t;
-}
-// what the safeguards of the dense stage Hessians (staged_hess_guard.hip.h) ask of the handle: the dense form with the
-// dense hand-over, and - they read the blocks - every block of nonzero order arrived since the analysis (need: of the
-// stages it marks alone)
-static int staged_hg_ready(const hqpkkt_t *h, const unsigned char *need) {
-  if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
-  const StagedDev &d = *h->sd;
-  const int K1 = d.plan.K + 1;
-  for (int k = 0; k < K1; k++)
-    if (d.plan.hess_order(k) > 0 && (!need || need[k]) && ((int)d.hess.set.size() != K1 || !d.hess.set[k])) return HQPKKT_E_INTERN;
-  return 0;
-}
-// ... their descriptors and buffers, made by the first call of any of them (outside every capture)
-static int staged_hg_prepare(StagedDev &d) {
-  StagedDev::Hessians &q = d.hess;
-  if (q.hg_desc.p) return 0;
-  const kktdev::StagedPlan &P = d.plan;
-  const int K1 = P.K + 1;
-  std::vector<stg::HgDesc> gd(K1);
-  q.hg_slots = 0, q.hg_tiles_max = q.hg_nz_max = 0;
-  for (int k = 0; k < K1; k++) {
-    const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
-    const bool packed = nz > 0 && P.stage_packed(k);
-    gd[k] = stg::HgDesc{P.oQ[k], q.hg_slots, P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, packed ? (int)P.hess_tiles(nz) : 0};
-    if (packed) q.hg_slots += (long long)nt * nt * stg::HP_T;
-    q.hg_tiles_max = std::max(q.hg_tiles_max, gd[k].tiles), q.hg_nz_max = std::max(q.hg_nz_max, nz);
-  }
-  int e;
-  if ((e = q.hg_scr.alloc((size_t)(2 * q.hg_slots) + 1)) || (e = q.hg_vec.alloc(4 * (size_t)P.n + 1)) || (e = q.he_st.alloc((size_t)K1 * stg::HE_STATE)) ||
-      (e = q.he_T.alloc((size_t)K1 * 2 * stg::HE_MAX_STEPS)) || (e = q.he_rep.alloc((size_t)K1 * stg::HE_REPORT)) || (e = q.he_floor.alloc(K1)))
-    return e;
-  HIPCHK(q.he_hfloor.alloc(K1, hipHostMallocDefault));
-  HIPCHK(hipEventCreateWithFlags(&q.he_ev.h, hipEventDisableTiming));
-  return q.hg_desc.upload(gd);
-}
-// ... and the row pass: rowmax and offsum (either may be null) of every stage, device vectors of n
-static void staged_hg_rows(hqpkkt_t *h, StagedDev &d, double *rowmax, double *offsum) {
-  StagedDev::Hessians &q = d.hess;
-  const unsigned K1 = (unsigned)d.plan.K + 1;
-  if (q.hs_nz_max > 0)
-    KLAUNCH(h, KC_VECTOR, stg::k_hg_rows<<<dim3((unsigned)std::min((q.hs_nz_max + 3) / 4, 1024), K1), 256, 0, h->stream>>>(q.hg_desc.p, q.Q.p, rowmax, offsum));
-  if (q.hg_tiles_max > 0) {
-    KLAUNCH(h, KC_VECTOR, stg::k_hg_tiles<<<dim3((unsigned)q.hg_tiles_max, K1), 256, 0, h->stream>>>(q.hg_desc.p, q.Q.p, q.hg_scr.p, q.hg_scr.p + q.hg_slots));
-    KLAUNCH(h, KC_VECTOR, stg::k_hg_finish<<<dim3((unsigned)q.hp_nt_max, K1), stg::HP_T, 0, h->stream>>>(q.hg_desc.p, q.hg_scr.p, q.hg_scr.p + q.hg_slots, rowmax, offsum));
-  }
-}
+
+#include "staged_hess_host.hip.h"
 
 extern "C" {
 
@@ -494,415 +429,6 @@ int hqpkkt_set_stage_block(hqpkkt_t *h, int k, const double *F, long long ldF) {
     if ((int)d.blocks_set.size() != P.K) d.blocks_set.assign(P.K, 0);
     d.blocks_set[k] = 1;
     h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_set_stage_hessian(hqpkkt_t *h, int k, const double *Q, long long ldQ) {
-  return guarded([&]() -> int {
-    if (!h || !Q) return HQPKKT_E_NULL;
-    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
-    int e;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    StagedDev &d = *h->sd;
-    const kktdev::StagedPlan &P = d.plan;
-    if (k < 0 || k > P.K) return HQPKKT_E_RANGE;
-    const int nz = P.hess_order(k);
-    if (ldQ < nz) return HQPKKT_E_SIZES;
-    HIPCHK(hipSetDevice(h->opts.device));
-    const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (nz > 0 && P.stage_packed(k)) {
-      // packed lower tiles: k_hp_pack reads a device block where it lies; of a host block the rows come in groups of
-      // HESS_COPY_ROWS, every group from its first column on, into the staging block (reused in stream order)
-      const double *src = Q;
-      long long lds = ldQ;
-      if (kind == hipMemcpyHostToDevice) {
-        if (d.hess.stage.count < (size_t)P.q_stage_elems && (e = d.hess.stage.alloc((size_t)P.q_stage_elems))) return e;
-        lds = P.ldQ[k], src = d.hess.stage.p;
-        for (int r = 0; r < nz; r += P.HESS_COPY_ROWS)
-          HIPCHK(hipMemcpy2DAsync(d.hess.stage.p + (long long)r * lds + r, sizeof(double) * lds, Q + (long long)r * ldQ + r, sizeof(double) * ldQ,
-                                  sizeof(double) * (nz - r), std::min(P.HESS_COPY_ROWS, nz - r), kind, h->stream));
-      }
-      stg::k_hp_pack<<<dim3((unsigned)P.hess_tiles(nz), 16), 256, 0, h->stream>>>(src, lds, nz, d.hess.Q.p + P.oQ[k]);
-    } else if (nz > 0) {  // the caller's nz columns of every row, then the strict lower triangle from the upper one
-      double *dst = d.hess.Q.p + P.oQ[k];
-      HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * P.ldQ[k], Q, sizeof(double) * ldQ, sizeof(double) * nz, nz, kind, h->stream));
-      const unsigned T = (unsigned)((nz + stg::HS_TILE - 1) / stg::HS_TILE);
-      stg::k_hs_mirror<<<T * (T + 1) / 2, 256, 0, h->stream>>>(dst, P.ldQ[k], nz, (int)T);
-    }
-    if ((e = staged_staging_used(h, Q))) return e;
-    if ((int)d.hess.set.size() != P.K + 1) d.hess.set.assign(P.K + 1, 0);
-    d.hess.set[k] = 1;
-    h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_debug_stage_hessian(hqpkkt_t *h, int k, double *out, long long cap, long long *len) {
-  return guarded([&]() -> int {
-    if (!h || !len) return HQPKKT_E_NULL;
-    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
-    const kktdev::StagedPlan &P = h->sd->plan;
-    if (k < 0 || k > P.K) return HQPKKT_E_RANGE;
-    const long long elems = (long long)P.hess_order(k) * P.ldQ[k];
-    *len = elems;
-    if (!out) return 0;
-    if (cap < elems) return HQPKKT_E_SIZES;
-    HIPCHK(hipSetDevice(h->opts.device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (elems && P.stage_packed(k)) {  // the unpacked view: entry (i, j) out of its stored tile, zero padding
-      const int T = P.HESS_T, nz = P.hess_order(k);
-      std::vector<double> t((size_t)P.hess_tiles(nz) * T * T);
-      HIPCHK(hipMemcpy(t.data(), h->sd->hess.Q.p + P.oQ[k], sizeof(double) * t.size(), hipMemcpyDeviceToHost));
-      std::fill(out, out + elems, 0.0);
-      for (int i = 0; i < nz; i++)
-        for (int j = 0; j < nz; j++) {
-          const int a = std::max(i, j) / T, b = std::min(i, j) / T;
-          const size_t tile = ((size_t)a * (a + 1) / 2 + b) * T * T;
-          out[(long long)i * P.ldQ[k] + j] = i / T >= j / T ? t[tile + (size_t)(i % T) * T + j % T] : t[tile + (size_t)(j % T) * T + i % T];
-        }
-      return 0;
-    }
-    if (elems) HIPCHK(hipMemcpy(out, h->sd->hess.Q.p + P.oQ[k], sizeof(double) * elems, hipMemcpyDeviceToHost));
-    return 0;
-  });
-}
-
-int hqpkkt_debug_hess_symv(hqpkkt_t *h, const double *x, double *y) {
-  return guarded([&]() -> int {
-    if (!h || !x || !y) return HQPKKT_E_NULL;
-    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    const size_t n = (size_t)d.plan.n;
-    HIPCHK(hipSetDevice(h->opts.device));
-    int e;
-    if (!d.hess.x.p && (e = d.hess.x.alloc(n + 1))) return e;  // (the tests' operand: made here, outside every capture)
-    // hess_y is the buffer the residual's launches read: everything here goes to the handle's stream, behind whatever
-    // residual is still in it, and is over when this call returns
-    HIPCHK(hipMemcpyAsync(d.hess.x.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    staged_hess_symv(h, d, d.hess.x.p, d.hess.y.p);
-    HIPCHK(hipMemcpyAsync(y, d.hess.y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-int hqpkkt_debug_hess_symv_timed(hqpkkt_t *h, const double *x, double *y, int reps, double *ms) {
-  return guarded([&]() -> int {
-    if (!h || !x || !y || !ms) return HQPKKT_E_NULL;
-    if (reps < 1) return HQPKKT_E_RANGE;
-    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    const size_t n = (size_t)d.plan.n;
-    HIPCHK(hipSetDevice(h->opts.device));
-    int e;
-    if (!d.hess.x.p && (e = d.hess.x.alloc(n + 1))) return e;
-    EventOwner t0, t1;
-    HIPCHK(hipEventCreate(&t0.h));
-    HIPCHK(hipEventCreate(&t1.h));
-    HIPCHK(hipMemcpyAsync(d.hess.x.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    staged_hess_symv(h, d, d.hess.x.p, d.hess.y.p);  // (one product ahead of the timed ones)
-    HIPCHK(hipEventRecord(t0, h->stream));
-    for (int r = 0; r < reps; r++) staged_hess_symv(h, d, d.hess.x.p, d.hess.y.p);
-    HIPCHK(hipEventRecord(t1, h->stream));
-    HIPCHK(hipMemcpyAsync(y, d.hess.y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, t0, t1));
-    *ms = (double)t / reps;
-    return 0;
-  });
-}
-
-int hqpkkt_hessian_product(hqpkkt_t *h, const double *x, double *y) {
-  if (h && h->opts.loc != HQPKKT_LOC_DEVICE) return hqpkkt_debug_hess_symv(h, x, y);  // (host vectors: the hook's own path)
-  return guarded([&]() -> int {
-    if (!h || !x || !y) return HQPKKT_E_NULL;
-    if (!h->sd || !h->uploaded || !h->sd->plan.hess_dense) return HQPKKT_E_INTERN;
-    HIPCHK(hipSetDevice(h->opts.device));
-    staged_hess_symv(h, *h->sd, x, y);  // (the same launches on the caller's vectors)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-int hqpkkt_update_stage_hessians(hqpkkt_t *h, const hqpkkt_hess_update *u) {
-  return guarded([&]() -> int {
-    if (!h || !u) return HQPKKT_E_NULL;
-    static_assert(stg::HU_RANK == HQPKKT_HESS_UPDATE_RANK, "the kernel's descriptor holds the coefficients");
-    const int r = u->r;
-    if (r < 0 || r > HQPKKT_HESS_UPDATE_RANK) return HQPKKT_E_RANGE;
-    if (r > 0 && (!u->U || !u->coef)) return HQPKKT_E_NULL;
-    for (int j = 0; j < r; j++)
-      if (!u->U[j]) return HQPKKT_E_NULL;
-    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    const kktdev::StagedPlan &P = d.plan;
-    const int K1 = P.K + 1;
-    for (int k = 0; k < K1; k++) {
-      if (u->beta && !std::isfinite(u->beta[k])) return HQPKKT_E_RANGE;
-      for (int j = 0; j < r; j++)
-        if (!std::isfinite(u->coef[(size_t)k * r + j])) return HQPKKT_E_RANGE;
-    }
-    // the launch's descriptors; a stage with beta = 1, every coefficient 0 and no diagonal is left alone (units = 0)
-    std::vector<stg::HuDesc> hd(K1);
-    int units_max = 0;
-    for (int k = 0; k < K1; k++) {
-      const double beta = u->beta ? u->beta[k] : 1.0;
-      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
-      const bool packed = P.stage_packed(k);
-      stg::HuDesc &q = hd[k];
-      q = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, 0, beta == 0.0 ? 0 : beta == 1.0 ? 1 : 2, 0, beta, {0.0, 0.0, 0.0, 0.0}};
-      bool touched = beta != 1.0 || u->diag;
-      for (int j = 0; j < r; j++) q.c[j] = u->coef[(size_t)k * r + j], touched = touched || q.c[j] != 0.0;
-      if (!touched || nz == 0) continue;
-      // (the hand-over rule: what is kept of a block must have arrived since the analysis)
-      if (beta != 0.0 && ((int)d.hess.set.size() != K1 || !d.hess.set[k])) return HQPKKT_E_INTERN;
-      q.units = packed ? (int)P.hess_tiles(nz) : nt * nt;
-      units_max = std::max(units_max, q.units);
-    }
-    int e;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    if (units_max > 0) {
-      const size_t n = (size_t)P.n;
-      stg::HuVecs V{};
-      V.r = r;
-      if (h->opts.loc == HQPKKT_LOC_DEVICE) {
-        for (int j = 0; j < r; j++) V.u[j] = u->U[j];
-        V.diag = u->diag;
-      } else {  // a host caller's vectors through the handle's own buffer
-        if (!d.hess.hu_vec.p && (e = d.hess.hu_vec.alloc((size_t)(stg::HU_RANK + 1) * n + 1))) return e;
-        for (int j = 0; j < r; j++) {
-          HIPCHK(hipMemcpyAsync(d.hess.hu_vec.p + j * n, u->U[j], sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-          V.u[j] = d.hess.hu_vec.p + j * n;
-        }
-        if (u->diag) {
-          HIPCHK(hipMemcpyAsync(d.hess.hu_vec.p + stg::HU_RANK * n, u->diag, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-          V.diag = d.hess.hu_vec.p + stg::HU_RANK * n;
-        }
-      }
-      if ((e = staged_hu_descriptors(h, d, hd))) return e;
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
-      HIPCHK(hipGetLastError());
-      if (h->opts.loc != HQPKKT_LOC_DEVICE) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vectors are free again)
-    }
-    if ((int)d.hess.set.size() != K1) d.hess.set.assign(K1, 0);
-    for (int k = 0; k < K1; k++)
-      if (hd[k].mode == 0) d.hess.set[k] = 1;  // (beta = 0: the block has been made here)
-    h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_bfgs_update_stage_hessians(hqpkkt_t *h, const hqpkkt_bfgs_update *b) {
-  return guarded([&]() -> int {
-    if (!h || !b || !b->s || !b->y) return HQPKKT_E_NULL;
-    static_assert(stg::HB_REPORT == HQPKKT_BFGS_REPORT, "the kernel writes the report's words");
-    if (!std::isfinite(b->gamma) || (b->gamma < 0.0 && !std::isfinite(b->alpha))) return HQPKKT_E_RANGE;
-    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    const kktdev::StagedPlan &P = d.plan;
-    const int K1 = P.K + 1;
-    // the base descriptors of the update launch: beta = 1, every stage as if touched - k_hb_terms writes the coefficients
-    // and takes the stages it leaves alone out (units = 0); every block is kept, so every block must have arrived
-    std::vector<stg::HuDesc> hd(K1);
-    int units_max = 0;
-    for (int k = 0; k < K1; k++) {
-      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
-      const bool packed = P.stage_packed(k);
-      if (nz > 0 && ((int)d.hess.set.size() != K1 || !d.hess.set[k])) return HQPKKT_E_INTERN;
-      hd[k] = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, packed ? (int)P.hess_tiles(nz) : nt * nt, 1, 0, 1.0, {0.0, 0.0, 0.0, 0.0}};
-      units_max = std::max(units_max, hd[k].units);
-    }
-    const double gamma_eff = bfgs_gamma_eff(b->gamma, b->alpha);
-    int e;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    const size_t n = (size_t)P.n;
-    const bool host = h->opts.loc != HQPKKT_LOC_DEVICE;
-    if (d.hess.hb_vec.count < (host ? 4 : 2) * n + 1 && (e = d.hess.hb_vec.alloc((host ? 4 : 2) * n + 1))) return e;
-    if (!d.hess.hb_rep.p && (e = d.hess.hb_rep.alloc((size_t)K1 * stg::HB_REPORT))) return e;
-    double *Qs = d.hess.hb_vec.p, *v = b->v && !host ? b->v : d.hess.hb_vec.p + n;
-    const double *s = b->s, *y = b->y;
-    if (host) {  // a host caller's vectors through the handle's own buffer
-      HIPCHK(hipMemcpyAsync(d.hess.hb_vec.p + 2 * n, b->s, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(d.hess.hb_vec.p + 3 * n, b->y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-      s = d.hess.hb_vec.p + 2 * n, y = d.hess.hb_vec.p + 3 * n;
-    }
-    if ((e = staged_hu_descriptors(h, d, hd))) return e;
-    staged_hess_symv(h, d, s, Qs);
-    KLAUNCH(h, KC_VECTOR, stg::k_hb_terms<<<(unsigned)K1, 256, 0, h->stream>>>(d.hess.hu_desc.p, s, y, Qs, v, gamma_eff, d.hess.hb_rep.p));
-    if (units_max > 0) {
-      stg::HuVecs V{};
-      V.r = 2, V.u[0] = v, V.u[1] = Qs;
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
-    }
-    HIPCHK(hipGetLastError());
-    d.hess.hb_done = true;
-    h->factored = false;
-    if (host) {
-      if (b->v) HIPCHK(hipMemcpyAsync(b->v, v, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vectors are free again, v is complete)
-    }
-    return 0;
-  });
-}
-
-int hqpkkt_bfgs_report(hqpkkt_t *h, double *out) {
-  return guarded([&]() -> int {
-    if (!h || !out) return HQPKKT_E_NULL;
-    if (!h->sd || !h->uploaded || !h->sd->hess.hb_done) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    HIPCHK(hipSetDevice(h->opts.device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d.hess.hb_rep.p, sizeof(double) * d.hess.hb_rep.count, hipMemcpyDeviceToHost));
-    return 0;
-  });
-}
-
-int hqpkkt_hessian_row_stats(hqpkkt_t *h, double *rowmax, double *offsum) {
-  return guarded([&]() -> int {
-    if (!h || (!rowmax && !offsum)) return HQPKKT_E_NULL;
-    int e;
-    if ((e = staged_hg_ready(h, nullptr))) return e;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    StagedDev &d = *h->sd;
-    if ((e = staged_hg_prepare(d))) return e;
-    const size_t n = (size_t)d.plan.n;
-    const bool host = h->opts.loc != HQPKKT_LOC_DEVICE;
-    double *rm = !rowmax ? nullptr : host ? d.hess.hg_vec.p : rowmax, *os = !offsum ? nullptr : host ? d.hess.hg_vec.p + n : offsum;
-    staged_hg_rows(h, d, rm, os);
-    HIPCHK(hipGetLastError());
-    if (host) {
-      if (rm) HIPCHK(hipMemcpyAsync(rowmax, rm, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-      if (os) HIPCHK(hipMemcpyAsync(offsum, os, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return 0;
-  });
-}
-
-int hqpkkt_restart_stage_hessians(hqpkkt_t *h, double eps, const unsigned char *stages) {
-  return guarded([&]() -> int {
-    if (!h) return HQPKKT_E_NULL;
-    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
-    int e;
-    if ((e = staged_hg_ready(h, stages))) return e;
-    StagedDev &d = *h->sd;
-    const kktdev::StagedPlan &P = d.plan;
-    const int K1 = P.K + 1;
-    // the update launch's descriptors: beta = 0 on the chosen stages, every other stage left alone (units = 0)
-    std::vector<stg::HuDesc> hd(K1);
-    int units_max = 0;
-    for (int k = 0; k < K1; k++) {
-      const int nz = P.hess_order(k), nt = (nz + stg::HP_T - 1) / stg::HP_T;
-      const bool packed = P.stage_packed(k), chosen = nz > 0 && (!stages || stages[k]);
-      hd[k] = stg::HuDesc{P.oQ[k], P.ldQ[k], nt, nz, P.nmk[k], packed ? 1 : 0, 0, chosen ? 0 : 1, 0, chosen ? 0.0 : 1.0, {0.0, 0.0, 0.0, 0.0}};
-      if (chosen) hd[k].units = packed ? (int)P.hess_tiles(nz) : nt * nt;
-      units_max = std::max(units_max, hd[k].units);
-    }
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    if ((e = staged_hg_prepare(d))) return e;
-    if (units_max > 0) {
-      const size_t n = (size_t)P.n;
-      double *rm = d.hess.hg_vec.p, *dv = d.hess.hg_vec.p + 2 * n;
-      staged_hg_rows(h, d, rm, nullptr);
-      KLAUNCH(h, KC_VECTOR, stg::k_hg_clip<<<nblk((long long)n), 256, 0, h->stream>>>((long long)n, rm, eps, 1.0 / eps, dv));
-      if ((e = staged_hu_descriptors(h, d, hd))) return e;
-      stg::HuVecs V{};
-      V.r = 0, V.diag = dv;
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_hu_update<<<dim3((unsigned)units_max, (unsigned)K1), 256, 0, h->stream>>>(d.hess.hu_desc.p, d.hess.Q.p, V));
-      HIPCHK(hipGetLastError());
-    }
-    h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps) {
-  return guarded([&]() -> int {
-    if (!h) return HQPKKT_E_NULL;
-    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
-    int e;
-    if ((e = staged_hg_ready(h, nullptr))) return e;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    StagedDev &d = *h->sd;
-    if ((e = staged_hg_prepare(d))) return e;
-    if (d.hess.hg_nz_max > 0) {
-      double *os = d.hess.hg_vec.p + (size_t)d.plan.n;
-      staged_hg_rows(h, d, nullptr, os);
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_hg_diag<<<dim3((unsigned)((d.hess.hg_nz_max + 255) / 256), (unsigned)(d.plan.K + 1)), 256, 0, h->stream>>>(
-                                  d.hess.hg_desc.p, d.hess.Q.p, os, eps, nullptr, 0));
-      HIPCHK(hipGetLastError());
-    }
-    h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *c) {
-  return guarded([&]() -> int {
-    if (!h || !c) return HQPKKT_E_NULL;
-    static_assert(stg::HE_MAX_STEPS == HQPKKT_EIG_MAX_STEPS && stg::HE_REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
-    if (!std::isfinite(c->eps) || !(c->eps > 0.0) || c->max_steps < 0 || c->max_steps > HQPKKT_EIG_MAX_STEPS) return HQPKKT_E_RANGE;
-    if (!staged_dense_ready(h, true)) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    const kktdev::StagedPlan &P = d.plan;
-    const int K1 = P.K + 1;
-    for (int k = 0; k < K1 && c->floor; k++)
-      if (!std::isfinite(c->floor[k])) return HQPKKT_E_RANGE;
-    int e;
-    if ((e = staged_hg_ready(h, nullptr))) return e;
-    if (c->floor_from_bfgs && !d.hess.hb_done) return HQPKKT_E_INTERN;
-    if (!h->uploaded && (e = staged_upload(h))) return e;
-    HIPCHK(hipSetDevice(h->opts.device));
-    if ((e = staged_hg_prepare(d))) return e;
-    const size_t n = (size_t)P.n;
-    // the floors the caller gave, NaN where theta_k comes from eps: through the pinned words, in the handle's stream
-    HIPCHK(hipEventSynchronize(d.hess.he_ev));  // (the copy of the last call's floors out of the pinned words)
-    for (int k = 0; k < K1; k++) d.hess.he_hfloor.p[k] = c->floor ? c->floor[k] : std::numeric_limits<double>::quiet_NaN();
-    HIPCHK(hipMemcpyAsync(d.hess.he_floor.p, d.hess.he_hfloor.p, sizeof(double) * K1, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(d.hess.he_ev, h->stream));
-    double *os = d.hess.hg_vec.p + n, *w = d.hess.hg_vec.p + 3 * n;
-    const int steps = std::min(c->max_steps ? c->max_steps : 64, d.hess.hg_nz_max);
-    // the basis of the recurrence, `steps` vectors of n: grown here, outside every capture, and cleared - a stage that is
-    // done keeps v = 0 from there on
-    if (d.hess.he_V.count < (size_t)steps * n + 1 && (e = d.hess.he_V.alloc((size_t)steps * n + 1))) return e;
-    double *V = d.hess.he_V.p;
-    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, h->stream));
-    staged_hg_rows(h, d, nullptr, os);
-    KLAUNCH(h, KC_VECTOR, stg::k_he_start<<<(unsigned)K1, 256, 0, h->stream>>>(d.hess.hg_desc.p, d.hess.Q.p, os, d.hess.he_floor.p, c->eps * c->eps,
-                                                                             c->floor_from_bfgs ? d.hess.hb_rep.p : nullptr, d.hess.he_st.p,
-                                                                             d.hess.he_rep.p, d.hess.he_T.p, V));
-    for (int j = 0; j < steps; j++) {  // (nothing is read back: a stage that has ended returns from its workgroup at once)
-      staged_hess_symv(h, d, V + (size_t)j * n, w);
-      KLAUNCH(h, KC_VECTOR, stg::k_he_step<<<(unsigned)K1, stg::HE_STEP_THREADS, 0, h->stream>>>(d.hess.hg_desc.p, d.hess.he_st.p, d.hess.he_T.p, V, w, (long long)n, j,
-                                                                              j + 1 == steps ? 1 : 0));
-    }
-    KLAUNCH(h, KC_VECTOR, stg::k_he_ritz<<<(unsigned)K1, 64, 0, h->stream>>>(d.hess.he_st.p, d.hess.he_T.p, d.hess.he_rep.p));
-    if (d.hess.hg_nz_max > 0)
-      KLAUNCH(h, KC_ASSEMBLE, stg::k_hg_diag<<<dim3((unsigned)((d.hess.hg_nz_max + 255) / 256), (unsigned)K1), 256, 0, h->stream>>>(
-                                  d.hess.hg_desc.p, d.hess.Q.p, nullptr, 0.0, d.hess.he_rep.p, 1));
-    HIPCHK(hipGetLastError());
-    d.hess.he_done = true;
-    h->factored = false;
-    return 0;
-  });
-}
-
-int hqpkkt_eigen_report(hqpkkt_t *h, double *out, double *T) {
-  return guarded([&]() -> int {
-    if (!h || !out) return HQPKKT_E_NULL;
-    if (!h->sd || !h->uploaded || !h->sd->hess.he_done) return HQPKKT_E_INTERN;
-    StagedDev &d = *h->sd;
-    HIPCHK(hipSetDevice(h->opts.device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d.hess.he_rep.p, sizeof(double) * d.hess.he_rep.count, hipMemcpyDeviceToHost));
-    if (T) HIPCHK(hipMemcpy(T, d.hess.he_T.p, sizeof(double) * d.hess.he_T.count, hipMemcpyDeviceToHost));
     return 0;
   });
 }

@@ -67,25 +67,13 @@ struct StagedDev {
     DBuf<double> xc, cdx;
     int pairs_max = 0;
   } wr;
-  // Dense stage Hessians (StagedPlan::hess_dense): the arena of the blocks Q_k, the scatter map of the CSR hand-over, per
-  // stage what k_hs_symv needs, y = Q x of the residual products (n), which blocks Q_k have arrived since the analysis
-  // (dense hand-over) ...
-  // ... as packed lower tiles (StagedPlan::hess_packed): per stage what k_hp_symv_tiles needs, the slots of that product; the
-  // launches' extents: most chunks of tiles and tile rows of a packed stage, largest order of a stage that keeps its dense
-  // block (0: none) ...
-  // ... and what the entry points make at their first call, because only their callers need it: x, the operand of
-  // hqpkkt_debug_hess_symv (n); stage, the staging block of a packed stage's dense hand-over from host memory (reused in
-  // stream order); of the update in place (hqpkkt_update_stage_hessians) the per-stage descriptors of the launch, written
-  // to pinned memory and copied from there in the handle's stream (hu_ev: that copy is over, the pinned words may be
-  // rewritten), and the device copies of a host caller's vectors (HU_RANK + 1 vectors of n); of the BFGS update on the
-  // device (hqpkkt_bfgs_update_stage_hessians) Q s and v, behind them the copies of a host caller's s and y (hb_vec: 2 n
-  // or 4 n - never hess.y, which the residual reads), the report words of k_hb_terms (8 per stage), and whether an
-  // update has written them since the analysis; of the safeguards (hqpkkt_hessian_row_stats and the entries behind it,
-  // staged_hess_guard.hip.h) per stage what their kernels need, the slots of the packed row pass (hg_slots doubles of
-  // maxima, then as many of sums - twice what the product's scratch holds, so it is not shared), four vectors of n (row
-  // maxima, off-diagonal sums, the restart's diagonal, w of the recurrence), the recurrence's basis (as many vectors of n as
-  // the control with the most steps asked for), its state, T and report per stage, the floors through pinned words (he_ev: copied), and whether a control has run since the analysis
+  // Dense stage Hessians (StagedPlan::hess_dense); the entries' host side is staged_hess_host.hip.h
   struct Hessians {
+    // the blocks and their product (upload_hessians; read by the factor, the residual and every entry): the arena of the
+    // blocks Q_k, the scatter map of the CSR hand-over, per stage what k_hs_symv needs, y = Q x of the residual (n), which
+    // blocks have arrived since the analysis (HessCall::arrived); as packed lower tiles (StagedPlan::hess_packed) per stage
+    // what k_hp_symv_tiles needs and the slots of that product; the launches' extents: most chunks of tiles and tile rows
+    // of a packed stage, largest order of a stage that keeps its dense block (0: none)
     DBuf<double> Q, y;
     DBuf<long long> q_dst;
     DBuf<stg::HessDesc> desc;
@@ -93,20 +81,39 @@ struct StagedDev {
     DBuf<stg::HpDesc> hp_desc;
     DBuf<double> scr;
     int hp_chunks_max = 0, hp_nt_max = 0, hs_nz_max = 0;
-    DBuf<double> x, stage;
-    PinnedBuf<stg::HuDesc> hu_hdesc;
-    DBuf<stg::HuDesc> hu_desc;
-    EventOwner hu_ev;
-    DBuf<double> hu_vec;
-    DBuf<double> hb_vec, hb_rep;
-    bool hb_done = false;
-    DBuf<stg::HgDesc> hg_desc;
-    DBuf<double> hg_scr, hg_vec, he_V, he_st, he_T, he_rep, he_floor;
-    PinnedBuf<double> he_hfloor;
-    EventOwner he_ev;
-    long long hg_slots = 0;
-    int hg_tiles_max = 0, hg_nz_max = 0;
-    bool he_done = false;
+    // hqpkkt_set_stage_hessian, first host block of a packed stage: its staging block (reused in stream order)
+    DBuf<double> stage;
+    // HessCall::scratch, first call of BFGS or of a safeguard: four work vectors of n, carved per call (BFGS: Q s, v; the safeguards: row maxima,
+    // off-diagonal sums, the restart's diagonal, w of the recurrence) - never y, which the residual reads.  Nothing reads
+    // them once the entry has returned
+    DBuf<double> work;
+    // the update launch (HessCall::update; rank-r update, BFGS, restart), first call: the per-stage descriptors, written to
+    // pinned words and copied from there in the handle's stream (ev: that copy is over, the words may be rewritten)
+    struct Update {
+      PinnedBuf<stg::HuDesc> hdesc;
+      DBuf<stg::HuDesc> desc;
+      EventOwner ev;
+    } upd;
+    // the BFGS terms (hqpkkt_bfgs_update_stage_hessians, first call): the report words of k_hb_terms (8 per stage; read by
+    // hqpkkt_bfgs_report and by eigenvalue control with floor_from_bfgs), and whether an update has written them since the analysis
+    struct Bfgs {
+      DBuf<double> rep;
+      bool done = false;
+    } bfgs;
+    // the safeguards (row stats, restart, Gerschgorin, eigenvalue control; HessCall::prepare_guard at the first call of any):
+    // per stage what their kernels need, the slots of the packed row pass (`slots` doubles of maxima, then as many of sums
+    // - twice what the product's scratch holds, so it is not shared), the recurrence's basis (as many vectors of n as the
+    // control with the most steps asked for), its state, T and report per stage (read by hqpkkt_eigen_report), the floors
+    // through pinned words (ev: copied), and whether a control has run since the analysis
+    struct Guard {
+      DBuf<stg::HgDesc> desc;
+      DBuf<double> scr, V, st, T, rep, floor;
+      PinnedBuf<double> hfloor;
+      EventOwner ev;
+      long long slots = 0;
+      int tiles_max = 0, nz_max = 0;
+      bool done = false;
+    } guard;
   } hess;
   // The sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A' ...
   // ... its heavy columns (StagedPlan::hv_cols): the ranges without them, the columns per stage, and per column of A its

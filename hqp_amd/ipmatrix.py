@@ -166,6 +166,43 @@ class Hqp_IpMatrix:
         return ins + outs
 
     # -- the plugin interface ----------------------------------------------------
+    def _vec_in(self, a, size, what):
+        """(pointer, what keeps it alive) of a caller's input vector of the entries on Q (the sparse Q, the dense stage
+        Hessians): numpy, or a torch CUDA tensor with device_vectors=True; None is the null pointer."""
+        if a is None:
+            return C.c_void_p(None), None
+        if self._device_vectors:
+            if not (hasattr(a, "data_ptr") and a.is_cuda):
+                raise TypeError(f"{what}: device_vectors=True needs torch CUDA float64 tensors")
+            if a.numel() != size or str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                raise KktError(_lib.E_SIZES, what)
+            return C.c_void_p(a.data_ptr()), a
+        if hasattr(a, "data_ptr"):
+            raise TypeError(f"{what}: torch tensors need device_vectors=True")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != size:
+            raise KktError(_lib.E_SIZES, what)
+        return C.c_void_p(a.ctypes.data), a
+
+    def _vec_out(self, size):
+        """(pointer, vector) of a result of those entries: a numpy array, or a torch CUDA tensor with device_vectors=True."""
+        if self._device_vectors:
+            import torch
+            v = torch.zeros(size, dtype=torch.float64, device=torch.device("cuda", self._dev))
+            return C.c_void_p(v.data_ptr()), v
+        v = np.zeros(size)
+        return C.c_void_p(v.ctypes.data), v
+
+    def _stream_sync(self, after=False):
+        """Device vectors are read and written in the handle's stream: what torch has queued for them is over before the
+        call, and (``after``) the handle's work before torch reads a result."""
+        if self._device_vectors:
+            import torch
+            if after:
+                torch.cuda.synchronize(self._dev)
+            else:
+                torch.cuda.current_stream(self._dev).synchronize()
+
     def init(self, qp):
         """Hqp_IpSpBKP::init (hqp/Hqp_IpSpBKP.C:76-114): analyse, then update."""
         self.analyze(qp)
@@ -310,74 +347,38 @@ class Hqp_IpMatrix:
         return x, y, z, w, res.asdict()
 
     # -- the sparse Q where it lies on the device (hqpkkt_q_*, hqpkkt_lagrangian_gradient) ----------
-    def _q_in(self, a, size, what):
-        """(pointer, what keeps it alive) of an input vector: numpy, or a torch CUDA tensor with device_vectors=True."""
-        if a is None:
-            return None, None
-        if self._device_vectors:
-            if not (hasattr(a, "data_ptr") and a.is_cuda):
-                raise TypeError(f"{what}: device_vectors=True needs torch CUDA float64 tensors")
-            if a.numel() != size or str(a.dtype) != "torch.float64" or not a.is_contiguous():
-                raise KktError(_lib.E_SIZES, what)
-            return C.c_void_p(a.data_ptr()), a
-        if hasattr(a, "data_ptr"):
-            raise TypeError(f"{what}: torch tensors need device_vectors=True")
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.size != size:
-            raise KktError(_lib.E_SIZES, what)
-        return C.c_void_p(a.ctypes.data), a
-
-    def _q_out(self, size):
-        """(pointer, vector) of a result: a numpy array, or a torch CUDA tensor with device_vectors=True."""
-        if self._device_vectors:
-            import torch
-            v = torch.zeros(size, dtype=torch.float64, device=torch.device("cuda", self._dev))
-            return C.c_void_p(v.data_ptr()), v
-        v = np.zeros(size)
-        return C.c_void_p(v.ctypes.data), v
-
-    def _q_sync(self, after=False):
-        """Device vectors are read and written in the handle's stream: what torch has queued for them is over before the
-        call, and the handle's work before torch reads a result."""
-        if self._device_vectors:
-            import torch
-            if after:
-                torch.cuda.synchronize(self._dev)
-            else:
-                torch.cuda.current_stream(self._dev).synchronize()
-
     def _q_nnz(self):
         return int(self._keep[0][-1]) if self._keep and len(self._keep[0]) else 0
 
     def q_values(self):
         """Qx as it lies in the handle (hqpkkt_q_values): nnz(Q) values in the order of the analysed pattern."""
-        p, v = self._q_out(self._q_nnz())
-        self._q_sync()
+        p, v = self._vec_out(self._q_nnz())
+        self._stream_sync()
         _check(self._L.hqpkkt_q_values(self._h, p), "q_values")
         return v
 
     def q_product(self, x):
         """y = Q x, Q symmetric from its stored upper entries (hqpkkt_q_product)."""
-        px, kx = self._q_in(x, self.n, "x")
-        py, y = self._q_out(self.n)
-        self._q_sync()
+        px, kx = self._vec_in(x, self.n, "x")
+        py, y = self._vec_out(self.n)
+        self._stream_sync()
         _check(self._L.hqpkkt_q_product(self._h, px, py), "q_product")
-        self._q_sync(after=True)
+        self._stream_sync(after=True)
         return y
 
     def q_row_stats(self, want_diag=True, want_offsum=True):
         """(diag, offsum) of Q (hqpkkt_q_row_stats): the stored q_ii (0.0 without one) and the sum of |q_ij| over j != i of
         the symmetric image; None for the one not wanted."""
-        out = [self._q_out(self.n) if w else (None, None) for w in (want_diag, want_offsum)]
-        self._q_sync()
+        out = [self._vec_out(self.n) if w else (None, None) for w in (want_diag, want_offsum)]
+        self._stream_sync()
         _check(self._L.hqpkkt_q_row_stats(self._h, out[0][0], out[1][0]), "q_row_stats")
-        self._q_sync(after=True)
+        self._stream_sync(after=True)
         return out[0][1], out[1][1]
 
     def q_set_diagonal(self, d):
         """Q <- diag(d) on the stored pattern (hqpkkt_q_set_diagonal): Hqp_HL::init, sp_ident, a restart."""
-        pd, kd = self._q_in(d, self.n, "d")
-        self._q_sync()
+        pd, kd = self._vec_in(d, self.n, "d")
+        self._stream_sync()
         _check(self._L.hqpkkt_q_set_diagonal(self._h, pd), "q_set_diagonal")
         self._keep_qv = [kd]
 
@@ -393,19 +394,19 @@ class Hqp_IpMatrix:
         """Hqp_HL_DScale::update on the diagonal of the sparse Q (hqpkkt_q_dscale_update) for the step ``s`` and the change
         ``y`` of the Lagrangian's gradient, in blocks of ``bsize`` variables (0: one block).  ``want_v``: returns v as
         applied, else None.  q_dscale_report() tells what every block did."""
-        ps, ks = self._q_in(s, self.n, "s")
-        py, ky = self._q_in(y, self.n, "y")
+        ps, ks = self._vec_in(s, self.n, "s")
+        py, ky = self._vec_in(y, self.n, "y")
         u = _lib.DScaleUpdate()
         u.s, u.y, u.gamma, u.bsize = ps.value, py.value, float(gamma), int(bsize)
         v = None
         if want_v:
-            pv, v = self._q_out(self.n)
+            pv, v = self._vec_out(self.n)
             u.v = pv.value
-        self._q_sync()
+        self._stream_sync()
         _check(self._L.hqpkkt_q_dscale_update(self._h, C.byref(u)), "q_dscale_update")
         self._keep_qv = [ks, ky, v]
         if want_v:
-            self._q_sync(after=True)
+            self._stream_sync(after=True)
         return v
 
     def q_dscale_report(self):
@@ -424,14 +425,14 @@ class Hqp_IpMatrix:
     def lagrangian_gradient(self, c, y, z, minus=None):
         """Hqp_SqpSolver::grd_L (hqpkkt_lagrangian_gradient): c - A'y - C'z, and minus ``minus`` where given - the
         difference of two gradients from the second call."""
-        pc, kc = self._q_in(c, self.n, "c")
-        py, ky = self._q_in(y if self.me else None, self.me, "y")
-        pz, kz = self._q_in(z if self.m else None, self.m, "z")
-        pm, km = self._q_in(minus, self.n, "minus")
-        po, out = self._q_out(self.n)
-        self._q_sync()
+        pc, kc = self._vec_in(c, self.n, "c")
+        py, ky = self._vec_in(y if self.me else None, self.me, "y")
+        pz, kz = self._vec_in(z if self.m else None, self.m, "z")
+        pm, km = self._vec_in(minus, self.n, "minus")
+        po, out = self._vec_out(self.n)
+        self._stream_sync()
         _check(self._L.hqpkkt_lagrangian_gradient(self._h, pc, py, pz, pm, po), "lagrangian_gradient")
-        self._q_sync(after=True)
+        self._stream_sync(after=True)
         return out
 
     def read_block(self, what, node):
@@ -650,39 +651,12 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
                "hess_symv_timed")
         return y, ms.value
 
-    def _hess_vec(self, a, what):
-        """(pointer, what keeps it alive) of a vector of n: numpy, or a torch CUDA tensor with device_vectors=True."""
-        if hasattr(a, "data_ptr"):
-            if not self._device_vectors or not a.is_cuda:
-                raise TypeError(f"{what}: torch CUDA tensors need device_vectors=True")
-            if a.numel() != self.n or str(a.dtype) != "torch.float64" or not a.is_contiguous():
-                raise KktError(_lib.E_SIZES, what)
-            return C.c_void_p(a.data_ptr()), a
-        if self._device_vectors:
-            raise TypeError(f"{what}: device_vectors=True needs torch CUDA float64 tensors")
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.size != self.n:
-            raise KktError(_lib.E_SIZES, what)
-        return C.c_void_p(a.ctypes.data), a
-
-    def _torch_sync(self):
-        """Device vectors are read in the handle's stream: what torch has queued for them is over first."""
-        if self._device_vectors:
-            import torch
-            torch.cuda.current_stream(self._dev).synchronize()
-
     def hessian_product(self, x):
         """y = Q x over the dense stage Hessians (hqpkkt_hessian_product): x of length n, numpy - or a torch CUDA tensor with
         device_vectors=True, and y is one then.  The launches and the bits of the residual's product."""
-        px, kx = self._hess_vec(x, "x")
-        if self._device_vectors:
-            import torch
-            y = torch.zeros(self.n, dtype=torch.float64, device=kx.device)
-            py = C.c_void_p(y.data_ptr())
-            self._torch_sync()
-        else:
-            y = np.zeros(self.n)
-            py = C.c_void_p(y.ctypes.data)
+        px, kx = self._vec_in(x, self.n, "x")
+        py, y = self._vec_out(self.n)
+        self._stream_sync()
         _check(self._L.hqpkkt_hessian_product(self._h, px, py), "hessian_product")
         return y
 
@@ -701,7 +675,7 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         keep = [coef]
         up = (C.c_void_p * max(r, 1))()
         for j, v in enumerate(U):
-            p, k = self._hess_vec(v, f"U[{j}]")
+            p, k = self._vec_in(v, self.n, f"U[{j}]")
             up[j] = p.value
             keep.append(k)
         u = _lib.HessUpdate()
@@ -712,10 +686,10 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
             beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(K1)
             u.beta = beta.ctypes.data
         if diag is not None:
-            p, k = self._hess_vec(diag, "diag")
+            p, k = self._vec_in(diag, self.n, "diag")
             u.diag = p.value
             keep.append(k)
-        self._torch_sync()
+        self._stream_sync()
         _check(self._L.hqpkkt_update_stage_hessians(self._h, C.byref(u)), "update_stage_hessians")
         self._keep_u = keep
 
@@ -747,20 +721,15 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         step length ``alpha``.  ``want_v``: returns v as applied (a tensor with device_vectors=True), else None.
         ``eigen_control``: an eps - the reference's eigenvalue control runs behind the update in the same stream,
         eigen_control(eps, from_bfgs=True); None (the default): the update alone.  bfgs_report() tells what every stage did."""
-        ps, ks = self._hess_vec(s, "s")
-        py, ky = self._hess_vec(y, "y")
+        ps, ks = self._vec_in(s, self.n, "s")
+        py, ky = self._vec_in(y, self.n, "y")
         b = _lib.BfgsUpdate()
         b.s, b.y, b.gamma, b.alpha = ps.value, py.value, float(gamma), float(alpha)
         v = None
         if want_v:
-            if self._device_vectors:
-                import torch
-                v = torch.zeros(self.n, dtype=torch.float64, device=ks.device)
-                b.v = v.data_ptr()
-            else:
-                v = np.zeros(self.n)
-                b.v = v.ctypes.data
-        self._torch_sync()
+            pv, v = self._vec_out(self.n)
+            b.v = pv.value
+        self._stream_sync()
         _check(self._L.hqpkkt_bfgs_update_stage_hessians(self._h, C.byref(b)), "bfgs_update_device")
         self._keep_b = [ks, ky, v]
         if eigen_control is not None:
@@ -781,20 +750,11 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         |Q_k(i, j)| and the sum of |Q_k(i, j)| over j != i, vectors of n - numpy, or torch CUDA tensors with
         device_vectors=True.  The entry writes device vectors asynchronously in the handle's stream, which torch's streams do
         not wait for: this wrapper waits for the device before it returns the tensors.  None for the one not wanted."""
-        torch = None
-        if self._device_vectors:
-            import torch
-            dev = torch.device("cuda", self._dev)
-            out = [torch.zeros(self.n, dtype=torch.float64, device=dev) if w else None for w in (want_max, want_sum)]
-            ptr = [None if a is None else C.c_void_p(a.data_ptr()) for a in out]
-            self._torch_sync()
-        else:
-            out = [np.zeros(self.n) if w else None for w in (want_max, want_sum)]
-            ptr = [None if a is None else C.c_void_p(a.ctypes.data) for a in out]
-        _check(self._L.hqpkkt_hessian_row_stats(self._h, ptr[0], ptr[1]), "hessian_row_stats")
-        if torch is not None:
-            torch.cuda.synchronize(self._dev)
-        return out[0], out[1]
+        out = [self._vec_out(self.n) if w else (None, None) for w in (want_max, want_sum)]
+        self._stream_sync()
+        _check(self._L.hqpkkt_hessian_row_stats(self._h, out[0][0], out[1][0]), "hessian_row_stats")
+        self._stream_sync(after=True)
+        return out[0][1], out[1][1]
 
     def restart_hessians(self, eps, stages=None):
         """The reference's restart_Q on the device (hqpkkt_restart_stage_hessians): Q_k <- diag(min(max(eps, rowmax_i),

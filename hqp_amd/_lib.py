@@ -21,6 +21,8 @@ HESS_CSR, HESS_DENSE = 0, 1
 HQPKKT_HESS_UPDATE_RANK = 4
 HQPKKT_BFGS_REPORT = 8
 HQPKKT_DSCALE_REPORT = 8
+HQPKKT_QBFGS_FULL, HQPKKT_QBFGS_PATTERN = 0, 1
+HQPKKT_QBFGS_REPORT = 8
 HQPKKT_EIG_MAX_STEPS = 128
 HQPKKT_EIG_REPORT = 10
 HQPKKT_EIG_END_REL = 2.0 ** -40
@@ -52,6 +54,7 @@ SYMBOLS = [
     "hqpkkt_debug_rows_gemv",
     "hqpkkt_q_values", "hqpkkt_q_product", "hqpkkt_q_row_stats", "hqpkkt_q_set_diagonal", "hqpkkt_q_gerschgorin",
     "hqpkkt_q_dscale_setup", "hqpkkt_q_dscale_update", "hqpkkt_q_dscale_report", "hqpkkt_lagrangian_gradient",
+    "hqpkkt_q_blocks", "hqpkkt_q_bfgs_update", "hqpkkt_q_bfgs_report",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -80,6 +83,11 @@ class BfgsUpdate(C.Structure):  # hqpkkt_bfgs_update
 
 class DScaleUpdate(C.Structure):  # hqpkkt_dscale_update
     _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("bsize", C.c_int), ("v", C.c_void_p)]
+
+
+class QBfgsUpdate(C.Structure):  # hqpkkt_q_bfgs_update_args
+    _fields_ = [("s", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_double), ("alpha", C.c_double), ("bsize", C.c_int), ("fill", C.c_int),
+                ("v", C.c_void_p), ("Qs", C.c_void_p)]
 
 
 class EigenControl(C.Structure):  # hqpkkt_eigen_control
@@ -255,6 +263,9 @@ def lib():
     L.hqpkkt_q_dscale_update.argtypes = [vp, C.POINTER(DScaleUpdate)]
     L.hqpkkt_q_dscale_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_lagrangian_gradient.argtypes = [vp] * 6
+    L.hqpkkt_q_blocks.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.hqpkkt_q_bfgs_update.argtypes = [vp, C.POINTER(QBfgsUpdate)]
+    L.hqpkkt_q_bfgs_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

@@ -4,6 +4,7 @@
 // their declarations in include/hqpkkt.h.
 #include "hqpkkt_handle.hpp"
 #include "q_values.hip.h"
+#include "q_bfgs.hip.h"
 
 char g_last_hip_error[512] = "";
 std::atomic<long long> g_live_bufs[2];
@@ -609,13 +610,18 @@ int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const dou
 // The checks that follow an entry's own NULL and RANGE tests, in the header's order: call order and refused handles
 // (HQPKKT_E_INTERN), the diagonal rule of the entries that write a diagonal (HQPKKT_E_FORMAT; decided on the host from the
 // pattern the handle keeps, tables made once), the device, and what the first call makes on it.
-static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
+static int qv_refused(hqpkkt_t *h, bool touches_q) {
   if (!h->analyzed || !h->have_values) return HQPKKT_E_INTERN;
   if (h->shard_count > 1 || h->an.shard_count > 1) return HQPKKT_E_INTERN;
   if (h->opts.mode == HQPKKT_MODE_STAGED) {
     const int f = staged_form(h);
     if ((f & STAGED_FORM_SHARDED) || (f & (touches_q ? STAGED_FORM_HESS_DENSE : STAGED_FORM_DENSE_DYN))) return HQPKKT_E_INTERN;
   }
+  return 0;
+}
+static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
+  int e = qv_refused(h, touches_q);
+  if (e) return e;
   const Analysis &an = h->an;
   TreeDev::QVal &q = h->td.qv;
   if (touches_q && !q.mapped) {
@@ -634,8 +640,7 @@ static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
     q.mapped = true;
   }
   if (writes_diag && q.bad_diag) return HQPKKT_E_FORMAT;
-  int e = ensure_device(h);
-  if (e) return e;
+  if ((e = ensure_device(h))) return e;
   if (touches_q && !q.didx.p && ((e = q.didx.upload(q.h_didx)) || (e = q.kind.upload(q.h_kind)))) return e;
   return CallerVecs{h}.ready();
 }
@@ -795,6 +800,160 @@ int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out, long long cap_blocks, long 
     if (cap_blocks < q.rep_blocks) return HQPKKT_E_RANGE;
     if (q.rep_blocks)
       HIPCHK(hipMemcpyAsync(out, q.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)q.rep_blocks, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+// ---- Hqp_HL_BFGS and the pattern-kept update on the sparse Q (q_bfgs.hip.h)
+
+// Hqp_HL_BFGS::next_block on the analysed pattern of Q: the blocks' first indices, n behind them; and per block whether
+// every (i, j), i <= j, of it is stored (the rows are strictly ascending: a count decides)
+static void qb_partition(const hqpkkt_t *h, int bsize, std::vector<int> &first, std::vector<unsigned char> &full) {
+  const int n = h->an.n;
+  const int *Qp = h->pQp.data(), *Qi = h->pQi.data();
+  first.clear(), full.clear();
+  for (int b = 0; b < n;) {
+    first.push_back(b);
+    if (bsize < 0) {
+      int end = b;
+      for (; b <= end; b++) {
+        const int last = Qp[b + 1] > Qp[b] ? Qi[Qp[b + 1] - 1] : b;
+        end = std::max(end, last);
+      }
+    } else
+      b += bsize > 0 ? std::min(bsize, n - b) : n - b;
+  }
+  first.push_back(n);
+  if (n == 0) first.clear();
+  for (size_t k = 0; k + 1 < first.size(); k++) {
+    const int a = first[k], e = first[k + 1];
+    long long stored = 0;
+    for (int i = a; i < e; i++)
+      for (int j = Qp[i]; j < Qp[i + 1]; j++) stored += Qi[j] >= i && Qi[j] < e;
+    full.push_back(stored == (long long)(e - a) * (e - a + 1) / 2);
+  }
+}
+static int qb_key(const hqpkkt_t *h, int bsize) { return bsize < 0 ? -1 : (bsize >= h->an.n ? 0 : bsize); }
+
+int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first, int *full, long long cap, long long *n_blocks) {
+  return guarded([&]() -> int {
+    if (!h || !n_blocks) return HQPKKT_E_NULL;
+    if (!h->analyzed) return HQPKKT_E_INTERN;
+    std::vector<int> f;
+    std::vector<unsigned char> fl;
+    qb_partition(h, qb_key(h, bsize), f, fl);
+    *n_blocks = (long long)fl.size();
+    if (!first) return 0;
+    if (cap < *n_blocks) return HQPKKT_E_RANGE;
+    std::copy(f.begin(), f.end(), first);
+    if (full) std::copy(fl.begin(), fl.end(), full);
+    return 0;
+  });
+}
+
+// the plan of one bsize: the host's partition, then (with_device) its tables, partial sums and report on the device
+static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) {
+  TreeDev::QVal &q = h->td.qv;
+  const int key = qb_key(h, bsize), n = h->an.n;
+  int at = -1;
+  for (size_t k = 0; k < q.bfgs_plans.size(); k++)
+    if (q.bfgs_plans[k].bsize == key) at = (int)k;
+  if (at < 0) {
+    TreeDev::QVal::BfgsPlan p;
+    p.bsize = key;
+    qb_partition(h, key, p.first, p.full);
+    p.nblocks = (int)p.full.size();
+    p.all_full = true;
+    for (int b = 0; b < p.nblocks; b++) {
+      const int len = p.first[b + 1] - p.first[b];
+      p.max_len = std::max(p.max_len, len), p.nunits += (len + qv::QV_CHUNK - 1) / qv::QV_CHUNK;
+      p.all_full = p.all_full && p.full[b];
+    }
+    q.bfgs_plans.push_back(std::move(p));
+    at = (int)q.bfgs_plans.size() - 1;
+  }
+  *index = at;
+  TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
+  if (!with_device || p.blk_of.p || n <= 0) return 0;
+  std::vector<int> blk_of((size_t)n), bunit((size_t)p.nblocks + 1), ublk((size_t)p.nunits);
+  for (int b = 0, u = 0; b < p.nblocks; b++) {
+    const int len = p.first[b + 1] - p.first[b];
+    std::fill(blk_of.begin() + p.first[b], blk_of.begin() + p.first[b + 1], b);
+    bunit[b] = u;
+    for (int j = 0; j < (len + qv::QV_CHUNK - 1) / qv::QV_CHUNK; j++) ublk[u++] = b;
+    bunit[b + 1] = u;
+  }
+  int e;
+  if ((e = p.boff.upload(p.first)) || (e = p.bunit.upload(bunit)) || (e = p.ublk.upload(ublk)) || (e = p.part.alloc(3 * (size_t)p.nunits)) ||
+      (e = p.rep.alloc((size_t)qv::QV_REPORT * p.nblocks)))
+    return e;
+  return p.blk_of.upload(blk_of);  // (last: it says the plan is complete)
+}
+
+static const decltype(&qv::k_qb_rows<4>) qb_rows_kernels[2] = {qv::k_qb_rows<16>, qv::k_qb_rows<4>};
+static const decltype(&qv::k_qb_sums<1>) qb_sums_kernels[2] = {qv::k_qb_sums<4>, qv::k_qb_sums<1>};
+static const decltype(&qv::k_qb_damped<1>) qb_damped_kernels[2] = {qv::k_qb_damped<4>, qv::k_qb_damped<1>};
+
+int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
+  return guarded([&]() -> int {
+    if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
+    static_assert(qv::QV_REPORT == HQPKKT_QBFGS_REPORT, "the kernels write the report's words");
+    if (!std::isfinite(u->gamma) || (u->gamma < 0.0 && !std::isfinite(u->alpha))) return HQPKKT_E_RANGE;
+    if (u->fill != HQPKKT_QBFGS_FULL && u->fill != HQPKKT_QBFGS_PATTERN) return HQPKKT_E_RANGE;
+    int e = qv_refused(h, true), at = -1;
+    if (e || (e = qb_plan(h, u->bsize, false, &at))) return e;
+    if (u->fill == HQPKKT_QBFGS_FULL && !h->td.qv.bfgs_plans[at].all_full) return HQPKKT_E_FORMAT;
+    if ((e = qv_prepare(h, true, false))) return e;
+    TreeDev::QVal &q = h->td.qv;
+    const int n = h->an.n, nq = h->an.nq;
+    if (n <= 0) {
+      q.bfgs_last = at;
+      return 0;
+    }
+    if (!q.erow.p) {  // what every plan shares: the entries' rows and columns, Q s and v
+      std::vector<int> erow((size_t)nq);
+      for (int i = 0; i < n; i++) std::fill(erow.begin() + h->pQp[i], erow.begin() + h->pQp[i + 1], i);
+      if ((e = q.ecol.upload(h->pQi)) || (e = q.bfgs_qs.alloc((size_t)n)) || (e = q.bfgs_v.alloc((size_t)n)) || (e = q.erow.upload(erow))) return e;
+    }
+    if ((e = qb_plan(h, u->bsize, true, &at))) return e;
+    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
+    const double gamma_eff = bfgs_gamma_eff(u->gamma, u->alpha);
+    CallerVecs io{h};
+    const double *ds, *dy;
+    if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
+    const qv::BfgsTables g{n, p.nblocks, p.nunits, p.blk_of.p, p.boff.p, p.bunit.p, p.ublk.p};
+    double *Qs = q.bfgs_qs.p, *v = q.bfgs_v.p, *part = p.part.p, *part2 = p.part.p + 2 * (size_t)p.nunits;
+    hipStream_t s = h->stream;
+    const bool sh = qv_short_q(h), wave_units = p.max_len <= 64;  // lanes per row as hqpkkt_q_product; a block per wavefront
+    const unsigned ugrid = (unsigned)(wave_units ? (p.nunits + 3) / 4 : p.nunits);
+    qb_rows_kernels[sh]<<<nblk(n, sh ? 64 : 16), 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, ds, Qs);
+    qb_sums_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, ds, dy, Qs, part);
+    qv::k_qb_decide<<<nblk(p.nblocks), 256, 0, s>>>(g, part, gamma_eff, p.rep.p);
+    qb_damped_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, ds, dy, Qs, p.rep.p, part2, v);
+    qv::k_qb_outcome<<<nblk(p.nblocks), 256, 0, s>>>(g, part2, p.rep.p);
+    if (nq) qv::k_qb_apply<<<nblk(nq), 256, 0, s>>>(nq, q.erow.p, q.ecol.p, q.kind.p, p.blk_of.p, Qs, v, p.rep.p, h->td.vals.p);
+    q.bfgs_last = at;
+    // v and Q s are the handle's own vectors (the update reads them): a caller who asks gets a copy, in the stream
+    const hipMemcpyKind back = io.host() ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (u->v) HIPCHK(hipMemcpyAsync(u->v, v, sizeof(double) * (size_t)n, back, s));
+    if (u->Qs) HIPCHK(hipMemcpyAsync(u->Qs, Qs, sizeof(double) * (size_t)n, back, s));
+    if ((e = qv_written(h))) return e;
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
+  return guarded([&]() -> int {
+    if (!h || !out || !n_blocks) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    const TreeDev::QVal &q = h->td.qv;
+    if (q.bfgs_last < 0) return HQPKKT_E_INTERN;
+    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[q.bfgs_last];
+    *n_blocks = p.nblocks;
+    if (cap_blocks < p.nblocks) return HQPKKT_E_RANGE;
+    if (p.nblocks) HIPCHK(hipMemcpyAsync(out, p.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)p.nblocks, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
   });

@@ -280,6 +280,21 @@ struct TreeDev {
     DBuf<int> didx, kind;
     DBuf<double> offsum, part, rep;         // Gerschgorin's row pass; DScale's partial sums (3 per unit) and its report
     long long rep_blocks = -1;              // blocks of the last DScale update since the analysis
+    // hqpkkt_q_blocks / hqpkkt_q_bfgs_update (q_bfgs.hip.h): the partition of 0 .. n-1 for one bsize (< 0 detected, 0 one
+    // block, > 0 blocks of bsize) with its device tables, partial sums and report - made by the first update with that
+    // bsize, never regrown.  Both fills share a plan: they differ in the host's test of `all_full` alone.
+    struct BfgsPlan {
+      int bsize = 0, nblocks = 0, nunits = 0, max_len = 0;
+      bool all_full = false;
+      std::vector<int> first;            // nblocks + 1: the blocks' first indices, n behind them
+      std::vector<unsigned char> full;   // per block: every (i, j), i <= j, is stored
+      DBuf<int> blk_of, boff, bunit, ublk;  // block of a variable; first index / first unit of a block (+ 1); block of a unit
+      DBuf<double> part, rep;               // 3 per unit; QV_REPORT per block
+    };
+    std::vector<BfgsPlan> bfgs_plans;
+    int bfgs_last = -1;               // plan of the last BFGS update since the analysis
+    DBuf<int> erow, ecol;             // row and column of every stored entry of Qx
+    DBuf<double> bfgs_qs, bfgs_v;     // Q s restricted to the blocks, v as applied
   } qv;
   // a host caller's vectors of those entries and of the entries on the dense stage Hessians (CallerVecs, which makes them)
   struct CallerBufs {
@@ -538,6 +553,16 @@ static inline float elapsed(hipEvent_t a, hipEvent_t b) {
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = -1.f;
   return ms;
+}
+
+// the damping factor of the BFGS updates (of the dense stage Hessians, of the sparse Q) as hessian_update.bfgs_terms forms
+// it, operation by operation (no contraction)
+static inline double bfgs_gamma_eff(double gamma, double alpha) {
+#pragma clang fp contract(off)
+  if (gamma >= 0.0) return gamma;
+  const double g = -gamma, omg = 1.0 + gamma, oma = 1.0 - alpha;
+  const double t = omg * oma;
+  return g + t;
 }
 
 // ---- what one unit calls in another

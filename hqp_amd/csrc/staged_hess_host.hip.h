@@ -129,15 +129,6 @@ struct HessCall {
   }
 };
 
-// the damping factor of the BFGS update as hessian_update.bfgs_terms forms it, operation by operation (no contraction)
-double bfgs_gamma_eff(double gamma, double alpha) {
-#pragma clang fp contract(off)
-  if (gamma >= 0.0) return gamma;
-  const double g = -gamma, omg = 1.0 + gamma, oma = 1.0 - alpha;
-  const double t = omg * oma;
-  return g + t;
-}
-
 // y = Q x of the three entries that ask for it: x, y per opts.loc or (as_host, the debug entries) host arrays; complete
 // when it returns.  ms: the average device time of `reps` further products, by events on the handle's stream
 int hess_symv_call(hqpkkt_t *h, const double *x, double *y, bool as_host, int reps = 0, double *ms = nullptr) {

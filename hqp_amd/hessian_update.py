@@ -27,6 +27,11 @@ The approximations that work on the sparse Q of the program itself (``Hqp_IpMatr
 ``q_dscale_update``; hqpkkt_q_*) have their models at the end: ``q_gerschgorin_model``, ``dscale_terms`` - Hqp_HL_DScale::update
 with the reference's operations and sequential sums - and ``dscale_replay``, the device's decision and update from the sums
 it REPORTED.
+
+The reference's default, Hqp_HL_BFGS, on the sparse Q itself (``Hqp_IpMatrix.q_blocks``, ``q_bfgs_update``; hqpkkt_q_blocks,
+hqpkkt_q_bfgs_update) closes the file: ``q_blocks_model`` is Hqp_HL_BFGS::next_block, ``q_bfgs_terms`` the update of every block
+with the reference's operations and sequential sums - on the stored entries alone under ``pattern`` -, and ``q_bfgs_replay``
+the device's decision and its two steps of every stored entry from the sums it REPORTED and the Q s it returned.
 """
 from __future__ import annotations
 
@@ -354,3 +359,142 @@ def dscale_replay(report, s, y, q, bsize=0):
         raise ValueError("dscale_replay: report of (blocks, 8), s, y and q vectors of one length")
     v, qn, outcome, _theta, _sv = _dscale_apply(report, s, y, q, blocks)
     return v, qn, outcome
+
+
+# ---- Hqp_HL_BFGS on the sparse Q of the program (Hqp_IpMatrix.q_blocks, q_bfgs_update) ----
+
+def q_blocks_model(Qp, Qi, n, bsize):
+    """Hqp_HL_BFGS::next_block (hqp/Hqp_HL_BFGS.C:257-292) on the pattern (Qp, Qi) of Q, rows ascending: returns (first, full),
+    the blocks' first indices with n behind the last (empty for n = 0) and per block 1 where every (i, j), i <= j, of it is
+    stored.  bsize < 0: a block grows while the last stored column of one of its rows reaches past its end; 0: one block;
+    > 0: blocks of bsize, the last one shorter."""
+    Qp, Qi = np.asarray(Qp, dtype=np.int64), np.asarray(Qi, dtype=np.int64)
+    n, bsize = int(n), int(bsize)
+    first = []
+    b = 0
+    while b < n:
+        first.append(b)
+        if bsize < 0:
+            end = b
+            while b <= end:
+                last = int(Qi[Qp[b + 1] - 1]) if Qp[b + 1] > Qp[b] else b
+                end = max(end, last)
+                b += 1
+        else:
+            b += min(bsize, n - b) if bsize > 0 else n - b
+    if n:
+        first.append(n)
+    first = np.array(first, dtype=np.int64)
+    rows = np.repeat(np.arange(n), np.diff(Qp[: n + 1])) if n else np.zeros(0, dtype=np.int64)
+    full = np.zeros(max(first.size - 1, 0), dtype=np.int64)
+    for k in range(full.size):
+        a, e = int(first[k]), int(first[k + 1])
+        lo, hi = int(Qp[a]), int(Qp[e])
+        c, r = Qi[lo:hi], rows[lo:hi]
+        full[k] = int(((c >= r) & (c < e)).sum()) == (e - a) * (e - a + 1) // 2
+    return first, full
+
+
+def _q_bfgs_entries(Q_csr, first):
+    """rows and columns of Q's entries, the block of every variable, and the mask of the entries an update may touch:
+    col >= row, both in one block"""
+    p, ix, x = (np.asarray(a) for a in Q_csr)
+    n = p.size - 1
+    first = np.asarray(first, dtype=np.int64)
+    if n and (first.size < 2 or first[0] != 0 or first[-1] != n or (np.diff(first) <= 0).any()):
+        raise ValueError("first: the blocks' first indices, ascending from 0, and n behind the last")
+    rows = np.repeat(np.arange(n), np.diff(p))
+    of = np.repeat(np.arange(max(first.size - 1, 0)), np.diff(first)) if n else np.zeros(0, dtype=np.int64)
+    ix = ix.astype(np.int64)
+    inb = (ix >= rows) & (of[rows] == of[ix]) if n else np.zeros(0, dtype=bool)
+    return rows, ix, np.array(x, dtype=np.float64), of, inb
+
+
+def _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs):
+    """decision, theta, v and both steps of every stored entry from the sums in ``rep`` (columns 0 sy, 1 sQs, 2 gamma_eff,
+    4 sv where damped): one numpy operation per rounded operation, all blocks at once"""
+    nb = rep.shape[0]
+    if nb == 0:
+        return y.copy(), x.copy(), np.zeros(0, dtype=np.int64), np.ones(0), np.zeros(0)
+    one = np.float64(1.0)
+    with np.errstate(all="ignore"):
+        sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
+        damp = sy < gamma * sqs
+        theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
+        omt = one - theta
+        v = np.where(damp[of], theta[of] * y + omt[of] * Qs, y)
+        sv = np.where(damp, rep[:, 4], sy)
+        finite = np.isfinite(sv) & np.isfinite(sqs)
+        ok = finite & (sv != 0.0) & (sqs != 0.0)
+        outcome = np.where(~finite, 3, np.where(~ok, 2, np.where(damp, 1, 0))).astype(np.int64)
+        xn = x.copy()
+        k = np.flatnonzero(inb)
+        k = k[ok[of[rows[k]]]]
+        r, c, b = rows[k], ix[k], of[rows[k]]
+        t = x[k] - (Qs[r] * Qs[c]) / sqs[b]
+        xn[k] = t + (v[r] * v[c]) / sv[b]
+    return v, xn, outcome, theta, sv
+
+
+def _seq_sums(keys, terms, size):
+    """per key the sum of its terms in the order they stand, from +0.0 (in_prod); numpy's unbuffered add.at runs in order"""
+    out = np.zeros(size)
+    np.add.at(out, keys, terms)
+    return out
+
+
+def q_bfgs_terms(Q_csr, s, y, first, gamma=0.1, alpha=1.0, pattern=False):
+    """Hqp_HL_BFGS::update (hqp/Hqp_HL_BFGS.C:150-251, without its eigenvalue control) on the CSR triple ``Q_csr`` = (indptr,
+    indices, data), of which the entries with col >= row exist, for the blocks ``first`` (``q_blocks_model``): per block the
+    reference's operations with its sequential sums - (Q s)_i over row i of the block's symmetric image by ascending column,
+    s'y, s'(Q s), s'v by ascending index.  Returns (report, v, Qs, Qx_new): ``report`` in the layout of
+    ``Hqp_IpMatrix.q_bfgs_report``, v as applied, the block-restricted Q s and the new data.  ``pattern``: the stored entries
+    of a block alone are updated (the operator of Hqp_HL_Gangster); otherwise a block that is not fully stored raises
+    ValueError.  As on the device a block whose sv or sQs is not finite is left alone (outcome 3)."""
+    s, y = (np.ascontiguousarray(a, dtype=np.float64) for a in (s, y))
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first)
+    n, nb = s.size, max(np.asarray(first).size - 1, 0)
+    first = np.asarray(first, dtype=np.int64)
+    if not pattern:
+        cnt = np.bincount(of[rows[inb]], minlength=nb) if nb else np.zeros(0)
+        ln = np.diff(first) if nb else np.zeros(0)
+        if (cnt != ln * (ln + 1) // 2).any():
+            raise ValueError("q_bfgs_terms: a block is not fully stored (pattern=False)")
+    if gamma < 0.0:  # damping adapted to the step length, as bfgs_terms forms it
+        gamma = -gamma + (1.0 + gamma) * (1.0 - alpha)
+    g = np.float64(gamma)
+    rep = np.zeros((nb, 8))
+    with np.errstate(all="ignore"):
+        # the block's symmetric image, row by row in ascending column order
+        st = inb & (ix > rows)
+        r2, c2, v2 = np.concatenate([rows[inb], ix[st]]), np.concatenate([ix[inb], rows[st]]), np.concatenate([x[inb], x[st]])
+        o = np.lexsort((c2, r2))
+        Qs = _seq_sums(r2[o], v2[o] * s[c2[o]], n)
+        sy, sqs = _seq_sums(of, s * y, nb), _seq_sums(of, s * Qs, nb)
+        one = np.float64(1.0)
+        damp = sy < g * sqs
+        theta = np.where(damp, ((one - g) * sqs) / (sqs - sy), one)
+        if nb:
+            vd = theta[of] * y + (one - theta)[of] * Qs
+            sv = np.where(damp, _seq_sums(of, s * vd, nb), sy)
+            rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 4], rep[:, 5], rep[:, 6] = sy, sqs, g, sv, first[:-1], np.diff(first)
+    v, xn, outcome, theta, sv = _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs)
+    if nb:
+        rep[:, 3], rep[:, 4], rep[:, 7] = theta, sv, outcome
+    return rep, v, Qs, xn
+
+
+def q_bfgs_replay(report, Q_csr, y, Qs, first):
+    """(v, Qx_new, outcome) of ``Hqp_IpMatrix.q_bfgs_update`` (hqpkkt_q_bfgs_update) repeated in numpy from the sums the device
+    REPORTED and the ``Qs`` it returned: of ``report``, (blocks, 8), sy (0), sQs (1), gamma_eff (2) and - on a damped block -
+    sv (4) are read.  One numpy operation per device operation: the test sy < fl(gamma_eff sQs), theta = fl(fl((1 - gamma_eff)
+    sQs) / fl(sQs - sy)), v_i = fl(fl(theta y_i) + fl(fl(1 - theta) Qs_i)), and for every stored (i, j), j >= i, inside an
+    updated block q <- fl(q - fl(fl(Qs_i Qs_j) / sQs)), then q <- fl(q + fl(fl(v_i v_j) / sv)); v = y on a block that is not
+    damped; a block stays where sv or sQs is zero (outcome 2) or not finite (3).  ``Q_csr`` holds the data before the update."""
+    report = np.asarray(report, dtype=np.float64)
+    y, Qs = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, Qs))
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first)
+    if report.shape != (max(np.asarray(first).size - 1, 0), 8) or not (y.shape == Qs.shape == (np.asarray(Q_csr[0]).size - 1,)):
+        raise ValueError("q_bfgs_replay: report of (blocks, 8), y and Qs vectors of n entries")
+    v, xn, outcome, _theta, _sv = _q_bfgs_apply(report, rows, ix, x, of, inb, y, Qs)
+    return v, xn, outcome

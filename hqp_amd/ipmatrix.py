@@ -422,6 +422,56 @@ class Hqp_IpMatrix:
         _check(e, "q_dscale_report")
         return out[: k.value]
 
+    def q_blocks(self, bsize=-1):
+        """(first, full) of hqpkkt_q_blocks: Hqp_HL_BFGS::next_block on the analysed pattern of Q.  ``first``: the blocks'
+        first indices and n behind the last (blocks + 1 ints; empty for n = 0); ``full``: per block 1 where its whole upper
+        triangle is stored.  ``bsize`` < 0 detects the blocks, 0 is one block, > 0 blocks of bsize.  Needs analyze() alone."""
+        k = C.c_longlong()
+        _check(self._L.hqpkkt_q_blocks(self._h, int(bsize), None, None, 0, C.byref(k)), "q_blocks")
+        first, full = np.zeros(k.value + 1, dtype=np.int32), np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            _check(self._L.hqpkkt_q_blocks(self._h, int(bsize), C.c_void_p(first.ctypes.data), C.c_void_p(full.ctypes.data), k.value, C.byref(k)), "q_blocks")
+        return first[: k.value + 1 if k.value else 0], full
+
+    def q_bfgs_update(self, s, y, gamma=0.1, alpha=1.0, bsize=-1, pattern=False, want_v=False, want_Qs=False):
+        """Hqp_HL_BFGS::update on the sparse Q where it lies (hqpkkt_q_bfgs_update): the damped BFGS update of every block of
+        q_blocks(bsize) for the step ``s`` and the change ``y`` of the Lagrangian's gradient; ``gamma`` < 0 adapts the
+        damping to the step length ``alpha``.  ``pattern``: the update on the stored entries alone, any pattern (with
+        bsize = 0 the update of Hqp_HL_Gangster); otherwise every block must be fully stored (HQPKKT_E_FORMAT).  Returns
+        (v, Qs) - v as applied and the block-restricted Q s, None for the one not wanted.  q_bfgs_report() tells what every
+        block did."""
+        ps, ks = self._vec_in(s, self.n, "s")
+        py, ky = self._vec_in(y, self.n, "y")
+        u = _lib.QBfgsUpdate()
+        u.s, u.y, u.gamma, u.alpha, u.bsize = ps.value, py.value, float(gamma), float(alpha), int(bsize)
+        u.fill = _lib.HQPKKT_QBFGS_PATTERN if pattern else _lib.HQPKKT_QBFGS_FULL
+        v = Qs = None
+        if want_v:
+            pv, v = self._vec_out(self.n)
+            u.v = pv.value
+        if want_Qs:
+            pq, Qs = self._vec_out(self.n)
+            u.Qs = pq.value
+        self._stream_sync()
+        _check(self._L.hqpkkt_q_bfgs_update(self._h, C.byref(u)), "q_bfgs_update")
+        self._keep_qv = [ks, ky, v, Qs]
+        if want_v or want_Qs:
+            self._stream_sync(after=True)
+        return v, Qs
+
+    def q_bfgs_report(self):
+        """Per block of the last q_bfgs_update() (hqpkkt_q_bfgs_report), an array of shape (blocks, 8): sy, sQs, gamma_eff,
+        theta (1 where not damped), sv as used, first index, length and the outcome - 0 updated, 1 updated with damping,
+        2 left alone (sv or sQs is zero), 3 left alone (sv or sQs is not finite).  Waits for the handle's stream."""
+        k = C.c_longlong()
+        out = np.zeros((1, _lib.HQPKKT_QBFGS_REPORT))
+        e = self._L.hqpkkt_q_bfgs_report(self._h, C.c_void_p(out.ctypes.data), 1, C.byref(k))
+        if e == _lib.E_RANGE:
+            out = np.zeros((k.value, _lib.HQPKKT_QBFGS_REPORT))
+            e = self._L.hqpkkt_q_bfgs_report(self._h, C.c_void_p(out.ctypes.data), k.value, C.byref(k))
+        _check(e, "q_bfgs_report")
+        return out[: k.value]
+
     def lagrangian_gradient(self, c, y, z, minus=None):
         """Hqp_SqpSolver::grd_L (hqpkkt_lagrangian_gradient): c - A'y - C'z, and minus ``minus`` where given - the
         difference of two gradients from the second call."""

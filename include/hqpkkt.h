@@ -634,7 +634,7 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  * row has no stored diagonal or more than one - the reference inserts one; the pattern here is fixed - decided on the host
  * from the analysed pattern, before any launch; the map row -> index of its diagonal is built once.
  * Checks, before anything is launched, in this order: HQPKKT_E_NULL; HQPKKT_E_RANGE (eps not finite or <= 0, gamma not
- * finite or < 0); HQPKKT_E_INTERN (not analysed, no values yet, a refused handle; hqpkkt_q_dscale_report: no update since the
+ * finite or < 0 - hqpkkt_q_bfgs_update has its own, below); HQPKKT_E_INTERN (not analysed, no values yet, a refused handle; hqpkkt_q_dscale_report: no update since the
  * analysis - and its HQPKKT_E_RANGE for cap_blocks comes behind that, with *n_blocks set); HQPKKT_E_FORMAT; HQPKKT_E_DEVICE.
  * Values: every operation named here is rounded once (kernels without contraction); max(a, b) is the reference's macro,
  * a > b ? a : b.
@@ -665,6 +665,47 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       2 gamma, 3 theta (1.0 undamped), 4 sv as used, 5 first index, 6 length, 7 outcome - 0 updated,
  *                       1 updated with damping, 2 left alone (zero), 3 left alone (not finite).  out is a HOST array.
  *                       hessian_update.dscale_replay repeats the decision and the update in numpy from the reported sums.
+ *   hqpkkt_q_blocks     Hqp_HL_BFGS::next_block on the analysed pattern of Q: the partition of 0 .. n-1 into contiguous blocks.
+ *                       bsize < 0 (sqp_hela_bsize's default): a block grows while the last stored column of any of its rows
+ *                       reaches past its end (a row without entries, or whose last column is below the diagonal, reaches
+ *                       itself); bsize == 0: one block; bsize > 0: blocks of bsize, the last one shorter.  Host only: works
+ *                       after hqpkkt_analyze alone (HQPKKT_E_INTERN before it) and touches no device.  first: n_blocks + 1
+ *                       ints, the blocks' first indices and n behind the last; full (optional, n_blocks ints): 1 where
+ *                       every (i, j), i <= j, of the block is stored.  first == NULL: *n_blocks alone is set; cap (in
+ *                       blocks) too small: HQPKKT_E_RANGE with *n_blocks set.  n == 0: no blocks.
+ *   hqpkkt_q_bfgs_update    Hqp_HL_BFGS::update (the reference's default approximation) on the blocks of hqpkkt_q_blocks(bsize),
+ *                       in place in Qx.  Per block B: Qs_i = sum over j in B of q_ij s_j over row i of the symmetric image -
+ *                       the walk and the bits of hqpkkt_q_product where no stored entry crosses a block (always so for
+ *                       bsize <= 0); entries whose column lies in another block are skipped, as symsp_extract_mat leaves
+ *                       them out -, sy = s'y, sQs = s'(Qs).  gamma_eff = gamma for gamma >= 0, else fl(g + fl(fl(1 - g) fl(1 -
+ *                       alpha))), g = -gamma, formed on the host (as hqpkkt_bfgs_update_stage_hessians).  Damped where
+ *                       sy < fl(gamma_eff sQs): theta = fl(fl((1 - gamma_eff) sQs) / fl(sQs - sy)) - not clamped, unlike
+ *                       Hqp_HL_SparseBFGS -, v_i = fl(fl(theta y_i) + fl(fl(1 - theta) Qs_i)), sv = s'v; otherwise v = y,
+ *                       sv = sy.  Every stored entry (i, j), j >= i, with both indices in B: q <- fl(q - fl(fl(Qs_i Qs_j) /
+ *                       sQs)), then q <- fl(q + fl(fl(v_i v_j) / sv)) - divisions, as in the reference.  Entries with col < row
+ *                       and entries whose indices lie in different blocks are never read or written.  A block with sv or
+ *                       sQs zero is left alone (the reference), and so is one with either not finite (the rule of the
+ *                       other BFGS / DScale entries; the reference writes NaN); a NaN in one block's y reaches no other
+ *                       block.  The sums are made as hqpkkt_q_dscale_update makes them (chunks of 4096 from the block's
+ *                       first index): a block's bits depend on its length alone.
+ *                       fill = HQPKKT_QBFGS_FULL: Hqp_HL_BFGS proper, every block's upper triangle must be stored - a block
+ *                       that is not makes the call return HQPKKT_E_FORMAT, decided on the host from the pattern before
+ *                       any launch: a call applies to every block or to none (the reference allocates the entries; the
+ *                       pattern here is fixed).  fill = HQPKKT_QBFGS_PATTERN: any pattern, the update on the stored entries
+ *                       alone; with bsize = 0 that is the update of Hqp_HL_Gangster on the symmetric image.  (The
+ *                       reference's Hqp_HL_Gangster multiplies with the stored triangle alone - sp_mv_mlt on an upper-stored
+ *                       Q; the two coincide for a diagonal Q.  This entry follows hqpkkt_q_product.)
+ *                       Checks: HQPKKT_E_NULL (h, the arguments, s or y); HQPKKT_E_RANGE (gamma not finite; gamma < 0 with
+ *                       alpha not finite; fill neither value - a negative gamma is valid here); HQPKKT_E_INTERN;
+ *                       HQPKKT_E_FORMAT; HQPKKT_E_DEVICE.  v, Qs (optional, n doubles each, overlapping neither input): v as
+ *                       applied (y where a block is not damped) and the block-restricted Q s the update used.  The
+ *                       device tables of a bsize are made by the first update with it; later ones allocate nothing.
+ *                       Not built: the eigenvalue control of Hqp_HL_BFGS (on by default there) - until it is an entry of its
+ *                       own a caller safeguards with hqpkkt_q_gerschgorin.
+ *   hqpkkt_q_bfgs_report    as hqpkkt_q_dscale_report, per block of the last hqpkkt_q_bfgs_update: 0 sy, 1 sQs, 2 gamma_eff,
+ *                       3 theta (1.0 undamped), 4 sv as used, 5 first index, 6 length, 7 outcome - 0 updated, 1 updated
+ *                       with damping, 2 left alone (zero), 3 left alone (not finite).  hessian_update.q_bfgs_replay repeats
+ *                       the decision and the update in numpy from the reported sums and the returned Qs.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -687,6 +728,21 @@ typedef struct hqpkkt_dscale_update {
 int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u);
 #define HQPKKT_DSCALE_REPORT 8
 int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
+#define HQPKKT_QBFGS_FULL 0    /* Hqp_HL_BFGS: every block's upper triangle must be stored */
+#define HQPKKT_QBFGS_PATTERN 1 /* the update on the stored entries of a block alone (the operator of Hqp_HL_Gangster) */
+#define HQPKKT_QBFGS_REPORT 8
+typedef struct hqpkkt_q_bfgs_update_args {
+  const double *s, *y; /* the step and the change of the Lagrangian's gradient, n doubles each */
+  double gamma;        /* sqp_hela_gamma: >= 0 the damping factor, < 0 adapted to alpha (as hqpkkt_bfgs_update) */
+  double alpha;        /* the step length; read only when gamma < 0 */
+  int bsize;           /* sqp_hela_bsize: < 0 detect the blocks, 0 one block of everything, > 0 blocks of bsize */
+  int fill;            /* HQPKKT_QBFGS_FULL or HQPKKT_QBFGS_PATTERN */
+  double *v;           /* optional, n doubles: the vector as applied */
+  double *Qs;          /* optional, n doubles: the block-restricted product Q s the update used */
+} hqpkkt_q_bfgs_update_args;
+int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first /* HOST */, int *full /* HOST */, long long cap, long long *n_blocks);
+int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u);
+int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
 int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, const double *z,
                                const double *minus /* or NULL */, double *out);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of

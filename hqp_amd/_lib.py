@@ -55,6 +55,7 @@ SYMBOLS = [
     "hqpkkt_q_values", "hqpkkt_q_product", "hqpkkt_q_row_stats", "hqpkkt_q_set_diagonal", "hqpkkt_q_gerschgorin",
     "hqpkkt_q_dscale_setup", "hqpkkt_q_dscale_update", "hqpkkt_q_dscale_report", "hqpkkt_lagrangian_gradient",
     "hqpkkt_q_blocks", "hqpkkt_q_bfgs_update", "hqpkkt_q_bfgs_report",
+    "hqpkkt_q_eigen_control", "hqpkkt_q_eigen_report",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -92,6 +93,10 @@ class QBfgsUpdate(C.Structure):  # hqpkkt_q_bfgs_update_args
 
 class EigenControl(C.Structure):  # hqpkkt_eigen_control
     _fields_ = [("eps", C.c_double), ("floor_from_bfgs", C.c_int), ("floor", C.c_void_p), ("max_steps", C.c_int)]
+
+
+class QEigenControl(C.Structure):  # hqpkkt_q_eigen_control_args
+    _fields_ = [("eps", C.c_double), ("bsize", C.c_int), ("floor_from_bfgs", C.c_int), ("floor", C.c_void_p), ("max_steps", C.c_int)]
 
 
 class Stats(C.Structure):
@@ -266,6 +271,8 @@ def lib():
     L.hqpkkt_q_blocks.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_q_bfgs_update.argtypes = [vp, C.POINTER(QBfgsUpdate)]
     L.hqpkkt_q_bfgs_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.hqpkkt_q_eigen_control.argtypes = [vp, C.POINTER(QEigenControl)]
+    L.hqpkkt_q_eigen_report.argtypes = [vp, vp, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.hqpkkt_set_values_staged.argtypes = [vp, dp, vp, vp, dp, dp]

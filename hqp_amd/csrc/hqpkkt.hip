@@ -5,6 +5,7 @@
 #include "hqpkkt_handle.hpp"
 #include "q_values.hip.h"
 #include "q_bfgs.hip.h"
+#include "q_eigen.hip.h"
 
 char g_last_hip_error[512] = "";
 std::atomic<long long> g_live_bufs[2];
@@ -954,6 +955,111 @@ int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out, long long cap_blocks, long lo
     *n_blocks = p.nblocks;
     if (cap_blocks < p.nblocks) return HQPKKT_E_RANGE;
     if (p.nblocks) HIPCHK(hipMemcpyAsync(out, p.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)p.nblocks, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+// ---- the eigenvalue control of Hqp_HL_BFGS on the blocks of the sparse Q (q_eigen.hip.h)
+
+static const decltype(&qv::k_qe_rows<4>) qe_rows_kernels[2] = {qv::k_qe_rows<16>, qv::k_qe_rows<4>};
+static const decltype(&qv::k_qe_unit0<1>) qe_unit0_kernels[2] = {qv::k_qe_unit0<4>, qv::k_qe_unit0<1>};
+static const decltype(&qv::k_qe_v0<1>) qe_v0_kernels[2] = {qv::k_qe_v0<4>, qv::k_qe_v0<1>};
+static const decltype(&qv::k_qe_alpha<1>) qe_alpha_kernels[2] = {qv::k_qe_alpha<4>, qv::k_qe_alpha<1>};
+static const decltype(&qv::k_qe_resid<1>) qe_resid_kernels[2] = {qv::k_qe_resid<4>, qv::k_qe_resid<1>};
+static const decltype(&qv::k_qe_ortho<1>) qe_ortho_kernels[2] = {qv::k_qe_ortho<4>, qv::k_qe_ortho<1>};
+static const decltype(&qv::k_qe_next<1>) qe_next_kernels[2] = {qv::k_qe_next<4>, qv::k_qe_next<1>};
+
+// what a control with `steps` steps needs on the device beside the plan's tables: made or grown here, all or nothing - a
+// failed allocation leaves the plan as it was
+static int qe_buffers(hqpkkt_t *h, TreeDev::QVal::BfgsPlan &p, int steps) {
+  TreeDev::QVal &q = h->td.qv;
+  const size_t n = (size_t)h->an.n;
+  int e;
+  if (!q.eig_w.p && (e = q.eig_w.alloc(2 * n))) return e;  // w, and behind it the row pass
+  if (p.eig_V.p && p.eig_cap >= steps) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (a report or a control still in the stream reads the old ones)
+  DBuf<double> V, part, T, rep, st, flr;
+  if ((e = V.alloc((size_t)steps * n)) || (e = part.alloc(((size_t)steps + 4) * p.nunits)) || (e = T.alloc(2 * (size_t)steps * p.nblocks)) ||
+      (e = rep.alloc((size_t)qv::QE_REPORT * p.nblocks)) || (e = st.alloc(2 * (size_t)qv::QE_STATE * p.nblocks)) || (e = flr.alloc((size_t)p.nblocks)))
+    return e;
+  p.eig_V = std::move(V), p.eig_part = std::move(part), p.eig_T = std::move(T), p.eig_rep = std::move(rep), p.eig_st = std::move(st),
+  p.eig_floor = std::move(flr);
+  p.eig_cap = steps;
+  return 0;
+}
+
+int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+  return guarded([&]() -> int {
+    if (!h || !ec) return HQPKKT_E_NULL;
+    static_assert(eig::MAX_STEPS == HQPKKT_EIG_MAX_STEPS && eig::REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
+    if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps < 0 || ec->max_steps > HQPKKT_EIG_MAX_STEPS) return HQPKKT_E_RANGE;
+    if (ec->floor_from_bfgs != 0 && ec->floor_from_bfgs != 1) return HQPKKT_E_RANGE;
+    int e = qv_refused(h, true), at = -1;
+    if (e || (e = qb_plan(h, ec->bsize, false, &at))) return e;
+    TreeDev::QVal &q = h->td.qv;
+    if (ec->floor_from_bfgs && q.bfgs_last != at) return HQPKKT_E_INTERN;
+    for (int b = 0; ec->floor && b < q.bfgs_plans[at].nblocks; b++)
+      if (!std::isfinite(ec->floor[b])) return HQPKKT_E_RANGE;
+    if ((e = qv_prepare(h, true, true))) return e;
+    const int n = h->an.n;
+    if (n <= 0) {
+      q.eig_last = at, q.bfgs_plans[at].eig_steps = 0;
+      return 0;
+    }
+    if ((e = qb_plan(h, ec->bsize, true, &at))) return e;
+    TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
+    const int steps = std::min(ec->max_steps ? ec->max_steps : 64, p.max_len);
+    if ((e = qe_buffers(h, p, steps))) return e;
+    hipStream_t s = h->stream;
+    if (ec->floor) {  // (a host array of the caller's, in the stream behind the last control's reads; it is the caller's again on return)
+      HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    const qv::BfgsTables g{n, p.nblocks, p.nunits, p.blk_of.p, p.boff.p, p.bunit.p, p.ublk.p};
+    // the partials of a unit: its products against the basis (steps), then v'w, w'w, the row pass' minimum and the start vector's sum
+    double *V = p.eig_V.p, *T = p.eig_T.p, *rep = p.eig_rep.p, *w = q.eig_w.p, *offs = q.eig_w.p + n;
+    double *partc = p.eig_part.p, *parta = partc + (size_t)steps * p.nunits, *partb = parta + p.nunits, *partg = partb + p.nunits, *partf = partg + p.nunits;
+    double *st[2] = {p.eig_st.p, p.eig_st.p + (size_t)qv::QE_STATE * p.nblocks};
+    const bool sh = qv_short_q(h), wave_units = p.max_len <= 64;  // lanes per row as hqpkkt_q_product; a block per wavefront
+    const unsigned ugrid = (unsigned)(wave_units ? (p.nunits + 3) / 4 : p.nunits), rgrid = nblk(n, sh ? 64 : 16);
+    // the basis, `steps` vectors of n, and T are cleared: a block that is done keeps v = 0, words past a block's steps are 0
+    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, s));
+    HIPCHK(hipMemsetAsync(T, 0, sizeof(double) * 2 * (size_t)steps * p.nblocks, s));
+    qe_rows_kernels[sh]<<<rgrid, 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, offs);
+    qe_unit0_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, offs, partg, partf);
+    qv::k_qe_begin<<<nblk(p.nblocks), 256, 0, s>>>(g, partg, ec->floor ? p.eig_floor.p : nullptr, ec->eps * ec->eps,
+                                                   ec->floor_from_bfgs ? p.rep.p : nullptr, st[0], rep);
+    qe_v0_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, partf, st[0], V);
+    for (int j = 0; j < steps; j++) {  // (nothing is read back: a unit of a block that has ended returns at once)
+      const double *sj = st[j & 1];
+      qb_rows_kernels[sh]<<<rgrid, 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, V + (size_t)j * n, w);
+      qe_alpha_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V + (size_t)j * n, w, parta);
+      qe_resid_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V, (long long)n, j, steps, w, parta, partc);
+      qe_ortho_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V, (long long)n, j, steps, w, partc, partb);
+      qe_next_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, st[(j + 1) & 1], V, (long long)n, j, j + 1 == steps ? 1 : 0, steps, w, parta, partb, T);
+    }
+    qv::k_qe_ritz<<<(unsigned)p.nblocks, 64, 0, s>>>(st[steps & 1], T, steps, rep);
+    qv::k_qe_shift<<<nblk(n), 256, 0, s>>>(n, p.blk_of.p, q.didx.p, rep, h->td.vals.p);
+    q.eig_last = at, p.eig_steps = steps;
+    return qv_written(h);
+  });
+}
+
+int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {
+  return guarded([&]() -> int {
+    if (!h || !out || !n_blocks || !t_steps) return HQPKKT_E_NULL;
+    int e = qv_prepare(h, true, false);
+    if (e) return e;
+    const TreeDev::QVal &q = h->td.qv;
+    if (q.eig_last < 0) return HQPKKT_E_INTERN;
+    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[q.eig_last];
+    *n_blocks = p.nblocks, *t_steps = p.eig_steps;
+    if (cap_blocks < p.nblocks) return HQPKKT_E_RANGE;
+    if (p.nblocks) {
+      HIPCHK(hipMemcpyAsync(out, p.eig_rep.p, sizeof(double) * qv::QE_REPORT * (size_t)p.nblocks, hipMemcpyDeviceToHost, h->stream));
+      if (T) HIPCHK(hipMemcpyAsync(T, p.eig_T.p, sizeof(double) * 2 * (size_t)p.eig_steps * p.nblocks, hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
   });

@@ -281,8 +281,8 @@ struct TreeDev {
     DBuf<double> offsum, part, rep;         // Gerschgorin's row pass; DScale's partial sums (3 per unit) and its report
     long long rep_blocks = -1;              // blocks of the last DScale update since the analysis
     // hqpkkt_q_blocks / hqpkkt_q_bfgs_update (q_bfgs.hip.h): the partition of 0 .. n-1 for one bsize (< 0 detected, 0 one
-    // block, > 0 blocks of bsize) with its device tables, partial sums and report - made by the first update with that
-    // bsize, never regrown.  Both fills share a plan: they differ in the host's test of `all_full` alone.
+    // block, > 0 blocks of bsize) with its device tables, partial sums and report - made by the first update or eigenvalue
+    // control with that bsize (qb_plan), never regrown.  Both fills share a plan: they differ in the host's test of `all_full` alone.
     struct BfgsPlan {
       int bsize = 0, nblocks = 0, nunits = 0, max_len = 0;
       bool all_full = false;
@@ -290,11 +290,17 @@ struct TreeDev {
       std::vector<unsigned char> full;   // per block: every (i, j), i <= j, is stored
       DBuf<int> blk_of, boff, bunit, ublk;  // block of a variable; first index / first unit of a block (+ 1); block of a unit
       DBuf<double> part, rep;               // 3 per unit; QV_REPORT per block
+      // hqpkkt_q_eigen_control (q_eigen.hip.h), made or grown by the control that needs them: the basis (eig_cap vectors of
+      // n), the units' partial sums, T (stride 2 eig_steps per block), the report, the state's two copies and the floors
+      int eig_cap = 0, eig_steps = 0;       // steps the buffers hold; the step cap of the plan's last control
+      DBuf<double> eig_V, eig_part, eig_T, eig_rep, eig_st, eig_floor;
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1;               // plan of the last BFGS update since the analysis
     DBuf<int> erow, ecol;             // row and column of every stored entry of Qx
     DBuf<double> bfgs_qs, bfgs_v;     // Q s restricted to the blocks, v as applied
+    int eig_last = -1;                // plan of the last eigenvalue control since the analysis
+    DBuf<double> eig_w;               // its product w = Q v (n) and the block-restricted row pass (n)
   } qv;
   // a host caller's vectors of those entries and of the entries on the dense stage Hessians (CallerVecs, which makes them)
   struct CallerBufs {

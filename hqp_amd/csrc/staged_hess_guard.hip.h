@@ -14,12 +14,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "eigen_ritz.hip.h"
+
 namespace stg {
 
-static const int HE_MAX_STEPS = 128;  // (HQPKKT_EIG_MAX_STEPS)
-static const int HE_REPORT = 10;      // (HQPKKT_EIG_REPORT)
-static const int HE_STATE = 4;        // per stage: done, steps, beta of the last step, max(|alpha|, beta) so far
-#define HE_END_REL 0x1p-40            // (HQPKKT_EIG_END_REL)
+static const int HE_MAX_STEPS = eig::MAX_STEPS;  // (HQPKKT_EIG_MAX_STEPS)
+static const int HE_REPORT = eig::REPORT;        // (HQPKKT_EIG_REPORT)
+static const int HE_STATE = 4;                   // per stage: done, steps, beta of the last step, max(|alpha|, beta) so far
+#define HE_END_REL EIG_END_REL                   // (HQPKKT_EIG_END_REL)
 
 // Per stage what these kernels need.  tiles: the stored tiles of a packed stage (0: the stage keeps its dense block);
 // oS: its first slot in the scratch of k_hg_tiles, in doubles.
@@ -28,9 +30,9 @@ struct HgDesc {
   int ld, nt, nz, col0, packed, tiles;
 };
 
-// max and min that keep a NaN once they have met one (a > m is false for a NaN on either side)
-__device__ __forceinline__ double hg_max(double m, double a) { return (a > m || a != a) ? a : m; }
-__device__ __forceinline__ double hg_min(double m, double a) { return (a < m || a != a) ? a : m; }
+// max and min that keep a NaN once they have met one
+__device__ __forceinline__ double hg_max(double m, double a) { return eig::nan_max(m, a); }
+__device__ __forceinline__ double hg_min(double m, double a) { return eig::nan_min(m, a); }
 __device__ __forceinline__ double hg_wave_max(double m) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = hg_max(m, __shfl_xor(m, o));
@@ -182,8 +184,8 @@ __device__ __forceinline__ double hg_block_min(double a, double *red) {
   return hg_min(hg_min(hg_min(red[0], red[1]), red[2]), red[3]);
 }
 
-// entry i of the start vector before it is normalised: 1 + ((37 i + 11) mod 64) / 64, in [1, 2), exact
-__device__ __forceinline__ double he_start_entry(int i) { return 1.0 + (double)((37 * i + 11) & 63) * 0.015625; }
+// entry i of the start vector before it is normalised
+__device__ __forceinline__ double he_start_entry(int i) { return eig::start_entry(i); }
 
 // Workgroup k: stage k ahead of the recurrence.  g = min_i (q_ii - offsum_i), Gerschgorin's lower bound of the spectrum;
 // the floor theta: flr[k] where the host gave one (not NaN), else eps2 = fl(eps eps) - lowered to sQs where bfgs (the
@@ -308,102 +310,17 @@ __global__ void __launch_bounds__(HE_STEP_THREADS) k_he_step(const HgDesc *__res
   for (int i = threadIdx.x; i < nz; i += HE_STEP_THREADS) vn[i] = wk[i] / beta;
 }
 
-// Workgroup k, one wavefront: the smallest eigenvalue of stage k's tridiagonal T (order m = steps, diagonal alpha_0 ..
-// alpha_{m-1}, off-diagonal beta_0 .. beta_{m-2}; beta_{m-1} is the norm of the last residual) and the shift.  Every
-// operation rounded on its own; hessian_update.eigen_replay repeats them in numpy.
-//   norm      |T| = max_i (|alpha_i| + |beta_{i-1}| + |beta_i|), and Gerschgorin's interval [gl, gu] of T; not finite: outcome 4
-//   bracket   lo = gl - tol, hi = gu + tol, tol = 2^-50 |T|; while hi - lo > tol (32 rounds at most) lane l counts the
-//             eigenvalues below x_l = lo + fl((hi - lo) c_l), c_l = fl((l + 1) / 65), by the Sturm sequence
-//             p_0 = alpha_0 - x, p_i = fl(fl(alpha_i - x) - fl(fl(beta_{i-1}^2) / p_{i-1})), a |p| below pivmin = max(2^-104 |T|,
-//             2^-1000) replaced by pivmin with its sign; hi becomes the first x_l with a count >= 1 and lo the point before it
-//   residual  by lane 0: one step of inverse iteration with T - lo I from a unit vector e_t, by the twisted factorisation -
-//             p_i above at x = lo, the same sequence r_i from the last row upwards, t the first index with the smallest
-//             |fl(fl(p_i + r_i) - fl(alpha_i - lo))|; z_t = 1, z_i = -fl(fl(beta_i / p_i) z_{i+1}) above t and z_{i+1} =
-//             -fl(fl(beta_i / r_{i+1}) z_i) below it: products alone, so that a last component far below the rounding
-//             unit keeps its digits; rho = |beta_{m-1}| fl(|z_{m-1}| / sqrt(z'z)), z'z by separate products and sums
-//   shift     lambda_est = lo - rho; not finite: outcome 4, left alone; lambda_est < theta: d = theta - lambda_est, outcome 2
-//             where rho <= HE_END_REL |T|, else 3; otherwise d = 0, outcome 1
+// Workgroup k, one wavefront: the smallest eigenvalue of stage k's tridiagonal T and the shift - eig::ritz
+// (eigen_ritz.hip.h, which says what it does; hqpkkt_q_eigen_control runs the same body on the blocks of the sparse Q).
 // rep[HE_REPORT k ..]: g, theta (k_he_start), steps, lo, hi, rho, lambda_est, d, |T|, outcome.
 __global__ void __launch_bounds__(64) k_he_ritz(const double *__restrict__ st, const double *__restrict__ T, double *__restrict__ rep) {
-#pragma clang fp contract(off)
-  __shared__ double al[HE_MAX_STEPS], be[HE_MAX_STEPS], b2[HE_MAX_STEPS], pv[HE_MAX_STEPS], rv[HE_MAX_STEPS], z[HE_MAX_STEPS];
-  const int k = blockIdx.x, lane = threadIdx.x;
+  __shared__ eig::RitzLds lds;
+  const int k = blockIdx.x;
   double *r = rep + (long long)HE_REPORT * k;
   if (r[HE_REPORT - 1] >= 0.0) return;  // (outcome 0 or 5: decided by k_he_start)
-  const int m = min((int)st[(long long)HE_STATE * k + 1], HE_MAX_STEPS);
-  for (int i = lane; i < m; i += 64) {
-    const double bi = T[(long long)2 * HE_MAX_STEPS * k + HE_MAX_STEPS + i];
-    al[i] = T[(long long)2 * HE_MAX_STEPS * k + i], be[i] = bi, b2[i] = bi * bi;
-  }
-  __syncthreads();
-  double normT = 0.0, gl = __builtin_inf(), gu = -__builtin_inf();
-  for (int i = 0; i < m; i++) {
-    const double off = (i > 0 ? fabs(be[i - 1]) : 0.0) + (i < m - 1 ? fabs(be[i]) : 0.0);
-    normT = hg_max(normT, fabs(al[i]) + off);
-    gl = hg_min(gl, al[i] - off), gu = hg_max(gu, al[i] + off);
-  }
-  if (m < 1 || !isfinite(normT)) {  // (m < 1: no step has run - the host launches none for orders of 0 alone)
-    if (lane == 0) r[2] = (double)m, r[8] = normT, r[HE_REPORT - 1] = 4.0;
-    return;
-  }
-  const double tol = 0x1p-50 * normT, pivmin = fmax(0x1p-104 * normT, 0x1p-1000);
-  double lo = gl - tol, hi = gu + tol;
-  const double c = (double)(lane + 1) / 65.0;
-  for (int round = 0; round < 32 && hi - lo > tol; round++) {
-    const double x = lo + (hi - lo) * c;
-    double p = al[0] - x;
-    int cnt = p < 0.0;
-    for (int i = 1; i < m; i++) {
-      if (fabs(p) < pivmin) p = p < 0.0 ? -pivmin : pivmin;
-      p = (al[i] - x) - b2[i - 1] / p;
-      cnt += p < 0.0;
-    }
-    const unsigned long long mask = __ballot(cnt >= 1);
-    if (mask == 0ull)
-      lo = __shfl(x, 63);
-    else {
-      const int f = __ffsll((long long)mask) - 1;
-      hi = __shfl(x, f);
-      if (f > 0) lo = __shfl(x, f - 1);
-    }
-  }
-  if (lane != 0) return;
-  pv[0] = al[0] - lo;
-  for (int i = 1; i <= m; i++) {
-    double p = pv[i - 1];
-    if (fabs(p) < pivmin) p = p < 0.0 ? -pivmin : pivmin;
-    pv[i - 1] = p;
-    if (i < m) pv[i] = (al[i] - lo) - b2[i - 1] / p;
-  }
-  rv[m - 1] = al[m - 1] - lo;
-  for (int i = m - 1; i >= 0; i--) {
-    double p = rv[i];
-    if (fabs(p) < pivmin) p = p < 0.0 ? -pivmin : pivmin;
-    rv[i] = p;
-    if (i > 0) rv[i - 1] = (al[i - 1] - lo) - b2[i - 1] / p;
-  }
-  int t = 0;
-  double gmin = __builtin_inf();
-  for (int i = 0; i < m; i++) {
-    const double gam = fabs((pv[i] + rv[i]) - (al[i] - lo));
-    if (gam < gmin) gmin = gam, t = i;
-  }
-  z[t] = 1.0;
-  for (int i = t - 1; i >= 0; i--) z[i] = -((be[i] / pv[i]) * z[i + 1]);
-  for (int i = t; i < m - 1; i++) z[i + 1] = -((be[i] / rv[i + 1]) * z[i]);
-  double zz = 0.0;
-  for (int i = 0; i < m; i++) zz = zz + z[i] * z[i];  // (two roundings: no contraction in this body)
-  const double rho = fabs(be[m - 1]) * (fabs(z[m - 1]) / sqrt(zz));
-  const double lam = lo - rho, theta = r[1];
-  double dk = 0.0;
-  int outcome;
-  if (!isfinite(lam))
-    outcome = 4;
-  else if (lam < theta)
-    dk = theta - lam, outcome = rho <= HE_END_REL * normT ? 2 : 3;
-  else
-    outcome = 1;
-  r[2] = (double)m, r[3] = lo, r[4] = hi, r[5] = rho, r[6] = lam, r[7] = dk, r[8] = normT, r[HE_REPORT - 1] = (double)outcome;
+  const int m = min((int)st[(long long)HE_STATE * k + 1], HE_MAX_STEPS);  // (m < 1: the host launches no step for orders of 0 alone)
+  const double *al = T + (long long)2 * HE_MAX_STEPS * k;
+  eig::ritz(al, al + HE_MAX_STEPS, m, r[1], r, lds);
 }
 
 }  // namespace stg

@@ -498,3 +498,79 @@ def q_bfgs_replay(report, Q_csr, y, Qs, first):
         raise ValueError("q_bfgs_replay: report of (blocks, 8), y and Qs vectors of n entries")
     v, xn, outcome, _theta, _sv = _q_bfgs_apply(report, rows, ix, x, of, inb, y, Qs)
     return v, xn, outcome
+
+
+# ---- the eigenvalue control of Hqp_HL_BFGS on the blocks of the sparse Q (Hqp_IpMatrix.q_eigen_control) ----
+
+def q_block_dense(Q_csr, first, b):
+    """Block ``b`` of the partition ``first`` (``q_blocks_model``) as ``Hqp_IpMatrix.q_eigen_control`` sees it: the symmetric
+    image of the stored entries of the CSR triple ``Q_csr`` with col >= row and both indices in the block (what
+    symsp_extract_mat extracts), a dense matrix with zeros where nothing is stored."""
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first)
+    a, e = int(first[b]), int(first[b + 1])
+    k = np.flatnonzero(inb & (rows >= a) & (rows < e))
+    B = np.zeros((e - a, e - a))
+    B[rows[k] - a, ix[k] - a] = x[k]
+    B[ix[k] - a, rows[k] - a] = x[k]
+    return B
+
+
+def q_lanczos_model(Q_csr, first, theta, max_steps=0):
+    """``lanczos_model`` on every block of the partition ``first`` of the sparse Q, the products through the CSR triple - a
+    block of 8193 needs no dense matrix.  ``theta``: one floor, or one per block.  Returns (g, steps, T): per block
+    Gerschgorin's bound over the block's own entries, the steps taken (0 where g >= theta: no recurrence runs) and T of
+    shape (blocks, 2, cap), alpha then beta, cap = min(max_steps or 64, longest block) - the stride of
+    ``Hqp_IpMatrix.q_eigen_report(with_T=True)``.  numpy's sums run in another order than the device's."""
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first)
+    first = np.asarray(first, dtype=np.int64)
+    n, nb = np.asarray(Q_csr[0]).size - 1, max(first.size - 1, 0)
+    theta = np.broadcast_to(np.asarray(theta, dtype=np.float64), (nb,))
+    cap = int(min(max_steps if max_steps else 64, np.diff(first).max())) if nb else 0
+    g, steps, T = np.zeros(nb), np.zeros(nb, dtype=np.int64), np.zeros((nb, 2, cap))
+    # the blocks' symmetric image as one list of entries, and the diagonal
+    st = inb & (ix > rows)
+    r2, c2, v2 = np.concatenate([rows[inb], ix[st]]), np.concatenate([ix[inb], rows[st]]), np.concatenate([x[inb], x[st]])
+    dg = np.zeros(n)
+    dk = inb & (ix == rows)
+    np.add.at(dg, rows[dk], x[dk])
+    off = np.zeros(n)
+    od = r2 != c2
+    with np.errstate(all="ignore"):
+        np.add.at(off, r2[od], np.abs(v2[od]))
+    for b in range(nb):
+        a, e = int(first[b]), int(first[b + 1])
+        nz = e - a
+        g[b] = (dg[a:e] - off[a:e]).min()  # (a NaN is kept)
+        if g[b] >= theta[b]:
+            continue
+        k = np.flatnonzero((r2 >= a) & (r2 < e))
+        rb, cb, vb = r2[k] - a, c2[k] - a, v2[k]
+
+        def mult(v):
+            w = np.zeros(nz)
+            np.add.at(w, rb, vb * v[cb])
+            return w
+
+        f = lanczos_start(nz)
+        V = [f / np.sqrt(f @ f)]
+        bprev, scale = 0.0, 0.0
+        with np.errstate(all="ignore"):
+            for j in range(min(cap, nz)):
+                v = V[j]
+                w = mult(v)
+                alpha = float(v @ w)
+                w = w - alpha * v
+                if j > 0:
+                    w = w - bprev * V[j - 1]
+                B = np.array(V)
+                w = w - B.T @ (B @ w)
+                beta = float(np.sqrt(w @ w))
+                T[b, 0, j], T[b, 1, j] = alpha, beta
+                steps[b] = j + 1
+                scale = max(scale, abs(alpha))
+                if j + 1 >= nz or not beta > EIG_END_REL * scale:
+                    break
+                scale = max(scale, beta)
+                V.append(w / beta)
+                bprev = beta
+    return g, steps, T

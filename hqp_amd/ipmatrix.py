@@ -433,13 +433,14 @@ class Hqp_IpMatrix:
             _check(self._L.hqpkkt_q_blocks(self._h, int(bsize), C.c_void_p(first.ctypes.data), C.c_void_p(full.ctypes.data), k.value, C.byref(k)), "q_blocks")
         return first[: k.value + 1 if k.value else 0], full
 
-    def q_bfgs_update(self, s, y, gamma=0.1, alpha=1.0, bsize=-1, pattern=False, want_v=False, want_Qs=False):
+    def q_bfgs_update(self, s, y, gamma=0.1, alpha=1.0, bsize=-1, pattern=False, want_v=False, want_Qs=False, eigen_control=None):
         """Hqp_HL_BFGS::update on the sparse Q where it lies (hqpkkt_q_bfgs_update): the damped BFGS update of every block of
         q_blocks(bsize) for the step ``s`` and the change ``y`` of the Lagrangian's gradient; ``gamma`` < 0 adapts the
         damping to the step length ``alpha``.  ``pattern``: the update on the stored entries alone, any pattern (with
         bsize = 0 the update of Hqp_HL_Gangster); otherwise every block must be fully stored (HQPKKT_E_FORMAT).  Returns
         (v, Qs) - v as applied and the block-restricted Q s, None for the one not wanted.  q_bfgs_report() tells what every
-        block did."""
+        block did.  ``eigen_control``: the reference's _eps - the update is followed by q_eigen_control(eps, bsize,
+        from_bfgs=True), the reference's default (sqp_hela_eigen_control); q_eigen_report() tells what that did."""
         ps, ks = self._vec_in(s, self.n, "s")
         py, ky = self._vec_in(y, self.n, "y")
         u = _lib.QBfgsUpdate()
@@ -457,7 +458,48 @@ class Hqp_IpMatrix:
         self._keep_qv = [ks, ky, v, Qs]
         if want_v or want_Qs:
             self._stream_sync(after=True)
+        if eigen_control is not None:
+            self.q_eigen_control(eigen_control, bsize=bsize, from_bfgs=True)
         return v, Qs
+
+    def q_eigen_control(self, eps, bsize=-1, from_bfgs=False, floor=None, max_steps=0):
+        """The eigenvalue control of Hqp_HL_BFGS on the blocks of q_blocks(bsize) of the sparse Q where it lies
+        (hqpkkt_q_eigen_control): every block whose smallest eigenvalue - estimated from below by a Lanczos recurrence on
+        the device - lies under its floor gets the difference added to its diagonal.  The floor is eps^2; ``from_bfgs``
+        lowers it to the s'Qs of the last q_bfgs_update() with this bsize where 0 <= s'Qs < eps^2 and skips the blocks that
+        update left alone; ``floor`` (one value per block) overrides both.  ``max_steps``: 1 .. 128 Lanczos steps, 0 = 64.
+        q_eigen_report() tells what every block did."""
+        e = _lib.QEigenControl()
+        e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = float(eps), int(bsize), int(from_bfgs), int(max_steps)
+        fl = None
+        if floor is not None:
+            fl = np.ascontiguousarray(floor, dtype=np.float64)
+            k = C.c_longlong()
+            _check(self._L.hqpkkt_q_blocks(self._h, int(bsize), None, None, 0, C.byref(k)), "q_blocks")
+            if fl.shape != (k.value,):
+                raise ValueError("q_eigen_control: floor holds one value per block of q_blocks(bsize)")
+            e.floor = fl.ctypes.data
+        self._stream_sync()
+        _check(self._L.hqpkkt_q_eigen_control(self._h, C.byref(e)), "q_eigen_control")
+
+    def q_eigen_report(self, with_T=False):
+        """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound
+        g, the floor theta as used, the Lanczos steps, lo, hi (the bracket of T's smallest eigenvalue), rho (the residual
+        bound), lambda_est = lo - rho, the shift d, |T| and the outcome - 0 no shift, by Gerschgorin; 1 no shift, by Lanczos;
+        2 shifted, converged; 3 shifted, not converged; 4 left alone, not finite; 6 skipped, the last BFGS update left the
+        block alone.  ``with_T``: returns (report, T), T of shape (blocks, 2, t_steps) - alpha then beta of the recurrence,
+        t_steps the step cap of that control.  Waits for the handle's stream."""
+        k, ts = C.c_longlong(), C.c_int()
+        out = np.zeros((1, _lib.HQPKKT_EIG_REPORT))
+        e = self._L.hqpkkt_q_eigen_report(self._h, C.c_void_p(out.ctypes.data), None, 0, C.byref(k), C.byref(ts))
+        T = None
+        if e in (0, _lib.E_RANGE):
+            out = np.zeros((k.value, _lib.HQPKKT_EIG_REPORT))
+            T = np.zeros((k.value, 2, ts.value)) if with_T else None
+            e = self._L.hqpkkt_q_eigen_report(self._h, C.c_void_p(out.ctypes.data), C.c_void_p(T.ctypes.data) if with_T else None, k.value,
+                                              C.byref(k), C.byref(ts))
+        _check(e, "q_eigen_report")
+        return (out, T) if with_T else out
 
     def q_bfgs_report(self):
         """Per block of the last q_bfgs_update() (hqpkkt_q_bfgs_report), an array of shape (blocks, 8): sy, sQs, gamma_eff,

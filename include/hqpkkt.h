@@ -630,7 +630,7 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  * asynchronously in the handle's stream.  Plain loads and stores, no atomics.
  * Entries of Q: only the stored entries with col >= row exist, as for the whole library; entries with col < row are never
  * read and never written.  The diagonal of row i is its stored (i, i).  The entries that write the diagonal
- * (hqpkkt_q_set_diagonal, hqpkkt_q_gerschgorin, hqpkkt_q_dscale_setup, hqpkkt_q_dscale_update) return HQPKKT_E_FORMAT where a
+ * (hqpkkt_q_set_diagonal, hqpkkt_q_gerschgorin, hqpkkt_q_dscale_setup, hqpkkt_q_dscale_update, hqpkkt_q_eigen_control) return HQPKKT_E_FORMAT where a
  * row has no stored diagonal or more than one - the reference inserts one; the pattern here is fixed - decided on the host
  * from the analysed pattern, before any launch; the map row -> index of its diagonal is built once.
  * Checks, before anything is launched, in this order: HQPKKT_E_NULL; HQPKKT_E_RANGE (eps not finite or <= 0, gamma not
@@ -700,12 +700,69 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       HQPKKT_E_FORMAT; HQPKKT_E_DEVICE.  v, Qs (optional, n doubles each, overlapping neither input): v as
  *                       applied (y where a block is not damped) and the block-restricted Q s the update used.  The
  *                       device tables of a bsize are made by the first update with it; later ones allocate nothing.
- *                       Not built: the eigenvalue control of Hqp_HL_BFGS (on by default there) - until it is an entry of its
- *                       own a caller safeguards with hqpkkt_q_gerschgorin.
+ *                       The eigenvalue control of Hqp_HL_BFGS (on by default there) is the entry behind it,
+ *                       hqpkkt_q_eigen_control.
  *   hqpkkt_q_bfgs_report    as hqpkkt_q_dscale_report, per block of the last hqpkkt_q_bfgs_update: 0 sy, 1 sQs, 2 gamma_eff,
  *                       3 theta (1.0 undamped), 4 sv as used, 5 first index, 6 length, 7 outcome - 0 updated, 1 updated
  *                       with damping, 2 left alone (zero), 3 left alone (not finite).  hessian_update.q_bfgs_replay repeats
  *                       the decision and the update in numpy from the reported sums and the returned Qs.
+ *   hqpkkt_q_eigen_control  the eigenvalue control at the end of Hqp_HL_BFGS::update_b_Q (hqp/Hqp_HL_BFGS.C:203-212, which
+ *                       sqp_hela_eigen_control turns on by default) on the blocks of hqpkkt_q_blocks(bsize), in place in Qx.
+ *                       The block of the variable set B is the symmetric image of the stored upper entries with both
+ *                       indices in B - the operator of hqpkkt_q_bfgs_update, what symsp_extract_mat extracts; a block that is
+ *                       not fully stored is the matrix with zeros in the missing places (any pattern is accepted).  Entries
+ *                       across blocks and entries with col < row are never read or written.  Per block, with lambda its
+ *                       smallest eigenvalue and theta_b the floor, the reference's effect: where lambda - theta_b < 0,
+ *                       q_ii -= lambda - theta_b.  theta_b = fl(eps eps); with floor_from_bfgs lowered to sQs_b where
+ *                       0 <= sQs_b < eps eps, sQs_b read ON THE DEVICE from the report words of the last
+ *                       hqpkkt_q_bfgs_update (the reference's rule), and a block that update left alone (its outcome 2, 3)
+ *                       is skipped (outcome 6: the reference's early return); floor, where given, overrides both per
+ *                       block.  lambda is estimated, not computed (the reference calls symmeig per block): a Lanczos
+ *                       recurrence runs on all blocks in lockstep, with the rules of hqpkkt_eigen_control_stage_hessians -
+ *                         Start.  A block-restricted row pass (hqpkkt_q_row_stats counts the entries across blocks) gives
+ *                         Gerschgorin's bound g_b = min_i (q_ii - offsum_i), a NaN kept.  A block with g_b >= theta_b needs no
+ *                         shift and is done (outcome 0).  Every other block starts from v = f / |f|, f_i = 1 + ((37 i + 11)
+ *                         mod 64) / 64 for the index i inside the block.
+ *                         Steps.  min(max_steps, longest block) steps (max_steps 0: 64), each one product w = Q v over all
+ *                         blocks by the launch of hqpkkt_q_bfgs_update's Q s, unchanged, and four launches: alpha_j = v'w;
+ *                         w <- fl(fl(w - fl(alpha_j v)) - fl(beta_{j-1} v_prev)) and the products v_i'w against the whole
+ *                         basis; their removal in ascending i, each product and difference rounded on its own (one full
+ *                         re-orthogonalisation per step), and w'w; beta_j = |w|, the end test, T and v_{j+1} = w / beta_j.
+ *                         A block ends itself where j + 1 equals its length or where beta_j > HQPKKT_EIG_END_REL
+ *                         max(|alpha_0 .. alpha_j|, beta_0 .. beta_{j-1}) does not hold (an invariant subspace; the value
+ *                         is a condition, not critical): its v becomes 0 and it records its step count.  Every sum is made
+ *                         as hqpkkt_q_dscale_update makes its sums (chunks of 4096 from the block's first index, a block's
+ *                         chunks in ascending order): a block's bits depend on its length and its values alone, not on
+ *                         where it lies, on the other blocks or on the mode.  Nothing is read back inside the loop.
+ *                         Ritz value, estimate and shift.  As for the stage entry and by the same device function: the
+ *                         Sturm bracket of T's smallest eigenvalue down to hi - lo <= 2^-50 |T|, rho by the twisted
+ *                         factorisation, lambda_est = lo - rho, d_b = theta_b - lambda_est where lambda_est < theta_b, else 0.
+ *                         Where T or lambda_est is not finite the block is left alone (outcome 4) - NOT the reference,
+ *                         which would write NaN into the block; a NaN in one block reaches no other block.  A thread per
+ *                         variable adds d_b to the stored diagonals, fl(q_ii + d_b); blocks with d_b == 0 are not touched.
+ *                       Checks, before any launch (a call applies to every block or to none), in this order: HQPKKT_E_NULL
+ *                       (h, the arguments); HQPKKT_E_RANGE (eps not finite or <= 0, max_steps outside 0 ..
+ *                       HQPKKT_EIG_MAX_STEPS, floor_from_bfgs neither 0 nor 1); HQPKKT_E_INTERN (not analysed, no values, a
+ *                       refused handle; floor_from_bfgs where the last hqpkkt_q_bfgs_update since the analysis was not
+ *                       with this bsize, or there was none); HQPKKT_E_RANGE (a floor that is not finite: the block count is
+ *                       known only here); HQPKKT_E_FORMAT (a row without exactly one stored diagonal, as for the other
+ *                       entries that write the diagonal); HQPKKT_E_DEVICE; HQPKKT_E_MEM.  The device state belongs to the
+ *                       plan of the bsize, which both this entry and hqpkkt_q_bfgs_update make: the basis (step cap x n
+ *                       doubles - one block of 10^6 at 64 steps is 512 MB), the units' partial sums, T and the report are
+ *                       made or grown by the call that needs them; later calls with the same bsize and a step cap no
+ *                       higher allocate nothing; a failed allocation is HQPKKT_E_MEM with the handle unchanged.
+ *                       Not built: sharded handles; dense stage Hessians (hqpkkt_eigen_control_stage_hessians);
+ *                       Hqp_HL_SparseBFGS's RCM re-blocking; Hqp_HL_AugBFGS; the reference's _logging print.
+ *   hqpkkt_q_eigen_report   as hqpkkt_q_bfgs_report (HQPKKT_E_INTERN before a control since the analysis; cap_blocks too small:
+ *                       HQPKKT_E_RANGE with *n_blocks and *t_steps set); waits for the stream.  Per block of the last
+ *                       hqpkkt_q_eigen_control HQPKKT_EIG_REPORT doubles with the meanings of hqpkkt_eigen_report: 0 g_b;
+ *                       1 theta_b as used; 2 steps; 3 lo; 4 hi; 5 rho; 6 lambda_est; 7 d_b; 8 |T|; 9 the outcome - 0 no shift,
+ *                       by Gerschgorin; 1 no shift, by Lanczos; 2 shifted, converged (rho <= 2^-40 |T|); 3 shifted, not
+ *                       converged; 4 left alone, not finite; 5 never (order 0: reserved, so that hessian_update.eigen_replay
+ *                       serves both entries); 6 skipped, the block's last BFGS update left it alone.  T (optional): per
+ *                       block alpha_0 .. (*t_steps doubles), then beta_0 .. (as many), words past a block's steps 0;
+ *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
+ *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -743,6 +800,18 @@ typedef struct hqpkkt_q_bfgs_update_args {
 int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first /* HOST */, int *full /* HOST */, long long cap, long long *n_blocks);
 int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u);
 int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
+typedef struct hqpkkt_q_eigen_control_args {
+  double eps;          /* the reference's _eps: floor theta_b = fl(eps eps) ... */
+  int bsize;           /* the partition: hqpkkt_q_blocks(bsize) */
+  int floor_from_bfgs; /* 1: ... lowered to sQs_b where 0 <= sQs_b < eps eps, read ON THE DEVICE from the report words of
+                          the last hqpkkt_q_bfgs_update; a block that update left alone (outcome 2, 3) is skipped */
+  const double *floor; /* HOST, n_blocks doubles or NULL: overrides both per block */
+  int max_steps;       /* 1 .. HQPKKT_EIG_MAX_STEPS; 0 = 64 */
+} hqpkkt_q_eigen_control_args;
+int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e);
+int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
+                          double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
+                          long long *n_blocks, int *t_steps);
 int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, const double *z,
                                const double *minus /* or NULL */, double *out);
 /* The same with the dynamics handed over as DENSE blocks instead of CSR rows - what a DOCP of

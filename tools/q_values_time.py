@@ -8,6 +8,12 @@ factorisation.  Per call by wall clock to a device synchronisation, mean of --re
   memory: a device-vector handle does not take them)  (g) hqpkkt_set_values of the device handle from device arrays.
   (h) q_bfgs_update, blocks detected, on a second handle: a block-diagonal Q of --bfgs-blocks fully stored blocks of order
   --bfgs-order with n / 2 bounds      (i) q_bfgs_update, bsize 0, the stored entries alone (PATTERN), on the grid's handle.
+  (j) q_eigen_control on the detected blocks of (h)'s handle (the cap is the blocks' order)      (k) q_eigen_control, bsize 0
+  (one block of n, 64 steps), on a third handle of the grid whose diagonal is lowered by 8 so that Gerschgorin's bound does
+  not settle the block; its values are set again, untimed, before every call.
+  (m), (n) the route through the host that (k) and (j) replace, without the host's eigen-solver, which comes on top:
+  hqpkkt_q_values out to host memory and hqpkkt_set_values in from the pinned staging buffers, on host-vector handles of
+  the grid and of the block-diagonal program.
 Bytes: what the call must move at the least - every operand once per pass that needs it, and the regather of Q's image
 behind a write - and the rate that makes at the measured time.
 
@@ -60,7 +66,16 @@ def main():
     t0 = time.perf_counter()
     Mb = ipmatrix.IpRedSpBKP(device_vectors=True, ordering=2)
     Mb.init(progb)
+    Hb = ipmatrix.IpRedSpBKP(device_vectors=False, ordering=2)
+    Hb.init(progb)
     t_initb = time.perf_counter() - t0
+    # the grid with its diagonal lowered, for (k)
+    pk, ixk, qxk = (np.asarray(v) for v in prog.Q)
+    qlow = np.array(qxk, dtype=np.float64)
+    qlow[ixk == np.repeat(np.arange(n), np.diff(pk))] -= 8.0
+    progk = problems.Program(n, me, m, (prog.Q[0], prog.Q[1], qlow), prog.A, prog.C, prog.c, prog.b, prog.d)
+    Mk = ipmatrix.IpRedSpBKP(device_vectors=True, ordering=2)
+    Mk.init(progk)
     L = _lib.lib()
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(1)
@@ -73,12 +88,20 @@ def main():
     x, c, out, v = tens(rng.normal(size=n)), tens(prog.c), tens(np.zeros(n)), tens(np.zeros(n))
     yy, zz = tens(rng.normal(size=me)), tens(rng.normal(size=m))
     dQ, dA, dC = tens(prog.Q[2]), tens(prog.A[2]), tens(prog.C[2])
-    sq, sa, sc = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert L.hqpkkt_values_staging(Hh._h, C.byref(sq), C.byref(sa), C.byref(sc)) == 0
-    for ptr, val in ((sq, prog.Q[2]), (sa, prog.A[2]), (sc, prog.C[2])):
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        if val.size:
-            C.memmove(ptr.value, val.ctypes.data, val.nbytes)
+    dQk = tens(qlow)
+
+    def staging(H, pr):
+        ptrs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        assert L.hqpkkt_values_staging(H._h, *(C.byref(t) for t in ptrs)) == 0
+        for ptr, val in zip(ptrs, (pr.Q[2], pr.A[2], pr.C[2])):
+            val = np.ascontiguousarray(val, dtype=np.float64)
+            if val.size:
+                C.memmove(ptr.value, val.ctypes.data, val.nbytes)
+        return ptrs
+
+    sq, sa, sc = staging(Hh, prog)
+    bq, ba, bc = staging(Hb, progb)
+    qout, qoutb = np.zeros(len(prog.Q[2])), np.zeros(len(Qb[2]))
     P = lambda t: C.c_void_p(t.data_ptr())
     sb_h = rngb.normal(size=nB)
     sb, yb = tens(sb_h), tens(1.1 * np.einsum("bij,bj->bi", Bm, sb_h.reshape(nb, k)).ravel())
@@ -87,6 +110,14 @@ def main():
         u = _lib.QBfgsUpdate()
         u.s, u.y, u.gamma, u.alpha, u.bsize, u.fill = s_.data_ptr(), y_.data_ptr(), 0.1, 1.0, bsize, fill
         return lambda: L.hqpkkt_q_bfgs_update(H._h, C.byref(u))
+
+    def eigen(H, bsize):
+        e = _lib.QEigenControl()
+        e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, bsize, 0, 0
+        return lambda: L.hqpkkt_q_eigen_control(H._h, C.byref(e))
+
+    def host_route(H, buf, ptrs):
+        return lambda: L.hqpkkt_q_values(H._h, C.c_void_p(buf.ctypes.data)) or L.hqpkkt_set_values(H._h, *ptrs)
 
     def dscale(bsize):
         u = _lib.DScaleUpdate()
@@ -103,7 +134,12 @@ def main():
         ("g set_values, device handle, device arrays", lambda: L.hqpkkt_set_values(M._h, P(dQ), P(dA), P(dC))),
         ("h q_bfgs_update detected blocks, block-diag Q", bfgs(Mb, sb, yb, -1, _lib.HQPKKT_QBFGS_FULL)),
         ("i q_bfgs_update bsize 0 PATTERN, the grid", bfgs(M, s, y, 0, _lib.HQPKKT_QBFGS_PATTERN)),
+        ("j q_eigen_control detected blocks, block-diag Q", eigen(Mb, -1)),
+        ("k q_eigen_control bsize 0, the grid lowered", eigen(Mk, 0)),
+        ("m q_values out + set_values in, host, the grid", host_route(Hh, qout, (sq, sa, sc))),
+        ("n q_values out + set_values in, host, block-diag", host_route(Hb, qoutb, (bq, ba, bc))),
     ]
+    prep = {"k": lambda: L.hqpkkt_set_values(Mk._h, P(dQk), P(dA), P(dC))}  # (untimed: the same block before every control)
     nq, na, nc = len(prog.Q[2]), len(prog.A[2]), len(prog.C[2])
     nqf = 2 * nq - n  # entries of the symmetric image (every row has its diagonal)
     regather = nqf * (4 + 8 + 8)
@@ -116,7 +152,19 @@ def main():
         # stored entry: row, column, kind, the value in and out, Qs, v and the block table gathered; the regather of the image
         return nqf_ * 12 + (n_ + 1) * 4 + n_ * 4 + 2 * n_ * 8 + 3 * n_ * 8 + 2 * n_ * 8 + nq_ * (12 + 16) + 2 * n_ * 8 + n_ * 4 + nqf_ * (4 + 8 + 8)
 
+    def eigen_bytes(n_, nq_, nqf_, steps):
+        # the row pass with the block table and the diagonals; per step the product (the image, the block table, v in, w out),
+        # v'w (2 n), the residual (w in and out, v_j, v_{j-1}), the second pass (w in and out), the next vector (w in, v out) and
+        # the basis read twice, j + 1 vectors each time; the basis cleared; the shift; the regather of the image
+        walk = nqf_ * 12 + (n_ + 1) * 4 + n_ * 4
+        return (walk + 3 * n_ * 8 + n_ * 4 + steps * (walk + 2 * n_ * 8 + 2 * n_ * 8 + 4 * n_ * 8 + 2 * n_ * 8 + 2 * n_ * 8)
+                + 2 * n_ * 8 * steps * (steps + 1) // 2 + steps * n_ * 8 + 2 * n_ * 8 + 2 * n_ * 4 + nqf_ * (4 + 8 + 8))
+
     bytes_min = {
+        "j": eigen_bytes(nB, nqb, nqfb, min(64, k)),
+        "k": eigen_bytes(n, nq, nqf, 64),
+        "m": nq * 8 * 2 + (nq + na + nc) * 8 * 2 + (nqf + 2 * na + 2 * nc) * (4 + 8 + 8),
+        "n": nqb * 8 * 2 + (nqb + nB // 2) * 8 * 2 + (nqfb + 2 * (nB // 2)) * (4 + 8 + 8),
         "h": bfgs_bytes(nB, nqb, nqfb),
         "i": bfgs_bytes(n, nq, nqf),
         "a": 3 * n * 8 + 4 * n * 8 + 2 * n * 4 + regather,  # the sums read s, y, q; the update reads them again and writes q; the diagonal's index twice
@@ -131,6 +179,9 @@ def main():
     torch.cuda.synchronize()
     for r in range(a.warmup + a.reps):
         for nm, fn in paths:
+            if nm[0] in prep:
+                assert prep[nm[0]]() == 0
+                torch.cuda.synchronize()
             t = time.perf_counter()
             e = fn()
             torch.cuda.synchronize()
@@ -156,6 +207,13 @@ def main():
         tm = np.mean(times[paths[k2][0]])
         lines.append(f"({paths[k2][0][0]}): {tm * 1e6:.1f} us against (f) {fm * 1e6:.1f} us and (g) {gm * 1e6:.1f} us"
                      + (" - (f) and (g) are the grid's, whose Q has other sizes" if k2 == 7 else ""))
+    hm, hn = np.mean(times[paths[11][0]]), np.mean(times[paths[12][0]])
+    for k2, host, H in ((9, hn, Mb), (10, hm, Mk)):
+        tm = np.mean(times[paths[k2][0]])
+        r_ = H.q_eigen_report()
+        oc = {int(o): int((r_[:, 9] == o).sum()) for o in np.unique(r_[:, 9])}
+        lines.append(f"({paths[k2][0][0]}): {tm * 1e6:.1f} us, {'below' if tm < host else 'NOT below'} the route through the host ({'n' if k2 == 9 else 'm'}) "
+                     f"{host * 1e6:.1f} us; steps at most {int(r_[:, 2].max())}, blocks by outcome {oc}")
     text = "\n".join(lines)
     print(text)
     if a.out:

@@ -56,6 +56,7 @@ SYMBOLS = [
     "hqpkkt_q_dscale_setup", "hqpkkt_q_dscale_update", "hqpkkt_q_dscale_report", "hqpkkt_lagrangian_gradient",
     "hqpkkt_q_blocks", "hqpkkt_q_bfgs_update", "hqpkkt_q_bfgs_report",
     "hqpkkt_q_eigen_control", "hqpkkt_q_eigen_report",
+    "hqpkkt_lagrangian_gradient_staged",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -268,6 +269,7 @@ def lib():
     L.hqpkkt_q_dscale_update.argtypes = [vp, C.POINTER(DScaleUpdate)]
     L.hqpkkt_q_dscale_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_lagrangian_gradient.argtypes = [vp] * 6
+    L.hqpkkt_lagrangian_gradient_staged.argtypes = [vp] * 6
     L.hqpkkt_q_blocks.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.hqpkkt_q_bfgs_update.argtypes = [vp, C.POINTER(QBfgsUpdate)]
     L.hqpkkt_q_bfgs_report.argtypes = [vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]

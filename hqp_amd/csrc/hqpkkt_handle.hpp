@@ -463,8 +463,8 @@ struct OutPtrs {
   double *dx, *dy, *dz, *dw;
 };
 
-// The caller's vectors of one call of an entry on the sparse Q (hqpkkt.hip) or on the dense stage Hessians
-// (staged_hess_host.hip.h): device vectors are handed through where they lie and finish() does nothing; host vectors are
+// The caller's vectors of one call of an entry on the sparse Q (hqpkkt.hip), on the dense stage Hessians
+// (staged_hess_host.hip.h) or of hqpkkt_lagrangian_gradient_staged (staged_engine.hip): device vectors are handed through where they lie and finish() does nothing; host vectors are
 // copied through the handle's two buffers (TreeDev::CallerBufs) in the handle's stream, and finish() copies the outputs
 // back and waits - a host caller has its results, and its vectors back, when it returns.  At most 5 inputs and 2 outputs,
 // a null vector takes no room.  ready() makes the buffers at the first host call, for the largest need of any entry, so

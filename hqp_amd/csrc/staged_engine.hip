@@ -8,6 +8,7 @@
 #include <limits>
 
 #include "staged.hip.h"
+#include "staged_gradl.hip.h"
 #include "staged_sparse.hip.h"
 #include "staged_profile.hip.h"
 #include "staged_rows.hip.h"
@@ -371,6 +372,34 @@ int hqpkkt_set_values_staged(hqpkkt_t *h, const double *Qx, const double *const 
       if ((int)qs.size() != h->sd->plan.K + 1 || std::find(qs.begin(), qs.end(), 0) != qs.end()) return HQPKKT_E_INTERN;
     }
     return staged_set_values(h, Qx, Ex, Cx, F, ldF, true);
+  });
+}
+
+int hqpkkt_lagrangian_gradient_staged(hqpkkt_t *h, const double *c, const double *y, const double *z, const double *minus, double *out) {
+  return guarded([&]() -> int {
+    if (!h || !c || !out) return HQPKKT_E_NULL;
+    if (h->analyzed && ((h->an.me > 0 && !y) || (h->an.m > 0 && !z))) return HQPKKT_E_NULL;
+    if (!h->analyzed || !h->have_values) return HQPKKT_E_INTERN;
+    if (!staged_dense_ready(h)) return HQPKKT_E_INTERN;  // (a handle of the CSR hand-over: hqpkkt_lagrangian_gradient)
+    if (h->shard_count > 1 || h->an.shard_count > 1 || h->sd->plan.sharded) return HQPKKT_E_INTERN;  // (not built: the ranks' sum)
+    int e;
+    if ((e = ensure_device(h)) || (e = CallerVecs{h}.ready())) return e;
+    const StagedDev &d = *h->sd;
+    const kktdev::StagedPlan &P = d.plan;
+    const Analysis &an = h->an;
+    const size_t n = (size_t)an.n;
+    CallerVecs io{h};
+    const double *dc, *dy, *dz, *dm;
+    double *dout;
+    if ((e = io.in(c, n, &dc)) || (e = io.in(an.me > 0 ? y : nullptr, (size_t)an.me, &dy)) ||
+        (e = io.in(an.m > 0 ? z : nullptr, (size_t)an.m, &dz)) || (e = io.in(minus, n, &dm)))
+      return e;
+    io.out(out, n, &dout);
+    // every variable is a column of one stage: (column blocks of the widest stage) x (K + 1) workgroups
+    KLAUNCH(h, KC_VECTOR, stg::k_st_grad_l<<<dim3((unsigned)d.dres.part_cols, (unsigned)(P.K + 1)), 256, 0, h->stream>>>(
+                              d.dres.desc.p, d.F.p, h->td.AT.dev(), h->td.CT.dev(), dc, dy, dz, dm, dout));
+    HIPCHK(hipGetLastError());
+    return io.finish();
   });
 }
 

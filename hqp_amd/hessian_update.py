@@ -32,6 +32,10 @@ The reference's default, Hqp_HL_BFGS, on the sparse Q itself (``Hqp_IpMatrix.q_b
 hqpkkt_q_bfgs_update) closes the file: ``q_blocks_model`` is Hqp_HL_BFGS::next_block, ``q_bfgs_terms`` the update of every block
 with the reference's operations and sequential sums - on the stored entries alone under ``pattern`` -, and ``q_bfgs_replay``
 the device's decision and its two steps of every stored entry from the sums it REPORTED and the Q s it returned.
+
+The y of all these updates is a difference of two gradients of the Lagrangian; ``grad_l_dense_model`` is grad L = c - A'y - C'z
+for a program whose dynamics rows are dense blocks (``IpLQDOCP.lagrangian_gradient_staged``, hqpkkt_lagrangian_gradient_staged),
+in longdouble, with the term counts and magnitudes its error bound needs.
 """
 from __future__ import annotations
 
@@ -574,3 +578,48 @@ def q_lanczos_model(Q_csr, first, theta, max_steps=0):
                 V.append(w / beta)
                 bprev = beta
     return g, steps, T
+
+
+def grad_l_dense_model(dq, c, y, z, dtype=np.longdouble):
+    """(g, L, mag) of ``IpLQDOCP.lagrangian_gradient_staged`` (hqpkkt_lagrangian_gradient_staged) for a
+    :class:`hqp_amd.problems.DenseDocp`: g = c - A'y - C'z in ``dtype`` (numpy longdouble; int64 for integer data), with the
+    dynamics rows of A taken from the blocks - row li of stage k is [F_k[li], -1.0 at component li of x_{k+1}] - then
+    the rows of E and C.  ``y`` in the reference's row order: the dynamics rows first, then the rows of E.  Per variable
+    i also L_i, the number of terms of t_i = (A'y + C'z)_i - the rows of its stage's block, one for the -y of the row
+    that produces a state of a stage k > 0, the stored entries of column i of E and of C - and mag_i, the sum of the
+    terms' absolute values: a sum of those terms rounded in ANY order, each term rounded once, lies within
+    (L_i + 3) 2^-53 (mag_i + |c_i|) of g_i once c_i has been subtracted."""
+    nx, nu, K = dq.nx, dq.nu, dq.K
+    n, ndyn = dq.n, dq.ndyn
+    y, z, c = (np.asarray(a).astype(dtype) for a in (y, z, c))
+    if c.shape != (n,) or y.shape != (dq.me,) or z.shape != (dq.m,):
+        raise ValueError("grad_l_dense_model: c, y, z are vectors of n, me, m entries")
+    t, mag = np.zeros(n, dtype=dtype), np.zeros(n, dtype=dtype)
+    L = np.zeros(n, dtype=np.int64)
+    col0 = row0 = 0
+    for k in range(K + 1):
+        if k > 0:  # the -1.0 of the rows that produce x_k
+            prev = y[row0 - nx[k]: row0]
+            t[col0: col0 + nx[k]] -= prev
+            mag[col0: col0 + nx[k]] += np.abs(prev)
+            L[col0: col0 + nx[k]] += 1
+        if k == K:
+            break
+        nz, np_ = nx[k] + nu[k], nx[k + 1]
+        F = np.asarray(dq.F[k].cpu().numpy() if hasattr(dq.F[k], "data_ptr") else dq.F[k])
+        if F.shape != (np_, nz):
+            raise ValueError("grad_l_dense_model: F[%d] is not nx[k+1] x (nx[k] + nu[k])" % k)
+        terms = F.astype(dtype) * y[row0: row0 + np_, None]
+        t[col0: col0 + nz] += terms.sum(axis=0)
+        mag[col0: col0 + nz] += np.abs(terms).sum(axis=0)
+        L[col0: col0 + nz] += np_
+        col0 += nz
+        row0 += np_
+    for (p, ix, v), vec in ((dq.E, y[ndyn:]), (dq.C, z)):
+        p, ix = np.asarray(p), np.asarray(ix)
+        v = np.asarray(v.cpu().numpy() if hasattr(v, "data_ptr") else v)
+        if v.size == 0:
+            continue
+        w = v.astype(dtype) * vec[np.repeat(np.arange(p.size - 1), np.diff(p))]
+        np.add.at(t, ix, w), np.add.at(mag, ix, np.abs(w)), np.add.at(L, ix, 1)
+    return c - t, L, mag

@@ -975,6 +975,21 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         _check(self._L.hqpkkt_set_values_staged(self._h, vals[0], fp, ld, vals[1], vals[2]), "update_dense")
         self._keep_q = []  # (set_values_staged has waited for the stream)
 
+    def lagrangian_gradient_staged(self, c, y, z, minus=None):
+        """Hqp_SqpSolver::grd_L on a handle of the dense hand-over (hqpkkt_lagrangian_gradient_staged): c - A'y - C'z with
+        the dynamics rows of A read from the blocks F_k on the device, and minus ``minus`` where given - the difference of
+        two gradients from the second call, the y of bfgs_update_device().  ``y`` in the reference's row order: the
+        dynamics rows first, then the rows of E.  numpy vectors, or torch CUDA tensors with device_vectors=True."""
+        pc, kc = self._vec_in(c, self.n, "c")
+        py, ky = self._vec_in(y if self.me else None, self.me, "y")
+        pz, kz = self._vec_in(z if self.m else None, self.m, "z")
+        pm, km = self._vec_in(minus, self.n, "minus")
+        po, out = self._vec_out(self.n)
+        self._stream_sync()
+        _check(self._L.hqpkkt_lagrangian_gradient_staged(self._h, pc, py, pz, pm, po), "lagrangian_gradient_staged")
+        self._stream_sync(after=True)
+        return out
+
     def stage_structure(self):
         names = {"nk": 20, "mk": 21, "nmk": 22, "eq_ptr": 23, "eq_rows": 24, "fix_rows": 25, "cap": 26}
         return {nm: self.debug(i) for nm, i in names.items()}

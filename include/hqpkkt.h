@@ -624,7 +624,8 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  * Handles: FULL, REDUCED and STAGED ones that have had values.  HQPKKT_E_INTERN otherwise, on a sharded handle, for every
  * hqpkkt_q_* entry on a STAGED handle with HQPKKT_HESS_DENSE (its Hessians are the blocks: the stage-Hessian entries
  * above), and for hqpkkt_lagrangian_gradient on a STAGED handle analysed by hqpkkt_analyze_staged (the dynamics are
- * not in A then; not built).  hqpkkt_lagrangian_gradient does not touch Q and is accepted with dense stage Hessians.
+ * not in A then: hqpkkt_lagrangian_gradient_staged, below, is the entry for such a handle).  hqpkkt_lagrangian_gradient
+ * does not touch Q and is accepted with dense stage Hessians.
  * Vectors hold n doubles (y: me, z: m), pointers per opts.loc.  Host vectors go through buffers the handle owns (made
  * by the first call) and the call returns when the stream has read or written them; device vectors are read and written
  * asynchronously in the handle's stream.  Plain loads and stores, no atomics.
@@ -848,6 +849,37 @@ int hqpkkt_stage_staging(hqpkkt_t *h, int which, double **buf, long long *elems)
 int hqpkkt_set_stage_block(hqpkkt_t *h, int k, const double *F, long long ldF);
 int hqpkkt_set_values_staged(hqpkkt_t *h, const double *Qx, const double *const *F, const long long *ldF,
                              const double *Ex, const double *Cx);
+/* ---- grad L on a handle of the dense hand-over: Hqp_SqpSolver::grd_L, c - A'y - C'z, where the dynamics rows of A are the
+ * blocks F_k in the engine's arena - the y = grad L(x+) - grad L(x) that hqpkkt_bfgs_update_stage_hessians and the other
+ * Hessian approximations consume, formed without a copy of F on the host.  Kernel: csrc/staged_gradl.hip.h.
+ * Handles: STAGED ones analysed by hqpkkt_analyze_staged whose hand-over has ended (hqpkkt_set_values_staged), with the
+ * Hessians in CSR form or as dense blocks, packed or not (Q is not read).  Nothing in the handle is written: a
+ * factorisation stays valid.
+ * Vectors: c, minus and out hold n doubles, z m doubles, y me doubles in the reference's row order - the sum of nx[1..K]
+ * dynamics rows first (stage k's rows start at row0_k = sum of nx[1..k]), then the me_rest rows of E.  Pointers per opts.loc,
+ * host vectors through the buffers of the hqpkkt_q_* entries, with their rule of completion.  y / z may be NULL where
+ * me / m is 0; minus may be NULL.
+ * Checks, before anything is launched, in this order: HQPKKT_E_NULL (h, c, out; y or z of an analysed handle with rows);
+ * HQPKKT_E_INTERN (not analysed; the hand-over has not ended; a handle of the CSR hand-over - hqpkkt_lagrangian_gradient
+ * serves it; a sharded handle: not built, it needs the ranks' sum); HQPKKT_E_DEVICE.
+ * Values, for variable i = column lc of stage k (states of the stage first, then its controls; stage K: its states):
+ *   t_i = sum over the rows li = 0 .. nx[k+1] - 1 of F_k[li][lc] y[row0_k + li]   (k < K; 0 for stage K, which has no block):
+ *         four partial sums, partial w over the rows li = w, w + 4, .. in ascending order from +0.0 by fused multiply-adds,
+ *         added as (p0 + p1) + (p2 + p3)
+ *   t_i = fl(t_i - y[row0_k - nx[k] + lc])   where k > 0 and lc is a state column: the -1.0 of the dynamics row that
+ *         produces that component of x_k
+ *   then t_i = fma(e, y_r, t_i) over the stored entries of column i of E in ascending row order, then t_i = fma(c, z_r, t_i)
+ *         over those of column i of C in ascending row order
+ *   out_i = fl(c_i - t_i), then fl(out_i - minus_i) where minus is given: the two-call protocol of
+ *         hqpkkt_lagrangian_gradient - the gradient with the old blocks first, then, the new blocks handed over, with
+ *         minus = the first result.
+ * One launch, no atomics, no scratch, nothing read back: the same bits from run to run, and a column's bits depend on its
+ * stage's sizes and values alone - not on K, not on the other stages.  The order differs from hqpkkt_lagrangian_gradient's
+ * (lanes share a row there): the two hand-overs of one program agree to rounding, and exactly on integer operands.
+ * The launch is (column blocks of 256 of the widest stage) x (K + 1) workgroups, each sweeping all rows of its columns: a
+ * handle of very few, very wide stages underfills the device, as the residual's pass over F does. */
+int hqpkkt_lagrangian_gradient_staged(hqpkkt_t *h, const double *c, const double *y, const double *z,
+                                      const double *minus /* or NULL */, double *out);
 /* tests: rank and number of carried rows per stage (2 ints each, K+1 stages) of the last factor */
 int hqpkkt_debug_stage_ranks(hqpkkt_t *h, int *out, int cap);
 /* tests: V_k of the last factor (n_k x n_k, row-major); one GPU.  out null: *len alone */

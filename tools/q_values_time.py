@@ -16,8 +16,11 @@ factorisation.  Per call by wall clock to a device synchronisation, mean of --re
   the grid and of the block-diagonal program.
 Bytes: what the call must move at the least - every operand once per pass that needs it, and the regather of Q's image
 behind a write - and the rate that makes at the measured time.
+  (s) --staged K NX NU: hqpkkt_lagrangian_gradient_staged on a handle of the dense hand-over, next to the residual's pass
+  over the same F blocks (staged_gradient_rows below); a run of its own, appended to --out.
 
     python tools/q_values_time.py [--gx 1000 --gy 1000 --reps 20 --warmup 3 --out FILE]
+    python tools/q_values_time.py --staged 200 5000 50 [--reps 20 --warmup 3 --out FILE]
 """
 import argparse
 import ctypes as C
@@ -31,8 +34,81 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hqp_amd import _lib, ipmatrix, problems  # noqa: E402
 
 
+def staged_gradient_rows(K, nx, nu, reps, warmup):
+    """(s) hqpkkt_lagrangian_gradient_staged on the headline's handle: bench.c4_dense(K, nx, nu) - the F blocks made on the
+    device -, Hqp_IpLQDOCP, device vectors, analysis and values alone.  Next to it, on the same handle in the same
+    session, the pass it shares its loads with: the residual's products with the dense dynamics rows, k_st_dyn_both +
+    k_st_dyn_ax_finish (both products, one sweep over F).
+    Times.  (s) by wall clock to a device synchronisation, as the rows above, and by the handle's events around its one
+    launch (class "vector" of hqpkkt_set_profile).  The residual's pass by the events of its class "residual" over one
+    hqpkkt_residual: the two kernels of the pass and the residual's own kernel over Q, E, C and the vectors - n + me + m
+    rows against 40 GB of F at the headline.  hqpkkt_residual is what collects the events, so (s)'s event time is the
+    class "vector" of (s) + a residual less that of a residual alone; the two kinds of round take turns.
+    GB/s: the bytes of the F blocks over the time."""
+    import torch
+    from bench import c4_dense
+    dq = c4_dense(K, nx, nu)
+    fbytes = 8 * sum(int(blk.numel()) for blk in dq.F)
+    t0 = time.perf_counter()
+    M = ipmatrix.IpLQDOCP(device_vectors=True)
+    M.init_dense(dq)
+    t_init = time.perf_counter() - t0
+    dq.F = None  # (the engine holds its own copy)
+    torch.cuda.empty_cache()
+    n, me, m = dq.dims
+    L = _lib.lib()
+    g = torch.Generator(device="cuda").manual_seed(5)
+    rnd = lambda k, lo=-1.0, hi=1.0: torch.empty(k, dtype=torch.float64, device="cuda").uniform_(lo, hi, generator=g)
+    c, y, z, out = rnd(n), rnd(me), rnd(m), rnd(n)
+    zz, ww = rnd(m, 0.1, 1.1), rnd(m, 0.1, 1.1)
+    r = [rnd(k) for k in (n, me, m, m)]
+    d = [rnd(k) for k in (n, me, m, m)]
+    P = lambda t: C.c_void_p(t.data_ptr())
+    res = C.c_double()
+    grad = lambda: L.hqpkkt_lagrangian_gradient_staged(M._h, P(c), P(y), P(z), None, P(out))
+    resid = lambda: L.hqpkkt_residual(M._h, P(zz), P(ww), *(P(t) for t in r), *(P(t) for t in d), C.byref(res))
+    wall, ev = [], {"alone": [], "with": []}
+    torch.cuda.synchronize()
+    for rep in range(warmup + reps):
+        t = time.perf_counter()
+        e = grad()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert e == 0, e
+        if rep >= warmup:
+            wall.append(dt)
+        for kind in ("alone", "with"):
+            M.set_profile(True)
+            assert (grad() if kind == "with" else 0) == 0 and resid() == 0
+            torch.cuda.synchronize()
+            p = M.profile()
+            M.set_profile(False)
+            if rep >= warmup:
+                ev[kind].append((p["vector"][0], p["vector"][1], p["residual"][0], p["residual"][1]))
+    a, w = np.array(ev["alone"]), np.array(ev["with"])
+    wall = np.array(wall)
+    g_ev = w[:, 0] - a[:, 0].mean()
+    rs = np.concatenate([a[:, 2], w[:, 2]])
+    gb = lambda ms: fbytes / (ms * 1e-3) / 1e9
+    spread = rs.max() - rs.min()
+    lines = [
+        f"c4_dense({K}, {nx}, {nu}), Hqp_IpLQDOCP, dense hand-over, device vectors: n {n} me {me} m {m}, F {fbytes / 1e9:.2f} GB; analysis + values {t_init:.1f} s",
+        f"device {torch.cuda.get_device_name(0)}; {reps} rounds after {warmup}; launches per call by class: (s) vector {int(w[0, 1] - a[0, 1])}, "
+        f"hqpkkt_residual vector {int(a[0, 1])} residual {int(a[0, 3])}",
+        f"{'path':58s} {'mean ms':>9s} {'min ms':>9s} {'max ms':>9s} {'GB/s of F':>10s}",
+        f"{'s lagrangian_gradient_staged, wall clock to a synchronise':58s} {wall.mean() * 1e3:9.3f} {wall.min() * 1e3:9.3f} {wall.max() * 1e3:9.3f} {gb(wall.mean() * 1e3):10.1f}",
+        f"{'s lagrangian_gradient_staged, events (k_st_grad_l)':58s} {g_ev.mean():9.3f} {g_ev.min():9.3f} {g_ev.max():9.3f} {gb(g_ev.mean()):10.1f}",
+        f"{'residual class: k_st_dyn_both + k_st_dyn_ax_finish + k_residual':58s} {rs.mean():9.3f} {rs.min():9.3f} {rs.max():9.3f} {gb(rs.mean()):10.1f}",
+        f"(s) by events is {'below' if g_ev.mean() < rs.mean() else 'NOT below'} the residual's pass: {g_ev.mean():.3f} ms against {rs.mean():.3f} ms, "
+        f"whose spread over the rounds is {spread:.3f} ms",
+    ]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--staged", type=int, nargs=3, metavar=("K", "NX", "NU"), default=None,
+                    help="the rows of hqpkkt_lagrangian_gradient_staged at this DOCP alone (the headline: 200 5000 50); --out is appended to")
     ap.add_argument("--gx", type=int, default=1000)
     ap.add_argument("--gy", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=20)
@@ -41,6 +117,14 @@ def main():
     ap.add_argument("--bfgs-order", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.staged:
+        text = "\n".join(staged_gradient_rows(*a.staged, a.reps, a.warmup))
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(text + "\n")
+        return
     import torch
 
     prog = problems.grid_sparse_qp(a.gx, a.gy)

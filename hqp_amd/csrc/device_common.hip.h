@@ -1,5 +1,5 @@
 // Device types, constants and wave-level helpers shared by the units of the library (tree.hip,
-// staged_engine.hip, ip_loops.hip, hqpkkt.hip): declarations and inline functions only, no kernel and no
+// staged_engine.hip, ip_loops.hip, q_entries.hip, hqpkkt.hip): declarations and inline functions only, no kernel and no
 // device variable, so that every unit may include it.
 #pragma once
 #include <hip/hip_runtime.h>

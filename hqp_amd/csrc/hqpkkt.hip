@@ -1,11 +1,8 @@
 // C ABI of the MI355X KKT path (include/hqpkkt.h): handle management, symbolic phase and values, factor / step /
-// residual / solve with the refinement of Hqp_IpMatrix::solve, getters and setters, profile, statistics.  The engines
-// and the interior-point loops are units of their own (hqpkkt_handle.hpp); the entry points here have C linkage by
-// their declarations in include/hqpkkt.h.
+// residual / solve with the refinement of Hqp_IpMatrix::solve, getters and setters, profile, statistics.  The engines,
+// the interior-point loops and the entries on the sparse Q are units of their own (hqpkkt_handle.hpp); the entry points
+// here have C linkage by their declarations in include/hqpkkt.h.
 #include "hqpkkt_handle.hpp"
-#include "q_values.hip.h"
-#include "q_bfgs.hip.h"
-#include "q_eigen.hip.h"
 
 char g_last_hip_error[512] = "";
 std::atomic<long long> g_live_bufs[2];
@@ -152,7 +149,7 @@ static int run_analysis(hqpkkt_t *h, int n, int me, int m, int zd) {
 // the host copies it keeps.  Qx, Ax, Cx: the caller's arrays the values came from.  q_only (the hqpkkt_q_* entries that
 // write Q): A and C are as they were - of the copies Qf alone is gathered again, and the kept host copies come from
 // the device.
-static int values_changed(hqpkkt_t *h, bool q_only, const double *Qx, const double *Ax, const double *Cx) {
+int values_changed(hqpkkt_t *h, bool q_only, const double *Qx, const double *Ax, const double *Cx) {
   Analysis &an = h->an;
   int e;
   for (CsrBuf *c : {&h->td.Qf, &h->td.A, &h->td.AT, &h->td.C, &h->td.CT})
@@ -604,491 +601,6 @@ int solve_tail(hqpkkt_t *h, Vecs &v, const double *z, const double *w, const dou
     if (!(res_acc < rnorm)) return HQPKKT_E_SING;
   }
   return 0;
-}
-
-// ---- the sparse Q where it lies: hqpkkt_q_values .. hqpkkt_lagrangian_gradient (q_values.hip.h)
-
-// The checks that follow an entry's own NULL and RANGE tests, in the header's order: call order and refused handles
-// (HQPKKT_E_INTERN), the diagonal rule of the entries that write a diagonal (HQPKKT_E_FORMAT; decided on the host from the
-// pattern the handle keeps, tables made once), the device, and what the first call makes on it.
-static int qv_refused(hqpkkt_t *h, bool touches_q) {
-  if (!h->analyzed || !h->have_values) return HQPKKT_E_INTERN;
-  if (h->shard_count > 1 || h->an.shard_count > 1) return HQPKKT_E_INTERN;
-  if (h->opts.mode == HQPKKT_MODE_STAGED) {
-    const int f = staged_form(h);
-    if ((f & STAGED_FORM_SHARDED) || (f & (touches_q ? STAGED_FORM_HESS_DENSE : STAGED_FORM_DENSE_DYN))) return HQPKKT_E_INTERN;
-  }
-  return 0;
-}
-static int qv_prepare(hqpkkt_t *h, bool touches_q, bool writes_diag) {
-  int e = qv_refused(h, touches_q);
-  if (e) return e;
-  const Analysis &an = h->an;
-  TreeDev::QVal &q = h->td.qv;
-  if (touches_q && !q.mapped) {
-    q.h_didx.assign((size_t)an.n, -1), q.h_kind.assign((size_t)an.nq, qv::QV_LOWER);
-    q.bad_diag = false;
-    for (int i = 0; i < an.n; i++) {
-      for (int k = h->pQp[i]; k < h->pQp[i + 1]; k++) {
-        const int c = h->pQi[k];
-        if (c > i) q.h_kind[k] = qv::QV_UPPER;
-        if (c != i) continue;
-        if (q.h_didx[i] >= 0) q.bad_diag = true;  // stored twice
-        q.h_didx[i] = k, q.h_kind[k] = i;
-      }
-      if (q.h_didx[i] < 0) q.bad_diag = true;
-    }
-    q.mapped = true;
-  }
-  if (writes_diag && q.bad_diag) return HQPKKT_E_FORMAT;
-  if ((e = ensure_device(h))) return e;
-  if (touches_q && !q.didx.p && ((e = q.didx.upload(q.h_didx)) || (e = q.kind.upload(q.h_kind)))) return e;
-  return CallerVecs{h}.ready();
-}
-
-// lanes per row of the walk over Qf, from its mean row length (as short_rows chooses for the residual's kernels)
-static bool qv_short_q(const hqpkkt_t *h) { return h->an.n > 0 && (double)h->an.Qfull.col.size() / h->an.n < 8.0; }
-// the instances of k_qv_rows by [stats][short rows], of the DScale passes by [a block per wavefront]
-using QvRowsFn = decltype(&qv::k_qv_rows<4, true>);
-static const QvRowsFn qv_rows_kernels[2][2] = {{qv::k_qv_rows<16, false>, qv::k_qv_rows<4, false>}, {qv::k_qv_rows<16, true>, qv::k_qv_rows<4, true>}};
-static const decltype(&qv::k_qv_ds_sums<1>) qv_ds_sums_kernels[2] = {qv::k_qv_ds_sums<4>, qv::k_qv_ds_sums<1>};
-static const decltype(&qv::k_qv_ds_damped<1>) qv_ds_damped_kernels[2] = {qv::k_qv_ds_damped<4>, qv::k_qv_ds_damped<1>};
-static void qv_rows(hqpkkt_t *h, bool stats, const double *x, double *y, double *diag) {
-  const int n = h->an.n;
-  if (n <= 0) return;
-  const TreeDev::QVal &q = h->td.qv;
-  const bool sh = qv_short_q(h);
-  qv_rows_kernels[stats][sh]<<<nblk(n, sh ? 64 : 16), 256, 0, h->stream>>>(n, h->td.Qf.dev(), x, y, q.didx.p, h->td.vals.p, diag);
-}
-// Q's values have been written on the device: the state hqpkkt_set_values would leave with them
-static int qv_written(hqpkkt_t *h) {
-  HIPCHK(hipGetLastError());
-  return h->opts.mode == HQPKKT_MODE_STAGED ? staged_values_changed(h, true) : values_changed(h, true, nullptr, nullptr, nullptr);
-}
-
-int hqpkkt_q_values(hqpkkt_t *h, double *Qx) {
-  return guarded([&]() -> int {
-    if (!h || !Qx) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    const hipMemcpyKind kind = h->opts.loc == HQPKKT_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (h->an.nq) HIPCHK(hipMemcpyAsync(Qx, h->td.vals.p, sizeof(double) * h->an.nq, kind, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-int hqpkkt_q_product(hqpkkt_t *h, const double *x, double *y) {
-  return guarded([&]() -> int {
-    if (!h || !x || !y) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    CallerVecs io{h};
-    const double *dx;
-    double *dy;
-    if ((e = io.in(x, (size_t)h->an.n, &dx))) return e;
-    io.out(y, (size_t)h->an.n, &dy);
-    qv_rows(h, false, dx, dy, nullptr);
-    HIPCHK(hipGetLastError());
-    return io.finish();
-  });
-}
-
-int hqpkkt_q_row_stats(hqpkkt_t *h, double *diag, double *offsum) {
-  return guarded([&]() -> int {
-    if (!h || (!diag && !offsum)) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    CallerVecs io{h};
-    double *dd, *ds;
-    io.out(diag, (size_t)h->an.n, &dd), io.out(offsum, (size_t)h->an.n, &ds);
-    qv_rows(h, true, nullptr, ds, dd);
-    HIPCHK(hipGetLastError());
-    return io.finish();
-  });
-}
-
-int hqpkkt_q_set_diagonal(hqpkkt_t *h, const double *d) {
-  return guarded([&]() -> int {
-    if (!h || !d) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, true);
-    if (e) return e;
-    CallerVecs io{h};
-    const double *dd;
-    if ((e = io.in(d, (size_t)h->an.n, &dd))) return e;
-    if (h->an.nq) qv::k_qv_reset<<<nblk(h->an.nq), 256, 0, h->stream>>>(h->an.nq, h->td.qv.kind.p, h->td.vals.p, dd, 0.0, 0);
-    if ((e = qv_written(h))) return e;
-    return io.finish();
-  });
-}
-
-int hqpkkt_q_dscale_setup(hqpkkt_t *h, double eps) {
-  return guarded([&]() -> int {
-    if (!h) return HQPKKT_E_NULL;
-    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
-    int e = qv_prepare(h, true, true);
-    if (e) return e;
-    if (h->an.nq) qv::k_qv_reset<<<nblk(h->an.nq), 256, 0, h->stream>>>(h->an.nq, h->td.qv.kind.p, h->td.vals.p, nullptr, eps, 1);
-    return qv_written(h);
-  });
-}
-
-int hqpkkt_q_gerschgorin(hqpkkt_t *h, double eps) {
-  return guarded([&]() -> int {
-    if (!h) return HQPKKT_E_NULL;
-    if (!std::isfinite(eps) || !(eps > 0.0)) return HQPKKT_E_RANGE;
-    int e = qv_prepare(h, true, true);
-    if (e) return e;
-    TreeDev::QVal &q = h->td.qv;
-    const int n = h->an.n;
-    if (!q.offsum.p && (e = q.offsum.alloc((size_t)n + 1))) return e;
-    qv_rows(h, true, nullptr, q.offsum.p, nullptr);
-    if (n) qv::k_qv_gerschgorin<<<nblk(n), 256, 0, h->stream>>>(n, q.didx.p, q.offsum.p, eps, h->td.vals.p);
-    return qv_written(h);
-  });
-}
-
-int hqpkkt_q_dscale_update(hqpkkt_t *h, const hqpkkt_dscale_update *u) {
-  return guarded([&]() -> int {
-    if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
-    static_assert(qv::QV_REPORT == HQPKKT_DSCALE_REPORT, "the kernels write the report's words");
-    if (!std::isfinite(u->gamma) || u->gamma < 0.0) return HQPKKT_E_RANGE;
-    int e = qv_prepare(h, true, true);
-    if (e) return e;
-    TreeDev::QVal &q = h->td.qv;
-    const int n = h->an.n;
-    if (n <= 0) {
-      q.rep_blocks = 0;
-      return 0;
-    }
-    qv::DsGeom g;
-    g.n = n, g.B = (u->bsize > 0 && u->bsize < n) ? u->bsize : n;
-    g.cpb = (g.B + qv::QV_CHUNK - 1) / qv::QV_CHUNK;
-    g.nblocks = (int)(((long long)n + g.B - 1) / g.B);
-    g.nunits = (long long)g.nblocks * g.cpb;
-    if (q.part.count < 3 * (size_t)g.nunits || q.rep.count < (size_t)qv::QV_REPORT * g.nblocks) {
-      HIPCHK(hipStreamSynchronize(h->stream));  // (a report or an update still in the stream reads the old ones)
-      if ((e = q.part.alloc(3 * (size_t)g.nunits)) || (e = q.rep.alloc((size_t)qv::QV_REPORT * g.nblocks))) return e;
-    }
-    CallerVecs io{h};
-    const double *ds, *dy;
-    double *dv;
-    if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
-    io.out(u->v, (size_t)n, &dv);
-    double *part = q.part.p, *part2 = q.part.p + 2 * g.nunits;
-    hipStream_t s = h->stream;
-    const bool wave_units = g.B <= 64;  // a block per wavefront (q_values.hip.h)
-    const unsigned ugrid = (unsigned)(wave_units ? (g.nunits + 3) / 4 : g.nunits);
-    qv_ds_sums_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, part);
-    qv::k_qv_ds_decide<<<nblk(g.nblocks), 256, 0, s>>>(g, part, u->gamma, q.rep.p);
-    qv_ds_damped_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, ds, dy, q.rep.p, part2, dv);
-    qv::k_qv_ds_outcome<<<nblk(g.nblocks), 256, 0, s>>>(g, part2, q.rep.p);
-    qv::k_qv_ds_apply<<<nblk(n), 256, 0, s>>>(g, q.didx.p, ds, dy, q.rep.p, h->td.vals.p);
-    q.rep_blocks = g.nblocks;
-    if ((e = qv_written(h))) return e;
-    return io.finish();
-  });
-}
-
-int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
-  return guarded([&]() -> int {
-    if (!h || !out || !n_blocks) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    const TreeDev::QVal &q = h->td.qv;
-    if (q.rep_blocks < 0) return HQPKKT_E_INTERN;
-    *n_blocks = q.rep_blocks;
-    if (cap_blocks < q.rep_blocks) return HQPKKT_E_RANGE;
-    if (q.rep_blocks)
-      HIPCHK(hipMemcpyAsync(out, q.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)q.rep_blocks, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-// ---- Hqp_HL_BFGS and the pattern-kept update on the sparse Q (q_bfgs.hip.h)
-
-// Hqp_HL_BFGS::next_block on the analysed pattern of Q: the blocks' first indices, n behind them; and per block whether
-// every (i, j), i <= j, of it is stored (the rows are strictly ascending: a count decides)
-static void qb_partition(const hqpkkt_t *h, int bsize, std::vector<int> &first, std::vector<unsigned char> &full) {
-  const int n = h->an.n;
-  const int *Qp = h->pQp.data(), *Qi = h->pQi.data();
-  first.clear(), full.clear();
-  for (int b = 0; b < n;) {
-    first.push_back(b);
-    if (bsize < 0) {
-      int end = b;
-      for (; b <= end; b++) {
-        const int last = Qp[b + 1] > Qp[b] ? Qi[Qp[b + 1] - 1] : b;
-        end = std::max(end, last);
-      }
-    } else
-      b += bsize > 0 ? std::min(bsize, n - b) : n - b;
-  }
-  first.push_back(n);
-  if (n == 0) first.clear();
-  for (size_t k = 0; k + 1 < first.size(); k++) {
-    const int a = first[k], e = first[k + 1];
-    long long stored = 0;
-    for (int i = a; i < e; i++)
-      for (int j = Qp[i]; j < Qp[i + 1]; j++) stored += Qi[j] >= i && Qi[j] < e;
-    full.push_back(stored == (long long)(e - a) * (e - a + 1) / 2);
-  }
-}
-static int qb_key(const hqpkkt_t *h, int bsize) { return bsize < 0 ? -1 : (bsize >= h->an.n ? 0 : bsize); }
-
-int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first, int *full, long long cap, long long *n_blocks) {
-  return guarded([&]() -> int {
-    if (!h || !n_blocks) return HQPKKT_E_NULL;
-    if (!h->analyzed) return HQPKKT_E_INTERN;
-    std::vector<int> f;
-    std::vector<unsigned char> fl;
-    qb_partition(h, qb_key(h, bsize), f, fl);
-    *n_blocks = (long long)fl.size();
-    if (!first) return 0;
-    if (cap < *n_blocks) return HQPKKT_E_RANGE;
-    std::copy(f.begin(), f.end(), first);
-    if (full) std::copy(fl.begin(), fl.end(), full);
-    return 0;
-  });
-}
-
-// the plan of one bsize: the host's partition, then (with_device) its tables, partial sums and report on the device
-static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) {
-  TreeDev::QVal &q = h->td.qv;
-  const int key = qb_key(h, bsize), n = h->an.n;
-  int at = -1;
-  for (size_t k = 0; k < q.bfgs_plans.size(); k++)
-    if (q.bfgs_plans[k].bsize == key) at = (int)k;
-  if (at < 0) {
-    TreeDev::QVal::BfgsPlan p;
-    p.bsize = key;
-    qb_partition(h, key, p.first, p.full);
-    p.nblocks = (int)p.full.size();
-    p.all_full = true;
-    for (int b = 0; b < p.nblocks; b++) {
-      const int len = p.first[b + 1] - p.first[b];
-      p.max_len = std::max(p.max_len, len), p.nunits += (len + qv::QV_CHUNK - 1) / qv::QV_CHUNK;
-      p.all_full = p.all_full && p.full[b];
-    }
-    q.bfgs_plans.push_back(std::move(p));
-    at = (int)q.bfgs_plans.size() - 1;
-  }
-  *index = at;
-  TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
-  if (!with_device || p.blk_of.p || n <= 0) return 0;
-  std::vector<int> blk_of((size_t)n), bunit((size_t)p.nblocks + 1), ublk((size_t)p.nunits);
-  for (int b = 0, u = 0; b < p.nblocks; b++) {
-    const int len = p.first[b + 1] - p.first[b];
-    std::fill(blk_of.begin() + p.first[b], blk_of.begin() + p.first[b + 1], b);
-    bunit[b] = u;
-    for (int j = 0; j < (len + qv::QV_CHUNK - 1) / qv::QV_CHUNK; j++) ublk[u++] = b;
-    bunit[b + 1] = u;
-  }
-  int e;
-  if ((e = p.boff.upload(p.first)) || (e = p.bunit.upload(bunit)) || (e = p.ublk.upload(ublk)) || (e = p.part.alloc(3 * (size_t)p.nunits)) ||
-      (e = p.rep.alloc((size_t)qv::QV_REPORT * p.nblocks)))
-    return e;
-  return p.blk_of.upload(blk_of);  // (last: it says the plan is complete)
-}
-
-static const decltype(&qv::k_qb_rows<4>) qb_rows_kernels[2] = {qv::k_qb_rows<16>, qv::k_qb_rows<4>};
-static const decltype(&qv::k_qb_sums<1>) qb_sums_kernels[2] = {qv::k_qb_sums<4>, qv::k_qb_sums<1>};
-static const decltype(&qv::k_qb_damped<1>) qb_damped_kernels[2] = {qv::k_qb_damped<4>, qv::k_qb_damped<1>};
-
-int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
-  return guarded([&]() -> int {
-    if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
-    static_assert(qv::QV_REPORT == HQPKKT_QBFGS_REPORT, "the kernels write the report's words");
-    if (!std::isfinite(u->gamma) || (u->gamma < 0.0 && !std::isfinite(u->alpha))) return HQPKKT_E_RANGE;
-    if (u->fill != HQPKKT_QBFGS_FULL && u->fill != HQPKKT_QBFGS_PATTERN) return HQPKKT_E_RANGE;
-    int e = qv_refused(h, true), at = -1;
-    if (e || (e = qb_plan(h, u->bsize, false, &at))) return e;
-    if (u->fill == HQPKKT_QBFGS_FULL && !h->td.qv.bfgs_plans[at].all_full) return HQPKKT_E_FORMAT;
-    if ((e = qv_prepare(h, true, false))) return e;
-    TreeDev::QVal &q = h->td.qv;
-    const int n = h->an.n, nq = h->an.nq;
-    if (n <= 0) {
-      q.bfgs_last = at;
-      return 0;
-    }
-    if (!q.erow.p) {  // what every plan shares: the entries' rows and columns, Q s and v
-      std::vector<int> erow((size_t)nq);
-      for (int i = 0; i < n; i++) std::fill(erow.begin() + h->pQp[i], erow.begin() + h->pQp[i + 1], i);
-      if ((e = q.ecol.upload(h->pQi)) || (e = q.bfgs_qs.alloc((size_t)n)) || (e = q.bfgs_v.alloc((size_t)n)) || (e = q.erow.upload(erow))) return e;
-    }
-    if ((e = qb_plan(h, u->bsize, true, &at))) return e;
-    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
-    const double gamma_eff = bfgs_gamma_eff(u->gamma, u->alpha);
-    CallerVecs io{h};
-    const double *ds, *dy;
-    if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
-    const qv::BfgsTables g{n, p.nblocks, p.nunits, p.blk_of.p, p.boff.p, p.bunit.p, p.ublk.p};
-    double *Qs = q.bfgs_qs.p, *v = q.bfgs_v.p, *part = p.part.p, *part2 = p.part.p + 2 * (size_t)p.nunits;
-    hipStream_t s = h->stream;
-    const bool sh = qv_short_q(h), wave_units = p.max_len <= 64;  // lanes per row as hqpkkt_q_product; a block per wavefront
-    const unsigned ugrid = (unsigned)(wave_units ? (p.nunits + 3) / 4 : p.nunits);
-    qb_rows_kernels[sh]<<<nblk(n, sh ? 64 : 16), 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, ds, Qs);
-    qb_sums_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, ds, dy, Qs, part);
-    qv::k_qb_decide<<<nblk(p.nblocks), 256, 0, s>>>(g, part, gamma_eff, p.rep.p);
-    qb_damped_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, ds, dy, Qs, p.rep.p, part2, v);
-    qv::k_qb_outcome<<<nblk(p.nblocks), 256, 0, s>>>(g, part2, p.rep.p);
-    if (nq) qv::k_qb_apply<<<nblk(nq), 256, 0, s>>>(nq, q.erow.p, q.ecol.p, q.kind.p, p.blk_of.p, Qs, v, p.rep.p, h->td.vals.p);
-    q.bfgs_last = at;
-    // v and Q s are the handle's own vectors (the update reads them): a caller who asks gets a copy, in the stream
-    const hipMemcpyKind back = io.host() ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (u->v) HIPCHK(hipMemcpyAsync(u->v, v, sizeof(double) * (size_t)n, back, s));
-    if (u->Qs) HIPCHK(hipMemcpyAsync(u->Qs, Qs, sizeof(double) * (size_t)n, back, s));
-    if ((e = qv_written(h))) return e;
-    return io.finish();
-  });
-}
-
-int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
-  return guarded([&]() -> int {
-    if (!h || !out || !n_blocks) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    const TreeDev::QVal &q = h->td.qv;
-    if (q.bfgs_last < 0) return HQPKKT_E_INTERN;
-    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[q.bfgs_last];
-    *n_blocks = p.nblocks;
-    if (cap_blocks < p.nblocks) return HQPKKT_E_RANGE;
-    if (p.nblocks) HIPCHK(hipMemcpyAsync(out, p.rep.p, sizeof(double) * qv::QV_REPORT * (size_t)p.nblocks, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-// ---- the eigenvalue control of Hqp_HL_BFGS on the blocks of the sparse Q (q_eigen.hip.h)
-
-static const decltype(&qv::k_qe_rows<4>) qe_rows_kernels[2] = {qv::k_qe_rows<16>, qv::k_qe_rows<4>};
-static const decltype(&qv::k_qe_unit0<1>) qe_unit0_kernels[2] = {qv::k_qe_unit0<4>, qv::k_qe_unit0<1>};
-static const decltype(&qv::k_qe_v0<1>) qe_v0_kernels[2] = {qv::k_qe_v0<4>, qv::k_qe_v0<1>};
-static const decltype(&qv::k_qe_alpha<1>) qe_alpha_kernels[2] = {qv::k_qe_alpha<4>, qv::k_qe_alpha<1>};
-static const decltype(&qv::k_qe_resid<1>) qe_resid_kernels[2] = {qv::k_qe_resid<4>, qv::k_qe_resid<1>};
-static const decltype(&qv::k_qe_ortho<1>) qe_ortho_kernels[2] = {qv::k_qe_ortho<4>, qv::k_qe_ortho<1>};
-static const decltype(&qv::k_qe_next<1>) qe_next_kernels[2] = {qv::k_qe_next<4>, qv::k_qe_next<1>};
-
-// what a control with `steps` steps needs on the device beside the plan's tables: made or grown here, all or nothing - a
-// failed allocation leaves the plan as it was
-static int qe_buffers(hqpkkt_t *h, TreeDev::QVal::BfgsPlan &p, int steps) {
-  TreeDev::QVal &q = h->td.qv;
-  const size_t n = (size_t)h->an.n;
-  int e;
-  if (!q.eig_w.p && (e = q.eig_w.alloc(2 * n))) return e;  // w, and behind it the row pass
-  if (p.eig_V.p && p.eig_cap >= steps) return 0;
-  HIPCHK(hipStreamSynchronize(h->stream));  // (a report or a control still in the stream reads the old ones)
-  DBuf<double> V, part, T, rep, st, flr;
-  if ((e = V.alloc((size_t)steps * n)) || (e = part.alloc(((size_t)steps + 4) * p.nunits)) || (e = T.alloc(2 * (size_t)steps * p.nblocks)) ||
-      (e = rep.alloc((size_t)qv::QE_REPORT * p.nblocks)) || (e = st.alloc(2 * (size_t)qv::QE_STATE * p.nblocks)) || (e = flr.alloc((size_t)p.nblocks)))
-    return e;
-  p.eig_V = std::move(V), p.eig_part = std::move(part), p.eig_T = std::move(T), p.eig_rep = std::move(rep), p.eig_st = std::move(st),
-  p.eig_floor = std::move(flr);
-  p.eig_cap = steps;
-  return 0;
-}
-
-int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
-  return guarded([&]() -> int {
-    if (!h || !ec) return HQPKKT_E_NULL;
-    static_assert(eig::MAX_STEPS == HQPKKT_EIG_MAX_STEPS && eig::REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
-    if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps < 0 || ec->max_steps > HQPKKT_EIG_MAX_STEPS) return HQPKKT_E_RANGE;
-    if (ec->floor_from_bfgs != 0 && ec->floor_from_bfgs != 1) return HQPKKT_E_RANGE;
-    int e = qv_refused(h, true), at = -1;
-    if (e || (e = qb_plan(h, ec->bsize, false, &at))) return e;
-    TreeDev::QVal &q = h->td.qv;
-    if (ec->floor_from_bfgs && q.bfgs_last != at) return HQPKKT_E_INTERN;
-    for (int b = 0; ec->floor && b < q.bfgs_plans[at].nblocks; b++)
-      if (!std::isfinite(ec->floor[b])) return HQPKKT_E_RANGE;
-    if ((e = qv_prepare(h, true, true))) return e;
-    const int n = h->an.n;
-    if (n <= 0) {
-      q.eig_last = at, q.bfgs_plans[at].eig_steps = 0;
-      return 0;
-    }
-    if ((e = qb_plan(h, ec->bsize, true, &at))) return e;
-    TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[at];
-    const int steps = std::min(ec->max_steps ? ec->max_steps : 64, p.max_len);
-    if ((e = qe_buffers(h, p, steps))) return e;
-    hipStream_t s = h->stream;
-    if (ec->floor) {  // (a host array of the caller's, in the stream behind the last control's reads; it is the caller's again on return)
-      HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-    const qv::BfgsTables g{n, p.nblocks, p.nunits, p.blk_of.p, p.boff.p, p.bunit.p, p.ublk.p};
-    // the partials of a unit: its products against the basis (steps), then v'w, w'w, the row pass' minimum and the start vector's sum
-    double *V = p.eig_V.p, *T = p.eig_T.p, *rep = p.eig_rep.p, *w = q.eig_w.p, *offs = q.eig_w.p + n;
-    double *partc = p.eig_part.p, *parta = partc + (size_t)steps * p.nunits, *partb = parta + p.nunits, *partg = partb + p.nunits, *partf = partg + p.nunits;
-    double *st[2] = {p.eig_st.p, p.eig_st.p + (size_t)qv::QE_STATE * p.nblocks};
-    const bool sh = qv_short_q(h), wave_units = p.max_len <= 64;  // lanes per row as hqpkkt_q_product; a block per wavefront
-    const unsigned ugrid = (unsigned)(wave_units ? (p.nunits + 3) / 4 : p.nunits), rgrid = nblk(n, sh ? 64 : 16);
-    // the basis, `steps` vectors of n, and T are cleared: a block that is done keeps v = 0, words past a block's steps are 0
-    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, s));
-    HIPCHK(hipMemsetAsync(T, 0, sizeof(double) * 2 * (size_t)steps * p.nblocks, s));
-    qe_rows_kernels[sh]<<<rgrid, 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, offs);
-    qe_unit0_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, q.didx.p, h->td.vals.p, offs, partg, partf);
-    qv::k_qe_begin<<<nblk(p.nblocks), 256, 0, s>>>(g, partg, ec->floor ? p.eig_floor.p : nullptr, ec->eps * ec->eps,
-                                                   ec->floor_from_bfgs ? p.rep.p : nullptr, st[0], rep);
-    qe_v0_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, partf, st[0], V);
-    for (int j = 0; j < steps; j++) {  // (nothing is read back: a unit of a block that has ended returns at once)
-      const double *sj = st[j & 1];
-      qb_rows_kernels[sh]<<<rgrid, 256, 0, s>>>(n, h->td.Qf.dev(), p.blk_of.p, V + (size_t)j * n, w);
-      qe_alpha_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V + (size_t)j * n, w, parta);
-      qe_resid_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V, (long long)n, j, steps, w, parta, partc);
-      qe_ortho_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, V, (long long)n, j, steps, w, partc, partb);
-      qe_next_kernels[wave_units]<<<ugrid, 256, 0, s>>>(g, sj, st[(j + 1) & 1], V, (long long)n, j, j + 1 == steps ? 1 : 0, steps, w, parta, partb, T);
-    }
-    qv::k_qe_ritz<<<(unsigned)p.nblocks, 64, 0, s>>>(st[steps & 1], T, steps, rep);
-    qv::k_qe_shift<<<nblk(n), 256, 0, s>>>(n, p.blk_of.p, q.didx.p, rep, h->td.vals.p);
-    q.eig_last = at, p.eig_steps = steps;
-    return qv_written(h);
-  });
-}
-
-int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {
-  return guarded([&]() -> int {
-    if (!h || !out || !n_blocks || !t_steps) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, true, false);
-    if (e) return e;
-    const TreeDev::QVal &q = h->td.qv;
-    if (q.eig_last < 0) return HQPKKT_E_INTERN;
-    const TreeDev::QVal::BfgsPlan &p = q.bfgs_plans[q.eig_last];
-    *n_blocks = p.nblocks, *t_steps = p.eig_steps;
-    if (cap_blocks < p.nblocks) return HQPKKT_E_RANGE;
-    if (p.nblocks) {
-      HIPCHK(hipMemcpyAsync(out, p.eig_rep.p, sizeof(double) * qv::QE_REPORT * (size_t)p.nblocks, hipMemcpyDeviceToHost, h->stream));
-      if (T) HIPCHK(hipMemcpyAsync(T, p.eig_T.p, sizeof(double) * 2 * (size_t)p.eig_steps * p.nblocks, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  });
-}
-
-int hqpkkt_lagrangian_gradient(hqpkkt_t *h, const double *c, const double *y, const double *z, const double *minus, double *out) {
-  return guarded([&]() -> int {
-    if (!h || !c || !out) return HQPKKT_E_NULL;
-    if (h->analyzed && ((h->an.me > 0 && !y) || (h->an.m > 0 && !z))) return HQPKKT_E_NULL;
-    int e = qv_prepare(h, false, false);
-    if (e) return e;
-    const Analysis &an = h->an;
-    const int n = an.n;
-    CallerVecs io{h};
-    const double *dc, *dy, *dz, *dm;
-    double *dout;
-    if ((e = io.in(c, (size_t)n, &dc)) || (e = io.in(an.me > 0 ? y : nullptr, (size_t)an.me, &dy)) ||
-        (e = io.in(an.m > 0 ? z : nullptr, (size_t)an.m, &dz)) || (e = io.in(minus, (size_t)n, &dm)))
-      return e;
-    io.out(out, (size_t)n, &dout);
-    if (n > 0) {
-      if ((double)(an.na + an.nc) / n < 8.0)
-        qv::k_qv_grad_l<4><<<nblk(n, 64), 256, 0, h->stream>>>(n, h->td.AT.dev(), h->td.CT.dev(), dc, dy, dz, dm, dout);
-      else
-        qv::k_qv_grad_l<16><<<nblk(n, 16), 256, 0, h->stream>>>(n, h->td.AT.dev(), h->td.CT.dev(), dc, dy, dz, dm, dout);
-    }
-    HIPCHK(hipGetLastError());
-    return io.finish();
-  });
 }
 
 int hqpkkt_get_sbw(const hqpkkt_t *h, int *sbw) {

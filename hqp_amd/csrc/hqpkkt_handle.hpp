@@ -5,6 +5,7 @@
 //                      posted read-backs
 //   staged_engine.hip  the STAGED engine (staged.hip.h, staged_gemm.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
 //   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
+//   q_entries.hip      the entries on the sparse Q where it lies (q_values.hip.h, q_bfgs.hip.h, q_eigen.hip.h)
 //   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
 #pragma once
 #include "../../include/hqpkkt.h"
@@ -273,30 +274,32 @@ struct TreeDev {
   DBuf<double> tree_x, tree_u;   // tree_u: the exchange copies of the update arena (2 x upd_elems)
   DBuf<int> tree_words, tree_down;  // [0] solves so far, [1] factorisations so far; the fronts root first
   DBuf<double> top_x;  // the exchange arrays of the launch: 2 x top_n x ST_CS contributions, then 2 x top_n x ST_XS solution
-  // the entries on the sparse Q where it lies (hqpkkt_q_product .. hqpkkt_lagrangian_gradient; q_values.hip.h), both engines
+  // the entries on the sparse Q where it lies (hqpkkt_q_product .. hqpkkt_lagrangian_gradient; q_entries.hip), both engines
   struct QVal {
     bool mapped = false, bad_diag = false;  // the host tables are made / a row without exactly one stored diagonal
     std::vector<int> h_didx, h_kind;        // per row the index of its diagonal in Qx (-1: none); per entry its row, QV_UPPER or QV_LOWER
     DBuf<int> didx, kind;
-    DBuf<double> offsum, part, rep;         // Gerschgorin's row pass; DScale's partial sums (3 per unit) and its report
-    long long rep_blocks = -1;              // blocks of the last DScale update since the analysis
-    // hqpkkt_q_blocks / hqpkkt_q_bfgs_update (q_bfgs.hip.h): the partition of 0 .. n-1 for one bsize (< 0 detected, 0 one
-    // block, > 0 blocks of bsize) with its device tables, partial sums and report - made by the first update or eigenvalue
-    // control with that bsize (qb_plan), never regrown.  Both fills share a plan: they differ in the host's test of `all_full` alone.
+    DBuf<double> offsum;                    // Gerschgorin's row pass
+    // hqpkkt_q_blocks / hqpkkt_q_bfgs_update / hqpkkt_q_dscale_update (q_bfgs.hip.h): the partition of 0 .. n-1 for one bsize
+    // (< 0 detected, 0 one block, > 0 blocks of bsize) with its device tables, partial sums and reports - made by the first
+    // update or eigenvalue control with that bsize (qb_plan), never regrown.  Both fills and DScale share a plan: the fills
+    // differ in the host's test of `all_full` alone, and DScale's bsize <= 0 is the one block of key 0.
     struct BfgsPlan {
       int bsize = 0, nblocks = 0, nunits = 0, max_len = 0;
       bool all_full = false;
       std::vector<int> first;            // nblocks + 1: the blocks' first indices, n behind them
       std::vector<unsigned char> full;   // per block: every (i, j), i <= j, is stored
       DBuf<int> blk_of, boff, bunit, ublk;  // block of a variable; first index / first unit of a block (+ 1); block of a unit
-      DBuf<double> part, rep;               // 3 per unit; QV_REPORT per block
+      DBuf<double> part;                    // 3 per unit: scratch of whichever update runs (the stream orders them)
+      DBuf<double> rep, ds_rep;             // QV_REPORT per block: the last BFGS update's words; the last DScale update's,
+                                            // made by the first DScale update on this plan
       // hqpkkt_q_eigen_control (q_eigen.hip.h), made or grown by the control that needs them: the basis (eig_cap vectors of
       // n), the units' partial sums, T (stride 2 eig_steps per block), the report, the state's two copies and the floors
       int eig_cap = 0, eig_steps = 0;       // steps the buffers hold; the step cap of the plan's last control
       DBuf<double> eig_V, eig_part, eig_T, eig_rep, eig_st, eig_floor;
     };
     std::vector<BfgsPlan> bfgs_plans;
-    int bfgs_last = -1;               // plan of the last BFGS update since the analysis
+    int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis
     DBuf<int> erow, ecol;             // row and column of every stored entry of Qx
     DBuf<double> bfgs_qs, bfgs_v;     // Q s restricted to the blocks, v as applied
     int eig_last = -1;                // plan of the last eigenvalue control since the analysis
@@ -463,7 +466,7 @@ struct OutPtrs {
   double *dx, *dy, *dz, *dw;
 };
 
-// The caller's vectors of one call of an entry on the sparse Q (hqpkkt.hip), on the dense stage Hessians
+// The caller's vectors of one call of an entry on the sparse Q (q_entries.hip), on the dense stage Hessians
 // (staged_hess_host.hip.h) or of hqpkkt_lagrangian_gradient_staged (staged_engine.hip): device vectors are handed through where they lie and finish() does nothing; host vectors are
 // copied through the handle's two buffers (TreeDev::CallerBufs) in the handle's stream, and finish() copies the outputs
 // back and waits - a host caller has its results, and its vectors back, when it returns.  At most 5 inputs and 2 outputs,
@@ -607,6 +610,9 @@ void staged_rows_products(hqpkkt_t *h, const Vecs &v, const double **xcw, const 
 int staged_debug_get(const hqpkkt_t *h, int what, std::vector<int> &out);
 // what staged_set_values does behind its copies into the handle's values; q_only: Q's values alone have changed
 int staged_values_changed(hqpkkt_t *h, bool q_only);
+// ... and what hqpkkt_set_values does behind its copies on the tree engine (hqpkkt.hip); Qx, Ax, Cx: the caller's arrays the
+// values came from, null with q_only
+int values_changed(hqpkkt_t *h, bool q_only, const double *Qx, const double *Ax, const double *Cx);
 enum { STAGED_FORM_HESS_DENSE = 1, STAGED_FORM_DENSE_DYN = 2, STAGED_FORM_SHARDED = 4 };
 int staged_form(const hqpkkt_t *h);  // of an analysed STAGED handle
 // hqpkkt.hip

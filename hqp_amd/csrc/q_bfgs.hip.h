@@ -1,16 +1,20 @@
-// gfx950 kernels of hqpkkt_q_bfgs_update (include/hqpkkt.h): the reference's default Hessian approximation Hqp_HL_BFGS - the
-// damped BFGS update of every diagonal block of Hqp_Program::Q - on the sparse Q where it lies on the device, and with
-// it the update on the stored entries of a block alone (the operator of Hqp_HL_Gangster).  The blocks are a partition of
-// the variables into contiguous ranges of ANY lengths (hqpkkt_q_blocks), handed over as tables:
+// gfx950 kernels of hqpkkt_q_bfgs_update and of the passes of hqpkkt_q_dscale_update (include/hqpkkt.h): the reference's
+// default Hessian approximation Hqp_HL_BFGS - the damped BFGS update of every diagonal block of Hqp_Program::Q - on the
+// sparse Q where it lies on the device, and with it the update on the stored entries of a block alone (the operator of
+// Hqp_HL_Gangster).  The blocks are a partition of the variables into contiguous ranges of ANY lengths (hqpkkt_q_blocks),
+// handed over as tables:
 //   blk_of[i]  the block of variable i                      boff[b]   the first index of block b, n behind the last
 //   bunit[b]   the first unit of block b, nunits behind     ublk[u]   the block of unit u
 //   erow[k], ecol[k]  row and column of stored entry k of Qx (kind[k] as in q_values.hip.h)
 // Unit bunit[b] + j is chunk j of block b: QV_CHUNK entries counted from the block's first index.  A unit's sum and a
-// block's sum are those of the DScale passes (ds_unit_sum, ds_block_sum), so a block's bits depend on its length alone -
-// not on where it lies, on the other blocks, on the grid or on the mode.
+// block's sum are ds_unit_sum and ds_block_sum (q_values.hip.h), so a block's bits depend on its length alone - not on
+// where it lies, on the other blocks, on the grid or on the mode.
+// Hqp_HL_DScale::update is the same damped update of a Q that is its diagonal: its sums, decision and outcome are the
+// passes here over the plan of its uniform partition, with (Q s)_i = fl(s_i q_ii) formed in registers (DIAG) where the
+// BFGS update loads the vector Q s; its own kernel is the write of the diagonal alone (k_qv_ds_apply).
 // Plain loads and stores in the handle's stream: no polled words, no waits between workgroups, no atomics.  Operations
 // that are promised to be rounded one by one stand in kernels without contraction; sums that may fuse say __fma_rn.
-// Included by hqpkkt.hip behind q_values.hip.h.
+// Included by q_entries.hip behind q_values.hip.h.
 #pragma once
 #include "q_values.hip.h"
 
@@ -24,6 +28,20 @@ __device__ __forceinline__ void qb_unit(const BfgsTables &g, int u, int &b, int 
   b = g.ublk[u];
   first = g.boff[b] + (u - g.bunit[b]) * QV_CHUNK;
   const int blk_end = g.boff[b + 1];
+  end = blk_end - first > QV_CHUNK ? first + QV_CHUNK : blk_end;
+}
+// The range of unit u in a unit pass.  DIAG (Hqp_HL_DScale): the partition is uniform by definition - blocks of B, the
+// last one shorter - and the plan numbers its units b cpb + j, since only the last block can have fewer than cpb.  So a
+// unit finds its range by division, as k_qv_ds_apply finds a variable's block: the chain of table loads (ublk, then boff
+// and bunit) that would stand before a unit's first entry costs a block of 10^6 variables 5 % of the call.
+template <bool DIAG>
+__device__ __forceinline__ void qb_pass_unit(const BfgsTables &g, int B, int u, int &b, int &first, int &end) {
+  if (!DIAG) return qb_unit(g, u, b, first, end);
+  const int cpb = (B + QV_CHUNK - 1) / QV_CHUNK;
+  b = u / cpb;
+  const int b0 = b * B;
+  first = b0 + (u - b * cpb) * QV_CHUNK;
+  const int blk_end = g.n - b0 > B ? b0 + B : g.n;
   end = blk_end - first > QV_CHUNK ? first + QV_CHUNK : blk_end;
 }
 
@@ -47,11 +65,21 @@ __global__ void __launch_bounds__(256) k_qb_rows(int n, kktdev::CsrDev Q, const 
   if (live && sub == 0) y[row] = s;
 }
 
-// pass 1: part[2 u] = sum s_i y_i, part[2 u + 1] = sum s_i (Qs)_i over unit u.  WPU as in k_qv_ds_sums: 1 where every
-// block of the plan is at most 64 long.
-template <int WPU>
+// (Q s)_i of a pass.  DIAG = false: src is the vector Q s (k_qb_rows).  DIAG = true: Q is its diagonal, src the handle's
+// values and didx the diagonals' indices there - fl(s_i q_ii), one rounded product, never stored; B is the block length
+// of its uniform partition (not read otherwise).
+template <bool DIAG>
+__device__ __forceinline__ double qb_qs(const double *__restrict__ src, const int *__restrict__ didx, int i, double si) {
+#pragma clang fp contract(off)
+  return DIAG ? si * src[didx[i]] : src[i];
+}
+
+// pass 1: part[2 u] = sum s_i y_i, part[2 u + 1] = sum s_i (Qs)_i over unit u.  One unit's sum: thread t takes the
+// entries t, t + stride, .. by fused multiply-adds, then ds_unit_sum.  WPU = 1 where every block of the plan is at most
+// 64 long.
+template <int WPU, bool DIAG>
 __global__ void __launch_bounds__(256) k_qb_sums(BfgsTables g, const double *__restrict__ s, const double *__restrict__ y,
-                                                 const double *__restrict__ Qs, double *__restrict__ part) {
+                                                 const double *__restrict__ src, const int *__restrict__ didx, int B, double *__restrict__ part) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
   const long long u = WPU == 1 ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long long)blockIdx.x;
@@ -59,11 +87,11 @@ __global__ void __launch_bounds__(256) k_qb_sums(BfgsTables g, const double *__r
   double a = 0.0, c = 0.0;
   if (u < g.nunits) {
     int b, first, end;
-    qb_unit(g, (int)u, b, first, end);
+    qb_pass_unit<DIAG>(g, B, (int)u, b, first, end);
     for (int i = first + t; i < end; i += stride) {
       const double si = s[i];
       a = __fma_rn(si, y[i], a);
-      c = __fma_rn(si, Qs[i], c);
+      c = __fma_rn(si, qb_qs<DIAG>(src, didx, i, si), c);
     }
   }
   a = ds_unit_sum<WPU>(a, red), c = ds_unit_sum<WPU>(c, red);
@@ -88,11 +116,12 @@ __global__ void __launch_bounds__(256) k_qb_decide(BfgsTables g, const double *_
 }
 
 // pass 2: v_i = fl(fl(theta y_i) + fl(fl(1 - theta) (Qs)_i)) on a damped block and part2[u] = sum s_i v_i in the order of
-// pass 1; v_i = y_i on the others.  v is the handle's own vector: k_qb_apply reads it.
-template <int WPU>
+// pass 1; v_i = y_i on the others.  DIAG = false: v is the handle's own vector, k_qb_apply reads it.  DIAG = true: v is
+// the caller's and optional - k_qv_ds_apply forms v_i again.
+template <int WPU, bool DIAG>
 __global__ void __launch_bounds__(256) k_qb_damped(BfgsTables g, const double *__restrict__ s, const double *__restrict__ y,
-                                                   const double *__restrict__ Qs, const double *__restrict__ rep,
-                                                   double *__restrict__ part2, double *__restrict__ v) {
+                                                   const double *__restrict__ src, const int *__restrict__ didx, int B,
+                                                   const double *__restrict__ rep, double *__restrict__ part2, double *__restrict__ v) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
   const long long u = WPU == 1 ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long long)blockIdx.x;
@@ -100,17 +129,18 @@ __global__ void __launch_bounds__(256) k_qb_damped(BfgsTables g, const double *_
   double c = 0.0;
   if (u < g.nunits) {
     int b, first, end;
-    qb_unit(g, (int)u, b, first, end);
+    qb_pass_unit<DIAG>(g, B, (int)u, b, first, end);
     const double *r = rep + QV_REPORT * (long long)b;
     const bool damp = r[7] == 1.0;
     const double theta = r[3], omt = 1.0 - theta;
     if (damp)
       for (int i = first + t; i < end; i += stride) {
-        const double vi = theta * y[i] + omt * Qs[i];
-        v[i] = vi;
-        c = __fma_rn(s[i], vi, c);
+        const double si = s[i];
+        const double vi = theta * y[i] + omt * qb_qs<DIAG>(src, didx, i, si);
+        if (!DIAG || v) v[i] = vi;
+        c = __fma_rn(si, vi, c);
       }
-    else
+    else if (!DIAG || v)
       for (int i = first + t; i < end; i += stride) v[i] = y[i];
   }
   c = ds_unit_sum<WPU>(c, red);

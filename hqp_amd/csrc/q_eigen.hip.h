@@ -19,7 +19,7 @@
 // word another unit of its block writes in the same launch.
 // Per step, behind the product w = Q v_j by k_qb_rows (unchanged): k_qe_alpha, k_qe_resid, k_qe_ortho, k_qe_next - four
 // launches.  A block that is done costs a state test per unit.
-// Included by hqpkkt.hip behind q_bfgs.hip.h.
+// Included by q_entries.hip behind q_bfgs.hip.h.
 #pragma once
 #include "eigen_ritz.hip.h"
 #include "q_bfgs.hip.h"

@@ -8,7 +8,7 @@
 // Plain loads and stores in the handle's stream: no polled words, no waits between workgroups, no atomics.  The kernels
 // whose operations are promised to be rounded one by one are compiled without contraction and written with the
 // operators (staged_hess_bfgs.hip.h says why __dmul_rn is not enough); sums that may fuse say so with __fma_rn.
-// Included by hqpkkt.hip.
+// Included by q_entries.hip, which has the host code of these entries.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,23 +97,13 @@ __global__ void __launch_bounds__(256) k_qv_gerschgorin(int n, const int *__rest
   vals[didx[i]] = q > t ? q : t;
 }
 
-// ---------------------------------------------------------------- Hqp_HL_DScale::update
-// Block b: the variables [b B, min((b + 1) B, n)).  A block's sums are made of its chunks of QV_CHUNK entries, counted
-// from its first index; unit u = b cpb + j is chunk j of block b (the last block's units past its end are empty and never
-// read).  One unit's sum: thread t of 256 takes the entries t, t + 256, .. by fused multiply-adds, kktdev::wave_sum, the
-// four wavefronts in order.  WPU = 4: a workgroup per unit.  WPU = 1 (B <= 64 alone): a wavefront per unit, four units a
-// workgroup - the entries sit in the lanes they have as the first wavefront of a workgroup, and the three sums that a
-// workgroup's other wavefronts would bring are the zeros added here, so the bits are those of WPU = 4.
-struct DsGeom {
-  int n, B, cpb, nblocks;
-  long long nunits;
-};
-__device__ __forceinline__ void ds_unit(const DsGeom &g, long long u, long long &first, long long &end) {
-  const long long b = u / g.cpb, j = u % g.cpb;
-  const long long blk_end = (b + 1) * g.B < g.n ? (b + 1) * g.B : g.n;
-  first = b * g.B + j * QV_CHUNK;
-  end = first + QV_CHUNK < blk_end ? first + QV_CHUNK : blk_end;
-}
+// ---------------------------------------------------------------- sums of a block
+// A block's sums (Hqp_HL_DScale::update, Hqp_HL_BFGS, the eigenvalue control; the passes are in q_bfgs.hip.h and
+// q_eigen.hip.h) are made of its chunks of QV_CHUNK entries, counted from its first index: a unit each.  One unit's sum:
+// thread t of 256 takes the entries t, t + 256, .. by fused multiply-adds, kktdev::wave_sum, the four wavefronts in order.
+// WPU = 4: a workgroup per unit.  WPU = 1 (no block longer than 64): a wavefront per unit, four units a workgroup - the
+// entries sit in the lanes they have as the first wavefront of a workgroup, and the three sums that a workgroup's other
+// wavefronts would bring are the zeros added here, so the bits are those of WPU = 4.
 template <int WPU>
 __device__ __forceinline__ double ds_unit_sum(double a, double *red) {
   a = kktdev::wave_sum(a);
@@ -123,30 +113,6 @@ __device__ __forceinline__ double ds_unit_sum(double a, double *red) {
   __syncthreads();
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
-
-// pass 1: part[2 u] = sum s_i y_i, part[2 u + 1] = sum sq_i s_i with sq_i = fl(s_i q_i)
-template <int WPU>
-__global__ void __launch_bounds__(256) k_qv_ds_sums(DsGeom g, const int *__restrict__ didx, const double *__restrict__ vals,
-                                                    const double *__restrict__ s, const double *__restrict__ y, double *__restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ double red[4];
-  const long long u = WPU == 1 ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long long)blockIdx.x;
-  const int t = WPU == 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x, stride = WPU == 1 ? 64 : 256;
-  double a = 0.0, b = 0.0;
-  if (u < g.nunits) {
-    long long first, end;
-    ds_unit(g, u, first, end);
-    for (long long i = first + t; i < end; i += stride) {
-      const double si = s[i];
-      const double sq = si * vals[didx[i]];
-      a = __fma_rn(si, y[i], a);
-      b = __fma_rn(sq, si, b);
-    }
-  }
-  a = ds_unit_sum<WPU>(a, red), b = ds_unit_sum<WPU>(b, red);
-  if (t == 0 && u < g.nunits) part[2 * u] = a, part[2 * u + 1] = b;
-}
-
 // a block's sum: its units' partials added in ascending order
 __device__ __forceinline__ double ds_block_sum(long long len, const double *__restrict__ p, int stride) {
   const long long nch = (len + QV_CHUNK - 1) / QV_CHUNK;
@@ -154,81 +120,20 @@ __device__ __forceinline__ double ds_block_sum(long long len, const double *__re
   for (long long j = 1; j < nch; j++) a += p[j * stride];
   return a;
 }
-// the decision, a thread per block: damped where sy < fl(gamma sqs), theta = fl(fl((1 - gamma) sqs) / fl(sqs - sy)).
-// rep[8 b ..]: sy, sqs, gamma, theta, sv (sy so far), first index, length, 1 where damped (k_qv_ds_outcome ends 4 and 7)
-__global__ void __launch_bounds__(256) k_qv_ds_decide(DsGeom g, const double *__restrict__ part, double gamma, double *__restrict__ rep) {
-#pragma clang fp contract(off)
-  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b >= g.nblocks) return;
-  const long long first = b * g.B, end = (b + 1) * g.B < g.n ? (b + 1) * g.B : g.n;
-  const double *p = part + 2 * b * g.cpb;
-  const double sy = ds_block_sum(end - first, p, 2), sqs = ds_block_sum(end - first, p + 1, 2);
-  const bool damp = sy < gamma * sqs;  // (false where a sum is NaN)
-  double theta = 1.0;
-  if (damp) theta = ((1.0 - gamma) * sqs) / (sqs - sy);
-  double *r = rep + QV_REPORT * b;
-  r[0] = sy, r[1] = sqs, r[2] = gamma, r[3] = theta, r[4] = sy, r[5] = (double)first, r[6] = (double)(end - first), r[7] = damp ? 1.0 : 0.0;
-}
 
-// pass 2: on a damped block v_i = fl(fl(theta y_i) + fl((1 - theta) sq_i)) and part2[u] = sum s_i v_i in the order of
-// pass 1; v (optional) as applied: y where the block is not damped
-template <int WPU>
-__global__ void __launch_bounds__(256) k_qv_ds_damped(DsGeom g, const int *__restrict__ didx, const double *__restrict__ vals,
-                                                      const double *__restrict__ s, const double *__restrict__ y,
-                                                      const double *__restrict__ rep, double *__restrict__ part2, double *__restrict__ v) {
-#pragma clang fp contract(off)
-  __shared__ double red[4];
-  const long long u = WPU == 1 ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long long)blockIdx.x;
-  const int t = WPU == 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x, stride = WPU == 1 ? 64 : 256;
-  double c = 0.0;
-  if (u < g.nunits) {
-    long long first, end;
-    ds_unit(g, u, first, end);
-    const double *r = rep + QV_REPORT * (u / g.cpb);
-    const bool damp = r[7] == 1.0;
-    const double theta = r[3], omt = 1.0 - theta;
-    if (damp)
-      for (long long i = first + t; i < end; i += stride) {
-        const double si = s[i];
-        const double sq = si * vals[didx[i]];
-        const double vi = theta * y[i] + omt * sq;
-        if (v) v[i] = vi;
-        c = __fma_rn(si, vi, c);
-      }
-    else if (v)
-      for (long long i = first + t; i < end; i += stride) v[i] = y[i];
-  }
-  c = ds_unit_sum<WPU>(c, red);
-  if (t == 0 && u < g.nunits) part2[u] = c;
-}
-
-// the outcome, a thread per block: sv = the sum of pass 2 on a damped block, sy otherwise; 0 updated, 1 updated with
-// damping, 2 left alone (sv or sqs zero), 3 left alone (sv or sqs not finite)
-__global__ void __launch_bounds__(256) k_qv_ds_outcome(DsGeom g, const double *__restrict__ part2, double *__restrict__ rep) {
-  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b >= g.nblocks) return;
-  double *r = rep + QV_REPORT * b;
-  const bool damp = r[7] == 1.0;
-  const double sqs = r[1];
-  double sv = r[0];
-  if (damp) sv = ds_block_sum((long long)r[6], part2 + b * g.cpb, 1);
-  int outcome = damp ? 1 : 0;
-  if (!isfinite(sv) || !isfinite(sqs))
-    outcome = 3;
-  else if (sv == 0.0 || sqs == 0.0)
-    outcome = 2;
-  r[4] = sv, r[7] = (double)outcome;
-}
-
+// ---------------------------------------------------------------- Hqp_HL_DScale::update
+// Block b: the variables [b B, min((b + 1) B, n)).  Sums, decision, v and outcome are k_qb_sums .. k_qb_outcome
+// (q_bfgs.hip.h) over that partition's plan; rep[8 b ..]: sy, sqs, gamma, theta, sv, first index, length, outcome.
 // the update, a thread per variable: q_i <- fl(q_i - fl(fl(sq_i sq_i) / sqs)), then q_i <- fl(q_i + fl(fl(v_i v_i) / sv)),
 // v_i formed again by the operations of pass 2.  Divisions, as in the reference.  The damping of a block that is then
-// left alone (outcome 2, 3) is the one place theta says more than the outcome: rep[3] != 1 there.
-__global__ void __launch_bounds__(256) k_qv_ds_apply(DsGeom g, const int *__restrict__ didx, const double *__restrict__ s,
+// left alone (outcome 2, 3) is the one place theta says more than the outcome: rep[3] != 1 there.  The partition is
+// uniform by definition, so a variable finds its block by a division - no table is loaded.
+__global__ void __launch_bounds__(256) k_qv_ds_apply(int n, int B, const int *__restrict__ didx, const double *__restrict__ s,
                                                      const double *__restrict__ y, const double *__restrict__ rep, double *__restrict__ vals) {
 #pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= g.n) return;
-  const double *r = rep + QV_REPORT * (i / g.B);
+  if (i >= n) return;
+  const double *r = rep + QV_REPORT * (i / B);
   const int outcome = (int)r[7];
   if (outcome >= 2) return;
   const double sqs = r[1], theta = r[3], sv = r[4];

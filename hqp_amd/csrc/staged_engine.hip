@@ -246,7 +246,7 @@ static int staged_set_request(hqpkkt_t *h, bool in_range, Set set) {
     return set(h->staged_rq);
   });
 }
-// the forms of an analysed STAGED handle that the entries on the sparse Q ask about (hqpkkt.hip, qv_prepare)
+// the forms of an analysed STAGED handle that the entries on the sparse Q ask about (q_entries.hip, qv_prepare)
 int staged_form(const hqpkkt_t *h) {
   if (!h->analyzed || h->opts.mode != HQPKKT_MODE_STAGED || !h->sd) return 0;
   const kktdev::StagedPlan &P = h->sd->plan;

@@ -296,32 +296,45 @@ def _dscale_blocks(n, bsize):
     return [(o, min(o + B, n)) for o in range(0, n, B)] if n else []
 
 
+def _seq_sums(keys, terms, size, start=0.0):
+    """per key the sum of its terms in the order they stand, from +0.0 (in_prod); numpy's unbuffered add.at runs in order.
+    ``start`` = -0.0: from the key's first term, whose sign a zero sum then keeps (-0.0 + t is t for every t)."""
+    out = np.full(size, start)
+    np.add.at(out, keys, terms)
+    return out
+
+
+def _damped(rep, of, y, Qs):
+    """What the damped updates share - Hqp_HL_DScale::update_b_Q with Qs = fl(s q), Hqp_HL_BFGS::update_b_Q with Qs = Q s -
+    from the sums in ``rep`` (columns 0 sy, 1 sQs, 2 gamma, 4 sv where damped), one numpy operation per rounded operation,
+    all blocks at once: the decision, theta, v, sv as used, the blocks that are updated and the outcome codes.  ``of``: the
+    block of every variable.  Returns (v, sqs, sv, ok, outcome, theta)."""
+    one = np.float64(1.0)
+    sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
+    damp = sy < gamma * sqs
+    theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
+    omt = one - theta
+    v = np.where(damp[of], theta[of] * y + omt[of] * Qs, y)
+    sv = np.where(damp, rep[:, 4], sy)
+    finite = np.isfinite(sv) & np.isfinite(sqs)
+    ok = finite & (sv != 0.0) & (sqs != 0.0)
+    outcome = np.where(~finite, 3, np.where(~ok, 2, np.where(damp, 1, 0))).astype(np.int64)
+    return v, sqs, sv, ok, outcome, theta
+
+
 def _dscale_apply(rep, s, y, q, blocks):
-    """decision, theta, v and both steps of q of every block from the sums in ``rep`` (columns 0 sy, 1 sqs, 2 gamma,
-    4 sv where damped): one numpy operation per rounded operation of Hqp_HL_DScale::update_b_Q, all blocks at once."""
+    """decision, theta, v and both steps of q of every block from the sums in ``rep``: ``_damped`` with fl(s q), then the
+    two steps of the diagonal, one numpy operation per rounded operation of Hqp_HL_DScale::update_b_Q"""
     nb = len(blocks)
     if nb == 0:
         return y.copy(), q.copy(), np.zeros(0, dtype=np.int64), np.ones(0), np.zeros(0)
     of = np.repeat(np.arange(nb), [e - a for a, e in blocks])  # the block of every variable
-    one = np.float64(1.0)
     with np.errstate(all="ignore"):
-        sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
-        damp = sy < gamma * sqs
-        theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
-        omt = one - theta
         sq = s * q
-        v = np.where(damp[of], theta[of] * y + omt[of] * sq, y)
-        sv = np.where(damp, rep[:, 4], sy)
-        finite = np.isfinite(sv) & np.isfinite(sqs)
-        ok = finite & (sv != 0.0) & (sqs != 0.0)
-        outcome = np.where(~finite, 3, np.where(~ok, 2, np.where(damp, 1, 0))).astype(np.int64)
+        v, sqs, sv, ok, outcome, theta = _damped(rep, of, y, sq)
         t = q - (sq * sq) / sqs[of]
         qn = np.where(ok[of], t + (v * v) / sv[of], q)
     return v, qn, outcome, theta, sv
-
-
-def _seq_sum(terms):
-    return np.float64(np.add.accumulate(terms)[-1]) if terms.size else np.float64(0.0)
 
 
 def dscale_terms(s, y, q, gamma=0.2, bsize=0):
@@ -332,18 +345,19 @@ def dscale_terms(s, y, q, gamma=0.2, bsize=0):
     reference would write NaN)."""
     s, y, q = (np.ascontiguousarray(a, dtype=np.float64) for a in (s, y, q))
     blocks = _dscale_blocks(s.size, bsize)
-    rep = np.zeros((len(blocks), 8))
+    nb = len(blocks)
+    rep = np.zeros((nb, 8))
     one, g = np.float64(1.0), np.float64(gamma)
-    with np.errstate(all="ignore"):
-        for k, (a, e) in enumerate(blocks):
-            sq = s[a:e] * q[a:e]
-            sy, sqs = _seq_sum(s[a:e] * y[a:e]), _seq_sum(sq * s[a:e])
-            sv = sy
-            if sy < g * sqs:
-                theta = ((one - g) * sqs) / (sqs - sy)
-                sv = _seq_sum(s[a:e] * (theta * y[a:e] + (one - theta) * sq))
-            rep[k, :3] = sy, sqs, g
-            rep[k, 4:7] = sv, a, e - a
+    if nb:
+        of = np.repeat(np.arange(nb), [e - a for a, e in blocks])
+        with np.errstate(all="ignore"):
+            sq = s * q
+            sy, sqs = _seq_sums(of, s * y, nb, -0.0), _seq_sums(of, sq * s, nb, -0.0)
+            damp = sy < g * sqs
+            theta = np.where(damp, ((one - g) * sqs) / (sqs - sy), one)
+            sv = np.where(damp, _seq_sums(of, s * (theta[of] * y + (one - theta)[of] * sq), nb, -0.0), sy)
+        rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 4] = sy, sqs, g, sv
+        rep[:, 5], rep[:, 6] = [a for a, _e in blocks], [e - a for a, e in blocks]
     v, qn, outcome, theta, sv = _dscale_apply(rep, s, y, q, blocks)
     rep[:, 3], rep[:, 4], rep[:, 7] = theta, sv, outcome
     return rep, v, qn
@@ -415,22 +429,13 @@ def _q_bfgs_entries(Q_csr, first):
 
 
 def _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs):
-    """decision, theta, v and both steps of every stored entry from the sums in ``rep`` (columns 0 sy, 1 sQs, 2 gamma_eff,
-    4 sv where damped): one numpy operation per rounded operation, all blocks at once"""
+    """decision, theta, v and both steps of every stored entry from the sums in ``rep``: ``_damped`` with Q s, then the two
+    steps of the entries an update may touch, one numpy operation per rounded operation, all blocks at once"""
     nb = rep.shape[0]
     if nb == 0:
         return y.copy(), x.copy(), np.zeros(0, dtype=np.int64), np.ones(0), np.zeros(0)
-    one = np.float64(1.0)
     with np.errstate(all="ignore"):
-        sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
-        damp = sy < gamma * sqs
-        theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
-        omt = one - theta
-        v = np.where(damp[of], theta[of] * y + omt[of] * Qs, y)
-        sv = np.where(damp, rep[:, 4], sy)
-        finite = np.isfinite(sv) & np.isfinite(sqs)
-        ok = finite & (sv != 0.0) & (sqs != 0.0)
-        outcome = np.where(~finite, 3, np.where(~ok, 2, np.where(damp, 1, 0))).astype(np.int64)
+        v, sqs, sv, ok, outcome, theta = _damped(rep, of, y, Qs)
         xn = x.copy()
         k = np.flatnonzero(inb)
         k = k[ok[of[rows[k]]]]
@@ -438,13 +443,6 @@ def _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs):
         t = x[k] - (Qs[r] * Qs[c]) / sqs[b]
         xn[k] = t + (v[r] * v[c]) / sv[b]
     return v, xn, outcome, theta, sv
-
-
-def _seq_sums(keys, terms, size):
-    """per key the sum of its terms in the order they stand, from +0.0 (in_prod); numpy's unbuffered add.at runs in order"""
-    out = np.zeros(size)
-    np.add.at(out, keys, terms)
-    return out
 
 
 def q_bfgs_terms(Q_csr, s, y, first, gamma=0.1, alpha=1.0, pattern=False):

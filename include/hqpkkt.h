@@ -620,7 +620,7 @@ int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control 
 int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * HQPKKT_EIG_MAX_STEPS */);
 /* ---- The sparse Q where it lies on the device: the reference's Hessian approximations that work on Hqp_Program::Q itself
  * (Hqp_HL::init, Hqp_HL_Gerschgorin, Hqp_HL_DScale - what hqp_cute.tcl selects next to RedSpBKP) and grd_L of
- * Hqp_SqpSolver, without a round trip of Qx | Ax | Cx through hqpkkt_set_values.  Kernels: csrc/q_values.hip.h.
+ * Hqp_SqpSolver, without a round trip of Qx | Ax | Cx through hqpkkt_set_values.  Kernels: csrc/q_values.hip.h; host code: csrc/q_entries.hip.
  * Handles: FULL, REDUCED and STAGED ones that have had values.  HQPKKT_E_INTERN otherwise, on a sharded handle, for every
  * hqpkkt_q_* entry on a STAGED handle with HQPKKT_HESS_DENSE (its Hessians are the blocks: the stage-Hessian entries
  * above), and for hqpkkt_lagrangian_gradient on a STAGED handle analysed by hqpkkt_analyze_staged (the dynamics are

@@ -491,8 +491,52 @@ def check_refused_handles():
     assert _lib.lib().hqpkkt_q_dscale_report(G._h, C.c_void_p(out.ctypes.data), 1, C.byref(k2)) == _lib.E_RANGE and k2.value == 6
 
 
+def check_shared_plans():
+    """A DScale update and a BFGS update (PATTERN) with the same bsize use one partition: neither touches the other's report,
+    whatever ran in between, and the DScale update's bits do not depend on a BFGS update having made the partition's tables
+    first; the eigenvalue control's floor_from_bfgs still reads the BFGS update's words behind a DScale update.  band_qp(65) with bsize 64 (blocks of 64 and 1: a wavefront per unit) and band_qp(4097) with bsize 0 (one block of
+    two chunks: a workgroup per unit)."""
+    for n, bsize in ((65, 64), (4097, 0)):
+        prog = band_qp(n)
+        di = diag_index(prog)
+        s, y, _q = _dscale_case(prog, 17)
+        s2, y2, _q = _dscale_case(prog, 18)
+        for cls in (ipmatrix.IpSpBKP, ipmatrix.IpRedSpBKP):
+            tag = (n, bsize, cls.__name__)
+            M = handle(cls, prog)
+            M.q_bfgs_update(s, y, bsize=bsize, pattern=True)
+            R = M.q_bfgs_report()
+            q_mid = M.q_values().copy()
+            v = M.q_dscale_update(s2, y2, bsize=bsize, want_v=True).copy()
+            D = M.q_dscale_report()
+            d_after = M.q_values()[di].copy()
+            assert D.shape == R.shape == ((n + 63) // 64 if bsize else 1, 8), tag
+            assert bits(M.q_bfgs_report(), R), tag  # (a)
+            M.q_bfgs_update(s2, y2, bsize=bsize, pattern=True)
+            assert not bits(M.q_bfgs_report(), R), tag  # (the other update did write its own words)
+            assert bits(M.q_dscale_report(), D), tag  # (b)
+            F = handle(cls, prog)  # (c): it has never made a BFGS update
+            F.update(with_q(prog, q_mid))
+            vf = F.q_dscale_update(s2, y2, bsize=bsize, want_v=True)
+            assert bits(vf, v) and bits(F.q_dscale_report(), D) and bits(F.q_values()[di], d_after), tag
+            # the eigenvalue control's floor_from_bfgs reads the BFGS update's words behind a DScale update on the same
+            # partition: as on a handle with the same BFGS words and the same Q that has no DScale report
+            A, G = handle(cls, prog), handle(cls, prog)
+            for H in (A, G):
+                H.q_bfgs_update(s, y, bsize=bsize, pattern=True)
+            assert bits(A.q_bfgs_report(), R) and bits(G.q_bfgs_report(), R), tag
+            A.q_dscale_update(s2, y2, bsize=bsize)
+            G.update(with_q(prog, A.q_values()))
+            res = []
+            for H in (A, G):
+                H.q_eigen_control(1.0, bsize=bsize, from_bfgs=True, max_steps=4)
+                rep, T = H.q_eigen_report(with_T=True)
+                res.append((rep, T, H.q_values()))
+            assert all(bits(a, b) for a, b in zip(*res)), tag
+
+
 CHECKS = {f.__name__[6:]: f for f in (check_integers, check_reals, check_lower_entries_and_skips, check_reproducible,
-                                       check_handle_afterwards, check_refused_handles)}
+                                       check_handle_afterwards, check_refused_handles, check_shared_plans)}
 
 
 def main():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The bits of what the entries on the dense stage Hessians (hqpkkt_set_stage_hessian .. hqpkkt_eigen_report, 13 of them)
-and on the sparse Q (hqpkkt_q_values .. hqpkkt_lagrangian_gradient, 9) return and leave behind, for comparing two builds
+and on the sparse Q (hqpkkt_q_values .. hqpkkt_lagrangian_gradient, 16) return and leave behind, for comparing two builds
 of the library whose kernels are the same (a change of the entries' host code): run it once per library (HQPKKT_LIB
 selects one, hqp_amd/_lib.py) and compare the two outputs line for line - there is no tolerance.
 
@@ -11,8 +11,11 @@ of every vector and report every call returned and, behind every call, of every 
 shows it (or of hqpkkt_q_values), in the order of the calls, the code of a call that must fail in its place -, and
 "entries": per entry point the first 16 digits of the sha256 over its own calls alone, which tells where two runs part,
 then the codes of its calls that must fail.  The shapes are those of the GPU tests: tests/hessian_guard_cases.ORDERS on
-packed and unpacked handles, the programs and plugins of tests/q_values_worker.py, host and device vectors each.  Every
-handle runs in a child process of its own, one at a time; a child that fails ends the run."""
+packed and unpacked handles, the programs and plugins of tests/q_values_worker.py, host and device vectors each; for
+hqpkkt_q_blocks, the BFGS update and the eigenvalue control on the sparse Q the cases of tests/q_bfgs_worker.cases() - per
+program and plugin, a fresh handle for every bsize of that program - and of tests/q_eigen_cases.cases(); and DScale and
+BFGS updates taking turns on one handle with one bsize.  Every line runs in a child process of its own, one at a time; a
+child that fails ends the run."""
 import argparse
 import hashlib
 import json
@@ -201,6 +204,92 @@ def sparse_child(problem, cls, device):
     R.done()
 
 
+def bfgs_groups():
+    """q_bfgs_worker.cases() by program and plugin: [(name, class, [(program, bsize, pattern), ..])], a program's cases together"""
+    import q_bfgs_worker as B
+    out = {}
+    for name, prog, classes, bsize, pattern in B.cases():
+        for cls in classes:
+            out.setdefault((name, cls), []).append((prog, bsize, pattern))
+    return [(name, cls, runs) for (name, cls), runs in out.items()]
+
+
+def sparse_bfgs_child(group, device):
+    import q_bfgs_worker as B
+    import q_values_worker as W
+    name, cls, runs = bfgs_groups()[group]
+    cur = {}
+    R = Run(f"sparse-bfgs/{name}/{cls.__name__}/{'device' if device else 'host'}", device, lambda: [to_np(cur["M"].q_values())])
+    v = R.vec
+    for k, (prog, bsize, pattern) in enumerate(runs):
+        M = cur["M"] = W.handle(cls, prog, device)
+        first = B.blocks_of(prog, bsize)
+        s, y = B.mixed_inputs(prog, first, 40 + k)
+        s2, y2 = B.secant_inputs(prog, first, 60 + k)
+        tag = f" bsize={bsize}"
+        R.call("q_blocks", "q_blocks" + tag, lambda: M.q_blocks(bsize))
+        R.call("q_bfgs_report", "q_bfgs_report early", lambda: M.q_bfgs_report(), fails=True)
+        R.call("q_eigen_control", "q_eigen_control from_bfgs early", lambda: M.q_eigen_control(1e-3, bsize=bsize, from_bfgs=True), fails=True)
+        R.call("q_bfgs_update", "q_bfgs_update" + tag, lambda: M.q_bfgs_update(v(s), v(y), bsize=bsize, pattern=pattern, want_v=True, want_Qs=True))
+        R.call("q_bfgs_report", "q_bfgs_report", lambda: M.q_bfgs_report())
+        R.call("q_bfgs_update", "q_bfgs_update gamma<0" + tag, lambda: M.q_bfgs_update(v(s2), v(y2), gamma=-0.5, alpha=0.7, bsize=bsize, pattern=pattern))
+        R.call("q_bfgs_report", "q_bfgs_report", lambda: M.q_bfgs_report())
+        R.call("q_bfgs_update", "q_bfgs_update gamma=nan", lambda: M.q_bfgs_update(v(s), v(y), gamma=np.nan, bsize=bsize, pattern=pattern), fails=True)
+        R.call("q_eigen_control", "q_eigen_control from_bfgs" + tag, lambda: M.q_eigen_control(1.0, bsize=bsize, from_bfgs=True, max_steps=6))
+        R.call("q_eigen_report", "q_eigen_report", lambda: M.q_eigen_report(with_T=True))
+    R.done()
+
+
+def eigen_groups():
+    import q_eigen_cases as E
+    return [(c, cls) for c in E.cases() for cls in c["classes"]]
+
+
+def sparse_eigen_child(group, device):
+    import q_eigen_cases as E
+    import q_values_worker as W
+    case, cls = eigen_groups()[group]
+    prog, bsize = case["prog"], case["bsize"]
+    M = W.handle(cls, prog, device)
+    R = Run(f"sparse-eigen/{case['name']}/{cls.__name__}/{'device' if device else 'host'}", device, lambda: [to_np(M.q_values())])
+    nb = len(case["first"]) - 1
+    R.call("q_eigen_report", "q_eigen_report early", lambda: M.q_eigen_report(), fails=True)
+    R.call("q_eigen_control", "q_eigen_control", lambda: M.q_eigen_control(E.EPS, bsize=bsize))
+    R.call("q_eigen_report", "q_eigen_report", lambda: M.q_eigen_report(with_T=True))
+    R.call("q_eigen_control", "q_eigen_control floors 5 steps", lambda: M.q_eigen_control(E.EPS, bsize=bsize, floor=np.linspace(1.0, 1e3, nb), max_steps=5))
+    R.call("q_eigen_report", "q_eigen_report", lambda: M.q_eigen_report(with_T=True))
+    R.call("q_eigen_report", "q_eigen_report without T", lambda: M.q_eigen_report())
+    R.call("q_eigen_control", "q_eigen_control 129 steps", lambda: M.q_eigen_control(E.EPS, bsize=bsize, max_steps=129), fails=True)
+    R.call("q_eigen_control", "q_eigen_control floor=inf", lambda: M.q_eigen_control(E.EPS, bsize=bsize, floor=np.full(nb, np.inf)), fails=True)
+    R.call("q_eigen_control", "q_eigen_control eps=0", lambda: M.q_eigen_control(0.0, bsize=bsize), fails=True)
+    R.done()
+
+
+INTERLEAVED = ((65, 64), (4097, 0), (300, 7))
+
+
+def sparse_interleaved_child(which, device):
+    """DScale and BFGS (PATTERN) updates with one bsize taking turns on one handle, each report read behind the other's update"""
+    import q_values_worker as W
+    from hqp_amd import ipmatrix
+    n, bsize = INTERLEAVED[which]
+    prog = W.band_qp(n)
+    M = W.handle(ipmatrix.IpRedSpBKP, prog, device)
+    R = Run(f"sparse-interleaved/band{n}/bsize{bsize}/{'device' if device else 'host'}", device, lambda: [to_np(M.q_values())])
+    v = R.vec
+    for k in range(2):
+        s, y, _q = W._dscale_case(prog, 70 + k)
+        R.call("q_dscale_update", "q_dscale_update", lambda: M.q_dscale_update(v(s), v(y), bsize=bsize, want_v=True))
+        R.call("q_bfgs_report", "q_bfgs_report", lambda: M.q_bfgs_report(), fails=k == 0)
+        R.call("q_bfgs_update", "q_bfgs_update", lambda: M.q_bfgs_update(v(y), v(s), bsize=bsize, pattern=True, want_v=True, want_Qs=True))
+        R.call("q_dscale_report", "q_dscale_report", lambda: M.q_dscale_report())
+        R.call("q_bfgs_report", "q_bfgs_report", lambda: M.q_bfgs_report())
+        R.call("q_eigen_control", "q_eigen_control from_bfgs", lambda: M.q_eigen_control(1.0, bsize=bsize, from_bfgs=True, max_steps=4))
+        R.call("q_dscale_report", "q_dscale_report", lambda: M.q_dscale_report())
+        R.call("q_eigen_report", "q_eigen_report", lambda: M.q_eigen_report(with_T=True))
+    R.done()
+
+
 def sparse_refused_child():
     """Dense stage Hessians refuse the entries on Q, the dense hand-over the gradient, a row without a diagonal the writers."""
     import q_values_worker as W
@@ -238,7 +327,10 @@ def jobs():
     out += [["dense-refused", str(pk)] for pk in (1, 0)]
     for q, (name, _prog) in enumerate(W.programs()):
         out += [["sparse", str(q), str(c), str(dev)] for c in range(len(W.classes(name))) for dev in (0, 1)]
-    return out + [["sparse-refused"]]
+    out += [["sparse-refused"]]
+    out += [["sparse-bfgs", str(g), str(dev)] for g in range(len(bfgs_groups())) for dev in (0, 1)]
+    out += [["sparse-eigen", str(g), str(dev)] for g in range(len(eigen_groups())) for dev in (0, 1)]
+    return out + [["sparse-interleaved", str(w), str(dev)] for w in range(len(INTERLEAVED)) for dev in (0, 1)]
 
 
 def main():
@@ -249,7 +341,8 @@ def main():
     args = ap.parse_args()
     if args.child:
         kind, rest = args.child[0], [int(a) for a in args.child[1:]]
-        return {"dense": dense_child, "dense-refused": dense_refused_child, "sparse": sparse_child, "sparse-refused": sparse_refused_child}[kind](*rest)
+        return {"dense": dense_child, "dense-refused": dense_refused_child, "sparse": sparse_child, "sparse-refused": sparse_refused_child,
+                "sparse-bfgs": sparse_bfgs_child, "sparse-eigen": sparse_eigen_child, "sparse-interleaved": sparse_interleaved_child}[kind](*rest)
     out = open(args.out, "w") if args.out else None
     for extra in jobs():  # a fresh process each, one at a time; the first that fails ends the run
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + extra, cwd=ROOT, stdout=subprocess.PIPE, text=True,

@@ -794,6 +794,9 @@ int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long ca
     case 1: src = h->td.linv.p + an.linv_off[node], n = p * p; break;
     case 2: src = h->td.xar.p + an.x_off[node], n = b * p; break;
     case 3: src = h->td.upd.p + an.upd_off[node], n = b * b; break;
+    case 4: src = h->td.dinv.p + 2 * (long long)an.piv_start[node], n = 2 * p; break;
+    case 5: case 6: n = p; break;  // ptype, lperm: ints, returned as doubles
+    case 7: src = h->td.sc.p, n = an.dim; break;
     default: return HQPKKT_E_RANGE;
   }
   *len = n;
@@ -801,6 +804,13 @@ int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long ca
   if (cap < n) return HQPKKT_E_SIZES;
   HIPCHK(hipSetDevice(h->opts.device));
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (what == 5 || what == 6) {
+    std::vector<int> iv((size_t)n);
+    const int *isrc = (what == 5 ? h->td.ptype.p : h->td.lperm.p) + an.piv_start[node];
+    if (n) HIPCHK(hipMemcpy(iv.data(), isrc, sizeof(int) * n, hipMemcpyDeviceToHost));
+    for (long long t = 0; t < n; t++) out[t] = (double)iv[(size_t)t];
+    return 0;
+  }
   if (what == 3 && h->plan.tree_factor) {  // the block is in the exchange copy of the last factorisation (lower triangle; the rest idle)
     int ep = 0;
     HIPCHK(hipMemcpy(&ep, h->td.tree_words.p + 1, sizeof(int), hipMemcpyDeviceToHost));

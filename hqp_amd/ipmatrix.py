@@ -529,7 +529,8 @@ class Hqp_IpMatrix:
 
     def read_block(self, what, node):
         """Numeric block of a supernode after factor() (tests): 0 panel, 1 inverse of
-        L11, 2 X, 3 update block; flat float64 array, column-major."""
+        L11, 2 X, 3 update block; flat float64 array, column-major.  4 dinv (2 p), 5 ptype,
+        6 lperm (p each, as float64), 7 the scale vector (dim, QP numbering; node unused)."""
         k = C.c_longlong()
         _check(self._L.hqpkkt_debug_read(self._h, what, node, None, 0, C.byref(k)), "debug_read")
         out = np.zeros(max(k.value, 1))

@@ -1270,7 +1270,14 @@ int hqpkkt_debug_solve_top_stamps(hqpkkt_t *h, double *out, int cap);
 /* Numeric blocks of one supernode after factor (device -> host copy, tests only):
  * what 0 = panel ((p+b) x p, column-major: L11 below the diagonal, L21), 1 = the
  * explicit inverse of the unit lower L11 (p x p, column-major, diagonal blocks of
- * 16 complete), 2 = X = A21 P' L11^-T (b x p), 3 = update block (b x b).
+ * 16 complete), 2 = X = A21 P' L11^-T (b x p), 3 = update block (b x b; lower
+ * triangle; after a whole-tree factorisation the exchange copy it was posted to),
+ * 4 = the inverse pivot data of the supernode (2 p doubles, the layout of dinv in
+ * hqpkkt_debug_factor_block: 1/d, 0 for a 1x1 pivot; i11 i21 | i22 i21 for a 2x2),
+ * 5 = the pivot types (p values: 0, or 1 followed by 2 for a 2x2), 6 = the pivot
+ * order inside the block (p values: local row at every pivot position) - 5 and 6
+ * are ints on the device and come back as doubles -, 7 = the scale vector of the
+ * last factorisation (dim doubles, QP numbering; `node` must be valid, is not used).
  * *len receives the element count; out may be NULL to query it. */
 int hqpkkt_debug_read(hqpkkt_t *h, int what, int node, double *out, long long cap, long long *len);
 

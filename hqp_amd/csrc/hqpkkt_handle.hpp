@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -284,6 +285,11 @@ struct TreeDev {
     // (< 0 detected, 0 one block, > 0 blocks of bsize) with its device tables, partial sums and reports - made by the first
     // update or eigenvalue control with that bsize (qb_plan), never regrown.  Both fills and DScale share a plan: the fills
     // differ in the host's test of `all_full` alone, and DScale's bsize <= 0 is the one block of key 0.
+    // hqpkkt_q_components / hqpkkt_q_sparse_bfgs_update (q_sparse_bfgs.hip.h): the plan of key QB_COMPONENTS is the partition
+    // into the connected components of Q's graph.  It is a partition of POSITIONS: `member` lists the variables in block
+    // order, first / boff / bunit / ublk count positions, and the unit passes run on vectors packed in that order (`pk`);
+    // blk_of stays per variable.  Every other plan has no member list: a variable is its own position.
+    static const int QB_COMPONENTS = INT_MIN;  // (no bsize gives this key: qb_key makes -1, 0 or a positive one)
     struct BfgsPlan {
       int bsize = 0, nblocks = 0, nunits = 0, max_len = 0;
       bool all_full = false;
@@ -293,6 +299,9 @@ struct TreeDev {
       DBuf<double> part;                    // 3 per unit: scratch of whichever update runs (the stream orders them)
       DBuf<double> rep, ds_rep;             // QV_REPORT per block: the last BFGS update's words; the last DScale update's,
                                             // made by the first DScale update on this plan
+      std::vector<int> member;              // QB_COMPONENTS: the variable at every position (n), ascending inside a block
+      DBuf<int> d_member, pos_of;           // ... on the device, and the position of every variable
+      DBuf<double> pk;                      // ... s and y in block order, n doubles each (Q s and v: bfgs_qs, bfgs_v)
       // hqpkkt_q_eigen_control (q_eigen.hip.h), made or grown by the control that needs them: the basis (eig_cap vectors of
       // n), the units' partial sums, T (stride 2 eig_steps per block), the report, the state's two copies and the floors
       int eig_cap = 0, eig_steps = 0;       // steps the buffers hold; the step cap of the plan's last control
@@ -300,8 +309,9 @@ struct TreeDev {
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis
+    int sbfgs_last = -1;              // the components' plan once hqpkkt_q_sparse_bfgs_update has run since the analysis
     DBuf<int> erow, ecol;             // row and column of every stored entry of Qx
-    DBuf<double> bfgs_qs, bfgs_v;     // Q s restricted to the blocks, v as applied
+    DBuf<double> bfgs_qs, bfgs_v;     // Q s restricted to the blocks, v as applied (the components' plan: in block order)
     int eig_last = -1;                // plan of the last eigenvalue control since the analysis
     DBuf<double> eig_w;               // its product w = Q v (n) and the block-restricted row pass (n)
   } qv;

@@ -1,14 +1,18 @@
-// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 16 of them:
+// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 19 of them:
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
-// (q_bfgs.hip.h), hqpkkt_q_eigen_control and its report (q_eigen.hip.h) and hqpkkt_lagrangian_gradient.  Their state is
+// (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
+// hqpkkt_q_eigen_control and its report (q_eigen.hip.h) and hqpkkt_lagrangian_gradient.  Their state is
 // TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
 // update's own write (k_qv_ds_apply per variable, k_qb_apply per stored entry).  The eigenvalue control runs over the
 // same plans.
+#include <numeric>
+
 #include "hqpkkt_handle.hpp"
 #include "q_values.hip.h"
 #include "q_bfgs.hip.h"
+#include "q_sparse_bfgs.hip.h"
 #include "q_eigen.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
@@ -202,18 +206,84 @@ int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first, int *full, long long cap
   });
 }
 
-// the plan of one bsize: the host's partition, then (with_device) its tables, partial sums and the BFGS update's report on
-// the device
-static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) {
+// The connected components of the graph of Q's analysed pattern (the blocks Hqp_HL_SparseBFGS finds behind its
+// permutation), from the entries with col > row alone: numbered by their smallest variable, `member` their variables block
+// after block and ascending inside one, `first` the blocks' first POSITIONS in it with n behind them; and per block whether
+// every (i, j), i <= j, of it is stored.  Union by the smaller root, so a root is its component's smallest variable.
+static void qsb_partition(const hqpkkt_t *h, std::vector<int> &first, std::vector<int> &member, std::vector<unsigned char> &full) {
+  const int n = h->an.n;
+  const int *Qp = h->pQp.data(), *Qi = h->pQi.data();
+  first.clear(), member.clear(), full.clear();
+  if (n <= 0) return;
+  std::vector<int> root((size_t)n), blk((size_t)n);
+  std::iota(root.begin(), root.end(), 0);
+  const auto find = [&](int i) {
+    while (root[i] != i) i = root[i] = root[root[i]];
+    return i;
+  };
+  for (int i = 0; i < n; i++)
+    for (int k = Qp[i]; k < Qp[i + 1]; k++)
+      if (Qi[k] > i) {
+        const int a = find(i), b = find(Qi[k]);
+        root[std::max(a, b)] = std::min(a, b);
+      }
+  int nb = 0;
+  for (int i = 0; i < n; i++) {  // (a root comes before its members: it has its number when they ask)
+    const int r = find(i);
+    if (r == i) first.push_back(0), nb++;
+    blk[i] = r == i ? nb - 1 : blk[r];
+    first[blk[i]]++;
+  }
+  first.push_back(0);
+  for (int b = 0, at = 0; b <= nb; b++) {  // lengths -> first positions
+    const int len = first[b];
+    first[b] = at, at += len;
+  }
+  member.resize((size_t)n);
+  std::vector<int> fill(first.begin(), first.end() - 1);
+  std::vector<long long> stored((size_t)nb, 0);
+  for (int i = 0; i < n; i++) {
+    member[fill[blk[i]]++] = i;
+    for (int k = Qp[i]; k < Qp[i + 1]; k++) stored[blk[i]] += Qi[k] >= i;  // (the rows are strictly ascending: a count decides)
+  }
+  for (int b = 0; b < nb; b++) {
+    const long long len = first[b + 1] - first[b];
+    full.push_back(stored[b] == len * (len + 1) / 2);
+  }
+}
+
+int hqpkkt_q_components(hqpkkt_t *h, int *first, int *member, int *full, long long cap, long long *n_blocks) {
+  return guarded([&]() -> int {
+    if (!h || !n_blocks || (first && !member)) return HQPKKT_E_NULL;
+    if (!h->analyzed) return HQPKKT_E_INTERN;
+    std::vector<int> f, m;
+    std::vector<unsigned char> fl;
+    qsb_partition(h, f, m, fl);
+    *n_blocks = (long long)fl.size();
+    if (!first) return 0;
+    if (cap < *n_blocks) return HQPKKT_E_RANGE;
+    std::copy(f.begin(), f.end(), first), std::copy(m.begin(), m.end(), member);
+    if (full) std::copy(fl.begin(), fl.end(), full);
+    return 0;
+  });
+}
+
+// the plan of one key - a bsize's (qb_key) or QB_COMPONENTS -: the host's partition, then (with_device) its tables, partial
+// sums and the BFGS update's report on the device; the components' plan has its member list, the positions and the packed
+// vectors besides
+static int qb_plan_of(hqpkkt_t *h, int key, bool with_device, int *index) {
   TreeDev::QVal &q = h->td.qv;
-  const int key = qb_key(h, bsize), n = h->an.n;
+  const int n = h->an.n;
   int at = -1;
   for (size_t k = 0; k < q.bfgs_plans.size(); k++)
     if (q.bfgs_plans[k].bsize == key) at = (int)k;
   if (at < 0) {
     QPlan p;
     p.bsize = key;
-    qb_partition(h, key, p.first, p.full);
+    if (key == TreeDev::QVal::QB_COMPONENTS)
+      qsb_partition(h, p.first, p.member, p.full);
+    else
+      qb_partition(h, key, p.first, p.full);
     p.nblocks = (int)p.full.size();
     p.all_full = true;
     for (int b = 0; b < p.nblocks; b++) {
@@ -230,7 +300,7 @@ static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) {
   std::vector<int> blk_of((size_t)n), bunit((size_t)p.nblocks + 1), ublk((size_t)p.nunits);
   for (int b = 0, u = 0; b < p.nblocks; b++) {
     const int len = p.first[b + 1] - p.first[b];
-    std::fill(blk_of.begin() + p.first[b], blk_of.begin() + p.first[b + 1], b);
+    for (int j = p.first[b]; j < p.first[b + 1]; j++) blk_of[p.member.empty() ? j : p.member[j]] = b;
     bunit[b] = u;
     for (int j = 0; j < (len + qv::QV_CHUNK - 1) / qv::QV_CHUNK; j++) ublk[u++] = b;
     bunit[b + 1] = u;
@@ -239,8 +309,14 @@ static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) {
   if ((e = p.boff.upload(p.first)) || (e = p.bunit.upload(bunit)) || (e = p.ublk.upload(ublk)) || (e = p.part.alloc(3 * (size_t)p.nunits)) ||
       (e = p.rep.alloc((size_t)qv::QV_REPORT * p.nblocks)))
     return e;
+  if (!p.member.empty()) {
+    std::vector<int> pos_of((size_t)n);
+    for (int j = 0; j < n; j++) pos_of[p.member[j]] = j;
+    if ((e = p.d_member.upload(p.member)) || (e = p.pos_of.upload(pos_of)) || (e = p.pk.alloc(2 * (size_t)n))) return e;
+  }
   return p.blk_of.upload(blk_of);  // (last: it says the plan is complete)
 }
+static int qb_plan(hqpkkt_t *h, int bsize, bool with_device, int *index) { return qb_plan_of(h, qb_key(h, bsize), with_device, index); }
 
 // a plan's launch shape: lanes per row as hqpkkt_q_product; a wavefront per unit where no block is longer than 64
 // (q_values.hip.h), four of them a workgroup; the grids of the unit passes and of the row passes; the kernels' tables
@@ -256,14 +332,18 @@ struct QShape {
 // The passes of a damped update over plan p, four launches: the units' sums, the decision per block into `rep`, v and the
 // units' s'v, the outcome per block.  DIAG (Hqp_HL_DScale): src are the handle's values, didx the diagonals' indices, v
 // optional; otherwise src is Q s and v the handle's own vector.  The plan's `part` is scratch: the stream orders its users.
+// `member` (the components' plan, its vectors in block order): the decision with Hqp_HL_SparseBFGS's clamp.
 template <bool DIAG>
 static void qb_passes(hqpkkt_t *h, const QPlan &p, const QShape &L, const double *s, const double *y, const double *src, const int *didx,
-                      double gamma, double *rep, double *v) {
+                      double gamma, double *rep, double *v, const int *member = nullptr) {
   const int B = p.max_len;  // (DIAG: the block length of the uniform partition)
   double *part = p.part.p, *part2 = p.part.p + 2 * (size_t)p.nunits;
   hipStream_t st = h->stream;
   pick(L.wave_units, qv::k_qb_sums<4, DIAG>, qv::k_qb_sums<1, DIAG>)<<<L.ugrid, 256, 0, st>>>(L.g, s, y, src, didx, B, part);
-  qv::k_qb_decide<<<nblk(p.nblocks), 256, 0, st>>>(L.g, part, gamma, rep);
+  if (member)
+    qv::k_qsb_decide<<<nblk(p.nblocks), 256, 0, st>>>(L.g, member, part, gamma, rep);
+  else
+    qv::k_qb_decide<<<nblk(p.nblocks), 256, 0, st>>>(L.g, part, gamma, rep);
   pick(L.wave_units, qv::k_qb_damped<4, DIAG>, qv::k_qb_damped<1, DIAG>)<<<L.ugrid, 256, 0, st>>>(L.g, s, y, src, didx, B, rep, part2, v);
   qv::k_qb_outcome<<<nblk(p.nblocks), 256, 0, st>>>(L.g, part2, rep);
 }
@@ -330,6 +410,18 @@ int hqpkkt_q_dscale_report(hqpkkt_t *h, double *out, long long cap_blocks, long 
 
 // ---- Hqp_HL_BFGS and the pattern-kept update on the sparse Q
 
+// what every plan's BFGS update shares, made by the first: the entries' rows and columns, Q s and v
+static int qb_shared(hqpkkt_t *h) {
+  TreeDev::QVal &q = h->td.qv;
+  if (q.erow.p) return 0;
+  const int n = h->an.n;
+  std::vector<int> erow((size_t)h->an.nq);
+  for (int i = 0; i < n; i++) std::fill(erow.begin() + h->pQp[i], erow.begin() + h->pQp[i + 1], i);
+  int e;
+  if ((e = q.ecol.upload(h->pQi)) || (e = q.bfgs_qs.alloc((size_t)n)) || (e = q.bfgs_v.alloc((size_t)n)) || (e = q.erow.upload(erow))) return e;
+  return 0;
+}
+
 int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
   return guarded([&]() -> int {
     if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
@@ -346,12 +438,7 @@ int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
       q.bfgs_last = at;
       return 0;
     }
-    if (!q.erow.p) {  // what every plan shares: the entries' rows and columns, Q s and v
-      std::vector<int> erow((size_t)nq);
-      for (int i = 0; i < n; i++) std::fill(erow.begin() + h->pQp[i], erow.begin() + h->pQp[i + 1], i);
-      if ((e = q.ecol.upload(h->pQi)) || (e = q.bfgs_qs.alloc((size_t)n)) || (e = q.bfgs_v.alloc((size_t)n)) || (e = q.erow.upload(erow))) return e;
-    }
-    if ((e = qb_plan(h, u->bsize, true, &at))) return e;
+    if ((e = qb_shared(h)) || (e = qb_plan(h, u->bsize, true, &at))) return e;
     const QPlan &p = q.bfgs_plans[at];
     CallerVecs io{h};
     const double *ds, *dy;
@@ -374,6 +461,48 @@ int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
 
 int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
   return qv_report(h, &TreeDev::QVal::bfgs_last, &QPlan::rep, qv::QV_REPORT, out, cap_blocks, n_blocks);
+}
+
+// ---- Hqp_HL_SparseBFGS: the update on the connected components, their variables anywhere (q_sparse_bfgs.hip.h)
+
+int hqpkkt_q_sparse_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u) {
+  return guarded([&]() -> int {
+    if (!h || !u || !u->s || !u->y) return HQPKKT_E_NULL;
+    if (!std::isfinite(u->gamma) || u->gamma < 0.0 || u->bsize != 0) return HQPKKT_E_RANGE;  // (the reference's SparseBFGS ignores alpha)
+    if (u->fill != HQPKKT_QBFGS_FULL && u->fill != HQPKKT_QBFGS_PATTERN) return HQPKKT_E_RANGE;
+    int e = qv_refused(h, true), at = -1;
+    if (e || (e = qb_plan_of(h, TreeDev::QVal::QB_COMPONENTS, false, &at))) return e;
+    if (u->fill == HQPKKT_QBFGS_FULL && !h->td.qv.bfgs_plans[at].all_full) return HQPKKT_E_FORMAT;
+    if ((e = qv_prepare(h, true, false))) return e;
+    TreeDev::QVal &q = h->td.qv;
+    const int n = h->an.n, nq = h->an.nq;
+    if (n <= 0) {
+      q.sbfgs_last = at;
+      return 0;
+    }
+    if ((e = qb_shared(h)) || (e = qb_plan_of(h, TreeDev::QVal::QB_COMPONENTS, true, &at))) return e;
+    const QPlan &p = q.bfgs_plans[at];
+    CallerVecs io{h};
+    const double *ds, *dy;
+    double *dv, *dQs;
+    if ((e = io.in(u->s, (size_t)n, &ds)) || (e = io.in(u->y, (size_t)n, &dy))) return e;
+    io.out(u->v, (size_t)n, &dv), io.out(u->Qs, (size_t)n, &dQs);
+    double *sp = p.pk.p, *yp = sp + n, *Qsp = q.bfgs_qs.p, *vp = q.bfgs_v.p;  // all four in block order
+    hipStream_t s = h->stream;
+    const QShape L(h, p);
+    qv::k_qsb_pack<<<nblk(n), 256, 0, s>>>(n, p.d_member.p, ds, dy, sp, yp);
+    pick(L.short_rows, qv::k_qsb_rows<16>, qv::k_qsb_rows<4>)<<<L.rgrid, 256, 0, s>>>(n, h->td.Qf.dev(), p.pos_of.p, ds, Qsp);
+    qb_passes<false>(h, p, L, sp, yp, Qsp, nullptr, u->gamma, p.rep.p, vp, p.d_member.p);
+    if (nq) qv::k_qsb_apply<<<nblk(nq), 256, 0, s>>>(nq, q.erow.p, q.ecol.p, q.kind.p, p.blk_of.p, p.pos_of.p, Qsp, vp, p.rep.p, h->td.vals.p);
+    if (dv || dQs) qv::k_qsb_unpack<<<nblk(n), 256, 0, s>>>(n, p.d_member.p, vp, Qsp, dv, dQs);
+    q.sbfgs_last = at;
+    if ((e = qv_written(h))) return e;
+    return io.finish();
+  });
+}
+
+int hqpkkt_q_sparse_bfgs_report(hqpkkt_t *h, double *out, long long cap_blocks, long long *n_blocks) {
+  return qv_report(h, &TreeDev::QVal::sbfgs_last, &QPlan::rep, qv::QV_REPORT, out, cap_blocks, n_blocks);
 }
 
 // ---- the eigenvalue control of Hqp_HL_BFGS on the blocks of the sparse Q (q_eigen.hip.h)

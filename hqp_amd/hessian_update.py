@@ -28,6 +28,8 @@ The approximations that work on the sparse Q of the program itself (``Hqp_IpMatr
 with the reference's operations and sequential sums - and ``dscale_replay``, the device's decision and update from the sums
 it REPORTED.
 
+Hqp_HL_SparseBFGS on the connected components of Q (``Hqp_IpMatrix.q_components``, ``q_sparse_bfgs_update``) has
+``q_components_model``, ``q_sparse_bfgs_terms`` and ``q_sparse_bfgs_replay``, built on the models of Hqp_HL_BFGS below.
 The reference's default, Hqp_HL_BFGS, on the sparse Q itself (``Hqp_IpMatrix.q_blocks``, ``q_bfgs_update``; hqpkkt_q_blocks,
 hqpkkt_q_bfgs_update) closes the file: ``q_blocks_model`` is Hqp_HL_BFGS::next_block, ``q_bfgs_terms`` the update of every block
 with the reference's operations and sequential sums - on the stored entries alone under ``pattern`` -, and ``q_bfgs_replay``
@@ -304,7 +306,7 @@ def _seq_sums(keys, terms, size, start=0.0):
     return out
 
 
-def _damped(rep, of, y, Qs):
+def _damped(rep, of, y, Qs, clamp=False):
     """What the damped updates share - Hqp_HL_DScale::update_b_Q with Qs = fl(s q), Hqp_HL_BFGS::update_b_Q with Qs = Q s -
     from the sums in ``rep`` (columns 0 sy, 1 sQs, 2 gamma, 4 sv where damped), one numpy operation per rounded operation,
     all blocks at once: the decision, theta, v, sv as used, the blocks that are updated and the outcome codes.  ``of``: the
@@ -313,6 +315,9 @@ def _damped(rep, of, y, Qs):
     sy, sqs, gamma = (np.array(rep[:, j], dtype=np.float64) for j in (0, 1, 2))
     damp = sy < gamma * sqs
     theta = np.where(damp, ((one - gamma) * sqs) / (sqs - sy), one)
+    if clamp:  # Hqp_HL_SparseBFGS: theta = 1 unless theta <= 1, then 0 unless theta >= 0 (a NaN becomes 1)
+        theta = np.where(theta <= one, theta, one)
+        theta = np.where(theta >= 0.0, theta, np.float64(0.0))
     omt = one - theta
     v = np.where(damp[of], theta[of] * y + omt[of] * Qs, y)
     sv = np.where(damp, rep[:, 4], sy)
@@ -413,9 +418,9 @@ def q_blocks_model(Qp, Qi, n, bsize):
     return first, full
 
 
-def _q_bfgs_entries(Q_csr, first):
+def _q_bfgs_entries(Q_csr, first, member=None):
     """rows and columns of Q's entries, the block of every variable, and the mask of the entries an update may touch:
-    col >= row, both in one block"""
+    col >= row, both in one block.  ``member`` (``q_components_model``): ``first`` counts positions in it."""
     p, ix, x = (np.asarray(a) for a in Q_csr)
     n = p.size - 1
     first = np.asarray(first, dtype=np.int64)
@@ -423,19 +428,21 @@ def _q_bfgs_entries(Q_csr, first):
         raise ValueError("first: the blocks' first indices, ascending from 0, and n behind the last")
     rows = np.repeat(np.arange(n), np.diff(p))
     of = np.repeat(np.arange(max(first.size - 1, 0)), np.diff(first)) if n else np.zeros(0, dtype=np.int64)
+    if member is not None and n:
+        of = of[np.argsort(np.asarray(member, dtype=np.int64))]  # position -> block becomes variable -> block
     ix = ix.astype(np.int64)
     inb = (ix >= rows) & (of[rows] == of[ix]) if n else np.zeros(0, dtype=bool)
     return rows, ix, np.array(x, dtype=np.float64), of, inb
 
 
-def _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs):
+def _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs, clamp=False):
     """decision, theta, v and both steps of every stored entry from the sums in ``rep``: ``_damped`` with Q s, then the two
     steps of the entries an update may touch, one numpy operation per rounded operation, all blocks at once"""
     nb = rep.shape[0]
     if nb == 0:
         return y.copy(), x.copy(), np.zeros(0, dtype=np.int64), np.ones(0), np.zeros(0)
     with np.errstate(all="ignore"):
-        v, sqs, sv, ok, outcome, theta = _damped(rep, of, y, Qs)
+        v, sqs, sv, ok, outcome, theta = _damped(rep, of, y, Qs, clamp)
         xn = x.copy()
         k = np.flatnonzero(inb)
         k = k[ok[of[rows[k]]]]
@@ -500,6 +507,81 @@ def q_bfgs_replay(report, Q_csr, y, Qs, first):
         raise ValueError("q_bfgs_replay: report of (blocks, 8), y and Qs vectors of n entries")
     v, xn, outcome, _theta, _sv = _q_bfgs_apply(report, rows, ix, x, of, inb, y, Qs)
     return v, xn, outcome
+
+
+# ---- Hqp_HL_SparseBFGS on the sparse Q of the program (Hqp_IpMatrix.q_components, q_sparse_bfgs_update) ----
+
+def q_components_model(Qp, Qi, n):
+    """The connected components of the graph of the pattern (Qp, Qi), entries with col > row alone, by plain union-find:
+    returns (first, member, full) as ``Hqp_IpMatrix.q_components`` - components numbered by their smallest variable,
+    ``member[first[b]:first[b + 1]]`` the variables of block b ascending, ``full[b]`` 1 where every (i, j), i <= j, of it
+    is stored."""
+    Qp, Qi, n = np.asarray(Qp, dtype=np.int64), np.asarray(Qi, dtype=np.int64), int(n)
+    if n == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    root = list(range(n))
+
+    def find(i):
+        while root[i] != i:
+            root[i] = root[root[i]]
+            i = root[i]
+        return i
+
+    rows = np.repeat(np.arange(n), np.diff(Qp[: n + 1]))
+    for i, j in zip(rows[Qi > rows].tolist(), Qi[Qi > rows].tolist()):
+        a, b = find(i), find(j)
+        root[max(a, b)] = min(a, b)
+    r = np.array([find(i) for i in range(n)])
+    _, of = np.unique(r, return_inverse=True)  # (a root is its component's smallest variable: sorted roots number them)
+    member = np.argsort(of, kind="stable")
+    ln = np.bincount(of)
+    first = np.concatenate([[0], np.cumsum(ln)])
+    stored = np.bincount(of[rows[Qi >= rows]], minlength=ln.size)
+    return first, member, (stored == ln * (ln + 1) // 2).astype(np.int64)
+
+
+def q_sparse_bfgs_terms(Q_csr, s, y, first, member, gamma=0.2, pattern=False):
+    """Hqp_HL_SparseBFGS::update (hqp/Hqp_HL_SparseBFGS.C) on the CSR triple ``Q_csr`` for the components (``first``,
+    ``member``) of ``q_components_model``: as ``q_bfgs_terms`` with the sums of a block over its members in their order and
+    theta clamped to [0, 1]; ``gamma`` is used as given.  Returns (report, v, Qs, Qx_new), word 5 of ``report`` the block's
+    smallest variable, the vectors in the caller's order."""
+    s, y = (np.ascontiguousarray(a, dtype=np.float64) for a in (s, y))
+    first, member = np.asarray(first, dtype=np.int64), np.asarray(member, dtype=np.int64)
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first, member)
+    n, nb = s.size, max(first.size - 1, 0)
+    if not pattern and nb and (np.bincount(of[rows[inb]], minlength=nb) != np.diff(first) * (np.diff(first) + 1) // 2).any():
+        raise ValueError("q_sparse_bfgs_terms: a component is not fully stored (pattern=False)")
+    g = np.float64(gamma)
+    rep = np.zeros((nb, 8))
+    with np.errstate(all="ignore"):
+        st = inb & (ix > rows)  # the symmetric image, row by row in ascending column order: the member order inside a block
+        r2, c2, v2 = np.concatenate([rows[inb], ix[st]]), np.concatenate([ix[inb], rows[st]]), np.concatenate([x[inb], x[st]])
+        o = np.lexsort((c2, r2))
+        Qs = _seq_sums(r2[o], v2[o] * s[c2[o]], n)
+        ofm = of[member]
+        sy, sqs = _seq_sums(ofm, (s * y)[member], nb), _seq_sums(ofm, (s * Qs)[member], nb)
+        if nb:
+            rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 5], rep[:, 6] = sy, sqs, g, member[first[:-1]], np.diff(first)
+            _v, _sqs, _sv, _ok, _out, theta = _damped(rep, of, y, Qs, clamp=True)
+            vd = theta[of] * y + (np.float64(1.0) - theta)[of] * Qs
+            rep[:, 4] = np.where(sy < g * sqs, _seq_sums(ofm, (s * vd)[member], nb), sy)
+    v, xn, outcome, theta, sv = _q_bfgs_apply(rep, rows, ix, x, of, inb, y, Qs, clamp=True)
+    if nb:
+        rep[:, 3], rep[:, 4], rep[:, 7] = theta, sv, outcome
+    return rep, v, Qs, xn
+
+
+def q_sparse_bfgs_replay(report, Q_csr, y, Qs, first, member):
+    """(v, Qx_new, outcome, theta) of ``Hqp_IpMatrix.q_sparse_bfgs_update`` repeated in numpy from the sums the device REPORTED and
+    the ``Qs`` it returned: ``q_bfgs_replay`` on the components (``first``, ``member``) with the clamp - theta = 1 unless
+    theta <= 1, then theta = 0 unless theta >= 0; a block that is damped with theta = 1 keeps outcome 1."""
+    report = np.asarray(report, dtype=np.float64)
+    y, Qs = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, Qs))
+    rows, ix, x, of, inb = _q_bfgs_entries(Q_csr, first, member)
+    if report.shape != (max(np.asarray(first).size - 1, 0), 8) or not (y.shape == Qs.shape == (np.asarray(Q_csr[0]).size - 1,)):
+        raise ValueError("q_sparse_bfgs_replay: report of (blocks, 8), y and Qs vectors of n entries")
+    v, xn, outcome, theta, _sv = _q_bfgs_apply(report, rows, ix, x, of, inb, y, Qs, clamp=True)
+    return v, xn, outcome, theta
 
 
 # ---- the eigenvalue control of Hqp_HL_BFGS on the blocks of the sparse Q (Hqp_IpMatrix.q_eigen_control) ----

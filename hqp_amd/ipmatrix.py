@@ -501,18 +501,64 @@ class Hqp_IpMatrix:
         _check(e, "q_eigen_report")
         return (out, T) if with_T else out
 
+    def _q_bfgs_report(self, entry):
+        k = C.c_longlong()
+        out = np.zeros((1, _lib.HQPKKT_QBFGS_REPORT))
+        fn = getattr(self._L, "hqpkkt_" + entry)
+        e = fn(self._h, C.c_void_p(out.ctypes.data), 1, C.byref(k))
+        if e == _lib.E_RANGE:
+            out = np.zeros((k.value, _lib.HQPKKT_QBFGS_REPORT))
+            e = fn(self._h, C.c_void_p(out.ctypes.data), k.value, C.byref(k))
+        _check(e, entry)
+        return out[: k.value]
+
     def q_bfgs_report(self):
         """Per block of the last q_bfgs_update() (hqpkkt_q_bfgs_report), an array of shape (blocks, 8): sy, sQs, gamma_eff,
         theta (1 where not damped), sv as used, first index, length and the outcome - 0 updated, 1 updated with damping,
         2 left alone (sv or sQs is zero), 3 left alone (sv or sQs is not finite).  Waits for the handle's stream."""
+        return self._q_bfgs_report("q_bfgs_report")
+
+    def q_components(self):
+        """(first, member, full) of hqpkkt_q_components: the connected components of the graph of Q's analysed pattern - the
+        blocks of Hqp_HL_SparseBFGS -, numbered by their smallest variable.  ``member[first[b]:first[b + 1]]``: the variables
+        of block b, ascending (``first``: blocks + 1 ints, empty for n = 0); ``full``: per block 1 where every pair of its
+        variables is stored.  Needs analyze() alone."""
         k = C.c_longlong()
-        out = np.zeros((1, _lib.HQPKKT_QBFGS_REPORT))
-        e = self._L.hqpkkt_q_bfgs_report(self._h, C.c_void_p(out.ctypes.data), 1, C.byref(k))
-        if e == _lib.E_RANGE:
-            out = np.zeros((k.value, _lib.HQPKKT_QBFGS_REPORT))
-            e = self._L.hqpkkt_q_bfgs_report(self._h, C.c_void_p(out.ctypes.data), k.value, C.byref(k))
-        _check(e, "q_bfgs_report")
-        return out[: k.value]
+        _check(self._L.hqpkkt_q_components(self._h, None, None, None, 0, C.byref(k)), "q_components")
+        first, member, full = np.zeros(k.value + 1, dtype=np.int32), np.zeros(self.n, dtype=np.int32), np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            _check(self._L.hqpkkt_q_components(self._h, C.c_void_p(first.ctypes.data), C.c_void_p(member.ctypes.data),
+                                               C.c_void_p(full.ctypes.data), k.value, C.byref(k)), "q_components")
+        return first[: k.value + 1 if k.value else 0], member, full
+
+    def q_sparse_bfgs_update(self, s, y, gamma=0.2, pattern=False, want_v=False, want_Qs=False):
+        """Hqp_HL_SparseBFGS::update on the sparse Q where it lies (hqpkkt_q_sparse_bfgs_update): the damped BFGS update of
+        every block of q_components() - its variables may lie anywhere - with theta clamped to [0, 1].  ``pattern``: the
+        update on the stored entries alone; otherwise every component must be fully stored (HQPKKT_E_FORMAT).  Returns
+        (v, Qs) as q_bfgs_update does.  q_sparse_bfgs_report() tells what every block did."""
+        ps, ks = self._vec_in(s, self.n, "s")
+        py, ky = self._vec_in(y, self.n, "y")
+        u = _lib.QBfgsUpdate()
+        u.s, u.y, u.gamma, u.alpha, u.bsize = ps.value, py.value, float(gamma), 1.0, 0
+        u.fill = _lib.HQPKKT_QBFGS_PATTERN if pattern else _lib.HQPKKT_QBFGS_FULL
+        v = Qs = None
+        if want_v:
+            pv, v = self._vec_out(self.n)
+            u.v = pv.value
+        if want_Qs:
+            pq, Qs = self._vec_out(self.n)
+            u.Qs = pq.value
+        self._stream_sync()
+        _check(self._L.hqpkkt_q_sparse_bfgs_update(self._h, C.byref(u)), "q_sparse_bfgs_update")
+        self._keep_qv = [ks, ky, v, Qs]
+        if want_v or want_Qs:
+            self._stream_sync(after=True)
+        return v, Qs
+
+    def q_sparse_bfgs_report(self):
+        """Per block of the last q_sparse_bfgs_update() (hqpkkt_q_sparse_bfgs_report): the words of q_bfgs_report(), word 5
+        the block's smallest variable.  Waits for the handle's stream."""
+        return self._q_bfgs_report("q_sparse_bfgs_report")
 
     def lagrangian_gradient(self, c, y, z, minus=None):
         """Hqp_SqpSolver::grd_L (hqpkkt_lagrangian_gradient): c - A'y - C'z, and minus ``minus`` where given - the

@@ -681,7 +681,7 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       them out -, sy = s'y, sQs = s'(Qs).  gamma_eff = gamma for gamma >= 0, else fl(g + fl(fl(1 - g) fl(1 -
  *                       alpha))), g = -gamma, formed on the host (as hqpkkt_bfgs_update_stage_hessians).  Damped where
  *                       sy < fl(gamma_eff sQs): theta = fl(fl((1 - gamma_eff) sQs) / fl(sQs - sy)) - not clamped, unlike
- *                       Hqp_HL_SparseBFGS -, v_i = fl(fl(theta y_i) + fl(fl(1 - theta) Qs_i)), sv = s'v; otherwise v = y,
+ *                       Hqp_HL_SparseBFGS (hqpkkt_q_sparse_bfgs_update) -, v_i = fl(fl(theta y_i) + fl(fl(1 - theta) Qs_i)), sv = s'v; otherwise v = y,
  *                       sv = sy.  Every stored entry (i, j), j >= i, with both indices in B: q <- fl(q - fl(fl(Qs_i Qs_j) /
  *                       sQs)), then q <- fl(q + fl(fl(v_i v_j) / sv)) - divisions, as in the reference.  Entries with col < row
  *                       and entries whose indices lie in different blocks are never read or written.  A block with sv or
@@ -707,6 +707,51 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       3 theta (1.0 undamped), 4 sv as used, 5 first index, 6 length, 7 outcome - 0 updated, 1 updated
  *                       with damping, 2 left alone (zero), 3 left alone (not finite).  hessian_update.q_bfgs_replay repeats
  *                       the decision and the update in numpy from the reported sums and the returned Qs.
+ *   hqpkkt_q_components the blocks of Hqp_HL_SparseBFGS (hqp/Hqp_HL_SparseBFGS.C): the connected components of the graph of the
+ *                       analysed pattern of Q, read from its entries with col > row alone; a row without one is a component of
+ *                       one.  The reference reaches them by a reverse Cuthill-McKee permutation and next_block behind it - a
+ *                       cut inside a component always has an entry across it, and RCM numbers one component after another -;
+ *                       sp_symrcm is not restated here.  The order is this library's own and the pattern alone fixes it:
+ *                       components are numbered by their smallest variable, and member[first[b] .. first[b + 1]) lists the
+ *                       variables of block b in ascending order (first: n_blocks + 1 ints, positions in member, n behind the
+ *                       last; member: n ints).  full (optional, n_blocks ints): 1 where every (i, j), i <= j, of the component
+ *                       is stored.  Host only, after hqpkkt_analyze alone, in all three modes (HQPKKT_E_INTERN before it);
+ *                       first == NULL: *n_blocks alone is set; first without member: HQPKKT_E_NULL; cap (in blocks) too small:
+ *                       HQPKKT_E_RANGE with *n_blocks set; n == 0: no blocks.
+ *   hqpkkt_q_sparse_bfgs_update  Hqp_HL_SparseBFGS::update on the blocks of hqpkkt_q_components, in place in Qx: the block BFGS
+ *                       of a partially separable program, whose blocks' variables are interleaved (the rows of a CUTE-style
+ *                       program; a DOCP whose host orders the states before the controls).  The argument struct of
+ *                       hqpkkt_q_bfgs_update; bsize must be 0, and gamma is used as given - the reference's SparseBFGS does
+ *                       not read alpha, so gamma < 0 is HQPKKT_E_RANGE here.  Per block B, its members in their order:
+ *                       Qs_i = sum_j q_ij s_j over row i of the symmetric image - the walk and the bits of hqpkkt_q_product:
+ *                       every stored entry with col >= row joins its two ends in one component, so a row of the image is its
+ *                       row of the block and nothing is skipped -, sy = s'y, sQs = s'(Qs) over the members.  Damped where
+ *                       sy < fl(gamma sQs): theta = fl(fl((1 - gamma) sQs) / fl(sQs - sy)), then theta = 1 unless theta <= 1,
+ *                       then theta = 0 unless theta >= 0 (the reference's clamp, in its order: a NaN becomes 1);
+ *                       v_i = fl(fl(theta y_i) + fl(fl(1 - theta) Qs_i)), sv = s'v; otherwise v = y, sv = sy.  A block that is
+ *                       damped with theta = 1 is still reported damped.  Every stored (i, j), j >= i: q <- fl(q - fl(fl(Qs_i
+ *                       Qs_j) / sQs)), then q <- fl(q + fl(fl(v_i v_j) / sv)).  Entries with col < row are never read or
+ *                       written.  A block with sv or sQs zero is left alone, and so is one with either not finite; a NaN in
+ *                       one block reaches no other.  The sums are those of hqpkkt_q_dscale_update over the block's POSITIONS
+ *                       in member (chunks of 4096 from its first position): a block's bits depend on its length, its values
+ *                       and the order of its members alone - not on where its variables lie, on the other blocks or on the
+ *                       mode (the lanes per row of Q s are chosen from Q's mean row length, as for hqpkkt_q_product) -, and
+ *                       are the same from call to call; where the components are contiguous and theta needs no clamp they are
+ *                       the bits of hqpkkt_q_bfgs_update with detected blocks.  The sums of the reference run in another
+ *                       order; results agree with it to rounding.  On the device: s and y are gathered into block order once,
+ *                       Q s is written there, the unit passes of hqpkkt_q_bfgs_update run on those vectors unchanged, the
+ *                       update of an entry reads Q s and v at the positions of its row and column, and v / Qs (optional) are
+ *                       scattered back into the caller's order.  Plain loads and stores in the handle's stream, no atomics.
+ *                       fill: as for hqpkkt_q_bfgs_update - under HQPKKT_QBFGS_FULL a component that is not fully stored makes
+ *                       the call return HQPKKT_E_FORMAT before any launch; HQPKKT_QBFGS_PATTERN accepts any pattern.  Checks in
+ *                       that entry's order: HQPKKT_E_NULL; HQPKKT_E_RANGE (gamma not finite or < 0, bsize != 0, fill);
+ *                       HQPKKT_E_INTERN (not analysed, no values, dense stage Hessians, a sharded handle); HQPKKT_E_FORMAT;
+ *                       HQPKKT_E_DEVICE.  The plan's device tables (the members, their positions, the block of a variable,
+ *                       the units) and the two packed vectors are made by the first call; later calls allocate nothing.
+ *                       The plan is its own: hqpkkt_q_bfgs_report and floor_from_bfgs of hqpkkt_q_eigen_control never see it.
+ *                       Not built: an eigenvalue control on the components - the reference's SparseBFGS has none.
+ *   hqpkkt_q_sparse_bfgs_report  as hqpkkt_q_bfgs_report, per component of the last hqpkkt_q_sparse_bfgs_update; word 5 is the
+ *                       block's smallest variable.  hessian_update.q_sparse_bfgs_replay repeats decision, clamp and update.
  *   hqpkkt_q_eigen_control  the eigenvalue control at the end of Hqp_HL_BFGS::update_b_Q (hqp/Hqp_HL_BFGS.C:203-212, which
  *                       sqp_hela_eigen_control turns on by default) on the blocks of hqpkkt_q_blocks(bsize), in place in Qx.
  *                       The block of the variable set B is the symmetric image of the stored upper entries with both
@@ -753,7 +798,8 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       made or grown by the call that needs them; later calls with the same bsize and a step cap no
  *                       higher allocate nothing; a failed allocation is HQPKKT_E_MEM with the handle unchanged.
  *                       Not built: sharded handles; dense stage Hessians (hqpkkt_eigen_control_stage_hessians);
- *                       Hqp_HL_SparseBFGS's RCM re-blocking; Hqp_HL_AugBFGS; the reference's _logging print.
+ *                       the components of hqpkkt_q_sparse_bfgs_update (Hqp_HL_SparseBFGS has no control); Hqp_HL_AugBFGS; the
+ *                       reference's _logging print.
  *   hqpkkt_q_eigen_report   as hqpkkt_q_bfgs_report (HQPKKT_E_INTERN before a control since the analysis; cap_blocks too small:
  *                       HQPKKT_E_RANGE with *n_blocks and *t_steps set); waits for the stream.  Per block of the last
  *                       hqpkkt_q_eigen_control HQPKKT_EIG_REPORT doubles with the meanings of hqpkkt_eigen_report: 0 g_b;
@@ -801,6 +847,10 @@ typedef struct hqpkkt_q_bfgs_update_args {
 int hqpkkt_q_blocks(hqpkkt_t *h, int bsize, int *first /* HOST */, int *full /* HOST */, long long cap, long long *n_blocks);
 int hqpkkt_q_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u);
 int hqpkkt_q_bfgs_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
+int hqpkkt_q_components(hqpkkt_t *h, int *first /* HOST, n_blocks + 1 */, int *member /* HOST, n */, int *full /* HOST or NULL, n_blocks */,
+                        long long cap, long long *n_blocks);
+int hqpkkt_q_sparse_bfgs_update(hqpkkt_t *h, const hqpkkt_q_bfgs_update_args *u); /* bsize must be 0, gamma >= 0; alpha is not read */
+int hqpkkt_q_sparse_bfgs_report(hqpkkt_t *h, double *out /* HOST */, long long cap_blocks, long long *n_blocks);
 typedef struct hqpkkt_q_eigen_control_args {
   double eps;          /* the reference's _eps: floor theta_b = fl(eps eps) ... */
   int bsize;           /* the partition: hqpkkt_q_blocks(bsize) */

@@ -305,6 +305,8 @@ struct TreeDev {
       // hqpkkt_q_eigen_control (q_eigen.hip.h), made or grown by the control that needs them: the basis (eig_cap vectors of
       // n), the units' partial sums, T (stride 2 eig_steps per block), the report, the state's two copies and the floors
       int eig_cap = 0, eig_steps = 0;       // steps the buffers hold; the step cap of the plan's last control
+      int eig_tcap = 0;                     // half the doubles per block eig_T holds (hqpkkt_q_eigen_control_short makes T,
+                                            // the report and the floors alone: eig_cap stays what the basis holds)
       DBuf<double> eig_V, eig_part, eig_T, eig_rep, eig_st, eig_floor;
     };
     std::vector<BfgsPlan> bfgs_plans;

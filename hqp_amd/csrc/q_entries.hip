@@ -1,7 +1,8 @@
-// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 19 of them:
+// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 20 of them:
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
 // (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
-// hqpkkt_q_eigen_control and its report (q_eigen.hip.h) and hqpkkt_lagrangian_gradient.  Their state is
+// hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h) and
+// hqpkkt_lagrangian_gradient.  Their state is
 // TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
@@ -14,6 +15,7 @@
 #include "q_bfgs.hip.h"
 #include "q_sparse_bfgs.hip.h"
 #include "q_eigen.hip.h"
+#include "q_eigen_short.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
 
@@ -522,7 +524,7 @@ static int qe_buffers(hqpkkt_t *h, QPlan &p, int steps) {
     return e;
   p.eig_V = std::move(V), p.eig_part = std::move(part), p.eig_T = std::move(T), p.eig_rep = std::move(rep), p.eig_st = std::move(st),
   p.eig_floor = std::move(flr);
-  p.eig_cap = steps;
+  p.eig_cap = p.eig_tcap = steps;
   return 0;
 }
 
@@ -578,6 +580,56 @@ int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
     qv::k_qe_ritz<<<(unsigned)p.nblocks, 64, 0, s>>>(st[steps & 1], T, steps, rep);
     qv::k_qe_shift<<<nblk(n), 256, 0, s>>>(n, p.blk_of.p, q.didx.p, rep, h->td.vals.p);
     q.eig_last = at, p.eig_steps = steps;
+    return qv_written(h);
+  });
+}
+
+// ---- the same control on a plan of short blocks: Householder's T of every block, one launch (q_eigen_short.hip.h)
+
+// what it needs beside the plan's tables - the report, T with stride 2 max_len per block, the floors -, made or grown as
+// qe_buffers does; the basis, the partials and the states stay as they are for hqpkkt_q_eigen_control to make or grow
+static int qes_buffers(hqpkkt_t *h, QPlan &p) {
+  if (p.eig_rep.p && p.eig_tcap >= p.max_len) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (a report or a control still in the stream reads the old ones)
+  DBuf<double> T, rep, flr;
+  int e;
+  if ((e = T.alloc(2 * (size_t)p.max_len * p.nblocks)) || (e = rep.alloc((size_t)qv::QE_REPORT * p.nblocks)) || (e = flr.alloc((size_t)p.nblocks))) return e;
+  p.eig_T = std::move(T), p.eig_rep = std::move(rep), p.eig_floor = std::move(flr);
+  p.eig_tcap = p.max_len;
+  return 0;
+}
+
+int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+  return guarded([&]() -> int {
+    if (!h || !ec) return HQPKKT_E_NULL;
+    if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps != 0) return HQPKKT_E_RANGE;
+    if (ec->floor_from_bfgs != 0 && ec->floor_from_bfgs != 1) return HQPKKT_E_RANGE;
+    int e = qv_refused(h, true), at = -1;
+    if (e || (e = qb_plan(h, ec->bsize, false, &at))) return e;
+    TreeDev::QVal &q = h->td.qv;
+    if (ec->floor_from_bfgs && q.bfgs_last != at) return HQPKKT_E_INTERN;
+    for (int b = 0; ec->floor && b < q.bfgs_plans[at].nblocks; b++)
+      if (!std::isfinite(ec->floor[b])) return HQPKKT_E_RANGE;
+    const int cap = q.bfgs_plans[at].max_len;
+    if (cap > 64) return HQPKKT_E_SIZES;
+    if ((e = qv_prepare(h, true, true))) return e;
+    if (h->an.n <= 0) {
+      q.eig_last = at, q.bfgs_plans[at].eig_steps = 0;
+      return 0;
+    }
+    if ((e = qb_plan(h, ec->bsize, true, &at))) return e;
+    QPlan &p = q.bfgs_plans[at];
+    if ((e = qes_buffers(h, p))) return e;
+    hipStream_t s = h->stream;
+    if (ec->floor) {  // (as hqpkkt_q_eigen_control: the caller's again on return)
+      HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    // the instance by the LDS of its image: the smallest that holds the plan's longest block
+    const auto block = pick(cap > 16, pick(cap > 8, qv::k_qes_block<8>, qv::k_qes_block<16>), pick(cap > 32, qv::k_qes_block<32>, qv::k_qes_block<64>));
+    block<<<(unsigned)p.nblocks, 64, 0, s>>>(p.boff.p, h->td.Qf.dev(), q.didx.p, h->td.vals.p, ec->floor ? p.eig_floor.p : nullptr,
+                                             ec->eps * ec->eps, ec->floor_from_bfgs ? p.rep.p : nullptr, cap, p.eig_T.p, p.eig_rep.p);
+    q.eig_last = at, p.eig_steps = cap;
     return qv_written(h);
   });
 }

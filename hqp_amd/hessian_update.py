@@ -660,6 +660,50 @@ def q_lanczos_model(Q_csr, first, theta, max_steps=0):
     return g, steps, T
 
 
+def q_block_gerschgorin_model(block):
+    """g of one dense block as ``Hqp_IpMatrix.q_eigen_control_short`` forms it: offsum_i = the sum of |a_ij|, j != i, in
+    ascending j from +0.0, every add rounded on its own, and g = min_i (a_ii - offsum_i), a NaN kept."""
+    B = np.asarray(block, dtype=np.float64)
+    g = np.float64(np.inf)
+    with np.errstate(all="ignore"):
+        for i in range(B.shape[0]):
+            off = np.float64(0.0)
+            for j in range(B.shape[0]):
+                if j != i:
+                    off = off + abs(B[i, j])
+            g = _nan_min(g, B[i, i] - off)
+    return float(g)
+
+
+def q_tridiag_model(block):
+    """Householder's reduction of a dense symmetric block to a tridiagonal T in float64, the method of
+    ``Hqp_IpMatrix.q_eigen_control_short`` (tred2's steps; numpy's sums run in another order than the device's): returns
+    (alpha, beta) of L entries each, beta[L - 1] = 0.  A sub-column that is zero below its first entry gets no
+    reflector."""
+    A = np.array(block, dtype=np.float64)
+    L = A.shape[0]
+    alpha, beta = np.zeros(L), np.zeros(L)
+    with np.errstate(all="ignore"):
+        for k in range(L - 2):
+            x = A[k + 1:, k].copy()
+            if not (np.abs(x[1:]).max() != 0.0):  # (a NaN is not zero)
+                beta[k] = x[0]
+                continue
+            ss = x @ x
+            x0 = x[0]
+            beta[k] = -np.sqrt(ss) if x0 > 0.0 else np.sqrt(ss)
+            v = x
+            v[0] = x0 - beta[k]
+            h = ss - x0 * beta[k]
+            p =A[k + 1:, k + 1:] @ v / h
+            q = p - (v @ p) / (2.0 * h) * v
+            A[k + 1:, k + 1:] -= np.outer(v, q) + np.outer(q, v)
+    alpha[:] = np.diag(A)
+    if L >= 2:
+        beta[L - 2] = A[L - 1, L - 2]
+    return alpha, beta
+
+
 def grad_l_dense_model(dq, c, y, z, dtype=np.longdouble):
     """(g, L, mag) of ``IpLQDOCP.lagrangian_gradient_staged`` (hqpkkt_lagrangian_gradient_staged) for a
     :class:`hqp_amd.problems.DenseDocp`: g = c - A'y - C'z in ``dtype`` (numpy longdouble; int64 for integer data), with the

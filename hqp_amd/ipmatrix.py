@@ -462,7 +462,7 @@ class Hqp_IpMatrix:
             self.q_eigen_control(eigen_control, bsize=bsize, from_bfgs=True)
         return v, Qs
 
-    def q_eigen_control(self, eps, bsize=-1, from_bfgs=False, floor=None, max_steps=0):
+    def q_eigen_control(self, eps, bsize=-1, from_bfgs=False, floor=None, max_steps=0, _entry="q_eigen_control"):
         """The eigenvalue control of Hqp_HL_BFGS on the blocks of q_blocks(bsize) of the sparse Q where it lies
         (hqpkkt_q_eigen_control): every block whose smallest eigenvalue - estimated from below by a Lanczos recurrence on
         the device - lies under its floor gets the difference added to its diagonal.  The floor is eps^2; ``from_bfgs``
@@ -480,7 +480,16 @@ class Hqp_IpMatrix:
                 raise ValueError("q_eigen_control: floor holds one value per block of q_blocks(bsize)")
             e.floor = fl.ctypes.data
         self._stream_sync()
-        _check(self._L.hqpkkt_q_eigen_control(self._h, C.byref(e)), "q_eigen_control")
+        _check(getattr(self._L, "hqpkkt_" + _entry)(self._h, C.byref(e)), _entry)
+
+    def q_eigen_control_short(self, eps, bsize=-1, floor_from_bfgs=False, floor=None):
+        """q_eigen_control() for a partition whose blocks are all at most 64 long (hqpkkt_q_eigen_control_short; a longer
+        block: HQPKKT_E_SIZES, nothing done): every block is reduced to a tridiagonal T by Householder reflections in one
+        wavefront and its smallest eigenvalue is bracketed there - the reference's symmeig per block, one launch, no
+        Lanczos recurrence, so no "shifted, not converged".  ``eps``, ``floor_from_bfgs`` and ``floor`` as for
+        q_eigen_control(); q_eigen_report() serves the last control of either kind - steps is the block's length, rho 0,
+        T the reduction's, of stride the longest block."""
+        self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_short")
 
     def q_eigen_report(self, with_T=False):
         """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound

@@ -809,7 +809,54 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       serves both entries); 6 skipped, the block's last BFGS update left it alone.  T (optional): per
  *                       block alpha_0 .. (*t_steps doubles), then beta_0 .. (as many), words past a block's steps 0;
  *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
- *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.
+ *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.  It serves the last
+ *                       control of either kind, hqpkkt_q_eigen_control or hqpkkt_q_eigen_control_short.
+ *   hqpkkt_q_eigen_control_short  the job of hqpkkt_q_eigen_control on the same blocks of hqpkkt_q_blocks(bsize), for a plan
+ *                       whose blocks are ALL at most 64 long (the partition of a DOCP: 125 000 blocks of order 8 at
+ *                       n = 10^6), in ONE launch, a wavefront per block - and lambda is computed as the reference
+ *                       computes it (symmeig: Householder's reduction, then T's eigenvalues), not estimated by a
+ *                       recurrence from a start vector.  Unchanged: the block (the symmetric image of the stored upper
+ *                       entries with both indices in it, zeros in the missing places; entries across blocks and with
+ *                       col < row never read or written), the floor rules (eps, floor_from_bfgs with outcome 6, the
+ *                       host floor), the shift fl(q_ii + d_b), the handle's state afterwards, the report's channel.
+ *                       Per block of length L:
+ *                         Gather.  The L x L image in LDS, lane i walks row first + i of the symmetric image.
+ *                         g_b = min_i (a_ii - offsum_i), a NaN kept, offsum_i = sum of |a_ij|, j != i, in ascending j from
+ *                         +0.0, every add rounded on its own (hessian_update.q_block_gerschgorin_model repeats it).  theta_b as
+ *                         above.  Skipped: outcome 6; g_b >= theta_b: outcome 0; both done, their T words 0.
+ *                         Reduction, k = 0 .. L - 3, x the sub-column a_{k+1 .. L-1, k}: where x is zero below its first
+ *                         entry no reflector is formed, beta_k = x_0 (a zero sub-column: beta_k = 0; no division).
+ *                         Otherwise ss = x'x, beta_k = -sign(x_0) sqrt(ss), v = x with v_0 = x_0 - beta_k, h = ss - x_0
+ *                         beta_k, p = A v / h, q = p - (v'p / 2h) v, a_ij <- fl(a_ij - fl(fl(v_i q_j) + fl(q_i v_j))) on
+ *                         the trailing block.  alpha_i = a_ii at the end, beta_{L-2} = a_{L-1,L-2}, beta_{L-1} = 0; L = 1, 2
+ *                         need no reflector; a diagonal block gives its diagonal bit for bit.  Sums over the wavefront
+ *                         in a fixed order by the index inside the block: a block's bits depend on its length and its
+ *                         values alone, not on where it lies, on the other blocks or on the mode; equal from call to
+ *                         call.  Squares that overflow, or a sub-column whose squares all underflow (entries beyond
+ *                         about 2^+-500), give a T that is not finite: outcome 4.  hessian_update.q_tridiag_model is the
+ *                         method in numpy; T's eigenvalues are the block's to rounding.
+ *                         Bracket and shift.  The device function of the other two controls on T with beta_{L-1} = 0:
+ *                         lo, hi the Sturm bracket of T's smallest eigenvalue, hi - lo <= 2^-50 |T|; rho = 0,
+ *                         lambda_est = lo; d_b = theta_b - lo where lo < theta_b (outcome 2), else 0 (outcome 1); T not
+ *                         finite: outcome 4, the block left alone, no other block touched by it.  Never outcome 3.
+ *                       Differences in the contract.  Every block of the plan must be at most 64 long: otherwise
+ *                       HQPKKT_E_SIZES, nothing is launched, Q is untouched - a mixed plan stays with
+ *                       hqpkkt_q_eigen_control; its short blocks here and its long ones there is not built.  max_steps
+ *                       must be 0 (HQPKKT_E_RANGE otherwise): there is no recurrence to cap.  Checks, before any
+ *                       launch, in this order: HQPKKT_E_NULL; HQPKKT_E_RANGE (eps not finite or <= 0, max_steps != 0,
+ *                       floor_from_bfgs neither 0 nor 1); HQPKKT_E_INTERN (not analysed, no values, a refused handle;
+ *                       floor_from_bfgs without a last hqpkkt_q_bfgs_update of this bsize); HQPKKT_E_RANGE (a floor that
+ *                       is not finite); HQPKKT_E_SIZES (a block longer than 64); HQPKKT_E_FORMAT (a row without exactly
+ *                       one stored diagonal); HQPKKT_E_DEVICE; HQPKKT_E_MEM.  Device state of the plan: the report, T
+ *                       with stride 2 x longest block per block and the floors alone, made or grown by the call that
+ *                       needs them - no basis, no partial sums, no state copies, no n-vectors; a later
+ *                       hqpkkt_q_eigen_control on the plan makes or grows what it needs.  Nothing is cleared ahead of
+ *                       the launch: the kernel writes every word of the report and of T.  Report: 0 g_b; 1 theta_b as
+ *                       used; 2 the block's length L, the order of T; 3 .. 9 as above with rho = 0 and lambda_est = lo,
+ *                       the outcome 0, 1, 2, 4 or 6.  *t_steps is the plan's longest block; T per block alpha_0 ..
+ *                       alpha_{L-1}, words up to *t_steps 0, then beta_0 .. beta_{L-2}, 0, words up to *t_steps 0.
+ *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit.
+ *                       Not built: several order-8 blocks in one wavefront.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -860,6 +907,7 @@ typedef struct hqpkkt_q_eigen_control_args {
   int max_steps;       /* 1 .. HQPKKT_EIG_MAX_STEPS; 0 = 64 */
 } hqpkkt_q_eigen_control_args;
 int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e);
+int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 64 long; max_steps must be 0 */
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
                           double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
                           long long *n_blocks, int *t_steps);

@@ -14,6 +14,7 @@ factorisation.  Per call by wall clock to a device synchronisation, mean of --re
   (m), (n) the route through the host that (k) and (j) replace, without the host's eigen-solver, which comes on top:
   hqpkkt_q_values out to host memory and hqpkkt_set_values in from the pinned staging buffers, on host-vector handles of
   the grid and of the block-diagonal program.
+  (l) q_eigen_control_short on (j)'s handle and plan, taking turns with (j): Householder's T of every block, one launch.
 Bytes: what the call must move at the least - every operand once per pass that needs it, and the regather of Q's image
 behind a write - and the rate that makes at the measured time.
   (s) --staged K NX NU: hqpkkt_lagrangian_gradient_staged on a handle of the dense hand-over, next to the residual's pass
@@ -200,6 +201,11 @@ def main():
         e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, bsize, 0, 0
         return lambda: L.hqpkkt_q_eigen_control(H._h, C.byref(e))
 
+    def eigen_short(H, bsize):
+        e = _lib.QEigenControl()
+        e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, bsize, 0, 0
+        return lambda: L.hqpkkt_q_eigen_control_short(H._h, C.byref(e))
+
     def host_route(H, buf, ptrs):
         return lambda: L.hqpkkt_q_values(H._h, C.c_void_p(buf.ctypes.data)) or L.hqpkkt_set_values(H._h, *ptrs)
 
@@ -222,6 +228,7 @@ def main():
         ("k q_eigen_control bsize 0, the grid lowered", eigen(Mk, 0)),
         ("m q_values out + set_values in, host, the grid", host_route(Hh, qout, (sq, sa, sc))),
         ("n q_values out + set_values in, host, block-diag", host_route(Hb, qoutb, (bq, ba, bc))),
+        ("l q_eigen_control_short detected, block-diag Q", eigen_short(Mb, -1)),
     ]
     prep = {"k": lambda: L.hqpkkt_set_values(Mk._h, P(dQk), P(dA), P(dC))}  # (untimed: the same block before every control)
     nq, na, nc = len(prog.Q[2]), len(prog.A[2]), len(prog.C[2])
@@ -245,6 +252,9 @@ def main():
                 + 2 * n_ * 8 * steps * (steps + 1) // 2 + steps * n_ * 8 + 2 * n_ * 8 + 2 * n_ * 4 + nqf_ * (4 + 8 + 8))
 
     bytes_min = {
+        # the image walked once (columns and values, the row pointers), the blocks' first indices, the report and T written;
+        # the regather of the image behind the write.  The diagonals of the blocks that are shifted come on top.
+        "l": nqfb * 12 + (nB + 1) * 4 + (nb + 1) * 4 + nb * 10 * 8 + nb * 2 * k * 8 + nqfb * (4 + 8 + 8),
         "j": eigen_bytes(nB, nqb, nqfb, min(64, k)),
         "k": eigen_bytes(n, nq, nqf, 64),
         "m": nq * 8 * 2 + (nq + na + nc) * 8 * 2 + (nqf + 2 * na + 2 * nc) * (4 + 8 + 8),
@@ -294,10 +304,17 @@ def main():
     hm, hn = np.mean(times[paths[11][0]]), np.mean(times[paths[12][0]])
     for k2, host, H in ((9, hn, Mb), (10, hm, Mk)):
         tm = np.mean(times[paths[k2][0]])
+        assert k2 != 9 or paths[9][1]() == 0  # (untimed: (l) was the last control on (j)'s handle)
         r_ = H.q_eigen_report()
         oc = {int(o): int((r_[:, 9] == o).sum()) for o in np.unique(r_[:, 9])}
         lines.append(f"({paths[k2][0][0]}): {tm * 1e6:.1f} us, {'below' if tm < host else 'NOT below'} the route through the host ({'n' if k2 == 9 else 'm'}) "
                      f"{host * 1e6:.1f} us; steps at most {int(r_[:, 2].max())}, blocks by outcome {oc}")
+    tl, tj = np.mean(times[paths[13][0]]), np.mean(times[paths[9][0]])
+    assert paths[13][1]() == 0  # (untimed, for its report)
+    r_ = Mb.q_eigen_report()
+    oc = {int(o): int((r_[:, 9] == o).sum()) for o in np.unique(r_[:, 9])}
+    lines.append(f"(l): {tl * 1e6:.1f} us against (j) {tj * 1e6:.1f} us on the same plan, {'below' if tl < hn else 'NOT below'} the route through the host (n) "
+                 f"{hn * 1e6:.1f} us; order of T at most {int(r_[:, 2].max())}, blocks by outcome {oc}")
     text = "\n".join(lines)
     print(text)
     if a.out:

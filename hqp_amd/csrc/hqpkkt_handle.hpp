@@ -308,6 +308,10 @@ struct TreeDev {
       int eig_tcap = 0;                     // half the doubles per block eig_T holds (hqpkkt_q_eigen_control_short makes T,
                                             // the report and the floors alone: eig_cap stays what the basis holds)
       DBuf<double> eig_V, eig_part, eig_T, eig_rep, eig_st, eig_floor;
+      // hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h): the blocks 65 .. 128 long in ascending order, made by its first call
+      int mid_count = -1, mid_max = 0;      // how many (-1: not made yet) and the longest of them
+      int short_max = 0;                    // ... and the longest block of at most 64
+      DBuf<int> mid_list;
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis

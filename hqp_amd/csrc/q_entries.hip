@@ -1,13 +1,14 @@
-// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 20 of them:
+// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 21 of them:
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
 // (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
-// hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h) and
-// hqpkkt_lagrangian_gradient.  Their state is
+// hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h),
+// hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it) and hqpkkt_lagrangian_gradient.  Their state is
 // TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
 // update's own write (k_qv_ds_apply per variable, k_qb_apply per stored entry).  The eigenvalue control runs over the
 // same plans.
+#include <mutex>
 #include <numeric>
 
 #include "hqpkkt_handle.hpp"
@@ -16,6 +17,7 @@
 #include "q_sparse_bfgs.hip.h"
 #include "q_eigen.hip.h"
 #include "q_eigen_short.hip.h"
+#include "q_eigen_mid.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
 
@@ -599,7 +601,41 @@ static int qes_buffers(hqpkkt_t *h, QPlan &p) {
   return 0;
 }
 
-int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+// ---- and on blocks up to 128: the blocks of 65 .. 128 by a workgroup each, over their list (q_eigen_mid.hip.h)
+
+// the list of a plan's blocks of 65 .. 128, their longest and the longest block of at most 64: made once per plan
+static int qem_list(QPlan &p) {
+  if (p.mid_count >= 0) return 0;
+  std::vector<int> list;
+  int mid_max = 0, short_max = 0;
+  for (int b = 0; b < p.nblocks; b++) {
+    const int len = p.first[b + 1] - p.first[b];
+    if (len >= qv::QEM_MIN && len <= qv::QEM_MAX)
+      list.push_back(b), mid_max = std::max(mid_max, len);
+    else if (len < qv::QEM_MIN)
+      short_max = std::max(short_max, len);
+  }
+  int e = p.mid_list.upload(list);
+  if (e) return e;
+  p.mid_count = (int)list.size(), p.mid_max = mid_max, p.short_max = short_max;
+  return 0;
+}
+// the dynamic-LDS limits of k_qem_block: state of the process and of the current device (as raise_lds_limits, tree.hip),
+// constants here, so set once per device
+static int qem_raise_lds(hqpkkt_t *h) {
+  static std::mutex attr_mutex;
+  static bool done[64];
+  if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
+  std::lock_guard<std::mutex> lk(attr_mutex);
+  if (done[h->opts.device]) return 0;
+  HIPCHK(hipFuncSetAttribute((const void *)qv::k_qem_block<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qv::qem_lds_bytes<96>()));
+  HIPCHK(hipFuncSetAttribute((const void *)qv::k_qem_block<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qv::qem_lds_bytes<128>()));
+  done[h->opts.device] = true;
+  return 0;
+}
+
+// both entries: `longest` is the block length the entry serves, 64 or 128
+static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int longest) {
   return guarded([&]() -> int {
     if (!h || !ec) return HQPKKT_E_NULL;
     if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps != 0) return HQPKKT_E_RANGE;
@@ -611,7 +647,7 @@ int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args 
     for (int b = 0; ec->floor && b < q.bfgs_plans[at].nblocks; b++)
       if (!std::isfinite(ec->floor[b])) return HQPKKT_E_RANGE;
     const int cap = q.bfgs_plans[at].max_len;
-    if (cap > 64) return HQPKKT_E_SIZES;
+    if (cap > longest) return HQPKKT_E_SIZES;
     if ((e = qv_prepare(h, true, true))) return e;
     if (h->an.n <= 0) {
       q.eig_last = at, q.bfgs_plans[at].eig_steps = 0;
@@ -620,19 +656,33 @@ int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args 
     if ((e = qb_plan(h, ec->bsize, true, &at))) return e;
     QPlan &p = q.bfgs_plans[at];
     if ((e = qes_buffers(h, p))) return e;
+    const bool mid = cap > 64;  // (the plan has blocks for k_qem_block)
+    if (mid && ((e = qem_list(p)) || (e = qem_raise_lds(h)))) return e;
     hipStream_t s = h->stream;
     if (ec->floor) {  // (as hqpkkt_q_eigen_control: the caller's again on return)
       HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
       HIPCHK(hipStreamSynchronize(s));
     }
-    // the instance by the LDS of its image: the smallest that holds the plan's longest block
-    const auto block = pick(cap > 16, pick(cap > 8, qv::k_qes_block<8>, qv::k_qes_block<16>), pick(cap > 32, qv::k_qes_block<32>, qv::k_qes_block<64>));
-    block<<<(unsigned)p.nblocks, 64, 0, s>>>(p.boff.p, h->td.Qf.dev(), q.didx.p, h->td.vals.p, ec->floor ? p.eig_floor.p : nullptr,
-                                             ec->eps * ec->eps, ec->floor_from_bfgs ? p.rep.p : nullptr, cap, p.eig_T.p, p.eig_rep.p);
+    const double *flr = ec->floor ? p.eig_floor.p : nullptr, *bfgs = ec->floor_from_bfgs ? p.rep.p : nullptr;
+    const double eps2 = ec->eps * ec->eps;
+    // the instance by the LDS of its image: the smallest that holds the longest block of at most 64, which returns at
+    // once on a longer one
+    const int sm = mid ? p.short_max : cap;
+    const auto block = pick(sm > 16, pick(sm > 8, qv::k_qes_block<8>, qv::k_qes_block<16>), pick(sm > 32, qv::k_qes_block<32>, qv::k_qes_block<64>));
+    block<<<(unsigned)p.nblocks, 64, 0, s>>>(p.boff.p, h->td.Qf.dev(), q.didx.p, h->td.vals.p, flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
+    if (mid) {
+      const bool big = p.mid_max > 96;
+      pick(big, qv::k_qem_block<96>, qv::k_qem_block<128>)<<<(unsigned)p.mid_count, 256, big ? qv::qem_lds_bytes<128>() : qv::qem_lds_bytes<96>(), s>>>(
+          p.mid_list.p, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
+      qv::k_qem_ritz<<<(unsigned)p.mid_count, 64, 0, s>>>(p.mid_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
+    }
     q.eig_last = at, p.eig_steps = cap;
     return qv_written(h);
   });
 }
+
+int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) { return qes_control(h, ec, 64); }
+int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) { return qes_control(h, ec, qv::QEM_MAX); }
 
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {
   if (!t_steps) return HQPKKT_E_NULL;

@@ -491,6 +491,14 @@ class Hqp_IpMatrix:
         T the reduction's, of stride the longest block."""
         self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_short")
 
+    def q_eigen_control_exact(self, eps, bsize=-1, floor_from_bfgs=False, floor=None):
+        """q_eigen_control_short() for a partition whose blocks are all at most 128 long, short and longer ones in one plan
+        (hqpkkt_q_eigen_control_exact; a longer block: HQPKKT_E_SIZES, nothing done): the blocks up to 64 as there, the
+        blocks of 65 .. 128 reduced by a workgroup each, then bracketed and shifted by a wavefront each - the exact
+        eigenvalue where q_eigen_control() at its 64 steps can only estimate, no basis of steps x n doubles.  A partition
+        with no block over 64 gives q_eigen_control_short()'s bits."""
+        self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_exact")
+
     def q_eigen_report(self, with_T=False):
         """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound
         g, the floor theta as used, the Lanczos steps, lo, hi (the bracket of T's smallest eigenvalue), rho (the residual

@@ -810,7 +810,8 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       block alpha_0 .. (*t_steps doubles), then beta_0 .. (as many), words past a block's steps 0;
  *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
  *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.  It serves the last
- *                       control of either kind, hqpkkt_q_eigen_control or hqpkkt_q_eigen_control_short.
+ *                       control of any kind: hqpkkt_q_eigen_control, hqpkkt_q_eigen_control_short or
+ *                       hqpkkt_q_eigen_control_exact.
  *   hqpkkt_q_eigen_control_short  the job of hqpkkt_q_eigen_control on the same blocks of hqpkkt_q_blocks(bsize), for a plan
  *                       whose blocks are ALL at most 64 long (the partition of a DOCP: 125 000 blocks of order 8 at
  *                       n = 10^6), in ONE launch, a wavefront per block - and lambda is computed as the reference
@@ -840,8 +841,8 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                         lambda_est = lo; d_b = theta_b - lo where lo < theta_b (outcome 2), else 0 (outcome 1); T not
  *                         finite: outcome 4, the block left alone, no other block touched by it.  Never outcome 3.
  *                       Differences in the contract.  Every block of the plan must be at most 64 long: otherwise
- *                       HQPKKT_E_SIZES, nothing is launched, Q is untouched - a mixed plan stays with
- *                       hqpkkt_q_eigen_control; its short blocks here and its long ones there is not built.  max_steps
+ *                       HQPKKT_E_SIZES, nothing is launched, Q is untouched - a plan with blocks up to 128 goes to
+ *                       hqpkkt_q_eigen_control_exact, one with longer blocks to hqpkkt_q_eigen_control.  max_steps
  *                       must be 0 (HQPKKT_E_RANGE otherwise): there is no recurrence to cap.  Checks, before any
  *                       launch, in this order: HQPKKT_E_NULL; HQPKKT_E_RANGE (eps not finite or <= 0, max_steps != 0,
  *                       floor_from_bfgs neither 0 nor 1); HQPKKT_E_INTERN (not analysed, no values, a refused handle;
@@ -857,6 +858,28 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       alpha_{L-1}, words up to *t_steps 0, then beta_0 .. beta_{L-2}, 0, words up to *t_steps 0.
  *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit.
  *                       Not built: several order-8 blocks in one wavefront.
+ *   hqpkkt_q_eigen_control_exact  hqpkkt_q_eigen_control_short for a plan whose blocks are all at most 128 long, blocks of
+ *                       both classes in one plan (one DOCP stage of 60 - 120 states and controls among 125 000 blocks
+ *                       of order 8): the same arguments, floor rules, checks in the same order, report, T layout and
+ *                       handle state, and per block the same mathematics - gather, g_b, theta_b, outcomes 0 and 6, the
+ *                       reduction's zero-sub-column rule, beta_k, v, h, p, q, the commuting rank-2 update, the bracket and
+ *                       the shift as above.  Launches: the short entry's launch over all blocks (it returns at once on
+ *                       a block over 64), in the instance of the longest block of at most 64; then, over the list of
+ *                       the blocks of 65 .. 128 (made on the host by the first call that needs it, kept with the plan),
+ *                       a workgroup of four wavefronts per block - thread t has row t mod 128 and one half of the
+ *                       trailing columns, p_i = fl(fl(half0 + half1) / h); sums over the block by a butterfly per
+ *                       wavefront and the wavefronts' values in ascending order: fixed by the index inside the block,
+ *                       so a block's bits depend on its length and its values alone and are equal from call to call -
+ *                       and a launch of a wavefront per listed block for the bracket and the shift.  A plan with no
+ *                       block over 64 runs the short entry's launch alone and gives its bits.  HQPKKT_E_SIZES: a
+ *                       block longer than 128; nothing is launched, Q is untouched.  HQPKKT_E_DEVICE also where the
+ *                       device refuses the 134 KB of LDS of the longer instance, before any launch.  Device state:
+ *                       the short entry's and the list.  Report: word 2 is L, rho = 0, lambda_est = lo, the outcome
+ *                       0, 1, 2, 4 or 6, never 3; *t_steps is the plan's longest block;
+ *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit, and
+ *                       hessian_update.q_tridiag_model is the method in numpy at these lengths too.
+ *                       Not built: blocks over 128 beside shorter ones (hqpkkt_q_eigen_control serves that plan);
+ *                       several order-8 blocks in one wavefront.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -908,6 +931,7 @@ typedef struct hqpkkt_q_eigen_control_args {
 } hqpkkt_q_eigen_control_args;
 int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e);
 int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 64 long; max_steps must be 0 */
+int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 128 long; max_steps must be 0 */
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
                           double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
                           long long *n_blocks, int *t_steps);

@@ -17,10 +17,12 @@ __device__ __forceinline__ double nan_min(double m, double a) { return (a < m ||
 // entry i of the start vector before it is normalised: 1 + ((37 i + 11) mod 64) / 64, in [1, 2), exact
 __device__ __forceinline__ double start_entry(int i) { return 1.0 + (double)((37 * i + 11) & 63) * 0.015625; }
 
-// the work arrays of ritz: one set per workgroup of one wavefront
-struct RitzLds {
-  double al[MAX_STEPS], be[MAX_STEPS], b2[MAX_STEPS], pv[MAX_STEPS], rv[MAX_STEPS], z[MAX_STEPS];
+// the work arrays of ritz for a T of order up to CAP: one set per workgroup of one wavefront
+template <int CAP>
+struct RitzLdsT {
+  double al[CAP], be[CAP], b2[CAP], pv[CAP], rv[CAP], z[CAP];
 };
+using RitzLds = RitzLdsT<MAX_STEPS>;
 
 // One wavefront, the only one of its workgroup: the smallest eigenvalue of the tridiagonal T (order m = steps, diagonal
 // alpha_0 .. alpha_{m-1}, off-diagonal beta_0 .. beta_{m-2}; beta_{m-1} is the norm of the last residual) and the shift
@@ -39,8 +41,10 @@ struct RitzLds {
 //             where rho <= EIG_END_REL |T|, else 3; otherwise d = 0, outcome 1
 // r: the REPORT words of the block - of g, theta (the caller's start kernel wrote them), steps, lo, hi, rho, lambda_est, d,
 // |T|, outcome this writes 2 .. 9 (of a T that is not finite 2, 8 and 9 alone).  m < 1: no step has run (outcome 4).
+// Lds: a RitzLdsT whose capacity is at least m.
+template <class Lds>
 __device__ __forceinline__ void ritz(const double *__restrict__ alpha, const double *__restrict__ beta, int m, double theta,
-                                     double *__restrict__ r, RitzLds &w) {
+                                     double *__restrict__ r, Lds &w) {
 #pragma clang fp contract(off)
   double *al = w.al, *be = w.be, *b2 = w.b2, *pv = w.pv, *rv = w.rv, *z = w.z;
   const int lane = threadIdx.x;

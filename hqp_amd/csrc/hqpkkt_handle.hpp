@@ -5,7 +5,7 @@
 //                      posted read-backs
 //   staged_engine.hip  the STAGED engine (staged.hip.h, staged_gemm.hip.h, staged_host.hip.h; launch rule of its product: gemm_form.hpp)
 //   ip_loops.hip       the device-resident interior-point loops (ipdriver.hip.h)
-//   q_entries.hip      the entries on the sparse Q where it lies (q_values.hip.h, q_bfgs.hip.h, q_eigen.hip.h)
+//   q_entries.hip      the entries on the sparse Q where it lies (q_values.hip.h, q_bfgs.hip.h, q_eigen.hip.h .. q_eigen_long.hip.h)
 //   hqpkkt.hip         the rest of the C ABI: handle management, factor / solve and their refinement, getters
 #pragma once
 #include "../../include/hqpkkt.h"
@@ -312,6 +312,12 @@ struct TreeDev {
       int mid_count = -1, mid_max = 0;      // how many (-1: not made yet) and the longest of them
       int short_max = 0;                    // ... and the longest block of at most 64
       DBuf<int> mid_list;
+      // hqpkkt_q_eigen_control_long (q_eigen_long.hip.h): the blocks 129 .. 512 long, listed by the same pass; their images'
+      // workspace, long_slots x long_ld x long_ld doubles, made by the first call that needs it
+      int long_count = 0, long_max = 0;     // how many and the longest of them
+      int long_slots = 0, long_ld = 0;      // workgroups of k_qel_block, one image each; an image's leading dimension
+      DBuf<int> long_list;
+      DBuf<double> long_ws;
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis

@@ -30,7 +30,7 @@
 // launches.  No contraction; sums that fuse say __fma_rn.
 // No MFMA: every step is a matrix-vector product and a symmetric rank-2 update of order <= 128 whose operands change with
 // the step - L^2 multiply-adds against a vector, no product of two matrices to tile.
-// Not built: blocks over 128 (the image leaves LDS); several order-8 blocks per wavefront.
+// Not built: several order-8 blocks per wavefront.  (Blocks over 128, whose image leaves LDS: q_eigen_long.hip.h.)
 // Included by q_entries.hip behind q_eigen_short.hip.h.
 #pragma once
 #include "q_eigen_short.hip.h"

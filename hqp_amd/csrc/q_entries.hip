@@ -2,7 +2,8 @@
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
 // (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
 // hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h),
-// hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it) and hqpkkt_lagrangian_gradient.  Their state is
+// hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it), hqpkkt_q_eigen_control_long (q_eigen_long.hip.h beside both) and
+// hqpkkt_lagrangian_gradient.  Their state is
 // TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
@@ -18,6 +19,7 @@
 #include "q_eigen.hip.h"
 #include "q_eigen_short.hip.h"
 #include "q_eigen_mid.hip.h"
+#include "q_eigen_long.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
 
@@ -601,23 +603,45 @@ static int qes_buffers(hqpkkt_t *h, QPlan &p) {
   return 0;
 }
 
-// ---- and on blocks up to 128: the blocks of 65 .. 128 by a workgroup each, over their list (q_eigen_mid.hip.h)
+// ---- and on blocks up to 128 and up to 512: the blocks of 65 .. 128 by a workgroup each, over their list (q_eigen_mid.hip.h);
+// the blocks of 129 .. 512 by persistent workgroups over theirs, the images in device memory (q_eigen_long.hip.h)
 
-// the list of a plan's blocks of 65 .. 128, their longest and the longest block of at most 64: made once per plan
+// one pass over the plan: the list of its blocks of 65 .. 128 and the list of its blocks of 129 .. 512, the longest of
+// each and the longest block of at most 64: made once per plan
 static int qem_list(QPlan &p) {
   if (p.mid_count >= 0) return 0;
-  std::vector<int> list;
-  int mid_max = 0, short_max = 0;
+  std::vector<int> mid, lng;
+  int mid_max = 0, short_max = 0, long_max = 0;
   for (int b = 0; b < p.nblocks; b++) {
     const int len = p.first[b + 1] - p.first[b];
-    if (len >= qv::QEM_MIN && len <= qv::QEM_MAX)
-      list.push_back(b), mid_max = std::max(mid_max, len);
+    if (len >= qv::QEL_MIN && len <= qv::QEL_MAX)
+      lng.push_back(b), long_max = std::max(long_max, len);
+    else if (len >= qv::QEM_MIN && len <= qv::QEM_MAX)
+      mid.push_back(b), mid_max = std::max(mid_max, len);
     else if (len < qv::QEM_MIN)
       short_max = std::max(short_max, len);
   }
-  int e = p.mid_list.upload(list);
-  if (e) return e;
-  p.mid_count = (int)list.size(), p.mid_max = mid_max, p.short_max = short_max;
+  DBuf<int> dm, dl;
+  int e;
+  if ((e = dm.upload(mid)) || (e = dl.upload(lng))) return e;
+  p.mid_list = std::move(dm), p.long_list = std::move(dl);
+  p.long_count = (int)lng.size(), p.long_max = long_max;
+  p.mid_count = (int)mid.size(), p.mid_max = mid_max, p.short_max = short_max;
+  return 0;
+}
+// the images of k_qel_block: slots = min(listed blocks, CUs) - capped by the test hook HQPKKT_QEL_SLOTS, read here -, each
+// LD x LD doubles, LD the longest listed block rounded up to 16: at most 256 x 2 MB.  All or nothing
+static int qel_workspace(hqpkkt_t *h, QPlan &p) {
+  if (p.long_ws.p || p.long_count <= 0) return 0;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+  int slots = std::min(p.long_count, std::max(cus, 1));
+  if (const char *cap = getenv("HQPKKT_QEL_SLOTS"))
+    if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
+  const int ld = (p.long_max + 15) & ~15;
+  DBuf<double> ws;
+  if (int e = ws.alloc((size_t)slots * ld * ld)) return e;
+  p.long_ws = std::move(ws), p.long_slots = slots, p.long_ld = ld;
   return 0;
 }
 // the dynamic-LDS limits of k_qem_block: state of the process and of the current device (as raise_lds_limits, tree.hip),
@@ -634,7 +658,15 @@ static int qem_raise_lds(hqpkkt_t *h) {
   return 0;
 }
 
-// both entries: `longest` is the block length the entry serves, 64 or 128
+// threads per workgroup of k_qel_block: QEL_THREADS by the measurement in DESIGN.md; HQPKKT_QEL_THREADS (512 or 1024) is the
+// hook that measurement used - the two instances give the same bits
+static const int QEL_THREADS = 1024;
+static int qel_threads() {
+  const char *v = getenv("HQPKKT_QEL_THREADS");  // (read per call: the measurement lets the two take turns)
+  return v ? atoi(v) : QEL_THREADS;
+}
+
+// the three entries: `longest` is the block length the entry serves, 64, 128 or 512
 static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int longest) {
   return guarded([&]() -> int {
     if (!h || !ec) return HQPKKT_E_NULL;
@@ -657,7 +689,9 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
     QPlan &p = q.bfgs_plans[at];
     if ((e = qes_buffers(h, p))) return e;
     const bool mid = cap > 64;  // (the plan has blocks for k_qem_block)
-    if (mid && ((e = qem_list(p)) || (e = qem_raise_lds(h)))) return e;
+    if (mid && (e = qem_list(p))) return e;
+    const bool lng = mid && p.long_count > 0;  // (and blocks for k_qel_block)
+    if ((lng && (e = qel_workspace(h, p))) || (mid && p.mid_count > 0 && (e = qem_raise_lds(h)))) return e;
     hipStream_t s = h->stream;
     if (ec->floor) {  // (as hqpkkt_q_eigen_control: the caller's again on return)
       HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
@@ -670,11 +704,17 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
     const int sm = mid ? p.short_max : cap;
     const auto block = pick(sm > 16, pick(sm > 8, qv::k_qes_block<8>, qv::k_qes_block<16>), pick(sm > 32, qv::k_qes_block<32>, qv::k_qes_block<64>));
     block<<<(unsigned)p.nblocks, 64, 0, s>>>(p.boff.p, h->td.Qf.dev(), q.didx.p, h->td.vals.p, flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
-    if (mid) {
+    if (mid && p.mid_count > 0) {
       const bool big = p.mid_max > 96;
       pick(big, qv::k_qem_block<96>, qv::k_qem_block<128>)<<<(unsigned)p.mid_count, 256, big ? qv::qem_lds_bytes<128>() : qv::qem_lds_bytes<96>(), s>>>(
           p.mid_list.p, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
       qv::k_qem_ritz<<<(unsigned)p.mid_count, 64, 0, s>>>(p.mid_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
+    }
+    if (lng) {
+      const bool wide = qel_threads() > 512;
+      pick(wide, qv::k_qel_block<512>, qv::k_qel_block<1024>)<<<(unsigned)p.long_slots, wide ? 1024 : 512, 0, s>>>(
+          p.long_list.p, p.long_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.long_ws.p, p.long_ld);
+      qv::k_qel_ritz<<<(unsigned)p.long_count, 64, 0, s>>>(p.long_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
     }
     q.eig_last = at, p.eig_steps = cap;
     return qv_written(h);
@@ -683,6 +723,10 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
 
 int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) { return qes_control(h, ec, 64); }
 int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) { return qes_control(h, ec, qv::QEM_MAX); }
+int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+  static_assert(qv::QEL_MAX == HQPKKT_QEIG_LONG_MAX, "the kernels size their LDS by it");
+  return qes_control(h, ec, qv::QEL_MAX);
+}
 
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {
   if (!t_steps) return HQPKKT_E_NULL;

@@ -499,6 +499,15 @@ class Hqp_IpMatrix:
         with no block over 64 gives q_eigen_control_short()'s bits."""
         self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_exact")
 
+    def q_eigen_control_long(self, eps, bsize=-1, floor_from_bfgs=False, floor=None):
+        """q_eigen_control_exact() for a partition whose blocks are all at most 512 long (_lib.HQPKKT_QEIG_LONG_MAX), short,
+        mid and long ones in one plan (hqpkkt_q_eigen_control_long; a longer block: HQPKKT_E_SIZES, nothing done): the
+        blocks up to 128 as there, the blocks of 129 .. 512 reduced in device memory by persistent workgroups - one pass
+        over the trailing image per step -, then bracketed and shifted by a wavefront each.  The images take
+        min(long blocks, CUs) x LD x LD doubles, LD the longest of them rounded up to 16: at most 512 MB.  A partition
+        with no block over 128 gives q_eigen_control_exact()'s bits; q_eigen_report() returns T of stride up to 512."""
+        self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_long")
+
     def q_eigen_report(self, with_T=False):
         """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound
         g, the floor theta as used, the Lanczos steps, lo, hi (the bracket of T's smallest eigenvalue), rho (the residual

@@ -810,8 +810,9 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       block alpha_0 .. (*t_steps doubles), then beta_0 .. (as many), words past a block's steps 0;
  *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
  *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.  It serves the last
- *                       control of any kind: hqpkkt_q_eigen_control, hqpkkt_q_eigen_control_short or
- *                       hqpkkt_q_eigen_control_exact.
+ *                       control of any kind: hqpkkt_q_eigen_control, hqpkkt_q_eigen_control_short,
+ *                       hqpkkt_q_eigen_control_exact or hqpkkt_q_eigen_control_long - behind the last of these *t_steps
+ *                       may exceed HQPKKT_EIG_MAX_STEPS (up to HQPKKT_QEIG_LONG_MAX).
  *   hqpkkt_q_eigen_control_short  the job of hqpkkt_q_eigen_control on the same blocks of hqpkkt_q_blocks(bsize), for a plan
  *                       whose blocks are ALL at most 64 long (the partition of a DOCP: 125 000 blocks of order 8 at
  *                       n = 10^6), in ONE launch, a wavefront per block - and lambda is computed as the reference
@@ -878,8 +879,42 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       0, 1, 2, 4 or 6, never 3; *t_steps is the plan's longest block;
  *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit, and
  *                       hessian_update.q_tridiag_model is the method in numpy at these lengths too.
- *                       Not built: blocks over 128 beside shorter ones (hqpkkt_q_eigen_control serves that plan);
- *                       several order-8 blocks in one wavefront.
+ *                       Not built: several order-8 blocks in one wavefront.  (Blocks over 128 beside shorter ones:
+ *                       hqpkkt_q_eigen_control_long.)
+ *   hqpkkt_q_eigen_control_long  hqpkkt_q_eigen_control_exact for a plan whose blocks are all at most HQPKKT_QEIG_LONG_MAX =
+ *                       512 long, short, mid and long blocks in one plan (one DOCP stage with up to 512 states and
+ *                       controls): the same arguments and floor rules (eps, floor_from_bfgs with outcome 6, the host
+ *                       floor), checks in the same order, report words (rho = 0, lambda_est = lo, the outcome 0, 1, 2, 4
+ *                       or 6, never 3), T layout (alpha then beta at stride 2 x the plan's longest block) and handle
+ *                       state, and per block the same mathematics.  max_steps must be 0.  Launches: the exact entry's -
+ *                       the short launch over all blocks, the two launches over the list of the blocks of 65 .. 128 if
+ *                       there are any -, then two over the list of the blocks of 129 .. 512 (both lists made on the
+ *                       host by one pass at the first call that needs them, kept with the plan).  The image of a long
+ *                       block lies in device memory: a workspace of slots x LD x LD doubles, LD the longest listed
+ *                       block rounded up to 16, slots = min(listed blocks, CUs of the device) - at most 512 MB -, made
+ *                       by the first call that needs it and kept with the plan; HQPKKT_E_MEM where it cannot be had,
+ *                       the handle unchanged.  `slots` persistent workgroups (1024 threads) take the listed blocks in
+ *                       turn, each in its own image, sharing nothing.  Per block: the image cleared and gathered, g_b,
+ *                       theta_b and the outcomes 0 and 6 as above (offsum_i in ascending j by one thread per row:
+ *                       hessian_update.q_block_gerschgorin_model repeats it), then the reduction's steps with the rules
+ *                       above, the rank-2 update of a step applied by the NEXT step's pass, so that every element of the
+ *                       trailing image is loaded once per step: p_i is the sum of the row's products by one chain of
+ *                       fused multiply-adds per lane over its columns k + 1 + lane + 64 c in ascending c, then a
+ *                       butterfly over the wavefront, divided by h; sums over the block by a butterfly per wavefront
+ *                       and the wavefronts' values in ascending order.  A block's bits depend on its length and its
+ *                       values alone - not on its slot, on where it lies, on the other blocks or on the mode - and
+ *                       are equal from call to call.  Then a wavefront per listed block for the bracket and the
+ *                       shift.  A plan with no block over 128 runs exactly the exact entry's launches and gives its
+ *                       bits.  HQPKKT_E_SIZES: a block longer than 512; nothing is launched, Q is untouched.  Report:
+ *                       word 2 is L; *t_steps of hqpkkt_q_eigen_report is the plan's longest block and so MAY EXCEED
+ *                       HQPKKT_EIG_MAX_STEPS (up to 512): size T by *t_steps, never by that macro.
+ *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit, and
+ *                       hessian_update.q_tridiag_model is the method in numpy at these lengths too.  The environment
+ *                       variable HQPKKT_QEL_SLOTS caps `slots` (a test hook, read when the workspace is sized).
+ *                       Not built: storage of one triangle of the image alone (half the traffic); a blocked reduction
+ *                       with MFMA (it changes the order of the operations); blocks over 512 (hqpkkt_q_eigen_control
+ *                       serves that plan); the dense stage Hessians' own exact control; several order-8 blocks in one
+ *                       wavefront.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -932,6 +967,8 @@ typedef struct hqpkkt_q_eigen_control_args {
 int hqpkkt_q_eigen_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e);
 int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 64 long; max_steps must be 0 */
 int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 128 long; max_steps must be 0 */
+#define HQPKKT_QEIG_LONG_MAX 512
+int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_LONG_MAX long; max_steps must be 0 */
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
                           double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
                           long long *n_blocks, int *t_steps);

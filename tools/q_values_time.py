@@ -25,6 +25,9 @@ behind a write - and the rate that makes at the measured time.
   (x) --exact: q_eigen_control_exact against q_eigen_control on two plans with blocks of 128 (exact_rows below); a run of
   its own, appended to --out.
     python tools/q_values_time.py --exact [--reps 20 --warmup 3 --out FILE]
+  (y) --long: q_eigen_control_long against q_eigen_control at 64 and 128 steps on plans with blocks of 512, 200 and 8 beside one
+    of 512, and the long entry at 512 and 1024 threads per workgroup (long_rows below); a run of its own, appended to --out.
+    python tools/q_values_time.py --long [--reps 20 --warmup 3 --out FILE]
 """
 import argparse
 import ctypes as C
@@ -109,47 +112,55 @@ def staged_gradient_rows(K, nx, nu, reps, warmup):
     return lines
 
 
-def exact_rows(reps, warmup):
-    """(x) hqpkkt_q_eigen_control_exact against hqpkkt_q_eigen_control at its default 64 steps, on two plans of n about 10^6
-    with detected blocks: 7812 full blocks of order 128, and 124 984 blocks of order 8 with one block of 128 in their middle.
-    Every block is symmetric with entries of size 1 / sqrt(order) on a unit diagonal - indefinite, so that no block ends at
-    Gerschgorin's bound.  The two entries take turns; the values are set again from device arrays, untimed, before every
-    call.  By wall clock to a device synchronisation.  The shifts: the exact entry's d_b against the recurrence's."""
+def _block_program(orders):
+    """full symmetric blocks of these orders on the diagonal, entries of size 1 / sqrt(order) beside a unit diagonal"""
+    rng = np.random.default_rng(3)
+    first = np.concatenate([[0], np.cumsum(orders)])
+    qr, qc, qv = [], [], []
+    for k in np.unique(orders):
+        at = first[:-1][orders == k][:, None]
+        i, j = np.triu_indices(k)
+        qr.append((at + i).ravel()), qc.append((at + j).ravel())
+        qv.append(np.where(i == j, 1.0, rng.uniform(-1.0, 1.0, (at.size, i.size)) / np.sqrt(k)).ravel())
+    n = int(first[-1])
+    qr, qc, qv = (np.concatenate(v) for v in (qr, qc, qv))
+    if np.unique(orders).size > 1:  # (one order alone comes out by rows)
+        order = np.lexsort((qc, qr))
+        qr, qc, qv = qr[order], qc[order], qv[order]
+    Q = problems._csr(qr, qc, qv, n)
+    none = problems._csr([], [], [], 0)
+    Cm = problems._csr(np.arange(n // 2), 2 * np.arange(n // 2), np.ones(n // 2), n // 2)
+    return problems.Program(n, 0, n // 2, Q, none, Cm, d=-np.ones(n // 2))
+
+
+def _control_rows(cases, paths, reps, warmup):
+    """the entries of ``paths`` - (name, symbol, max_steps, HQPKKT_QEL_THREADS or None), the first the one that computes lambda -
+    taking turns on every plan of ``cases`` - (label, block orders, how many of the paths) -; the values are set again from device arrays, untimed, before every call.  By wall clock
+    to a device synchronisation.  The shifts: the first entry's d_b against the others'."""
     import torch
     L = _lib.lib()
     lines = [f"device {torch.cuda.get_device_name(0)}; mean of {reps} after {warmup}, wall clock to a device synchronisation; values set again before every call",
              f"{'path':58s} {'mean us':>10s} {'min us':>10s} {'max us':>10s}"]
-    for label, orders in (("7812 blocks of 128", np.full(7812, 128)), ("124984 blocks of 8, one of 128", np.insert(np.full(124984, 8), 62492, 128))):
-        rng = np.random.default_rng(3)
-        first = np.concatenate([[0], np.cumsum(orders)])
-        qr, qc, qv = [], [], []
-        for k in np.unique(orders):
-            at = first[:-1][orders == k][:, None]
-            i, j = np.triu_indices(k)
-            qr.append((at + i).ravel()), qc.append((at + j).ravel())
-            qv.append(np.where(i == j, 1.0, rng.uniform(-1.0, 1.0, (at.size, i.size)) / np.sqrt(k)).ravel())
-        n = int(first[-1])
-        qr, qc, qv = (np.concatenate(v) for v in (qr, qc, qv))
-        if np.unique(orders).size > 1:  # (one order alone comes out by rows)
-            order = np.lexsort((qc, qr))
-            qr, qc, qv = qr[order], qc[order], qv[order]
-        Q = problems._csr(qr, qc, qv, n)
-        none = problems._csr([], [], [], 0)
-        Cm = problems._csr(np.arange(n // 2), 2 * np.arange(n // 2), np.ones(n // 2), n // 2)
-        prog = problems.Program(n, 0, n // 2, Q, none, Cm, d=-np.ones(n // 2))
+    for label, orders, npaths in cases:
+        prog = _block_program(orders)
+        n = prog.n
+        print(f"{label}: program made", file=sys.stderr, flush=True)
         t0 = time.perf_counter()
         M = ipmatrix.IpRedSpBKP(device_vectors=True, ordering=2)
         M.init(prog)
         t_init = time.perf_counter() - t0
         dev = torch.device("cuda", 0)
         dQ, dC = (torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64)).to(dev) for v in (prog.Q[2], prog.C[2]))
-        e = _lib.QEigenControl()
-        e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, -1, 0, 0
-        paths = [("x q_eigen_control_exact, " + label, L.hqpkkt_q_eigen_control_exact), ("  q_eigen_control, 64 steps, " + label, L.hqpkkt_q_eigen_control)]
-        times, reports = {nm: [] for nm, _f in paths}, {}
+        named = [(nm + label, getattr(L, sym), steps, thr) for nm, sym, steps, thr in paths[:npaths]]
+        times, reports = {nm: [] for nm, _f, _s, _t in named}, {}
         torch.cuda.synchronize()
         for r in range(warmup + reps):
-            for nm, fn in paths:
+            for nm, fn, steps, thr in named:
+                os.environ.pop("HQPKKT_QEL_THREADS", None)
+                if thr:
+                    os.environ["HQPKKT_QEL_THREADS"] = thr
+                e = _lib.QEigenControl()
+                e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, -1, 0, steps
                 assert L.hqpkkt_set_values(M._h, C.c_void_p(dQ.data_ptr()), None, C.c_void_p(dC.data_ptr())) == 0
                 torch.cuda.synchronize()
                 t = time.perf_counter()
@@ -161,20 +172,47 @@ def exact_rows(reps, warmup):
                     times[nm].append(dt)
                 reports[nm] = M.q_eigen_report() if r == 0 else reports[nm]
         lines.append(f"{label}: n {n}, nnz Q {len(prog.Q[2])}; analysis + values {t_init:.1f} s")
-        for nm, _f in paths:
+        os.environ.pop("HQPKKT_QEL_THREADS", None)
+        for nm, _f, _s, _t in named:
             t, r_ = np.array(times[nm]), reports[nm]
             oc = {int(o): int((r_[:, 9] == o).sum()) for o in np.unique(r_[:, 9])}
             lines.append(f"{nm:58s} {t.mean() * 1e6:10.1f} {t.min() * 1e6:10.1f} {t.max() * 1e6:10.1f}   blocks by outcome {oc}, "
                          f"steps at most {int(r_[:, 2].max())}, largest shift {r_[:, 7].max():.6f}")
-        over = reports[paths[1][0]][:, 7] - reports[paths[0][0]][:, 7]
-        lines.append(f"  the recurrence's shift less the exact one: at most {over.max():.3e}, at least {over.min():.3e}")
+        for nm, _f, _s, _t in named[1:]:
+            over = reports[nm][:, 7] - reports[named[0][0]][:, 7]
+            lines.append(f"  the shift of {nm.strip()} less the exact one: at most {over.max():.3e}, at least {over.min():.3e}")
+        del M, dQ, dC, prog
     return lines
+
+
+def exact_rows(reps, warmup):
+    """(x) hqpkkt_q_eigen_control_exact against hqpkkt_q_eigen_control at its default 64 steps, on two plans of n about 10^6
+    with detected blocks: 7812 full blocks of order 128, and 124 984 blocks of order 8 with one block of 128 in their middle.
+    Every block is indefinite, so that no block ends at Gerschgorin's bound (_block_program, _control_rows)."""
+    return _control_rows((("7812 blocks of 128", np.full(7812, 128), 2), ("124984 blocks of 8, one of 128", np.insert(np.full(124984, 8), 62492, 128), 2)),
+                         (("x q_eigen_control_exact, ", "hqpkkt_q_eigen_control_exact", 0, None), ("  q_eigen_control, 64 steps, ", "hqpkkt_q_eigen_control", 0, None)),
+                         reps, warmup)
+
+
+def long_rows(reps, warmup):
+    """(y) hqpkkt_q_eigen_control_long against hqpkkt_q_eigen_control at 64 and at 128 steps, as exact_rows, on three plans:
+    1953 full blocks of 512, 5000 of 200, and 124 936 blocks of 8 with one block of 512 in their middle.  On the first plan the
+    long entry runs twice more per round, at 512 and at 1024 threads per workgroup of k_qel_block (HQPKKT_QEL_THREADS)."""
+    cases = (("1953 blocks of 512", np.full(1953, 512), 5), ("5000 blocks of 200", np.full(5000, 200), 3),
+             ("124936 blocks of 8, one of 512", np.insert(np.full(124936, 8), 62468, 512), 3))
+    paths = (("y q_eigen_control_long, ", "hqpkkt_q_eigen_control_long", 0, None), ("  q_eigen_control, 64 steps, ", "hqpkkt_q_eigen_control", 64, None),
+             ("  q_eigen_control, 128 steps, ", "hqpkkt_q_eigen_control", 128, None),
+             ("y q_eigen_control_long, 512 threads, ", "hqpkkt_q_eigen_control_long", 0, "512"),
+             ("y q_eigen_control_long, 1024 threads, ", "hqpkkt_q_eigen_control_long", 0, "1024"))
+    return _control_rows(cases, paths, reps, warmup)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--exact", action="store_true",
                     help="the rows of hqpkkt_q_eigen_control_exact against hqpkkt_q_eigen_control alone; --out is appended to")
+    ap.add_argument("--long", action="store_true",
+                    help="the rows of hqpkkt_q_eigen_control_long against hqpkkt_q_eigen_control at 64 and 128 steps alone; --out is appended to")
     ap.add_argument("--staged", type=int, nargs=3, metavar=("K", "NX", "NU"), default=None,
                     help="the rows of hqpkkt_lagrangian_gradient_staged at this DOCP alone (the headline: 200 5000 50); --out is appended to")
     ap.add_argument("--gx", type=int, default=1000)
@@ -185,8 +223,9 @@ def main():
     ap.add_argument("--bfgs-order", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.staged or a.exact:
-        text = "\n".join(exact_rows(a.reps, a.warmup) if a.exact else staged_gradient_rows(*a.staged, a.reps, a.warmup))
+    if a.staged or a.exact or a.long:
+        text = "\n".join(long_rows(a.reps, a.warmup) if a.long else
+                         exact_rows(a.reps, a.warmup) if a.exact else staged_gradient_rows(*a.staged, a.reps, a.warmup))
         print(text)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -59,6 +59,7 @@ SYMBOLS = [
     "hqpkkt_q_components", "hqpkkt_q_sparse_bfgs_update", "hqpkkt_q_sparse_bfgs_report",
     "hqpkkt_q_eigen_control", "hqpkkt_q_eigen_report", "hqpkkt_q_eigen_control_short",
     "hqpkkt_q_eigen_control_exact", "hqpkkt_q_eigen_control_long", "hqpkkt_lagrangian_gradient_staged",
+    "hqpkkt_debug_ip_vec", "hqpkkt_debug_ip_rows",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
 RCCL_SYMBOLS = ["hqpkkt_rccl_unique_id", "hqpkkt_rccl_create", "hqpkkt_rccl_create_from_env",
@@ -162,6 +163,15 @@ class RowsCase(C.Structure):
     """hqpkkt_rows_case (include/hqpkkt.h)"""
     _fields_ = [("nblocks", C.c_int)] + [(k, C.c_void_p) for k in ("rows", "cols", "ld", "col0", "off", "E")] + [("e_len", C.c_longlong), ("row_index", C.c_void_p),
                 ("n", C.c_int), ("m", C.c_int)] + [(k, C.c_void_p) for k in ("x", "t", "tz", "zw", "r3", "y", "dz", "dw", "xc")]
+
+
+class IpCase(C.Structure):
+    """hqpkkt_ip_case (include/hqpkkt.h)"""
+    _fields_ = [(k, C.c_int) for k in ("op", "form", "n", "me", "m", "ops", "epi", "inplace")] + \
+               [(k, C.c_double) for k in ("alpha", "mu", "sum", "gamma", "gammaf", "smm", "p0", "p1")] + \
+               [(k, C.c_void_p) for k in ("x", "y", "z", "w", "dx", "dy", "dz", "dw", "c", "b", "d", "part_in", "Bk_in", "S_in",
+                                          "ox", "oy", "oz", "ow", "r1", "r2", "r3", "r4")] + \
+               [("out", C.c_double * 8), ("Bk", C.c_double * 12), ("S", C.c_double * 8)]
 
 
 class GemmCaps(C.Structure):
@@ -310,6 +320,8 @@ def lib():
     L.hqpkkt_debug_symv_batch.argtypes = [C.c_int, C.c_int, C.POINTER(GemvCase), vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_int]
     L.hqpkkt_debug_symv_map.restype = C.c_longlong
     L.hqpkkt_debug_symv_map.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_longlong]
+    L.hqpkkt_debug_ip_vec.argtypes = [C.c_int, C.POINTER(IpCase)]
+    L.hqpkkt_debug_ip_rows.argtypes = [vp, C.c_int, C.POINTER(IpCase)]
     L.hqpkkt_debug_solve_top_stamps.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_debug_factor_block.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 7
     _lib = L

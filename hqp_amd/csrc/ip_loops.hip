@@ -2,6 +2,9 @@
 // ipdriver.hip.h): they drive the handle through hqpkkt_factor / hqpkkt_solve and the posted read-backs.
 #include "hqpkkt_handle.hpp"
 
+#include <algorithm>
+#include <limits>
+
 #include "ipdriver.hip.h"
 
 // The attempts of a device-resident loop (hqpkkt_mehrotra / hqpkkt_franke; `loop` reads the caller's `opts` through the
@@ -70,6 +73,141 @@ enum : int {
 static_assert(IP_SUM == 0, "the slots a pattern leaves out are sums");
 constexpr IpOps OPS_SUM{}, OPS_HEAD{{IP_SUM, IP_SUM, IP_SUM, IP_MAX, IP_MIN, IP_MIN}}, OPS_COLD{{IP_MIN, IP_MIN, IP_MAX, IP_MAX}},
     OPS_MIN_MAX{{IP_MIN, IP_MAX}}, OPS_MIN{{IP_MIN}}, OPS_SUM_MAX{{IP_SUM, IP_MAX}};
+
+// ---- The launch groups of the loops' vector work: the stream, the sizes and device pointers in, launches out.  The loops
+// below and the test hooks at the end of this file (hqpkkt_debug_ip_vec, hqpkkt_debug_ip_rows) call the same functions.
+constexpr IpEpi EPI_NONE{0, 0, 0.0, 0.0, 0.0, nullptr, nullptr};
+void ip_final_launch(hipStream_t s, const double *part, const IpOps &ops, double *out, const IpEpi &epi = EPI_NONE) {
+  k_ip_final<<<1, 256, 0, s>>>(part, ops, out, epi);
+}
+// predictor statistics: ratio test, Terlaky's sigma, the corrector's r4.  small: one workgroup, mu = *zw_sum / m on the
+// device; else three launches with the host's mu
+void ip_pred_launch(hipStream_t s, bool small, int m, const double *z, const double *w, const double *dza, const double *dwa,
+                    const double *zw_sum, double mu, double gamma, double *part, double *out, double *S, double *r4) {
+  if (small) {
+    k_ip_pred_small<<<1, 1024, 0, s>>>(m, z, w, dza, dwa, zw_sum, gamma, S, r4);
+  } else {
+    k_ip_ratio<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dza, dwa, part);
+    ip_final_launch(s, part, OPS_MIN_MAX, out, IpEpi{1, m, mu, gamma, 0.0, nullptr, S});
+    k_ip_corr_rhs<<<nblk(m), 256, 0, s>>>(m, z, w, dza, dwa, 0.0, S + IPS_SMM, r4);
+  }
+}
+// the step: blocking components, the damped step length, the update.  small: one workgroup; else five launches
+void ip_step_launch(hipStream_t s, bool small, int n, int me, int m, double *x, double *y, double *z, double *w, const double *dx,
+                    const double *dy, const double *dz, const double *dw, double *part, double *out, double *Bk, double gamma,
+                    double gammaf, double *S) {
+  if (small) {
+    k_ip_step_small<<<1, 1024, 0, s>>>(n, me, m, x, y, z, w, dx, dy, dz, dw, Bk, gamma, gammaf, S);
+  } else {
+    k_ip_minratio_part<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
+    k_ip_minratio_final<<<1, 256, 0, s>>>(part, z, w, dz, dw, Bk, m, gamma, S);
+    k_ip_mupl<<<IP_BLOCKS, 256, 0, s>>>(m, 0.0, S + IPS_ALPHA_PRE, z, w, dz, dw, part);
+    ip_final_launch(s, part, OPS_SUM, out, IpEpi{2, m, 0.0, 0.0, gammaf, Bk, S});
+    k_ip_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, 0.0, S + IPS_ALPHA, x, y, z, w, dx, dy, dz, dw, part);
+  }
+}
+// corrector right-hand side with the host's sigma mu
+void ip_corr_rhs_launch(hipStream_t s, int m, const double *z, const double *w, const double *dza, const double *dwa, double smm,
+                        double *r4) {
+  k_ip_corr_rhs<<<nblk(m), 256, 0, s>>>(m, z, w, dza, dwa, smm, nullptr, r4);
+}
+// blocking components without the step's scalars
+void ip_blocking_launch(hipStream_t s, int m, const double *z, const double *w, const double *dz, const double *dw, double *part,
+                        double *Bk) {
+  k_ip_minratio_part<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
+  k_ip_minratio_final<<<1, 256, 0, s>>>(part, z, w, dz, dw, Bk, m, 0.0, nullptr);
+}
+// (z + alpha dz)'(w + alpha dw) and the update with the host's alpha: partials
+void ip_mupl_launch(hipStream_t s, int m, double alpha, const double *z, const double *w, const double *dz, const double *dw,
+                    double *part) {
+  k_ip_mupl<<<IP_BLOCKS, 256, 0, s>>>(m, alpha, nullptr, z, w, dz, dw, part);
+}
+void ip_update_launch(hipStream_t s, int n, int me, int m, double alpha, double *x, double *y, double *z, double *w, const double *dx,
+                      const double *dy, const double *dz, const double *dw, double *part) {
+  k_ip_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, alpha, nullptr, x, y, z, w, dx, dy, dz, dw, part);
+}
+// the CSR blocks a walk over the rows needs, and the STAGED engine's shares (IpRun::dx1 .. dxq)
+struct IpBlocks {
+  CsrDev Q, AT, CT, A, C;
+  const double *vals;
+  const double *x1 = nullptr, *x2 = nullptr;
+  int ndyn = 0;
+  const double *xq = nullptr;
+};
+// right-hand sides and the partials of the convergence sums; lpr4: 4 lanes per CSR row, else 16
+void ip_rhs_launch(hipStream_t s, bool lpr4, int n, int me, int m, const IpBlocks &B, const double *c, const double *b,
+                   const double *d, const double *x, const double *y, const double *z, const double *w, double *t1, double *t2,
+                   double *t3, double *r4, double *part) {
+  if (lpr4)
+    k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, B.Q, B.AT, B.CT, B.A, B.C, B.vals, c, b, d, x, y, z, w, t1, t2, t3, r4, part, B.x1, B.x2,
+                                          B.ndyn, B.xq);
+  else
+    k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, B.Q, B.AT, B.CT, B.A, B.C, B.vals, c, b, d, x, y, z, w, t1, t2, t3, r4, part, B.x1, B.x2,
+                                           B.ndyn, B.xq);
+}
+// the cold starts
+void ip_cold_rhs_launch(hipStream_t s, int n, int me, int m, const double *c, const double *b, const double *d, double *z, double *w,
+                        double *r1, double *r2, double *r3, double *r4, double w0, double r40) {
+  k_ip_cold_rhs<<<nblk(n + me + m), 256, 0, s>>>(n, me, m, c, b, d, z, w, r1, r2, r3, r4, w0, r40);
+}
+void ip_cold_stats_launch(hipStream_t s, int m, const double *dz, const double *dw, double *part) {
+  k_ip_cold_stats<<<IP_BLOCKS, 256, 0, s>>>(m, dz, dw, part);
+}
+void ip_shift_launch(hipStream_t s, int m, const double *dz, const double *dw, double delz, double delw, double *z, double *w) {
+  k_ip_shift<<<nblk(m), 256, 0, s>>>(m, dz, dw, delz, delw, z, w);
+}
+void ip_fill_launch(hipStream_t s, int m, double v, double *x) { k_ip_fill<<<nblk(m), 256, 0, s>>>(m, v, x); }
+void fr_dstats_launch(hipStream_t s, int m, const double *d, double *part) { k_fr_dstats<<<IP_BLOCKS, 256, 0, s>>>(m, d, part); }
+void fr_cold_launch(hipStream_t s, bool lpr4, int n, int me, int m, CsrDev CT, double Ltilde, const double *c, const double *b,
+                    const double *d, double *x, double *y, double *z, double *w, double *a1, double *a2, double *a3, double *part) {
+  if (lpr4)
+    k_fr_cold<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, CT, Ltilde, c, b, d, x, y, z, w, a1, a2, a3, part);
+  else
+    k_fr_cold<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, CT, Ltilde, c, b, d, x, y, z, w, a1, a2, a3, part);
+}
+// Franke's ratio test and step length min(1, beta ratio) into S[IPS_ALPHA]
+void fr_ratio_launch(hipStream_t s, int m, const double *z, const double *w, const double *dz, const double *dw, double beta,
+                     double *part, double *out, double *S) {
+  k_fr_ratio<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
+  ip_final_launch(s, part, OPS_MIN, out, IpEpi{3, m, 0.0, 0.0, beta, nullptr, S});
+}
+// Franke's update (alpha_dev, or the host's alpha where it is null) and its reduction
+void fr_update_launch(hipStream_t s, int n, int me, int m, double alpha, const double *alpha_dev, double *x, double *y, double *z,
+                      double *w, const double *dx, const double *dy, const double *dz, const double *dw, double *part, double *out) {
+  k_fr_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, alpha, alpha_dev, x, y, z, w, dx, dy, dz, dw, part);
+  ip_final_launch(s, part, OPS_SUM_MAX, out);
+}
+// Franke's right-hand sides; zm: the device's address of the two mapped host words zeta, mu
+void fr_rhs_launch(hipStream_t s, int n, int me, int m, const double *zm, const double *a1, const double *a2, const double *a3,
+                   const double *z, const double *w, double *r1, double *r2, double *r3, double *r4) {
+  k_fr_rhs<<<nblk(n + me + m), 256, 0, s>>>(n, me, m, zm, a1, a2, a3, z, w, r1, r2, r3, r4);
+}
+// The second corrector's HOST copy of Mehrotra's step rule (hqp/Hqp_IpsMehrotra.C:629-672; the device's copy is ip_alpha_pre /
+// ip_alpha_fin of ipdriver.hip.h - two implementations on purpose).  B: k_ip_minratio_final's 12 values.
+// alpha before the damping; *blocked: there is a blocking component
+double host_alpha_pre(const double *B, bool *blocked) {
+  const double zmin = B[0], wmin = B[6];
+  const int izmin = (int)B[1], iwmin = (int)B[7];
+  *blocked = !(izmin < 0 && iwmin < 0);
+  if (!*blocked) return 1.0;
+  return izmin < 0 ? wmin : iwmin < 0 ? zmin : std::fmin(zmin, wmin);
+}
+// the damped step from alpha and sum = (z + alpha dz)'(w + alpha dw)
+double host_alpha_fin(const double *B, double alpha, double sum, int m, double gammaf) {
+  const double zmin = B[0], wmin = B[6];
+  const int izmin = (int)B[1], iwmin = (int)B[7];
+  const double z_iz = B[2], dz_iz = B[3], w_iz = B[4], dw_iz = B[5];
+  const double z_iw = B[8], dz_iw = B[9], w_iw = B[10], dw_iw = B[11];
+  const double mu_pl = sum / m;
+  double fpd;
+  if (iwmin >= 0 && alpha == wmin && z_iw > -alpha * dz_iw)
+    fpd = (gammaf * mu_pl / (z_iw + alpha * dz_iw) - w_iw) / (alpha * dw_iw);
+  else if (izmin >= 0 && alpha == zmin && w_iz > -alpha * dw_iz)
+    fpd = (gammaf * mu_pl / (w_iz + alpha * dw_iz) - z_iz) / (alpha * dz_iz);
+  else
+    fpd = 0.0;
+  return std::fmax(0.0, std::fmin(std::fmax(1.0 - gammaf, fpd) * alpha, 1.0));
+}
 
 // One call of a device-resident loop: the handle, the caller's vectors, the loop's own vectors in h->kept.ipv, the
 // counters, and what both loops do with them.  Lives on the stack of the call.
@@ -199,18 +337,14 @@ struct IpRun {
     return staged_dense_products(h, vv, &dx1, &dx2, &dndyn, &dxq);
   }
   int reduce(const IpOps &ops, int nout) {
-    k_ip_final<<<1, 256, 0, s>>>(part, ops, out, IpEpi{0, 0, 0.0, 0.0, 0.0, nullptr, nullptr});
+    ip_final_launch(s, part, ops, out);
     const int e = post_words(h, out, nout);
     return e ? e : post_wait(h);
   }
   // the right-hand sides of the iterate (x, y, z, w) into t1..t3 and r4, their reductions into `part`
   void rhs(double *t1, double *t2, double *t3) {
-    if (h->short_rows)
-      k_ip_rhs<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
-                                            h->td.vals.p, c, b, d, x, y, z, w, t1, t2, t3, r4, part, dx1, dx2, dndyn, dxq);
-    else
-      k_ip_rhs<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(),
-                                             h->td.vals.p, c, b, d, x, y, z, w, t1, t2, t3, r4, part, dx1, dx2, dndyn, dxq);
+    const IpBlocks B{h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p, dx1, dx2, dndyn, dxq};
+    ip_rhs_launch(s, h->short_rows, n, me, m, B, c, b, d, x, y, z, w, t1, t2, t3, r4, part);
   }
   // A factorisation or solve that failed with E_SING: inside a hot start the hot start is thrown away
   // (hqp/Hqp_IpsMehrotra.C:723-727, hqp/Hqp_IpsFranke.C:405-411), otherwise the QP is Hqp_Degenerate
@@ -314,35 +448,35 @@ struct Mehrotra : IpRun {
       double w0 = 1.0;
       if (o.init_method == 1) w0 = std::fmax(o.norm_d, 1e-10) * o.norm_Q / o.norm_C;
       if (o.init_method == 2) w0 = o.norm_C / std::fmax(o.norm_d, 1e-10) / o.norm_Q;
-      k_ip_cold_rhs<<<nblk(n + me + m), 256, 0, s>>>(n, me, m, c, b, d, z, w, r1, r2, r3, r4, w0, o.init_method ? -w0 : 0.0);
+      ip_cold_rhs_launch(s, n, me, m, c, b, d, z, w, r1, r2, r3, r4, w0, o.init_method ? -w0 : 0.0);
       if ((e = factor()) || (e = solve(dx, dy, dz, dw))) return failed(e);  // E_SING: Hqp_Degenerate (:262-269)
       HIPCHK(hipMemcpyAsync(x, dx, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
       if (me) HIPCHK(hipMemcpyAsync(y, dy, sizeof(double) * me, hipMemcpyDeviceToDevice, s));
-      if (o.init_method == 3) k_ip_shift<<<nblk(m), 256, 0, s>>>(m, dz, dw, 1.0, 1.0, dz, dw);  // :294-297
-      k_ip_cold_stats<<<IP_BLOCKS, 256, 0, s>>>(m, dz, dw, part);
+      if (o.init_method == 3) ip_shift_launch(s, m, dz, dw, 1.0, 1.0, dz, dw);  // :294-297
+      ip_cold_stats_launch(s, m, dz, dw, part);
       if ((e = reduce(OPS_COLD, 6))) return e;
       double mindz = hout[0], mindw = hout[1], sumdz = hout[4], sumdw = hout[5];
       if (hout[2] == 0.0) {  // :301-304
-        k_ip_fill<<<nblk(m), 256, 0, s>>>(m, 1.0e-10, dz);
+        ip_fill_launch(s, m, 1.0e-10, dz);
         mindz = 1.0e-10, sumdz = 1.0e-10 * m;
       }
       if (hout[3] == 0.0) {
-        k_ip_fill<<<nblk(m), 256, 0, s>>>(m, 1.0e-10, dw);
+        ip_fill_launch(s, m, 1.0e-10, dw);
         mindw = 1.0e-10, sumdw = 1.0e-10 * m;
       }
       double delz = std::fmax(-1.5 * mindz, 0.0), delw = std::fmax(-1.5 * mindw, 0.0);
       // gap = (dz + delz)'(dw + delw): k_ip_mupl with alpha = 1 on (delz, dz), (delw, dw) shifted vectors
-      k_ip_shift<<<nblk(m), 256, 0, s>>>(m, dz, dw, delz, delw, z, w);
-      k_ip_mupl<<<IP_BLOCKS, 256, 0, s>>>(m, 0.0, nullptr, z, w, dz, dw, part);
+      ip_shift_launch(s, m, dz, dw, delz, delw, z, w);
+      ip_mupl_launch(s, m, 0.0, z, w, dz, dw, part);
       if ((e = reduce(OPS_SUM, 1))) return e;
       const double gap0 = hout[0];
       delz += 0.5 * gap0 / (sumdw + m * delw);
       delw += 0.5 * gap0 / (sumdz + m * delz);
-      k_ip_shift<<<nblk(m), 256, 0, s>>>(m, dz, dw, delz, delw, z, w);
+      ip_shift_launch(s, m, dz, dw, delz, delw, z, w);
     }
     if (keep_hot) {  // :318-319
-      k_ip_fill<<<nblk(m), 256, 0, s>>>(m, 1.0, zh);
-      k_ip_fill<<<nblk(m), 256, 0, s>>>(m, 1.0, wh);
+      ip_fill_launch(s, m, 1.0, zh);
+      ip_fill_launch(s, m, 1.0, wh);
     }
     return GO_ON;
   }
@@ -359,13 +493,13 @@ struct Mehrotra : IpRun {
   int enqueue_head() {
     rhs(r1, r2, r3);
     if (m == 0) return 0;
-    k_ip_final<<<1, 256, 0, s>>>(part, OPS_HEAD, out, IpEpi{0, 0, 0.0, 0.0, 0.0, nullptr, nullptr});
+    ip_final_launch(s, part, OPS_HEAD, out);
     return post_words(h, out, 40);
   }
   int equality_step() {  // equality-constrained QP: one Newton step (:364-413)
     int e;
     if ((e = factor()) || (e = solve(dx, dy, dz, dw))) return failed(e);
-    k_ip_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, 1.0, nullptr, x, y, z, w, dx, dy, dz, dw, part);
+    ip_update_launch(s, n, me, m, 1.0, x, y, z, w, dx, dy, dz, dw, part);
     iter++;
     result = 0;
     return FINISH;
@@ -458,7 +592,7 @@ struct Mehrotra : IpRun {
     if (seg_ok) {
       h->defer_residual = true;
       e = graphed(h, seg_slot(2), [&]() {
-        k_ip_pred_small<<<1, 1024, 0, s>>>(m, z, w, dza, dwa, out + 2, gamma, S, r4);
+        ip_pred_launch(s, true, m, z, w, dza, dwa, out + 2, mu, gamma, part, out, S, r4);
         return hqpkkt_solve(h, z, w, r1, r2, r3, r4, dx, dy, dz, dw, &resid);
       });
       h->defer_residual = false;
@@ -468,13 +602,8 @@ struct Mehrotra : IpRun {
         e = finish_solve(dx, dy, dz, dw);
       }
     } else {
-      if (ip_small) {  // one workgroup: the three launches below, same arithmetic (ipdriver.hip.h)
-        k_ip_pred_small<<<1, 1024, 0, s>>>(m, z, w, dza, dwa, out + 2, gamma, S, r4);
-      } else {
-        k_ip_ratio<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dza, dwa, part);
-        k_ip_final<<<1, 256, 0, s>>>(part, OPS_MIN_MAX, out, IpEpi{1, m, mu, gamma, 0.0, nullptr, S});
-        k_ip_corr_rhs<<<nblk(m), 256, 0, s>>>(m, z, w, dza, dwa, 0.0, S + IPS_SMM, r4);
-      }
+      // ip_small: one workgroup for the three launches of the separate form, same arithmetic (ipdriver.hip.h)
+      ip_pred_launch(s, ip_small, m, z, w, dza, dwa, out + 2, mu, gamma, part, out, S, r4);
       e = solve(dx, dy, dz, dw);
     }
     return e ? failed(e) : GO_ON;
@@ -483,20 +612,13 @@ struct Mehrotra : IpRun {
   int take_step() {
     if (seg_ok) {
       const int e = graphed(h, seg_slot(3), [&]() {
-        k_ip_step_small<<<1, 1024, 0, s>>>(n, me, m, x, y, z, w, dx, dy, dz, dw, Bk, gamma, o.gammaf, S);
+        ip_step_launch(s, true, n, me, m, x, y, z, w, dx, dy, dz, dw, part, out, Bk, gamma, o.gammaf, S);
         return enqueue_head();
       });
       if (e) return e;
       head_in_stream = true;
-    } else if (ip_small) {  // one workgroup: the five launches below, same arithmetic
-      k_ip_step_small<<<1, 1024, 0, s>>>(n, me, m, x, y, z, w, dx, dy, dz, dw, Bk, gamma, o.gammaf, S);
-    } else {
-      k_ip_minratio_part<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
-      k_ip_minratio_final<<<1, 256, 0, s>>>(part, z, w, dz, dw, Bk, m, gamma, S);
-      k_ip_mupl<<<IP_BLOCKS, 256, 0, s>>>(m, 0.0, S + IPS_ALPHA_PRE, z, w, dz, dw, part);
-      k_ip_final<<<1, 256, 0, s>>>(part, OPS_SUM, out, IpEpi{2, m, 0.0, 0.0, o.gammaf, Bk, S});
-      k_ip_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, 0.0, S + IPS_ALPHA, x, y, z, w, dx, dy, dz, dw, part);
-    }
+    } else  // ip_small: one workgroup for the five launches of the separate form, same arithmetic
+      ip_step_launch(s, ip_small, n, me, m, x, y, z, w, dx, dy, dz, dw, part, out, Bk, gamma, o.gammaf, S);
     // (:684-690: a non-finite mu or x ends the solve as degenerate; seen here by the next
     // pass through k_ip_rhs, whose sums and maximum carry the NaN / inf)
     iter++;
@@ -508,35 +630,22 @@ struct Mehrotra : IpRun {
   int second_corrector(double mu_) {
     int e;
     const double smm = gamma / (1.0 - gamma) * mu_;
-    k_ip_corr_rhs<<<nblk(m), 256, 0, s>>>(m, z, w, dza, dwa, smm, nullptr, r4);
+    ip_corr_rhs_launch(s, m, z, w, dza, dwa, smm, r4);
     if ((e = solve(dx, dy, dz, dw))) return e;
-    k_ip_minratio_part<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
-    k_ip_minratio_final<<<1, 256, 0, s>>>(part, z, w, dz, dw, Bk, m, gamma, nullptr);
+    ip_blocking_launch(s, m, z, w, dz, dw, part, Bk);
     HIPCHK(hipMemcpyAsync(hout, Bk, sizeof(double) * 12, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const double zmin = hout[0], wmin = hout[6];
-    const int izmin = (int)hout[1], iwmin = (int)hout[7];
-    const double z_iz = hout[2], dz_iz = hout[3], w_iz = hout[4], dw_iz = hout[5];
-    const double z_iw = hout[8], dz_iw = hout[9], w_iw = hout[10], dw_iw = hout[11];
-    double alpha;
-    if (izmin < 0 && iwmin < 0)
-      alpha = 1.0;
-    else {
-      alpha = izmin < 0 ? wmin : iwmin < 0 ? zmin : std::fmin(zmin, wmin);
-      k_ip_mupl<<<IP_BLOCKS, 256, 0, s>>>(m, alpha, nullptr, z, w, dz, dw, part);
+    double B[12];  // (hout is written again by the reduction below)
+    std::copy(hout, hout + 12, B);
+    bool blocked;
+    double alpha = host_alpha_pre(B, &blocked);
+    if (blocked) {
+      ip_mupl_launch(s, m, alpha, z, w, dz, dw, part);
       if ((e = reduce(OPS_SUM, 1))) return e;
-      const double mu_pl = hout[0] / m;
-      double fpd;
-      if (iwmin >= 0 && alpha == wmin && z_iw > -alpha * dz_iw)
-        fpd = (o.gammaf * mu_pl / (z_iw + alpha * dz_iw) - w_iw) / (alpha * dw_iw);
-      else if (izmin >= 0 && alpha == zmin && w_iz > -alpha * dw_iz)
-        fpd = (o.gammaf * mu_pl / (w_iz + alpha * dw_iz) - z_iz) / (alpha * dz_iz);
-      else
-        fpd = 0.0;
-      alpha = std::fmax(0.0, std::fmin(std::fmax(1.0 - o.gammaf, fpd) * alpha, 1.0));
+      alpha = host_alpha_fin(B, alpha, hout[0], m, o.gammaf);
     }
     res->alpha = alpha;
-    k_ip_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, alpha, nullptr, x, y, z, w, dx, dy, dz, dw, part);
+    ip_update_launch(s, n, me, m, alpha, x, y, z, w, dx, dy, dz, dw, part);
     return 0;
   }
   // before leaving the loop with a step still in the stream: was it taken?
@@ -605,7 +714,7 @@ struct Franke : IpRun {
   // hot_start (:222-266): x, y, z, w of the last solve, w += 1e-10, the slack vectors a1..a3 of that point
   int hot_start() {
     int e;
-    k_ip_shift<<<nblk(m), 256, 0, s>>>(m, z, w, 0.0, 1e-10, z, w);
+    ip_shift_launch(s, m, z, w, 0.0, 1e-10, z, w);
     if ((e = dyn_products())) return e;
     rhs(a1(), a2(), a3());
     if ((e = reduce(OPS_SUM, 3))) return e;
@@ -617,7 +726,7 @@ struct Franke : IpRun {
     int e;
     if (m > 0) {
       rhomin = 1000.0 * m;
-      k_fr_dstats<<<IP_BLOCKS, 256, 0, s>>>(m, d, part);
+      fr_dstats_launch(s, m, d, part);
       if ((e = reduce(OPS_MIN_MAX, 3))) return e;
       const double min_d = hout[0], norm_d = hout[1];
       if (o.qp_mu0 > 0.0) {  // "choose Ltilde according _mu0" (:167-173)
@@ -629,10 +738,7 @@ struct Franke : IpRun {
         Ltilde = std::fmax(Ltilde, 1e2 * m);
       }
     }
-    if (h->short_rows)
-      k_fr_cold<4><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.CT.dev(), Ltilde, c, b, d, x, y, z, w, a1(), a2(), a3(), part);
-    else
-      k_fr_cold<16><<<IP_BLOCKS, 256, 0, s>>>(n, me, m, h->td.CT.dev(), Ltilde, c, b, d, x, y, z, w, a1(), a2(), a3(), part);
+    fr_cold_launch(s, h->short_rows, n, me, m, h->td.CT.dev(), Ltilde, c, b, d, x, y, z, w, a1(), a2(), a3(), part);
     gap = 0.0;
     if (m > 0) {
       if ((e = reduce(OPS_SUM, 1))) return e;
@@ -658,12 +764,8 @@ struct Franke : IpRun {
   }
   // step length, update, the new gap and the post of the iteration's scalars
   int take_step_enqueue() {
-    if (m > 0) {
-      k_fr_ratio<<<IP_BLOCKS, 256, 0, s>>>(m, z, w, dz, dw, part);
-      k_ip_final<<<1, 256, 0, s>>>(part, OPS_MIN, out, IpEpi{3, m, 0.0, 0.0, beta, nullptr, S});
-    }
-    k_fr_update<<<IP_BLOCKS, 256, 0, s>>>(n, me, m, 1.0, m > 0 ? S + IPS_ALPHA : nullptr, x, y, z, w, dx, dy, dz, dw, part);
-    k_ip_final<<<1, 256, 0, s>>>(part, OPS_SUM_MAX, out, IpEpi{0, 0, 0.0, 0.0, 0.0, nullptr, nullptr});
+    if (m > 0) fr_ratio_launch(s, m, z, w, dz, dw, beta, part, out, S);
+    fr_update_launch(s, n, me, m, 1.0, m > 0 ? S + IPS_ALPHA : nullptr, x, y, z, w, dx, dy, dz, dw, part, out);
     return post_words(h, out, 40);  // (the residual of the solve has gone to the host with the post behind its kernel)
   }
   int take_step() {
@@ -671,7 +773,7 @@ struct Franke : IpRun {
     return e ? e : post_wait(h);
   }
   void fr_rhs() {
-    k_fr_rhs<<<nblk(n + me + m), 256, 0, s>>>(n, me, m, h->kept.hpin.dev + HPIN_ZM, a1(), a2(), a3(), z, w, r1, r2, r3, r4);
+    fr_rhs_launch(s, n, me, m, h->kept.hpin.dev + HPIN_ZM, a1(), a2(), a3(), z, w, r1, r2, r3, r4);
   }
   // The whole step - right-hand sides, factorisation, solve, its residual, the step length, the update, the new gap,
   // both posts - as ONE captured graph (the launches take nothing from the host that changes from step to step)
@@ -788,9 +890,216 @@ struct Franke : IpRun {
     return result == 0 || result == 3 || result == 4 ? LEAVE : GO_ON;
   }
 };
+
+// ---- the test hooks of the launch groups (include/hqpkkt.h, hqpkkt_debug_ip_vec / hqpkkt_debug_ip_rows)
+constexpr int IPD_GUARD = 64;
+constexpr unsigned long long IPD_MARK = 0x7ff8c0de5eed1234ULL;  // a NaN no arithmetic produces
+// a vector of a case on the device: its n entries (the caller's, or NaN) and the marks behind them
+struct IpDebugVec {
+  DBuf<double> d;
+  long long n = 0;
+  int up(const double *p, long long n_) {
+    n = n_;
+    double mark;
+    std::memcpy(&mark, &IPD_MARK, sizeof(mark));
+    std::vector<double> v((size_t)(n + IPD_GUARD), mark);
+    if (p)
+      std::copy(p, p + n, v.begin());
+    else
+      std::fill(v.begin(), v.begin() + n, std::numeric_limits<double>::quiet_NaN());
+    return d.upload(v);
+  }
+  // the entries into p (may be null); HQPKKT_E_INTERN where a mark has changed
+  int down(double *p, long long k = -1) {
+    std::vector<double> back((size_t)(n + IPD_GUARD));
+    HIPCHK(hipMemcpy(back.data(), d.p, sizeof(double) * back.size(), hipMemcpyDeviceToHost));
+    if (p) std::copy(back.begin(), back.begin() + (k < 0 ? n : k), p);
+    for (long long i = n; i < n + IPD_GUARD; i++) {
+      unsigned long long b;
+      std::memcpy(&b, &back[(size_t)i], sizeof(b));
+      if (b != IPD_MARK) return HQPKKT_E_INTERN;
+    }
+    return 0;
+  }
+};
+// everything a case can name, on the device
+struct IpDebugBufs {
+  IpDebugVec x, y, z, w, dx, dy, dz, dw, c, b, d, r1, r2, r3, r4, oz, ow, part, out;  // out: 64 doubles as IpRun's (Bk at 16, S at 32)
+  double *Bk() const { return out.d.p + 16; }
+  double *S() const { return out.d.p + 32; }
+  int up(const hqpkkt_ip_case &k, bool want_part_in) {
+    const int n = k.n, me = k.me, m = k.m;
+    int e;
+    if ((e = x.up(k.x, n)) || (e = y.up(k.y, me)) || (e = z.up(k.z, m)) || (e = w.up(k.w, m)) || (e = dx.up(k.dx, n)) || (e = dy.up(k.dy, me)) ||
+        (e = dz.up(k.dz, m)) || (e = dw.up(k.dw, m)) || (e = c.up(k.c, n)) || (e = b.up(k.b, me)) || (e = d.up(k.d, m)) || (e = r1.up(nullptr, n)) ||
+        (e = r2.up(nullptr, me)) || (e = r3.up(nullptr, m)) || (e = r4.up(nullptr, m)) || (e = oz.up(nullptr, m)) || (e = ow.up(nullptr, m)) ||
+        (e = part.up(want_part_in ? k.part_in : nullptr, (long long)IP_BLOCKS * IP_SLOTS)))
+      return e;
+    std::vector<double> o(64, std::numeric_limits<double>::quiet_NaN());
+    if (k.Bk_in) std::copy(k.Bk_in, k.Bk_in + 12, o.begin() + 16);
+    if (k.S_in) std::copy(k.S_in, k.S_in + 8, o.begin() + 32);
+    return out.up(o.data(), 64);
+  }
+  // results back: which of x .. w the op has written in place (xyzw), or into oz / ow (zw_out); every mark is looked at
+  int down(hqpkkt_ip_case &k, bool xyzw, bool zw_out, bool zw_inplace) {
+    int e = 0, e2;
+    auto keep = [&](int code) { if (code && !e) e = code; };
+    keep(x.down(xyzw ? k.ox : nullptr)), keep(y.down(xyzw ? k.oy : nullptr));
+    keep(z.down(xyzw ? k.oz : nullptr)), keep(w.down(xyzw ? k.ow : nullptr));
+    keep(dx.down(nullptr)), keep(dy.down(nullptr)), keep(dz.down(zw_inplace ? k.oz : nullptr)), keep(dw.down(zw_inplace ? k.ow : nullptr));
+    keep(c.down(nullptr)), keep(b.down(nullptr)), keep(d.down(nullptr));
+    keep(r1.down(k.r1)), keep(r2.down(k.r2)), keep(r3.down(k.r3)), keep(r4.down(k.r4));
+    keep(oz.down(zw_out ? k.oz : nullptr)), keep(ow.down(zw_out ? k.ow : nullptr)), keep(part.down(nullptr));
+    std::vector<double> o(64);
+    e2 = out.down(o.data());
+    keep(e2);
+    std::copy(o.begin(), o.begin() + 8, k.out), std::copy(o.begin() + 16, o.begin() + 28, k.Bk), std::copy(o.begin() + 32, o.begin() + 40, k.S);
+    return e;
+  }
+};
+bool ip_debug_need(const hqpkkt_ip_case &k, bool xyzw, bool d4, bool cbd) {
+  const int n = k.n, me = k.me, m = k.m;
+  if (xyzw && ((n && (!k.x || !k.dx)) || (me && (!k.y || !k.dy)))) return false;
+  if ((xyzw || d4) && m && (!k.z || !k.w || !k.dz || !k.dw)) return false;
+  if (cbd && ((n && !k.c) || (me && !k.b) || (m && !k.d))) return false;
+  return true;
+}
+
+int debug_ip_vec(int device, hqpkkt_ip_case *k) {
+  static const IpOps patterns[6] = {OPS_SUM, OPS_HEAD, OPS_COLD, OPS_MIN_MAX, OPS_MIN, OPS_SUM_MAX};
+  if (!k) return HQPKKT_E_NULL;
+  const int op = k->op, n = k->n, me = k->me, m = k->m;
+  if (op < 0 || op > 15 || n < 0 || me < 0 || m < 0 || k->form < 0 || k->form > 1 || (k->form && op > 1)) return HQPKKT_E_RANGE;
+  const bool small = k->form == 1, total_op = op == 5 || op == 6 || op == 12 || op == 13;
+  if ((long long)n + me + m > 0x7fffffffLL - 65536) return HQPKKT_E_RANGE;
+  if (small && (m > IP_SMALL_M || (long long)n + me + m > 4 * IP_SMALL_M)) return HQPKKT_E_RANGE;
+  // (no empty grid, and nothing the loops never launch: m = 0 only where they launch with it)
+  if (op != 14 && (total_op ? ((op == 6 || op == 13) && n + me + m == 0) : m == 0)) return HQPKKT_E_RANGE;
+  if (op == 6 && m == 0) return HQPKKT_E_RANGE;
+  if (op == 14 && (k->ops < 0 || k->ops > 5 || k->epi < 0 || k->epi > 3 || !k->part_in)) return k->part_in ? HQPKKT_E_RANGE : HQPKKT_E_NULL;
+  if (op == 14 && ((k->epi == 2 && (!k->Bk_in || !k->S_in)) || (k->epi && m <= 0))) return HQPKKT_E_NULL;
+  const bool xyzw = op == 1 || op == 5 || op == 12, d4 = op <= 4 || op == 11, cbd = op == 6 || op == 13;
+  if (!ip_debug_need(*k, xyzw, d4, cbd) || (op == 1 && !k->S_in) || (op == 12 && m > 0 && !k->S_in) || (op == 15 && !k->Bk_in)) return HQPKKT_E_NULL;
+  if ((op == 7 || op == 8) && (!k->dz || !k->dw)) return HQPKKT_E_NULL;
+  if ((op == 10 && !k->d) || (op == 13 && m && (!k->z || !k->w))) return HQPKKT_E_NULL;
+  if (op == 15) {  // the host's copy of the step rule: no device
+    for (double &v : k->S) v = std::numeric_limits<double>::quiet_NaN();
+    bool blocked;
+    double alpha = host_alpha_pre(k->Bk_in, &blocked);
+    k->S[IPS_ALPHA_PRE] = alpha, k->S[IPS_DAMP] = blocked ? 1.0 : 0.0;
+    if (blocked) alpha = host_alpha_fin(k->Bk_in, alpha, k->sum, m, k->gammaf);
+    k->S[IPS_ALPHA] = alpha;
+    return 0;
+  }
+  int e;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return HQPKKT_E_DEVICE;
+  HIPCHK(hipSetDevice(device));
+  IpDebugBufs B;
+  if ((e = B.up(*k, op == 14))) return e;
+  hipStream_t s = nullptr;
+  double *part = B.part.d.p, *out = B.out.d.p, *Bk = B.Bk(), *S = B.S();
+  PinnedBuf<double> zm;
+  bool zw_out = false, zw_inplace = false;
+  switch (op) {
+    case 0: {
+      const double mu = k->sum / m;  // (the division read_head makes with the word it read back)
+      HIPCHK(hipMemcpy(out + 2, &k->sum, sizeof(double), hipMemcpyHostToDevice));
+      ip_pred_launch(s, small, m, B.z.d.p, B.w.d.p, B.dz.d.p, B.dw.d.p, out + 2, mu, k->gamma, part, out, S, B.r4.d.p);
+      break;
+    }
+    case 1:
+      ip_step_launch(s, small, n, me, m, B.x.d.p, B.y.d.p, B.z.d.p, B.w.d.p, B.dx.d.p, B.dy.d.p, B.dz.d.p, B.dw.d.p, part, out, Bk, k->gamma,
+                     k->gammaf, S);
+      break;
+    case 2: ip_corr_rhs_launch(s, m, B.z.d.p, B.w.d.p, B.dz.d.p, B.dw.d.p, k->smm, B.r4.d.p); break;
+    case 3: ip_blocking_launch(s, m, B.z.d.p, B.w.d.p, B.dz.d.p, B.dw.d.p, part, Bk); break;
+    case 4:
+      ip_mupl_launch(s, m, k->alpha, B.z.d.p, B.w.d.p, B.dz.d.p, B.dw.d.p, part);
+      ip_final_launch(s, part, OPS_SUM, out);
+      break;
+    case 5:
+      ip_update_launch(s, n, me, m, k->alpha, B.x.d.p, B.y.d.p, B.z.d.p, B.w.d.p, B.dx.d.p, B.dy.d.p, B.dz.d.p, B.dw.d.p, part);
+      ip_final_launch(s, part, OPS_SUM_MAX, out);
+      break;
+    case 6:
+      ip_cold_rhs_launch(s, n, me, m, B.c.d.p, B.b.d.p, B.d.d.p, B.oz.d.p, B.ow.d.p, B.r1.d.p, B.r2.d.p, B.r3.d.p, B.r4.d.p, k->p0, k->p1);
+      zw_out = true;
+      break;
+    case 7:
+      ip_cold_stats_launch(s, m, B.dz.d.p, B.dw.d.p, part);
+      ip_final_launch(s, part, OPS_COLD, out);
+      break;
+    case 8:
+      if (k->inplace)
+        ip_shift_launch(s, m, B.dz.d.p, B.dw.d.p, k->p0, k->p1, B.dz.d.p, B.dw.d.p), zw_inplace = true;
+      else
+        ip_shift_launch(s, m, B.dz.d.p, B.dw.d.p, k->p0, k->p1, B.oz.d.p, B.ow.d.p), zw_out = true;
+      break;
+    case 9: ip_fill_launch(s, m, k->p0, B.oz.d.p), zw_out = true; break;
+    case 10:
+      fr_dstats_launch(s, m, B.d.d.p, part);
+      ip_final_launch(s, part, OPS_MIN_MAX, out);
+      break;
+    case 11: fr_ratio_launch(s, m, B.z.d.p, B.w.d.p, B.dz.d.p, B.dw.d.p, k->gammaf, part, out, S); break;
+    case 12:
+      fr_update_launch(s, n, me, m, k->alpha, m > 0 ? S + IPS_ALPHA : nullptr, B.x.d.p, B.y.d.p, B.z.d.p, B.w.d.p, B.dx.d.p, B.dy.d.p, B.dz.d.p,
+                       B.dw.d.p, part, out);
+      break;
+    case 13:
+      if (zm.alloc(2, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || zm.map() != hipSuccess) return HQPKKT_E_MEM;
+      zm.p[0] = k->p0, zm.p[1] = k->p1;
+      std::atomic_thread_fence(std::memory_order_release);
+      fr_rhs_launch(s, n, me, m, zm.dev, B.c.d.p, B.b.d.p, B.d.d.p, B.z.d.p, B.w.d.p, B.r1.d.p, B.r2.d.p, B.r3.d.p, B.r4.d.p);
+      break;
+    case 14: ip_final_launch(s, part, patterns[k->ops], out, IpEpi{k->epi, m, k->mu, k->gamma, k->gammaf, Bk, S}); break;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return B.down(*k, xyzw, zw_out, zw_inplace);
+}
+
+int debug_ip_rows(hqpkkt_t *h, int lpr, hqpkkt_ip_case *k) {
+  if (!h || !k) return HQPKKT_E_NULL;
+  if (!h->analyzed || !h->have_values) return HQPKKT_E_INTERN;
+  if (h->opts.mode == HQPKKT_MODE_STAGED || h->an.shard_count > 1) return HQPKKT_E_INTERN;  // (x1, x2, xq: the STAGED tests' ground)
+  if ((lpr != 0 && lpr != 4 && lpr != 16) || k->op < 0 || k->op > 1) return HQPKKT_E_RANGE;
+  k->n = h->an.n, k->me = h->an.me, k->m = h->an.m;
+  const int n = k->n, me = k->me, m = k->m;
+  if (n + me + m == 0) return HQPKKT_E_RANGE;
+  if (!ip_debug_need(*k, false, false, true)) return HQPKKT_E_NULL;
+  if (k->op == 0 && ((n && !k->x) || (me && !k->y) || (m && (!k->z || !k->w)))) return HQPKKT_E_NULL;
+  HIPCHK(hipSetDevice(h->opts.device));
+  int e;
+  IpDebugBufs B;
+  if ((e = B.up(*k, false))) return e;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  hipStream_t s = h->stream;
+  const bool lpr4 = lpr ? lpr == 4 : h->short_rows;
+  double *part = B.part.d.p, *out = B.out.d.p;
+  if (k->op == 0) {
+    const IpBlocks Bl{h->td.Qf.dev(), h->td.AT.dev(), h->td.CT.dev(), h->td.A.dev(), h->td.C.dev(), h->td.vals.p};
+    ip_rhs_launch(s, lpr4, n, me, m, Bl, B.c.d.p, B.b.d.p, B.d.d.p, B.x.d.p, B.y.d.p, B.z.d.p, B.w.d.p, B.r1.d.p, B.r2.d.p, B.r3.d.p, B.r4.d.p, part);
+    ip_final_launch(s, part, OPS_HEAD, out);
+  } else {
+    fr_cold_launch(s, lpr4, n, me, m, h->td.CT.dev(), k->p0, B.c.d.p, B.b.d.p, B.d.d.p, B.x.d.p, B.y.d.p, B.z.d.p, B.w.d.p, B.r1.d.p, B.r2.d.p,
+                   B.r3.d.p, part);
+    ip_final_launch(s, part, OPS_SUM, out);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
+  return B.down(*k, k->op == 1, false, false);
+}
 }  // namespace
 
 extern "C" {
+
+int hqpkkt_debug_ip_vec(int device, hqpkkt_ip_case *c) {
+  return guarded([&]() -> int { return debug_ip_vec(device, c); });
+}
+int hqpkkt_debug_ip_rows(hqpkkt_t *h, int lpr, hqpkkt_ip_case *c) {
+  return guarded([&]() -> int { return debug_ip_rows(h, lpr, c); });
+}
 
 int hqpkkt_default_ip_opts(hqpkkt_ip_opts *o) {
   if (!o) return HQPKKT_E_NULL;

@@ -1490,3 +1490,63 @@ def selftest_mfma(device=0):
     err = C.c_double()
     _check(_lib.lib().hqpkkt_selftest_mfma(device, C.byref(err)), "selftest_mfma")
     return err.value
+
+
+IP_VEC_OPS = ("pred", "step", "corr_rhs", "blocking", "mupl", "update", "cold_rhs", "cold_stats", "shift", "fill", "fr_dstats",
+              "fr_ratio", "fr_update", "fr_rhs", "final", "host_step_rule")
+IP_FINAL_OPS = ("OPS_SUM", "OPS_HEAD", "OPS_COLD", "OPS_MIN_MAX", "OPS_MIN", "OPS_SUM_MAX")
+IP_ROWS_OPS = ("rhs", "fr_cold")
+_IP_IN = ("x", "y", "z", "w", "dx", "dy", "dz", "dw", "c", "b", "d", "part_in", "Bk_in", "S_in")
+_IP_OUT = (("ox", "n"), ("oy", "me"), ("oz", "m"), ("ow", "m"), ("r1", "n"), ("r2", "me"), ("r3", "m"), ("r4", "m"))
+
+
+def _ip_case(op, n, me, m, kw):
+    """A hqpkkt_ip_case over the caller's arrays (uploaded at exactly their lengths) and NaN-filled result vectors:
+    (case, results by name, the arrays that must outlive the call)."""
+    c = _lib.IpCase()
+    c.op, c.n, c.me, c.m = op, n, me, m
+    c.form = 1 if kw.pop("small", False) else 0
+    ops = kw.pop("ops", "OPS_SUM")
+    c.ops = IP_FINAL_OPS.index(ops) if isinstance(ops, str) else int(ops)
+    c.epi, c.inplace = int(kw.pop("epi", 0)), int(bool(kw.pop("inplace", False)))
+    for name in ("alpha", "mu", "sum", "gamma", "gammaf", "smm", "p0", "p1"):
+        setattr(c, name, float(kw.pop(name, 0.0)))
+    kept = []
+    for name in _IP_IN:
+        v = kw.pop(name, None)
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            want = {"part_in": 2048, "Bk_in": 12, "S_in": 8}.get(name)
+            if want is None:
+                want = {"x": n, "dx": n, "c": n, "y": me, "dy": me, "b": me}.get(name, m)
+            assert v.ndim == 1 and v.size == want, (name, v.size, want)
+            kept.append(v)
+            setattr(c, name, v.ctypes.data if v.size else None)
+    assert not kw, sorted(kw)
+    res = {}
+    for name, dim in _IP_OUT:
+        res[name] = np.full({"n": n, "me": me, "m": m}[dim], np.nan)
+        setattr(c, name, res[name].ctypes.data if res[name].size else None)
+    return c, res, kept
+
+
+def _ip_results(c, res):
+    res.update(out=np.array(c.out[:]), Bk=np.array(c.Bk[:]), S=np.array(c.S[:]))
+    return res
+
+
+def ip_vec(op, n, me, m, device=0, **kw):
+    """One launch group of the vector kernels of the device-resident loops (hqpkkt_debug_ip_vec; op: a name of IP_VEC_OPS,
+    operands and scalars by the names of hqpkkt_ip_case, small=True: the one-workgroup form).  Returns a dict: the result
+    vectors ox, oy, oz, ow, r1 .. r4 (NaN where the op does not write), out (8), Bk (12), S (8)."""
+    c, res, _kept = _ip_case(IP_VEC_OPS.index(op), n, me, m, kw)
+    _check(_lib.lib().hqpkkt_debug_ip_vec(device, C.byref(c)), "debug_ip_vec " + op)
+    return _ip_results(c, res)
+
+
+def ip_rows(mat, op, lpr=0, **kw):
+    """k_ip_rhs ("rhs") or k_fr_cold ("fr_cold") with its reduction on the CSR blocks of an initialised matrix `mat`
+    (hqpkkt_debug_ip_rows), lpr lanes per row (4, 16; 0: the handle's choice).  Returns a dict as ip_vec."""
+    c, res, _kept = _ip_case(IP_ROWS_OPS.index(op), mat.n, mat.me, mat.m, kw)
+    _check(mat._L.hqpkkt_debug_ip_rows(mat._h, int(lpr), C.byref(c)), "debug_ip_rows " + op)
+    return _ip_results(c, res)

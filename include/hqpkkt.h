@@ -1457,6 +1457,51 @@ int hqpkkt_debug_factor_block(int device, int p, const double *A, double tol, do
                               int reps, double *L, double *dinv, int *ptype, int *lperm, double *W,
                               int *counters, double *ms);
 
+/* Test hooks of the vector kernels of the device-resident loops (ipdriver.hip.h): ONE launch group on the caller's host
+ * arrays through the launch functions hqpkkt_mehrotra / hqpkkt_franke call, host arrays back, nothing compared in the
+ * library.  Every vector goes into a device buffer of exactly its length with 64 marked doubles behind it (the mark is a
+ * NaN with a payload of its own, so whatever a kernel reads behind a length is NaN); every result vector, the 256 x 8
+ * partials, out, Bk and S are NaN before the launch; HQPKKT_E_INTERN where a mark has changed.
+ * Vectors by length: x, dx, c, r1, ox: n; y, dy, b, r2, oy: me; z, w, dz, dw, d, r3, r4, oz, ow: m.  A result pointer
+ * may be NULL.  out: the 8 reduced slots (k_ip_final), Bk: the blocking components (k_ip_minratio_final's 12), S: the
+ * step's scalars (IPS_*); where an op reads S or Bk it reads S_in / Bk_in (NULL: NaN).
+ * hqpkkt_debug_ip_vec, op (form 1: the one-workgroup kernels, ops 0 and 1 alone, HQPKKT_E_RANGE beyond m = 8192 or
+ * n + me + m = 32768):
+ *    0 predictor statistics: z, w, dz, dw (the affine step), sum (z'w of the iterate; mu = sum / m), gamma -> S, r4, and
+ *      on form 0 out (0 smallest ratio, 1 Terlaky's t)
+ *    1 the step: x .. w, dx .. dw, gamma, gammaf, S_in -> ox .. ow, Bk, S, on form 0 out (0: the sum behind mu_pl)
+ *    2 corrector right-hand side with the host's sigma mu (smm): z, w, dz, dw -> r4
+ *    3 blocking components alone (the second corrector's): z, w, dz, dw -> Bk
+ *    4 (z + alpha dz)'(w + alpha dw) with the host's alpha -> out[0]
+ *    5 k_ip_update with the host's alpha -> ox .. ow, out (0 z'w, 1 max |x|)
+ *    6 k_ip_cold_rhs: c, b, d, p0 = w0, p1 = r40 -> oz, ow, r1 .. r4
+ *    7 k_ip_cold_stats of dz, dw -> out (6 slots)
+ *    8 k_ip_shift: oz = dz + p0, ow = dw + p1; inplace != 0: results in the buffers of dz, dw themselves
+ *    9 k_ip_fill: oz = p0 (m entries)
+ *   10 k_fr_dstats of d -> out (3 slots)
+ *   11 Franke's ratio test and step length: z, w, dz, dw, gammaf = beta -> out[0], S
+ *   12 k_fr_update, alpha from S_in (m > 0; else the host's alpha) -> ox .. ow, out (0 z'w, 1 max |x|)
+ *   13 k_fr_rhs: c, b, d = a1, a2, a3, z, w, p0 = zeta, p1 = mu (through two mapped host words) -> r1 .. r4
+ *   14 k_ip_final alone: part_in (256 x 8), ops (0 OPS_SUM, 1 OPS_HEAD, 2 OPS_COLD, 3 OPS_MIN_MAX, 4 OPS_MIN, 5 OPS_SUM_MAX),
+ *      epi (kind 0 - 3) with m, mu, gamma, gammaf, Bk_in, S_in -> out, S
+ *   15 no launch: the second corrector's HOST copy of the step rule on Bk_in, sum (the sum behind mu_pl), m, gammaf ->
+ *      S[2] alpha before damping, S[5] alpha
+ * hqpkkt_debug_ip_rows (an analysed handle with values; lpr 4 or 16 lanes per CSR row, 0: the handle's own choice), op:
+ *    0 k_ip_rhs + k_ip_final: c, b, d, x, y, z, w -> r1 .. r4, out (6 slots)
+ *    1 k_fr_cold + k_ip_final: c, b, d, p0 = Ltilde -> ox .. ow, r1 .. r3 = a1 .. a3, out[0]
+ * HQPKKT_E_NULL, HQPKKT_E_RANGE (unknown op / form / ops / epi / lpr, a size below zero, m = 0 where the loop never
+ * launches with it, a grid that would be empty), HQPKKT_E_DEVICE, HQPKKT_E_MEM, HQPKKT_E_INTERN. */
+typedef struct hqpkkt_ip_case {
+  int op, form, n, me, m, ops, epi, inplace;
+  double alpha, mu, sum, gamma, gammaf, smm, p0, p1;
+  const double *x, *y, *z, *w, *dx, *dy, *dz, *dw, *c, *b, *d;
+  const double *part_in, *Bk_in, *S_in;
+  double *ox, *oy, *oz, *ow, *r1, *r2, *r3, *r4;
+  double out[8], Bk[12], S[8]; /* out */
+} hqpkkt_ip_case;
+int hqpkkt_debug_ip_vec(int device, hqpkkt_ip_case *c);
+int hqpkkt_debug_ip_rows(hqpkkt_t *h, int lpr, hqpkkt_ip_case *c);
+
 #ifdef __cplusplus
 }
 #endif

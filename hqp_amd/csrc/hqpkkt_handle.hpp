@@ -318,6 +318,12 @@ struct TreeDev {
       int long_slots = 0, long_ld = 0;      // workgroups of k_qel_block, one image each; an image's leading dimension
       DBuf<int> long_list;
       DBuf<double> long_ws;
+      // hqpkkt_q_eigen_control_blocked (q_eigen_blocked.hip.h): the blocks 513 .. 2048 long, listed by the same pass; their
+      // slots' workspace (image and two panels each), made by the first call that needs it
+      int blk_count = 0, blk_max = 0;       // how many and the longest of them
+      int blk_slots = 0, blk_ld = 0;        // workgroups of k_qeb_block, one slot each; an image's leading dimension
+      DBuf<int> blk_list;
+      DBuf<double> blk_ws;
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis

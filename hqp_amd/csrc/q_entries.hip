@@ -1,9 +1,9 @@
-// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 21 of them:
+// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 22 of them:
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
 // (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
 // hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h),
-// hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it), hqpkkt_q_eigen_control_long (q_eigen_long.hip.h beside both) and
-// hqpkkt_lagrangian_gradient.  Their state is
+// hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it), hqpkkt_q_eigen_control_long (q_eigen_long.hip.h beside both),
+// hqpkkt_q_eigen_control_blocked (q_eigen_blocked.hip.h beside all three) and hqpkkt_lagrangian_gradient.  Their state is
 // TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
@@ -20,6 +20,7 @@
 #include "q_eigen_short.hip.h"
 #include "q_eigen_mid.hip.h"
 #include "q_eigen_long.hip.h"
+#include "q_eigen_blocked.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
 
@@ -606,26 +607,29 @@ static int qes_buffers(hqpkkt_t *h, QPlan &p) {
 // ---- and on blocks up to 128 and up to 512: the blocks of 65 .. 128 by a workgroup each, over their list (q_eigen_mid.hip.h);
 // the blocks of 129 .. 512 by persistent workgroups over theirs, the images in device memory (q_eigen_long.hip.h)
 
-// one pass over the plan: the list of its blocks of 65 .. 128 and the list of its blocks of 129 .. 512, the longest of
-// each and the longest block of at most 64: made once per plan
+// one pass over the plan: the list of its blocks of 65 .. 128, of its blocks of 129 .. 512 and of its blocks of 513 .. 2048
+// (q_eigen_blocked.hip.h), the longest of each and the longest block of at most 64: made once per plan
 static int qem_list(QPlan &p) {
   if (p.mid_count >= 0) return 0;
-  std::vector<int> mid, lng;
-  int mid_max = 0, short_max = 0, long_max = 0;
+  std::vector<int> mid, lng, blk;
+  int mid_max = 0, short_max = 0, long_max = 0, blk_max = 0;
   for (int b = 0; b < p.nblocks; b++) {
     const int len = p.first[b + 1] - p.first[b];
-    if (len >= qv::QEL_MIN && len <= qv::QEL_MAX)
+    if (len >= qv::QEB_MIN && len <= qv::QEB_MAX)
+      blk.push_back(b), blk_max = std::max(blk_max, len);
+    else if (len >= qv::QEL_MIN && len <= qv::QEL_MAX)
       lng.push_back(b), long_max = std::max(long_max, len);
     else if (len >= qv::QEM_MIN && len <= qv::QEM_MAX)
       mid.push_back(b), mid_max = std::max(mid_max, len);
     else if (len < qv::QEM_MIN)
       short_max = std::max(short_max, len);
   }
-  DBuf<int> dm, dl;
+  DBuf<int> dm, dl, db;
   int e;
-  if ((e = dm.upload(mid)) || (e = dl.upload(lng))) return e;
-  p.mid_list = std::move(dm), p.long_list = std::move(dl);
+  if ((e = dm.upload(mid)) || (e = dl.upload(lng)) || (e = db.upload(blk))) return e;
+  p.mid_list = std::move(dm), p.long_list = std::move(dl), p.blk_list = std::move(db);
   p.long_count = (int)lng.size(), p.long_max = long_max;
+  p.blk_count = (int)blk.size(), p.blk_max = blk_max;
   p.mid_count = (int)mid.size(), p.mid_max = mid_max, p.short_max = short_max;
   return 0;
 }
@@ -643,6 +647,42 @@ static int qel_workspace(hqpkkt_t *h, QPlan &p) {
   if (int e = ws.alloc((size_t)slots * ld * ld)) return e;
   p.long_ws = std::move(ws), p.long_slots = slots, p.long_ld = ld;
   return 0;
+}
+// the slots of k_qeb_block: slots = min(listed blocks, CUs, what 4 GiB hold) - capped by the test hook HQPKKT_QEB_SLOTS, read
+// here -, each an image of LD x LD doubles, LD the longest listed block rounded up to 16, and two panels of LD x 32.  All or
+// nothing
+static int qeb_workspace(hqpkkt_t *h, QPlan &p) {
+  if (p.blk_ws.p || p.blk_count <= 0) return 0;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+  const int ld = (p.blk_max + 15) & ~15;
+  const size_t slot = qv::qeb_slot_doubles(ld) * sizeof(double), most = ((size_t)4 << 30) / slot;
+  int slots = (int)std::min<size_t>(std::min(p.blk_count, std::max(cus, 1)), most);
+  if (const char *cap = getenv("HQPKKT_QEB_SLOTS"))
+    if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
+  DBuf<double> ws;
+  if (int e = ws.alloc((size_t)slots * qv::qeb_slot_doubles(ld))) return e;
+  p.blk_ws = std::move(ws), p.blk_slots = slots, p.blk_ld = ld;
+  return 0;
+}
+// the dynamic LDS of k_qeb_ritz, 96 KB: set once per device, as qem_raise_lds below does; a device that refuses it is
+// HQPKKT_E_DEVICE before any launch
+static int qeb_raise_lds(hqpkkt_t *h) {
+  static std::mutex attr_mutex;
+  static bool done[64];
+  if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
+  std::lock_guard<std::mutex> lk(attr_mutex);
+  if (done[h->opts.device]) return 0;
+  HIPCHK(hipFuncSetAttribute((const void *)qv::k_qeb_ritz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(eig::RitzLdsT<qv::QEB_MAX>)));
+  done[h->opts.device] = true;
+  return 0;
+}
+// columns per panel of k_qeb_block: QEB_NB by the measurement in DESIGN.md; HQPKKT_QEB_NB (16 or 32) is the hook that
+// measurement used - the two instances give different bits, each its own from call to call
+static const int QEB_NB = 16;
+static int qeb_nb() {
+  const char *v = getenv("HQPKKT_QEB_NB");  // (read per call: the measurement lets the two take turns)
+  return v && (atoi(v) == 16 || atoi(v) == 32) ? atoi(v) : QEB_NB;
 }
 // the dynamic-LDS limits of k_qem_block: state of the process and of the current device (as raise_lds_limits, tree.hip),
 // constants here, so set once per device
@@ -666,7 +706,7 @@ static int qel_threads() {
   return v ? atoi(v) : QEL_THREADS;
 }
 
-// the three entries: `longest` is the block length the entry serves, 64, 128 or 512
+// the four entries: `longest` is the block length the entry serves, 64, 128, 512 or 2048
 static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int longest) {
   return guarded([&]() -> int {
     if (!h || !ec) return HQPKKT_E_NULL;
@@ -691,7 +731,9 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
     const bool mid = cap > 64;  // (the plan has blocks for k_qem_block)
     if (mid && (e = qem_list(p))) return e;
     const bool lng = mid && p.long_count > 0;  // (and blocks for k_qel_block)
+    const bool blk = mid && p.blk_count > 0;   // (and blocks for k_qeb_block)
     if ((lng && (e = qel_workspace(h, p))) || (mid && p.mid_count > 0 && (e = qem_raise_lds(h)))) return e;
+    if (blk && ((e = qeb_workspace(h, p)) || (e = qeb_raise_lds(h)))) return e;
     hipStream_t s = h->stream;
     if (ec->floor) {  // (as hqpkkt_q_eigen_control: the caller's again on return)
       HIPCHK(hipMemcpyAsync(p.eig_floor.p, ec->floor, sizeof(double) * (size_t)p.nblocks, hipMemcpyHostToDevice, s));
@@ -716,6 +758,12 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
           p.long_list.p, p.long_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.long_ws.p, p.long_ld);
       qv::k_qel_ritz<<<(unsigned)p.long_count, 64, 0, s>>>(p.long_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
     }
+    if (blk) {
+      pick(qeb_nb() > 16, qv::k_qeb_block<16>, qv::k_qeb_block<32>)<<<(unsigned)p.blk_slots, qv::QEB_NT, 0, s>>>(
+          p.blk_list.p, p.blk_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.blk_ws.p, p.blk_ld);
+      qv::k_qeb_ritz<<<(unsigned)p.blk_count, 64, sizeof(eig::RitzLdsT<qv::QEB_MAX>), s>>>(p.blk_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p,
+                                                                                           p.eig_rep.p);
+    }
     q.eig_last = at, p.eig_steps = cap;
     return qv_written(h);
   });
@@ -726,6 +774,10 @@ int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args 
 int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
   static_assert(qv::QEL_MAX == HQPKKT_QEIG_LONG_MAX, "the kernels size their LDS by it");
   return qes_control(h, ec, qv::QEL_MAX);
+}
+int hqpkkt_q_eigen_control_blocked(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+  static_assert(qv::QEB_MAX == HQPKKT_QEIG_BLOCKED_MAX, "the kernels size their LDS by it");
+  return qes_control(h, ec, qv::QEB_MAX);
 }
 
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {

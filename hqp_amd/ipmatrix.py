@@ -508,6 +508,16 @@ class Hqp_IpMatrix:
         with no block over 128 gives q_eigen_control_exact()'s bits; q_eigen_report() returns T of stride up to 512."""
         self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_long")
 
+    def q_eigen_control_blocked(self, eps, bsize=-1, floor_from_bfgs=False, floor=None):
+        """q_eigen_control_long() for a partition whose blocks are all at most 2048 long (_lib.HQPKKT_QEIG_BLOCKED_MAX;
+        hqpkkt_q_eigen_control_blocked; a longer block: HQPKKT_E_SIZES, nothing done): the blocks up to 512 as there, the
+        blocks of 513 .. 2048 reduced in device memory by persistent workgroups in panels of 16 columns - one pass over
+        the trailing image per step for the product, one rank-32 update per panel on the matrix pipe -, then bracketed and
+        shifted by a wavefront each.  A slot takes LD x (LD + 64) doubles, LD the longest of them rounded up to 16, and
+        there are min(such blocks, CUs, what 4 GiB hold) slots.  A partition with no block over 512 gives
+        q_eigen_control_long()'s bits; q_eigen_report() returns T of stride up to 2048."""
+        self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_blocked")
+
     def q_eigen_report(self, with_T=False):
         """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound
         g, the floor theta as used, the Lanczos steps, lo, hi (the bracket of T's smallest eigenvalue), rho (the residual

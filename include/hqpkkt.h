@@ -811,8 +811,9 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
  *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.  It serves the last
  *                       control of any kind: hqpkkt_q_eigen_control, hqpkkt_q_eigen_control_short,
- *                       hqpkkt_q_eigen_control_exact or hqpkkt_q_eigen_control_long - behind the last of these *t_steps
- *                       may exceed HQPKKT_EIG_MAX_STEPS (up to HQPKKT_QEIG_LONG_MAX).
+ *                       hqpkkt_q_eigen_control_exact, hqpkkt_q_eigen_control_long or hqpkkt_q_eigen_control_blocked - behind
+ *                       the last two *t_steps may exceed HQPKKT_EIG_MAX_STEPS (up to HQPKKT_QEIG_LONG_MAX = 512 and up to
+ *                       HQPKKT_QEIG_BLOCKED_MAX = 2048).
  *   hqpkkt_q_eigen_control_short  the job of hqpkkt_q_eigen_control on the same blocks of hqpkkt_q_blocks(bsize), for a plan
  *                       whose blocks are ALL at most 64 long (the partition of a DOCP: 125 000 blocks of order 8 at
  *                       n = 10^6), in ONE launch, a wavefront per block - and lambda is computed as the reference
@@ -912,9 +913,50 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       hessian_update.q_tridiag_model is the method in numpy at these lengths too.  The environment
  *                       variable HQPKKT_QEL_SLOTS caps `slots` (a test hook, read when the workspace is sized).
  *                       Not built: storage of one triangle of the image alone (half the traffic); a blocked reduction
- *                       with MFMA (it changes the order of the operations); blocks over 512 (hqpkkt_q_eigen_control
- *                       serves that plan); the dense stage Hessians' own exact control; several order-8 blocks in one
- *                       wavefront.
+ *                       with MFMA (it changes the order of the operations) and blocks over 512 (both:
+ *                       hqpkkt_q_eigen_control_blocked, next); the dense stage Hessians' own exact control; several
+ *                       order-8 blocks in one wavefront.
+ *   hqpkkt_q_eigen_control_blocked  hqpkkt_q_eigen_control_long for a plan whose blocks are all at most
+ *                       HQPKKT_QEIG_BLOCKED_MAX = 2048 long (one DOCP stage with up to 2048 states and controls): the same
+ *                       arguments and floor rules, checks in the same order, report words (rho = 0, lambda_est = lo, the
+ *                       outcome 0, 1, 2, 4 or 6, never 3; a NaN in a block: outcome 4 for that block alone), T layout
+ *                       (alpha then beta at stride 2 x the plan's longest block) and handle state.  max_steps must be 0.
+ *                       Launches: the long entry's, unchanged, for the blocks up to 512, then two over the list of the
+ *                       blocks of 513 .. 2048 (made by the same pass as the other two lists).  A plan with no block
+ *                       over 512 runs exactly the long entry's launches and gives its bits.  A listed block lies in a
+ *                       slot of a workspace in device memory: its image, LD x LD doubles, LD the longest listed block
+ *                       rounded up to 16, and two panels V and W of LD x 32 doubles; slots = min(listed blocks, CUs of
+ *                       the device, the most that 4 GiB hold), made by the first call that needs it and kept with the
+ *                       plan; HQPKKT_E_MEM where it cannot be had, the handle unchanged.  `slots` persistent workgroups
+ *                       (1024 threads, thread t the indices t and t + 1024) take the listed blocks in turn, sharing
+ *                       nothing.  Per block: the image cleared and gathered, g_b (offsum_i in ascending j from +0.0,
+ *                       every add rounded: hessian_update.q_block_gerschgorin_model repeats it), theta_b and the outcomes
+ *                       0 and 6 as above; then the reduction BLOCKED in panels of NB = 16 columns (dlatrd's scheme, lower
+ *                       form).  Column k = j0 + i of a panel: the column less the panel's earlier columns, a_{k:,k} -
+ *                       V_{k:,:i} W_{k,:i}' - W_{k:,:i} V_{k,:i}'; alpha_k; the zero-sub-column rule (no reflector, beta_k =
+ *                       x_0), beta_k, v and h as above; p = A v / h by one pass over the rows of the trailing image AS
+ *                       THE LAST PANEL LEFT IT (a chain of fused multiply-adds per lane over its columns k + 1 + lane +
+ *                       64 c, a butterfly, the division), corrected by -(V (W'v) + W (V'v)) / h; q = p - (v'p / 2h) v;
+ *                       column i of V <- v, of W <- q.  Behind a whole panel A <- A - V W' - W V' on the trailing image by
+ *                       v_mfma_f64_16x16x4 on 16 x 16 tiles on and below the diagonal, each stored with its transposed
+ *                       image: (i, j) and (j, i) hold the same bits.  The last panel has no update; the columns L - 2
+ *                       and L - 1 form no reflector and give alpha_{L-2}, beta_{L-2}, alpha_{L-1}, beta_{L-1} = 0.  A
+ *                       diagonal block gives its diagonal bit for bit.  Sums over a block run in an order fixed by the
+ *                       index inside the block: a block's bits depend on its length and its values alone - not on its
+ *                       slot, on where it lies, on the other blocks or on the mode - and are equal from call to
+ *                       call.  The order is NOT that of hessian_update.q_tridiag_model, and the matrix pipe's own order
+ *                       is not restated: T's eigenvalues are the block's to rounding, no numpy model gives T's bits.
+ *                       Then a wavefront per listed block for the bracket and the shift, on 96 KB of dynamic LDS:
+ *                       HQPKKT_E_DEVICE, before any launch, where the device refuses it.  HQPKKT_E_SIZES: a block longer
+ *                       than 2048; nothing is launched, Q is untouched.  Report: word 2 is L; *t_steps of
+ *                       hqpkkt_q_eigen_report is the plan's longest block and so MAY REACH 2048: size T by *t_steps.
+ *                       hessian_update.eigen_replay(L, g_b, theta_b, L, T) repeats words 3 .. 9 bit for bit.  The
+ *                       environment variable HQPKKT_QEB_SLOTS caps `slots` (a test hook, read when the workspace is
+ *                       sized); HQPKKT_QEB_NB = 32 selects the wider panel (the hook of the measurement in DESIGN.md;
+ *                       other bits of T, the same contract).
+ *                       Not built: storage of one triangle of the image alone; several workgroups per block; blocks
+ *                       over 2048 (hqpkkt_q_eigen_control serves that plan); the dense stage Hessians' own exact
+ *                       control; a numpy model of the blocked order.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -969,6 +1011,8 @@ int hqpkkt_q_eigen_control_short(hqpkkt_t *h, const hqpkkt_q_eigen_control_args 
 int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= 128 long; max_steps must be 0 */
 #define HQPKKT_QEIG_LONG_MAX 512
 int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_LONG_MAX long; max_steps must be 0 */
+#define HQPKKT_QEIG_BLOCKED_MAX 2048
+int hqpkkt_q_eigen_control_blocked(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_BLOCKED_MAX long; max_steps must be 0 */
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
                           double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
                           long long *n_blocks, int *t_steps);

@@ -28,6 +28,9 @@ behind a write - and the rate that makes at the measured time.
   (y) --long: q_eigen_control_long against q_eigen_control at 64 and 128 steps on plans with blocks of 512, 200 and 8 beside one
     of 512, and the long entry at 512 and 1024 threads per workgroup (long_rows below); a run of its own, appended to --out.
     python tools/q_values_time.py --long [--reps 20 --warmup 3 --out FILE]
+  (z) --blocked: q_eigen_control_blocked, at 16 and at 32 columns per panel, against q_eigen_control at 64 and 128 steps on plans
+    with blocks of 1024, of 2048 and of 8 beside one of 1500 (blocked_rows below); a run of its own, appended to --out.
+    python tools/q_values_time.py --blocked [--reps 20 --warmup 3 --out FILE]
 """
 import argparse
 import ctypes as C
@@ -133,8 +136,8 @@ def _block_program(orders):
     return problems.Program(n, 0, n // 2, Q, none, Cm, d=-np.ones(n // 2))
 
 
-def _control_rows(cases, paths, reps, warmup):
-    """the entries of ``paths`` - (name, symbol, max_steps, HQPKKT_QEL_THREADS or None), the first the one that computes lambda -
+def _control_rows(cases, paths, reps, warmup, hook="HQPKKT_QEL_THREADS"):
+    """the entries of ``paths`` - (name, symbol, max_steps, the value of the environment variable ``hook`` or None), the first the one that computes lambda -
     taking turns on every plan of ``cases`` - (label, block orders, how many of the paths) -; the values are set again from device arrays, untimed, before every call.  By wall clock
     to a device synchronisation.  The shifts: the first entry's d_b against the others'."""
     import torch
@@ -156,9 +159,9 @@ def _control_rows(cases, paths, reps, warmup):
         torch.cuda.synchronize()
         for r in range(warmup + reps):
             for nm, fn, steps, thr in named:
-                os.environ.pop("HQPKKT_QEL_THREADS", None)
+                os.environ.pop(hook, None)
                 if thr:
-                    os.environ["HQPKKT_QEL_THREADS"] = thr
+                    os.environ[hook] = thr
                 e = _lib.QEigenControl()
                 e.eps, e.bsize, e.floor_from_bfgs, e.max_steps = 2.0 ** -10, -1, 0, steps
                 assert L.hqpkkt_set_values(M._h, C.c_void_p(dQ.data_ptr()), None, C.c_void_p(dC.data_ptr())) == 0
@@ -172,7 +175,7 @@ def _control_rows(cases, paths, reps, warmup):
                     times[nm].append(dt)
                 reports[nm] = M.q_eigen_report() if r == 0 else reports[nm]
         lines.append(f"{label}: n {n}, nnz Q {len(prog.Q[2])}; analysis + values {t_init:.1f} s")
-        os.environ.pop("HQPKKT_QEL_THREADS", None)
+        os.environ.pop(hook, None)
         for nm, _f, _s, _t in named:
             t, r_ = np.array(times[nm]), reports[nm]
             oc = {int(o): int((r_[:, 9] == o).sum()) for o in np.unique(r_[:, 9])}
@@ -207,8 +210,22 @@ def long_rows(reps, warmup):
     return _control_rows(cases, paths, reps, warmup)
 
 
+def blocked_rows(reps, warmup):
+    """(z) hqpkkt_q_eigen_control_blocked at 16 and at 32 columns per panel of k_qeb_block (HQPKKT_QEB_NB; the two give different
+    T, so the first is the one the shifts are compared with) against hqpkkt_q_eigen_control at 64 and at 128 steps, the only
+    path such plans had, as long_rows, on three plans: 201 full blocks of 1024, 20 of 2048, and 125 000 blocks of 8 with one
+    block of 1500 in their middle."""
+    cases = (("201 blocks of 1024", np.full(201, 1024), 4), ("20 blocks of 2048", np.full(20, 2048), 4),
+             ("125000 blocks of 8, one of 1500", np.insert(np.full(125000, 8), 62500, 1500), 4))
+    paths = (("z q_eigen_control_blocked, NB 16, ", "hqpkkt_q_eigen_control_blocked", 0, "16"), ("z q_eigen_control_blocked, NB 32, ", "hqpkkt_q_eigen_control_blocked", 0, "32"),
+             ("  q_eigen_control, 64 steps, ", "hqpkkt_q_eigen_control", 64, None), ("  q_eigen_control, 128 steps, ", "hqpkkt_q_eigen_control", 128, None))
+    return _control_rows(cases, paths, reps, warmup, hook="HQPKKT_QEB_NB")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--blocked", action="store_true",
+                    help="the rows of hqpkkt_q_eigen_control_blocked against hqpkkt_q_eigen_control at 64 and 128 steps alone; --out is appended to")
     ap.add_argument("--exact", action="store_true",
                     help="the rows of hqpkkt_q_eigen_control_exact against hqpkkt_q_eigen_control alone; --out is appended to")
     ap.add_argument("--long", action="store_true",
@@ -223,8 +240,8 @@ def main():
     ap.add_argument("--bfgs-order", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.staged or a.exact or a.long:
-        text = "\n".join(long_rows(a.reps, a.warmup) if a.long else
+    if a.staged or a.exact or a.long or a.blocked:
+        text = "\n".join(blocked_rows(a.reps, a.warmup) if a.blocked else long_rows(a.reps, a.warmup) if a.long else
                          exact_rows(a.reps, a.warmup) if a.exact else staged_gradient_rows(*a.staged, a.reps, a.warmup))
         print(text)
         if a.out:

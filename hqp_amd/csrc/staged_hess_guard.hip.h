@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(256) k_he_start(const HgDesc *__restrict__ des
     pending = outcome < 0;
   }
   __syncthreads();
-  if (!pending) return;
+  if (!pending || !V) return;  // (V null: the exact control, which starts from no vector)
   for (int i = threadIdx.x; i < d.nz; i += 256) V[d.col0 + i] = he_start_entry(i) / nrm;
 }
 

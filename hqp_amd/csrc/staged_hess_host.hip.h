@@ -171,6 +171,101 @@ int hess_read_back(hqpkkt_t *h, double *a, const DBuf<double> &A, double *b = nu
   return 0;
 }
 
+// what the exact control makes at its first call, ahead of every launch: T at stride nz_max; the slots of k_hx_block,
+// slots = min(K + 1, CUs, what 4 GiB hold) - capped by the test hook HQPKKT_HX_SLOTS, read here -, each an image of LD x LD
+// doubles, LD the largest stage order rounded up to 16, and two panels of LD x 32; and the dynamic LDS of k_hx_ritz, 96 KB,
+// set once per device (a device that refuses it: HQPKKT_E_DEVICE).  All or nothing: a failure leaves the handle as it was
+int hx_prepare(hqpkkt_t *h, HessCall &c) {
+  StagedDev::Hessians::Guard &g = c.d.hess.guard;
+  static std::mutex attr_mutex;
+  static bool raised[64];
+  if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
+  {
+    std::lock_guard<std::mutex> lk(attr_mutex);
+    if (!raised[h->opts.device])
+      HIPCHK(hipFuncSetAttribute((const void *)stg::k_hx_ritz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(eig::RitzLdsT<stg::HX_MAX>)));
+    raised[h->opts.device] = true;
+  }
+  if (g.xws.p) return 0;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+  const int ld = (g.nz_max + 15) & ~15;
+  const size_t slot = stg::hx_slot_doubles(ld) * sizeof(double), most = ((size_t)4 << 30) / slot;
+  int slots = (int)std::min<size_t>(std::min(c.K1, std::max(cus, 1)), most);
+  if (const char *cap = getenv("HQPKKT_HX_SLOTS"))
+    if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
+  DBuf<double> ws, T;
+  int e;
+  if ((e = ws.alloc((size_t)slots * stg::hx_slot_doubles(ld))) || (e = T.alloc((size_t)c.K1 * 2 * g.nz_max))) return e;
+  g.xws = std::move(ws), g.xT = std::move(T), g.x_slots = slots, g.x_ld = ld;
+  return 0;
+}
+// rows in flight per wavefront of k_hx_block's pass: HX_ROWS by the measurement in DESIGN.md; HQPKKT_HX_ROWS (4 or 8) is the
+// hook that measurement used, read per call - both instances give the same bits
+const int HX_ROWS = 4;
+int hx_rows() {
+  const char *v = getenv("HQPKKT_HX_ROWS");
+  return v && (atoi(v) == 4 || atoi(v) == 8) ? atoi(v) : HX_ROWS;
+}
+
+// Both eigenvalue controls: hqpkkt_eigen_control_stage_hessians (Lanczos) and, exact, .._exact.  One preamble - the tests
+// of the arguments in the header's order, the floors through the pinned words, the row pass and k_he_start -, then the
+// recurrence or the reduction, then the shifts of the report by k_hg_diag.  Nothing is read back
+int eigen_control_call(hqpkkt_t *h, const hqpkkt_eigen_control *ec, bool exact) {
+  if (!h || !ec) return HQPKKT_E_NULL;
+  static_assert(stg::HE_MAX_STEPS == HQPKKT_EIG_MAX_STEPS && stg::HE_REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
+  static_assert(stg::HX_MAX == HQPKKT_EIG_EXACT_MAX, "the kernels size their LDS by it");
+  if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps < 0 || ec->max_steps > (exact ? 0 : HQPKKT_EIG_MAX_STEPS)) return HQPKKT_E_RANGE;
+  if (!HessCall::ready(h)) return HQPKKT_E_INTERN;
+  HessCall c(h);
+  const int K1 = c.K1;
+  const size_t n = c.n;
+  for (int k = 0; k < K1 && ec->floor; k++)
+    if (!std::isfinite(ec->floor[k])) return HQPKKT_E_RANGE;
+  for (int k = 0; k < K1 && exact; k++)
+    if (c.P.hess_order(k) > HQPKKT_EIG_EXACT_MAX) return HQPKKT_E_SIZES;
+  int e;
+  if ((e = c.all_arrived(nullptr))) return e;
+  if (ec->floor_from_bfgs && !c.d.hess.bfgs.done) return HQPKKT_E_INTERN;
+  if ((e = c.device(true))) return e;
+  StagedDev::Hessians::Guard &g = c.d.hess.guard;
+  if (exact && g.nz_max > 0 && (e = hx_prepare(h, c))) return e;
+  // the floors the caller gave, NaN where theta_k comes from eps: through the pinned words, in the handle's stream
+  HIPCHK(hipEventSynchronize(g.ev));  // (the copy of the last call's floors out of the pinned words)
+  for (int k = 0; k < K1; k++) g.hfloor.p[k] = ec->floor ? ec->floor[k] : std::numeric_limits<double>::quiet_NaN();
+  HIPCHK(hipMemcpyAsync(g.floor.p, g.hfloor.p, sizeof(double) * K1, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipEventRecord(g.ev, h->stream));
+  double *os = c.work(1), *w = c.work(3);
+  const int steps = exact ? 0 : std::min(ec->max_steps ? ec->max_steps : 64, g.nz_max);
+  // the basis of the recurrence, `steps` vectors of n: grown here, outside every capture, and cleared - a stage that is
+  // done keeps v = 0 from there on
+  double *V = nullptr;
+  if (!exact) {
+    if (g.V.count < (size_t)steps * n + 1 && (e = g.V.alloc((size_t)steps * n + 1))) return e;
+    V = g.V.p;
+    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, h->stream));
+  }
+  c.rows(nullptr, os);
+  KLAUNCH(h, KC_VECTOR, stg::k_he_start<<<(unsigned)K1, 256, 0, h->stream>>>(g.desc.p, c.d.hess.Q.p, os, g.floor.p, ec->eps * ec->eps,
+                                                                           ec->floor_from_bfgs ? c.d.hess.bfgs.rep.p : nullptr, g.st.p, g.rep.p, g.T.p, V));
+  for (int j = 0; j < steps; j++) {  // (nothing is read back: a stage that has ended returns from its workgroup at once)
+    staged_hess_symv(h, c.d, V + (size_t)j * n, w);
+    KLAUNCH(h, KC_VECTOR, stg::k_he_step<<<(unsigned)K1, stg::HE_STEP_THREADS, 0, h->stream>>>(g.desc.p, g.st.p, g.T.p, V, w, (long long)n, j, j + 1 == steps ? 1 : 0));
+  }
+  if (!exact)
+    KLAUNCH(h, KC_VECTOR, stg::k_he_ritz<<<(unsigned)K1, 64, 0, h->stream>>>(g.st.p, g.T.p, g.rep.p));
+  else if (g.nz_max > 0) {
+    const auto block = hx_rows() == 4 ? stg::k_hx_block<16, 4> : stg::k_hx_block<16, 8>;
+    KLAUNCH(h, KC_VECTOR, block<<<(unsigned)g.x_slots, stg::HX_NT, 0, h->stream>>>(g.desc.p, K1, c.d.hess.Q.p, g.nz_max, g.xT.p, g.rep.p, g.xws.p, g.x_ld));
+    KLAUNCH(h, KC_VECTOR, stg::k_hx_ritz<<<(unsigned)K1, 64, sizeof(eig::RitzLdsT<stg::HX_MAX>), h->stream>>>(g.desc.p, g.nz_max, g.xT.p, g.rep.p));
+  }
+  c.lift_diagonal(nullptr, 0.0, g.rep.p);
+  HIPCHK(hipGetLastError());
+  g.done = true, g.exact = exact;
+  c.touched();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -419,54 +514,29 @@ int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps) {
 }
 
 int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *ec) {
-  return guarded([&]() -> int {
-    if (!h || !ec) return HQPKKT_E_NULL;
-    static_assert(stg::HE_MAX_STEPS == HQPKKT_EIG_MAX_STEPS && stg::HE_REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
-    if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps < 0 || ec->max_steps > HQPKKT_EIG_MAX_STEPS) return HQPKKT_E_RANGE;
-    if (!HessCall::ready(h)) return HQPKKT_E_INTERN;
-    HessCall c(h);
-    const int K1 = c.K1;
-    const size_t n = c.n;
-    for (int k = 0; k < K1 && ec->floor; k++)
-      if (!std::isfinite(ec->floor[k])) return HQPKKT_E_RANGE;
-    int e;
-    if ((e = c.all_arrived(nullptr))) return e;
-    if (ec->floor_from_bfgs && !c.d.hess.bfgs.done) return HQPKKT_E_INTERN;
-    if ((e = c.device(true))) return e;
-    StagedDev::Hessians::Guard &g = c.d.hess.guard;
-    // the floors the caller gave, NaN where theta_k comes from eps: through the pinned words, in the handle's stream
-    HIPCHK(hipEventSynchronize(g.ev));  // (the copy of the last call's floors out of the pinned words)
-    for (int k = 0; k < K1; k++) g.hfloor.p[k] = ec->floor ? ec->floor[k] : std::numeric_limits<double>::quiet_NaN();
-    HIPCHK(hipMemcpyAsync(g.floor.p, g.hfloor.p, sizeof(double) * K1, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(g.ev, h->stream));
-    double *os = c.work(1), *w = c.work(3);
-    const int steps = std::min(ec->max_steps ? ec->max_steps : 64, g.nz_max);
-    // the basis of the recurrence, `steps` vectors of n: grown here, outside every capture, and cleared - a stage that is
-    // done keeps v = 0 from there on
-    if (g.V.count < (size_t)steps * n + 1 && (e = g.V.alloc((size_t)steps * n + 1))) return e;
-    double *V = g.V.p;
-    HIPCHK(hipMemsetAsync(V, 0, sizeof(double) * (size_t)steps * n, h->stream));
-    c.rows(nullptr, os);
-    KLAUNCH(h, KC_VECTOR, stg::k_he_start<<<(unsigned)K1, 256, 0, h->stream>>>(g.desc.p, c.d.hess.Q.p, os, g.floor.p, ec->eps * ec->eps,
-                                                                             ec->floor_from_bfgs ? c.d.hess.bfgs.rep.p : nullptr, g.st.p, g.rep.p, g.T.p, V));
-    for (int j = 0; j < steps; j++) {  // (nothing is read back: a stage that has ended returns from its workgroup at once)
-      staged_hess_symv(h, c.d, V + (size_t)j * n, w);
-      KLAUNCH(h, KC_VECTOR, stg::k_he_step<<<(unsigned)K1, stg::HE_STEP_THREADS, 0, h->stream>>>(g.desc.p, g.st.p, g.T.p, V, w, (long long)n, j, j + 1 == steps ? 1 : 0));
-    }
-    KLAUNCH(h, KC_VECTOR, stg::k_he_ritz<<<(unsigned)K1, 64, 0, h->stream>>>(g.st.p, g.T.p, g.rep.p));
-    c.lift_diagonal(nullptr, 0.0, g.rep.p);
-    HIPCHK(hipGetLastError());
-    g.done = true;
-    c.touched();
-    return 0;
-  });
+  return guarded([&]() -> int { return eigen_control_call(h, ec, false); });
+}
+
+int hqpkkt_eigen_control_stage_hessians_exact(hqpkkt_t *h, const hqpkkt_eigen_control *ec) {
+  return guarded([&]() -> int { return eigen_control_call(h, ec, true); });
 }
 
 int hqpkkt_eigen_report(hqpkkt_t *h, double *out, double *T) {
   return guarded([&]() -> int {
     if (!h || !out) return HQPKKT_E_NULL;
     if (!h->sd || !h->uploaded || !h->sd->hess.guard.done) return HQPKKT_E_INTERN;
+    if (T && h->sd->hess.guard.exact) return HQPKKT_E_SIZES;  // (its T has another stride: hqpkkt_eigen_report_exact)
     return hess_read_back(h, out, h->sd->hess.guard.rep, T, &h->sd->hess.guard.T);
+  });
+}
+
+int hqpkkt_eigen_report_exact(hqpkkt_t *h, double *out, double *T, int *t_steps) {
+  return guarded([&]() -> int {
+    if (!h || !out || !t_steps) return HQPKKT_E_NULL;
+    if (!h->sd || !h->uploaded || !h->sd->hess.guard.done || !h->sd->hess.guard.exact) return HQPKKT_E_INTERN;
+    const StagedDev::Hessians::Guard &g = h->sd->hess.guard;
+    *t_steps = g.nz_max;
+    return hess_read_back(h, out, g.rep, g.nz_max > 0 ? T : nullptr, &g.xT);
   });
 }
 

@@ -104,15 +104,17 @@ struct StagedDev {
     // per stage what their kernels need, the slots of the packed row pass (`slots` doubles of maxima, then as many of sums
     // - twice what the product's scratch holds, so it is not shared), the recurrence's basis (as many vectors of n as the
     // control with the most steps asked for), its state, T and report per stage (read by hqpkkt_eigen_report), the floors
-    // through pinned words (ev: copied), and whether a control has run since the analysis
+    // through pinned words (ev: copied), and whether a control has run since the analysis.  The exact control
+    // (hqpkkt_eigen_control_stage_hessians_exact, first call): its T at stride nz_max (xT), the slots of k_hx_block (xws:
+    // x_slots images of x_ld x x_ld and their panels), and whether the last control was that one (the report's T is xT)
     struct Guard {
       DBuf<stg::HgDesc> desc;
-      DBuf<double> scr, V, st, T, rep, floor;
+      DBuf<double> scr, V, st, T, rep, floor, xT, xws;
       PinnedBuf<double> hfloor;
       EventOwner ev;
       long long slots = 0;
-      int tiles_max = 0, nz_max = 0;
-      bool done = false;
+      int tiles_max = 0, nz_max = 0, x_slots = 0, x_ld = 0;
+      bool done = false, exact = false;
     } guard;
   } hess;
   // The sparse form (StagedPlan::sparse_dyn): the plan's ranges into the CSR arrays of A and A' ...

@@ -971,6 +971,34 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         _check(self._L.hqpkkt_eigen_report(self._h, C.c_void_p(out.ctypes.data), None if T is None else C.c_void_p(T.ctypes.data)), "eigen_report")
         return (out, T) if with_T else out
 
+    def eigen_control_exact(self, eps, floor=None, from_bfgs=False):
+        """eigen_control() with the smallest eigenvalue of every stage computed, not estimated, for a handle whose stage
+        orders are all at most _lib.HQPKKT_EIG_EXACT_MAX = 2048 (hqpkkt_eigen_control_stage_hessians_exact; a larger stage:
+        HQPKKT_E_SIZES, nothing done): every block is reduced to a tridiagonal T of its own order by Householder reflectors
+        on the device, and the shift is theta_k less T's smallest eigenvalue - the reference's effect.  The floors are
+        eigen_control()'s.  The call returns with the work enqueued; eigen_report_exact() tells what every stage did."""
+        c = _lib.EigenControl()
+        c.eps, c.floor_from_bfgs, c.max_steps = float(eps), int(bool(from_bfgs)), 0
+        if floor is not None:
+            floor = np.ascontiguousarray(floor, dtype=np.float64).reshape(len(self.debug(20)))
+            c.floor = floor.ctypes.data
+        _check(self._L.hqpkkt_eigen_control_stage_hessians_exact(self._h, C.byref(c)), "eigen_control_exact")
+
+    def eigen_report_exact(self, with_T=False):
+        """Per stage what the last eigen_control_exact() did (hqpkkt_eigen_report_exact): eigen_report()'s array, with the
+        stage's order as its steps, rho = 0, the estimate lo, and an outcome that is never 3.  ``with_T``: (report, T) with
+        T of shape (K + 1, 2, t_steps), t_steps the largest stage order: alpha then beta of every stage's tridiagonal.
+        Waits for the handle's stream."""
+        K1 = len(self.debug(20))
+        out = np.zeros((K1, _lib.HQPKKT_EIG_REPORT))
+        ts = C.c_int(0)
+        _check(self._L.hqpkkt_eigen_report_exact(self._h, C.c_void_p(out.ctypes.data), None, C.byref(ts)), "eigen_report_exact")
+        if not with_T:
+            return out
+        T = np.zeros((K1, 2, ts.value))
+        _check(self._L.hqpkkt_eigen_report_exact(self._h, C.c_void_p(out.ctypes.data), C.c_void_p(T.ctypes.data), C.byref(ts)), "eigen_report_exact")
+        return out, T
+
     def set_packed_hessians(self, on):
         """Dense stage Hessians stored as packed lower tiles (hqpkkt_set_packed_hessians); holds from the next init() on."""
         _check(self._L.hqpkkt_set_packed_hessians(self._h, int(on)), "set_packed_hessians")

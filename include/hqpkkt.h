@@ -602,6 +602,39 @@ int hqpkkt_bfgs_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * 8 doubles */)
  * given, per stage alpha_0 .. (HQPKKT_EIG_MAX_STEPS doubles), then beta_0 .. (as many); words past the steps are 0.
  * hessian_update.eigen_replay repeats k_he_ritz in numpy from the reported T.  HQPKKT_E_INTERN before the first control
  * since the analysis.
+ * hqpkkt_eigen_control_stage_hessians_exact: the same control with lambda COMPUTED, as the reference's symmeig computes it,
+ * for handles whose stage orders are all at most HQPKKT_EIG_EXACT_MAX = 2048 (kernels: staged_hess_exact.hip.h).  The
+ * struct, the floors (eps, floor_from_bfgs read on the device, the host floor through the pinned words), the handles and
+ * the checks are those of hqpkkt_eigen_control_stage_hessians, in its order, with two differences: max_steps must be 0
+ * (HQPKKT_E_RANGE otherwise), and behind the test of the floors a stage order over 2048 gives HQPKKT_E_SIZES, before anything
+ * is allocated or launched, the blocks bit-unchanged (hqpkkt_eigen_control_stage_hessians serves such a handle).
+ *   Launches.  The Lanczos entry's preamble unchanged - the floors, the row pass, k_he_start (which writes no start vector
+ *   here): g_k, theta_k and the outcomes 0 and 5 are that entry's bits.  Then k_hx_block: persistent workgroups of 1024
+ *   threads, one per slot, workgroup w the stages w, w + slots, ..; a stage that is done already is passed over.  The
+ *   workgroup copies the stage's block from where it lies into the slot's image - a dense block row by row, packed tiles
+ *   each read once and written at their place and, transposed through LDS, at their image: both layouts give the same
+ *   image, symmetric bit for bit; padding and ragged tile rows are never read as values - and reduces it to a tridiagonal T
+ *   of the stage's order by Householder reflectors in panels of 16 columns (dlatrd's scheme, lower form): per column one
+ *   pass over the trailing image for p = A v / h, per panel one rank-32 update A - V W' - W V' on v_mfma_f64_16x16x4.
+ *   The sums run in an order fixed by the index inside the stage: a stage's T depends on its order and its values alone -
+ *   not on the layout, the slot, the other stages or the hooks below - and is equal from call to call.  Then k_hx_ritz, a
+ *   wavefront per stage: the Ritz step above, its body unchanged, on all of T (m = the order; beta_{m-1} = 0, so rho = 0 and
+ *   lambda_est = lo, the bracket's lower end, at most 2^-50 |T| below T's smallest eigenvalue).  Then the shift by k_hg_diag as
+ *   above.  Nothing is read back: with device vectors the call is asynchronous.
+ *   Report.  hqpkkt_eigen_report_exact: the words of hqpkkt_eigen_report - 2 is the stage's order, 5 rho = 0, 6 lambda_est =
+ *   lo; the outcome is 0, 1, 2, 4 or 5, never 3; a stage that holds a NaN ends with outcome 4 and is left bit-unchanged, the
+ *   other stages as without it - and *t_steps = the largest stage order; T, where given, per stage alpha_0 .. (*t_steps
+ *   doubles), then beta_0 .. (as many), words past the stage's order 0 and beta of the last column 0.  HQPKKT_E_NULL without
+ *   out or t_steps; HQPKKT_E_INTERN unless the last control since the analysis was the exact one.  hqpkkt_eigen_report serves
+ *   `out` behind either control; asked for T behind the exact one it returns HQPKKT_E_SIZES and writes nothing (its stride is
+ *   HQPKKT_EIG_MAX_STEPS).
+ *   Workspace.  slots = min(K + 1, compute units, what 4 GiB hold) images of LD x LD doubles, LD the largest order rounded up
+ *   to 16, with two panels of LD x 32 each, and T: made by the first exact call, kept with the handle; HQPKKT_E_MEM where that
+ *   fails, HQPKKT_E_DEVICE where the device refuses k_hx_ritz its 96 KB of dynamic LDS, both before any launch.
+ *   Hooks (environment): HQPKKT_HX_SLOTS caps the slots (read when the workspace is made); HQPKKT_HX_ROWS = 4 or 8 selects
+ *   the rows a wavefront of k_hx_block keeps in flight in the pass (read per call; default 4, the faster; the same bits).
+ *   Not built: the exact control chained from hqpkkt_bfgs_update_stage_hessians (the caller makes the two calls;
+ *   floor_from_bfgs works as above); stages over 2048 - an exact reduction there moves about n^3 8/3 bytes per stage.
  * Not built: sharded handles and the CSR hand-over.  (The reference's Hqp_HL_DScale works on the sparse Q: the hqpkkt_q_*
  * entries below.) */
 #define HQPKKT_EIG_MAX_STEPS 128
@@ -618,6 +651,10 @@ int hqpkkt_restart_stage_hessians(hqpkkt_t *h, double eps, const unsigned char *
 int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps);
 int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *e);
 int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * HQPKKT_EIG_MAX_STEPS */);
+#define HQPKKT_EIG_EXACT_MAX 2048
+int hqpkkt_eigen_control_stage_hessians_exact(hqpkkt_t *h, const hqpkkt_eigen_control *e); /* every stage order <= HQPKKT_EIG_EXACT_MAX; max_steps must be 0 */
+int hqpkkt_eigen_report_exact(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * *t_steps */,
+                              int *t_steps /* the largest stage order */);
 /* ---- The sparse Q where it lies on the device: the reference's Hessian approximations that work on Hqp_Program::Q itself
  * (Hqp_HL::init, Hqp_HL_Gerschgorin, Hqp_HL_DScale - what hqp_cute.tcl selects next to RedSpBKP) and grd_L of
  * Hqp_SqpSolver, without a round trip of Qx | Ax | Cx through hqpkkt_set_values.  Kernels: csrc/q_values.hip.h; host code: csrc/q_entries.hip.
@@ -914,7 +951,7 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       variable HQPKKT_QEL_SLOTS caps `slots` (a test hook, read when the workspace is sized).
  *                       Not built: storage of one triangle of the image alone (half the traffic); a blocked reduction
  *                       with MFMA (it changes the order of the operations) and blocks over 512 (both:
- *                       hqpkkt_q_eigen_control_blocked, next); the dense stage Hessians' own exact control; several
+ *                       hqpkkt_q_eigen_control_blocked, next); several
  *                       order-8 blocks in one wavefront.
  *   hqpkkt_q_eigen_control_blocked  hqpkkt_q_eigen_control_long for a plan whose blocks are all at most
  *                       HQPKKT_QEIG_BLOCKED_MAX = 2048 long (one DOCP stage with up to 2048 states and controls): the same
@@ -955,8 +992,9 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
  *                       sized); HQPKKT_QEB_NB = 32 selects the wider panel (the hook of the measurement in DESIGN.md;
  *                       other bits of T, the same contract).
  *                       Not built: storage of one triangle of the image alone; several workgroups per block; blocks
- *                       over 2048 (hqpkkt_q_eigen_control serves that plan); the dense stage Hessians' own exact
- *                       control; a numpy model of the blocked order.
+ *                       over 2048 (hqpkkt_q_eigen_control serves that plan); a numpy model of the blocked order.  (The
+ *                       dense stage Hessians have an exact control of their own:
+ *                       hqpkkt_eigen_control_stage_hessians_exact.)
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may

@@ -10,7 +10,13 @@ synchronisation of the device:
       parts are timed apart
 Mean, median and least of REPS calls after WARM untimed ones for (u) and (a), ROUNDS rounds, the paths and the handles
 taking turns; (b) once per handle: it takes seconds.
-python tools/eigen_control_time.py [out.txt]"""
+python tools/eigen_control_time.py [out.txt]
+
+--exact: the exact control (hqpkkt_eigen_control_stage_hessians_exact) beside the Lanczos control (64 steps) on the same
+handles - 201 stages of order 1024, 21 of order 2048, 201 of order 200, no controls, one symmetric random block (eigenvalues
+within +-2 sqrt(order)) on every stage; packed and unpacked; HQPKKT_HX_ROWS 4 and 8 (read per call).  Per call by wall clock
+to a synchronisation, EXACT_REPS calls after one; the outcome counts of both entries.
+python tools/eigen_control_time.py --exact [out.txt]"""
 import os
 import sys
 import time
@@ -57,6 +63,39 @@ def read_back_route(D, st, yt):
     return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, low
 
 
+EXACT_SHAPES, EXACT_REPS = ((201, 1024), (21, 2048), (201, 200)), 3
+
+
+def main_exact(out_path):
+    rng = np.random.default_rng(5)
+    empty = lambda rows: (np.zeros(rows + 1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
+    lines = [f"eigen_control_time --exact: eigen_control_exact beside eigen_control (64 Lanczos steps) on the same handles, {torch.cuda.get_device_name(0)}; "
+             f"per call by wall clock to a synchronisation, {EXACT_REPS} calls after one; ms: mean (least)"]
+    counts = lambda rep: {int(o): int((rep[:, 9] == o).sum()) for o in np.unique(rep[:, 9])}
+    for stages, v in EXACT_SHAPES:
+        Ud = torch.as_tensor(rng.standard_normal((v, v))).cuda()
+        Fd = torch.zeros((v, v), dtype=torch.float64, device="cuda")
+        for name, packed in (("packed", True), ("unpacked", False)):
+            dq = problems.DenseDocp([v] * stages, [0] * (stages - 1), empty(stages * v), empty(0), empty(0), [Fd] * (stages - 1), 0, 0, Qd=[Ud] * stages)
+            D = ipmatrix.IpLQDOCP(q_dense=True, q_packed=packed, device_vectors=True)
+            D.init_dense(dq)
+            row = f"{stages} stages of order {v}, {name}:"
+            for rows in (4, 8):
+                os.environ["HQPKKT_HX_ROWS"] = str(rows)
+                t = timed(lambda: D.eigen_control_exact(EPS), 1 + EXACT_REPS)[1:]
+                row += f"  exact ROWS={rows} {np.mean(t):.2f} ({min(t):.2f})"
+            del os.environ["HQPKKT_HX_ROWS"]
+            out_x = counts(D.eigen_report_exact())
+            t = timed(lambda: D.eigen_control(EPS), 1 + EXACT_REPS)[1:]
+            lines.append(row + f"  Lanczos {np.mean(t):.2f} ({min(t):.2f});  outcomes exact {out_x}, Lanczos {counts(D.eigen_report())}")
+            print(lines[-1], flush=True)
+            del D
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+
+
 def main(out_path):
     rng = np.random.default_rng(5)
     U = rng.standard_normal((NZ[0], NZ[0]))  # (the upper triangle is read: a symmetric matrix with eigenvalues within +-2 sqrt(order))
@@ -99,4 +138,8 @@ def main(out_path):
 
 
 if __name__ == "__main__":
+    if "--exact" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--exact"]
+        main_exact(rest[0] if rest else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eigen_control_time.txt"))
+        sys.exit(0)
     main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r20_eigen_control.txt"))

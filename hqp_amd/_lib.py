@@ -27,6 +27,7 @@ HQPKKT_EIG_MAX_STEPS = 128
 HQPKKT_QEIG_LONG_MAX = 512
 HQPKKT_QEIG_BLOCKED_MAX = 2048
 HQPKKT_EIG_EXACT_MAX = 2048
+HQPKKT_EIG_WIDE_MAX = 8192
 HQPKKT_EIG_REPORT = 10
 HQPKKT_EIG_END_REL = 2.0 ** -40
 
@@ -52,7 +53,7 @@ SYMBOLS = [
     "hqpkkt_bfgs_update_stage_hessians", "hqpkkt_bfgs_report",
     "hqpkkt_hessian_row_stats", "hqpkkt_restart_stage_hessians", "hqpkkt_gerschgorin_stage_hessians",
     "hqpkkt_eigen_control_stage_hessians", "hqpkkt_eigen_report",
-    "hqpkkt_eigen_control_stage_hessians_exact", "hqpkkt_eigen_report_exact",
+    "hqpkkt_eigen_control_stage_hessians_exact", "hqpkkt_eigen_report_exact", "hqpkkt_eigen_control_stage_hessians_wide",
     "hqpkkt_debug_gemm_schedule",
     "hqpkkt_debug_gemv_dense", "hqpkkt_debug_symv", "hqpkkt_debug_symv_batch", "hqpkkt_debug_symv_map",
     "hqpkkt_debug_rows_gemv",
@@ -277,6 +278,7 @@ def lib():
     L.hqpkkt_eigen_report.argtypes = [vp, vp, vp]
     L.hqpkkt_eigen_control_stage_hessians_exact.argtypes = [vp, C.POINTER(EigenControl)]
     L.hqpkkt_eigen_report_exact.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
+    L.hqpkkt_eigen_control_stage_hessians_wide.argtypes = [vp, C.POINTER(EigenControl)]
     L.hqpkkt_q_values.argtypes = [vp, vp]
     L.hqpkkt_q_product.argtypes = [vp, vp, vp]
     L.hqpkkt_q_row_stats.argtypes = [vp, vp, vp]

@@ -126,3 +126,4 @@ __global__ void __launch_bounds__(256) k_hs_symv(const HessDesc *__restrict__ de
 #include "staged_hess_bfgs.hip.h"    // (the damped BFGS terms of that update on the device: hqpkkt_bfgs_update_stage_hessians)
 #include "staged_hess_guard.hip.h"   // (row statistics, restart_Q, Gerschgorin and the eigenvalue control: hqpkkt_hessian_row_stats ..)
 #include "staged_hess_exact.hip.h"   // (the eigenvalue control with exact eigenvalues, orders up to 2048: hqpkkt_eigen_control_stage_hessians_exact)
+#include "staged_hess_wide.hip.h"    // (... and up to 8192, several workgroups per stage: hqpkkt_eigen_control_stage_hessians_wide)

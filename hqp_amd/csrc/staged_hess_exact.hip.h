@@ -41,7 +41,7 @@
 // (11 and 25 SGPRs spilled to VGPR lanes), 41 992 B of static LDS each, no scratch, no VGPR spill; k_hx_ritz 64 VGPRs,
 // 96 KB of dynamic LDS, no scratch, no spill.
 // Plain loads and stores in the handle's stream.  No contraction; sums that fuse say __fma_rn (and the matrix pipe fuses).
-// Not built: stages over 2048 (the Lanczos entry serves them); several workgroups per stage; the control chained from the
+// Stages over 2048 and several workgroups per stage: staged_hess_wide.hip.h.  Not built: the control chained from the
 // BFGS update's launch sequence.  Included by staged_hess.hip.h behind staged_hess_guard.hip.h.
 #pragma once
 #include "staged_hess_guard.hip.h"

@@ -108,6 +108,7 @@ struct HessCall {
       return e;
     HIPCHK(q.hfloor.alloc(K1, hipHostMallocDefault));
     HIPCHK(hipEventCreateWithFlags(&q.ev.h, hipEventDisableTiming));
+    q.hdesc = gd;  // (the wide control hands k_hx_block a copy with the wide stages' orders 0)
     return q.desc.upload(gd);
   }
   // ... and their row pass: rowmax and offsum (either may be null) of every stage, device vectors of n
@@ -173,8 +174,9 @@ int hess_read_back(hqpkkt_t *h, double *a, const DBuf<double> &A, double *b = nu
 
 // what the exact control makes at its first call, ahead of every launch: T at stride nz_max; the slots of k_hx_block,
 // slots = min(K + 1, CUs, what 4 GiB hold) - capped by the test hook HQPKKT_HX_SLOTS, read here -, each an image of LD x LD
-// doubles, LD the largest stage order rounded up to 16, and two panels of LD x 32; and the dynamic LDS of k_hx_ritz, 96 KB,
-// set once per device (a device that refuses it: HQPKKT_E_DEVICE).  All or nothing: a failure leaves the handle as it was
+// doubles, LD the largest stage order k_hx_block serves (on a handle of the exact entry: the largest) rounded up to 16, and
+// two panels of LD x 32; and the dynamic LDS of k_hx_ritz, 96 KB, set once per device (a device that refuses it:
+// HQPKKT_E_DEVICE).  All or nothing: a failure leaves the handle as it was
 int hx_prepare(hqpkkt_t *h, HessCall &c) {
   StagedDev::Hessians::Guard &g = c.d.hess.guard;
   static std::mutex attr_mutex;
@@ -189,8 +191,11 @@ int hx_prepare(hqpkkt_t *h, HessCall &c) {
   if (g.xws.p) return 0;
   int cus = 0;
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
-  const int ld = (g.nz_max + 15) & ~15;
-  const size_t slot = stg::hx_slot_doubles(ld) * sizeof(double), most = ((size_t)4 << 30) / slot;
+  int short_max = 0;
+  for (int k = 0; k < c.K1; k++)
+    if (c.P.hess_order(k) <= stg::HX_MAX) short_max = std::max(short_max, c.P.hess_order(k));
+  const int ld = (short_max + 15) & ~15;
+  const size_t slot = std::max<size_t>(stg::hx_slot_doubles(ld), 1) * sizeof(double), most = ((size_t)4 << 30) / slot;
   int slots = (int)std::min<size_t>(std::min(c.K1, std::max(cus, 1)), most);
   if (const char *cap = getenv("HQPKKT_HX_SLOTS"))
     if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
@@ -200,6 +205,76 @@ int hx_prepare(hqpkkt_t *h, HessCall &c) {
   g.xws = std::move(ws), g.xT = std::move(T), g.x_slots = slots, g.x_ld = ld;
   return 0;
 }
+// ... and the wide control, behind hx_prepare: w_slots = min(wide stages there can be, CUs, what 4 GiB hold) slots - capped
+// by the test hook HQPKKT_HW_SLOTS, read here - of hw_slot_doubles(LD), LD the largest stage order rounded up to 16; six work
+// arrays of nz_max per stage for k_hw_ritz; the per-call descriptors and list; and the dynamic LDS of k_hw_pass, v of a
+// stage of 8192 and the parts, set once per device.  All or nothing
+int hw_prepare(hqpkkt_t *h, HessCall &c) {
+  StagedDev::Hessians::Guard &g = c.d.hess.guard;
+  static std::mutex attr_mutex;
+  static bool raised[64];
+  int e;
+  if ((e = hx_prepare(h, c))) return e;
+  {
+    std::lock_guard<std::mutex> lk(attr_mutex);
+    if (!raised[h->opts.device])
+      HIPCHK(hipFuncSetAttribute((const void *)stg::k_hw_pass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * (256 + stg::HW_MAX))));
+    raised[h->opts.device] = true;
+  }
+  if (g.wws.p) return 0;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+  const int ld = (g.nz_max + 15) & ~15;
+  const size_t most = ((size_t)4 << 30) / (stg::hw_slot_doubles(ld) * sizeof(double));
+  int slots = (int)std::max<size_t>(std::min<size_t>(std::min(c.K1, std::max(cus, 1)), most), 1);
+  if (const char *cap = getenv("HQPKKT_HW_SLOTS"))
+    if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
+  DBuf<double> ws, rz;
+  DBuf<stg::HgDesc> wd;
+  DBuf<int> wl;
+  PinnedBuf<stg::HgDesc> hwd;
+  PinnedBuf<int> hwl;
+  if ((e = ws.alloc((size_t)slots * stg::hw_slot_doubles(ld))) || (e = rz.alloc((size_t)c.K1 * 6 * g.nz_max)) || (e = wd.alloc(c.K1)) || (e = wl.alloc(c.K1))) return e;
+  HIPCHK(hwd.alloc(c.K1, hipHostMallocDefault));
+  HIPCHK(hwl.alloc(c.K1, hipHostMallocDefault));
+  g.wws = std::move(ws), g.wrz = std::move(rz), g.wdesc = std::move(wd), g.wlist = std::move(wl), g.hwdesc = std::move(hwd), g.hwlist = std::move(hwl);
+  g.w_slots = slots, g.w_ld = ld;
+  return 0;
+}
+// the test hooks of the wide control, read per call: HQPKKT_HW_FROM, the smallest order that takes the k_hw_* kernels (1 ..
+// 2049, the default: k_hx_block serves no more than 2048), and HQPKKT_HW_GROUPS, the most workgroups per slot of k_hw_pass
+int hw_env(const char *name, int lo, int hi, int dflt) {
+  const char *v = getenv(name);
+  return v && atoi(v) >= lo && atoi(v) <= hi ? atoi(v) : dflt;
+}
+// The wide stages `wide` (longest first) in batches of w_slots, all slots of a batch in lockstep: the copy, then per column k
+// k_hw_column (finish k - 1, form k; behind a whole panel finish, k_hw_update, form) and k_hw_pass; then k_hw_ritz over all
+void hw_launches(hqpkkt_t *h, HessCall &c, const std::vector<int> &wide) {
+  StagedDev::Hessians::Guard &g = c.d.hess.guard;
+  const int nw = (int)wide.size(), cap = g.nz_max, LD = g.w_ld, NB = stg::HW_NB, M = stg::HW_M;
+  const int groups = hw_env("HQPKKT_HW_GROUPS", 1, stg::HW_G, stg::HW_G);
+  const double *Q = c.d.hess.Q.p, *rep = g.rep.p;
+  for (int b0 = 0; b0 < nw; b0 += g.w_slots) {
+    const unsigned nb = (unsigned)std::min(g.w_slots, nw - b0);
+    const int *wl = g.wlist.p + b0;
+    const int Lb = c.P.hess_order(wide[b0]), nT = (Lb + M - 1) / M;
+    KLAUNCH(h, KC_VECTOR, stg::k_hw_copy<<<dim3((unsigned)(nT * (nT + 1) / 2), nb), 256, 0, h->stream>>>(g.desc.p, wl, Q, cap, g.xT.p, rep, g.wws.p, LD));
+    for (int k = 0; k < Lb; k++) {
+      if (k > 0 && k % NB == 0) {
+        const int left = nT - k / M;
+        KLAUNCH(h, KC_VECTOR, stg::k_hw_column<<<nb, stg::HW_NT, 0, h->stream>>>(g.desc.p, wl, cap, g.xT.p, rep, g.wws.p, LD, k - 1, -1));
+        KLAUNCH(h, KC_VECTOR, stg::k_hw_update<<<dim3((unsigned)(left * (left + 1) / 2), nb), 256, 0, h->stream>>>(g.desc.p, wl, rep, cap, g.wws.p, LD, k));
+        KLAUNCH(h, KC_VECTOR, stg::k_hw_column<<<nb, stg::HW_NT, 0, h->stream>>>(g.desc.p, wl, cap, g.xT.p, rep, g.wws.p, LD, -1, k));
+      } else
+        KLAUNCH(h, KC_VECTOR, stg::k_hw_column<<<nb, stg::HW_NT, 0, h->stream>>>(g.desc.p, wl, cap, g.xT.p, rep, g.wws.p, LD, k - 1, k));
+      if (k + 2 < Lb) {  // (the last two columns form no reflector)
+        const int m = Lb - k - 1;
+        KLAUNCH(h, KC_VECTOR, stg::k_hw_pass<<<dim3((unsigned)std::min((m + M - 1) / M, groups), nb), 256, sizeof(double) * (256 + m), h->stream>>>(g.desc.p, wl, rep, cap, g.wws.p, LD, k));
+      }
+    }
+  }
+  KLAUNCH(h, KC_VECTOR, stg::k_hw_ritz<<<(unsigned)nw, 64, 0, h->stream>>>(g.desc.p, g.wlist.p, cap, g.xT.p, g.rep.p, g.wrz.p));
+}
 // rows in flight per wavefront of k_hx_block's pass: HX_ROWS by the measurement in DESIGN.md; HQPKKT_HX_ROWS (4 or 8) is the
 // hook that measurement used, read per call - both instances give the same bits
 const int HX_ROWS = 4;
@@ -208,13 +283,17 @@ int hx_rows() {
   return v && (atoi(v) == 4 || atoi(v) == 8) ? atoi(v) : HX_ROWS;
 }
 
-// Both eigenvalue controls: hqpkkt_eigen_control_stage_hessians (Lanczos) and, exact, .._exact.  One preamble - the tests
-// of the arguments in the header's order, the floors through the pinned words, the row pass and k_he_start -, then the
-// recurrence or the reduction, then the shifts of the report by k_hg_diag.  Nothing is read back
-int eigen_control_call(hqpkkt_t *h, const hqpkkt_eigen_control *ec, bool exact) {
+// The three eigenvalue controls: hqpkkt_eigen_control_stage_hessians (Lanczos), .._exact and .._wide (both exact: the
+// reduction, and the report through hqpkkt_eigen_report_exact).  One preamble - the tests of the arguments in the header's
+// order, the floors through the pinned words, the row pass and k_he_start -, then the recurrence or the reduction, then the
+// shifts of the report by k_hg_diag.  Nothing is read back
+enum EigenMode { EIG_LANCZOS, EIG_EXACT, EIG_WIDE };
+int eigen_control_call(hqpkkt_t *h, const hqpkkt_eigen_control *ec, EigenMode mode) {
+  const bool exact = mode != EIG_LANCZOS, wide = mode == EIG_WIDE;
   if (!h || !ec) return HQPKKT_E_NULL;
   static_assert(stg::HE_MAX_STEPS == HQPKKT_EIG_MAX_STEPS && stg::HE_REPORT == HQPKKT_EIG_REPORT, "the kernels size T and the report");
   static_assert(stg::HX_MAX == HQPKKT_EIG_EXACT_MAX, "the kernels size their LDS by it");
+  static_assert(stg::HW_MAX == HQPKKT_EIG_WIDE_MAX, "the kernels size their partial sums by it");
   if (!std::isfinite(ec->eps) || !(ec->eps > 0.0) || ec->max_steps < 0 || ec->max_steps > (exact ? 0 : HQPKKT_EIG_MAX_STEPS)) return HQPKKT_E_RANGE;
   if (!HessCall::ready(h)) return HQPKKT_E_INTERN;
   HessCall c(h);
@@ -223,17 +302,31 @@ int eigen_control_call(hqpkkt_t *h, const hqpkkt_eigen_control *ec, bool exact) 
   for (int k = 0; k < K1 && ec->floor; k++)
     if (!std::isfinite(ec->floor[k])) return HQPKKT_E_RANGE;
   for (int k = 0; k < K1 && exact; k++)
-    if (c.P.hess_order(k) > HQPKKT_EIG_EXACT_MAX) return HQPKKT_E_SIZES;
+    if (c.P.hess_order(k) > (wide ? HQPKKT_EIG_WIDE_MAX : HQPKKT_EIG_EXACT_MAX)) return HQPKKT_E_SIZES;
   int e;
   if ((e = c.all_arrived(nullptr))) return e;
   if (ec->floor_from_bfgs && !c.d.hess.bfgs.done) return HQPKKT_E_INTERN;
   if ((e = c.device(true))) return e;
   StagedDev::Hessians::Guard &g = c.d.hess.guard;
-  if (exact && g.nz_max > 0 && (e = hx_prepare(h, c))) return e;
+  if (exact && g.nz_max > 0 && (e = wide ? hw_prepare(h, c) : hx_prepare(h, c))) return e;
   // the floors the caller gave, NaN where theta_k comes from eps: through the pinned words, in the handle's stream
   HIPCHK(hipEventSynchronize(g.ev));  // (the copy of the last call's floors out of the pinned words)
   for (int k = 0; k < K1; k++) g.hfloor.p[k] = ec->floor ? ec->floor[k] : std::numeric_limits<double>::quiet_NaN();
   HIPCHK(hipMemcpyAsync(g.floor.p, g.hfloor.p, sizeof(double) * K1, hipMemcpyHostToDevice, h->stream));
+  // the wide control's third list: the stages of order HQPKKT_HW_FROM and more, longest first (equal orders by stage), and
+  // the descriptors of the others for k_hx_block and k_hx_ritz, which pass a stage of order 0 over
+  std::vector<int> wlist;
+  if (wide && g.nz_max > 0) {
+    const int from = hw_env("HQPKKT_HW_FROM", 1, stg::HX_MAX + 1, stg::HX_MAX + 1);
+    for (int k = 0; k < K1; k++) {
+      g.hwdesc.p[k] = g.hdesc[k];
+      if (g.hdesc[k].nz >= from) wlist.push_back(k), g.hwdesc.p[k].nz = 0;
+    }
+    std::stable_sort(wlist.begin(), wlist.end(), [&](int a, int b) { return g.hdesc[a].nz > g.hdesc[b].nz; });
+    std::copy(wlist.begin(), wlist.end(), g.hwlist.p);
+    HIPCHK(hipMemcpyAsync(g.wdesc.p, g.hwdesc.p, sizeof(stg::HgDesc) * K1, hipMemcpyHostToDevice, h->stream));
+    if (!wlist.empty()) HIPCHK(hipMemcpyAsync(g.wlist.p, g.hwlist.p, sizeof(int) * wlist.size(), hipMemcpyHostToDevice, h->stream));
+  }
   HIPCHK(hipEventRecord(g.ev, h->stream));
   double *os = c.work(1), *w = c.work(3);
   const int steps = exact ? 0 : std::min(ec->max_steps ? ec->max_steps : 64, g.nz_max);
@@ -256,8 +349,12 @@ int eigen_control_call(hqpkkt_t *h, const hqpkkt_eigen_control *ec, bool exact) 
     KLAUNCH(h, KC_VECTOR, stg::k_he_ritz<<<(unsigned)K1, 64, 0, h->stream>>>(g.st.p, g.T.p, g.rep.p));
   else if (g.nz_max > 0) {
     const auto block = hx_rows() == 4 ? stg::k_hx_block<16, 4> : stg::k_hx_block<16, 8>;
-    KLAUNCH(h, KC_VECTOR, block<<<(unsigned)g.x_slots, stg::HX_NT, 0, h->stream>>>(g.desc.p, K1, c.d.hess.Q.p, g.nz_max, g.xT.p, g.rep.p, g.xws.p, g.x_ld));
-    KLAUNCH(h, KC_VECTOR, stg::k_hx_ritz<<<(unsigned)K1, 64, sizeof(eig::RitzLdsT<stg::HX_MAX>), h->stream>>>(g.desc.p, g.nz_max, g.xT.p, g.rep.p));
+    const stg::HgDesc *xd = wide ? g.wdesc.p : g.desc.p;  // (the stages k_hx_block reduces)
+    if ((int)wlist.size() < K1) {
+      KLAUNCH(h, KC_VECTOR, block<<<(unsigned)g.x_slots, stg::HX_NT, 0, h->stream>>>(xd, K1, c.d.hess.Q.p, g.nz_max, g.xT.p, g.rep.p, g.xws.p, g.x_ld));
+      KLAUNCH(h, KC_VECTOR, stg::k_hx_ritz<<<(unsigned)K1, 64, sizeof(eig::RitzLdsT<stg::HX_MAX>), h->stream>>>(xd, g.nz_max, g.xT.p, g.rep.p));
+    }
+    if (!wlist.empty()) hw_launches(h, c, wlist);
   }
   c.lift_diagonal(nullptr, 0.0, g.rep.p);
   HIPCHK(hipGetLastError());
@@ -514,11 +611,15 @@ int hqpkkt_gerschgorin_stage_hessians(hqpkkt_t *h, double eps) {
 }
 
 int hqpkkt_eigen_control_stage_hessians(hqpkkt_t *h, const hqpkkt_eigen_control *ec) {
-  return guarded([&]() -> int { return eigen_control_call(h, ec, false); });
+  return guarded([&]() -> int { return eigen_control_call(h, ec, EIG_LANCZOS); });
 }
 
 int hqpkkt_eigen_control_stage_hessians_exact(hqpkkt_t *h, const hqpkkt_eigen_control *ec) {
-  return guarded([&]() -> int { return eigen_control_call(h, ec, true); });
+  return guarded([&]() -> int { return eigen_control_call(h, ec, EIG_EXACT); });
+}
+
+int hqpkkt_eigen_control_stage_hessians_wide(hqpkkt_t *h, const hqpkkt_eigen_control *ec) {
+  return guarded([&]() -> int { return eigen_control_call(h, ec, EIG_WIDE); });
 }
 
 int hqpkkt_eigen_report(hqpkkt_t *h, double *out, double *T) {

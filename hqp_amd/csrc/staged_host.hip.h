@@ -106,14 +106,21 @@ struct StagedDev {
     // control with the most steps asked for), its state, T and report per stage (read by hqpkkt_eigen_report), the floors
     // through pinned words (ev: copied), and whether a control has run since the analysis.  The exact control
     // (hqpkkt_eigen_control_stage_hessians_exact, first call): its T at stride nz_max (xT), the slots of k_hx_block (xws:
-    // x_slots images of x_ld x x_ld and their panels), and whether the last control was that one (the report's T is xT)
+    // x_slots images of x_ld x x_ld and their panels, x_ld by the largest order up to 2048), and whether the last control was
+    // that one or the wide one (the report's T is xT).  The wide control (.._wide, first call): the slots of the k_hw_* kernels
+    // (wws: w_slots of stg::hw_slot_doubles(w_ld)), the work arrays of k_hw_ritz (wrz), and per call through pinned words
+    // (copied with the floors) the descriptors k_hx_block sees - a wide stage's order 0 - and the wide stages, longest first
     struct Guard {
-      DBuf<stg::HgDesc> desc;
-      DBuf<double> scr, V, st, T, rep, floor, xT, xws;
+      DBuf<stg::HgDesc> desc, wdesc;
+      std::vector<stg::HgDesc> hdesc;
+      DBuf<double> scr, V, st, T, rep, floor, xT, xws, wws, wrz;
+      DBuf<int> wlist;
       PinnedBuf<double> hfloor;
+      PinnedBuf<stg::HgDesc> hwdesc;
+      PinnedBuf<int> hwlist;
       EventOwner ev;
       long long slots = 0;
-      int tiles_max = 0, nz_max = 0, x_slots = 0, x_ld = 0;
+      int tiles_max = 0, nz_max = 0, x_slots = 0, x_ld = 0, w_slots = 0, w_ld = 0;
       bool done = false, exact = false;
     } guard;
   } hess;

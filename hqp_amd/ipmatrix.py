@@ -971,7 +971,14 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         _check(self._L.hqpkkt_eigen_report(self._h, C.c_void_p(out.ctypes.data), None if T is None else C.c_void_p(T.ctypes.data)), "eigen_report")
         return (out, T) if with_T else out
 
-    def eigen_control_exact(self, eps, floor=None, from_bfgs=False):
+    def eigen_control_wide(self, eps, floor=None, from_bfgs=False):
+        """eigen_control_exact() for a handle whose stage orders are all at most _lib.HQPKKT_EIG_WIDE_MAX = 8192
+        (hqpkkt_eigen_control_stage_hessians_wide; a larger stage: HQPKKT_E_SIZES, nothing done).  Stages of order up to 2048
+        are reduced as there - a handle with no larger stage gets eigen_control_exact()'s bits -, the larger ones by the
+        whole chip, a few images at a time in lockstep.  eigen_report_exact() tells what every stage did."""
+        self.eigen_control_exact(eps, floor=floor, from_bfgs=from_bfgs, _entry="eigen_control_stage_hessians_wide")
+
+    def eigen_control_exact(self, eps, floor=None, from_bfgs=False, _entry="eigen_control_stage_hessians_exact"):
         """eigen_control() with the smallest eigenvalue of every stage computed, not estimated, for a handle whose stage
         orders are all at most _lib.HQPKKT_EIG_EXACT_MAX = 2048 (hqpkkt_eigen_control_stage_hessians_exact; a larger stage:
         HQPKKT_E_SIZES, nothing done): every block is reduced to a tridiagonal T of its own order by Householder reflectors
@@ -982,7 +989,7 @@ class Hqp_IpLQDOCP(Hqp_IpMatrix):
         if floor is not None:
             floor = np.ascontiguousarray(floor, dtype=np.float64).reshape(len(self.debug(20)))
             c.floor = floor.ctypes.data
-        _check(self._L.hqpkkt_eigen_control_stage_hessians_exact(self._h, C.byref(c)), "eigen_control_exact")
+        _check(getattr(self._L, "hqpkkt_" + _entry)(self._h, C.byref(c)), _entry.replace("_stage_hessians", ""))
 
     def eigen_report_exact(self, with_T=False):
         """Per stage what the last eigen_control_exact() did (hqpkkt_eigen_report_exact): eigen_report()'s array, with the

@@ -634,7 +634,35 @@ int hqpkkt_bfgs_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * 8 doubles */)
  *   Hooks (environment): HQPKKT_HX_SLOTS caps the slots (read when the workspace is made); HQPKKT_HX_ROWS = 4 or 8 selects
  *   the rows a wavefront of k_hx_block keeps in flight in the pass (read per call; default 4, the faster; the same bits).
  *   Not built: the exact control chained from hqpkkt_bfgs_update_stage_hessians (the caller makes the two calls;
- *   floor_from_bfgs works as above); stages over 2048 - an exact reduction there moves about n^3 8/3 bytes per stage.
+ *   floor_from_bfgs works as above); stages over 2048 - an exact reduction there moves about n^3 8/3 bytes per stage:
+ *   hqpkkt_eigen_control_stage_hessians_wide serves them.
+ * hqpkkt_eigen_control_stage_hessians_wide: the exact control for handles whose stage orders are all at most
+ * HQPKKT_EIG_WIDE_MAX = 8192, both layouts (kernels: staged_hess_wide.hip.h).  The struct, the floors, max_steps = 0, the
+ * refused handles and the checks are the exact entry's, in its order; HQPKKT_E_SIZES, in the exact entry's place, is kept for a
+ * stage order over 8192.  The preamble is the exact entry's (g_k, theta_k and the outcomes 0 and 5 are its bits), the shift
+ * k_hg_diag's, the report and T hqpkkt_eigen_report_exact's (T at stride the largest order); hqpkkt_eigen_report refuses T
+ * behind it as behind the exact entry.
+ *   Stages of order up to 2048 go through k_hx_block and k_hx_ritz as they are: on a handle with no stage over 2048 the
+ *   report, T and the blocks are the exact entry's, bit for bit.
+ *   Stages over 2048 are reduced by the whole chip, a few images at a time: in batches of S slots, longest first, all slots
+ *   of a batch in lockstep, one launch moving every slot by one step - k_hw_copy (the image: both layouts give the same,
+ *   symmetric bit for bit), then per column k k_hw_column (one workgroup per slot: column k - 1 finished into the panels V
+ *   and W, column k formed, alpha_k and beta_k to T) and k_hw_pass (p = A v / h over the trailing image, a workgroup per 64
+ *   rows), and per panel of 16 columns k_hw_update (A - V W' - W V' on v_mfma_f64_16x16x4 over 64 x 64 macro-tiles on and
+ *   below the diagonal, stored with their transposed images); then k_hw_ritz, a wavefront per stage, the Ritz step above with
+ *   its work arrays in device memory.  About 2 L + L / 16 launches per batch in the handle's stream; no workgroup waits for
+ *   another: no polled words, no grid-wide barriers, no atomics.  The sums run in an order fixed by the index inside the
+ *   stage: a stage's T depends on its order and its values alone - not on its slot, the batch, the layout or the hooks
+ *   below - and is equal from call to call.  It is not k_hx_block's T of the same block (other groups of the sums); both hold
+ *   the same bound against the block's eigenvalues.  A stage that holds a NaN ends with outcome 4 and is left bit-unchanged,
+ *   the other stages of its batch as without it.
+ *   Workspace, made by the first wide call and kept with the handle: what the exact entry makes, its images sized by the
+ *   largest order up to 2048; S = min(K + 1, compute units, what 4 GiB hold) slots of LD x LD + 34 LD + 8200 doubles, LD the
+ *   largest order rounded up to 16; 6 (K + 1) t_steps doubles for k_hw_ritz.  HQPKKT_E_MEM or HQPKKT_E_DEVICE before any launch.
+ *   Hooks (environment): HQPKKT_HW_FROM, the smallest order that takes the k_hw_* kernels (1 .. 2049, default 2049, read per
+ *   call, this entry alone); HQPKKT_HW_SLOTS caps S (read when the workspace is made); HQPKKT_HW_GROUPS caps the workgroups
+ *   per slot of k_hw_pass, a workgroup then walks several row groups (read per call; the same bits).
+ *   Not built: orders over 8192; one triangle of the image stored; the control chained from the BFGS update.
  * Not built: sharded handles and the CSR hand-over.  (The reference's Hqp_HL_DScale works on the sparse Q: the hqpkkt_q_*
  * entries below.) */
 #define HQPKKT_EIG_MAX_STEPS 128
@@ -655,6 +683,8 @@ int hqpkkt_eigen_report(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_R
 int hqpkkt_eigen_control_stage_hessians_exact(hqpkkt_t *h, const hqpkkt_eigen_control *e); /* every stage order <= HQPKKT_EIG_EXACT_MAX; max_steps must be 0 */
 int hqpkkt_eigen_report_exact(hqpkkt_t *h, double *out /* HOST, (K + 1) * HQPKKT_EIG_REPORT */, double *T /* HOST or NULL: (K + 1) * 2 * *t_steps */,
                               int *t_steps /* the largest stage order */);
+#define HQPKKT_EIG_WIDE_MAX 8192
+int hqpkkt_eigen_control_stage_hessians_wide(hqpkkt_t *h, const hqpkkt_eigen_control *e); /* every stage order <= HQPKKT_EIG_WIDE_MAX; max_steps must be 0 */
 /* ---- The sparse Q where it lies on the device: the reference's Hessian approximations that work on Hqp_Program::Q itself
  * (Hqp_HL::init, Hqp_HL_Gerschgorin, Hqp_HL_DScale - what hqp_cute.tcl selects next to RedSpBKP) and grd_L of
  * Hqp_SqpSolver, without a round trip of Qx | Ax | Cx through hqpkkt_set_values.  Kernels: csrc/q_values.hip.h; host code: csrc/q_entries.hip.

@@ -16,7 +16,12 @@ python tools/eigen_control_time.py [out.txt]
 handles - 201 stages of order 1024, 21 of order 2048, 201 of order 200, no controls, one symmetric random block (eigenvalues
 within +-2 sqrt(order)) on every stage; packed and unpacked; HQPKKT_HX_ROWS 4 and 8 (read per call).  Per call by wall clock
 to a synchronisation, EXACT_REPS calls after one; the outcome counts of both entries.
-python tools/eigen_control_time.py --exact [out.txt]"""
+python tools/eigen_control_time.py --exact [out.txt]
+
+--wide: the wide control (hqpkkt_eigen_control_stage_hessians_wide) on 21 stages of order 5050 (packed and unpacked), 8 of
+order 8192, 201 of order 5050, x_0 fixed; and on 21 stages of order 2048 with HQPKKT_HW_FROM=1025 beside the exact and the
+Lanczos control.  EIGEN_TIME_ONLY=201x5050 (or 21x5050, 8x8192, 21x2048) runs that shape alone.  Appends to the file.
+python tools/eigen_control_time.py --wide [out.txt]"""
 import os
 import sys
 import time
@@ -96,6 +101,55 @@ def main_exact(out_path):
         f.write(text)
 
 
+WIDE_SHAPES = ((21, 5050, (True, False)), (8, 8192, (False,)), (201, 5050, (True,)))
+
+
+def main_wide(out_path):
+    """every call timed by wall clock to a synchronisation and listed: the first makes the workspace"""
+    rng = np.random.default_rng(5)
+    empty = lambda rows: (np.zeros(rows + 1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
+    counts = lambda rep: {int(o): int((rep[:, 9] == o).sum()) for o in np.unique(rep[:, 9])}
+    ms = lambda t: " ".join(f"{x:.1f}" for x in t)
+
+    def handle_of(stages, v, packed):
+        Ud = torch.as_tensor(rng.standard_normal((v, v))).cuda()
+        Fd = torch.zeros((v, v), dtype=torch.float64, device="cuda")
+        fix = (np.arange(v + 1, dtype=np.int32), np.arange(v, dtype=np.int32), np.ones(v))  # (x_0 fixed: the analysis holds a free one to 4096)
+        dq = problems.DenseDocp([v] * stages, [0] * (stages - 1), empty(stages * v), fix, empty(0), [Fd] * (stages - 1), v, 0, Qd=[Ud] * stages)
+        D = ipmatrix.IpLQDOCP(q_dense=True, q_packed=packed, device_vectors=True)
+        D.init_dense(dq)
+        return D
+
+    lines = [f"eigen_control_time --wide: eigen_control_wide, {torch.cuda.get_device_name(0)}; per call by wall clock to a synchronisation, "
+             f"every call listed (the first makes the workspace); ms"]
+    only = os.environ.get("EIGEN_TIME_ONLY")  # (a run's time limit: one shape per run, e.g. 201x5050)
+    for stages, v, layouts in WIDE_SHAPES:
+        if only and only != f"{stages}x{v}":
+            continue
+        for packed in layouts:
+            D = handle_of(stages, v, packed)
+            t = timed(lambda: D.eigen_control_wide(EPS), 1 if stages > 100 else 3)
+            lines.append(f"{stages} stages of order {v}, {'packed' if packed else 'unpacked'}: wide {ms(t)};  outcomes {counts(D.eigen_report_exact())}")
+            print(lines[-1], flush=True)
+            del D
+    if not only or only == "21x2048":
+        D = handle_of(21, 2048, True)
+        os.environ["HQPKKT_HW_FROM"] = "1025"
+        t = timed(lambda: D.eigen_control_wide(EPS), 3)
+        del os.environ["HQPKKT_HW_FROM"]
+        out_w = counts(D.eigen_report_exact())
+        tx = timed(lambda: D.eigen_control_exact(EPS), 3)
+        out_x = counts(D.eigen_report_exact())
+        tl = timed(lambda: D.eigen_control(EPS), 3)
+        lines.append(f"21 stages of order 2048, packed: wide (HQPKKT_HW_FROM=1025) {ms(t)};  exact {ms(tx)};  Lanczos, 64 steps {ms(tl)};  outcomes wide {out_w}, "
+                     f"exact {out_x}, Lanczos {counts(D.eigen_report())}")
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:  # (behind the --exact lines of the same file)
+        f.write(text)
+
+
 def main(out_path):
     rng = np.random.default_rng(5)
     U = rng.standard_normal((NZ[0], NZ[0]))  # (the upper triangle is read: a symmetric matrix with eigenvalues within +-2 sqrt(order))
@@ -138,6 +192,10 @@ def main(out_path):
 
 
 if __name__ == "__main__":
+    if "--wide" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--wide"]
+        main_wide(rest[0] if rest else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eigen_control_time.txt"))
+        sys.exit(0)
     if "--exact" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--exact"]
         main_exact(rest[0] if rest else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eigen_control_time.txt"))

@@ -26,6 +26,7 @@ HQPKKT_QBFGS_REPORT = 8
 HQPKKT_EIG_MAX_STEPS = 128
 HQPKKT_QEIG_LONG_MAX = 512
 HQPKKT_QEIG_BLOCKED_MAX = 2048
+HQPKKT_QEIG_WIDE_MAX = 8192
 HQPKKT_EIG_EXACT_MAX = 2048
 HQPKKT_EIG_WIDE_MAX = 8192
 HQPKKT_EIG_REPORT = 10
@@ -62,7 +63,7 @@ SYMBOLS = [
     "hqpkkt_q_blocks", "hqpkkt_q_bfgs_update", "hqpkkt_q_bfgs_report",
     "hqpkkt_q_components", "hqpkkt_q_sparse_bfgs_update", "hqpkkt_q_sparse_bfgs_report",
     "hqpkkt_q_eigen_control", "hqpkkt_q_eigen_report", "hqpkkt_q_eigen_control_short",
-    "hqpkkt_q_eigen_control_exact", "hqpkkt_q_eigen_control_long", "hqpkkt_q_eigen_control_blocked", "hqpkkt_lagrangian_gradient_staged",
+    "hqpkkt_q_eigen_control_exact", "hqpkkt_q_eigen_control_long", "hqpkkt_q_eigen_control_blocked", "hqpkkt_q_eigen_control_wide", "hqpkkt_lagrangian_gradient_staged",
     "hqpkkt_debug_ip_vec", "hqpkkt_debug_ip_rows",
 ]
 RCCL_LIB_PATH = os.path.join(_HERE, "libhqpkkt_rccl.so")
@@ -300,6 +301,7 @@ def lib():
     L.hqpkkt_q_eigen_control_exact.argtypes = [vp, C.POINTER(QEigenControl)]
     L.hqpkkt_q_eigen_control_long.argtypes = [vp, C.POINTER(QEigenControl)]
     L.hqpkkt_q_eigen_control_blocked.argtypes = [vp, C.POINTER(QEigenControl)]
+    L.hqpkkt_q_eigen_control_wide.argtypes = [vp, C.POINTER(QEigenControl)]
     L.hqpkkt_q_eigen_report.argtypes = [vp, vp, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     L.hqpkkt_debug_stage_ranks.argtypes = [vp, vp, C.c_int]
     L.hqpkkt_analyze_staged.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 6

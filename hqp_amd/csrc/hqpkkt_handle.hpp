@@ -324,6 +324,19 @@ struct TreeDev {
       int blk_slots = 0, blk_ld = 0;        // workgroups of k_qeb_block, one slot each; an image's leading dimension
       DBuf<int> blk_list;
       DBuf<double> blk_ws;
+      // hqpkkt_q_eigen_control_wide (q_eigen_wide.hip.h): the blocks at least wide_from long, longest first (equal lengths by
+      // block), the runs [a, b) of the blocks between them, and the three lists above without them - all made again where a
+      // call's HQPKKT_QEW_FROM is not wide_from; the slots' workspace and the work arrays of k_qew_ritz (6 per listed block,
+      // max_len each), made by the first call that needs them
+      struct WideLists {
+        int from = -1;                      // (-1: not made yet)
+        std::vector<int> wide, runs;        // runs: a, b, a, b, ..
+        int short_max = 0, mid_count = 0, mid_max = 0, long_count = 0, blk_count = 0;
+        DBuf<int> wide_list, mid_list, long_list, blk_list;
+      } wl;
+      int wide_slots = 0, wide_ld = 0;      // slots of the workspace; LD of a slot: max_len rounded up to 64
+      size_t wide_rz = 0;                   // listed blocks the work arrays hold
+      DBuf<double> wide_ws, wide_ritz;
     };
     std::vector<BfgsPlan> bfgs_plans;
     int bfgs_last = -1, ds_last = -1; // plan of the last BFGS update / the last DScale update since the analysis

@@ -1,10 +1,10 @@
-// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 22 of them:
+// The entries of the C ABI (include/hqpkkt.h) on the sparse Q of the program where it lies on the device, 23 of them:
 // hqpkkt_q_values .. hqpkkt_q_dscale_report (kernels: q_values.hip.h), hqpkkt_q_blocks, hqpkkt_q_bfgs_update and its report
 // (q_bfgs.hip.h), hqpkkt_q_components, hqpkkt_q_sparse_bfgs_update and its report (q_sparse_bfgs.hip.h),
 // hqpkkt_q_eigen_control and its report (q_eigen.hip.h), hqpkkt_q_eigen_control_short (q_eigen_short.hip.h),
 // hqpkkt_q_eigen_control_exact (q_eigen_mid.hip.h beside it), hqpkkt_q_eigen_control_long (q_eigen_long.hip.h beside both),
-// hqpkkt_q_eigen_control_blocked (q_eigen_blocked.hip.h beside all three) and hqpkkt_lagrangian_gradient.  Their state is
-// TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
+// hqpkkt_q_eigen_control_blocked (q_eigen_blocked.hip.h beside all three), hqpkkt_q_eigen_control_wide (q_eigen_wide.hip.h
+// beside all four) and hqpkkt_lagrangian_gradient.  Their state is TreeDev::QVal; everything else they use of the handle is declared in hqpkkt_handle.hpp.
 // The damped updates - Hqp_HL_DScale::update on the diagonal, Hqp_HL_BFGS on the blocks - are ONE pipeline over the plan of
 // a partition (qb_plan): the sums of the units, the decision per block, v and s'v, the outcome per block, and then the
 // update's own write (k_qv_ds_apply per variable, k_qb_apply per stored entry).  The eigenvalue control runs over the
@@ -21,6 +21,7 @@
 #include "q_eigen_mid.hip.h"
 #include "q_eigen_long.hip.h"
 #include "q_eigen_blocked.hip.h"
+#include "q_eigen_wide.hip.h"
 
 using QPlan = TreeDev::QVal::BfgsPlan;
 
@@ -706,7 +707,127 @@ static int qel_threads() {
   return v ? atoi(v) : QEL_THREADS;
 }
 
-// the four entries: `longest` is the block length the entry serves, 64, 128, 512 or 2048
+// ---- and on blocks up to 8192: the blocks of HQPKKT_QEW_FROM and more by the whole chip, a few slots in lockstep, one lower
+// triangle of the image stored (q_eigen_wide.hip.h); the others by the kernels above, over lists without them
+
+// the test hooks of the wide control, read per call: HQPKKT_QEW_FROM, the smallest block length that takes the k_qew_* kernels
+// (1 .. 2049, the default: k_qeb_block serves no more than 2048), and HQPKKT_QEW_GROUPS, the most workgroups per slot of
+// k_qew_pass
+static int qew_env(const char *name, int lo, int hi, int dflt) {
+  const char *v = getenv(name);
+  return v && atoi(v) >= lo && atoi(v) <= hi ? atoi(v) : dflt;
+}
+// one pass over the plan for a threshold `from`: the blocks that long, longest first; the runs of blocks between them for
+// k_qes_block; the lists of qem_list without them.  Kept with the plan until a call comes with another threshold
+static int qew_lists(hqpkkt_t *h, QPlan &p, int from) {
+  if (p.wl.from == from) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (a control still in the stream reads the old lists)
+  QPlan::WideLists w;
+  std::vector<int> mid, lng, blk;
+  for (int b = 0; b < p.nblocks; b++) {
+    const int len = p.first[b + 1] - p.first[b];
+    if (len >= from) {
+      w.wide.push_back(b);
+      continue;
+    }
+    if (!w.runs.empty() && w.runs.back() == b)
+      w.runs.back() = b + 1;
+    else
+      w.runs.push_back(b), w.runs.push_back(b + 1);
+    if (len >= qv::QEB_MIN)
+      blk.push_back(b);
+    else if (len >= qv::QEL_MIN)
+      lng.push_back(b);
+    else if (len >= qv::QEM_MIN)
+      mid.push_back(b), w.mid_max = std::max(w.mid_max, len);
+    else
+      w.short_max = std::max(w.short_max, len);
+  }
+  std::stable_sort(w.wide.begin(), w.wide.end(), [&](int a, int b) { return p.first[a + 1] - p.first[a] > p.first[b + 1] - p.first[b]; });
+  w.mid_count = (int)mid.size(), w.long_count = (int)lng.size(), w.blk_count = (int)blk.size();
+  int e;
+  if ((e = w.wide_list.upload(w.wide)) || (e = w.mid_list.upload(mid)) || (e = w.long_list.upload(lng)) || (e = w.blk_list.upload(blk))) return e;
+  w.from = from;
+  p.wl = std::move(w);
+  return 0;
+}
+// the slots of k_qew_*: slots = min(listed blocks, CUs, what 4 GiB and half the free memory hold) - capped by the test hook
+// HQPKKT_QEW_SLOTS, read here -, each qew_slot_doubles(LD), LD the plan's longest block rounded up to 64: made once and kept
+// with the plan; six work arrays of max_len per listed block for k_qew_ritz, grown where a call lists more; and the dynamic
+// LDS of k_qew_pass, v of a block of 8192 and the parts, set once per device.  All or nothing
+static int qew_workspace(hqpkkt_t *h, QPlan &p) {
+  const size_t count = p.wl.wide.size();
+  if (!count) return 0;
+  static std::mutex attr_mutex;
+  static bool raised[64];
+  if (h->opts.device < 0 || h->opts.device >= 64) return HQPKKT_E_RANGE;
+  {
+    std::lock_guard<std::mutex> lk(attr_mutex);
+    if (!raised[h->opts.device])
+      HIPCHK(hipFuncSetAttribute((const void *)qv::k_qew_pass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * qv::qew_pass_doubles(qv::QEW_MAX))));
+    raised[h->opts.device] = true;
+  }
+  DBuf<double> ws, rz;
+  int e, slots = p.wide_slots;
+  const int ld = (p.max_len + qv::QEW_M - 1) & ~(qv::QEW_M - 1);
+  if (p.wide_rz < count) {
+    HIPCHK(hipStreamSynchronize(h->stream));  // (a control still in the stream uses the old arrays)
+    if ((e = rz.alloc(6 * (size_t)p.max_len * count))) return e;
+  }
+  if (!p.wide_ws.p) {
+    int cus = 0;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->opts.device));
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t slot = qv::qew_slot_doubles(ld) * sizeof(double), most = std::max<size_t>(std::min<size_t>((size_t)4 << 30, free_b / 2) / slot, 1);
+    slots = (int)std::min<size_t>(std::min<size_t>(count, (size_t)std::max(cus, 1)), most);
+    if (const char *cap = getenv("HQPKKT_QEW_SLOTS"))
+      if (atoi(cap) > 0) slots = std::min(slots, atoi(cap));
+    if ((e = ws.alloc((size_t)slots * qv::qew_slot_doubles(ld)))) return e;
+  }
+  if (rz.p) p.wide_ritz = std::move(rz), p.wide_rz = count;
+  if (ws.p) p.wide_ws = std::move(ws), p.wide_slots = slots, p.wide_ld = ld;
+  return 0;
+}
+// The listed blocks in batches of wide_slots, all slots of a batch in lockstep: the gather, the off-diagonal sums and the
+// start, then per column k k_qew_column (finish k - 1, form k; behind a whole panel finish, k_qew_update, form) and k_qew_pass;
+// then k_qew_ritz over all, and the shift over the rows of each
+static void qew_launches(hqpkkt_t *h, const QPlan &p, const double *flr, double eps2, const double *bfgs, int cap) {
+  const int nw = (int)p.wl.wide.size(), LD = p.wide_ld, NB = qv::QEW_NB, M = qv::QEW_M;
+  const int groups = qew_env("HQPKKT_QEW_GROUPS", 1, qv::QEW_G, qv::QEW_G);
+  const int *boff = p.boff.p;
+  double *T = p.eig_T.p, *rep = p.eig_rep.p, *ws = p.wide_ws.p;
+  hipStream_t s = h->stream;
+  for (int b0 = 0; b0 < nw; b0 += p.wide_slots) {
+    const unsigned nb = (unsigned)std::min(p.wide_slots, nw - b0);
+    const int *wl = p.wl.wide_list.p + b0;
+    const int Lb = p.first[p.wl.wide[b0] + 1] - p.first[p.wl.wide[b0]], nT = (Lb + M - 1) / M;
+    qv::k_qew_gather<<<dim3((unsigned)nT, nb), 256, 0, s>>>(wl, boff, h->td.Qf.dev(), cap, ws, LD);
+    qv::k_qew_offsum<<<dim3((unsigned)nT, nb), 64, 0, s>>>(wl, boff, cap, ws, LD);
+    qv::k_qew_start<<<nb, 256, 0, s>>>(wl, boff, flr, eps2, bfgs, cap, T, rep, ws, LD);
+    for (int k = 0; k < Lb; k++) {
+      if (k > 0 && k % NB == 0) {
+        const int left = nT - k / M;
+        qv::k_qew_column<<<nb, qv::QEW_NT, 0, s>>>(wl, boff, cap, T, rep, ws, LD, k - 1, -1);
+        qv::k_qew_update<<<dim3((unsigned)(left * (left + 1) / 2), nb), 256, 0, s>>>(wl, boff, rep, cap, ws, LD, k);
+        qv::k_qew_column<<<nb, qv::QEW_NT, 0, s>>>(wl, boff, cap, T, rep, ws, LD, -1, k);
+      } else
+        qv::k_qew_column<<<nb, qv::QEW_NT, 0, s>>>(wl, boff, cap, T, rep, ws, LD, k - 1, k);
+      if (k + 2 < Lb) {  // (the last two columns form no reflector)
+        const int rows = nT - (k + 1) / M;  // the tile rows that hold an index > k
+        qv::k_qew_pass<<<dim3((unsigned)std::min(rows, groups), nb), qv::QEW_PNT, sizeof(double) * qv::qew_pass_doubles(M * rows), s>>>(wl, boff, rep, cap, ws, LD, k);
+      }
+    }
+  }
+  qv::k_qew_ritz<<<(unsigned)nw, 64, 0, s>>>(p.wl.wide_list.p, boff, cap, T, rep, p.wide_ritz.p);
+  for (int b : p.wl.wide) {
+    const int first = p.first[b], len = p.first[b + 1] - first;
+    qv::k_qe_shift<<<nblk(len), 256, 0, s>>>(len, p.blk_of.p + first, h->td.qv.didx.p + first, rep, h->td.vals.p);
+  }
+}
+
+// the five entries: `longest` is the block length the entry serves, 64, 128, 512, 2048 or 8192 (the wide entry: the blocks
+// of its threshold and more through qew_launches, the lists of the others from qew_lists)
 static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int longest) {
   return guarded([&]() -> int {
     if (!h || !ec) return HQPKKT_E_NULL;
@@ -728,11 +849,18 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
     if ((e = qb_plan(h, ec->bsize, true, &at))) return e;
     QPlan &p = q.bfgs_plans[at];
     if ((e = qes_buffers(h, p))) return e;
-    const bool mid = cap > 64;  // (the plan has blocks for k_qem_block)
+    const bool wide = longest == qv::QEW_MAX;
+    const bool mid = cap > 64 || wide;  // (the plan has blocks for k_qem_block)
     if (mid && (e = qem_list(p))) return e;
-    const bool lng = mid && p.long_count > 0;  // (and blocks for k_qel_block)
-    const bool blk = mid && p.blk_count > 0;   // (and blocks for k_qeb_block)
-    if ((lng && (e = qel_workspace(h, p))) || (mid && p.mid_count > 0 && (e = qem_raise_lds(h)))) return e;
+    if (wide && ((e = qew_lists(h, p, qew_env("HQPKKT_QEW_FROM", 1, qv::QEW_MIN, qv::QEW_MIN))) || (e = qew_workspace(h, p)))) return e;
+    // the lists of this call: the plan's, or the wide entry's without its own blocks (the same where it has none)
+    const QPlan::WideLists &w = p.wl;
+    const int mid_count = wide ? w.mid_count : mid ? p.mid_count : 0, mid_max = wide ? w.mid_max : p.mid_max;
+    const int long_count = wide ? w.long_count : mid ? p.long_count : 0, blk_count = wide ? w.blk_count : mid ? p.blk_count : 0;
+    const int *mid_list = wide ? w.mid_list.p : p.mid_list.p, *long_list = wide ? w.long_list.p : p.long_list.p, *blk_list = wide ? w.blk_list.p : p.blk_list.p;
+    const bool lng = long_count > 0;  // (blocks for k_qel_block)
+    const bool blk = blk_count > 0;   // (and for k_qeb_block)
+    if ((lng && (e = qel_workspace(h, p))) || (mid_count > 0 && (e = qem_raise_lds(h)))) return e;
     if (blk && ((e = qeb_workspace(h, p)) || (e = qeb_raise_lds(h)))) return e;
     hipStream_t s = h->stream;
     if (ec->floor) {  // (as hqpkkt_q_eigen_control: the caller's again on return)
@@ -742,28 +870,34 @@ static int qes_control(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec, int l
     const double *flr = ec->floor ? p.eig_floor.p : nullptr, *bfgs = ec->floor_from_bfgs ? p.rep.p : nullptr;
     const double eps2 = ec->eps * ec->eps;
     // the instance by the LDS of its image: the smallest that holds the longest block of at most 64, which returns at
-    // once on a longer one
-    const int sm = mid ? p.short_max : cap;
+    // once on a longer one; the wide entry launches it over the runs of blocks between its own
+    const int sm = wide ? w.short_max : mid ? p.short_max : cap;
     const auto block = pick(sm > 16, pick(sm > 8, qv::k_qes_block<8>, qv::k_qes_block<16>), pick(sm > 32, qv::k_qes_block<32>, qv::k_qes_block<64>));
-    block<<<(unsigned)p.nblocks, 64, 0, s>>>(p.boff.p, h->td.Qf.dev(), q.didx.p, h->td.vals.p, flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
-    if (mid && p.mid_count > 0) {
-      const bool big = p.mid_max > 96;
-      pick(big, qv::k_qem_block<96>, qv::k_qem_block<128>)<<<(unsigned)p.mid_count, 256, big ? qv::qem_lds_bytes<128>() : qv::qem_lds_bytes<96>(), s>>>(
-          p.mid_list.p, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
-      qv::k_qem_ritz<<<(unsigned)p.mid_count, 64, 0, s>>>(p.mid_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
+    const int whole[2] = {0, p.nblocks};
+    const int *runs = wide ? w.runs.data() : whole;
+    for (size_t r = 0; r < (wide ? w.runs.size() : 2); r += 2) {
+      const long long a = runs[r];
+      block<<<(unsigned)(runs[r + 1] - runs[r]), 64, 0, s>>>(p.boff.p + a, h->td.Qf.dev(), q.didx.p, h->td.vals.p, flr ? flr + a : nullptr, eps2,
+                                                          bfgs ? bfgs + qv::QV_REPORT * a : nullptr, cap, p.eig_T.p + 2 * (long long)cap * a, p.eig_rep.p + qv::QE_REPORT * a);
+    }
+    if (mid_count > 0) {
+      const bool big = mid_max > 96;
+      pick(big, qv::k_qem_block<96>, qv::k_qem_block<128>)<<<(unsigned)mid_count, 256, big ? qv::qem_lds_bytes<128>() : qv::qem_lds_bytes<96>(), s>>>(
+          mid_list, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p);
+      qv::k_qem_ritz<<<(unsigned)mid_count, 64, 0, s>>>(mid_list, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
     }
     if (lng) {
-      const bool wide = qel_threads() > 512;
-      pick(wide, qv::k_qel_block<512>, qv::k_qel_block<1024>)<<<(unsigned)p.long_slots, wide ? 1024 : 512, 0, s>>>(
-          p.long_list.p, p.long_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.long_ws.p, p.long_ld);
-      qv::k_qel_ritz<<<(unsigned)p.long_count, 64, 0, s>>>(p.long_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
+      const bool many = qel_threads() > 512;
+      pick(many, qv::k_qel_block<512>, qv::k_qel_block<1024>)<<<(unsigned)std::min(p.long_slots, long_count), many ? 1024 : 512, 0, s>>>(
+          long_list, long_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.long_ws.p, p.long_ld);
+      qv::k_qel_ritz<<<(unsigned)long_count, 64, 0, s>>>(long_list, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
     }
     if (blk) {
-      pick(qeb_nb() > 16, qv::k_qeb_block<16>, qv::k_qeb_block<32>)<<<(unsigned)p.blk_slots, qv::QEB_NT, 0, s>>>(
-          p.blk_list.p, p.blk_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.blk_ws.p, p.blk_ld);
-      qv::k_qeb_ritz<<<(unsigned)p.blk_count, 64, sizeof(eig::RitzLdsT<qv::QEB_MAX>), s>>>(p.blk_list.p, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p,
-                                                                                           p.eig_rep.p);
+      pick(qeb_nb() > 16, qv::k_qeb_block<16>, qv::k_qeb_block<32>)<<<(unsigned)std::min(p.blk_slots, blk_count), qv::QEB_NT, 0, s>>>(
+          blk_list, blk_count, p.boff.p, h->td.Qf.dev(), flr, eps2, bfgs, cap, p.eig_T.p, p.eig_rep.p, p.blk_ws.p, p.blk_ld);
+      qv::k_qeb_ritz<<<(unsigned)blk_count, 64, sizeof(eig::RitzLdsT<qv::QEB_MAX>), s>>>(blk_list, p.boff.p, q.didx.p, h->td.vals.p, cap, p.eig_T.p, p.eig_rep.p);
     }
+    if (wide && !w.wide.empty()) qew_launches(h, p, flr, eps2, bfgs, cap);
     q.eig_last = at, p.eig_steps = cap;
     return qv_written(h);
   });
@@ -778,6 +912,10 @@ int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *
 int hqpkkt_q_eigen_control_blocked(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
   static_assert(qv::QEB_MAX == HQPKKT_QEIG_BLOCKED_MAX, "the kernels size their LDS by it");
   return qes_control(h, ec, qv::QEB_MAX);
+}
+int hqpkkt_q_eigen_control_wide(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *ec) {
+  static_assert(qv::QEW_MAX == HQPKKT_QEIG_WIDE_MAX, "the kernels size their partial sums by it");
+  return qes_control(h, ec, qv::QEW_MAX);
 }
 
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out, double *T, long long cap_blocks, long long *n_blocks, int *t_steps) {

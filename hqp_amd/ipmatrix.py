@@ -518,6 +518,16 @@ class Hqp_IpMatrix:
         q_eigen_control_long()'s bits; q_eigen_report() returns T of stride up to 2048."""
         self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_blocked")
 
+    def q_eigen_control_wide(self, eps, bsize=-1, floor_from_bfgs=False, floor=None):
+        """q_eigen_control_blocked() for a partition whose blocks are all at most 8192 long (_lib.HQPKKT_QEIG_WIDE_MAX;
+        hqpkkt_q_eigen_control_wide; a longer block: HQPKKT_E_SIZES, nothing done): the blocks up to 2048 as there, the
+        blocks of 2049 .. 8192 reduced by the whole chip, a few of them in lockstep, on ONE stored lower triangle of
+        64 x 64 tiles - the pass reads a tile once and uses it for its rows and for its columns, the panel update runs on
+        the matrix pipe -, then bracketed by a wavefront each and shifted.  A slot takes about L^2 / 2 + 100 L doubles at
+        the longest block L (280 MB at 8192).  A partition with no block over 2048 gives q_eigen_control_blocked()'s
+        bits; q_eigen_report() returns T of stride up to 8192."""
+        self.q_eigen_control(eps, bsize=bsize, from_bfgs=floor_from_bfgs, floor=floor, _entry="q_eigen_control_wide")
+
     def q_eigen_report(self, with_T=False):
         """Per block of the last q_eigen_control() (hqpkkt_q_eigen_report), an array of shape (blocks, 10): Gerschgorin's bound
         g, the floor theta as used, the Lanczos steps, lo, hi (the bracket of T's smallest eigenvalue), rho (the residual

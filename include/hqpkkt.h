@@ -878,9 +878,9 @@ int hqpkkt_eigen_control_stage_hessians_wide(hqpkkt_t *h, const hqpkkt_eigen_con
  *                       *t_steps is the step cap of that call, min(max_steps or 64, longest block) - not
  *                       HQPKKT_EIG_MAX_STEPS: 125 000 blocks at stride 128 would be 256 MB of zeros.  It serves the last
  *                       control of any kind: hqpkkt_q_eigen_control, hqpkkt_q_eigen_control_short,
- *                       hqpkkt_q_eigen_control_exact, hqpkkt_q_eigen_control_long or hqpkkt_q_eigen_control_blocked - behind
- *                       the last two *t_steps may exceed HQPKKT_EIG_MAX_STEPS (up to HQPKKT_QEIG_LONG_MAX = 512 and up to
- *                       HQPKKT_QEIG_BLOCKED_MAX = 2048).
+ *                       hqpkkt_q_eigen_control_exact, hqpkkt_q_eigen_control_long, hqpkkt_q_eigen_control_blocked or
+ *                       hqpkkt_q_eigen_control_wide - behind the last three *t_steps may exceed HQPKKT_EIG_MAX_STEPS (up to
+ *                       HQPKKT_QEIG_LONG_MAX = 512, up to HQPKKT_QEIG_BLOCKED_MAX = 2048 and up to HQPKKT_QEIG_WIDE_MAX = 8192).
  *   hqpkkt_q_eigen_control_short  the job of hqpkkt_q_eigen_control on the same blocks of hqpkkt_q_blocks(bsize), for a plan
  *                       whose blocks are ALL at most 64 long (the partition of a DOCP: 125 000 blocks of order 8 at
  *                       n = 10^6), in ONE launch, a wavefront per block - and lambda is computed as the reference
@@ -1021,10 +1021,40 @@ int hqpkkt_eigen_control_stage_hessians_wide(hqpkkt_t *h, const hqpkkt_eigen_con
  *                       environment variable HQPKKT_QEB_SLOTS caps `slots` (a test hook, read when the workspace is
  *                       sized); HQPKKT_QEB_NB = 32 selects the wider panel (the hook of the measurement in DESIGN.md;
  *                       other bits of T, the same contract).
- *                       Not built: storage of one triangle of the image alone; several workgroups per block; blocks
- *                       over 2048 (hqpkkt_q_eigen_control serves that plan); a numpy model of the blocked order.  (The
- *                       dense stage Hessians have an exact control of their own:
- *                       hqpkkt_eigen_control_stage_hessians_exact.)
+ *                       Not built: a numpy model of the blocked order.  Blocks over 2048, with one triangle of the image
+ *                       stored and several workgroups per block: hqpkkt_q_eigen_control_wide, next.  (The dense stage
+ *                       Hessians have an exact control of their own: hqpkkt_eigen_control_stage_hessians_exact.)
+ *   hqpkkt_q_eigen_control_wide  hqpkkt_q_eigen_control_blocked for a plan whose blocks are all at most
+ *                       HQPKKT_QEIG_WIDE_MAX = 8192 long (a DOCP whose diagonal blocks have order 5050, handed over as a
+ *                       plain sparse Q): the same arguments and floor rules, checks in the same order, report words,
+ *                       T layout and handle state; max_steps must be 0.  The blocks up to 2048 run the blocked entry's
+ *                       launches over lists without the longer ones: a plan with no block over 2048 gives the blocked
+ *                       entry's bits.  The blocks of 2049 .. 8192 are taken longest first in batches of `slots`, all slots
+ *                       of a batch in lockstep, every launch a bounded piece of work in the handle's stream - no polled
+ *                       words, no grid-wide barriers, no atomics.  A slot holds ONE lower triangle of the block's image
+ *                       as 64 x 64 tiles (I, J), J <= I, tile after tile, a tile's rows side by side, the upper half of a
+ *                       diagonal tile a mirror of its lower half - nT (nT + 1) / 2 tiles, nT = ceil(L / 64): 270 MB at 8192
+ *                       where both triangles take 537 MB -, the panels V and W, two vectors and 2 nT x LD doubles of
+ *                       column sums.  slots = min(such blocks, CUs, what 4 GiB and half the free memory hold), made by the first
+ *                       call that needs it and kept with the plan; HQPKKT_E_MEM where it cannot be had, the handle
+ *                       unchanged.  Per block: the gather of the entries with column <= row, g_b by the blocked entry's
+ *                       sums in its order, theta_b, the outcomes 0 and 6; then the same reduction, panels of NB = 16.
+ *                       p = A v / h reads every stored tile ONCE and uses it twice: the workgroup of tile row I sums
+ *                       A_IJ v_J over J <= I for its rows (a chain of fused multiply-adds per lane over ascending columns,
+ *                       a butterfly) and stores the 64 column sums of A_IJ' v_I (rows ascending) of every J < I; the
+ *                       column kernel adds to a row's part the column sums of the tile rows below it, I ascending, and
+ *                       divides by h.  Behind a whole panel A <- A - V W' - W V' by v_mfma_f64_16x16x4 on the stored
+ *                       tiles, one store per element, the mirror of a diagonal tile besides.  A block's bits depend on
+ *                       its length and its values alone - not on its slot, the batch, the grids, the mode or the other
+ *                       blocks -, equal from call to call; they are not the blocked entry's for the same block.  Then a
+ *                       wavefront per such block for the bracket, its work arrays in device memory, and
+ *                       hqpkkt_q_eigen_control's shift kernel over the block's rows.  HQPKKT_E_SIZES: a block longer than
+ *                       8192; nothing is launched, Q is untouched.  *t_steps of hqpkkt_q_eigen_report MAY REACH 8192.
+ *                       Test hooks: HQPKKT_QEW_SLOTS caps `slots` (read when the workspace is sized), HQPKKT_QEW_FROM
+ *                       (1 .. 2049, read per call, this entry alone) is the smallest block length that takes these
+ *                       kernels, HQPKKT_QEW_GROUPS the most workgroups per slot of the pass (no bits change).
+ *                       Not built: blocks over 8192; the control on the components of hqpkkt_q_sparse_bfgs_update; the
+ *                       dense stage entry on this layout.
  *   hqpkkt_lagrangian_gradient  Hqp_SqpSolver::grd_L: t_i = sum over row i of A' of a y, then over row i of C' of c z (one
  *                       accumulator per lane, fused multiply-adds, fixed order), out_i = fl(c_i - t_i), then fl(out_i -
  *                       minus_i) where minus is given (u = grad L+ - grad L from the second call).  One kernel.  y / z may
@@ -1081,6 +1111,8 @@ int hqpkkt_q_eigen_control_exact(hqpkkt_t *h, const hqpkkt_q_eigen_control_args 
 int hqpkkt_q_eigen_control_long(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_LONG_MAX long; max_steps must be 0 */
 #define HQPKKT_QEIG_BLOCKED_MAX 2048
 int hqpkkt_q_eigen_control_blocked(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_BLOCKED_MAX long; max_steps must be 0 */
+#define HQPKKT_QEIG_WIDE_MAX 8192
+int hqpkkt_q_eigen_control_wide(hqpkkt_t *h, const hqpkkt_q_eigen_control_args *e); /* every block <= HQPKKT_QEIG_WIDE_MAX long; max_steps must be 0 */
 int hqpkkt_q_eigen_report(hqpkkt_t *h, double *out /* HOST, cap_blocks * HQPKKT_EIG_REPORT */,
                           double *T /* HOST or NULL: cap_blocks * 2 * *t_steps */, long long cap_blocks,
                           long long *n_blocks, int *t_steps);

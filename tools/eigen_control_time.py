@@ -21,7 +21,13 @@ python tools/eigen_control_time.py --exact [out.txt]
 --wide: the wide control (hqpkkt_eigen_control_stage_hessians_wide) on 21 stages of order 5050 (packed and unpacked), 8 of
 order 8192, 201 of order 5050, x_0 fixed; and on 21 stages of order 2048 with HQPKKT_HW_FROM=1025 beside the exact and the
 Lanczos control.  EIGEN_TIME_ONLY=201x5050 (or 21x5050, 8x8192, 21x2048) runs that shape alone.  Appends to the file.
-python tools/eigen_control_time.py --wide [out.txt]"""
+python tools/eigen_control_time.py --wide [out.txt]
+
+--qwide: the sparse Q's wide control (hqpkkt_q_eigen_control_wide) on plain programs (IpSpBKP) whose Q is 21 dense blocks of
+order 5050, 8 of order 8192 - beside the dense stage entry (eigen_control_wide, unpacked) on the same block in the same run -
+and 21 of order 2048 with HQPKKT_QEW_FROM=1 beside hqpkkt_q_eigen_control_blocked.  EIGEN_TIME_ONLY as for --wide.  Every call
+by wall clock to a synchronisation and listed (the first makes the workspace).  Appends to the file.
+python tools/eigen_control_time.py --qwide [out.txt]"""
 import os
 import sys
 import time
@@ -150,6 +156,61 @@ def main_wide(out_path):
         f.write(text)
 
 
+QWIDE_SHAPES = ((21, 2048), (21, 5050), (8, 8192))
+
+
+def block_program(stages, v, U):
+    """a plain program whose Q is `stages` copies of the upper triangle of U (order v), rows ascending; two equalities, no bounds"""
+    i, j = np.triu_indices(v)
+    ptr = np.concatenate([[0], np.cumsum(np.tile(np.arange(v, 0, -1), stages))]).astype(np.int64)
+    idx = np.concatenate([(j + b * v).astype(np.int32) for b in range(stages)])
+    n = stages * v
+    A = problems._csr(np.array([0, 1]), np.array([0, n - 1]), np.ones(2), 2)
+    Cm = (np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
+    return problems.Program(n, 2, 0, (ptr, idx, np.tile(U[i, j], stages)), A, Cm, c=np.zeros(n), b=np.zeros(2), d=np.zeros(0))
+
+
+def main_qwide(out_path):
+    rng = np.random.default_rng(5)
+    empty = lambda rows: (np.zeros(rows + 1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
+    counts = lambda rep: {int(o): int((rep[:, 9] == o).sum()) for o in np.unique(rep[:, 9])}
+    ms = lambda t: " ".join(f"{x:.1f}" for x in t)
+    lines = [f"eigen_control_time --qwide: q_eigen_control_wide on a plain program of dense blocks, {torch.cuda.get_device_name(0)}; per call by wall "
+             f"clock to a synchronisation, every call listed (the first makes the workspace); ms"]
+    only = os.environ.get("EIGEN_TIME_ONLY")
+    for stages, v in QWIDE_SHAPES:
+        if only and only != f"{stages}x{v}":
+            continue
+        U = rng.standard_normal((v, v))
+        t0 = time.perf_counter()
+        M = ipmatrix.IpSpBKP(device_vectors=True)
+        M.init(block_program(stages, v, U))
+        row = f"{stages} blocks of order {v} (hand-over and analysis {time.perf_counter() - t0:.0f} s):"
+        if v <= 2048:
+            os.environ["HQPKKT_QEW_FROM"] = "1"
+        t = timed(lambda: M.q_eigen_control_wide(EPS, bsize=v), 4)
+        os.environ.pop("HQPKKT_QEW_FROM", None)
+        row += f"  q wide{' (HQPKKT_QEW_FROM=1)' if v <= 2048 else ''} {ms(t)}, outcomes {counts(M.q_eigen_report())}"
+        if v <= 2048:
+            t = timed(lambda: M.q_eigen_control_blocked(EPS, bsize=v), 4)
+            row += f";  q blocked {ms(t)}, outcomes {counts(M.q_eigen_report())}"
+        del M
+        if v > 2048:
+            Ud, Fd = torch.as_tensor(U).cuda(), torch.zeros((v, v), dtype=torch.float64, device="cuda")
+            fix = (np.arange(v + 1, dtype=np.int32), np.arange(v, dtype=np.int32), np.ones(v))
+            dq = problems.DenseDocp([v] * stages, [0] * (stages - 1), empty(stages * v), fix, empty(0), [Fd] * (stages - 1), v, 0, Qd=[Ud] * stages)
+            D = ipmatrix.IpLQDOCP(q_dense=True, q_packed=False, device_vectors=True)
+            D.init_dense(dq)
+            t = timed(lambda: D.eigen_control_wide(EPS), 3)
+            row += f";  stage wide, unpacked {ms(t)}, outcomes {counts(D.eigen_report_exact())}"
+            del D
+        lines.append(row)
+        print(row, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main(out_path):
     rng = np.random.default_rng(5)
     U = rng.standard_normal((NZ[0], NZ[0]))  # (the upper triangle is read: a symmetric matrix with eigenvalues within +-2 sqrt(order))
@@ -192,6 +253,10 @@ def main(out_path):
 
 
 if __name__ == "__main__":
+    if "--qwide" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--qwide"]
+        main_qwide(rest[0] if rest else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eigen_control_time.txt"))
+        sys.exit(0)
     if "--wide" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--wide"]
         main_wide(rest[0] if rest else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eigen_control_time.txt"))
